@@ -11,6 +11,9 @@ before the timed region.  Weak scaling: every rank samples its own batch.
     N > 1: either launched under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or plain
     `python bench.py --gpus N ...`: the parent then starts N fresh children of itself, one per GPU, with that environment (it has
     not touched the GPU at that point), relays rank 0's JSON line and exits with the worst child's code.
+    --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned as float32 .npy files: DIR/images_u8.npy
+    (the uint8 images, all ranks' after the all-gather, as 0..255) and DIR/x_final.npy (its own final sampler state).  Every input is
+    seeded, so two builds run with the same arguments can be compared array for array.
     --dry-run: stop before the first GPU call; every rank joins a gloo group, checks its environment and its batch shard, rank 0
     prints one JSON line (the launcher's CPU test, tests/test_host_logic.py).
 
@@ -74,6 +77,25 @@ WORKLOADS = {
                                      unet="CIFAR arch at 64x64 (attention at 16x16)"),
 }
 DEFAULT = "cifar10_cfm_euler50_b256"
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this many bytes in all; larger outputs are dumped as a fixed, seeded sample of images
+
+
+def dump_outputs(out_dir, arrays):
+    """Write arrays (name -> tensor whose dim 0 is the image) as out_dir/<name>.npy in float32.  If they exceed DUMP_BYTES together, every
+    array keeps the same rows: a sorted random subset drawn with a fixed seed (its indices are written as sample_rows.npy, float64)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    n = min(v.shape[0] for v in arrays.values())
+    row_bytes = sum(v[0].numel() * 4 for v in arrays.values())
+    keep = max(1, min(n, DUMP_BYTES // row_bytes))
+    rows = None
+    if keep < max(v.shape[0] for v in arrays.values()):
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        np.save(os.path.join(out_dir, "sample_rows.npy"), rows.numpy().astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), (v if rows is None else v[rows]).numpy())
 
 
 def cpu_baseline(sd, steps_sample=10, batch=32, nfe=50, reps=2):
@@ -236,9 +258,12 @@ def main():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "bf16x2", "fp16", "fp32"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-out", default="", help="write the per-op HIP-event profile of one forward to this JSON file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--dry-run", action="store_true", help="launcher check: process group + shard ranges over gloo, no GPU call")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch only: rendezvous port (default: a free one)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a.gpus, a.master_port))   # nothing above has touched the GPU (no HIP call, no library load)
@@ -276,9 +301,10 @@ def main():
     t_span = torch.linspace(0, 1, nfe + 1).tolist()
     tables = DDPM(nfe).host_tables() if wl["kind"] != "cfm" else None
     step_no = [0]
+    last_x = [None]
 
     def one_step():
-        x = x0.clone()
+        x = last_x[0] = x0.clone()
         if wl["kind"] == "cfm":
             _, _, u8 = eng.cfm_euler(x, t_span, cond=cond, want_u8=True)
         else:
@@ -303,6 +329,8 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
     assert out.shape[0] == B * world and out.dtype == torch.uint8
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"images_u8": out, "x_final": last_x[0]})
 
     # ---- box calibration, right behind the timed region (same thermal / clock state): a FROZEN MFMA-only launch (csrc/box_probe.hip) ----
     box = None
