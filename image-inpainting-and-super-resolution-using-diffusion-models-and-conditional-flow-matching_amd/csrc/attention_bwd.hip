@@ -334,6 +334,7 @@ int launch_bwd_ch(const AttnBwdArgs& a, int ch, hipStream_t s) {
 
 int attention_bwd_launch(const AttnBwdDesc& d, hipStream_t stream) {
   MI355_REQUIRE(d.qkv && d.a && d.da && d.dqkv && d.L && d.D, -1, "attention backward: null argument");
+  MI355_REQUIRE(d.dtype == DT_F32 || d.dtype == DT_BF16, -4, "attention backward: element type must be fp32 or bf16");
   AttnBwdArgs a;
   a.qkv = d.qkv; a.a = d.a; a.da = d.da; a.dqkv = d.dqkv; a.L = d.L; a.D = d.D;
   a.N = d.N; a.T = d.T; a.heads = d.heads; a.C = d.heads * d.ch;

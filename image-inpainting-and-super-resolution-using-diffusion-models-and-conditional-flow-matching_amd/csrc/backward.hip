@@ -215,6 +215,7 @@ __global__ void unpack_channels_kernel(const T* in, int N, int HW, int stride, i
 }  // namespace
 
 int unpack_channels_launch(int dtype, const void* in, int N, int HW, int stride, int c0, int count, float* out, hipStream_t s) {
+  MI355_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, -4, "unpack channels: element type must be fp32 or bf16");
   const size_t total = (size_t)N * count * HW;
   dim3 grid((unsigned)((total + 255) / 256));
   if (dtype == 0) hipLaunchKernelGGL(unpack_channels_kernel<float>, grid, dim3(256), 0, s, (const float*)in, N, HW, stride, c0, count, out);
@@ -224,6 +225,7 @@ int unpack_channels_launch(int dtype, const void* in, int N, int HW, int stride,
 }
 
 int gn_silu_bwd_launch(const GnBwdDesc& d, hipStream_t stream) {
+  MI355_REQUIRE(d.dtype == DT_F32 || d.dtype == DT_BF16, -4, "gn backward: element type must be fp32 or bf16");
   const int C = d.C0 + d.C1;
   const int V = d.dtype == 0 ? 4 : 8;
   MI355_REQUIRE(C % d.groups == 0 && d.C0 % V == 0 && d.C1 % V == 0 && d.du_stride % V == 0, -2, "gn backward: channel fragments");
@@ -244,6 +246,7 @@ int gn_silu_bwd_launch(const GnBwdDesc& d, hipStream_t stream) {
 
 int grad_gather_launch(int dtype, void* dst, const void* src, int N, int Hd, int Wd, int Cd, int Hs, int Ws, int cs, int coff, int mode,
                        int accumulate, float scale, hipStream_t s) {
+  MI355_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, -4, "grad gather: element type must be fp32 or bf16");
   const int V = dtype == 0 ? 4 : 8;
   MI355_REQUIRE(Cd % V == 0 && cs % V == 0 && coff % V == 0, -2, "grad gather: channel fragments");
   GaArgs a{dst, src, N, Hd, Wd, Cd, Hs, Ws, cs, coff, mode, accumulate, scale};

@@ -30,7 +30,7 @@ const mi355_debug_config& mi355_default_debug() {
 
 extern "C" {
 
-int mi355_version(void) { return 105; }
+int mi355_version(void) { return 106; }
 void mi355_debug_defaults(mi355_debug_config* c) {
   if (!c) return;
   std::memset(c, 0, sizeof(*c));
@@ -738,6 +738,34 @@ int mi355_qkv_attention(const float* qkv, float* out, int batch, int heads, int 
   AttnDesc a; a.dtype = dtype; a.qkv = qin; a.out = o; a.N = batch; a.T = length; a.heads = heads; a.ch = head_channels; a.new_order = new_order;
   if ((rc = attention_launch(a, s))) return rc;
   return unpack_nchw_launch(dtype, o, batch, length, C, out, s);
+}
+
+int mi355_qkv_attention_vjp(const float* qkv, const float* grad_out, float* grad_qkv, int batch, int heads, int head_channels, int length,
+                            int new_order, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(qkv && grad_out && grad_qkv && workspace, -1, "qkv_attention_vjp: null argument");
+  MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_BF16, -1, "qkv_attention_vjp: dtype must be MI355_F32 or MI355_BF16 (the attention backward has no other form)");
+  MI355_REQUIRE(batch > 0 && heads > 0 && head_channels > 0 && length > 0, -1, "qkv_attention_vjp: bad sizes");
+  hipStream_t s = S(stream);
+  const int esz = dtype == DT_F32 ? 4 : 2, C = heads * head_channels;
+  const size_t rows = (size_t)batch * length;
+  char* p = reinterpret_cast<char*>(workspace);
+  void* qin = p; p += al256(rows * 3 * C * esz);
+  void* din = p; p += al256(rows * C * esz);
+  void* a = p; p += al256(rows * C * esz);
+  void* dq = p; p += al256(rows * 3 * C * esz);
+  float* Ls = reinterpret_cast<float*>(p); p += al256((size_t)batch * heads * length * 4);
+  float* Ds = reinterpret_cast<float*>(p); p += al256((size_t)batch * heads * length * 4);
+  MI355_REQUIRE(p <= reinterpret_cast<char*>(workspace) + workspace_bytes, -2, "qkv_attention_vjp: workspace too small");
+  int rc;
+  if ((rc = pack_nhwc_launch(dtype, qkv, 3 * C, nullptr, 0, batch, length, 3 * C, qin, s))) return rc;
+  if ((rc = pack_nhwc_launch(dtype, grad_out, C, nullptr, 0, batch, length, C, din, s))) return rc;
+  // A from the forward kernel a differentiable plan runs (OP_ATTN), then the two backward kernels as unet_backward calls them
+  AttnDesc f; f.dtype = dtype; f.qkv = qin; f.out = a; f.N = batch; f.T = length; f.heads = heads; f.ch = head_channels; f.new_order = new_order;
+  if ((rc = attention_launch(f, s))) return rc;
+  AttnBwdDesc b; b.dtype = dtype; b.qkv = qin; b.a = a; b.da = din; b.dqkv = dq; b.L = Ls; b.D = Ds;
+  b.N = batch; b.T = length; b.heads = heads; b.ch = head_channels; b.new_order = new_order;
+  if ((rc = attention_bwd_launch(b, s))) return rc;
+  return unpack_nchw_launch(dtype, dq, batch, length, 3 * C, grad_qkv, s);
 }
 
 }  // extern "C"

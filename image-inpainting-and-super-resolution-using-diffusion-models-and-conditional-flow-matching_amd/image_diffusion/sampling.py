@@ -232,7 +232,9 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
         x_update = -gamma * alpha_i * (1 - alpha_i) * x_grad;  "before": xi += x_update (the predictor then runs on the moved xi),
         "after": the predictor runs on xi and x_update is added to its result.
     The losses are per sample and the network has no cross-sample coupling, so vmap(grad) is ONE batched backward pass:
-    seed kernel (clip / loss / predict_start chain rule) -> UNetEngine.vjp -> update kernel."""
+    seed kernel (clip / loss / predict_start chain rule) -> UNetEngine.vjp -> update kernel.  The guided steps' forward and VJP run on the
+    differentiable plan, which is bf16 when the model's precision is 'fp16' (use_fp16=True) or 'bf16x2' (the backward exists in fp32 and bf16
+    only, UNetModel.engine); the unguided steps and correctors keep the model's precision."""
     net = getattr(eps_model, "_mi355_network", None)
     if net is None or getattr(eps_model, "_mi355_Ns", None) != ddpm.Ns or not hasattr(net, "engine"):
         raise NotImplementedError(

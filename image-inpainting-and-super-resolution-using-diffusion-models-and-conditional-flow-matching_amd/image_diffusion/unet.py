@@ -204,7 +204,9 @@ class UNetModel(nn.Module):
 
     def engine(self, device=None, differentiable: bool = False) -> UNetEngine:
         """The packed HIP engine for the CURRENT parameter values (re-packed when any parameter changed).
-        differentiable=True: the plan that keeps what `UNetEngine.vjp` needs (its own handle and weight copy)."""
+        differentiable=True: the plan that keeps what `UNetEngine.vjp` needs (its own handle and weight copy).  The backward pass exists in
+        fp32 and bf16 only, so for precision 'fp16' (use_fp16=True) or 'bf16x2' the differentiable plan is built in bf16, the nearest precision
+        that has one; the non-differentiable engine keeps the model's precision."""
         params = list(self.parameters())
         device = torch.device(device) if device is not None else params[0].device
         if device.type != "cuda":
@@ -216,7 +218,8 @@ class UNetModel(nn.Module):
                tuple(p.data_ptr() for p in params))
         if differentiable:
             if self._dengine is None or key != self._dengine_key:
-                self._dengine = UNetEngine(self._cfg_kwargs(), self.state_dict(), device, self.precision, differentiable=True,
+                prec = "bf16" if self.precision in ("fp16", "f16", "bf16x2") else self.precision
+                self._dengine = UNetEngine(self._cfg_kwargs(), self.state_dict(), device, prec, differentiable=True,
                                            debug=getattr(self, "debug", None))
                 self._dengine_key = key
             return self._dengine

@@ -155,6 +155,7 @@ SIGNATURES = {
     "mi355_conv2d_ex": (_I, [_VP, _VP, _I, _FP, _FP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _I, C.POINTER(DebugConfigC), _VP,
                              _I64, _VP, C.POINTER(ConvExtrasC)]),
     "mi355_qkv_attention": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I64, _VP]),
+    "mi355_qkv_attention_vjp": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I64, _VP]),
 }
 
 _lock = threading.Lock()

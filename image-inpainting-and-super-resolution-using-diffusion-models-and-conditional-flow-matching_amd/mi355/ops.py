@@ -285,5 +285,22 @@ class Ops:
                                     C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_qkv_attention")
         return out
 
+    def qkv_attention_vjp(self, qkv, grad_out, heads, new_order=False, dtype=_lib.MI355_F32, ws_fill=None):
+        """(d qkv_attention / d qkv)^T grad_out through the HIP attention backward (mi355_qkv_attention_vjp): qkv [B, 3 H ch, T],
+        grad_out [B, H ch, T] -> grad_qkv [B, 3 H ch, T].  ws_fill: a byte value the workspace is filled with first (tests: 0xFF makes
+        every packed intermediate NaN until a kernel writes it)."""
+        B, width, T = qkv.shape
+        ch = width // (3 * heads)
+        if tuple(grad_out.shape) != (B, heads * ch, T):
+            raise ValueError(f"grad_out must be {(B, heads * ch, T)}, got {tuple(grad_out.shape)}")
+        gq = torch.empty_like(qkv)
+        L = _lib.lib()
+        wsb = L.mi355_op_workspace_bytes(B, width, T)
+        ws = torch.empty(wsb, device=qkv.device, dtype=torch.uint8) if ws_fill is None else \
+            torch.full((wsb,), int(ws_fill), device=qkv.device, dtype=torch.uint8)
+        check(L.mi355_qkv_attention_vjp(_req(qkv, "qkv"), _req(grad_out, "grad_out"), _req(gq, "grad_qkv"), B, heads, ch, T, int(new_order),
+                                        dtype, C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_qkv_attention_vjp")
+        return gq
+
 
 default_ops = Ops()

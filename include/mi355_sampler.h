@@ -42,7 +42,8 @@ extern "C" {
                      * precision mode (UNetModel(use_fp16=True) runs its torso in float16, AD/image_diffusion/unet.py:559-563): bf16's speed, three more
                      * mantissa bits on every stored activation and weight; values beyond +-65504 overflow to inf as they do in the reference */
 
-/* ABI version = 100 * major + minor.  The minor number counts additive changes; 105 (round 5, last): mi355_debug_config::sampler_graph (carved out of the
+/* ABI version = 100 * major + minor.  The minor number counts additive changes; 106: mi355_qkv_attention_vjp (the attention backward as a test
+ * op).  105 (round 5, last): mi355_debug_config::sampler_graph (carved out of the
  * reserved tail), mi355_box_probe_hbm.  104 (round 5, later): mi355_conv2d_ex (the small-level conv's fused forms as a
  * test op), gn_epilogue bit 2, conv_small bit 3, conv_edge bits 2-3, conv_pp bit 5, mi355_op_profile::tile_m = -1 for plan ops that launched nothing.
  * 103 (round 5): conv_pp became a bit mask (bits 2, 3, 4: the
@@ -401,6 +402,12 @@ int mi355_conv2d_ex(const float* x, const float* x1, int cin1, const float* w_ho
 /* QKVAttentionLegacy / QKVAttention (unet.py:424-487): qkv [B, 3*H*ch, T] -> out [B, H*ch, T] */
 int mi355_qkv_attention(const float* qkv, float* out, int batch, int heads, int head_channels, int length, int new_order,
                         int dtype, void* workspace, int64_t workspace_bytes, void* stream);
+/* Its data gradient, for op-level parity tests of the backward kernels (ABI 106): grad_qkv [B, 3*H*ch, T] = (d out / d qkv)^T grad_out, grad_out
+ * [B, H*ch, T].  Runs the forward kernel of a differentiable plan for `out`, then csrc/attention_bwd.hip (the L / D statistics are scratch of
+ * the workspace).  dtype MI355_F32 or MI355_BF16 only (the backward's two element types); head_channels 32, 64, 96, 128, 192 or 256.
+ * workspace: mi355_op_workspace_bytes(batch, 3 * H * ch, T) suffices. */
+int mi355_qkv_attention_vjp(const float* qkv, const float* grad_out, float* grad_qkv, int batch, int heads, int head_channels, int length,
+                            int new_order, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
