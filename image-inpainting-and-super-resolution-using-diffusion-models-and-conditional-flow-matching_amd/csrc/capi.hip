@@ -590,7 +590,6 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
   ExScratch xs;
   void* act_dev[2] = {nullptr, nullptr};
   std::vector<char> packed_f; std::vector<float> bias_f;
-  int act_done = 0;
   if (ex) {
     ex->act_done = 0; ex->skip_done = 0;
     MI355_REQUIRE(nhwc && !pool, -4, "conv2d_ex: extras need an NHWC output and no pooling");
@@ -613,8 +612,6 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
       MI355_CHECK_HIP(hipMemcpyAsync(bdev, bias_f.data(), (size_t)cout * 4, hipMemcpyHostToDevice, s));
       d.w = wf; d.bias = bdev;
       d.skip_src0 = k0; d.skip_C0 = ex->skip_c0; d.skip_src1 = k1; d.skip_C1 = ex->skip_c1;
-      if (conv_fused_skip_ok(d) != 0) { mi355_set_error("conv2d_ex: this launch cannot carry the fused skip conv (shape, batch or knobs)"); return MI355_ERR_UNSUPPORTED; }
-      ex->skip_done = 1;
     }
     for (int k = 0; k < 2; ++k) {
       if (!ex->act_out[k]) continue;
@@ -635,18 +632,24 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
       d.act2_silu = ex->act_silu[1]; d.act2_stride = ex->act_ctotal[1]; d.act2_coff = ex->act_coff[1]; d.act2_cpg = ex->act_ctotal[1] / 32;
     }
   }
-  if ((rc = conv_launch(d, s, nullptr, ex ? &act_done : nullptr))) return rc;
+  ConvRoute route;
+  if ((rc = conv_route(d, &route))) {
+    if (d.skip_src0) { mi355_set_error("conv2d_ex: this launch cannot carry the fused skip conv (shape, batch or knobs)"); return MI355_ERR_UNSUPPORTED; }
+    return rc;
+  }
+  if ((rc = conv_launch(d, route, s))) return rc;
   if (ex) {
-    ex->act_done = act_done;
+    ex->skip_done = route.skip; ex->act_done = route.act_done;
     for (int k = 0; k < 2; ++k)
-      if (act_dev[k] && (act_done & (1 << k)) && (rc = unpack_nchw_launch(dtype, act_dev[k], batch, g.Ho * g.Wo, ex->act_ctotal[k], ex->act_out[k], s))) return rc;
+      if (act_dev[k] && (route.act_done & (1 << k)) && (rc = unpack_nchw_launch(dtype, act_dev[k], batch, g.Ho * g.Wo, ex->act_ctotal[k], ex->act_out[k], s))) return rc;
   }
   if (K.conv_time_reps > 0) {   // diagnostic: average duration of the conv launch alone
     const int reps = K.conv_time_reps;
     hipEvent_t e0, e1;
     MI355_CHECK_HIP(hipEventCreate(&e0)); MI355_CHECK_HIP(hipEventCreate(&e1));
     MI355_CHECK_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < reps; ++i) if ((rc = conv_launch(d, s))) return rc;
+    ConvRoute plain = route; plain.act_done = 0;   // the same kernel without the fused GroupNorm sites
+    for (int i = 0; i < reps; ++i) if ((rc = conv_launch(d, plain, s))) return rc;
     MI355_CHECK_HIP(hipEventRecord(e1, s));
     MI355_CHECK_HIP(hipEventSynchronize(e1));
     float ms = 0.f;

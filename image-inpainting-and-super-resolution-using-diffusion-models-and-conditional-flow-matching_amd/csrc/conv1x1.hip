@@ -273,13 +273,8 @@ int launch1(const K1Args& a, dim3 grid, size_t lds, hipStream_t s) {
 
 }  // namespace
 
-// Returns 1 if this conv is not eligible (caller falls back to the generic implicit-GEMM kernel), 0 on launch, <0 on error.
-int conv1x1_try_launch(const ConvDesc& d, hipStream_t stream, int* gn_slots_used) {
-  if (d.ks != 1 || d.mode != CONV_UNIT || d.out_mode != OUT_NHWC || d.wsplit) return 1;   // (hi / lo split weights: the ping-pong / generic kernels)
-  {   // prologue-free, 256-channel output tiles, whole 256-pixel tiles per image: the streaming ping-pong kernel (conv_pp1.inc.h)
-    const int r = conv1x1_pp_try_launch(d, stream, gn_slots_used);
-    if (r <= 0) return r;
-  }
+int conv1x1_route(const ConvDesc& d, ConvRoute* r) {
+  if (d.ks != 1 || d.mode != CONV_UNIT || d.out_mode != OUT_NHWC) return 1;
   if (d.Cout % 128 != 0 || (d.res && d.res_mode != RES_SAME)) return 1;
   const int CH = d.dtype == 0 ? 16 : 32, esz = d.dtype == 0 ? 4 : 2;
   const int Cin = d.C0 + d.C1, nchunks = Cin / CH;
@@ -299,50 +294,55 @@ int conv1x1_try_launch(const ConvDesc& d, hipStream_t stream, int* gn_slots_used
   if ((size_t)nchunks * BM * 64 + wl > 160 * 1024) return 1;
   // A stationary tile only pays when it is reused by several output-channel tiles or when two workgroups still fit a CU
   if ((size_t)nchunks * BM * 64 + wl > 80 * 1024 && d.Cout / 128 < 3) return 1;
+  const int lw = ilog2_ceil(d.Ws);
+  r->lvw = (1 << lw) > BM ? ilog2_ceil(BM) : lw;
+  const int VW = 1 << r->lvw, thfull = BM / VW;
+  if (d.Hs >= thfull) { r->lth = ilog2_ceil(thfull); r->G = 1; }
+  else { r->lth = ilog2_ceil(d.Hs); r->G = thfull >> r->lth; }
+  r->tiles_x = (d.Ws + VW - 1) / VW;
+  r->tiles_y = (d.Hs + (1 << r->lth) - 1) >> r->lth;
+  const int mt = (d.N + r->G - 1) / r->G * r->tiles_x * r->tiles_y, slots = 2 * r->tiles_x * r->tiles_y;
+  const int ntiles = d.Cout / 128;
+  // all output-channel tiles in one workgroup unless that leaves CUs idle
+  int ntn = ntiles;
+  while (ntn > 1 && (long)mt * ((ntiles + ntn - 1) / ntn) < 512) ntn = (ntn + 1) / 2;
+  const size_t b0 = (size_t)d.N * d.Hs * d.Ws * d.C0 * esz, b1 = (size_t)d.N * d.Hs * d.Ws * d.C1 * esz;
+  const size_t wb = conv_packed_weight_bytes(d.dtype, d.Cout, Cin, 1);
+  MI355_REQUIRE(b0 < 0xFFFF0000ull && b1 < 0xFFFF0000ull && wb < 0xFFFF0000ull, -4,
+                "conv1x1: a source tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
+  const size_t ob = (size_t)d.N * d.Hs * d.Ws * d.Cout * esz;
+  MI355_REQUIRE(ob < 0xFFFF0000ull, -4, "conv1x1: output tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
+  r->kernel = CONV_K_1X1; r->BM = BM; r->GC = GC; r->ntn = ntn; r->n_mt = mt; r->n_nt = (ntiles + ntn - 1) / ntn;
+  r->lds = (size_t)nchunks * BM * 64 + wl;
+  r->gn_slots = d.gn_stats && r->G == 1 && slots <= d.gn_slots_cap ? slots : 0;
+  return 0;
+}
+
+int conv1x1_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream) {
+  const int CH = d.dtype == 0 ? 16 : 32, esz = d.dtype == 0 ? 4 : 2;
+  const int Cin = d.C0 + d.C1;
   K1Args a;
-  a.src0 = d.src0; a.src1 = d.src1; a.C0 = d.C0; a.C1 = d.C1; a.Cin = Cin; a.nchunks = nchunks;
+  a.src0 = d.src0; a.src1 = d.src1; a.C0 = d.C0; a.C1 = d.C1; a.Cin = Cin; a.nchunks = Cin / CH;
   a.N = d.N; a.H = d.Hs; a.W = d.Ws;
   a.pro_a = d.pro_a; a.pro_b = d.pro_b; a.pro_silu = d.pro_silu;
   a.w = d.w; a.bias = d.bias; a.Cout = d.Cout;
   a.emb = d.emb; a.emb_stride = d.emb_stride;
   a.res = d.res_mode == RES_NONE ? nullptr : d.res;
   a.out = d.out;
-  a.gn_stats = nullptr; a.gn_slots = 0;
-  const int lw = ilog2_ceil(d.Ws);
-  a.lvw = (1 << lw) > BM ? ilog2_ceil(BM) : lw;
-  const int VW = 1 << a.lvw, thfull = BM / VW;
-  if (d.Hs >= thfull) { a.lth = ilog2_ceil(thfull); a.G = 1; }
-  else { a.lth = ilog2_ceil(d.Hs); a.G = thfull >> a.lth; }
-  a.tiles_x = (d.Ws + VW - 1) / VW;
-  a.tiles_y = (d.Hs + (1 << a.lth) - 1) >> a.lth;
-  const int groups = (d.N + a.G - 1) / a.G;
-  const int mt = groups * a.tiles_x * a.tiles_y;
-  if (d.gn_stats && a.G == 1 && 2 * a.tiles_x * a.tiles_y <= d.gn_slots_cap) { a.gn_stats = d.gn_stats; a.gn_slots = 2 * a.tiles_x * a.tiles_y; }
-  const int ntiles = d.Cout / 128;
-  // all output-channel tiles in one workgroup unless that leaves CUs idle
-  int ntn = ntiles;
-  while (ntn > 1 && (long)mt * ((ntiles + ntn - 1) / ntn) < 512) ntn = (ntn + 1) / 2;
-  a.ntn = ntn;
-  const size_t b0 = (size_t)d.N * d.Hs * d.Ws * d.C0 * esz, b1 = (size_t)d.N * d.Hs * d.Ws * d.C1 * esz;
-  const size_t wb = conv_packed_weight_bytes(d.dtype, d.Cout, Cin, 1);
-  MI355_REQUIRE(b0 < 0xFFFF0000ull && b1 < 0xFFFF0000ull && wb < 0xFFFF0000ull, -4,
-                "conv1x1: a source tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-  a.bytes0 = (uint32_t)b0; a.bytes1 = d.src1 ? (uint32_t)b1 : 0u; a.wbytes = (uint32_t)wb;
-  const size_t ob = (size_t)d.N * d.Hs * d.Ws * d.Cout * esz;
-  MI355_REQUIRE(ob < 0xFFFF0000ull, -4, "conv1x1: output tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-  a.obytes = (uint32_t)ob;
-  dim3 grid(mt, (ntiles + ntn - 1) / ntn);
-  const size_t lds = (size_t)nchunks * BM * 64 + wl;
-  int rc;
-  rc = dispatch_dtype(d.dtype, [&](auto t) {
+  a.gn_stats = r.gn_slots ? d.gn_stats : nullptr; a.gn_slots = r.gn_slots;
+  a.lvw = r.lvw; a.lth = r.lth; a.G = r.G; a.tiles_x = r.tiles_x; a.tiles_y = r.tiles_y; a.ntn = r.ntn;
+  a.bytes0 = (uint32_t)((size_t)d.N * d.Hs * d.Ws * d.C0 * esz); a.bytes1 = d.src1 ? (uint32_t)((size_t)d.N * d.Hs * d.Ws * d.C1 * esz) : 0u;
+  a.wbytes = (uint32_t)conv_packed_weight_bytes(d.dtype, d.Cout, Cin, 1);
+  a.obytes = (uint32_t)((size_t)d.N * d.Hs * d.Ws * d.Cout * esz);
+  const dim3 grid(r.n_mt, r.n_nt);
+  const int rc = dispatch_dtype(d.dtype, [&](auto t) {
     using T = decltype(t);
-    if (BM == 128 && GC == 3) return launch1<T, 128, 3>(a, grid, lds, stream);
-    if (BM == 128) return launch1<T, 128, 1>(a, grid, lds, stream);
-    if (GC == 1) return launch1<T, 64, 1>(a, grid, lds, stream);
-    return launch1<T, 64, 3>(a, grid, lds, stream);
+    if (r.BM == 128 && r.GC == 3) return launch1<T, 128, 3>(a, grid, r.lds, stream);
+    if (r.BM == 128) return launch1<T, 128, 1>(a, grid, r.lds, stream);
+    if (r.GC == 1) return launch1<T, 64, 1>(a, grid, r.lds, stream);
+    return launch1<T, 64, 3>(a, grid, r.lds, stream);
   });
   if (rc) return rc;
   MI355_CHECK_HIP(hipGetLastError());
-  if (gn_slots_used) *gn_slots_used = a.gn_slots;
   return 0;
 }

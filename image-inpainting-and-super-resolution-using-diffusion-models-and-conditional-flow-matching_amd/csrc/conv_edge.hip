@@ -339,72 +339,64 @@ __global__ void __launch_bounds__(256, 4) conv3x3_in_kernel(InArgs p) {
 
 }  // namespace
 
-// 0 = launched, 1 = not eligible (the caller goes on to the generic kernel), < 0 = error.  Switch: mi355_debug_config::conv_edge.
-int conv_out_try_launch(const ConvDesc& d, hipStream_t stream) {
+// The last conv (see conv3x3_out_kernel).  Switch: mi355_debug_config::conv_edge bit 0 (bit 3: the Euler update in the epilogue).
+int conv_out_route(const ConvDesc& d, ConvRoute* r) {
   const mi355_debug_config& K = d.knobs ? *d.knobs : mi355_default_debug();
-  if (!(K.conv_edge & 1) || d.wsplit) return 1;   // (hi / lo split weights: the generic kernel)
+  if (!(K.conv_edge & 1)) return 1;
   if (d.ks != 3 || d.mode != CONV_UNIT || d.out_mode != OUT_NCHW_F32 || d.src1 || d.res || d.emb || !d.pro_a || d.Cout > 4 || d.Cout < 1) return 1;
   const int V = d.dtype == 0 ? 4 : 8, esz = d.dtype == 0 ? 4 : 2;
   const int FPP = d.C0 / V;
   if (d.C0 % (16 * V) != 0 || FPP > 64 || (64 % FPP) != 0 || conv_tile_n(d.Cout) != 32) return 1;   // whole 16-fragment swizzle groups per pixel, whole pixels per 1-KB DMA piece
   const size_t lds = (size_t)OP_N * d.C0 * esz + (size_t)(d.C0 / (d.dtype == 0 ? 16 : 32)) * 9 * (d.Cout <= 3 ? 3 : 4) * 64;
   if (lds > 160 * 1024) return 1;
+  const size_t bs = (size_t)d.N * d.Hs * d.Ws * d.C0 * esz;
+  MI355_REQUIRE(bs < 0xFFFF0000ull, -4, "conv (out): the source tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
+  r->kernel = CONV_K_OUT; r->form = FPP == 16; r->lds = lds; r->axpy = (K.conv_edge & 8) && d.axpy_x;
+  return 0;
+}
+int conv_out_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream) {
+  const int esz = d.dtype == 0 ? 4 : 2;
   OutArgs a;
   a.src = d.src0; a.C = d.C0; a.N = d.N; a.H = d.Hs; a.W = d.Ws;
   a.pro_a = d.pro_a; a.pro_b = d.pro_b; a.pro_silu = d.pro_silu;
   a.w = d.w; a.bias = d.bias; a.Cout = d.Cout; a.out = reinterpret_cast<float*>(d.out);
-  a.axpy_x = (K.conv_edge & 8) ? d.axpy_x : nullptr; a.axpy_scale = d.axpy_scale;
-  const size_t bs = (size_t)d.N * d.Hs * d.Ws * d.C0 * esz, wb = conv_packed_weight_bytes(d.dtype, d.Cout, d.C0, 3);
-  MI355_REQUIRE(bs < 0xFFFF0000ull, -4, "conv (out): the source tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-  a.bytes_src = (uint32_t)bs; a.wbytes = (uint32_t)wb;
+  a.axpy_x = r.axpy ? d.axpy_x : nullptr; a.axpy_scale = d.axpy_scale;
+  a.bytes_src = (uint32_t)((size_t)d.N * d.Hs * d.Ws * d.C0 * esz); a.wbytes = (uint32_t)conv_packed_weight_bytes(d.dtype, d.Cout, d.C0, 3);
   a.tiles_x = (d.Ws + OT_W - 1) / OT_W; a.tiles_y = (d.Hs + OT_H - 1) / OT_H; a.ntiles = d.N * a.tiles_x * a.tiles_y;
-  const bool fixed = FPP == 16;
   auto go = [&](auto kern) -> int {
-    if (int r = mi355_allow_big_lds(kern, "conv (out)")) return r;
-    hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(256), lds, stream, a);
+    if (int rc = mi355_allow_big_lds(kern, "conv (out)")) return rc;
+    hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(256), r.lds, stream, a);
     return 0;
   };
-  int rc;
-  rc = dispatch_dtype(d.dtype, [&](auto t) { using T = decltype(t); return fixed ? go(conv3x3_out_kernel<T, true>) : go(conv3x3_out_kernel<T, false>); });
+  const int rc = dispatch_dtype(d.dtype, [&](auto t) { using T = decltype(t); return r.form ? go(conv3x3_out_kernel<T, true>) : go(conv3x3_out_kernel<T, false>); });
   if (rc) return rc;
   MI355_CHECK_HIP(hipGetLastError());
-  if (a.axpy_x && d.axpy_done) *d.axpy_done = 1;
   return 0;
 }
 
-// The first conv (see conv3x3_in_kernel).  0 = launched, 1 = not eligible, < 0 = error.  Switch: mi355_debug_config::conv_edge bit 1.
-static bool conv_in_eligible(const ConvDesc& d);
-int conv_in_reads_nchw(const ConvDesc& d) {
+// The first conv (see conv3x3_in_kernel).  Switch: mi355_debug_config::conv_edge bit 1 (bit 2: the caller's fp32 NCHW tensors read directly).
+int conv_in_route(const ConvDesc& d, ConvRoute* r) {
   const mi355_debug_config& K = d.knobs ? *d.knobs : mi355_default_debug();
-  return (d.nchw0 && (K.conv_edge & 4) && d.nchw_c0 >= 1 && d.nchw_c0 + d.nchw_c1 == d.cin_real && (d.nchw_c1 == 0 || d.nchw1) && conv_in_eligible(d)) ? 0 : 1;
-}
-static bool conv_in_eligible(const ConvDesc& d) {
-  const mi355_debug_config& K = d.knobs ? *d.knobs : mi355_default_debug();
-  if (!(K.conv_edge & 2) || d.wsplit) return false;
-  if (d.dtype == DT_F32 || d.ks != 3 || d.mode != CONV_UNIT || d.out_mode != OUT_NHWC || d.src1 || d.res || d.emb || d.pro_a || d.act_out) return false;
-  if (d.cin_real < 1 || d.cin_real > 8 || d.C0 != 32 || d.Cout != 128 || conv_tile_n(d.Cout) != 128 || !d.bias) return false;
-  if (d.Hs % 16 != 0 || d.Ws % 16 != 0) return false;
-  return true;
-}
-int conv_in_try_launch(const ConvDesc& d, hipStream_t stream, int* gn_slots_used) {
-  const mi355_debug_config& K = d.knobs ? *d.knobs : mi355_default_debug();
-  if (d.nchw0) MI355_REQUIRE(conv_in_reads_nchw(d) == 0, -5, "conv (in): this launch cannot read the fp32 NCHW input itself (ask conv_in_reads_nchw first)");
-  if (!(K.conv_edge & 2) || d.wsplit) return 1;
+  if (!(K.conv_edge & 2)) return 1;
   if (d.dtype == DT_F32 || d.ks != 3 || d.mode != CONV_UNIT || d.out_mode != OUT_NHWC || d.src1 || d.res || d.emb || d.pro_a || d.act_out) return 1;
   if (d.cin_real < 1 || d.cin_real > 8 || d.C0 != 32 || d.Cout != 128 || conv_tile_n(d.Cout) != 128 || !d.bias) return 1;
   if (d.Hs % 16 != 0 || d.Ws % 16 != 0) return 1;
+  r->kernel = CONV_K_IN;
+  const int slots = (d.Ws / 16) * (d.Hs / 16) * 4;
+  r->gn_slots = d.gn_stats && slots <= d.gn_slots_cap ? slots : 0;
+  r->reads_nchw = d.nchw0 && (K.conv_edge & 4) && d.nchw_c0 >= 1 && d.nchw_c0 + d.nchw_c1 == d.cin_real && (d.nchw_c1 == 0 || d.nchw1);
+  return 0;
+}
+int conv_in_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream) {
   InArgs a;
   a.src = d.src0; a.w = d.w; a.bias = d.bias; a.out = d.out;
-  a.x0 = d.nchw0; a.x1 = d.nchw_c1 ? d.nchw1 : nullptr; a.c0 = d.nchw_c0; a.c1 = d.nchw1 ? d.nchw_c1 : 0;
+  a.x0 = r.reads_nchw ? d.nchw0 : nullptr; a.x1 = r.reads_nchw && d.nchw_c1 ? d.nchw1 : nullptr; a.c0 = r.reads_nchw ? d.nchw_c0 : 0; a.c1 = r.reads_nchw && d.nchw1 ? d.nchw_c1 : 0;
   a.N = d.N; a.H = d.Hs; a.W = d.Ws; a.tiles_x = d.Ws / 16; a.tiles_y = d.Hs / 16;
-  const int slots = a.tiles_x * a.tiles_y * 4;
-  a.gn_stats = nullptr; a.gn_slots = 0;
-  if (d.gn_stats && slots <= d.gn_slots_cap) { a.gn_stats = d.gn_stats; a.gn_slots = slots; }
+  a.gn_stats = r.gn_slots ? d.gn_stats : nullptr; a.gn_slots = r.gn_slots;
   const dim3 gr(d.N * a.tiles_x * a.tiles_y);
   if (d.dtype == DT_F16) { if (a.gn_stats) hipLaunchKernelGGL((conv3x3_in_kernel<true, f16>), gr, dim3(256), 0, stream, a); else hipLaunchKernelGGL((conv3x3_in_kernel<false, f16>), gr, dim3(256), 0, stream, a); }
   else if (a.gn_stats) hipLaunchKernelGGL((conv3x3_in_kernel<true, bf16>), gr, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL((conv3x3_in_kernel<false, bf16>), gr, dim3(256), 0, stream, a);
   MI355_CHECK_HIP(hipGetLastError());
-  if (gn_slots_used) *gn_slots_used = a.gn_slots;
   return 0;
 }

@@ -653,9 +653,46 @@ int compute_geo(const ConvDesc& d, Geo& g) {
   return 0;
 }
 
-}  // namespace
+// The plain kernel's arguments (the ping-pong, warp-specialised and small-level launches start from them): 0, or < 0 past the 32-bit offset limits
+int igemm_args(const ConvDesc& d, const Geo& g, ConvKArgs& a) {
+  const int CH = d.dtype == 0 ? 16 : 32, Cin = d.C0 + d.C1;
+  const bool fskip = d.skip_src0 != nullptr;
+  a.src0 = d.src0; a.src1 = d.src1; a.C0 = d.C0; a.C1 = d.C1; a.Cin = Cin; a.nreal = Cin / CH; a.nchunks = a.nreal * (d.wsplit ? 2 : 1);
+  a.N = d.N; a.Hs = d.Hs; a.Ws = d.Ws; a.Hc = g.Hc; a.Wc = g.Wc; a.Ho = g.Ho; a.Wo = g.Wo;
+  a.mode = d.mode; a.pad = g.pad; a.stride = g.stride;
+  a.pro_a = d.pro_a; a.pro_b = d.pro_b; a.pro_silu = d.pro_silu;
+  a.w = d.w; a.bias = d.bias; a.Cout = d.Cout; a.bn_pack = g.bn_pack;
+  const size_t esz = d.dtype == 0 ? 4 : 2;
+  const size_t b0 = (size_t)d.N * d.Hs * d.Ws * d.C0 * esz, b1 = (size_t)d.N * d.Hs * d.Ws * d.C1 * esz;
+  const size_t wb = conv_packed_weight_bytes(d.dtype, d.Cout, Cin, d.ks, d.wsplit) + (fskip ? conv_packed_weight_bytes(d.dtype, d.Cout, d.skip_C0 + d.skip_C1, 1, 0) : 0);
+  MI355_REQUIRE(b0 < 0xFFFF0000ull && b1 < 0xFFFF0000ull && wb < 0xFFFF0000ull, -4,
+                "conv: a source tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
+  a.bytes0 = (uint32_t)b0; a.bytes1 = d.src1 ? (uint32_t)b1 : 0u; a.wbytes = (uint32_t)wb;
+  a.Hr = d.res_mode == RES_UP2 ? g.Ho / 2 : g.Ho;
+  a.Wr = d.res_mode == RES_UP2 ? g.Wo / 2 : g.Wo;
+  const size_t ob = (size_t)d.N * g.Ho * g.Wo * d.Cout * esz, rb = (size_t)d.N * a.Hr * a.Wr * d.Cout * esz;
+  MI355_REQUIRE(ob < 0xFFFF0000ull && rb < 0xFFFF0000ull, -4, "conv: output tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
+  a.obytes = (uint32_t)ob; a.rbytes = d.res ? (uint32_t)rb : 0u;
+  a.dbg = reinterpret_cast<unsigned long long*>(d.dbg);
+  const mi355_debug_config& K = d.knobs ? *d.knobs : mi355_default_debug();
+  a.stagger = K.conv_stagger; a.ablate = K.conv_ablate;
+  a.err = d.err; a.spin_limit = K.conv_spin_limit > 0 ? K.conv_spin_limit : 1;
+  a.emb = d.emb; a.emb_stride = d.emb_stride;
+  a.res = d.res; a.res_mode = d.res ? d.res_mode : RES_NONE;
+  a.out = d.out; a.out_mode = d.out_mode;
+  a.gn_stats = nullptr; a.gn_slots = 0;
+  a.lvw = g.lvw; a.lth = g.lth; a.G = g.G; a.PW = g.PW; a.PH = g.PH; a.NP = g.NP;
+  a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
+  if (fskip) {
+    const size_t k0 = (size_t)d.N * g.Ho * g.Wo * d.skip_C0 * esz, k1 = (size_t)d.N * g.Ho * g.Wo * d.skip_C1 * esz;
+    MI355_REQUIRE(k0 < 0xFFFF0000ull && k1 < 0xFFFF0000ull, -4, "conv: a source tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
+    a.sk0 = d.skip_src0; a.sk1 = d.skip_src1; a.SC0 = d.skip_C0; a.SC1 = d.skip_src1 ? d.skip_C1 : 0;
+    a.skbytes0 = (uint32_t)k0; a.skbytes1 = d.skip_src1 ? (uint32_t)k1 : 0u;
+  }
+  return 0;
+}
 
-int conv1x1_pp_try_launch(const ConvDesc& d, hipStream_t stream, int* gn_slots_used) { return pp1_try_launch(d, stream, gn_slots_used); }
+}  // namespace
 
 int conv_tile_n(int Cout) {
   if (Cout % 128 == 0) return 128;
@@ -736,44 +773,19 @@ void conv_pack_weights_dgrad(int dtype, const float* w, int Cout, int Cin, int k
   conv_pack_weights(dtype, t.data(), cin_pad, Cout, ks, dst);
 }
 
-ConvGeom conv_geometry(const ConvDesc& d) {
+ConvGeom conv_geometry(const ConvDesc& d) { ConvRoute r; conv_route(d, &r); return r.geom; }
+
+int conv_route(const ConvDesc& d, ConvRoute* r) {
+  *r = ConvRoute{};
   Geo g; compute_geo(d, g);
-  ConvGeom r;
-  r.Ho = g.Ho; r.Wo = g.Wo; r.BM = g.BM; r.BN = g.BN; r.lds_bytes = g.lds;
-  r.grid_m = g.groups * g.tiles_x * g.tiles_y; r.grid_n = (d.Cout + g.BN - 1) / g.BN;
-  const int CH = d.dtype == 0 ? 16 : 32;
-  const mi355_debug_config& Kg = d.knobs ? *d.knobs : mi355_default_debug();
-  if (d.C0 % CH == 0 && d.C1 % CH == 0) {
-    const int pc = pp_config(Kg.conv_pp, d.ks, g.G, g.bn_pack, d.out_mode, g.stride, (d.C0 + d.C1) / CH * (d.wsplit ? 2 : 1), d.pro_a != nullptr, d.pro_silu != 0, d.N, g.Ho, g.Wo, d.Cout);
-    if (pc >= 0) {   // ping-pong kernel (conv_pp.inc.h): 256 px x 256 ch or 512 px x 128 ch tiles
-      r.BM = pc == 0 ? 256 : 512; r.BN = pc == 0 ? 256 : 128;
-      r.lds_bytes = pc == 0 ? pp::D<0>::lds_bytes(d.pro_a != nullptr) : pp::D<1>::lds_bytes(d.pro_a != nullptr);
-      return r;
-    }
-  }
-  if (d.C0 % CH == 0 && d.C1 % CH == 0 &&
-      ws_eligible((d.knobs ? d.knobs : &mi355_default_debug())->conv_ws, d.ks, g.BM, g.BN, g.G, g.bn_pack, d.out_mode, g.stride, (d.C0 + d.C1) / CH * (d.wsplit ? 2 : 1), d.N, g.Ho, g.Wo, d.Cout)) {
-    r.BM = 256; r.lds_bytes = ws::LDS_BYTES;   // warp-specialised persistent kernel: 16 x 16 pixel tiles (grid_m / grid_n stay the plain launch's: workspace sizing)
-  }
-  return r;
-}
-
-static int conv_launch_impl(const ConvDesc& d, hipStream_t stream, int* gn_slots_used, int* act_done, bool dry);
-int conv_launch(const ConvDesc& d, hipStream_t stream, int* gn_slots_used, int* act_done) { return conv_launch_impl(d, stream, gn_slots_used, act_done, false); }
-// 0: a conv with a fused skip conv (ConvDesc::skip_src0) of this description would launch; nothing is launched
-int conv_fused_skip_ok(const ConvDesc& d) { return d.skip_src0 ? conv_launch_impl(d, nullptr, nullptr, nullptr, true) : 1; }
-
-static int conv_launch_impl(const ConvDesc& d, hipStream_t stream, int* gn_slots_used, int* act_done, bool dry) {
-  if (gn_slots_used) *gn_slots_used = 0;
-  if (act_done) *act_done = 0;
+  r->geom = ConvGeom{g.Ho, g.Wo, g.BM, g.BN, g.lds, g.groups * g.tiles_x * g.tiles_y, (d.Cout + g.BN - 1) / g.BN};
   const bool fskip = d.skip_src0 != nullptr;   // only the small-level kernel carries a fused skip conv
-  if (!fskip) {
-    int r = conv1x1_try_launch(d, stream, gn_slots_used);
-    if (r <= 0) return r;
-    r = conv_out_try_launch(d, stream);
-    if (r <= 0) return r;
-    r = conv_in_try_launch(d, stream, gn_slots_used);
-    if (r <= 0) return r;
+  if (!fskip && !d.wsplit) {   // (hi / lo split weights: the implicit-GEMM kernels)
+    int rc = pp1_route(d, r);
+    if (rc == 1) rc = conv1x1_route(d, r);
+    if (rc == 1) rc = conv_out_route(d, r);
+    if (rc == 1) rc = conv_in_route(d, r);
+    if (rc <= 0) return rc;
   }
   const int CH = chunk_of(d.dtype);
   const int Cin = d.C0 + d.C1;
@@ -782,109 +794,96 @@ static int conv_launch_impl(const ConvDesc& d, hipStream_t stream, int* gn_slots
   MI355_REQUIRE(d.mode == CONV_UNIT || d.ks == 3, -1, "conv: resampling modes need a 3x3 kernel");
   MI355_REQUIRE(d.out_mode == OUT_NCHW_F32 || d.Cout % 32 == 0, -2, "conv: NHWC output needs Cout % 32 == 0 (a wave stores whole 32-channel tiles)");
   MI355_REQUIRE(d.mode != CONV_POOL2 && d.res_mode != RES_POOL2, -4, "conv: average pooling is a separate pass (affine_pool / resample), not a gather mode");
-  Geo g; compute_geo(d, g);
   MI355_REQUIRE(g.lds <= 160 * 1024, -4, "conv: LDS budget exceeded");
   MI355_REQUIRE(g.pit <= g.pit_t, -4, "conv: input patch too large for the staging loops");
-  ConvKArgs a{};
   MI355_REQUIRE(!d.wsplit || d.dtype == DT_BF16, -1, "conv: hi / lo split weights are a bf16 mode");
-  a.src0 = d.src0; a.src1 = d.src1; a.C0 = d.C0; a.C1 = d.C1; a.Cin = Cin; a.nreal = Cin / CH; a.nchunks = a.nreal * (d.wsplit ? 2 : 1);
-  a.N = d.N; a.Hs = d.Hs; a.Ws = d.Ws; a.Hc = g.Hc; a.Wc = g.Wc; a.Ho = g.Ho; a.Wo = g.Wo;
-  a.mode = d.mode; a.pad = g.pad; a.stride = g.stride;
-  a.pro_a = d.pro_a; a.pro_b = d.pro_b; a.pro_silu = d.pro_silu;
-  a.w = d.w; a.bias = d.bias; a.Cout = d.Cout; a.bn_pack = g.bn_pack;
-  const size_t esz = d.dtype == 0 ? 4 : 2;
-  const size_t b0 = (size_t)d.N * d.Hs * d.Ws * d.C0 * esz, b1 = (size_t)d.N * d.Hs * d.Ws * d.C1 * esz;
-  const size_t wb = conv_packed_weight_bytes(d.dtype, d.Cout, Cin, d.ks, d.wsplit) + (fskip ? conv_packed_weight_bytes(d.dtype, d.Cout, d.skip_C0 + d.skip_C1, 1, 0) : 0);
-  MI355_REQUIRE(b0 < 0xFFFF0000ull && b1 < 0xFFFF0000ull && wb < 0xFFFF0000ull, -4,
-                "conv: a source tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-  a.bytes0 = (uint32_t)b0; a.bytes1 = d.src1 ? (uint32_t)b1 : 0u; a.wbytes = (uint32_t)wb;
-  a.Hr = d.res_mode == RES_UP2 ? g.Ho / 2 : g.Ho;
-  a.Wr = d.res_mode == RES_UP2 ? g.Wo / 2 : g.Wo;
-  const size_t ob = (size_t)d.N * g.Ho * g.Wo * d.Cout * esz, rb = (size_t)d.N * a.Hr * a.Wr * d.Cout * esz;
-  MI355_REQUIRE(ob < 0xFFFF0000ull && rb < 0xFFFF0000ull, -4, "conv: output tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-  a.obytes = (uint32_t)ob; a.rbytes = d.res ? (uint32_t)rb : 0u;
-  a.dbg = reinterpret_cast<unsigned long long*>(d.dbg);
+  ConvKArgs a{};
+  if (int rc = igemm_args(d, g, a)) return rc;
   const mi355_debug_config& K = d.knobs ? *d.knobs : mi355_default_debug();
-  a.stagger = K.conv_stagger; a.ablate = K.conv_ablate;
-  a.err = d.err; a.spin_limit = K.conv_spin_limit > 0 ? K.conv_spin_limit : 1;
-  a.emb = d.emb; a.emb_stride = d.emb_stride;
-  a.res = d.res; a.res_mode = d.res ? d.res_mode : RES_NONE;
-  a.out = d.out; a.out_mode = d.out_mode;
-  a.gn_stats = nullptr; a.gn_slots = 0;
-  a.lvw = g.lvw; a.lth = g.lth; a.G = g.G; a.PW = g.PW; a.PH = g.PH; a.NP = g.NP;
-  a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
-  if (fskip) {
-    const size_t k0 = (size_t)d.N * g.Ho * g.Wo * d.skip_C0 * esz, k1 = (size_t)d.N * g.Ho * g.Wo * d.skip_C1 * esz;
-    MI355_REQUIRE(k0 < 0xFFFF0000ull && k1 < 0xFFFF0000ull, -4, "conv: a source tensor exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-    a.sk0 = d.skip_src0; a.sk1 = d.skip_src1; a.SC0 = d.skip_C0; a.SC1 = d.skip_src1 ? d.skip_C1 : 0;
-    a.skbytes0 = (uint32_t)k0; a.skbytes1 = d.skip_src1 ? (uint32_t)k1 : 0u;
-  }
-  dim3 grid(g.groups * g.tiles_x * g.tiles_y, (d.Cout + g.BN - 1) / g.BN);
   const bool gn_ok = d.gn_stats && d.out_mode == OUT_NHWC && g.G == 1 && d.Cout % g.BN == 0 && d.Cout % 4 == 0;
-  if (!fskip) {   // ping-pong kernel (conv_pp.inc.h): 256- or 128-channel output tiles, input as it is or through the in-LDS GroupNorm + SiLU prologue
-    const int pc = pp_config(K.conv_pp, d.ks, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, d.pro_a != nullptr, d.pro_silu != 0, d.N, g.Ho, g.Wo, d.Cout);
-    const int pp_slots = pc >= 0 ? pp_gn_slots(pc, g.Ho, g.Wo) : 0;
-    if (pc >= 0 && gn_ok && pp_slots <= d.gn_slots_cap) { a.gn_stats = d.gn_stats; a.gn_slots = pp_slots; }
-    int pp_act = 0;
-    if (d.act_out && act_done && (K.gn_epilogue & 2) && d.act_out == d.out && !d.act_raw) {   // in place: the activated tensor replaces the raw one
-      a.act_out = d.act_out; a.act_gamma = d.act_gamma; a.act_beta = d.act_beta; a.act_film = d.act_film; a.act_film_stride = d.act_film_stride;
-      a.act_eps = d.act_eps; a.act_silu = d.act_silu; a.act_raw = 0;
-    }
-    const int r = dispatch_dtype(d.dtype, [&](auto t) { return launch_pp<decltype(t)>(a, K.conv_pp, d.ks, stream, &pp_act); });
-    if (r == 0) {
-      MI355_CHECK_HIP(hipGetLastError());
-      if (pp_act) { if (act_done) *act_done = 1; if (gn_slots_used) *gn_slots_used = 0; }
-      else if (gn_slots_used) *gn_slots_used = a.gn_slots;
-      return 0;
-    }
-    if (r < 0) return r;
-    a.act_out = nullptr;
-    a.gn_stats = nullptr; a.gn_slots = 0;
+  const bool has_pro = d.pro_a != nullptr;
+  // ping-pong kernel (conv_pp.inc.h): 256- or 128-channel output tiles, input as it is or through the in-LDS GroupNorm + SiLU prologue
+  const int pc = fskip ? -1 : pp_config(K.conv_pp, d.ks, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, has_pro, d.pro_silu != 0, d.N, g.Ho, g.Wo, d.Cout);
+  if (pc >= 0) {
+    r->kernel = CONV_K_PP; r->form = pc;
+    r->geom.BM = pc == 0 ? 256 : 512; r->geom.BN = pc == 0 ? 256 : 128;
+    r->geom.lds_bytes = pc == 0 ? pp::D<0>::lds_bytes(has_pro) : pp::D<1>::lds_bytes(has_pro);
+    // the output GroupNorm in place (the activated tensor replaces the raw one): one 16 x 16 tile per image, no residual, 8 or 16 channels per group
+    const bool act = pc == 0 && g.Ho == 16 && g.Wo == 16 && (d.Cout == 256 || d.Cout == 512) && a.res_mode == RES_NONE;
+    if (act && d.act_out && (K.gn_epilogue & 2) && d.act_out == d.out && !d.act_raw) r->act_done = 1;
+    const int slots = pc == 0 ? 2 * ((g.Wo + 15) / 16) * ((g.Ho + 15) / 16) : 4 * ((g.Wo + 31) / 32) * ((g.Ho + 15) / 16);   // (pixel tile, pixel wave) per image
+    if (!r->act_done && gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
+    return 0;
   }
-  if (!fskip) {   // dominant shapes: warp-specialised persistent kernel (conv_ws.inc.h)
-    const int ws_slots = 2 * ((g.Wo + ws::VW - 1) / ws::VW) * ((g.Ho + ws::TH - 1) / ws::TH);   // (16x16 pixel tile, 8-row half) per image
-    if (gn_ok && ws_slots <= d.gn_slots_cap) { a.gn_stats = d.gn_stats; a.gn_slots = ws_slots; }
-    const int r = dispatch_dtype(d.dtype, [&](auto t) { return launch_ws<decltype(t)>(a, K.conv_ws, g.BM, g.BN, d.ks, stream); });
-    if (r == 0) {
-      MI355_CHECK_HIP(hipGetLastError());
-      if (gn_slots_used) *gn_slots_used = a.gn_slots;
-      return 0;
-    }
-    if (r < 0) return r;
-    a.gn_stats = nullptr; a.gn_slots = 0;
+  // dominant shapes: warp-specialised persistent kernel (conv_ws.inc.h)
+  if (!fskip && ws_eligible(K.conv_ws, d.ks, g.BM, g.BN, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, d.N, g.Ho, g.Wo, d.Cout)) {
+    r->kernel = CONV_K_WS;
+    r->geom.BM = 256; r->geom.lds_bytes = ws::LDS_BYTES;   // 16 x 16 pixel tiles
+    const int slots = 2 * ((g.Wo + ws::VW - 1) / ws::VW) * ((g.Ho + ws::TH - 1) / ws::TH);   // (16x16 pixel tile, 8-row half) per image
+    if (gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
+    return 0;
   }
-  {   // 8x8 / 4x4 levels: barrier-free K loop over an LDS-resident patch, weights straight into registers (conv_small.inc.h)
-    if (d.act_out && act_done && (K.gn_epilogue & 1) && d.act_out != d.out) {
-      a.act_out = d.act_out; a.act_gamma = d.act_gamma; a.act_beta = d.act_beta; a.act_film = d.act_film; a.act_film_stride = d.act_film_stride;
-      a.act_eps = d.act_eps; a.act_silu = d.act_silu; a.act_raw = d.act_raw;
+  // 8x8 / 4x4 levels: barrier-free K loop over an LDS-resident patch, weights straight into registers (conv_small.inc.h)
+  const bool act = d.act_out && (K.gn_epilogue & 1) && d.act_out != d.out, act2 = act && d.act2_out && (K.gn_epilogue & 4);
+  const size_t esz = d.dtype == 0 ? 4 : 2;
+  MI355_REQUIRE(!act || (size_t)d.N * g.Ho * g.Wo * (d.act_stride ? d.act_stride : d.Cout) * esz < 0xFFFF0000ull, -4,
+                "conv: activated output exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
+  MI355_REQUIRE(!act2 || (size_t)d.N * g.Ho * g.Wo * (d.act2_stride ? d.act2_stride : d.Cout) * esz < 0xFFFF0000ull, -4,
+                "conv: activated output exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
+  if (small_route(a, K.conv_small, d.ks, d.dtype, r) == 0) {
+    // GroupNorm of the output in the epilogue: whole images per wave (an 8x8 image split over K-sharing waves is not), 4 / 8 / 16 channels per group
+    auto cpg_ok = [&](int cpg, int coff) { return (cpg == 4 || cpg == 8 || cpg == 16) && d.Cout % cpg == 0 && coff % cpg == 0; };
+    const bool ok = act && cpg_ok(d.act_cpg ? d.act_cpg : d.Cout / 32, d.act_coff) && (g.Ho != 8 || r->ksplit == 1);
+    const bool ok2 = ok && act2 && cpg_ok(d.act2_cpg ? d.act2_cpg : d.Cout / 32, d.act2_coff);
+    r->act_done = (ok ? 1 : 0) | (ok2 ? 2 : 0);
+    return 0;
+  }
+  MI355_REQUIRE(!fskip, -5, "conv: no kernel carries the fused skip conv of this description (shape, batch or knobs)");
+  const int slots = g.tiles_x * g.tiles_y * (g.BN == 32 ? 4 : 2);   // (pixel tile, pixel-wave) per image
+  if (gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
+  return 0;
+}
+
+int conv_launch(const ConvDesc& d, hipStream_t stream) { ConvRoute r; int rc = conv_route(d, &r); return rc ? rc : conv_launch(d, r, stream); }
+
+int conv_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream) {
+  switch (r.kernel) {
+    case CONV_K_1X1_PP: return pp1_launch(d, r, stream);
+    case CONV_K_1X1: return conv1x1_launch(d, r, stream);
+    case CONV_K_OUT: return conv_out_launch(d, r, stream);
+    case CONV_K_IN: return conv_in_launch(d, r, stream);
+    default: break;
+  }
+  Geo g; compute_geo(d, g);
+  ConvKArgs a{};
+  if (int rc = igemm_args(d, g, a)) return rc;
+  if (r.gn_slots) { a.gn_stats = d.gn_stats; a.gn_slots = r.gn_slots; }
+  const size_t esz = d.dtype == 0 ? 4 : 2;
+  if (r.act_done & 1) {
+    a.act_out = d.act_out; a.act_gamma = d.act_gamma; a.act_beta = d.act_beta; a.act_film = d.act_film; a.act_film_stride = d.act_film_stride;
+    a.act_eps = d.act_eps; a.act_silu = d.act_silu; a.act_raw = d.act_raw;
+  }
+  int rc;
+  if (r.kernel == CONV_K_PP) rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_pp<decltype(t)>(a, r.form, stream); });
+  else if (r.kernel == CONV_K_WS) rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_ws<decltype(t)>(a, stream); });
+  else if (r.kernel == CONV_K_SMALL) {
+    if (r.act_done & 1) {
       a.act_stride = d.act_stride ? d.act_stride : d.Cout; a.act_coff = d.act_coff; a.act_cpg = d.act_cpg ? d.act_cpg : d.Cout / 32;
-      const size_t ab = (size_t)d.N * g.Ho * g.Wo * a.act_stride * esz;
-      MI355_REQUIRE(ab < 0xFFFF0000ull, -4, "conv: activated output exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-      a.abytes = (uint32_t)ab;
-      if (d.act2_out && (K.gn_epilogue & 4)) {
-        a.act2_out = d.act2_out; a.act2_gamma = d.act2_gamma; a.act2_beta = d.act2_beta; a.act2_silu = d.act2_silu;
-        a.act2_stride = d.act2_stride ? d.act2_stride : d.Cout; a.act2_coff = d.act2_coff; a.act2_cpg = d.act2_cpg ? d.act2_cpg : d.Cout / 32;
-        const size_t a2b = (size_t)d.N * g.Ho * g.Wo * a.act2_stride * esz;
-        MI355_REQUIRE(a2b < 0xFFFF0000ull, -4, "conv: activated output exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-        a.a2bytes = (uint32_t)a2b;
-      }
+      a.abytes = (uint32_t)((size_t)d.N * g.Ho * g.Wo * a.act_stride * esz);
+      const mi355_debug_config& K = d.knobs ? *d.knobs : mi355_default_debug();
       a.warm = (K.l2_warm & 1) ? d.warm : nullptr; a.warm_bytes = a.warm ? d.warm_bytes : 0u;
     }
-    const int r = dispatch_dtype(d.dtype, [&](auto t) { return launch_small<decltype(t)>(a, K.conv_small, d.ks, stream, act_done, dry); });
-    if (dry) return r;
-    if (r == 0) { MI355_CHECK_HIP(hipGetLastError()); return 0; }
-    MI355_REQUIRE(!fskip || r < 0, -5, "conv: this launch cannot carry the fused skip conv (ask conv_fused_skip_ok first)");
-    if (act_done) *act_done = 0;
-    a.act_out = nullptr; a.act2_out = nullptr; a.warm = nullptr; a.warm_bytes = 0;
-    if (r < 0) return r;
+    if (r.act_done & 2) {
+      a.act2_out = d.act2_out; a.act2_gamma = d.act2_gamma; a.act2_beta = d.act2_beta; a.act2_silu = d.act2_silu;
+      a.act2_stride = d.act2_stride ? d.act2_stride : d.Cout; a.act2_coff = d.act2_coff; a.act2_cpg = d.act2_cpg ? d.act2_cpg : d.Cout / 32;
+      a.a2bytes = (uint32_t)((size_t)d.N * g.Ho * g.Wo * a.act2_stride * esz);
+    }
+    rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_small<decltype(t)>(a, r, stream); });
+  } else {
+    const dim3 grid(g.groups * g.tiles_x * g.tiles_y, (d.Cout + g.BN - 1) / g.BN);
+    rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_cfg<decltype(t)>(a, g.BM, g.BN, d.ks, g.pit_t, grid, g.lds, stream); });
   }
-  {
-    const int slots = g.tiles_x * g.tiles_y * (g.BN == 32 ? 4 : 2);   // (pixel tile, pixel-wave) per image
-    if (gn_ok && slots <= d.gn_slots_cap) { a.gn_stats = d.gn_stats; a.gn_slots = slots; }
-  }
-  int rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_cfg<decltype(t)>(a, g.BM, g.BN, d.ks, g.pit_t, grid, g.lds, stream); });
   if (rc) return rc;
   MI355_CHECK_HIP(hipGetLastError());
-  if (gn_slots_used) *gn_slots_used = a.gn_slots;
   return 0;
 }

@@ -714,28 +714,10 @@ int launch_pp_k(ConvKArgs a, hipStream_t s) {
   return 0;
 }
 
-// statistics slots per image the launch fills (pixel tile x pixel wave), for a geometry pp_config returned
-static int pp_gn_slots(int cfg, int Ho, int Wo) {
-  return cfg == 0 ? 2 * ((Wo + 15) / 16) * ((Ho + 15) / 16) : 4 * ((Wo + 31) / 32) * ((Ho + 15) / 16);
-}
-
-// 0 = launched, 1 = not eligible, < 0 = error.  a.act_out set: the caller asks for the fused output GroupNorm (in place); *act_done reports whether this
-// launch did it (wide form, one 16 x 16 tile per image, no residual, 8 or 16 channels per group) - otherwise the conv runs without it.
+// cfg: pp_config's geometry; a.act_out set: the form that applies the output GroupNorm in place (wide, conv_route decides)
 template <typename T>
-int launch_pp(ConvKArgs a, int mode, int ks, hipStream_t s, int* act_done = nullptr) {
-  if (act_done) *act_done = 0;
-  const int cfg = pp_config(mode, ks, a.G, a.bn_pack, a.out_mode, a.stride, a.nchunks, a.pro_a != nullptr, a.pro_silu != 0, a.N, a.Ho, a.Wo, a.Cout);
-  if (cfg < 0) return 1;
-  if (a.act_out) {
-    const int cpg = a.Cout / 32;
-    const bool ok = cfg == 0 && a.Ho == 16 && a.Wo == 16 && (cpg == 8 || cpg == 16) && a.res_mode == RES_NONE && a.act_out == a.out && !a.act_raw;
-    if (!ok) a.act_out = nullptr;
-  }
-  if (a.act_out) {
-    a.gn_stats = nullptr; a.gn_slots = 0;
-    if (act_done) *act_done = 1;
-    return a.pro_a ? launch_pp_k<T, 0, 2, 1>(a, s) : launch_pp_k<T, 0, 0, 1>(a, s);
-  }
+int launch_pp(const ConvKArgs& a, int cfg, hipStream_t s) {
+  if (a.act_out) return a.pro_a ? launch_pp_k<T, 0, 2, 1>(a, s) : launch_pp_k<T, 0, 0, 1>(a, s);
   if (a.pro_a) return cfg == 0 ? launch_pp_k<T, 0, 2>(a, s) : launch_pp_k<T, 1, 2>(a, s);
   return cfg == 0 ? launch_pp_k<T, 0, 0>(a, s) : launch_pp_k<T, 1, 0>(a, s);
 }

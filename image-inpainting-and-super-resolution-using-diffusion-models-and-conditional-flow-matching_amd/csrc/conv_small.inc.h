@@ -562,11 +562,8 @@ __global__ void __launch_bounds__(NI == 4 ? 256 : 512, NI == 4 ? 1 : 2) conv3x3_
 // 16 -> 8 and 8 -> 4, AD/image_diffusion/unet.py:217-240: the staged patch is the (2 Ho + 1)^2 input window, the fragment addresses step two
 // pixels per output pixel: 2-way bank conflicts on reads that are a tenth of this kernel's LDS budget), no GroupNorm prologue (these
 // levels normalise in a pass of their own), NHWC output with C_out % 128 == 0, residual at the output resolution or none.
-// 0 = launched, 1 = not eligible (the caller goes on to the plain kernel), < 0 = error
-// dry: eligibility only (the walker decides about a fused skip conv before it reaches the conv that would carry it)
-template <typename T>
-int launch_small(const ConvKArgs& a0, int enabled, int ks, hipStream_t s, int* act_done, bool dry = false) {
-  ConvKArgs a = a0;
+// 0 = taken (r: ksplit, waves, w8x2, sm::Args, LDS, fused skip conv), 1 = not this kernel (the plain kernel).  a: the plain kernel's arguments.
+static int small_route(const ConvKArgs& a, int enabled, int ks, int dtype, ConvRoute* r) {
   if (!enabled || ks != 3 || a.out_mode != OUT_NHWC || a.pro_a) return 1;
   const bool s2 = a.stride == 2;
   const bool skip = a.sk0 != nullptr;
@@ -574,21 +571,19 @@ int launch_small(const ConvKArgs& a0, int enabled, int ks, hipStream_t s, int* a
   if (s2 && (!(enabled & 4) || a.mode != CONV_STRIDE2 || a.Hc != 2 * a.Ho || a.Wc != 2 * a.Wo)) return 1;
   if (a.Ho != a.Wo || (a.Ho != 8 && a.Ho != 4) || a.Cout % 128 != 0) return 1;
   if (a.res_mode != RES_NONE && a.res_mode != RES_SAME) return 1;
-  constexpr int CH = Elem<T>::CHUNK;
+  const int CH = dtype == 0 ? 16 : 32;
   if (a.C0 % CH || a.C1 % CH) return 1;
   const bool w8 = a.Ho == 8;
   sm::Args g;
-  a.lvw = a.lth = w8 ? 3 : 2;
-  a.G = w8 ? 1 : 4;
-  a.PW = a.PH = s2 ? 2 * a.Ho + 1 : a.Ho + 2;
-  g.pwp = s2 ? a.PW : (w8 ? 16 : 8); g.sh = w8 ? 1 : 2;
-  g.pimg = a.PH * g.pwp;
-  g.plane = (a.G * g.pimg - (g.pwp - a.PW)) * 64;
+  const int G = w8 ? 1 : 4, PW = s2 ? 2 * a.Ho + 1 : a.Ho + 2;
+  g.pwp = s2 ? PW : (w8 ? 16 : 8); g.sh = w8 ? 1 : 2;
+  g.pimg = PW * g.pwp;
+  g.plane = (G * g.pimg - (g.pwp - PW)) * 64;
   const int nchp = s2 ? (w8 ? 8 : 4) : (w8 ? 16 : 8);
   g.nphase = (a.nchunks + nchp - 1) / nchp;
   g.chp = a.nchunks / g.nphase;
   if (g.chp * g.nphase != a.nchunks) return 1;
-  const int tiles = (a.N + a.G - 1) / a.G;
+  const int tiles = (a.N + G - 1) / G;
   // waves along N: as many as keep every CU busy (each halving doubles the workgroups and splits K between wave pairs)
   const int ncu = ws_num_cus();
   int nw = 4;
@@ -598,7 +593,6 @@ int launch_small(const ConvKArgs& a0, int enabled, int ks, hipStream_t s, int* a
   if (g.chp % ksplit) return 1;
   g.red_bytes = ksplit > 1 ? 4 * 16 * 1024 : 0;
   g.sphase = g.schp = g.sup = 0;
-  a.wstride = (uint32_t)a.nchunks * 9;
   if (skip) {
     if (a.SC0 % CH || a.SC1 % CH) return 1;
     const int ns = (a.SC0 + a.SC1) / CH;
@@ -606,28 +600,36 @@ int launch_small(const ConvKArgs& a0, int enabled, int ks, hipStream_t s, int* a
     g.sphase = g.sup ? 1 : (ns + nchp - 1) / nchp;
     g.schp = ns / g.sphase;
     if (g.schp * g.sphase != ns || g.schp % ksplit) return 1;
-    a.wstride += (uint32_t)ns;
   }
   const size_t lds = g.sup ? std::max((size_t)g.chp * g.plane + (size_t)g.schp * sm::SPLANE, (size_t)g.red_bytes)
                            : std::max((size_t)std::max(g.chp, g.schp) * g.plane, (size_t)g.red_bytes);
   if (lds > 160 * 1024) return 1;
-  if (dry) return 0;
-  a.gn_stats = nullptr; a.gn_slots = 0;
-  {   // GroupNorm of the output in the epilogue: whole images per wave (an 8x8 image split over K-sharing waves is not), 4 / 8 / 16 channels per group
-    auto cpg_ok = [&](int cpg, int coff) { return (cpg == 4 || cpg == 8 || cpg == 16) && a.Cout % cpg == 0 && coff % cpg == 0; };
-    const bool ok = a.act_out && cpg_ok(a.act_cpg, a.act_coff) && (!w8 || ksplit == 1);
-    if (!ok) { a.act_out = nullptr; a.warm = nullptr; a.warm_bytes = 0; }
-    const bool ok2 = ok && a.act2_out && cpg_ok(a.act2_cpg, a.act2_coff);
-    if (!ok2) a.act2_out = nullptr;
-    if (act_done) *act_done = (ok ? 1 : 0) | (ok2 ? 2 : 0);
-  }
+  r->kernel = CONV_K_SMALL; r->ksplit = ksplit; r->n_mt = tiles; r->n_nt = a.Cout / (64 * nw); r->lds = lds; r->skip = skip;
   // whole-chip launches of the 8x8 level (one image per workgroup, no K split): eight waves of 32 channels (knob conv_small bit 1)
-  const bool w8x2 = w8 && !s2 && !skip && ksplit == 1 && (enabled & 2) && a.Cout % 256 == 0;
-  dim3 grid(tiles, a.Cout / (64 * nw));
+  r->form = w8 && !s2 && !skip && ksplit == 1 && (enabled & 2) && a.Cout % 256 == 0;
+  static_assert(sizeof(r->sm) == sizeof(sm::Args), "ConvRoute::sm holds sm::Args");
+  memcpy(r->sm, &g, sizeof g);
+  return 0;
+}
+
+// a.act_out / a.act2_out: the GroupNorm sites the route applies (ConvRoute::act_done), or null
+template <typename T>
+int launch_small(const ConvKArgs& a0, const ConvRoute& r, hipStream_t s) {
+  ConvKArgs a = a0;
+  const bool s2 = a.stride == 2, skip = r.skip, w8 = a.Ho == 8, w8x2 = r.form;
+  const int ksplit = r.ksplit;
+  sm::Args g;
+  memcpy(&g, r.sm, sizeof g);
+  a.lvw = a.lth = w8 ? 3 : 2;
+  a.G = w8 ? 1 : 4;
+  a.PW = a.PH = s2 ? 2 * a.Ho + 1 : a.Ho + 2;
+  a.wstride = (uint32_t)a.nchunks * 9 + (skip ? (uint32_t)(g.sphase * g.schp) : 0u);
+  a.gn_stats = nullptr; a.gn_slots = 0;
+  const dim3 grid(r.n_mt, r.n_nt);
   int rc = 0;
   auto go = [&](auto kern, int threads) {
     rc = mi355_allow_big_lds(kern, "conv3x3 (small levels)");
-    if (rc == 0) hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, a, g);
+    if (rc == 0) hipLaunchKernelGGL(kern, grid, dim3(threads), r.lds, s, a, g);
   };
   if (s2) {   // (2 Ho + 1)^2 patch pixels per image: 289 x 4 / 256 -> 5 fragments per thread (8x8), 4 x 81 x 4 / 256 -> 6 (4x4)
     if (w8) {

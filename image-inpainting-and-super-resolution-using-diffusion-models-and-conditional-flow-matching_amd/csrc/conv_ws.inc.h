@@ -916,10 +916,9 @@ static bool ws_eligible(int enabled, int ks, int BM, int BN, int G, int bn_pack,
   return n_mt * n_nt >= ws_num_cus();   // fewer tiles than CUs: the plain kernel's smaller tiles fill the chip better
 }
 
-// 0 = launched, 1 = not eligible (caller uses the plain kernel), < 0 = error
+// a shape ws_eligible accepts
 template <typename T>
-int launch_ws(ConvKArgs a, int enabled, int BM, int BN, int ks, hipStream_t s) {
-  if (!ws_eligible(enabled, ks, BM, BN, a.G, a.bn_pack, a.out_mode, a.stride, a.nchunks, a.N, a.Ho, a.Wo, a.Cout)) return 1;
+int launch_ws(ConvKArgs a, hipStream_t s) {
   a.lvw = 4; a.lth = 4; a.PW = ws::PW; a.PH = ws::PH; a.NP = ws::NPX;
   a.tiles_x = (a.Wo + ws::VW - 1) / ws::VW; a.tiles_y = (a.Ho + ws::TH - 1) / ws::TH;
   const int n_mt = a.N * a.tiles_x * a.tiles_y, n_nt = (a.Cout + 127) / 128;

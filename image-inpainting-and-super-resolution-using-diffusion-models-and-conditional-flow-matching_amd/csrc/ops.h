@@ -43,14 +43,14 @@ struct ConvDesc {
   const void* res = nullptr; int res_mode = RES_NONE;  // residual NHWC tensor with Cout channels
   void* out = nullptr; int out_mode = OUT_NHWC;
   // optional fused GroupNorm statistics of the OUTPUT (common.h GnPartial): [N][slots][Cout/4][2] fp32, room for gn_slots_cap slots
-  // per image; conv_launch reports the slots it filled (0 = this launch cannot produce them: the caller runs the stats kernel)
+  // per image; ConvRoute::gn_slots is the number the launch fills (0 = this launch cannot produce them: the caller runs the stats kernel)
   float* gn_stats = nullptr; int gn_slots_cap = 0;
   void* dbg = nullptr;                      // diagnostic builds only (-DCONV_STAMPS): 9 x u64 phase-cycle sums
   const mi355_debug_config* knobs = nullptr; // diagnostic switches (null = defaults)
   uint32_t* err = nullptr;                  // device-visible error word: the persistent kernel ORs 1 into it when a counter wait expires
   // Optional: the GroupNorm (+ SiLU) site that reads this conv's output, applied in the conv's epilogue where the kernel holds whole
   // images x whole groups per wave (conv_small.inc.h): act_out = silu?(GN(out)) in out's layout; out itself only if act_raw; one touch
-  // of the next conv's packed weights (warm).  conv_launch reports through *act_done whether the launch did it (0: run the pass).
+  // of the next conv's packed weights (warm).  Null: no fusion asked for.  ConvRoute::act_done says whether the launch does it (0: run the pass).
   void* act_out = nullptr; const float* act_gamma = nullptr; const float* act_beta = nullptr;
   const float* act_film = nullptr; int act_film_stride = 0; float act_eps = 1e-5f; int act_silu = 0, act_raw = 1;
   // Where the site is the GroupNorm of a CONCAT consumer (unet.py:650: h = cat([h, hs.pop()])) and its groups are whole inside each
@@ -58,20 +58,20 @@ struct ConvDesc {
   // act_coff ..., in groups of act_cpg channels (0 = Cout / 32); act_gamma / act_beta already point at channel act_coff.
   int act_stride = 0, act_coff = 0, act_cpg = 0;
   // A skip connection is read by TWO such sites (the next ResBlock's in_layers norm now, the up path's concat norm later): the second
-  // one, same conventions, never FiLM.  *act_done: bit 0 = the first site was applied, bit 1 = the second.
+  // one, same conventions, never FiLM.  ConvRoute::act_done: bit 0 = the first site is applied, bit 1 = the second.
   void* act2_out = nullptr; const float* act2_gamma = nullptr; const float* act2_beta = nullptr;
   int act2_silu = 0, act2_stride = 0, act2_coff = 0, act2_cpg = 0;
   const void* warm = nullptr; uint32_t warm_bytes = 0;
-  // Optional (small-level kernel only; ask conv_fused_skip_ok first): out += conv1x1(cat(skip_src0, skip_src1)) - a ResBlock's skip_connection
+  // Optional (small-level kernel only: conv_route fails where it cannot carry it): out += conv1x1(cat(skip_src0, skip_src1)) - a ResBlock's skip_connection
   // (unet.py:312-317, 351) inside its second conv: centre-tap K chunks of the raw block input at the output resolution.  w then is the image
   // conv_pack_weights_skip made, bias the sum of both biases, res none, src1 none.
   const void* skip_src0 = nullptr; const void* skip_src1 = nullptr; int skip_C0 = 0, skip_C1 = 0;
   // Optional, the network's two edge convs (conv_edge.hip), sampler loops: (i) first conv: the caller's fp32 NCHW tensors x (nchw_c0 channels)
   // and condition (nchw_c1) read directly while the patch is staged - src0's packed NHWC copy (pack_nhwc) is then never made
-  // (conv_in_reads_nchw says whether the launch would); (ii) last conv (NCHW fp32 output v): axpy_x += axpy_scale * v instead of storing
-  // v - the Euler update x <- x + dt v of the flow-matching sampler (mnist/utils_mnist2.py:118-138) in the epilogue; *axpy_done = 1 if done
+  // (ConvRoute::reads_nchw says whether the launch does; otherwise it reads src0); (ii) last conv (NCHW fp32 output v): axpy_x += axpy_scale * v
+  // instead of storing v - the Euler update x <- x + dt v of the flow-matching sampler (mnist/utils_mnist2.py:118-138) in the epilogue (ConvRoute::axpy)
   const float* nchw0 = nullptr; const float* nchw1 = nullptr; int nchw_c0 = 0, nchw_c1 = 0;
-  float* axpy_x = nullptr; float axpy_scale = 0.f; int* axpy_done = nullptr;
+  float* axpy_x = nullptr; float axpy_scale = 0.f;
   int cin_real = 0;                         // > 0: only the first cin_real channels of src0 are non-zero (the network's first conv: in_channels padded to a chunk)
   int wsplit = 0;                           // 1 (bf16x2 precision): w holds [bf16(w) | bf16(w - bf16(w))] along K (twice the chunks): the contraction runs over the
                                             // input channels twice, once against each half - fp32 accumulation of both, activations read (not stored) twice
@@ -82,26 +82,44 @@ struct ConvGeom {
   size_t lds_bytes;
   int grid_m, grid_n;
 };
-ConvGeom conv_geometry(const ConvDesc& d);
+// The kernel conv_launch takes for a description, how it is configured and what it does with the description's optional parts.
+enum ConvKernel { CONV_K_IGEMM = 0, CONV_K_1X1, CONV_K_1X1_PP, CONV_K_IN, CONV_K_OUT, CONV_K_PP, CONV_K_WS, CONV_K_SMALL };
+struct ConvRoute {
+  int kernel = CONV_K_IGEMM;
+  ConvGeom geom{};          // the implicit-GEMM tile, or the ping-pong / warp-specialised one (grid_m / grid_n stay the plain launch's: workspace sizing)
+  int form = 0;             // 1X1_PP: 0 = 512 x 128, 1 = 256 x 256, 2 = 128 x 256 tiles; OUT: 1 = FIXED; PP: 0 = wide, 1 = narrow; SMALL: 1 = w8x2
+  int BM = 0, GC = 0, ntn = 0;     // 1X1: pixel tile, weight chunks per group, output-channel tiles per workgroup,
+  int lvw = 0, lth = 0, G = 0, tiles_x = 0, tiles_y = 0;   //   and its pixel tiling: log2 of the tile's width / height, images per tile
+  int n_mt = 0, n_nt = 0;          // 1X1_PP: pixel and channel tiles; 1X1 / SMALL: workgroups along M / N
+  int ksplit = 0, sm[10] = {};     // SMALL: waves sharing K; the kernel's sm::Args (conv_small.inc.h), field for field
+  size_t lds = 0;                  // dynamic LDS bytes (1X1, OUT, SMALL)
+  int gn_slots = 0;         // statistics slots per image the launch fills (0: the caller runs the statistics kernel)
+  int act_done = 0;         // bit 0 / 1: the GroupNorm site act_out / act2_out is applied in the epilogue
+  int axpy = 0, skip = 0;   // the Euler update replaces the store; the fused 1x1 skip conv is carried
+  int reads_nchw = 0;       // the first conv reads the fp32 NCHW tensors nchw0 / nchw1 itself (src0 unused)
+};
+// Pure host code (nothing launched or allocated): 0 and *r filled, or < 0 for a description no kernel runs (message set).
+int conv_route(const ConvDesc& d, ConvRoute* r);
+int conv_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream);   // launches r = conv_route(d): 0 or < 0, never "not mine"
+int conv_launch(const ConvDesc& d, hipStream_t stream);                       // conv_route, then conv_launch
+ConvGeom conv_geometry(const ConvDesc& d);                                    // conv_route(d).geom
 // bytes of the packed weight image for a [Cout][Cin][ks][ks] filter
 size_t conv_packed_weight_bytes(int dtype, int Cout, int Cin, int ks, int split = 0);
 int conv_tile_n(int Cout);
 // host-side packing: w_host [Cout][Cin][ks][ks] fp32 (Cin = logical input channels; padded to a chunk)
 // split = 1 (bf16 only): [hi | lo] halves along K, hi = bf16(w), lo = bf16(w - hi); the chunk count doubles
 void conv_pack_weights(int dtype, const float* w_host, int Cout, int Cin, int ks, void* dst_host, int split = 0);
-int conv_launch(const ConvDesc& d, hipStream_t stream, int* gn_slots_used = nullptr, int* act_done = nullptr);
-int conv_in_reads_nchw(const ConvDesc& d);    // 0 = conv_launch(d) with nchw0 set would take the first-conv kernel and read the fp32 NCHW tensors itself
-int conv_fused_skip_ok(const ConvDesc& d);   // 0 = conv_launch(d) would launch with its fused skip conv (nothing is launched here)
 // [3x3 filter w3 [Cout][Cin][3][3] | 1x1 filter w1 [Cout][Cskip]] per 128-channel pack tile: the 3x3 tiles, then one tile per skip chunk
 size_t conv_packed_weight_bytes_skip(int dtype, int Cout, int Cin, int Cskip);
 void conv_pack_weights_skip(int dtype, const float* w3, const float* w1, int Cout, int Cin, int Cskip, void* dst_host);
-// 1x1 GEMM with a stationary activation tile (conv1x1.hip): 0 = launched, 1 = not eligible, <0 = error
-int conv1x1_try_launch(const ConvDesc& d, hipStream_t stream, int* gn_slots_used = nullptr);
-// 1x1 GEMM in the ping-pong structure (conv_pp1.inc.h: 256 pixels x 256 channels, both operands streamed by DMA): same return convention
-int conv1x1_pp_try_launch(const ConvDesc& d, hipStream_t stream, int* gn_slots_used = nullptr);
-int conv_in_try_launch(const ConvDesc& d, hipStream_t stream, int* gn_slots_used = nullptr);   // conv_edge.hip: the network's first conv
-// the network's last conv (GN + SiLU prologue, <= 4 output channels, NCHW fp32) as a streaming kernel (conv_edge.hip): same convention
-int conv_out_try_launch(const ConvDesc& d, hipStream_t stream);
+// Families outside conv_igemm.hip (*_route: 0 = taken, 1 = not this family, < 0 = error; *_launch launches that route): conv1x1.hip's 1x1 GEMM
+// with a stationary activation tile; conv_edge.hip's first conv and last conv (GN + SiLU prologue, <= 4 output channels, NCHW fp32)
+int conv1x1_route(const ConvDesc& d, ConvRoute* r);
+int conv1x1_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream);
+int conv_in_route(const ConvDesc& d, ConvRoute* r);
+int conv_in_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream);
+int conv_out_route(const ConvDesc& d, ConvRoute* r);
+int conv_out_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream);
 
 // ---- GroupNorm statistics -> per-(n, channel) affine ----------------------------------------------
 // a[n,c] = rstd * gamma[c] (* (1 + film_scale)), b[n,c] = beta[c] - mean * rstd * gamma[c] (FiLM folded)

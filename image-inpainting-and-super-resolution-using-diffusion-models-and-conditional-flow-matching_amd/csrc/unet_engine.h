@@ -43,7 +43,7 @@ struct PlanOp {
   // attention
   int heads = 0, ch = 0;
   // small levels: a ResBlock's 1x1 skip_connection op names the second conv that can carry it (carrier), and that conv names the skip op
-  // (skip_op) and holds the fused weight image / summed bias (conv_pack_weights_skip); decided per launch (conv_fused_skip_ok)
+  // (skip_op) and holds the fused weight image / summed bias (conv_pack_weights_skip); decided per launch (conv_route)
   int carrier = -1, skip_op = -1; size_t wf_off = 0, bf_off = 0;
 };
 

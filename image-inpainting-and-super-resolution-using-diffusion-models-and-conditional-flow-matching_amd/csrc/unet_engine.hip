@@ -200,7 +200,7 @@ struct Walker {
       const int out = add_conv(p + ".out_layers.3", y2, -1, cout, cout, 3, CONV_UNIT, false, 0, 0, -1, res, res_mode, OUT_NHWC);
       // Small levels (apply-type norms: the second conv reads one already-activated tensor): the 1x1 skip_connection can ride in the
       // second conv as centre-tap K chunks of the raw block input (unet.py:312-317, 351: return skip_connection(x) + h), if the launch
-      // agrees (conv_fused_skip_ok: the small-level kernel, conv_small bit 3).  Both weight images are kept.
+      // agrees (conv_route: the small-level kernel, conv_small bit 3).  Both weight images are kept.
       if (out >= 0 && skip_idx >= 0 && net->ops[skip_idx].ks == 1 && !cfg.differentiable && !net->wsplit && cout % 128 == 0) {
         const int conv2_idx = (int)net->ops.size() - 1;
         PlanOp& c2 = net->ops[conv2_idx];
@@ -594,24 +594,6 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
   const float* embp = run.emb_row ? run.emb_row : F(l.embp);
   if (!run.emb_row && (rc = unet_embedding_table(net, t, Be, F(l.embp), F(l.temb), stream))) return rc;
   const int S = net->cfg.image_size;
-  // the first conv reads the caller's fp32 NCHW tensors itself where its kernel can (conv_edge bit 2): no packed copy, no pack launch
-  bool in_direct = false;
-  if (!net->cfg.differentiable && readers[net->in_tensor] == 1) {
-    for (const PlanOp& o : net->ops) {
-      if (o.kind != OP_CONV || o.src0 != net->in_tensor) continue;
-      const PlanTensor& ti = net->tensors[net->in_tensor];
-      ConvDesc c; c.dtype = dtype; c.src0 = TP(o.src0); c.C0 = ti.C; c.N = B; c.Hs = ti.H; c.Ws = ti.W; c.mode = o.mode; c.ks = o.ks; c.wsplit = net->wsplit;
-      c.w = W + o.w_off; c.bias = WF(o.bias_off); c.Cout = o.Cout; c.out_mode = o.out_mode; c.out = TP(o.dst); c.knobs = &net->knobs;
-      c.cin_real = net->cfg.in_channels;
-      if (o.use_pro || o.emb_off >= 0 || o.res >= 0 || o.src1 >= 0) break;
-      c.nchw0 = x; c.nchw_c0 = Cx; c.nchw1 = cond; c.nchw_c1 = cond ? Cc : 0;
-      in_direct = conv_in_reads_nchw(c) == 0;
-      break;
-    }
-  }
-  if (in_direct) { if ((size_t)net->in_tensor < net->tensor_state_n) net->tensor_state[net->in_tensor].store((char)1, std::memory_order_relaxed); }
-  else if ((rc = pack_nhwc_launch(dtype, x, Cx, cond, cond ? Cc : 0, B, S * S, net->in_pad, TP(net->in_tensor), stream))) return rc;
-  { mi355_op_profile r{}; r.kind = MI355_OP_PRELUDE; mark(r); }
   // the conv a GroupNorm pass feeds is the next op of the plan: the pass warms the L2s with its weights (common.h l2_warm_wave)
   const int warm_mask = net->knobs.l2_warm;   // 1 = statistics / apply passes, 2 = finalize passes (measured: no gain, off)
   auto warm_next = [&](const PlanOp& op, const void*& wp, uint32_t& wb, int bit) {
@@ -621,6 +603,96 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
     const int cin = net->tensors[nx.src0].C + (nx.src1 >= 0 ? net->tensors[nx.src1].C : 0);
     wp = W + nx.w_off; wb = (uint32_t)conv_packed_weight_bytes(dtype, nx.Cout, cin, nx.ks, net->wsplit);
   };
+  // The whole description of plan conv oi, everything it may do included; conv_route says which of it the launch does.  skip: with its
+  // ResBlock's 1x1 skip conv (op.skip_op) riding along.  act_consumer / fused_site: the GroupNorm sites act_out / act2_out stand for.
+  struct ConvOp { ConvDesc c; size_t act_consumer = 0; int fused_site[2] = {-1, -1}; };
+  auto conv_op = [&](size_t oi, bool skip) {
+    const PlanOp& op = net->ops[oi];
+    const PlanTensor& s0 = net->tensors[op.src0];
+    ConvOp r;
+    ConvDesc& c = r.c;
+    c.dtype = dtype; c.src0 = TP(op.src0); c.C0 = s0.C; c.src1 = TP(op.src1); c.C1 = op.src1 >= 0 ? net->tensors[op.src1].C : 0;
+    c.N = B; c.Hs = s0.H; c.Ws = s0.W; c.mode = op.mode; c.ks = op.ks; c.wsplit = net->wsplit;
+    if (op.use_pro && !pro_off[oi]) { c.pro_a = F(l.gna); c.pro_b = F(l.gnb); c.pro_silu = op.pro_silu; }
+    if (op.use_pro && !pro_off[oi] && op.gn_site >= 0) {
+      float* sp = F(l.sites) + net->site_off[op.gn_site] * (size_t)B;
+      c.pro_a = sp; c.pro_b = sp + (size_t)B * net->site_C[op.gn_site];
+    }
+    c.w = W + op.w_off; c.bias = WF(op.bias_off); c.Cout = op.Cout;
+    if (op.src0 == net->in_tensor) {
+      c.cin_real = net->cfg.in_channels;
+      // the first conv may read the caller's fp32 NCHW tensors itself (conv_edge bit 2): no packed copy, no pack launch
+      if (!net->cfg.differentiable && readers[net->in_tensor] == 1) { c.nchw0 = x; c.nchw_c0 = Cx; c.nchw1 = cond; c.nchw_c1 = cond ? Cc : 0; }
+    }
+    if (op.out_mode == OUT_NCHW_F32 && run.euler_x) { c.axpy_x = run.euler_x; c.axpy_scale = run.euler_dt; }
+    if (op.emb_off >= 0) { c.emb = embp + op.emb_off; c.emb_stride = estride; }
+    if (op.res >= 0) { c.res = TP(op.res); c.res_mode = op.res_mode; }
+    c.out_mode = op.out_mode;
+    c.knobs = &net->knobs; c.err = net->err_dev;
+    c.out = op.out_mode == OUT_NHWC ? TP(op.dst) : (void*)out;
+    if (skip) {
+      const PlanOp& sk = net->ops[op.skip_op];
+      c.skip_src0 = TP(sk.src0); c.skip_C0 = net->tensors[sk.src0].C;
+      c.skip_src1 = TP(sk.src1); c.skip_C1 = sk.src1 >= 0 ? net->tensors[sk.src1].C : 0;
+      c.w = W + op.wf_off; c.bias = WF(op.bf_off); c.res = nullptr; c.res_mode = RES_NONE;
+    }
+    if (op.dst >= 0 && net->tensors[op.dst].stats_cap) { c.gn_stats = SP(op.dst); c.gn_slots_cap = net->tensors[op.dst].stats_cap; }
+    if (op.dst >= 0 && op.out_mode == OUT_NHWC && op.res < 0 && oi + 2 < net->ops.size() && readers[op.dst] == 2) {
+      // statistics-type site (larger images) read by exactly one prologue conv: where the persistent kernel's tile is the whole
+      // image (16x16) it normalises its own output in place, the site's launch disappears and the consumer runs prologue-free
+      const PlanOp& g = net->ops[oi + 1];
+      if (g.kind == OP_GN && g.fin_ok && g.dst < 0 && g.src0 == op.dst && g.src1 < 0 && g.gn_site < 0) {
+        for (size_t j = oi + 2; j < net->ops.size() && j <= oi + 3; ++j) {
+          const PlanOp& cn = net->ops[j];
+          if (cn.kind == OP_CONV && cn.use_pro && cn.src0 == op.dst && cn.src1 < 0 && cn.gn_site < 0) { r.act_consumer = j; break; }
+        }
+        if (r.act_consumer) {
+          c.act_out = c.out; c.act_raw = 0; c.act_gamma = WF(g.gamma_off); c.act_beta = WF(g.beta_off);
+          if (g.film_emb_off >= 0) { c.act_film = embp + g.film_emb_off; c.act_film_stride = estride; }
+          c.act_silu = net->ops[r.act_consumer].pro_silu;
+        }
+      }
+    }
+    if (!c.act_out && op.dst >= 0 && op.out_mode == OUT_NHWC) {
+      // The apply-type GroupNorm sites (small images) that read this conv's output: the one that follows it (in_layers / out_layers norm of
+      // the next conv, unet.py:196-212) and, for a skip connection, the norm of the up path's concat (unet.py:650), whose groups are whole
+      // inside each source when both channel counts are multiples of the group width: each producer then applies its own channels.
+      for (int gi : apply_sites[op.dst]) {
+        const PlanOp& g = net->ops[gi];
+        const bool cat = g.src1 >= 0;
+        const int Cg = net->tensors[g.src0].C + (cat ? net->tensors[g.src1].C : 0);
+        const int coff = g.src0 == op.dst ? 0 : net->tensors[g.src0].C;
+        if (cat) {
+          const int cpg = Cg / 32;
+          if (!(net->knobs.gn_epilogue & 4) || g.film_emb_off >= 0 || g.src0 == g.src1 || Cg % 32 || net->tensors[g.src0].C % cpg || net->tensors[g.src1].C % cpg) continue;
+        }
+        if (!c.act_out) {
+          c.act_out = TP(g.dst); c.act_gamma = WF(g.gamma_off) + coff; c.act_beta = WF(g.beta_off) + coff;
+          if (g.film_emb_off >= 0) { c.act_film = embp + g.film_emb_off; c.act_film_stride = estride; }
+          c.act_silu = g.pro_silu; c.act_stride = Cg; c.act_coff = coff; c.act_cpg = Cg / 32;
+          if (!cat || coff == 0) warm_next(g, c.warm, c.warm_bytes, 1);
+          r.fused_site[0] = gi;
+        } else if (!c.act2_out && g.film_emb_off < 0) {
+          c.act2_out = TP(g.dst); c.act2_gamma = WF(g.gamma_off) + coff; c.act2_beta = WF(g.beta_off) + coff;
+          c.act2_silu = g.pro_silu; c.act2_stride = Cg; c.act2_coff = coff; c.act2_cpg = Cg / 32;
+          r.fused_site[1] = gi;
+        }
+      }
+      // the raw tensor is written unless the one site asked for is its only reader (with two sites asked for the launch may still take one)
+      if (c.act_out) c.act_raw = c.act2_out ? 1 : readers[op.dst] > 1;
+    }
+    return r;
+  };
+  bool in_direct = false;
+  for (size_t j = 0; j < net->ops.size(); ++j) {
+    if (net->ops[j].kind != OP_CONV || net->ops[j].src0 != net->in_tensor) continue;
+    ConvRoute rt;
+    in_direct = conv_route(conv_op(j, false).c, &rt) == 0 && rt.reads_nchw;
+    break;
+  }
+  if (in_direct) { if ((size_t)net->in_tensor < net->tensor_state_n) net->tensor_state[net->in_tensor].store((char)1, std::memory_order_relaxed); }
+  else if ((rc = pack_nhwc_launch(dtype, x, Cx, cond, cond ? Cc : 0, B, S * S, net->in_pad, TP(net->in_tensor), stream))) return rc;
+  { mi355_op_profile r{}; r.kind = MI355_OP_PRELUDE; mark(r); }
   for (const PlanOp& op : net->ops) {
     mi355_op_profile r{};
     const PlanTensor& s0 = net->tensors[op.src0];
@@ -654,15 +726,9 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
       r.kind = MI355_OP_GN; r.cin = s0.C + C1; r.h = s0.H; r.w = s0.W;
       r.bytes = (double)B * s0.H * s0.W * (s0.C + C1) * esz * (op.dst >= 0 ? 2 : 1);
     } else if (op.kind == OP_CONV && op.carrier >= 0 && [&]() {
-                 // 1x1 skip_connection of a small-level ResBlock: does the second conv's launch take it along?  (same description as below,
-                 // as far as eligibility looks: shapes, batch, precision, knobs)
-                 const PlanOp& c2 = net->ops[op.carrier];
-                 const PlanTensor& y2 = net->tensors[c2.src0];
-                 ConvDesc c; c.dtype = dtype; c.src0 = TP(c2.src0); c.C0 = y2.C; c.N = B; c.Hs = y2.H; c.Ws = y2.W; c.mode = c2.mode; c.ks = c2.ks;
-                 c.wsplit = net->wsplit; c.w = W + c2.wf_off; c.bias = WF(c2.bf_off); c.Cout = c2.Cout; c.out_mode = c2.out_mode; c.out = TP(c2.dst);
-                 c.knobs = &net->knobs; c.err = net->err_dev;
-                 c.skip_src0 = TP(op.src0); c.skip_C0 = s0.C; c.skip_src1 = TP(op.src1); c.skip_C1 = C1;
-                 return conv_fused_skip_ok(c) == 0;
+                 // 1x1 skip_connection of a small-level ResBlock: does the second conv's launch take it along?
+                 ConvRoute rt;
+                 return conv_route(conv_op((size_t)op.carrier, true).c, &rt) == 0;
                }()) {
       skip_fused[op.carrier] = 1;   // nothing to launch: the tensor is never written
       gn_done[(size_t)(&op - net->ops.data())] = 1;   // (counts as a launch that did not happen)
@@ -670,97 +736,24 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
       rc = 0;
       r.kind = MI355_OP_CONV; r.ks = op.ks; r.cin = s0.C + C1; r.cout = op.Cout; r.h = s0.H; r.w = s0.W; r.tile_m = r.tile_n = -1;
     } else if (op.kind == OP_CONV) {
-      ConvDesc c; c.dtype = dtype; c.src0 = TP(op.src0); c.C0 = s0.C; c.src1 = TP(op.src1); c.C1 = C1;
-      c.N = B; c.Hs = s0.H; c.Ws = s0.W; c.mode = op.mode; c.ks = op.ks; c.wsplit = net->wsplit;
       const size_t oi = (size_t)(&op - net->ops.data());
-      if (op.use_pro && !pro_off[oi]) { c.pro_a = F(l.gna); c.pro_b = F(l.gnb); c.pro_silu = op.pro_silu; }
-      if (op.use_pro && !pro_off[oi] && op.gn_site >= 0) {
-        float* sp = F(l.sites) + net->site_off[op.gn_site] * (size_t)B;
-        c.pro_a = sp; c.pro_b = sp + (size_t)B * net->site_C[op.gn_site];
-      }
-      c.w = W + op.w_off; c.bias = WF(op.bias_off); c.Cout = op.Cout;
-      if (op.src0 == net->in_tensor) {
-        c.cin_real = net->cfg.in_channels;
-        if (in_direct) { c.nchw0 = x; c.nchw_c0 = Cx; c.nchw1 = cond; c.nchw_c1 = cond ? Cc : 0; }
-      }
-      if (op.out_mode == OUT_NCHW_F32 && run.euler_x) { c.axpy_x = run.euler_x; c.axpy_scale = run.euler_dt; c.axpy_done = &euler_done; }
-      if (op.emb_off >= 0) { c.emb = embp + op.emb_off; c.emb_stride = estride; }
-      if (op.res >= 0) { c.res = TP(op.res); c.res_mode = op.res_mode; }
-      c.out_mode = op.out_mode;
-      c.knobs = &net->knobs; c.err = net->err_dev;
-      c.out = op.out_mode == OUT_NHWC ? TP(op.dst) : (void*)out;
-      if (skip_fused[oi]) {   // the ResBlock's 1x1 skip conv rides in this launch (its op was skipped above)
-        const PlanOp& sk = net->ops[op.skip_op];
-        c.skip_src0 = TP(sk.src0); c.skip_C0 = net->tensors[sk.src0].C;
-        c.skip_src1 = TP(sk.src1); c.skip_C1 = sk.src1 >= 0 ? net->tensors[sk.src1].C : 0;
-        c.w = W + op.wf_off; c.bias = WF(op.bf_off); c.res = nullptr; c.res_mode = RES_NONE;
-      }
-      int slots = 0, act_done = 0;
-      if (op.dst >= 0 && net->tensors[op.dst].stats_cap) { c.gn_stats = SP(op.dst); c.gn_slots_cap = net->tensors[op.dst].stats_cap; }
-      bool try_act = false;
-      size_t act_consumer = 0;
-      if (op.dst >= 0 && op.out_mode == OUT_NHWC && op.res < 0 && oi + 2 < net->ops.size() && readers[op.dst] == 2) {
-        // statistics-type site (larger images) read by exactly one prologue conv: where the persistent kernel's tile is the whole
-        // image (16x16) it normalises its own output in place, the site's launch disappears and the consumer runs prologue-free
-        const PlanOp& g = net->ops[oi + 1];
-        if (g.kind == OP_GN && g.fin_ok && g.dst < 0 && g.src0 == op.dst && g.src1 < 0 && g.gn_site < 0) {
-          for (size_t j = oi + 2; j < net->ops.size() && j <= oi + 3; ++j) {
-            const PlanOp& cn = net->ops[j];
-            if (cn.kind == OP_CONV && cn.use_pro && cn.src0 == op.dst && cn.src1 < 0 && cn.gn_site < 0) { act_consumer = j; break; }
-          }
-          if (act_consumer) {
-            c.act_out = c.out; c.act_raw = 0; c.act_gamma = WF(g.gamma_off); c.act_beta = WF(g.beta_off);
-            if (g.film_emb_off >= 0) { c.act_film = embp + g.film_emb_off; c.act_film_stride = estride; }
-            c.act_silu = net->ops[act_consumer].pro_silu;
-            try_act = true;
-          }
-        }
-      }
-      int fused_site[2] = {-1, -1};
-      if (!try_act && op.dst >= 0 && op.out_mode == OUT_NHWC) {
-        // The apply-type GroupNorm sites (small images) that read this conv's output: the one that follows it (in_layers / out_layers norm of
-        // the next conv, unet.py:196-212) and, for a skip connection, the norm of the up path's concat (unet.py:650), whose groups are whole
-        // inside each source when both channel counts are multiples of the group width: each producer then applies its own channels.
-        for (int gi : apply_sites[op.dst]) {
-          const PlanOp& g = net->ops[gi];
-          const bool cat = g.src1 >= 0;
-          const int Cg = net->tensors[g.src0].C + (cat ? net->tensors[g.src1].C : 0);
-          const int coff = g.src0 == op.dst ? 0 : net->tensors[g.src0].C;
-          if (cat) {
-            const int cpg = Cg / 32;
-            if (!(net->knobs.gn_epilogue & 4) || g.film_emb_off >= 0 || g.src0 == g.src1 || Cg % 32 || net->tensors[g.src0].C % cpg || net->tensors[g.src1].C % cpg) continue;
-          }
-          if (!c.act_out) {
-            c.act_out = TP(g.dst); c.act_gamma = WF(g.gamma_off) + coff; c.act_beta = WF(g.beta_off) + coff;
-            if (g.film_emb_off >= 0) { c.act_film = embp + g.film_emb_off; c.act_film_stride = estride; }
-            c.act_silu = g.pro_silu; c.act_stride = Cg; c.act_coff = coff; c.act_cpg = Cg / 32;
-            if (!cat || coff == 0) warm_next(g, c.warm, c.warm_bytes, 1);
-            fused_site[0] = gi;
-          } else if (!c.act2_out && g.film_emb_off < 0) {
-            c.act2_out = TP(g.dst); c.act2_gamma = WF(g.gamma_off) + coff; c.act2_beta = WF(g.beta_off) + coff;
-            c.act2_silu = g.pro_silu; c.act2_stride = Cg; c.act2_coff = coff; c.act2_cpg = Cg / 32;
-            fused_site[1] = gi;
-          }
-        }
-        if (c.act_out) {
-          // the raw tensor is written unless the one site asked for is its only reader (with two sites asked for the launch may still take one)
-          c.act_raw = c.act2_out ? 1 : readers[op.dst] > 1;
-          try_act = true;
-        }
-      }
-      rc = conv_launch(c, stream, &slots, try_act ? &act_done : nullptr);
-      if (act_done && act_consumer) { gn_done[oi + 1] = 1; pro_off[act_consumer] = 1; }
-      else if (act_done) {
+      const ConvOp co = conv_op(oi, skip_fused[oi]);   // (skip_fused: the ResBlock's 1x1 skip conv rides in this launch, its op was skipped above)
+      const ConvDesc& c = co.c;
+      ConvRoute rt;
+      if ((rc = conv_route(c, &rt)) || (rc = conv_launch(c, rt, stream))) return rc;
+      if (rt.act_done && co.act_consumer) { gn_done[oi + 1] = 1; pro_off[co.act_consumer] = 1; }
+      else if (rt.act_done) {
         for (int k = 0; k < 2; ++k) {
-          if (!(act_done & (1 << k)) || fused_site[k] < 0) continue;
-          const PlanOp& g = net->ops[fused_site[k]];
-          if (++site_parts[fused_site[k]] == (g.src1 >= 0 ? 2 : 1)) gn_done[fused_site[k]] = 1;
+          if (!(rt.act_done & (1 << k)) || co.fused_site[k] < 0) continue;
+          const PlanOp& g = net->ops[co.fused_site[k]];
+          if (++site_parts[co.fused_site[k]] == (g.src1 >= 0 ? 2 : 1)) gn_done[co.fused_site[k]] = 1;
         }
       }
-      if (op.dst >= 0 && (size_t)op.dst < net->tensor_state_n) net->tensor_state[op.dst].store((char)(!act_done ? 0 : (act_consumer ? 2 : (c.act_raw ? 0 : 1))), std::memory_order_relaxed);
-      if (op.dst >= 0) gn_slots[op.dst] = slots;
+      if (rt.axpy) euler_done = 1;
+      if (op.dst >= 0 && (size_t)op.dst < net->tensor_state_n) net->tensor_state[op.dst].store((char)(!rt.act_done ? 0 : (co.act_consumer ? 2 : (c.act_raw ? 0 : 1))), std::memory_order_relaxed);
+      if (op.dst >= 0) gn_slots[op.dst] = rt.gn_slots;
       if (run.prof) {
-        const ConvGeom cg = conv_geometry(c);
+        const ConvGeom& cg = rt.geom;
         const int cin = s0.C + C1;
         r.kind = MI355_OP_CONV; r.ks = op.ks; r.cin = cin; r.cout = op.Cout; r.h = cg.Ho; r.w = cg.Wo; r.tile_m = cg.BM; r.tile_n = cg.BN;
         r.flops = 2.0 * B * cg.Ho * cg.Wo * (double)op.Cout * cin * op.ks * op.ks;

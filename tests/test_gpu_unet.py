@@ -496,6 +496,36 @@ def test_first_conv_kernel_in_network_feeds_groupnorm_partial_sums():
 
 
 @pytest.mark.gpu
+def test_first_conv_feeding_an_apply_site_bf16():
+    """bf16 forward with gn_apply_max_hw raised to 32x32: the first conv's output then feeds an apply-type GroupNorm site, which its
+    description asks the conv to apply, so the first-conv kernel (and with it the direct read of the fp32 NCHW input) is not taken.  The
+    forward runs and agrees with the default bf16 forward."""
+    from image_diffusion.unet import UNetModel, param_shapes
+    from mi355._lib import debug_config
+
+    kw = dict(image_size=32, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=1, attention_resolutions=(2,),
+              channel_mult=(1, 2, 2), num_heads=4, num_head_channels=64)
+    B = 72
+    x = randn(4500, B, 3, 32, 32).to(DEV)
+    t = torch.linspace(0, 1, B).to(DEV)
+    sd = None
+    outs = []
+    for knobs in (dict(), dict(gn_apply_max_hw=4096)):
+        net = UNetModel(precision="bf16", **kw)
+        if sd is None:
+            sd = synth_state_dict(param_shapes(net), 4501)
+        net.load_state_dict(sd)
+        net.debug = debug_config(**knobs)
+        net.to(DEV)
+        e = net.engine(DEV)
+        outs.append(e.forward(x, t).float().cpu())
+        torch.cuda.synchronize(); e.check()
+    scale = outs[0].pow(2).mean().sqrt().item()
+    d = (outs[1] - outs[0]).pow(2).mean().sqrt().item()
+    assert d < 1.5e-2 * scale, (d, scale)   # two bf16 roundings of one forward; a wrong normalisation would be O(1)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("shape", ["c256_heads4", "c128_heads2"])
 def test_attention_block_persistent_kernel_matches_per_image_kernel(shape):
     """AttentionBlock front half (norm -> qkv -> attention, AD/image_diffusion/unet.py:395-401, :433-448) in bf16 mode at 256 tokens:
