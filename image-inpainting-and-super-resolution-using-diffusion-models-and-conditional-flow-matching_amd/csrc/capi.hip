@@ -102,6 +102,23 @@ int mi355_unet_forward_t(mi355_unet* net, const float* x, int x_channels, const 
   return unet_forward(net, x, x_channels, cond, cond_channels, tdev, out, batch, workspace, workspace_bytes, S(stream), uniform_t_run());
 }
 
+int mi355_unet_forward_labels(mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, const float* t, float t_host,
+                              const int32_t* labels, float* out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && workspace && batch > 0, -1, "unet_forward_labels: bad argument");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "unet_forward_labels: class labels given to a net built without num_classes");
+  UnetRun run;
+  run.labels = labels;
+  if (!t) {   // one host time for the batch: staged as in mi355_unet_forward_t
+    const WsLayout l = unet_ws_layout(net, batch);
+    MI355_REQUIRE((int64_t)l.total <= workspace_bytes, -2, "unet_forward_labels: workspace too small");
+    float* tdev = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + l.emb2);
+    if (int rc = fill_launch(tdev, t_host, 1, S(stream))) return rc;
+    t = tdev;
+    run.t_uniform = 1;
+  }
+  return unet_forward(net, x, x_channels, cond, cond_channels, t, out, batch, workspace, workspace_bytes, S(stream), run);
+}
+
 int mi355_unet_vjp(mi355_unet* net, const float* grad_out, float* grad_x, int x_channels, int batch, void* workspace, int64_t workspace_bytes,
                    void* stream) {
   MI355_REQUIRE(net && workspace, -1, "unet_vjp: null argument");
@@ -193,13 +210,17 @@ int mi355_unet_profile(mi355_unet* net, const float* x, int x_channels, const fl
 struct Scratch { float* t; float* v; float* none; float* tsteps; float* embtab; float* xstate; char* unet_ws; int64_t unet_bytes; };
 // every image of a sampler step shares the step time: the engine computes ONE embedding row (stride-0 broadcast)
 static UnetRun uniform_t_run() { UnetRun r; r.t_uniform = 1; return r; }
-// table[k] = emb_layers outputs for step time t_host[k] (k < n <= EMB_TABLE_STEPS); returns the table or null (per-step path)
-static int make_emb_table(const mi355_unet* net, const Scratch& sc, const float* t_host, int n, hipStream_t s, const float** table) {
+// table[k] = emb_layers outputs for step time t_host[k] (k < n <= EMB_TABLE_STEPS); returns the table or null (per-step path).
+// labelled (class-conditional sampling): table[k * K + c] = the rows of step k and class c, for n * K <= EMB_TABLE_STEPS rows
+// (three time launches over n rows, one label_emb_linear over n * K); the steps gather their images' rows from it.
+static int make_emb_table(const mi355_unet* net, const Scratch& sc, const float* t_host, int n, bool labelled, hipStream_t s, const float** table) {
   *table = nullptr;
-  if (n <= 0 || n > EMB_TABLE_STEPS) return 0;
+  const int K = labelled ? net->num_classes : 1;
+  if (n <= 0 || (int64_t)n * K > EMB_TABLE_STEPS) return 0;
   MI355_CHECK_HIP(hipMemcpyAsync(sc.tsteps, t_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
   float* scratch = sc.embtab + (size_t)EMB_TABLE_STEPS * net->emb_total;
-  if (int rc = unet_embedding_table(net, sc.tsteps, n, sc.embtab, scratch, s)) return rc;
+  if (int rc = labelled ? unet_embedding_rows_labels(net, sc.tsteps, n, nullptr, n * K, K, sc.embtab, scratch, s)
+                        : unet_embedding_table(net, sc.tsteps, n, sc.embtab, scratch, s)) return rc;
   *table = sc.embtab;
   return 0;
 }
@@ -221,13 +242,17 @@ static int carve(mi355_unet* net, int B, void* workspace, int64_t workspace_byte
 }
 
 // The loop proper: every launch of every step on stream s (the caller's stream, or the handle's capture stream while a graph is recorded).
+// labels: class-conditional steps (with a table: step k's block of the (step, class) table, one gather launch per step).
 static int cfm_euler_loop(mi355_unet* net, const Scratch& sc, float* x, int x_channels, const float* cond, int cond_channels, float* cdrift,
-                          const float* t_span_host, int n_t, const float* emb_table, float* traj, int batch, int64_t n, int64_t nc, hipStream_t s) {
+                          const float* t_span_host, int n_t, const float* emb_table, float* traj, int batch, int64_t n, int64_t nc, hipStream_t s,
+                          const int32_t* labels = nullptr) {
   UnetRun run = uniform_t_run();
+  run.labels = labels;
+  const size_t block = (size_t)(labels ? net->num_classes : 1) * net->emb_total;
   for (int k = 0; k + 1 < n_t; ++k) {
     const float t = t_span_host[k], dt = t_span_host[k + 1] - t_span_host[k];
     int rc;
-    if (emb_table) run.emb_row = emb_table + (size_t)k * net->emb_total;
+    if (emb_table) run.emb_row = emb_table + (size_t)k * block;
     else if ((rc = fill_launch(sc.t, t, batch, s))) return rc;
     run.euler_x = x; run.euler_dt = dt;   // x += dt * v: in the last conv's epilogue, or as a launch of unet_forward's own behind it
     if ((rc = unet_forward(net, x, x_channels, cond, cond_channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
@@ -287,13 +312,21 @@ static int cfm_euler_graph(mi355_unet* net, const Scratch& sc, float* x, int x_c
 int mi355_cfm_euler_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
                            const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch, void* workspace,
                            int64_t workspace_bytes, void* stream) {
+  return mi355_cfm_euler_sample_labels(net, x, x_channels, cond, cond_channels, cond_drift, nullptr, t_span_host, n_t, traj, u8_out, batch,
+                                       workspace, workspace_bytes, stream);
+}
+
+int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
+                                  const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(net && x && t_span_host && n_t >= 1, -1, "cfm_euler_sample: bad argument");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_euler_sample: class labels given to a net built without num_classes");
   MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_euler_sample: the vector field must have the state's channel count");
   Scratch sc;
   if (int rc = carve(net, batch, workspace, workspace_bytes, sc)) return rc;
   hipStream_t s = S(stream);
   const float* emb_table = nullptr;
-  if (int rc = make_emb_table(net, sc, t_span_host, n_t - 1, s, &emb_table)) return rc;
+  if (int rc = make_emb_table(net, sc, t_span_host, n_t - 1, labels != nullptr, s, &emb_table)) return rc;
   const int64_t n = (int64_t)batch * x_channels * net->cfg.image_size * net->cfg.image_size;
   const int64_t nc = (int64_t)batch * cond_channels * net->cfg.image_size * net->cfg.image_size;
   if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
@@ -308,10 +341,10 @@ int mi355_cfm_euler_sample(mi355_unet* net, float* x, int x_channels, const floa
     cond = cdrift;
   }
   int rc;
-  if (net->knobs.sampler_graph && emb_table && !traj && !cdrift && n_t > 1)
+  if (net->knobs.sampler_graph && emb_table && !traj && !cdrift && !labels && n_t > 1)
     rc = cfm_euler_graph(net, sc, x, x_channels, cond, cond_channels, t_span_host, n_t, emb_table, batch, n, workspace, s);
   else
-    rc = cfm_euler_loop(net, sc, x, x_channels, cond, cond_channels, cdrift, t_span_host, n_t, emb_table, traj, batch, n, nc, s);
+    rc = cfm_euler_loop(net, sc, x, x_channels, cond, cond_channels, cdrift, t_span_host, n_t, emb_table, traj, batch, n, nc, s, labels);
   if (rc) return rc;
   if (u8_out) return quantize_u8_launch(x, u8_out, n, s);
   return 0;
@@ -338,7 +371,7 @@ int mi355_ddpm_sample(mi355_unet* net, float* x, int channels, const float* cond
   if (Ns <= EMB_TABLE_STEPS) {
     std::vector<float> th((size_t)Ns);
     for (int i = 0; i < Ns; ++i) th[i] = (float)i / (float)Ns;
-    if ((rc = make_emb_table(net, sc, th.data(), Ns, s, &emb_table))) return rc;
+    if ((rc = make_emb_table(net, sc, th.data(), Ns, false, s, &emb_table))) return rc;
     MI355_CHECK_HIP(hipStreamSynchronize(s));   // `th` is a temporary host buffer (once per sample() call)
   }
   if (amortized && (rc = fill_launch(sc.none, opt->none_value, n, s))) return rc;

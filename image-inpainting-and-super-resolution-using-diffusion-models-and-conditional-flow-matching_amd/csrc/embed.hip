@@ -4,6 +4,7 @@
 // (unet.py:564-569: Linear, SiLU, Linear) and every ResBlock's emb_layers (unet.py:297-305: SiLU,
 // Linear) - the latter are batched into ONE linear over the concatenated output channels of all
 // ResBlocks per forward.  All fp32 (the reference forces fp32 here, nn.py:111).
+// Class-conditional nets add label_emb(y) to the time embedding before that SiLU (label_emb_linear_kernel, emb_gather_kernel).
 #include "ops.h"
 
 namespace {
@@ -24,9 +25,41 @@ __global__ void timestep_embedding_kernel(const float* t, int B, int dim, float 
   out[idx] = v;
 }
 
-// out[b][j] = bias[j] + sum_k act(in[b][k]) * Wt[k][j].  One thread per (j, 8-row batch slab): the 8 input rows
+// out[b][j] = bias[j] + sum_k act(in[b][k]) * Wt[k][j].  One thread per (j, LR-row batch slab): the LR input rows
 // are staged in LDS (broadcast reads), Wt reads are coalesced across lanes, 4 independent loads in flight.
 constexpr int LB = 8;
+template <int LR>
+__device__ __forceinline__ void linear_rows(const float* xin, const float* __restrict__ Wt, const float* __restrict__ bias,
+                                            float* __restrict__ out, int b0, int B, int K, int J, int j, int out_act) {
+  float acc[LR];
+#pragma unroll
+  for (int r = 0; r < LR; ++r) acc[r] = 0.f;
+  int k = 0;
+  for (; k + 4 <= K; k += 4) {
+    const float w0 = Wt[(size_t)k * J + j], w1 = Wt[(size_t)(k + 1) * J + j];
+    const float w2 = Wt[(size_t)(k + 2) * J + j], w3 = Wt[(size_t)(k + 3) * J + j];
+#pragma unroll
+    for (int r = 0; r < LR; ++r) {
+      const f32x4 x = *reinterpret_cast<const f32x4*>(xin + r * K + k);
+      acc[r] = fmaf(x[3], w3, fmaf(x[2], w2, fmaf(x[1], w1, fmaf(x[0], w0, acc[r]))));
+    }
+  }
+  for (; k < K; ++k) {
+    const float w = Wt[(size_t)k * J + j];
+#pragma unroll
+    for (int r = 0; r < LR; ++r) acc[r] = fmaf(xin[r * K + k], w, acc[r]);
+  }
+  const float bj = bias ? bias[j] : 0.f;
+#pragma unroll
+  for (int r = 0; r < LR; ++r) {
+    const int b = b0 + r;
+    if (b < B) {
+      float v = acc[r] + bj;
+      out[(size_t)b * J + j] = out_act ? silu_f<false>(v) : v;
+    }
+  }
+}
+
 __global__ void __launch_bounds__(128) linear_kernel(const float* __restrict__ in, const float* __restrict__ Wt,
                                                      const float* __restrict__ bias, float* __restrict__ out, int B, int K, int J,
                                                      int in_act, int out_act) {
@@ -40,33 +73,65 @@ __global__ void __launch_bounds__(128) linear_kernel(const float* __restrict__ i
   }
   __syncthreads();
   if (j >= J) return;
-  float acc[LB];
-#pragma unroll
-  for (int r = 0; r < LB; ++r) acc[r] = 0.f;
-  int k = 0;
-  for (; k + 4 <= K; k += 4) {
-    const float w0 = Wt[(size_t)k * J + j], w1 = Wt[(size_t)(k + 1) * J + j];
-    const float w2 = Wt[(size_t)(k + 2) * J + j], w3 = Wt[(size_t)(k + 3) * J + j];
-#pragma unroll
-    for (int r = 0; r < LB; ++r) {
-      const f32x4 x = *reinterpret_cast<const f32x4*>(xin + r * K + k);
-      acc[r] = fmaf(x[3], w3, fmaf(x[2], w2, fmaf(x[1], w1, fmaf(x[0], w0, acc[r]))));
+  linear_rows<LB>(xin, Wt, bias, out, b0, B, K, J, j, out_act);
+}
+
+// The error word of a handle is pinned host memory: a plain system-scope store (no read-modify-write over the bus); 2 = bad class label
+__device__ __forceinline__ void flag_label_error(uint32_t* err) {
+  if (err) __hip_atomic_store(err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Class-conditional emb_layers: the linear_kernel contraction with a fused prologue that stages row r as
+// silu(h[r / h_div] + label_emb[lab(r)]) - the time embedding (time_embed output, before the SiLU every emb_layers opens with) plus the
+// label's embedding row, then that SiLU.  h_div = rows per time row (B for one shared step time, K for the sampler's (step, class) table).
+template <int LR>
+__global__ void __launch_bounds__(128) label_emb_linear_kernel(const float* __restrict__ h, int h_div, const float* __restrict__ lemb,
+                                                               const int32_t* __restrict__ labels, int n_classes, const float* __restrict__ Wt,
+                                                               const float* __restrict__ bias, float* __restrict__ out, int R, int K, int J,
+                                                               uint32_t* err) {
+  extern __shared__ float xin[];  // [LR][K]
+  __shared__ int lab_s[LR];
+  const int j = blockIdx.x * 128 + threadIdx.x;
+  const int r0 = blockIdx.y * LR;
+  if (threadIdx.x < LR) {
+    const int r = r0 + threadIdx.x;
+    int lab = -1;
+    if (r < R) {
+      lab = labels ? labels[r] : r % n_classes;
+      if (lab < 0 || lab >= n_classes) {   // never read outside label_emb: the label term is zero, the handle is told
+        if (blockIdx.x == 0) flag_label_error(err);
+        lab = -1;
+      }
     }
+    lab_s[threadIdx.x] = lab;
   }
-  for (; k < K; ++k) {
-    const float w = Wt[(size_t)k * J + j];
-#pragma unroll
-    for (int r = 0; r < LB; ++r) acc[r] = fmaf(xin[r * K + k], w, acc[r]);
-  }
-  const float bj = bias ? bias[j] : 0.f;
-#pragma unroll
-  for (int r = 0; r < LB; ++r) {
-    const int b = b0 + r;
-    if (b < B) {
-      float v = acc[r] + bj;
-      out[(size_t)b * J + j] = out_act ? silu_f<false>(v) : v;
+  __syncthreads();
+  for (int i = threadIdx.x; i < LR * K; i += 128) {
+    const int rr = i / K, k = i - rr * K;
+    const int r = r0 + rr;
+    float x = 0.f;
+    if (r < R) {
+      const int lab = lab_s[rr];
+      x = silu_f<false>(h[(size_t)(r / h_div) * K + k] + (lab >= 0 ? lemb[(size_t)lab * K + k] : 0.f));
     }
+    xin[i] = x;
   }
+  __syncthreads();
+  if (j >= J) return;
+  linear_rows<LR>(xin, Wt, bias, out, r0, R, K, J, j, 0);
+}
+
+// out[b] = table[labels[b]]: one thread per 16-byte quad of a row (a row's quads are adjacent threads: full-line loads and stores)
+__global__ void __launch_bounds__(256) emb_gather_kernel(const float* __restrict__ table, const int32_t* __restrict__ labels, int n_classes,
+                                                         float* __restrict__ out, int B, int J4, uint32_t* err) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)B * J4) return;
+  const int b = (int)(idx / J4), q = (int)(idx - (size_t)b * J4);
+  const int lab = labels[b];
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (lab >= 0 && lab < n_classes) v = *reinterpret_cast<const f32x4*>(table + ((size_t)lab * J4 + q) * 4);
+  else if (q == 0) flag_label_error(err);
+  *reinterpret_cast<f32x4*>(out + idx * 4) = v;
 }
 
 // Small-batch form (the sampler loops share one step time, so B = 1): a GEMV is latency-bound, so the K range is split
@@ -186,6 +251,31 @@ int linear_launch(const float* in, const float* Wt, const float* bias, float* ou
   dim3 grid((J + 127) / 128, (B + LB - 1) / LB);
   MI355_REQUIRE(K % 4 == 0 && (size_t)LB * K * 4 <= 64 * 1024, -4, "linear: K must be a multiple of 4 and <= 2048");
   hipLaunchKernelGGL(linear_kernel, grid, dim3(128), (size_t)LB * K * 4, s, in, Wt, bias, out, B, K, J, in_act, out_act);
+  MI355_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int label_emb_linear_launch(const float* h, int h_div, const float* lemb, const int32_t* labels, int n_classes, const float* Wt,
+                            const float* bias, float* out, int R, int K, int J, uint32_t* err, hipStream_t s) {
+  MI355_REQUIRE(R > 0 && h_div > 0 && n_classes > 0, -1, "label_emb_linear: bad sizes");
+  MI355_REQUIRE(K % 4 == 0 && (size_t)LB * K * 4 <= 64 * 1024, -4, "label_emb_linear: K must be a multiple of 4 and <= 2048");
+  // 16-row slabs halve the weight re-reads of the per-step form (B rows) where they fit the LDS budget of linear_kernel
+  if ((size_t)16 * K * 4 <= 64 * 1024) {
+    hipLaunchKernelGGL(label_emb_linear_kernel<16>, dim3((J + 127) / 128, (R + 15) / 16), dim3(128), (size_t)16 * K * 4, s, h, h_div, lemb,
+                       labels, n_classes, Wt, bias, out, R, K, J, err);
+  } else {
+    hipLaunchKernelGGL(label_emb_linear_kernel<LB>, dim3((J + 127) / 128, (R + LB - 1) / LB), dim3(128), (size_t)LB * K * 4, s, h, h_div, lemb,
+                       labels, n_classes, Wt, bias, out, R, K, J, err);
+  }
+  MI355_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int emb_gather_launch(const float* table, const int32_t* labels, int n_classes, float* out, int B, int J, uint32_t* err, hipStream_t s) {
+  MI355_REQUIRE(table && labels && out && B > 0 && n_classes > 0, -1, "emb_gather: bad argument");
+  MI355_REQUIRE(J % 4 == 0 && (reinterpret_cast<uintptr_t>(table) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0, -2,
+                "emb_gather: rows must be whole 16-byte vectors");
+  hipLaunchKernelGGL(emb_gather_kernel, grid1d((size_t)B * (J / 4), 256), dim3(256), 0, s, table, labels, n_classes, out, B, J / 4, err);
   MI355_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -61,6 +61,7 @@ struct mi355_unet {
   // fp32 side tables in the weight blob
   size_t te_w0 = 0, te_b0 = 0, te_w2 = 0, te_b2 = 0, emb_w = 0, emb_b = 0;
   int emb_total = 0;   // concatenated emb_layers output channels of all ResBlocks
+  int num_classes = 0; size_t label_w = 0;   // class-conditional nets: label_emb.weight, fp32 [num_classes][4 mc]
   int in_pad = 0;      // first conv's padded input channels
   int max_gn_c = 0;
   size_t act_elems_per_image = 0;  // activation arena (elements of T) per image
@@ -100,6 +101,10 @@ struct UnetRun {
   // sampler loops (flow-matching Euler): x += euler_dt * (network output) in the last conv's epilogue where that conv runs on the streaming kernel
   // (the output tensor is then not written); else unet_forward adds the step launch itself.  euler_x may be the network input x.
   float* euler_x = nullptr; float euler_dt = 0.f;
+  // class-conditional nets: device int32[B] labels (emb = time_embed(.) + label_emb(labels)): every image gets its own embedding row.  With
+  // emb_row set, emb_row is this step's block of a (step, class) table [num_classes][emb_total] and the images' rows are gathered from it
+  // (one launch); without, the rows are computed from t and the labels (unet_embedding_rows_labels, the usual four launches)
+  const int32_t* labels = nullptr;
   // optional per-op profiling (mi355_unet_profile)
   std::vector<mi355_op_profile>* prof = nullptr;
   std::vector<hipEvent_t>* prof_events = nullptr;
@@ -118,5 +123,9 @@ int unet_backward(const mi355_unet* net, const float* grad_out, float* grad_x, i
 // All emb_layers outputs (UNetModel.time_embed + every ResBlock's emb_layers, unet.py:564-569,293-299) for n step times at once:
 // table [n][emb_total] fp32; scratch = n * 9 * model_channels floats.  The sampler loops know every step time in advance.
 int unet_embedding_table(const mi355_unet* net, const float* t_dev, int n, float* table, float* scratch, hipStream_t stream);
+// Class-conditional form: h = time_embed(timestep_embedding(t)) (before the SiLU) for n_t times, then rows r < R of
+// table = emb_layers(silu(h[r / h_div] + label_emb[lab(r)])), lab(r) = labels ? labels[r] : r % num_classes.  scratch = n_t * 9 * mc floats.
+int unet_embedding_rows_labels(const mi355_unet* net, const float* t_dev, int n_t, const int32_t* labels, int R, int h_div, float* table,
+                               float* scratch, hipStream_t stream);
 int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* cond, int Cc, const float* t, float* out, int batch,
                  void* workspace, int64_t workspace_bytes, hipStream_t stream, const UnetRun& run = UnetRun());

@@ -277,6 +277,10 @@ struct Walker {
     net->te_b0 = put_f32("time_embed.0.bias", {4 * mc});
     net->te_w2 = put_linear_t("time_embed.2.weight", 4 * mc, 4 * mc);
     net->te_b2 = put_f32("time_embed.2.bias", {4 * mc});
+    if (cfg.num_classes > 0) {   // UNetModel.label_emb (unet.py:571-572): nn.Embedding(num_classes, 4 mc), rows as they are
+      net->num_classes = cfg.num_classes;
+      net->label_w = put_f32("label_emb.weight", {cfg.num_classes, 4 * mc});
+    }
     int ch = cfg.channel_mult[0] * mc;
     const int input_ch = ch;
     net->in_tensor = tensor(net->in_pad, S, S);
@@ -361,6 +365,7 @@ int check_cfg(const mi355_unet_config& c) {
   MI355_REQUIRE(c.model_channels % 32 == 0 && c.model_channels > 0, -4, "unet: model_channels must be a multiple of 32 (GroupNorm32 + 64-byte channel chunks)");
   MI355_REQUIRE(c.in_channels > 0 && c.in_channels <= 32 && c.out_channels > 0 && c.out_channels <= 32, -4, "unet: in/out channels must be in 1..32");
   MI355_REQUIRE(c.image_size > 0 && c.num_res_blocks > 0, -1, "unet: bad sizes");
+  MI355_REQUIRE(c.num_classes >= 0, -1, "unet: num_classes must be >= 0 (0: no label embedding)");
   return 0;
 }
 
@@ -389,6 +394,7 @@ int unet_enumerate_params(const mi355_unet_config& cfg, std::vector<ParamInfo>& 
   auto has_attn = [&](int ds) { for (int i = 0; i < cfg.n_attention_ds; ++i) if (cfg.attention_ds[i] == ds) return true; return false; };
   add("time_embed.0.weight", {E, mc}); add("time_embed.0.bias", {E});
   add("time_embed.2.weight", {E, E}); add("time_embed.2.bias", {E});
+  if (cfg.num_classes > 0) add("label_emb.weight", {cfg.num_classes, E});
   int ch = cfg.channel_mult[0] * mc;
   const int input_ch = ch;
   conv("input_blocks.0.0", ch, cfg.in_channels, 3);
@@ -497,6 +503,11 @@ int unet_status(const mi355_unet* net, int clear) {
   const uint32_t v = *reinterpret_cast<volatile uint32_t*>(net->err_host);
   if (clear) *reinterpret_cast<volatile uint32_t*>(net->err_host) = 0u;
   if (v == 0u) return 0;
+  if (!(v & 1u)) {   // bit 1 alone: a label kernel met a class label outside [0, num_classes)
+    mi355_set_error("a launch of this handle was given a class label outside [0, num_classes) (labels of mi355_unet_forward_labels / "
+                    "mi355_cfm_euler_sample_labels): that image's label term was taken as zero, its output is invalid [error word " + std::to_string(v) + "]");
+    return MI355_ERR_ARG;
+  }
   mi355_set_error("a launch of this handle gave up a bounded counter wait of the persistent conv (hand-over stalled): its output is invalid"
                   " [error word " + std::to_string(v) + "]");
   return MI355_ERR_TIMEOUT;
@@ -540,6 +551,22 @@ int unet_embedding_table(const mi355_unet* net, const float* t_dev, int n, float
   if ((rc = linear_launch(temb, WF(net->te_w0), WF(net->te_b0), e1, n, mc, 4 * mc, 0, 1, stream))) return rc;
   if ((rc = linear_launch(e1, WF(net->te_w2), WF(net->te_b2), e2, n, 4 * mc, 4 * mc, 0, 1, stream))) return rc;
   return linear_launch(e2, WF(net->emb_w), WF(net->emb_b), table, n, 4 * mc, net->emb_total, 0, 0, stream);
+}
+
+int unet_embedding_rows_labels(const mi355_unet* net, const float* t_dev, int n_t, const int32_t* labels, int R, int h_div, float* table,
+                               float* scratch, hipStream_t stream) {
+  MI355_REQUIRE(net->num_classes > 0 && net->label_w, -1, "class labels given to a net built without num_classes");
+  const int mc = net->cfg.model_channels;
+  const char* W = net->dev_weights;
+  auto WF = [&](size_t off) { return reinterpret_cast<const float*>(W + off); };
+  float* temb = scratch; float* e1 = scratch + (size_t)n_t * mc; float* e2 = e1 + (size_t)n_t * 4 * mc;
+  int rc;
+  // e2 = time_embed(timestep_embedding(t)) WITHOUT the SiLU: with labels it follows the add (label_emb_linear's prologue)
+  if ((rc = timestep_embedding_launch(t_dev, n_t, mc, 10000.f, temb, stream))) return rc;
+  if ((rc = linear_launch(temb, WF(net->te_w0), WF(net->te_b0), e1, n_t, mc, 4 * mc, 0, 1, stream))) return rc;
+  if ((rc = linear_launch(e1, WF(net->te_w2), WF(net->te_b2), e2, n_t, 4 * mc, 4 * mc, 0, 0, stream))) return rc;
+  return label_emb_linear_launch(e2, h_div, WF(net->label_w), labels, net->num_classes, WF(net->emb_w), WF(net->emb_b), table, R, 4 * mc,
+                                 net->emb_total, net->err_dev, stream);
 }
 
 int64_t unet_workspace_bytes(const mi355_unet* net, int batch) { return (int64_t)ws_layout(net, batch).total; }
@@ -590,9 +617,16 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
   if (run.prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, stream); run.prof_events->push_back(e); }
   // time embedding path (fp32): emb2 = silu(time_embed(timestep_embedding(t))) ; embp = all emb_layers linears
   // in the sampler loops every image shares the step time: one embedding row, broadcast with stride 0
-  const int Be = run.t_uniform ? 1 : B, estride = run.t_uniform ? 0 : net->emb_total;
-  const float* embp = run.emb_row ? run.emb_row : F(l.embp);
-  if (!run.emb_row && (rc = unet_embedding_table(net, t, Be, F(l.embp), F(l.temb), stream))) return rc;
+  // class labels: every image has its own row (estride = emb_total even for a shared t), gathered from the sampler's (step, class) table or
+  // computed here from t and the labels
+  const bool labelled = run.labels != nullptr;
+  MI355_REQUIRE(!labelled || net->num_classes > 0, -1, "unet_forward: class labels given to a net built without num_classes");
+  const int Be = run.t_uniform ? 1 : B, estride = run.t_uniform && !labelled ? 0 : net->emb_total;
+  const float* embp = run.emb_row && !labelled ? run.emb_row : F(l.embp);
+  if (labelled && run.emb_row) rc = emb_gather_launch(run.emb_row, run.labels, net->num_classes, F(l.embp), B, net->emb_total, net->err_dev, stream);
+  else if (labelled) rc = unet_embedding_rows_labels(net, t, Be, run.labels, B, run.t_uniform ? B : 1, F(l.embp), F(l.temb), stream);
+  else rc = run.emb_row ? 0 : unet_embedding_table(net, t, Be, F(l.embp), F(l.temb), stream);
+  if (rc) return rc;
   const int S = net->cfg.image_size;
   // the conv a GroupNorm pass feeds is the next op of the plan: the pass warms the L2s with its weights (common.h l2_warm_wave)
   const int warm_mask = net->knobs.l2_warm;   // 1 = statistics / apply passes, 2 = finalize passes (measured: no gain, off)
@@ -798,7 +832,7 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
   {
     int64_t skipped = in_direct ? 1 : 0;   // (the Euler update is the sampler's launch, not the forward's: not counted either way)
     for (char d : gn_done) skipped += d;
-    net->last_launches = net->launches - skipped - (run.emb_row ? 4 : 0);
+    net->last_launches = net->launches - skipped - (run.emb_row ? 4 : 0) + (run.emb_row && labelled ? 1 : 0);   // (+ the row gather)
   }
   return 0;
 }

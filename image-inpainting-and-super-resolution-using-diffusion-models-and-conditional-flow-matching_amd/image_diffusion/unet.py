@@ -26,7 +26,7 @@ def param_shapes(cfg) -> "OrderedDict[str, tuple]":
 
     `cfg` is any object with the UNetModel constructor attributes (image_size, in_channels,
     model_channels, out_channels, num_res_blocks, attention_resolutions, channel_mult, conv_resample,
-    use_scale_shift_norm, resblock_updown)."""
+    use_scale_shift_norm, resblock_updown; num_classes when the net is class-conditional)."""
     mc = cfg.model_channels
     E = 4 * mc
     out: "OrderedDict[str, tuple]" = OrderedDict()
@@ -60,6 +60,9 @@ def param_shapes(cfg) -> "OrderedDict[str, tuple]":
     out["time_embed.0.bias"] = (E,)
     out["time_embed.2.weight"] = (E, E)
     out["time_embed.2.bias"] = (E,)
+    num_classes = getattr(cfg, "num_classes", None)
+    if num_classes is not None:   # unet.py:571-572: label_emb = nn.Embedding(num_classes, time_embed_dim)
+        out["label_emb.weight"] = (int(num_classes), E)
     mult = tuple(cfg.channel_mult)
     ch = input_ch = int(mult[0] * mc)
     conv("input_blocks.0.0", ch, cfg.in_channels, 3)
@@ -134,8 +137,8 @@ class UNetModel(nn.Module):
         super().__init__()
         if dims != 2:
             raise NotImplementedError("the MI355X build supports dims=2 only (every reference config is 2-D)")
-        if num_classes is not None:
-            raise NotImplementedError("class-conditional label_emb is not used by the reference's samplers and is not built")
+        if num_classes is not None and int(num_classes) <= 0:
+            raise ValueError("num_classes must be a positive class count (or None)")
         if num_heads_upsample == -1:
             num_heads_upsample = num_heads
         self.image_size, self.in_channels, self.model_channels, self.out_channels = image_size, in_channels, model_channels, out_channels
@@ -153,7 +156,9 @@ class UNetModel(nn.Module):
         for name, shape in self._shapes.items():
             p = nn.Parameter(torch.empty(shape))
             with torch.no_grad():
-                if _is_norm(name):
+                if name == "label_emb.weight":   # nn.Embedding's init: N(0, 1)
+                    p.normal_()
+                elif _is_norm(name):
                     p.fill_(1.0 if name.endswith("weight") else 0.0)
                 elif _is_zero_init(name):
                     p.zero_()
@@ -200,7 +205,7 @@ class UNetModel(nn.Module):
                     channel_mult=self.channel_mult, conv_resample=self.conv_resample, num_heads=self.num_heads,
                     num_head_channels=self.num_head_channels, num_heads_upsample=self.num_heads_upsample,
                     use_scale_shift_norm=self.use_scale_shift_norm, resblock_updown=self.resblock_updown,
-                    use_new_attention_order=self.use_new_attention_order)
+                    use_new_attention_order=self.use_new_attention_order, num_classes=self.num_classes or 0)
 
     def engine(self, device=None, differentiable: bool = False) -> UNetEngine:
         """The packed HIP engine for the CURRENT parameter values (re-packed when any parameter changed).
@@ -234,16 +239,23 @@ class UNetModel(nn.Module):
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
     # ---- reference API ---------------------------------------------------------------------
+    def _check_labels(self, y):
+        if y is not None and self.num_classes is None:
+            raise ValueError("y (class labels) was given, but this model was built without num_classes")
+
     @torch.no_grad()
-    def forward(self, x, timesteps):
-        """unet.py:708-728: x [N, Cin, H, W], timesteps [N] (may be fractional) -> [N, Cout, H, W]."""
+    def forward(self, x, timesteps, y=None):
+        """unet.py:708-728: x [N, Cin, H, W], timesteps [N] (may be fractional) -> [N, Cout, H, W].
+        y: class labels [N] (integer tensor on x's device) of a class-conditional model: emb = time_embed(.) + label_emb(y), the
+        guided-diffusion / torchcfm rule.  y=None runs the reference's forward(x, timesteps), which never reads label_emb."""
+        self._check_labels(y)
         if not x.is_cuda:
             raise MI355BackendError("UNetModel.forward: x is a CPU tensor; this build only runs on the MI355X HIP backend")
         t = torch.as_tensor(timesteps, device=x.device).float()
         if t.dim() == 0:
             t = t.repeat(x.shape[0])
         eng = self.engine(x.device)
-        return eng.forward(x.float().contiguous(), t.contiguous())
+        return eng.forward(x.float().contiguous(), t.contiguous(), y=y)
 
 
 def create_model(*, image_size: int, in_channels: int, out_channels: int, num_channels: int, num_res_blocks,

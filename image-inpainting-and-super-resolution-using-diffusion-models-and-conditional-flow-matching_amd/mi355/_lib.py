@@ -61,7 +61,7 @@ class UNetConfigC(C.Structure):
         ("conv_resample", C.c_int32), ("num_heads", C.c_int32), ("num_head_channels", C.c_int32),
         ("num_heads_upsample", C.c_int32), ("use_scale_shift_norm", C.c_int32), ("resblock_updown", C.c_int32),
         ("use_new_attention_order", C.c_int32), ("dtype", C.c_int32), ("differentiable", C.c_int32),
-        ("debug", C.POINTER(DebugConfigC)),
+        ("debug", C.POINTER(DebugConfigC)), ("num_classes", C.c_int32),
     ]
 
 
@@ -117,12 +117,14 @@ SIGNATURES = {
     "mi355_unet_workspace_bytes": (_I64, [_VP, _I]),
     "mi355_unet_forward": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_unet_forward_t": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _I, _VP, _I64, _VP]),
+    "mi355_unet_forward_labels": (_I, [_VP, _VP, _I, _VP, _I, _VP, _F, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_unet_vjp": (_I, [_VP, _VP, _VP, _I, _I, _VP, _I64, _VP]),
     "mi355_unet_plan_op": (_I, [_VP, _I, C.POINTER(C.c_int32)]),
     "mi355_unet_read_tensor": (_I, [_VP, _I, _I, _VP, _I, _VP, _I64, _VP]),
     "mi355_unet_get_stats": (_I, [_VP, _I, C.POINTER(UNetStatsC)]),
     "mi355_unet_profile": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _VP, _I64, _VP, C.POINTER(OpProfileC), _I]),
     "mi355_cfm_euler_sample": (_I, [_VP, _VP, _I, _VP, _I, _I, _FP, _I, _VP, _VP, _I, _VP, _I64, _VP]),
+    "mi355_cfm_euler_sample_labels": (_I, [_VP, _VP, _I, _VP, _I, _I, _VP, _FP, _I, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_ddpm_sample": (_I, [_VP, _VP, _I, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), _VP, _I64, _I, _VP, _I64, _VP]),
     "mi355_timestep_embedding": (_I, [_VP, _I, _I, _F, _VP, _VP]),
     "mi355_groupnorm": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _F, _I, _VP]),
@@ -208,7 +210,9 @@ def check(rc: int, what: str = ""):
 
 def make_config(*, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_ds, channel_mult,
                 conv_resample=True, num_heads=1, num_head_channels=-1, num_heads_upsample=-1, use_scale_shift_norm=False,
-                resblock_updown=False, use_new_attention_order=False, dtype=MI355_BF16, differentiable=False, debug=None) -> UNetConfigC:
+                resblock_updown=False, use_new_attention_order=False, dtype=MI355_BF16, differentiable=False, debug=None,
+                num_classes=0) -> UNetConfigC:
+    """num_classes: > 0 for a class-conditional net (label_emb.weight in the inventory); 0 or None: no label embedding."""
     c = UNetConfigC()
     c._debug_keepalive = debug if debug is not None else debug_config()   # the struct must outlive the pointer (read at creation)
     c.debug = C.pointer(c._debug_keepalive)
@@ -232,4 +236,7 @@ def make_config(*, image_size, in_channels, model_channels, out_channels, num_re
     c.use_scale_shift_norm, c.resblock_updown = int(use_scale_shift_norm), int(resblock_updown)
     c.use_new_attention_order, c.dtype = int(use_new_attention_order), dtype
     c.differentiable = int(bool(differentiable))
+    c.num_classes = int(num_classes or 0)
+    if c.num_classes < 0:
+        raise ValueError("num_classes must be >= 0")
     return c

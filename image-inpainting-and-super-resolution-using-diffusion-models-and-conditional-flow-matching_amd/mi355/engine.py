@@ -63,6 +63,7 @@ class UNetEngine:
         self.in_channels = self.cfg.in_channels
         self.out_channels = self.cfg.out_channels
         self.image_size = self.cfg.image_size
+        self.num_classes = int(self.cfg.num_classes)   # 0: no label embedding
 
     def __del__(self):
         try:
@@ -76,8 +77,9 @@ class UNetEngine:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def check(self, clear: bool = True):
-        """Raise MI355BackendError if a launch of this engine gave up a bounded counter wait (mi355_unet_status).  Synchronise first to
-        cover the launches already queued; every engine call also checks the flag on entry."""
+        """Raise MI355BackendError if a launch of this engine gave up a bounded counter wait or met a class label outside
+        [0, num_classes) (mi355_unet_status).  Synchronise first to cover the launches already queued; every engine call also checks the flag
+        on entry."""
         check(self.L.mi355_unet_status(self.handle, int(clear)), "mi355_unet_status")
 
     def workspace(self, batch: int):
@@ -94,6 +96,21 @@ class UNetEngine:
             raise TypeError(f"{name} must be contiguous {dtype}")
         return C.c_void_p(t.data_ptr())
 
+    def _labels(self, y, B: int):
+        """Class labels -> contiguous int32 [B] on the engine's device (ctypes pointer, tensor kept alive by the caller), or (None, None)."""
+        if y is None:
+            return None, None
+        if not self.num_classes:
+            raise ValueError("y (class labels) given to a model built without num_classes")
+        if not isinstance(y, torch.Tensor) or y.dtype.is_floating_point or y.dtype.is_complex or y.dtype == torch.bool:
+            raise TypeError("y must be an integer tensor of class labels")
+        if tuple(y.shape) != (B,):
+            raise ValueError(f"y must have shape ({B},), got {tuple(y.shape)}")
+        if y.device != self.device:
+            raise MI355BackendError(f"y is on {y.device}, the engine lives on {self.device} (no CPU fallback)")
+        y = y.to(torch.int32).contiguous()
+        return y, C.c_void_p(y.data_ptr())
+
     def _split(self, x, cond):
         B, Cx, H, W = x.shape
         if H != self.image_size or W != self.image_size:
@@ -107,9 +124,24 @@ class UNetEngine:
             raise ValueError(f"x ({Cx}) + condition ({Cc}) channels != in_channels ({self.in_channels})")
         return B, Cx, Cc
 
-    def forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
-        """t: a [B] device tensor, or a host scalar shared by the batch (no device tensor is made for it: mi355_unet_forward_t)."""
+    def forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None):
+        """t: a [B] device tensor, or a host scalar shared by the batch (no device tensor is made for it: mi355_unet_forward_t).
+        y: class labels [B] (integer, on the device) of a class-conditional engine: emb = time_embed(.) + label_emb(y)
+        (mi355_unet_forward_labels); None = the reference's forward(x, timesteps), which never reads label_emb."""
         B, Cx, Cc = self._split(x, cond)
+        if y is not None:
+            lab, lab_p = self._labels(y, B)
+            host_t = isinstance(t, (int, float))
+            if not host_t and t.shape != (B,):
+                raise ValueError(f"timesteps must have shape ({B},)")
+            if out is None:
+                out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
+            ws, wsb = self.workspace(B)
+            check(self.L.mi355_unet_forward_labels(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
+                                                   Cc, None if host_t else self._chk(t, "timesteps"), float(t) if host_t else 0.0, lab_p,
+                                                   self._chk(out, "out"), B, ws, wsb, self._stream()), "mi355_unet_forward_labels")
+            self._fwd_state = (B, self._ws.data_ptr())
+            return out
         if isinstance(t, (int, float)):
             if out is None:
                 out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
@@ -206,20 +238,23 @@ class UNetEngine:
         return self._max_batch
 
     def cfm_euler(self, x: torch.Tensor, t_span: Sequence[float], cond: Optional[torch.Tensor] = None, keep_traj: bool = False,
-                  want_u8: bool = False, cond_drift: bool = False):
+                  want_u8: bool = False, cond_drift: bool = False, y: Optional[torch.Tensor] = None):
         """In-place Euler integration of x over t_span (host floats).  Returns (x, traj or None, u8 or None).
         cond_drift: the condition is integrated with derivative `cond` (the concatenated-state sampler of
         mnist/utils_mnist2.py:118-138); the caller's tensor is not modified.
         A batch beyond max_batch() is integrated in slices (every image's trajectory is independent of its batch mates; the kernels chosen for a
-        slice may sum in another order than those of the whole batch would)."""
+        slice may sum in another order than those of the whole batch would).
+        y: class labels [B] of a class-conditional engine: every step evaluates model(t_k, x_k, y) (mi355_cfm_euler_sample_labels)."""
         B, Cx, Cc = self._split(x, cond)
+        lab, lab_p = self._labels(y, B)
         mb = self.max_batch()
         if B > mb:
             traj = torch.empty((len(t_span),) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
             u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
             for lo in range(0, B, mb):
                 hi = min(B, lo + mb)
-                _, tr, u = self.cfm_euler(x[lo:hi], t_span, cond[lo:hi] if cond is not None else None, keep_traj, want_u8, cond_drift)
+                _, tr, u = self.cfm_euler(x[lo:hi], t_span, cond[lo:hi] if cond is not None else None, keep_traj, want_u8, cond_drift,
+                                          lab[lo:hi] if lab is not None else None)
                 if traj is not None:
                     traj[:, lo:hi] = tr
                 if u8 is not None:
@@ -231,6 +266,12 @@ class UNetEngine:
         u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
         self._fwd_state = None
         ws, wsb = self.workspace(B)
+        if lab is not None:
+            check(self.L.mi355_cfm_euler_sample_labels(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
+                                                       Cc, int(bool(cond_drift)), lab_p, arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
+                                                       self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
+                  "mi355_cfm_euler_sample_labels")
+            return x, traj, u8
         check(self.L.mi355_cfm_euler_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
                                             Cc, int(bool(cond_drift)), arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
                                             self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),

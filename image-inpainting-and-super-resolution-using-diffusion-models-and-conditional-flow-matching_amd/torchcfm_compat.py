@@ -31,7 +31,10 @@ def _default_mult(image_size):
 
 
 class UNetModelWrapper(UNetModel):
-    """torchcfm UNetModelWrapper: dim=(C,H,W), attention_resolutions as a string of resolutions."""
+    """torchcfm UNetModelWrapper: dim=(C,H,W), attention_resolutions as a string of resolutions.  The stand-in of the cifar10/ and mnist/
+    call sites, which build no label embedding: class_cond=True with num_classes set is refused here (ClassCondUNetModelWrapper builds it)."""
+
+    _class_cond_ok = False   # ClassCondUNetModelWrapper: label_emb is built
 
     def __init__(self, dim, num_channels, num_res_blocks, channel_mult=None, learn_sigma=False, class_cond=False, num_classes=None,
                  use_checkpoint=False, attention_resolutions="16", num_heads=1, num_head_channels=-1, num_heads_upsample=-1,
@@ -40,16 +43,19 @@ class UNetModelWrapper(UNetModel):
         image_size = dim[-1]
         channel_mult = _default_mult(image_size) if channel_mult is None else tuple(channel_mult)
         attention_ds = tuple(image_size // int(res) for res in str(attention_resolutions).split(","))
-        # torchcfm: `num_classes = NUM_CLASSES if class_cond else None`-style gating - a label embedding exists only when a class
-        # count is given.  Every reference call site passes class_cond=True WITH num_classes=None (mnist/train_mnist.py:262-267,
-        # train_mnist2.py:350-355, train_mnist_hy.py:312-318, train_mnist_hy2.py:313-318), i.e. an unconditional network.
-        if class_cond and num_classes is not None:
-            raise NotImplementedError("class-conditional label_emb (class_cond=True with num_classes set) is not used by the "
-                                      "reference's samplers and is not built")
+        # torchcfm: `num_classes if class_cond else None` - a label embedding exists only when class_cond is set AND a class count is
+        # given (conditional_mnist.ipynb: class_cond=True, num_classes=10).  The mnist/ call sites pass class_cond=True WITH
+        # num_classes=None (mnist/train_mnist.py:262-267, train_mnist2.py:350-355, train_mnist_hy.py:312-318, train_mnist_hy2.py:313-318),
+        # i.e. an unconditional network.
+        num_classes = num_classes if class_cond else None
+        if num_classes is not None and not self._class_cond_ok:
+            raise NotImplementedError("UNetModelWrapper stands in for the cifar10/ and mnist/ call sites and builds no label_emb; the "
+                                      "class-conditional torchcfm model (class_cond=True, num_classes=K, as conditional_mnist.ipynb builds it) "
+                                      "is torchcfm_compat.ClassCondUNetModelWrapper")
         super().__init__(image_size=image_size, in_channels=dim[0] if in_channels is None else in_channels,
                          model_channels=num_channels, out_channels=(dim[0] if not learn_sigma else dim[0] * 2),
                          num_res_blocks=num_res_blocks, attention_resolutions=attention_ds, dropout=dropout,
-                         channel_mult=channel_mult, num_classes=None, use_checkpoint=use_checkpoint, use_fp16=use_fp16,
+                         channel_mult=channel_mult, num_classes=num_classes, use_checkpoint=use_checkpoint, use_fp16=use_fp16,
                          num_heads=num_heads, num_head_channels=num_head_channels, num_heads_upsample=num_heads_upsample,
                          use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown,
                          use_new_attention_order=use_new_attention_order, precision=precision)
@@ -70,9 +76,25 @@ class UNetModelWrapper(UNetModel):
 
     @torch.no_grad()
     def forward(self, t, x, y=None, *args, **kwargs):
+        """torchcfm: model(t, x, y).  A class-conditional model (num_classes set) needs y, the labels [B]; without num_classes y is ignored
+        (the mnist/ call sites' class_cond=True, num_classes=None networks)."""
+        if self.num_classes is None:
+            y = None
+        elif y is None:
+            raise ValueError("y (class labels) is required: this model was built with class_cond=True and num_classes="
+                             f"{self.num_classes} (torchcfm asserts (y is not None) == (num_classes is not None))")
         if not x.is_cuda:
             return super().forward(x, t)     # raises MI355BackendError (no CPU path)
-        return self.engine(x.device).forward(x.float().contiguous(), self._c(self._t(t, x)))
+        return self.engine(x.device).forward(x.float().contiguous(), self._c(self._t(t, x)), y=y)
+
+
+class ClassCondUNetModelWrapper(UNetModelWrapper):
+    """torchcfm's UNetModelWrapper built class-conditional, the model of conditional_mnist.ipynb (`from torchcfm.models.unet import
+    UNetModel`; `UNetModel(dim=(1, 28, 28), num_channels=32, num_res_blocks=1, num_classes=10, class_cond=True)`): the same constructor,
+    label_emb.weight [num_classes, 4 * num_channels] (N(0, 1) init), and model(t, x, y) with y, the labels [B], required.  Sample it with
+    odeint_dopri5(lambda t, x: model(t, x, y), ...) or model.engine().cfm_euler(x, t_span, y=y); NeuralODE has no labels to pass."""
+
+    _class_cond_ok = True
 
 
 class InPaintModelWrapper(UNetModelWrapper):

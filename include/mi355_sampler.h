@@ -43,7 +43,8 @@ extern "C" {
                      * mantissa bits on every stored activation and weight; values beyond +-65504 overflow to inf as they do in the reference */
 
 /* ABI version = 100 * major + minor.  The minor number counts additive changes; 106: mi355_qkv_attention_vjp (the attention backward as a test
- * op).  105 (round 5, last): mi355_debug_config::sampler_graph (carved out of the
+ * op); later additions to 106: mi355_unet_config::num_classes (class-conditional nets), mi355_unet_forward_labels,
+ * mi355_cfm_euler_sample_labels, and the error word's bit 1 (a class label out of range, reported as MI355_ERR_ARG).  105 (round 5, last): mi355_debug_config::sampler_graph (carved out of the
  * reserved tail), mi355_box_probe_hbm.  104 (round 5, later): mi355_conv2d_ex (the small-level conv's fused forms as a
  * test op), gn_epilogue bit 2, conv_small bit 3, conv_edge bits 2-3, conv_pp bit 5, mi355_op_profile::tile_m = -1 for plan ops that launched nothing.
  * 103 (round 5): conv_pp became a bit mask (bits 2, 3, 4: the
@@ -125,6 +126,9 @@ typedef struct mi355_unet_config {
   int32_t dtype; /* MI355_F32 | MI355_BF16 | MI355_BF16X2 | MI355_F16 */
   int32_t differentiable; /* 1: keep what mi355_unet_vjp needs (per-site GroupNorm statistics, the qkv tensors, transposed weights) */
   const mi355_debug_config* debug; /* NULL = defaults; copied at mi355_unet_create */
+  int32_t num_classes; /* > 0: class-conditional net (UNetModel(num_classes=K), unet.py:571-572): the inventory gains label_emb.weight [K, 4*model_channels]
+                        * right after time_embed.2.bias, and mi355_unet_forward_labels / mi355_cfm_euler_sample_labels add label_emb(y) to the time
+                        * embedding (emb = time_embed(timestep_embedding(t)) + label_emb(y), then each ResBlock's SiLU -> Linear).  0: no label embedding */
 } mi355_unet_config;
 
 typedef struct mi355_unet mi355_unet; /* opaque */
@@ -149,7 +153,7 @@ int64_t mi355_unet_workspace_bytes(const mi355_unet* net, int batch);
  * hand-over ends after conv_spin_limit polls, the launch's output is then invalid).  The flag is one word of pinned host memory
  * the kernels write through; it is also checked at the start of every call that takes the handle, so a failure is reported by the
  * next call at the latest - synchronise the stream first to learn about the launches already queued.  `clear` resets it. */
-int mi355_unet_status(mi355_unet* net, int clear);
+int mi355_unet_status(mi355_unet* net, int clear);   /* (bit 1 of the word: a class label out of range -> MI355_ERR_ARG) */
 
 /* UNetModel.forward(x, timesteps) (unet.py:708-728).  x: [B, Cx, H, W]; cond: NULL or [B, Cc, H, W]
  * with Cx + Cc == in_channels (the Amortized sampler's channel concat, AD/image_diffusion/sampling.py:39,
@@ -161,6 +165,14 @@ int mi355_unet_forward(mi355_unet* net, const float* x, int x_channels, const fl
  * cifar10/utils_cifar.py:34-39, mnist/utils_mnist.py:96-97): one time-embedding row instead of B, no device tensor for t. */
 int mi355_unet_forward_t(mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, float t, float* out,
                          int batch, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Class-conditional forward (cfg.num_classes > 0): emb = time_embed(timestep_embedding(t)) + label_emb(labels).  t: device float[B], or NULL for
+ * ONE host time t_host shared by the batch (as mi355_unet_forward_t); labels: device int32[B] in [0, num_classes), or NULL = the reference's
+ * forward(x, timesteps), which never reads label_emb.  Labels on a net without num_classes: MI355_ERR_ARG.  A label outside the range reads
+ * nothing outside label_emb: its label term is zero and the handle's error word records it - mi355_unet_status (and the next call that takes the
+ * handle) then returns MI355_ERR_ARG.  mi355_unet_vjp differentiates this forward like any other. */
+int mi355_unet_forward_labels(mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, const float* t, float t_host,
+                              const int32_t* labels, float* out, int batch, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Vector-Jacobian product of the last mi355_unet_forward on this workspace w.r.t. its image input: grad_x = (d out / d x)^T grad_out
  * (and, when cond was given, nothing for cond).  This is the `grad(constraint)` through the x0 model of the reconstruction-guidance
@@ -224,6 +236,14 @@ int mi355_unet_profile(mi355_unet* net, const float* x, int x_channels, const fl
 int mi355_cfm_euler_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
                            const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
                            void* workspace, int64_t workspace_bytes, void* stream);
+
+/* mi355_cfm_euler_sample of a class-conditional net: every step evaluates model(t_k, x_k, labels) (labels: device int32[B]; NULL = as
+ * mi355_cfm_euler_sample).  With (n_t - 1) * num_classes <= 1024 all emb_layers outputs of every (step, class) pair are computed before the loop
+ * and each step gathers its images' rows (one launch); otherwise each step computes its rows from the labels (the same four launches as an
+ * unconditional step).  sampler_graph is not used with labels. */
+int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
+                                  const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
 
 /* per-step scalars of the DDPM tables (AD/image_diffusion/sde_diffusion.py:127-167), host arrays of length Ns */
 typedef struct mi355_ddpm_tables {
