@@ -421,6 +421,73 @@ int mi355_ddpm_sample(mi355_unet* net, float* x, int channels, const float* cond
   return clip_launch(x, -1.f, 1.f, n, s);
 }
 
+// SF2M (torchcfm notebooks' torchsde.sdeint of drift = model + score_model, g = sigma): per step two forwards, each net on its own workspace
+// (its own embedding table: label_emb differs between the nets), then the Euler-Maruyama launch, which also writes the step's output time.
+int mi355_sf2m_euler_sample(mi355_unet* drift, mi355_unet* score, float* x, int channels, const int32_t* labels, const float* t_grid_host,
+                            int n_steps, float sigma, int reverse, const float* dW, uint64_t seed, const int32_t* out_step_host,
+                            const float* out_w_host, int n_out, float* traj, int batch, void* drift_workspace, int64_t drift_workspace_bytes,
+                            void* score_workspace, int64_t score_workspace_bytes, void* stream) {
+  MI355_REQUIRE(drift && score && x && t_grid_host && batch > 0, -1, "sf2m_euler_sample: bad argument");
+  MI355_REQUIRE(n_steps >= 1, -1, "sf2m_euler_sample: the step grid needs at least one step (n_steps >= 1)");
+  MI355_REQUIRE(drift_workspace != score_workspace, -1, "sf2m_euler_sample: the two nets need separate workspaces");
+  const mi355_unet_config &cd = drift->cfg, &cs = score->cfg;
+  MI355_REQUIRE(cd.in_channels == cs.in_channels && cd.out_channels == cs.out_channels && cd.image_size == cs.image_size, -2,
+                "sf2m_euler_sample: the drift and score nets differ in in_channels, out_channels or image_size");
+  MI355_REQUIRE(cd.in_channels == channels && cd.out_channels == channels, -2,
+                "sf2m_euler_sample: both nets must map the state's channel count to itself (in_channels == out_channels == channels)");
+  MI355_REQUIRE(!labels || (drift->num_classes > 0 && score->num_classes > 0), -1,
+                "sf2m_euler_sample: class labels given to a net built without num_classes (both nets must be class-conditional)");
+  MI355_REQUIRE(!labels || drift->num_classes == score->num_classes, -1, "sf2m_euler_sample: the two class-conditional nets differ in num_classes");
+  MI355_REQUIRE(n_out == 0 || (traj && out_step_host && out_w_host), -1, "sf2m_euler_sample: outputs need traj, out_step and out_w");
+  for (int j = 0; j < n_out; ++j)
+    MI355_REQUIRE(out_step_host[j] >= 0 && out_step_host[j] < n_steps && out_w_host[j] >= 0.f && out_w_host[j] <= 1.f, -1,
+                  "sf2m_euler_sample: an output's step must be in [0, n_steps) and its weight in [0, 1]");
+  Scratch sd, ss;
+  if (int rc = carve(drift, batch, drift_workspace, drift_workspace_bytes, sd)) return rc;
+  if (int rc = carve(score, batch, score_workspace, score_workspace_bytes, ss)) return rc;
+  hipStream_t s = S(stream);
+  const int64_t n = (int64_t)batch * channels * cd.image_size * cd.image_size;
+  const int64_t n_al = (n + 3) / 4 * 4;
+  // the times the nets see: t_k, or 1 - t_k rounded in fp32 (the notebook's reverse SDE evaluates at `1 - t` of the fp32 tensor)
+  std::vector<float> te((size_t)n_steps);
+  for (int k = 0; k < n_steps; ++k) te[k] = reverse ? 1.0f - t_grid_host[k] : t_grid_host[k];
+  const float *tab_d = nullptr, *tab_s = nullptr;
+  if (int rc = make_emb_table(drift, sd, te.data(), n_steps, labels != nullptr, s, &tab_d)) return rc;
+  if (int rc = make_emb_table(score, ss, te.data(), n_steps, labels != nullptr, s, &tab_s)) return rc;
+  if (tab_d || tab_s) MI355_CHECK_HIP(hipStreamSynchronize(s));   // `te` is a temporary host buffer (once per sample() call)
+  UnetRun rd = uniform_t_run(), rs = uniform_t_run();
+  rd.labels = rs.labels = labels;
+  const size_t blk_d = (size_t)(labels ? drift->num_classes : 1) * drift->emb_total, blk_s = (size_t)(labels ? score->num_classes : 1) * score->emb_total;
+  const float ca = reverse ? -1.f : 1.f;
+  int rc = 0;
+  for (int k = 0; k < n_steps && rc == 0; ++k) {
+    const float dt = t_grid_host[k + 1] - t_grid_host[k];
+    if (tab_d) rd.emb_row = tab_d + (size_t)k * blk_d;
+    else if ((rc = fill_launch(sd.t, te[k], batch, s))) break;
+    if (tab_s) rs.emb_row = tab_s + (size_t)k * blk_s;
+    else if ((rc = fill_launch(ss.t, te[k], batch, s))) break;
+    if ((rc = unet_forward(drift, x, channels, nullptr, 0, sd.t, sd.v, batch, sd.unet_ws, sd.unet_bytes, s, rd))) break;
+    if ((rc = unet_forward(score, x, channels, nullptr, 0, ss.t, ss.v, batch, ss.unet_ws, ss.unet_bytes, s, rs))) break;
+    const float* dw = dW ? dW + (size_t)k * n : nullptr;
+    const uint64_t off = dW ? 0 : (uint64_t)k * (uint64_t)n_al;
+    // outputs of this step: w == 0 is x_k itself (copied before the update); the first other one rides in the step launch; further ones
+    // (several output times inside one step) re-run the same deterministic update on a copy of x_k held in the drift net's spare scratch
+    float* fused = nullptr; float fused_w = 0.f;
+    for (int j = 0; j < n_out && rc == 0; ++j) {
+      if (out_step_host[j] != k) continue;
+      float* oj = traj + (size_t)j * n;
+      if (out_w_host[j] == 0.f) { MI355_CHECK_HIP(hipMemcpyAsync(oj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s)); continue; }
+      if (!fused) { fused = oj; fused_w = out_w_host[j]; continue; }
+      MI355_REQUIRE(channels <= 32, -4, "sf2m_euler_sample: several output times inside one step need channels <= 32");
+      MI355_CHECK_HIP(hipMemcpyAsync(sd.none, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      rc = sde_euler_step_launch(sd.none, sd.v, ss.v, ca, 1.f, dt, nullptr, sigma, dw, !dW, seed, off, oj, out_w_host[j], n, s);
+    }
+    if (rc) break;
+    rc = sde_euler_step_launch(x, sd.v, ss.v, ca, 1.f, dt, nullptr, sigma, dw, !dW, seed, off, fused, fused_w, n, s);
+  }
+  return rc;
+}
+
 // ---- single ops -------------------------------------------------------------------------------------
 
 int mi355_timestep_embedding(const float* t, int batch, int dim, float max_period, float* out, void* stream) {
@@ -433,6 +500,11 @@ int mi355_groupnorm(const float* x, const float* gamma, const float* beta, float
   return groupnorm_nchw_launch(x, gamma, beta, y, batch, channels, hw, groups, eps, silu, S(stream));
 }
 int mi355_euler_step(float* x, const float* v, float dt, int64_t n, void* stream) { return euler_step_launch(x, v, dt, n, S(stream)); }
+int mi355_sde_euler_step(float* x, const float* a, const float* b, float ca, float cb, float dt, const float* g, float g_scalar, const float* dW,
+                         int use_philox, uint64_t seed, uint64_t offset, float* out, float w, int64_t n, void* stream) {
+  MI355_REQUIRE((ca == 1.f || ca == -1.f) && (cb == 1.f || cb == -1.f), -1, "sde_euler_step: ca and cb must be +1 or -1");
+  return sde_euler_step_launch(x, a, b, ca, cb, dt, g, g_scalar, dW, use_philox, seed, offset, out, w, n, S(stream));
+}
 int mi355_ddpm_step(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
                     float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
   return ddpm_step_launch(x, eps, z, c_recip, c_recipm1, coef1, coef2, sigma, use_philox, seed, offset, n, S(stream));

@@ -240,6 +240,8 @@ int resample_launch(int dtype, const void* in, void* out, int N, int Hs, int Ws,
 
 // elementwise sampler steps (steps.hip)
 int euler_step_launch(float* x, const float* v, float dt, int64_t n, hipStream_t s);
+int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, float cb, float dt, const float* g, float g_s, const float* dW,
+                          int use_philox, uint64_t seed, uint64_t offset, float* out, float w, int64_t n, hipStream_t s);
 int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
                      float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,

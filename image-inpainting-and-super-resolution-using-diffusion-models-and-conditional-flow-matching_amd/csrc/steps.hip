@@ -99,6 +99,41 @@ int euler_step_launch(float* x, const float* v, float dt, int64_t n, hipStream_t
   });
 }
 
+// Euler-Maruyama step of a diagonal-noise Ito SDE (torchsde's fixed-step Euler: y1 = y0 + f * dt + g * dW), f = ca * a (+ cb * b):
+// the SF2M drift is model + score_model (ca = cb = +1), its reverse -model + score_model (ca = -1).  The sum is rounded once before
+// the product, as the eager `f` is returned, and y0 + f*dt + g*dW is evaluated left to right with every operation rounded (no
+// contraction: this file).  g: per-element tensor or, when null, the scalar g_s.  dW: injected increments, or sqrt(dt) * z with z the
+// Philox stream of randn_launch at (seed, offset); neither = no noise.  out (optional): out = x_k + w * (x_{k+1} - x_k), torchsde's linear
+// interpolation of an output time inside the step; w == 0 and w == 1 store the end points themselves, as torchsde returns them.
+int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, float cb, float dt, const float* g, float g_s, const float* dW,
+                          int use_philox, uint64_t seed, uint64_t offset, float* out, float w, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(x && a, -1, "sde_euler_step: null argument");
+  MI355_REQUIRE(offset % 4 == 0, -1, "sde_euler_step: the Philox offset must be a multiple of 4");
+  const uint64_t off4 = offset / 4;
+  const float sdt = sqrtf(dt);   // correctly rounded, as torch's fp32 sqrt
+  const int noisy = dW != nullptr || use_philox;
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
+    float xv[4], av[4], bv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {g_s, g_s, g_s, g_s}, zz[4] = {0.f, 0.f, 0.f, 0.f};
+    ld4(x, i, cnt, xv); ld4(a, i, cnt, av);
+    if (b) ld4(b, i, cnt, bv);
+    if (g) ld4(g, i, cnt, gv);
+    if (noisy) noise4(dW, use_philox, seed, off4, i, i4, cnt, zz);
+    float x1[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float f = b ? ca * av[j] + cb * bv[j] : ca * av[j];
+      const float dw = dW ? zz[j] : sdt * zz[j];
+      x1[j] = noisy ? (xv[j] + f * dt) + gv[j] * dw : xv[j] + f * dt;
+    }
+    st4(x, i, cnt, x1);
+    if (out) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xv[j] = w == 0.f ? xv[j] : (w == 1.f ? x1[j] : xv[j] + w * (x1[j] - xv[j]));
+      st4(out, i, cnt, xv);
+    }
+  });
+}
+
 int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
                      float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
   const uint64_t off4 = offset / 4;

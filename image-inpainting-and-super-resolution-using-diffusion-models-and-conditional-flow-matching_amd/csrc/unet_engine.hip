@@ -505,7 +505,7 @@ int unet_status(const mi355_unet* net, int clear) {
   if (v == 0u) return 0;
   if (!(v & 1u)) {   // bit 1 alone: a label kernel met a class label outside [0, num_classes)
     mi355_set_error("a launch of this handle was given a class label outside [0, num_classes) (labels of mi355_unet_forward_labels / "
-                    "mi355_cfm_euler_sample_labels): that image's label term was taken as zero, its output is invalid [error word " + std::to_string(v) + "]");
+                    "mi355_cfm_euler_sample_labels / mi355_sf2m_euler_sample): that image's label term was taken as zero, its output is invalid [error word " + std::to_string(v) + "]");
     return MI355_ERR_ARG;
   }
   mi355_set_error("a launch of this handle gave up a bounded counter wait of the persistent conv (hand-over stalled): its output is invalid"

@@ -125,10 +125,13 @@ SIGNATURES = {
     "mi355_unet_profile": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _VP, _I64, _VP, C.POINTER(OpProfileC), _I]),
     "mi355_cfm_euler_sample": (_I, [_VP, _VP, _I, _VP, _I, _I, _FP, _I, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_cfm_euler_sample_labels": (_I, [_VP, _VP, _I, _VP, _I, _I, _VP, _FP, _I, _VP, _VP, _I, _VP, _I64, _VP]),
+    "mi355_sf2m_euler_sample": (_I, [_VP, _VP, _VP, _I, _VP, _FP, _I, _F, _I, _VP, _U64, C.POINTER(C.c_int32), _FP, _I, _VP, _I, _VP, _I64,
+                                     _VP, _I64, _VP]),
     "mi355_ddpm_sample": (_I, [_VP, _VP, _I, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), _VP, _I64, _I, _VP, _I64, _VP]),
     "mi355_timestep_embedding": (_I, [_VP, _I, _I, _F, _VP, _VP]),
     "mi355_groupnorm": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _F, _I, _VP]),
     "mi355_euler_step": (_I, [_VP, _VP, _F, _I64, _VP]),
+    "mi355_sde_euler_step": (_I, [_VP, _VP, _VP, _F, _F, _F, _VP, _F, _VP, _I, _U64, _U64, _VP, _F, _I64, _VP]),
     "mi355_ddpm_step": (_I, [_VP, _VP, _VP, _F, _F, _F, _F, _F, _I, _U64, _U64, _I64, _VP]),
     "mi355_corrector_step": (_I, [_VP, _VP, _VP, _F, _F, _F, _F, _F, _I, _U64, _U64, _I64, _VP]),
     "mi355_ddim_step": (_I, [_VP, _VP, _F, _F, _F, _I64, _VP]),

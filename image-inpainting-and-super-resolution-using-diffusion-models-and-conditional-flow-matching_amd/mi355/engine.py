@@ -5,7 +5,7 @@ PyTorch is used for device memory (weight blob, workspace, I/O tensors) and the 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -277,6 +277,57 @@ class UNetEngine:
                                             self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
               "mi355_cfm_euler_sample")
         return x, traj, u8
+
+    def sf2m_euler(self, score_engine: "UNetEngine", x: torch.Tensor, t_grid: Sequence[float], sigma: float, reverse: bool = False,
+                   y: Optional[torch.Tensor] = None, dW: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                   outputs: Optional[Sequence[Tuple[int, float]]] = None):
+        """In-place SF2M Euler-Maruyama integration of x over the step grid t_grid (host floats, fp32 boundaries), this engine as the flow
+        `model`, score_engine as `score_model` (mi355_sf2m_euler_sample):  x <- x + (model(t, x) + score_model(t, x)) * dt + sigma * dW,
+        reverse: both nets at 1 - t and -model + score_model.
+        y: class labels [B] used by both nets.  dW: injected increments [n_steps, B, C, H, W]; None: device Philox noise keyed by `seed`
+        (None: drawn from torch's default generator).  outputs: (step k, weight w) pairs -> returns traj [len(outputs), B, C, H, W] with
+        traj[j] = x_k + w * (x_{k+1} - x_k), or None.  Returns (x, traj).
+        A batch beyond min(max_batch()) of the two engines runs in slices; with Philox noise each slice draws from its own key (seed + slice)."""
+        if not isinstance(score_engine, UNetEngine) or score_engine.device != self.device:
+            raise MI355BackendError("sf2m_euler: score_engine must be a UNetEngine on the same device")
+        B, Cx, _ = self._split(x, None)
+        ts = [float(v) for v in t_grid]
+        n = len(ts) - 1
+        if n < 1:
+            raise ValueError("sf2m_euler: t_grid needs at least two times (one step)")
+        outs = [(int(k), float(w)) for k, w in (outputs or [])]
+        if dW is not None and tuple(dW.shape) != (n,) + tuple(x.shape):
+            raise ValueError(f"dW must be [n_steps, *x.shape] = {(n,) + tuple(x.shape)}, got {tuple(dW.shape)}")
+        if dW is None and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        lab_eng = self if self.num_classes else score_engine   # the net without num_classes is refused by the library (both must be conditional)
+        lab, lab_p = lab_eng._labels(y, B)
+        mb = min(self.max_batch(), score_engine.max_batch())
+        if B > mb:
+            traj = torch.empty((len(outs),) + tuple(x.shape), device=self.device, dtype=torch.float32) if outs else None
+            for i, lo in enumerate(range(0, B, mb)):
+                hi = min(B, lo + mb)
+                xs = x[lo:hi].contiguous()
+                _, tr = self.sf2m_euler(score_engine, xs, ts, sigma, reverse, lab[lo:hi] if lab is not None else None,
+                                        dW[:, lo:hi].contiguous() if dW is not None else None,
+                                        None if dW is not None else (seed + i) % 2 ** 64, outs)
+                x[lo:hi] = xs
+                if traj is not None:
+                    traj[:, lo:hi] = tr
+            return x, traj
+        traj = torch.empty((len(outs),) + tuple(x.shape), device=self.device, dtype=torch.float32) if outs else None
+        grid = (C.c_float * len(ts))(*ts)
+        osteps = (C.c_int32 * max(1, len(outs)))(*[k for k, _ in outs])
+        ows = (C.c_float * max(1, len(outs)))(*[w for _, w in outs])
+        self._fwd_state = None
+        score_engine._fwd_state = None
+        ws_d, wsb_d = self.workspace(B)
+        ws_s, wsb_s = score_engine.workspace(B)
+        check(self.L.mi355_sf2m_euler_sample(self.handle, score_engine.handle, self._chk(x, "x"), Cx, lab_p, grid, n, float(sigma), int(bool(reverse)),
+                                             self._chk(dW, "dW") if dW is not None else None, int(seed or 0) % 2 ** 64, osteps, ows, len(outs),
+                                             self._chk(traj, "traj") if traj is not None else None, B, ws_d, wsb_d, ws_s, wsb_s, self._stream()),
+              "mi355_sf2m_euler_sample")
+        return x, traj
 
     def ddpm_sample(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], *, mode: int, cond: Optional[torch.Tensor] = None,
                     noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0,

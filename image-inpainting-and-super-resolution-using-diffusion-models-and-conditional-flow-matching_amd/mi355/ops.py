@@ -55,6 +55,29 @@ class Ops:
         check(_lib.lib().mi355_euler_step(_req(x, "x"), _req(v, "v"), float(dt), x.numel(), _stream()))
         return x
 
+    def sde_euler_step_(self, x, a, dt, g, b=None, ca=1.0, cb=1.0, dW=None, philox=None, out=None, w=0.0):
+        """Euler-Maruyama update in place: x <- x + (ca*a + cb*b) * dt + g * dW (torchsde's Euler step, rounded as its eager expression).
+        g: a tensor of x's shape or a float; dW: injected increments, or None with philox = (seed, offset): sqrt(dt) * N(0, 1) from the device
+        stream; both None: no noise.  out: a tensor that receives x_old + w * (x_new - x_old) from the same launch.  -> x"""
+        _same(x, a, "x", "a")
+        if b is not None:
+            _same(x, b, "x", "b")
+        if isinstance(g, torch.Tensor):
+            _same(x, g, "x", "g")
+            gp, gs = _req(g, "g"), 0.0
+        else:
+            gp, gs = None, float(g)
+        if dW is not None:
+            _same(x, dW, "x", "dW")
+        if out is not None:
+            _same(x, out, "x", "out")
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_sde_euler_step(_req(x, "x"), _req(a, "a"), _req(b, "b") if b is not None else None, float(ca), float(cb), float(dt),
+                                              gp, gs, _req(dW, "dW") if dW is not None else None, int(philox is not None and dW is None),
+                                              int(seed), int(off), _req(out, "out") if out is not None else None, float(w), x.numel(), _stream()),
+              "mi355_sde_euler_step")
+        return x
+
     def ddpm_step_(self, x, eps, z, c_recip, c_recipm1, coef1, coef2, sigma, philox=None):
         """z: injected noise tensor, or None; philox: (seed, offset) for device noise; both None = no noise (i == 0)."""
         _same(x, eps, "x", "eps")

@@ -44,7 +44,8 @@ extern "C" {
 
 /* ABI version = 100 * major + minor.  The minor number counts additive changes; 106: mi355_qkv_attention_vjp (the attention backward as a test
  * op); later additions to 106: mi355_unet_config::num_classes (class-conditional nets), mi355_unet_forward_labels,
- * mi355_cfm_euler_sample_labels, and the error word's bit 1 (a class label out of range, reported as MI355_ERR_ARG).  105 (round 5, last): mi355_debug_config::sampler_graph (carved out of the
+ * mi355_cfm_euler_sample_labels, and the error word's bit 1 (a class label out of range, reported as MI355_ERR_ARG); then
+ * mi355_sf2m_euler_sample (the two-network SF2M SDE sampler) and mi355_sde_euler_step (its Euler-Maruyama update as an op).  105 (round 5, last): mi355_debug_config::sampler_graph (carved out of the
  * reserved tail), mi355_box_probe_hbm.  104 (round 5, later): mi355_conv2d_ex (the small-level conv's fused forms as a
  * test op), gn_epilogue bit 2, conv_small bit 3, conv_edge bits 2-3, conv_pp bit 5, mi355_op_profile::tile_m = -1 for plan ops that launched nothing.
  * 103 (round 5): conv_pp became a bit mask (bits 2, 3, 4: the
@@ -245,6 +246,26 @@ int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, con
                                   const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
                                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* SF2M stochastic sampler (torchcfm's mnist_example.ipynb / conditional_mnist.ipynb, third section: torchsde.sdeint of an SDE module with
+ * drift f(t, y) = model(t, y[, labels]) + score_model(t, y[, labels]) and diagonal diffusion g = sigma; un-vendored, restated as fixed-step
+ * Euler-Maruyama).  Step k (k < n_steps) of the host grid t_grid_host[n_steps + 1] evaluates both nets at t_eval = t_k (reverse: 1 - t_k in fp32)
+ * and updates x <- x + (ca * drift + score) * dt_k + sigma * dW_k with dt_k = t_{k+1} - t_k and ca = +1 (reverse: -1).
+ *   drift, score : two handles with equal in_channels == out_channels == channels and image_size; x: in/out [B, channels, H, W];
+ *   labels       : device int32[B] used by both nets (both built with the same num_classes > 0), or NULL (the reference's forward);
+ *                  a label out of range is reported as by mi355_unet_forward_labels (each handle's error word, MI355_ERR_ARG);
+ *   dW           : injected increments [n_steps, B, channels, H, W], or NULL: sqrt(dt_k) * N(0, 1) from the device Philox stream at
+ *                  (seed, offset = k * n_al), n_al = B*channels*H*W rounded up to a multiple of 4 (the convention of mi355_ddpm_sample);
+ *   outputs      : traj[j] [B, channels, H, W] (j < n_out) = x_k + w_j * (x_{k+1} - x_k) with k = out_step_host[j], w = out_w_host[j] in [0, 1]
+ *                  (w = 0 / 1 store x_k / x_{k+1} exactly): torchsde's linear interpolation of an output time inside step k; traj may be NULL
+ *                  when n_out == 0;
+ *   workspaces   : one per handle, each mi355_unet_workspace_bytes(handle, batch) bytes, 256-byte aligned, distinct.
+ * With n_steps * K <= 1024 (K = num_classes with labels, else 1) each net's emb_layers outputs of every step are computed before the loop (as
+ * mi355_cfm_euler_sample does); the stream is synchronised once after that.  sampler_graph is not used here. */
+int mi355_sf2m_euler_sample(mi355_unet* drift, mi355_unet* score, float* x, int channels, const int32_t* labels, const float* t_grid_host,
+                            int n_steps, float sigma, int reverse, const float* dW, uint64_t seed, const int32_t* out_step_host,
+                            const float* out_w_host, int n_out, float* traj, int batch, void* drift_workspace, int64_t drift_workspace_bytes,
+                            void* score_workspace, int64_t score_workspace_bytes, void* stream);
+
 /* per-step scalars of the DDPM tables (AD/image_diffusion/sde_diffusion.py:127-167), host arrays of length Ns */
 typedef struct mi355_ddpm_tables {
   int32_t Ns;
@@ -295,6 +316,14 @@ int mi355_groupnorm(const float* x, const float* gamma, const float* beta, float
 
 /* x += dt * v  (Euler update) */
 int mi355_euler_step(float* x, const float* v, float dt, int64_t n, void* stream);
+
+/* Euler-Maruyama update of a diagonal-noise Ito SDE (torchsde's Euler step y1 = y0 + f*dt + g*dW), elementwise over n values:
+ *   x <- x + (ca*a + cb*b) * dt + g * dW        (b may be NULL: f = ca*a; ca, cb in {+1, -1}; every operation rounded, left to right)
+ * g: per-element values, or NULL for the scalar g_scalar.  dW: injected increments, or NULL with use_philox = 1: dW = sqrt(dt) * z, z the
+ * mi355_randn stream at (seed, offset), offset a multiple of 4; neither: no noise term.  out: NULL, or out = x_old + w * (x_new - x_old)
+ * written by the same launch (w = 0 / 1: x_old / x_new exactly). */
+int mi355_sde_euler_step(float* x, const float* a, const float* b, float ca, float cb, float dt, const float* g, float g_scalar, const float* dW,
+                         int use_philox, uint64_t seed, uint64_t offset, float* out, float w, int64_t n, void* stream);
 
 /* DDPM ancestral step (sampling.py:59-67 + sde_diffusion.py:220-237), elementwise over n values:
  *   x0 = clip(c_recip*x - c_recipm1*eps, -1, 1); mean = coef1*x0 + coef2*x; x <- mean + sigma*z
