@@ -194,6 +194,7 @@ __global__ void __launch_bounds__(256) guidance_seed_kernel(const float* x, cons
 // x_grad = g_x + vjp; update = -scale * x_grad; optionally x += update ("before"); update is kept for the "after" rule
 __global__ void __launch_bounds__(256) guidance_update_kernel(float* x, const float* g_x, const float* vjp, float scale, int apply, float* update,
                                                             int64_t n) {
+#pragma clang fp contract(off)   // x + u adds the ROUNDED update, as the eager `xi + update` does (no fma of -scale * x_grad into the sum)
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float u = -scale * (g_x[i] + vjp[i]);

@@ -563,7 +563,6 @@ int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const floa
 }
 int mi355_rk_interp(float* out, const float* y0, const float* y1, const float* y_mid, const float* f0, const float* f1, float dt, float x,
                     int64_t n, void* stream) {
-  MI355_REQUIRE(out && y0 && y1 && y_mid && f0 && f1, -1, "rk_interp: null argument");
   return rk_interp_launch(out, y0, y1, y_mid, f0, f1, dt, x, n, S(stream));
 }
 

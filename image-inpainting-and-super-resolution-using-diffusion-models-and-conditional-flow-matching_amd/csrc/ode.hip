@@ -8,10 +8,10 @@ namespace {
 
 struct KPtrs { const float* k[7]; float c[7]; };
 
-__global__ void __launch_bounds__(256) rk_combine_kernel(float* out, const float* y0, KPtrs kp, int nk, int64_t n) {
+__global__ void __launch_bounds__(256) rk_combine_kernel(float* out, const float* y0, KPtrs kp, int nk, int64_t n, int vec) {
   const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i >= n) return;
-  if (i + 4 <= n) {
+  if (i + 4 <= n && vec) {   // vec: every pointer is 16-byte aligned (checked once by the launcher); a view at an odd storage offset goes scalar
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < nk; ++j) {
       const f32x4 kv = *reinterpret_cast<const f32x4*>(kp.k[j] + i);
@@ -21,7 +21,8 @@ __global__ void __launch_bounds__(256) rk_combine_kernel(float* out, const float
     f32x4 y = y0 ? *reinterpret_cast<const f32x4*>(y0 + i) : f32x4{0.f, 0.f, 0.f, 0.f};
     *reinterpret_cast<f32x4*>(out + i) = f32x4{y[0] + acc[0], y[1] + acc[1], y[2] + acc[2], y[3] + acc[3]};
   } else {
-    for (int64_t e = i; e < n; ++e) {
+    const int64_t end = i + 4 < n ? i + 4 : n;
+    for (int64_t e = i; e < end; ++e) {
       float acc = 0.f;
       for (int j = 0; j < nk; ++j) acc += kp.k[j][e] * kp.c[j];
       out[e] = (y0 ? y0[e] : 0.f) + acc;
@@ -62,17 +63,25 @@ __global__ void __launch_bounds__(256) rk_interp_kernel(float* out, const float*
 }  // namespace
 
 int rk_combine_launch(float* out, const float* y0, const float* const* k, const float* c, int nk, int64_t n, hipStream_t s) {
-  MI355_REQUIRE(out && nk >= 0 && nk <= 7, -1, "rk_combine: bad argument");
+  MI355_REQUIRE(nk >= 0 && nk <= 7, -1, "rk_combine: bad argument");
+  if (n <= 0) return 0;   // an empty tensor (its pointer may be null): nothing to do, and a zero-sized grid is a launch error
+  MI355_REQUIRE(out, -1, "rk_combine: bad argument");
   KPtrs kp;
-  for (int j = 0; j < 7; ++j) { kp.k[j] = j < nk ? k[j] : nullptr; kp.c[j] = j < nk ? c[j] : 0.f; }
+  uintptr_t bits = reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(y0);   // a null y0 adds no bits
+  for (int j = 0; j < 7; ++j) {
+    kp.k[j] = j < nk ? k[j] : nullptr; kp.c[j] = j < nk ? c[j] : 0.f;
+    MI355_REQUIRE(j >= nk || k[j], -1, "rk_combine: null stage pointer");
+    bits |= reinterpret_cast<uintptr_t>(kp.k[j]);
+  }
   const int64_t nth = (n + 3) / 4;
-  hipLaunchKernelGGL(rk_combine_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s, out, y0, kp, nk, n);
+  hipLaunchKernelGGL(rk_combine_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s, out, y0, kp, nk, n, (int)((bits & 15) == 0));
   MI355_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
 int rk_sqnorm_launch(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                      hipStream_t s) {
+  if (n <= 0) return 0;   // the sum over no elements adds nothing
   MI355_REQUIRE(a && out, -1, "rk_sqnorm: null argument");
   int64_t blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
@@ -83,6 +92,8 @@ int rk_sqnorm_launch(const float* a, const float* sub, const float* b, const flo
 
 int rk_interp_launch(float* out, const float* y0, const float* y1, const float* ym, const float* f0, const float* f1, float dt, float x,
                      int64_t n, hipStream_t s) {
+  if (n <= 0) return 0;
+  MI355_REQUIRE(out && y0 && y1 && ym && f0 && f1, -1, "rk_interp: null argument");
   hipLaunchKernelGGL(rk_interp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, y0, y1, ym, f0, f1, dt, x, n);
   MI355_CHECK_HIP(hipGetLastError());
   return 0;

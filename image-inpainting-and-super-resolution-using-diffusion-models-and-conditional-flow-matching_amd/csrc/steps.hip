@@ -136,6 +136,7 @@ int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, fl
 
 int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
                      float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "ddpm_step: the Philox offset must be a multiple of 4");
   const uint64_t off4 = offset / 4;
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
     float xv[4], ev[4], zz[4];
@@ -153,6 +154,7 @@ int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, 
 
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,
                           float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "corrector_step: the Philox offset must be a multiple of 4");
   const uint64_t off4 = offset / 4;
   const float kd = 0.5f * dt * delta, kn = sqrtf(dt * delta);
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
@@ -186,6 +188,7 @@ int ddim_step_launch(float* x, const float* eps, float c_recip, float c_recipm1,
 
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb, int use_philox,
                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "replace_mask: the Philox offset must be a multiple of 4");
   const uint64_t off4 = offset / 4;
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
     float xv[4], cv[4], zz[4] = {0.f, 0.f, 0.f, 0.f};
@@ -272,6 +275,7 @@ int to_unit_range_launch(const float* x, float* out, int64_t n, hipStream_t s) {
 }
 
 int randn_launch(float* out, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "randn: the Philox offset must be a multiple of 4");
   const uint64_t off4 = offset / 4;
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
     float zz[4];

@@ -34,7 +34,8 @@ from .sde_diffusion import DDPM
 
 _ops = default_ops
 _injected: Optional[List[torch.Tensor]] = None
-_draw_counter = 0
+_draw_counter = 0   # device-noise draws (host loop) and fast-path calls so far: the fast path keys each call with it
+_noise_offset = 0   # elements of the host-loop Philox stream consumed so far (always a multiple of 4)
 
 
 @contextlib.contextmanager
@@ -74,28 +75,31 @@ def make_eps_model(network, ddpm: DDPM):
 
 
 class _Noise:
-    """Hands out one noise draw per reference `torch.randn_like` call."""
+    """Hands out one noise draw per reference `torch.randn_like` call.
+
+    Device noise: every draw takes the next `stride` elements (this tensor's size rounded up to a multiple of 4, one Philox counter = 4
+    elements) of the process-wide stream, starting where the previous draw - of this or of any earlier sampler call, whatever its batch
+    size - ended.  `_noise_offset` counts elements consumed, so ranges never overlap; the first call of a process starts at 0."""
 
     def __init__(self, like: torch.Tensor):
-        global _draw_counter
         self.like = like
         self.injected = list(_injected) if _injected is not None else None
         self.seed = int(torch.initial_seed()) & ((1 << 63) - 1)
-        self.base = _draw_counter
         self.k = 0
         n = like.numel()
         self.stride = (n + 3) // 4 * 4
 
     def next(self):
         """-> (z tensor or None, philox (seed, offset) or None)"""
-        global _draw_counter
+        global _draw_counter, _noise_offset
         if self.injected is not None:
             if self.k >= len(self.injected):
                 raise RuntimeError("injected noise exhausted")
             z = self.injected[self.k].to(self.like.device, torch.float32).contiguous()
             self.k += 1
             return z, None
-        off = (self.base + self.k) * self.stride
+        off = _noise_offset
+        _noise_offset += self.stride
         self.k += 1
         _draw_counter += 1
         return None, (self.seed, off)

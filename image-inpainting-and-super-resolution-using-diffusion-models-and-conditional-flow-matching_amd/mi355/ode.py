@@ -6,7 +6,8 @@ torchdiffeq is not vendored (version unpinned); its published algorithm (rk_comm
 misc.py of the 0.2.x line) is restated here: Hairer initial step, FSAL Dormand-Prince stages, RMS error norm
 (max over components for tuple states), accept iff ratio <= 1, step factor min(10, max(0.9 / ratio**(1/5), 0.2))
 with the lower bound lifted to 1 on accepted steps, quartic dense output at the requested time.
-No reference test pins it: "parity unpinned"; checked against oracle/cfm_ref.dopri5 (same restatement, PyTorch-CPU).
+No reference test pins it: "parity unpinned"; checked against oracle/cfm_ref.dopri5 (same restatement, PyTorch-CPU) and, without a
+shared source, against the order conditions of the tables, an analytic solution and scipy's RK45 (tests/test_dopri5_cpu.py).
 
 Stage combinations, error norms and the dense output are HIP kernels (csrc/ode.hip); the controller needs one
 scalar per step and stays on the host.
@@ -40,18 +41,21 @@ State = List[torch.Tensor]
 
 class Dopri5:
     def __init__(self, func: Callable[[float, State], Sequence[torch.Tensor]], rtol: float, atol: float, ops=None,
-                 safety=0.9, ifactor=10.0, dfactor=0.2, max_num_steps=100000, sync_norm=True):
+                 safety=0.9, ifactor=10.0, dfactor=0.2, max_num_steps=100000, sync_norm=True, dtype=torch.float32):
+        """dtype: the state's type.  The HIP ops are fp32; the CPU tests measure the tables' orders with an fp64 op table."""
         self.func, self.rtol, self.atol = func, float(rtol), float(atol)
         self.ops = ops or default_ops
         self.safety, self.ifactor, self.dfactor, self.max_num_steps = safety, ifactor, dfactor, max_num_steps
         self.nfe = 0
-        self.n_steps = 0
+        self.n_steps = 0        # attempted steps, rejected ones included: nfe == 6 * n_steps + 2
+        self.n_rejected = 0
+        self.dtype = dtype
         self.sync_norm = sync_norm
 
     # ---- helpers -----------------------------------------------------------------------------------------
     def _f(self, t: float, y: State) -> State:
         self.nfe += 1
-        return [v.float().contiguous() for v in self.func(t, y)]
+        return [v.to(self.dtype).contiguous() for v in self.func(t, y)]
 
     def _norm(self, a: State, sub=None, b=None, b2=None, atol=1.0, rtol=0.0) -> float:
         """max over components of rms((a - sub) / (atol + rtol * max(|b|, |b2|)))  (torchdiffeq _mixed_norm / _rms_norm)."""
@@ -88,12 +92,37 @@ class Dopri5:
             h1 = (0.01 / max(d1, d2)) ** (1.0 / 5.0)
         return min(100 * h0, h1)
 
+    # ---- one step ----------------------------------------------------------------------------------------------
+    def _step(self, t: float, dt: float, y0: State, f0: State):
+        """One Dormand-Prince step from (t, y0) with f0 = f(t, y0) -> (y1, f1, err, ks): the 5th-order state, f(t + dt, y1) (FSAL:
+        the last stage), the embedded error estimate and the 7 stage derivatives."""
+        t1 = t + dt
+        ks = [f0]
+        yi = None
+        for a, beta in zip(ALPHA, BETA):
+            ti = t1 if a == 1.0 else t + a * dt
+            yi = self._combine(y0, ks, [b * dt for b in beta])
+            ks.append(self._f(ti, yi))
+        err = self._combine([None] * len(y0), ks, [c * dt for c in C_ERROR])
+        return yi, ks[-1], err, ks                                   # FSAL: c_sol == beta[-1]
+
+    def _midpoint(self, y0: State, ks: List[State], dt: float) -> State:
+        return self._combine(y0, ks, [c * dt for c in C_MID])
+
+    def _dense(self, interp, t_eval: float) -> State:
+        """interp = (y0, y1, ymid, f0, f1, t0, dt) of an accepted step -> the quartic dense output at t_eval."""
+        ya, yb, ym, fa, fb, ta, dta = interp
+        out = [torch.empty_like(v) for v in ya]
+        for i in range(len(ya)):
+            self.ops.rk_interp(out[i], ya[i], yb[i], ym[i], fa[i], fb[i], dta, (t_eval - ta) / dta)
+        return out
+
     # ---- integration ---------------------------------------------------------------------------------------
     @torch.no_grad()
     def integrate_times(self, y0: Sequence[torch.Tensor], times: Sequence[float]) -> List[State]:
         """States at times[1:], one continuous adaptive solve with dense output (torchdiffeq: _before_integrate once,
         then per output time `while next_t > t1: step` followed by `_interp_evaluate`)."""
-        y0 = [v.detach().float().contiguous() for v in y0]
+        y0 = [v.detach().to(self.dtype).contiguous() for v in y0]
         t = float(times[0])
         f0 = self._f(t, y0)
         dt = self._initial_step(t, y0, f0)
@@ -104,20 +133,13 @@ class Dopri5:
                 if self.n_steps >= self.max_num_steps:
                     raise RuntimeError("dopri5: max_num_steps exceeded")
                 self.n_steps += 1
-                t1 = t + dt
-                ks = [f0]
-                yi = None
-                for a, beta in zip(ALPHA, BETA):
-                    ti = t1 if a == 1.0 else t + a * dt
-                    yi = self._combine(y0, ks, [b * dt for b in beta])
-                    ks.append(self._f(ti, yi))
-                y1, f1 = yi, ks[-1]                                  # FSAL: c_sol == beta[-1]
-                err = self._combine([None] * len(y0), ks, [c * dt for c in C_ERROR])
+                y1, f1, err, ks = self._step(t, dt, y0, f0)
                 ratio = self._norm(err, b=y0, b2=y1, atol=self.atol, rtol=self.rtol)
                 if ratio <= 1.0:
-                    ymid = self._combine(y0, ks, [c * dt for c in C_MID])
-                    interp = (y0, y1, ymid, f0, f1, t, dt)
-                    t, y0, f0 = t1, y1, f1
+                    interp = (y0, y1, self._midpoint(y0, ks, dt), f0, f1, t, dt)
+                    t, y0, f0 = t + dt, y1, f1
+                else:
+                    self.n_rejected += 1
                 if ratio == 0.0:
                     factor = self.ifactor
                 else:
@@ -127,11 +149,7 @@ class Dopri5:
             if interp is None:      # requested time equals the start time
                 outs.append([v.clone() for v in y0])
                 continue
-            ya, yb, ym, fa, fb, ta, dta = interp
-            out = [torch.empty_like(v) for v in ya]
-            for i in range(len(ya)):
-                self.ops.rk_interp(out[i], ya[i], yb[i], ym[i], fa[i], fb[i], dta, (t_end - ta) / dta)
-            outs.append(out)
+            outs.append(self._dense(interp, t_end))
         return outs
 
     def integrate(self, y0: Sequence[torch.Tensor], t0: float, t_end: float) -> State:

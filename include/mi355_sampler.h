@@ -382,7 +382,9 @@ int mi355_paint_patch(const float* images, const int32_t* top, const int32_t* le
 int mi355_quantize_u8(const float* x, uint8_t* out, int64_t n, void* stream);
 /* x.clip(-1,1)/2 + 0.5  cifar10/utils_cifar.py:40-41 */
 int mi355_to_unit_range(const float* x, float* out, int64_t n, void* stream);
-/* N(0,1) fill from the device Philox4x32-10 stream (seed, offset) */
+/* N(0,1) fill from the device Philox4x32-10 stream (seed, offset): element e of the stream is lane e % 4 of the Box-Muller pair of
+ * Philox counter e / 4, so out[j] is stream element offset + j.  `offset` must be a multiple of 4 (one counter = 4 elements); any other
+ * value is an argument error here and in every step op above that takes (use_philox, seed, offset). */
 int mi355_randn(float* out, uint64_t seed, uint64_t offset, int64_t n, void* stream);
 
 /* Adaptive Dormand-Prince 5(4) building blocks (torchdiffeq.odeint(method="dopri5"): cifar10/compute_fid.py:80-85,

@@ -534,11 +534,21 @@ def test_cfg3_b512_amortized_ddpm_vs_oracle():
     emax, _, rms = _report("cfg3 B=512 Ns=25 bf16 vs fp32", got16, got32)
     assert torch.isfinite(got16).all() and rms < 0.05 and (got16 - got32).abs().mean() < 0.02
     # the device-Philox path (the throughput configuration) runs and is deterministic in the seed
+    # (the fast path keys each call with the seed and the process-wide call counter: both are put back before the second run)
     torch.manual_seed(5)
+    counter = sampling._draw_counter
     a = fn(xT.to(DEV), cond.to(DEV))
+    assert sampling._draw_counter == counter + 1
     torch.manual_seed(5)
-    sampling._draw_counter = 0
+    sampling._draw_counter = counter
+    b = fn(xT.to(DEV), cond.to(DEV))
     assert torch.isfinite(a).all() and float(a.abs().max()) <= 1.0
+    assert torch.equal(a, b)
+    torch.manual_seed(6)
+    sampling._draw_counter = counter
+    c = fn(xT.to(DEV), cond.to(DEV))
+    assert torch.isfinite(c).all() and float(c.abs().max()) <= 1.0
+    assert not torch.equal(a, c) and (a - c).abs().mean().item() > 1e-3     # another seed: another sample, not a few flipped pixels
 
 
 # ---- (d) cfg 5: 128 px, attention at 32 / 16 / 8, free-form mask -----------------------------------------------------------------
