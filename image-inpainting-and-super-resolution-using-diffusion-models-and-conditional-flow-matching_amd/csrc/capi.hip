@@ -30,7 +30,7 @@ const mi355_debug_config& mi355_default_debug() {
 
 extern "C" {
 
-int mi355_version(void) { return 106; }
+int mi355_version(void) { return 107; }
 void mi355_debug_defaults(mi355_debug_config* c) {
   if (!c) return;
   std::memset(c, 0, sizeof(*c));
@@ -873,6 +873,198 @@ int mi355_qkv_attention_vjp(const float* qkv, const float* grad_out, float* grad
   b.N = batch; b.T = length; b.heads = heads; b.ch = head_channels; b.new_order = new_order;
   if ((rc = attention_bwd_launch(b, s))) return rc;
   return unpack_nchw_launch(dtype, dq, batch, length, 3 * C, grad_qkv, s);
+}
+
+// ---- GroupNorm test ops (ABI 107): the kernels the network launches, one op each, NCHW fp32 at the boundary ------------------------
+// Device scratch is the op's own (ExScratch); every op synchronises the stream before it returns.
+namespace {
+int gn_op_dtype(int dtype, bool backward, const char* who, int* out) {
+  if (backward) {
+    if (dtype != MI355_F32 && dtype != MI355_BF16) { mi355_set_error(std::string(who) + ": dtype must be MI355_F32 or MI355_BF16 (the backward kernels have no other form)"); return -1; }
+  } else if (dtype != MI355_F32 && dtype != MI355_BF16 && dtype != MI355_F16) { mi355_set_error(std::string(who) + ": dtype must be MI355_F32, MI355_BF16 or MI355_F16"); return -1; }
+  *out = dtype == MI355_F16 ? DT_F16 : dtype;
+  return 0;
+}
+}  // namespace
+
+int mi355_gn_affine(const float* x, const float* x1, const float* gamma, const float* beta, const float* film, float eps, float* a, float* b,
+                    float* mean, float* rstd, float* y, int y_silu, int32_t* form, int batch, int c0, int c1, int hw, int dtype, void* stream) {
+  MI355_REQUIRE(x && gamma && beta && a && b && batch > 0 && c0 > 0 && c1 >= 0 && hw > 0, -1, "gn_affine: bad argument");
+  MI355_REQUIRE((x1 != nullptr) == (c1 > 0) && (mean != nullptr) == (rstd != nullptr), -1, "gn_affine: x1 / c1 and mean / rstd go together");
+  if (int rc = gn_op_dtype(dtype, false, "gn_affine", &dtype)) return rc;
+  hipStream_t s = S(stream);
+  const size_t esz = dtype == 0 ? 4 : 2;
+  const int C = c0 + c1;
+  ExScratch xs;
+  void* p0 = xs.get((size_t)batch * hw * c0 * esz);
+  void* p1 = x1 ? xs.get((size_t)batch * hw * c1 * esz) : nullptr;
+  void* py = y ? xs.get((size_t)batch * hw * C * esz) : nullptr;
+  MI355_REQUIRE(p0 && (!x1 || p1) && (!y || py), -2, "gn_affine: out of device memory");
+  int rc;
+  if ((rc = pack_nhwc_launch(dtype, x, c0, nullptr, 0, batch, hw, c0, p0, s))) return rc;
+  if (x1 && (rc = pack_nhwc_launch(dtype, x1, c1, nullptr, 0, batch, hw, c1, p1, s))) return rc;
+  if (py) MI355_CHECK_HIP(hipMemsetAsync(py, 0xFF, (size_t)batch * hw * C * esz, s));   // NaN in every element type until the kernel writes it
+  GnDesc g; g.dtype = dtype; g.src0 = p0; g.C0 = c0; g.src1 = p1; g.C1 = c1; g.N = batch; g.HW = hw; g.eps = eps;
+  g.gamma = gamma; g.beta = beta; g.film = film; g.film_stride = film ? 2 * C : 0;
+  g.a = a; g.b = b; g.mean = mean; g.rstd = rstd; g.y = py; g.y_silu = y_silu;
+  if (form) *form = gn_affine_form(g);
+  if ((rc = gn_affine_launch(g, s))) return rc;
+  if (py && (rc = unpack_nchw_launch(dtype, py, batch, hw, C, y, s))) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mi355_conv2d_gn(const float* x0, const float* w0_host, const float* bias0_host, float* y0, int cin0, int cout0, const float* x1,
+                    const float* w1_host, const float* bias1_host, float* y1, int cin1, int cout1, int batch, int h, int w, int ksize, int stride,
+                    int resample, const float* gamma, const float* beta, const float* film, float eps, float* a, float* b, int dtype,
+                    const mi355_debug_config* debug, int32_t info[6], void* stream) {
+  const mi355_debug_config& K = debug ? *debug : mi355_default_debug();
+  MI355_REQUIRE(x0 && w0_host && y0 && gamma && beta && a && b && info && batch > 0, -1, "conv2d_gn: bad argument");
+  MI355_REQUIRE((x1 != nullptr) == (cout1 > 0) && (!x1 || (w1_host && y1 && cin1 > 0)), -1, "conv2d_gn: the second producer needs x1, w1, y1, cin1 and cout1");
+  MI355_REQUIRE((stride == 1 || stride == 2) && (resample == 0 || resample == 2) && !(stride == 2 && resample), -1, "conv2d_gn: stride 1 or 2, resample 0 or 2 (nearest x2)");
+  if (int rc = gn_op_dtype(dtype, false, "conv2d_gn", &dtype)) return rc;
+  hipStream_t s = S(stream);
+  const int CH = dtype == 0 ? 16 : 32;
+  const size_t esz = dtype == 0 ? 4 : 2;
+  ExScratch xs;
+  const float* xin[2] = {x0, x1}; const float* wh[2] = {w0_host, w1_host}; const float* bh[2] = {bias0_host, bias1_host};
+  float* yo[2] = {y0, y1}; const int cin[2] = {cin0, cin1}, cout[2] = {cout0, cout1};
+  void* out_dev[2] = {nullptr, nullptr}; float* st[2] = {nullptr, nullptr};
+  int Ho = 0, Wo = 0, rc;
+  for (int i = 0; i < 6; ++i) info[i] = 0;
+  std::vector<char> packed[2];
+  for (int k = 0; k < (x1 ? 2 : 1); ++k) {
+    MI355_REQUIRE(cout[k] % 32 == 0, -2, "conv2d_gn: NHWC outputs need cout % 32 == 0");
+    const int cpad = (cin[k] + CH - 1) / CH * CH;
+    ConvDesc d; d.dtype = dtype; d.N = batch; d.Hs = h; d.Ws = w; d.C0 = cpad; d.ks = ksize; d.Cout = cout[k]; d.knobs = &K;
+    d.mode = stride == 2 ? CONV_STRIDE2 : (resample == 2 ? CONV_UP2 : CONV_UNIT);
+    if (cin[k] <= 8) d.cin_real = cin[k];
+    const ConvGeom g = conv_geometry(d);
+    MI355_REQUIRE(k == 0 || (g.Ho == Ho && g.Wo == Wo), -2, "conv2d_gn: the producers' outputs differ in size");
+    Ho = g.Ho; Wo = g.Wo;
+    void* xd = xs.get((size_t)batch * h * w * cpad * esz);
+    const size_t wbytes = conv_packed_weight_bytes(dtype, cout[k], cin[k], ksize, 0);
+    void* wd = xs.get(wbytes);
+    float* bd = reinterpret_cast<float*>(xs.get((size_t)cout[k] * 4));
+    out_dev[k] = xs.get((size_t)batch * Ho * Wo * cout[k] * esz);
+    const int cap = 4 * ((Ho * Wo + 63) / 64) + 8;   // the plan builder's stats_cap (unet_engine.hip)
+    st[k] = reinterpret_cast<float*>(xs.get((size_t)batch * cap * (cout[k] / 4) * 2 * 4));
+    uint32_t* errw = reinterpret_cast<uint32_t*>(xs.get(256));
+    MI355_REQUIRE(xd && wd && bd && out_dev[k] && st[k] && errw, -2, "conv2d_gn: out of device memory");
+    MI355_CHECK_HIP(hipMemsetAsync(errw, 0, 256, s));
+    MI355_CHECK_HIP(hipMemsetAsync(st[k], 0xFF, (size_t)batch * cap * (cout[k] / 4) * 2 * 4, s));   // a slot no wave writes stays NaN
+    if ((rc = pack_nhwc_launch(dtype, xin[k], cin[k], nullptr, 0, batch, h * w, cpad, xd, s))) return rc;
+    packed[k].resize(wbytes);
+    conv_pack_weights(dtype, wh[k], cout[k], cin[k], ksize, packed[k].data(), 0);
+    MI355_CHECK_HIP(hipMemcpyAsync(wd, packed[k].data(), wbytes, hipMemcpyHostToDevice, s));
+    if (bh[k]) MI355_CHECK_HIP(hipMemcpyAsync(bd, bh[k], (size_t)cout[k] * 4, hipMemcpyHostToDevice, s));
+    d.src0 = xd; d.w = wd; d.bias = bh[k] ? bd : nullptr; d.out = out_dev[k]; d.out_mode = OUT_NHWC; d.err = errw;
+    d.gn_stats = st[k]; d.gn_slots_cap = cap;
+    ConvRoute route;
+    if ((rc = conv_route(d, &route)) || (rc = conv_launch(d, route, s))) return rc;
+    info[3 * k] = route.kernel; info[3 * k + 1] = route.gn_slots; info[3 * k + 2] = route.form;
+    if ((rc = unpack_nchw_launch(dtype, out_dev[k], batch, Ho * Wo, cout[k], yo[k], s))) return rc;
+    MI355_CHECK_HIP(hipStreamSynchronize(s));   // the packed weights are staged from host memory
+    uint32_t ev = 0;
+    MI355_CHECK_HIP(hipMemcpy(&ev, errw, 4, hipMemcpyDeviceToHost));
+    if (ev) { mi355_set_error("conv2d_gn: the persistent kernel gave up a bounded counter wait: the output is invalid"); return MI355_ERR_TIMEOUT; }
+  }
+  if (info[1] > 0 && (!x1 || info[4] > 0)) {
+    GnFinDesc f; f.stats0 = st[0]; f.slots0 = info[1]; f.C0 = cout0;
+    if (x1) { f.stats1 = st[1]; f.slots1 = info[4]; f.C1 = cout1; }
+    f.N = batch; f.HW = Ho * Wo; f.eps = eps; f.gamma = gamma; f.beta = beta; f.film = film; f.film_stride = film ? 2 * (cout0 + cout1) : 0;
+    f.a = a; f.b = b; f.dtype = dtype; f.src0 = out_dev[0]; f.src1 = out_dev[1];
+    if ((rc = gn_finalize_launch(f, s))) return rc;
+  }
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mi355_affine_pool(const float* x, const float* a, const float* b, int silu, float* out, int batch, int channels, int h, int w, int dtype,
+                      void* stream) {
+  MI355_REQUIRE(x && out && (a != nullptr) == (b != nullptr) && batch > 0 && channels > 0 && h > 0 && w > 0, -1, "affine_pool: bad argument");
+  if (int rc = gn_op_dtype(dtype, false, "affine_pool", &dtype)) return rc;
+  hipStream_t s = S(stream);
+  const size_t esz = dtype == 0 ? 4 : 2;
+  ExScratch xs;
+  void* pi = xs.get((size_t)batch * h * w * channels * esz);
+  void* po = xs.get((size_t)batch * (h / 2) * (w / 2) * channels * esz);
+  MI355_REQUIRE(pi && po, -2, "affine_pool: out of device memory");
+  int rc;
+  if ((rc = pack_nhwc_launch(dtype, x, channels, nullptr, 0, batch, h * w, channels, pi, s))) return rc;
+  MI355_CHECK_HIP(hipMemsetAsync(po, 0xFF, (size_t)batch * (h / 2) * (w / 2) * channels * esz, s));
+  if ((rc = affine_pool_launch(dtype, pi, a, b, silu, po, batch, h, w, channels, s))) return rc;
+  if ((rc = unpack_nchw_launch(dtype, po, batch, (h / 2) * (w / 2), channels, out, s))) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mi355_gn_silu_vjp(const float* x0, const float* x1, const float* gamma, const float* beta, const float* film, float eps, int silu,
+                      const float* du, int du_stride, float* g0, float* g1, int acc0, int acc1, int batch, int c0, int c1, int hw, int dtype,
+                      void* stream) {
+  MI355_REQUIRE(x0 && gamma && beta && du && g0 && batch > 0 && c0 > 0 && c1 >= 0 && hw > 0, -1, "gn_silu_vjp: bad argument");
+  MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_BF16, -1, "gn_silu_vjp: dtype must be MI355_F32 or MI355_BF16 (the GroupNorm backward has no other form)");
+  MI355_REQUIRE((x1 != nullptr) == (c1 > 0) && (x1 != nullptr) == (g1 != nullptr), -1, "gn_silu_vjp: x1, g1 and c1 go together");
+  const int C = c0 + c1;
+  MI355_REQUIRE(du_stride >= C, -2, "gn_silu_vjp: du_stride must be at least c0 + c1");
+  hipStream_t s = S(stream);
+  const size_t esz = dtype == 0 ? 4 : 2;
+  ExScratch xs;
+  void* p0 = xs.get((size_t)batch * hw * c0 * esz);
+  void* p1 = x1 ? xs.get((size_t)batch * hw * c1 * esz) : nullptr;
+  void* pd = xs.get((size_t)batch * hw * du_stride * esz);
+  void* q0 = xs.get((size_t)batch * hw * c0 * esz);
+  void* q1 = x1 ? xs.get((size_t)batch * hw * c1 * esz) : nullptr;
+  float* ab = reinterpret_cast<float*>(xs.get(((size_t)2 * batch * C + (size_t)2 * batch * 32) * 4));
+  MI355_REQUIRE(p0 && pd && q0 && ab && (!x1 || (p1 && q1)), -2, "gn_silu_vjp: out of device memory");
+  int rc;
+  if ((rc = pack_nhwc_launch(dtype, x0, c0, nullptr, 0, batch, hw, c0, p0, s))) return rc;
+  if (x1 && (rc = pack_nhwc_launch(dtype, x1, c1, nullptr, 0, batch, hw, c1, p1, s))) return rc;
+  if ((rc = pack_nhwc_launch(dtype, du, C, nullptr, 0, batch, hw, du_stride, pd, s))) return rc;   // channels C .. du_stride: zero padding, as a channel-padded dgrad conv leaves it
+  // a gradient the kernel accumulates into is the caller's, packed; one it overwrites starts as NaN
+  if (acc0) { if ((rc = pack_nhwc_launch(dtype, g0, c0, nullptr, 0, batch, hw, c0, q0, s))) return rc; }
+  else MI355_CHECK_HIP(hipMemsetAsync(q0, 0xFF, (size_t)batch * hw * c0 * esz, s));
+  if (x1) {
+    if (acc1) { if ((rc = pack_nhwc_launch(dtype, g1, c1, nullptr, 0, batch, hw, c1, q1, s))) return rc; }
+    else MI355_CHECK_HIP(hipMemsetAsync(q1, 0xFF, (size_t)batch * hw * c1 * esz, s));
+  }
+  // forward statistics as a differentiable plan keeps them (unet_engine.hip: a, b, mean, rstd of the site), then the backward kernel
+  GnDesc g; g.dtype = dtype; g.src0 = p0; g.C0 = c0; g.src1 = p1; g.C1 = c1; g.N = batch; g.HW = hw; g.eps = eps;
+  g.gamma = gamma; g.beta = beta; g.film = film; g.film_stride = film ? 2 * C : 0;
+  g.a = ab; g.b = ab + (size_t)batch * C; g.mean = ab + (size_t)2 * batch * C; g.rstd = g.mean + (size_t)batch * 32;
+  if ((rc = gn_affine_launch(g, s))) return rc;
+  GnBwdDesc d; d.dtype = dtype; d.x0 = p0; d.x1 = p1; d.C0 = c0; d.C1 = c1; d.du = pd; d.du_stride = du_stride; d.N = batch; d.HW = hw; d.silu = silu;
+  d.a = g.a; d.b = g.b; d.mean = g.mean; d.rstd = g.rstd; d.g0 = q0; d.g1 = q1; d.acc0 = acc0; d.acc1 = acc1;
+  if ((rc = gn_silu_bwd_launch(d, s))) return rc;
+  if ((rc = unpack_nchw_launch(dtype, q0, batch, hw, c0, g0, s))) return rc;
+  if (x1 && (rc = unpack_nchw_launch(dtype, q1, batch, hw, c1, g1, s))) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mi355_grad_gather(const float* src, float* dst, int batch, int cd, int hd, int wd, int hs, int ws, int src_channels, int src_coff, int mode,
+                      int accumulate, float scale, int dtype, void* stream) {
+  MI355_REQUIRE(src && dst && batch > 0 && cd > 0 && hd > 0 && wd > 0 && hs > 0 && ws > 0, -1, "grad_gather: bad argument");
+  MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_BF16, -1, "grad_gather: dtype must be MI355_F32 or MI355_BF16 (the gather kernels have no other form)");
+  MI355_REQUIRE(src_coff >= 0 && src_coff + cd <= src_channels, -2, "grad_gather: channels src_coff .. src_coff + cd must lie inside the source");
+  // every source pixel the mode reads must exist (the kernel does not clamp): identity; 2x2 blocks; half-resolution; zero insertion (any source size)
+  const bool fits = mode == GATHER_SAME ? (hs == hd && ws == wd) : mode == GATHER_POOL ? (hs == 2 * hd && ws == 2 * wd)
+                  : mode == GATHER_UP ? (2 * hs >= hd && 2 * ws >= wd) : mode == GATHER_STUFF;
+  MI355_REQUIRE(fits, -2, "grad_gather: source size does not match the mode");
+  hipStream_t s = S(stream);
+  const size_t esz = dtype == 0 ? 4 : 2;
+  ExScratch xs;
+  void* ps = xs.get((size_t)batch * hs * ws * src_channels * esz);
+  void* pd = xs.get((size_t)batch * hd * wd * cd * esz);
+  MI355_REQUIRE(ps && pd, -2, "grad_gather: out of device memory");
+  int rc;
+  if ((rc = pack_nhwc_launch(dtype, src, src_channels, nullptr, 0, batch, hs * ws, src_channels, ps, s))) return rc;
+  if (accumulate) { if ((rc = pack_nhwc_launch(dtype, dst, cd, nullptr, 0, batch, hd * wd, cd, pd, s))) return rc; }
+  else MI355_CHECK_HIP(hipMemsetAsync(pd, 0xFF, (size_t)batch * hd * wd * cd * esz, s));
+  if ((rc = grad_gather_launch(dtype, pd, ps, batch, hd, wd, cd, hs, ws, src_channels, src_coff, mode, accumulate, scale, s))) return rc;
+  if ((rc = unpack_nchw_launch(dtype, pd, batch, hd * wd, cd, dst, s))) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
 }
 
 }  // extern "C"

@@ -7,6 +7,13 @@
 //
 // HBM-bound: one pass over the activation, 16 B per lane, a workgroup per image; lanes keep
 // per-channel fp32 partial sums (a 16-B fragment = 4 or 8 fixed channels), reduced through LDS.
+//
+// Statistics never form E[x^2] - mean^2 of the raw values (that cancels once |mean| >> std: 6e-3 error in the normalised value at
+// mean / std = 100).  A lane sums (x - pivot) and (x - pivot)^2 about its own first pixel, turns them into (mean, M2 = sum of squared
+// deviations) of its n pixels, and the partials are merged with the pairwise update of Chan, Golub & LeVeque (1979),
+//   M2 = sum M2_t + sum n_t (mean_t - mean)^2,
+// lanes -> channel -> group, every mean taken relative to the first partial so that the differences, not the offsets, are summed.
+// A constant group gives M2 = 0 exactly (rstd = 1 / sqrt(eps)); still one pass over memory.
 #include "ops.h"
 
 namespace {
@@ -32,11 +39,13 @@ __global__ void __launch_bounds__(GN_THREADS + 64) gn_affine_kernel(GnKArgs p) {
   extern __shared__ __attribute__((aligned(16))) float red[];
   const int C = p.C0 + p.C1, CV = C / V;
   const int ppi = GN_THREADS / CV;  // pixels handled per sweep
-  float* red_s = red;                       // [ppi][C]
-  float* red_q = red + (size_t)ppi * C;     // [ppi][C]
-  float* ch_s = red_q + (size_t)ppi * C;    // [C]
+  float* red_s = red;                       // [ppi][C] mean of the lane's pixels minus its pivot
+  float* red_q = red + (size_t)ppi * C;     // [ppi][C] their M2
+  float* red_p = red_q + (size_t)ppi * C;   // [ppi][C] the pivot (a mean is kept as pivot + small part: adding them would round at the offset's size)
+  float* ch_s = red_p + (size_t)ppi * C;    // [C]
   float* ch_q = ch_s + C;                   // [C]
-  float* g_mean = ch_q + C;                 // [groups]
+  float* ch_p = ch_q + C;                   // [C]
+  float* g_mean = ch_p + C;                 // [groups]
   float* g_rstd = g_mean + p.groups;
   const int tid = threadIdx.x, n = blockIdx.x;
   if (tid >= GN_THREADS) { l2_warm_wave(p.warm, p.warm_bytes); return; }   // the extra wave (launched only when there is something to warm)
@@ -60,14 +69,17 @@ __global__ void __launch_bounds__(GN_THREADS + 64) gn_affine_kernel(GnKArgs p) {
     sp += (size_t)n * p.HW * Cs;
 #pragma unroll
     for (int i = 0; i < NL; ++i) keep[i] = *reinterpret_cast<const u32x4*>(sp + (size_t)(prow + i * ppi) * Cs);
+    float pv[V];   // pivot: this lane's first pixel
+    frag_to_float(keep[0], pv, T());
 #pragma unroll
     for (int i = 0; i + 3 < NL; i += 4) {   // the summation order of the general form
       float f0[V], f1[V], f2[V], f3[V];
       frag_to_float(keep[i], f0, T()); frag_to_float(keep[i + 1], f1, T()); frag_to_float(keep[i + 2], f2, T()); frag_to_float(keep[i + 3], f3, T());
 #pragma unroll
       for (int j = 0; j < V; ++j) {
-        s[j] += (f0[j] + f1[j]) + (f2[j] + f3[j]);
-        q[j] += (f0[j] * f0[j] + f1[j] * f1[j]) + (f2[j] * f2[j] + f3[j] * f3[j]);
+        const float d0 = f0[j] - pv[j], d1 = f1[j] - pv[j], d2 = f2[j] - pv[j], d3 = f3[j] - pv[j];
+        s[j] += (d0 + d1) + (d2 + d3);
+        q[j] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
       }
     }
 #pragma unroll
@@ -75,16 +87,23 @@ __global__ void __launch_bounds__(GN_THREADS + 64) gn_affine_kernel(GnKArgs p) {
       float f0[V];
       frag_to_float(keep[i], f0, T());
 #pragma unroll
-      for (int j = 0; j < V; ++j) { s[j] += f0[j]; q[j] += f0[j] * f0[j]; }
+      for (int j = 0; j < V; ++j) { const float d0 = f0[j] - pv[j]; s[j] += d0; q[j] += d0 * d0; }
     }
 #pragma unroll
-    for (int j = 0; j < V; ++j) { red_s[prow * C + cb + j] = s[j]; red_q[prow * C + cb + j] = q[j]; }
+    for (int j = 0; j < V; ++j) {   // (mean, M2) of this lane's NL pixels
+      const float ds = s[j] * (1.0f / NL);
+      red_s[prow * C + cb + j] = ds; red_p[prow * C + cb + j] = pv[j]; red_q[prow * C + cb + j] = fmaxf(q[j] - s[j] * ds, 0.f);
+    }
   } else if (prow < ppi) {
     const bool from0 = cb < p.C0;
     const T* sp = from0 ? reinterpret_cast<const T*>(p.src0) + cb : reinterpret_cast<const T*>(p.src1) + (cb - p.C0);
     const int Cs = from0 ? p.C0 : p.C1;
     sp += (size_t)n * p.HW * Cs;
     int pix = prow;
+    float pv[V];   // pivot: this lane's first pixel (a lane row beyond a tiny image has no pixel: n = 0 below)
+#pragma unroll
+    for (int j = 0; j < V; ++j) pv[j] = 0.f;
+    if (prow < p.HW) frag_to_float(*reinterpret_cast<const u32x4*>(sp + (size_t)prow * Cs), pv, T());
     for (; pix + 3 * ppi < p.HW; pix += 4 * ppi) {  // 4 independent 16-B loads in flight
       u32x4 r0 = *reinterpret_cast<const u32x4*>(sp + (size_t)pix * Cs);
       u32x4 r1 = *reinterpret_cast<const u32x4*>(sp + (size_t)(pix + ppi) * Cs);
@@ -94,8 +113,9 @@ __global__ void __launch_bounds__(GN_THREADS + 64) gn_affine_kernel(GnKArgs p) {
       frag_to_float(r0, f0, T()); frag_to_float(r1, f1, T()); frag_to_float(r2, f2, T()); frag_to_float(r3, f3, T());
 #pragma unroll
       for (int j = 0; j < V; ++j) {
-        s[j] += (f0[j] + f1[j]) + (f2[j] + f3[j]);
-        q[j] += (f0[j] * f0[j] + f1[j] * f1[j]) + (f2[j] * f2[j] + f3[j] * f3[j]);
+        const float d0 = f0[j] - pv[j], d1 = f1[j] - pv[j], d2 = f2[j] - pv[j], d3 = f3[j] - pv[j];
+        s[j] += (d0 + d1) + (d2 + d3);
+        q[j] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
       }
     }
     for (; pix < p.HW; pix += ppi) {
@@ -103,25 +123,44 @@ __global__ void __launch_bounds__(GN_THREADS + 64) gn_affine_kernel(GnKArgs p) {
       float f0[V];
       frag_to_float(r0, f0, T());
 #pragma unroll
-      for (int j = 0; j < V; ++j) { s[j] += f0[j]; q[j] += f0[j] * f0[j]; }
+      for (int j = 0; j < V; ++j) { const float d0 = f0[j] - pv[j]; s[j] += d0; q[j] += d0 * d0; }
     }
+    const int nt = prow < p.HW ? (p.HW - prow + ppi - 1) / ppi : 0;
+    const float invt = nt ? 1.0f / (float)nt : 0.f;
 #pragma unroll
-    for (int j = 0; j < V; ++j) { red_s[prow * C + cb + j] = s[j]; red_q[prow * C + cb + j] = q[j]; }
+    for (int j = 0; j < V; ++j) {   // (mean, M2) of this lane's nt pixels
+      const float ds = s[j] * invt;
+      red_s[prow * C + cb + j] = ds; red_p[prow * C + cb + j] = pv[j]; red_q[prow * C + cb + j] = fmaxf(q[j] - s[j] * ds, 0.f);
+    }
   }
   __syncthreads();
-  for (int c = tid; c < C; c += GN_THREADS) {
-    float ts = 0.f, tq = 0.f;
-    for (int r = 0; r < ppi; ++r) { ts += red_s[r * C + c]; tq += red_q[r * C + c]; }
-    ch_s[c] = ts; ch_q[c] = tq;
+  {
+    // lane rows -> channel: row r holds n_r = HW / ppi (+ 1 for r < HW % ppi) pixels; rows beyond the image hold none
+    const int rows = min(ppi, p.HW), nfull = p.HW / ppi, nrem = p.HW % ppi;
+    const float invn = 1.0f / (float)p.HW;
+    for (int c = tid; c < C; c += GN_THREADS) {
+      // every mean as (pivot of row 0) + small part: e_r = mean_r - p0 = (p_r - p0) + ds_r, differences of nearby numbers
+      const float p0 = red_p[c];
+      float acc = 0.f;
+      for (int r = 0; r < rows; ++r) acc += (float)(nfull + (r < nrem)) * ((red_p[r * C + c] - p0) + red_s[r * C + c]);
+      const float ec = acc * invn;   // channel mean - p0
+      float m2 = 0.f;
+      for (int r = 0; r < rows; ++r) { const float d = ((red_p[r * C + c] - p0) + red_s[r * C + c]) - ec; m2 += red_q[r * C + c] + (float)(nfull + (r < nrem)) * (d * d); }
+      ch_p[c] = p0; ch_s[c] = ec; ch_q[c] = m2;   // channel mean = ch_p + ch_s, channel M2
+    }
   }
   __syncthreads();
   const int cpg = C / p.groups;
   if (tid < p.groups) {
-    float ts = 0.f, tq = 0.f;
-    for (int j = 0; j < cpg; ++j) { ts += ch_s[tid * cpg + j]; tq += ch_q[tid * cpg + j]; }
-    const float inv = 1.0f / ((float)cpg * (float)p.HW);
-    const float mean = ts * inv;
-    const float var = fmaxf(tq * inv - mean * mean, 0.f);
+    // channels -> group (every channel holds HW pixels), the same way
+    const float p0 = ch_p[tid * cpg];
+    float acc = 0.f;
+    for (int j = 0; j < cpg; ++j) acc += (ch_p[tid * cpg + j] - p0) + ch_s[tid * cpg + j];
+    const float eg = acc / (float)cpg;
+    float m2 = 0.f;
+    for (int j = 0; j < cpg; ++j) { const float d = ((ch_p[tid * cpg + j] - p0) + ch_s[tid * cpg + j]) - eg; m2 += ch_q[tid * cpg + j] + (float)p.HW * (d * d); }
+    const float mean = p0 + eg;
+    const float var = fmaxf(m2 / ((float)cpg * (float)p.HW), 0.f);
     g_mean[tid] = mean;
     g_rstd[tid] = 1.0f / sqrtf(var + p.eps);
     if (p.mean) { p.mean[(size_t)n * p.groups + tid] = mean; p.rstd[(size_t)n * p.groups + tid] = g_rstd[tid]; }
@@ -130,14 +169,16 @@ __global__ void __launch_bounds__(GN_THREADS + 64) gn_affine_kernel(GnKArgs p) {
   for (int c = tid; c < C; c += GN_THREADS) {
     const int g = c / cpg;
     const bool mine = c == tid;   // the first sweep uses the prefetched parameters
+    // b from the ROUNDED a: a x + b = a (x - mean) + beta_eff then has one rounding at the size of mean * a (b's own), not one per factor
     float a = g_rstd[g] * (mine ? pg : p.gamma[c]);
-    float b = (mine ? pbt : p.beta[c]) - g_mean[g] * a;
+    float be = mine ? pbt : p.beta[c];
     if (p.film) {
       const float sc = 1.0f + (mine ? psc : p.film[(size_t)n * p.film_stride + c]);
       const float sh = mine ? psh : p.film[(size_t)n * p.film_stride + C + c];
       a *= sc;
-      b = b * sc + sh;
+      be = fmaf(be, sc, sh);
     }
+    const float b = fmaf(-g_mean[g], a, be);
     p.a[(size_t)n * C + c] = a;
     p.b[(size_t)n * C + c] = b;
     ch_s[c] = a; ch_q[c] = b;
@@ -190,13 +231,29 @@ __global__ void __launch_bounds__(GN_THREADS + 64) gn_affine_kernel(GnKArgs p) {
 // stats[N][slots][C/4][2] = sum, sum of squares per channel quad): no pass over the activation.  A workgroup per image; the
 // partials are summed in a fixed order (bitwise reproducible).  The input may be the channel concat of two tensors, each with
 // its own partial buffer; a group may straddle the two (e.g. 256 + 128 channels: groups of 12).
+//
+// The partials are sums of raw values and raw squares, so var = E[x^2] - mean^2 loses mean^2 / var of its digits.  With fp32 sums
+// good to about 2^-22 relative (a few hundred rounded additions of like-signed terms per channel, slots then quads), the variance is
+// off by 2^-22 (1 + mean^2 / var), and the normalised value, |xhat| up to ~4.5, by about half of that times |xhat|: 5e-7 (1 + mean^2 /
+// var).  The fp32 reference's own error is 5e-7 .. 1e-6, so the estimate is kept while mean^2 <= GN_FIN_RATIO * var with GN_FIN_RATIO = 2
+// (at most 3x the best case) and, beyond that, the group's statistics are recomputed from the activation the convs just wrote
+// (src0 / src1; the workgroup reads the group's channels once, summing deviations from the estimated mean, which is good to 2^-22 of
+// itself: no cancellation is left).  Well-conditioned groups never touch the activation.
+constexpr float GN_FIN_RATIO = 2.0f;
 struct GnFinArgs {
   const float* st0; const float* st1; int slots0, slots1, C0, C1;
   int HW, groups; float eps;
   const float* gamma; const float* beta; const float* film; int film_stride;
   float* a; float* b;
   const void* warm; uint32_t warm_bytes;   // as in GnKArgs: one extra wave touches the consumer conv's weights
+  const void* src0; const void* src1; int dtype;   // the activation itself (NHWC, internal dtype code), or null: never recompute
 };
+// four consecutive channels of an NHWC tensor as floats
+template <typename T> __device__ __forceinline__ void gn_load4(const void* base, size_t elem, float (&v)[4]) {
+  const T* q = reinterpret_cast<const T*>(base) + elem;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = (float)q[k];
+}
 __global__ void __launch_bounds__(320) gn_finalize_kernel(GnFinArgs p) {
   extern __shared__ __attribute__((aligned(16))) float fsm[];
   const int C = p.C0 + p.C1, Q = C >> 2, Q0 = p.C0 >> 2, Q1 = p.C1 >> 2;
@@ -204,6 +261,8 @@ __global__ void __launch_bounds__(320) gn_finalize_kernel(GnFinArgs p) {
   float* qq = fsm + Q;        // [Q] sums of squares
   float* g_mean = qq + Q;     // [groups]
   float* g_rstd = g_mean + p.groups;
+  float* g_part = g_rstd + p.groups;   // [8] per-wave partials of a recomputed group
+  int* g_redo = reinterpret_cast<int*>(g_part + 8);   // [groups]
   const int tid = threadIdx.x, n = blockIdx.x;
   if (tid >= 256) { l2_warm_wave(p.warm, p.warm_bytes); return; }
   // the per-channel parameters of this thread's (up to two) channels are requested FIRST: they do not depend on the statistics, and
@@ -245,20 +304,51 @@ __global__ void __launch_bounds__(320) gn_finalize_kernel(GnFinArgs p) {
     const float var = fmaxf(tq * inv - mean * mean, 0.f);
     g_mean[tid] = mean;
     g_rstd[tid] = 1.0f / sqrtf(var + p.eps);
+    g_redo[tid] = p.src0 != nullptr && !(mean * mean <= GN_FIN_RATIO * var);
   }
   __syncthreads();
+  for (int g = 0; g < p.groups; ++g) {   // ill-conditioned groups only (the flag is workgroup-uniform): one sweep over the group's channels
+    if (!g_redo[g]) continue;
+    const float m = g_mean[g];
+    const int total = qpg * p.HW;
+    float s = 0.f, sq = 0.f;
+    for (int i = tid; i < total; i += 256) {
+      const int pix = i / qpg, c = g * cpg + 4 * (i - pix * qpg);   // a channel quad lies inside one source (C0 % 4 == 0)
+      const bool first = c < p.C0;
+      const void* base = first ? p.src0 : p.src1;
+      const size_t elem = ((size_t)n * p.HW + pix) * (first ? p.C0 : p.C1) + (first ? c : c - p.C0);
+      float v[4];
+      if (p.dtype == DT_F32) gn_load4<float>(base, elem, v);
+      else if (p.dtype == DT_F16) gn_load4<f16>(base, elem, v);
+      else gn_load4<bf16>(base, elem, v);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { const float d = v[k] - m; s += d; sq += d * d; }
+    }
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); sq += __shfl_xor(sq, o); }
+    if ((tid & 63) == 0) { g_part[tid >> 6] = s; g_part[4 + (tid >> 6)] = sq; }
+    __syncthreads();
+    if (tid == 0) {
+      const float inv = 1.0f / (4.0f * (float)total);
+      const float ds = ((g_part[0] + g_part[1]) + (g_part[2] + g_part[3])) * inv;
+      const float var = fmaxf(((g_part[4] + g_part[5]) + (g_part[6] + g_part[7])) * inv - ds * ds, 0.f);
+      g_mean[g] = m + ds;
+      g_rstd[g] = 1.0f / sqrtf(var + p.eps);
+    }
+    __syncthreads();
+  }
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int c = tid + 256 * k;
     if (c < C) {
       const int g = c / cpg;
       float a = g_rstd[g] * pg[k];
-      float b = pbt[k] - g_mean[g] * a;
-      if (p.film) {
+      float be = pbt[k];
+      if (p.film) {   // (b from the rounded a: see gn_affine_kernel)
         const float sc = 1.0f + psc[k];
         a *= sc;
-        b = b * sc + psh[k];
+        be = fmaf(be, sc, psh[k]);
       }
+      const float b = fmaf(-g_mean[g], a, be);
       p.a[(size_t)n * C + c] = a;
       p.b[(size_t)n * C + c] = b;
     }
@@ -266,13 +356,14 @@ __global__ void __launch_bounds__(320) gn_finalize_kernel(GnFinArgs p) {
   for (int c = tid + 512; c < C; c += 256) {   // more than 512 channels: the rest the slow way
     const int g = c / cpg;
     float a = g_rstd[g] * p.gamma[c];
-    float b = p.beta[c] - g_mean[g] * a;
+    float be = p.beta[c];
     if (p.film) {
       const float sc = 1.0f + p.film[(size_t)n * p.film_stride + c];
       const float sh = p.film[(size_t)n * p.film_stride + C + c];
       a *= sc;
-      b = b * sc + sh;
+      be = fmaf(be, sc, sh);
     }
+    const float b = fmaf(-g_mean[g], a, be);
     p.a[(size_t)n * C + c] = a;
     p.b[(size_t)n * C + c] = b;
   }
@@ -285,14 +376,17 @@ __global__ void __launch_bounds__(256) groupnorm_nchw_kernel(const float* x, con
   const int n = blockIdx.x / groups, g = blockIdx.x % groups, cpg = C / groups;
   const size_t base = ((size_t)n * C + (size_t)g * cpg) * HW;
   const int cnt = cpg * HW;
+  // deviations from the group's first element (shared by every thread, so plain sums combine): var = E[d^2] - E[d]^2 has E[d] of the
+  // order of the standard deviation whatever the group's offset is (see the note on statistics at the top of this file)
+  const float pv = x[base];
   float s = 0.f, q = 0.f;
-  for (int i = threadIdx.x; i < cnt; i += 256) { float v = x[base + i]; s += v; q += v * v; }
+  for (int i = threadIdx.x; i < cnt; i += 256) { const float d = x[base + i] - pv; s += d; q += d * d; }
   for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }  // wave64 shuffle reduction
   if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = s; sh[4 + (threadIdx.x >> 6)] = q; }
   __syncthreads();
   s = sh[0] + sh[1] + sh[2] + sh[3];
   q = sh[4] + sh[5] + sh[6] + sh[7];
-  const float mean = s / cnt, var = fmaxf(q / cnt - mean * mean, 0.f), rstd = 1.0f / sqrtf(var + eps);
+  const float ds = s / cnt, mean = pv + ds, var = fmaxf(q / cnt - ds * ds, 0.f), rstd = 1.0f / sqrtf(var + eps);
   for (int i = threadIdx.x; i < cnt; i += 256) {
     const int c = g * cpg + i / HW;
     float v = (x[base + i] - mean) * rstd * gamma[c] + beta[c];
@@ -348,6 +442,17 @@ int affine_pool_launch(int dtype, const void* in, const float* a, const float* b
   return 0;
 }
 
+// small-image form: the image is a whole number NL of fragments per thread and the launch writes y
+int gn_affine_form(const GnDesc& d) {
+  const int C = d.C0 + d.C1, V = d.dtype == 0 ? 4 : 8;
+  if (C <= 0 || C % V || C / V > GN_THREADS) return 0;
+  if (d.y && GN_THREADS % (C / V) == 0 && ((size_t)d.HW * (C / V)) % GN_THREADS == 0) {
+    const size_t q = (size_t)d.HW * (C / V) / GN_THREADS;
+    if (q == 1 || q == 2 || q == 4 || q == 8) return (int)q;
+  }
+  return 0;
+}
+
 int gn_affine_launch(const GnDesc& d, hipStream_t stream) {
   const int C = d.C0 + d.C1;
   const int V = d.dtype == 0 ? 4 : 8;
@@ -357,21 +462,21 @@ int gn_affine_launch(const GnDesc& d, hipStream_t stream) {
   MI355_REQUIRE(d.groups <= GN_THREADS, -4, "groupnorm: too many groups");
   GnKArgs a{d.src0, d.src1, d.C0, d.C1, d.N, d.HW, d.groups, d.eps, d.gamma, d.beta, d.film, d.film_stride, d.a, d.b, d.y, d.y_silu, d.mean, d.rstd, d.warm, d.warm_bytes};
   const int ppi = GN_THREADS / (C / V);
-  const size_t lds = ((size_t)2 * ppi * C + 2 * C + 2 * d.groups) * sizeof(float);
+  const size_t lds = ((size_t)3 * ppi * C + 3 * C + 2 * d.groups) * sizeof(float);
+  MI355_REQUIRE(lds <= 160 * 1024, -4, "groupnorm: LDS budget exceeded");
   const int nthreads = GN_THREADS + (d.warm && d.warm_bytes ? 64 : 0);
-  // small-image form: the image is a whole number NL of fragments per thread and the launch writes y
-  int nl = 0;
-  if (d.y && GN_THREADS % (C / V) == 0 && ((size_t)d.HW * (C / V)) % GN_THREADS == 0) {
-    const size_t q = (size_t)d.HW * (C / V) / GN_THREADS;
-    if (q == 1 || q == 2 || q == 4 || q == 8) nl = (int)q;
-  }
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(d.N), dim3(nthreads), lds, stream, a); };
-  dispatch_dtype(d.dtype, [&](auto t) {
-    using T = decltype(t);
-    switch (nl) { case 1: go(gn_affine_kernel<T, 1>); break; case 2: go(gn_affine_kernel<T, 2>); break; case 4: go(gn_affine_kernel<T, 4>); break;
-                  case 8: go(gn_affine_kernel<T, 8>); break; default: go(gn_affine_kernel<T, 0>); }
+  const int nl = gn_affine_form(d);
+  auto go = [&](auto kern) -> int {
+    if (lds > 64 * 1024) { if (int rc = mi355_allow_big_lds(kern, "groupnorm")) return rc; }
+    hipLaunchKernelGGL(kern, dim3(d.N), dim3(nthreads), lds, stream, a);
     return 0;
+  };
+  const int rc = dispatch_dtype(d.dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    switch (nl) { case 1: return go(gn_affine_kernel<T, 1>); case 2: return go(gn_affine_kernel<T, 2>); case 4: return go(gn_affine_kernel<T, 4>);
+                  case 8: return go(gn_affine_kernel<T, 8>); default: return go(gn_affine_kernel<T, 0>); }
   });
+  if (rc) return rc;
   MI355_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -382,8 +487,10 @@ int gn_finalize_launch(const GnFinDesc& d, hipStream_t stream) {
   MI355_REQUIRE(C % d.groups == 0 && (C / d.groups) % 4 == 0 && d.C0 % 4 == 0 && d.C1 % 4 == 0, -2,
                 "gn_finalize: groups must be whole channel quads");
   MI355_REQUIRE(d.groups <= 256, -4, "gn_finalize: too many groups");
-  GnFinArgs a{d.stats0, d.stats1, d.slots0, d.slots1, d.C0, d.C1, d.HW, d.groups, d.eps, d.gamma, d.beta, d.film, d.film_stride, d.a, d.b, d.warm, d.warm_bytes};
-  const size_t lds = ((size_t)2 * (C / 4) + 2 * d.groups) * sizeof(float);
+  MI355_REQUIRE(!d.src0 || d.C1 == 0 || d.src1, -1, "gn_finalize: the second source's activation is missing");
+  GnFinArgs a{d.stats0, d.stats1, d.slots0, d.slots1, d.C0, d.C1, d.HW, d.groups, d.eps, d.gamma, d.beta, d.film, d.film_stride, d.a, d.b, d.warm, d.warm_bytes,
+              d.src0, d.src1, d.dtype};
+  const size_t lds = ((size_t)2 * (C / 4) + 3 * d.groups + 8) * sizeof(float);
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(d.N), dim3(d.warm && d.warm_bytes ? 320 : 256), lds, stream, a);
   MI355_CHECK_HIP(hipGetLastError());
   return 0;

@@ -140,6 +140,7 @@ struct GnDesc {
   const void* warm = nullptr; uint32_t warm_bytes = 0;   // optional: packed weights of the conv this pass feeds (common.h l2_warm_issue)
 };
 int gn_affine_launch(const GnDesc& d, hipStream_t stream);
+int gn_affine_form(const GnDesc& d);   // the template form gn_affine_launch takes: NL = 1, 2, 4, 8 (image held in registers) or 0
 // The same (a, b) from the partial sums the producing convs left (ConvDesc::gn_stats): no pass over the activation.
 struct GnFinDesc {
   const float* stats0 = nullptr; int slots0 = 0, C0 = 0;
@@ -150,6 +151,9 @@ struct GnFinDesc {
   const float* film = nullptr; int film_stride = 0;
   float* a = nullptr; float* b = nullptr;
   const void* warm = nullptr; uint32_t warm_bytes = 0;   // as GnDesc::warm
+  // the tensors the partials describe (NHWC, C0 / C1 channels, element type dtype): a group whose mean^2 dominates its variance is
+  // recomputed from them (gn_stats.hip GN_FIN_RATIO); null: the partial sums are all there is
+  int dtype = DT_F32; const void* src0 = nullptr; const void* src1 = nullptr;
 };
 int gn_finalize_launch(const GnFinDesc& d, hipStream_t stream);
 // out = avgpool2x2(silu?(a * in + b)) on NHWC tensors (a, b per (n, c), may be null): the ResBlock(down=True) input path

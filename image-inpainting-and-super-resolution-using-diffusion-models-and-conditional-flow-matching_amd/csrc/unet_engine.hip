@@ -740,6 +740,7 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
       g.N = B; g.HW = s0.H * s0.W; g.gamma = WF(op.gamma_off); g.beta = WF(op.beta_off);
       if (op.film_emb_off >= 0) { g.film = embp + op.film_emb_off; g.film_stride = estride; }
       g.a = F(l.gna); g.b = F(l.gnb);
+      g.dtype = dtype; g.src0 = TP(op.src0); g.src1 = op.src1 >= 0 ? TP(op.src1) : nullptr;
       warm_next(op, g.warm, g.warm_bytes, 2);
       rc = gn_finalize_launch(g, stream);
       r.kind = MI355_OP_GN; r.cin = s0.C + C1; r.h = s0.H; r.w = s0.W;

@@ -325,5 +325,117 @@ class Ops:
                                         dtype, C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_qkv_attention_vjp")
         return gq
 
+    # --- GroupNorm32 test ops: the kernels the network launches, one op each (NCHW fp32 tensors; see include/mi355_sampler.h) ---
+    def gn_affine(self, x, gamma, beta, x1=None, film=None, eps=1e-5, dtype=_lib.MI355_F32, apply=None, stats=True):
+        """gn_affine_kernel on x [B, C0, *] (and x1 [B, C1, *], the channel concat).  apply: None, "affine" or "silu" (also write y).
+        -> dict(a, b [B, C]; mean, rstd [B, 32] if stats; y [B, C, *] if apply; form = NL of the launched template form)."""
+        B, C0 = x.shape[:2]
+        C1 = 0 if x1 is None else x1.shape[1]
+        hw = x[0, 0].numel()
+        if x1 is not None and (x1.shape[0] != B or x1[0, 0].numel() != hw):
+            raise ValueError("x1 must match x in batch and spatial size")
+        Cc = C0 + C1
+        if tuple(gamma.shape) != (Cc,) or tuple(beta.shape) != (Cc,) or (film is not None and tuple(film.shape) != (B, 2 * Cc)):
+            raise ValueError("gamma / beta must be [C0 + C1], film [B, 2 (C0 + C1)]")
+        if apply not in (None, "affine", "silu"):
+            raise ValueError("apply must be None, 'affine' or 'silu'")
+        dev = x.device
+        a = torch.full((B, Cc), float("nan"), device=dev)
+        b = torch.full((B, Cc), float("nan"), device=dev)
+        mean = torch.full((B, 32), float("nan"), device=dev) if stats else None
+        rstd = torch.full((B, 32), float("nan"), device=dev) if stats else None
+        y = torch.full((B, Cc) + tuple(x.shape[2:]), float("nan"), device=dev) if apply else None
+        form = C.c_int32(-1)
+        check(_lib.lib().mi355_gn_affine(_req(x, "x"), _req(x1, "x1") if x1 is not None else None, _req(gamma, "gamma"), _req(beta, "beta"),
+                                         _req(film, "film") if film is not None else None, float(eps), _req(a, "a"), _req(b, "b"),
+                                         _req(mean, "mean") if stats else None, _req(rstd, "rstd") if stats else None,
+                                         _req(y, "y") if apply else None, int(apply == "silu"), C.byref(form), B, C0, C1, hw, dtype, _stream()),
+              "mi355_gn_affine")
+        return dict(a=a, b=b, mean=mean, rstd=rstd, y=y, form=form.value)
+
+    def conv2d_gn(self, x, weight, bias, gamma, beta, x1=None, weight1=None, bias1=None, film=None, eps=1e-5, stride=1, resample=0,
+                  dtype=_lib.MI355_F32, debug=None):
+        """One conv (or two: x1, weight1, bias1) with GroupNorm partial sums of the output(s) from the epilogue, then gn_finalize_kernel
+        over the channel concat of the outputs.  weight / bias: CPU tensors [Co, Ci, k, k] / [Co].
+        -> dict(y, y1, a, b, kernel, slots, form, kernel1, slots1, form1); a / b are NaN when a producer filled no slots."""
+        B, Cin, H, W = x.shape
+        Co, Ci, k, _ = weight.shape
+        assert Ci == Cin
+        Co1 = 0
+        if x1 is not None:
+            Co1, Ci1, k1, _ = weight1.shape
+            assert Ci1 == x1.shape[1] and k1 == k and x1.shape[0] == B and x1.shape[2:] == x.shape[2:]
+        Hc, Wc = (H * 2, W * 2) if resample == 2 else (H, W)
+        Ho = (Hc + 2 * (k // 2) - k) // stride + 1
+        Wo = (Wc + 2 * (k // 2) - k) // stride + 1
+        Cc = Co + Co1
+        if tuple(gamma.shape) != (Cc,) or tuple(beta.shape) != (Cc,) or (film is not None and tuple(film.shape) != (B, 2 * Cc)):
+            raise ValueError("gamma / beta must be [Co + Co1], film [B, 2 (Co + Co1)]")
+        dev = x.device
+        y = torch.full((B, Co, Ho, Wo), float("nan"), device=dev)
+        y1 = torch.full((B, Co1, Ho, Wo), float("nan"), device=dev) if x1 is not None else None
+        a = torch.full((B, Cc), float("nan"), device=dev)
+        b = torch.full((B, Cc), float("nan"), device=dev)
+        fp = C.POINTER(C.c_float)
+        host = lambda t: t.detach().to("cpu", torch.float32).contiguous() if t is not None else None
+        w0, b0, w1, b1 = host(weight), host(bias), host(weight1), host(bias1)
+        hp = lambda t: C.cast(t.data_ptr(), fp) if t is not None else None
+        info = (C.c_int32 * 6)()
+        check(_lib.lib().mi355_conv2d_gn(_req(x, "x"), hp(w0), hp(b0), _req(y, "y"), Cin, Co,
+                                         _req(x1, "x1") if x1 is not None else None, hp(w1), hp(b1), _req(y1, "y1") if x1 is not None else None,
+                                         x1.shape[1] if x1 is not None else 0, Co1, B, H, W, k, stride, resample, _req(gamma, "gamma"),
+                                         _req(beta, "beta"), _req(film, "film") if film is not None else None, float(eps), _req(a, "a"), _req(b, "b"),
+                                         dtype, C.byref(debug if debug is not None else _lib.debug_config()), info, _stream()), "mi355_conv2d_gn")
+        return dict(y=y, y1=y1, a=a, b=b, kernel=info[0], slots=info[1], form=info[2], kernel1=info[3], slots1=info[4], form1=info[5])
+
+    def affine_pool(self, x, a=None, b=None, silu=False, dtype=_lib.MI355_F32):
+        """AvgPool2d(2)(silu?(a x + b)) through affine_pool_kernel; a, b [B, C] or both None."""
+        B, Cc, H, W = x.shape
+        if (a is None) != (b is None) or (a is not None and (tuple(a.shape) != (B, Cc) or tuple(b.shape) != (B, Cc))):
+            raise ValueError("a and b must both be [B, C] or both None")
+        out = torch.full((B, Cc, H // 2, W // 2), float("nan"), device=x.device)
+        check(_lib.lib().mi355_affine_pool(_req(x, "x"), _req(a, "a") if a is not None else None, _req(b, "b") if b is not None else None,
+                                           int(bool(silu)), _req(out, "out"), B, Cc, H, W, dtype, _stream()), "mi355_affine_pool")
+        return out
+
+    def gn_silu_vjp(self, x, du, gamma, beta, x1=None, film=None, eps=1e-5, silu=True, du_stride=None, g0=None, g1=None,
+                    dtype=_lib.MI355_F32):
+        """Data gradient of silu?(GroupNorm32(cat(x, x1)) (1 + scale) + shift) for the cotangent du [B, C0 + C1, *] through
+        gn_affine_kernel + gn_silu_bwd_kernel.  g0 / g1: gradients to accumulate into (modified in place), or None: overwritten.
+        -> (grad of x, grad of x1 or None)"""
+        B, C0 = x.shape[:2]
+        C1 = 0 if x1 is None else x1.shape[1]
+        hw = x[0, 0].numel()
+        Cc = C0 + C1
+        if tuple(du.shape[:2]) != (B, Cc) or du[0, 0].numel() != hw:
+            raise ValueError("du must be [B, C0 + C1, *] with x's spatial size")
+        if tuple(gamma.shape) != (Cc,) or tuple(beta.shape) != (Cc,) or (film is not None and tuple(film.shape) != (B, 2 * Cc)):
+            raise ValueError("gamma / beta must be [C0 + C1], film [B, 2 (C0 + C1)]")
+        acc0, acc1 = g0 is not None, g1 is not None
+        if acc0:
+            _same(g0, x, "g0", "x")
+        if acc1:
+            _same(g1, x1, "g1", "x1")
+        g0 = g0 if acc0 else torch.full_like(x, float("nan"))
+        g1 = None if x1 is None else (g1 if acc1 else torch.full_like(x1, float("nan")))
+        check(_lib.lib().mi355_gn_silu_vjp(_req(x, "x"), _req(x1, "x1") if x1 is not None else None, _req(gamma, "gamma"), _req(beta, "beta"),
+                                           _req(film, "film") if film is not None else None, float(eps), int(bool(silu)), _req(du, "du"),
+                                           int(du_stride or Cc), _req(g0, "g0"), _req(g1, "g1") if g1 is not None else None, int(acc0), int(acc1),
+                                           B, C0, C1, hw, dtype, _stream()), "mi355_gn_silu_vjp")
+        return g0, g1
+
+    def grad_gather(self, src, shape, mode, coff=0, scale=1.0, dst=None, dtype=_lib.MI355_F32):
+        """grad_gather_kernel: dst [B, Cd, Hd, Wd] (+)= scale * G(src)[:, coff : coff + Cd]; mode 0 identity, 1 2x2 block sum, 2 src[y/2, x/2],
+        3 zero insertion.  shape = (Cd, Hd, Wd); dst: a tensor to accumulate into (in place), or None."""
+        B, Cs, Hs, Ws = src.shape
+        Cd, Hd, Wd = shape
+        acc = dst is not None
+        if acc and tuple(dst.shape) != (B, Cd, Hd, Wd):
+            raise ValueError("dst must be [B, Cd, Hd, Wd]")
+        out = dst if acc else torch.full((B, Cd, Hd, Wd), float("nan"), device=src.device)
+        check(_lib.lib().mi355_grad_gather(_req(src, "src"), _req(out, "dst"), B, Cd, Hd, Wd, Hs, Ws, Cs, int(coff), int(mode), int(acc),
+                                           float(scale), dtype, _stream()), "mi355_grad_gather")
+        return out
+
 
 default_ops = Ops()

@@ -42,7 +42,8 @@ extern "C" {
                      * precision mode (UNetModel(use_fp16=True) runs its torso in float16, AD/image_diffusion/unet.py:559-563): bf16's speed, three more
                      * mantissa bits on every stored activation and weight; values beyond +-65504 overflow to inf as they do in the reference */
 
-/* ABI version = 100 * major + minor.  The minor number counts additive changes; 106: mi355_qkv_attention_vjp (the attention backward as a test
+/* ABI version = 100 * major + minor.  The minor number counts additive changes; 107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels).  106: mi355_qkv_attention_vjp (the attention backward as a test
  * op); later additions to 106: mi355_unet_config::num_classes (class-conditional nets), mi355_unet_forward_labels,
  * mi355_cfm_euler_sample_labels, and the error word's bit 1 (a class label out of range, reported as MI355_ERR_ARG); then
  * mi355_sf2m_euler_sample (the two-network SF2M SDE sampler) and mi355_sde_euler_step (its Euler-Maruyama update as an op).  105 (round 5, last): mi355_debug_config::sampler_graph (carved out of the
@@ -459,6 +460,42 @@ int mi355_qkv_attention(const float* qkv, float* out, int batch, int heads, int 
  * workspace: mi355_op_workspace_bytes(batch, 3 * H * ch, T) suffices. */
 int mi355_qkv_attention_vjp(const float* qkv, const float* grad_out, float* grad_qkv, int batch, int heads, int head_channels, int length,
                             int new_order, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- GroupNorm32 test ops (ABI 107): the statistics, apply and backward kernels the network launches, one op each ------------------
+ * Tensors are NCHW fp32 device tensors; the ops pack them to NHWC in `dtype`, launch the descriptor the engine builds and unpack.  Scratch is
+ * the op's own; every op synchronises `stream` before it returns.  A buffer a kernel must fill completely starts as NaN.
+ *
+ * mi355_gn_affine: csrc/gn_stats.hip gn_affine_kernel.  x [B, c0, hw], x1 NULL or [B, c1, hw] (the never-materialised concat, unet.py:725),
+ * gamma / beta [c0 + c1], film NULL or [B, 2 (c0 + c1)] = scale | shift (unet.py:343-347).  Writes a, b [B, c0 + c1] with
+ * GN(x) (1 + scale) + shift = a x + b, optionally mean, rstd [B, 32] and y = silu?(a x + b) [B, c0 + c1, hw]; *form (host) = the template form
+ * launched: NL = 1, 2, 4, 8 fragments per lane held in registers, or 0 (any size; the apply pass re-reads the image).  dtype F32 / BF16 / F16. */
+int mi355_gn_affine(const float* x, const float* x1, const float* gamma, const float* beta, const float* film, float eps, float* a, float* b,
+                    float* mean, float* rstd, float* y, int y_silu, int32_t* form, int batch, int c0, int c1, int hw, int dtype, void* stream);
+/* One or two convs (x_k [B, cin_k, h, w] -> y_k [B, cout_k, Ho, Wo]; w_k / bias_k HOST pointers as in mi355_conv2d; resample 0 or 2) that leave
+ * GroupNorm partial sums of their outputs in their epilogues, then gn_finalize_kernel over the channel concat of the outputs: a, b
+ * [B, cout0 + cout1] for gamma / beta [cout0 + cout1], film NULL or [B, 2 (cout0 + cout1)].  info (host, 6 words) = {kernel of conv 0 (csrc/ops.h
+ * ConvKernel: 0 implicit GEMM, 1 1x1, 2 1x1 ping-pong, 3 first conv, 5 ping-pong, 6 warp-specialised, 7 small-level), slots it filled, its
+ * ConvRoute::form (ping-pong: 0 wide, 1 narrow), the same three for conv 1};
+ * a and b are written only when every producer filled slots.  x1 NULL: one producer. */
+int mi355_conv2d_gn(const float* x0, const float* w0_host, const float* bias0_host, float* y0, int cin0, int cout0, const float* x1,
+                    const float* w1_host, const float* bias1_host, float* y1, int cin1, int cout1, int batch, int h, int w, int ksize, int stride,
+                    int resample, const float* gamma, const float* beta, const float* film, float eps, float* a, float* b, int dtype,
+                    const mi355_debug_config* debug, int32_t info[6], void* stream);
+/* out [B, C, h/2, w/2] = AvgPool2d(2)(silu?(a x + b)), a / b [B, C] or both NULL: the ResBlock(down=True) input path (unet.py:332-337, 236). */
+int mi355_affine_pool(const float* x, const float* a, const float* b, int silu, float* out, int batch, int channels, int h, int w, int dtype,
+                      void* stream);
+/* Data gradient of u = silu?(GroupNorm32(cat(x0, x1)) (1 + scale) + shift): forward statistics by gn_affine_kernel (a, b, mean, rstd kept as a
+ * differentiable plan keeps them), then csrc/backward.hip gn_silu_bwd_kernel.  du [B, c0 + c1, hw] is packed into rows of du_stride >= c0 + c1
+ * channels (zero padding, as a channel-padded dgrad conv leaves it); g0 [B, c0, hw] / g1 [B, c1, hw]: overwritten, or added to when acc0 / acc1.
+ * dtype MI355_F32 or MI355_BF16 only. */
+int mi355_gn_silu_vjp(const float* x0, const float* x1, const float* gamma, const float* beta, const float* film, float eps, int silu,
+                      const float* du, int du_stride, float* g0, float* g1, int acc0, int acc1, int batch, int c0, int c1, int hw, int dtype,
+                      void* stream);
+/* csrc/backward.hip grad_gather_kernel: dst [B, cd, hd, wd] (+)= scale * G(src)[:, src_coff : src_coff + cd], src [B, src_channels, hs, ws];
+ * mode 0 identity, 1 sum of the 2x2 block (backward of nearest x2), 2 src[y/2, x/2] (backward of AvgPool2d(2) with scale 1/4), 3 zero
+ * insertion (backward of a stride-2 conv).  dtype MI355_F32 or MI355_BF16 only. */
+int mi355_grad_gather(const float* src, float* dst, int batch, int cd, int hd, int wd, int hs, int ws, int src_channels, int src_coff, int mode,
+                      int accumulate, float scale, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
