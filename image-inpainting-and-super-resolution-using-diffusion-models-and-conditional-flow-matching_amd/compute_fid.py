@@ -44,8 +44,14 @@ def draw_x0_shard(batch, seed, call_idx, device, shape=(3, 32, 32)):
 
 
 def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integration_method="euler", device="cuda:0", tol=1e-5, seed=0):
-    if integration_method not in ("euler", "dopri5"):
-        raise NotImplementedError("--integration_method must be euler or dopri5")
+    """integration_method: "euler", "dopri5", or a fixed-step Runge-Kutta name ("midpoint", "heun2", "rk4", "rk4_38": mi355.ode.TABLEAUS).
+    The fixed-step methods integrate over linspace(0, 1, integration_steps + 1) like the Euler branch - a build-defined reading: the
+    reference forwards any name but "euler" to odeint with the two-point grid linspace(0, 1, 2), which for a fixed-grid method is ONE
+    step over [0, 1]."""
+    from mi355.ode import RK_SOLVERS as rk
+
+    if integration_method not in ("euler", "dopri5") + rk:
+        raise NotImplementedError(f"--integration_method must be euler, dopri5 or one of {rk}")
     device = torch.device(device)
     calls = [0]
 
@@ -57,6 +63,9 @@ def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integrat
             if integration_method == "euler":
                 t_span = torch.linspace(0, 1, integration_steps + 1).tolist()
                 _, _, img = new_net.engine(device).cfm_euler(x, t_span, want_u8=True)  # (traj*127.5+128).clip(0,255).to(uint8)
+            elif integration_method in rk:
+                t_span = torch.linspace(0, 1, integration_steps + 1).tolist()
+                _, _, img = new_net.engine(device).cfm_rk(x, t_span, integration_method, want_u8=True)
             else:  # odeint(new_net, x, linspace(0,1,2), rtol=tol, atol=tol, method="dopri5")  (cifar10/compute_fid.py:80-85)
                 from mi355.ode import odeint_dopri5
                 from mi355.ops import default_ops

@@ -350,6 +350,92 @@ int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, con
   return 0;
 }
 
+// Fixed-step explicit Runge-Kutta CFM sampler over a general tableau (midpoint, Heun, RK4, ...).  The stage derivatives k_1..k_s and the stage state
+// live behind the network workspace: (stages + 1) state-sized buffers.
+static size_t rk_state_bytes(const mi355_unet* net, int batch) {
+  return al256((size_t)batch * net->cfg.out_channels * net->cfg.image_size * net->cfg.image_size * 4);
+}
+// t + c * dt with the product and the sum each rounded to fp32 (c == 0 / 1: the interval's end points themselves, as mi355/ode.py's dopri5 does)
+static float rk_stage_time(float t0, float t1, float c) {
+#pragma clang fp contract(off)
+  if (c == 0.f) return t0;
+  if (c == 1.f) return t1;
+  const float dt = t1 - t0;
+  const float p = c * dt;
+  return t0 + p;
+}
+
+int64_t mi355_cfm_rk_workspace_bytes(const mi355_unet* net, int batch, int stages) {
+  if (!net || batch <= 0 || stages < 1 || stages > 4) { mi355_set_error("cfm_rk_workspace_bytes: bad argument (1 <= stages <= 4)"); return -1; }
+  return (int64_t)al256((size_t)mi355_unet_workspace_bytes(net, batch)) + (int64_t)(stages + 1) * (int64_t)rk_state_bytes(net, batch);
+}
+
+int mi355_cfm_rk_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, const int32_t* labels,
+                        const float* t_span_host, int n_t, int stages, const float* a_host, const float* b_host, const float* c_host, float* traj,
+                        uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && x && t_span_host && n_t >= 1 && batch > 0, -1, "cfm_rk_sample: bad argument");
+  MI355_REQUIRE(stages >= 1 && stages <= 4, -1, "cfm_rk_sample: the tableau must have 1 to 4 stages");
+  MI355_REQUIRE(a_host && b_host && c_host, -1, "cfm_rk_sample: null tableau");
+  bool any_b = false;
+  for (int j = 0; j < stages; ++j) any_b = any_b || b_host[j] != 0.f;
+  MI355_REQUIRE(any_b, -1, "cfm_rk_sample: the tableau's weights b are all zero");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_rk_sample: class labels given to a net built without num_classes");
+  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_rk_sample: the vector field must have the state's channel count");
+  MI355_REQUIRE(workspace_bytes >= mi355_cfm_rk_workspace_bytes(net, batch, stages), -2, "cfm_rk_sample: workspace too small");
+  const int64_t base = (int64_t)al256((size_t)mi355_unet_workspace_bytes(net, batch));
+  Scratch sc;
+  if (int rc = carve(net, batch, workspace, base, sc)) return rc;
+  hipStream_t s = S(stream);
+  const int64_t n = (int64_t)batch * x_channels * net->cfg.image_size * net->cfg.image_size;
+  float* kbuf[4] = {nullptr, nullptr, nullptr, nullptr};
+  char* tail = reinterpret_cast<char*>(workspace) + base;
+  for (int i = 0; i < stages; ++i) kbuf[i] = reinterpret_cast<float*>(tail + (size_t)i * rk_state_bytes(net, batch));
+  float* ystage = reinterpret_cast<float*>(tail + (size_t)stages * rk_state_bytes(net, batch));
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  const int n_steps = n_t - 1;
+  if (n_steps == 0) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
+  // every evaluation time is known in advance: one embedding row (block of num_classes rows with labels) per (step, stage)
+  std::vector<float> te((size_t)n_steps * stages);
+  for (int k = 0; k < n_steps; ++k)
+    for (int i = 0; i < stages; ++i) te[(size_t)k * stages + i] = rk_stage_time(t_span_host[k], t_span_host[k + 1], c_host[i]);
+  // The rule is rows = n_steps * stages * K <= EMB_TABLE_STEPS (K = num_classes with labels, else 1), and make_emb_table applies it: beyond
+  // it the table stays null and every evaluation computes its own rows.  The test here leaves K out on purpose: it only keeps the row
+  // count that is handed over within an int and within sc.tsteps.
+  const float* emb_table = nullptr;
+  if ((int64_t)n_steps * stages <= EMB_TABLE_STEPS) {
+    if (int rc = make_emb_table(net, sc, te.data(), n_steps * stages, labels != nullptr, s, &emb_table)) return rc;
+    // `te` is a temporary host buffer: wait for its copy, once per call, as ddpm_sample and sf2m_euler_sample do (no graph capture here)
+    if (emb_table) MI355_CHECK_HIP(hipStreamSynchronize(s));
+  }
+  UnetRun run = uniform_t_run();   // no euler_x: the last conv stores v (conv_edge bit 3 stays out of these evaluations)
+  run.labels = labels;
+  const size_t block = (size_t)(labels ? net->num_classes : 1) * net->emb_total;
+  int rc = 0;
+  for (int k = 0; k < n_steps; ++k) {
+    const float dt = t_span_host[k + 1] - t_span_host[k];
+    for (int i = 0; i < stages; ++i) {
+      // y_i = x + sum_{j<i} (dt * a_ij) k_j over the non-zero a_ij; none: the stage reads x itself
+      const float* kp[4]; float cf[4]; int nk = 0;
+      for (int j = 0; j < i; ++j) {
+        const float a = a_host[(size_t)i * stages + j];
+        if (a != 0.f) { kp[nk] = kbuf[j]; cf[nk] = dt * a; ++nk; }
+      }
+      const float* yin = x;
+      if (nk) { if ((rc = rk_stage_launch(ystage, x, kp, cf, nk, n, nullptr, nullptr, s))) return rc; yin = ystage; }
+      const size_t e = (size_t)k * stages + i;
+      if (emb_table) run.emb_row = emb_table + e * block;
+      else if ((rc = fill_launch(sc.t, te[e], batch, s))) return rc;
+      if ((rc = unet_forward(net, yin, x_channels, cond, cond_channels, sc.t, kbuf[i], batch, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    }
+    const float* kp[4]; float cf[4]; int nk = 0;
+    for (int j = 0; j < stages; ++j)
+      if (b_host[j] != 0.f) { kp[nk] = kbuf[j]; cf[nk] = dt * b_host[j]; ++nk; }   // nk >= 1: an all-zero b was refused above
+    // the step's update, in place, with the trajectory slot and (last step) the image bytes from the same launch
+    if ((rc = rk_stage_launch(x, x, kp, cf, nk, n, traj ? traj + (size_t)(k + 1) * n : nullptr, k + 1 == n_steps ? u8_out : nullptr, s))) return rc;
+  }
+  return 0;
+}
+
 int mi355_ddpm_sample(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb,
                       const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
                       int64_t workspace_bytes, void* stream) {
@@ -556,6 +642,10 @@ int mi355_rk_combine(float* out, const float* y0, const float* k0, const float* 
   MI355_REQUIRE(coeff_host || nk == 0, -1, "rk_combine: null coefficients");
   const float* k[7] = {k0, k1, k2, k3, k4, k5, k6};
   return rk_combine_launch(out, y0, k, coeff_host, nk, n, S(stream));
+}
+int mi355_rk_stage(float* out, const float* y0, const float* const k[4], const float* coeff_host, int nk, int64_t n, float* copy_out,
+                   uint8_t* u8_out, void* stream) {
+  return rk_stage_launch(out, y0, k, coeff_host, nk, n, copy_out, u8_out, S(stream));
 }
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream) {

@@ -30,6 +30,50 @@ __global__ void __launch_bounds__(256) rk_combine_kernel(float* out, const float
   }
 }
 
+struct StagePtrs { const float* k[4]; float c[4]; };
+
+// (x * 127.5 + 128).clip(0, 255).to(uint8) of quantize_u8_launch (steps.hip, compiled with contraction off): product and sum rounded separately
+__device__ __forceinline__ uint8_t stage_u8(float x) {
+#pragma clang fp contract(off)
+  const float p = x * 127.5f;
+  const float v = clip_nan(p + 128.f, 0.f, 255.f);
+  return (uint8_t)(int)v;
+}
+
+// One stage of a fixed-step explicit Runge-Kutta sampler: out = y0 + sum_j c_j k_j, summed as rk_combine_kernel does, with the step's other outputs
+// in the same launch: copy_out (the trajectory slot) and u8_out (the image bytes of the rounded fp32 result).  out may be y0 (the state updated in
+// place: every thread reads its own elements before it writes them).
+__global__ void __launch_bounds__(256) rk_stage_kernel(float* out, const float* y0, StagePtrs kp, int nk, int64_t n, float* copy_out,
+                                                     uint8_t* u8_out, int vec) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= n) return;
+  if (i + 4 <= n && vec) {   // vec: every fp32 pointer is 16-byte aligned and u8_out 4-byte aligned (checked once by the launcher)
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < nk; ++j) {
+      const f32x4 kv = *reinterpret_cast<const f32x4*>(kp.k[j] + i);
+      const float c = kp.c[j];
+      acc = f32x4{acc[0] + kv[0] * c, acc[1] + kv[1] * c, acc[2] + kv[2] * c, acc[3] + kv[3] * c};
+    }
+    const f32x4 y = *reinterpret_cast<const f32x4*>(y0 + i);
+    const f32x4 r = f32x4{y[0] + acc[0], y[1] + acc[1], y[2] + acc[2], y[3] + acc[3]};
+    *reinterpret_cast<f32x4*>(out + i) = r;
+    if (copy_out) *reinterpret_cast<f32x4*>(copy_out + i) = r;
+    if (u8_out)
+      *reinterpret_cast<uint32_t*>(u8_out + i) = (uint32_t)stage_u8(r[0]) | ((uint32_t)stage_u8(r[1]) << 8) | ((uint32_t)stage_u8(r[2]) << 16) |
+                                                 ((uint32_t)stage_u8(r[3]) << 24);
+  } else {
+    const int64_t end = i + 4 < n ? i + 4 : n;
+    for (int64_t e = i; e < end; ++e) {
+      float acc = 0.f;
+      for (int j = 0; j < nk; ++j) acc += kp.k[j][e] * kp.c[j];
+      const float r = y0[e] + acc;
+      out[e] = r;
+      if (copy_out) copy_out[e] = r;
+      if (u8_out) u8_out[e] = stage_u8(r);
+    }
+  }
+}
+
 // sum_i ((a_i - sub_i) / (atol + rtol * max(|b_i|, |b2_i|)))^2  accumulated into *out (fp64 atomics, one per block)
 __global__ void __launch_bounds__(256) rk_sqnorm_kernel(const float* a, const float* sub, const float* b, const float* b2, float atol,
                                                       float rtol, int64_t n, double* out) {
@@ -75,6 +119,25 @@ int rk_combine_launch(float* out, const float* y0, const float* const* k, const 
   }
   const int64_t nth = (n + 3) / 4;
   hipLaunchKernelGGL(rk_combine_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s, out, y0, kp, nk, n, (int)((bits & 15) == 0));
+  MI355_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int rk_stage_launch(float* out, const float* y0, const float* const* k, const float* c, int nk, int64_t n, float* copy_out, uint8_t* u8_out,
+                    hipStream_t s) {
+  MI355_REQUIRE(nk >= 1 && nk <= 4, -1, "rk_stage: 1 to 4 stage derivatives");
+  if (n <= 0) return 0;   // an empty tensor (its pointers may be null): nothing to do
+  MI355_REQUIRE(out && y0 && k && c, -1, "rk_stage: null argument");
+  StagePtrs kp;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(y0) | reinterpret_cast<uintptr_t>(copy_out);   // null adds no bits
+  for (int j = 0; j < 4; ++j) {
+    MI355_REQUIRE(j >= nk || k[j], -1, "rk_stage: null stage pointer");
+    kp.k[j] = j < nk ? k[j] : nullptr; kp.c[j] = j < nk ? c[j] : 0.f;
+    bits |= reinterpret_cast<uintptr_t>(kp.k[j]);
+  }
+  const int vec = (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(u8_out) & 3) == 0;
+  const int64_t nth = (n + 3) / 4;
+  hipLaunchKernelGGL(rk_stage_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s, out, y0, kp, nk, n, copy_out, u8_out, vec);
   MI355_CHECK_HIP(hipGetLastError());
   return 0;
 }

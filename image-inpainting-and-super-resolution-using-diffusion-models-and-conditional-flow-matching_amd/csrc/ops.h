@@ -271,6 +271,10 @@ int groupnorm_nchw_launch(const float* x, const float* gamma, const float* beta,
 
 // adaptive RK45 helpers (ode.hip)
 int rk_combine_launch(float* out, const float* y0, const float* const* k, const float* c, int nk, int64_t n, hipStream_t s);
+// one stage of a fixed-step explicit RK sampler: out = y0 + sum_j c[j] * k[j] (1 <= nk <= 4; out may be y0), the result also to copy_out and,
+// quantised as quantize_u8_launch does, to u8_out (either may be null)
+int rk_stage_launch(float* out, const float* y0, const float* const* k, const float* c, int nk, int64_t n, float* copy_out, uint8_t* u8_out,
+                    hipStream_t s);
 int rk_sqnorm_launch(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                      hipStream_t s);
 int rk_interp_launch(float* out, const float* y0, const float* y1, const float* ym, const float* f0, const float* f1, float dt, float x,

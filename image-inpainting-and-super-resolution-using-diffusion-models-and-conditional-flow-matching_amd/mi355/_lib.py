@@ -125,6 +125,8 @@ SIGNATURES = {
     "mi355_unet_profile": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _VP, _I64, _VP, C.POINTER(OpProfileC), _I]),
     "mi355_cfm_euler_sample": (_I, [_VP, _VP, _I, _VP, _I, _I, _FP, _I, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_cfm_euler_sample_labels": (_I, [_VP, _VP, _I, _VP, _I, _I, _VP, _FP, _I, _VP, _VP, _I, _VP, _I64, _VP]),
+    "mi355_cfm_rk_workspace_bytes": (_I64, [_VP, _I, _I]),
+    "mi355_cfm_rk_sample": (_I, [_VP, _VP, _I, _VP, _I, _VP, _FP, _I, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_sf2m_euler_sample": (_I, [_VP, _VP, _VP, _I, _VP, _FP, _I, _F, _I, _VP, _U64, C.POINTER(C.c_int32), _FP, _I, _VP, _I, _VP, _I64,
                                      _VP, _I64, _VP]),
     "mi355_ddpm_sample": (_I, [_VP, _VP, _I, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), _VP, _I64, _I, _VP, _I64, _VP]),
@@ -148,6 +150,7 @@ SIGNATURES = {
     "mi355_to_unit_range": (_I, [_VP, _VP, _I64, _VP]),
     "mi355_randn": (_I, [_VP, _U64, _U64, _I64, _VP]),
     "mi355_rk_combine": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _FP, _I, _I64, _VP]),
+    "mi355_rk_stage": (_I, [_VP, _VP, C.POINTER(_VP), _FP, _I, _I64, _VP, _VP, _VP]),
     "mi355_rk_sqnorm": (_I, [_VP, _VP, _VP, _VP, _F, _F, _I64, _VP, _VP]),
     "mi355_rk_interp": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _F, _F, _I64, _VP]),
     "mi355_op_workspace_bytes": (_I64, [_I, _I, _I]),

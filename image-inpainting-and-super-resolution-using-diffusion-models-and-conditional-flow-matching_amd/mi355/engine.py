@@ -59,6 +59,7 @@ class UNetEngine:
                                            self._stream(), C.byref(handle)), "mi355_unet_create")
         self.handle = handle
         self._ws: Optional[torch.Tensor] = None
+        self._rk_bytes: Dict[Tuple[int, int], int] = {}   # mi355_cfm_rk_workspace_bytes per (batch, stages)
         self._fwd_state = None   # (batch, workspace pointer) of the last forward(): what vjp() differentiates
         self.in_channels = self.cfg.in_channels
         self.out_channels = self.cfg.out_channels
@@ -276,6 +277,59 @@ class UNetEngine:
                                             Cc, int(bool(cond_drift)), arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
                                             self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
               "mi355_cfm_euler_sample")
+        return x, traj, u8
+
+    def _workspace_rk(self, batch: int, stages: int):
+        """The sampler workspace with the RK stage buffers behind it (mi355_cfm_rk_workspace_bytes), its size cached per (batch, stages)."""
+        need = self._rk_bytes.get((batch, stages))
+        if need is None:
+            need = self._rk_bytes[(batch, stages)] = check(self.L.mi355_cfm_rk_workspace_bytes(self.handle, batch, stages), "mi355_cfm_rk_workspace_bytes")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return C.c_void_p(self._ws.data_ptr()), self._ws.numel()
+
+    def cfm_rk(self, x: torch.Tensor, t_span: Sequence[float], method="rk4", cond: Optional[torch.Tensor] = None, keep_traj: bool = False,
+               want_u8: bool = False, y: Optional[torch.Tensor] = None, cond_drift: bool = False):
+        """In-place fixed-step explicit Runge-Kutta integration of x over t_span (host floats), one step per interval, the whole loop one
+        library call (mi355_cfm_rk_sample).  method: a name of mi355.ode.TABLEAUS ("euler", "midpoint", "heun2", "rk4", "rk4_38") or an
+        (a, b, c) tableau of 1 to 4 stages.  Returns (x, traj or None, u8 or None).
+        cond: passed to every stage unchanged.  y: class labels [B] of a class-conditional engine.  A batch beyond max_batch() runs in slices,
+        as in cfm_euler.  cond_drift, the concatenated-state sampler of cfm_euler, is not built for these methods and is refused (the
+        reference runs it with Euler only)."""
+        if cond_drift:
+            raise NotImplementedError("cond_drift (the drifting condition of the concatenated-state sampler) is built for Euler only: cfm_euler")
+        from .ode import resolve_tableau
+
+        a, b, c = resolve_tableau(method)
+        stages = len(b)
+        B, Cx, Cc = self._split(x, cond)
+        lab, lab_p = self._labels(y, B)
+        mb = self.max_batch()
+        ts = [float(v) for v in t_span]
+        if B > mb:
+            traj = torch.empty((len(ts),) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
+            u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
+            for lo in range(0, B, mb):
+                hi = min(B, lo + mb)
+                _, tr, u = self.cfm_rk(x[lo:hi], ts, (a, b, c), cond[lo:hi] if cond is not None else None, keep_traj, want_u8,
+                                       lab[lo:hi] if lab is not None else None)
+                if traj is not None:
+                    traj[:, lo:hi] = tr
+                if u8 is not None:
+                    u8[lo:hi] = u
+            return x, traj, u8
+        arr = (C.c_float * len(ts))(*ts)
+        a_arr = (C.c_float * (stages * stages))(*[v for row in a for v in row])
+        b_arr, c_arr = (C.c_float * stages)(*b), (C.c_float * stages)(*c)
+        traj = torch.empty((len(ts),) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
+        u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
+        self._fwd_state = None
+        ws, wsb = self._workspace_rk(B, stages)
+        check(self.L.mi355_cfm_rk_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc, lab_p,
+                                         arr, len(ts), stages, a_arr, b_arr, c_arr, self._chk(traj, "traj") if traj is not None else None,
+                                         self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
+              "mi355_cfm_rk_sample")
         return x, traj, u8
 
     def sf2m_euler(self, score_engine: "UNetEngine", x: torch.Tensor, t_grid: Sequence[float], sigma: float, reverse: bool = False,

@@ -11,10 +11,22 @@ shared source, against the order conditions of the tables, an analytic solution 
 
 Stage combinations, error norms and the dense output are HIP kernels (csrc/ode.hip); the controller needs one
 scalar per step and stays on the host.
+
+Fixed-step explicit Runge-Kutta methods (`TABLEAUS`, `FixedStepRK`): the solvers behind torchdyn's NeuralODE(solver=...) and the
+reference's --integration_method beyond "euler".  One step per interval of the time grid (torchdyn's meaning of t_span).  A tableau is
+(a, b, c): a the square stage matrix, row-major, strictly lower triangular; step k with dt = t_{k+1} - t_k evaluates
+k_i = f(T_i, y + sum_{j<i} dt a_ij k_j) and ends at y + sum_j dt b_j k_j.  The stage time T_i is t_k for c_i == 0, t_{k+1} itself for c_i == 1
+(the rule of the dopri5 stages above) and t_k + c_i * dt otherwise, each operation rounded in the state's type.  Zero coefficients are
+skipped.  The same rule runs inside the library as mi355_cfm_rk_sample (UNetEngine.cfm_rk: the whole integration in one call);
+FixedStepRK is the host-driven loop for any callable and any tuple state, one mi355_rk_stage launch per stage and component.
+Which names the un-vendored libraries give these tables is recalled, not checked - "parity unpinned": torchdyn's "rk4" is recalled as the
+classical tableau ("rk4" here), torchdiffeq's fixed-grid "rk4" as the 3/8 rule ("rk4_38" here), "midpoint" as the explicit midpoint rule
+in both.  The tables themselves are held to their order conditions and a measured convergence order (tests/test_rk_cpu.py).
 """
 from __future__ import annotations
 
 import math
+from fractions import Fraction as _Fr
 from typing import Callable, List, Sequence
 
 import torch
@@ -164,3 +176,101 @@ def odeint_dopri5(func, y0, t0: float, t_end: float, rtol: float, atol: float):
     solver = Dopri5(f, rtol, atol)
     out = solver.integrate(ys, t0, t_end)
     return (tuple(out) if is_tuple else out[0]), solver.nfe
+
+
+# ---- fixed-step explicit Runge-Kutta ---------------------------------------------------------------------------------------------------
+
+def _tab(a, b, c):
+    n = len(b)
+    return ([[_Fr(v) for v in list(r) + [0] * (n - len(r))] for r in a], [_Fr(v) for v in b], [_Fr(v) for v in c])
+
+
+_h, _t = _Fr(1, 2), _Fr(1, 3)
+# name -> (a, b, c), exact rationals (float(.) of each is what the solvers use)
+TABLEAUS = {
+    "euler": _tab([[]], [1], [0]),
+    "midpoint": _tab([[], [_h]], [0, 1], [0, _h]),                                     # explicit midpoint
+    "heun2": _tab([[], [1]], [_h, _h], [0, 1]),                                        # explicit trapezoid
+    "rk4": _tab([[], [_h], [0, _h], [0, 0, 1]], [_Fr(1, 6), _t, _t, _Fr(1, 6)], [0, _h, _h, 1]),                       # classical
+    "rk4_38": _tab([[], [_t], [-_t, 1], [1, -1, 1]], [_Fr(1, 8), _Fr(3, 8), _Fr(3, 8), _Fr(1, 8)], [0, _t, 2 * _t, 1]),   # 3/8 rule
+}
+RK_SOLVERS = tuple(n for n in TABLEAUS if n != "euler")   # the names NeuralODE(solver=...) and --integration_method add to "euler" / "dopri5"
+
+
+def resolve_tableau(method):
+    """A name of TABLEAUS or an (a, b, c) triple -> (a [s][s], b [s], c [s]) as floats, 1 <= s <= 4 stages (a: rows of any length up to s;
+    only the strictly lower part is kept).  Unknown names raise NotImplementedError; a triple that is not explicit, whose weights b are all
+    zero or whose c_i differs from sum_j a_ij (beyond 1e-6, room for decimal thirds) raises ValueError."""
+    if isinstance(method, str):
+        if method not in TABLEAUS:
+            raise NotImplementedError(f"method={method!r}: the fixed-step tableaus are {sorted(TABLEAUS)}")
+        method = TABLEAUS[method]
+    try:
+        a, b, c = method
+        b, c = [float(v) for v in b], [float(v) for v in c]
+        rows = [[float(v) for v in r] for r in a]
+    except (TypeError, ValueError) as e:
+        raise ValueError("a tableau is a name or an (a, b, c) triple of numbers") from e
+    s = len(b)
+    if not 1 <= s <= 4:
+        raise ValueError(f"a tableau must have 1 to 4 stages, got {s}")
+    if len(c) != s or len(rows) != s:
+        raise ValueError("a, b and c of a tableau must have one entry (row) per stage")
+    if any(v != 0.0 for i, r in enumerate(rows) for v in r[i:]):
+        raise ValueError("only explicit methods are built: a must be strictly lower triangular")
+    if all(v == 0.0 for v in b):
+        raise ValueError("the weights b of a tableau are all zero: such a step leaves the state where it is")
+    if any(abs(c[i] - sum(r[:i])) > 1e-6 for i, r in enumerate(rows)):
+        raise ValueError("c_i must equal sum_j a_ij: the stage times would not match the stage states")
+    return [[r[j] if j < min(i, len(r)) else 0.0 for j in range(s)] for i, r in enumerate(rows)], b, c
+
+
+class FixedStepRK:
+    """Host-driven fixed-step explicit Runge-Kutta integration of y' = func(t, y) for any callable and any tuple state."""
+
+    def __init__(self, func: Callable[[float, State], Sequence[torch.Tensor]], tableau, ops=None, dtype=torch.float32):
+        """tableau: a name of TABLEAUS or an (a, b, c) triple.  dtype: the state's type (the HIP op is fp32; the CPU tests measure the
+        tables' orders with an fp64 op table)."""
+        self.func = func
+        self.a, self.b, self.c = resolve_tableau(tableau)
+        self.stages = len(self.b)
+        self.ops = ops or default_ops
+        self.dtype = dtype
+        self.nfe = 0
+
+    def _f(self, t: float, y: State) -> State:
+        self.nfe += 1
+        return [v.to(self.dtype).contiguous() for v in self.func(t, y)]
+
+    def _s(self, v) -> torch.Tensor:
+        return torch.tensor(float(v), dtype=self.dtype)   # host scalars are rounded, and combined, in the state's type
+
+    def _stage(self, y: State, ks: List[State], coeffs: Sequence[float], dt: torch.Tensor) -> State:
+        """y + sum_j (dt * coeffs[j]) ks[j] over the non-zero coefficients; y itself when there is none."""
+        nz = [(k, float(dt * self._s(c))) for k, c in zip(ks, coeffs) if c != 0.0]
+        if not nz:
+            return y
+        out = [torch.empty_like(v) for v in y]
+        for i in range(len(y)):
+            self.ops.rk_stage(out[i], y[i], [k[i] for k, _ in nz], [c for _, c in nz])
+        return out
+
+    @torch.no_grad()
+    def integrate_times(self, y0: Sequence[torch.Tensor], times: Sequence[float]) -> List[State]:
+        """States at times[1:], one step per interval (the grid may be non-uniform or decreasing)."""
+        y = [v.detach().to(self.dtype).contiguous() for v in y0]
+        outs: List[State] = []
+        for k in range(len(times) - 1):
+            t0, t1 = self._s(times[k]), self._s(times[k + 1])
+            dt = t1 - t0
+            ks: List[State] = []
+            for i in range(self.stages):
+                ti = t0 if self.c[i] == 0.0 else (t1 if self.c[i] == 1.0 else t0 + self._s(self.c[i]) * dt)
+                ks.append(self._f(float(ti), self._stage(y, ks, self.a[i][:i], dt)))
+            y1 = self._stage(y, ks, self.b, dt)
+            y = y1 if y1 is not y else [v.clone() for v in y]
+            outs.append(y)
+        return outs
+
+    def integrate(self, y0: Sequence[torch.Tensor], t0: float, t_end: float) -> State:
+        return self.integrate_times(y0, [t0, t_end])[-1]

@@ -207,6 +207,26 @@ class Ops:
                                           _stream()))
         return out
 
+    def rk_stage(self, out, y0, ks, coeffs, copy_out=None, u8_out=None):
+        """One stage of a fixed-step explicit RK method: out = y0 + sum_j coeffs[j] * ks[j] (1 to 4 terms; coeffs already include dt; out may
+        be y0: the state updated in place).  The same launch writes the result to copy_out (fp32) and its image bytes, as quantize_u8 of
+        the result, to u8_out (uint8)."""
+        if not 1 <= len(ks) == len(coeffs) <= 4:
+            raise ValueError("rk_stage takes 1 to 4 stage derivatives, one coefficient each")
+        _same(out, y0, "out", "y0")
+        for k in ks:
+            _same(out, k, "out", "k")
+        if copy_out is not None:
+            _same(out, copy_out, "out", "copy_out")
+        if u8_out is not None:
+            _same(out, u8_out, "out", "u8_out")
+        arr = (C.c_float * 4)(*([float(c) for c in coeffs] + [0.0] * (4 - len(coeffs))))
+        kp = (C.c_void_p * 4)(*([_req(k, "k") for k in ks] + [None] * (4 - len(ks))))
+        check(_lib.lib().mi355_rk_stage(_req(out, "out"), _req(y0, "y0"), kp, arr, len(ks), out.numel(),
+                                        _req(copy_out, "copy_out") if copy_out is not None else None,
+                                        _req(u8_out, "u8_out", torch.uint8) if u8_out is not None else None, _stream()), "mi355_rk_stage")
+        return out
+
     def rk_sqnorm(self, acc, a, sub=None, b=None, b2=None, atol=1.0, rtol=0.0):
         """acc (device fp64 scalar tensor) += sum(((a - sub) / (atol + rtol * max(|b|, |b2|)))**2)."""
         check(_lib.lib().mi355_rk_sqnorm(_req(a, "a"), _req(sub, "sub") if sub is not None else None, _req(b, "b") if b is not None else None,

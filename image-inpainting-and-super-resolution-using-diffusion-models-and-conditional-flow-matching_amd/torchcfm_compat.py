@@ -19,6 +19,7 @@ from typing import Optional
 import torch
 
 from image_diffusion.unet import UNetModel
+from mi355.ode import RK_SOLVERS
 from mi355.ops import default_ops
 
 
@@ -128,15 +129,20 @@ class SuperResModelWrapper(UNetModelWrapper):
 
 
 class NeuralODE:
-    """torchdyn.core.NeuralODE front-end: solver="euler" (fixed step) or "dopri5" (adaptive, mi355.ode.Dopri5).
+    """torchdyn.core.NeuralODE front-end: solver="euler" (fixed step), "midpoint", "heun2", "rk4", "rk4_38" (fixed-step explicit
+    Runge-Kutta, the tableaus of mi355.ode.TABLEAUS: "rk4" the classical one, "rk4_38" the 3/8 rule) or "dopri5" (adaptive,
+    mi355.ode.Dopri5).
 
-    trajectory(x, t_span) -> Tensor[len(t_span), *x.shape].  Euler with a UNetModelWrapper vector field runs the whole
-    integration inside libmi355_sampler (mi355_cfm_euler_sample); any other callable f(t, x[, args]) is driven step by step from
-    the host with the HIP Euler-update kernel.  dopri5 is one continuous adaptive solve with dense output at the requested times."""
+    trajectory(x, t_span) -> Tensor[len(t_span), *x.shape], one step per interval of t_span for the fixed-step solvers.  With a
+    UNetModelWrapper vector field these run the whole integration inside libmi355_sampler (mi355_cfm_euler_sample /
+    mi355_cfm_rk_sample); any other callable f(t, x[, args]) is driven step by step from the host with the HIP update kernels
+    (mi355.ode.FixedStepRK for the Runge-Kutta methods).  dopri5 is one continuous adaptive solve with dense output at the requested times."""
+
+    RK_SOLVERS = RK_SOLVERS   # mi355.ode: every fixed-step tableau name but "euler"
 
     def __init__(self, vector_field, solver="euler", sensitivity="adjoint", atol=1e-4, rtol=1e-4, **kwargs):
-        if solver not in ("euler", "dopri5"):
-            raise NotImplementedError(f"solver={solver!r}: only 'euler' and 'dopri5' are built")
+        if solver not in ("euler", "dopri5") + self.RK_SOLVERS:
+            raise NotImplementedError(f"solver={solver!r}: only 'euler', 'dopri5' and {self.RK_SOLVERS} are built")
         self.vf = vector_field
         self.solver = solver
         self.atol, self.rtol = atol, rtol
@@ -162,6 +168,14 @@ class NeuralODE:
 
             solver = Dopri5(lambda t, y: [self._call(t, y[0])], self.rtol, self.atol)
             states = solver.integrate_times([x], ts)   # one continuous adaptive solve, dense output at every requested time
+            return torch.stack([x] + [s[0] for s in states])
+        if self.solver in self.RK_SOLVERS:
+            if type(self.vf) is UNetModelWrapper and x.is_cuda:
+                _, traj, _ = self.vf.engine(x.device).cfm_rk(x, ts, self.solver, keep_traj=True)
+                return traj
+            from mi355.ode import FixedStepRK
+
+            states = FixedStepRK(lambda t, y: [self._call(t, y[0])], self.solver).integrate_times([x], ts)
             return torch.stack([x] + [s[0] for s in states])
         if type(self.vf) is UNetModelWrapper and x.is_cuda:
             _, traj, _ = self.vf.engine(x.device).cfm_euler(x, ts, keep_traj=True)

@@ -43,7 +43,8 @@ extern "C" {
                      * mantissa bits on every stored activation and weight; values beyond +-65504 overflow to inf as they do in the reference */
 
 /* ABI version = 100 * major + minor.  The minor number counts additive changes; 107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
- * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels).  106: mi355_qkv_attention_vjp (the attention backward as a test
+ * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
+ * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4).  106: mi355_qkv_attention_vjp (the attention backward as a test
  * op); later additions to 106: mi355_unet_config::num_classes (class-conditional nets), mi355_unet_forward_labels,
  * mi355_cfm_euler_sample_labels, and the error word's bit 1 (a class label out of range, reported as MI355_ERR_ARG); then
  * mi355_sf2m_euler_sample (the two-network SF2M SDE sampler) and mi355_sde_euler_step (its Euler-Maruyama update as an op).  105 (round 5, last): mi355_debug_config::sampler_graph (carved out of the
@@ -247,6 +248,32 @@ int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, con
                                   const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
                                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Fixed-step explicit Runge-Kutta CFM sampler over a Butcher tableau (a, b, c) of 1 to 4 stages: explicit midpoint, Heun, classical RK4, the
+ * 3/8 rule (torchdyn NeuralODE(solver=...) / the reference's --integration_method beyond "euler"; the tableaus are mi355/ode.py's TABLEAUS).
+ * One step per interval of t_span_host (torchdyn's meaning of t_span).  Step k, dt = t_{k+1} - t_k in fp32:
+ *   k_i = model(T_i, y_i[, labels]),  y_1 = x,  y_i = x + sum_{j<i} (dt * a_ij) k_j,   then   x <- x + sum_j (dt * b_j) k_j
+ *   T_i = t_k for c_i == 0, t_{k+1} itself for c_i == 1, else t_k + c_i * dt (product and sum each rounded to fp32).
+ * a_host: stages * stages, row-major, only the strictly lower part is read; the products dt * a_ij, dt * b_j are formed on the host in fp32
+ * and zero coefficients are skipped (classical RK4: every stage launch reads one k).
+ *   x      : in/out [B, Cx, H, W], Cx == out_channels;  cond: NULL or [B, Cc, H, W], passed to every stage unchanged (the drifting condition of
+ *            the Euler sampler's cond_drift is not built here);  labels: device int32[B] or NULL, as in the labelled Euler sampler;
+ *   traj   : NULL or [n_t, B, Cx, H, W], traj[0] = x as given;  u8_out: NULL or the bytes of the final state (the quantize_u8 formula);
+ *   n_t == 1: no step; traj[0] and u8_out are still written.
+ * Launches per step: `stages` network evaluations and `stages` mi355_rk_stage launches (a stage without non-zero a_ij reads x and has none); the
+ * step's last one updates x in place and writes traj[k + 1] and, on the last step, u8_out: no separate copy or quantise launch.
+ * With (n_t - 1) * stages * K <= 1024 (K = num_classes with labels, else 1) the emb_layers outputs of every (step, stage) time are computed
+ * before the loop (the stream is synchronised once after that); otherwise every evaluation computes its own, as the Euler sampler does without
+ * a table.  sampler_graph is not used here, and the Euler update inside the last conv (conv_edge bit 3) takes no part: v is needed as a tensor.
+ * workspace: mi355_cfm_rk_workspace_bytes(net, batch, stages) = the mi355_unet_workspace_bytes amount rounded up to 256, then (stages + 1)
+ * buffers of the state's size, each rounded up to 256 bytes; 256-byte aligned.
+ * c is taken as given: the library does not check c_i == sum_j a_ij (mi355/ode.py's resolve_tableau does, for a caller's own triple).
+ * Errors: stages outside 1..4, a null tableau, weights b that are all zero, labels on a net without num_classes (MI355_ERR_ARG);
+ * Cx != out_channels, a short workspace (-2). */
+int64_t mi355_cfm_rk_workspace_bytes(const mi355_unet* net, int batch, int stages);
+int mi355_cfm_rk_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, const int32_t* labels,
+                        const float* t_span_host, int n_t, int stages, const float* a_host, const float* b_host, const float* c_host,
+                        float* traj, uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* SF2M stochastic sampler (torchcfm's mnist_example.ipynb / conditional_mnist.ipynb, third section: torchsde.sdeint of an SDE module with
  * drift f(t, y) = model(t, y[, labels]) + score_model(t, y[, labels]) and diagonal diffusion g = sigma; un-vendored, restated as fixed-step
  * Euler-Maruyama).  Step k (k < n_steps) of the host grid t_grid_host[n_steps + 1] evaluates both nets at t_eval = t_k (reverse: 1 - t_k in fp32)
@@ -392,9 +419,14 @@ int mi355_randn(float* out, uint64_t seed, uint64_t offset, int64_t n, void* str
  * mnist/utils_mnist.py:101-108; un-vendored, algorithm restated).  The step-size controller runs on the host.
  *   rk_combine: out = y0 + sum_j coeff_host[j] * k_j   (coefficients already multiplied by dt; y0 may be NULL)
  *   rk_sqnorm : *out += sum_i ((a_i - sub_i) / (atol + rtol * max(|b_i|, |b2_i|)))^2   (sub, b, b2 may be NULL; fp64)
- *   rk_interp : torchdiffeq's quartic dense output at x = (t - t0) / dt                                   */
+ *   rk_interp : torchdiffeq's quartic dense output at x = (t - t0) / dt
+ *   rk_stage  : one stage of the fixed-step samplers: out = y0 + sum_j coeff_host[j] * k[j], 1 <= nk <= 4, summed in index order from zero as
+ *               rk_combine; out may be y0 (in place).  The same launch writes the result to copy_out and, as mi355_quantize_u8 of the
+ *               rounded fp32 result, to u8_out (either may be NULL).  n <= 0: nothing is done. */
 int mi355_rk_combine(float* out, const float* y0, const float* k0, const float* k1, const float* k2, const float* k3, const float* k4,
                      const float* k5, const float* k6, const float* coeff_host, int nk, int64_t n, void* stream);
+int mi355_rk_stage(float* out, const float* y0, const float* const k[4], const float* coeff_host, int nk, int64_t n, float* copy_out,
+                   uint8_t* u8_out, void* stream);
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream);
 int mi355_rk_interp(float* out, const float* y0, const float* y1, const float* y_mid, const float* f0, const float* f1, float dt, float x,
