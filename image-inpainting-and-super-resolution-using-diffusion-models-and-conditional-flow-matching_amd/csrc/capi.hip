@@ -35,7 +35,7 @@ void mi355_debug_defaults(mi355_debug_config* c) {
   if (!c) return;
   std::memset(c, 0, sizeof(*c));
   c->conv_ws = 1; c->conv_small = 15; c->conv_min_wgs = 512; c->conv_stagger = 0; c->conv_ablate = 0; c->conv_spin_limit = 1 << 22;
-  c->conv_time_reps = 0; c->gn_apply_max_hw = 64; c->gn_fuse = 1; c->l2_warm = 1; c->attn_fused = 1; c->gn_epilogue = 7; c->conv_pp = 45; c->conv_edge = 15;
+  c->conv_time_reps = 0; c->gn_apply_max_hw = 64; c->gn_fuse = 1; c->l2_warm = 1; c->attn_fused = 1; c->gn_epilogue = 7; c->conv_pp = 109; c->conv_edge = 15;
 }
 int mi355_unet_status(mi355_unet* net, int clear) {
   if (!net) { mi355_set_error("null handle"); return -1; }
@@ -706,6 +706,7 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
                        int h, int w, int cout, int ksize, int stride, int resample, const float* gn_gamma, const float* gn_beta, int gn_silu,
                        const float* emb, const float* res, int res_mode, int dtype, const mi355_debug_config* debug, void* workspace,
                        int64_t workspace_bytes, void* stream, mi355_conv_extras* ex) {
+
   const mi355_debug_config& K = debug ? *debug : mi355_default_debug();
   MI355_REQUIRE(x && w_host && y && workspace, -1, "conv2d: null argument");
   MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_BF16 || dtype == MI355_BF16X2 || dtype == MI355_F16, -1, "conv2d: bad dtype");
@@ -736,6 +737,12 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
   void* xin = p; p += al256((size_t)batch * h * w * cpad * esz);
   void* xin1 = p; if (x1) p += al256((size_t)batch * h * w * cin1 * esz);
   void* wdev = p; const size_t wbytes = conv_packed_weight_bytes(dtype, cout, ctot, ksize, wsplit); p += al256(wbytes);
+  // an up-sampling 3x3 conv may run in phase form (conv_pp bit 6): the collapsed weight image next to the nine-tap one, as the plan builder keeps both
+  const bool want_up2 = d.mode == CONV_UP2 && ksize == 3 && !wsplit && (K.conv_pp & 64) && cpad == cin;
+  const size_t wbytes_up2 = want_up2 ? conv_packed_weight_bytes_up2(dtype, cout, ctot) : 0;
+  ExScratch xs_up2;
+  void* wdev_up2 = want_up2 ? xs_up2.get(wbytes_up2) : nullptr;
+  MI355_REQUIRE(!want_up2 || wdev_up2, -2, "conv2d: out of device memory");
   float* bdev = reinterpret_cast<float*>(p); p += al256((size_t)cout * 4);
   float* ga = reinterpret_cast<float*>(p); p += al256((size_t)batch * ctot_pad * 4);
   float* gb = reinterpret_cast<float*>(p); p += al256((size_t)batch * ctot_pad * 4);
@@ -753,6 +760,12 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
   std::vector<char> packed(wbytes);
   conv_pack_weights(dtype, w_host, cout, ctot, ksize, packed.data(), wsplit);
   MI355_CHECK_HIP(hipMemcpyAsync(wdev, packed.data(), wbytes, hipMemcpyHostToDevice, s));
+  std::vector<char> packed_up2(wbytes_up2);
+  if (want_up2) {
+    conv_pack_weights_up2(dtype, w_host, cout, ctot, packed_up2.data());
+    MI355_CHECK_HIP(hipMemcpyAsync(wdev_up2, packed_up2.data(), wbytes_up2, hipMemcpyHostToDevice, s));
+    d.w_up2 = wdev_up2;
+  }
   if (bias_host) MI355_CHECK_HIP(hipMemcpyAsync(bdev, bias_host, (size_t)cout * 4, hipMemcpyHostToDevice, s));
   if (gn_gamma) {
     MI355_REQUIRE(ctot % 32 == 0 && cin % 32 == 0, -2, "conv2d: the GroupNorm32 prologue needs channels % 32 == 0");
@@ -786,6 +799,7 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
   std::vector<char> packed_f; std::vector<float> bias_f;
   if (ex) {
     ex->act_done = 0; ex->skip_done = 0;
+    for (int i = 0; i < 4; ++i) ex->route[i] = -1;
     MI355_REQUIRE(nhwc && !pool, -4, "conv2d_ex: extras need an NHWC output and no pooling");
     if (ex->skip_x0) {
       MI355_REQUIRE(ksize == 3 && stride == 1 && !resample && !x1 && !res && !wsplit && ex->skip_w_host && ex->skip_c0 > 0, -1, "conv2d_ex: the fused skip conv goes with a plain 3x3 conv of one source");
@@ -834,6 +848,7 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
   if ((rc = conv_launch(d, route, s))) return rc;
   if (ex) {
     ex->skip_done = route.skip; ex->act_done = route.act_done;
+    ex->route[0] = route.kernel; ex->route[1] = route.form; ex->route[2] = route.geom.BM; ex->route[3] = route.geom.BN;
     for (int k = 0; k < 2; ++k)
       if (act_dev[k] && (route.act_done & (1 << k)) && (rc = unpack_nchw_launch(dtype, act_dev[k], batch, g.Ho * g.Wo, ex->act_ctotal[k], ex->act_out[k], s))) return rc;
   }
@@ -1022,7 +1037,7 @@ int mi355_conv2d_gn(const float* x0, const float* w0_host, const float* bias0_ho
   void* out_dev[2] = {nullptr, nullptr}; float* st[2] = {nullptr, nullptr};
   int Ho = 0, Wo = 0, rc;
   for (int i = 0; i < 6; ++i) info[i] = 0;
-  std::vector<char> packed[2];
+  std::vector<char> packed[2], packed_up2[2];
   for (int k = 0; k < (x1 ? 2 : 1); ++k) {
     MI355_REQUIRE(cout[k] % 32 == 0, -2, "conv2d_gn: NHWC outputs need cout % 32 == 0");
     const int cpad = (cin[k] + CH - 1) / CH * CH;
@@ -1047,6 +1062,15 @@ int mi355_conv2d_gn(const float* x0, const float* w0_host, const float* bias0_ho
     packed[k].resize(wbytes);
     conv_pack_weights(dtype, wh[k], cout[k], cin[k], ksize, packed[k].data(), 0);
     MI355_CHECK_HIP(hipMemcpyAsync(wd, packed[k].data(), wbytes, hipMemcpyHostToDevice, s));
+    if (d.mode == CONV_UP2 && ksize == 3 && (K.conv_pp & 64) && cpad == cin[k]) {   // the phase form's collapsed image too (the route decides)
+      const size_t ub = conv_packed_weight_bytes_up2(dtype, cout[k], cin[k]);
+      void* wu = xs.get(ub);
+      MI355_REQUIRE(wu, -2, "conv2d_gn: out of device memory");
+      packed_up2[k].resize(ub);
+      conv_pack_weights_up2(dtype, wh[k], cout[k], cin[k], packed_up2[k].data());
+      MI355_CHECK_HIP(hipMemcpyAsync(wu, packed_up2[k].data(), ub, hipMemcpyHostToDevice, s));
+      d.w_up2 = wu;
+    }
     if (bh[k]) MI355_CHECK_HIP(hipMemcpyAsync(bd, bh[k], (size_t)cout[k] * 4, hipMemcpyHostToDevice, s));
     d.src0 = xd; d.w = wd; d.bias = bh[k] ? bd : nullptr; d.out = out_dev[k]; d.out_mode = OUT_NHWC; d.err = errw;
     d.gn_stats = st[k]; d.gn_slots_cap = cap;

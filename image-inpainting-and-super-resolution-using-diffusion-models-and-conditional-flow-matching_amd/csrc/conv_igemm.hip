@@ -744,6 +744,47 @@ void conv_pack_weights(int dtype, const float* w, int Cout, int Cin, int ks, voi
       }
 }
 
+// Nearest-x2 up-sample followed by a 3x3 conv (padding 1) = four 2x2 convs of the low-res image, one per output phase (a, b) = (row, column parity):
+// output row 2 i + a reads high-res rows 2 i + a - 1 .. 2 i + a + 1 = low-res rows {i - 1, i, i} (a = 0) or {i, i, i + 1} (a = 1), so tap ky' of the
+// phase filter is the sum of the 3x3 rows ky with (a + ky + 1) / 2 == a + ky' (and the same along x).  Summed in fp32, then rounded and swizzled per
+// element exactly as conv_pack_weights does.  Layout per 128-row pack tile: [phase 2 a + b][chunk][tap 2 ky' + kx'][128 rows][64 B].
+size_t conv_packed_weight_bytes_up2(int dtype, int Cout, int Cin) {
+  const int BN = conv_tile_n(Cout), CH = chunk_of(dtype);
+  const size_t nt = (Cout + BN - 1) / BN, nc = (size_t)((Cin + CH - 1) / CH);
+  return nt * 4 * nc * 4 * (size_t)BN * 64;
+}
+void conv_pack_weights_up2(int dtype, const float* w, int Cout, int Cin, void* dst) {
+  const int BN = conv_tile_n(Cout), CH = chunk_of(dtype), V = CH / 4, esz = dtype == 0 ? 4 : 2;
+  const int nt = (Cout + BN - 1) / BN, nc = (Cin + CH - 1) / CH;
+  char* out = reinterpret_cast<char*>(dst);
+  memset(out, 0, conv_packed_weight_bytes_up2(dtype, Cout, Cin));
+  for (int t = 0; t < nt; ++t)
+    for (int ph = 0; ph < 4; ++ph)
+      for (int c = 0; c < nc; ++c)
+        for (int tap = 0; tap < 4; ++tap) {
+          const int pa = ph >> 1, pb = ph & 1, ty = tap >> 1, tx = tap & 1;
+          char* tile = out + ((((size_t)t * 4 + ph) * nc + c) * 4 + tap) * (size_t)BN * 64;
+          for (int row = 0; row < BN; ++row) {
+            const int co = t * BN + row;
+            if (co >= Cout) break;
+            for (int kl = 0; kl < CH; ++kl) {
+              const int ci = c * CH + kl;
+              if (ci >= Cin) break;
+              const float* w9 = w + ((size_t)co * Cin + ci) * 9;
+              float v = 0.f;
+              for (int ky = 0; ky < 3; ++ky)
+                for (int kx = 0; kx < 3; ++kx)
+                  if ((pa + ky + 1) / 2 == pa + ty && (pb + kx + 1) / 2 == pb + tx) v += w9[ky * 3 + kx];
+              const int q = kl / V, e = kl % V;
+              char* dstp = tile + row * 64 + 16 * (q ^ ((row >> 1) & 3)) + e * esz;
+              if (dtype == DT_F32) memcpy(dstp, &v, 4);
+              else if (dtype == DT_F16) { const _Float16 h = (_Float16)v; memcpy(dstp, &h, 2); }   // RNE
+              else { uint16_t h = f2bf(v); memcpy(dstp, &h, 2); }
+            }
+          }
+        }
+}
+
 size_t conv_packed_weight_bytes_skip(int dtype, int Cout, int Cin, int Cskip) {
   return conv_packed_weight_bytes(dtype, Cout, Cin, 3, 0) + conv_packed_weight_bytes(dtype, Cout, Cskip, 1, 0);
 }
@@ -803,7 +844,16 @@ int conv_route(const ConvDesc& d, ConvRoute* r) {
   const bool gn_ok = d.gn_stats && d.out_mode == OUT_NHWC && g.G == 1 && d.Cout % g.BN == 0 && d.Cout % 4 == 0;
   const bool has_pro = d.pro_a != nullptr;
   // ping-pong kernel (conv_pp.inc.h): 256- or 128-channel output tiles, input as it is or through the in-LDS GroupNorm + SiLU prologue
-  const int pc = fskip ? -1 : pp_config(K.conv_pp, d.ks, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, has_pro, d.pro_silu != 0, d.N, g.Ho, g.Wo, d.Cout);
+  // (phase form of an up-sampling conv: needs the collapsed weight image, carries no residual / split weights / fused output norm)
+  const bool up_ok = d.mode == CONV_UP2 && d.w_up2 && !d.wsplit && a.res_mode == RES_NONE;
+  const int pc = fskip ? -1 : pp_config(K.conv_pp, d.ks, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, has_pro, d.pro_silu != 0, d.N, g.Ho, g.Wo, d.Cout, up_ok);
+  if (pc == 2) {
+    r->kernel = CONV_K_PP; r->form = 2; r->w_up2 = 1;
+    r->geom.BM = 256; r->geom.BN = 256; r->geom.lds_bytes = pp::D<0>::lds_bytes(false);
+    const int slots = 4 * 2 * ((d.Ws + 15) / 16) * ((d.Hs + 15) / 16);   // (phase, low-res pixel tile, pixel wave) per image
+    if (gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
+    return 0;
+  }
   if (pc >= 0) {
     r->kernel = CONV_K_PP; r->form = pc;
     r->geom.BM = pc == 0 ? 256 : 512; r->geom.BN = pc == 0 ? 256 : 128;
@@ -858,6 +908,10 @@ int conv_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream) {
   ConvKArgs a{};
   if (int rc = igemm_args(d, g, a)) return rc;
   if (r.gn_slots) { a.gn_stats = d.gn_stats; a.gn_slots = r.gn_slots; }
+  if (r.w_up2) {
+    MI355_REQUIRE(d.w_up2, -1, "conv: the route asks for the collapsed up-sampling weights (conv_pack_weights_up2) and the description has none");
+    a.w = d.w_up2; a.wbytes = (uint32_t)conv_packed_weight_bytes_up2(d.dtype, d.Cout, d.C0 + d.C1);
+  }
   const size_t esz = d.dtype == 0 ? 4 : 2;
   if (r.act_done & 1) {
     a.act_out = d.act_out; a.act_gamma = d.act_gamma; a.act_beta = d.act_beta; a.act_film = d.act_film; a.act_film_stride = d.act_film_stride;

@@ -79,11 +79,14 @@ template <int CFG> struct D : G<CFG> {
   static constexpr size_t lds_bytes(int pro, int act = 0) { return (size_t)OFF_AB + (pro ? 8 * ABUF : 0) + (act ? XBUF : 0); }
   static_assert(NPX <= NPIECE * 16, "plane too small");
 };
-// Issue / wait schedule of a chunk (9 taps).  Operations a wave issues in L(s), in this order: [PRO, s = 0: the two (a, b) DMAs] [patch
-// pieces of the next chunk whose issue tap is s] [NWP weight pieces of tap s + 5].
-template <int CFG, int PRO> struct S {
+// Issue / wait schedule of a chunk (TAPS taps: 9, or 4 in the phase form of an up-sampling conv).  Operations a wave issues in L(s), in this
+// order: [PRO, s = 0: the two (a, b) DMAs] [patch pieces of the next chunk whose issue tap is s] [NWP weight pieces of tap s + 5].
+// TAPS = 4: the weight stream still runs five taps ahead, so the window of a wait spans the chunk boundary (L(s - 3) .. L(s) are the four L
+// segments of one whole chunk period, whatever s is), and the three patch pieces of a wide chunk go out in L(0), L(0), L(1).
+template <int CFG, int PRO, int TAPS = 9> struct S {
   static constexpr int NWP = G<CFG>::NWP, NPW = G<CFG>::NPW, NAB = PRO ? 2 : 0;
-  static constexpr int iss(int i) { return PRO ? 0 : (CFG == 0 ? 2 * i : i); }                       // tap whose L segment issues patch piece i
+  static_assert(TAPS == 9 || (TAPS == 4 && CFG == 0 && PRO == 0), "the four-tap schedule exists for the wide prologue-free form");
+  static constexpr int iss(int i) { return TAPS == 4 ? i >> 1 : (PRO ? 0 : (CFG == 0 ? 2 * i : i)); }   // tap whose L segment issues patch piece i
   // PRO: piece i is transformed in the L segment of tap trn(i): wide in taps 3 / 5 / 7, narrow in taps 3 .. 7 (tap 1 would wait for pieces issued one L
   // segment earlier; tap 8's barrier publishes the plane).  Same-box A/Bs (profiles/r5_experiments.md; the kernel with those switches is kept as
   // tools/experiments/r5_conv_pp_with_experiment_switches.inc.h.txt): the prologue costs its VALU issue time wherever it runs - whole pieces, half
@@ -94,19 +97,48 @@ template <int CFG, int PRO> struct S {
   static constexpr int npatch(int s) { int n = 0; for (int i = 0; i < NPW; ++i) n += iss(i) == s ? 1 : 0; return n; }
   static constexpr int ops_of(int s) { return (s == 0 ? NAB : 0) + npatch(s) + NWP; }
   // operations younger than the weight pieces of tap s + 1 (issued last in L(s - 4)) at the end of L(s): those of L(s - 3) .. L(s)
-  static constexpr int yw(int s) { int n = 0; for (int u = s - 3; u <= s; ++u) n += ops_of(u < 0 ? u + 9 : u); return n; }
+  static constexpr int yw(int s) { int n = 0; for (int u = s - 3; u <= s; ++u) n += ops_of(u < 0 ? u + TAPS : u); return n; }
   // PRO: operations younger than the piece that L(s + 1) transforms (all pieces are issued in L(0) of this chunk, in index order); 99 = none is due
+  // TAPS = 4: operations younger than the LAST patch piece of the next chunk at the end of the chunk's last L segment (the barrier behind it publishes
+  // the plane; with nine taps the weight window of L(8) is the tighter one already)
   static constexpr int yp(int s) {
+    if (TAPS == 4) {
+      if (s != TAPS - 1) return 99;
+      int n = NWP;
+      for (int v = iss(NPW - 1) + 1; v <= s; ++v) n += ops_of(v);
+      return n;
+    }
     if (!PRO || piece_of(s + 1) < 0) return 99;
     int n = (NPW - 1 - piece_of(s + 1)) + NWP;
     for (int v = 1; v <= s; ++v) n += ops_of(v);
     return n;
   }
   static constexpr int younger(int s) { return yw(s) < yp(s) ? yw(s) : yp(s); }
+  // The first taps of a workgroup's walk follow the pipeline FILL, not a steady-state chunk: the fill issues the patch pieces of chunk 0, then the weight
+  // pieces of taps 0 .. AHEAD - 1 back to back, and waits until fill_left() operations are in flight.  At the end of the first L(s), s < AHEAD - 1, the
+  // operations younger than the weight pieces of tap s + 1 are the fill's taps s + 2 .. AHEAD - 1 and L(0) .. L(s): fill_yw(s).  The counted wait yw(s)
+  // publishes tap s + 1 only if it is no looser than that - or the fill itself already waited for the tap.  Nine taps: fill_yw(s) == yw(s).  Four taps:
+  // the steady-state window of L(0) holds the patch pieces of L(1) of the previous chunk, which the fill never issued (fill_yw(0) = 10 < yw(0) = 11), so
+  // the fill of that form waits for tap 1 as well.
+  static constexpr int fill_left() { return (TAPS == 4 ? 3 : 4) * NWP; }
+  static constexpr int fill_yw(int s) { int n = (3 - s) * NWP; for (int v = 0; v <= s; ++v) n += ops_of(v); return n; }
+  static constexpr bool fill_ok() {
+    for (int s = 0; s < 4; ++s) if (yw(s) > fill_yw(s) && fill_left() > (3 - s) * NWP) return false;
+    return true;
+  }
+  static_assert(fill_ok(), "a counted wait of the walk's first taps is looser than what the pipeline fill left in flight");
   static constexpr bool trn_ok() { for (int i = 0; i < NPW; ++i) if (trn(i) < 2 || trn(i) > 7) return false; return true; }
   static_assert(!PRO || trn_ok(), "a piece is transformed in L(2) .. L(7): after its own wait, before the wave's last lgkmcnt(0) in front of the publishing barrier");
 };
 static_assert(S<0, 0>::younger(0) == 9 && S<0, 0>::younger(2) == 10 && S<0, 0>::younger(5) == 10 && S<0, 0>::younger(6) == 9 && S<0, 0>::younger(8) == 8, "window sums of the round-4 kernel");
+// phase form: L(0) issues 2 patch + 2 weight pieces, L(1) 1 + 2, L(2) and L(3) 2: every weight window is one chunk period (11); the last patch
+// piece (L(1)) has the weight pieces of L(1) .. L(3) behind it (6), so three taps of weights stay in flight across the publishing wait
+static_assert(S<0, 0, 4>::ops_of(0) == 4 && S<0, 0, 4>::ops_of(1) == 3 && S<0, 0, 4>::ops_of(2) == 2 && S<0, 0, 4>::ops_of(3) == 2, "issue counts of the phase form");
+static_assert(S<0, 0, 4>::yw(0) == 11 && S<0, 0, 4>::yw(1) == 11 && S<0, 0, 4>::yw(2) == 11 && S<0, 0, 4>::yw(3) == 11, "weight windows of the phase form");
+static_assert(S<0, 0, 4>::younger(0) == 11 && S<0, 0, 4>::younger(2) == 11 && S<0, 0, 4>::younger(3) == 6, "window sums of the phase form");
+static_assert(S<0, 0>::fill_yw(0) == 9 && S<1, 0>::fill_yw(0) == 5 && S<0, 0, 4>::fill_yw(0) == 10 && S<0, 0, 4>::fill_left() == 6 && S<0, 0, 4>::fill_yw(1) == 11,
+              "fill windows: nine taps equal the steady state; four taps: the first L(0) has one operation fewer behind tap 1, so the fill waits for tap 1 too");
+static_assert(S<0, 0, 4>::iss(2) < 4 - 1, "the last patch piece is issued before the L segment whose wait publishes the plane");
 }  // namespace pp
 
 template <int N> __device__ __forceinline__ void pp_wait_vm() {   // s_waitcnt vmcnt(N) only (gfx9 encoding: vmcnt[3:0] | expcnt << 4 | lgkmcnt << 8 | vmcnt[5:4] << 14)
@@ -153,10 +185,20 @@ __device__ __forceinline__ void pp_pro_words(const uint32_t (&raw)[NV], const fl
 
 // ACT = 1 (wide only): the GroupNorm (+ SiLU, FiLM) site that READS this conv's output is applied in the epilogue, in place (launcher: one 16 x 16 tile
 // per image, no residual, 8 or 16 channels per group) - as conv3x3_ws_kernel<T, PRO, 1> did; a template parameter so that the other forms keep their registers.
-template <typename T, int CFG, int PRO, int ACT = 0>
+// UP = 1 (wide, prologue-free): the PHASE form of a conv over a nearest-x2 up-sampled input (unet.py:209-212 Upsample.conv).  Output pixel
+// (2 i + a, 2 j + b) of phase (a, b) reads low-res rows i - 1 + a, i + a and columns j - 1 + b, j + b only (neighbouring taps of the 3x3 filter meet
+// the same low-res pixel), so each phase is a 2x2 conv of the LOW-RES image with the filter rows / columns summed ([w0, w1 + w2] for phase 0,
+// [w0 + w1, w2] for phase 1: conv_pack_weights_up2) - 4 taps per chunk instead of 9 for the same output, and the high-res zero padding is the low-res
+// zero padding.  A pixel tile is (phase, 16 x 16 low-res pixels of one image): mt = phase * (N * tiles per image) + tile, so with a whole-chip batch a
+// workgroup walks the four phases of one image back to back (its patch comes from its XCD's L2).  The patch is gathered unshifted from origin
+// (y0 - 1 + a, x0 - 1 + b), tap (ky, kx) in {0, 1}^2 reads patch pixel (row + ky, col + kx), the epilogue stores pixel (2 y + a, 2 x + b).  Four taps per
+// chunk are no multiple of the 6-slot weight ring: this form keeps the ring position in two scalars instead of immediates.
+template <typename T, int CFG, int PRO, int ACT = 0, int UP = 0>
 __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_mt, int n_nt) {
+  constexpr int TAPS = UP ? 4 : 9, KW = UP ? 2 : 3;
+  static_assert(UP == 0 || (CFG == 0 && PRO == 0 && ACT == 0), "the phase form is the wide prologue-free kernel");
   using Dg = pp::D<CFG>;
-  using Sc = pp::S<CFG, PRO>;
+  using Sc = pp::S<CFG, PRO, TAPS>;
   using E = Elem<T>;
   constexpr int NRING = pp::NRING, AHEAD = pp::AHEAD;
   constexpr int VW = Dg::VW, TH = Dg::TH, PW = Dg::PW, NPX = Dg::NPX, PLANE = Dg::PLANE, AROWB = Dg::AROWB, BN = Dg::BN, WTAP = Dg::WTAP;
@@ -174,7 +216,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
   const int wm = CFG == 0 ? grp : wave8 >> 1, wn = CFG == 0 ? wave8 & 3 : wave8 & 1;
   const int lr = lane & 15, lq = lane >> 4;
   const int tpi = p.tiles_x * p.tiles_y;
-  const int T9 = p.nchunks * 9;               // taps per tile (a multiple of 18: the launcher requires an even chunk count)
+  const int T9 = p.nchunks * TAPS;            // taps per tile (a multiple of 2 TAPS: the launcher requires an even chunk count)
+  const int npt = p.N * tpi;                  // UP: pixel tiles per phase (tiles_x / tiles_y tile the LOW-RES image)
   // Tile walk (as conv3x3_ws_kernel): 8 consecutive workgroups (one per XCD) take 8 consecutive pixel tiles, the workgroup 8 further on
   // (same XCD, same L2) the next channel tile of the same pixels.
   const int ntp = ((n_mt + 7) / 8) * 8 * n_nt;
@@ -186,7 +229,9 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
     for (t += gridDim.x; t < ntp; t += gridDim.x) { int mt, nt; decode(t, mt, nt); if (mt < n_mt) break; }
     return t;
   };
-  auto origin = [&](int mt, int& n0, int& y0, int& x0) {
+  auto origin = [&](int mt, int& n0, int& y0, int& x0, int& ph) {
+    ph = UP ? mt / npt : 0;
+    if constexpr (UP != 0) mt -= ph * npt;
     const int ng = mt / tpi, rem = mt - ng * tpi;
     const int tyi = rem / p.tiles_x, txi = rem - tyi * p.tiles_x;
     n0 = ng; y0 = tyi * TH; x0 = txi * VW;
@@ -208,16 +253,23 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
   // Weights: packed image [nt128][chunk][tap][128 rows][64 B], rows already XOR-swizzled: the LDS image.  Wide: a tap of a 256-channel
   // tile = the same (chunk, tap) tile of two consecutive 128-row tiles, 16 pieces of 1 KB; wave w moves pieces 2w, 2w + 1, so group g
   // moves half g.  Narrow: one 128-row tile, 8 pieces, wave w moves piece w.  Piece j lands at ring slot + 1024 j: row r at 64 r.
-  auto ws_base = [&](int t) { int mt, nt; decode(t, mt, nt); return (uint32_t)((CFG == 0 ? 2 * nt + grp : nt) * T9) * 8192u; };
+  // UP: [nt128][phase][chunk][tap 0..3][128 rows][64 B] (conv_pack_weights_up2): the stream of a (phase, channel) tile is linear as well
+  auto ws_base = [&](int t) {
+    int mt, nt; decode(t, mt, nt);
+    const int t128 = CFG == 0 ? 2 * nt + grp : nt;
+    return (uint32_t)((UP ? 4 * t128 + mt / npt : t128) * T9) * 8192u;
+  };
   uint32_t ws_soff = ws_base(t_first);   // the stream's next tap; moves to the next tile of the walk five taps before the multiplication does
   const uint32_t wvo0 = (uint32_t)((CFG == 0 ? ((2 * wave8) & 7) : wave8) * 1024 + lane * 16), wvo1 = wvo0 + 1024u;
-  auto issue_w = [&](auto ringc) {
-    constexpr int ring = decltype(ringc)::value;
-    char* dst = smem + ring * WTAP + (NWP * wave8) * 1024;
+  auto issue_w_at = [&](int roff) {           // roff: byte offset of the ring slot (an immediate, or UP: a scalar)
+    char* dst = smem + roff + (NWP * wave8) * 1024;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void*)dst, 16, wvo0, ws_soff, 0, 0);
     if constexpr (NWP == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void*)(dst + 1024), 16, wvo1, ws_soff, 0, 0);
     ws_soff += 8192u;
   };
+  auto issue_w = [&](auto ringc) { issue_w_at(decltype(ringc)::value * WTAP); };
+  int ring_rd = 0, ring_wr = AHEAD * WTAP;   // UP: the ring slot the next tap reads / fills (byte offsets, uniform)
+  (void)ring_rd; (void)ring_wr;
   // Patch: piece j = 16 pixel rows of 64 B (pixels 16 j .. 16 j + 15 of the PW x PH patch, row-major); lane l lands at slot l & 3 of pixel
   // 16 j + (l >> 2), so the slot swizzle (by the pixel's column) goes into the per-lane SOURCE address; zero padding and the pad pixels
   // are out-of-range offsets (the DMA writes zeros for them: tools/probe/lds_dma_oob_probe.cpp).  Wave w moves pieces w, 8 + w, 16 + w, ...
@@ -236,10 +288,11 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
     int ln;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
     asm volatile("" : "+s"(t));
-    int mt, nt, n0, y0, x0;
+    int mt, nt, n0, y0, x0, ph;
     decode(t, mt, nt);
-    origin(mt, n0, y0, x0);
-    const int cy0 = y0 - 1, cx0 = x0 - 1;
+    origin(mt, n0, y0, x0, ph);
+    const int cy0 = y0 - 1 + (ph >> 1), cx0 = x0 - 1 + (ph & 1);   // (UP: low-res coordinates, shifted by the phase)
+    const int Hb = UP ? p.Hs : p.Hc, Wb = UP ? p.Ws : p.Wc;
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
       const int idx = 16 * (8 * i + wave8) + (ln >> 2);
@@ -247,8 +300,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
       const int fqx = (ln & 3) ^ ((px >> 1) & 3);
       const int cy = cy0 + py, cx = cx0 + px;
       int sp = -1;
-      if (idx < NPX && cy >= 0 && cy < p.Hc && cx >= 0 && cx < p.Wc) {
-        if (p.mode == CONV_UP2) sp = (n0 * p.Hs + (cy >> 1)) * p.Ws + (cx >> 1);
+      if (idx < NPX && cy >= 0 && cy < Hb && cx >= 0 && cx < Wb) {
+        if (UP == 0 && p.mode == CONV_UP2) sp = (n0 * p.Hs + (cy >> 1)) * p.Ws + (cx >> 1);
         else sp = (n0 * p.Hs + cy) * p.Ws + cx;
       }
       if constexpr (KEYED) {
@@ -340,9 +393,9 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
   f32x4 acc[8][NI];
   f32x4 cin[NI];                           // bias + timestep embedding of this lane's channels: the accumulators start from it
   auto cinit_load = [&](int t) {
-    int mt, nt, n0, y0, x0;
+    int mt, nt, n0, y0, x0, ph;
     decode(t, mt, nt);
-    origin(mt, n0, y0, x0);
+    origin(mt, n0, y0, x0, ph);
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
       const int co = nt * BN + wn * 64 + ni * 16 + 4 * lq;   // Cout % BN == 0: always in range
@@ -371,7 +424,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
   if constexpr (NPW > 5) issue_patch(IC<5>(), IC<0>(), 0);
   issue_w(IC<0>()); issue_w(IC<1>()); issue_w(IC<2>()); issue_w(IC<3>()); issue_w(IC<4>());
   acc_init();
-  pp_wait_vm<4 * NWP>();                   // this wave's pieces of the patch (and (a, b)) and of tap 0 have landed (taps 1 .. 4 may fly)
+  pp_wait_vm<Sc::fill_left()>();           // this wave's pieces of the patch (and (a, b)) and of tap 0 have landed (taps 1 .. 4 may fly; phase form: taps 2 .. 4, pp::S::fill_yw)
   if constexpr (PRO != 0) {
     transform_piece(IC<0>(), IC<0>()); transform_piece(IC<1>(), IC<0>()); transform_piece(IC<2>(), IC<0>());
     if constexpr (NPW > 3) transform_piece(IC<3>(), IC<0>());
@@ -391,16 +444,16 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
   for (int t = t_first; t < ntp;) {
     const int t_next = next_valid(t);
     const int t_nextc = t_next < ntp ? t_next : t;   // the streams' next tile (clamped at the end of the walk)
-    int mt, nt, n0, y0, x0;
+    int mt, nt, n0, y0, x0, ph;
     decode(t, mt, nt);
-    origin(mt, n0, y0, x0);
+    origin(mt, n0, y0, x0, ph);
     if (grp == 1) pp_barrier();            // one tick behind group 0
     STAMP(7)
     // one tap: c = the chunk being multiplied (runtime), P = its parity (patch plane), S = tap of the chunk; lastp: the chunk pair is the tile's last
     auto tap = [&](auto Pc, auto Sc_, int c, bool lastp) {
       constexpr int P = decltype(Pc)::value, S = decltype(Sc_)::value;
-      constexpr int ky = S / 3, kx = S % 3, ring = (P * 9 + S) % NRING, ringn = (ring + AHEAD) % NRING;
-      const bool last_of_tile = lastp && P == 1 && S == 8;
+      constexpr int ky = S / KW, kx = S % KW, ring = UP ? 0 : (P * 9 + S) % NRING, ringn = (ring + AHEAD) % NRING;   // (UP: ring_rd / ring_wr instead)
+      const bool last_of_tile = lastp && P == 1 && S == TAPS - 1;
       // ---- L segment: this tap's fragments; this wave's share of the DMA; PRO: one of its pieces of the next chunk in place ----
       u32x4 af[8], bf[NI];
       constexpr int TRP = PRO != 0 && !(abl & 256) ? Sc::piece_of(S) : -1;   // the piece of the next chunk this tap transforms
@@ -410,7 +463,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
         __builtin_amdgcn_sched_barrier(0);
       }
       {
-        int ab = a_base[kx], bb = ring < 3 ? b_base0 : b_base1;
+        int ab = a_base[kx], bb = UP ? b_base0 + ring_rd : (ring < 3 ? b_base0 : b_base1);
         asm volatile("" : "+v"(ab), "+v"(bb));
         const char* ap = smem + ab;
         const char* bp = smem + bb;
@@ -430,27 +483,34 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
       // in once, in front of that chunk), the weights five taps ahead (tap S = 4 of a tile's last chunk is the first to fetch the next
       // tile's weights).  Past the end of the walk both re-fetch the last tile's addresses into buffers nobody reads.
       if constexpr (P == 1 && S == 0) { if (lastp) ps_setup(t_nextc); }
-      if constexpr (P == 1 && S == 4) { if (lastp) ws_soff = ws_base(t_nextc); }
+      if constexpr (P * TAPS + S == 2 * TAPS - AHEAD) { if (lastp) ws_soff = ws_base(t_nextc); }   // (9 taps: P = 1, S = 4; 4 taps: P = 0, S = 3)
       {
         const int scn = P == 0 ? c + 1 : (lastp ? 0 : c + 1);
         if constexpr (S == 0 && !(abl & 16)) issue_ab(scn);
         if constexpr (!(abl & 16)) issue_patch_at(IC<S>(), IC<1 - P>(), scn);
       }
-      if constexpr (!(abl & 8)) issue_w(IC<ringn>());
+      if constexpr (UP != 0) {
+        if constexpr (!(abl & 8)) issue_w_at(ring_wr);
+        ring_rd = ring_rd == (NRING - 1) * WTAP ? 0 : ring_rd + WTAP;
+        ring_wr = ring_wr == (NRING - 1) * WTAP ? 0 : ring_wr + WTAP;
+      } else {
+        if constexpr (!(abl & 8)) issue_w(IC<ringn>());
+      }
       if constexpr (TRP >= 0) {
         __builtin_amdgcn_sched_barrier(0);
         tr_finish(IC<(TRP < 0 ? 0 : TRP)>(), tro);
       }
 #ifdef CONV_STAMPS
-      const int tr_tap = c * 9 + S;
+      const int tr_tap = c * TAPS + S;
       const bool tr_on = blockIdx.x == 0 && t == t_first && tr_tap >= PP_TRACE_TAP0 && tr_tap < PP_TRACE_TAP0 + 4;   // every lane writes the same word
       uint32_t tr_a, tr_v;
 #endif
       STAMP(0) PP_TRACE(0)
       constexpr int YW = Sc::yw(S), YP = Sc::yp(S), YY = YW < YP ? YW : YP;
       if constexpr (P == 0 && S < 4 && PAIR) {     // the first taps of a tile: the previous tile's epilogue is inside the weight window
-        if (extra == 0) pp_wait_vm<YY>();
-        else if (extra == EPI_STORES) pp_wait_vm<(YW + EPI_STORES < YP ? YW + EPI_STORES : YP)>();
+        const int ex = UP ? (c == 0 ? extra : 0) : extra;   // (UP: every chunk has four taps; only the tile's first chunk has the epilogue behind it.  Nine taps: DESIGN.md section 9)
+        if (ex == 0) pp_wait_vm<YY>();
+        else if (ex == EPI_STORES) pp_wait_vm<(YW + EPI_STORES < YP ? YW + EPI_STORES : YP)>();
         else pp_wait_vm<(YW + 2 * EPI_STORES < YP ? YW + 2 * EPI_STORES : YP)>();
       } else {
         pp_wait_vm<YY>();
@@ -478,12 +538,17 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
     };
     for (int c = 0; c < p.nchunks; c += 2) {
       const bool lastp = c + 2 >= p.nchunks;
+      if constexpr (UP != 0) {
+        tap(IC<0>(), IC<0>(), c, lastp); tap(IC<0>(), IC<1>(), c, lastp); tap(IC<0>(), IC<2>(), c, lastp); tap(IC<0>(), IC<3>(), c, lastp);
+        tap(IC<1>(), IC<0>(), c + 1, lastp); tap(IC<1>(), IC<1>(), c + 1, lastp); tap(IC<1>(), IC<2>(), c + 1, lastp); tap(IC<1>(), IC<3>(), c + 1, lastp);
+      } else {
       tap(IC<0>(), IC<0>(), c, lastp); tap(IC<0>(), IC<1>(), c, lastp); tap(IC<0>(), IC<2>(), c, lastp);
       tap(IC<0>(), IC<3>(), c, lastp); tap(IC<0>(), IC<4>(), c, lastp); tap(IC<0>(), IC<5>(), c, lastp);
       tap(IC<0>(), IC<6>(), c, lastp); tap(IC<0>(), IC<7>(), c, lastp); tap(IC<0>(), IC<8>(), c, lastp);
       tap(IC<1>(), IC<0>(), c + 1, lastp); tap(IC<1>(), IC<1>(), c + 1, lastp); tap(IC<1>(), IC<2>(), c + 1, lastp);
       tap(IC<1>(), IC<3>(), c + 1, lastp); tap(IC<1>(), IC<4>(), c + 1, lastp); tap(IC<1>(), IC<5>(), c + 1, lastp);
       tap(IC<1>(), IC<6>(), c + 1, lastp); tap(IC<1>(), IC<7>(), c + 1, lastp); tap(IC<1>(), IC<8>(), c + 1, lastp);
+      }
     }
 
     // ---------------- epilogue (as conv3x3_ws_kernel: MFMA rows are channels, columns are pixels; lane (lr, lq) holds 4 consecutive
@@ -493,7 +558,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
     const int co_s = PAIR ? nt * BN + wn * 64 + (lq & 1) * 16 + (lq >> 1) * 8 : co_w;
     GnPartial<NI> gp;
     const bool do_gn = p.gn_stats != nullptr;
-    const bool gn_mask = ((p.Wo & (VW - 1)) | (p.Ho & (TH - 1))) != 0;
+    const int Hm = UP ? p.Hs : p.Ho, Wm = UP ? p.Ws : p.Wo;   // the image the tile's pixels index (UP: low-res; the store goes to (2 y + a, 2 x + b))
+    const bool gn_mask = ((Wm & (VW - 1)) | (Hm & (TH - 1))) != 0;
     auto epi_half = [&](auto hc, auto resc, auto gnc) {
       constexpr int h = decltype(hc)::value, GNM = decltype(gnc)::value;
       constexpr bool HAS_RES = decltype(resc)::value != 0;
@@ -502,9 +568,9 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int y = y0 + wm * WROWS + Dg::row(h * 4 + j), x = x0 + Dg::col(h * 4 + j) + lr;
-        const bool ok = y < p.Ho && x < p.Wo;
+        const bool ok = y < Hm && x < Wm;
         vm[j] = ok ? 1.f : 0.f;
-        const uint32_t opix = (uint32_t)((n0 * p.Ho + y) * p.Wo + x);
+        const uint32_t opix = UP ? (uint32_t)((n0 * p.Ho + 2 * y + (ph >> 1)) * p.Wo + 2 * x + (ph & 1)) : (uint32_t)((n0 * p.Ho + y) * p.Wo + x);
         ovo[j] = ok ? (opix * (uint32_t)p.Cout + (uint32_t)co_s) * ESZ : p.obytes;
         uint32_t rpix = opix;
         if (p.res_mode == RES_UP2) rpix = (uint32_t)((n0 * p.Hr + (y >> 1)) * p.Wr + (x >> 1));
@@ -657,8 +723,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
     } else {
       if (!do_gn) epi(IC<0>(), IC<0>()); else if (!gn_mask) epi(IC<0>(), IC<1>()); else epi(IC<0>(), IC<2>());
     }
-    if (do_gn && ACT == 0) {   // slot = (pixel tile of the image, pixel wave); quads of this wave's 64 channels
-      const int rem = mt - n0 * tpi;
+    if (do_gn && ACT == 0) {   // slot = (pixel tile of the image, pixel wave); quads of this wave's 64 channels (UP: (phase, low-res tile, pixel wave))
+      const int rem = UP ? mt - ph * npt - n0 * tpi + ph * tpi : mt - n0 * tpi;
       gp.store(p.gn_stats + (((size_t)n0 * p.gn_slots + rem * WMN + wm) * (size_t)(p.Cout >> 2) + ((nt * BN + wn * 64) >> 2)) * 2, lq, lr);
     }
     acc_init();
@@ -685,11 +751,20 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
 // gets a tile, 2 = always (tests); bit 2: the prologue form of the wide geometry; bit 3: the narrow geometry; bit 4: the prologue form of the
 // narrow geometry too (off by default: same-box it ties the warp-specialised kernel at 256 / 384 input channels and loses 3-5 % at 128,
 // profiles/r5_experiments.md - the prologue's arithmetic is amortised over 128 output channels instead of 256).
-// Returns the geometry (0 wide, 1 narrow) or -1.
-static int pp_config(int mode, int ks, int G, int bn_pack, int out_mode, int stride, int nchunks, bool has_pro, bool pro_silu, int N, int Ho, int Wo, int Cout) {
+// Bit 6 (64): the phase form of a prologue-free conv over a nearest-x2 up-sampled input (four 2x2 convs of the low-res image, UP = 1 above: 4/9 of
+// the MFMAs): wide geometry only, the geometry rule and the tile count apply to the LOW-RES image (16 x 16 low-res pixels per tile, four phase
+// tiles each); up_ok: the caller has the collapsed weight image and nothing the form does not carry (residual, split weights, fused output norm).
+// Returns the geometry (0 wide, 1 narrow, 2 wide in phase form) or -1.
+static int pp_config(int mode, int ks, int G, int bn_pack, int out_mode, int stride, int nchunks, bool has_pro, bool pro_silu, int N, int Ho, int Wo, int Cout,
+                     bool up_ok = false) {
   if (!(mode & 3) || ks != 3 || G != 1 || bn_pack != 128 || out_mode != OUT_NHWC || stride != 1) return -1;
   if (has_pro && !pro_silu) return -1;
   if (nchunks < 2 || (nchunks & 1)) return -1;
+  if (up_ok && (mode & 64) && !has_pro && Cout % 256 == 0 && !(Ho & 1) && !(Wo & 1) && Ho >= 32 && Wo >= 32) {
+    const int Hs = Ho / 2, Ws = Wo / 2;
+    const int n_mt = 4 * N * ((Ws + 15) / 16) * ((Hs + 15) / 16), n_nt = Cout / 256;
+    if ((mode & 3) >= 2 || n_mt * n_nt >= ws_num_cus()) return 2;
+  }
   int cfg = -1;
   if (Cout % 256 == 0 && Wo >= 16 && Ho >= 16) cfg = 0;
   else if (Cout % 128 == 0 && (mode & 8) && Wo >= 32 && Ho >= 16) cfg = 1;
@@ -701,22 +776,24 @@ static int pp_config(int mode, int ks, int G, int bn_pack, int out_mode, int str
   return n_mt * n_nt >= ws_num_cus() ? cfg : -1;
 }
 
-template <typename T, int CFG, int PRO, int ACT = 0>
+template <typename T, int CFG, int PRO, int ACT = 0, int UP = 0>
 int launch_pp_k(ConvKArgs a, hipStream_t s) {
   using Dg = pp::D<CFG>;
   a.lvw = CFG == 0 ? 4 : 5; a.lth = 4; a.PW = Dg::PW; a.PH = Dg::PH; a.NP = Dg::NPX;
-  a.tiles_x = (a.Wo + Dg::VW - 1) / Dg::VW; a.tiles_y = (a.Ho + Dg::TH - 1) / Dg::TH;
-  const int n_mt = a.N * a.tiles_x * a.tiles_y, n_nt = a.Cout / Dg::BN;
-  if (int rc = mi355_allow_big_lds(conv3x3_pp_kernel<T, CFG, PRO, ACT>, "conv3x3 (ping-pong)")) return rc;
+  const int Ht = UP ? a.Hs : a.Ho, Wt = UP ? a.Ws : a.Wo;   // the image the pixel tiles cover (phase form: the low-res source)
+  a.tiles_x = (Wt + Dg::VW - 1) / Dg::VW; a.tiles_y = (Ht + Dg::TH - 1) / Dg::TH;
+  const int n_mt = (UP ? 4 : 1) * a.N * a.tiles_x * a.tiles_y, n_nt = a.Cout / Dg::BN;
+  if (int rc = mi355_allow_big_lds(conv3x3_pp_kernel<T, CFG, PRO, ACT, UP>, "conv3x3 (ping-pong)")) return rc;
   const int ntp = ((n_mt + 7) / 8) * 8 * n_nt, ncu = ws_num_cus();
   const int grid = ntp < ncu ? ntp : ncu;   // one persistent workgroup per CU
-  hipLaunchKernelGGL((conv3x3_pp_kernel<T, CFG, PRO, ACT>), dim3(grid), dim3(512), Dg::lds_bytes(PRO, ACT) + PP_TRACE_BYTES, s, a, n_mt, n_nt);
+  hipLaunchKernelGGL((conv3x3_pp_kernel<T, CFG, PRO, ACT, UP>), dim3(grid), dim3(512), Dg::lds_bytes(PRO, ACT) + PP_TRACE_BYTES, s, a, n_mt, n_nt);
   return 0;
 }
 
 // cfg: pp_config's geometry; a.act_out set: the form that applies the output GroupNorm in place (wide, conv_route decides)
 template <typename T>
 int launch_pp(const ConvKArgs& a, int cfg, hipStream_t s) {
+  if (cfg == 2) return launch_pp_k<T, 0, 0, 0, 1>(a, s);   // phase form: a.w is the collapsed image (conv_launch)
   if (a.act_out) return a.pro_a ? launch_pp_k<T, 0, 2, 1>(a, s) : launch_pp_k<T, 0, 0, 1>(a, s);
   if (a.pro_a) return cfg == 0 ? launch_pp_k<T, 0, 2>(a, s) : launch_pp_k<T, 1, 2>(a, s);
   return cfg == 0 ? launch_pp_k<T, 0, 0>(a, s) : launch_pp_k<T, 1, 0>(a, s);

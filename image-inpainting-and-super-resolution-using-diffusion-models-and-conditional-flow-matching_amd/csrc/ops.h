@@ -37,6 +37,8 @@ struct ConvDesc {
   const float* pro_b = nullptr;
   int pro_silu = 0;
   const void* w = nullptr;                  // packed by conv_pack_weights
+  const void* w_up2 = nullptr;              // optional, mode CONV_UP2 / ks 3: the same filter collapsed to four 2x2 phase filters (conv_pack_weights_up2);
+                                            // ConvRoute::w_up2 says whether the launch reads this image instead of w (null: it never does)
   const float* bias = nullptr;              // [Cout]
   int Cout = 0;
   const float* emb = nullptr; int emb_stride = 0;   // per-(n, co) additive term (ResBlock emb_layers)
@@ -87,7 +89,7 @@ enum ConvKernel { CONV_K_IGEMM = 0, CONV_K_1X1, CONV_K_1X1_PP, CONV_K_IN, CONV_K
 struct ConvRoute {
   int kernel = CONV_K_IGEMM;
   ConvGeom geom{};          // the implicit-GEMM tile, or the ping-pong / warp-specialised one (grid_m / grid_n stay the plain launch's: workspace sizing)
-  int form = 0;             // 1X1_PP: 0 = 512 x 128, 1 = 256 x 256, 2 = 128 x 256 tiles; OUT: 1 = FIXED; PP: 0 = wide, 1 = narrow; SMALL: 1 = w8x2
+  int form = 0;             // 1X1_PP: 0 = 512 x 128, 1 = 256 x 256, 2 = 128 x 256 tiles; OUT: 1 = FIXED; PP: 0 = wide, 1 = narrow, 2 = wide in phase form (up-sampling conv as four 2x2 convs); SMALL: 1 = w8x2
   int BM = 0, GC = 0, ntn = 0;     // 1X1: pixel tile, weight chunks per group, output-channel tiles per workgroup,
   int lvw = 0, lth = 0, G = 0, tiles_x = 0, tiles_y = 0;   //   and its pixel tiling: log2 of the tile's width / height, images per tile
   int n_mt = 0, n_nt = 0;          // 1X1_PP: pixel and channel tiles; 1X1 / SMALL: workgroups along M / N
@@ -97,6 +99,7 @@ struct ConvRoute {
   int act_done = 0;         // bit 0 / 1: the GroupNorm site act_out / act2_out is applied in the epilogue
   int axpy = 0, skip = 0;   // the Euler update replaces the store; the fused 1x1 skip conv is carried
   int reads_nchw = 0;       // the first conv reads the fp32 NCHW tensors nchw0 / nchw1 itself (src0 unused)
+  int w_up2 = 0;            // the launch reads ConvDesc::w_up2 (the collapsed weight image of the phase form), not ConvDesc::w
 };
 // Pure host code (nothing launched or allocated): 0 and *r filled, or < 0 for a description no kernel runs (message set).
 int conv_route(const ConvDesc& d, ConvRoute* r);
@@ -109,6 +112,10 @@ int conv_tile_n(int Cout);
 // host-side packing: w_host [Cout][Cin][ks][ks] fp32 (Cin = logical input channels; padded to a chunk)
 // split = 1 (bf16 only): [hi | lo] halves along K, hi = bf16(w), lo = bf16(w - hi); the chunk count doubles
 void conv_pack_weights(int dtype, const float* w_host, int Cout, int Cin, int ks, void* dst_host, int split = 0);
+// a [Cout][Cin][3][3] filter applied behind a nearest-x2 up-sample, collapsed (in fp32) to the four [2][2] filters of the output phases:
+// per 128-channel pack tile [phase][chunk][tap 0..3][128 rows][64 B], elements rounded and swizzled as above
+size_t conv_packed_weight_bytes_up2(int dtype, int Cout, int Cin);
+void conv_pack_weights_up2(int dtype, const float* w_host, int Cout, int Cin, void* dst_host);
 // [3x3 filter w3 [Cout][Cin][3][3] | 1x1 filter w1 [Cout][Cskip]] per 128-channel pack tile: the 3x3 tiles, then one tile per skip chunk
 size_t conv_packed_weight_bytes_skip(int dtype, int Cout, int Cin, int Cskip);
 void conv_pack_weights_skip(int dtype, const float* w3, const float* w1, int Cout, int Cin, int Cskip, void* dst_host);

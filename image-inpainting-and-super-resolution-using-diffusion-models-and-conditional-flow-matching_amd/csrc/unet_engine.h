@@ -45,6 +45,9 @@ struct PlanOp {
   // small levels: a ResBlock's 1x1 skip_connection op names the second conv that can carry it (carrier), and that conv names the skip op
   // (skip_op) and holds the fused weight image / summed bias (conv_pack_weights_skip); decided per launch (conv_route)
   int carrier = -1, skip_op = -1; size_t wf_off = 0, bf_off = 0;
+  // prologue-free conv over a nearest-x2 up-sample (Upsample.conv): a second weight image, the filter collapsed to four 2x2 phase filters
+  // (conv_pack_weights_up2), for the ping-pong kernel's phase form; both images are kept, the route decides per launch
+  int has_wu = 0; size_t wu_off = 0;
 };
 
 struct mi355_unet {

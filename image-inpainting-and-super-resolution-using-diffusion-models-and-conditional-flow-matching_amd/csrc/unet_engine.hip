@@ -134,6 +134,14 @@ struct Walker {
     op.w_off = put_conv(prefix + ".weight", Cout, Cin_logical, ks, conv1d);
     op.bias_off = put_f32(prefix + ".bias", {Cout});
     op.use_pro = use_pro; op.pro_silu = pro_silu; op.emb_off = emb_off; op.res = res; op.res_mode = res_mode; op.out_mode = out_mode;
+    // Upsample.conv in a shape the phase form of the ping-pong kernel could take (conv_pp bit 6; the route looks at batch and knobs again per launch)
+    const int cin_t = T(s0).C + (s1 >= 0 ? T(s1).C : 0);
+    if (mode == CONV_UP2 && ks == 3 && !conv1d && !use_pro && res < 0 && out_mode == OUT_NHWC && !cfg.differentiable && !net->wsplit && (net->knobs.conv_pp & 64) &&
+        Cout % 256 == 0 && cin_t == Cin_logical && T(s0).H >= 16 && T(s0).W >= 16) {
+      const float* pw = P(prefix + ".weight", {Cout, Cin_logical, ks, ks});
+      op.has_wu = 1; op.wu_off = alloc(conv_packed_weight_bytes_up2(dtype, Cout, Cin_logical));
+      if (!dry && pw) conv_pack_weights_up2(dtype, pw, Cout, Cin_logical, blob.data() + op.wu_off);
+    }
     int Ho = T(s0).H, Wo = T(s0).W;
     if (mode == CONV_UP2) { Ho *= 2; Wo *= 2; }
     else if (mode == CONV_POOL2) { Ho /= 2; Wo /= 2; }
@@ -653,6 +661,7 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
       c.pro_a = sp; c.pro_b = sp + (size_t)B * net->site_C[op.gn_site];
     }
     c.w = W + op.w_off; c.bias = WF(op.bias_off); c.Cout = op.Cout;
+    if (op.has_wu) c.w_up2 = W + op.wu_off;
     if (op.src0 == net->in_tensor) {
       c.cin_real = net->cfg.in_channels;
       // the first conv may read the caller's fp32 NCHW tensors itself (conv_edge bit 2): no packed copy, no pack launch

@@ -241,10 +241,11 @@ class Ops:
 
     # --- parity-test ops on NCHW fp32 tensors (pack -> MFMA kernel -> unpack) ---
     def conv2d(self, x, weight, bias=None, stride=1, resample=0, gn=None, gn_silu=False, dtype=_lib.MI355_F32, x1=None, emb=None,
-               res=None, res_mode=1, debug=None):
+               res=None, res_mode=1, debug=None, info=None):
         """weight/bias: CPU fp32 tensors in the reference layout [Co,Ci(+Ci1),k,k]; gn = (gamma, beta) device tensors over the
         (concatenated) input channels; x1: second source of a channel concat; emb [B, Co]; res [B, Co, Hr, Wr] with res_mode 1
-        (same size) or 2 (nearest x2 of a half-size tensor)."""
+        (same size) or 2 (nearest x2 of a half-size tensor).  info: a dict that receives what was launched (kernel, form, tile_m, tile_n:
+        mi355_conv_extras::route; the call then goes through mi355_conv2d_ex with no fused form asked for, which needs Co % 32 == 0)."""
         B, Cin, H, W = x.shape
         Co, Ci, k, _ = weight.shape
         Cin1 = 0 if x1 is None else x1.shape[1]
@@ -268,12 +269,17 @@ class Ops:
         w = weight.detach().to("cpu", torch.float32).contiguous()
         b = bias.detach().to("cpu", torch.float32).contiguous() if bias is not None else None
         fp = C.POINTER(C.c_float)
-        check(L.mi355_conv2d(_req(x, "x"), _req(x1, "x1") if x1 is not None else None, Cin1, C.cast(w.data_ptr(), fp),
-                             C.cast(b.data_ptr(), fp) if b is not None else None, _req(y, "y"), B, Cin, H, W, Co, k, stride, resample,
-                             _req(gn[0], "gamma") if gn else None, _req(gn[1], "beta") if gn else None, int(gn_silu),
-                             _req(emb, "emb") if emb is not None else None, _req(res, "res") if res is not None else None, int(res_mode),
-                             dtype, C.byref(debug if debug is not None else _lib.debug_config()), C.c_void_p(ws.data_ptr()), wsb, _stream()),
-              "mi355_conv2d")
+        args = (_req(x, "x"), _req(x1, "x1") if x1 is not None else None, Cin1, C.cast(w.data_ptr(), fp),
+                C.cast(b.data_ptr(), fp) if b is not None else None, _req(y, "y"), B, Cin, H, W, Co, k, stride, resample,
+                _req(gn[0], "gamma") if gn else None, _req(gn[1], "beta") if gn else None, int(gn_silu),
+                _req(emb, "emb") if emb is not None else None, _req(res, "res") if res is not None else None, int(res_mode),
+                dtype, C.byref(debug if debug is not None else _lib.debug_config()), C.c_void_p(ws.data_ptr()), wsb, _stream())
+        if info is None:
+            check(L.mi355_conv2d(*args), "mi355_conv2d")
+        else:
+            ex = _lib.ConvExtrasC()
+            check(L.mi355_conv2d_ex(*args, C.byref(ex)), "mi355_conv2d_ex")
+            info.update(kernel=ex.route[0], form=ex.route[1], tile_m=ex.route[2], tile_n=ex.route[3])
         return y
 
     def conv2d_ex(self, x, weight, bias, dtype=_lib.MI355_F32, skip=None, sites=(), film=None, debug=None):
