@@ -12,13 +12,16 @@ import os
 import torch
 
 from mi355 import dist as mdist
-from torchcfm_compat import UNetModelWrapper
+from torchcfm_compat import ClassCondUNetModelWrapper, UNetModelWrapper
 
 
-def build_model(num_channel=128, device="cuda:0", precision=None):
-    """cifar10/compute_fid.py:39-48."""
-    return UNetModelWrapper(dim=(3, 32, 32), num_res_blocks=2, num_channels=num_channel, channel_mult=[1, 2, 2, 2], num_heads=4,
-                            num_head_channels=64, attention_resolutions="16", dropout=0.1, precision=precision).to(device)
+def build_model(num_channel=128, device="cuda:0", precision=None, num_classes=None):
+    """cifar10/compute_fid.py:39-48.  num_classes: the class-conditional form of the same net (for --guidance_scale)."""
+    kw = dict(dim=(3, 32, 32), num_res_blocks=2, num_channels=num_channel, channel_mult=[1, 2, 2, 2], num_heads=4, num_head_channels=64,
+              attention_resolutions="16", dropout=0.1, precision=precision)
+    if num_classes:
+        return ClassCondUNetModelWrapper(class_cond=True, num_classes=int(num_classes), **kw).to(device)
+    return UNetModelWrapper(**kw).to(device)
 
 
 def load_checkpoint(net, path):
@@ -43,8 +46,11 @@ def draw_x0_shard(batch, seed, call_idx, device, shape=(3, 32, 32)):
     return torch.randn(batch, *shape, device=device, generator=g)[lo:hi].contiguous()
 
 
-def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integration_method="euler", device="cuda:0", tol=1e-5, seed=0):
-    """integration_method: "euler", "dopri5", or a fixed-step Runge-Kutta name ("midpoint", "heun2", "rk4", "rk4_38": mi355.ode.TABLEAUS).
+def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integration_method="euler", device="cuda:0", tol=1e-5, seed=0,
+                   guidance_scale=None, null_label=None):
+    """guidance_scale (None: unguided, the reference's call): classifier-free guidance on a class-conditional net; each image's label is drawn
+    uniformly from the classes other than null_label (default: the last class) by the batch's seeded generator.
+    integration_method: "euler", "dopri5", or a fixed-step Runge-Kutta name ("midpoint", "heun2", "rk4", "rk4_38": mi355.ode.TABLEAUS).
     The fixed-step methods integrate over linspace(0, 1, integration_steps + 1) like the Euler branch - a build-defined reading: the
     reference forwards any name but "euler" to odeint with the two-point grid linspace(0, 1, 2), which for a fixed-grid method is ONE
     step over [0, 1]."""
@@ -54,23 +60,41 @@ def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integrat
         raise NotImplementedError(f"--integration_method must be euler, dopri5 or one of {rk}")
     device = torch.device(device)
     calls = [0]
+    guide = {}
+    if guidance_scale is not None:
+        K = getattr(new_net, "num_classes", None)
+        if not K:
+            raise ValueError("--guidance_scale needs a class-conditional model (num_classes)")
+        nl = K - 1 if null_label is None else int(null_label)
+        if not 0 <= nl < K:
+            raise ValueError(f"--null_label must be a class index in [0, {K})")
+        guide = dict(guidance_scale=float(guidance_scale), null_label=nl)
+
+    def draw_labels(B, call_idx):
+        lo, hi = mdist.shard_range(B)
+        g = torch.Generator(device="cpu")
+        g.manual_seed(int(seed) + int(call_idx) + (1 << 20))
+        y = torch.randint(0, new_net.num_classes - 1, (B,), generator=g)
+        return (y + (y >= guide["null_label"]).long())[lo:hi].to(device)
 
     def gen_1_img(unused_latent):
         with torch.no_grad():
             B = int(batch_size_fid)
             x = draw_x0_shard(B, seed, calls[0], device)
+            kw = dict(guide, y=draw_labels(B, calls[0])) if guide else {}
             calls[0] += 1
             if integration_method == "euler":
                 t_span = torch.linspace(0, 1, integration_steps + 1).tolist()
-                _, _, img = new_net.engine(device).cfm_euler(x, t_span, want_u8=True)  # (traj*127.5+128).clip(0,255).to(uint8)
+                _, _, img = new_net.engine(device).cfm_euler(x, t_span, want_u8=True, **kw)  # (traj*127.5+128).clip(0,255).to(uint8)
             elif integration_method in rk:
                 t_span = torch.linspace(0, 1, integration_steps + 1).tolist()
-                _, _, img = new_net.engine(device).cfm_rk(x, t_span, integration_method, want_u8=True)
+                _, _, img = new_net.engine(device).cfm_rk(x, t_span, integration_method, want_u8=True, **kw)
             else:  # odeint(new_net, x, linspace(0,1,2), rtol=tol, atol=tol, method="dopri5")  (cifar10/compute_fid.py:80-85)
                 from mi355.ode import odeint_dopri5
                 from mi355.ops import default_ops
 
-                traj, _ = odeint_dopri5(lambda t, y: new_net(torch.tensor(float(t), device=device), y), x, 0.0, 1.0, tol, tol)
+                # guided: model(t, x, y, guidance_scale=, null_label=), the 2B forward plus cfg_stage per evaluation
+                traj, _ = odeint_dopri5(lambda t, xt: new_net(torch.tensor(float(t), device=device), xt, **kw), x, 0.0, 1.0, tol, tol)
                 img = default_ops.quantize_u8(traj.contiguous())
             return mdist.all_gather_batch(img, B)
 
@@ -89,14 +113,17 @@ def main(argv=None):
     ap.add_argument("--num_gen", type=int, default=50000)
     ap.add_argument("--batch_size_fid", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=0, help="x0 stream seed, shared by all ranks (each takes its batch slice)")
+    ap.add_argument("--guidance_scale", type=float, default=None, help="classifier-free guidance scale w (needs --num_classes); unset: unguided")
+    ap.add_argument("--null_label", type=int, default=None, help="the class index trained as the null token (default: the last class)")
+    ap.add_argument("--num_classes", type=int, default=None, help="build the class-conditional net (K + 1 classes with a null token); the checkpoint must be that net's")
     a = ap.parse_args(argv)
     rank, world, local = mdist.init_from_env()
     device = f"cuda:{local}"
-    net = build_model(a.num_channel, device)
+    net = build_model(a.num_channel, device, num_classes=a.num_classes)
     path = f"{a.input_dir}/{a.model}/{a.model}_cifar10_weights_step_{a.step}.pt"
     print("path: ", path)
     load_checkpoint(net, path)
-    gen = make_gen_1_img(net, a.batch_size_fid, a.integration_steps, a.integration_method, device, a.tol, a.seed)
+    gen = make_gen_1_img(net, a.batch_size_fid, a.integration_steps, a.integration_method, device, a.tol, a.seed, a.guidance_scale, a.null_label)
     try:
         from cleanfid import fid
     except ImportError as e:

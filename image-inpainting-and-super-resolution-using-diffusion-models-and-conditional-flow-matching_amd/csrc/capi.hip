@@ -507,6 +507,209 @@ int mi355_ddpm_sample(mi355_unet* net, float* x, int channels, const float* cond
   return clip_launch(x, -1.f, 1.f, n, s);
 }
 
+// ---- classifier-free guidance: every evaluation is ONE forward at batch 2B (images 0..B-1 conditional, B..2B-1 unconditional) -------------------
+namespace {
+// the buffers behind the 2B network workspace: duplicated state, condition | none, labels | null, then the CFM sampler's stage buffers
+struct CfgTail { float* x2; float* cond2; int32_t* labels2; char* rest; };
+inline size_t cfg_cond_channels(const mi355_unet* net) { return (size_t)(net->cfg.in_channels > net->cfg.out_channels ? net->cfg.in_channels - net->cfg.out_channels : 0); }
+inline size_t cfg_state2_bytes(const mi355_unet* net, int batch) {
+  return al256((size_t)2 * batch * net->cfg.out_channels * net->cfg.image_size * net->cfg.image_size * 4);
+}
+inline size_t cfg_cond2_bytes(const mi355_unet* net, int batch) {
+  const size_t cc = cfg_cond_channels(net);
+  return cc ? al256((size_t)2 * batch * cc * net->cfg.image_size * net->cfg.image_size * 4) : 0;
+}
+inline size_t cfg_labels2_bytes(const mi355_unet* net, int batch) { return net->num_classes > 0 ? al256((size_t)2 * batch * 4) : 0; }
+inline size_t cfg_tail_bytes(const mi355_unet* net, int batch) { return cfg_state2_bytes(net, batch) + cfg_cond2_bytes(net, batch) + cfg_labels2_bytes(net, batch); }
+inline CfgTail cfg_tail(const mi355_unet* net, int batch, char* p) {
+  CfgTail t;
+  t.x2 = reinterpret_cast<float*>(p); p += cfg_state2_bytes(net, batch);
+  t.cond2 = reinterpret_cast<float*>(p); p += cfg_cond2_bytes(net, batch);
+  t.labels2 = reinterpret_cast<int32_t*>(p); p += cfg_labels2_bytes(net, batch);
+  t.rest = p;
+  return t;
+}
+// x2 = x | x, cond2 = cond | none_value, labels2 = labels | null_label: built once per call
+int cfg_fill_tail(const CfgTail& t, const float* x, int64_t n, const float* cond, int64_t nc, float none_value, const int32_t* labels, int null_label,
+                  int batch, hipStream_t s) {
+  MI355_CHECK_HIP(hipMemcpyAsync(t.x2, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  MI355_CHECK_HIP(hipMemcpyAsync(t.x2 + n, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (cond) {
+    MI355_CHECK_HIP(hipMemcpyAsync(t.cond2, cond, (size_t)nc * 4, hipMemcpyDeviceToDevice, s));
+    if (int rc = fill_launch(t.cond2 + nc, none_value, nc, s)) return rc;
+  }
+  if (labels) {
+    MI355_CHECK_HIP(hipMemcpyAsync(t.labels2, labels, (size_t)batch * 4, hipMemcpyDeviceToDevice, s));
+    MI355_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(t.labels2 + batch), null_label, (size_t)batch, s));
+  }
+  return 0;
+}
+}  // namespace
+
+int64_t mi355_cfg_workspace_bytes(const mi355_unet* net, int batch, int stages) {
+  if (!net || batch <= 0 || stages < 1 || stages > 4) { mi355_set_error("cfg_workspace_bytes: bad argument (1 <= stages <= 4)"); return -1; }
+  return (int64_t)al256((size_t)mi355_unet_workspace_bytes(net, 2 * batch)) + (int64_t)cfg_tail_bytes(net, batch) +
+         (int64_t)(stages + (stages > 1 ? 1 : 0)) * (int64_t)cfg_state2_bytes(net, batch);
+}
+
+int64_t mi355_ddpm_cfg_workspace_bytes(const mi355_unet* net, int batch) {
+  if (!net || batch <= 0) { mi355_set_error("ddpm_cfg_workspace_bytes: bad argument"); return -1; }
+  return (int64_t)al256((size_t)mi355_unet_workspace_bytes(net, 2 * batch)) + (int64_t)cfg_tail_bytes(net, batch);
+}
+
+int mi355_cfm_cfg_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, float none_value, const int32_t* labels,
+                         int null_label, float w, const float* w_dev, const float* t_span_host, int n_t, int stages, const float* a_host,
+                         const float* b_host, const float* c_host, float* traj, uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes,
+                         void* stream) {
+  MI355_REQUIRE(net && x && t_span_host && n_t >= 1 && batch > 0, -1, "cfm_cfg_sample: bad argument");
+  MI355_REQUIRE(stages >= 1 && stages <= 4, -1, "cfm_cfg_sample: the tableau must have 1 to 4 stages");
+  MI355_REQUIRE(a_host && b_host && c_host, -1, "cfm_cfg_sample: null tableau");
+  bool any_b = false;
+  for (int j = 0; j < stages; ++j) any_b = any_b || b_host[j] != 0.f;
+  MI355_REQUIRE(any_b, -1, "cfm_cfg_sample: the tableau's weights b are all zero");
+  MI355_REQUIRE(cond || labels, -1, "cfm_cfg_sample: nothing to guide (neither a condition nor class labels)");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_cfg_sample: class labels given to a net built without num_classes");
+  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, "cfm_cfg_sample: null_label must be a class index in [0, num_classes)");
+  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_cfg_sample: the vector field must have the state's channel count");
+  MI355_REQUIRE(!cond || (cond_channels > 0 && (size_t)cond_channels == cfg_cond_channels(net)), -2,
+                "cfm_cfg_sample: the condition must have in_channels - out_channels channels");
+  MI355_REQUIRE(workspace_bytes >= mi355_cfg_workspace_bytes(net, batch, stages), -2, "cfm_cfg_sample: workspace too small");
+  const int B2 = 2 * batch;
+  const int64_t base = (int64_t)al256((size_t)mi355_unet_workspace_bytes(net, B2));
+  Scratch sc;
+  if (int rc = carve(net, B2, workspace, base, sc)) return rc;
+  hipStream_t s = S(stream);
+  const int64_t hw = (int64_t)net->cfg.image_size * net->cfg.image_size;
+  const int64_t per = (int64_t)x_channels * hw, n = (int64_t)batch * per, nc = (int64_t)batch * cond_channels * hw;
+  const CfgTail tl = cfg_tail(net, batch, reinterpret_cast<char*>(workspace) + base);
+  float* kbuf[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < stages; ++i) kbuf[i] = reinterpret_cast<float*>(tl.rest + (size_t)i * cfg_state2_bytes(net, batch));
+  float* ystage = reinterpret_cast<float*>(tl.rest + (size_t)stages * cfg_state2_bytes(net, batch));   // (stages > 1 only)
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  const int n_steps = n_t - 1;
+  if (n_steps == 0) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
+  if (int rc = cfg_fill_tail(tl, x, n, cond, nc, none_value, labels, null_label, batch, s)) return rc;
+  std::vector<float> te((size_t)n_steps * stages);
+  for (int k = 0; k < n_steps; ++k)
+    for (int i = 0; i < stages; ++i) te[(size_t)k * stages + i] = rk_stage_time(t_span_host[k], t_span_host[k + 1], c_host[i]);
+  // rows = n_steps * stages * K <= EMB_TABLE_STEPS (make_emb_table applies it), as in mi355_cfm_rk_sample
+  const float* emb_table = nullptr;
+  if ((int64_t)n_steps * stages <= EMB_TABLE_STEPS) {
+    if (int rc = make_emb_table(net, sc, te.data(), n_steps * stages, labels != nullptr, s, &emb_table)) return rc;
+    if (emb_table) MI355_CHECK_HIP(hipStreamSynchronize(s));   // `te` is a temporary host buffer: once per call
+  }
+  UnetRun run = uniform_t_run();
+  run.labels = labels ? tl.labels2 : nullptr;
+  const float* cond2 = cond ? tl.cond2 : nullptr;
+  const size_t block = (size_t)(labels ? net->num_classes : 1) * net->emb_total;
+  int64_t step_launches = 0;
+  int rc = 0;
+  for (int k = 0; k < n_steps; ++k) {
+    const float dt = t_span_host[k + 1] - t_span_host[k];
+    step_launches = 0;
+    for (int i = 0; i < stages; ++i) {
+      const float* kp[4]; float cf[4]; int nk = 0;
+      for (int j = 0; j < i; ++j) {
+        const float a = a_host[(size_t)i * stages + j];
+        if (a != 0.f) { kp[nk] = kbuf[j]; cf[nk] = dt * a; ++nk; }
+      }
+      const float* yin = tl.x2;
+      if (nk) {   // the stage state, both halves
+        if ((rc = cfg_stage_launch(ystage, tl.x2, kp, cf, nk, n, w, w_dev, per, 1, nullptr, nullptr, s))) return rc;
+        yin = ystage; ++step_launches;
+      }
+      const size_t e = (size_t)k * stages + i;
+      if (emb_table) run.emb_row = emb_table + e * block;
+      else { if ((rc = fill_launch(sc.t, te[e], B2, s))) return rc; ++step_launches; }
+      if ((rc = unet_forward(net, yin, x_channels, cond2, cond_channels, sc.t, kbuf[i], B2, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+      step_launches += net->last_launches;
+    }
+    const float* kp[4]; float cf[4]; int nk = 0;
+    for (int j = 0; j < stages; ++j)
+      if (b_host[j] != 0.f) { kp[nk] = kbuf[j]; cf[nk] = dt * b_host[j]; ++nk; }
+    // the update: both halves of x2 in place, the trajectory slot and (last step) the image bytes from the same launch
+    if ((rc = cfg_stage_launch(tl.x2, tl.x2, kp, cf, nk, n, w, w_dev, per, 1, traj ? traj + (size_t)(k + 1) * n : nullptr,
+                               k + 1 == n_steps ? u8_out : nullptr, s))) return rc;
+    ++step_launches;
+  }
+  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  net->last_launches = step_launches;   // mi355_unet_get_stats: every launch of the last step (evaluations and stage launches)
+  return 0;
+}
+
+int mi355_ddpm_cfg_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w, const float* w_dev,
+                          const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && x && tb && opt && batch > 0, -1, "ddpm_cfg_sample: bad argument");
+  const int mode = opt->mode, Ns = tb->Ns;
+  MI355_REQUIRE(mode == MI355_DDPM_AMORTIZED || mode == MI355_DDIM, -1,
+                "ddpm_cfg_sample: guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement modes are refused)");
+  MI355_REQUIRE(cond || labels, -1, "ddpm_cfg_sample: nothing to guide (neither a condition nor class labels)");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "ddpm_cfg_sample: class labels given to a net built without num_classes");
+  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, "ddpm_cfg_sample: null_label must be a class index in [0, num_classes)");
+  MI355_REQUIRE(channels == net->cfg.out_channels, -2, "ddpm_cfg_sample: eps model must output the state's channel count");
+  MI355_REQUIRE(net->cfg.in_channels == 2 * channels && cond, -2, "ddpm_cfg_sample: needs a 2C-input net and a condition");
+  MI355_REQUIRE(workspace_bytes >= mi355_ddpm_cfg_workspace_bytes(net, batch), -2, "ddpm_cfg_sample: workspace too small");
+  const int B2 = 2 * batch;
+  const int64_t base = (int64_t)al256((size_t)mi355_unet_workspace_bytes(net, B2));
+  Scratch sc;
+  if (int rc = carve(net, B2, workspace, base, sc)) return rc;
+  hipStream_t s = S(stream);
+  const int64_t per = (int64_t)channels * net->cfg.image_size * net->cfg.image_size, n = (int64_t)batch * per;
+  const int64_t n_al = (n + 3) / 4 * 4;
+  const CfgTail tl = cfg_tail(net, batch, reinterpret_cast<char*>(workspace) + base);
+  int rc;
+  const float* emb_table = nullptr;   // row i (block of num_classes rows with labels) = step i (time i / Ns)
+  if (Ns <= EMB_TABLE_STEPS) {
+    std::vector<float> th((size_t)Ns);
+    for (int i = 0; i < Ns; ++i) th[i] = (float)i / (float)Ns;
+    if ((rc = make_emb_table(net, sc, th.data(), Ns, labels != nullptr, s, &emb_table))) return rc;
+    MI355_CHECK_HIP(hipStreamSynchronize(s));   // `th` is a temporary host buffer (once per call)
+  }
+  if ((rc = cfg_fill_tail(tl, x, n, cond, n, opt->none_value, labels, null_label, batch, s))) return rc;
+  UnetRun run = uniform_t_run(), run_corr = uniform_t_run();
+  run.labels = labels ? tl.labels2 : nullptr;
+  run_corr.labels = labels ? tl.labels2 + batch : nullptr;   // the corrector sees no condition (sampling.py:116): none_like and the null label
+  const size_t block = (size_t)(labels ? net->num_classes : 1) * net->emb_total;
+  int64_t draw = 0;
+  auto next_noise = [&](const float*& zptr, int& philox, uint64_t& off) -> int {
+    if (noise) {
+      MI355_REQUIRE(draw < n_noise_draws, -2, "ddpm_cfg_sample: injected noise exhausted");
+      zptr = noise + (size_t)draw * n; philox = 0; off = 0;
+    } else { zptr = nullptr; philox = 1; off = (uint64_t)draw * (uint64_t)n_al; }
+    ++draw;
+    return 0;
+  };
+  for (int i = Ns - 1; i >= 0; --i) {
+    const float tval = (float)i / (float)Ns;
+    if (emb_table) run.emb_row = run_corr.emb_row = emb_table + (size_t)i * block;
+    else if ((rc = fill_launch(sc.t, tval, B2, s))) return rc;
+    if ((rc = unet_forward(net, tl.x2, channels, tl.cond2, channels, sc.t, sc.v, B2, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    if (mode == MI355_DDIM) {
+      if ((rc = ddim_cfg_step_launch(tl.x2, sc.v, w, w_dev, per, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i],
+                                     tb->alphas_cumprod_prev[i], n, s))) return rc;
+      continue;
+    }
+    const float* z = nullptr; int ph = 0; uint64_t off = 0;
+    if (i > 0 && (rc = next_noise(z, ph, off))) return rc;
+    const float sigma = expf(0.5f * tb->posterior_log_variance_clipped[i]);
+    if ((rc = ddpm_cfg_step_launch(tl.x2, sc.v, z, w, w_dev, per, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i],
+                                   tb->posterior_mean_coef1[i], tb->posterior_mean_coef2[i], sigma, ph, opt->seed, off, n, s))) return rc;
+    for (int c = 0; c < opt->n_corrector; ++c) {   // at batch B on the first half, as mi355_ddpm_sample runs them
+      if ((rc = unet_forward(net, tl.x2, channels, tl.cond2 + n, channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run_corr))) return rc;
+      const float* z2 = nullptr; int ph2 = 0; uint64_t off2 = 0;
+      if ((rc = next_noise(z2, ph2, off2))) return rc;
+      const float dt = (opt->tmax - opt->tmin) / (float)Ns;
+      if ((rc = corrector_step_launch(tl.x2, sc.v, z2, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i],
+                                      tb->recip_sqrt_m1_alphas_cumprod[i], dt, opt->delta, ph2, opt->seed, off2, n, s))) return rc;
+    }
+    if (opt->n_corrector > 0) MI355_CHECK_HIP(hipMemcpyAsync(tl.x2 + n, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));   // refresh the second half
+  }
+  if ((rc = clip_launch(tl.x2, -1.f, 1.f, n, s))) return rc;
+  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
 // SF2M (torchcfm notebooks' torchsde.sdeint of drift = model + score_model, g = sigma): per step two forwards, each net on its own workspace
 // (its own embedding table: label_emb differs between the nets), then the Euler-Maruyama launch, which also writes the step's output time.
 int mi355_sf2m_euler_sample(mi355_unet* drift, mi355_unet* score, float* x, int channels, const int32_t* labels, const float* t_grid_host,
@@ -646,6 +849,18 @@ int mi355_rk_combine(float* out, const float* y0, const float* k0, const float* 
 int mi355_rk_stage(float* out, const float* y0, const float* const k[4], const float* coeff_host, int nk, int64_t n, float* copy_out,
                    uint8_t* u8_out, void* stream) {
   return rk_stage_launch(out, y0, k, coeff_host, nk, n, copy_out, u8_out, S(stream));
+}
+int mi355_cfg_stage(float* out, const float* y0, const float* const k[4], const float* coeff_host, int nk, int64_t n, float w, const float* w_dev,
+                    int64_t elems_per_image, int dup, float* copy_out, uint8_t* u8_out, void* stream) {
+  return cfg_stage_launch(out, y0, k, coeff_host, nk, n, w, w_dev, elems_per_image, dup, copy_out, u8_out, S(stream));
+}
+int mi355_ddpm_cfg_step(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1,
+                        float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
+  return ddpm_cfg_step_launch(x, eps, z, w, w_dev, elems_per_image, c_recip, c_recipm1, coef1, coef2, sigma, use_philox, seed, offset, n, S(stream));
+}
+int mi355_ddim_cfg_step(float* x, const float* eps, float w, const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1, float acp_prev,
+                        int64_t n, void* stream) {
+  return ddim_cfg_step_launch(x, eps, w, w_dev, elems_per_image, c_recip, c_recipm1, acp_prev, n, S(stream));
 }
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream) {

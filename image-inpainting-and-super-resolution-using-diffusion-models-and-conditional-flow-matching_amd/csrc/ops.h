@@ -258,6 +258,11 @@ int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, 
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,
                           float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int ddim_step_launch(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s);
+// classifier-free-guided ddpm / ddim steps: eps [2n] = conditional | unconditional evaluation, x [2n] the duplicated state (both halves written)
+int ddpm_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
+                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
+int ddim_cfg_step_launch(float* x, const float* eps, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float acp_prev, int64_t n,
+                         hipStream_t s);
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb,
                         int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int clip_launch(float* x, float lo, float hi, int64_t n, hipStream_t s);
@@ -282,6 +287,10 @@ int rk_combine_launch(float* out, const float* y0, const float* const* k, const 
 // quantised as quantize_u8_launch does, to u8_out (either may be null)
 int rk_stage_launch(float* out, const float* y0, const float* const* k, const float* c, int nk, int64_t n, float* copy_out, uint8_t* u8_out,
                     hipStream_t s);
+// rk_stage over guided derivatives: k[j] [2n] = conditional | unconditional evaluation, g_j = ku + w * (kc - ku) (w_dev: one scale per image of
+// `per` elements), out = y0 + sum_j c[j] * g_j (y0 may be null); dup: also to out + n
+int cfg_stage_launch(float* out, const float* y0, const float* const* k, const float* c, int nk, int64_t n, float w, const float* w_dev, int64_t per,
+                     int dup, float* copy_out, uint8_t* u8_out, hipStream_t s);
 int rk_sqnorm_launch(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                      hipStream_t s);
 int rk_interp_launch(float* out, const float* y0, const float* y1, const float* ym, const float* f0, const float* f1, float dt, float x,

@@ -186,6 +186,73 @@ int ddim_step_launch(float* x, const float* eps, float c_recip, float c_recipm1,
   });
 }
 
+// Classifier-free-guided forms of the two steps above: eps holds 2n values, the conditional evaluation in [0, n) and the unconditional one in
+// [n, 2n) (one network call at twice the batch); eps_g = eps_u + w * (eps_c - eps_u) with the difference, the product and the sum each rounded,
+// then the arithmetic of ddpm_step_launch / ddim_step_launch on eps_g.  x holds the duplicated state [2n]: the first half is read, the result goes
+// to both halves.  w_dev (optional): one scale per image of `per` elements.  Philox: indexed by the element of the n-element state.
+namespace {
+__device__ inline void cfg_eps4(const float* eps, int64_t n, float w, const float* w_dev, int64_t per, int64_t i, int cnt, float (&ev)[4]) {
+  float ec[4], eu[4], wv[4] = {w, w, w, w};
+  ld4(eps, i, cnt, ec); ld4(eps + n, i, cnt, eu);
+  if (w_dev) {   // a group of four may straddle images when per % 4 != 0
+    int64_t img = i / per, r = i - img * per;
+    for (int l = 0; l < cnt; ++l) {
+      while (r >= per) { r -= per; ++img; }
+      wv[l] = w_dev[img];
+      ++r;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float d = ec[j] - eu[j];
+    const float p = wv[j] * d;
+    ev[j] = eu[j] + p;
+  }
+}
+}  // namespace
+
+int ddpm_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
+                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "ddpm_cfg_step: the Philox offset must be a multiple of 4");
+  MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "ddpm_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
+  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddpm_cfg_step: null argument");
+  const uint64_t off4 = offset / 4;
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
+    float xv[4], ev[4], zz[4];
+    ld4(x, i, cnt, xv);
+    cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
+    noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
+      const float mean = coef1 * x0 + coef2 * xv[j];
+      xv[j] = mean + sigma * zz[j];
+    }
+    st4(x, i, cnt, xv);
+    st4(x + n, i, cnt, xv);
+  });
+}
+
+int ddim_cfg_step_launch(float* x, const float* eps, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float acp_prev, int64_t n,
+                         hipStream_t s) {
+  MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "ddim_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
+  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_cfg_step: null argument");
+  const float sa = sqrtf(acp_prev), sb = sqrtf(1.0f - acp_prev);
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
+    float xv[4], ev[4];
+    ld4(x, i, cnt, xv);
+    cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
+      const float e2 = (c_recip * xv[j] - x0) / c_recipm1;
+      xv[j] = sa * x0 + sb * e2;
+    }
+    st4(x, i, cnt, xv);
+    st4(x + n, i, cnt, xv);
+  });
+}
+
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb, int use_philox,
                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
   MI355_REQUIRE(offset % 4 == 0, -1, "replace_mask: the Philox offset must be a multiple of 4");

@@ -39,6 +39,13 @@ class Amortized(Conditioning):
     KEY, PARAMS = "amortized", ("p_cond", "n_corrector", "delta")
 
 
+class ClassifierFreeGuidance(Amortized):
+    """Amortized sampling with classifier-free guidance of the predictor: eps = eps_u + guidance_scale * (eps_c - eps_u), eps_u the net fed
+    likelihood.none_like (what p_cond's condition dropout trains, loss_functions.py:47-50).  No reference counterpart: the reference trains
+    for it and never samples with it."""
+    KEY, PARAMS = "classifier_free_guidance", Amortized.PARAMS + ("guidance_scale",)
+
+
 class ReconstructionGuidance(Conditioning):
     """Gradient guidance through the x0 predictor (sampling.py:136-206); needs the U-Net backward: not built yet."""
     KEY, PARAMS = "reconstruction_guidance", ("gamma", "start_fraction", "update_rule", "n_corrector", "delta")
@@ -49,7 +56,7 @@ class Replacement(Conditioning):
     KEY, PARAMS = "replacement", ("delta", "start_fraction", "noise", "n_corrector")
 
 
-_REGISTRY: Dict[str, Type[Conditioning]] = {c.KEY: c for c in (Amortized, ReconstructionGuidance, Replacement)}
+_REGISTRY: Dict[str, Type[Conditioning]] = {c.KEY: c for c in (Amortized, ClassifierFreeGuidance, ReconstructionGuidance, Replacement)}
 
 
 def get_conditioning(type_: str) -> Type[Conditioning]:

@@ -28,7 +28,7 @@ import torch
 from mi355 import _lib
 from mi355.ops import default_ops
 
-from .conditioning import Amortized, Conditioning, ReconstructionGuidance, Replacement
+from .conditioning import Amortized, ClassifierFreeGuidance, Conditioning, ReconstructionGuidance, Replacement
 from .likelihoods import Likelihood
 from .sde_diffusion import DDPM
 
@@ -167,8 +167,29 @@ def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replac
     return process_x0(xi)
 
 
+def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corrector=0, delta=0.1, ddim=False):
+    """The guided host loop for any eps_model callable: two calls per predictor step (condition, none_like), cfg_combine, the step kernel;
+    correctors as in _run_generic (the net sees none_like)."""
+    T = _tables(ddpm)
+    xi = xT.detach().clone().float().contiguous()
+    noise = _Noise(xi)
+    for i in reversed(range(ddpm.Ns)):
+        ec = eps_model(_net_in(xi, cond, True), _times(xi, i)).float()
+        eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
+        eps = _ops.cfg_combine(torch.cat((ec, eu)).contiguous(), guidance_scale)
+        if ddim:
+            _ops.ddim_step_(xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
+                            float(T["alphas_cumprod_prev"][i]))
+            continue
+        _predictor(eps, xi, i, T, noise)
+        for _ in range(n_corrector):
+            eps = eps_model(_net_in(xi, none, True), _times(xi, i))
+            _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise)
+    return process_x0(xi)
+
+
 def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_fraction=1.0, noise_condition=True,
-              pad_value=-2.0, none_value=-2.0):
+              pad_value=-2.0, none_value=-2.0, guidance_scale=None):
     global _draw_counter
     xi = xT.detach().clone().float().contiguous()
     noise = None
@@ -180,7 +201,7 @@ def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_f
         _draw_counter += 1
     engine.ddpm_sample(xi, _tables(ddpm), mode=mode, cond=cond, noise=noise, n_corrector=n_corrector, delta=float(delta),
                        tmin=ddpm.tmin, tmax=ddpm.tmax, start_fraction=float(start_fraction), noise_condition=bool(noise_condition),
-                       pad_value=float(pad_value), none_value=float(none_value), seed=seed)
+                       pad_value=float(pad_value), none_value=float(none_value), seed=seed, guidance_scale=guidance_scale)
     return xi
 
 
@@ -204,6 +225,8 @@ def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Condition
 # Conditional sampling ---------------------------------------------------------------------------------
 
 def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood):
+    if isinstance(conditioning, ClassifierFreeGuidance):   # (an Amortized: before it)
+        return _cfg_sample_fn(eps_model, ddpm, conditioning, likelihood)
     if isinstance(conditioning, Amortized):
         return _amortized_sample_fn(eps_model, ddpm, conditioning, likelihood)
     if isinstance(conditioning, Replacement):
@@ -226,6 +249,25 @@ def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood):
                              delta=conditioning.delta, none_value=_none_value(likelihood, xT))
         return _run_generic(eps_model, ddpm, xT, amortized=True, cond_pred=condition, cond_corr=likelihood.none_like(xT),
                             n_corrector=conditioning.n_corrector, delta=conditioning.delta)
+
+    return sample
+
+
+def _cfg_sample_fn(eps_model, ddpm, conditioning: ClassifierFreeGuidance, likelihood):
+    """Amortized sampling with the predictor's eps guided: eps_u + guidance_scale * (eps_c - eps_u), eps_u from likelihood.none_like.
+    Fast path: the whole loop in mi355_ddpm_cfg_sample (one forward at twice the batch per predictor step); generic path: two eps_model
+    calls per predictor step and the cfg_combine kernel.  The corrector is the amortized sampler's."""
+
+    @torch.no_grad()
+    def sample(xT, condition):
+        condition = condition.to(xT.device).float().contiguous()
+        w = float(conditioning.guidance_scale)
+        engine = _fast_engine(eps_model, ddpm, xT)
+        if engine is not None:
+            return _run_fast(engine, ddpm, xT, _lib.DDPM_AMORTIZED, condition, n_corrector=conditioning.n_corrector,
+                             delta=conditioning.delta, none_value=_none_value(likelihood, xT), guidance_scale=w)
+        return _run_generic_cfg(eps_model, ddpm, xT, cond=condition, none=likelihood.none_like(xT), guidance_scale=w,
+                                n_corrector=conditioning.n_corrector, delta=conditioning.delta)
 
     return sample
 
@@ -312,9 +354,10 @@ def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihoo
     return sample
 
 
-def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Likelihood] = None):
+def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Likelihood] = None, guidance_scale=None):
     """BUILD-DEFINED EXTENSION (no reference counterpart; BASELINE.json configs 3/5 name DDIM): deterministic
-    DDIM(eta=0) on the same tables with the reference's clipped x0_hat.  sample(xT, condition=None)."""
+    DDIM(eta=0) on the same tables with the reference's clipped x0_hat.  sample(xT, condition=None).
+    guidance_scale (None: unguided): classifier-free guidance of eps against the none_like condition; needs a condition."""
 
     @torch.no_grad()
     def sample(xT, condition=None):
@@ -322,9 +365,14 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
         engine = _fast_engine(eps_model, ddpm, xT)
         if condition is not None:
             condition = condition.to(xT.device).float().contiguous()
+        if guidance_scale is not None and condition is None:
+            raise ValueError("guidance_scale needs a condition to guide towards")
         if engine is not None:
             nv = _none_value(likelihood, xT) if likelihood is not None else 0.0
-            return _run_fast(engine, ddpm, xT, _lib.DDIM, condition, none_value=nv)
+            return _run_fast(engine, ddpm, xT, _lib.DDIM, condition, none_value=nv, guidance_scale=guidance_scale)
+        if guidance_scale is not None:
+            none = likelihood.none_like(xT) if likelihood is not None else torch.zeros_like(condition)
+            return _run_generic_cfg(eps_model, ddpm, xT, cond=condition, none=none, guidance_scale=guidance_scale, ddim=True)
         xi = xT.detach().clone().float().contiguous()
         for i in reversed(range(ddpm.Ns)):
             eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i))

@@ -127,6 +127,11 @@ SIGNATURES = {
     "mi355_cfm_euler_sample_labels": (_I, [_VP, _VP, _I, _VP, _I, _I, _VP, _FP, _I, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_cfm_rk_workspace_bytes": (_I64, [_VP, _I, _I]),
     "mi355_cfm_rk_sample": (_I, [_VP, _VP, _I, _VP, _I, _VP, _FP, _I, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
+    "mi355_cfg_workspace_bytes": (_I64, [_VP, _I, _I]),
+    "mi355_cfm_cfg_sample": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _I, _F, _VP, _FP, _I, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
+    "mi355_ddpm_cfg_workspace_bytes": (_I64, [_VP, _I]),
+    "mi355_ddpm_cfg_sample": (_I, [_VP, _VP, _I, _VP, _VP, _I, _F, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), _VP, _I64, _I, _VP, _I64,
+                                   _VP]),
     "mi355_sf2m_euler_sample": (_I, [_VP, _VP, _VP, _I, _VP, _FP, _I, _F, _I, _VP, _U64, C.POINTER(C.c_int32), _FP, _I, _VP, _I, _VP, _I64,
                                      _VP, _I64, _VP]),
     "mi355_ddpm_sample": (_I, [_VP, _VP, _I, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), _VP, _I64, _I, _VP, _I64, _VP]),
@@ -151,6 +156,9 @@ SIGNATURES = {
     "mi355_randn": (_I, [_VP, _U64, _U64, _I64, _VP]),
     "mi355_rk_combine": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _FP, _I, _I64, _VP]),
     "mi355_rk_stage": (_I, [_VP, _VP, C.POINTER(_VP), _FP, _I, _I64, _VP, _VP, _VP]),
+    "mi355_cfg_stage": (_I, [_VP, _VP, C.POINTER(_VP), _FP, _I, _I64, _F, _VP, _I64, _I, _VP, _VP, _VP]),
+    "mi355_ddpm_cfg_step": (_I, [_VP, _VP, _VP, _F, _VP, _I64, _F, _F, _F, _F, _F, _I, _U64, _U64, _I64, _VP]),
+    "mi355_ddim_cfg_step": (_I, [_VP, _VP, _F, _VP, _I64, _F, _F, _F, _I64, _VP]),
     "mi355_rk_sqnorm": (_I, [_VP, _VP, _VP, _VP, _F, _F, _I64, _VP, _VP]),
     "mi355_rk_interp": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _F, _F, _I64, _VP]),
     "mi355_op_workspace_bytes": (_I64, [_I, _I, _I]),

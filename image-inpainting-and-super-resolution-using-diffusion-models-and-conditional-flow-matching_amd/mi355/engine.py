@@ -59,7 +59,7 @@ class UNetEngine:
                                            self._stream(), C.byref(handle)), "mi355_unet_create")
         self.handle = handle
         self._ws: Optional[torch.Tensor] = None
-        self._rk_bytes: Dict[Tuple[int, int], int] = {}   # mi355_cfm_rk_workspace_bytes per (batch, stages)
+        self._ws_bytes: Dict[tuple, int] = {}   # sizes of the samplers' workspaces with tail buffers, per (size function, its arguments)
         self._fwd_state = None   # (batch, workspace pointer) of the last forward(): what vjp() differentiates
         self.in_channels = self.cfg.in_channels
         self.out_channels = self.cfg.out_channels
@@ -125,10 +125,76 @@ class UNetEngine:
             raise ValueError(f"x ({Cx}) + condition ({Cc}) channels != in_channels ({self.in_channels})")
         return B, Cx, Cc
 
-    def forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None):
+    # ---- classifier-free guidance: v = v_u + w (v_c - v_u), both halves from one evaluation at batch 2B ----
+    def _guidance_args(self, guidance_scale, B: int, y, cond, null_label):
+        """Host checks of a guided call -> (w float, per-image scale tensor or None, null label int).  guidance_scale: a float or a [B] tensor."""
+        if cond is None and y is None:
+            raise ValueError("guidance_scale needs something to guide: a condition (cond) and / or class labels (y)")
+        nl = 0
+        if y is not None:
+            if not self.num_classes:
+                raise ValueError("y (class labels) given to a model built without num_classes")
+            nl = self.num_classes - 1 if null_label is None else int(null_label)   # the usual recipe: K + 1 classes, the last one the null token
+            if not 0 <= nl < self.num_classes:
+                raise ValueError(f"null_label must be a class index in [0, {self.num_classes}), got {null_label}")
+        if isinstance(guidance_scale, torch.Tensor) and guidance_scale.dim() > 0:
+            if tuple(guidance_scale.shape) != (B,):
+                raise ValueError(f"a per-image guidance_scale must have shape ({B},), got {tuple(guidance_scale.shape)}")
+            if guidance_scale.device != self.device:
+                raise MI355BackendError(f"guidance_scale is on {guidance_scale.device}, the engine lives on {self.device} (no CPU fallback)")
+            return 0.0, guidance_scale.to(torch.float32).contiguous(), nl
+        return float(guidance_scale), None, nl
+
+    def cfg_batch(self) -> int:
+        """Largest batch of one guided call, max_batch() // 2: every evaluation runs at twice the batch.  An engine whose max_batch() is 1
+        cannot run a guided evaluation at all (it is two images) and is refused."""
+        mb = self.max_batch()
+        if mb < 2:
+            raise MI355BackendError(f"guidance evaluates the network at twice the batch, and max_batch() of this engine is {mb}: "
+                                    "a guided call needs max_batch() >= 2")
+        return mb // 2
+
+    def _workspace_sized(self, name: str, *args):
+        """The workspace of a sampler that keeps buffers behind the network's (size function `name`(handle, *args)), its size cached."""
+        need = self._ws_bytes.get((name,) + args)
+        if need is None:
+            need = self._ws_bytes[(name,) + args] = check(getattr(self.L, name)(self.handle, *args), name)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return C.c_void_p(self._ws.data_ptr()), self._ws.numel()
+
+    def _forward_cfg(self, x, t, cond, out, y, guidance_scale, null_label, none_value):
+        """The guided field of one evaluation: the 2B forward, then cfg_stage with no base term."""
+        from .ops import default_ops
+
+        B, Cx, Cc = self._split(x, cond)
+        lab, _ = self._labels(y, B)
+        w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
+        mb = self.cfg_batch()
+        if out is None:
+            out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
+        host_t = isinstance(t, (int, float))
+        for lo in range(0, B, mb):
+            hi = min(B, lo + mb)
+            x2 = torch.cat((x[lo:hi], x[lo:hi]))
+            c2 = torch.cat((cond[lo:hi], torch.full_like(cond[lo:hi], float(none_value)))) if cond is not None else None
+            y2 = torch.cat((lab[lo:hi], torch.full_like(lab[lo:hi], nl))) if lab is not None else None
+            t2 = t if host_t else torch.cat((t[lo:hi], t[lo:hi]))
+            v2 = self.forward(x2, t2, cond=c2, y=y2)
+            default_ops.cfg_combine(v2, w if wt is None else wt[lo:hi], out=out[lo:hi] if (lo, hi) != (0, B) else out)
+        self._fwd_state = None
+        return out
+
+    def forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
+                guidance_scale=None, null_label: Optional[int] = None, none_value: float = -2.0):
         """t: a [B] device tensor, or a host scalar shared by the batch (no device tensor is made for it: mi355_unet_forward_t).
         y: class labels [B] (integer, on the device) of a class-conditional engine: emb = time_embed(.) + label_emb(y)
-        (mi355_unet_forward_labels); None = the reference's forward(x, timesteps), which never reads label_emb."""
+        (mi355_unet_forward_labels); None = the reference's forward(x, timesteps), which never reads label_emb.
+        guidance_scale (a float or a [B] tensor; None: the plain forward): the classifier-free-guided field v_u + w (v_c - v_u) of ONE forward at
+        batch 2B, v_u from the none_value-filled condition and / or null_label (default: the last class) - then mi355_cfg_stage."""
+        if guidance_scale is not None:
+            return self._forward_cfg(x, t, cond, out, y, guidance_scale, null_label, none_value)
         B, Cx, Cc = self._split(x, cond)
         if y is not None:
             lab, lab_p = self._labels(y, B)
@@ -238,14 +304,65 @@ class UNetEngine:
             self._max_batch = max(1, 0xFFFF0000 // (2 * per_image))   # x2: a concat source pair / an in-flight double of the same tensor
         return self._max_batch
 
+    def cfm_cfg(self, x: torch.Tensor, t_span: Sequence[float], method="euler", cond: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
+                guidance_scale=1.0, null_label: Optional[int] = None, none_value: float = -2.0, keep_traj: bool = False, want_u8: bool = False):
+        """In-place classifier-free-guided fixed-step integration of x over t_span (mi355_cfm_cfg_sample): the loop of cfm_rk over `method`
+        ("euler" is the one-stage tableau) with every evaluation v_u + w (v_c - v_u), run as one forward at batch 2B.  guidance_scale: a float
+        or a [B] tensor.  Returns (x, traj or None, u8 or None).  A batch beyond cfg_batch() = max_batch() // 2 runs in slices that
+        carry their labels, conditions and scales."""
+        from .ode import resolve_tableau
+
+        a, b, c = resolve_tableau(method)
+        B, Cx, Cc = self._split(x, cond)
+        lab, _ = self._labels(y, B)
+        w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
+        ts = [float(v) for v in t_span]
+        traj = torch.empty((len(ts),) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
+        u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
+        mb = self.cfg_batch()
+        for lo in range(0, B, mb):
+            hi = min(B, lo + mb)
+            whole = (lo, hi) == (0, B)
+            xs = x if whole else x[lo:hi]
+            tr = traj if whole or traj is None else torch.empty((len(ts),) + tuple(xs.shape), device=self.device, dtype=torch.float32)
+            us = u8 if whole or u8 is None else u8[lo:hi]
+            self._cfm_cfg_call(xs, ts, (a, b, c), cond[lo:hi] if cond is not None else None, lab[lo:hi] if lab is not None else None, nl, w,
+                               wt[lo:hi] if wt is not None else None, float(none_value), tr, us)
+            if traj is not None and not whole:
+                traj[:, lo:hi] = tr
+        return x, traj, u8
+
+    def _cfm_cfg_call(self, x, ts, tableau, cond, lab, null_label, w, wt, none_value, traj, u8):
+        """One mi355_cfm_cfg_sample call (a batch within cfg_batch())."""
+        a, b, c = tableau
+        stages = len(b)
+        B, Cx, Cc = self._split(x, cond)
+        arr = (C.c_float * len(ts))(*ts)
+        a_arr = (C.c_float * (stages * stages))(*[v for row in a for v in row])
+        b_arr, c_arr = (C.c_float * stages)(*b), (C.c_float * stages)(*c)
+        self._fwd_state = None
+        ws, wsb = self._workspace_sized("mi355_cfg_workspace_bytes", B, stages)
+        check(self.L.mi355_cfm_cfg_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc,
+                                          none_value, C.c_void_p(lab.data_ptr()) if lab is not None else None, int(null_label), float(w),
+                                          self._chk(wt, "guidance_scale") if wt is not None else None, arr, len(ts), stages, a_arr, b_arr, c_arr,
+                                          self._chk(traj, "traj") if traj is not None else None,
+                                          self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
+              "mi355_cfm_cfg_sample")
+
     def cfm_euler(self, x: torch.Tensor, t_span: Sequence[float], cond: Optional[torch.Tensor] = None, keep_traj: bool = False,
-                  want_u8: bool = False, cond_drift: bool = False, y: Optional[torch.Tensor] = None):
+                  want_u8: bool = False, cond_drift: bool = False, y: Optional[torch.Tensor] = None, guidance_scale=None,
+                  null_label: Optional[int] = None, none_value: float = -2.0):
         """In-place Euler integration of x over t_span (host floats).  Returns (x, traj or None, u8 or None).
         cond_drift: the condition is integrated with derivative `cond` (the concatenated-state sampler of
         mnist/utils_mnist2.py:118-138); the caller's tensor is not modified.
         A batch beyond max_batch() is integrated in slices (every image's trajectory is independent of its batch mates; the kernels chosen for a
         slice may sum in another order than those of the whole batch would).
-        y: class labels [B] of a class-conditional engine: every step evaluates model(t_k, x_k, y) (mi355_cfm_euler_sample_labels)."""
+        y: class labels [B] of a class-conditional engine: every step evaluates model(t_k, x_k, y) (mi355_cfm_euler_sample_labels).
+        guidance_scale (a float or a [B] tensor; None: the paths above, untouched): classifier-free guidance, see cfm_cfg."""
+        if guidance_scale is not None:
+            if cond_drift:
+                raise NotImplementedError("cond_drift (the drifting condition of the concatenated-state sampler) is not built with guidance")
+            return self.cfm_cfg(x, t_span, "euler", cond, y, guidance_scale, null_label, none_value, keep_traj, want_u8)
         B, Cx, Cc = self._split(x, cond)
         lab, lab_p = self._labels(y, B)
         mb = self.max_batch()
@@ -281,16 +398,11 @@ class UNetEngine:
 
     def _workspace_rk(self, batch: int, stages: int):
         """The sampler workspace with the RK stage buffers behind it (mi355_cfm_rk_workspace_bytes), its size cached per (batch, stages)."""
-        need = self._rk_bytes.get((batch, stages))
-        if need is None:
-            need = self._rk_bytes[(batch, stages)] = check(self.L.mi355_cfm_rk_workspace_bytes(self.handle, batch, stages), "mi355_cfm_rk_workspace_bytes")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return C.c_void_p(self._ws.data_ptr()), self._ws.numel()
+        return self._workspace_sized("mi355_cfm_rk_workspace_bytes", batch, stages)
 
     def cfm_rk(self, x: torch.Tensor, t_span: Sequence[float], method="rk4", cond: Optional[torch.Tensor] = None, keep_traj: bool = False,
-               want_u8: bool = False, y: Optional[torch.Tensor] = None, cond_drift: bool = False):
+               want_u8: bool = False, y: Optional[torch.Tensor] = None, cond_drift: bool = False, guidance_scale=None,
+               null_label: Optional[int] = None, none_value: float = -2.0):
         """In-place fixed-step explicit Runge-Kutta integration of x over t_span (host floats), one step per interval, the whole loop one
         library call (mi355_cfm_rk_sample).  method: a name of mi355.ode.TABLEAUS ("euler", "midpoint", "heun2", "rk4", "rk4_38") or an
         (a, b, c) tableau of 1 to 4 stages.  Returns (x, traj or None, u8 or None).
@@ -299,6 +411,8 @@ class UNetEngine:
         reference runs it with Euler only)."""
         if cond_drift:
             raise NotImplementedError("cond_drift (the drifting condition of the concatenated-state sampler) is built for Euler only: cfm_euler")
+        if guidance_scale is not None:   # classifier-free guidance: see cfm_cfg
+            return self.cfm_cfg(x, t_span, method, cond, y, guidance_scale, null_label, none_value, keep_traj, want_u8)
         from .ode import resolve_tableau
 
         a, b, c = resolve_tableau(method)
@@ -385,23 +499,37 @@ class UNetEngine:
 
     def ddpm_sample(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], *, mode: int, cond: Optional[torch.Tensor] = None,
                     noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0,
-                    noise_condition=True, pad_value=-2.0, none_value=-2.0, seed=0):
-        """In-place reverse-denoising loop.  tables: name -> CPU fp32 tensor [Ns] (DDPM buffers)."""
+                    noise_condition=True, pad_value=-2.0, none_value=-2.0, seed=0, guidance_scale=None, y: Optional[torch.Tensor] = None,
+                    null_label: Optional[int] = None):
+        """In-place reverse-denoising loop.  tables: name -> CPU fp32 tensor [Ns] (DDPM buffers).
+        guidance_scale (a float or a [B] tensor; None: mi355_ddpm_sample, untouched): classifier-free guidance of the predictor's eps
+        (mi355_ddpm_cfg_sample; Amortized mode, or DDIM with a condition, on a 2C-input net), eps_u from the none_value-filled condition and, with
+        y (class labels [B]), null_label (default: the last class).  A batch beyond cfg_batch() runs in slices (Philox: seed + slice index)."""
         B, Cx = x.shape[:2]
         if cond is not None and cond.shape != x.shape:
             raise ValueError("condition must have the shape of x")
-        tb = _lib.DDPMTablesC()
-        keep = []
-        Ns = None
-        fp = C.POINTER(C.c_float)
-        for name, _ in _lib.DDPMTablesC._fields_[1:]:
-            v = tables[name].detach().to("cpu", torch.float32).contiguous()
-            Ns = v.numel() if Ns is None else Ns
-            if v.numel() != Ns:
-                raise ValueError("DDPM tables must all have length Ns")
-            keep.append(v)
-            setattr(tb, name, C.cast(v.data_ptr(), fp))
-        tb.Ns = Ns
+        if guidance_scale is None and y is not None:
+            raise NotImplementedError("ddpm_sample takes class labels on the guided path only (guidance_scale=)")
+        if guidance_scale is not None:
+            if mode not in (_lib.DDPM_AMORTIZED, _lib.DDIM):
+                raise NotImplementedError("guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement are refused)")
+            lab, _ = self._labels(y, B)
+            w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
+            if noise is not None and noise.shape[1:] != x.shape:
+                raise ValueError("injected noise must be [n_draws, B, C, H, W]")
+            mb = self.cfg_batch()
+            for i, lo in enumerate(range(0, B, mb)):
+                hi = min(B, lo + mb)
+                whole = (lo, hi) == (0, B)
+                xs = x if whole else x[lo:hi].contiguous()
+                self._ddpm_cfg_call(xs, tables, mode, cond if whole or cond is None else cond[lo:hi].contiguous(),
+                                    lab[lo:hi] if lab is not None else None, nl, w, wt[lo:hi] if wt is not None else None,
+                                    noise if whole or noise is None else noise[:, lo:hi].contiguous(),
+                                    dict(n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, none_value=none_value, seed=(seed + i) % 2 ** 64))
+                if not whole:
+                    x[lo:hi] = xs
+            return x
+        tb, keep = self._ddpm_tables(tables)
         opt = _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value,
                                 int(cond is None), seed)
         ndraws = 0
@@ -415,3 +543,34 @@ class UNetEngine:
                                        C.byref(tb), C.byref(opt), self._chk(noise, "noise") if noise is not None else None, ndraws, B,
                                        ws, wsb, self._stream()), "mi355_ddpm_sample")
         return x
+
+    @staticmethod
+    def _ddpm_tables(tables):
+        """name -> CPU fp32 tensor [Ns]  =>  (mi355_ddpm_tables, the tensors it points into)."""
+        tb = _lib.DDPMTablesC()
+        keep = []
+        Ns = None
+        fp = C.POINTER(C.c_float)
+        for name, _ in _lib.DDPMTablesC._fields_[1:]:
+            v = tables[name].detach().to("cpu", torch.float32).contiguous()
+            Ns = v.numel() if Ns is None else Ns
+            if v.numel() != Ns:
+                raise ValueError("DDPM tables must all have length Ns")
+            keep.append(v)
+            setattr(tb, name, C.cast(v.data_ptr(), fp))
+        tb.Ns = Ns
+        return tb, keep
+
+    def _ddpm_cfg_call(self, x, tables, mode, cond, lab, null_label, w, wt, noise, o):
+        """One mi355_ddpm_cfg_sample call (a batch within cfg_batch())."""
+        B, Cx = x.shape[:2]
+        tb, keep = self._ddpm_tables(tables)
+        opt = _lib.DDPMOptionsC(mode, o["n_corrector"], o["delta"], o["tmin"], o["tmax"], 1.0, 1, -2.0, o["none_value"], int(cond is None), o["seed"])
+        self._fwd_state = None
+        ws, wsb = self._workspace_sized("mi355_ddpm_cfg_workspace_bytes", B)
+        check(self.L.mi355_ddpm_cfg_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
+                                           C.c_void_p(lab.data_ptr()) if lab is not None else None, int(null_label), float(w),
+                                           self._chk(wt, "guidance_scale") if wt is not None else None, C.byref(tb), C.byref(opt),
+                                           self._chk(noise, "noise") if noise is not None else None, noise.shape[0] if noise is not None else 0, B,
+                                           ws, wsb, self._stream()), "mi355_ddpm_cfg_sample")
+        del keep

@@ -227,6 +227,80 @@ class Ops:
                                         _req(u8_out, "u8_out", torch.uint8) if u8_out is not None else None, _stream()), "mi355_rk_stage")
         return out
 
+    # --- classifier-free guidance (csrc/ode.hip cfg_stage_kernel, csrc/steps.hip) ---
+    @staticmethod
+    def _cfg_w(w, B):
+        """guidance scale -> (host float, device pointer or None, tensor kept alive)."""
+        if isinstance(w, torch.Tensor) and w.dim() > 0:
+            if tuple(w.shape) != (B,):
+                raise ValueError(f"a per-image guidance scale must have shape ({B},), got {tuple(w.shape)}")
+            w = w.to(torch.float32).contiguous()
+            return 0.0, _req(w, "w"), w
+        return float(w), None, None
+
+    def cfg_stage(self, out, y0, ks, coeffs, w, dup=False, copy_out=None, u8_out=None):
+        """rk_stage over classifier-free-guided derivatives: every ks[j] is [2B, ...] (the conditional evaluation in the first half, the
+        unconditional one in the second), g_j = u + w (c - u) with each operation rounded, out = y0 + sum_j coeffs[j] * g_j.  w: a float
+        or a [B] tensor.  y0: [B, ...] or None (no base term).  out: [B, ...], or [2B, ...] with dup (the result in both halves).  y0 may be
+        out's first half (in place)."""
+        if not 1 <= len(ks) == len(coeffs) <= 4:
+            raise ValueError("cfg_stage takes 1 to 4 stage derivatives, one coefficient each")
+        B2 = ks[0].shape[0]
+        if B2 % 2:
+            raise ValueError("the derivatives hold the conditional and the unconditional evaluation: an even leading size")
+        B = B2 // 2
+        half = (B,) + tuple(ks[0].shape[1:])
+        for k in ks:
+            _same(ks[0], k, "k", "k")
+        if tuple(out.shape) != ((B2,) + half[1:] if dup else half):
+            raise ValueError(f"out must be {(B2,) + half[1:] if dup else half}, got {tuple(out.shape)}")
+        for t, nm in ((y0, "y0"), (copy_out, "copy_out"), (u8_out, "u8_out")):
+            if t is not None and tuple(t.shape) != half and not (nm == "y0" and dup and tuple(t.shape) == tuple(out.shape)):
+                raise ValueError(f"{nm} must be {half}, got {tuple(t.shape)}")
+        n = ks[0].numel() // 2
+        wf, wp, keep = self._cfg_w(w, B)
+        arr = (C.c_float * 4)(*([float(c) for c in coeffs] + [0.0] * (4 - len(coeffs))))
+        kp = (C.c_void_p * 4)(*([_req(k, "k") for k in ks] + [None] * (4 - len(ks))))
+        check(_lib.lib().mi355_cfg_stage(_req(out, "out"), _req(y0, "y0") if y0 is not None else None, kp, arr, len(ks), n, wf, wp,
+                                         n // B if B else 1, int(bool(dup)), _req(copy_out, "copy_out") if copy_out is not None else None,
+                                         _req(u8_out, "u8_out", torch.uint8) if u8_out is not None else None, _stream()), "mi355_cfg_stage")
+        return out
+
+    def cfg_combine(self, v2, w, out=None):
+        """The guided field of one 2B evaluation: v2 [2B, ...] = conditional | unconditional -> u + w (c - u) [B, ...] (cfg_stage, no base term)."""
+        if out is None:
+            out = torch.empty((v2.shape[0] // 2,) + tuple(v2.shape[1:]), device=v2.device, dtype=torch.float32)
+        return self.cfg_stage(out, None, [v2], [1.0], w)
+
+    def ddpm_cfg_step_(self, x2, eps2, z, w, c_recip, c_recipm1, coef1, coef2, sigma, philox=None):
+        """ddpm_step_ on the guided eps: x2 [2B, ...] the duplicated state (first half read, both halves written), eps2 [2B, ...] =
+        conditional | unconditional; z [B, ...] injected noise or None; philox (seed, offset) indexes the B-image state."""
+        _same(x2, eps2, "x2", "eps2")
+        B = x2.shape[0] // 2
+        if x2.shape[0] % 2:
+            raise ValueError("x2 holds the state twice: an even leading size")
+        n = x2.numel() // 2
+        if z is not None and z.numel() != n:
+            raise ValueError("z must have the B-image state's size")
+        wf, wp, keep = self._cfg_w(w, B)
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_ddpm_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _req(z, "z") if z is not None else None, wf, wp, n // B if B else 1,
+                                             c_recip, c_recipm1, coef1, coef2, sigma, int(philox is not None and z is None), seed, off, n, _stream()),
+              "mi355_ddpm_cfg_step")
+        return x2
+
+    def ddim_cfg_step_(self, x2, eps2, w, c_recip, c_recipm1, acp_prev):
+        """ddim_step_ on the guided eps, operands as ddpm_cfg_step_."""
+        _same(x2, eps2, "x2", "eps2")
+        if x2.shape[0] % 2:
+            raise ValueError("x2 holds the state twice: an even leading size")
+        B = x2.shape[0] // 2
+        n = x2.numel() // 2
+        wf, wp, keep = self._cfg_w(w, B)
+        check(_lib.lib().mi355_ddim_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), wf, wp, n // B if B else 1, c_recip, c_recipm1, acp_prev, n, _stream()),
+              "mi355_ddim_cfg_step")
+        return x2
+
     def rk_sqnorm(self, acc, a, sub=None, b=None, b2=None, atol=1.0, rtol=0.0):
         """acc (device fp64 scalar tensor) += sum(((a - sub) / (atol + rtol * max(|b|, |b2|)))**2)."""
         check(_lib.lib().mi355_rk_sqnorm(_req(a, "a"), _req(sub, "sub") if sub is not None else None, _req(b, "b") if b is not None else None,

@@ -76,9 +76,12 @@ class UNetModelWrapper(UNetModel):
         return t if isinstance(t, float) else t.contiguous()
 
     @torch.no_grad()
-    def forward(self, t, x, y=None, *args, **kwargs):
+    def forward(self, t, x, y=None, *args, guidance_scale=None, null_label=None, **kwargs):
         """torchcfm: model(t, x, y).  A class-conditional model (num_classes set) needs y, the labels [B]; without num_classes y is ignored
-        (the mnist/ call sites' class_cond=True, num_classes=None networks)."""
+        (the mnist/ call sites' class_cond=True, num_classes=None networks).
+        guidance_scale (a float or a [B] tensor; None: the plain forward): the classifier-free-guided field v_u + w (v_c - v_u), v_u at
+        null_label (default: the last class), from one evaluation at twice the batch - odeint_dopri5(lambda t, x: model(t, x, y,
+        guidance_scale=w, null_label=K), ...)."""
         if self.num_classes is None:
             y = None
         elif y is None:
@@ -86,6 +89,9 @@ class UNetModelWrapper(UNetModel):
                              f"{self.num_classes} (torchcfm asserts (y is not None) == (num_classes is not None))")
         if not x.is_cuda:
             return super().forward(x, t)     # raises MI355BackendError (no CPU path)
+        if guidance_scale is not None:
+            return self.engine(x.device).forward(x.float().contiguous(), self._c(self._t(t, x)), y=y, guidance_scale=guidance_scale,
+                                                 null_label=null_label)
         return self.engine(x.device).forward(x.float().contiguous(), self._c(self._t(t, x)), y=y)
 
 
@@ -93,7 +99,8 @@ class ClassCondUNetModelWrapper(UNetModelWrapper):
     """torchcfm's UNetModelWrapper built class-conditional, the model of conditional_mnist.ipynb (`from torchcfm.models.unet import
     UNetModel`; `UNetModel(dim=(1, 28, 28), num_channels=32, num_res_blocks=1, num_classes=10, class_cond=True)`): the same constructor,
     label_emb.weight [num_classes, 4 * num_channels] (N(0, 1) init), and model(t, x, y) with y, the labels [B], required.  Sample it with
-    odeint_dopri5(lambda t, x: model(t, x, y), ...) or model.engine().cfm_euler(x, t_span, y=y); NeuralODE has no labels to pass."""
+    odeint_dopri5(lambda t, x: model(t, x, y), ...), model.engine().cfm_euler(x, t_span, y=y), or NeuralODE(GuidedVectorField(model, y=y,
+    guidance_scale=w)): NeuralODE itself has no labels to pass, the GuidedVectorField carries them."""
 
     _class_cond_ok = True
 
@@ -128,6 +135,28 @@ class SuperResModelWrapper(UNetModelWrapper):
         return eng.forward(x.float().contiguous(), self._c(self._t(t, x)), cond=up)
 
 
+class GuidedVectorField:
+    """A vector field with what a NeuralODE call site cannot pass: class labels y [B] and / or a condition con [B, Cc, H, W], and a
+    classifier-free guidance scale (a float or a [B] tensor).  f(t, x) = v_u + w (v_c - v_u), v_u at null_label (default: the last class)
+    and / or the none_value-filled condition.  NeuralODE.trajectory recognises it: with a fixed-step solver the whole guided integration is
+    one library call (UNetEngine.cfm_euler / cfm_rk, mi355_cfm_cfg_sample); dopri5 calls it per evaluation."""
+
+    def __init__(self, model, y=None, con=None, guidance_scale=1.0, null_label=None, none_value=-2.0):
+        if y is None and con is None:
+            raise ValueError("GuidedVectorField needs class labels (y) and / or a condition (con)")
+        self.model, self.y, self.con = model, y, con
+        self.guidance_scale, self.null_label, self.none_value = guidance_scale, null_label, float(none_value)
+
+    def _kw(self, device):
+        con = self.con.to(device).float().contiguous() if self.con is not None else None
+        return dict(cond=con, y=self.y.to(device) if self.y is not None else None, guidance_scale=self.guidance_scale,
+                    null_label=self.null_label, none_value=self.none_value)
+
+    @torch.no_grad()
+    def __call__(self, t, x, *args, **kwargs):
+        return self.model.engine(x.device).forward(x.float().contiguous(), self.model._c(self.model._t(t, x)), **self._kw(x.device))
+
+
 class NeuralODE:
     """torchdyn.core.NeuralODE front-end: solver="euler" (fixed step), "midpoint", "heun2", "rk4", "rk4_38" (fixed-step explicit
     Runge-Kutta, the tableaus of mi355.ode.TABLEAUS: "rk4" the classical one, "rk4_38" the 3/8 rule) or "dopri5" (adaptive,
@@ -152,7 +181,7 @@ class NeuralODE:
 
     def _call(self, t, x):
         # the library's own wrappers take the host scalar as it is; any other vector field gets the 0-dim tensor torchdyn passes
-        tt = float(t) if isinstance(self.vf, UNetModelWrapper) else torch.tensor(float(t), device=x.device, dtype=torch.float32)
+        tt = float(t) if isinstance(self.vf, (UNetModelWrapper, GuidedVectorField)) else torch.tensor(float(t), device=x.device, dtype=torch.float32)
         try:
             return self.vf(tt, x)
         except TypeError:
@@ -169,6 +198,12 @@ class NeuralODE:
             solver = Dopri5(lambda t, y: [self._call(t, y[0])], self.rtol, self.atol)
             states = solver.integrate_times([x], ts)   # one continuous adaptive solve, dense output at every requested time
             return torch.stack([x] + [s[0] for s in states])
+        if isinstance(self.vf, GuidedVectorField) and x.is_cuda:   # fixed-step and guided: one library call
+            eng = self.vf.model.engine(x.device)
+            kw = self.vf._kw(x.device)
+            if self.solver == "euler":
+                return eng.cfm_euler(x, ts, keep_traj=True, **kw)[1]
+            return eng.cfm_rk(x, ts, self.solver, keep_traj=True, **kw)[1]
         if self.solver in self.RK_SOLVERS:
             if type(self.vf) is UNetModelWrapper and x.is_cuda:
                 _, traj, _ = self.vf.engine(x.device).cfm_rk(x, ts, self.solver, keep_traj=True)

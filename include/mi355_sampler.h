@@ -44,7 +44,9 @@ extern "C" {
 
 /* ABI version = 100 * major + minor.  The minor number counts additive changes; 107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
- * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4).  106: mi355_qkv_attention_vjp (the attention backward as a test
+ * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
+ * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
+ * symbols only).  106: mi355_qkv_attention_vjp (the attention backward as a test
  * op); later additions to 106: mi355_unet_config::num_classes (class-conditional nets), mi355_unet_forward_labels,
  * mi355_cfm_euler_sample_labels, and the error word's bit 1 (a class label out of range, reported as MI355_ERR_ARG); then
  * mi355_sf2m_euler_sample (the two-network SF2M SDE sampler) and mi355_sde_euler_step (its Euler-Maruyama update as an op).  105 (round 5, last): mi355_debug_config::sampler_graph (carved out of the
@@ -336,6 +338,47 @@ int mi355_ddpm_sample(mi355_unet* net, float* x, int channels, const float* cond
                       const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Classifier-free guidance (Ho & Salimans 2022) for nets trained with condition dropout (AD/image_diffusion/loss_functions.py:47-50 feeds
+ * likelihood.none_like(x) with probability 1 - p_cond; class-conditional nets reserve a null class): every evaluation is
+ *   v = v_u + w * (v_c - v_u),   v_c = model(t, x, cond, labels),  v_u = model(t, x, none_value-filled condition, null_label),
+ * the difference, the product and the sum each rounded to fp32.  Both halves come from ONE forward at batch 2B (images 0..B-1 conditional, B..2B-1
+ * unconditional): the weights stream once and the launch count of an evaluation is that of a single one.  w: host scalar, or w_dev: device
+ * float[B], one scale per image (w is then ignored).  w = 1 is the conditional model up to the rounding of v_u + (v_c - v_u), w = 0 the unconditional.
+ *
+ * mi355_cfm_cfg_sample: the loop of mi355_cfm_rk_sample (same tableau arguments, times, traj, u8_out; Euler is the 1-stage tableau a = {0}, b = {1},
+ * c = {0}) with every evaluation guided.  At least one of (cond, none_value) and (labels, null_label) must be given; both may be.
+ *   cond   : NULL or [B, Cc, H, W], Cc == in_channels - out_channels;  labels: NULL or device int32[B];  null_label: a class index of the net,
+ *            checked on the host (the usual recipe trains num_classes = K + 1 with the last index as the null token).
+ * The sampler works on a duplicated state x2[2B] behind the network workspace (x is copied in and out once per call; cond | none and labels | null are
+ * built once per call); each stage state and the update is one mi355_cfg_stage launch that writes both halves.  Launches per step: `stages`
+ * evaluations at 2B and `stages` stage launches (a stage without non-zero a_ij has none); no copy.  After the call mi355_unet_get_stats reports the
+ * launches of the whole last step.  Embedding table: with (n_t - 1) * stages * K <= 1024 as in mi355_cfm_rk_sample (the (step, class) table and its
+ * gather work on the 2B label array unchanged), else per-evaluation rows.  cond_drift, sampler_graph and the Euler update inside the last conv take
+ * no part.  workspace: mi355_cfg_workspace_bytes(net, batch, stages) = mi355_unet_workspace_bytes(net, 2 * batch) rounded up to 256, then, each
+ * rounded up to 256: x2; cond2 when in_channels > out_channels; labels2 when num_classes > 0; `stages` derivative buffers of 2B images; one stage
+ * state of 2B images when stages > 1.
+ * Errors: those of mi355_cfm_rk_sample; neither cond nor labels, null_label outside [0, num_classes) (MI355_ERR_ARG); a condition of another
+ * channel count, a short workspace (-2).
+ *
+ * mi355_ddpm_cfg_sample: mi355_ddpm_sample for MI355_DDPM_AMORTIZED and for MI355_DDIM with a condition, on a 2C-input net, with the predictor's eps
+ * guided: eps = eps_u + w * (eps_c - eps_u), eps_u from the none_value-filled condition (opt->none_value) and, with labels, null_label.  Corrector
+ * steps run as in mi355_ddpm_sample, at batch B on the first half with none_like as the condition (the reference's corrector, sampling.py:116) and,
+ * on a class-conditional net, the null label; one device copy after the last corrector of a step refreshes the second half.  Noise draws keep
+ * mi355_ddpm_sample's numbering and Philox offsets (n_al of the B-image state): with w = 1 and the same seed the result differs from
+ * mi355_ddpm_sample's only by the rounding of eps_u + (eps_c - eps_u).  labels: NULL or device int32[B] (the first DDPM path that takes them).
+ * workspace: mi355_ddpm_cfg_workspace_bytes(net, batch) = the 2B network workspace rounded up to 256, then x2, cond2, labels2 (num_classes > 0).
+ * Errors: MI355_DDPM_PRIOR / MI355_DDPM_REPLACEMENT, neither cond nor labels, labels on a net without num_classes, null_label out of range
+ * (MI355_ERR_ARG); no condition or not a 2C-input net, a short workspace (-2). */
+int64_t mi355_cfg_workspace_bytes(const mi355_unet* net, int batch, int stages);
+int mi355_cfm_cfg_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, float none_value, const int32_t* labels,
+                         int null_label, float w, const float* w_dev, const float* t_span_host, int n_t, int stages, const float* a_host,
+                         const float* b_host, const float* c_host, float* traj, uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+int64_t mi355_ddpm_cfg_workspace_bytes(const mi355_unet* net, int batch);
+int mi355_ddpm_cfg_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w, const float* w_dev,
+                          const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- single ops (used by the Python mirror for arbitrary eps_model callables, and by the tests) --- */
 
 /* timestep_embedding (AD/image_diffusion/nn.py:97-115): t[B] -> out[B, dim] */
@@ -430,6 +473,20 @@ int mi355_rk_combine(float* out, const float* y0, const float* k0, const float* 
                      const float* k5, const float* k6, const float* coeff_host, int nk, int64_t n, void* stream);
 int mi355_rk_stage(float* out, const float* y0, const float* const k[4], const float* coeff_host, int nk, int64_t n, float* copy_out,
                    uint8_t* u8_out, void* stream);
+/* Classifier-free-guided forms of rk_stage / ddpm_step / ddim_step.  The derivative (eps) tensors hold 2n values: the conditional evaluation in
+ * [0, n), the unconditional one in [n, 2n).  g = u + w * (c - u), difference, product and sum each rounded to fp32; w_dev (or NULL): one scale per
+ * image of elems_per_image elements (n a multiple of it), instead of w.  16-byte accesses only when every pointer and every half base p + n is
+ * 16-byte aligned; n need not be a multiple of 4; n <= 0: nothing is done.
+ *   cfg_stage    : out = y0 + sum_j coeff_host[j] * g_j, then exactly rk_stage's arithmetic; y0 may be NULL (no base term: nk = 1, coeff 1 gives the
+ *                  guided field itself); dup != 0: the result also goes to out[n + e] (out then holds 2n values); copy_out / u8_out as in rk_stage.
+ *   ddpm_cfg_step: x holds the duplicated state [2n]; mi355_ddpm_step's arithmetic on eps_g from x's first half, the result to BOTH halves; the
+ *                  Philox stream is indexed by the element of the n-element state.  ddim_cfg_step likewise for mi355_ddim_step. */
+int mi355_cfg_stage(float* out, const float* y0, const float* const k[4], const float* coeff_host, int nk, int64_t n, float w, const float* w_dev,
+                    int64_t elems_per_image, int dup, float* copy_out, uint8_t* u8_out, void* stream);
+int mi355_ddpm_cfg_step(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1,
+                        float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream);
+int mi355_ddim_cfg_step(float* x, const float* eps, float w, const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1, float acp_prev,
+                        int64_t n, void* stream);
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream);
 int mi355_rk_interp(float* out, const float* y0, const float* y1, const float* y_mid, const float* f0, const float* f1, float dt, float x,
