@@ -5,7 +5,7 @@
 
 const mi355_debug_config& mi355_default_debug();   // the shipped behaviour (capi.hip)
 
-// INTERNAL element-type codes of every descriptor below (the C ABI's MI355_* dtype values are translated at the boundary, capi.hip: MI355_BF16X2 ->
+// INTERNAL element-type codes of every descriptor below (the C ABI's MI355_* dtype values are translated at the boundary, capi.hip and test_ops.hip: MI355_BF16X2 ->
 // DT_BF16 + ConvDesc::wsplit, MI355_F16 -> DT_F16).  Sizes and chunking depend only on "4-byte or 2-byte": dtype == 0 ? 4 : 2.
 enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };
 // run f(T()) for the element type of an internal dtype code

@@ -1,0 +1,580 @@
+// The sampler loops of libmi355_sampler.so (see include/mi355_sampler.h): workspace layouts, the embedding rows of the evaluations, and the
+// Euler (+ graph form), Runge-Kutta, DDPM, their classifier-free-guided forms, and SF2M entry points.  Host code only.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "capi_internal.h"
+
+// The sampler loops know every evaluation time in advance: all emb_layers outputs of up to EMB_TABLE_STEPS evaluations are computed by four
+// launches before the loop instead of four launches per evaluation (longer schedules fall back to the per-evaluation path).
+constexpr int EMB_TABLE_STEPS = 1024;
+
+namespace {
+
+// ---- workspace layouts ------------------------------------------------------------------------------
+// ONE walk over the regions of a sampler's workspace: a size function walks from a null base and returns where the walk ends, a sampler walks
+// from the caller's pointer and keeps the addresses.  A region's size is written here and nowhere else.
+struct Walk {
+  uintptr_t p;
+  template <class T = float> T* take(size_t bytes) { T* r = reinterpret_cast<T*>(p); p += al256(bytes); return r; }
+};
+// sampler scratch: t[B], eps/v [B,32,H,W], none_like [B,32,H,W], the step times and the embedding table of EvalEmb, the graph form's resident
+// state [B,Cout,H,W] (mi355_debug_config::sampler_graph), then the engine workspace
+struct Scratch { float* t; float* v; float* none; float* tsteps; float* embtab; float* xstate; char* unet_ws; int64_t unet_bytes; };
+// classifier-free guidance: duplicated state x | x, condition | none_value, labels | null label (the last two only where the net takes them)
+struct CfgTail { float* x2; float* cond2; int32_t* labels2; };
+// fixed-step Runge-Kutta: the stage derivatives k_1..k_s and the stage state y_i, each a state at the evaluation batch
+struct RkBufs { float* k[4]; float* ystage; };
+struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; uintptr_t end; };
+inline size_t cfg_cond_channels(const mi355_unet* net) { return (size_t)(net->cfg.in_channels > net->cfg.out_channels ? net->cfg.in_channels - net->cfg.out_channels : 0); }
+
+// guided: the network runs at 2 * batch and the guidance tail follows its workspace; stages > 0: the Runge-Kutta buffers close the layout
+Layout layout(const mi355_unet* net, int batch, bool guided, int stages, uintptr_t base) {
+  const size_t hw = (size_t)net->cfg.image_size * net->cfg.image_size;
+  const int B = guided ? 2 * batch : batch;
+  const size_t state = (size_t)B * net->cfg.out_channels * hw * 4;
+  Layout l = {};
+  Walk w{base};
+  l.sc.t = w.take((size_t)B * 4);
+  l.sc.v = w.take((size_t)B * 32 * hw * 4);
+  l.sc.none = w.take((size_t)B * 32 * hw * 4);
+  l.sc.tsteps = w.take((size_t)EMB_TABLE_STEPS * 4);
+  l.sc.embtab = w.take((size_t)EMB_TABLE_STEPS * ((size_t)net->emb_total + 9 * (size_t)net->cfg.model_channels) * 4);
+  l.sc.xstate = w.take(state);
+  l.sc.unet_bytes = unet_workspace_bytes(net, B);
+  l.sc.unet_ws = reinterpret_cast<char*>(w.p);
+  w.p += (size_t)l.sc.unet_bytes;   // not rounded up: mi355_unet_workspace_bytes ends here
+  if (guided || stages) w.p = al256(w.p);
+  if (guided) {
+    l.cfg.x2 = w.take(state);
+    l.cfg.cond2 = w.take((size_t)B * cfg_cond_channels(net) * hw * 4);
+    l.cfg.labels2 = w.take<int32_t>(net->num_classes > 0 ? (size_t)B * 4 : 0);
+  }
+  for (int i = 0; i < stages; ++i) l.rk.k[i] = w.take(state);
+  if (stages > (guided ? 1 : 0)) l.rk.ystage = w.take(state);   // a one-stage guided sampler never forms a stage state (stage 1 reads the state itself)
+  l.end = w.p;
+  return l;
+}
+inline int64_t layout_bytes(const mi355_unet* net, int batch, bool guided, int stages) { return (int64_t)layout(net, batch, guided, stages, 0).end; }
+
+// The layout of a sampler call in the caller's workspace.
+int carve(const mi355_unet* net, int batch, bool guided, int stages, void* workspace, int64_t workspace_bytes, Layout& l) {
+  MI355_REQUIRE(net && workspace, -1, "null argument");
+  MI355_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, -1, "workspace must be 256-byte aligned");
+  l = layout(net, batch, guided, stages, reinterpret_cast<uintptr_t>(workspace));
+  MI355_REQUIRE(workspace_bytes >= (int64_t)(l.end - reinterpret_cast<uintptr_t>(workspace)), -2, "workspace too small");
+  return 0;
+}
+
+// ---- embedding rows of the evaluations -----------------------------------------------------------------
+// The emb_layers outputs of a sampler's network evaluations, whose times t_host[e] (e < n) are all known before the loop.  Where they fit, ONE
+// table holds them: table[e] for an unlabelled sampler; with class labels table[e * K + c] = the rows of evaluation e and class c (three time
+// launches over n rows, one label_emb_linear over n * K), from which every evaluation gathers its images' rows.  Otherwise every evaluation
+// stages its time in sc.t and computes its own rows.
+class EvalEmb {
+ public:
+  // temporary: t_host dies with the calling function, so its copy is waited for, once per call.  A caller's own array (the Euler loop, which is
+  // also recorded into a graph) is not waited for; nor is one whose caller waits itself (SF2M: one wait for its two instances).
+  int init(const mi355_unet* net, const Scratch& sc, const float* t_host, int64_t n, bool labelled, bool temporary, hipStream_t s) {
+    sc_ = &sc; t_host_ = t_host;
+    const int K = labelled ? net->num_classes : 1;
+    block_ = (size_t)K * net->emb_total;
+    // The rule is rows = n * K <= EMB_TABLE_STEPS (K = num_classes with labels, else 1): beyond it the table stays null and every evaluation
+    // computes its own rows.  n is 64-bit so that a caller's product (steps * stages) needs no test of its own: one that left K out would only
+    // keep the row count within an int and within sc.tsteps, which this rule does as well (K >= 1).
+    if (n <= 0 || n * K > EMB_TABLE_STEPS) return 0;
+    MI355_CHECK_HIP(hipMemcpyAsync(sc.tsteps, t_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    float* scratch = sc.embtab + (size_t)EMB_TABLE_STEPS * net->emb_total;
+    if (int rc = labelled ? unet_embedding_rows_labels(net, sc.tsteps, (int)n, nullptr, (int)n * K, K, sc.embtab, scratch, s)
+                          : unet_embedding_table(net, sc.tsteps, (int)n, sc.embtab, scratch, s)) return rc;
+    table_ = sc.embtab;
+    if (temporary) MI355_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+  }
+  const float* table() const { return table_; }
+  // Evaluation e at `batch` images on stream s: run.emb_row = its table block, or a fill_launch of its time into sc.t (*launched: counted).
+  int select(UnetRun& run, size_t e, int batch, hipStream_t s, int64_t* launched = nullptr) const {
+    if (table_) { run.emb_row = table_ + e * block_; return 0; }
+    if (launched) ++*launched;
+    return fill_launch(sc_->t, t_host_[e], batch, s);
+  }
+
+ private:
+  const Scratch* sc_ = nullptr;
+  const float* t_host_ = nullptr;
+  const float* table_ = nullptr;
+  size_t block_ = 0;
+};
+
+// ---- classifier-free guidance: every evaluation is ONE forward at batch 2B (images 0..B-1 conditional, B..2B-1 unconditional) -------------------
+// The one point where a guided loop differs from its plain form: the launch that consumes the network output.  off: the plain kernel; on: its
+// guided form, which combines the two halves with w (or the per-image w_dev) over `per` elements per image.
+struct Guide {
+  bool on = false; float w = 0.f; const float* w_dev = nullptr; int64_t per = 0;
+  int stage(float* out, const float* y0, const float* const* kp, const float* cf, int nk, int64_t n, float* copy_out, uint8_t* u8_out, hipStream_t s) const {
+    return on ? cfg_stage_launch(out, y0, kp, cf, nk, n, w, w_dev, per, 1, copy_out, u8_out, s) : rk_stage_launch(out, y0, kp, cf, nk, n, copy_out, u8_out, s);
+  }
+  int ddim(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s) const {
+    return on ? ddim_cfg_step_launch(x, eps, w, w_dev, per, c_recip, c_recipm1, acp_prev, n, s) : ddim_step_launch(x, eps, c_recip, c_recipm1, acp_prev, n, s);
+  }
+  int ddpm(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float sigma, int philox, uint64_t seed,
+           uint64_t off, int64_t n, hipStream_t s) const {
+    return on ? ddpm_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, coef1, coef2, sigma, philox, seed, off, n, s)
+              : ddpm_step_launch(x, eps, z, c_recip, c_recipm1, coef1, coef2, sigma, philox, seed, off, n, s);
+  }
+};
+// x2 = x | x, cond2 = cond | none_value, labels2 = labels | null_label: built once per call
+int cfg_fill_tail(const CfgTail& t, const float* x, int64_t n, const float* cond, int64_t nc, float none_value, const int32_t* labels, int null_label,
+                  int batch, hipStream_t s) {
+  MI355_CHECK_HIP(hipMemcpyAsync(t.x2, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  MI355_CHECK_HIP(hipMemcpyAsync(t.x2 + n, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (cond) {
+    MI355_CHECK_HIP(hipMemcpyAsync(t.cond2, cond, (size_t)nc * 4, hipMemcpyDeviceToDevice, s));
+    if (int rc = fill_launch(t.cond2 + nc, none_value, nc, s)) return rc;
+  }
+  if (labels) {
+    MI355_CHECK_HIP(hipMemcpyAsync(t.labels2, labels, (size_t)batch * 4, hipMemcpyDeviceToDevice, s));
+    MI355_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(t.labels2 + batch), null_label, (size_t)batch, s));
+  }
+  return 0;
+}
+
+// ---- flow-matching Euler ----------------------------------------------------------------------------------
+// The loop proper: every launch of every step on stream s (the caller's stream, or the handle's capture stream while a graph is recorded).
+// labels: class-conditional steps (with a table: step k's block of the (step, class) table, one gather launch per step).
+int cfm_euler_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, float* x, int x_channels, const float* cond, int cond_channels, float* cdrift,
+                   const float* t_span_host, int n_t, float* traj, int batch, int64_t n, int64_t nc, hipStream_t s, const int32_t* labels = nullptr) {
+  UnetRun run = uniform_t_run();
+  run.labels = labels;
+  for (int k = 0; k + 1 < n_t; ++k) {
+    const float dt = t_span_host[k + 1] - t_span_host[k];
+    int rc;
+    if ((rc = emb.select(run, (size_t)k, batch, s))) return rc;
+    run.euler_x = x; run.euler_dt = dt;   // x += dt * v: in the last conv's epilogue, or as a launch of unet_forward's own behind it
+    if ((rc = unet_forward(net, x, x_channels, cond, cond_channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    if (cdrift && (rc = euler_step_launch(cdrift, cdrift, dt, nc, s))) return rc;
+    if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * n, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  }
+  return 0;
+}
+
+// knobs.sampler_graph: the loop as ONE graph launch.  The graph works on the workspace's resident state (sc.xstate) so that it does not depend on
+// the caller's x / u8 pointers (a fresh tensor per call is the normal use); it does depend on the workspace, the batch, the schedule (dt is a kernel
+// argument, the embedding rows are table addresses) and the condition pointer: those are its key.  The embedding table is rebuilt on every call,
+// outside the graph (the workspace is the caller's: another sampler may have used it in between).
+int cfm_euler_graph(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, float* x, int x_channels, const float* cond, int cond_channels,
+                    const float* t_span_host, int n_t, int batch, int64_t n, void* workspace, hipStream_t s) {
+  uint64_t h = 1469598103934665603ull;
+  for (int k = 0; k < n_t; ++k) { uint32_t b; std::memcpy(&b, &t_span_host[k], 4); h = (h ^ b) * 1099511628211ull; }
+  const uint64_t key[8] = {(uint64_t)reinterpret_cast<uintptr_t>(workspace), (uint64_t)batch, (uint64_t)n_t, h, (uint64_t)reinterpret_cast<uintptr_t>(cond),
+                           (uint64_t)cond_channels, (uint64_t)x_channels, (uint64_t)reinterpret_cast<uintptr_t>(emb.table())};
+  std::lock_guard<std::mutex> lock(net->graph_mu);
+  mi355_unet::SamplerGraph* g = nullptr;
+  for (auto& e : net->graphs) if (e.exec && std::memcmp(e.key, key, sizeof(key)) == 0) { g = &e; break; }
+  if (!g) {
+    if (!net->capture_stream) MI355_CHECK_HIP(hipStreamCreateWithFlags(&net->capture_stream, hipStreamNonBlocking));
+    hipStream_t cs = net->capture_stream;
+    MI355_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    int rc = cfm_euler_loop(net, sc, emb, sc.xstate, x_channels, cond, cond_channels, nullptr, t_span_host, n_t, nullptr, batch, n, 0, cs);
+    hipGraph_t graph = nullptr;
+    hipError_t e = hipStreamEndCapture(cs, &graph);
+    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (e != hipSuccess || !graph) { mi355_set_error(std::string("cfm_euler_sample: graph capture failed: ") + hipGetErrorString(e)); return -3; }
+    hipGraphExec_t exec = nullptr;
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) { mi355_set_error(std::string("cfm_euler_sample: graph instantiation failed: ") + hipGetErrorString(e)); return -3; }
+    constexpr size_t CAP = 4;
+    if (net->graphs.size() < CAP) { net->graphs.emplace_back(); g = &net->graphs.back(); }
+    else {
+      g = &net->graphs[0];
+      for (auto& c : net->graphs) if (c.stamp < g->stamp) g = &c;
+      // the replaced graph may still be running on a stream of the caller's: wait for the device before its nodes are freed (rare: a fifth key)
+      (void)hipDeviceSynchronize();
+      (void)hipGraphExecDestroy(g->exec);
+    }
+    std::memcpy(g->key, key, sizeof(key));
+    g->exec = exec;
+    g->launches = net->last_launches;
+  }
+  g->stamp = ++net->graph_clock;
+  MI355_CHECK_HIP(hipMemcpyAsync(sc.xstate, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  MI355_CHECK_HIP(hipGraphLaunch(g->exec, s));
+  MI355_CHECK_HIP(hipMemcpyAsync(x, sc.xstate, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  net->last_launches = g->launches;
+  return 0;
+}
+
+// ---- fixed-step explicit Runge-Kutta over a general tableau (midpoint, Heun, RK4, ...) ----------------------------------------
+int check_tableau(const char* who, int stages, const float* a_host, const float* b_host, const float* c_host) {
+  const std::string f(who);
+  MI355_REQUIRE(stages >= 1 && stages <= 4, -1, f + ": the tableau must have 1 to 4 stages");
+  MI355_REQUIRE(a_host && b_host && c_host, -1, f + ": null tableau");
+  bool any_b = false;
+  for (int j = 0; j < stages; ++j) any_b = any_b || b_host[j] != 0.f;
+  MI355_REQUIRE(any_b, -1, f + ": the tableau's weights b are all zero");
+  return 0;
+}
+// t + c * dt with the product and the sum each rounded to fp32 (c == 0 / 1: the interval's end points themselves, as mi355/ode.py's dopri5 does)
+float rk_stage_time(float t0, float t1, float c) {
+#pragma clang fp contract(off)
+  if (c == 0.f) return t0;
+  if (c == 1.f) return t1;
+  const float dt = t1 - t0;
+  const float p = c * dt;
+  return t0 + p;
+}
+// the non-zero entries of a tableau row (a stage's a_i., or b) times dt, each with its derivative buffer
+int gather_row(const float* row, int count, float dt, float* const* kbuf, const float** kp, float* cf) {
+  int nk = 0;
+  for (int j = 0; j < count; ++j)
+    if (row[j] != 0.f) { kp[nk] = kbuf[j]; cf[nk] = dt * row[j]; ++nk; }
+  return nk;
+}
+
+// n_steps >= 1 steps of `state` (n elements per half: the whole state, or each half of a guided sampler's x | x), the network evaluated at
+// batch evalB on cond / labels as given.  *step_launches: every launch of the last step (evaluations, stage launches, fill launches).
+int cfm_rk_loop(mi355_unet* net, const Scratch& sc, const RkBufs& rk, const Guide& guide, float* state, int x_channels, const float* cond, int cond_channels,
+                const int32_t* labels, const float* t_span_host, int n_steps, int stages, const float* a_host, const float* b_host, const float* c_host,
+                float* traj, uint8_t* u8_out, int evalB, int64_t n, hipStream_t s, int64_t* step_launches) {
+  // every evaluation time is known in advance: one embedding row (block of num_classes rows with labels) per (step, stage)
+  std::vector<float> te((size_t)n_steps * stages);
+  for (int k = 0; k < n_steps; ++k)
+    for (int i = 0; i < stages; ++i) te[(size_t)k * stages + i] = rk_stage_time(t_span_host[k], t_span_host[k + 1], c_host[i]);
+  EvalEmb emb;
+  if (int rc = emb.init(net, sc, te.data(), (int64_t)n_steps * stages, labels != nullptr, true, s)) return rc;
+  UnetRun run = uniform_t_run();   // no euler_x: the last conv stores v (conv_edge bit 3 stays out of these evaluations)
+  run.labels = labels;
+  const float* kp[4]; float cf[4];
+  int rc = 0;
+  for (int k = 0; k < n_steps; ++k) {
+    const float dt = t_span_host[k + 1] - t_span_host[k];
+    *step_launches = 0;
+    for (int i = 0; i < stages; ++i) {
+      // y_i = state + sum_{j<i} (dt * a_ij) k_j over the non-zero a_ij; none: the stage reads the state itself
+      const float* yin = state;
+      if (const int nk = gather_row(a_host + (size_t)i * stages, i, dt, rk.k, kp, cf)) {
+        if ((rc = guide.stage(rk.ystage, state, kp, cf, nk, n, nullptr, nullptr, s))) return rc;
+        yin = rk.ystage; ++*step_launches;
+      }
+      if ((rc = emb.select(run, (size_t)k * stages + i, evalB, s, step_launches))) return rc;
+      if ((rc = unet_forward(net, yin, x_channels, cond, cond_channels, sc.t, rk.k[i], evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+      *step_launches += net->last_launches;
+    }
+    // the step's update, in place, with the trajectory slot and (last step) the image bytes from the same launch; nk >= 1: an all-zero b was refused
+    const int nk = gather_row(b_host, stages, dt, rk.k, kp, cf);
+    if ((rc = guide.stage(state, state, kp, cf, nk, n, traj ? traj + (size_t)(k + 1) * n : nullptr, k + 1 == n_steps ? u8_out : nullptr, s))) return rc;
+    ++*step_launches;
+  }
+  return 0;
+}
+
+// ---- DDPM / DDIM reverse loop ----------------------------------------------------------------------------------
+std::vector<float> ddpm_times(int Ns) {   // evaluation i = step i: eps_model(xi, i) = network(xi, 1.0*i/Ns)  loss_functions.py:18-19
+  std::vector<float> th((size_t)(Ns > 0 ? Ns : 0));
+  for (int i = 0; i < Ns; ++i) th[i] = (float)i / (float)Ns;
+  return th;
+}
+struct DdpmLoop {
+  const char* who;          // the entry point's name: prefix of the loop's refusals
+  float* state; int evalB;  // the state the steps update (n elements; a guided sampler's first half) and the predictor's batch
+  const float* cond_pred; const int32_t* labels_pred;   // what the net sees on predictor steps (at evalB)
+  const float* cond_corr; const int32_t* labels_corr;   // ... and on corrector steps (at batch): no condition (sampling.py:116 -> none_like, the null label)
+  const float* mask_cond;   // replacement mode: the condition pasted over the state
+  float* mirror;            // guided: the state's second half, refreshed after a step's correctors
+  Guide guide;
+};
+int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const DdpmLoop& a, int channels, const mi355_ddpm_tables* tb,
+              const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch, int64_t n, hipStream_t s) {
+  const int mode = opt->mode, Ns = tb->Ns;
+  const int64_t n_al = (n + 3) / 4 * 4;
+  float* x = a.state;
+  UnetRun run = uniform_t_run(), run_corr = uniform_t_run();
+  run.labels = a.labels_pred;
+  run_corr.labels = a.labels_corr;
+  int rc;
+  int64_t draw = 0;
+  auto next_noise = [&](const float*& zptr, int& philox, uint64_t& off) -> int {
+    if (noise) {
+      MI355_REQUIRE(draw < n_noise_draws, -2, std::string(a.who) + ": injected noise exhausted");
+      zptr = noise + (size_t)draw * n; philox = 0; off = 0;
+    } else { zptr = nullptr; philox = 1; off = (uint64_t)draw * (uint64_t)n_al; }
+    ++draw;
+    return 0;
+  };
+  for (int i = Ns - 1; i >= 0; --i) {
+    if (mode == MI355_DDPM_REPLACEMENT && i < (int)(Ns * opt->start_fraction)) {
+      const float* z = nullptr; int ph = 0; uint64_t off = 0;
+      if (opt->noise_condition && (rc = next_noise(z, ph, off))) return rc;
+      if ((rc = replace_mask_launch(x, a.mask_cond, z, opt->pad_value, opt->noise_condition, tb->sqrt_alphas_cumprod[i],
+                                    tb->sqrt_one_minus_alphas_cumprod[i], ph, opt->seed, off, n, s))) return rc;
+    }
+    if ((rc = emb.select(run, (size_t)i, a.evalB, s))) return rc;
+    run_corr.emb_row = run.emb_row;
+    if ((rc = unet_forward(net, x, channels, a.cond_pred, channels, sc.t, sc.v, a.evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    if (mode == MI355_DDIM) {
+      if ((rc = a.guide.ddim(x, sc.v, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i], n, s))) return rc;
+      continue;
+    }
+    const float* z = nullptr; int ph = 0; uint64_t off = 0;
+    if (i > 0 && (rc = next_noise(z, ph, off))) return rc;
+    const float sigma = expf(0.5f * tb->posterior_log_variance_clipped[i]);
+    if ((rc = a.guide.ddpm(x, sc.v, z, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->posterior_mean_coef1[i],
+                           tb->posterior_mean_coef2[i], sigma, ph, opt->seed, off, n, s))) return rc;
+    for (int c = 0; c < opt->n_corrector; ++c) {   // at batch B (a guided sampler's first half)
+      if ((rc = unet_forward(net, x, channels, a.cond_corr, channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run_corr))) return rc;
+      const float* z2 = nullptr; int ph2 = 0; uint64_t off2 = 0;
+      if ((rc = next_noise(z2, ph2, off2))) return rc;
+      const float dt = (opt->tmax - opt->tmin) / (float)Ns;
+      if ((rc = corrector_step_launch(x, sc.v, z2, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i],
+                                      tb->recip_sqrt_m1_alphas_cumprod[i], dt, opt->delta, ph2, opt->seed, off2, n, s))) return rc;
+    }
+    if (a.mirror && opt->n_corrector > 0) MI355_CHECK_HIP(hipMemcpyAsync(a.mirror, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  }
+  return clip_launch(x, -1.f, 1.f, n, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mi355_unet_workspace_bytes(const mi355_unet* net, int batch) {
+  if (!net || batch <= 0) { mi355_set_error("bad argument"); return -1; }
+  return layout_bytes(net, batch, false, 0);
+}
+
+int64_t mi355_cfm_rk_workspace_bytes(const mi355_unet* net, int batch, int stages) {
+  if (!net || batch <= 0 || stages < 1 || stages > 4) { mi355_set_error("cfm_rk_workspace_bytes: bad argument (1 <= stages <= 4)"); return -1; }
+  return layout_bytes(net, batch, false, stages);
+}
+
+int64_t mi355_cfg_workspace_bytes(const mi355_unet* net, int batch, int stages) {
+  if (!net || batch <= 0 || stages < 1 || stages > 4) { mi355_set_error("cfg_workspace_bytes: bad argument (1 <= stages <= 4)"); return -1; }
+  return layout_bytes(net, batch, true, stages);
+}
+
+int64_t mi355_ddpm_cfg_workspace_bytes(const mi355_unet* net, int batch) {
+  if (!net || batch <= 0) { mi355_set_error("ddpm_cfg_workspace_bytes: bad argument"); return -1; }
+  return layout_bytes(net, batch, true, 0);
+}
+
+int mi355_cfm_euler_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
+                           const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch, void* workspace,
+                           int64_t workspace_bytes, void* stream) {
+  return mi355_cfm_euler_sample_labels(net, x, x_channels, cond, cond_channels, cond_drift, nullptr, t_span_host, n_t, traj, u8_out, batch,
+                                       workspace, workspace_bytes, stream);
+}
+
+int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
+                                  const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && x && t_span_host && n_t >= 1, -1, "cfm_euler_sample: bad argument");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_euler_sample: class labels given to a net built without num_classes");
+  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_euler_sample: the vector field must have the state's channel count");
+  Layout l;
+  if (int rc = carve(net, batch, false, 0, workspace, workspace_bytes, l)) return rc;
+  const Scratch& sc = l.sc;
+  hipStream_t s = S(stream);
+  EvalEmb emb;   // t_span_host is the caller's array: no wait
+  if (int rc = emb.init(net, sc, t_span_host, n_t - 1, labels != nullptr, false, s)) return rc;
+  const int64_t n = (int64_t)batch * x_channels * net->cfg.image_size * net->cfg.image_size;
+  const int64_t nc = (int64_t)batch * cond_channels * net->cfg.image_size * net->cfg.image_size;
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  // cond_drift: the reference integrates the CONCATENATED state [x, con] whose second half has derivative con itself
+  // (mnist/utils_mnist2.py:120-124), so under Euler the condition the model sees is con_{k+1} = con_k + dt * con_k.
+  // The drifting copy lives in the sampler scratch (the caller's tensor is not modified).
+  float* cdrift = nullptr;
+  if (cond && cond_drift) {
+    MI355_REQUIRE(cond_channels <= 32, -2, "cfm_euler_sample: condition has more than 32 channels");
+    cdrift = sc.none;
+    MI355_CHECK_HIP(hipMemcpyAsync(cdrift, cond, (size_t)nc * 4, hipMemcpyDeviceToDevice, s));
+    cond = cdrift;
+  }
+  int rc;
+  if (net->knobs.sampler_graph && emb.table() && !traj && !cdrift && !labels && n_t > 1)
+    rc = cfm_euler_graph(net, sc, emb, x, x_channels, cond, cond_channels, t_span_host, n_t, batch, n, workspace, s);
+  else
+    rc = cfm_euler_loop(net, sc, emb, x, x_channels, cond, cond_channels, cdrift, t_span_host, n_t, traj, batch, n, nc, s, labels);
+  if (rc) return rc;
+  if (u8_out) return quantize_u8_launch(x, u8_out, n, s);
+  return 0;
+}
+
+int mi355_cfm_rk_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, const int32_t* labels,
+                        const float* t_span_host, int n_t, int stages, const float* a_host, const float* b_host, const float* c_host, float* traj,
+                        uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && x && t_span_host && n_t >= 1 && batch > 0, -1, "cfm_rk_sample: bad argument");
+  if (int rc = check_tableau("cfm_rk_sample", stages, a_host, b_host, c_host)) return rc;
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_rk_sample: class labels given to a net built without num_classes");
+  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_rk_sample: the vector field must have the state's channel count");
+  MI355_REQUIRE(workspace_bytes >= mi355_cfm_rk_workspace_bytes(net, batch, stages), -2, "cfm_rk_sample: workspace too small");
+  Layout l;
+  if (int rc = carve(net, batch, false, stages, workspace, workspace_bytes, l)) return rc;
+  hipStream_t s = S(stream);
+  const int64_t n = (int64_t)batch * x_channels * net->cfg.image_size * net->cfg.image_size;
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (n_t == 1) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
+  int64_t step_launches = 0;   // not reported: mi355_unet_get_stats keeps the last evaluation's count
+  return cfm_rk_loop(net, l.sc, l.rk, Guide(), x, x_channels, cond, cond_channels, labels, t_span_host, n_t - 1, stages, a_host, b_host, c_host, traj, u8_out,
+                     batch, n, s, &step_launches);
+}
+
+int mi355_cfm_cfg_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, float none_value, const int32_t* labels,
+                         int null_label, float w, const float* w_dev, const float* t_span_host, int n_t, int stages, const float* a_host,
+                         const float* b_host, const float* c_host, float* traj, uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes,
+                         void* stream) {
+  MI355_REQUIRE(net && x && t_span_host && n_t >= 1 && batch > 0, -1, "cfm_cfg_sample: bad argument");
+  if (int rc = check_tableau("cfm_cfg_sample", stages, a_host, b_host, c_host)) return rc;
+  MI355_REQUIRE(cond || labels, -1, "cfm_cfg_sample: nothing to guide (neither a condition nor class labels)");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_cfg_sample: class labels given to a net built without num_classes");
+  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, "cfm_cfg_sample: null_label must be a class index in [0, num_classes)");
+  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_cfg_sample: the vector field must have the state's channel count");
+  MI355_REQUIRE(!cond || (cond_channels > 0 && (size_t)cond_channels == cfg_cond_channels(net)), -2,
+                "cfm_cfg_sample: the condition must have in_channels - out_channels channels");
+  MI355_REQUIRE(workspace_bytes >= mi355_cfg_workspace_bytes(net, batch, stages), -2, "cfm_cfg_sample: workspace too small");
+  Layout l;
+  if (int rc = carve(net, batch, true, stages, workspace, workspace_bytes, l)) return rc;
+  const CfgTail& tl = l.cfg;
+  hipStream_t s = S(stream);
+  const int64_t hw = (int64_t)net->cfg.image_size * net->cfg.image_size;
+  const int64_t per = (int64_t)x_channels * hw, n = (int64_t)batch * per, nc = (int64_t)batch * cond_channels * hw;
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (n_t == 1) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
+  if (int rc = cfg_fill_tail(tl, x, n, cond, nc, none_value, labels, null_label, batch, s)) return rc;
+  Guide guide; guide.on = true; guide.w = w; guide.w_dev = w_dev; guide.per = per;
+  int64_t step_launches = 0;
+  if (int rc = cfm_rk_loop(net, l.sc, l.rk, guide, tl.x2, x_channels, cond ? tl.cond2 : nullptr, cond_channels, labels ? tl.labels2 : nullptr, t_span_host,
+                           n_t - 1, stages, a_host, b_host, c_host, traj, u8_out, 2 * batch, n, s, &step_launches)) return rc;
+  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  net->last_launches = step_launches;   // mi355_unet_get_stats: every launch of the last step (evaluations and stage launches)
+  return 0;
+}
+
+int mi355_ddpm_sample(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb,
+                      const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
+                      int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && x && tb && opt, -1, "ddpm_sample: null argument");
+  MI355_REQUIRE(channels == net->cfg.out_channels, -2, "ddpm_sample: eps model must output the state's channel count");
+  const int mode = opt->mode;
+  const bool amortized = net->cfg.in_channels == 2 * channels;
+  MI355_REQUIRE(amortized || net->cfg.in_channels == channels, -2, "ddpm_sample: network in_channels must be C or 2C");
+  MI355_REQUIRE(mode != MI355_DDPM_REPLACEMENT || (!amortized && cond), -2, "ddpm_sample: replacement needs an unconditional net and a condition");
+  MI355_REQUIRE(mode != MI355_DDPM_AMORTIZED || (amortized && cond), -2, "ddpm_sample: amortized needs a 2C-input net and a condition");
+  Layout l;
+  if (int rc = carve(net, batch, false, 0, workspace, workspace_bytes, l)) return rc;
+  const Scratch& sc = l.sc;
+  hipStream_t s = S(stream);
+  const int64_t n = (int64_t)batch * channels * net->cfg.image_size * net->cfg.image_size;
+  const std::vector<float> th = ddpm_times(tb->Ns);
+  EvalEmb emb;
+  if (int rc = emb.init(net, sc, th.data(), tb->Ns, false, true, s)) return rc;
+  if (amortized) { if (int rc = fill_launch(sc.none, opt->none_value, n, s)) return rc; }
+  DdpmLoop a = {};
+  a.who = "ddpm_sample"; a.state = x; a.evalB = batch; a.mask_cond = cond;
+  // the net's condition input on predictor steps / on corrector steps (the reference's corrector calls
+  // x0_model without the condition, sampling.py:116 -> none_like)
+  a.cond_pred = !amortized ? nullptr : ((mode == MI355_DDPM_AMORTIZED || (mode == MI355_DDIM && cond)) ? cond : sc.none);
+  a.cond_corr = amortized ? sc.none : nullptr;
+  return ddpm_loop(net, sc, emb, a, channels, tb, opt, noise, n_noise_draws, batch, n, s);
+}
+
+int mi355_ddpm_cfg_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w, const float* w_dev,
+                          const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && x && tb && opt && batch > 0, -1, "ddpm_cfg_sample: bad argument");
+  const int mode = opt->mode;
+  MI355_REQUIRE(mode == MI355_DDPM_AMORTIZED || mode == MI355_DDIM, -1,
+                "ddpm_cfg_sample: guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement modes are refused)");
+  MI355_REQUIRE(cond || labels, -1, "ddpm_cfg_sample: nothing to guide (neither a condition nor class labels)");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "ddpm_cfg_sample: class labels given to a net built without num_classes");
+  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, "ddpm_cfg_sample: null_label must be a class index in [0, num_classes)");
+  MI355_REQUIRE(channels == net->cfg.out_channels, -2, "ddpm_cfg_sample: eps model must output the state's channel count");
+  MI355_REQUIRE(net->cfg.in_channels == 2 * channels && cond, -2, "ddpm_cfg_sample: needs a 2C-input net and a condition");
+  MI355_REQUIRE(workspace_bytes >= mi355_ddpm_cfg_workspace_bytes(net, batch), -2, "ddpm_cfg_sample: workspace too small");
+  Layout l;
+  if (int rc = carve(net, batch, true, 0, workspace, workspace_bytes, l)) return rc;
+  const Scratch& sc = l.sc;
+  const CfgTail& tl = l.cfg;
+  hipStream_t s = S(stream);
+  const int64_t per = (int64_t)channels * net->cfg.image_size * net->cfg.image_size, n = (int64_t)batch * per;
+  const std::vector<float> th = ddpm_times(tb->Ns);
+  EvalEmb emb;   // row i (block of num_classes rows with labels) = step i
+  if (int rc = emb.init(net, sc, th.data(), tb->Ns, labels != nullptr, true, s)) return rc;
+  if (int rc = cfg_fill_tail(tl, x, n, cond, n, opt->none_value, labels, null_label, batch, s)) return rc;
+  DdpmLoop a = {};
+  a.who = "ddpm_cfg_sample"; a.state = tl.x2; a.evalB = 2 * batch; a.mirror = tl.x2 + n;
+  a.cond_pred = tl.cond2; a.labels_pred = labels ? tl.labels2 : nullptr;
+  a.cond_corr = tl.cond2 + n; a.labels_corr = labels ? tl.labels2 + batch : nullptr;
+  a.guide.on = true; a.guide.w = w; a.guide.w_dev = w_dev; a.guide.per = per;
+  if (int rc = ddpm_loop(net, sc, emb, a, channels, tb, opt, noise, n_noise_draws, batch, n, s)) return rc;
+  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// SF2M (torchcfm notebooks' torchsde.sdeint of drift = model + score_model, g = sigma): per step two forwards, each net on its own workspace
+// (its own embedding table: label_emb differs between the nets), then the Euler-Maruyama launch, which also writes the step's output time.
+int mi355_sf2m_euler_sample(mi355_unet* drift, mi355_unet* score, float* x, int channels, const int32_t* labels, const float* t_grid_host,
+                            int n_steps, float sigma, int reverse, const float* dW, uint64_t seed, const int32_t* out_step_host,
+                            const float* out_w_host, int n_out, float* traj, int batch, void* drift_workspace, int64_t drift_workspace_bytes,
+                            void* score_workspace, int64_t score_workspace_bytes, void* stream) {
+  MI355_REQUIRE(drift && score && x && t_grid_host && batch > 0, -1, "sf2m_euler_sample: bad argument");
+  MI355_REQUIRE(n_steps >= 1, -1, "sf2m_euler_sample: the step grid needs at least one step (n_steps >= 1)");
+  MI355_REQUIRE(drift_workspace != score_workspace, -1, "sf2m_euler_sample: the two nets need separate workspaces");
+  const mi355_unet_config &cd = drift->cfg, &cs = score->cfg;
+  MI355_REQUIRE(cd.in_channels == cs.in_channels && cd.out_channels == cs.out_channels && cd.image_size == cs.image_size, -2,
+                "sf2m_euler_sample: the drift and score nets differ in in_channels, out_channels or image_size");
+  MI355_REQUIRE(cd.in_channels == channels && cd.out_channels == channels, -2,
+                "sf2m_euler_sample: both nets must map the state's channel count to itself (in_channels == out_channels == channels)");
+  MI355_REQUIRE(!labels || (drift->num_classes > 0 && score->num_classes > 0), -1,
+                "sf2m_euler_sample: class labels given to a net built without num_classes (both nets must be class-conditional)");
+  MI355_REQUIRE(!labels || drift->num_classes == score->num_classes, -1, "sf2m_euler_sample: the two class-conditional nets differ in num_classes");
+  MI355_REQUIRE(n_out == 0 || (traj && out_step_host && out_w_host), -1, "sf2m_euler_sample: outputs need traj, out_step and out_w");
+  for (int j = 0; j < n_out; ++j)
+    MI355_REQUIRE(out_step_host[j] >= 0 && out_step_host[j] < n_steps && out_w_host[j] >= 0.f && out_w_host[j] <= 1.f, -1,
+                  "sf2m_euler_sample: an output's step must be in [0, n_steps) and its weight in [0, 1]");
+  Layout ld, ls;
+  if (int rc = carve(drift, batch, false, 0, drift_workspace, drift_workspace_bytes, ld)) return rc;
+  if (int rc = carve(score, batch, false, 0, score_workspace, score_workspace_bytes, ls)) return rc;
+  const Scratch &sd = ld.sc, &ss = ls.sc;
+  hipStream_t s = S(stream);
+  const int64_t n = (int64_t)batch * channels * cd.image_size * cd.image_size;
+  const int64_t n_al = (n + 3) / 4 * 4;
+  // the times the nets see: t_k, or 1 - t_k rounded in fp32 (the notebook's reverse SDE evaluates at `1 - t` of the fp32 tensor)
+  std::vector<float> te((size_t)n_steps);
+  for (int k = 0; k < n_steps; ++k) te[k] = reverse ? 1.0f - t_grid_host[k] : t_grid_host[k];
+  EvalEmb ed, es;
+  if (int rc = ed.init(drift, sd, te.data(), n_steps, labels != nullptr, false, s)) return rc;
+  if (int rc = es.init(score, ss, te.data(), n_steps, labels != nullptr, false, s)) return rc;
+  if (ed.table() || es.table()) MI355_CHECK_HIP(hipStreamSynchronize(s));   // `te` is a temporary host buffer: ONE wait for both copies
+  UnetRun rd = uniform_t_run(), rs = uniform_t_run();
+  rd.labels = rs.labels = labels;
+  const float ca = reverse ? -1.f : 1.f;
+  int rc = 0;
+  for (int k = 0; k < n_steps && rc == 0; ++k) {
+    const float dt = t_grid_host[k + 1] - t_grid_host[k];
+    if ((rc = ed.select(rd, (size_t)k, batch, s))) break;
+    if ((rc = es.select(rs, (size_t)k, batch, s))) break;
+    if ((rc = unet_forward(drift, x, channels, nullptr, 0, sd.t, sd.v, batch, sd.unet_ws, sd.unet_bytes, s, rd))) break;
+    if ((rc = unet_forward(score, x, channels, nullptr, 0, ss.t, ss.v, batch, ss.unet_ws, ss.unet_bytes, s, rs))) break;
+    const float* dw = dW ? dW + (size_t)k * n : nullptr;
+    const uint64_t off = dW ? 0 : (uint64_t)k * (uint64_t)n_al;
+    // outputs of this step: w == 0 is x_k itself (copied before the update); the first other one rides in the step launch; further ones
+    // (several output times inside one step) re-run the same deterministic update on a copy of x_k held in the drift net's spare scratch
+    float* fused = nullptr; float fused_w = 0.f;
+    for (int j = 0; j < n_out && rc == 0; ++j) {
+      if (out_step_host[j] != k) continue;
+      float* oj = traj + (size_t)j * n;
+      if (out_w_host[j] == 0.f) { MI355_CHECK_HIP(hipMemcpyAsync(oj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s)); continue; }
+      if (!fused) { fused = oj; fused_w = out_w_host[j]; continue; }
+      MI355_REQUIRE(channels <= 32, -4, "sf2m_euler_sample: several output times inside one step need channels <= 32");
+      MI355_CHECK_HIP(hipMemcpyAsync(sd.none, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      rc = sde_euler_step_launch(sd.none, sd.v, ss.v, ca, 1.f, dt, nullptr, sigma, dw, !dW, seed, off, oj, out_w_host[j], n, s);
+    }
+    if (rc) break;
+    rc = sde_euler_step_launch(x, sd.v, ss.v, ca, 1.f, dt, nullptr, sigma, dw, !dW, seed, off, fused, fused_w, n, s);
+  }
+  return rc;
+}
+
+}  // extern "C"

@@ -29,6 +29,24 @@ def param_inventory(cfg: _lib.UNetConfigC):
     return out
 
 
+def _slices(B: int, mb: int):
+    """(lo, hi, whole) for a batch of B run at most mb images at a time; whole: this slice is the caller's batch itself."""
+    for lo in range(0, B, mb):
+        hi = min(B, lo + mb)
+        yield lo, hi, (lo, hi) == (0, B)
+
+
+def _cut(t, lo: int, hi: int):
+    return None if t is None else t[lo:hi]
+
+
+def _tableau_arrays(tableau):
+    """(a, b, c) -> (stages, ctypes float arrays of a (row-major), b and c)."""
+    a, b, c = tableau
+    stages = len(b)
+    return stages, (C.c_float * (stages * stages))(*[v for row in a for v in row]), (C.c_float * stages)(*b), (C.c_float * stages)(*c)
+
+
 class UNetEngine:
     def __init__(self, cfg_kwargs: dict, state_dict: Dict[str, torch.Tensor], device, precision: str = "bf16", differentiable: bool = False,
                  debug=None):
@@ -175,14 +193,13 @@ class UNetEngine:
         if out is None:
             out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
         host_t = isinstance(t, (int, float))
-        for lo in range(0, B, mb):
-            hi = min(B, lo + mb)
+        for lo, hi, whole in _slices(B, mb):
             x2 = torch.cat((x[lo:hi], x[lo:hi]))
             c2 = torch.cat((cond[lo:hi], torch.full_like(cond[lo:hi], float(none_value)))) if cond is not None else None
             y2 = torch.cat((lab[lo:hi], torch.full_like(lab[lo:hi], nl))) if lab is not None else None
             t2 = t if host_t else torch.cat((t[lo:hi], t[lo:hi]))
             v2 = self.forward(x2, t2, cond=c2, y=y2)
-            default_ops.cfg_combine(v2, w if wt is None else wt[lo:hi], out=out[lo:hi] if (lo, hi) != (0, B) else out)
+            default_ops.cfg_combine(v2, w if wt is None else wt[lo:hi], out=out if whole else out[lo:hi])
         self._fwd_state = None
         return out
 
@@ -196,35 +213,22 @@ class UNetEngine:
         if guidance_scale is not None:
             return self._forward_cfg(x, t, cond, out, y, guidance_scale, null_label, none_value)
         B, Cx, Cc = self._split(x, cond)
-        if y is not None:
-            lab, lab_p = self._labels(y, B)
-            host_t = isinstance(t, (int, float))
-            if not host_t and t.shape != (B,):
-                raise ValueError(f"timesteps must have shape ({B},)")
-            if out is None:
-                out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
-            ws, wsb = self.workspace(B)
-            check(self.L.mi355_unet_forward_labels(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                                   Cc, None if host_t else self._chk(t, "timesteps"), float(t) if host_t else 0.0, lab_p,
-                                                   self._chk(out, "out"), B, ws, wsb, self._stream()), "mi355_unet_forward_labels")
-            self._fwd_state = (B, self._ws.data_ptr())
-            return out
-        if isinstance(t, (int, float)):
-            if out is None:
-                out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
-            ws, wsb = self.workspace(B)
-            check(self.L.mi355_unet_forward_t(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                              Cc, float(t), self._chk(out, "out"), B, ws, wsb, self._stream()), "mi355_unet_forward_t")
-            self._fwd_state = (B, self._ws.data_ptr())
-            return out
-        if t.shape != (B,):
+        lab, lab_p = self._labels(y, B)
+        host_t = isinstance(t, (int, float))
+        if not host_t and t.shape != (B,):
             raise ValueError(f"timesteps must have shape ({B},)")
         if out is None:
             out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
         ws, wsb = self.workspace(B)
-        check(self.L.mi355_unet_forward(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                        Cc, self._chk(t, "timesteps"), self._chk(out, "out"), B, ws, wsb, self._stream()),
-              "mi355_unet_forward")
+        xp, cp = self._chk(x, "x"), self._chk(cond, "condition") if cond is not None else None
+        tp, op = None if host_t else self._chk(t, "timesteps"), self._chk(out, "out")
+        if lab is not None:
+            check(self.L.mi355_unet_forward_labels(self.handle, xp, Cx, cp, Cc, tp, float(t) if host_t else 0.0, lab_p, op, B, ws, wsb, self._stream()),
+                  "mi355_unet_forward_labels")
+        elif host_t:
+            check(self.L.mi355_unet_forward_t(self.handle, xp, Cx, cp, Cc, float(t), op, B, ws, wsb, self._stream()), "mi355_unet_forward_t")
+        else:
+            check(self.L.mi355_unet_forward(self.handle, xp, Cx, cp, Cc, tp, op, B, ws, wsb, self._stream()), "mi355_unet_forward")
         self._fwd_state = (B, self._ws.data_ptr())
         return out
 
@@ -304,6 +308,12 @@ class UNetEngine:
             self._max_batch = max(1, 0xFFFF0000 // (2 * per_image))   # x2: a concat source pair / an in-flight double of the same tensor
         return self._max_batch
 
+    def _traj_u8(self, x: torch.Tensor, n_t: int, keep_traj: bool, want_u8: bool):
+        """The samplers' optional outputs for state x over n_t times: (traj [n_t, *x.shape] fp32 or None, u8 image bytes or None)."""
+        traj = torch.empty((n_t,) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
+        u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
+        return traj, u8
+
     def cfm_cfg(self, x: torch.Tensor, t_span: Sequence[float], method="euler", cond: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
                 guidance_scale=1.0, null_label: Optional[int] = None, none_value: float = -2.0, keep_traj: bool = False, want_u8: bool = False):
         """In-place classifier-free-guided fixed-step integration of x over t_span (mi355_cfm_cfg_sample): the loop of cfm_rk over `method`
@@ -317,29 +327,21 @@ class UNetEngine:
         lab, _ = self._labels(y, B)
         w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
         ts = [float(v) for v in t_span]
-        traj = torch.empty((len(ts),) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
-        u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
-        mb = self.cfg_batch()
-        for lo in range(0, B, mb):
-            hi = min(B, lo + mb)
-            whole = (lo, hi) == (0, B)
+        traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
+        for lo, hi, whole in _slices(B, self.cfg_batch()):
             xs = x if whole else x[lo:hi]
-            tr = traj if whole or traj is None else torch.empty((len(ts),) + tuple(xs.shape), device=self.device, dtype=torch.float32)
-            us = u8 if whole or u8 is None else u8[lo:hi]
-            self._cfm_cfg_call(xs, ts, (a, b, c), cond[lo:hi] if cond is not None else None, lab[lo:hi] if lab is not None else None, nl, w,
-                               wt[lo:hi] if wt is not None else None, float(none_value), tr, us)
+            tr = traj if whole else self._traj_u8(xs, len(ts), keep_traj, False)[0]
+            us = u8 if whole else _cut(u8, lo, hi)
+            self._cfm_cfg_call(xs, ts, (a, b, c), _cut(cond, lo, hi), _cut(lab, lo, hi), nl, w, _cut(wt, lo, hi), float(none_value), tr, us)
             if traj is not None and not whole:
                 traj[:, lo:hi] = tr
         return x, traj, u8
 
     def _cfm_cfg_call(self, x, ts, tableau, cond, lab, null_label, w, wt, none_value, traj, u8):
         """One mi355_cfm_cfg_sample call (a batch within cfg_batch())."""
-        a, b, c = tableau
-        stages = len(b)
+        stages, a_arr, b_arr, c_arr = _tableau_arrays(tableau)
         B, Cx, Cc = self._split(x, cond)
         arr = (C.c_float * len(ts))(*ts)
-        a_arr = (C.c_float * (stages * stages))(*[v for row in a for v in row])
-        b_arr, c_arr = (C.c_float * stages)(*b), (C.c_float * stages)(*c)
         self._fwd_state = None
         ws, wsb = self._workspace_sized("mi355_cfg_workspace_bytes", B, stages)
         check(self.L.mi355_cfm_cfg_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc,
@@ -366,13 +368,10 @@ class UNetEngine:
         B, Cx, Cc = self._split(x, cond)
         lab, lab_p = self._labels(y, B)
         mb = self.max_batch()
+        traj, u8 = self._traj_u8(x, len(t_span), keep_traj, want_u8)
         if B > mb:
-            traj = torch.empty((len(t_span),) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
-            u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
-            for lo in range(0, B, mb):
-                hi = min(B, lo + mb)
-                _, tr, u = self.cfm_euler(x[lo:hi], t_span, cond[lo:hi] if cond is not None else None, keep_traj, want_u8, cond_drift,
-                                          lab[lo:hi] if lab is not None else None)
+            for lo, hi, _ in _slices(B, mb):
+                _, tr, u = self.cfm_euler(x[lo:hi], t_span, _cut(cond, lo, hi), keep_traj, want_u8, cond_drift, _cut(lab, lo, hi))
                 if traj is not None:
                     traj[:, lo:hi] = tr
                 if u8 is not None:
@@ -380,8 +379,6 @@ class UNetEngine:
             return x, traj, u8
         ts = [float(v) for v in t_span]
         arr = (C.c_float * len(ts))(*ts)
-        traj = torch.empty((len(ts),) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
-        u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
         self._fwd_state = None
         ws, wsb = self.workspace(B)
         if lab is not None:
@@ -415,29 +412,22 @@ class UNetEngine:
             return self.cfm_cfg(x, t_span, method, cond, y, guidance_scale, null_label, none_value, keep_traj, want_u8)
         from .ode import resolve_tableau
 
-        a, b, c = resolve_tableau(method)
-        stages = len(b)
+        tableau = resolve_tableau(method)
         B, Cx, Cc = self._split(x, cond)
         lab, lab_p = self._labels(y, B)
         mb = self.max_batch()
         ts = [float(v) for v in t_span]
+        traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
         if B > mb:
-            traj = torch.empty((len(ts),) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
-            u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
-            for lo in range(0, B, mb):
-                hi = min(B, lo + mb)
-                _, tr, u = self.cfm_rk(x[lo:hi], ts, (a, b, c), cond[lo:hi] if cond is not None else None, keep_traj, want_u8,
-                                       lab[lo:hi] if lab is not None else None)
+            for lo, hi, _ in _slices(B, mb):
+                _, tr, u = self.cfm_rk(x[lo:hi], ts, tableau, _cut(cond, lo, hi), keep_traj, want_u8, _cut(lab, lo, hi))
                 if traj is not None:
                     traj[:, lo:hi] = tr
                 if u8 is not None:
                     u8[lo:hi] = u
             return x, traj, u8
         arr = (C.c_float * len(ts))(*ts)
-        a_arr = (C.c_float * (stages * stages))(*[v for row in a for v in row])
-        b_arr, c_arr = (C.c_float * stages)(*b), (C.c_float * stages)(*c)
-        traj = torch.empty((len(ts),) + tuple(x.shape), device=self.device, dtype=torch.float32) if keep_traj else None
-        u8 = torch.empty(x.shape, device=self.device, dtype=torch.uint8) if want_u8 else None
+        stages, a_arr, b_arr, c_arr = _tableau_arrays(tableau)
         self._fwd_state = None
         ws, wsb = self._workspace_rk(B, stages)
         check(self.L.mi355_cfm_rk_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc, lab_p,
@@ -471,19 +461,17 @@ class UNetEngine:
         lab_eng = self if self.num_classes else score_engine   # the net without num_classes is refused by the library (both must be conditional)
         lab, lab_p = lab_eng._labels(y, B)
         mb = min(self.max_batch(), score_engine.max_batch())
+        traj = self._traj_u8(x, len(outs), bool(outs), False)[0]
         if B > mb:
-            traj = torch.empty((len(outs),) + tuple(x.shape), device=self.device, dtype=torch.float32) if outs else None
-            for i, lo in enumerate(range(0, B, mb)):
-                hi = min(B, lo + mb)
+            for i, (lo, hi, _) in enumerate(_slices(B, mb)):
                 xs = x[lo:hi].contiguous()
-                _, tr = self.sf2m_euler(score_engine, xs, ts, sigma, reverse, lab[lo:hi] if lab is not None else None,
+                _, tr = self.sf2m_euler(score_engine, xs, ts, sigma, reverse, _cut(lab, lo, hi),
                                         dW[:, lo:hi].contiguous() if dW is not None else None,
                                         None if dW is not None else (seed + i) % 2 ** 64, outs)
                 x[lo:hi] = xs
                 if traj is not None:
                     traj[:, lo:hi] = tr
             return x, traj
-        traj = torch.empty((len(outs),) + tuple(x.shape), device=self.device, dtype=torch.float32) if outs else None
         grid = (C.c_float * len(ts))(*ts)
         osteps = (C.c_int32 * max(1, len(outs)))(*[k for k, _ in outs])
         ows = (C.c_float * max(1, len(outs)))(*[w for _, w in outs])
@@ -517,13 +505,10 @@ class UNetEngine:
             w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
             if noise is not None and noise.shape[1:] != x.shape:
                 raise ValueError("injected noise must be [n_draws, B, C, H, W]")
-            mb = self.cfg_batch()
-            for i, lo in enumerate(range(0, B, mb)):
-                hi = min(B, lo + mb)
-                whole = (lo, hi) == (0, B)
+            for i, (lo, hi, whole) in enumerate(_slices(B, self.cfg_batch())):
                 xs = x if whole else x[lo:hi].contiguous()
                 self._ddpm_cfg_call(xs, tables, mode, cond if whole or cond is None else cond[lo:hi].contiguous(),
-                                    lab[lo:hi] if lab is not None else None, nl, w, wt[lo:hi] if wt is not None else None,
+                                    _cut(lab, lo, hi), nl, w, _cut(wt, lo, hi),
                                     noise if whole or noise is None else noise[:, lo:hi].contiguous(),
                                     dict(n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, none_value=none_value, seed=(seed + i) % 2 ** 64))
                 if not whole:

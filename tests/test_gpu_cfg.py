@@ -266,6 +266,20 @@ def test_cfm_cfg_identities(mnist_eng):
     eng.check()
 
 
+def test_guided_single_time_is_a_no_op(mnist_eng):
+    """n_t == 1 on the guided entry point, as test_gpu_rk.test_single_time_is_a_no_op on the plain one: no step; traj[0] and the uint8
+    output are still written."""
+    from mi355.ops import default_ops
+
+    x0 = randn(5402, 3, 1, 28, 28).to(DEV)
+    x = x0.clone()
+    _, traj, u8 = mnist_eng.cfm_rk(x, [0.3], "rk4", y=torch.tensor([3, 0, 8], device=DEV), guidance_scale=2.0, null_label=NULL,
+                                   keep_traj=True, want_u8=True)
+    torch.cuda.synchronize()
+    assert torch.equal(x, x0) and traj.shape[0] == 1 and torch.equal(traj[0], x0) and torch.equal(u8, default_ops.quantize_u8(x0))
+    mnist_eng.check()
+
+
 def test_guided_step_launch_counts():
     """stats() after a guided call: every launch of the last step = `stages` evaluations (each a labelled table-path evaluation at 2B)
     plus `stages` stage launches; nothing else (no per-step copy)."""

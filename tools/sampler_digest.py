@@ -1,0 +1,195 @@
+"""Digest of every sampler loop of libmi355_sampler.so on a tiny net with seeded inputs: one line per output tensor with its SHA-256, the
+launch count mi355_unet_get_stats reports after the call, and the values of the four workspace size functions.
+
+The forward is bitwise reproducible (reductions run in a fixed order), so two builds of the library whose host code issues the same launches
+with the same arguments print the same lines.  Run it once per library, each run in its own process:
+
+    MI355_SAMPLER_LIB=/path/to/libmi355_sampler.so python tools/sampler_digest.py --out digest.txt [--save tensors.pt]
+
+and compare the files.  --save keeps the tensors themselves, for a max-abs comparison of a case that is not reproducible run to run.
+--mark launches one torch.flip kernel behind every case (nothing else here uses it), so that a kernel trace of the run
+(rocprofv3 --kernel-trace -- python tools/sampler_digest.py --mark) can be cut into cases and compared case by case.
+"""
+import argparse
+import hashlib
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "image-inpainting-and-super-resolution-using-diffusion-models-and-conditional-flow-matching_amd")
+for p in (REPO, PKG):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+from image_diffusion.sde_diffusion import DDPM  # noqa: E402
+from image_diffusion.unet import UNetModel, param_shapes  # noqa: E402
+from mi355 import _lib  # noqa: E402
+from mi355.synth import randn, synth_state_dict  # noqa: E402
+
+DEV = "cuda:0"
+B, S, NS = 3, 16, 24   # batch, image size, DDPM steps (DDPM(Ns <= 20) has non-finite tables, as the reference does)
+LINES, KEPT, MARK = [], {}, [False]
+
+
+def net(prec, in_ch=3, num_classes=None, seed=0, **debug):
+    """The 16x16 / 32-channel two-level net of smoke(), with 3 output channels."""
+    kw = dict(image_size=S, in_channels=in_ch, model_channels=32, out_channels=3, num_res_blocks=1, attention_resolutions=(2,),
+              channel_mult=(1, 2), num_heads=2, num_classes=num_classes, precision=prec)
+    m = UNetModel(**kw)
+    m.load_state_dict(synth_state_dict(param_shapes(UNetModel(**kw)), 7000 + seed))
+    if debug:
+        m.debug = _lib.debug_config(**debug)
+    return m.to(DEV).engine(DEV)
+
+
+def emit(line):
+    LINES.append(line)
+    print(line, flush=True)
+
+
+def case(prec, name, eng, outs):
+    """outs: name -> tensor or None, the outputs of one sampler call on `eng`."""
+    torch.cuda.synchronize()
+    eng.check()
+    launches = eng.stats(B)["launches"]
+    if MARK[0]:
+        torch.arange(4, device=DEV).flip(0)
+    for k, t in outs.items():
+        if t is None:
+            continue
+        t = t.detach().cpu().contiguous()
+        KEPT[f"{prec}/{name}/{k}"] = t
+        emit(f"{prec} {name} {k} {tuple(t.shape)} sha256={hashlib.sha256(t.numpy().tobytes()).hexdigest()} launches={launches}")
+
+
+def sizes(prec, tag, eng):
+    L = eng.L
+    for b in (1, B, 2 * B):
+        emit(f"{prec} bytes {tag} unet_workspace batch={b} {L.mi355_unet_workspace_bytes(eng.handle, b)}")
+        emit(f"{prec} bytes {tag} ddpm_cfg_workspace batch={b} {L.mi355_ddpm_cfg_workspace_bytes(eng.handle, b)}")
+        for st in (1, 2, 3, 4):
+            emit(f"{prec} bytes {tag} cfm_rk_workspace batch={b} stages={st} {L.mi355_cfm_rk_workspace_bytes(eng.handle, b, st)}")
+            emit(f"{prec} bytes {tag} cfg_workspace batch={b} stages={st} {L.mi355_cfg_workspace_bytes(eng.handle, b, st)}")
+
+
+def span(n):
+    return torch.linspace(0, 1, n + 1).tolist()
+
+
+def sliced(eng, mb, fn):
+    eng.max_batch_override = mb
+    try:
+        return fn()
+    finally:
+        eng.max_batch_override = None
+
+
+def run(prec):
+    u3, u6, l3, l6 = net(prec), net(prec, 6, seed=1), net(prec, 3, 10, seed=2), net(prec, 6, 4, seed=3)
+    score = net(prec, seed=4)
+    for tag, e in (("u3", u3), ("u6", u6), ("l3", l3), ("l6", l6)):
+        sizes(prec, tag, e)
+    x0 = randn(7101, B, 3, S, S).to(DEV)
+    cond = (randn(7102, B, 3, S, S) * 0.5).clamp(-1, 1).to(DEV)
+    cond[:, :, 4:10, 5:11] = -2.0
+    y = torch.tensor([3, 0, 8], device=DEV)
+    y4 = torch.tensor([2, 0, 1], device=DEV)
+    wv = torch.tensor([0.5, 2.0, 3.5], device=DEV)
+    xtu = ("x", "traj", "u8")
+
+    # ---- flow-matching Euler ----
+    case(prec, "euler_plain", u3, dict(zip(xtu, u3.cfm_euler(x0.clone(), span(3), keep_traj=True, want_u8=True))))
+    case(prec, "euler_labels", l3, dict(zip(xtu, l3.cfm_euler(x0.clone(), span(3), keep_traj=True, want_u8=True, y=y))))
+    case(prec, "euler_cond_drift", u6, dict(zip(xtu, u6.cfm_euler(x0.clone(), span(3), cond=cond, keep_traj=True, want_u8=True, cond_drift=True))))
+    g3 = net(prec, sampler_graph=1)
+    for rep in range(2):   # the recording call, then a replay
+        case(prec, f"euler_graph_call{rep}", g3, dict(zip(xtu, g3.cfm_euler(x0.clone(), span(3), want_u8=True))))
+    case(prec, "euler_sliced", u6, dict(zip(xtu, sliced(u6, 2, lambda: u6.cfm_euler(x0.clone(), span(3), cond=cond, keep_traj=True, want_u8=True)))))
+
+    # ---- fixed-step Runge-Kutta: embedding table rows, and beyond EMB_TABLE_STEPS = 1024 rows one row set per evaluation ----
+    for method, n_over in (("midpoint", 513), ("rk4", 257)):
+        case(prec, f"rk_{method}_table", u3, dict(zip(xtu, u3.cfm_rk(x0.clone(), span(3), method, keep_traj=True, want_u8=True))))
+        case(prec, f"rk_{method}_per_eval", u3, dict(zip(xtu, u3.cfm_rk(x0.clone(), span(n_over), method, want_u8=True))))
+    case(prec, "rk_rk4_cond_table", u6, dict(zip(xtu, u6.cfm_rk(x0.clone(), span(3), "rk4", cond=cond, keep_traj=True, want_u8=True))))
+    case(prec, "rk_rk4_labels_table", l3, dict(zip(xtu, l3.cfm_rk(x0.clone(), span(3), "rk4", keep_traj=True, want_u8=True, y=y))))
+    case(prec, "rk_rk4_labels_per_eval", l3, dict(zip(xtu, l3.cfm_rk(x0.clone(), span(26), "rk4", want_u8=True, y=y))))   # 26 * 4 * 10 rows
+    case(prec, "rk_one_time", u3, dict(zip(xtu, u3.cfm_rk(x0.clone(), [0.5], "rk4", keep_traj=True, want_u8=True))))
+    case(prec, "rk_sliced", l3, dict(zip(xtu, sliced(l3, 2, lambda: l3.cfm_rk(x0.clone(), span(3), "heun2", keep_traj=True, want_u8=True, y=y)))))
+
+    # ---- classifier-free guidance of the flow-matching samplers ----
+    for wname, w in (("scalar", 2.0), ("per_image", wv)):
+        case(prec, f"cfg_euler_labels_{wname}", l3,
+             dict(zip(xtu, l3.cfm_euler(x0.clone(), span(3), keep_traj=True, want_u8=True, y=y, guidance_scale=w, null_label=9))))
+        case(prec, f"cfg_rk4_labels_{wname}", l3,
+             dict(zip(xtu, l3.cfm_rk(x0.clone(), span(3), "rk4", keep_traj=True, want_u8=True, y=y, guidance_scale=w, null_label=9))))
+        case(prec, f"cfg_rk4_cond_{wname}", u6,
+             dict(zip(xtu, u6.cfm_rk(x0.clone(), span(3), "rk4", cond=cond, keep_traj=True, want_u8=True, guidance_scale=w))))
+    case(prec, "cfg_rk4_labels_cond", l6,
+         dict(zip(xtu, l6.cfm_rk(x0.clone(), span(3), "rk4", cond=cond, keep_traj=True, want_u8=True, y=y4, guidance_scale=2.0, null_label=3))))
+    case(prec, "cfg_rk4_labels_per_eval", l3, dict(zip(xtu, l3.cfm_rk(x0.clone(), span(26), "rk4", want_u8=True, y=y, guidance_scale=2.0, null_label=9))))
+    case(prec, "cfg_one_time", l3, dict(zip(xtu, l3.cfm_rk(x0.clone(), [0.5], "rk4", keep_traj=True, want_u8=True, y=y, guidance_scale=2.0))))
+    case(prec, "cfg_sliced", l3,
+         dict(zip(xtu, sliced(l3, 2, lambda: l3.cfm_rk(x0.clone(), span(3), "midpoint", keep_traj=True, want_u8=True, y=y, guidance_scale=wv, null_label=9)))))
+
+    # ---- DDPM / DDIM reverse loops: injected noise and device Philox noise ----
+    ddpm = DDPM(NS)
+    T = ddpm.host_tables()
+    xT = randn(7201, B, 3, S, S).to(DEV)
+    draws = torch.stack([randn(7210 + j, B, 3, S, S) for j in range(3 * NS)]).to(DEV)
+    kw = dict(tmin=ddpm.tmin, tmax=ddpm.tmax)
+    for nname, noise in (("injected", draws), ("philox", None)):
+        kn = dict(kw, noise=noise, seed=1234)
+        case(prec, f"ddpm_prior_{nname}", u3, {"x": u3.ddpm_sample(xT.clone(), T, mode=_lib.DDPM_PRIOR, **kn)})
+        case(prec, f"ddpm_replacement_{nname}", u3, {"x": u3.ddpm_sample(xT.clone(), T, mode=_lib.DDPM_REPLACEMENT, cond=cond, **kn)})
+        case(prec, f"ddpm_amortized_corr1_{nname}", u6, {"x": u6.ddpm_sample(xT.clone(), T, mode=_lib.DDPM_AMORTIZED, cond=cond, n_corrector=1, **kn)})
+        case(prec, f"ddpm_ddim_{nname}", u6, {"x": u6.ddpm_sample(xT.clone(), T, mode=_lib.DDIM, cond=cond, **kn)})
+        case(prec, f"ddpm_cfg_amortized_corr1_{nname}", u6,
+             {"x": u6.ddpm_sample(xT.clone(), T, mode=_lib.DDPM_AMORTIZED, cond=cond, n_corrector=1, guidance_scale=2.0, **kn)})
+        case(prec, f"ddpm_cfg_amortized_{nname}", u6, {"x": u6.ddpm_sample(xT.clone(), T, mode=_lib.DDPM_AMORTIZED, cond=cond, guidance_scale=wv, **kn)})
+        case(prec, f"ddpm_cfg_ddim_{nname}", u6, {"x": u6.ddpm_sample(xT.clone(), T, mode=_lib.DDIM, cond=cond, guidance_scale=2.0, **kn)})
+        case(prec, f"ddpm_cfg_labels_cond_corr1_{nname}", l6,
+             {"x": l6.ddpm_sample(xT.clone(), T, mode=_lib.DDPM_AMORTIZED, cond=cond, n_corrector=1, guidance_scale=2.0, y=y4, null_label=3, **kn)})
+        case(prec, f"ddpm_cfg_sliced_{nname}", u6,
+             {"x": sliced(u6, 2, lambda: u6.ddpm_sample(xT.clone(), T, mode=_lib.DDPM_AMORTIZED, cond=cond, n_corrector=1, guidance_scale=2.0, **kn))})
+
+    # beyond the embedding table: Ns > 1024 steps, and Ns * num_classes > 1024 rows on the guided labelled path
+    big, big_l = DDPM(1030), DDPM(260)
+    case(prec, "ddpm_prior_per_eval", u3, {"x": u3.ddpm_sample(xT.clone(), big.host_tables(), mode=_lib.DDPM_PRIOR, tmin=big.tmin, tmax=big.tmax, seed=1234)})
+    case(prec, "ddpm_cfg_labels_cond_per_eval", l6,
+         {"x": l6.ddpm_sample(xT.clone(), big_l.host_tables(), mode=_lib.DDPM_AMORTIZED, cond=cond, guidance_scale=2.0, y=y4, null_label=3,
+                              tmin=big_l.tmin, tmax=big_l.tmax, seed=1234)})
+
+    # ---- SF2M Euler-Maruyama: two nets, two output times inside step 1 ----
+    grid = span(3)
+    dW = torch.stack([randn(7300 + j, B, 3, S, S) * 0.5 for j in range(3)]).to(DEV)
+    outs = [(0, 0.0), (1, 0.25), (1, 0.75), (2, 1.0)]
+    for rev in (False, True):
+        for nname, nk in (("injected", dict(dW=dW)), ("philox", dict(seed=77))):
+            case(prec, f"sf2m_{'reverse' if rev else 'forward'}_{nname}", u3,
+                 dict(zip(("x", "traj"), u3.sf2m_euler(score, x0.clone(), grid, 0.3, reverse=rev, outputs=outs, **nk))))
+    case(prec, "sf2m_per_eval", u3, {"x": u3.sf2m_euler(score, x0.clone(), span(1030), 0.3, seed=77)[0]})
+    case(prec, "sf2m_sliced", u3, dict(zip(("x", "traj"), sliced(u3, 2, lambda: u3.sf2m_euler(score, x0.clone(), grid, 0.3, outputs=outs, seed=77)))))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--out", help="also write the lines to this file")
+    ap.add_argument("--save", help="keep every output tensor in this torch file")
+    ap.add_argument("--mark", action="store_true", help="one torch.flip launch behind every case: the cut marks of a kernel trace")
+    ap.add_argument("--precisions", default="fp32,bf16")
+    a = ap.parse_args()
+    MARK[0] = a.mark
+    emit(f"mi355_version {_lib.lib().mi355_version()}")
+    for prec in a.precisions.split(","):
+        run(prec)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(LINES) + "\n")
+    if a.save:
+        torch.save(KEPT, a.save)
+
+
+if __name__ == "__main__":
+    main()
