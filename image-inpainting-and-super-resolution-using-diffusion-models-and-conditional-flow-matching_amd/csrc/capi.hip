@@ -118,8 +118,8 @@ int mi355_unet_read_tensor(const mi355_unet* net, int tensor, int gradient, floa
   MI355_REQUIRE(net && out && workspace, -1, "read_tensor: null argument");
   MI355_REQUIRE(tensor >= 0 && tensor < (int)net->tensors.size(), -1, "read_tensor: tensor index out of range");
   MI355_REQUIRE(!gradient || net->cfg.differentiable, -4, "read_tensor: gradients exist in differentiable plans only");
-  const WsLayout l = unet_ws_layout(net, batch);
-  MI355_REQUIRE((int64_t)l.total <= workspace_bytes, -2, "read_tensor: workspace too small");
+  const WsView v(net, workspace, batch);
+  MI355_REQUIRE((int64_t)v.l.total <= workspace_bytes, -2, "read_tensor: workspace too small");
   const PlanTensor& t = net->tensors[tensor];
   const int tstate = (!gradient && (size_t)tensor < net->tensor_state_n) ? (int)net->tensor_state[tensor].load(std::memory_order_relaxed) : 0;
   if (tstate) {
@@ -131,9 +131,7 @@ int mi355_unet_read_tensor(const mi355_unet* net, int tensor, int gradient, floa
                           "create the handle with debug.gn_epilogue = 0 (or 1) to inspect it");
     return MI355_ERR_UNSUPPORTED;
   }
-  const int esz = net->cfg.dtype == 0 ? 4 : 2;
-  const char* p = reinterpret_cast<const char*>(workspace) + (gradient ? l.grads : l.arena) + t.offset_per_image * (size_t)batch * esz;
-  return unpack_nchw_launch(net->cfg.dtype, p, batch, t.H * t.W, t.C, out, S(stream));
+  return unpack_nchw_launch(net->cfg.dtype, gradient ? v.grad(tensor) : v.tensor(tensor), batch, t.H * t.W, t.C, out, S(stream));
 }
 
 int mi355_unet_get_stats(const mi355_unet* net, int batch, mi355_unet_stats* out) {

@@ -716,8 +716,26 @@ static inline uint16_t f2bf(float f) {
 }
 static inline float bf2f(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
 
+// A packed weight image is a sequence of [BN rows][64 B] tiles, one per (output-channel tile, K chunk, tap): a row holds one chunk of CH input
+// channels as four 16-byte quads of V elements, quad q at slot q ^ ((row >> 1) & 3) (the swizzle the kernels' LDS reads undo, brow above).
+namespace {
+struct PackTile {
+  int dtype, BN, CH, V, esz;
+  PackTile(int dtype_, int Cout) : dtype(dtype_), BN(conv_tile_n(Cout)), CH(chunk_of(dtype_)), V(CH / 4), esz(dtype_ == 0 ? 4 : 2) {}
+  // element kl of the chunk, output channel `row` of the tile: v rounded to the image's element type
+  void store(char* tile, int row, int kl, float v) const {
+    const int q = kl / V, e = kl % V;
+    char* dstp = tile + row * 64 + 16 * (q ^ ((row >> 1) & 3)) + e * esz;
+    if (dtype == DT_F32) memcpy(dstp, &v, 4);
+    else if (dtype == DT_F16) { const _Float16 h = (_Float16)v; memcpy(dstp, &h, 2); }   // RNE
+    else { uint16_t h = f2bf(v); memcpy(dstp, &h, 2); }
+  }
+};
+}  // namespace
+
 void conv_pack_weights(int dtype, const float* w, int Cout, int Cin, int ks, void* dst, int split) {
-  const int BN = conv_tile_n(Cout), CH = chunk_of(dtype), V = CH / 4, esz = dtype == 0 ? 4 : 2;
+  const PackTile pk(dtype, Cout);
+  const int BN = pk.BN, CH = pk.CH;
   const int nt = (Cout + BN - 1) / BN, nr = (Cin + CH - 1) / CH, nc = nr * (split && dtype == 1 ? 2 : 1), ntaps = ks * ks;
   char* out = reinterpret_cast<char*>(dst);
   memset(out, 0, conv_packed_weight_bytes(dtype, Cout, Cin, ks, split));
@@ -734,11 +752,7 @@ void conv_pack_weights(int dtype, const float* w, int Cout, int Cin, int ks, voi
             if (ci >= Cin) break;
             float v = w[((size_t)co * Cin + ci) * ntaps + tap];
             if (lo) v = v - bf2f(f2bf(v));
-            const int q = kl / V, e = kl % V;
-            char* dstp = tile + row * 64 + 16 * (q ^ ((row >> 1) & 3)) + e * esz;
-            if (dtype == DT_F32) memcpy(dstp, &v, 4);
-            else if (dtype == DT_F16) { const _Float16 h = (_Float16)v; memcpy(dstp, &h, 2); }   // RNE
-            else { uint16_t h = f2bf(v); memcpy(dstp, &h, 2); }
+            pk.store(tile, row, kl, v);
           }
         }
       }
@@ -754,7 +768,8 @@ size_t conv_packed_weight_bytes_up2(int dtype, int Cout, int Cin) {
   return nt * 4 * nc * 4 * (size_t)BN * 64;
 }
 void conv_pack_weights_up2(int dtype, const float* w, int Cout, int Cin, void* dst) {
-  const int BN = conv_tile_n(Cout), CH = chunk_of(dtype), V = CH / 4, esz = dtype == 0 ? 4 : 2;
+  const PackTile pk(dtype, Cout);
+  const int BN = pk.BN, CH = pk.CH;
   const int nt = (Cout + BN - 1) / BN, nc = (Cin + CH - 1) / CH;
   char* out = reinterpret_cast<char*>(dst);
   memset(out, 0, conv_packed_weight_bytes_up2(dtype, Cout, Cin));
@@ -775,11 +790,7 @@ void conv_pack_weights_up2(int dtype, const float* w, int Cout, int Cin, void* d
               for (int ky = 0; ky < 3; ++ky)
                 for (int kx = 0; kx < 3; ++kx)
                   if ((pa + ky + 1) / 2 == pa + ty && (pb + kx + 1) / 2 == pb + tx) v += w9[ky * 3 + kx];
-              const int q = kl / V, e = kl % V;
-              char* dstp = tile + row * 64 + 16 * (q ^ ((row >> 1) & 3)) + e * esz;
-              if (dtype == DT_F32) memcpy(dstp, &v, 4);
-              else if (dtype == DT_F16) { const _Float16 h = (_Float16)v; memcpy(dstp, &h, 2); }   // RNE
-              else { uint16_t h = f2bf(v); memcpy(dstp, &h, 2); }
+              pk.store(tile, row, kl, v);
             }
           }
         }

@@ -20,26 +20,18 @@ int unet_backward(const mi355_unet* net, const float* grad_out, float* grad_x, i
   MI355_REQUIRE(net && grad_out && grad_x && workspace, -1, "unet_vjp: null argument");
   MI355_REQUIRE(net->cfg.differentiable, -4, "unet_vjp: the handle was not created with cfg.differentiable = 1");
   MI355_REQUIRE(B > 0 && Cx > 0 && Cx <= net->cfg.in_channels, -2, "unet_vjp: bad batch / channel count");
-  const WsLayout l = unet_ws_layout(net, B);
-  MI355_REQUIRE((int64_t)l.total <= workspace_bytes, -2, "unet_vjp: workspace too small");
-  const int dtype = net->cfg.dtype, esz = dtype == 0 ? 4 : 2, CH = dtype == 0 ? 16 : 32;
-  char* ws = reinterpret_cast<char*>(workspace);
+  const WsView v(net, workspace, B);
+  MI355_REQUIRE((int64_t)v.l.total <= workspace_bytes, -2, "unet_vjp: workspace too small");
+  const int dtype = net->cfg.dtype, CH = dtype == 0 ? 16 : 32;
   const char* W = net->dev_weights;
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  auto TP = [&](int id) -> void* { return ws + l.arena + net->tensors[id].offset_per_image * (size_t)B * esz; };
-  auto GP = [&](int id) -> void* { return ws + l.grads + net->tensors[id].offset_per_image * (size_t)B * esz; };
-  void* du = ws + l.du; void* tmp = ws + l.tmp; void* zbuf = ws + l.z; void* dyp = ws + l.dy;
+  void* du = v.at(v.l.du); void* tmp = v.at(v.l.tmp); void* zbuf = v.at(v.l.z); void* dyp = v.at(v.l.dy);
   std::vector<char> written(net->tensors.size(), 0);
   int rc;
-  auto site = [&](int k, const float*& a, const float*& b, const float*& mean, const float*& rstd) {
-    const float* sp = F(l.sites) + net->site_off[k] * (size_t)B;
-    const size_t Cs = (size_t)net->site_C[k];
-    a = sp; b = sp + (size_t)B * Cs; mean = sp + (size_t)2 * B * Cs; rstd = mean + (size_t)B * 32;
-  };
+  auto site = [&](int k, GnBwdDesc& g) { const WsView::Site s = v.site(k); g.a = s.a; g.b = s.b; g.mean = s.mean; g.rstd = s.rstd; };
   // grad[id] (+)= gather(src)
   auto accumulate = [&](int id, const void* src, int Hs, int Ws, int cs, int coff, int mode, float scale) -> int {
     const PlanTensor& t = net->tensors[id];
-    const int r = grad_gather_launch(dtype, GP(id), src, B, t.H, t.W, t.C, Hs, Ws, cs, coff, mode, written[id], scale, stream);
+    const int r = grad_gather_launch(dtype, v.grad(id), src, B, t.H, t.W, t.C, Hs, Ws, cs, coff, mode, written[id], scale, stream);
     written[id] = 1;
     return r;
   };
@@ -58,7 +50,7 @@ int unet_backward(const mi355_unet* net, const float* grad_out, float* grad_x, i
       } else {
         MI355_REQUIRE(written[op.dst], -4, "unet_vjp: a conv output has no gradient (plan order)");
         const PlanTensor& d = net->tensors[op.dst];
-        G = GP(op.dst); Hg = d.H; Wg = d.W; Cg = d.C;
+        G = v.grad(op.dst); Hg = d.H; Wg = d.W; Cg = d.C;
       }
       // ---- residual operand ----
       if (op.res >= 0) {
@@ -85,11 +77,11 @@ int unet_backward(const mi355_unet* net, const float* grad_out, float* grad_x, i
           if ((rc = grad_gather_launch(dtype, tmp, du, B, s0.H, s0.W, op.cin_pad, Hd, Wd, op.cin_pad, 0, GATHER_POOL, 0, 1.0f, stream))) return rc;
           dU = tmp;
         }
-        GnBwdDesc g; g.dtype = dtype; g.x0 = TP(op.src0); g.C0 = s0.C; g.x1 = op.src1 >= 0 ? TP(op.src1) : nullptr; g.C1 = C1;
+        GnBwdDesc g; g.dtype = dtype; g.x0 = v.tensor(op.src0); g.C0 = s0.C; g.x1 = op.src1 >= 0 ? v.tensor(op.src1) : nullptr; g.C1 = C1;
         g.du = dU; g.du_stride = cs; g.N = B; g.HW = s0.H * s0.W; g.silu = op.pro_silu;
-        site(op.gn_site, g.a, g.b, g.mean, g.rstd);
-        g.g0 = GP(op.src0); g.acc0 = written[op.src0];
-        if (op.src1 >= 0) { g.g1 = GP(op.src1); g.acc1 = written[op.src1]; }
+        site(op.gn_site, g);
+        g.g0 = v.grad(op.src0); g.acc0 = written[op.src0];
+        if (op.src1 >= 0) { g.g1 = v.grad(op.src1); g.acc1 = written[op.src1]; }
         if ((rc = gn_silu_bwd_launch(g, stream))) return rc;
         written[op.src0] = 1;
         if (op.src1 >= 0) written[op.src1] = 1;
@@ -100,27 +92,27 @@ int unet_backward(const mi355_unet* net, const float* grad_out, float* grad_x, i
       }
     } else if (op.kind == OP_ATTN) {
       MI355_REQUIRE(written[op.dst], -4, "unet_vjp: an attention output has no gradient (plan order)");
-      AttnBwdDesc a; a.dtype = dtype; a.qkv = TP(op.src0); a.a = TP(op.dst); a.da = GP(op.dst); a.dqkv = GP(op.src0);
+      AttnBwdDesc a; a.dtype = dtype; a.qkv = v.tensor(op.src0); a.a = v.tensor(op.dst); a.da = v.grad(op.dst); a.dqkv = v.grad(op.src0);
       a.N = B; a.T = s0.H * s0.W; a.heads = op.heads; a.ch = op.ch; a.new_order = net->cfg.use_new_attention_order;
-      a.L = F(l.ld); a.D = a.L + (size_t)B * op.heads * a.T;
+      a.L = v.f32(v.l.ld); a.D = a.L + (size_t)B * op.heads * a.T;
       if ((rc = attention_bwd_launch(a, stream))) return rc;
       written[op.src0] = 1;   // q, k and v parts are all written: the qkv tensor has this one consumer
     } else if (op.kind == OP_POOLAFF) {
       // forward: out = avgpool2(silu(a x + b)): each input position got 1/4 of its block's gradient
       MI355_REQUIRE(written[op.dst], -4, "unet_vjp: a pooled tensor has no gradient (plan order)");
       const PlanTensor& d = net->tensors[op.dst];
-      if ((rc = grad_gather_launch(dtype, tmp, GP(op.dst), B, s0.H, s0.W, s0.C, d.H, d.W, d.C, 0, GATHER_UP, 0, 0.25f, stream))) return rc;
-      GnBwdDesc g; g.dtype = dtype; g.x0 = TP(op.src0); g.C0 = s0.C; g.du = tmp; g.du_stride = s0.C; g.N = B; g.HW = s0.H * s0.W;
+      if ((rc = grad_gather_launch(dtype, tmp, v.grad(op.dst), B, s0.H, s0.W, s0.C, d.H, d.W, d.C, 0, GATHER_UP, 0, 0.25f, stream))) return rc;
+      GnBwdDesc g; g.dtype = dtype; g.x0 = v.tensor(op.src0); g.C0 = s0.C; g.du = tmp; g.du_stride = s0.C; g.N = B; g.HW = s0.H * s0.W;
       g.silu = op.pro_silu;
-      site(op.gn_site, g.a, g.b, g.mean, g.rstd);
-      g.g0 = GP(op.src0); g.acc0 = written[op.src0];
+      site(op.gn_site, g);
+      g.g0 = v.grad(op.src0); g.acc0 = written[op.src0];
       if ((rc = gn_silu_bwd_launch(g, stream))) return rc;
       written[op.src0] = 1;
     } else if (op.kind == OP_RESAMPLE) {
       MI355_REQUIRE(written[op.dst], -4, "unet_vjp: a resampled tensor has no gradient (plan order)");
       const PlanTensor& d = net->tensors[op.dst];
-      if (op.mode == CONV_POOL2) rc = accumulate(op.src0, GP(op.dst), d.H, d.W, d.C, 0, GATHER_UP, 0.25f);
-      else rc = accumulate(op.src0, GP(op.dst), d.H, d.W, d.C, 0, GATHER_POOL, 1.0f);
+      if (op.mode == CONV_POOL2) rc = accumulate(op.src0, v.grad(op.dst), d.H, d.W, d.C, 0, GATHER_UP, 0.25f);
+      else rc = accumulate(op.src0, v.grad(op.dst), d.H, d.W, d.C, 0, GATHER_POOL, 1.0f);
       if (rc) return rc;
     } else {
       mi355_set_error("unet_vjp: op kind without an adjoint in a differentiable plan");
@@ -128,5 +120,5 @@ int unet_backward(const mi355_unet* net, const float* grad_out, float* grad_x, i
     }
   }
   MI355_REQUIRE(written[net->in_tensor], -4, "unet_vjp: the input received no gradient");
-  return unpack_channels_launch(dtype, GP(net->in_tensor), B, S * S, net->in_pad, 0, Cx, grad_x, stream);
+  return unpack_channels_launch(dtype, v.grad(net->in_tensor), B, S * S, net->in_pad, 0, Cx, grad_x, stream);
 }

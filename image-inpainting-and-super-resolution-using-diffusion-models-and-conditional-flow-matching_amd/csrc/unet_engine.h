@@ -1,6 +1,7 @@
 // U-Net layer plan + executor (host C++).  See unet_engine.hip.
 #pragma once
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "../../include/mi355_sampler.h"
@@ -120,6 +121,24 @@ int unet_status(const mi355_unet* net, int clear);   // 0 or MI355_ERR_TIMEOUT (
 int64_t unet_workspace_bytes(const mi355_unet* net, int batch);
 struct WsLayout { size_t temb, emb1, emb2, embp, gna, gnb, stats, sites, arena, grads, du, tmp, z, dy, ld, total; };
 WsLayout unet_ws_layout(const mi355_unet* net, int B);
+// One call's view of a workspace: the regions of unet_ws_layout at batch B as pointers (forward, backward and mi355_unet_read_tensor).
+struct WsView {
+  const mi355_unet* net; char* ws; WsLayout l; size_t B, esz;
+  WsView(const mi355_unet* n, void* workspace, int batch)
+      : net(n), ws(reinterpret_cast<char*>(workspace)), l(unet_ws_layout(n, batch)), B((size_t)batch), esz(n->cfg.dtype == 0 ? 4 : 2) {}
+  float* f32(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+  void* at(size_t off) const { return ws + off; }
+  void* tensor(int id) const { return id < 0 ? nullptr : ws + l.arena + net->tensors[id].offset_per_image * B * esz; }   // activation (NHWC)
+  void* grad(int id) const { return id < 0 ? nullptr : ws + l.grads + net->tensors[id].offset_per_image * B * esz; }     // its gradient (differentiable plans)
+  float* stats(int id) const { return f32(l.stats) + net->tensors[id].stats_off_per_image * B; }   // partial GroupNorm sums its producer leaves
+  // differentiable plans: GroupNorm site k's own a[B][C] | b[B][C] | mean[B][32] | rstd[B][32]
+  struct Site { float *a, *b, *mean, *rstd; };
+  Site site(int k) const {
+    float* sp = f32(l.sites) + net->site_off[k] * B;
+    const size_t BC = B * (size_t)net->site_C[k];
+    return {sp, sp + BC, sp + 2 * BC, sp + 2 * BC + B * 32};
+  }
+};
 // (d out / d x)^T grad_out of the last unet_forward on this workspace (differentiable plans only; unet_backward.hip)
 int unet_backward(const mi355_unet* net, const float* grad_out, float* grad_x, int Cx, int batch, void* workspace, int64_t workspace_bytes,
                   hipStream_t stream);
@@ -132,3 +151,27 @@ int unet_embedding_rows_labels(const mi355_unet* net, const float* t_dev, int n_
                                float* scratch, hipStream_t stream);
 int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* cond, int Cc, const float* t, float* out, int batch,
                  void* workspace, int64_t workspace_bytes, hipStream_t stream, const UnetRun& run = UnetRun());
+
+// ---- a forward, resolved ---------------------------------------------------------------------------------------------------------------
+// unet_forward = unet_resolve, then issue.  unet_resolve is pure host code: no HIP call, no handle state touched; it walks the plan once and
+// says what each plan op becomes in THIS forward (batch, knobs, run options) with the descriptor it is launched with.  The result is a local
+// value of the call: nothing of it is kept on the handle.
+struct GnAbsorbed {};    // GroupNorm site applied by its producers' epilogues: nothing launched
+struct ConvCarried {};   // 1x1 skip conv riding in its ResBlock's second conv (the next step): nothing launched, its tensor never written
+struct ConvStep { ConvDesc c; ConvRoute rt; };
+struct PoolAffStep { int dtype; const void* in; const float* a; const float* b; int silu; void* out; int N, H, W, C; };   // affine_pool_launch's arguments
+struct ResampleStep { int dtype; const void* in; void* out; int N, H, W, C, mode; };                                      // resample_launch's
+// GnFinDesc: (a, b) finalized from the producers' partial sums; GnDesc: the statistics (/ apply) pass
+using ForwardStep = std::variant<GnAbsorbed, GnFinDesc, GnDesc, ConvStep, ConvCarried, AttnDesc, AttnFusedDesc, PoolAffStep, ResampleStep>;
+enum EmbPath { EMB_ROW = 0, EMB_GATHER, EMB_LABELS, EMB_TIME };   // the caller's row as it is | rows gathered by label | computed from t and labels | from t
+struct ResolvedForward {
+  int emb = EMB_TIME, Be = 0, estride = 0; const float* embp = nullptr;   // embedding path, its rows (Be times) and their stride for the consumers
+  bool pack = true;                 // false: the first conv reads the caller's NCHW tensors itself (no pack_nhwc launch)
+  std::vector<ForwardStep> steps;   // one per plan op, in plan order
+  bool euler_in_conv = false;       // the last conv's epilogue applies UnetRun's Euler update
+};
+int unet_resolve(const WsView& v, const float* x, int Cx, const float* cond, int Cc, float* out, const UnetRun& run, ResolvedForward* f);
+inline bool unet_step_launches(const ForwardStep& s) { return !std::holds_alternative<GnAbsorbed>(s) && !std::holds_alternative<ConvCarried>(s); }
+int64_t unet_launch_count(const ResolvedForward& f);   // launches the issue pass makes (the sampler's Euler step not counted)
+// the plan alone, no host parameters and no weight image: the bytes that image would take, or < 0
+int64_t unet_plan_dry(const mi355_unet_config& cfg, mi355_unet* net);

@@ -17,6 +17,74 @@ namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The blocks of UNetModel.__init__ (unet.py:564-706) in construction order = state_dict order.  The input_blocks.N / output_blocks.N.j numbering,
+// the attention test and the stack of skip channel counts live here and nowhere else: unet_enumerate_params names the parameters of this
+// list, Walker::walk plans its ops.
+enum BlockKind { BLK_CONV_IN, BLK_RES, BLK_ATTN, BLK_RESAMPLE_CONV, BLK_RESAMPLE, BLK_OUT };
+struct Block {
+  std::string prefix;   // of its state_dict entries (BLK_RESAMPLE has none; BLK_OUT: "out", i.e. out.0 and out.2)
+  int kind, cin, cout;  // cin of a popping ResBlock counts the skip's channels too (unet.py:650); BLK_OUT: cin = the first conv's output channels
+  int dir = 0;          // BLK_RES: ResBlock(up) > 0, ResBlock(down) < 0; BLK_RESAMPLE_CONV: Upsample.conv > 0, Downsample.op < 0; BLK_RESAMPLE likewise
+  bool upsample = false;   // BLK_ATTN on the up path (num_heads_upsample, unet.py:370-378)
+  bool push = false, pop = false;   // its output goes onto the skip stack / its input is cat([h, hs.pop()])
+};
+std::vector<Block> unet_blocks(const mi355_unet_config& cfg) {
+  const int mc = cfg.model_channels, nl = cfg.n_channel_mult;
+  auto has_attn = [&](int ds) { for (int i = 0; i < cfg.n_attention_ds; ++i) if (cfg.attention_ds[i] == ds) return true; return false; };
+  std::vector<Block> out;
+  auto add = [&](const std::string& prefix, int kind, int cin, int cout, int dir = 0) -> Block& {
+    Block b; b.prefix = prefix; b.kind = kind; b.cin = cin; b.cout = cout; b.dir = dir;
+    out.push_back(b);
+    return out.back();
+  };
+  // a level change: ResBlock(up/down), Downsample.op / Upsample.conv, or the plain pool / nearest-x2 (which has no parameters)
+  auto resample = [&](const std::string& p, const char* conv_name, int ch, int dir) -> Block& {
+    if (cfg.resblock_updown) return add(p, BLK_RES, ch, ch, dir);
+    if (cfg.conv_resample) return add(p + conv_name, BLK_RESAMPLE_CONV, ch, ch, dir);
+    return add(p, BLK_RESAMPLE, ch, ch, dir);
+  };
+  int ch = cfg.channel_mult[0] * mc;
+  const int input_ch = ch;
+  add("input_blocks.0.0", BLK_CONV_IN, cfg.in_channels, ch).push = true;
+  std::vector<int> chans{ch};
+  int ds = 1, idx = 1;
+  for (int level = 0; level < nl; ++level) {
+    const int mult = cfg.channel_mult[level];
+    for (int r = 0; r < cfg.num_res_blocks; ++r, ++idx) {
+      const std::string p = "input_blocks." + std::to_string(idx);
+      add(p + ".0", BLK_RES, ch, mult * mc);
+      ch = mult * mc;
+      if (has_attn(ds)) add(p + ".1", BLK_ATTN, ch, ch);
+      out.back().push = true;
+      chans.push_back(ch);
+    }
+    if (level != nl - 1) {
+      resample("input_blocks." + std::to_string(idx) + ".0", ".op", ch, -1).push = true;
+      chans.push_back(ch);
+      ds *= 2; ++idx;
+    }
+  }
+  add("middle_block.0", BLK_RES, ch, ch); add("middle_block.1", BLK_ATTN, ch, ch); add("middle_block.2", BLK_RES, ch, ch);
+  idx = 0;
+  for (int level = nl - 1; level >= 0; --level) {
+    const int mult = cfg.channel_mult[level];
+    for (int i = 0; i <= cfg.num_res_blocks; ++i, ++idx) {
+      const std::string p = "output_blocks." + std::to_string(idx);
+      const int ich = chans.back(); chans.pop_back();
+      add(p + ".0", BLK_RES, ch + ich, mc * mult).pop = true;
+      ch = mc * mult;
+      int j = 1;
+      if (has_attn(ds)) { add(p + "." + std::to_string(j), BLK_ATTN, ch, ch).upsample = true; ++j; }
+      if (level && i == cfg.num_res_blocks) {
+        resample(p + "." + std::to_string(j), ".conv", ch, +1);
+        ds /= 2;
+      }
+    }
+  }
+  add("out", BLK_OUT, input_ch, cfg.out_channels);
+  return out;
+}
+
 struct Walker {
   mi355_unet_config cfg;
   int dtype, esz, CH;
@@ -33,10 +101,6 @@ struct Walker {
   int emb_total = 0;
   int last_site = -1;   // differentiable plans: the GroupNorm site the next prologue consumer applies
 
-  bool has_attn(int ds) const {
-    for (int i = 0; i < cfg.n_attention_ds; ++i) if (cfg.attention_ds[i] == ds) return true;
-    return false;
-  }
   int heads_for(int ch, bool upsample) const {  // unet.py:370-378
     if (cfg.num_head_channels == -1) {
       int nh = (upsample && cfg.num_heads_upsample != -1) ? cfg.num_heads_upsample : cfg.num_heads;
@@ -278,8 +342,7 @@ struct Walker {
   }
 
   int walk() {
-    const int mc = cfg.model_channels, nl = cfg.n_channel_mult;
-    const int S = cfg.image_size;
+    const int mc = cfg.model_channels, S = cfg.image_size;
     net->in_pad = (int)align_up(cfg.in_channels, CH);
     net->te_w0 = put_linear_t("time_embed.0.weight", 4 * mc, mc);
     net->te_b0 = put_f32("time_embed.0.bias", {4 * mc});
@@ -289,58 +352,28 @@ struct Walker {
       net->num_classes = cfg.num_classes;
       net->label_w = put_f32("label_emb.weight", {cfg.num_classes, 4 * mc});
     }
-    int ch = cfg.channel_mult[0] * mc;
-    const int input_ch = ch;
     net->in_tensor = tensor(net->in_pad, S, S);
-    int h = add_conv("input_blocks.0.0", net->in_tensor, -1, cfg.in_channels, ch, 3, CONV_UNIT, false, 0, 0, -1, -1, RES_NONE, OUT_NHWC);
-    std::vector<int> hs{h};
-    int ds = 1, idx = 1;
-    for (int level = 0; level < nl && err.empty(); ++level) {
-      const int mult = cfg.channel_mult[level];
-      for (int r = 0; r < cfg.num_res_blocks && err.empty(); ++r, ++idx) {
-        const std::string p = "input_blocks." + std::to_string(idx);
-        h = res_block(p + ".0", h, -1, ch, mult * mc, false, false);
-        ch = mult * mc;
-        if (has_attn(ds) && err.empty()) h = attn_block(p + ".1", h, ch, heads_for(ch, false));
-        hs.push_back(h);
+    int h = net->in_tensor;
+    std::vector<int> hs;
+    for (const Block& b : unet_blocks(cfg)) {
+      int skip = -1;
+      if (b.pop) { skip = hs.back(); hs.pop_back(); }
+      switch (b.kind) {
+        case BLK_CONV_IN: h = add_conv(b.prefix, h, -1, b.cin, b.cout, 3, CONV_UNIT, false, 0, 0, -1, -1, RES_NONE, OUT_NHWC); break;
+        case BLK_RES: h = res_block(b.prefix, h, skip, b.cin, b.cout, b.dir > 0, b.dir < 0); break;
+        case BLK_ATTN: h = attn_block(b.prefix, h, b.cout, heads_for(b.cout, b.upsample)); break;
+        case BLK_RESAMPLE_CONV:
+          h = add_conv(b.prefix, h, -1, b.cin, b.cout, 3, b.dir > 0 ? CONV_UP2 : CONV_STRIDE2, false, 0, 0, -1, -1, RES_NONE, OUT_NHWC);
+          break;
+        case BLK_RESAMPLE: h = resample(h, b.dir > 0 ? CONV_UP2 : CONV_POOL2); break;
+        case BLK_OUT:
+          add_gn(h, -1, b.prefix + ".0.weight", b.prefix + ".0.bias", -1, 1, false);
+          add_conv(b.prefix + ".2", h, -1, b.cin, b.cout, 3, CONV_UNIT, false, 1, 1, -1, -1, RES_NONE, OUT_NCHW_F32);
+          break;
       }
-      if (level != nl - 1 && err.empty()) {
-        const std::string p = "input_blocks." + std::to_string(idx) + ".0";
-        if (cfg.resblock_updown) h = res_block(p, h, -1, ch, ch, false, true);
-        else if (cfg.conv_resample) h = add_conv(p + ".op", h, -1, ch, ch, 3, CONV_STRIDE2, false, 0, 0, -1, -1, RES_NONE, OUT_NHWC);
-        else h = resample(h, CONV_POOL2);
-        hs.push_back(h);
-        ds *= 2; ++idx;
-      }
+      if (!err.empty()) return -1;
+      if (b.push) hs.push_back(h);
     }
-    if (!err.empty()) return -1;
-    h = res_block("middle_block.0", h, -1, ch, ch, false, false);
-    if (err.empty()) h = attn_block("middle_block.1", h, ch, heads_for(ch, false));
-    if (err.empty()) h = res_block("middle_block.2", h, -1, ch, ch, false, false);
-    idx = 0;
-    for (int level = nl - 1; level >= 0 && err.empty(); --level) {
-      const int mult = cfg.channel_mult[level];
-      for (int i = 0; i <= cfg.num_res_blocks && err.empty(); ++i, ++idx) {
-        const std::string p = "output_blocks." + std::to_string(idx);
-        const int skip = hs.back(); hs.pop_back();
-        const int ich = T(skip).C;
-        h = res_block(p + ".0", h, skip, ch + ich, mc * mult, false, false);
-        ch = mc * mult;
-        int j = 1;
-        if (has_attn(ds) && err.empty()) { h = attn_block(p + "." + std::to_string(j), h, ch, heads_for(ch, true)); ++j; }
-        if (level && i == cfg.num_res_blocks && err.empty()) {
-          const std::string q = p + "." + std::to_string(j);
-          if (cfg.resblock_updown) h = res_block(q, h, -1, ch, ch, true, false);
-          else if (cfg.conv_resample) h = add_conv(q + ".conv", h, -1, ch, ch, 3, CONV_UP2, false, 0, 0, -1, -1, RES_NONE, OUT_NHWC);
-          else h = resample(h, CONV_UP2);
-          ds /= 2;
-        }
-      }
-    }
-    if (!err.empty()) return -1;
-    add_gn(h, -1, "out.0.weight", "out.0.bias", -1, 1, false);
-    add_conv("out.2", h, -1, input_ch, cfg.out_channels, 3, CONV_UNIT, false, 1, 1, -1, -1, RES_NONE, OUT_NCHW_F32);
-    if (!err.empty()) return -1;
     // batched emb_layers: Wt [4mc][emb_total], bias [emb_total]
     const int K = 4 * mc;
     net->emb_total = emb_total;
@@ -382,7 +415,7 @@ int check_cfg(const mi355_unet_config& c) {
 int unet_enumerate_params(const mi355_unet_config& cfg, std::vector<ParamInfo>& out) {
   if (int rc = check_cfg(cfg)) return rc;
   out.clear();
-  const int mc = cfg.model_channels, E = 4 * mc, nl = cfg.n_channel_mult;
+  const int mc = cfg.model_channels, E = 4 * mc;
   auto add = [&](const std::string& n, std::vector<int64_t> s) { out.push_back({n, s}); };
   auto conv = [&](const std::string& p, int co, int ci, int k) { add(p + ".weight", {co, ci, k, k}); add(p + ".bias", {co}); };
   auto res = [&](const std::string& p, int cin, int cout) {
@@ -399,53 +432,35 @@ int unet_enumerate_params(const mi355_unet_config& cfg, std::vector<ParamInfo>& 
     add(p + ".qkv.weight", {3 * C, C, 1}); add(p + ".qkv.bias", {3 * C});
     add(p + ".proj_out.weight", {C, C, 1}); add(p + ".proj_out.bias", {C});
   };
-  auto has_attn = [&](int ds) { for (int i = 0; i < cfg.n_attention_ds; ++i) if (cfg.attention_ds[i] == ds) return true; return false; };
   add("time_embed.0.weight", {E, mc}); add("time_embed.0.bias", {E});
   add("time_embed.2.weight", {E, E}); add("time_embed.2.bias", {E});
   if (cfg.num_classes > 0) add("label_emb.weight", {cfg.num_classes, E});
-  int ch = cfg.channel_mult[0] * mc;
-  const int input_ch = ch;
-  conv("input_blocks.0.0", ch, cfg.in_channels, 3);
-  std::vector<int> chans{ch};
-  int ds = 1, idx = 1;
-  for (int level = 0; level < nl; ++level) {
-    const int mult = cfg.channel_mult[level];
-    for (int r = 0; r < cfg.num_res_blocks; ++r, ++idx) {
-      const std::string p = "input_blocks." + std::to_string(idx);
-      res(p + ".0", ch, mult * mc);
-      ch = mult * mc;
-      if (has_attn(ds)) attn(p + ".1", ch);
-      chans.push_back(ch);
-    }
-    if (level != nl - 1) {
-      const std::string p = "input_blocks." + std::to_string(idx) + ".0";
-      if (cfg.resblock_updown) res(p, ch, ch);
-      else if (cfg.conv_resample) conv(p + ".op", ch, ch, 3);
-      chans.push_back(ch);
-      ds *= 2; ++idx;
+  for (const Block& b : unet_blocks(cfg)) {
+    switch (b.kind) {
+      case BLK_CONV_IN: case BLK_RESAMPLE_CONV: conv(b.prefix, b.cout, b.cin, 3); break;
+      case BLK_RES: res(b.prefix, b.cin, b.cout); break;
+      case BLK_ATTN: attn(b.prefix, b.cout); break;
+      case BLK_RESAMPLE: break;
+      case BLK_OUT: add(b.prefix + ".0.weight", {b.cin}); add(b.prefix + ".0.bias", {b.cin}); conv(b.prefix + ".2", b.cout, b.cin, 3); break;
     }
   }
-  res("middle_block.0", ch, ch); attn("middle_block.1", ch); res("middle_block.2", ch, ch);
-  idx = 0;
-  for (int level = nl - 1; level >= 0; --level) {
-    const int mult = cfg.channel_mult[level];
-    for (int i = 0; i <= cfg.num_res_blocks; ++i, ++idx) {
-      const std::string p = "output_blocks." + std::to_string(idx);
-      const int ich = chans.back(); chans.pop_back();
-      res(p + ".0", ch + ich, mc * mult);
-      ch = mc * mult;
-      int j = 1;
-      if (has_attn(ds)) { attn(p + "." + std::to_string(j), ch); ++j; }
-      if (level && i == cfg.num_res_blocks) {
-        const std::string q = p + "." + std::to_string(j);
-        if (cfg.resblock_updown) res(q, ch, ch);
-        else if (cfg.conv_resample) conv(q + ".conv", ch, ch, 3);
-        ds /= 2;
-      }
-    }
+  return 0;
+}
+
+// apply-type GroupNorm site (small images): writes silu?(GN(x)) for a prologue-free consumer, and may be applied by its producers' epilogues
+static bool apply_site(const PlanOp& o) { return o.kind == OP_GN && o.dst >= 0 && o.gn_site < 0; }
+
+// What the forward resolver takes for granted about a plan, checked once where the plan is made: a tensor is read by at most two apply-type
+// sites (the next block's norm and, for a skip, the up path's concat norm), and the conv that can carry a 1x1 skip conv is the next op.
+static int check_plan(const mi355_unet* net) {
+  std::vector<char> n_sites(net->tensors.size(), 0);
+  for (size_t j = 0; j < net->ops.size(); ++j) {
+    const PlanOp& o = net->ops[j];
+    if (apply_site(o))
+      for (int s : {o.src0, o.src1}) MI355_REQUIRE(s < 0 || ++n_sites[s] <= 2, -4, "unet plan: a tensor is read by more than two apply-type GroupNorm sites");
+    MI355_REQUIRE(o.carrier < 0 || ((size_t)o.carrier == j + 1 && net->ops[j + 1].kind == OP_CONV && net->ops[j + 1].skip_op == (int)j), -4,
+                  "unet plan: a skip conv's carrier is not the next op");
   }
-  add("out.0.weight", {ch}); add("out.0.bias", {ch});
-  conv("out.2", cfg.out_channels, input_ch, 3);
   return 0;
 }
 
@@ -462,13 +477,17 @@ static int run_walker(const mi355_unet_config& cfg, const float* const* host, mi
   net->knobs = cfg.debug ? *cfg.debug : mi355_default_debug();
   net->cfg.debug = nullptr;
   if (w.walk() != 0 || !w.err.empty()) { mi355_set_error("unet plan: " + w.err); return -4; }
-  return 0;
+  return check_plan(net);
 }
 
-int64_t unet_weight_bytes(const mi355_unet_config& cfg) {
-  mi355_unet tmp; Walker w;
-  if (int rc = run_walker(cfg, nullptr, &tmp, w)) return rc;
+int64_t unet_plan_dry(const mi355_unet_config& cfg, mi355_unet* net) {
+  Walker w;
+  if (int rc = run_walker(cfg, nullptr, net, w)) return rc;
   return (int64_t)w.cursor;
+}
+int64_t unet_weight_bytes(const mi355_unet_config& cfg) {
+  mi355_unet tmp;
+  return unet_plan_dry(cfg, &tmp);
 }
 
 int unet_build(const mi355_unet_config& cfg, const float* const* params_host, int n_params, void* dev_weights,
@@ -546,7 +565,6 @@ WsLayout unet_ws_layout(const mi355_unet* net, int B) {
   l.total = c;
   return l;
 }
-static WsLayout ws_layout(const mi355_unet* net, int B) { return unet_ws_layout(net, B); }
 
 int unet_embedding_table(const mi355_unet* net, const float* t_dev, int n, float* table, float* scratch, hipStream_t stream) {
   const int mc = net->cfg.model_channels;
@@ -577,110 +595,87 @@ int unet_embedding_rows_labels(const mi355_unet* net, const float* t_dev, int n_
                                  net->emb_total, net->err_dev, stream);
 }
 
-int64_t unet_workspace_bytes(const mi355_unet* net, int batch) { return (int64_t)ws_layout(net, batch).total; }
+int64_t unet_workspace_bytes(const mi355_unet* net, int batch) { return (int64_t)unet_ws_layout(net, batch).total; }
 
-int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* cond, int Cc, const float* t, float* out, int B,
-                 void* workspace, int64_t workspace_bytes, hipStream_t stream, const UnetRun& run) {
-  MI355_REQUIRE(net && x && t && out && workspace, -1, "unet_forward: null argument");
-  MI355_REQUIRE(B > 0, -1, "unet_forward: batch must be positive");
-  if (int rc = unet_status(net, 0)) return rc;   // an earlier launch of this handle gave up a counter wait
-  MI355_REQUIRE(Cx + (cond ? Cc : 0) == net->cfg.in_channels, -2, "unet_forward: x/cond channels do not add up to in_channels");
-  const WsLayout l = ws_layout(net, B);
-  MI355_REQUIRE((int64_t)l.total <= workspace_bytes, -2, "unet_forward: workspace too small");
-  MI355_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, -1, "unet_forward: workspace must be 256-byte aligned");
-  const int dtype = net->cfg.dtype, esz = dtype == 0 ? 4 : 2;
-  char* ws = reinterpret_cast<char*>(workspace);
-  char* W = net->dev_weights;
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  auto WF = [&](size_t off) { return reinterpret_cast<const float*>(W + off); };
-  auto TP = [&](int id) -> void* { return id < 0 ? nullptr : ws + l.arena + net->tensors[id].offset_per_image * (size_t)B * esz; };
-  auto SP = [&](int id) -> float* { return F(l.stats) + net->tensors[id].stats_off_per_image * (size_t)B; };
-  std::vector<int> gn_slots(net->tensors.size(), 0);   // partial-statistics slots each tensor's producer filled in THIS forward
-  // GroupNorm sites the producing conv applied in its epilogue (small levels: ConvDesc::act_out); a tensor's raw copy is written only
-  // if an op other than that site reads it
-  std::vector<char> gn_done(net->ops.size(), 0);
-  int euler_done = 0;   // the last conv's epilogue applied the sampler's Euler update (UnetRun::euler_x)
-  std::vector<char> skip_fused(net->ops.size(), 0);   // second convs of small-level ResBlocks that carry the block's 1x1 skip conv in THIS forward
-  std::vector<char> pro_off(net->ops.size(), 0);   // convs whose input arrives already normalised (16x16 level: applied IN PLACE by the producer)
-  std::vector<int> readers(net->tensors.size(), 0);
-  // apply-type GroupNorm sites (small images) by the tensors they read, and how many of a site's sources their producers have already applied
-  std::vector<std::vector<int>> apply_sites(net->tensors.size());
-  std::vector<char> site_parts(net->ops.size(), 0);
-  for (size_t j = 0; j < net->ops.size(); ++j) {
-    const PlanOp& o = net->ops[j];
-    if (o.src0 >= 0) ++readers[o.src0];
-    if (o.src1 >= 0) ++readers[o.src1];
-    if (o.kind == OP_CONV && o.res >= 0) ++readers[o.res];
-    if (o.kind == OP_GN && o.dst >= 0 && o.gn_site < 0) {
-      apply_sites[o.src0].push_back((int)j);
-      if (o.src1 >= 0) apply_sites[o.src1].push_back((int)j);
+// ---- resolve ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// Walks the plan once, in order, deciding what each op becomes in this forward.  All of a forward's bookkeeping lives here.
+struct Resolver {
+  const mi355_unet* net; const WsView& v; const UnetRun& run; const int B;
+  const float* x; int Cx; const float* cond; int Cc; float* out;
+  const float* embp; int estride;
+  struct OpState {
+    char gn_done = 0;      // GroupNorm site its producers' epilogues applied (small levels: ConvDesc::act_out; 16x16: in place)
+    char pro_off = 0;      // conv whose input arrives already normalised (16x16 level: applied IN PLACE by the producer)
+    char site_parts = 0;   // how many of an apply-type site's sources their producers have applied so far
+  };
+  struct TensorState {
+    int readers = 0;
+    int gn_slots = 0;      // partial-statistics slots the tensor's producer filled in THIS forward
+    int n_sites = 0, sites[2] = {-1, -1};   // apply-type GroupNorm sites (small images) that read it: the next block's norm and, for a skip, the concat's
+  };
+  std::vector<OpState> ops;
+  std::vector<TensorState> tens;
+
+  const float* WF(size_t off) const { return reinterpret_cast<const float*>(net->dev_weights + off); }
+  int cin(const PlanOp& op) const { return net->tensors[op.src0].C + (op.src1 >= 0 ? net->tensors[op.src1].C : 0); }
+
+  void count_readers() {   // (at most two sites per tensor, a skip conv's carrier the next op: check_plan, at build)
+    ops.assign(net->ops.size(), OpState());
+    tens.assign(net->tensors.size(), TensorState());
+    for (size_t j = 0; j < net->ops.size(); ++j) {
+      const PlanOp& o = net->ops[j];
+      if (o.src0 >= 0) ++tens[o.src0].readers;
+      if (o.src1 >= 0) ++tens[o.src1].readers;
+      if (o.kind == OP_CONV && o.res >= 0) ++tens[o.res].readers;
+      if (apply_site(o)) {
+        for (int s : {o.src0, o.src1}) if (s >= 0) tens[s].sites[tens[s].n_sites++] = (int)j;
+      }
     }
   }
-  int rc;
-  auto mark = [&](const mi355_op_profile& r) {
-    if (!run.prof) return;
-    hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, stream);
-    run.prof_events->push_back(e); run.prof->push_back(r);
-  };
-  if (run.prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, stream); run.prof_events->push_back(e); }
-  // time embedding path (fp32): emb2 = silu(time_embed(timestep_embedding(t))) ; embp = all emb_layers linears
-  // in the sampler loops every image shares the step time: one embedding row, broadcast with stride 0
-  // class labels: every image has its own row (estride = emb_total even for a shared t), gathered from the sampler's (step, class) table or
-  // computed here from t and the labels
-  const bool labelled = run.labels != nullptr;
-  MI355_REQUIRE(!labelled || net->num_classes > 0, -1, "unet_forward: class labels given to a net built without num_classes");
-  const int Be = run.t_uniform ? 1 : B, estride = run.t_uniform && !labelled ? 0 : net->emb_total;
-  const float* embp = run.emb_row && !labelled ? run.emb_row : F(l.embp);
-  if (labelled && run.emb_row) rc = emb_gather_launch(run.emb_row, run.labels, net->num_classes, F(l.embp), B, net->emb_total, net->err_dev, stream);
-  else if (labelled) rc = unet_embedding_rows_labels(net, t, Be, run.labels, B, run.t_uniform ? B : 1, F(l.embp), F(l.temb), stream);
-  else rc = run.emb_row ? 0 : unet_embedding_table(net, t, Be, F(l.embp), F(l.temb), stream);
-  if (rc) return rc;
-  const int S = net->cfg.image_size;
+
   // the conv a GroupNorm pass feeds is the next op of the plan: the pass warms the L2s with its weights (common.h l2_warm_wave)
-  const int warm_mask = net->knobs.l2_warm;   // 1 = statistics / apply passes, 2 = finalize passes (measured: no gain, off)
-  auto warm_next = [&](const PlanOp& op, const void*& wp, uint32_t& wb, int bit) {
-    const size_t oi = (size_t)(&op - net->ops.data());
-    if (!(warm_mask & bit) || oi + 1 >= net->ops.size() || net->ops[oi + 1].kind != OP_CONV) return;
+  // knobs.l2_warm: 1 = statistics / apply passes, 2 = finalize passes (measured: no gain, off)
+  void warm_next(size_t oi, const void*& wp, uint32_t& wb, int bit) const {
+    if (!(net->knobs.l2_warm & bit) || oi + 1 >= net->ops.size() || net->ops[oi + 1].kind != OP_CONV) return;
     const PlanOp& nx = net->ops[oi + 1];
-    const int cin = net->tensors[nx.src0].C + (nx.src1 >= 0 ? net->tensors[nx.src1].C : 0);
-    wp = W + nx.w_off; wb = (uint32_t)conv_packed_weight_bytes(dtype, nx.Cout, cin, nx.ks, net->wsplit);
-  };
+    wp = net->dev_weights + nx.w_off; wb = (uint32_t)conv_packed_weight_bytes(net->cfg.dtype, nx.Cout, cin(nx), nx.ks, net->wsplit);
+  }
+
   // The whole description of plan conv oi, everything it may do included; conv_route says which of it the launch does.  skip: with its
-  // ResBlock's 1x1 skip conv (op.skip_op) riding along.  act_consumer / fused_site: the GroupNorm sites act_out / act2_out stand for.
-  struct ConvOp { ConvDesc c; size_t act_consumer = 0; int fused_site[2] = {-1, -1}; };
-  auto conv_op = [&](size_t oi, bool skip) {
+  // ResBlock's 1x1 skip conv (op.skip_op) riding along.  ConvSites: the GroupNorm sites act_out / act2_out stand for.
+  struct ConvSites { size_t act_consumer = 0; int fused[2] = {-1, -1}; };
+  void describe_conv(size_t oi, bool skip, ConvDesc& c, ConvSites& r) const {
     const PlanOp& op = net->ops[oi];
     const PlanTensor& s0 = net->tensors[op.src0];
-    ConvOp r;
-    ConvDesc& c = r.c;
-    c.dtype = dtype; c.src0 = TP(op.src0); c.C0 = s0.C; c.src1 = TP(op.src1); c.C1 = op.src1 >= 0 ? net->tensors[op.src1].C : 0;
+    c.dtype = net->cfg.dtype; c.src0 = v.tensor(op.src0); c.C0 = s0.C; c.src1 = v.tensor(op.src1); c.C1 = op.src1 >= 0 ? net->tensors[op.src1].C : 0;
     c.N = B; c.Hs = s0.H; c.Ws = s0.W; c.mode = op.mode; c.ks = op.ks; c.wsplit = net->wsplit;
-    if (op.use_pro && !pro_off[oi]) { c.pro_a = F(l.gna); c.pro_b = F(l.gnb); c.pro_silu = op.pro_silu; }
-    if (op.use_pro && !pro_off[oi] && op.gn_site >= 0) {
-      float* sp = F(l.sites) + net->site_off[op.gn_site] * (size_t)B;
-      c.pro_a = sp; c.pro_b = sp + (size_t)B * net->site_C[op.gn_site];
+    if (op.use_pro && !ops[oi].pro_off) {
+      c.pro_a = v.f32(v.l.gna); c.pro_b = v.f32(v.l.gnb); c.pro_silu = op.pro_silu;
+      if (op.gn_site >= 0) { const WsView::Site s = v.site(op.gn_site); c.pro_a = s.a; c.pro_b = s.b; }
     }
-    c.w = W + op.w_off; c.bias = WF(op.bias_off); c.Cout = op.Cout;
-    if (op.has_wu) c.w_up2 = W + op.wu_off;
+    c.w = net->dev_weights + op.w_off; c.bias = WF(op.bias_off); c.Cout = op.Cout;
+    if (op.has_wu) c.w_up2 = net->dev_weights + op.wu_off;
     if (op.src0 == net->in_tensor) {
       c.cin_real = net->cfg.in_channels;
       // the first conv may read the caller's fp32 NCHW tensors itself (conv_edge bit 2): no packed copy, no pack launch
-      if (!net->cfg.differentiable && readers[net->in_tensor] == 1) { c.nchw0 = x; c.nchw_c0 = Cx; c.nchw1 = cond; c.nchw_c1 = cond ? Cc : 0; }
+      if (!net->cfg.differentiable && tens[net->in_tensor].readers == 1) { c.nchw0 = x; c.nchw_c0 = Cx; c.nchw1 = cond; c.nchw_c1 = cond ? Cc : 0; }
     }
     if (op.out_mode == OUT_NCHW_F32 && run.euler_x) { c.axpy_x = run.euler_x; c.axpy_scale = run.euler_dt; }
     if (op.emb_off >= 0) { c.emb = embp + op.emb_off; c.emb_stride = estride; }
-    if (op.res >= 0) { c.res = TP(op.res); c.res_mode = op.res_mode; }
+    if (op.res >= 0) { c.res = v.tensor(op.res); c.res_mode = op.res_mode; }
     c.out_mode = op.out_mode;
     c.knobs = &net->knobs; c.err = net->err_dev;
-    c.out = op.out_mode == OUT_NHWC ? TP(op.dst) : (void*)out;
+    c.out = op.out_mode == OUT_NHWC ? v.tensor(op.dst) : (void*)out;
     if (skip) {
       const PlanOp& sk = net->ops[op.skip_op];
-      c.skip_src0 = TP(sk.src0); c.skip_C0 = net->tensors[sk.src0].C;
-      c.skip_src1 = TP(sk.src1); c.skip_C1 = sk.src1 >= 0 ? net->tensors[sk.src1].C : 0;
-      c.w = W + op.wf_off; c.bias = WF(op.bf_off); c.res = nullptr; c.res_mode = RES_NONE;
+      c.skip_src0 = v.tensor(sk.src0); c.skip_C0 = net->tensors[sk.src0].C;
+      c.skip_src1 = v.tensor(sk.src1); c.skip_C1 = sk.src1 >= 0 ? net->tensors[sk.src1].C : 0;
+      c.w = net->dev_weights + op.wf_off; c.bias = WF(op.bf_off); c.res = nullptr; c.res_mode = RES_NONE;
     }
-    if (op.dst >= 0 && net->tensors[op.dst].stats_cap) { c.gn_stats = SP(op.dst); c.gn_slots_cap = net->tensors[op.dst].stats_cap; }
-    if (op.dst >= 0 && op.out_mode == OUT_NHWC && op.res < 0 && oi + 2 < net->ops.size() && readers[op.dst] == 2) {
+    if (op.dst >= 0 && net->tensors[op.dst].stats_cap) { c.gn_stats = v.stats(op.dst); c.gn_slots_cap = net->tensors[op.dst].stats_cap; }
+    if (op.dst >= 0 && op.out_mode == OUT_NHWC && op.res < 0 && oi + 2 < net->ops.size() && tens[op.dst].readers == 2) {
       // statistics-type site (larger images) read by exactly one prologue conv: where the persistent kernel's tile is the whole
       // image (16x16) it normalises its own output in place, the site's launch disappears and the consumer runs prologue-free
       const PlanOp& g = net->ops[oi + 1];
@@ -700,149 +695,290 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
       // The apply-type GroupNorm sites (small images) that read this conv's output: the one that follows it (in_layers / out_layers norm of
       // the next conv, unet.py:196-212) and, for a skip connection, the norm of the up path's concat (unet.py:650), whose groups are whole
       // inside each source when both channel counts are multiples of the group width: each producer then applies its own channels.
-      for (int gi : apply_sites[op.dst]) {
+      for (int k = 0; k < tens[op.dst].n_sites; ++k) {
+        const int gi = tens[op.dst].sites[k];
         const PlanOp& g = net->ops[gi];
         const bool cat = g.src1 >= 0;
-        const int Cg = net->tensors[g.src0].C + (cat ? net->tensors[g.src1].C : 0);
+        const int Cg = cin(g);
         const int coff = g.src0 == op.dst ? 0 : net->tensors[g.src0].C;
         if (cat) {
           const int cpg = Cg / 32;
           if (!(net->knobs.gn_epilogue & 4) || g.film_emb_off >= 0 || g.src0 == g.src1 || Cg % 32 || net->tensors[g.src0].C % cpg || net->tensors[g.src1].C % cpg) continue;
         }
         if (!c.act_out) {
-          c.act_out = TP(g.dst); c.act_gamma = WF(g.gamma_off) + coff; c.act_beta = WF(g.beta_off) + coff;
+          c.act_out = v.tensor(g.dst); c.act_gamma = WF(g.gamma_off) + coff; c.act_beta = WF(g.beta_off) + coff;
           if (g.film_emb_off >= 0) { c.act_film = embp + g.film_emb_off; c.act_film_stride = estride; }
           c.act_silu = g.pro_silu; c.act_stride = Cg; c.act_coff = coff; c.act_cpg = Cg / 32;
-          if (!cat || coff == 0) warm_next(g, c.warm, c.warm_bytes, 1);
-          r.fused_site[0] = gi;
+          if (!cat || coff == 0) warm_next((size_t)gi, c.warm, c.warm_bytes, 1);
+          r.fused[0] = gi;
         } else if (!c.act2_out && g.film_emb_off < 0) {
-          c.act2_out = TP(g.dst); c.act2_gamma = WF(g.gamma_off) + coff; c.act2_beta = WF(g.beta_off) + coff;
+          c.act2_out = v.tensor(g.dst); c.act2_gamma = WF(g.gamma_off) + coff; c.act2_beta = WF(g.beta_off) + coff;
           c.act2_silu = g.pro_silu; c.act2_stride = Cg; c.act2_coff = coff; c.act2_cpg = Cg / 32;
-          r.fused_site[1] = gi;
+          r.fused[1] = gi;
         }
       }
       // the raw tensor is written unless the one site asked for is its only reader (with two sites asked for the launch may still take one)
-      if (c.act_out) c.act_raw = c.act2_out ? 1 : readers[op.dst] > 1;
+      if (c.act_out) c.act_raw = c.act2_out ? 1 : tens[op.dst].readers > 1;
     }
-    return r;
-  };
-  bool in_direct = false;
-  for (size_t j = 0; j < net->ops.size(); ++j) {
-    if (net->ops[j].kind != OP_CONV || net->ops[j].src0 != net->in_tensor) continue;
-    ConvRoute rt;
-    in_direct = conv_route(conv_op(j, false).c, &rt) == 0 && rt.reads_nchw;
-    break;
   }
-  if (in_direct) { if ((size_t)net->in_tensor < net->tensor_state_n) net->tensor_state[net->in_tensor].store((char)1, std::memory_order_relaxed); }
-  else if ((rc = pack_nhwc_launch(dtype, x, Cx, cond, cond ? Cc : 0, B, S * S, net->in_pad, TP(net->in_tensor), stream))) return rc;
-  { mi355_op_profile r{}; r.kind = MI355_OP_PRELUDE; mark(r); }
-  for (const PlanOp& op : net->ops) {
-    mi355_op_profile r{};
+  // what the routed launch of conv oi settles for the ops behind it
+  void settle_conv(size_t oi, const ConvRoute& rt, const ConvSites& r) {
+    if (rt.act_done && r.act_consumer) { ops[oi + 1].gn_done = 1; ops[r.act_consumer].pro_off = 1; }
+    else if (rt.act_done) {
+      for (int k = 0; k < 2; ++k) {
+        if (!(rt.act_done & (1 << k)) || r.fused[k] < 0) continue;
+        if (++ops[r.fused[k]].site_parts == (net->ops[r.fused[k]].src1 >= 0 ? 2 : 1)) ops[r.fused[k]].gn_done = 1;
+      }
+    }
+    if (net->ops[oi].dst >= 0) tens[net->ops[oi].dst].gn_slots = rt.gn_slots;
+  }
+
+  // a GroupNorm op's affine parameters and, under use_scale_shift_norm, its FiLM rows
+  void gn_common(const PlanOp& op, const float*& gamma, const float*& beta, const float*& film, int& film_stride) const {
+    gamma = WF(op.gamma_off); beta = WF(op.beta_off);
+    if (op.film_emb_off >= 0) { film = embp + op.film_emb_off; film_stride = estride; }
+  }
+  GnFinDesc describe_gn_finalize(size_t oi) const {
+    const PlanOp& op = net->ops[oi];
     const PlanTensor& s0 = net->tensors[op.src0];
-    const int C1 = op.src1 >= 0 ? net->tensors[op.src1].C : 0;
-    if (op.kind == OP_GN && gn_done[(size_t)(&op - net->ops.data())]) {
-      rc = 0;   // applied by the producing conv's epilogue
-      r.kind = MI355_OP_GN; r.cin = s0.C + C1; r.h = s0.H; r.w = s0.W; r.bytes = 0; r.tile_m = r.tile_n = -1;   // (tile -1: nothing was launched for this op)
-    } else if (op.kind == OP_GN && op.fin_ok && op.dst < 0 && gn_slots[op.src0] > 0 && (op.src1 < 0 || gn_slots[op.src1] > 0)) {
-      GnFinDesc g; g.stats0 = SP(op.src0); g.slots0 = gn_slots[op.src0]; g.C0 = s0.C;
-      if (op.src1 >= 0) { g.stats1 = SP(op.src1); g.slots1 = gn_slots[op.src1]; g.C1 = C1; }
-      g.N = B; g.HW = s0.H * s0.W; g.gamma = WF(op.gamma_off); g.beta = WF(op.beta_off);
-      if (op.film_emb_off >= 0) { g.film = embp + op.film_emb_off; g.film_stride = estride; }
-      g.a = F(l.gna); g.b = F(l.gnb);
-      g.dtype = dtype; g.src0 = TP(op.src0); g.src1 = op.src1 >= 0 ? TP(op.src1) : nullptr;
-      warm_next(op, g.warm, g.warm_bytes, 2);
-      rc = gn_finalize_launch(g, stream);
-      r.kind = MI355_OP_GN; r.cin = s0.C + C1; r.h = s0.H; r.w = s0.W;
-      r.bytes = 0;   // no activation traffic: the statistics came with the producers' epilogues
-    } else if (op.kind == OP_GN) {
-      GnDesc g; g.dtype = dtype; g.src0 = TP(op.src0); g.C0 = s0.C; g.src1 = TP(op.src1); g.C1 = C1;
-      g.N = B; g.HW = s0.H * s0.W; g.gamma = WF(op.gamma_off); g.beta = WF(op.beta_off);
-      if (op.film_emb_off >= 0) { g.film = embp + op.film_emb_off; g.film_stride = estride; }
-      g.a = F(l.gna); g.b = F(l.gnb);
-      if (op.gn_site >= 0) {   // differentiable plan: this site's own (a, b, mean, rstd)
-        float* sp = F(l.sites) + net->site_off[op.gn_site] * (size_t)B;
-        const size_t Cs = (size_t)net->site_C[op.gn_site];
-        g.a = sp; g.b = sp + (size_t)B * Cs; g.mean = sp + (size_t)2 * B * Cs; g.rstd = g.mean + (size_t)B * 32;
-      }
-      if (op.dst >= 0) { g.y = TP(op.dst); g.y_silu = op.pro_silu; }
-      warm_next(op, g.warm, g.warm_bytes, 1);
-      rc = gn_affine_launch(g, stream);
-      r.kind = MI355_OP_GN; r.cin = s0.C + C1; r.h = s0.H; r.w = s0.W;
-      r.bytes = (double)B * s0.H * s0.W * (s0.C + C1) * esz * (op.dst >= 0 ? 2 : 1);
-    } else if (op.kind == OP_CONV && op.carrier >= 0 && [&]() {
-                 // 1x1 skip_connection of a small-level ResBlock: does the second conv's launch take it along?
-                 ConvRoute rt;
-                 return conv_route(conv_op((size_t)op.carrier, true).c, &rt) == 0;
-               }()) {
-      skip_fused[op.carrier] = 1;   // nothing to launch: the tensor is never written
-      gn_done[(size_t)(&op - net->ops.data())] = 1;   // (counts as a launch that did not happen)
-      if (op.dst >= 0 && (size_t)op.dst < net->tensor_state_n) net->tensor_state[op.dst].store((char)1, std::memory_order_relaxed);
-      rc = 0;
-      r.kind = MI355_OP_CONV; r.ks = op.ks; r.cin = s0.C + C1; r.cout = op.Cout; r.h = s0.H; r.w = s0.W; r.tile_m = r.tile_n = -1;
-    } else if (op.kind == OP_CONV) {
-      const size_t oi = (size_t)(&op - net->ops.data());
-      const ConvOp co = conv_op(oi, skip_fused[oi]);   // (skip_fused: the ResBlock's 1x1 skip conv rides in this launch, its op was skipped above)
-      const ConvDesc& c = co.c;
-      ConvRoute rt;
-      if ((rc = conv_route(c, &rt)) || (rc = conv_launch(c, rt, stream))) return rc;
-      if (rt.act_done && co.act_consumer) { gn_done[oi + 1] = 1; pro_off[co.act_consumer] = 1; }
-      else if (rt.act_done) {
-        for (int k = 0; k < 2; ++k) {
-          if (!(rt.act_done & (1 << k)) || co.fused_site[k] < 0) continue;
-          const PlanOp& g = net->ops[co.fused_site[k]];
-          if (++site_parts[co.fused_site[k]] == (g.src1 >= 0 ? 2 : 1)) gn_done[co.fused_site[k]] = 1;
-        }
-      }
-      if (rt.axpy) euler_done = 1;
-      if (op.dst >= 0 && (size_t)op.dst < net->tensor_state_n) net->tensor_state[op.dst].store((char)(!rt.act_done ? 0 : (co.act_consumer ? 2 : (c.act_raw ? 0 : 1))), std::memory_order_relaxed);
-      if (op.dst >= 0) gn_slots[op.dst] = rt.gn_slots;
-      if (run.prof) {
-        const ConvGeom& cg = rt.geom;
-        const int cin = s0.C + C1;
-        r.kind = MI355_OP_CONV; r.ks = op.ks; r.cin = cin; r.cout = op.Cout; r.h = cg.Ho; r.w = cg.Wo; r.tile_m = cg.BM; r.tile_n = cg.BN;
-        r.flops = 2.0 * B * cg.Ho * cg.Wo * (double)op.Cout * cin * op.ks * op.ks;
-        r.bytes = ((double)B * s0.H * s0.W * cin + (double)B * cg.Ho * cg.Wo * op.Cout) * esz + (double)op.Cout * cin * op.ks * op.ks * esz;
-        if (skip_fused[oi]) {   // the ResBlock's 1x1 skip conv this launch carried
-          r.flops += 2.0 * B * cg.Ho * cg.Wo * (double)op.Cout * (c.skip_C0 + c.skip_C1);
-          r.bytes += ((double)B * cg.Ho * cg.Wo + (double)op.Cout) * (c.skip_C0 + c.skip_C1) * esz;
-        }
-      }
-    } else if (op.kind == OP_ATTN) {
-      AttnDesc a; a.dtype = dtype; a.qkv = TP(op.src0); a.out = TP(op.dst); a.N = B; a.T = s0.H * s0.W;
-      a.heads = op.heads; a.ch = op.ch; a.new_order = net->cfg.use_new_attention_order;
-      rc = attention_launch(a, stream);
-      r.kind = MI355_OP_ATTN; r.cin = 3 * op.heads * op.ch; r.cout = op.heads * op.ch; r.h = s0.H; r.w = s0.W;
-      r.flops = 4.0 * B * (double)a.T * a.T * op.heads * op.ch;
-      r.bytes = 4.0 * B * a.T * op.heads * op.ch * esz;
-    } else if (op.kind == OP_ATTN_FUSED) {
-      AttnFusedDesc a; a.dtype = dtype; a.x = TP(op.src0); a.ga = F(l.gna); a.gb = F(l.gnb); a.w = W + op.w_off; a.bias = WF(op.bias_off);
-      a.out = TP(op.dst); a.N = B; a.T = s0.H * s0.W; a.C = s0.C; a.heads = op.heads; a.ch = op.ch;
-      a.new_order = net->cfg.use_new_attention_order; a.knobs = &net->knobs;
-      rc = attn_fused_launch(a, stream);
-      r.kind = MI355_OP_ATTN; r.cin = s0.C; r.cout = s0.C; r.h = s0.H; r.w = s0.W; r.ks = 1;   // ks = 1 marks the fused form
-      r.flops = 2.0 * B * (double)a.T * 3.0 * s0.C * s0.C + 4.0 * B * (double)a.T * a.T * s0.C;
-      r.bytes = 2.0 * B * a.T * (double)s0.C * esz + 3.0 * s0.C * s0.C * esz;
-    } else if (op.kind == OP_POOLAFF) {
-      const float* pa = F(l.gna); const float* pb = F(l.gnb);
-      if (op.gn_site >= 0) { pa = F(l.sites) + net->site_off[op.gn_site] * (size_t)B; pb = pa + (size_t)B * net->site_C[op.gn_site]; }
-      rc = affine_pool_launch(dtype, TP(op.src0), pa, pb, op.pro_silu, TP(op.dst), B, s0.H, s0.W, s0.C, stream);
-      r.kind = MI355_OP_RESAMPLE; r.cin = s0.C; r.h = s0.H; r.w = s0.W;
-      r.bytes = 1.25 * B * s0.H * s0.W * (double)s0.C * esz;
-    } else {
-      rc = resample_launch(dtype, TP(op.src0), TP(op.dst), B, s0.H, s0.W, s0.C, op.mode, stream);
-      r.kind = MI355_OP_RESAMPLE; r.cin = s0.C; r.h = s0.H; r.w = s0.W;
-    }
-    if (rc) return rc;
-    mark(r);
+    GnFinDesc g; g.stats0 = v.stats(op.src0); g.slots0 = tens[op.src0].gn_slots; g.C0 = s0.C;
+    if (op.src1 >= 0) { g.stats1 = v.stats(op.src1); g.slots1 = tens[op.src1].gn_slots; g.C1 = net->tensors[op.src1].C; }
+    g.N = B; g.HW = s0.H * s0.W;
+    gn_common(op, g.gamma, g.beta, g.film, g.film_stride);
+    g.a = v.f32(v.l.gna); g.b = v.f32(v.l.gnb);
+    g.dtype = net->cfg.dtype; g.src0 = v.tensor(op.src0); g.src1 = v.tensor(op.src1);
+    warm_next(oi, g.warm, g.warm_bytes, 2);
+    return g;
   }
-  if (run.euler_x && !euler_done) {
+  GnDesc describe_gn(size_t oi) const {
+    const PlanOp& op = net->ops[oi];
+    const PlanTensor& s0 = net->tensors[op.src0];
+    GnDesc g; g.dtype = net->cfg.dtype; g.src0 = v.tensor(op.src0); g.C0 = s0.C; g.src1 = v.tensor(op.src1); g.C1 = op.src1 >= 0 ? net->tensors[op.src1].C : 0;
+    g.N = B; g.HW = s0.H * s0.W;
+    gn_common(op, g.gamma, g.beta, g.film, g.film_stride);
+    g.a = v.f32(v.l.gna); g.b = v.f32(v.l.gnb);
+    if (op.gn_site >= 0) { const WsView::Site s = v.site(op.gn_site); g.a = s.a; g.b = s.b; g.mean = s.mean; g.rstd = s.rstd; }   // differentiable plan: this site's own
+    if (op.dst >= 0) { g.y = v.tensor(op.dst); g.y_silu = op.pro_silu; }
+    warm_next(oi, g.warm, g.warm_bytes, 1);
+    return g;
+  }
+  AttnDesc describe_attn(const PlanOp& op) const {
+    const PlanTensor& s0 = net->tensors[op.src0];
+    AttnDesc a; a.dtype = net->cfg.dtype; a.qkv = v.tensor(op.src0); a.out = v.tensor(op.dst); a.N = B; a.T = s0.H * s0.W;
+    a.heads = op.heads; a.ch = op.ch; a.new_order = net->cfg.use_new_attention_order;
+    return a;
+  }
+  AttnFusedDesc describe_attn_fused(const PlanOp& op) const {
+    const PlanTensor& s0 = net->tensors[op.src0];
+    AttnFusedDesc a; a.dtype = net->cfg.dtype; a.x = v.tensor(op.src0); a.ga = v.f32(v.l.gna); a.gb = v.f32(v.l.gnb);
+    a.w = net->dev_weights + op.w_off; a.bias = WF(op.bias_off);
+    a.out = v.tensor(op.dst); a.N = B; a.T = s0.H * s0.W; a.C = s0.C; a.heads = op.heads; a.ch = op.ch;
+    a.new_order = net->cfg.use_new_attention_order; a.knobs = &net->knobs;
+    return a;
+  }
+  PoolAffStep describe_pool(const PlanOp& op) const {
+    const PlanTensor& s0 = net->tensors[op.src0];
+    PoolAffStep p{net->cfg.dtype, v.tensor(op.src0), v.f32(v.l.gna), v.f32(v.l.gnb), op.pro_silu, v.tensor(op.dst), B, s0.H, s0.W, s0.C};
+    if (op.gn_site >= 0) { const WsView::Site s = v.site(op.gn_site); p.a = s.a; p.b = s.b; }
+    return p;
+  }
+
+  static ConvStep& push_conv(ResolvedForward* f) { return std::get<ConvStep>(f->steps.emplace_back(std::in_place_type<ConvStep>)); }
+
+  int resolve(ResolvedForward* f) {
+    count_readers();
+    const size_t n = net->ops.size();
+    f->steps.clear();
+    f->steps.reserve(n);
+    // steps are described and routed in place.  carried: the previous op was a 1x1 skip conv whose probe the route took, so this op's step
+    // (its ResBlock's second conv) is already there; `sites` are that description's.
+    bool carried = false;
+    ConvSites sites;
+    for (size_t oi = 0; oi < n; ++oi) {
+      const PlanOp& op = net->ops[oi];
+      const PlanTensor& s0 = net->tensors[op.src0];
+      switch (op.kind) {
+        case OP_GN:
+          if (ops[oi].gn_done) f->steps.emplace_back(GnAbsorbed{});
+          else if (op.fin_ok && op.dst < 0 && tens[op.src0].gn_slots > 0 && (op.src1 < 0 || tens[op.src1].gn_slots > 0)) f->steps.emplace_back(describe_gn_finalize(oi));
+          else f->steps.emplace_back(describe_gn(oi));
+          break;
+        case OP_CONV: {
+          if (!carried && op.carrier >= 0) {
+            // 1x1 skip_connection of a small-level ResBlock: does the second conv's launch take it along?  The carrier is the next op and
+            // nothing it is described from changes in between, so the probe's description and route are that step's.
+            f->steps.emplace_back(ConvCarried{});
+            ConvStep& c2 = push_conv(f);
+            sites = ConvSites();
+            describe_conv(oi + 1, true, c2.c, sites);
+            if (conv_route(c2.c, &c2.rt) == 0) { carried = true; break; }
+            f->steps.pop_back(); f->steps.pop_back();   // declined: both convs are launched on their own
+          }
+          if (!carried) {
+            ConvStep& st = push_conv(f);
+            sites = ConvSites();
+            describe_conv(oi, false, st.c, sites);
+            if (int rc = conv_route(st.c, &st.rt)) return rc;
+          }
+          carried = false;
+          const ConvRoute& rt = std::get<ConvStep>(f->steps[oi]).rt;
+          settle_conv(oi, rt, sites);
+          if (rt.axpy) f->euler_in_conv = true;
+          if (op.src0 == net->in_tensor && rt.reads_nchw) f->pack = false;
+          break;
+        }
+        case OP_ATTN: f->steps.emplace_back(describe_attn(op)); break;
+        case OP_ATTN_FUSED: f->steps.emplace_back(describe_attn_fused(op)); break;
+        case OP_POOLAFF: f->steps.emplace_back(describe_pool(op)); break;
+        default: f->steps.emplace_back(ResampleStep{net->cfg.dtype, v.tensor(op.src0), v.tensor(op.dst), B, s0.H, s0.W, s0.C, op.mode}); break;
+      }
+    }
+    return 0;
+  }
+};
+
+template <typename T> bool is(const ForwardStep& s) { return std::holds_alternative<T>(s); }
+
+// ---- issue: one launch per descriptor type ---------------------------------------------------------------------------------------------
+int issue(const GnAbsorbed&, hipStream_t) { return 0; }
+int issue(const ConvCarried&, hipStream_t) { return 0; }
+int issue(const GnFinDesc& g, hipStream_t s) { return gn_finalize_launch(g, s); }
+int issue(const GnDesc& g, hipStream_t s) { return gn_affine_launch(g, s); }
+int issue(const ConvStep& c, hipStream_t s) { return conv_launch(c.c, c.rt, s); }
+int issue(const AttnDesc& a, hipStream_t s) { return attention_launch(a, s); }
+int issue(const AttnFusedDesc& a, hipStream_t s) { return attn_fused_launch(a, s); }
+int issue(const PoolAffStep& p, hipStream_t s) { return affine_pool_launch(p.dtype, p.in, p.a, p.b, p.silu, p.out, p.N, p.H, p.W, p.C, s); }
+int issue(const ResampleStep& r, hipStream_t s) { return resample_launch(r.dtype, r.in, r.out, r.N, r.H, r.W, r.C, r.mode, s); }
+
+// The mi355_op_profile record (all but ms) of plan op `op` as step `st` ran it at batch B.  tile -1, -1: nothing was launched for this op.
+mi355_op_profile profile_record(const mi355_unet* net, const PlanOp& op, const ForwardStep& st, int B) {
+  mi355_op_profile r{};
+  const PlanTensor& s0 = net->tensors[op.src0];
+  const int cin = s0.C + (op.src1 >= 0 ? net->tensors[op.src1].C : 0), esz = net->cfg.dtype == 0 ? 4 : 2;
+  r.h = s0.H; r.w = s0.W;
+  if (!unet_step_launches(st)) r.tile_m = r.tile_n = -1;
+  switch (op.kind) {
+    case OP_GN:
+      r.kind = MI355_OP_GN; r.cin = cin;
+      // absorbed / finalized: no activation traffic (the statistics came with the producers' epilogues)
+      if (is<GnDesc>(st)) r.bytes = (double)B * s0.H * s0.W * cin * esz * (op.dst >= 0 ? 2 : 1);
+      break;
+    case OP_CONV: {
+      r.kind = MI355_OP_CONV; r.ks = op.ks; r.cin = cin; r.cout = op.Cout;
+      if (!is<ConvStep>(st)) break;
+      const ConvStep& c = std::get<ConvStep>(st);
+      const ConvGeom& cg = c.rt.geom;
+      r.h = cg.Ho; r.w = cg.Wo; r.tile_m = cg.BM; r.tile_n = cg.BN;
+      r.flops = 2.0 * B * cg.Ho * cg.Wo * (double)op.Cout * cin * op.ks * op.ks;
+      r.bytes = ((double)B * s0.H * s0.W * cin + (double)B * cg.Ho * cg.Wo * op.Cout) * esz + (double)op.Cout * cin * op.ks * op.ks * esz;
+      if (c.c.skip_src0) {   // the ResBlock's 1x1 skip conv this launch carried
+        r.flops += 2.0 * B * cg.Ho * cg.Wo * (double)op.Cout * (c.c.skip_C0 + c.c.skip_C1);
+        r.bytes += ((double)B * cg.Ho * cg.Wo + (double)op.Cout) * (c.c.skip_C0 + c.c.skip_C1) * esz;
+      }
+      break;
+    }
+    case OP_ATTN: {
+      const int T = s0.H * s0.W;
+      r.kind = MI355_OP_ATTN; r.cin = 3 * op.heads * op.ch; r.cout = op.heads * op.ch;
+      r.flops = 4.0 * B * (double)T * T * op.heads * op.ch;
+      r.bytes = 4.0 * B * T * op.heads * op.ch * esz;
+      break;
+    }
+    case OP_ATTN_FUSED: {
+      const int T = s0.H * s0.W;
+      r.kind = MI355_OP_ATTN; r.cin = s0.C; r.cout = s0.C; r.ks = 1;   // ks = 1 marks the fused form
+      r.flops = 2.0 * B * (double)T * 3.0 * s0.C * s0.C + 4.0 * B * (double)T * T * s0.C;
+      r.bytes = 2.0 * B * T * (double)s0.C * esz + 3.0 * s0.C * s0.C * esz;
+      break;
+    }
+    case OP_POOLAFF:
+      r.kind = MI355_OP_RESAMPLE; r.cin = s0.C;
+      r.bytes = 1.25 * B * s0.H * s0.W * (double)s0.C * esz;
+      break;
+    default: r.kind = MI355_OP_RESAMPLE; r.cin = s0.C; break;
+  }
+  return r;
+}
+
+// What the forward leaves in a step's output tensor (mi355_unet::tensor_state): 0 as the reference defines it, 1 never written, 2 normalised in place
+char tensor_state_of(const ForwardStep& st) {
+  if (is<ConvCarried>(st)) return 1;
+  const ConvStep& c = std::get<ConvStep>(st);
+  if (!c.rt.act_done) return 0;
+  return c.c.act_out == c.c.out ? 2 : (c.c.act_raw ? 0 : 1);
+}
+
+}  // namespace
+
+int unet_resolve(const WsView& v, const float* x, int Cx, const float* cond, int Cc, float* out, const UnetRun& run, ResolvedForward* f) {
+  // time embedding path (fp32): emb2 = silu(time_embed(timestep_embedding(t))) ; embp = all emb_layers linears
+  // in the sampler loops every image shares the step time: one embedding row, broadcast with stride 0
+  // class labels: every image has its own row (estride = emb_total even for a shared t), gathered from the sampler's (step, class) table or
+  // computed from t and the labels
+  const mi355_unet* net = v.net;
+  const int B = (int)v.B;
+  const bool labelled = run.labels != nullptr;
+  MI355_REQUIRE(!labelled || net->num_classes > 0, -1, "unet_forward: class labels given to a net built without num_classes");
+  *f = ResolvedForward();
+  f->emb = labelled ? (run.emb_row ? EMB_GATHER : EMB_LABELS) : (run.emb_row ? EMB_ROW : EMB_TIME);
+  f->Be = run.t_uniform ? 1 : B; f->estride = run.t_uniform && !labelled ? 0 : net->emb_total;
+  f->embp = f->emb == EMB_ROW ? run.emb_row : v.f32(v.l.embp);
+  Resolver r{net, v, run, B, x, Cx, cond, Cc, out, f->embp, f->estride, {}, {}};
+  return r.resolve(f);
+}
+
+int64_t unet_launch_count(const ResolvedForward& f) {
+  int64_t n = (f.emb == EMB_ROW ? 0 : f.emb == EMB_GATHER ? 1 : 4) + (f.pack ? 1 : 0);
+  for (const ForwardStep& s : f.steps) n += unet_step_launches(s);
+  return n;
+}
+
+int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* cond, int Cc, const float* t, float* out, int B,
+                 void* workspace, int64_t workspace_bytes, hipStream_t stream, const UnetRun& run) {
+  MI355_REQUIRE(net && x && t && out && workspace, -1, "unet_forward: null argument");
+  MI355_REQUIRE(B > 0, -1, "unet_forward: batch must be positive");
+  if (int rc = unet_status(net, 0)) return rc;   // an earlier launch of this handle gave up a counter wait
+  MI355_REQUIRE(Cx + (cond ? Cc : 0) == net->cfg.in_channels, -2, "unet_forward: x/cond channels do not add up to in_channels");
+  const WsView v(net, workspace, B);
+  MI355_REQUIRE((int64_t)v.l.total <= workspace_bytes, -2, "unet_forward: workspace too small");
+  MI355_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, -1, "unet_forward: workspace must be 256-byte aligned");
+  ResolvedForward f;
+  int rc;
+  if ((rc = unet_resolve(v, x, Cx, cond, Cc, out, run, &f))) return rc;
+
+  // ---- the handle's diagnostics of its most recent forward: what this forward is about to leave, known before anything is launched ----
+  if (!f.pack && (size_t)net->in_tensor < net->tensor_state_n) net->tensor_state[net->in_tensor].store((char)1, std::memory_order_relaxed);
+  for (size_t i = 0; i < f.steps.size(); ++i) {
+    const PlanOp& op = net->ops[i];
+    if (op.kind == OP_CONV && op.dst >= 0 && (size_t)op.dst < net->tensor_state_n) net->tensor_state[op.dst].store(tensor_state_of(f.steps[i]), std::memory_order_relaxed);
+  }
+
+  // ---- issue: the prelude, then one launch per step ----
+  auto mark = [&](const mi355_op_profile& r) {
+    hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, stream);
+    run.prof_events->push_back(e); run.prof->push_back(r);
+  };
+  if (run.prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, stream); run.prof_events->push_back(e); }
+  float* rows = v.f32(v.l.embp);
+  switch (f.emb) {
+    case EMB_GATHER: rc = emb_gather_launch(run.emb_row, run.labels, net->num_classes, rows, B, net->emb_total, net->err_dev, stream); break;
+    case EMB_LABELS: rc = unet_embedding_rows_labels(net, t, f.Be, run.labels, B, run.t_uniform ? B : 1, rows, v.f32(v.l.temb), stream); break;
+    case EMB_TIME: rc = unet_embedding_table(net, t, f.Be, rows, v.f32(v.l.temb), stream); break;
+    default: break;
+  }
+  if (rc) return rc;
+  const int S = net->cfg.image_size;
+  if (f.pack && (rc = pack_nhwc_launch(net->cfg.dtype, x, Cx, cond, cond ? Cc : 0, B, S * S, net->in_pad, v.tensor(net->in_tensor), stream))) return rc;
+  if (run.prof) { mi355_op_profile r{}; r.kind = MI355_OP_PRELUDE; mark(r); }
+  for (size_t i = 0; i < f.steps.size(); ++i) {
+    if ((rc = std::visit([&](const auto& d) { return issue(d, stream); }, f.steps[i]))) return rc;
+    if (run.prof) mark(profile_record(net, net->ops[i], f.steps[i], B));
+  }
+  if (run.euler_x && !f.euler_in_conv) {
     const int64_t n_out = (int64_t)B * net->cfg.out_channels * S * S;
     if ((rc = euler_step_launch(run.euler_x, out, run.euler_dt, n_out, stream))) return rc;
   }
-  {
-    int64_t skipped = in_direct ? 1 : 0;   // (the Euler update is the sampler's launch, not the forward's: not counted either way)
-    for (char d : gn_done) skipped += d;
-    net->last_launches = net->launches - skipped - (run.emb_row ? 4 : 0) + (run.emb_row && labelled ? 1 : 0);   // (+ the row gather)
-  }
+
+  net->last_launches = unet_launch_count(f);
   return 0;
 }

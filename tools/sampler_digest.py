@@ -9,6 +9,11 @@ with the same arguments print the same lines.  Run it once per library, each run
 and compare the files.  --save keeps the tensors themselves, for a max-abs comparison of a case that is not reproducible run to run.
 --mark launches one torch.flip kernel behind every case (nothing else here uses it), so that a kernel trace of the run
 (rocprofv3 --kernel-trace -- python tools/sampler_digest.py --mark) can be cut into cases and compared case by case.
+
+--cases forward adds (or, alone, selects) the digest of single forwards, on the smallest nets and batches at which each decision of the
+executor (csrc/unet_engine.hip: unet_resolve) goes either way: per case the SHA-256 of the output, the launch count, every field of every
+profile() record except ms, and for every conv output tensor whether read_tensor refuses it and why (0 readable, 1 never written, 2
+normalised in place).  --inventory needs no GPU: the parameter inventory (names, shapes, order) and the weight-image bytes of the same nets.
 """
 import argparse
 import hashlib
@@ -26,6 +31,7 @@ import torch  # noqa: E402
 from image_diffusion.sde_diffusion import DDPM  # noqa: E402
 from image_diffusion.unet import UNetModel, param_shapes  # noqa: E402
 from mi355 import _lib  # noqa: E402
+from mi355.engine import _PREC, MI355BackendError, param_inventory  # noqa: E402
 from mi355.synth import randn, synth_state_dict  # noqa: E402
 
 DEV = "cuda:0"
@@ -173,17 +179,140 @@ def run(prec):
     case(prec, "sf2m_sliced", u3, dict(zip(("x", "traj"), sliced(u3, 2, lambda: u3.sf2m_euler(score, x0.clone(), grid, 0.3, outputs=outs, seed=77)))))
 
 
+# ---- single forwards --------------------------------------------------------------------------------------------------------------------
+CIFAR = dict(image_size=32, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2, attention_resolutions=(2,),
+             channel_mult=(1, 2, 2, 2), num_heads=4, num_head_channels=64)
+TWO_LEVEL = dict(CIFAR, num_res_blocks=1, channel_mult=(1, 2))                       # 32 px / 128 channels: the edge convs' kernels
+UPDOWN = dict(image_size=16, in_channels=3, model_channels=32, out_channels=3, num_res_blocks=1, attention_resolutions=(2,),
+              channel_mult=(1, 2, 2), num_heads=2, use_scale_shift_norm=True, resblock_updown=True)   # smallest with a down and an up ResBlock
+TINY = dict(image_size=S, in_channels=3, model_channels=32, out_channels=3, num_res_blocks=1, attention_resolutions=(2,), channel_mult=(1, 2),
+            num_heads=2)
+FWD_NETS = {
+    "cifar": CIFAR, "cifar_film": dict(CIFAR, use_scale_shift_norm=True), "cifar_in6": dict(CIFAR, in_channels=6),
+    "two_level": TWO_LEVEL, "two_level_in6": dict(TWO_LEVEL, in_channels=6),
+    "updown": UPDOWN, "updown_noconv": dict(UPDOWN, conv_resample=False),
+    "plain_resample": dict(UPDOWN, resblock_updown=False, conv_resample=False),      # the parameter-free pool / nearest-x2 ops
+    "classcond": dict(TINY, num_classes=10),
+    "differentiable": UPDOWN,   # (its pool + affine and GroupNorm passes then run on per-site statistics)
+}
+
+
+def fwd_model(tag, prec, seed=0):
+    m = UNetModel(precision=prec, **FWD_NETS[tag])
+    m.load_state_dict(synth_state_dict(param_shapes(m), 7500 + seed))
+    return m
+
+
+def fwd_engine(tag, prec, differentiable=False, **debug):
+    m = fwd_model(tag, prec)
+    if debug:
+        m.debug = _lib.debug_config(**debug)
+    return m.to(DEV).engine(DEV, differentiable=differentiable)
+
+
+def inventory():
+    for tag in FWD_NETS:
+        m = fwd_model(tag, "fp32")
+        for prec in ("fp32", "bf16"):
+            cfg = _lib.make_config(dtype=_PREC[prec], differentiable=tag == "differentiable", debug=None, **m._cfg_kwargs())
+            inv = param_inventory(cfg)
+            text = "\n".join(f"{n} {s}" for n, s in inv)
+            emit(f"inventory {tag} {prec} params={len(inv)} sha256={hashlib.sha256(text.encode()).hexdigest()} "
+                 f"weight_bytes={_lib.lib().mi355_unet_weight_bytes(cfg)}")
+            KEPT[f"inventory/{tag}/{prec}"] = text
+
+
+def fwd_case(prec, name, eng, b, cond=False, y=None, euler=False, vjp=False):
+    """One forward at batch b (and its profile(), read_tensor verdicts; optionally a 4-step Euler loop / the vjp behind it)."""
+    sz, cin = eng.image_size, eng.in_channels
+    x = randn(7601, b, 3, sz, sz).to(DEV)
+    c = (randn(7602, b, cin - 3, sz, sz) * 0.5).to(DEV) if cond else None
+    t = torch.linspace(0.1, 0.9, b).to(DEV)
+    out = eng.forward(x, t, cond=c, y=y)
+    torch.cuda.synchronize()
+    eng.check()
+    launches = eng.stats(b)["launches"]
+    outs = {"out": out}
+    if vjp:
+        outs["grad_x"] = eng.vjp(randn(7603, b, 3, sz, sz).to(DEV))
+    verdicts = []
+    for op in eng.plan_ops():
+        if op["kind"] != 1 or op["dst"] < 0:
+            continue
+        try:
+            eng.read_tensor(op["dst"], b, (op["dst_c"], op["dst_h"], op["dst_h"]))
+            verdicts.append("0")
+        except MI355BackendError as e:
+            verdicts.append("1" if "did not materialise" in str(e) else "2" if "normalised this conv output in place" in str(e) else "?")
+    recs = eng.profile(x, t, cond=c) if y is None else []   # (profile() has no labelled form)
+    torch.cuda.synchronize()
+    if MARK[0]:
+        torch.arange(4, device=DEV).flip(0)
+    for k, v in outs.items():
+        v = v.detach().cpu().contiguous()
+        KEPT[f"{prec}/{name}/{k}"] = v
+        emit(f"{prec} {name} {k} {tuple(v.shape)} sha256={hashlib.sha256(v.numpy().tobytes()).hexdigest()} launches={launches}")
+    emit(f"{prec} {name} read_tensor {''.join(verdicts)}")
+    emit(f"{prec} {name} profile launches_after={eng.stats(b)['launches']} " + ";".join(
+        f"{r['kind']}/{r['ks']}/{r['cin']}/{r['cout']}/{r['h']}x{r['w']}/{r['tile'][0]}x{r['tile'][1]}/{r['flops']!r}/{r['bytes']!r}" for r in recs))
+    if euler:
+        xs = eng.cfm_euler(x.clone(), span(4), cond=c, y=y)[0]
+        torch.cuda.synchronize()
+        eng.check()
+        n = eng.stats(b)["launches"]
+        if MARK[0]:
+            torch.arange(4, device=DEV).flip(0)
+        xs = xs.detach().cpu().contiguous()
+        KEPT[f"{prec}/{name}/euler4"] = xs
+        emit(f"{prec} {name} euler4 {tuple(xs.shape)} sha256={hashlib.sha256(xs.numpy().tobytes()).hexdigest()} launches={n}")
+
+
+def run_forward(prec):
+    pp = _lib.debug_config().conv_pp
+    knobs = [("default", {}), ("gn_epilogue0", dict(gn_epilogue=0)), ("gn_epilogue1", dict(gn_epilogue=1)), ("gn_epilogue3", dict(gn_epilogue=3)),
+             ("conv_small7", dict(conv_small=7)), ("gn_fuse0", dict(gn_fuse=0))]
+    for kname, kw in knobs:
+        e = fwd_engine("cifar", prec, **kw)
+        for b in (8, 256):   # fewer tiles than CUs (generic tiles, K-sharing small-level forms) | persistent kernels, in-place 16x16 norm
+            fwd_case(prec, f"fwd_cifar_{kname}_b{b}", e, b)
+        del e
+    for tag in ("two_level", "two_level_in6"):   # first conv reading NCHW, last conv applying the Euler step - and neither
+        for edge in (15, 3):
+            fwd_case(prec, f"fwd_{tag}_edge{edge}_b18", fwd_engine(tag, prec, conv_edge=edge), 18, cond=tag.endswith("in6"), euler=True)
+    fwd_case(prec, "fwd_cifar_in6_b8", fwd_engine("cifar_in6", prec), 8, cond=True)
+    for tag in ("updown", "updown_noconv", "plain_resample"):
+        fwd_case(prec, f"fwd_{tag}_b3", fwd_engine(tag, prec), 3)
+    cc = fwd_engine("classcond", prec)
+    fwd_case(prec, "fwd_classcond_b3", cc, 3, y=torch.tensor([3, 0, 8], device=DEV), euler=True)   # per-forward rows, then table rows
+    if prec == "bf16":
+        e = fwd_engine("cifar_film", prec)
+        for b in (8, 256):
+            fwd_case(prec, f"fwd_cifar_film_b{b}", e, b)
+        del e
+        for bit in (1, 0):   # batch 64: the smallest where the phase-form upsample conv is eligible
+            fwd_case(prec, f"fwd_cifar_pp_phase{bit}_b64", fwd_engine("cifar", prec, conv_pp=(pp | 64) if bit else (pp & ~64)), 64)
+    if prec == "fp32":
+        fwd_case(prec, "fwd_differentiable_b3", fwd_engine("differentiable", prec, differentiable=True), 3, vjp=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--out", help="also write the lines to this file")
     ap.add_argument("--save", help="keep every output tensor in this torch file")
     ap.add_argument("--mark", action="store_true", help="one torch.flip launch behind every case: the cut marks of a kernel trace")
     ap.add_argument("--precisions", default="fp32,bf16")
+    ap.add_argument("--cases", default="sampler", help="comma list of: sampler (the loops), forward (single forwards)")
+    ap.add_argument("--inventory", action="store_true", help="no GPU: parameter inventories and weight-image bytes of the forward nets only")
     a = ap.parse_args()
     MARK[0] = a.mark
     emit(f"mi355_version {_lib.lib().mi355_version()}")
-    for prec in a.precisions.split(","):
-        run(prec)
+    if a.inventory:
+        inventory()
+    for prec in () if a.inventory else a.precisions.split(","):
+        if "sampler" in a.cases.split(","):
+            run(prec)
+        if "forward" in a.cases.split(","):
+            run_forward(prec)
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(LINES) + "\n")
