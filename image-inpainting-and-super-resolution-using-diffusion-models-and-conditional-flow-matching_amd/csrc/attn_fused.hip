@@ -687,6 +687,7 @@ int attn_fused_launch(const AttnFusedDesc& d, hipStream_t stream) {
     if (!(knob >> 8) && d.N < 2 * lanes) lanes = 0;   // fewer than two images per workgroup: nothing to amortise
     if (lanes > d.N) lanes = d.N;
   }
+  if (d.form) { d.form[0] = lanes > 0 ? 2 : 1; d.form[1] = lanes > 0 ? d.C / 32 : (d.T == 256 ? 2 : 1); d.form[2] = lanes; }
   if (lanes > 0 && d.dtype == DT_F16) rc = d.C == 256 ? launch_fused_pers<8, f16>(a, lanes, stream) : launch_fused_pers<4, f16>(a, lanes, stream);
   else if (lanes > 0) rc = d.C == 256 ? launch_fused_pers<8, bf16>(a, lanes, stream) : launch_fused_pers<4, bf16>(a, lanes, stream);
   else rc = dispatch_dtype(d.dtype, [&](auto t) { using T = decltype(t); return d.T == 256 ? launch_fused<T, 2>(a, stream) : launch_fused<T, 1>(a, stream); });

@@ -187,6 +187,7 @@ struct AttnFusedDesc {
   void* out = nullptr;
   int N = 0, T = 0, C = 0, heads = 0, ch = 0, new_order = 0;
   const mi355_debug_config* knobs = nullptr;
+  int* form = nullptr;   // optional out, 3 words, written by attn_fused_launch as it decides: {1 per-image | 2 persistent, QB | NCH, 0 | image lanes}
 };
 bool attn_fused_eligible(int dtype, int T, int C, int heads, int ch, const mi355_debug_config* knobs = nullptr);
 int attn_fused_launch(const AttnFusedDesc& d, hipStream_t stream);

@@ -322,6 +322,43 @@ int mi355_qkv_attention_vjp(const float* qkv, const float* grad_out, float* grad
   return unpack_nchw_launch(dtype, dq, batch, length, 3 * C, grad_qkv, s);
 }
 
+// ---- the fused AttentionBlock front half (ABI 108): attn_fused_launch as the engine calls it, (a, b) given instead of derived ------
+int mi355_attn_block_fused(const float* x, const float* a, const float* b, const float* w_host, const float* bias_host, float* out, int batch,
+                           int channels, int length, int heads, int new_order, int dtype, const mi355_debug_config* debug, int32_t form[3],
+                           void* workspace, int64_t workspace_bytes, void* stream) {
+  if (form) form[0] = form[1] = form[2] = -1;
+  MI355_REQUIRE(x && a && b && w_host && bias_host && out && workspace, -1, "attn_block_fused: null argument");
+  MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_BF16 || dtype == MI355_F16, -1, "attn_block_fused: dtype must be MI355_F32, MI355_BF16 or MI355_F16");
+  MI355_REQUIRE(batch > 0 && channels > 0 && length > 0 && heads > 0, -1, "attn_block_fused: bad sizes");
+  dtype = dtype == MI355_F16 ? DT_F16 : dtype;
+  hipStream_t s = S(stream);
+  const int C = channels;
+  AttnFusedDesc d; d.dtype = dtype; d.N = batch; d.T = length; d.C = C; d.heads = heads; d.ch = C / heads; d.new_order = new_order;
+  d.knobs = debug; d.form = form;
+  // a shape the fused kernels do not take is the launcher's own refusal, before anything is enqueued
+  if (!attn_fused_eligible(d.dtype, d.T, d.C, d.heads, d.ch, d.knobs)) return attn_fused_launch(d, s);
+  const size_t esz = dtype == DT_F32 ? 4 : 2;
+  const size_t wbytes = conv_packed_weight_bytes(dtype, 3 * C, C, 1, 0);
+  char* p = reinterpret_cast<char*>(workspace);
+  void* xin = p; p += al256((size_t)batch * length * C * esz);
+  void* o = p; p += al256((size_t)batch * length * C * esz);
+  void* wdev = p; p += al256(wbytes);
+  float* bdev = reinterpret_cast<float*>(p); p += al256((size_t)3 * C * 4);
+  MI355_REQUIRE(p <= reinterpret_cast<char*>(workspace) + workspace_bytes, -2, "attn_block_fused: workspace too small");
+  int rc;
+  if ((rc = pack_nhwc_launch(dtype, x, C, nullptr, 0, batch, length, C, xin, s))) return rc;
+  std::vector<char> packed(wbytes);
+  conv_pack_weights(dtype, w_host, 3 * C, C, 1, packed.data(), 0);
+  MI355_CHECK_HIP(hipMemcpyAsync(wdev, packed.data(), wbytes, hipMemcpyHostToDevice, s));
+  MI355_CHECK_HIP(hipMemcpyAsync(bdev, bias_host, (size_t)3 * C * 4, hipMemcpyHostToDevice, s));
+  MI355_CHECK_HIP(hipMemsetAsync(o, 0xFF, (size_t)batch * length * C * esz, s));   // NaN in every element type until the kernel writes it
+  d.x = xin; d.ga = a; d.gb = b; d.w = wdev; d.bias = bdev; d.out = o;
+  if ((rc = attn_fused_launch(d, s))) return rc;
+  if ((rc = unpack_nchw_launch(dtype, o, batch, length, C, out, s))) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));   // `packed` is a temporary host buffer
+  return 0;
+}
+
 // ---- GroupNorm test ops (ABI 107): the kernels the network launches, one op each, NCHW fp32 at the boundary ------------------------
 // Device scratch is the op's own (ExScratch); every op synchronises the stream before it returns.
 namespace {

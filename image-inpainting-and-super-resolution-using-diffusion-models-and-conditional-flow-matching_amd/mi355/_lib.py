@@ -172,6 +172,7 @@ SIGNATURES = {
                              _I64, _VP, C.POINTER(ConvExtrasC)]),
     "mi355_qkv_attention": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I64, _VP]),
     "mi355_qkv_attention_vjp": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I64, _VP]),
+    "mi355_attn_block_fused": (_I, [_VP, _VP, _VP, _FP, _FP, _VP, _I, _I, _I, _I, _I, _I, C.POINTER(DebugConfigC), C.POINTER(C.c_int32), _VP, _I64, _VP]),
     "mi355_gn_affine": (_I, [_VP, _VP, _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP, _I, C.POINTER(C.c_int32), _I, _I, _I, _I, _I, _VP]),
     "mi355_conv2d_gn": (_I, [_VP, _FP, _FP, _VP, _I, _I, _VP, _FP, _FP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _I,
                              C.POINTER(DebugConfigC), C.POINTER(C.c_int32), _VP]),

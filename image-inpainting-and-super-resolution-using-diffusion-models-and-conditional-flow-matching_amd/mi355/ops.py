@@ -425,6 +425,28 @@ class Ops:
                                         dtype, C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_qkv_attention_vjp")
         return gq
 
+    def attn_block_fused(self, x, a, b, weight, bias, heads, new_order=False, dtype=_lib.MI355_F32, debug=None):
+        """The fused AttentionBlock front half (mi355_attn_block_fused): attention(qkv(a x + b)) in one kernel.  x [B, C, T]; a, b [B, C] device
+        tensors (the per-image, per-channel affine); weight [3C, C] or [3C, C, 1] / bias [3C]: CPU tensors in the reference layout.
+        -> (out [B, C, T], form): form = ("image", QB) for the per-(image, head) kernel or ("persistent", NCH, lanes)."""
+        B, Cc, T = x.shape
+        if tuple(a.shape) != (B, Cc) or tuple(b.shape) != (B, Cc):
+            raise ValueError(f"a and b must be {(B, Cc)}")
+        w = weight.detach().to("cpu", torch.float32).reshape(weight.shape[0], -1).contiguous()
+        bh = bias.detach().to("cpu", torch.float32).contiguous()
+        if tuple(w.shape) != (3 * Cc, Cc) or tuple(bh.shape) != (3 * Cc,):
+            raise ValueError(f"weight must be {(3 * Cc, Cc)} and bias {(3 * Cc,)}")
+        out = torch.empty(B, Cc, T, device=x.device, dtype=torch.float32)
+        L = _lib.lib()
+        wsb = L.mi355_op_workspace_bytes(B, 3 * Cc, T)
+        ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
+        fp = C.POINTER(C.c_float)
+        form = (C.c_int32 * 3)(-1, -1, -1)
+        check(L.mi355_attn_block_fused(_req(x, "x"), _req(a, "a"), _req(b, "b"), C.cast(w.data_ptr(), fp), C.cast(bh.data_ptr(), fp), _req(out, "out"),
+                                       B, Cc, T, heads, int(new_order), dtype, C.byref(debug if debug is not None else _lib.debug_config()),
+                                       form, C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_attn_block_fused")
+        return out, (("image", form[1]) if form[0] == 1 else ("persistent", form[1], form[2]))
+
     # --- GroupNorm32 test ops: the kernels the network launches, one op each (NCHW fp32 tensors; see include/mi355_sampler.h) ---
     def gn_affine(self, x, gamma, beta, x1=None, film=None, eps=1e-5, dtype=_lib.MI355_F32, apply=None, stats=True):
         """gn_affine_kernel on x [B, C0, *] (and x1 [B, C1, *], the channel concat).  apply: None, "affine" or "silu" (also write y).

@@ -42,7 +42,8 @@ extern "C" {
                      * precision mode (UNetModel(use_fp16=True) runs its torso in float16, AD/image_diffusion/unet.py:559-563): bf16's speed, three more
                      * mantissa bits on every stored activation and weight; values beyond +-65504 overflow to inf as they do in the reference */
 
-/* ABI version = 100 * major + minor.  The minor number counts additive changes; 107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+/* ABI version = 100 * major + minor.  The minor number counts additive changes; 108: mi355_attn_block_fused (the fused AttentionBlock front half,
+ * csrc/attn_fused.hip, as a test op that reports which kernel form it launched; a new symbol only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -556,6 +557,19 @@ int mi355_qkv_attention(const float* qkv, float* out, int batch, int heads, int 
  * workspace: mi355_op_workspace_bytes(batch, 3 * H * ch, T) suffices. */
 int mi355_qkv_attention_vjp(const float* qkv, const float* grad_out, float* grad_qkv, int batch, int heads, int head_channels, int length,
                             int new_order, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The front half of an AttentionBlock in one kernel (ABI 108; csrc/attn_fused.hip, unet.py:395-401): out [B, C, T] = attention(qkv(a x + b)), head size
+ * C / heads.  x [B, C, T]; a, b [B, C] DEVICE fp32: the per-(image, channel) affine GroupNorm would apply, given directly (any values: a test can make
+ * every image's table different); w_host [3C, C], bias_host [3C] HOST pointers: the qkv 1x1 conv in the reference layout.  The op packs x to NHWC in
+ * `dtype` (F32 / BF16 / F16), packs and uploads the weights (ks = 1), calls attn_fused_launch as the engine does and unpacks; the output buffer starts as
+ * NaN.  A shape the fused kernels do not take (head size != 64, T not 128 / 256, C not 128 / 256 / 384 / 512, heads * 64 != C, attn_fused bit 0 clear)
+ * comes back as the launcher's own MI355_ERR_UNSUPPORTED "shape not supported" with nothing enqueued.  form (host, 3 words, may be NULL) = what the
+ * launcher decided: {1, QB, 0} the per-(image, head) kernel with QB = T / 128 query blocks per wave, {2, NCH, lanes} the persistent kernel with NCH = C / 32
+ * resident weight chunks walking `lanes` image lanes; {-1, -1, -1} if nothing was launched.  debug->attn_fused selects forms as in a network: bit 1 never
+ * the persistent form, bits 8.. its image lanes.  workspace: mi355_op_workspace_bytes(batch, 3 * channels, length) suffices.  Synchronises `stream`. */
+int mi355_attn_block_fused(const float* x, const float* a, const float* b, const float* w_host, const float* bias_host, float* out, int batch,
+                           int channels, int length, int heads, int new_order, int dtype, const mi355_debug_config* debug, int32_t form[3],
+                           void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- GroupNorm32 test ops (ABI 107): the statistics, apply and backward kernels the network launches, one op each ------------------
  * Tensors are NCHW fp32 device tensors; the ops pack them to NHWC in `dtype`, launch the descriptor the engine builds and unpack.  Scratch is

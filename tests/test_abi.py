@@ -21,7 +21,7 @@ def test_build_and_symbols():
     for name in sorted(declared):
         assert hasattr(L, name), f"{name} declared in the header but not exported"
     assert set(_lib.SIGNATURES) == declared, (set(_lib.SIGNATURES) ^ declared)
-    assert L.mi355_version() == 107
+    assert L.mi355_version() == 108
 
 
 def test_plan_builder_on_cpu():

@@ -23,7 +23,7 @@ def test_library_exports_the_new_symbols():
     L = _lib.lib()
     for name in NEW_SYMBOLS:
         assert name in _lib.SIGNATURES and hasattr(L, name), name
-    assert L.mi355_version() == 107   # additive: new symbols only
+    assert L.mi355_version() == 108   # additive: new symbols only
     # the size functions refuse a null handle and a bad stage count on the host
     assert L.mi355_cfg_workspace_bytes(None, 4, 1) < 0 and L.mi355_ddpm_cfg_workspace_bytes(None, 4) < 0
     assert b"stages" in L.mi355_last_error() or b"bad argument" in L.mi355_last_error()

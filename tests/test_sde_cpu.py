@@ -244,4 +244,4 @@ def test_new_symbols_are_exported():
     for name in ("mi355_sf2m_euler_sample", "mi355_sde_euler_step"):
         assert name in _lib.SIGNATURES
         assert hasattr(L, name)
-    assert L.mi355_version() == 107
+    assert L.mi355_version() == 108
