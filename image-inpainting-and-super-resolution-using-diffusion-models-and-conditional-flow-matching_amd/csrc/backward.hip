@@ -191,6 +191,102 @@ __global__ void __launch_bounds__(256) guidance_seed_kernel(const float* x, cons
   g_x[i] = c_recip * g;
 }
 
+// ---- low-resolution consistency seed: the seed above with a real down-sampling operator in the constraint ------------------------------
+// loss_n = mean over the sample's C * hl * wl low-res entries of (D(x0) - y_low)^2, x0 = clip(pre) as above, D = F.interpolate(size = (hl, wl),
+// mode = "bilinear", align_corners = False): the taps, weights and operation order of resize_bilinear_kernel (steps.hip).  Integer factors only
+// (H % hl == 0, W % wl == 0): the two taps of a low-res pixel along an axis then lie inside its own block of H / hl source pixels, so the adjoint
+// D^T is a gather - source pixel (Y, X) receives from low-res pixel (Y / sy, X / sx) alone - written with plain stores.
+//   resid = D(x0) - y_low                     lowres_resid_kernel, one thread per low-res element, x0 formed at the four taps
+//   loss_n = mean(resid^2)                    lowres_loss_kernel, one workgroup per sample (fp64 sums in a fixed order, as mse_per_sample_kernel)
+//   g = k * ((wy * wx) * resid), k = 2 / (C hl wl); g = 0 where pre is outside [-1, 1] or NaN; g_eps = -c_recipm1 g, g_x = c_recip g
+//                                             lowres_adjoint_kernel, four consecutive elements of a row per thread
+struct LinTaps { int i0, i1; float l0, l1; };
+// the two source taps of output index o along an axis of `size` source pixels (resize_bilinear_kernel's arithmetic, every operation rounded)
+__device__ __forceinline__ LinTaps lin_taps(int o, float scale, int size) {
+#pragma clang fp contract(off)
+  float f = scale * ((float)o + 0.5f) - 0.5f; f = f < 0.f ? 0.f : f;
+  LinTaps t;
+  t.i0 = (int)f;
+  t.i1 = t.i0 + (t.i0 < size - 1 ? 1 : 0);
+  t.l1 = fminf(fmaxf(f - (float)t.i0, 0.f), 1.f);
+  t.l0 = 1.f - t.l1;
+  return t;
+}
+__device__ __forceinline__ float seed_pre(float x, float eps, float c_recip, float c_recipm1) { return c_recip * x - c_recipm1 * eps; }
+
+__global__ void __launch_bounds__(256) lowres_resid_kernel(const float* x, const float* eps, const float* y_low, float c_recip, float c_recipm1,
+                                                         int64_t planes, int H, int W, int hl, int wl, float sh, float sw, float* resid) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= planes * hl * wl) return;
+  const int ox = (int)(idx % wl);
+  const int oy = (int)((idx / wl) % hl);
+  const int64_t base = idx / ((int64_t)wl * hl) * (int64_t)H * W;
+  const LinTaps ty = lin_taps(oy, sh, H), tx = lin_taps(ox, sw, W);
+  auto x0 = [&](int yy, int xx) {
+    const int64_t e = base + (int64_t)yy * W + xx;
+    return clip_nan(seed_pre(x[e], eps[e], c_recip, c_recipm1), -1.f, 1.f);
+  };
+  const float v00 = x0(ty.i0, tx.i0), v01 = x0(ty.i0, tx.i1), v10 = x0(ty.i1, tx.i0), v11 = x0(ty.i1, tx.i1);
+  {
+#pragma clang fp contract(off)
+    const float d = ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
+    resid[idx] = d - y_low[idx];
+  }
+}
+
+__global__ void __launch_bounds__(256) lowres_loss_kernel(const float* resid, float* loss, int64_t per) {
+  __shared__ double sh[4];
+  const float* p = resid + (int64_t)blockIdx.x * per;
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < per; i += 256) acc += (double)p[i] * (double)p[i];
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) loss[blockIdx.x] = (float)((sh[0] + sh[1] + sh[2] + sh[3]) / (double)per);
+}
+
+// element e of the [planes, H, W] state: its gradient through the clip from the one low-res pixel whose taps can reach it
+__device__ __forceinline__ float lowres_adjoint_elem(int64_t e, float pre, const float* resid, int H, int W, int hl, int wl, int sy, int sx, float sh,
+                                                     float sw, float k) {
+#pragma clang fp contract(off)
+  const int X = (int)(e % W);
+  const int Y = (int)((e / W) % H);
+  const int64_t pl = e / ((int64_t)W * H);
+  const int ly = Y / sy, lx = X / sx;
+  const LinTaps ty = lin_taps(ly, sh, H), tx = lin_taps(lx, sw, W);
+  const float wy = (Y == ty.i0 ? ty.l0 : 0.f) + (Y == ty.i1 ? ty.l1 : 0.f);
+  const float wx = (X == tx.i0 ? tx.l0 : 0.f) + (X == tx.i1 ? tx.l1 : 0.f);
+  const float w = wy * wx;
+  const float t = w * resid[(pl * hl + ly) * wl + lx];
+  const float g = k * t;
+  return (pre >= -1.f && pre <= 1.f) ? g : 0.f;
+}
+
+__global__ void __launch_bounds__(256) lowres_adjoint_kernel(const float* x, const float* eps, const float* resid, float c_recip, float c_recipm1,
+                                                           int64_t n, int H, int W, int hl, int wl, float sh, float sw, float k, float* g_eps,
+                                                           float* g_x, int vec) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= n) return;
+  const int sy = H / hl, sx = W / wl;
+  if (i + 4 <= n && vec) {   // vec: every pointer is 16-byte aligned and W % 4 == 0 (checked once by the launcher)
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i), ev = *reinterpret_cast<const f32x4*>(eps + i);
+    f32x4 ge, gx;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float g = lowres_adjoint_elem(i + j, seed_pre(xv[j], ev[j], c_recip, c_recipm1), resid, H, W, hl, wl, sy, sx, sh, sw, k);
+      ge[j] = -c_recipm1 * g; gx[j] = c_recip * g;
+    }
+    *reinterpret_cast<f32x4*>(g_eps + i) = ge;
+    *reinterpret_cast<f32x4*>(g_x + i) = gx;
+  } else {
+    const int64_t end = i + 4 < n ? i + 4 : n;
+    for (int64_t e = i; e < end; ++e) {
+      const float g = lowres_adjoint_elem(e, seed_pre(x[e], eps[e], c_recip, c_recipm1), resid, H, W, hl, wl, sy, sx, sh, sw, k);
+      g_eps[e] = -c_recipm1 * g; g_x[e] = c_recip * g;
+    }
+  }
+}
+
 // x_grad = g_x + vjp; update = -scale * x_grad; optionally x += update ("before"); update is kept for the "after" rule
 __global__ void __launch_bounds__(256) guidance_update_kernel(float* x, const float* g_x, const float* vjp, float scale, int apply, float* update,
                                                             int64_t n) {
@@ -264,6 +360,30 @@ int guidance_seed_launch(const float* x, const float* eps, const float* cond, fl
   MI355_REQUIRE(x && eps && cond && g_eps && g_x && n > 0 && per > 0, -1, "guidance_seed: bad argument");
   hipLaunchKernelGGL(guidance_seed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, eps, cond, c_recip, c_recipm1, mode, pad,
                      1.0f / (float)per, g_eps, g_x, n);
+  MI355_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int lowres_seed_launch(const float* x, const float* eps, const float* y_low, float c_recip, float c_recipm1, int B, int C, int H, int W, int hl,
+                       int wl, float* resid, float* g_eps, float* g_x, float* loss, hipStream_t s) {
+  MI355_REQUIRE(x && eps && y_low && resid && g_eps && g_x, -1, "lowres_seed: null argument");
+  MI355_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && hl > 0 && wl > 0, -1, "lowres_seed: bad argument");
+  MI355_REQUIRE(H % hl == 0 && W % wl == 0, -4,
+                "lowres_seed: the low resolution must divide the state's (integer factors only: the adjoint is a gather)");
+  const int64_t planes = (int64_t)B * C, n = planes * H * W, nl = planes * hl * wl, per = (int64_t)C * hl * wl;
+  const float sh = (float)H / (float)hl, sw = (float)W / (float)wl;
+  hipLaunchKernelGGL(lowres_resid_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, x, eps, y_low, c_recip, c_recipm1, planes, H, W, hl, wl,
+                     sh, sw, resid);
+  MI355_CHECK_HIP(hipGetLastError());
+  if (loss) {
+    hipLaunchKernelGGL(lowres_loss_kernel, dim3((unsigned)B), dim3(256), 0, s, resid, loss, per);
+    MI355_CHECK_HIP(hipGetLastError());
+  }
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(g_eps) | reinterpret_cast<uintptr_t>(g_x);
+  const int vec = (bits & 15) == 0 && W % 4 == 0;
+  const int64_t nth = (n + 3) / 4;
+  hipLaunchKernelGGL(lowres_adjoint_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s, x, eps, resid, c_recip, c_recipm1, n, H, W, hl, wl, sh, sw,
+                     2.0f / (float)per, g_eps, g_x, vec);
   MI355_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -218,6 +218,10 @@ int mi355_guidance_seed(const float* x, const float* eps, const float* cond, flo
 int mi355_guidance_update(float* x, const float* g_x, const float* vjp, float scale, int apply, float* update, int64_t n, void* stream) {
   return guidance_update_launch(x, g_x, vjp, scale, apply, update, n, S(stream));
 }
+int mi355_lowres_seed(const float* x, const float* eps, const float* y_low, float c_recip, float c_recipm1, int batch, int channels, int h, int w,
+                      int h_low, int w_low, float* resid, float* g_eps, float* g_x, float* loss, void* stream) {
+  return lowres_seed_launch(x, eps, y_low, c_recip, c_recipm1, batch, channels, h, w, h_low, w_low, resid, g_eps, g_x, loss, S(stream));
+}
 int mi355_ema_update(float* target, const float* source, float decay, float one_minus_decay, int64_t n, void* stream) {
   MI355_REQUIRE(target && source, -1, "ema_update: null argument");
   return ema_update_launch(target, source, decay, one_minus_decay, n, S(stream));

@@ -217,6 +217,10 @@ int attention_bwd_launch(const AttnBwdDesc& d, hipStream_t stream);
 int guidance_seed_launch(const float* x, const float* eps, const float* cond, float c_recip, float c_recipm1, int mode, float pad,
                          int64_t per, float* g_eps, float* g_x, int64_t n, hipStream_t s);
 int guidance_update_launch(float* x, const float* g_x, const float* vjp, float scale, int apply, float* update, int64_t n, hipStream_t s);
+// the seed of the low-resolution consistency term mean((D(x0) - y_low)^2), D the bilinear reduction to hl x wl (H % hl == 0, W % wl == 0, else -4
+// before a launch): resid [B,C,hl,wl] scratch, loss [B] or null; two launches, three with loss
+int lowres_seed_launch(const float* x, const float* eps, const float* y_low, float c_recip, float c_recipm1, int B, int C, int H, int W, int hl,
+                       int wl, float* resid, float* g_eps, float* g_x, float* loss, hipStream_t s);
 // out[n][c][hw] (NCHW fp32, c < count) = in[n][hw][c0 + c] (NHWC T, row stride `stride`)
 int unpack_channels_launch(int dtype, const void* in, int N, int HW, int stride, int c0, int count, float* out, hipStream_t s);
 

@@ -1,5 +1,6 @@
 // The sampler loops of libmi355_sampler.so (see include/mi355_sampler.h): workspace layouts, the embedding rows of the evaluations, and the
-// Euler (+ graph form), Runge-Kutta, DDPM, their classifier-free-guided forms, and SF2M entry points.  Host code only.
+// Euler (+ graph form), Runge-Kutta, DDPM, their classifier-free-guided forms, the replacement / reconstruction-guided flow sampler, and SF2M entry
+// points.  Host code only.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -26,11 +27,16 @@ struct Scratch { float* t; float* v; float* none; float* tsteps; float* embtab; 
 struct CfgTail { float* x2; float* cond2; int32_t* labels2; };
 // fixed-step Runge-Kutta: the stage derivatives k_1..k_s and the stage state y_i, each a state at the evaluation batch
 struct RkBufs { float* k[4]; float* ystage; };
-struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; uintptr_t end; };
+// training-free in-painting / super-resolution of a flow (mi355_cfm_recon_sample): the call's initial state (the noise end of the straight path the
+// "coupled" replacement pastes along), the seed's two outputs and the U-Net VJP, each a state; the low-res residual [B, C, h_low, w_low]
+struct ReconDims { int h_low, w_low; };
+struct ReconTail { float* x_init; float* g_eps; float* g_x; float* vjp; float* resid; };
+struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; ReconTail rec; uintptr_t end; };
 inline size_t cfg_cond_channels(const mi355_unet* net) { return (size_t)(net->cfg.in_channels > net->cfg.out_channels ? net->cfg.in_channels - net->cfg.out_channels : 0); }
 
-// guided: the network runs at 2 * batch and the guidance tail follows its workspace; stages > 0: the Runge-Kutta buffers close the layout
-Layout layout(const mi355_unet* net, int batch, bool guided, int stages, uintptr_t base) {
+// guided: the network runs at 2 * batch and the guidance tail follows its workspace; stages > 0: the Runge-Kutta buffers follow; recon: the
+// reconstruction tail closes the layout
+Layout layout(const mi355_unet* net, int batch, bool guided, int stages, uintptr_t base, const ReconDims* recon = nullptr) {
   const size_t hw = (size_t)net->cfg.image_size * net->cfg.image_size;
   const int B = guided ? 2 * batch : batch;
   const size_t state = (size_t)B * net->cfg.out_channels * hw * 4;
@@ -45,7 +51,7 @@ Layout layout(const mi355_unet* net, int batch, bool guided, int stages, uintptr
   l.sc.unet_bytes = unet_workspace_bytes(net, B);
   l.sc.unet_ws = reinterpret_cast<char*>(w.p);
   w.p += (size_t)l.sc.unet_bytes;   // not rounded up: mi355_unet_workspace_bytes ends here
-  if (guided || stages) w.p = al256(w.p);
+  if (guided || stages || recon) w.p = al256(w.p);
   if (guided) {
     l.cfg.x2 = w.take(state);
     l.cfg.cond2 = w.take((size_t)B * cfg_cond_channels(net) * hw * 4);
@@ -53,16 +59,23 @@ Layout layout(const mi355_unet* net, int batch, bool guided, int stages, uintptr
   }
   for (int i = 0; i < stages; ++i) l.rk.k[i] = w.take(state);
   if (stages > (guided ? 1 : 0)) l.rk.ystage = w.take(state);   // a one-stage guided sampler never forms a stage state (stage 1 reads the state itself)
+  if (recon) {
+    l.rec.x_init = w.take(state);
+    l.rec.g_eps = w.take(state);
+    l.rec.g_x = w.take(state);
+    l.rec.vjp = w.take(state);
+    l.rec.resid = w.take((size_t)B * net->cfg.out_channels * recon->h_low * recon->w_low * 4);
+  }
   l.end = w.p;
   return l;
 }
 inline int64_t layout_bytes(const mi355_unet* net, int batch, bool guided, int stages) { return (int64_t)layout(net, batch, guided, stages, 0).end; }
 
 // The layout of a sampler call in the caller's workspace.
-int carve(const mi355_unet* net, int batch, bool guided, int stages, void* workspace, int64_t workspace_bytes, Layout& l) {
+int carve(const mi355_unet* net, int batch, bool guided, int stages, void* workspace, int64_t workspace_bytes, Layout& l, const ReconDims* recon = nullptr) {
   MI355_REQUIRE(net && workspace, -1, "null argument");
   MI355_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, -1, "workspace must be 256-byte aligned");
-  l = layout(net, batch, guided, stages, reinterpret_cast<uintptr_t>(workspace));
+  l = layout(net, batch, guided, stages, reinterpret_cast<uintptr_t>(workspace), recon);
   MI355_REQUIRE(workspace_bytes >= (int64_t)(l.end - reinterpret_cast<uintptr_t>(workspace)), -2, "workspace too small");
   return 0;
 }
@@ -509,6 +522,104 @@ int mi355_ddpm_cfg_sample(mi355_unet* net, float* x, int channels, const float* 
   a.guide.on = true; a.guide.w = w; a.guide.w_dev = w_dev; a.guide.per = per;
   if (int rc = ddpm_loop(net, sc, emb, a, channels, tb, opt, noise, n_noise_draws, batch, n, s)) return rc;
   MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// Training-free in-painting / super-resolution of an unconditional flow: replacement along the straight path and / or reconstruction guidance
+// through the data estimate x1_hat = x + (1 - t) v, one Euler step per interval (include/mi355_sampler.h).  A guided step is forward -> seed ->
+// unet_backward -> ONE rk_stage launch over (v, g_x, vjp); an unguided one the stage launch over v alone.
+int64_t mi355_cfm_recon_workspace_bytes(const mi355_unet* net, int batch, int h_low, int w_low) {
+  if (!net || batch <= 0 || h_low < 0 || w_low < 0) { mi355_set_error("cfm_recon_workspace_bytes: bad argument"); return -1; }
+  const ReconDims rd{h_low, w_low};
+  return (int64_t)layout(net, batch, false, 0, 0, &rd).end;
+}
+
+int mi355_cfm_recon_sample(mi355_unet* net, float* x, int channels, const int32_t* labels, const float* t_span_host, int n_t, const float* y, int mode,
+                           float pad_value, int h_low, int w_low, const float* scales_host, int replace, int final_paste, const float* z, uint64_t seed,
+                           float* traj, uint8_t* u8_out, float* loss_out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && x && t_span_host && batch > 0, -1, "cfm_recon_sample: bad argument");
+  MI355_REQUIRE(n_t >= 1, -1, "cfm_recon_sample: the time span needs at least one time (n_t >= 1)");
+  MI355_REQUIRE(mode >= 0 && mode <= 2, -1, "cfm_recon_sample: mode must be 0 (painting), 1 (hyper-resolution) or 2 (low resolution)");
+  MI355_REQUIRE(replace >= 0 && replace <= 2, -1, "cfm_recon_sample: replace must be 0 (off), 1 (coupled) or 2 (fresh)");
+  MI355_REQUIRE(replace == 0 || mode == 0, -1, "cfm_recon_sample: replacement pastes the known pixels of a painting condition (mode 0)");
+  MI355_REQUIRE(final_paste == 0 || replace != 0, -1, "cfm_recon_sample: final_paste is the replacement's last paste (replace != 0)");
+  MI355_REQUIRE(net->cfg.in_channels == net->cfg.out_channels, -2,
+                "cfm_recon_sample: needs an unconditional net, in_channels == out_channels (amortized nets are not for this sampler)");
+  MI355_REQUIRE(channels == net->cfg.out_channels, -2, "cfm_recon_sample: the vector field must have the state's channel count");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_recon_sample: class labels given to a net built without num_classes");
+  bool any_scale = false;
+  for (int k = 0; scales_host && k + 1 < n_t; ++k) any_scale = any_scale || scales_host[k] != 0.f;
+  MI355_REQUIRE(y || (replace == 0 && !any_scale), -1, "cfm_recon_sample: replacement and guidance need the measurement y");
+  MI355_REQUIRE(!any_scale || net->cfg.differentiable, -4, "unet_vjp: the handle was not created with cfg.differentiable = 1");
+  MI355_REQUIRE(!loss_out || mode == 2, -1, "cfm_recon_sample: the per-step loss is the low-resolution seed's (mode 2)");
+  const int H = net->cfg.image_size, W = net->cfg.image_size;
+  if (mode == 2) {
+    MI355_REQUIRE(h_low > 0 && w_low > 0, -1, "cfm_recon_sample: mode 2 needs the low resolution (h_low, w_low)");
+    MI355_REQUIRE(H % h_low == 0 && W % w_low == 0, -4, "cfm_recon_sample: the low resolution must divide the state's (integer factors only)");
+  }
+  const ReconDims rd{mode == 2 ? h_low : 0, mode == 2 ? w_low : 0};
+  Layout l;
+  if (int rc = carve(net, batch, false, 0, workspace, workspace_bytes, l, &rd)) return rc;
+  const Scratch& sc = l.sc;
+  const ReconTail& rt = l.rec;
+  hipStream_t s = S(stream);
+  const int64_t per = (int64_t)channels * H * W, n = (int64_t)batch * per, n_al = (n + 3) / 4 * 4;
+  const int n_steps = n_t - 1;
+  EvalEmb emb;   // t_span_host is the caller's array: no wait
+  if (int rc = emb.init(net, sc, t_span_host, n_steps, labels != nullptr, false, s)) return rc;
+  if (replace == 1) MI355_CHECK_HIP(hipMemcpyAsync(rt.x_init, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (loss_out && n_steps > 0)   // rows of unguided steps: NaN (no loss was formed)
+    if (int rc = fill_launch(loss_out, __builtin_nanf(""), (int64_t)n_steps * batch, s)) return rc;
+  // x <- where(y == pad, x, t y + (1 - t) z_k): the known pixels on the straight path from the noise z_k to the measurement
+  auto paste = [&](int k) -> int {
+    const float t = t_span_host[k], omt = 1.0f - t;
+    const float* zk = replace == 1 ? rt.x_init : (z ? z + (size_t)k * n : nullptr);
+    return replace_mask_launch(x, y, zk, pad_value, 1, t, omt, zk ? 0 : 1, seed, zk ? 0 : (uint64_t)k * (uint64_t)n_al, n, s);
+  };
+  int64_t vjp_ops = 1;   // the adjoint ops unet_backward walks (each one or more launches) and its unpack: what a guided step adds to the count
+  for (const PlanOp& op : net->ops) vjp_ops += op.kind != OP_GN;
+  UnetRun run = uniform_t_run();   // no euler_x: the last conv stores v
+  run.labels = labels;
+  int64_t step_launches = 0;
+  int rc = 0;
+  for (int k = 0; k < n_steps; ++k) {
+    const float t = t_span_host[k], dt = t_span_host[k + 1] - t, omt = 1.0f - t;
+    step_launches = 0;
+    if (replace) { if ((rc = paste(k))) return rc; ++step_launches; }
+    if ((rc = emb.select(run, (size_t)k, batch, s, &step_launches))) return rc;
+    if ((rc = unet_forward(net, x, channels, nullptr, 0, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    step_launches += net->last_launches;
+    const float sk = scales_host ? scales_host[k] : 0.f;
+    const float* kp[4] = {sc.v, rt.g_x, rt.vjp, nullptr};
+    float cf[4] = {dt, 0.f, 0.f, 0.f};
+    int nk = 1;
+    if (sk != 0.f) {
+      // x1_hat = 1 * x - (-(1 - t)) * v: the seed kernels' pre = c_recip x - c_recipm1 eps with c_recip = 1, c_recipm1 = -(1 - t)
+      if (mode == 2) {
+        float* lk = loss_out ? loss_out + (size_t)k * batch : nullptr;
+        rc = lowres_seed_launch(x, sc.v, y, 1.f, -omt, batch, channels, H, W, h_low, w_low, rt.resid, rt.g_eps, rt.g_x, lk, s);
+        step_launches += lk ? 3 : 2;
+      } else {
+        rc = guidance_seed_launch(x, sc.v, y, 1.f, -omt, mode, pad_value, per, rt.g_eps, rt.g_x, n, s);
+        ++step_launches;
+      }
+      if (rc) return rc;
+      if ((rc = unet_backward(net, rt.g_eps, rt.vjp, channels, batch, sc.unet_ws, sc.unet_bytes, s))) return rc;
+      step_launches += vjp_ops;
+      const float c = dt * sk;   // rounded to fp32 here: x <- x + dt v - c g_x - c vjp
+      cf[1] = -c; cf[2] = -c; nk = 3;
+    }
+    const bool last = k + 1 == n_steps;
+    if ((rc = rk_stage_launch(x, x, kp, cf, nk, n, traj ? traj + (size_t)(k + 1) * n : nullptr, last && !final_paste ? u8_out : nullptr, s))) return rc;
+    ++step_launches;
+  }
+  if (final_paste) {   // at t = 1 this is 1 * y + 0 * z: the known pixels are the measurement itself
+    if ((rc = paste(n_t - 1))) return rc;
+    if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj + (size_t)n_steps * n, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  }
+  if (u8_out && (final_paste || n_steps == 0) && (rc = quantize_u8_launch(x, u8_out, n, s))) return rc;
+  if (n_steps > 0) net->last_launches = step_launches;   // mi355_unet_get_stats: the launches of the last step
   return 0;
 }
 

@@ -47,7 +47,8 @@ class ClassifierFreeGuidance(Amortized):
 
 
 class ReconstructionGuidance(Conditioning):
-    """Gradient guidance through the x0 predictor (sampling.py:136-206); needs the U-Net backward: not built yet."""
+    """Gradient guidance through the x0 predictor (sampling.py:136-206): the gradient is the HIP engine's vector-Jacobian product
+    (UNetEngine.vjp), so the sampler needs an eps_model made by make_eps_model around a UNetModel."""
     KEY, PARAMS = "reconstruction_guidance", ("gamma", "start_fraction", "update_rule", "n_corrector", "delta")
 
 
@@ -56,7 +57,53 @@ class Replacement(Conditioning):
     KEY, PARAMS = "replacement", ("delta", "start_fraction", "noise", "n_corrector")
 
 
-_REGISTRY: Dict[str, Type[Conditioning]] = {c.KEY: c for c in (Amortized, ClassifierFreeGuidance, ReconstructionGuidance, Replacement)}
+class FlowReplacement(Conditioning):
+    """Replacement for an unconditional flow-matching net (flow_sampling.py): during the first int(n_steps * start_fraction) steps the known
+    pixels are put on the straight path, x <- where(known, t y + (1 - t) z, x).  noise: "coupled" (z = the sample's own initial state) or
+    "fresh" (a new draw per step).  No reference counterpart."""
+    KEY, PARAMS = "flow_replacement", ("start_fraction", "noise")
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.noise not in ("coupled", "fresh"):
+            raise ValueError(f"noise must be 'coupled' or 'fresh', got {self.noise!r}")
+
+
+class FlowReconstructionGuidance(Conditioning):
+    """Reconstruction guidance for an unconditional flow-matching net (flow_sampling.py): during the first int(n_steps * start_fraction) steps
+    x <- x + dt v - dt s_k grad_x loss(x + (1 - t_k) v, y).  schedule: "constant" (s_k = gamma), "one_minus_t" (s_k = gamma (1 - t_k), both
+    factors and the product in fp32) or a callable t -> float.  replace: None, "coupled" or "fresh" (FlowReplacement's paste in the same steps;
+    painting likelihoods only).  No reference counterpart; the defaults are untested for sample quality."""
+    KEY, PARAMS = "flow_reconstruction_guidance", ("gamma", "start_fraction", "schedule", "replace")
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if not (self.schedule in ("constant", "one_minus_t") or callable(self.schedule)):
+            raise ValueError(f"schedule must be 'constant', 'one_minus_t' or a callable t -> float, got {self.schedule!r}")
+        if self.replace not in (None, "coupled", "fresh"):
+            raise ValueError(f"replace must be None, 'coupled' or 'fresh', got {self.replace!r}")
+
+    def scales(self, t_steps):
+        """The guidance scale of every step starting at the times t_steps, as fp32 values (Python floats that are exact fp32 numbers)."""
+        import torch
+
+        t = torch.tensor([float(v) for v in t_steps], dtype=torch.float32)
+        if callable(self.schedule):
+            s = torch.tensor([float(self.schedule(float(v))) for v in t], dtype=torch.float32)
+        elif self.schedule == "constant":
+            s = torch.full_like(t, float(self.gamma))
+        else:
+            s = torch.tensor(float(self.gamma), dtype=torch.float32) * (torch.tensor(1.0, dtype=torch.float32) - t)
+        return [float(v) for v in s]
+
+
+def flow_split_index(n_steps: int, start_fraction: float) -> int:
+    """How many of a flow sampler's n_steps steps, from the noise end, are conditioned: int(n_steps * start_fraction)."""
+    return int(n_steps * start_fraction)
+
+
+_REGISTRY: Dict[str, Type[Conditioning]] = {c.KEY: c for c in (Amortized, ClassifierFreeGuidance, ReconstructionGuidance, Replacement,
+                                                               FlowReplacement, FlowReconstructionGuidance)}
 
 
 def get_conditioning(type_: str) -> Type[Conditioning]:

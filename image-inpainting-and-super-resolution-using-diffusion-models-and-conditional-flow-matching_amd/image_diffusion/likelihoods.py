@@ -137,7 +137,36 @@ class HyperResolution(Likelihood):
         return F.mse_loss(_bilinear(condition, x.shape[-2:]), x)
 
 
-_BY_NAME: Dict[str, Type[Likelihood]] = {"inpainting": InPainting, "outpainting": OutPainting, "hyperresolution": HyperResolution}
+class LowResolution(Likelihood):
+    """The low-resolution measurement itself: y = D(x), the bilinear reduction to (target_height, target_width), and the consistency term
+    mean((D(x) - y)^2).  No reference counterpart: HyperResolution compares with the re-enlarged image and never applies D to the estimate
+    (likelihoods.py:134-139), so its guidance has no down-sampling operator.  The guided samplers take this likelihood's gradient from
+    mi355_lowres_seed, which needs the image size to be a multiple of the target size."""
+
+    def __init__(self, target_height: int, target_width: int):
+        self.target_height = target_height
+        self.target_width = target_width
+
+    @classmethod
+    def from_configdict(cls, config):
+        return cls(config["target_height"], config["target_width"])
+
+    def _sample(self, images):
+        return _bilinear(images, (self.target_height, self.target_width))
+
+    def sample(self, x):
+        return self._sample(x)   # per-image resizes are independent: the whole batch in one call (one launch on the device)
+
+    def none_like(self, x):
+        return torch.zeros(x.shape[0], x.shape[1], self.target_height, self.target_width, dtype=x.dtype, device=x.device)
+
+    def loss(self, x, condition):
+        d = self._sample(x) - condition
+        return (d * d).mean(dim=(1, 2, 3))
+
+
+_BY_NAME: Dict[str, Type[Likelihood]] = {"inpainting": InPainting, "outpainting": OutPainting, "hyperresolution": HyperResolution,
+                                         "lowresolution": LowResolution}
 
 
 def get_likelihood(type_: str) -> Type[Likelihood]:

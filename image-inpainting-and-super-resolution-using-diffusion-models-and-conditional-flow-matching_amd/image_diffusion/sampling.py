@@ -292,6 +292,8 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
         mode, pad = 0, float(likelihood.pad_value)      # Painting.loss (likelihoods.py:58-66)
     elif type(likelihood).__name__ == "HyperResolution":
         mode, pad = 1, 0.0                              # HyperResolution.loss (likelihoods.py:138-143)
+    elif type(likelihood).__name__ == "LowResolution":
+        mode, pad = 2, 0.0                              # mean((D(x0) - y)^2), D the bilinear reduction: mi355_lowres_seed
     else:
         raise NotImplementedError(f"no constraint gradient for likelihood {type(likelihood).__name__}")
 
@@ -313,8 +315,12 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
             update, eps = None, None
             if i < n_guided:
                 eps = deng.forward(xi, t)
-                g_eps, g_x = _ops.guidance_seed(xi, eps, condition, float(T["sqrt_recip_alphas_cumprod"][i]),
-                                                float(T["sqrt_recipm1_alphas_cumprod"][i]), mode, pad)
+                if mode == 2:
+                    g_eps, g_x, _ = _ops.lowres_seed(xi, eps, condition, float(T["sqrt_recip_alphas_cumprod"][i]),
+                                                     float(T["sqrt_recipm1_alphas_cumprod"][i]))
+                else:
+                    g_eps, g_x = _ops.guidance_seed(xi, eps, condition, float(T["sqrt_recip_alphas_cumprod"][i]),
+                                                    float(T["sqrt_recipm1_alphas_cumprod"][i]), mode, pad)
                 vjp = deng.vjp(g_eps)
                 a_i = float(alphas[i])
                 scale = float(conditioning.gamma) * a_i * (1.0 - a_i)

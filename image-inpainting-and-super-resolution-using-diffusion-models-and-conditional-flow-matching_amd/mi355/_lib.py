@@ -132,6 +132,8 @@ SIGNATURES = {
     "mi355_ddpm_cfg_workspace_bytes": (_I64, [_VP, _I]),
     "mi355_ddpm_cfg_sample": (_I, [_VP, _VP, _I, _VP, _VP, _I, _F, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), _VP, _I64, _I, _VP, _I64,
                                    _VP]),
+    "mi355_cfm_recon_workspace_bytes": (_I64, [_VP, _I, _I, _I]),
+    "mi355_cfm_recon_sample": (_I, [_VP, _VP, _I, _VP, _FP, _I, _VP, _I, _F, _I, _I, _FP, _I, _I, _VP, _U64, _VP, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_sf2m_euler_sample": (_I, [_VP, _VP, _VP, _I, _VP, _FP, _I, _F, _I, _VP, _U64, C.POINTER(C.c_int32), _FP, _I, _VP, _I, _VP, _I64,
                                      _VP, _I64, _VP]),
     "mi355_ddpm_sample": (_I, [_VP, _VP, _I, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), _VP, _I64, _I, _VP, _I64, _VP]),
@@ -145,6 +147,7 @@ SIGNATURES = {
     "mi355_replace_mask": (_I, [_VP, _VP, _VP, _F, _I, _F, _F, _I, _U64, _U64, _I64, _VP]),
     "mi355_guidance_seed": (_I, [_VP, _VP, _VP, _F, _F, _I, _F, _I64, _VP, _VP, _I64, _VP]),
     "mi355_guidance_update": (_I, [_VP, _VP, _VP, _F, _I, _VP, _I64, _VP]),
+    "mi355_lowres_seed": (_I, [_VP, _VP, _VP, _F, _F, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "mi355_clip": (_I, [_VP, _F, _F, _I64, _VP]),
     "mi355_ema_update": (_I, [_VP, _VP, _F, _F, _I64, _VP]),
     "mi355_mse_per_sample": (_I, [_VP, _VP, _VP, C.c_int, _I64, _VP]),

@@ -436,6 +436,83 @@ class UNetEngine:
               "mi355_cfm_rk_sample")
         return x, traj, u8
 
+    def cfm_recon(self, x: torch.Tensor, t_span: Sequence[float], y: Optional[torch.Tensor], mode: int, *, scales: Optional[Sequence[float]] = None,
+                  replace: Optional[str] = None, final_paste: bool = False, pad_value: float = -2.0, noise: Optional[torch.Tensor] = None,
+                  seed: Optional[int] = None, keep_traj: bool = False, want_u8: bool = False, return_loss: bool = False,
+                  y_labels: Optional[torch.Tensor] = None):
+        """In-place training-free in-painting / super-resolution of x over t_span with this unconditional flow net, the whole loop one library
+        call (mi355_cfm_recon_sample): per step an optional paste of the known pixels onto the straight path, the forward, and - where
+        scales[k] != 0 - reconstruction guidance through x1_hat = x + (1 - t) v:  x <- x + dt v - dt scales[k] (g_x + vjp).
+        y: the measurement; mode 0: a painting condition [B, C, H, W] with pad_value at the unknown pixels, 1: a full-size image
+        (HyperResolution.loss), 2: a low-resolution image [B, C, h, w] with H % h == 0 and W % w == 0.
+        scales: None (no guidance: any engine) or one float per step (guidance needs differentiable=True).
+        replace: None, "coupled" (the known pixels follow the path from this call's own initial state to y) or "fresh" (a new draw per step:
+        noise [n_draws, B, C, H, W] injected, or device Philox noise keyed by `seed`; None: drawn from torch's default generator).
+        final_paste: one more paste after the last step.  return_loss (mode 2): the per-step, per-sample loss [n_steps, B] (NaN where a step
+        was not guided).  y_labels: class labels [B] of a class-conditional engine.
+        Returns (x, traj or None, u8 or None, loss or None).  A batch beyond max_batch() runs in slices that carry their rows of y, labels and
+        injected draws; with Philox noise each slice draws from its own key (seed + slice index)."""
+        B, Cx, _ = self._split(x, None)
+        if mode not in (0, 1, 2):
+            raise ValueError("mode must be 0 (painting), 1 (hyper-resolution) or 2 (low resolution)")
+        rep = {None: 0, "coupled": 1, "fresh": 2}.get(replace, -1)
+        if rep < 0:
+            raise ValueError(f"replace must be None, 'coupled' or 'fresh', got {replace!r}")
+        ts = [float(v) for v in t_span]
+        n_steps = len(ts) - 1
+        sc = None
+        if scales is not None:
+            sc = [float(v) for v in scales]
+            if len(sc) != n_steps:
+                raise ValueError(f"scales must have one entry per step ({n_steps}), got {len(sc)}")
+            if any(v != 0.0 for v in sc) and not self.differentiable:
+                raise MI355BackendError("cfm_recon: guidance (a non-zero scale) needs an engine built with differentiable=True")
+        if return_loss and mode != 2:
+            raise ValueError("return_loss is the low-resolution seed's loss (mode 2)")
+        hl = wl = 0
+        if y is not None:
+            want = (B, Cx) if mode == 2 else tuple(x.shape)
+            if y.dim() != 4 or tuple(y.shape[:len(want)]) != want:
+                raise ValueError(f"y must be {'[B, C, h, w]' if mode == 2 else 'of the shape of x'}, got {tuple(y.shape)}")
+            if mode == 2:
+                hl, wl = int(y.shape[2]), int(y.shape[3])
+        n_draws = n_steps + int(bool(final_paste))
+        if noise is not None and (rep != 2 or tuple(noise.shape[1:]) != tuple(x.shape) or noise.shape[0] < n_draws):
+            raise ValueError(f"noise is replace='fresh' only and must be [>= {n_draws}, *x.shape], got {tuple(noise.shape)}")
+        if rep == 2 and noise is None and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        lab, _ = self._labels(y_labels, B)
+        traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
+        loss = torch.empty(max(n_steps, 0), B, device=self.device, dtype=torch.float32) if return_loss else None
+        for i, (lo, hi, whole) in enumerate(_slices(B, self.max_batch())):
+            xs = x if whole else x[lo:hi]
+            tr = traj if whole else self._traj_u8(xs, len(ts), keep_traj, False)[0]
+            ls = loss if whole or loss is None else torch.empty(n_steps, hi - lo, device=self.device, dtype=torch.float32)
+            self._cfm_recon_call(xs, ts, y if whole or y is None else y[lo:hi].contiguous(), int(mode), sc, rep, bool(final_paste), float(pad_value),
+                                 noise if whole or noise is None else noise[:, lo:hi].contiguous(), (int(seed or 0) + i) % 2 ** 64,
+                                 _cut(lab, lo, hi), tr, u8 if whole else _cut(u8, lo, hi), ls, hl, wl)
+            if not whole:
+                if traj is not None:
+                    traj[:, lo:hi] = tr
+                if loss is not None:
+                    loss[:, lo:hi] = ls
+        return x, traj, u8, loss
+
+    def _cfm_recon_call(self, x, ts, y, mode, scales, rep, final_paste, pad_value, noise, seed, lab, traj, u8, loss, hl, wl):
+        """One mi355_cfm_recon_sample call (a batch within max_batch())."""
+        B, Cx = x.shape[:2]
+        arr = (C.c_float * len(ts))(*ts)
+        sarr = (C.c_float * max(1, len(ts) - 1))(*scales) if scales is not None else None
+        self._fwd_state = None
+        ws, wsb = self._workspace_sized("mi355_cfm_recon_workspace_bytes", B, hl, wl)
+        check(self.L.mi355_cfm_recon_sample(self.handle, self._chk(x, "x"), Cx, C.c_void_p(lab.data_ptr()) if lab is not None else None, arr, len(ts),
+                                            self._chk(y, "y") if y is not None else None, mode, pad_value, hl, wl, sarr, rep, int(final_paste),
+                                            self._chk(noise, "noise") if noise is not None else None, seed,
+                                            self._chk(traj, "traj") if traj is not None else None,
+                                            self._chk(u8, "u8", torch.uint8) if u8 is not None else None,
+                                            self._chk(loss, "loss") if loss is not None else None, B, ws, wsb, self._stream()),
+              "mi355_cfm_recon_sample")
+
     def sf2m_euler(self, score_engine: "UNetEngine", x: torch.Tensor, t_grid: Sequence[float], sigma: float, reverse: bool = False,
                    y: Optional[torch.Tensor] = None, dW: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                    outputs: Optional[Sequence[Tuple[int, float]]] = None):

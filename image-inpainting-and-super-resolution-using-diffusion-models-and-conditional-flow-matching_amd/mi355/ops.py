@@ -121,6 +121,23 @@ class Ops:
                                              _stream()))
         return g_eps, g_x
 
+    def lowres_seed(self, x, eps, y_low, c_recip, c_recipm1):
+        """-> (g_eps, g_x, loss): guidance_seed for the low-resolution consistency term, loss[n] = mean((D(x0) - y_low)^2) over sample n with
+        D the bilinear reduction to y_low's size (F.interpolate, align_corners=False) and x0 = clip(c_recip x - c_recipm1 eps, -1, 1).  The
+        state's height and width must be multiples of y_low's (mi355_lowres_seed)."""
+        _same(x, eps, "x", "eps")
+        if x.dim() != 4 or y_low.dim() != 4 or tuple(y_low.shape[:2]) != tuple(x.shape[:2]):
+            raise ValueError(f"x must be [B, C, H, W] and y_low [B, C, h, w] with the same B and C, got {tuple(x.shape)} and {tuple(y_low.shape)}")
+        B, Cc, H, W = x.shape
+        hl, wl = y_low.shape[2:]
+        g_eps, g_x = torch.empty_like(x), torch.empty_like(x)
+        resid = torch.empty_like(y_low)
+        loss = torch.empty(B, device=x.device, dtype=torch.float32)
+        check(_lib.lib().mi355_lowres_seed(_req(x, "x"), _req(eps, "eps"), _req(y_low, "y_low"), float(c_recip), float(c_recipm1), B, Cc, H, W, hl, wl,
+                                           _req(resid, "resid"), _req(g_eps, "g_eps"), _req(g_x, "g_x"), _req(loss, "loss"), _stream()),
+              "mi355_lowres_seed")
+        return g_eps, g_x, loss
+
     def guidance_update_(self, x, g_x, vjp, scale, apply):
         """update = -scale * (g_x + vjp); x += update when `apply` (the "before" rule).  -> update"""
         _same(x, g_x, "x", "g_x")

@@ -43,7 +43,8 @@ extern "C" {
                      * mantissa bits on every stored activation and weight; values beyond +-65504 overflow to inf as they do in the reference */
 
 /* ABI version = 100 * major + minor.  The minor number counts additive changes; 108: mi355_attn_block_fused (the fused AttentionBlock front half,
- * csrc/attn_fused.hip, as a test op that reports which kernel form it launched; a new symbol only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * csrc/attn_fused.hip, as a test op that reports which kernel form it launched; a new symbol only); later additions to 108: mi355_lowres_seed,
+ * mi355_cfm_recon_workspace_bytes and mi355_cfm_recon_sample (training-free in-painting / super-resolution of a flow; new symbols only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -380,6 +381,42 @@ int mi355_ddpm_cfg_sample(mi355_unet* net, float* x, int channels, const float* 
                           const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Training-free in-painting / super-resolution with an UNCONDITIONAL flow-matching net (no reference counterpart: the reference has the two
+ * methods for diffusion only, AD/image_diffusion/sampling.py:136-260).  t runs from 0 (noise) to 1 (data), the net's output is the velocity
+ * v(t, x), and the data estimate of a straight-path flow is x1_hat = x + (1 - t) v.  One Euler step per interval of t_span; step k, with
+ * t = t_span[k], dt = t_span[k+1] - t_span[k], omt = 1.0f - t (fp32):
+ *   1. replace != 0:  x <- where(y == pad_value, x, t * y + omt * z_k)   (mi355_replace_mask: the known pixels on the straight path)
+ *        replace 1 ("coupled"): z_k = the call's own initial state, kept in the workspace: the known pixels sit exactly on the path from this
+ *                               sample's noise to the measurement, which is what the net was trained on;
+ *        replace 2 ("fresh")  : z_k = z[k] (injected draws [n_t - 1, or n_t with final_paste][B, C, H, W]) or, z == NULL, the mi355_randn
+ *                               stream at (seed, k * n_al), n_al = the state's size rounded up to a multiple of 4 (mi355_ddpm_sample's numbering).
+ *   2. v = net(t, x)  (labels: NULL or device int32[B]).
+ *   3. scales_host != NULL and s = scales_host[k] != 0: the seed of the constraint at x1_hat (mi355_guidance_seed for modes 0 and 1,
+ *      mi355_lowres_seed for mode 2, both with c_recip = 1, c_recipm1 = -omt, so that pre = x + omt v, g_eps = omt g, g_x = g), the U-Net VJP
+ *      of g_eps, then ONE mi355_rk_stage launch over three derivative buffers:  x <- x + dt v - c g_x - c vjp,  c = dt * s rounded to fp32 on
+ *      the host (the stage kernel sums 0 + dt v, - c g_x, - c vjp in that order and adds the sum to x).
+ *      mode 0: Painting.loss (y [B, C, H, W], entries equal to pad_value masked); 1: HyperResolution.loss (y [B, C, H, W]);
+ *      2: mean((D(x1_hat) - y)^2) with y [B, C, h_low, w_low]; loss_out (mode 2 only; NULL or device [n_t - 1, B]) receives the step's
+ *      per-sample loss, NaN in the rows of steps that were not guided.
+ *   4. otherwise the same stage launch over v alone (bit-identical to mi355_cfm_rk_sample's Euler tableau).
+ * The stage launch writes traj[k + 1] (traj: NULL or [n_t, B, C, H, W], traj[0] = the input) and, on the last step, u8_out.  final_paste
+ * (replace != 0 only): the paste of step 1 once more after the last step, at t = t_span[n_t - 1] with draw index n_t - 1 (at t = 1: 1 * y + 0 * z);
+ * traj's last slot and u8_out are then rewritten from the pasted state.  Launches of a guided step: the forward, 1 seed launch (2, or 3 with
+ * loss_out, in mode 2), the backward pass, 1 stage launch (+ 1 paste); no copy.  After the call mi355_unet_get_stats reports the last step's count,
+ * with the backward pass counted as its adjoint ops (one per plan op that is not a GroupNorm statistics op, plus the unpack).
+ * workspace: mi355_cfm_recon_workspace_bytes(net, batch, h_low, w_low) = mi355_unet_workspace_bytes(net, batch) rounded up to 256, then, each
+ * rounded up to 256: the initial state, g_eps, g_x, vjp (one state each) and the low-res residual [B, C, h_low, w_low] (pass 0, 0 for modes 0, 1).
+ * Errors, all before any launch: in_channels != out_channels (amortized nets are not for this sampler), another channel count (-2); labels on a
+ * net without num_classes, a mode outside 0..2, replace outside 0..2 or with a mode other than 0, final_paste without replace, no y where one
+ * is needed, loss_out outside mode 2, n_t < 1, a misaligned workspace (MI355_ERR_ARG); a non-zero scale on a handle created without
+ * differentiable = 1, a low resolution that does not divide the image size (MI355_ERR_UNSUPPORTED); a short workspace (-2).  With
+ * scales_host == NULL (pure replacement) any handle and any precision is accepted.  sampler_graph, cond_drift and the Euler update inside the last
+ * conv take no part. */
+int64_t mi355_cfm_recon_workspace_bytes(const mi355_unet* net, int batch, int h_low, int w_low);
+int mi355_cfm_recon_sample(mi355_unet* net, float* x, int channels, const int32_t* labels, const float* t_span_host, int n_t, const float* y, int mode,
+                           float pad_value, int h_low, int w_low, const float* scales_host, int replace, int final_paste, const float* z, uint64_t seed,
+                           float* traj, uint8_t* u8_out, float* loss_out, int batch, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- single ops (used by the Python mirror for arbitrary eps_model callables, and by the tests) --- */
 
 /* timestep_embedding (AD/image_diffusion/nn.py:97-115): t[B] -> out[B, dim] */
@@ -426,6 +463,17 @@ int mi355_replace_mask(float* x, const float* cond, const float* z, float pad_va
 int mi355_guidance_seed(const float* x, const float* eps, const float* cond, float c_recip, float c_recipm1, int mode, float pad_value,
                         int64_t elems_per_sample, float* g_eps, float* g_x, int64_t n, void* stream);
 int mi355_guidance_update(float* x, const float* g_x, const float* vjp, float scale, int apply, float* update, int64_t n, void* stream);
+
+/* Seed of the low-resolution consistency term, the guidance seed with a real down-sampling operator:
+ *   pre = c_recip x - c_recipm1 eps;  x0 = clip(pre, -1, 1);  resid = D(x0) - y_low;  loss[n] = mean of resid^2 over sample n's C h_low w_low entries;
+ *   g = (2 / (C h_low w_low)) D^T resid, zero where pre is outside [-1, 1] or NaN;  g_eps = -c_recipm1 g;  g_x = c_recip g.
+ * D = F.interpolate(size = (h_low, w_low), mode = "bilinear", align_corners = False) with mi355_resize_bilinear's taps, weights and operation
+ * order, x0 formed at the four taps (no full-size x0 is written).  h % h_low == 0 and w % w_low == 0 (factor 1 included), anything else
+ * returns MI355_ERR_UNSUPPORTED before a launch: for an integer factor the adjoint is a gather (source pixel (Y, X) receives from low-res pixel
+ * (Y / sy, X / sx) alone), written with plain stores; loss is summed in a fixed order.  The results are bit-identical from run to run.
+ * x, eps, g_eps, g_x: [B, C, h, w]; y_low, resid (scratch, holds the residual afterwards): [B, C, h_low, w_low]; loss: [B] or NULL. */
+int mi355_lowres_seed(const float* x, const float* eps, const float* y_low, float c_recip, float c_recipm1, int batch, int channels, int h, int w,
+                      int h_low, int w_low, float* resid, float* g_eps, float* g_x, float* loss, void* stream);
 
 /* clip(x, lo, hi) in place, NaN-propagating like torch.clip (sampling.py:13-14) */
 int mi355_clip(float* x, float lo, float hi, int64_t n, void* stream);
