@@ -207,6 +207,30 @@ int gn_silu_bwd_launch(const GnBwdDesc& d, hipStream_t stream);
 enum { GATHER_SAME = 0, GATHER_POOL = 1, GATHER_UP = 2, GATHER_STUFF = 3 };
 int grad_gather_launch(int dtype, void* dst, const void* src, int N, int Hd, int Wd, int Cd, int Hs, int Ws, int src_cstride, int src_coff,
                        int mode, int accumulate, float scale, hipStream_t s);
+// The data gradient through one conv of the forward plan (input channels cat(src0, src1) -> Cout, ks, mode UNIT / STRIDE2 / UP2): G is the
+// gradient of the conv's output, NHWC [N][Hg][Wg][Cg] (Cg = Cout padded to whole chunks), wT the image conv_pack_weights_dgrad made for
+// cin_pad = align_up(C0 + C1, 32) output channels.  One bias-free NHWC unit-mode conv of G with wT into du (stride 2: of G zero-stuffed into zbuf
+// at the input resolution Hs x Ws; nearest x2: at Hg x Wg = 2 Hs x 2 Ws, its 2x2 block sums are the gradient), then
+//   scatter = 1: g0 [N][Hs][Ws][C0] (+)= channels 0 .. C0 of the result, g1 [N][Hs][Ws][C1] (+)= channels C0 .. C0 + C1 (acc0 / acc1: add to
+//                what is there; g1 null: one source)
+//   scatter = 0: the result stays in scratch for the caller's GroupNorm adjoint (nearest x2: block sums into tmp): ConvDgradOut::dU, rows of
+//                dU_stride = cin_pad channels at Hs x Ws, channels >= the forward conv's input channels zero
+struct ConvDgradDesc {
+  int dtype;
+  const void* G = nullptr; int Cg = 0, Hg = 0, Wg = 0;
+  const void* wT = nullptr; int cin_pad = 0, ks = 3, mode = CONV_UNIT;
+  int N = 0, Hs = 0, Ws = 0;
+  void* du = nullptr; void* tmp = nullptr; void* zbuf = nullptr;   // scratch: [N][max(Hs Ws, Hg Wg)][cin_pad], [N][Hs][Ws][cin_pad] (UP2 without scatter), [N][Hs][Ws][Cg] (STRIDE2)
+  int scatter = 0;
+  void* g0 = nullptr; void* g1 = nullptr; int C0 = 0, C1 = 0, acc0 = 0, acc1 = 0;
+  const mi355_debug_config* knobs = nullptr; uint32_t* err = nullptr;   // as ConvDesc's
+};
+struct ConvDgradOut {
+  ConvRoute route;              // what the conv launch was
+  const void* dU = nullptr; int dU_stride = 0;
+};
+int conv_dgrad_launch(const ConvDgradDesc& d, hipStream_t stream, ConvDgradOut* out);
+int conv_dgrad_route(const ConvDgradDesc& d, ConvRoute* r);   // the route that launch takes: pure host code, the pointers are not read
 struct AttnBwdDesc {
   int dtype;
   const void* qkv = nullptr; const void* a = nullptr; const void* da = nullptr; void* dqkv = nullptr;

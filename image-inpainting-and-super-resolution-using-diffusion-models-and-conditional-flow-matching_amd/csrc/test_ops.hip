@@ -1,5 +1,5 @@
 // Single-op test harness of libmi355_sampler.so (see include/mi355_sampler.h): the kernels the network launches, one op per call, NCHW fp32 at
-// the boundary (mi355_conv2d / mi355_conv2d_ex, the attention ops, the GroupNorm test ops, mi355_affine_pool, mi355_grad_gather).
+// the boundary (mi355_conv2d / mi355_conv2d_ex, the attention ops, the GroupNorm test ops, mi355_affine_pool, mi355_grad_gather, mi355_conv2d_vjp).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -557,6 +557,76 @@ int mi355_grad_gather(const float* src, float* dst, int batch, int cd, int hd, i
   if ((rc = grad_gather_launch(dtype, pd, ps, batch, hd, wd, cd, hs, ws, src_channels, src_coff, mode, accumulate, scale, s))) return rc;
   if ((rc = unpack_nchw_launch(dtype, pd, batch, hd * wd, cd, dst, s))) return rc;
   MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// ---- the conv data gradient (later addition to ABI 108): conv_pack_weights_dgrad + conv_dgrad_launch, the sequence unet_backward runs per conv ----
+int mi355_conv2d_vjp(const float* w_host, const float* grad_out, float* g0, float* g1, float* du_raw, int acc0, int acc1, int batch, int cout,
+                     int cin, int c0, int c1, int h, int w, int ksize, int mode, int g_channels, int dtype, const mi355_debug_config* debug,
+                     int32_t route[4], void* workspace, int64_t workspace_bytes, void* stream) {
+  if (route) route[0] = route[1] = route[2] = route[3] = -1;
+  MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_BF16, -1, "conv2d_vjp: dtype must be MI355_F32 or MI355_BF16 (the backward pass has no other form)");
+  const bool dry = workspace == nullptr && workspace_bytes == 0 && route != nullptr;   // route query: host code only
+  MI355_REQUIRE(dry || (w_host && grad_out && workspace), -1, "conv2d_vjp: null argument");
+  MI355_REQUIRE(batch > 0 && cout > 0 && cin > 0 && c0 > 0 && c1 >= 0 && h > 0 && w > 0, -1, "conv2d_vjp: bad sizes");
+  MI355_REQUIRE(ksize == 1 || ksize == 3, -1, "conv2d_vjp: kernel size must be 1 or 3");
+  MI355_REQUIRE(mode == CONV_UNIT || ((mode == CONV_STRIDE2 || mode == CONV_UP2) && ksize == 3), -1, "conv2d_vjp: mode 0 (unit), or with a 3x3 kernel 1 (stride 2) / 2 (nearest x2)");
+  const bool raw = du_raw != nullptr;
+  MI355_REQUIRE((dry || raw) ? (!g0 && !g1 && !acc0 && !acc1) : (g0 && (g1 != nullptr) == (c1 > 0)), -1, "conv2d_vjp: either du_raw alone, or g0 (and g1 with c1 > 0)");
+  const int CH = dtype == 0 ? 16 : 32, V = dtype == 0 ? 4 : 8;
+  const size_t esz = dtype == 0 ? 4 : 2;
+  MI355_REQUIRE(c0 + c1 >= cin, -2, "conv2d_vjp: c0 + c1 must cover the conv's input channels");
+  MI355_REQUIRE(c0 % V == 0 && c1 % V == 0, -2, "conv2d_vjp: c0 and c1 must be whole 16-byte channel fragments");
+  MI355_REQUIRE(g_channels == (cout + CH - 1) / CH * CH, -2, "conv2d_vjp: g_channels must be cout padded to whole 64-byte chunks");
+  const int cin_pad = (c0 + c1 + 31) / 32 * 32;   // the plan builder's PlanOp::cin_pad
+  const int Ho = mode == CONV_STRIDE2 ? (h - 1) / 2 + 1 : (mode == CONV_UP2 ? 2 * h : h);
+  const int Wo = mode == CONV_STRIDE2 ? (w - 1) / 2 + 1 : (mode == CONV_UP2 ? 2 * w : w);
+  const int Hd = mode == CONV_UP2 ? Ho : h, Wd = mode == CONV_UP2 ? Wo : w;   // the data-gradient conv's own resolution
+  ConvDgradDesc d; d.dtype = dtype; d.Cg = g_channels; d.Hg = Ho; d.Wg = Wo; d.cin_pad = cin_pad; d.ks = ksize; d.mode = mode;
+  d.N = batch; d.Hs = h; d.Ws = w; d.knobs = debug;
+  if (dry) {
+    ConvRoute r;
+    if (int rc = conv_dgrad_route(d, &r)) return rc;
+    route[0] = r.kernel; route[1] = r.form; route[2] = r.geom.BM; route[3] = r.geom.BN;
+    return 0;
+  }
+  hipStream_t s = S(stream);
+  const size_t wbytes = conv_packed_weight_bytes_dgrad(dtype, cout, cin, ksize, cin_pad);
+  char* p = reinterpret_cast<char*>(workspace);
+  void* gp = p; p += al256((size_t)batch * Ho * Wo * g_channels * esz);
+  void* zbuf = p; if (mode == CONV_STRIDE2) p += al256((size_t)batch * h * w * g_channels * esz);
+  void* du = p; p += al256((size_t)batch * Hd * Wd * cin_pad * esz);
+  void* tmp = p; if (mode == CONV_UP2 && raw) p += al256((size_t)batch * h * w * cin_pad * esz);
+  void* q0 = p; if (!raw) p += al256((size_t)batch * h * w * c0 * esz);
+  void* q1 = p; if (!raw && c1) p += al256((size_t)batch * h * w * c1 * esz);
+  void* wdev = p; p += al256(wbytes);
+  uint32_t* errw = reinterpret_cast<uint32_t*>(p); p += 256;
+  MI355_REQUIRE(p <= reinterpret_cast<char*>(workspace) + workspace_bytes, -2, "conv2d_vjp: workspace too small");
+  int rc;
+  MI355_CHECK_HIP(hipMemsetAsync(errw, 0, 256, s));
+  // the cotangent as the walker holds it: NHWC, channels cout .. g_channels zero (pack_nhwc's padding, as for the network's own cotangent)
+  if ((rc = pack_nhwc_launch(dtype, grad_out, cout, nullptr, 0, batch, Ho * Wo, g_channels, gp, s))) return rc;
+  // a gradient the scatter adds to is the caller's, packed; anything else stays as the caller filled the workspace
+  if (acc0 && (rc = pack_nhwc_launch(dtype, g0, c0, nullptr, 0, batch, h * w, c0, q0, s))) return rc;
+  if (acc1 && c1 && (rc = pack_nhwc_launch(dtype, g1, c1, nullptr, 0, batch, h * w, c1, q1, s))) return rc;
+  std::vector<char> packed(wbytes);
+  conv_pack_weights_dgrad(dtype, w_host, cout, cin, ksize, cin_pad, packed.data());
+  MI355_CHECK_HIP(hipMemcpyAsync(wdev, packed.data(), wbytes, hipMemcpyHostToDevice, s));
+  d.G = gp; d.wT = wdev; d.du = du; d.tmp = tmp; d.zbuf = zbuf; d.scatter = !raw; d.err = errw;
+  if (!raw) { d.g0 = q0; d.C0 = c0; d.acc0 = acc0; if (c1) { d.g1 = q1; d.C1 = c1; d.acc1 = acc1; } }
+  ConvDgradOut o;
+  if ((rc = conv_dgrad_launch(d, s, &o))) return rc;
+  if (route) { route[0] = o.route.kernel; route[1] = o.route.form; route[2] = o.route.geom.BM; route[3] = o.route.geom.BN; }
+  if (raw) {
+    if ((rc = unpack_nchw_launch(dtype, o.dU, batch, h * w, o.dU_stride, du_raw, s))) return rc;
+  } else {
+    if ((rc = unpack_nchw_launch(dtype, q0, batch, h * w, c0, g0, s))) return rc;
+    if (c1 && (rc = unpack_nchw_launch(dtype, q1, batch, h * w, c1, g1, s))) return rc;
+  }
+  MI355_CHECK_HIP(hipStreamSynchronize(s));   // `packed` is a temporary host buffer
+  uint32_t ev = 0;
+  MI355_CHECK_HIP(hipMemcpy(&ev, errw, 4, hipMemcpyDeviceToHost));
+  if (ev) { mi355_set_error("conv2d_vjp: the persistent kernel gave up a bounded counter wait (hand-over stalled): the output is invalid"); return MI355_ERR_TIMEOUT; }
   return 0;
 }
 

@@ -15,6 +15,48 @@
 // of the same layout and are written by their first contributor, added to by the others.
 #include "unet_engine.h"
 
+// The conv branch's data gradient (ops.h ConvDgradDesc): the walker below and the test op mi355_conv2d_vjp run this one sequence.
+namespace {
+// the bias-free NHWC unit-mode conv of the (zero-stuffed) output gradient with the transposed filter
+ConvDesc dgrad_conv(const ConvDgradDesc& d) {
+  ConvDesc c; c.dtype = d.dtype; c.N = d.N; c.ks = d.ks; c.mode = CONV_UNIT; c.knobs = d.knobs; c.err = d.err;
+  c.w = d.wT; c.Cout = d.cin_pad; c.out = d.du; c.out_mode = OUT_NHWC; c.C0 = d.Cg;
+  if (d.mode == CONV_STRIDE2) { c.src0 = d.zbuf; c.Hs = d.Hs; c.Ws = d.Ws; }   // at the input resolution
+  else { c.src0 = d.G; c.Hs = d.Hg; c.Ws = d.Wg; }
+  return c;
+}
+}  // namespace
+
+int conv_dgrad_route(const ConvDgradDesc& d, ConvRoute* r) { return conv_route(dgrad_conv(d), r); }
+
+int conv_dgrad_launch(const ConvDgradDesc& d, hipStream_t stream, ConvDgradOut* out) {
+  MI355_REQUIRE(out && d.G && d.wT && d.du, -1, "conv dgrad: null argument");
+  MI355_REQUIRE(d.mode == CONV_UNIT || d.mode == CONV_STRIDE2 || d.mode == CONV_UP2, -4, "conv dgrad: the forward conv's mode must be unit, stride 2 or nearest x2");
+  MI355_REQUIRE(d.mode != CONV_STRIDE2 || d.zbuf, -1, "conv dgrad: a stride-2 conv needs the zero-stuffing scratch");
+  MI355_REQUIRE(d.scatter ? d.g0 != nullptr : (d.mode != CONV_UP2 || d.tmp), -1, "conv dgrad: no destination");
+  int rc;
+  // stride 2: zero insertion back to the input resolution, then a stride-1 conv with the flipped taps
+  if (d.mode == CONV_STRIDE2 && (rc = grad_gather_launch(d.dtype, d.zbuf, d.G, d.N, d.Hs, d.Ws, d.Cg, d.Hg, d.Wg, d.Cg, 0, GATHER_STUFF, 0, 1.0f, stream))) return rc;
+  const ConvDesc c = dgrad_conv(d);
+  const int Hd = c.Hs, Wd = c.Ws;   // resolution of the data-gradient conv's output
+  if ((rc = conv_route(c, &out->route))) return rc;
+  if ((rc = conv_launch(c, out->route, stream))) return rc;
+  // nearest-x2 input (Upsample / ResBlock(up)): the conv saw up2(u), so du(u) = 2x2 block sums of the conv's data gradient
+  const bool up = d.mode == CONV_UP2;
+  out->dU = d.du; out->dU_stride = d.cin_pad;
+  if (!d.scatter) {
+    if (up) {
+      if ((rc = grad_gather_launch(d.dtype, d.tmp, d.du, d.N, d.Hs, d.Ws, d.cin_pad, Hd, Wd, d.cin_pad, 0, GATHER_POOL, 0, 1.0f, stream))) return rc;
+      out->dU = d.tmp;
+    }
+    return 0;
+  }
+  const int mode = up ? GATHER_POOL : GATHER_SAME;
+  if ((rc = grad_gather_launch(d.dtype, d.g0, d.du, d.N, d.Hs, d.Ws, d.C0, Hd, Wd, d.cin_pad, 0, mode, d.acc0, 1.0f, stream))) return rc;
+  if (d.g1 && (rc = grad_gather_launch(d.dtype, d.g1, d.du, d.N, d.Hs, d.Ws, d.C1, Hd, Wd, d.cin_pad, d.C0, mode, d.acc1, 1.0f, stream))) return rc;
+  return 0;
+}
+
 int unet_backward(const mi355_unet* net, const float* grad_out, float* grad_x, int Cx, int B, void* workspace, int64_t workspace_bytes,
                   hipStream_t stream) {
   MI355_REQUIRE(net && grad_out && grad_x && workspace, -1, "unet_vjp: null argument");
@@ -58,38 +100,27 @@ int unet_backward(const mi355_unet* net, const float* grad_out, float* grad_x, i
         else rc = accumulate(op.res, G, Hg, Wg, Cg, 0, GATHER_POOL, 1.0f);   // forward added nearest-x2(res): sum the 2x2 blocks
         if (rc) return rc;
       }
-      // ---- data gradient through the conv ----
-      ConvDesc c; c.dtype = dtype; c.N = B; c.ks = op.ks; c.mode = CONV_UNIT;
-      c.w = W + op.wT_off; c.Cout = op.cin_pad; c.out = du; c.out_mode = OUT_NHWC;
-      int Hd, Wd;   // resolution of the data-gradient conv's output
-      if (op.mode == CONV_STRIDE2) {   // zero insertion back to the input resolution, then a stride-1 conv with the flipped taps
-        if ((rc = grad_gather_launch(dtype, zbuf, G, B, s0.H, s0.W, Cg, Hg, Wg, Cg, 0, GATHER_STUFF, 0, 1.0f, stream))) return rc;
-        c.src0 = zbuf; c.C0 = Cg; c.Hs = s0.H; c.Ws = s0.W; Hd = s0.H; Wd = s0.W;
-      } else {
-        c.src0 = G; c.C0 = Cg; c.Hs = Hg; c.Ws = Wg; Hd = Hg; Wd = Wg;
+      // ---- data gradient through the conv (conv_dgrad_launch below): scattered to the sources, or left for the GroupNorm adjoint ----
+      ConvDgradDesc c; c.dtype = dtype; c.G = G; c.Cg = Cg; c.Hg = Hg; c.Wg = Wg;
+      c.wT = W + op.wT_off; c.cin_pad = op.cin_pad; c.ks = op.ks; c.mode = op.mode;
+      c.N = B; c.Hs = s0.H; c.Ws = s0.W; c.du = du; c.tmp = tmp; c.zbuf = zbuf;
+      c.scatter = !op.use_pro;
+      if (c.scatter) {
+        c.g0 = v.grad(op.src0); c.C0 = s0.C; c.acc0 = written[op.src0];
+        if (op.src1 >= 0) { c.g1 = v.grad(op.src1); c.C1 = C1; c.acc1 = written[op.src1]; }
       }
-      if ((rc = conv_launch(c, stream))) return rc;
-      // nearest-x2 input (Upsample / ResBlock(up)): the conv saw up2(u), so du(u) = 2x2 block sums of the conv's data gradient
-      const void* dU = du; int cs = op.cin_pad;
-      const bool up = op.mode == CONV_UP2;
+      ConvDgradOut o;
+      if ((rc = conv_dgrad_launch(c, stream, &o))) return rc;
       if (op.use_pro) {
-        if (up) {
-          if ((rc = grad_gather_launch(dtype, tmp, du, B, s0.H, s0.W, op.cin_pad, Hd, Wd, op.cin_pad, 0, GATHER_POOL, 0, 1.0f, stream))) return rc;
-          dU = tmp;
-        }
         GnBwdDesc g; g.dtype = dtype; g.x0 = v.tensor(op.src0); g.C0 = s0.C; g.x1 = op.src1 >= 0 ? v.tensor(op.src1) : nullptr; g.C1 = C1;
-        g.du = dU; g.du_stride = cs; g.N = B; g.HW = s0.H * s0.W; g.silu = op.pro_silu;
+        g.du = o.dU; g.du_stride = o.dU_stride; g.N = B; g.HW = s0.H * s0.W; g.silu = op.pro_silu;
         site(op.gn_site, g);
         g.g0 = v.grad(op.src0); g.acc0 = written[op.src0];
         if (op.src1 >= 0) { g.g1 = v.grad(op.src1); g.acc1 = written[op.src1]; }
         if ((rc = gn_silu_bwd_launch(g, stream))) return rc;
-        written[op.src0] = 1;
-        if (op.src1 >= 0) written[op.src1] = 1;
-      } else {
-        const int mode = up ? GATHER_POOL : GATHER_SAME;
-        if ((rc = accumulate(op.src0, dU, Hd, Wd, cs, 0, mode, 1.0f))) return rc;
-        if (op.src1 >= 0 && (rc = accumulate(op.src1, dU, Hd, Wd, cs, s0.C, mode, 1.0f))) return rc;
       }
+      written[op.src0] = 1;
+      if (op.src1 >= 0) written[op.src1] = 1;
     } else if (op.kind == OP_ATTN) {
       MI355_REQUIRE(written[op.dst], -4, "unet_vjp: an attention output has no gradient (plan order)");
       AttnBwdDesc a; a.dtype = dtype; a.qkv = v.tensor(op.src0); a.a = v.tensor(op.dst); a.da = v.grad(op.dst); a.dqkv = v.grad(op.src0);

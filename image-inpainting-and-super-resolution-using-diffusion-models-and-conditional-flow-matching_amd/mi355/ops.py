@@ -576,5 +576,56 @@ class Ops:
                                            float(scale), dtype, _stream()), "mi355_grad_gather")
         return out
 
+    def conv2d_vjp(self, weight, grad_out, c0, c1=0, hw=None, mode=0, g_channels=None, g0=None, g1=None, raw=False, dtype=_lib.MI355_F32,
+                   debug=None, ws_fill=None, info=None):
+        """The data gradient through one conv as the U-Net backward computes it (mi355_conv2d_vjp: conv_pack_weights_dgrad, then the walker's
+        own helper).  weight: CPU tensor [Co, Ci, k, k] of the forward conv cat(x0 [B, c0, h, w], x1 [B, c1, h, w]) -> [B, Co, Ho, Wo], Ci <= c0 + c1;
+        grad_out [B, Co, Ho, Wo]; hw = (h, w) of the forward input (None: grad_out's size, mode 0); mode 0 plain, 1 stride 2, 2 nearest x2;
+        g_channels: packed channels of grad_out (None: Co rounded up to a chunk).  g0 / g1: gradients to accumulate into (in place), or None:
+        overwritten.  raw: return the helper's [B, cin_pad, h, w] buffer (the GroupNorm adjoint's input) instead.  ws_fill: a byte value the
+        workspace is filled with first (0xFF: whatever no kernel writes comes back NaN).  info: a dict that receives the conv launch (kernel, form,
+        tile_m, tile_n).  -> (grad of x0, grad of x1 or None), or the raw buffer."""
+        Co, Ci, k, _ = weight.shape
+        B = grad_out.shape[0]
+        h, w = hw if hw is not None else tuple(grad_out.shape[2:])
+        Ho, Wo = ((h - 1) // 2 + 1, (w - 1) // 2 + 1) if mode == 1 else ((2 * h, 2 * w) if mode == 2 else (h, w))
+        if tuple(grad_out.shape) != (B, Co, Ho, Wo):
+            raise ValueError(f"grad_out must be {(B, Co, Ho, Wo)}, got {tuple(grad_out.shape)}")
+        ch = 16 if dtype == _lib.MI355_F32 else 32
+        gch = int(g_channels) if g_channels is not None else (Co + ch - 1) // ch * ch
+        cin_pad = (c0 + c1 + 31) // 32 * 32
+        dev = grad_out.device
+        acc0, acc1 = g0 is not None, g1 is not None
+        if raw:
+            if acc0 or acc1:
+                raise ValueError("raw returns the helper's buffer: there is nothing to accumulate into")
+            out = torch.full((B, cin_pad, h, w), float("nan"), device=dev)
+        else:
+            if (acc0 and tuple(g0.shape) != (B, c0, h, w)) or (acc1 and tuple(g1.shape) != (B, c1, h, w)):
+                raise ValueError("g0 / g1 must be [B, c0, h, w] / [B, c1, h, w]")
+            g0 = g0 if acc0 else torch.full((B, c0, h, w), float("nan"), device=dev)
+            g1 = None if not c1 else (g1 if acc1 else torch.full((B, c1, h, w), float("nan"), device=dev))
+        L = _lib.lib()
+        wsb = L.mi355_op_workspace_bytes(B, max(cin_pad, gch), max(h * w, Ho * Wo))
+        ws = torch.empty(wsb, device=dev, dtype=torch.uint8) if ws_fill is None else torch.full((wsb,), int(ws_fill), device=dev, dtype=torch.uint8)
+        wh = weight.detach().to("cpu", torch.float32).contiguous()
+        route = (C.c_int32 * 4)(-1, -1, -1, -1)
+        check(L.mi355_conv2d_vjp(C.cast(wh.data_ptr(), C.POINTER(C.c_float)), _req(grad_out, "grad_out"), None if raw else _req(g0, "g0"),
+                                 _req(g1, "g1") if g1 is not None else None, _req(out, "du_raw") if raw else None, int(acc0), int(acc1), B, Co, Ci,
+                                 int(c0), int(c1), h, w, k, int(mode), gch, dtype, C.byref(debug) if debug is not None else None, route,
+                                 C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_conv2d_vjp")
+        if info is not None:
+            info.update(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3])
+        return out if raw else (g0, g1)
+
+    def conv2d_vjp_route(self, B, Co, Ci, c0, c1, h, w, k, mode=0, dtype=_lib.MI355_F32, debug=None):
+        """What conv_route decides for the data-gradient conv of these sizes: host code, nothing is launched (no GPU needed).
+        -> dict(kernel, form, tile_m, tile_n)"""
+        ch = 16 if dtype == _lib.MI355_F32 else 32
+        route = (C.c_int32 * 4)(-1, -1, -1, -1)
+        check(_lib.lib().mi355_conv2d_vjp(None, None, None, None, None, 0, 0, B, Co, Ci, int(c0), int(c1), h, w, k, int(mode), (Co + ch - 1) // ch * ch,
+                                          dtype, C.byref(debug) if debug is not None else None, route, None, 0, None), "mi355_conv2d_vjp")
+        return dict(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3])
+
 
 default_ops = Ops()

@@ -44,7 +44,8 @@ extern "C" {
 
 /* ABI version = 100 * major + minor.  The minor number counts additive changes; 108: mi355_attn_block_fused (the fused AttentionBlock front half,
  * csrc/attn_fused.hip, as a test op that reports which kernel form it launched; a new symbol only); later additions to 108: mi355_lowres_seed,
- * mi355_cfm_recon_workspace_bytes and mi355_cfm_recon_sample (training-free in-painting / super-resolution of a flow; new symbols only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * mi355_cfm_recon_workspace_bytes and mi355_cfm_recon_sample (training-free in-painting / super-resolution of a flow; new symbols only); then
+ * mi355_conv2d_vjp (the conv data gradient of the U-Net backward as a test op; a new symbol only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -654,6 +655,23 @@ int mi355_gn_silu_vjp(const float* x0, const float* x1, const float* gamma, cons
  * insertion (backward of a stride-2 conv).  dtype MI355_F32 or MI355_BF16 only. */
 int mi355_grad_gather(const float* src, float* dst, int batch, int cd, int hd, int wd, int hs, int ws, int src_channels, int src_coff, int mode,
                       int accumulate, float scale, int dtype, void* stream);
+/* The data gradient through one conv of the network, as mi355_unet_vjp computes it (later addition to ABI 108; csrc/unet_backward.hip
+ * conv_dgrad_launch: the helper the backward walker itself calls).  The forward conv: cat(x0 [B, c0, h, w], x1 [B, c1, h, w]) -> [B, cout, Ho, Wo]
+ * with the filter w_host [cout, cin, ksize, ksize] (HOST pointer; cin <= c0 + c1: the channels cin .. c0 + c1 are the channel padding of the network's
+ * first conv and see zero weights), padding ksize / 2 and mode 0 (plain), 1 (stride 2: Ho = (h - 1) / 2 + 1) or 2 (nearest x2 first: Ho = 2 h); modes
+ * 1 and 2 need ksize 3.  grad_out [B, cout, Ho, Wo] is packed to NHWC rows of g_channels = cout rounded up to a 64-byte chunk (16 fp32 / 32 bf16
+ * channels; the padding is zero, as the network's own cotangent is packed), the filter by conv_pack_weights_dgrad for cin_pad = c0 + c1 rounded up to
+ * 32 output channels; then the helper: zero stuffing (mode 1), one bias-free NHWC conv, 2x2 block sums (mode 2) and either
+ *  - the scatter into g0 [B, c0, h, w] and g1 [B, c1, h, w] (g1 NULL iff c1 = 0): overwritten, or added to when acc0 / acc1; du_raw NULL; or
+ *  - du_raw [B, cin_pad, h, w] (g0, g1 NULL): the buffer the GroupNorm adjoint of a conv with a prologue reads, padding channels included.
+ * c0 and c1 are multiples of 4 (fp32) / 8 (bf16).  dtype MI355_F32 or MI355_BF16 only.  route (host, 4 words, may be NULL) = the conv launch as
+ * mi355_conv_extras::route reports it; -1 if the call failed before the launch.  Every intermediate lives in `workspace`
+ * (mi355_op_workspace_bytes(batch, max(cin_pad, g_channels), max(h w, Ho Wo)) suffices) and only what a kernel writes is initialised: a caller that
+ * fills the workspace with 0xFF bytes gets NaN for any element no kernel wrote.  workspace NULL with workspace_bytes 0 and route given: nothing is
+ * launched or read, route receives what conv_route decides for these sizes (host code; no GPU needed).  Synchronises `stream`. */
+int mi355_conv2d_vjp(const float* w_host, const float* grad_out, float* g0, float* g1, float* du_raw, int acc0, int acc1, int batch, int cout,
+                     int cin, int c0, int c1, int h, int w, int ksize, int mode, int g_channels, int dtype, const mi355_debug_config* debug,
+                     int32_t route[4], void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -346,6 +346,9 @@ def test_backward_ops_reject_other_dtypes():
         assert rc < 0 and b"gn_silu_vjp" in L.mi355_last_error()
         rc = L.mi355_grad_gather(p, p, 1, 32, 4, 4, 4, 4, 32, 0, 0, 0, 1.0, bad, None)
         assert rc < 0 and b"grad_gather" in L.mi355_last_error()
+        route = (C.c_int32 * 4)(7, 7, 7, 7)
+        rc = L.mi355_conv2d_vjp(C.cast(p, C.POINTER(C.c_float)), p, p, None, None, 0, 0, 1, 32, 32, 32, 0, 4, 4, 3, 0, 32, bad, None, route, p, 1 << 20, None)
+        assert rc < 0 and b"conv2d_vjp" in L.mi355_last_error() and list(route) == [-1, -1, -1, -1]
 
 
 @pytest.mark.gpu
