@@ -831,7 +831,7 @@ int conv_route(const ConvDesc& d, ConvRoute* r) {
   *r = ConvRoute{};
   Geo g; compute_geo(d, g);
   r->geom = ConvGeom{g.Ho, g.Wo, g.BM, g.BN, g.lds, g.groups * g.tiles_x * g.tiles_y, (d.Cout + g.BN - 1) / g.BN};
-  const bool fskip = d.skip_src0 != nullptr;   // only the small-level kernel carries a fused skip conv
+  const bool fskip = d.skip_src0 != nullptr;   // the small-level kernel and the warp-specialised kernel's prologue forms carry a fused skip conv
   if (!fskip && !d.wsplit) {   // (hi / lo split weights: the implicit-GEMM kernels)
     int rc = pp1_route(d, r);
     if (rc == 1) rc = conv1x1_route(d, r);
@@ -857,7 +857,9 @@ int conv_route(const ConvDesc& d, ConvRoute* r) {
   // ping-pong kernel (conv_pp.inc.h): 256- or 128-channel output tiles, input as it is or through the in-LDS GroupNorm + SiLU prologue
   // (phase form of an up-sampling conv: needs the collapsed weight image, carries no residual / split weights / fused output norm)
   const bool up_ok = d.mode == CONV_UP2 && d.w_up2 && !d.wsplit && a.res_mode == RES_NONE;
-  const int pc = fskip ? -1 : pp_config(K.conv_pp, d.ks, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, has_pro, d.pro_silu != 0, d.N, g.Ho, g.Wo, d.Cout, up_ok);
+  // (a description with a fused skip conv never runs on the ping-pong kernel; where that kernel would take the conv alone, the two-launch form stays)
+  const int pc_alone = pp_config(K.conv_pp, d.ks, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, has_pro, d.pro_silu != 0, d.N, g.Ho, g.Wo, d.Cout, up_ok);
+  const int pc = fskip ? -1 : pc_alone;
   if (pc == 2) {
     r->kernel = CONV_K_PP; r->form = 2; r->w_up2 = 1;
     r->geom.BM = 256; r->geom.BN = 256; r->geom.lds_bytes = pp::D<0>::lds_bytes(false);
@@ -877,8 +879,9 @@ int conv_route(const ConvDesc& d, ConvRoute* r) {
     return 0;
   }
   // dominant shapes: warp-specialised persistent kernel (conv_ws.inc.h)
-  if (!fskip && ws_eligible(K.conv_ws, d.ks, g.BM, g.BN, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, d.N, g.Ho, g.Wo, d.Cout)) {
-    r->kernel = CONV_K_WS;
+  if (ws_eligible(K.conv_ws, d.ks, g.BM, g.BN, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, d.N, g.Ho, g.Wo, d.Cout) &&
+      (!fskip || (pc_alone < 0 && ws_skip_eligible(K.conv_ws, a, d.mode, d.act_out != nullptr, d.wsplit != 0, CH)))) {
+    r->kernel = CONV_K_WS; r->skip = fskip ? 1 : 0;
     r->geom.BM = 256; r->geom.lds_bytes = ws::LDS_BYTES;   // 16 x 16 pixel tiles
     const int slots = 2 * ((g.Wo + ws::VW - 1) / ws::VW) * ((g.Ho + ws::TH - 1) / ws::TH);   // (16x16 pixel tile, 8-row half) per image
     if (gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
@@ -930,7 +933,7 @@ int conv_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream) {
   }
   int rc;
   if (r.kernel == CONV_K_PP) rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_pp<decltype(t)>(a, r.form, stream); });
-  else if (r.kernel == CONV_K_WS) rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_ws<decltype(t)>(a, stream); });
+  else if (r.kernel == CONV_K_WS) rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_ws<decltype(t)>(a, (d.knobs ? d.knobs : &mi355_default_debug())->conv_ws >> 8, stream); });
   else if (r.kernel == CONV_K_SMALL) {
     if (r.act_done & 1) {
       a.act_stride = d.act_stride ? d.act_stride : d.Cout; a.act_coff = d.act_coff; a.act_cpg = d.act_cpg ? d.act_cpg : d.Cout / 32;

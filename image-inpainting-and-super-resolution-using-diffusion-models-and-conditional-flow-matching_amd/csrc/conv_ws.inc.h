@@ -56,6 +56,14 @@ constexpr size_t LDS_BYTES = NPLANES * (size_t)PLANE + NWBUF * 3 * (size_t)WTILE
 // Counter polls are bounded (p.spin_limit, default 1 << 22 polls of >= 64 cycles: seconds): a protocol bug or a wave that never arrives
 // ends in MI355_ERR_TIMEOUT instead of a hung GPU.  A wait that gives up stores 1 into the launch's error word (p.err; cold path inside
 // the poll's asm block), every later wait of that wave polls once, and the wave goes on: the tile is wrong, the grid drains at once.
+// A carried 1x1 skip conv (SKIP instantiations): ns centre-tap K chunks of the raw block input, each one more row item of the stream.  They travel in
+// PAIRS behind PAIRS of kernel rows: the consumers double-buffer their weight fragments by tap parity, a kernel row has three taps and a skip item
+// one, so both a row pair and an item pair leave the parity where it was and one copy of either loop body serves the whole stream.  An odd ns
+// is padded with an all-zero item.  Behind row pair rp (of nrp = 3 nm / 2) come item pairs skip_pair_first(rp) .. skip_pair_first(rp + 1) - 1 of the
+// tile's np = (ns + 1) / 2: spread evenly, the last row pair takes the rest (at least one, so a tile ends with a skip item).  BOTH roles derive
+// their item stream from these two functions: a miscount would end in the bounded poll.
+__host__ __device__ constexpr int skip_pair_first(int rp, int nrp, int np) { return rp * np / nrp; }
+__host__ __device__ constexpr int skip_pairs(int rp, int nrp, int np) { return skip_pair_first(rp + 1, nrp, np) - skip_pair_first(rp, nrp, np); }
 }  // namespace ws
 
 // GN affine (+ SiLU) of one 16-byte fragment.  bf16: fp32 math on element PAIRS (v_pk_fma/mul/add_f32: two elements per VALU
@@ -94,8 +102,13 @@ __device__ __forceinline__ u32x4 ws_pro_frag(const u32x4& raw, const f32x2 (&a2)
   return __builtin_bit_cast(u32x4, o);
 }
 
-template <typename T, int PRO>   // PRO: 0 = no prologue, 1 = GN affine, 2 = GN affine + SiLU
+// SKIP (prologue forms only): the launch carries its ResBlock's 1x1 skip conv.  A skip item is one more row of the stream: it takes ONE slot of
+// the weight-row ring (24 KB = its 8 KB weight tile + the 16 x 16 interior pixels of one 64-byte chunk of the raw block input, 16 KB), both moved
+// global -> LDS by DMA in the six pieces per wave a kernel row's weights take (so the loaders' counted waits are those of a kernel row), and
+// the consumers multiply its centre tap only (two half-taps).  The patch-plane ring is not involved: it stays the main chunks'.
+template <typename T, int PRO, bool SKIP = false>   // PRO: 0 = no prologue, 1 = GN affine, 2 = GN affine + SiLU
 __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_mt, int n_nt) {
+  static_assert(!SKIP || PRO != 0, "the carried skip conv rides in the prologue forms");
   using namespace ws;
   using E = Elem<T>;
   constexpr int V = E::VEC, CHUNK = E::CHUNK, ESZ = sizeof(T);
@@ -112,6 +125,9 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
   const bool loader = wave8 < 4;
   const int tpi = p.tiles_x * p.tiles_y;
   const int ngr = p.nchunks * 3;     // kernel rows (barrier intervals) per tile
+  const int nsk = SKIP ? (p.SC0 + p.SC1) / CHUNK : 0;   // skip chunks per tile
+  const int nsp = (nsk + 1) >> 1, nrp = ngr >> 1;       // skip item pairs / kernel row pairs per tile
+  const int wtiles = p.nchunks * 9 + nsk;               // weight tiles per 128-channel pack tile
   // Tile walk: items t = 0 .. ntp-1; 8 consecutive workgroups (one per XCD) take 8 consecutive pixel tiles, and the
   // workgroup 8 further on (same XCD, same L2) takes the next channel tile of the same pixels.
   const int ntp = ((n_mt + 7) / 8) * 8 * n_nt;
@@ -522,8 +538,23 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
     //      ds_write; lane l of a wave lands at M0 base + 16 l, probed in tools/probe/lds_dma_probe.cpp).  The host packer
     //      stores weights already in their LDS image, so a row (3 taps x 8 KB) is 6 linear 1-KB pieces per wave. ----
     int wl_t = t_first, wl_row = 0, wl_nt, wl_buf = 0;
-    { int mt; decode(wl_t, mt, wl_nt); }
+    // SKIP: the stream's position as (kernel row wl_row of the tile, wl_k: 0 = that row, j = skip item j - 1 of the wl_n behind it), the tile's
+    // running skip chunk wl_s, and the tile's interior pixel this lane moves in plane piece 4 i + wave (tile row 4 i + wave, column lane >> 2; -1 = outside)
+    int wl_k = 0, wl_s = 0, wl_n = 0;
+    int spix[4] = {-1, -1, -1, -1};
+    const uint32_t sfq16 = (uint32_t)(((lane & 3) ^ ((lane >> 3) & 3)) * 16);   // source fragment of LDS slot lane & 3 of pixel column lane >> 2 (the planes' swizzle)
+    auto skip_setup = [&](int mt) {
+      int n0, y0, x0;
+      origin(mt, n0, y0, x0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int y = y0 + 4 * i + wave8, x = x0 + (lane >> 2);
+        spix[i] = (y < p.Ho && x < p.Wo) ? (n0 * p.Ho + y) * p.Wo + x : -1;
+      }
+    };
+    { int mt; decode(wl_t, mt, wl_nt); if constexpr (SKIP) skip_setup(mt); }
     auto dma_w = [&]() {               // next row of the stream -> wbuf[wl_buf]
+      if constexpr (!SKIP) {
       const uint32_t so = ((uint32_t)wl_nt * p.nchunks * 9 + (uint32_t)wl_row * 3) * WTILE;
       if constexpr (!(WS_ABLATE & 8)) {
         char* dst = wbuf + wl_buf * (3 * WTILE) + wave8 * 1024;
@@ -536,6 +567,45 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
         wl_row = 0;
         wl_t = next_valid(wl_t);
         if (wl_t < ntp) { int mt; decode(wl_t, mt, wl_nt); }
+      }
+      } else {
+      // six 1-KB pieces per wave either way: a kernel row's three weight tiles, or a skip item's weight tile (two) and dense plane (four)
+      char* dst = wbuf + wl_buf * (3 * WTILE) + wave8 * 1024;
+      if (wl_k == 0) {
+        const uint32_t so = ((uint32_t)wl_nt * wtiles + (uint32_t)(wl_row * 3)) * WTILE;
+#pragma unroll
+        for (int i = 0; i < WIT; ++i)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void*)(dst + i * 4096), 16, woff[i], so, 0, 0);
+      } else {
+        // (the stream's position is wave-uniform; said explicitly, or the source descriptor chosen below is built per lane and read back through memory)
+        const int sidx = __builtin_amdgcn_readfirstlane(wl_s);
+        const uint32_t so = ((uint32_t)wl_nt * wtiles + (uint32_t)(p.nchunks * 9 + sidx)) * WTILE;
+        const bool real = sidx < nsk;   // the padding item of an odd count: every offset out of range, weights and plane are zeros
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void*)(dst + i * 4096), 16, real ? woff[i] : p.wbytes, so, 0, 0);
+        const int cb = sidx * CHUNK;
+        const bool first = cb < p.SC0;
+        const uint32_t pixb = (uint32_t)((first ? p.SC0 : p.SC1) * ESZ), oob = first ? p.skbytes0 : p.skbytes1;
+        const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(first || !p.sk1 ? p.sk0 : p.sk1), 0, oob, 0x00020000);
+        const uint32_t cso = (uint32_t)((first ? cb : cb - p.SC0) * ESZ);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const uint32_t vo = (spix[i] >= 0 && real) ? (uint32_t)spix[i] * pixb + sfq16 : oob;   // outside the image: an out-of-range offset, the DMA writes zeros
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsk, (__attribute__((address_space(3))) void*)(dst + WTILE + i * 4096), 16, vo, cso, 0, 0);
+        }
+        ++wl_s;
+      }
+      wl_buf = wl_buf == NWBUF - 1 ? 0 : wl_buf + 1;
+      if (wl_k == 0) wl_n = (wl_row & 1) ? 2 * skip_pairs(wl_row >> 1, nrp, nsp) : 0;
+      if (wl_k++ == wl_n) {
+        wl_k = 0;
+        if (++wl_row == ngr) {
+          wl_row = 0; wl_s = 0;
+          wl_t = next_valid(wl_t);
+          if (wl_t < ntp) { int mt; decode(wl_t, mt, wl_nt); skip_setup(mt); }
+        }
+      }
       }
     };
     // All but the 8 youngest vector-memory operations of this wave are complete: at the end of an interval those 8 are the
@@ -606,6 +676,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
       // interval queues the DMA of the next kernel row behind its fragment loads.
       auto body = [&](int c) {
         bool nx_ok = true;
+        int row = 3 * c;               // kernel row of the tile
         auto tail = [&]() {
           dma_w();
           STAMP(3)
@@ -615,6 +686,22 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
           ++R;
           acquire_free();              // before anything of the next interval is written
           STAMP(4)
+          if constexpr (SKIP) {
+            // the skip items behind a row pair, one interval each: nothing passes through registers; the six youngest operations are the next
+            // row's DMA pieces, everything older (this item's own pieces, issued one interval ago) has landed
+            if (row & 1) {
+              const int n = 2 * skip_pairs(row >> 1, nrp, nsp);
+              for (int j = 0; j < n; ++j) {
+                dma_w();
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_s_waitcnt(6 | (7 << 4) | (0 << 8));   // vmcnt(6) lgkmcnt(0)
+                bump(c_prod + wave8);
+                ++R;
+                acquire_free();
+              }
+            }
+            ++row;
+          }
         };
         // ---- ky = 0 ----
         cinit_load(t_next < ntp ? t_next : t);   // next tile's accumulator start values (tiny, L2-resident; loaded every chunk so that no load sits under a branch)
@@ -690,25 +777,43 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
     uint32_t rowc = 0;
     uint32_t pq0 = 0, pq1 = 0, pq2 = 0, pq3 = 0;   // producer counters read one half-tap before they are needed                // row of the stream this wave multiplies
     const bool gate512 = p.N > 0;   // always true, opaque to the compiler (WS_ABLATE & 512)
-    auto advance_row = [&]() {
+    auto advance_row = [&](bool main_row) __attribute__((always_inline)) {   // main_row: the row left behind was a kernel row (a skip item does not move the patch addresses)
       int bstep = 3 * WTILE, astep = AROWB;
       if (sel == NWBUF - 1) { sel = 0; bstep = -(NWBUF - 1) * 3 * WTILE; } else ++sel;
-      if (++ky == 3) {
-        ky = 0;
-        if (plane == NPLANES - 1) { plane = 0; astep = -(NPLANES - 1) * PLANE - 2 * AROWB; } else { ++plane; astep = PLANE - 2 * AROWB; }
-      }
+      if (main_row) {
+        if (++ky == 3) {
+          ky = 0;
+          if (plane == NPLANES - 1) { plane = 0; astep = -(NPLANES - 1) * PLANE - 2 * AROWB; } else { ++plane; astep = PLANE - 2 * AROWB; }
+        }
 #pragma unroll
-      for (int kx = 0; kx < 3; ++kx) a_cur[kx] += astep;
+        for (int kx = 0; kx < 3; ++kx) a_cur[kx] += astep;
+      }
       b_cur += bstep;
     };
-    auto read_a = [&](auto bufc, auto halfc, auto kxc) {
+    // a skip item's dense plane sits behind its weight tile in the row buffer: pixel (8 wm + 4 half + j, lr), same slot swizzle as the
+    // weight row wn * 64 + lr this lane reads (both follow lr), so its address is b_cur plus a wave-uniform offset
+    const int sa_delta = WTILE + (wm * 128 - wn * 64) * 64;
+    auto read_sa = [&](auto halfc) __attribute__((always_inline)) {
+      constexpr int half = decltype(halfc)::value;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) af[half][j] = *reinterpret_cast<const u32x4*>(wbuf + b_cur + sa_delta + (half * 4 + j) * 1024);
+    };
+    // the first patch fragments of whatever follows a row pair or an item pair (a skip item's dense plane or a kernel row's patch): one copy of the
+    // loads with the address and the row pitch selected, not two arms of a branch (a join that carries the fragments of two arms costs registers here)
+    auto read_next = [&](bool next_skip) __attribute__((always_inline)) {
+      const int base = next_skip ? NPLANES * PLANE + b_cur + sa_delta : a_cur[0];
+      const int pitch = next_skip ? 1024 : AROWB;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) af[0][j] = *reinterpret_cast<const u32x4*>(smem + base + j * pitch);
+    };
+    auto read_a = [&](auto bufc, auto halfc, auto kxc) __attribute__((always_inline)) {
       constexpr int buf = decltype(bufc)::value, half = decltype(halfc)::value, kx = decltype(kxc)::value;
       if constexpr (WS_ABLATE & 4) return;
       if constexpr (WS_ABLATE & 512) { if (gate512) return; }   // timing experiment: MFMAs on stale fragments, no LDS reads
 #pragma unroll
       for (int j = 0; j < 4; ++j) af[buf][j] = *reinterpret_cast<const u32x4*>(pbuf + a_cur[kx] + (half * 4 + j) * AROWB);
     };
-    auto read_b = [&](auto bufc, auto kxc) {
+    auto read_b = [&](auto bufc, auto kxc) __attribute__((always_inline)) {
       constexpr int buf = decltype(bufc)::value, kx = decltype(kxc)::value;
       if constexpr (WS_ABLATE & 4) return;
       if constexpr (WS_ABLATE & 512) { if (gate512) return; }
@@ -717,7 +822,9 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
     };
     // One half-tap: issue the LDS reads of the NEXT step, then the 16 MFMAs of this one.
     //   R: row parity inside the unrolled row pair, s = 2 * kx + half, ZERO: first tap of a tile (accumulators start at bias + emb)
-    auto step = [&](auto Rc, auto sc, auto zeroc, bool more_rows) {
+    //   nk (what follows the row): 0 = a kernel row, 3 (SKIP instantiations, a row pair's end) = a kernel row or a skip item (next_skip)
+    auto step = [&](auto Rc, auto sc, auto zeroc, bool more_rows, auto nkc, bool next_skip = false) __attribute__((always_inline)) {
+      constexpr int nk = decltype(nkc)::value;
       constexpr int R = decltype(Rc)::value, s = decltype(sc)::value;
       constexpr bool ZERO = decltype(zeroc)::value != 0;
       constexpr int half = s & 1, kx = s >> 1, bpar = (R + kx) & 1;
@@ -733,8 +840,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
           if constexpr (!(WS_ABLATE & 2048)) release_acquire(c_cons + wave, c_prod, rowc + 2u, pq0, pq1, pq2, pq3);
           ++rowc;
           STAMP(5)
-          advance_row();
-          read_a(IC<0>(), IC<0>(), IC<0>());
+          advance_row(true);
+          if constexpr (nk == 3) read_next(next_skip); else read_a(IC<0>(), IC<0>(), IC<0>());
           read_b(IC<(R + 1) & 1>(), IC<0>());
         }
       }
@@ -766,6 +873,27 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
       __builtin_amdgcn_sched_barrier(0);
     };
 
+    // One half of a skip item's single tap: Q = parity of its weight fragments; nk = 1: its pair's second item follows (static), 3: whatever follows
+    auto sstep = [&](auto Qc, auto halfc, bool more_rows, auto nkc, bool next_skip) __attribute__((always_inline)) {
+      constexpr int Q = decltype(Qc)::value, half = decltype(halfc)::value, nk = decltype(nkc)::value;
+      if constexpr (half == 0) {
+        read_sa(IC<1>());
+        poll_issue(c_prod, pq0, pq1, pq2, pq3);
+      } else if (more_rows) {
+        release_acquire(c_cons + wave, c_prod, rowc + 2u, pq0, pq1, pq2, pq3);
+        ++rowc;
+        advance_row(false);
+        if constexpr (nk == 1) read_sa(IC<0>()); else read_next(next_skip);
+        read_b(IC<Q ^ 1>(), IC<0>());
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) mma16(acc[half * 4 + j][ni], bf[Q][ni], af[half][j], T());
+      __builtin_amdgcn_sched_barrier(0);
+    };
+
     if constexpr (!(WS_ABLATE & 2048)) wait_ge_prod(c_prod, 1u);               // kernel row 0 of the first tile is staged
     STAMP(5)
     read_a(IC<0>(), IC<0>(), IC<0>());
@@ -778,13 +906,22 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
       const int co_w = nt * BN + wn * 64 + 4 * lq;
       for (int r = 0; r < ngr; r += 2) {
         const bool last_pair = r + 2 >= ngr;
-        if (r == 0) { read_cinit(); step(IC<0>(), IC<0>(), IC<1>(), true); step(IC<0>(), IC<1>(), IC<1>(), true); }
-        else { step(IC<0>(), IC<0>(), IC<0>(), true); step(IC<0>(), IC<1>(), IC<0>(), true); }
-        step(IC<0>(), IC<2>(), IC<0>(), true); step(IC<0>(), IC<3>(), IC<0>(), true);
-        step(IC<0>(), IC<4>(), IC<0>(), true); step(IC<0>(), IC<5>(), IC<0>(), true);
-        step(IC<1>(), IC<0>(), IC<0>(), true); step(IC<1>(), IC<1>(), IC<0>(), true);
-        step(IC<1>(), IC<2>(), IC<0>(), true); step(IC<1>(), IC<3>(), IC<0>(), true);
-        step(IC<1>(), IC<4>(), IC<0>(), true); step(IC<1>(), IC<5>(), IC<0>(), !last_pair);
+        if (r == 0) { read_cinit(); step(IC<0>(), IC<0>(), IC<1>(), true, IC<0>()); step(IC<0>(), IC<1>(), IC<1>(), true, IC<0>()); }
+        else { step(IC<0>(), IC<0>(), IC<0>(), true, IC<0>()); step(IC<0>(), IC<1>(), IC<0>(), true, IC<0>()); }
+        step(IC<0>(), IC<2>(), IC<0>(), true, IC<0>()); step(IC<0>(), IC<3>(), IC<0>(), true, IC<0>());
+        step(IC<0>(), IC<4>(), IC<0>(), true, IC<0>()); step(IC<0>(), IC<5>(), IC<0>(), true, IC<0>());
+        step(IC<1>(), IC<0>(), IC<0>(), true, IC<0>()); step(IC<1>(), IC<1>(), IC<0>(), true, IC<0>());
+        step(IC<1>(), IC<2>(), IC<0>(), true, IC<0>()); step(IC<1>(), IC<3>(), IC<0>(), true, IC<0>());
+        if constexpr (!SKIP) { step(IC<1>(), IC<4>(), IC<0>(), true, IC<0>()); step(IC<1>(), IC<5>(), IC<0>(), !last_pair, IC<0>()); }
+        else {
+          const int k = skip_pairs(r >> 1, nrp, nsp);   // the item pairs behind this row pair (the last row pair has at least one)
+          step(IC<1>(), IC<4>(), IC<0>(), true, IC<0>()); step(IC<1>(), IC<5>(), IC<0>(), true, IC<3>(), k > 0);
+          for (int q = 0; q < k; ++q) {
+            const bool more = !(last_pair && q + 1 == k);
+            sstep(IC<0>(), IC<0>(), true, IC<1>(), true); sstep(IC<0>(), IC<1>(), true, IC<1>(), true);
+            sstep(IC<1>(), IC<0>(), true, IC<3>(), true); sstep(IC<1>(), IC<1>(), more, IC<3>(), q + 1 < k);
+          }
+        }
       }
       // End of a tile: the last row is released before the epilogue (the loaders keep running through it), but the first fragments
       // of the next tile are read AFTER it - held across the epilogue they were 32 more live registers at the kernel's pressure peak
@@ -890,7 +1027,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
       if (t_next < ntp) {
         if constexpr (!(WS_ABLATE & 2048)) wait_ge_prod(c_prod, rowc + 2u);
         ++rowc;
-        advance_row();
+        advance_row(!SKIP);
         read_a(IC<0>(), IC<0>(), IC<0>());
         read_b(IC<0>(), IC<0>());
       }
@@ -909,16 +1046,23 @@ static int ws_num_cus() {
   return ncu;
 }
 static bool ws_eligible(int enabled, int ks, int BM, int BN, int G, int bn_pack, int out_mode, int stride, int nchunks, int N, int Ho, int Wo, int Cout) {
-  if (!enabled || ks != 3 || BM != 128 || BN != 128 || G != 1 || bn_pack != 128 || out_mode != OUT_NHWC) return false;
+  if (!(enabled & 1) || ks != 3 || BM != 128 || BN != 128 || G != 1 || bn_pack != 128 || out_mode != OUT_NHWC) return false;
   if (stride != 1 || nchunks < 2 || (nchunks & 1)) return false;
   if (Wo < ws::VW || Ho < ws::TH) return false;
   const int n_mt = N * ((Wo + ws::VW - 1) / ws::VW) * ((Ho + ws::TH - 1) / ws::TH), n_nt = (Cout + 127) / 128;
-  return n_mt * n_nt >= ws_num_cus();   // fewer tiles than CUs: the plain kernel's smaller tiles fill the chip better
+  return (enabled & 4) || n_mt * n_nt >= ws_num_cus();   // fewer tiles than CUs: the plain kernel's smaller tiles fill the chip better (knob bit 2, tests: take them too)
+}
+// ... and may carry the ResBlock's 1x1 skip conv (knob bit 1): a GroupNorm prologue form without split weights, plain geometry, no residual of its
+// own, whole 64-byte skip chunks
+static bool ws_skip_eligible(int enabled, const ConvKArgs& a, int mode, bool fused_act, bool wsplit, int CH) {
+  if (!(enabled & 2) || !a.sk0 || !a.pro_a || wsplit || mode != CONV_UNIT || fused_act || a.res_mode != RES_NONE) return false;
+  if (a.SC0 <= 0 || a.SC0 % CH || a.SC1 % CH) return false;
+  return true;
 }
 
 // a shape ws_eligible accepts
 template <typename T>
-int launch_ws(ConvKArgs a, hipStream_t s) {
+int launch_ws(ConvKArgs a, int grid_cap, hipStream_t s) {
   a.lvw = 4; a.lth = 4; a.PW = ws::PW; a.PH = ws::PH; a.NP = ws::NPX;
   a.tiles_x = (a.Wo + ws::VW - 1) / ws::VW; a.tiles_y = (a.Ho + ws::TH - 1) / ws::TH;
   const int n_mt = a.N * a.tiles_x * a.tiles_y, n_nt = (a.Cout + 127) / 128;
@@ -926,12 +1070,17 @@ int launch_ws(ConvKArgs a, hipStream_t s) {
   using KernT = void (*)(ConvKArgs, int, int);
   KernT kern = !a.pro_a ? (KernT)conv3x3_ws_kernel<T, 0> : (a.pro_silu ? (KernT)conv3x3_ws_kernel<T, 2> : (KernT)conv3x3_ws_kernel<T, 1>);
   int rc;
+  if (a.sk0) {   // the carried skip conv (conv_route: a prologue form)
+    kern = a.pro_silu ? (KernT)conv3x3_ws_kernel<T, 2, true> : (KernT)conv3x3_ws_kernel<T, 1, true>;
+    rc = a.pro_silu ? mi355_allow_big_lds(conv3x3_ws_kernel<T, 2, true>, "conv3x3 (persistent)") : mi355_allow_big_lds(conv3x3_ws_kernel<T, 1, true>, "conv3x3 (persistent)");
+  } else
   if (!a.pro_a) rc = mi355_allow_big_lds(conv3x3_ws_kernel<T, 0>, "conv3x3 (persistent)");
   else if (a.pro_silu) rc = mi355_allow_big_lds(conv3x3_ws_kernel<T, 2>, "conv3x3 (persistent)");
   else rc = mi355_allow_big_lds(conv3x3_ws_kernel<T, 1>, "conv3x3 (persistent)");
   if (rc) return rc;
   const int ntp = ((n_mt + 7) / 8) * 8 * n_nt;
-  const int grid = ntp < ncu ? ntp : ncu;   // one persistent workgroup per CU
+  int grid = ntp < ncu ? ntp : ncu;   // one persistent workgroup per CU
+  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;   // (tests: several tiles per workgroup at small shapes)
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), ws::LDS_BYTES, s, a, n_mt, n_nt);
   return 0;
 }

@@ -137,10 +137,13 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
 #endif
   // ---- extras (mi355_conv2d_ex): the small-level kernel's fused forms, as the engine's walker asks for them ----
   ExScratch xs;
+  bool ex_stats = false;
   void* act_dev[2] = {nullptr, nullptr};
   std::vector<char> packed_f; std::vector<float> bias_f;
   if (ex) {
     ex->act_done = 0; ex->skip_done = 0;
+    ex_stats = ex->route[3] == MI355_CONV_EXTRAS_STATS && ex->stat_a;   // the struct's later tail is read only behind this word
+    if (ex_stats) ex->stat_slots = 0;
     for (int i = 0; i < 4; ++i) ex->route[i] = -1;
     MI355_REQUIRE(nhwc && !pool, -4, "conv2d_ex: extras need an NHWC output and no pooling");
     if (ex->skip_x0) {
@@ -182,6 +185,15 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
       d.act2_silu = ex->act_silu[1]; d.act2_stride = ex->act_ctotal[1]; d.act2_coff = ex->act_coff[1]; d.act2_cpg = ex->act_ctotal[1] / 32;
     }
   }
+  if (ex_stats) {   // the output's GroupNorm partial sums (a slot no wave writes stays NaN)
+    MI355_REQUIRE(nhwc && ex->stat_b && ex->stat_gamma && ex->stat_beta, -1, "conv2d_ex: statistics need an NHWC output, stat_b, stat_gamma and stat_beta");
+    const int cap = 4 * ((g.Ho * g.Wo + 63) / 64) + 8;   // the plan builder's stats_cap (unet_engine.hip)
+    const size_t sb = (size_t)batch * cap * (cout / 4) * 2 * 4;
+    float* st = reinterpret_cast<float*>(xs.get(sb));
+    MI355_REQUIRE(st, -2, "conv2d_ex: out of device memory");
+    MI355_CHECK_HIP(hipMemsetAsync(st, 0xFF, sb, s));
+    d.gn_stats = st; d.gn_slots_cap = cap;
+  }
   ConvRoute route;
   if ((rc = conv_route(d, &route))) {
     if (d.skip_src0) { mi355_set_error("conv2d_ex: this launch cannot carry the fused skip conv (shape, batch or knobs)"); return MI355_ERR_UNSUPPORTED; }
@@ -190,6 +202,13 @@ static int conv2d_impl(const float* x, const float* x1, int cin1, const float* w
   if ((rc = conv_launch(d, route, s))) return rc;
   if (ex) {
     ex->skip_done = route.skip; ex->act_done = route.act_done;
+    if (ex_stats && route.gn_slots > 0) {
+      GnFinDesc f; f.stats0 = d.gn_stats; f.slots0 = route.gn_slots; f.C0 = cout;
+      f.N = batch; f.HW = g.Ho * g.Wo; f.gamma = ex->stat_gamma; f.beta = ex->stat_beta;
+      f.a = ex->stat_a; f.b = ex->stat_b; f.dtype = dtype; f.src0 = yout;
+      if ((rc = gn_finalize_launch(f, s))) return rc;
+      ex->stat_slots = route.gn_slots;
+    }
     ex->route[0] = route.kernel; ex->route[1] = route.form; ex->route[2] = route.geom.BM; ex->route[3] = route.geom.BN;
     for (int k = 0; k < 2; ++k)
       if (act_dev[k] && (route.act_done & (1 << k)) && (rc = unpack_nchw_launch(dtype, act_dev[k], batch, g.Ho * g.Wo, ex->act_ctotal[k], ex->act_out[k], s))) return rc;

@@ -268,31 +268,38 @@ struct Walker {
       return -1;
     }
     const int skip_idx = cin != cout ? (int)net->ops.size() - 1 : -1;
+    // The 1x1 skip_connection can ride in the second conv as centre-tap K chunks of the raw block input (unet.py:312-317, 351: return
+    // skip_connection(x) + h), if the launch agrees (conv_route).  Small levels (apply-type norms: the second conv reads one already-activated
+    // tensor): the small-level kernel, conv_small bit 3.  Levels at least 16 pixels wide (the second conv carries the GroupNorm + SiLU prologue):
+    // the warp-specialised kernel, conv_ws bit 1.  Both weight images are kept: a launch that declines runs the two convs on their own.
+    auto carry_skip = [&](int out) {
+      if (out < 0 || skip_idx < 0 || net->ops[skip_idx].ks != 1 || cfg.differentiable || net->wsplit || cout % 128 != 0) return;
+      const int conv2_idx = (int)net->ops.size() - 1;
+      PlanOp& c2 = net->ops[conv2_idx];
+      const float* w3 = P(p + ".out_layers.3.weight", {cout, cout, 3, 3});
+      const float* w1 = P(p + ".skip_connection.weight", {cout, cin, 1, 1});
+      const float* b3 = P(p + ".out_layers.3.bias", {cout});
+      const float* b1 = P(p + ".skip_connection.bias", {cout});
+      c2.wf_off = alloc(conv_packed_weight_bytes_skip(dtype, cout, cout, cin));
+      c2.bf_off = alloc((size_t)cout * 4);
+      if (!dry && w3 && w1 && b3 && b1) {
+        conv_pack_weights_skip(dtype, w3, w1, cout, cout, cin, blob.data() + c2.wf_off);
+        float* bs = reinterpret_cast<float*>(blob.data() + c2.bf_off);
+        for (int i = 0; i < cout; ++i) bs[i] = b3[i] + b1[i];
+      }
+      c2.skip_op = skip_idx;
+      net->ops[skip_idx].carrier = conv2_idx;
+    };
     if (y2 >= 0) {
       const int out = add_conv(p + ".out_layers.3", y2, -1, cout, cout, 3, CONV_UNIT, false, 0, 0, -1, res, res_mode, OUT_NHWC);
-      // Small levels (apply-type norms: the second conv reads one already-activated tensor): the 1x1 skip_connection can ride in the
-      // second conv as centre-tap K chunks of the raw block input (unet.py:312-317, 351: return skip_connection(x) + h), if the launch
-      // agrees (conv_route: the small-level kernel, conv_small bit 3).  Both weight images are kept.
-      if (out >= 0 && skip_idx >= 0 && net->ops[skip_idx].ks == 1 && !cfg.differentiable && !net->wsplit && cout % 128 == 0) {
-        const int conv2_idx = (int)net->ops.size() - 1;
-        PlanOp& c2 = net->ops[conv2_idx];
-        const float* w3 = P(p + ".out_layers.3.weight", {cout, cout, 3, 3});
-        const float* w1 = P(p + ".skip_connection.weight", {cout, cin, 1, 1});
-        const float* b3 = P(p + ".out_layers.3.bias", {cout});
-        const float* b1 = P(p + ".skip_connection.bias", {cout});
-        c2.wf_off = alloc(conv_packed_weight_bytes_skip(dtype, cout, cout, cin));
-        c2.bf_off = alloc((size_t)cout * 4);
-        if (!dry && w3 && w1 && b3 && b1) {
-          conv_pack_weights_skip(dtype, w3, w1, cout, cout, cin, blob.data() + c2.wf_off);
-          float* bs = reinterpret_cast<float*>(blob.data() + c2.bf_off);
-          for (int i = 0; i < cout; ++i) bs[i] = b3[i] + b1[i];
-        }
-        c2.skip_op = skip_idx;
-        net->ops[skip_idx].carrier = conv2_idx;
-      }
+      carry_skip(out);
       return out;
     }
-    return add_conv(p + ".out_layers.3", h1, -1, cout, cout, 3, CONV_UNIT, false, 1, 1, -1, res, res_mode, OUT_NHWC);
+    const int out = add_conv(p + ".out_layers.3", h1, -1, cout, cout, 3, CONV_UNIT, false, 1, 1, -1, res, res_mode, OUT_NHWC);
+    // (Cout % 256 != 0: what the warp-specialised kernel takes in the network; the 256-channel 16x16 blocks run on the ping-pong kernel, whose
+    //  route declines the fused form - no second weight image and no probe for them)
+    if (out >= 0 && T(h1).W >= 16 && T(h1).H >= 16 && cout % 256 != 0) carry_skip(out);
+    return out;
   }
 
   int attn_block(const std::string& p, int x, int C, int heads) {
@@ -805,7 +812,7 @@ struct Resolver {
           break;
         case OP_CONV: {
           if (!carried && op.carrier >= 0) {
-            // 1x1 skip_connection of a small-level ResBlock: does the second conv's launch take it along?  The carrier is the next op and
+            // 1x1 skip_connection of a ResBlock whose plan names a carrier (small levels, 128-channel large levels): does the second conv's launch take it along?  The carrier is the next op and
             // nothing it is described from changes in between, so the probe's description and route are that step's.
             f->steps.emplace_back(ConvCarried{});
             ConvStep& c2 = push_conv(f);

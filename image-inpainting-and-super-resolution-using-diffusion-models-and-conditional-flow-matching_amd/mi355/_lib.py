@@ -71,7 +71,8 @@ class ConvExtrasC(C.Structure):
                 ("skip_w_host", C.c_void_p), ("skip_bias_host", C.c_void_p),
                 ("act_out", C.c_void_p * 2), ("act_gamma", C.c_void_p * 2), ("act_beta", C.c_void_p * 2),
                 ("act_ctotal", C.c_int32 * 2), ("act_coff", C.c_int32 * 2), ("act_silu", C.c_int32 * 2),
-                ("act_film", C.c_void_p), ("act_done", C.c_int32), ("skip_done", C.c_int32), ("route", C.c_int32 * 4)]
+                ("act_film", C.c_void_p), ("act_done", C.c_int32), ("skip_done", C.c_int32), ("route", C.c_int32 * 4),
+                ("stat_gamma", C.c_void_p), ("stat_beta", C.c_void_p), ("stat_a", C.c_void_p), ("stat_b", C.c_void_p), ("stat_slots", C.c_int32)]
 
 
 class UNetStatsC(C.Structure):

@@ -373,11 +373,15 @@ class Ops:
             info.update(kernel=ex.route[0], form=ex.route[1], tile_m=ex.route[2], tile_n=ex.route[3])
         return y
 
-    def conv2d_ex(self, x, weight, bias, dtype=_lib.MI355_F32, skip=None, sites=(), film=None, debug=None):
+    def conv2d_ex(self, x, weight, bias, dtype=_lib.MI355_F32, skip=None, sites=(), film=None, debug=None, gn=None, gn_silu=False, emb=None,
+                  stats=None):
         """The 3x3 conv of the 8x8 / 4x4 levels with its fused forms (mi355_conv2d_ex): skip = (xs0, xs1 or None, w1 [Co, c0 + c1, 1, 1], b1) is a
         1x1 conv of cat(xs0, xs1) accumulated into the same output; sites = up to two dicts (ctotal, coff, gamma, beta, silu): GroupNorm32 (+SiLU)
         of the output as channels coff.. of a ctotal-channel tensor, written by the epilogue; film [B, 2 Co] on site 0.  Returns
-        (y, [act or None per site], skip_done)."""
+        (y, [act or None per site], skip_done).  gn = (gamma, beta) device tensors: the GroupNorm32 (+ SiLU) input prologue; emb [B, Co]; stats: a
+        dict that receives the finalized GroupNorm statistics of the output the launch produced itself (slots, and for slots > 0 a, b [B, Co]
+        for gamma = 1, beta = 0: a = rstd, b = -mean rstd of each channel's group) - with gn the 3x3 conv is the warp-specialised kernel's
+        prologue form, which carries the skip conv at the large levels."""
         B, Cin, H, W = x.shape
         Co, Ci, k, _ = weight.shape
         assert Ci == Cin and k == 3 and len(sites) <= 2
@@ -408,10 +412,22 @@ class Ops:
             ex.act_ctotal[i] = st["ctotal"]; ex.act_coff[i] = st["coff"]; ex.act_silu[i] = int(st.get("silu", True))
         if film is not None:
             ex.act_film = _req(film, "film")
+        if stats is not None:
+            one, zero = torch.ones(Co, device=x.device), torch.zeros(Co, device=x.device)
+            sa, sb = torch.full((B, Co), float("nan"), device=x.device), torch.full((B, Co), float("nan"), device=x.device)
+            keep += [one, zero]
+            ex.route[3] = 0x53544154   # MI355_CONV_EXTRAS_STATS: the stat_* fields are present
+            ex.stat_gamma = _req(one, "stat_gamma"); ex.stat_beta = _req(zero, "stat_beta"); ex.stat_a = _req(sa, "stat_a"); ex.stat_b = _req(sb, "stat_b")
+        if emb is not None and emb.shape != (B, Co):
+            raise ValueError("emb must be [B, Co]")
         check(L.mi355_conv2d_ex(_req(x, "x"), None, 0, C.cast(w.data_ptr(), fp), C.cast(b.data_ptr(), fp) if b is not None else None, _req(y, "y"),
-                                B, Cin, H, W, Co, 3, 1, 0, None, None, 0, None, None, 1, dtype,
+                                B, Cin, H, W, Co, 3, 1, 0, _req(gn[0], "gamma") if gn else None, _req(gn[1], "beta") if gn else None, int(gn_silu),
+                                _req(emb, "emb") if emb is not None else None, None, 1, dtype,
                                 C.byref(debug if debug is not None else _lib.debug_config()), C.c_void_p(ws.data_ptr()), wsb, _stream(), C.byref(ex)),
               "mi355_conv2d_ex")
+        if stats is not None:
+            stats.update(slots=ex.stat_slots, a=sa if ex.stat_slots > 0 else None, b=sb if ex.stat_slots > 0 else None,
+                         kernel=ex.route[0], tile_m=ex.route[2], tile_n=ex.route[3])
         return y, [a if (ex.act_done >> i) & 1 else None for i, a in enumerate(acts)], bool(ex.skip_done)
 
     def qkv_attention(self, qkv, heads, new_order=False, dtype=_lib.MI355_F32):

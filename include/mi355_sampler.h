@@ -45,7 +45,9 @@ extern "C" {
 /* ABI version = 100 * major + minor.  The minor number counts additive changes; 108: mi355_attn_block_fused (the fused AttentionBlock front half,
  * csrc/attn_fused.hip, as a test op that reports which kernel form it launched; a new symbol only); later additions to 108: mi355_lowres_seed,
  * mi355_cfm_recon_workspace_bytes and mi355_cfm_recon_sample (training-free in-painting / super-resolution of a flow; new symbols only); then
- * mi355_conv2d_vjp (the conv data gradient of the U-Net backward as a test op; a new symbol only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * mi355_conv2d_vjp (the conv data gradient of the U-Net backward as a test op; a new symbol only); then conv_ws became a bit mask (bit 1: the
+ * warp-specialised conv carries a ResBlock's 1x1 skip conv, off in mi355_debug_defaults; bits 2 and 8.. for tests) and mi355_conv_extras gained the
+ * stat_* fields at its end, read only behind MI355_CONV_EXTRAS_STATS in route[3] (a caller built against the shorter struct is unaffected).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -69,7 +71,11 @@ const char* mi355_last_error(void);
  * mi355_debug_defaults) = the shipped behaviour.  The struct is COPIED into the handle at mi355_unet_create and passed per call to
  * the test ops: the library reads no environment variable and keeps no process-global switch. */
 typedef struct mi355_debug_config {
-  int32_t conv_ws;         /* 1: 3x3 convs of the large levels run on the persistent warp-specialised kernel (conv_ws.inc.h); 0: plain tiles */
+  int32_t conv_ws;         /* 3: bit 0: 3x3 convs of the large levels run on the persistent warp-specialised kernel (conv_ws.inc.h), off: plain tiles;
+                            *    bit 1: a ResBlock's 1x1 skip_connection rides in the block's second 3x3 conv on that kernel (GroupNorm-prologue form, images
+                            *    at least 16 wide) as centre-tap row items of the raw block input (no launch, no tensor); bit 2 (tests): the kernel also takes
+                            *    launches with fewer tiles than CUs - EVERY eligible 3x3 conv of the handle or call, not only the carrying ones;
+                            *    bits 8..: (tests) at most this many workgroups per launch of the kernel, again for every conv on it */
   int32_t conv_small;      /* 15: bit 0: 8x8 / 4x4 levels run on the LDS-resident-patch kernel (conv_small.inc.h); bit 1: its whole-chip 8x8 launches use eight
                             *    waves of 32 channels (two per SIMD) instead of four of 64; bit 2: the stride-2 Downsample convs 16 -> 8 and 8 -> 4 too;
                             *    bit 3: a ResBlock's 1x1 skip_connection rides in the block's second 3x3 conv as centre-tap K chunks (no launch, no tensor) */
@@ -592,7 +598,14 @@ typedef struct mi355_conv_extras {
                                   * conv_route decided them (csrc/ops.h ConvKernel / ConvRoute::form; the ping-pong 3x3 kernel is family 5, its forms 0 wide,
                                   * 1 narrow, 2 wide in phase form); -1 if the call failed before its launch.  With no fused form asked for (everything else
                                   * zero) mi355_conv2d_ex is mi355_conv2d plus this report, resampling and a second source included */
+  /* (a later addition, at the struct's end; read ONLY when the caller sets route[3] = MI355_CONV_EXTRAS_STATS on entry - route[] is otherwise an
+   * output, so a caller built against the shorter struct, which zeroes it, never has these words read) the launch's fused GroupNorm statistics of its
+   * OUTPUT, finalized: with stat_a set the conv is asked for its partial sums and, where the launch fills them (stat_slots > 0), gn_finalize turns them into a = gamma rstd, b = beta - mean a per (image, channel)
+   * with the device vectors stat_gamma / stat_beta [cout]: stat_a / stat_b are device [batch][cout] fp32 */
+  const float* stat_gamma; const float* stat_beta; float* stat_a; float* stat_b;
+  int32_t stat_slots;            /* out */
 } mi355_conv_extras;
+#define MI355_CONV_EXTRAS_STATS 0x53544154   /* mi355_conv_extras::route[3] on entry: the stat_* fields are present */
 int mi355_conv2d_ex(const float* x, const float* x1, int cin1, const float* w_host, const float* bias_host, float* y, int batch, int cin,
                     int h, int w, int cout, int ksize, int stride, int resample, const float* gn_gamma, const float* gn_beta, int gn_silu,
                     const float* emb, const float* res, int res_mode, int dtype, const mi355_debug_config* debug, void* workspace,
