@@ -230,6 +230,13 @@ int mi355_mse_per_sample(const float* a, const float* b, float* out, int batch, 
   MI355_REQUIRE(a && b && out, -1, "mse_per_sample: null argument");
   return mse_per_sample_launch(a, b, out, batch, elems_per_sample, S(stream));
 }
+int mi355_image_metrics(const float* x, const float* ref, float* out, int batch, int channels, int h, int w, float data_range,
+                        const float* taps_host, int win, float cov_norm, float k1, float k2, void* stream) {
+  MI355_REQUIRE(x, -1, "image_metrics: x is null");
+  MI355_REQUIRE(ref, -1, "image_metrics: ref is null");
+  MI355_REQUIRE(out, -1, "image_metrics: out is null");
+  return image_metrics_launch(x, ref, out, batch, channels, h, w, data_range, taps_host, win, cov_norm, k1, k2, S(stream));
+}
 int mi355_lincomb_per_sample(float* out, const float* x, const float* y, const float* a, const float* b, int batch,
                              int64_t elems_per_sample, void* stream) {
   return lincomb_per_sample_launch(out, x, y, a, b, batch, elems_per_sample, S(stream));

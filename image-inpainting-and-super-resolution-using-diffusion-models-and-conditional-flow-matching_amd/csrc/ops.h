@@ -298,6 +298,9 @@ int clip_launch(float* x, float lo, float hi, int64_t n, hipStream_t s);
 int mse_per_sample_launch(const float* a, const float* b, float* out, int batch, int64_t per, hipStream_t s);
 int lincomb_per_sample_launch(float* out, const float* x, const float* y, const float* a, const float* b, int batch, int64_t per,
                               hipStream_t s);
+// per-sample { mse, data_range, psnr, ssim } of x against ref, one workgroup per sample (metrics.hip); taps_host NULL = uniform window
+int image_metrics_launch(const float* x, const float* ref, float* out, int batch, int channels, int h, int w, float data_range,
+                         const float* taps_host, int win, float cov_norm, float k1, float k2, hipStream_t s);
 int ema_update_launch(float* target, const float* source, float decay, float one_minus_decay, int64_t n, hipStream_t s);
 int quantize_u8_launch(const float* x, uint8_t* out, int64_t n, hipStream_t s);
 int to_unit_range_launch(const float* x, float* out, int64_t n, hipStream_t s);

@@ -7,6 +7,11 @@ LPIPS and FID need downloaded network weights (`lpips.LPIPS(net='vgg')`, torchme
 unavailable offline), so they are hooks: pass `lpips_fn(x0, batch) -> [B,1,1,1]` and / or a `fid` object with
 `update(img_uint8ish, real=bool)` / `compute()`; without them the keys are written as `None`.  The MSE is the HIP kernel
 `mi355_mse_per_sample`; the sampler is whatever `get_conditional_sample_fn` returned (HIP loop).
+
+`metrics=("mse", "lpips", "psnr", "ssim")` adds the other two numbers of the reference's results table
+(`AD/image_diffusion/trainer2.py:103-129`: skimage's PSNR and SSIM per image, data range = the ground truth's max - min): one
+`mi355_image_metrics` launch per batch gives MSE, PSNR and SSIM together, and `results.json` gains `psnr_*` / `ssim_*` in the
+reference's order (mse, lpips, psnr, ssim within each of mean, median, std).
 """
 from __future__ import annotations
 
@@ -25,14 +30,21 @@ def to_img(x):
 
 
 def evaluate(cond_sample_fn, likelihood, batches, experiment_dir, num_batches=None, lpips_fn=None, fid=None, save_images=True,
-             noise_fn=torch.randn_like):
+             noise_fn=torch.randn_like, metrics=("mse", "lpips")):
     """batches: iterable of image tensors [B,C,H,W] in [-1,1] already on the sampling device (or (images, labels) pairs).
+    metrics: which per-sample numbers to collect, any of "mse", "lpips", "psnr", "ssim" (reported in that order).
     Returns the `results` dict that is also written to `<experiment_dir>/results.json`."""
+    known = ("mse", "lpips", "psnr", "ssim")
+    unknown = [m for m in metrics if m not in known]
+    if unknown:
+        raise ValueError(f"unknown metrics {unknown}: choose from {known}")
+    names = [m for m in known if m in metrics]
+    fused = "psnr" in names or "ssim" in names   # one image_metrics launch per batch then yields mse, psnr and ssim
     gen_dir = os.path.join(str(experiment_dir), "generated")
     gt_dir = os.path.join(str(experiment_dir), "generated_groundtruth")
     os.makedirs(gen_dir, exist_ok=True)
     os.makedirs(gt_dir, exist_ok=True)
-    metrics = {"mse": [], "lpips": []}
+    collected = {name: [] for name in names}
     idx = 0
     for k, batch in enumerate(batches):
         if num_batches is not None and k >= num_batches:
@@ -54,11 +66,17 @@ def evaluate(cond_sample_fn, likelihood, batches, experiment_dir, num_batches=No
                 save_image(cond, os.path.join(gt_dir, f"image_gt_{str(idx).zfill(3)}.png"), nrow=1, padding=0)
                 save_image(im_true, os.path.join(gt_dir, f"image_gt2_{str(idx).zfill(3)}.png"), nrow=1, padding=0)
                 idx += 1
-        metrics["mse"].append(default_ops.mse_per_sample(x0.float().contiguous(), batch))
-        if lpips_fn is not None:
-            metrics["lpips"].append(lpips_fn(x0, batch).reshape(-1).float())
+        if fused:
+            m = default_ops.image_metrics(x0.float().contiguous(), batch)
+            for name in ("mse", "psnr", "ssim"):
+                if name in collected:
+                    collected[name].append(m[name])
+        elif "mse" in collected:
+            collected["mse"].append(default_ops.mse_per_sample(x0.float().contiguous(), batch))
+        if lpips_fn is not None and "lpips" in collected:
+            collected["lpips"].append(lpips_fn(x0, batch).reshape(-1).float())
     results = {}
-    for name, vals in metrics.items():
+    for name, vals in collected.items():
         if vals:
             v = torch.cat(vals, dim=0)
             results.update({f"{name}_mean": torch.mean(v).item(), f"{name}_median": torch.median(v).item(), f"{name}_std": torch.std(v).item()})
@@ -66,7 +84,7 @@ def evaluate(cond_sample_fn, likelihood, batches, experiment_dir, num_batches=No
             results.update({f"{name}_mean": None, f"{name}_median": None, f"{name}_std": None})
     results["fid"] = fid.compute().item() if fid is not None else None
     # key order of the reference: means, medians, stds, fid
-    ordered = {k: results[k] for suffix in ("_mean", "_median", "_std") for k in (f"mse{suffix}", f"lpips{suffix}")}
+    ordered = {f"{name}{suffix}": results[f"{name}{suffix}"] for suffix in ("_mean", "_median", "_std") for name in names}
     ordered["fid"] = results["fid"]
     with open(os.path.join(str(experiment_dir), "results.json"), "w") as f:
         json.dump(ordered, f)

@@ -152,6 +152,7 @@ SIGNATURES = {
     "mi355_clip": (_I, [_VP, _F, _F, _I64, _VP]),
     "mi355_ema_update": (_I, [_VP, _VP, _F, _F, _I64, _VP]),
     "mi355_mse_per_sample": (_I, [_VP, _VP, _VP, C.c_int, _I64, _VP]),
+    "mi355_image_metrics": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _F, _FP, _I, _F, _F, _F, _VP]),
     "mi355_lincomb_per_sample": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I64, _VP]),
     "mi355_resize_bilinear": (_I, [_VP, _VP, _I64, _I, _I, _I, _I, _VP]),
     "mi355_paint_patch": (_I, [_VP, _VP, _VP, _I, _F, _I, _VP, _I, _I, _I, _I, _VP]),

@@ -164,6 +164,47 @@ class Ops:
         check(_lib.lib().mi355_mse_per_sample(_req(a, "a"), _req(b, "b"), _req(out, "out"), a.shape[0], a[0].numel(), _stream()))
         return out
 
+    def image_metrics(self, x, ref, data_range=None, win_size=None, gaussian_weights=False, sigma=1.5, use_sample_covariance=True,
+                      K1=0.01, K2=0.03):
+        """Per-sample quality of x against ref, both [B, C, H, W] fp32 on the device -> {"mse", "data_range", "psnr", "ssim"}, float32 [B]
+        each: skimage's peak_signal_noise_ratio and structural_similarity(channel_axis=0) with their defaults, for the whole batch in one
+        launch (calculate_psnr / calculate_ssim and the per-image loop, AD/image_diffusion/trainer2.py:15-30,119-121).  data_range None: each
+        sample's max(ref) - min(ref), what the reference passes.  Uniform window: win_size 7; gaussian_weights: radius int(3.5 sigma + 0.5)."""
+        for t, name in ((x, "x"), (ref, "ref")):
+            if isinstance(t, torch.Tensor) and not t.is_cuda:
+                raise MI355BackendError(f"{name} is on {t.device}: the MI355X HIP backend needs device tensors (no CPU fallback)")
+        if x.dim() != 4 or x.shape != ref.shape:
+            raise MI355BackendError(f"image_metrics: x and ref must be [B, C, H, W] of one shape, got {tuple(x.shape)} and {tuple(ref.shape)}")
+        B, Cc, H, W = x.shape
+        if data_range is not None and not float(data_range) > 0:
+            raise MI355BackendError(f"image_metrics: data_range must be positive (None: each sample's own range), got {data_range}")
+        taps = None
+        if gaussian_weights:
+            # skimage filters with scipy's gaussian_filter(truncate=3.5): radius int(3.5 sigma + 0.5), weights normalised to sum 1
+            r = int(3.5 * float(sigma) + 0.5)
+            win = 2 * r + 1
+            if not 3 <= win <= 15:
+                raise MI355BackendError(f"image_metrics: sigma = {sigma} gives a window of {win} taps; 3 to 15 are supported")
+            wts = torch.exp(-0.5 * torch.arange(-r, r + 1, dtype=torch.float64) ** 2 / float(sigma) ** 2)
+            taps = (C.c_float * win)(*(wts / wts.sum()).float().tolist())
+            cov_norm = 1.0
+        else:
+            win = 7 if win_size is None else int(win_size)
+            cov_norm = win * win / (win * win - 1.0) if use_sample_covariance and win > 1 else 1.0
+        out = torch.empty(B, 4, device=x.device, dtype=torch.float32)
+        check(_lib.lib().mi355_image_metrics(_req(x, "x"), _req(ref, "ref"), _req(out, "out"), B, Cc, H, W,
+                                             0.0 if data_range is None else float(data_range), taps, win, cov_norm, float(K1), float(K2), _stream()),
+              "mi355_image_metrics")
+        return {"mse": out[:, 0], "data_range": out[:, 1], "psnr": out[:, 2], "ssim": out[:, 3]}
+
+    def psnr(self, x, ref, data_range=None):
+        """10 log10(R^2 / mse) per sample (image_metrics' "psnr")."""
+        return self.image_metrics(x, ref, data_range=data_range)["psnr"]
+
+    def ssim(self, x, ref, **kwargs):
+        """Mean structural similarity per sample (image_metrics' "ssim"; the same keywords)."""
+        return self.image_metrics(x, ref, **kwargs)["ssim"]
+
     def lincomb_per_sample(self, x, a, y=None, b=None, out=None):
         """out[n] = a[n] * x[n] (+ b[n] * y[n]) with per-sample fp32 device coefficients a, b of shape [B] (sde_diffusion.py:214-244)."""
         B = x.shape[0]

@@ -47,7 +47,8 @@ extern "C" {
  * mi355_cfm_recon_workspace_bytes and mi355_cfm_recon_sample (training-free in-painting / super-resolution of a flow; new symbols only); then
  * mi355_conv2d_vjp (the conv data gradient of the U-Net backward as a test op; a new symbol only); then conv_ws became a bit mask (bit 1: the
  * warp-specialised conv carries a ResBlock's 1x1 skip conv, off in mi355_debug_defaults; bits 2 and 8.. for tests) and mi355_conv_extras gained the
- * stat_* fields at its end, read only behind MI355_CONV_EXTRAS_STATS in route[3] (a caller built against the shorter struct is unaffected).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * stat_* fields at its end, read only behind MI355_CONV_EXTRAS_STATS in route[3] (a caller built against the shorter struct is unaffected); then
+ * mi355_image_metrics (per-sample MSE, PSNR and SSIM of the evaluation loop; a new symbol only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -491,6 +492,21 @@ int mi355_ema_update(float* target, const float* source, float decay, float one_
 /* out[n] = mean over (C,H,W) of (a - b)^2: the per-sample MSE metric of the evaluation loop
  * (AD/experiments/main.py:299 `torch.mean((x0 - batch)**2, dim=(1, 2, 3))`) */
 int mi355_mse_per_sample(const float* a, const float* b, float* out, int batch, int64_t elems_per_sample, void* stream);
+/* Per-sample image quality of x against ref (both [B, C, H, W] fp32 NCHW, device).  out: float[B][4] = { mse, data_range, psnr, ssim }: the
+ * reference's calculate_psnr / calculate_ssim (AD/image_diffusion/trainer2.py:15-30, a per-image loop over skimage at trainer2.py:119-121) for a
+ * whole batch in one launch; restates skimage 0.19+ peak_signal_noise_ratio and structural_similarity(channel_axis=0) in fp64.
+ * data_range <= 0: each sample uses max(ref_n) - min(ref_n) over its whole [C, H, W] (what the reference passes to skimage);
+ * data_range > 0: that value for every sample.  taps: host float[win] - the 1-D window, applied separably (rows then columns);
+ * NULL = uniform 1 / win.  win odd, 3 <= win <= 15, win <= min(H, W).  cov_norm multiplies the three (co)variances
+ * (skimage: win*win / (win*win - 1) for the uniform window with use_sample_covariance, 1 with Gaussian weights).
+ *   mse  = mean((x - ref)^2), the same bits as mi355_mse_per_sample;   psnr = 10 log10(R^2 / mse) under IEEE rules (+inf for identical images);
+ *   ssim = mean over channels and over the (H - win + 1)(W - win + 1) window positions wholly inside the image of
+ *          ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),  C1 = (k1 R)^2, C2 = (k2 R)^2,  v = cov_norm (E[ab] - E[a] E[b]).
+ * All products, window sums and means are fp64, each output is rounded to fp32 once; no atomics: the result is bit-identical from run to run and
+ * ssim(x, x) is exactly 1.  One 256-thread workgroup per sample.  Every argument is checked before any device call (MI355_ERR_ARG names it):
+ * null x / ref / out, batch / channels / h / w < 1, h or w > 4096, win even or outside 3..15 or > min(h, w), k1 or k2 < 0, cov_norm <= 0. */
+int mi355_image_metrics(const float* x, const float* ref, float* out, int batch, int channels, int h, int w, float data_range,
+                        const float* taps_host, int win, float cov_norm, float k1, float k2, void* stream);
 /* out[n,:] = a[n]*x[n,:] + b[n]*y[n,:] with per-sample device coefficients a, b (y and b may both be NULL: out = a*x).
  * The arithmetic of DDPM.predict_start_from_noise / q_posterior / q_sample / score_from_x0
  * (AD/image_diffusion/sde_diffusion.py:214-244), whose coefficients are `extract`ed per sample (sde_diffusion.py:101-104). */
