@@ -18,87 +18,9 @@
 //     kernel row's weight tiles are loaded into registers while the current row's MFMAs run; weight
 //     tiles are double-buffered in LDS, so there is one barrier per kernel row (48 MFMAs per wave).
 // 4 waves per workgroup, v_mfma_f32_16x16x32_bf16 (or v_mfma_f32_16x16x4_f32 in the fp32 build).
-#include <algorithm>
-#include <cstdlib>
-#include <type_traits>
-#include <vector>
-
-#include "ops.h"
+#include "conv_kargs.h"
 
 namespace {
-
-constexpr int PROW = 96;   // bytes per patch pixel row in LDS (64 data + 32 pad)
-
-struct ConvKArgs {
-  const void* src0; const void* src1;
-  int C0, C1, Cin, nchunks;          // nchunks: 64-byte K chunks of the packed weights (2 x nreal with hi / lo split weights, else nreal)
-  int nreal;                         // 64-byte channel chunks of the activations: weight chunk c contracts with activation chunk c mod nreal
-  int N, Hs, Ws, Hc, Wc, Ho, Wo;
-  int mode, pad, stride;
-  const float* pro_a; const float* pro_b; int pro_silu;
-  const void* w; const float* bias; int Cout; int bn_pack;
-  const float* emb; int emb_stride;
-  const void* res; int res_mode; int Hr, Wr;
-  void* out; int out_mode;
-  float* gn_stats; int gn_slots;     // fused GroupNorm partial sums of the output (common.h GnPartial), or null
-  int lvw, lth, G, PW, PH, NP, tiles_x, tiles_y;
-  uint32_t bytes0, bytes1, wbytes, obytes, rbytes;   // buffer sizes (raw buffer descriptors: out-of-range loads return 0, stores drop)
-  unsigned long long* dbg;           // diagnostic build only (-DCONV_STAMPS): per-phase cycle sums
-  int ablate;                        // diagnostic build only: 1 = no output stores, 2 = no prologue math, 4 = no MFMA
-  int stagger;                       // odd-slot workgroup start delay in units of s_sleep(127) (~8k cycles each)
-  uint32_t* err;                     // error word (device-visible): bit 0 = a counter wait of the persistent kernel expired
-  int spin_limit;                    // polls before such a wait gives up
-  // small-level kernel only (conv_small.inc.h): the GroupNorm site that reads this conv's output is applied in the epilogue - a wave
-  // holds whole images x 64 channels = whole groups, so act_out = silu?(GN(out)) needs no pass of its own; out itself is written
-  // only if somebody else reads it (act_raw); one touch of the NEXT conv's packed weights (the pass's L2 warm-up moves here too)
-  void* act_out; const float* act_gamma; const float* act_beta; const float* act_film; int act_film_stride; float act_eps;
-  int act_silu, act_raw;
-  int act_stride, act_coff, act_cpg; uint32_t abytes;   // act_out: channels per pixel, first channel this conv fills, channels per group, bytes
-  void* act2_out; const float* act2_gamma; const float* act2_beta; int act2_silu, act2_stride, act2_coff, act2_cpg; uint32_t a2bytes;   // a second site (no FiLM)
-  const void* warm; uint32_t warm_bytes;
-  // small-level kernel only: a 1x1 conv of cat(sk0, sk1) (SC0 + SC1 channels at the output resolution) accumulated into the same output - the
-  // ResBlock's skip_connection inside its second conv; w then holds, per 128-channel pack tile, the 3x3 tiles followed by one tile per skip chunk
-  const void* sk0; const void* sk1; int SC0, SC1; uint32_t skbytes0, skbytes1;
-  uint32_t wstride;                  // 8-KB weight tiles per 128-channel pack tile (9 nchunks without a fused skip conv)
-};
-
-#ifdef CONV_STAMPS
-// In-kernel phase stamps (cdna_hip_programming.md section 7): diagnostic build only, never the timed build.
-__device__ __forceinline__ unsigned long long conv_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define STAMP_DECL unsigned long long st_prev = conv_stamp(), st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define STAMP(k) { const unsigned long long st_now = conv_stamp(); st_acc[k] += st_now - st_prev; st_prev = st_now; }
-#define STAMP_FLUSH if (p.dbg && (threadIdx.x & 63) == 0) { unsigned long long* q = p.dbg + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x / 64) + (threadIdx.x >> 6)) * 8; for (int k = 0; k < 8; ++k) q[k] = st_acc[k]; }
-// In-kernel clock of a wave (MI355X_MICROARCH.md, DVFS give-back item 6): shader-clock cycles per 100-MHz reference tick over the wave's
-// life time; two u64 per wave in the 64 KB in FRONT of the stamp buffer (the persistent conv's consumer waves only).
-#define CLK_DECL const unsigned long long ck_t0 = __builtin_amdgcn_s_memtime(), ck_r0 = __builtin_amdgcn_s_memrealtime();
-#define CLK_FLUSH if (p.dbg && (threadIdx.x & 63) == 0) { unsigned long long* q = p.dbg - 8192 + ((size_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6)) * 2; q[0] = __builtin_amdgcn_s_memtime() - ck_t0; q[1] = __builtin_amdgcn_s_memrealtime() - ck_r0; }
-#else
-#define STAMP_DECL
-#define STAMP(k)
-#define STAMP_FLUSH
-#define CLK_DECL
-#define CLK_FLUSH
-#endif
-
-template <int I> struct IC { static constexpr int value = I; };
-
-// activation chunk of weight chunk c (hi / lo split weights: the second half of the K loop runs over the same activations again)
-__device__ __forceinline__ int src_chunk(const ConvKArgs& p, int c) { return c >= p.nreal ? c - p.nreal : c; }
-
-template <bool FAST> __device__ __forceinline__ float silu_fast(float v) {
-  if (FAST) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
-  return v / (1.0f + expf(-v));
-}
-
-__device__ __forceinline__ u32x4 buf_load16(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
 
 // KS: 3 (3x3) or 1 (1x1: three channel chunks play the role of the three taps of a kernel row)
 // PIT: 16-B patch fragments per thread per plane (compile-time bound of the staging loops)
@@ -589,19 +511,6 @@ int launch_cfg(const ConvKArgs& a, int BM, int BN, int ks, int pit, dim3 grid, s
   return -4;
 }
 
-#include "conv_ws.inc.h"
-#ifndef PP_IMPL   // experiments: make variant VARFLAGS='-DPP_IMPL="\"../../tools/experiments/<file>\""' VARTAG=_x builds a library around another version of the kernel
-#define PP_IMPL "conv_pp.inc.h"
-#endif
-#include PP_IMPL
-#include "conv_pp1.inc.h"
-#include "conv_small.inc.h"
-
-struct Geo {
-  int Hc, Wc, Ho, Wo, BM, BN, bn_pack, lvw, lth, G, PW, PH, NP, tiles_x, tiles_y, groups, pad, stride, plane_bytes, pit, pit_t;
-  size_t lds;
-};
-
 int compute_geo(const ConvDesc& d, Geo& g) {
   g.pad = d.ks / 2;
   g.stride = d.mode == CONV_STRIDE2 ? 2 : 1;
@@ -694,142 +603,18 @@ int igemm_args(const ConvDesc& d, const Geo& g, ConvKArgs& a) {
 
 }  // namespace
 
-int conv_tile_n(int Cout) {
-  if (Cout % 128 == 0) return 128;
-  if (Cout % 64 == 0) return 64;
-  return 32;
-}
-
-static inline int chunk_of(int dtype) { return dtype == 0 ? 16 : 32; }
-
-size_t conv_packed_weight_bytes(int dtype, int Cout, int Cin, int ks, int split) {
-  const int BN = conv_tile_n(Cout), CH = chunk_of(dtype);
-  const size_t nt = (Cout + BN - 1) / BN, nc = (size_t)((Cin + CH - 1) / CH) * (split ? 2 : 1);
-  return nt * nc * ks * ks * (size_t)BN * 64;
-}
-
-static inline uint16_t f2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-static inline float bf2f(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
-
-// A packed weight image is a sequence of [BN rows][64 B] tiles, one per (output-channel tile, K chunk, tap): a row holds one chunk of CH input
-// channels as four 16-byte quads of V elements, quad q at slot q ^ ((row >> 1) & 3) (the swizzle the kernels' LDS reads undo, brow above).
-namespace {
-struct PackTile {
-  int dtype, BN, CH, V, esz;
-  PackTile(int dtype_, int Cout) : dtype(dtype_), BN(conv_tile_n(Cout)), CH(chunk_of(dtype_)), V(CH / 4), esz(dtype_ == 0 ? 4 : 2) {}
-  // element kl of the chunk, output channel `row` of the tile: v rounded to the image's element type
-  void store(char* tile, int row, int kl, float v) const {
-    const int q = kl / V, e = kl % V;
-    char* dstp = tile + row * 64 + 16 * (q ^ ((row >> 1) & 3)) + e * esz;
-    if (dtype == DT_F32) memcpy(dstp, &v, 4);
-    else if (dtype == DT_F16) { const _Float16 h = (_Float16)v; memcpy(dstp, &h, 2); }   // RNE
-    else { uint16_t h = f2bf(v); memcpy(dstp, &h, 2); }
-  }
-};
-}  // namespace
-
-void conv_pack_weights(int dtype, const float* w, int Cout, int Cin, int ks, void* dst, int split) {
-  const PackTile pk(dtype, Cout);
-  const int BN = pk.BN, CH = pk.CH;
-  const int nt = (Cout + BN - 1) / BN, nr = (Cin + CH - 1) / CH, nc = nr * (split && dtype == 1 ? 2 : 1), ntaps = ks * ks;
-  char* out = reinterpret_cast<char*>(dst);
-  memset(out, 0, conv_packed_weight_bytes(dtype, Cout, Cin, ks, split));
-  for (int t = 0; t < nt; ++t)
-    for (int c = 0; c < nc; ++c)
-      for (int tap = 0; tap < ntaps; ++tap) {
-        char* tile = out + (((size_t)t * nc + c) * ntaps + tap) * (size_t)BN * 64;
-        const bool lo = c >= nr;               // second half of the K loop: the rounding residual of the first half's weights
-        for (int row = 0; row < BN; ++row) {
-          const int co = t * BN + row;
-          if (co >= Cout) break;
-          for (int kl = 0; kl < CH; ++kl) {
-            const int ci = (lo ? c - nr : c) * CH + kl;
-            if (ci >= Cin) break;
-            float v = w[((size_t)co * Cin + ci) * ntaps + tap];
-            if (lo) v = v - bf2f(f2bf(v));
-            pk.store(tile, row, kl, v);
-          }
-        }
-      }
-}
-
-// Nearest-x2 up-sample followed by a 3x3 conv (padding 1) = four 2x2 convs of the low-res image, one per output phase (a, b) = (row, column parity):
-// output row 2 i + a reads high-res rows 2 i + a - 1 .. 2 i + a + 1 = low-res rows {i - 1, i, i} (a = 0) or {i, i, i + 1} (a = 1), so tap ky' of the
-// phase filter is the sum of the 3x3 rows ky with (a + ky + 1) / 2 == a + ky' (and the same along x).  Summed in fp32, then rounded and swizzled per
-// element exactly as conv_pack_weights does.  Layout per 128-row pack tile: [phase 2 a + b][chunk][tap 2 ky' + kx'][128 rows][64 B].
-size_t conv_packed_weight_bytes_up2(int dtype, int Cout, int Cin) {
-  const int BN = conv_tile_n(Cout), CH = chunk_of(dtype);
-  const size_t nt = (Cout + BN - 1) / BN, nc = (size_t)((Cin + CH - 1) / CH);
-  return nt * 4 * nc * 4 * (size_t)BN * 64;
-}
-void conv_pack_weights_up2(int dtype, const float* w, int Cout, int Cin, void* dst) {
-  const PackTile pk(dtype, Cout);
-  const int BN = pk.BN, CH = pk.CH;
-  const int nt = (Cout + BN - 1) / BN, nc = (Cin + CH - 1) / CH;
-  char* out = reinterpret_cast<char*>(dst);
-  memset(out, 0, conv_packed_weight_bytes_up2(dtype, Cout, Cin));
-  for (int t = 0; t < nt; ++t)
-    for (int ph = 0; ph < 4; ++ph)
-      for (int c = 0; c < nc; ++c)
-        for (int tap = 0; tap < 4; ++tap) {
-          const int pa = ph >> 1, pb = ph & 1, ty = tap >> 1, tx = tap & 1;
-          char* tile = out + ((((size_t)t * 4 + ph) * nc + c) * 4 + tap) * (size_t)BN * 64;
-          for (int row = 0; row < BN; ++row) {
-            const int co = t * BN + row;
-            if (co >= Cout) break;
-            for (int kl = 0; kl < CH; ++kl) {
-              const int ci = c * CH + kl;
-              if (ci >= Cin) break;
-              const float* w9 = w + ((size_t)co * Cin + ci) * 9;
-              float v = 0.f;
-              for (int ky = 0; ky < 3; ++ky)
-                for (int kx = 0; kx < 3; ++kx)
-                  if ((pa + ky + 1) / 2 == pa + ty && (pb + kx + 1) / 2 == pb + tx) v += w9[ky * 3 + kx];
-              pk.store(tile, row, kl, v);
-            }
-          }
-        }
-}
-
-size_t conv_packed_weight_bytes_skip(int dtype, int Cout, int Cin, int Cskip) {
-  return conv_packed_weight_bytes(dtype, Cout, Cin, 3, 0) + conv_packed_weight_bytes(dtype, Cout, Cskip, 1, 0);
-}
-void conv_pack_weights_skip(int dtype, const float* w3, const float* w1, int Cout, int Cin, int Cskip, void* dst) {
-  const size_t b3 = conv_packed_weight_bytes(dtype, Cout, Cin, 3, 0), b1 = conv_packed_weight_bytes(dtype, Cout, Cskip, 1, 0);
-  std::vector<char> t3(b3), t1(b1);
-  conv_pack_weights(dtype, w3, Cout, Cin, 3, t3.data(), 0);
-  conv_pack_weights(dtype, w1, Cout, Cskip, 1, t1.data(), 0);
-  const size_t nt = (Cout + conv_tile_n(Cout) - 1) / conv_tile_n(Cout), s3 = b3 / nt, s1 = b1 / nt;
-  char* out = reinterpret_cast<char*>(dst);
-  for (size_t t = 0; t < nt; ++t) {
-    memcpy(out + t * (s3 + s1), t3.data() + t * s3, s3);
-    memcpy(out + t * (s3 + s1) + s3, t1.data() + t * s1, s1);
-  }
-}
-
-// Weights of the data-gradient conv (backward w.r.t. the input) of a [Cout][Cin][ks][ks] forward filter: the transposed conv of a
-// stride-1, padding ks/2 convolution is the same convolution with input / output channels swapped and the taps flipped,
-// W'[ci][co][ky][kx] = W[co][ci][ks-1-ky][ks-1-kx]; rows ci >= Cin (channel padding of the forward input) are zero.
-size_t conv_packed_weight_bytes_dgrad(int dtype, int Cout, int Cin, int ks, int cin_pad) { (void)Cin; return conv_packed_weight_bytes(dtype, cin_pad, Cout, ks); }
-void conv_pack_weights_dgrad(int dtype, const float* w, int Cout, int Cin, int ks, int cin_pad, void* dst) {
-  const int nt = ks * ks;
-  std::vector<float> t((size_t)cin_pad * Cout * nt, 0.f);
-  for (int co = 0; co < Cout; ++co)
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int tap = 0; tap < nt; ++tap) t[((size_t)ci * Cout + co) * nt + (nt - 1 - tap)] = w[((size_t)co * Cin + ci) * nt + tap];
-  conv_pack_weights(dtype, t.data(), cin_pad, Cout, ks, dst);
+int ws_num_cus() {
+  static const int ncu = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) == hipSuccess) { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, dev) == hipSuccess) n = pr.multiProcessorCount; } return n; }();
+  return ncu;
 }
 
 ConvGeom conv_geometry(const ConvDesc& d) { ConvRoute r; conv_route(d, &r); return r.geom; }
 
 int conv_route(const ConvDesc& d, ConvRoute* r) {
   *r = ConvRoute{};
-  Geo g; compute_geo(d, g);
+  ConvPre pre{};
+  Geo& g = pre.g;
+  compute_geo(d, g);
   r->geom = ConvGeom{g.Ho, g.Wo, g.BM, g.BN, g.lds, g.groups * g.tiles_x * g.tiles_y, (d.Cout + g.BN - 1) / g.BN};
   const bool fskip = d.skip_src0 != nullptr;   // the small-level kernel and the warp-specialised kernel's prologue forms carry a fused skip conv
   if (!fskip && !d.wsplit) {   // (hi / lo split weights: the implicit-GEMM kernels)
@@ -839,7 +624,7 @@ int conv_route(const ConvDesc& d, ConvRoute* r) {
     if (rc == 1) rc = conv_in_route(d, r);
     if (rc <= 0) return rc;
   }
-  const int CH = chunk_of(d.dtype);
+  const int CH = d.dtype == 0 ? 16 : 32;
   const int Cin = d.C0 + d.C1;
   MI355_REQUIRE(d.ks == 1 || d.ks == 3, -1, "conv: kernel size must be 1 or 3");
   MI355_REQUIRE(d.C0 % CH == 0 && d.C1 % CH == 0 && Cin > 0, -2, "conv: source channels must be multiples of the 64-byte chunk");
@@ -849,62 +634,24 @@ int conv_route(const ConvDesc& d, ConvRoute* r) {
   MI355_REQUIRE(g.lds <= 160 * 1024, -4, "conv: LDS budget exceeded");
   MI355_REQUIRE(g.pit <= g.pit_t, -4, "conv: input patch too large for the staging loops");
   MI355_REQUIRE(!d.wsplit || d.dtype == DT_BF16, -1, "conv: hi / lo split weights are a bf16 mode");
-  ConvKArgs a{};
-  if (int rc = igemm_args(d, g, a)) return rc;
-  const mi355_debug_config& K = d.knobs ? *d.knobs : mi355_default_debug();
-  const bool gn_ok = d.gn_stats && d.out_mode == OUT_NHWC && g.G == 1 && d.Cout % g.BN == 0 && d.Cout % 4 == 0;
-  const bool has_pro = d.pro_a != nullptr;
-  // ping-pong kernel (conv_pp.inc.h): 256- or 128-channel output tiles, input as it is or through the in-LDS GroupNorm + SiLU prologue
-  // (phase form of an up-sampling conv: needs the collapsed weight image, carries no residual / split weights / fused output norm)
-  const bool up_ok = d.mode == CONV_UP2 && d.w_up2 && !d.wsplit && a.res_mode == RES_NONE;
-  // (a description with a fused skip conv never runs on the ping-pong kernel; where that kernel would take the conv alone, the two-launch form stays)
-  const int pc_alone = pp_config(K.conv_pp, d.ks, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, has_pro, d.pro_silu != 0, d.N, g.Ho, g.Wo, d.Cout, up_ok);
-  const int pc = fskip ? -1 : pc_alone;
-  if (pc == 2) {
-    r->kernel = CONV_K_PP; r->form = 2; r->w_up2 = 1;
-    r->geom.BM = 256; r->geom.BN = 256; r->geom.lds_bytes = pp::D<0>::lds_bytes(false);
-    const int slots = 4 * 2 * ((d.Ws + 15) / 16) * ((d.Hs + 15) / 16);   // (phase, low-res pixel tile, pixel wave) per image
-    if (gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
-    return 0;
-  }
-  if (pc >= 0) {
-    r->kernel = CONV_K_PP; r->form = pc;
-    r->geom.BM = pc == 0 ? 256 : 512; r->geom.BN = pc == 0 ? 256 : 128;
-    r->geom.lds_bytes = pc == 0 ? pp::D<0>::lds_bytes(has_pro) : pp::D<1>::lds_bytes(has_pro);
-    // the output GroupNorm in place (the activated tensor replaces the raw one): one 16 x 16 tile per image, no residual, 8 or 16 channels per group
-    const bool act = pc == 0 && g.Ho == 16 && g.Wo == 16 && (d.Cout == 256 || d.Cout == 512) && a.res_mode == RES_NONE;
-    if (act && d.act_out && (K.gn_epilogue & 2) && d.act_out == d.out && !d.act_raw) r->act_done = 1;
-    const int slots = pc == 0 ? 2 * ((g.Wo + 15) / 16) * ((g.Ho + 15) / 16) : 4 * ((g.Wo + 31) / 32) * ((g.Ho + 15) / 16);   // (pixel tile, pixel wave) per image
-    if (!r->act_done && gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
-    return 0;
-  }
-  // dominant shapes: warp-specialised persistent kernel (conv_ws.inc.h)
-  if (ws_eligible(K.conv_ws, d.ks, g.BM, g.BN, g.G, g.bn_pack, d.out_mode, g.stride, a.nchunks, d.N, g.Ho, g.Wo, d.Cout) &&
-      (!fskip || (pc_alone < 0 && ws_skip_eligible(K.conv_ws, a, d.mode, d.act_out != nullptr, d.wsplit != 0, CH)))) {
-    r->kernel = CONV_K_WS; r->skip = fskip ? 1 : 0;
-    r->geom.BM = 256; r->geom.lds_bytes = ws::LDS_BYTES;   // 16 x 16 pixel tiles
-    const int slots = 2 * ((g.Wo + ws::VW - 1) / ws::VW) * ((g.Ho + ws::TH - 1) / ws::TH);   // (16x16 pixel tile, 8-row half) per image
-    if (gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
-    return 0;
-  }
-  // 8x8 / 4x4 levels: barrier-free K loop over an LDS-resident patch, weights straight into registers (conv_small.inc.h)
-  const bool act = d.act_out && (K.gn_epilogue & 1) && d.act_out != d.out, act2 = act && d.act2_out && (K.gn_epilogue & 4);
-  const size_t esz = d.dtype == 0 ? 4 : 2;
-  MI355_REQUIRE(!act || (size_t)d.N * g.Ho * g.Wo * (d.act_stride ? d.act_stride : d.Cout) * esz < 0xFFFF0000ull, -4,
-                "conv: activated output exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-  MI355_REQUIRE(!act2 || (size_t)d.N * g.Ho * g.Wo * (d.act2_stride ? d.act2_stride : d.Cout) * esz < 0xFFFF0000ull, -4,
-                "conv: activated output exceeds 4 GiB (32-bit buffer offsets): run the batch in slices");
-  if (small_route(a, K.conv_small, d.ks, d.dtype, r) == 0) {
-    // GroupNorm of the output in the epilogue: whole images per wave (an 8x8 image split over K-sharing waves is not), 4 / 8 / 16 channels per group
-    auto cpg_ok = [&](int cpg, int coff) { return (cpg == 4 || cpg == 8 || cpg == 16) && d.Cout % cpg == 0 && coff % cpg == 0; };
-    const bool ok = act && cpg_ok(d.act_cpg ? d.act_cpg : d.Cout / 32, d.act_coff) && (g.Ho != 8 || r->ksplit == 1);
-    const bool ok2 = ok && act2 && cpg_ok(d.act2_cpg ? d.act2_cpg : d.Cout / 32, d.act2_coff);
-    r->act_done = (ok ? 1 : 0) | (ok2 ? 2 : 0);
-    return 0;
-  }
+  if (int rc = igemm_args(d, g, pre.a)) return rc;
+  pre.K = d.knobs ? d.knobs : &mi355_default_debug();
+  pre.gn_ok = d.gn_stats && d.out_mode == OUT_NHWC && g.G == 1 && d.Cout % g.BN == 0 && d.Cout % 4 == 0;
+  pre.has_pro = d.pro_a != nullptr;
+  pre.fskip = fskip;
+  // ping-pong, warp-specialised, small-level (conv_pp.hip, conv_ws.hip, conv_small.hip), else the plain kernel.  A description with a fused skip conv never
+  // runs on the ping-pong kernel, and where that kernel would take the conv alone the two-launch form stays: the warp-specialised kernel is not asked
+  ConvRoute alone = *r;
+  int rc = pp_route(d, pre, &alone);
+  if (rc < 0) return rc;
+  const bool pp_alone = rc == 0;
+  if (pp_alone && !fskip) { *r = alone; return 0; }
+  rc = pp_alone ? 1 : ws_route(d, pre, r);
+  if (rc == 1) rc = small_route(d, pre, r);
+  if (rc <= 0) return rc;
   MI355_REQUIRE(!fskip, -5, "conv: no kernel carries the fused skip conv of this description (shape, batch or knobs)");
   const int slots = g.tiles_x * g.tiles_y * (g.BN == 32 ? 4 : 2);   // (pixel tile, pixel-wave) per image
-  if (gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
+  if (pre.gn_ok && slots <= d.gn_slots_cap) r->gn_slots = slots;
   return 0;
 }
 
@@ -918,36 +665,22 @@ int conv_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream) {
     case CONV_K_IN: return conv_in_launch(d, r, stream);
     default: break;
   }
-  Geo g; compute_geo(d, g);
-  ConvKArgs a{};
+  ConvPre pre{};
+  Geo& g = pre.g;
+  ConvKArgs& a = pre.a;
+  compute_geo(d, g);
   if (int rc = igemm_args(d, g, a)) return rc;
+  pre.K = d.knobs ? d.knobs : &mi355_default_debug();
   if (r.gn_slots) { a.gn_stats = d.gn_stats; a.gn_slots = r.gn_slots; }
-  if (r.w_up2) {
-    MI355_REQUIRE(d.w_up2, -1, "conv: the route asks for the collapsed up-sampling weights (conv_pack_weights_up2) and the description has none");
-    a.w = d.w_up2; a.wbytes = (uint32_t)conv_packed_weight_bytes_up2(d.dtype, d.Cout, d.C0 + d.C1);
-  }
-  const size_t esz = d.dtype == 0 ? 4 : 2;
   if (r.act_done & 1) {
     a.act_out = d.act_out; a.act_gamma = d.act_gamma; a.act_beta = d.act_beta; a.act_film = d.act_film; a.act_film_stride = d.act_film_stride;
     a.act_eps = d.act_eps; a.act_silu = d.act_silu; a.act_raw = d.act_raw;
   }
   int rc;
-  if (r.kernel == CONV_K_PP) rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_pp<decltype(t)>(a, r.form, stream); });
-  else if (r.kernel == CONV_K_WS) rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_ws<decltype(t)>(a, (d.knobs ? d.knobs : &mi355_default_debug())->conv_ws >> 8, stream); });
-  else if (r.kernel == CONV_K_SMALL) {
-    if (r.act_done & 1) {
-      a.act_stride = d.act_stride ? d.act_stride : d.Cout; a.act_coff = d.act_coff; a.act_cpg = d.act_cpg ? d.act_cpg : d.Cout / 32;
-      a.abytes = (uint32_t)((size_t)d.N * g.Ho * g.Wo * a.act_stride * esz);
-      const mi355_debug_config& K = d.knobs ? *d.knobs : mi355_default_debug();
-      a.warm = (K.l2_warm & 1) ? d.warm : nullptr; a.warm_bytes = a.warm ? d.warm_bytes : 0u;
-    }
-    if (r.act_done & 2) {
-      a.act2_out = d.act2_out; a.act2_gamma = d.act2_gamma; a.act2_beta = d.act2_beta; a.act2_silu = d.act2_silu;
-      a.act2_stride = d.act2_stride ? d.act2_stride : d.Cout; a.act2_coff = d.act2_coff; a.act2_cpg = d.act2_cpg ? d.act2_cpg : d.Cout / 32;
-      a.a2bytes = (uint32_t)((size_t)d.N * g.Ho * g.Wo * a.act2_stride * esz);
-    }
-    rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_small<decltype(t)>(a, r, stream); });
-  } else {
+  if (r.kernel == CONV_K_PP) rc = pp_launch(d, pre, r, stream);
+  else if (r.kernel == CONV_K_WS) rc = ws_launch(d, pre, r, stream);
+  else if (r.kernel == CONV_K_SMALL) rc = small_launch(d, pre, r, stream);
+  else {
     const dim3 grid(g.groups * g.tiles_x * g.tiles_y, (d.Cout + g.BN - 1) / g.BN);
     rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_cfg<decltype(t)>(a, g.BM, g.BN, d.ks, g.pit_t, grid, g.lds, stream); });
   }

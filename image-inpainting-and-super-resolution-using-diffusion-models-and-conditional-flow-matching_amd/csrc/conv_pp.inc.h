@@ -744,38 +744,6 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
 #endif
 }
 
-// Shapes the ping-pong kernel takes: 3x3 / stride 1 / NHWC output, input either as it is or through the GroupNorm affine + SiLU prologue
-// (PRO = 2; an affine-only prologue stays on the other kernels), an even number of 64-byte channel chunks per source switch (two chunks
-// are unrolled; a source boundary may fall anywhere), images of at least one tile.  Geometry: Cout % 256 == 0 -> wide (16 x 16 x 256);
-// otherwise Cout % 128 == 0 and Wo >= 32 -> narrow (16 x 32 x 128).  mode = mi355_debug_config::conv_pp: bits 0-1: 1 = only when every CU
-// gets a tile, 2 = always (tests); bit 2: the prologue form of the wide geometry; bit 3: the narrow geometry; bit 4: the prologue form of the
-// narrow geometry too (off by default: same-box it ties the warp-specialised kernel at 256 / 384 input channels and loses 3-5 % at 128,
-// profiles/r5_experiments.md - the prologue's arithmetic is amortised over 128 output channels instead of 256).
-// Bit 6 (64): the phase form of a prologue-free conv over a nearest-x2 up-sampled input (four 2x2 convs of the low-res image, UP = 1 above: 4/9 of
-// the MFMAs): wide geometry only, the geometry rule and the tile count apply to the LOW-RES image (16 x 16 low-res pixels per tile, four phase
-// tiles each); up_ok: the caller has the collapsed weight image and nothing the form does not carry (residual, split weights, fused output norm).
-// Returns the geometry (0 wide, 1 narrow, 2 wide in phase form) or -1.
-static int pp_config(int mode, int ks, int G, int bn_pack, int out_mode, int stride, int nchunks, bool has_pro, bool pro_silu, int N, int Ho, int Wo, int Cout,
-                     bool up_ok = false) {
-  if (!(mode & 3) || ks != 3 || G != 1 || bn_pack != 128 || out_mode != OUT_NHWC || stride != 1) return -1;
-  if (has_pro && !pro_silu) return -1;
-  if (nchunks < 2 || (nchunks & 1)) return -1;
-  if (up_ok && (mode & 64) && !has_pro && Cout % 256 == 0 && !(Ho & 1) && !(Wo & 1) && Ho >= 32 && Wo >= 32) {
-    const int Hs = Ho / 2, Ws = Wo / 2;
-    const int n_mt = 4 * N * ((Ws + 15) / 16) * ((Hs + 15) / 16), n_nt = Cout / 256;
-    if ((mode & 3) >= 2 || n_mt * n_nt >= ws_num_cus()) return 2;
-  }
-  int cfg = -1;
-  if (Cout % 256 == 0 && Wo >= 16 && Ho >= 16) cfg = 0;
-  else if (Cout % 128 == 0 && (mode & 8) && Wo >= 32 && Ho >= 16) cfg = 1;
-  if (cfg < 0) return -1;
-  if (has_pro && !(mode & (cfg == 0 ? 4 : 16))) return -1;
-  if ((mode & 3) >= 2) return cfg;
-  const int vw = cfg == 0 ? 16 : 32, bn = cfg == 0 ? 256 : 128;
-  const int n_mt = N * ((Wo + vw - 1) / vw) * ((Ho + 15) / 16), n_nt = Cout / bn;
-  return n_mt * n_nt >= ws_num_cus() ? cfg : -1;
-}
-
 template <typename T, int CFG, int PRO, int ACT = 0, int UP = 0>
 int launch_pp_k(ConvKArgs a, hipStream_t s) {
   using Dg = pp::D<CFG>;
@@ -790,10 +758,10 @@ int launch_pp_k(ConvKArgs a, hipStream_t s) {
   return 0;
 }
 
-// cfg: pp_config's geometry; a.act_out set: the form that applies the output GroupNorm in place (wide, conv_route decides)
+// cfg: pp_route's geometry (conv_pp.hip); a.act_out set: the form that applies the output GroupNorm in place (wide, pp_route decides)
 template <typename T>
 int launch_pp(const ConvKArgs& a, int cfg, hipStream_t s) {
-  if (cfg == 2) return launch_pp_k<T, 0, 0, 0, 1>(a, s);   // phase form: a.w is the collapsed image (conv_launch)
+  if (cfg == 2) return launch_pp_k<T, 0, 0, 0, 1>(a, s);   // phase form: a.w is the collapsed image (pp_launch)
   if (a.act_out) return a.pro_a ? launch_pp_k<T, 0, 2, 1>(a, s) : launch_pp_k<T, 0, 0, 1>(a, s);
   if (a.pro_a) return cfg == 0 ? launch_pp_k<T, 0, 2>(a, s) : launch_pp_k<T, 1, 2>(a, s);
   return cfg == 0 ? launch_pp_k<T, 0, 0>(a, s) : launch_pp_k<T, 1, 0>(a, s);

@@ -558,60 +558,6 @@ __global__ void __launch_bounds__(NI == 4 ? 256 : 512, NI == 4 ? 1 : 2) conv3x3_
   }
 }
 
-// Shapes this kernel takes: 3x3, whole 8x8 / 4x4 OUTPUT images, stride 1 (plain or nearest-x2 input) or - round 5 - stride 2 (the Downsample convs
-// 16 -> 8 and 8 -> 4, AD/image_diffusion/unet.py:217-240: the staged patch is the (2 Ho + 1)^2 input window, the fragment addresses step two
-// pixels per output pixel: 2-way bank conflicts on reads that are a tenth of this kernel's LDS budget), no GroupNorm prologue (these
-// levels normalise in a pass of their own), NHWC output with C_out % 128 == 0, residual at the output resolution or none.
-// 0 = taken (r: ksplit, waves, w8x2, sm::Args, LDS, fused skip conv), 1 = not this kernel (the plain kernel).  a: the plain kernel's arguments.
-static int small_route(const ConvKArgs& a, int enabled, int ks, int dtype, ConvRoute* r) {
-  if (!enabled || ks != 3 || a.out_mode != OUT_NHWC || a.pro_a) return 1;
-  const bool s2 = a.stride == 2;
-  const bool skip = a.sk0 != nullptr;
-  if (skip && (!(enabled & 8) || s2 || a.mode != CONV_UNIT || a.res_mode != RES_NONE || a.src1 || a.nchunks != a.nreal)) return 1;
-  if (s2 && (!(enabled & 4) || a.mode != CONV_STRIDE2 || a.Hc != 2 * a.Ho || a.Wc != 2 * a.Wo)) return 1;
-  if (a.Ho != a.Wo || (a.Ho != 8 && a.Ho != 4) || a.Cout % 128 != 0) return 1;
-  if (a.res_mode != RES_NONE && a.res_mode != RES_SAME) return 1;
-  const int CH = dtype == 0 ? 16 : 32;
-  if (a.C0 % CH || a.C1 % CH) return 1;
-  const bool w8 = a.Ho == 8;
-  sm::Args g;
-  const int G = w8 ? 1 : 4, PW = s2 ? 2 * a.Ho + 1 : a.Ho + 2;
-  g.pwp = s2 ? PW : (w8 ? 16 : 8); g.sh = w8 ? 1 : 2;
-  g.pimg = PW * g.pwp;
-  g.plane = (G * g.pimg - (g.pwp - PW)) * 64;
-  const int nchp = s2 ? (w8 ? 8 : 4) : (w8 ? 16 : 8);
-  g.nphase = (a.nchunks + nchp - 1) / nchp;
-  g.chp = a.nchunks / g.nphase;
-  if (g.chp * g.nphase != a.nchunks) return 1;
-  const int tiles = (a.N + G - 1) / G;
-  // waves along N: as many as keep every CU busy (each halving doubles the workgroups and splits K between wave pairs)
-  const int ncu = ws_num_cus();
-  int nw = 4;
-  while (nw > 1 && (long)tiles * (a.Cout / (64 * nw)) < ncu) nw >>= 1;
-  if (a.Cout % (64 * nw)) return 1;
-  const int ksplit = 4 / nw;
-  if (g.chp % ksplit) return 1;
-  g.red_bytes = ksplit > 1 ? 4 * 16 * 1024 : 0;
-  g.sphase = g.schp = g.sup = 0;
-  if (skip) {
-    if (a.SC0 % CH || a.SC1 % CH) return 1;
-    const int ns = (a.SC0 + a.SC1) / CH;
-    g.sup = g.nphase == 1 && ns <= sm::SDMAX && ns % ksplit == 0 && (size_t)g.chp * g.plane + (size_t)ns * sm::SPLANE <= 160 * 1024;
-    g.sphase = g.sup ? 1 : (ns + nchp - 1) / nchp;
-    g.schp = ns / g.sphase;
-    if (g.schp * g.sphase != ns || g.schp % ksplit) return 1;
-  }
-  const size_t lds = g.sup ? std::max((size_t)g.chp * g.plane + (size_t)g.schp * sm::SPLANE, (size_t)g.red_bytes)
-                           : std::max((size_t)std::max(g.chp, g.schp) * g.plane, (size_t)g.red_bytes);
-  if (lds > 160 * 1024) return 1;
-  r->kernel = CONV_K_SMALL; r->ksplit = ksplit; r->n_mt = tiles; r->n_nt = a.Cout / (64 * nw); r->lds = lds; r->skip = skip;
-  // whole-chip launches of the 8x8 level (one image per workgroup, no K split): eight waves of 32 channels (knob conv_small bit 1)
-  r->form = w8 && !s2 && !skip && ksplit == 1 && (enabled & 2) && a.Cout % 256 == 0;
-  static_assert(sizeof(r->sm) == sizeof(sm::Args), "ConvRoute::sm holds sm::Args");
-  memcpy(r->sm, &g, sizeof g);
-  return 0;
-}
-
 // a.act_out / a.act2_out: the GroupNorm sites the route applies (ConvRoute::act_done), or null
 template <typename T>
 int launch_small(const ConvKArgs& a0, const ConvRoute& r, hipStream_t s) {

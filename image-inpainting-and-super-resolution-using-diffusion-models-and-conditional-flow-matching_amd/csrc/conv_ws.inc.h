@@ -1038,29 +1038,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
   }
 }
 
-// Shapes the warp-specialised kernel takes (everything else stays on the plain kernel): the plain tile choice already was the
-// largest one (>= 512 workgroups of 128 x 128), 3x3 / stride 1 / NHWC output, an even number of 64-byte channel chunks
-// (row pairs and chunk pairs are unrolled), images of at least one 16 x 16 tile, and at least one tile per CU.
-static int ws_num_cus() {
-  static const int ncu = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) == hipSuccess) { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, dev) == hipSuccess) n = pr.multiProcessorCount; } return n; }();
-  return ncu;
-}
-static bool ws_eligible(int enabled, int ks, int BM, int BN, int G, int bn_pack, int out_mode, int stride, int nchunks, int N, int Ho, int Wo, int Cout) {
-  if (!(enabled & 1) || ks != 3 || BM != 128 || BN != 128 || G != 1 || bn_pack != 128 || out_mode != OUT_NHWC) return false;
-  if (stride != 1 || nchunks < 2 || (nchunks & 1)) return false;
-  if (Wo < ws::VW || Ho < ws::TH) return false;
-  const int n_mt = N * ((Wo + ws::VW - 1) / ws::VW) * ((Ho + ws::TH - 1) / ws::TH), n_nt = (Cout + 127) / 128;
-  return (enabled & 4) || n_mt * n_nt >= ws_num_cus();   // fewer tiles than CUs: the plain kernel's smaller tiles fill the chip better (knob bit 2, tests: take them too)
-}
-// ... and may carry the ResBlock's 1x1 skip conv (knob bit 1): a GroupNorm prologue form without split weights, plain geometry, no residual of its
-// own, whole 64-byte skip chunks
-static bool ws_skip_eligible(int enabled, const ConvKArgs& a, int mode, bool fused_act, bool wsplit, int CH) {
-  if (!(enabled & 2) || !a.sk0 || !a.pro_a || wsplit || mode != CONV_UNIT || fused_act || a.res_mode != RES_NONE) return false;
-  if (a.SC0 <= 0 || a.SC0 % CH || a.SC1 % CH) return false;
-  return true;
-}
-
-// a shape ws_eligible accepts
+// a shape ws_route (conv_ws.hip) accepts
 template <typename T>
 int launch_ws(ConvKArgs a, int grid_cap, hipStream_t s) {
   a.lvw = 4; a.lth = 4; a.PW = ws::PW; a.PH = ws::PH; a.NP = ws::NPX;
@@ -1070,7 +1048,7 @@ int launch_ws(ConvKArgs a, int grid_cap, hipStream_t s) {
   using KernT = void (*)(ConvKArgs, int, int);
   KernT kern = !a.pro_a ? (KernT)conv3x3_ws_kernel<T, 0> : (a.pro_silu ? (KernT)conv3x3_ws_kernel<T, 2> : (KernT)conv3x3_ws_kernel<T, 1>);
   int rc;
-  if (a.sk0) {   // the carried skip conv (conv_route: a prologue form)
+  if (a.sk0) {   // the carried skip conv (ws_route: a prologue form)
     kern = a.pro_silu ? (KernT)conv3x3_ws_kernel<T, 2, true> : (KernT)conv3x3_ws_kernel<T, 1, true>;
     rc = a.pro_silu ? mi355_allow_big_lds(conv3x3_ws_kernel<T, 2, true>, "conv3x3 (persistent)") : mi355_allow_big_lds(conv3x3_ws_kernel<T, 1, true>, "conv3x3 (persistent)");
   } else

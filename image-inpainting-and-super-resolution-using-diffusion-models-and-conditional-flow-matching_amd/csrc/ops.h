@@ -119,14 +119,27 @@ void conv_pack_weights_up2(int dtype, const float* w_host, int Cout, int Cin, vo
 // [3x3 filter w3 [Cout][Cin][3][3] | 1x1 filter w1 [Cout][Cskip]] per 128-channel pack tile: the 3x3 tiles, then one tile per skip chunk
 size_t conv_packed_weight_bytes_skip(int dtype, int Cout, int Cin, int Cskip);
 void conv_pack_weights_skip(int dtype, const float* w3, const float* w1, int Cout, int Cin, int Cskip, void* dst_host);
-// Families outside conv_igemm.hip (*_route: 0 = taken, 1 = not this family, < 0 = error; *_launch launches that route): conv1x1.hip's 1x1 GEMM
-// with a stationary activation tile; conv_edge.hip's first conv and last conv (GN + SiLU prologue, <= 4 output channels, NCHW fp32)
+// The kernel families conv_route asks in turn, one unit each.  X_route: pure host code; 0 = taken (*r filled: kernel, form, geom.BM / BN / lds_bytes, gn_slots,
+// act_done, skip, w_up2 and the family's own fields), 1 = not this family (*r untouched), < 0 = error (message set).  X_launch launches such a route: 0 or
+// < 0.  conv_pp1.hip: ping-pong 1x1; conv1x1.hip: 1x1 GEMM with a stationary activation tile; conv_edge.hip: the first conv and the last conv (GN + SiLU
+// prologue, <= 4 output channels, NCHW fp32).
+int pp1_route(const ConvDesc& d, ConvRoute* r);
+int pp1_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream);
 int conv1x1_route(const ConvDesc& d, ConvRoute* r);
 int conv1x1_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream);
 int conv_in_route(const ConvDesc& d, ConvRoute* r);
 int conv_in_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream);
 int conv_out_route(const ConvDesc& d, ConvRoute* r);
 int conv_out_launch(const ConvDesc& d, const ConvRoute& r, hipStream_t stream);
+// conv_pp.hip (ping-pong 3x3), conv_ws.hip (warp-specialised 3x3), conv_small.hip (8x8 / 4x4 levels): asked behind conv_route's argument checks, with what
+// it has worked out by then (ConvPre, conv_kargs.h: the plain tiling and the plain kernel's arguments, which their launches start from)
+struct ConvPre;
+int pp_route(const ConvDesc& d, const ConvPre& p, ConvRoute* r);
+int pp_launch(const ConvDesc& d, const ConvPre& p, const ConvRoute& r, hipStream_t stream);
+int ws_route(const ConvDesc& d, const ConvPre& p, ConvRoute* r);
+int ws_launch(const ConvDesc& d, const ConvPre& p, const ConvRoute& r, hipStream_t stream);
+int small_route(const ConvDesc& d, const ConvPre& p, ConvRoute* r);
+int small_launch(const ConvDesc& d, const ConvPre& p, const ConvRoute& r, hipStream_t stream);
 
 // ---- GroupNorm statistics -> per-(n, channel) affine ----------------------------------------------
 // a[n,c] = rstd * gamma[c] (* (1 + film_scale)), b[n,c] = beta[c] - mean * rstd * gamma[c] (FiLM folded)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Itemise a kernel's ISA by loop and instruction class (VERDICT r3 task 7: where does the VALU of a kernel with DMA-only loaders sit?).
 
-    hipcc ... --cuda-device-only -S csrc/conv_igemm.hip -o k.s ; python tools/isa_itemise.py k.s <mangled-name-substring> [out.json]
+    hipcc ... --cuda-device-only -S csrc/conv_ws.hip -o k.s ; python tools/isa_itemise.py k.s <mangled-name-substring> [out.json]
 
 A loop = a label that a later branch jumps back to; every instruction is attributed to the INNERMOST loop that contains it (or to
 "straight-line" code).  Classes: mfma, valu (v_* except mfma / readlane-type moves are counted too), salu, lds (ds_*), vmem (buffer_ /
