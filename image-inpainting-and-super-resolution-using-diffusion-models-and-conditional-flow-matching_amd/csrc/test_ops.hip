@@ -1,5 +1,5 @@
 // Single-op test harness of libmi355_sampler.so (see include/mi355_sampler.h): the kernels the network launches, one op per call, NCHW fp32 at
-// the boundary (mi355_conv2d / mi355_conv2d_ex, the attention ops, the GroupNorm test ops, mi355_affine_pool, mi355_grad_gather, mi355_conv2d_vjp).
+// the boundary (mi355_conv2d / mi355_conv2d_ex, the attention ops, the GroupNorm test ops, mi355_affine_pool, mi355_grad_gather, mi355_conv2d_vjp, mi355_conv2d_fwd).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -646,6 +646,108 @@ int mi355_conv2d_vjp(const float* w_host, const float* grad_out, float* g0, floa
   uint32_t ev = 0;
   MI355_CHECK_HIP(hipMemcpy(&ev, errw, 4, hipMemcpyDeviceToHost));
   if (ev) { mi355_set_error("conv2d_vjp: the persistent kernel gave up a bounded counter wait (hand-over stalled): the output is invalid"); return MI355_ERR_TIMEOUT; }
+  return 0;
+}
+
+// ---- one forward conv, isolated (later addition to ABI 108): mi355_conv2d_ex with the prologue's (a, b) given, the route always reported, the two
+// sampler-only edge forms, and nothing initialised that no kernel writes ----
+int mi355_conv2d_fwd(const float* x, const float* x1, int cin1, const float* w_host, const float* bias_host, float* y, int batch, int cin, int h,
+                     int w, int cout, int ksize, int stride, int resample, const float* pro_a, const float* pro_b, int pro_silu, const float* emb,
+                     const float* res, int res_mode, int flags, float* axpy_x, float axpy_scale, int dtype, const mi355_debug_config* debug,
+                     int32_t route[8], void* workspace, int64_t workspace_bytes, void* stream) {
+  if (route) for (int i = 0; i < 8; ++i) route[i] = -1;
+  const mi355_debug_config& K = debug ? *debug : mi355_default_debug();
+  const bool dry = workspace == nullptr && workspace_bytes == 0 && route != nullptr;   // route query: host code only, no pointer is read
+  MI355_REQUIRE(dry || (x && w_host && y && workspace), -1, "conv2d_fwd: null argument");
+  MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_BF16 || dtype == MI355_BF16X2 || dtype == MI355_F16, -1, "conv2d_fwd: bad dtype");
+  MI355_REQUIRE(batch > 0 && cin > 0 && cin1 >= 0 && cout > 0 && h > 0 && w > 0, -1, "conv2d_fwd: bad sizes");
+  MI355_REQUIRE(ksize == 1 || ksize == 3, -1, "conv2d_fwd: kernel size must be 1 or 3");
+  MI355_REQUIRE(stride == 1 || stride == 2, -1, "conv2d_fwd: stride must be 1 or 2");
+  MI355_REQUIRE(resample == 0 || resample == 2, -1, "conv2d_fwd: resample must be 0 or 2 (nearest x2; pooling is a pass of its own, mi355_affine_pool)");
+  MI355_REQUIRE(!(stride == 2 && resample), -1, "conv2d_fwd: stride 2 cannot be combined with resampling");
+  MI355_REQUIRE((stride == 1 && !resample) || ksize == 3, -1, "conv2d_fwd: stride 2 and nearest x2 need a 3x3 kernel");
+  MI355_REQUIRE((flags & ~MI355_CONV_FWD_NCHW_SRC) == 0, -1, "conv2d_fwd: unknown flag");
+  MI355_REQUIRE(dry ? !x1 || cin1 > 0 : (x1 != nullptr) == (cin1 > 0), -1, "conv2d_fwd: x1 and cin1 go together");
+  MI355_REQUIRE((pro_a != nullptr) == (pro_b != nullptr), -1, "conv2d_fwd: pro_a and pro_b go together");
+  MI355_REQUIRE(res == nullptr || res_mode == RES_SAME || res_mode == RES_UP2, -1, "conv2d_fwd: res_mode must be 1 (same size) or 2 (nearest x2)");
+  const int wsplit = dtype == MI355_BF16X2 ? 1 : 0;
+  dtype = dtype == MI355_F16 ? DT_F16 : (wsplit ? DT_BF16 : dtype);   // the internal element-type code from here on (ops.h)
+  const int CH = dtype == 0 ? 16 : 32, esz = dtype == 0 ? 4 : 2;
+  const bool nchw_src = (flags & MI355_CONV_FWD_NCHW_SRC) != 0;   // x | x1 are the caller's NCHW tensors of the network's first conv: one packed source
+  const bool two = cin1 > 0 && !nchw_src;
+  MI355_REQUIRE(!two || (cin % CH == 0 && cin1 % CH == 0), -2, "conv2d_fwd: a two-source conv needs both channel counts to be multiples of the 64-byte chunk");
+  MI355_REQUIRE(!nchw_src || (cin + cin1 <= 8 && !pro_a), -2, "conv2d_fwd: the NCHW source form is the first conv's: at most 8 channels in all, no prologue");
+  MI355_REQUIRE(!pro_a || cin % CH == 0, -2, "conv2d_fwd: a prologue needs whole 64-byte chunks of input channels (pro_a / pro_b are [batch][cin + cin1])");
+  const int c_src0 = nchw_src ? cin + cin1 : cin;
+  const int cpad = (c_src0 + CH - 1) / CH * CH;
+  const int ctot = cin + cin1;
+  const bool nhwc = cout % 32 == 0;
+  MI355_REQUIRE(nhwc || (!emb && !res), -4, "conv2d_fwd: emb / residual epilogues need an NHWC output (cout % 32 == 0)");
+  MI355_REQUIRE(!axpy_x || !nhwc, -4, "conv2d_fwd: the Euler update belongs to the NCHW fp32 out conv (cout % 32 != 0)");
+  static char placeholder[256];   // the route query's stand-in for every pointer the route functions test for null (never read)
+  ConvDesc d; d.dtype = dtype; d.N = batch; d.Hs = h; d.Ws = w; d.C0 = cpad; d.C1 = two ? cin1 : 0; d.ks = ksize; d.Cout = cout;
+  d.knobs = &K; d.wsplit = wsplit;
+  if (nchw_src) d.cin_real = ctot; else if (!two && cin <= 8) d.cin_real = cin;
+  d.mode = stride == 2 ? CONV_STRIDE2 : (resample == 2 ? CONV_UP2 : CONV_UNIT);
+  const ConvGeom g = conv_geometry(d);
+  const int Hr = res_mode == RES_UP2 ? g.Ho / 2 : g.Ho, Wr = res_mode == RES_UP2 ? g.Wo / 2 : g.Wo;
+  const bool want_up2 = d.mode == CONV_UP2 && ksize == 3 && !wsplit && (K.conv_pp & 64) && cpad == c_src0;
+  char* p = dry ? placeholder : reinterpret_cast<char*>(workspace);
+  auto take = [&](size_t bytes) { char* q = p; if (!dry) p += al256(bytes); return (void*)q; };
+  void* xin = take((size_t)batch * h * w * cpad * esz);
+  void* xin1 = two ? take((size_t)batch * h * w * cin1 * esz) : nullptr;
+  const size_t wbytes = conv_packed_weight_bytes(dtype, cout, ctot, ksize, wsplit);
+  void* wdev = take(wbytes);
+  float* bdev = reinterpret_cast<float*>(take((size_t)cout * 4));
+  void* yout = nhwc ? take((size_t)batch * g.Ho * g.Wo * cout * esz) : (void*)y;
+  void* rin = res ? take((size_t)batch * Hr * Wr * cout * esz) : nullptr;
+  uint32_t* errw = reinterpret_cast<uint32_t*>(take(256));
+  MI355_REQUIRE(dry || p <= reinterpret_cast<char*>(workspace) + workspace_bytes, -2, "conv2d_fwd: workspace too small");
+  const size_t wbytes_up2 = want_up2 ? conv_packed_weight_bytes_up2(dtype, cout, ctot) : 0;
+  ExScratch xs;
+  void* wdev_up2 = !want_up2 ? nullptr : (dry ? (void*)placeholder : xs.get(wbytes_up2));
+  MI355_REQUIRE(!want_up2 || wdev_up2, -2, "conv2d_fwd: out of device memory");
+  d.src0 = xin; d.src1 = xin1; d.w = wdev; d.w_up2 = wdev_up2; d.bias = bias_host ? bdev : nullptr; d.err = errw;
+  if (pro_a) { d.pro_a = pro_a; d.pro_b = pro_b; d.pro_silu = pro_silu; }
+  if (emb) { d.emb = emb; d.emb_stride = cout; }
+  if (res) { d.res = rin; d.res_mode = res_mode; }
+  d.out_mode = nhwc ? OUT_NHWC : OUT_NCHW_F32; d.out = dry ? (void*)placeholder : yout;
+  if (nchw_src) {
+    d.nchw0 = dry ? reinterpret_cast<const float*>(placeholder) : x; d.nchw_c0 = cin;
+    d.nchw1 = !cin1 ? nullptr : (dry ? reinterpret_cast<const float*>(placeholder) : x1); d.nchw_c1 = cin1;
+  }
+  if (axpy_x) { d.axpy_x = axpy_x; d.axpy_scale = axpy_scale; }
+  ConvRoute r;
+  int rc;
+  if ((rc = conv_route(d, &r))) return rc;
+  auto report = [&] {
+    if (!route) return;
+    route[0] = r.kernel; route[1] = r.form; route[2] = r.geom.BM; route[3] = r.geom.BN; route[4] = r.reads_nchw; route[5] = r.axpy;
+    route[6] = r.ksplit; route[7] = r.n_mt;
+  };
+  if (dry) { report(); return 0; }
+  hipStream_t s = S(stream);
+  MI355_CHECK_HIP(hipMemsetAsync(errw, 0, 256, s));
+  if (!r.reads_nchw) {   // a launch that reads the caller's tensors itself leaves the packed copy as the caller filled the workspace
+    if ((rc = pack_nhwc_launch(dtype, x, cin, nchw_src ? x1 : nullptr, nchw_src ? cin1 : 0, batch, h * w, cpad, xin, s))) return rc;
+  }
+  if (two && (rc = pack_nhwc_launch(dtype, x1, cin1, nullptr, 0, batch, h * w, cin1, xin1, s))) return rc;
+  if (res && (rc = pack_nhwc_launch(dtype, res, cout, nullptr, 0, batch, Hr * Wr, cout, rin, s))) return rc;
+  std::vector<char> packed(wbytes), packed_up2(wbytes_up2);
+  conv_pack_weights(dtype, w_host, cout, ctot, ksize, packed.data(), wsplit);
+  MI355_CHECK_HIP(hipMemcpyAsync(wdev, packed.data(), wbytes, hipMemcpyHostToDevice, s));
+  if (want_up2) {
+    conv_pack_weights_up2(dtype, w_host, cout, ctot, packed_up2.data());
+    MI355_CHECK_HIP(hipMemcpyAsync(wdev_up2, packed_up2.data(), wbytes_up2, hipMemcpyHostToDevice, s));
+  }
+  if (bias_host) MI355_CHECK_HIP(hipMemcpyAsync(bdev, bias_host, (size_t)cout * 4, hipMemcpyHostToDevice, s));
+  if ((rc = conv_launch(d, r, s))) return rc;
+  report();
+  if (nhwc && (rc = unpack_nchw_launch(dtype, yout, batch, g.Ho * g.Wo, cout, y, s))) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));   // `packed` is a temporary host buffer
+  uint32_t ev = 0;
+  MI355_CHECK_HIP(hipMemcpy(&ev, errw, 4, hipMemcpyDeviceToHost));
+  if (ev) { mi355_set_error("conv2d_fwd: the persistent kernel gave up a bounded counter wait (hand-over stalled): the output is invalid"); return MI355_ERR_TIMEOUT; }
   return 0;
 }
 

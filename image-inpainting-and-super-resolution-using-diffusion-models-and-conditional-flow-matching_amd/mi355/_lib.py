@@ -186,6 +186,8 @@ SIGNATURES = {
     "mi355_grad_gather": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _VP]),
     "mi355_conv2d_vjp": (_I, [_FP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(DebugConfigC), C.POINTER(C.c_int32), _VP,
                               _I64, _VP]),
+    "mi355_conv2d_fwd": (_I, [_VP, _VP, _I, _FP, _FP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _F, _I,
+                              C.POINTER(DebugConfigC), C.POINTER(C.c_int32), _VP, _I64, _VP]),
 }
 
 _lock = threading.Lock()

@@ -684,5 +684,67 @@ class Ops:
                                           dtype, C.byref(debug) if debug is not None else None, route, None, 0, None), "mi355_conv2d_vjp")
         return dict(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3])
 
+    def conv2d_fwd(self, x, weight, bias=None, stride=1, resample=0, pro=None, pro_silu=False, dtype=_lib.MI355_F32, x1=None, emb=None, res=None,
+                   res_mode=1, nchw_src=False, axpy_x=None, axpy_scale=0.0, debug=None, ws_fill=None, info=None):
+        """One forward conv as the network launches it (mi355_conv2d_fwd).  weight / bias: CPU tensors [Co, Ci (+ Ci1), k, k] / [Co]; pro = (a, b) device
+        tensors [B, Ci + Ci1]: the prologue silu?(a v + b) given directly; x1: second source of a channel concat; emb [B, Co]; res with res_mode 1
+        (same size) or 2 (nearest x2 of a half-size tensor); resample 0 or 2.  nchw_src: x (and x1, the condition) are handed over as the first conv's
+        NCHW tensors.  axpy_x [B, Co, H, W]: the out conv's Euler update x + axpy_scale v (a copy is updated and returned where the launch applies it).
+        ws_fill: a byte value the workspace is filled with first (0xFF: whatever no kernel writes comes back NaN).  info: a dict that receives the
+        launch (kernel, form, tile_m, tile_n, reads_nchw, axpy, ksplit, n_mt) and both tensors the op could write: y (NaN before the call) and axpy_x (the copy).  -> y [B, Co, Ho, Wo], or the updated copy of axpy_x."""
+        B, Cin, H, W = x.shape
+        Co, Ci, k, _ = weight.shape
+        Cin1 = 0 if x1 is None else x1.shape[1]
+        if Ci != Cin + Cin1:
+            raise ValueError(f"weight has {Ci} input channels, the sources {Cin} + {Cin1}")
+        if x1 is not None and (x1.shape[0] != B or x1.shape[2:] != x.shape[2:]):
+            raise ValueError("x1 must match x in batch and spatial size")
+        Hc, Wc = (2 * H, 2 * W) if resample == 2 else (H, W)
+        Ho = (Hc + 2 * (k // 2) - k) // stride + 1
+        Wo = (Wc + 2 * (k // 2) - k) // stride + 1
+        if pro is not None and (tuple(pro[0].shape) != (B, Ci) or tuple(pro[1].shape) != (B, Ci)):
+            raise ValueError(f"pro = (a, b) must both be {(B, Ci)}")
+        if emb is not None and tuple(emb.shape) != (B, Co):
+            raise ValueError("emb must be [B, Co]")
+        if res is not None:
+            want = (B, Co, Ho, Wo) if res_mode == 1 else (B, Co, Ho // 2, Wo // 2)
+            if tuple(res.shape) != want:
+                raise ValueError(f"res must be {want}")
+        if axpy_x is not None and tuple(axpy_x.shape) != (B, Co, Ho, Wo):
+            raise ValueError(f"axpy_x must be {(B, Co, Ho, Wo)}")
+        dev = x.device
+        y = torch.full((B, Co, Ho, Wo), float("nan"), device=dev)
+        xu = axpy_x.clone() if axpy_x is not None else None
+        L = _lib.lib()
+        wsb = L.mi355_op_workspace_bytes(B, max(Ci, Co), max(H * W, Ho * Wo))
+        ws = torch.empty(wsb, device=dev, dtype=torch.uint8) if ws_fill is None else torch.full((wsb,), int(ws_fill), device=dev, dtype=torch.uint8)
+        wh = weight.detach().to("cpu", torch.float32).contiguous()
+        bh = bias.detach().to("cpu", torch.float32).contiguous() if bias is not None else None
+        fp = C.POINTER(C.c_float)
+        route = (C.c_int32 * 8)(*([-1] * 8))
+        check(L.mi355_conv2d_fwd(_req(x, "x"), _req(x1, "x1") if x1 is not None else None, Cin1, C.cast(wh.data_ptr(), fp),
+                                 C.cast(bh.data_ptr(), fp) if bh is not None else None, _req(y, "y"), B, Cin, H, W, Co, k, int(stride), int(resample),
+                                 _req(pro[0], "pro_a") if pro else None, _req(pro[1], "pro_b") if pro else None, int(bool(pro_silu)),
+                                 _req(emb, "emb") if emb is not None else None, _req(res, "res") if res is not None else None, int(res_mode),
+                                 int(bool(nchw_src)), _req(xu, "axpy_x") if xu is not None else None, float(axpy_scale), dtype,
+                                 C.byref(debug) if debug is not None else None, route, C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_conv2d_fwd")
+        if info is not None:
+            info.update(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3], reads_nchw=route[4], axpy=route[5], ksplit=route[6], n_mt=route[7],
+                        y=y, axpy_x=xu)
+        return xu if route[5] == 1 else y
+
+    def conv2d_fwd_route(self, B, Cin, Co, h, w, k, stride=1, resample=0, Cin1=0, bias=True, pro=False, pro_silu=False, emb=False, res_mode=0,
+                         nchw_src=False, axpy=False, dtype=_lib.MI355_F32, debug=None):
+        """What conv_route decides for the forward conv conv2d_fwd would launch for these sizes and optional parts (res_mode 0: no residual): host
+        code, nothing is launched (no GPU needed).  -> dict(kernel, form, tile_m, tile_n, reads_nchw, axpy, ksplit, n_mt)"""
+        some = C.c_void_p(256)   # stands for "present": the route query reads no pointer
+        fp = C.POINTER(C.c_float)
+        route = (C.c_int32 * 8)(*([-1] * 8))
+        check(_lib.lib().mi355_conv2d_fwd(None, None, int(Cin1), None, C.cast(some, fp) if bias else None, None, B, Cin, h, w, Co, k, int(stride),
+                                          int(resample), some if pro else None, some if pro else None, int(bool(pro_silu)), some if emb else None,
+                                          some if res_mode else None, int(res_mode) if res_mode else 1, int(bool(nchw_src)), some if axpy else None,
+                                          0.0, dtype, C.byref(debug) if debug is not None else None, route, None, 0, None), "mi355_conv2d_fwd")
+        return dict(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3], reads_nchw=route[4], axpy=route[5], ksplit=route[6], n_mt=route[7])
+
 
 default_ops = Ops()

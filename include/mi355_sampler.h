@@ -48,7 +48,8 @@ extern "C" {
  * mi355_conv2d_vjp (the conv data gradient of the U-Net backward as a test op; a new symbol only); then conv_ws became a bit mask (bit 1: the
  * warp-specialised conv carries a ResBlock's 1x1 skip conv, off in mi355_debug_defaults; bits 2 and 8.. for tests) and mi355_conv_extras gained the
  * stat_* fields at its end, read only behind MI355_CONV_EXTRAS_STATS in route[3] (a caller built against the shorter struct is unaffected); then
- * mi355_image_metrics (per-sample MSE, PSNR and SSIM of the evaluation loop; a new symbol only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * mi355_image_metrics (per-sample MSE, PSNR and SSIM of the evaluation loop; a new symbol only); then mi355_conv2d_fwd (one forward conv as a test
+ * op: prologue given directly, route always reported, the first conv's NCHW read and the out conv's Euler update; a new symbol only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -701,6 +702,30 @@ int mi355_grad_gather(const float* src, float* dst, int batch, int cd, int hd, i
 int mi355_conv2d_vjp(const float* w_host, const float* grad_out, float* g0, float* g1, float* du_raw, int acc0, int acc1, int batch, int cout,
                      int cin, int c0, int c1, int h, int w, int ksize, int mode, int g_channels, int dtype, const mi355_debug_config* debug,
                      int32_t route[4], void* workspace, int64_t workspace_bytes, void* stream);
+/* One forward conv of the network, isolated (later addition to ABI 108): mi355_conv2d_ex with these differences.
+ *  - The prologue is given directly: pro_a / pro_b DEVICE fp32 [batch][cin + cin1] (both NULL: none) and pro_silu, P(v) = silu?(a v + b) per (image,
+ *    channel) as the conv stages its input; no gn_affine launch sits between the caller's numbers and the conv (cin must be whole 64-byte chunks).
+ *  - route (host, 8 words, may be NULL) = {kernel, form, tile pixels, tile channels (mi355_conv_extras::route), ConvRoute::reads_nchw,
+ *    ConvRoute::axpy, ConvRoute::ksplit (small-level kernel: waves sharing K; else 0), ConvRoute::n_mt (workgroups / tiles along the pixels; else 0)}, for the NCHW fp32 out conv (cout % 32 != 0) as well; -1 if the call failed before its launch.  workspace NULL with
+ *    workspace_bytes 0 and route given: nothing is launched or read; the same description is built with placeholder pointers (x, w_host, y may be
+ *    NULL; x1 is cin1 > 0; bias_host, pro_a / pro_b, emb, res, axpy_x count as present when not NULL) and route receives what conv_route decides
+ *    (host code; no GPU needed).
+ *  - Every activation, the packed nine-tap weights and the output live in `workspace` (mi355_op_workspace_bytes(batch, max(cin + cin1, cout),
+ *    max(h w, Ho Wo)) suffices) and only what a kernel writes is initialised: with the workspace pre-filled with 0xFF bytes an output element no kernel
+ *    wrote unpacks as NaN.  The one exception is the collapsed weight image of the phase form (nearest x2, ksize 3, conv_pp bit 6), which the op
+ *    allocates itself (hipMalloc, freed on return) and fills completely from the host, as mi355_conv2d_ex does.
+ *  - flags & MI355_CONV_FWD_NCHW_SRC: x [B, cin, H, W] and x1 [B, cin1, H, W] (cin + cin1 <= 8, no prologue) are the caller's tensors of the network's
+ *    first conv, handed over as ConvDesc::nchw0 / nchw1 with cin_real = cin + cin1 (x1 is then the condition, not a second source); route[4] says whether
+ *    the launch read them itself - the packed copy is then not made - or read the copy pack_nhwc made of x | x1.
+ *  - axpy_x (NULL, or DEVICE fp32 [B, cout, H, W]; out conv only) with axpy_scale: the Euler update x <- x + scale v in the out conv's epilogue;
+ *    route[5] says whether it replaced the store (y is then left untouched) or v was stored to y (axpy_x untouched).
+ * Everything else as mi355_conv2d_ex: x1 / cin1 (second source), emb, res with res_mode 1 / 2, stride, resample 0 / 2 (pooling, 3, is a pre-pass:
+ * mi355_affine_pool), the four dtype codes, debug.  Synchronises `stream`. */
+#define MI355_CONV_FWD_NCHW_SRC 1
+int mi355_conv2d_fwd(const float* x, const float* x1, int cin1, const float* w_host, const float* bias_host, float* y, int batch, int cin, int h,
+                     int w, int cout, int ksize, int stride, int resample, const float* pro_a, const float* pro_b, int pro_silu, const float* emb,
+                     const float* res, int res_mode, int flags, float* axpy_x, float axpy_scale, int dtype, const mi355_debug_config* debug,
+                     int32_t route[8], void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
