@@ -305,6 +305,12 @@ int ddpm_cfg_step_launch(float* x, const float* eps, const float* z, float w, co
                          float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int ddim_cfg_step_launch(float* x, const float* eps, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float acp_prev, int64_t n,
                          hipStream_t s);
+// DDIM(eta) step, its guided form (operands as ddim_cfg_step_launch) and the forward re-noising move x <- a x + b z of a RePaint walk
+int ddim_eta_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int use_philox,
+                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
+int ddim_eta_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
+                             float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
+int renoise_step_launch(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb,
                         int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int clip_launch(float* x, float lo, float hi, int64_t n, hipStream_t s);

@@ -131,6 +131,11 @@ struct Guide {
   int ddim(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s) const {
     return on ? ddim_cfg_step_launch(x, eps, w, w_dev, per, c_recip, c_recipm1, acp_prev, n, s) : ddim_step_launch(x, eps, c_recip, c_recipm1, acp_prev, n, s);
   }
+  int ddim_eta(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int philox, uint64_t seed,
+               uint64_t off, int64_t n, hipStream_t s) const {
+    return on ? ddim_eta_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, acp_prev, sigma, philox, seed, off, n, s)
+              : ddim_eta_step_launch(x, eps, z, c_recip, c_recipm1, acp_prev, sigma, philox, seed, off, n, s);
+  }
   int ddpm(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float sigma, int philox, uint64_t seed,
            uint64_t off, int64_t n, hipStream_t s) const {
     return on ? ddpm_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, coef1, coef2, sigma, philox, seed, off, n, s)
@@ -298,7 +303,16 @@ struct DdpmLoop {
   float* mirror;            // guided: the state's second half, refreshed after a step's correctors
   Guide guide;
 };
-int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const DdpmLoop& a, int channels, const mi355_ddpm_tables* tb,
+// What a scheduled entry point adds to the loop (mi355_ddpm_schedule, checked by check_schedule): all null = the plain descent Ns-1..0.
+struct LoopSched {
+  const float* ddim_sigma = nullptr;   // MI355_DDIM: sigma of step i (the DDIM(eta) step); null = the deterministic step
+  const int32_t* walk = nullptr;       // levels K, ..., 0 with +-1 moves; null = K, K-1, ..., 0
+  int n_walk = 0;
+  const float* renoise_a = nullptr;    // an upward move L -> L+1: x <- renoise_a[L] x + renoise_b[L] z
+  const float* renoise_b = nullptr;
+};
+// emb: row i = the evaluation of step i (ddpm_times(Ns), or a schedule's tau_i / train_steps), selected whenever step i runs, revisits included.
+int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const DdpmLoop& a, const LoopSched& ls, int channels, const mi355_ddpm_tables* tb,
               const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch, int64_t n, hipStream_t s) {
   const int mode = opt->mode, Ns = tb->Ns;
   const int64_t n_al = (n + 3) / 4 * 4;
@@ -316,7 +330,8 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     ++draw;
     return 0;
   };
-  for (int i = Ns - 1; i >= 0; --i) {
+  // the move L -> L - 1 for i = L - 1: the replacement paste, the evaluation, the predictor, the correctors
+  auto down = [&](int i) -> int {
     if (mode == MI355_DDPM_REPLACEMENT && i < (int)(Ns * opt->start_fraction)) {
       const float* z = nullptr; int ph = 0; uint64_t off = 0;
       if (opt->noise_condition && (rc = next_noise(z, ph, off))) return rc;
@@ -327,8 +342,12 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     run_corr.emb_row = run.emb_row;
     if ((rc = unet_forward(net, x, channels, a.cond_pred, channels, sc.t, sc.v, a.evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
     if (mode == MI355_DDIM) {
-      if ((rc = a.guide.ddim(x, sc.v, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i], n, s))) return rc;
-      continue;
+      if (!ls.ddim_sigma)
+        return a.guide.ddim(x, sc.v, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i], n, s);
+      const float* z = nullptr; int ph = 0; uint64_t off = 0;   // step 0 has acp_prev = 1: no noise term, no draw
+      if (i > 0 && (rc = next_noise(z, ph, off))) return rc;
+      return a.guide.ddim_eta(x, sc.v, z, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i],
+                              ls.ddim_sigma[i], ph, opt->seed, off, n, s);
     }
     const float* z = nullptr; int ph = 0; uint64_t off = 0;
     if (i > 0 && (rc = next_noise(z, ph, off))) return rc;
@@ -344,8 +363,116 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
                                       tb->recip_sqrt_m1_alphas_cumprod[i], dt, opt->delta, ph2, opt->seed, off2, n, s))) return rc;
     }
     if (a.mirror && opt->n_corrector > 0) MI355_CHECK_HIP(hipMemcpyAsync(a.mirror, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+  };
+  if (!ls.walk) {
+    for (int i = Ns - 1; i >= 0; --i) if ((rc = down(i))) return rc;
+  } else {
+    for (int j = 0; j + 1 < ls.n_walk; ++j) {
+      const int L = ls.walk[j];
+      if (ls.walk[j + 1] < L) { if ((rc = down(L - 1))) return rc; continue; }
+      const float* z = nullptr; int ph = 0; uint64_t off = 0;   // L -> L + 1: q(x_L | x_{L-1}), one draw
+      if ((rc = next_noise(z, ph, off))) return rc;
+      if ((rc = renoise_step_launch(x, z, ls.renoise_a[L], ls.renoise_b[L], ph, opt->seed, off, n, s))) return rc;
+    }
   }
   return clip_launch(x, -1.f, 1.f, n, s);
+}
+
+// Every refusal of a mi355_ddpm_schedule, before any launch, each naming its argument.
+int check_schedule(const char* who, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sd, bool guided, LoopSched& ls) {
+  const std::string f = std::string(who) + ": ";
+  MI355_REQUIRE(sd, -1, f + "sched is null");
+  const int K = tb->Ns;
+  MI355_REQUIRE(sd->train_steps >= 1, -1, f + "train_steps must be >= 1");
+  MI355_REQUIRE(sd->steps || K <= 0, -1, f + "steps is null");
+  for (int k = 0; k < K; ++k)
+    MI355_REQUIRE(sd->steps[k] >= 0 && sd->steps[k] < sd->train_steps && (k == 0 || sd->steps[k] > sd->steps[k - 1]), -1,
+                  f + "steps must be strictly increasing training indices in [0, train_steps)");
+  MI355_REQUIRE(!sd->ddim_sigma || opt->mode == MI355_DDIM, -1, f + "ddim_sigma belongs to MI355_DDIM (the other modes take their variance from the tables)");
+  for (int k = 0; sd->ddim_sigma && k < K; ++k)
+    MI355_REQUIRE(sd->ddim_sigma[k] >= 0.f && sd->ddim_sigma[k] <= 3.0e38f, -1, f + "ddim_sigma must be finite and >= 0");
+  ls = LoopSched();
+  ls.ddim_sigma = sd->ddim_sigma;
+  if (!sd->walk) return 0;
+  MI355_REQUIRE(sd->n_walk >= 1 && sd->walk[0] == K, -1, f + "walk must start at level K (= tables->Ns)");
+  MI355_REQUIRE(sd->walk[sd->n_walk - 1] == 0, -1, f + "walk must end at level 0");
+  bool up = false;
+  for (int j = 0; j + 1 < sd->n_walk; ++j) {
+    const int64_t d = (int64_t)sd->walk[j + 1] - (int64_t)sd->walk[j];
+    MI355_REQUIRE((d == 1 || d == -1) && sd->walk[j + 1] >= 0 && sd->walk[j + 1] <= K, -1, f + "walk must move by +-1 between levels in [0, K]");
+    up = up || d == 1;
+  }
+  MI355_REQUIRE(!up || !guided, -1, f + "walk has upward moves: the guided sampler's mirror half is not built for re-noising");
+  MI355_REQUIRE(!up || (sd->renoise_a && sd->renoise_b), -1, f + "walk has upward moves: renoise_a and renoise_b are needed");
+  ls.walk = sd->walk; ls.n_walk = sd->n_walk; ls.renoise_a = sd->renoise_a; ls.renoise_b = sd->renoise_b;
+  return 0;
+}
+std::vector<float> sched_times(int K, const mi355_ddpm_schedule* sd) {   // evaluation k = step k: network(x, (float)tau_k / (float)train_steps)
+  std::vector<float> th((size_t)(K > 0 ? K : 0));
+  for (int k = 0; k < K; ++k) th[k] = (float)sd->steps[k] / (float)sd->train_steps;
+  return th;
+}
+
+// The body of mi355_ddpm_sample and mi355_ddpm_sample_sched: th = the K evaluation times, ls = what the schedule adds (`who` prefixes the refusals).
+int ddpm_sample_run(const char* who, mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt,
+                    const std::vector<float>& th, const LoopSched& ls, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
+                    int64_t workspace_bytes, void* stream) {
+  const std::string f = std::string(who) + ": ";
+  MI355_REQUIRE(channels == net->cfg.out_channels, -2, f + "eps model must output the state's channel count");
+  const int mode = opt->mode;
+  const bool amortized = net->cfg.in_channels == 2 * channels;
+  MI355_REQUIRE(amortized || net->cfg.in_channels == channels, -2, f + "network in_channels must be C or 2C");
+  MI355_REQUIRE(mode != MI355_DDPM_REPLACEMENT || (!amortized && cond), -2, f + "replacement needs an unconditional net and a condition");
+  MI355_REQUIRE(mode != MI355_DDPM_AMORTIZED || (amortized && cond), -2, f + "amortized needs a 2C-input net and a condition");
+  Layout l;
+  if (int rc = carve(net, batch, false, 0, workspace, workspace_bytes, l)) return rc;
+  const Scratch& sc = l.sc;
+  hipStream_t s = S(stream);
+  const int64_t n = (int64_t)batch * channels * net->cfg.image_size * net->cfg.image_size;
+  EvalEmb emb;
+  if (int rc = emb.init(net, sc, th.data(), tb->Ns, false, true, s)) return rc;
+  if (amortized) { if (int rc = fill_launch(sc.none, opt->none_value, n, s)) return rc; }
+  DdpmLoop a = {};
+  a.who = who; a.state = x; a.evalB = batch; a.mask_cond = cond;
+  // the net's condition input on predictor steps / on corrector steps (the reference's corrector calls
+  // x0_model without the condition, sampling.py:116 -> none_like)
+  a.cond_pred = !amortized ? nullptr : ((mode == MI355_DDPM_AMORTIZED || (mode == MI355_DDIM && cond)) ? cond : sc.none);
+  a.cond_corr = amortized ? sc.none : nullptr;
+  return ddpm_loop(net, sc, emb, a, ls, channels, tb, opt, noise, n_noise_draws, batch, n, s);
+}
+
+// The body of mi355_ddpm_cfg_sample and mi355_ddpm_cfg_sample_sched.
+int ddpm_cfg_sample_run(const char* who, mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w,
+                        const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const std::vector<float>& th, const LoopSched& ls,
+                        const float* noise, int64_t n_noise_draws, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  const std::string f = std::string(who) + ": ";
+  const int mode = opt->mode;
+  MI355_REQUIRE(mode == MI355_DDPM_AMORTIZED || mode == MI355_DDIM, -1,
+                f + "guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement modes are refused)");
+  MI355_REQUIRE(cond || labels, -1, f + "nothing to guide (neither a condition nor class labels)");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, f + "class labels given to a net built without num_classes");
+  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, f + "null_label must be a class index in [0, num_classes)");
+  MI355_REQUIRE(channels == net->cfg.out_channels, -2, f + "eps model must output the state's channel count");
+  MI355_REQUIRE(net->cfg.in_channels == 2 * channels && cond, -2, f + "needs a 2C-input net and a condition");
+  MI355_REQUIRE(workspace_bytes >= mi355_ddpm_cfg_workspace_bytes(net, batch), -2, f + "workspace too small");
+  Layout l;
+  if (int rc = carve(net, batch, true, 0, workspace, workspace_bytes, l)) return rc;
+  const Scratch& sc = l.sc;
+  const CfgTail& tl = l.cfg;
+  hipStream_t s = S(stream);
+  const int64_t per = (int64_t)channels * net->cfg.image_size * net->cfg.image_size, n = (int64_t)batch * per;
+  EvalEmb emb;   // row i (block of num_classes rows with labels) = step i
+  if (int rc = emb.init(net, sc, th.data(), tb->Ns, labels != nullptr, true, s)) return rc;
+  if (int rc = cfg_fill_tail(tl, x, n, cond, n, opt->none_value, labels, null_label, batch, s)) return rc;
+  DdpmLoop a = {};
+  a.who = who; a.state = tl.x2; a.evalB = 2 * batch; a.mirror = tl.x2 + n;
+  a.cond_pred = tl.cond2; a.labels_pred = labels ? tl.labels2 : nullptr;
+  a.cond_corr = tl.cond2 + n; a.labels_corr = labels ? tl.labels2 + batch : nullptr;
+  a.guide.on = true; a.guide.w = w; a.guide.w_dev = w_dev; a.guide.per = per;
+  if (int rc = ddpm_loop(net, sc, emb, a, ls, channels, tb, opt, noise, n_noise_draws, batch, n, s)) return rc;
+  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
 }
 
 }  // namespace
@@ -468,61 +595,36 @@ int mi355_ddpm_sample(mi355_unet* net, float* x, int channels, const float* cond
                       const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
                       int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(net && x && tb && opt, -1, "ddpm_sample: null argument");
-  MI355_REQUIRE(channels == net->cfg.out_channels, -2, "ddpm_sample: eps model must output the state's channel count");
-  const int mode = opt->mode;
-  const bool amortized = net->cfg.in_channels == 2 * channels;
-  MI355_REQUIRE(amortized || net->cfg.in_channels == channels, -2, "ddpm_sample: network in_channels must be C or 2C");
-  MI355_REQUIRE(mode != MI355_DDPM_REPLACEMENT || (!amortized && cond), -2, "ddpm_sample: replacement needs an unconditional net and a condition");
-  MI355_REQUIRE(mode != MI355_DDPM_AMORTIZED || (amortized && cond), -2, "ddpm_sample: amortized needs a 2C-input net and a condition");
-  Layout l;
-  if (int rc = carve(net, batch, false, 0, workspace, workspace_bytes, l)) return rc;
-  const Scratch& sc = l.sc;
-  hipStream_t s = S(stream);
-  const int64_t n = (int64_t)batch * channels * net->cfg.image_size * net->cfg.image_size;
-  const std::vector<float> th = ddpm_times(tb->Ns);
-  EvalEmb emb;
-  if (int rc = emb.init(net, sc, th.data(), tb->Ns, false, true, s)) return rc;
-  if (amortized) { if (int rc = fill_launch(sc.none, opt->none_value, n, s)) return rc; }
-  DdpmLoop a = {};
-  a.who = "ddpm_sample"; a.state = x; a.evalB = batch; a.mask_cond = cond;
-  // the net's condition input on predictor steps / on corrector steps (the reference's corrector calls
-  // x0_model without the condition, sampling.py:116 -> none_like)
-  a.cond_pred = !amortized ? nullptr : ((mode == MI355_DDPM_AMORTIZED || (mode == MI355_DDIM && cond)) ? cond : sc.none);
-  a.cond_corr = amortized ? sc.none : nullptr;
-  return ddpm_loop(net, sc, emb, a, channels, tb, opt, noise, n_noise_draws, batch, n, s);
+  return ddpm_sample_run("ddpm_sample", net, x, channels, cond, tb, opt, ddpm_times(tb->Ns), LoopSched(), noise, n_noise_draws, batch, workspace,
+                         workspace_bytes, stream);
+}
+
+int mi355_ddpm_sample_sched(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb,
+                            const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched, const float* noise, int64_t n_noise_draws, int batch,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && x && tb && opt, -1, "ddpm_sample_sched: null argument");
+  LoopSched ls;
+  if (int rc = check_schedule("ddpm_sample_sched", tb, opt, sched, false, ls)) return rc;
+  return ddpm_sample_run("ddpm_sample_sched", net, x, channels, cond, tb, opt, sched_times(tb->Ns, sched), ls, noise, n_noise_draws, batch, workspace,
+                         workspace_bytes, stream);
 }
 
 int mi355_ddpm_cfg_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w, const float* w_dev,
                           const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch,
                           void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(net && x && tb && opt && batch > 0, -1, "ddpm_cfg_sample: bad argument");
-  const int mode = opt->mode;
-  MI355_REQUIRE(mode == MI355_DDPM_AMORTIZED || mode == MI355_DDIM, -1,
-                "ddpm_cfg_sample: guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement modes are refused)");
-  MI355_REQUIRE(cond || labels, -1, "ddpm_cfg_sample: nothing to guide (neither a condition nor class labels)");
-  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "ddpm_cfg_sample: class labels given to a net built without num_classes");
-  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, "ddpm_cfg_sample: null_label must be a class index in [0, num_classes)");
-  MI355_REQUIRE(channels == net->cfg.out_channels, -2, "ddpm_cfg_sample: eps model must output the state's channel count");
-  MI355_REQUIRE(net->cfg.in_channels == 2 * channels && cond, -2, "ddpm_cfg_sample: needs a 2C-input net and a condition");
-  MI355_REQUIRE(workspace_bytes >= mi355_ddpm_cfg_workspace_bytes(net, batch), -2, "ddpm_cfg_sample: workspace too small");
-  Layout l;
-  if (int rc = carve(net, batch, true, 0, workspace, workspace_bytes, l)) return rc;
-  const Scratch& sc = l.sc;
-  const CfgTail& tl = l.cfg;
-  hipStream_t s = S(stream);
-  const int64_t per = (int64_t)channels * net->cfg.image_size * net->cfg.image_size, n = (int64_t)batch * per;
-  const std::vector<float> th = ddpm_times(tb->Ns);
-  EvalEmb emb;   // row i (block of num_classes rows with labels) = step i
-  if (int rc = emb.init(net, sc, th.data(), tb->Ns, labels != nullptr, true, s)) return rc;
-  if (int rc = cfg_fill_tail(tl, x, n, cond, n, opt->none_value, labels, null_label, batch, s)) return rc;
-  DdpmLoop a = {};
-  a.who = "ddpm_cfg_sample"; a.state = tl.x2; a.evalB = 2 * batch; a.mirror = tl.x2 + n;
-  a.cond_pred = tl.cond2; a.labels_pred = labels ? tl.labels2 : nullptr;
-  a.cond_corr = tl.cond2 + n; a.labels_corr = labels ? tl.labels2 + batch : nullptr;
-  a.guide.on = true; a.guide.w = w; a.guide.w_dev = w_dev; a.guide.per = per;
-  if (int rc = ddpm_loop(net, sc, emb, a, channels, tb, opt, noise, n_noise_draws, batch, n, s)) return rc;
-  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-  return 0;
+  return ddpm_cfg_sample_run("ddpm_cfg_sample", net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, ddpm_times(tb->Ns), LoopSched(), noise,
+                             n_noise_draws, batch, workspace, workspace_bytes, stream);
+}
+
+int mi355_ddpm_cfg_sample_sched(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w,
+                                const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                                const float* noise, int64_t n_noise_draws, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(net && x && tb && opt && batch > 0, -1, "ddpm_cfg_sample_sched: bad argument");
+  LoopSched ls;
+  if (int rc = check_schedule("ddpm_cfg_sample_sched", tb, opt, sched, true, ls)) return rc;
+  return ddpm_cfg_sample_run("ddpm_cfg_sample_sched", net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, sched_times(tb->Ns, sched), ls,
+                             noise, n_noise_draws, batch, workspace, workspace_bytes, stream);
 }
 
 // Training-free in-painting / super-resolution of an unconditional flow: replacement along the straight path and / or reconstruction guidance

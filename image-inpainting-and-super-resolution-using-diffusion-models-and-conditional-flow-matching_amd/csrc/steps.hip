@@ -253,6 +253,88 @@ int ddim_cfg_step_launch(float* x, const float* eps, float w, const float* w_dev
   });
 }
 
+// DDIM(eta) step (Song et al. 2021, eq. 12) with the reference's clipped x0_hat: ddim_step_launch's x0 and e2, then
+//   x <- sqrt(acp_prev) x0 + sqrt(max(1 - acp_prev - sigma^2, 0)) e2 + sigma z,
+// the two square roots taken here on the host (1 - acp_prev - sigma^2 left to right, sigma^2 rounded).  Noise as ddpm_step_launch; with neither z
+// nor Philox the noise term is not added at all, so sigma = 0 without noise gives ddim_step_launch's bits.
+namespace {
+struct DdimEta { float sa, sb; };
+inline DdimEta ddim_eta_coefs(float acp_prev, float sigma) {
+  const float s2 = sigma * sigma;
+  const float r = 1.0f - acp_prev;
+  return {sqrtf(acp_prev), sqrtf(fmaxf(r - s2, 0.f))};
+}
+}  // namespace
+
+int ddim_eta_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int use_philox,
+                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "ddim_eta_step: the Philox offset must be a multiple of 4");
+  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_eta_step: null argument");
+  MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, "ddim_eta_step: sigma must be finite and >= 0");
+  const uint64_t off4 = offset / 4;
+  const DdimEta c = ddim_eta_coefs(acp_prev, sigma);
+  const float sa = c.sa, sb = c.sb;
+  const int noisy = z != nullptr || use_philox;
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
+    float xv[4], ev[4], zz[4] = {0.f, 0.f, 0.f, 0.f};
+    ld4(x, i, cnt, xv); ld4(eps, i, cnt, ev);
+    if (noisy) noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
+      const float e2 = (c_recip * xv[j] - x0) / c_recipm1;
+      const float m = sa * x0 + sb * e2;
+      xv[j] = noisy ? m + sigma * zz[j] : m;
+    }
+    st4(x, i, cnt, xv);
+  });
+}
+
+// its classifier-free-guided form, built as ddim_cfg_step_launch: eps [2n], x [2n] (first half read, both halves written), Philox indexed by the
+// element of the n-element state
+int ddim_eta_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
+                             float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "ddim_eta_cfg_step: the Philox offset must be a multiple of 4");
+  MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "ddim_eta_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
+  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_eta_cfg_step: null argument");
+  MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, "ddim_eta_cfg_step: sigma must be finite and >= 0");
+  const uint64_t off4 = offset / 4;
+  const DdimEta c = ddim_eta_coefs(acp_prev, sigma);
+  const float sa = c.sa, sb = c.sb;
+  const int noisy = z != nullptr || use_philox;
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
+    float xv[4], ev[4], zz[4] = {0.f, 0.f, 0.f, 0.f};
+    ld4(x, i, cnt, xv);
+    cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
+    if (noisy) noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
+      const float e2 = (c_recip * xv[j] - x0) / c_recipm1;
+      const float m = sa * x0 + sb * e2;
+      xv[j] = noisy ? m + sigma * zz[j] : m;
+    }
+    st4(x, i, cnt, xv);
+    st4(x + n, i, cnt, xv);
+  });
+}
+
+// Forward move q(x_k | x_{k-1}) of a (respaced) chain: x <- a x + b z with a = sqrt(alphas_k), b = sqrt(betas_k), two rounded products and one
+// sum.  Noise as ddpm_step_launch (neither z nor Philox: z = 0, x <- a x + b * 0).
+int renoise_step_launch(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "renoise_step: the Philox offset must be a multiple of 4");
+  MI355_REQUIRE(n <= 0 || x, -1, "renoise_step: null argument");
+  const uint64_t off4 = offset / 4;
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
+    float xv[4], zz[4];
+    ld4(x, i, cnt, xv);
+    noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) xv[j] = a * xv[j] + b * zz[j];
+    st4(x, i, cnt, xv);
+  });
+}
+
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb, int use_philox,
                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
   MI355_REQUIRE(offset % 4 == 0, -1, "replace_mask: the Philox offset must be a multiple of 4");

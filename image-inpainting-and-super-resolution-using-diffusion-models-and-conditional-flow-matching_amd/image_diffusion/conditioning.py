@@ -57,6 +57,50 @@ class Replacement(Conditioning):
     KEY, PARAMS = "replacement", ("delta", "start_fraction", "noise", "n_corrector")
 
 
+class RePaint(Replacement):
+    """Replacement with RePaint resampling (Lugmayr et al. 2022): the sampler walks the chain down and, at every jump point, back up
+    jump_length levels by the forward move q(x_k | x_{k-1}) and down again, n_resample times in all, which lets the generated pixels
+    harmonise with the pasted ones.  The walk is repaint_walk(ddpm.Ns, jump_length, n_resample); n_resample = 1 is Replacement itself.
+    Affordable on a respaced chain (DDPM.respace).  No reference counterpart; sample quality is untested."""
+    KEY, PARAMS = "repaint", Replacement.PARAMS + ("jump_length", "n_resample")
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if int(self.jump_length) != self.jump_length or self.jump_length < 1:
+            raise ValueError(f"jump_length must be an int >= 1, got {self.jump_length!r}")
+        if int(self.n_resample) != self.n_resample or self.n_resample < 1:
+            raise ValueError(f"n_resample must be an int >= 1, got {self.n_resample!r}")
+
+
+def repaint_walk(K: int, jump_length: int, n_resample: int):
+    """The levels a RePaint sampler visits on a K-step chain: a restatement of the jump schedule of Lugmayr et al. 2022 (their
+    get_schedule_jump with jump_n_sample = n_resample).  Level L in [0, K] is the state before step L - 1 is applied; K is noise, 0 the result.
+        budget[t] = n_resample - 1 for t in range(0, K - jump_length, jump_length)
+        t = K
+        while t >= 1:
+            t -= 1; emit t
+            if budget.get(t, 0) > 0: budget[t] -= 1; repeat jump_length times: t += 1; emit t
+    The levels are every emitted t + 1 (the first one is K itself: their t indexes the state x_t, which is level t + 1 here), and the walk
+    ends at level 0.  Consecutive levels differ by one: a move down is a sampling step, a move up one re-noising.  n_resample = 1 is the plain
+    descent K, K-1, ..., 0; K = 6, jump_length = 2, n_resample = 2 makes 10 steps down and 4 up."""
+    K, j, r = int(K), int(jump_length), int(n_resample)
+    if K < 1 or j < 1 or r < 1:
+        raise ValueError("repaint_walk needs K >= 1, jump_length >= 1 and n_resample >= 1")
+    budget = {t: r - 1 for t in range(0, K - j, j)}
+    levels = []
+    t = K
+    while t >= 1:
+        t -= 1
+        levels.append(t + 1)
+        if budget.get(t, 0) > 0:
+            budget[t] -= 1
+            for _ in range(j):
+                t += 1
+                levels.append(t + 1)
+    levels.append(0)
+    return levels
+
+
 class FlowReplacement(Conditioning):
     """Replacement for an unconditional flow-matching net (flow_sampling.py): during the first int(n_steps * start_fraction) steps the known
     pixels are put on the straight path, x <- where(known, t y + (1 - t) z, x).  noise: "coupled" (z = the sample's own initial state) or
@@ -102,7 +146,7 @@ def flow_split_index(n_steps: int, start_fraction: float) -> int:
     return int(n_steps * start_fraction)
 
 
-_REGISTRY: Dict[str, Type[Conditioning]] = {c.KEY: c for c in (Amortized, ClassifierFreeGuidance, ReconstructionGuidance, Replacement,
+_REGISTRY: Dict[str, Type[Conditioning]] = {c.KEY: c for c in (Amortized, ClassifierFreeGuidance, ReconstructionGuidance, Replacement, RePaint,
                                                                FlowReplacement, FlowReconstructionGuidance)}
 
 

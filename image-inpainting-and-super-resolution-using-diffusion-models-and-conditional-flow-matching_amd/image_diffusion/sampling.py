@@ -28,7 +28,7 @@ import torch
 from mi355 import _lib
 from mi355.ops import default_ops
 
-from .conditioning import Amortized, ClassifierFreeGuidance, Conditioning, ReconstructionGuidance, Replacement
+from .conditioning import Amortized, ClassifierFreeGuidance, Conditioning, ReconstructionGuidance, RePaint, Replacement, repaint_walk
 from .likelihoods import Likelihood
 from .sde_diffusion import DDPM
 
@@ -62,15 +62,33 @@ def use_ops(ops):
         _ops = prev
 
 
+def _sched_key(ddpm: DDPM):
+    """What identifies a sampling schedule: the training step count and the kept steps (None: all of them)."""
+    return (int(getattr(ddpm, "base_Ns", ddpm.Ns)), getattr(ddpm, "timesteps", None))
+
+
 def make_eps_model(network, ddpm: DDPM):
     """eps_model(xi, i) = network(xi, 1.0*i/Ns) (loss_functions.py:18-19, experiments/main.py:140),
-    tagged so the samplers can run the whole loop inside the C library."""
+    tagged so the samplers can run the whole loop inside the C library.  On a RespacedDDPM step i sits at training index tau_i:
+    eps_model(xi, i) = network(xi, tau_i / base_Ns), for an int i and for the long [B] tensor the samplers pass."""
+    steps = getattr(ddpm, "timesteps", None)
 
-    def eps_model(xi, i):
-        return network(xi, 1.0 * i / ddpm.Ns)
+    if steps is None:
+        def eps_model(xi, i):
+            return network(xi, 1.0 * i / ddpm.Ns)
+    else:
+        # time(k) for every k, rounded on the host: a device tensor divided by a Python number is multiplied by its rounded reciprocal,
+        # which need not be the correctly rounded quotient the fused loop feeds
+        times = torch.tensor([ddpm.time(k) for k in range(ddpm.Ns)], dtype=torch.float32)
+
+        def eps_model(xi, i):
+            if isinstance(i, torch.Tensor):
+                return network(xi, times.to(i.device)[i])
+            return network(xi, ddpm.time(i))
 
     eps_model._mi355_network = network
     eps_model._mi355_Ns = ddpm.Ns
+    eps_model._mi355_sched = _sched_key(ddpm)   # the fused loop evaluates the net at this schedule's times: only for this very schedule
     return eps_model
 
 
@@ -109,9 +127,15 @@ def process_x0(img):
     return _ops.clip_(img, -1.0, 1.0)
 
 
+def _same_schedule(eps_model, ddpm: DDPM) -> bool:
+    """eps_model was built for ddpm's step count and its very schedule (a model tagged with a step count alone: the unrespaced chain of it)."""
+    Ns = getattr(eps_model, "_mi355_Ns", None)
+    return Ns == ddpm.Ns and getattr(eps_model, "_mi355_sched", (Ns, None)) == _sched_key(ddpm)
+
+
 def _fast_engine(eps_model, ddpm: DDPM, xT: torch.Tensor):
     net = getattr(eps_model, "_mi355_network", None)
-    if net is None or getattr(eps_model, "_mi355_Ns", None) != ddpm.Ns or not hasattr(net, "engine") or not xT.is_cuda:
+    if net is None or not _same_schedule(eps_model, ddpm) or not hasattr(net, "engine") or not xT.is_cuda:
         return None
     return net.engine(xT.device)
 
@@ -150,11 +174,25 @@ def _net_in(xi, cond, amortized):
     return torch.concat((xi, cond), dim=-3) if amortized else xi  # sampling.py:39 (plumbing: the net's own input)
 
 
-def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replacement=None, n_corrector=0, delta=0.1):
+def _walk_moves(Ns, walk):
+    """(level, down) per move of a walk over the levels Ns..0 (None: the plain descent); down: step level - 1 runs, else the level re-noises."""
+    if walk is None:
+        return [(L, True) for L in range(Ns, 0, -1)]
+    if len(walk) < 1 or walk[0] != Ns or walk[-1] != 0 or any(abs(b - a) != 1 or not 0 <= b <= Ns for a, b in zip(walk, walk[1:])):
+        raise ValueError("walk must start at level Ns, end at level 0 and move by +-1")
+    return [(a, b < a) for a, b in zip(walk, walk[1:])]
+
+
+def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replacement=None, n_corrector=0, delta=0.1, walk=None):
     T = _tables(ddpm)
     xi = xT.detach().clone().float().contiguous()
     noise = _Noise(xi)
-    for i in reversed(range(ddpm.Ns)):
+    for level, down in _walk_moves(ddpm.Ns, walk):
+        if not down:   # q(x_level+1 | x_level): one draw
+            z, ph = noise.next()
+            _ops.renoise_(xi, z, float(T["alphas"][level].sqrt()), float(T["betas"][level].sqrt()), ph)
+            continue
+        i = level - 1
         if replacement is not None and i < int(ddpm.Ns * replacement["start_fraction"]):
             z, ph = noise.next() if replacement["noise"] else (None, None)
             _ops.replace_mask_(xi, replacement["condition"], z, replacement["pad_value"], replacement["noise"],
@@ -167,7 +205,16 @@ def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replac
     return process_x0(xi)
 
 
-def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corrector=0, delta=0.1, ddim=False):
+def _ddim_move(eps, xi, i, T, sigma, noise):
+    """One DDIM step: sigma None = the deterministic kernel; else DDIM(eta) with sigma[i] and one draw iff i > 0."""
+    cr, crm1, prev = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), float(T["alphas_cumprod_prev"][i])
+    if sigma is None:
+        return _ops.ddim_step_(xi, eps, cr, crm1, prev)
+    z, ph = noise.next() if i > 0 else (None, None)
+    return _ops.ddim_eta_step_(xi, eps, z, cr, crm1, prev, float(sigma[i]), ph)
+
+
+def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corrector=0, delta=0.1, ddim=False, ddim_sigma=None):
     """The guided host loop for any eps_model callable: two calls per predictor step (condition, none_like), cfg_combine, the step kernel;
     correctors as in _run_generic (the net sees none_like)."""
     T = _tables(ddpm)
@@ -178,8 +225,7 @@ def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corre
         eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
         eps = _ops.cfg_combine(torch.cat((ec, eu)).contiguous(), guidance_scale)
         if ddim:
-            _ops.ddim_step_(xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
-                            float(T["alphas_cumprod_prev"][i]))
+            _ddim_move(eps, xi, i, T, ddim_sigma, noise)
             continue
         _predictor(eps, xi, i, T, noise)
         for _ in range(n_corrector):
@@ -189,7 +235,7 @@ def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corre
 
 
 def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_fraction=1.0, noise_condition=True,
-              pad_value=-2.0, none_value=-2.0, guidance_scale=None):
+              pad_value=-2.0, none_value=-2.0, guidance_scale=None, ddim_sigma=None, walk=None):
     global _draw_counter
     xi = xT.detach().clone().float().contiguous()
     noise = None
@@ -199,9 +245,14 @@ def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_f
     else:
         seed = (seed + 0x9E3779B97F4A7C15 * (_draw_counter + 1)) & ((1 << 63) - 1)
         _draw_counter += 1
+    sched = {}
+    if getattr(ddpm, "timesteps", None) is not None or ddim_sigma is not None or walk is not None:
+        # the scheduled entry points: a respaced chain's steps in training time (an unrespaced one's: 0..Ns-1 of Ns)
+        sched = dict(timesteps=getattr(ddpm, "timesteps", None) or tuple(range(ddpm.Ns)), train_steps=int(getattr(ddpm, "base_Ns", ddpm.Ns)),
+                     ddim_sigma=ddim_sigma, walk=walk)
     engine.ddpm_sample(xi, _tables(ddpm), mode=mode, cond=cond, noise=noise, n_corrector=n_corrector, delta=float(delta),
                        tmin=ddpm.tmin, tmax=ddpm.tmax, start_fraction=float(start_fraction), noise_condition=bool(noise_condition),
-                       pad_value=float(pad_value), none_value=float(none_value), seed=seed, guidance_scale=guidance_scale)
+                       pad_value=float(pad_value), none_value=float(none_value), seed=seed, guidance_scale=guidance_scale, **sched)
     return xi
 
 
@@ -229,6 +280,9 @@ def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Con
         return _cfg_sample_fn(eps_model, ddpm, conditioning, likelihood)
     if isinstance(conditioning, Amortized):
         return _amortized_sample_fn(eps_model, ddpm, conditioning, likelihood)
+    if isinstance(conditioning, RePaint):   # (a Replacement: before it)
+        return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, walk=repaint_walk(ddpm.Ns, conditioning.jump_length,
+                                                                                                   conditioning.n_resample))
     if isinstance(conditioning, Replacement):
         return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood)
     if isinstance(conditioning, ReconstructionGuidance):
@@ -282,7 +336,7 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
     differentiable plan, which is bf16 when the model's precision is 'fp16' (use_fp16=True) or 'bf16x2' (the backward exists in fp32 and bf16
     only, UNetModel.engine); the unguided steps and correctors keep the model's precision."""
     net = getattr(eps_model, "_mi355_network", None)
-    if net is None or getattr(eps_model, "_mi355_Ns", None) != ddpm.Ns or not hasattr(net, "engine"):
+    if net is None or not _same_schedule(eps_model, ddpm) or not hasattr(net, "engine"):
         raise NotImplementedError(
             "ReconstructionGuidance differentiates through the network: pass an eps_model built by make_eps_model(network, ddpm) around "
             "a UNetModel (an arbitrary callable has no backward pass on the HIP backend)")
@@ -311,7 +365,7 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
         noise = _Noise(xi)
         n_guided = int(ddpm.Ns * conditioning.start_fraction)
         for i in reversed(range(ddpm.Ns)):
-            t = torch.full((B,), 1.0 * i / ddpm.Ns, device=xi.device, dtype=torch.float32)
+            t = torch.full((B,), ddpm.time(i), device=xi.device, dtype=torch.float32)
             update, eps = None, None
             if i < n_guided:
                 eps = deng.forward(xi, t)
@@ -341,8 +395,12 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
     return sample
 
 
-def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihood):
-    """sampling.py:209-260: overwrite the known pixels with the (noised) condition before each predictor step."""
+def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihood, walk=None):
+    """sampling.py:209-260: overwrite the known pixels with the (noised) condition before each predictor step.
+    walk (RePaint; None: the plain descent): the levels to visit, conditioning.repaint_walk; a move up re-noises the state by
+    q(x_k | x_{k-1}) (mi355_renoise_step), a move down is the replacement step of its level.  A walk without upward moves is the plain descent."""
+    if walk is not None and all(b < a for a, b in zip(walk, walk[1:])):
+        walk = None
 
     @torch.no_grad()
     def sample(xT, condition):
@@ -352,18 +410,24 @@ def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihoo
         if engine is not None:
             return _run_fast(engine, ddpm, xT, _lib.DDPM_REPLACEMENT, condition, n_corrector=conditioning.n_corrector,
                              delta=conditioning.delta, start_fraction=conditioning.start_fraction,
-                             noise_condition=conditioning.noise, pad_value=pad)
+                             noise_condition=conditioning.noise, pad_value=pad, walk=walk)
         rep = dict(condition=condition, start_fraction=conditioning.start_fraction, noise=bool(conditioning.noise), pad_value=pad)
         return _run_generic(eps_model, ddpm, xT, amortized=False, cond_pred=None, cond_corr=None, replacement=rep,
-                            n_corrector=conditioning.n_corrector, delta=conditioning.delta)
+                            n_corrector=conditioning.n_corrector, delta=conditioning.delta, walk=walk)
 
     return sample
 
 
-def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Likelihood] = None, guidance_scale=None):
+def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Likelihood] = None, guidance_scale=None, eta=0.0):
     """BUILD-DEFINED EXTENSION (no reference counterpart; BASELINE.json configs 3/5 name DDIM): deterministic
     DDIM(eta=0) on the same tables with the reference's clipped x0_hat.  sample(xT, condition=None).
-    guidance_scale (None: unguided): classifier-free guidance of eps against the none_like condition; needs a condition."""
+    guidance_scale (None: unguided): classifier-free guidance of eps against the none_like condition; needs a condition.
+    eta (0: the deterministic sampler, untouched): stochastic DDIM with sigma = ddpm.ddim_sigma(eta), one noise draw per step with i > 0;
+    eta = 1 has the ancestral step's mean and variance.  On a RespacedDDPM this is DDIM on a sub-sequence of the training steps."""
+    eta = float(eta)
+    if not (math.isfinite(eta) and eta >= 0.0):
+        raise ValueError(f"eta must be finite and >= 0, got {eta!r}")
+    sigma = ddpm.ddim_sigma(eta) if eta != 0.0 else None
 
     @torch.no_grad()
     def sample(xT, condition=None):
@@ -375,15 +439,15 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
             raise ValueError("guidance_scale needs a condition to guide towards")
         if engine is not None:
             nv = _none_value(likelihood, xT) if likelihood is not None else 0.0
-            return _run_fast(engine, ddpm, xT, _lib.DDIM, condition, none_value=nv, guidance_scale=guidance_scale)
+            return _run_fast(engine, ddpm, xT, _lib.DDIM, condition, none_value=nv, guidance_scale=guidance_scale, ddim_sigma=sigma)
         if guidance_scale is not None:
             none = likelihood.none_like(xT) if likelihood is not None else torch.zeros_like(condition)
-            return _run_generic_cfg(eps_model, ddpm, xT, cond=condition, none=none, guidance_scale=guidance_scale, ddim=True)
+            return _run_generic_cfg(eps_model, ddpm, xT, cond=condition, none=none, guidance_scale=guidance_scale, ddim=True, ddim_sigma=sigma)
         xi = xT.detach().clone().float().contiguous()
+        noise = _Noise(xi) if sigma is not None else None
         for i in reversed(range(ddpm.Ns)):
             eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i))
-            _ops.ddim_step_(xi, eps.float().contiguous(), float(T["sqrt_recip_alphas_cumprod"][i]),
-                            float(T["sqrt_recipm1_alphas_cumprod"][i]), float(T["alphas_cumprod_prev"][i]))
+            _ddim_move(eps.float().contiguous(), xi, i, T, sigma, noise)
         return process_x0(xi)
 
     return sample

@@ -102,6 +102,12 @@ class DDPMOptionsC(C.Structure):
                 ("pad_value", C.c_float), ("none_value", C.c_float), ("cond_is_none", C.c_int32), ("seed", C.c_uint64)]
 
 
+class DDPMScheduleC(C.Structure):
+    """mi355_ddpm_schedule (include/mi355_sampler.h): where the K sampling steps of respaced tables sit in training time."""
+    _fields_ = [("steps", C.POINTER(C.c_int32)), ("train_steps", C.c_int32), ("ddim_sigma", _FP), ("walk", C.POINTER(C.c_int32)),
+                ("n_walk", C.c_int32), ("renoise_a", _FP), ("renoise_b", _FP)]
+
+
 _VP, _I, _I64, _F, _U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
@@ -164,6 +170,13 @@ SIGNATURES = {
     "mi355_cfg_stage": (_I, [_VP, _VP, C.POINTER(_VP), _FP, _I, _I64, _F, _VP, _I64, _I, _VP, _VP, _VP]),
     "mi355_ddpm_cfg_step": (_I, [_VP, _VP, _VP, _F, _VP, _I64, _F, _F, _F, _F, _F, _I, _U64, _U64, _I64, _VP]),
     "mi355_ddim_cfg_step": (_I, [_VP, _VP, _F, _VP, _I64, _F, _F, _F, _I64, _VP]),
+    "mi355_ddim_eta_step": (_I, [_VP, _VP, _VP, _F, _F, _F, _F, _I, _U64, _U64, _I64, _VP]),
+    "mi355_ddim_eta_cfg_step": (_I, [_VP, _VP, _VP, _F, _VP, _I64, _F, _F, _F, _F, _I, _U64, _U64, _I64, _VP]),
+    "mi355_renoise_step": (_I, [_VP, _VP, _F, _F, _I, _U64, _U64, _I64, _VP]),
+    "mi355_ddpm_sample_sched": (_I, [_VP, _VP, _I, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), C.POINTER(DDPMScheduleC), _VP, _I64, _I, _VP,
+                                     _I64, _VP]),
+    "mi355_ddpm_cfg_sample_sched": (_I, [_VP, _VP, _I, _VP, _VP, _I, _F, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC),
+                                         C.POINTER(DDPMScheduleC), _VP, _I64, _I, _VP, _I64, _VP]),
     "mi355_rk_sqnorm": (_I, [_VP, _VP, _VP, _VP, _F, _F, _I64, _VP, _VP]),
     "mi355_rk_interp": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _F, _F, _I64, _VP]),
     "mi355_op_workspace_bytes": (_I64, [_I, _I, _I]),

@@ -565,8 +565,12 @@ class UNetEngine:
     def ddpm_sample(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], *, mode: int, cond: Optional[torch.Tensor] = None,
                     noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0,
                     noise_condition=True, pad_value=-2.0, none_value=-2.0, seed=0, guidance_scale=None, y: Optional[torch.Tensor] = None,
-                    null_label: Optional[int] = None):
+                    null_label: Optional[int] = None, timesteps=None, train_steps=None, ddim_sigma=None, walk=None):
         """In-place reverse-denoising loop.  tables: name -> CPU fp32 tensor [Ns] (DDPM buffers).
+        timesteps / train_steps (both or neither; None: exactly the unscheduled calls): `tables` are the K respaced tables of a RespacedDDPM, step k
+        sits at training index timesteps[k] of train_steps (mi355_ddpm_sample_sched / mi355_ddpm_cfg_sample_sched).  With them, ddim_sigma ([K] floats,
+        DDIM mode: the DDIM(eta) step) and walk (levels K, ..., 0 moving by +-1, e.g. conditioning.repaint_walk; upward moves re-noise with
+        sqrt(alphas), sqrt(betas) of `tables`) may be given.
         guidance_scale (a float or a [B] tensor; None: mi355_ddpm_sample, untouched): classifier-free guidance of the predictor's eps
         (mi355_ddpm_cfg_sample; Amortized mode, or DDIM with a condition, on a 2C-input net), eps_u from the none_value-filled condition and, with
         y (class labels [B]), null_label (default: the last class).  A batch beyond cfg_batch() runs in slices (Philox: seed + slice index)."""
@@ -575,6 +579,7 @@ class UNetEngine:
             raise ValueError("condition must have the shape of x")
         if guidance_scale is None and y is not None:
             raise NotImplementedError("ddpm_sample takes class labels on the guided path only (guidance_scale=)")
+        sched = self._ddpm_schedule(tables, timesteps, train_steps, ddim_sigma, walk)
         if guidance_scale is not None:
             if mode not in (_lib.DDPM_AMORTIZED, _lib.DDIM):
                 raise NotImplementedError("guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement are refused)")
@@ -587,7 +592,8 @@ class UNetEngine:
                 self._ddpm_cfg_call(xs, tables, mode, cond if whole or cond is None else cond[lo:hi].contiguous(),
                                     _cut(lab, lo, hi), nl, w, _cut(wt, lo, hi),
                                     noise if whole or noise is None else noise[:, lo:hi].contiguous(),
-                                    dict(n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, none_value=none_value, seed=(seed + i) % 2 ** 64))
+                                    dict(n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, none_value=none_value, seed=(seed + i) % 2 ** 64),
+                                    **({} if sched is None else {"sched": sched}))
                 if not whole:
                     x[lo:hi] = xs
             return x
@@ -601,6 +607,11 @@ class UNetEngine:
             ndraws = noise.shape[0]
         self._fwd_state = None
         ws, wsb = self.workspace(B)
+        if sched is not None:
+            check(self.L.mi355_ddpm_sample_sched(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
+                                                 C.byref(tb), C.byref(opt), C.byref(sched[0]), self._chk(noise, "noise") if noise is not None else None,
+                                                 ndraws, B, ws, wsb, self._stream()), "mi355_ddpm_sample_sched")
+            return x
         check(self.L.mi355_ddpm_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
                                        C.byref(tb), C.byref(opt), self._chk(noise, "noise") if noise is not None else None, ndraws, B,
                                        ws, wsb, self._stream()), "mi355_ddpm_sample")
@@ -623,13 +634,54 @@ class UNetEngine:
         tb.Ns = Ns
         return tb, keep
 
-    def _ddpm_cfg_call(self, x, tables, mode, cond, lab, null_label, w, wt, noise, o):
-        """One mi355_ddpm_cfg_sample call (a batch within cfg_batch())."""
+    @staticmethod
+    def _ddpm_schedule(tables, timesteps, train_steps, ddim_sigma, walk):
+        """-> None (no schedule given), or (mi355_ddpm_schedule, the host arrays it points into)."""
+        if timesteps is None and train_steps is None:
+            if ddim_sigma is not None or walk is not None:
+                raise ValueError("ddim_sigma and walk belong to a scheduled call: give timesteps and train_steps (DDPM.respace)")
+            return None
+        if timesteps is None or train_steps is None:
+            raise ValueError("timesteps and train_steps go together")
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        sd = _lib.DDPMScheduleC()
+        K = len(timesteps)
+        if K != tables["alphas_cumprod_prev"].numel():
+            raise ValueError("timesteps must have one entry per row of the (respaced) tables")
+        keep = [(C.c_int32 * max(1, K))(*[int(t) for t in timesteps])]
+        sd.steps, sd.train_steps = C.cast(keep[0], ip), int(train_steps)
+        if ddim_sigma is not None:
+            sg = torch.as_tensor(ddim_sigma, dtype=torch.float32).detach().to("cpu").contiguous()
+            if sg.numel() != K:
+                raise ValueError("ddim_sigma must have one entry per step")
+            keep.append(sg)
+            sd.ddim_sigma = C.cast(sg.data_ptr(), fp)
+        if walk is not None:
+            wl = (C.c_int32 * max(1, len(walk)))(*[int(v) for v in walk])
+            keep.append(wl)
+            sd.walk, sd.n_walk = C.cast(wl, ip), len(walk)
+            if any(b > a for a, b in zip(walk, list(walk)[1:])):   # upward moves: q(x_k | x_{k-1}) = sqrt(alphas_k) x + sqrt(betas_k) z
+                ra = torch.sqrt(tables["alphas"].detach().to("cpu", torch.float32)).contiguous()
+                rb = torch.sqrt(tables["betas"].detach().to("cpu", torch.float32)).contiguous()
+                keep += [ra, rb]
+                sd.renoise_a, sd.renoise_b = C.cast(ra.data_ptr(), fp), C.cast(rb.data_ptr(), fp)
+        return sd, keep
+
+    def _ddpm_cfg_call(self, x, tables, mode, cond, lab, null_label, w, wt, noise, o, sched=None):
+        """One mi355_ddpm_cfg_sample (sched: mi355_ddpm_cfg_sample_sched) call (a batch within cfg_batch())."""
         B, Cx = x.shape[:2]
         tb, keep = self._ddpm_tables(tables)
         opt = _lib.DDPMOptionsC(mode, o["n_corrector"], o["delta"], o["tmin"], o["tmax"], 1.0, 1, -2.0, o["none_value"], int(cond is None), o["seed"])
         self._fwd_state = None
         ws, wsb = self._workspace_sized("mi355_ddpm_cfg_workspace_bytes", B)
+        if sched is not None:
+            check(self.L.mi355_ddpm_cfg_sample_sched(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
+                                                     C.c_void_p(lab.data_ptr()) if lab is not None else None, int(null_label), float(w),
+                                                     self._chk(wt, "guidance_scale") if wt is not None else None, C.byref(tb), C.byref(opt),
+                                                     C.byref(sched[0]), self._chk(noise, "noise") if noise is not None else None,
+                                                     noise.shape[0] if noise is not None else 0, B, ws, wsb, self._stream()),
+                  "mi355_ddpm_cfg_sample_sched")
+            return
         check(self.L.mi355_ddpm_cfg_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
                                            C.c_void_p(lab.data_ptr()) if lab is not None else None, int(null_label), float(w),
                                            self._chk(wt, "guidance_scale") if wt is not None else None, C.byref(tb), C.byref(opt),

@@ -102,6 +102,44 @@ class Ops:
         check(_lib.lib().mi355_ddim_step(_req(x, "x"), _req(eps, "eps"), c_recip, c_recipm1, acp_prev, x.numel(), _stream()))
         return x
 
+    def ddim_eta_step_(self, x, eps, z, c_recip, c_recipm1, acp_prev, sigma, philox=None):
+        """DDIM(eta) step in place: ddim_step_'s x0 and e2, x <- sqrt(acp_prev) x0 + sqrt(max(1 - acp_prev - sigma^2, 0)) e2 + sigma z.
+        z / philox as in ddpm_step_; both None = no noise term (sigma = 0 then gives ddim_step_'s bits)."""
+        _same(x, eps, "x", "eps")
+        zp = _req(z, "z") if z is not None else None
+        if z is not None:
+            _same(x, z, "x", "z")
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_ddim_eta_step(_req(x, "x"), _req(eps, "eps"), zp, c_recip, c_recipm1, acp_prev, float(sigma),
+                                             int(philox is not None and z is None), seed, off, x.numel(), _stream()), "mi355_ddim_eta_step")
+        return x
+
+    def ddim_eta_cfg_step_(self, x2, eps2, z, w, c_recip, c_recipm1, acp_prev, sigma, philox=None):
+        """ddim_eta_step_ on the guided eps, operands as ddpm_cfg_step_."""
+        _same(x2, eps2, "x2", "eps2")
+        if x2.shape[0] % 2:
+            raise ValueError("x2 holds the state twice: an even leading size")
+        B = x2.shape[0] // 2
+        n = x2.numel() // 2
+        if z is not None and z.numel() != n:
+            raise ValueError("z must have the B-image state's size")
+        wf, wp, keep = self._cfg_w(w, B)
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_ddim_eta_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _req(z, "z") if z is not None else None, wf, wp,
+                                                 n // B if B else 1, c_recip, c_recipm1, acp_prev, float(sigma),
+                                                 int(philox is not None and z is None), seed, off, n, _stream()), "mi355_ddim_eta_cfg_step")
+        return x2
+
+    def renoise_(self, x, z, a, b, philox=None):
+        """The forward move q(x_k | x_{k-1}) in place: x <- a x + b z (a = sqrt(alphas_k), b = sqrt(betas_k)); z / philox as in ddpm_step_."""
+        zp = _req(z, "z") if z is not None else None
+        if z is not None:
+            _same(x, z, "x", "z")
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_renoise_step(_req(x, "x"), zp, float(a), float(b), int(philox is not None and z is None), seed, off, x.numel(),
+                                            _stream()), "mi355_renoise_step")
+        return x
+
     def replace_mask_(self, x, cond, z, pad_value, noisy, sa, sb, philox=None):
         _same(x, cond, "x", "condition")
         zp = _req(z, "z") if z is not None else None

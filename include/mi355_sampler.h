@@ -49,7 +49,9 @@ extern "C" {
  * warp-specialised conv carries a ResBlock's 1x1 skip conv, off in mi355_debug_defaults; bits 2 and 8.. for tests) and mi355_conv_extras gained the
  * stat_* fields at its end, read only behind MI355_CONV_EXTRAS_STATS in route[3] (a caller built against the shorter struct is unaffected); then
  * mi355_image_metrics (per-sample MSE, PSNR and SSIM of the evaluation loop; a new symbol only); then mi355_conv2d_fwd (one forward conv as a test
- * op: prologue given directly, route always reported, the first conv's NCHW read and the out conv's Euler update; a new symbol only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * op: prologue given directly, route always reported, the first conv's NCHW read and the out conv's Euler update; a new symbol only); then respaced DDPM sampling:
+ * mi355_ddpm_sample_sched, mi355_ddpm_cfg_sample_sched and the ops mi355_ddim_eta_step, mi355_ddim_eta_cfg_step, mi355_renoise_step (new symbols
+ * and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -390,6 +392,43 @@ int mi355_ddpm_cfg_sample(mi355_unet* net, float* x, int channels, const float* 
                           const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Sampling a DDPM net on a sub-sequence of the steps it was trained with (improved-DDPM timestep respacing, DDIM sub-sequences with eta, RePaint
+ * resampling; no reference counterpart).  The scheduled entry points run the loop of their unscheduled namesakes with `tables` holding the K
+ * respaced per-step scalars (tables->Ns = K; DDPM.respace builds them) and this description of where the K sampling steps sit in training time: */
+typedef struct mi355_ddpm_schedule {
+  const int32_t* steps;      /* host int32[K], K = tables->Ns: training index tau_k of sampling step k, strictly increasing, in [0, train_steps) */
+  int32_t train_steps;       /* the net is evaluated at (float)tau_k / (float)train_steps */
+  const float* ddim_sigma;   /* MI355_DDIM only: host float[K]; NULL = the deterministic step */
+  const int32_t* walk;       /* host int32[n_walk] levels, or NULL = K, K-1, ..., 0 */
+  int32_t n_walk;
+  const float* renoise_a;    /* host float[K]: sqrt(alphas'_k), sqrt(betas'_k); needed iff walk has an upward move */
+  const float* renoise_b;
+} mi355_ddpm_schedule;
+/* The embedding rows are those of the K times tau_k / train_steps; row k is selected whenever step k is evaluated, revisits included.
+ * A level L in [0, K] is the state before step L - 1 is applied: K is pure noise, 0 the result.  walk starts at K, ends at 0 and moves by +-1:
+ *   L -> L - 1 : the unscheduled loop's body for i = L - 1 (the replacement paste if i < int(K * start_fraction), the evaluation, the predictor, the
+ *                correctors, whose dt is (tmax - tmin) / K); launches as in the unscheduled entry point for the same mode;
+ *   L -> L + 1 : one mi355_renoise_step with renoise_a[L], renoise_b[L].
+ * ddim_sigma (MI355_DDIM): step i is mi355_ddim_eta_step (guided entry: mi355_ddim_eta_cfg_step) with ddim_sigma[i].
+ * Noise draws are numbered in loop order, one per launch that takes noise, as in the unscheduled loop (injected: draw d = noise[d]; Philox: offset
+ * d * n_al): a noised replacement paste, a predictor with i > 0, every corrector, every upward move; with ddim_sigma every DDIM step with i > 0
+ * (step 0 has acp_prev = 1, hence sigma = 0, and draws none); without ddim_sigma a DDIM step draws none.  A plain descent with a noised paste in
+ * its first P = int(K * start_fraction) steps therefore consumes P + (K - 1) + K * n_corrector draws; a walk with D downward moves, D0 of them
+ * to level 0, Dp of them pasting, and U upward moves consumes Dp + (D - D0) + D * n_corrector + U.  Too few injected draws: -2, "injected noise
+ * exhausted", at the launch that misses one.
+ * With steps = 0..Ns-1, train_steps = Ns, the net's own tables, no ddim_sigma and no walk the result is bit-identical to the unscheduled entry point's.
+ * The guided entry refuses a walk with upward moves (the mirror half is not built for re-noising).  Workspaces: those of the unscheduled entry points.
+ * Errors beyond theirs, all MI355_ERR_ARG, all before any launch, each naming its argument: sched NULL; steps NULL, not strictly increasing or
+ * outside [0, train_steps); train_steps < 1; ddim_sigma in a mode other than MI355_DDIM; a negative or non-finite ddim_sigma; a walk that does not
+ * start at K, does not end at 0 or moves by anything but +-1; upward moves without renoise_a / renoise_b.  Sample quality of respaced, stochastic-DDIM
+ * and RePaint sampling is untested (no trained checkpoint is at hand); the arithmetic is tested against an fp64 restatement. */
+int mi355_ddpm_sample_sched(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tables,
+                            const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched, const float* noise, int64_t n_noise_draws, int batch,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int mi355_ddpm_cfg_sample_sched(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w,
+                                const float* w_dev, const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                                const float* noise, int64_t n_noise_draws, int batch, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Training-free in-painting / super-resolution with an UNCONDITIONAL flow-matching net (no reference counterpart: the reference has the two
  * methods for diffusion only, AD/image_diffusion/sampling.py:136-260).  t runs from 0 (noise) to 1 (data), the net's output is the velocity
  * v(t, x), and the data estimate of a straight-path flow is x1_hat = x + (1 - t) v.  One Euler step per interval of t_span; step k, with
@@ -560,6 +599,21 @@ int mi355_ddpm_cfg_step(float* x, const float* eps, const float* z, float w, con
                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream);
 int mi355_ddim_cfg_step(float* x, const float* eps, float w, const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1, float acp_prev,
                         int64_t n, void* stream);
+/* DDIM(eta) step (Song et al. 2021, eq. 12; build-defined extension) with the reference's clipped x0_hat, elementwise over n values:
+ *   x0 = clip(c_recip*x - c_recipm1*eps, -1, 1);  e2 = (c_recip*x - x0) / c_recipm1;
+ *   x <- sqrtf(acp_prev) * x0 + sqrtf(fmaxf(1 - acp_prev - sigma*sigma, 0)) * e2 + sigma * z
+ * (the two square roots on the host, sigma*sigma and each difference rounded to fp32).  z, use_philox, seed, offset as in mi355_ddpm_step; neither z
+ * nor use_philox: the noise term is not added, and sigma = 0 then gives the bits of mi355_ddim_step.  sigma = eta * sqrt((1 - acp_prev) / (1 - acp))
+ * * sqrt(1 - acp / acp_prev) (DDPM.ddim_sigma): eta = 1 is the ancestral step's mean and variance.  A negative or non-finite sigma: MI355_ERR_ARG.
+ * ddim_eta_cfg_step: its classifier-free-guided form, operands and both-halves store as mi355_ddim_cfg_step, z and the Philox stream indexed by the
+ * element of the n-element state. */
+int mi355_ddim_eta_step(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int use_philox,
+                        uint64_t seed, uint64_t offset, int64_t n, void* stream);
+int mi355_ddim_eta_cfg_step(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t elems_per_image, float c_recip,
+                            float c_recipm1, float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream);
+/* Forward move q(x_k | x_{k-1}) of a (respaced) chain, what a RePaint walk (Lugmayr et al. 2022) does on its way back up:
+ *   x <- a*x + b*z,   a = sqrt(alphas_k), b = sqrt(betas_k)   (two rounded products, one sum; noise arguments as in mi355_ddpm_step) */
+int mi355_renoise_step(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream);
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream);
 int mi355_rk_interp(float* out, const float* y0, const float* y1, const float* y_mid, const float* f0, const float* f1, float dt, float x,
