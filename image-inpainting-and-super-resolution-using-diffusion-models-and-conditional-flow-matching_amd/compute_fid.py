@@ -50,14 +50,15 @@ def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integrat
                    guidance_scale=None, null_label=None):
     """guidance_scale (None: unguided, the reference's call): classifier-free guidance on a class-conditional net; each image's label is drawn
     uniformly from the classes other than null_label (default: the last class) by the batch's seeded generator.
-    integration_method: "euler", "dopri5", or a fixed-step Runge-Kutta name ("midpoint", "heun2", "rk4", "rk4_38": mi355.ode.TABLEAUS).
+    integration_method: "euler", "dopri5", a fixed-step Runge-Kutta name ("midpoint", "heun2", "rk4", "rk4_38": mi355.ode.TABLEAUS) or an
+    Adams-Bashforth name ("ab2", "ab3", "ab4": mi355.ode.AB_SOLVERS).
     The fixed-step methods integrate over linspace(0, 1, integration_steps + 1) like the Euler branch - a build-defined reading: the
     reference forwards any name but "euler" to odeint with the two-point grid linspace(0, 1, 2), which for a fixed-grid method is ONE
     step over [0, 1]."""
-    from mi355.ode import RK_SOLVERS as rk
+    from mi355.ode import AB_SOLVERS as ab, RK_SOLVERS as rk
 
-    if integration_method not in ("euler", "dopri5") + rk:
-        raise NotImplementedError(f"--integration_method must be euler, dopri5 or one of {rk}")
+    if integration_method not in ("euler", "dopri5") + rk + ab:
+        raise NotImplementedError(f"--integration_method must be euler, dopri5 or one of {rk + ab}")
     device = torch.device(device)
     calls = [0]
     guide = {}
@@ -89,6 +90,9 @@ def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integrat
             elif integration_method in rk:
                 t_span = torch.linspace(0, 1, integration_steps + 1).tolist()
                 _, _, img = new_net.engine(device).cfm_rk(x, t_span, integration_method, want_u8=True, **kw)
+            elif integration_method in ab:   # Adams-Bashforth on the same grid: one evaluation per step after the start steps
+                t_span = torch.linspace(0, 1, integration_steps + 1).tolist()
+                _, _, img = new_net.engine(device).cfm_ab(x, t_span, integration_method, want_u8=True, **kw)
             else:  # odeint(new_net, x, linspace(0,1,2), rtol=tol, atol=tol, method="dopri5")  (cifar10/compute_fid.py:80-85)
                 from mi355.ode import odeint_dopri5
                 from mi355.ops import default_ops

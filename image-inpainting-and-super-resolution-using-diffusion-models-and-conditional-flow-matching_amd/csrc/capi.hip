@@ -285,6 +285,13 @@ int mi355_ddim_eta_cfg_step(float* x, const float* eps, const float* z, float w,
 int mi355_renoise_step(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
   return renoise_step_launch(x, z, a, b, use_philox, seed, offset, n, S(stream));
 }
+int mi355_dpmpp_step(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, void* stream) {
+  return dpmpp_step_launch(x, eps, hist, c_recip, c_recipm1, cx, c0, c1, n, S(stream));
+}
+int mi355_dpmpp_cfg_step(float* x, const float* eps, float* hist, float w, const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1,
+                         float cx, float c0, float c1, int64_t n, void* stream) {
+  return dpmpp_cfg_step_launch(x, eps, hist, w, w_dev, elems_per_image, c_recip, c_recipm1, cx, c0, c1, n, S(stream));
+}
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream) {
   return rk_sqnorm_launch(a, sub, b, b2, atol, rtol, n, out, S(stream));

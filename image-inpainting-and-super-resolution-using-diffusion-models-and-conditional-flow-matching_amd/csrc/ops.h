@@ -311,6 +311,11 @@ int ddim_eta_step_launch(float* x, const float* eps, const float* z, float c_rec
 int ddim_eta_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
                              float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int renoise_step_launch(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
+// DPM-Solver++ multistep step on the clipped x0_hat: D = clip(c_recip x - c_recipm1 eps); x <- cx x + c0 D + c1 hist; hist <- D (hist: not read when
+// c1 == 0, not written when null), and its guided form (operands as ddim_cfg_step_launch, hist [n])
+int dpmpp_step_launch(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s);
+int dpmpp_cfg_step_launch(float* x, const float* eps, float* hist, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float cx,
+                          float c0, float c1, int64_t n, hipStream_t s);
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb,
                         int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int clip_launch(float* x, float lo, float hi, int64_t n, hipStream_t s);

@@ -25,8 +25,9 @@ struct Walk {
 struct Scratch { float* t; float* v; float* none; float* tsteps; float* embtab; float* xstate; char* unet_ws; int64_t unet_bytes; };
 // classifier-free guidance: duplicated state x | x, condition | none_value, labels | null label (the last two only where the net takes them)
 struct CfgTail { float* x2; float* cond2; int32_t* labels2; };
-// fixed-step Runge-Kutta: the stage derivatives k_1..k_s and the stage state y_i, each a state at the evaluation batch
-struct RkBufs { float* k[4]; float* ystage; };
+// fixed-step Runge-Kutta: the stage derivatives k_1..k_s and the stage state y_i, each a state at the evaluation batch.  Adams-Bashforth: the ring
+// of `order` stored velocities, then the start method's stages 2..s (order + s - 1 <= 7 buffers)
+struct RkBufs { float* k[7]; float* ystage; };
 // training-free in-painting / super-resolution of a flow (mi355_cfm_recon_sample): the call's initial state (the noise end of the straight path the
 // "coupled" replacement pastes along), the seed's two outputs and the U-Net VJP, each a state; the low-res residual [B, C, h_low, w_low]
 struct ReconDims { int h_low, w_low; };
@@ -127,6 +128,10 @@ struct Guide {
   bool on = false; float w = 0.f; const float* w_dev = nullptr; int64_t per = 0;
   int stage(float* out, const float* y0, const float* const* kp, const float* cf, int nk, int64_t n, float* copy_out, uint8_t* u8_out, hipStream_t s) const {
     return on ? cfg_stage_launch(out, y0, kp, cf, nk, n, w, w_dev, per, 1, copy_out, u8_out, s) : rk_stage_launch(out, y0, kp, cf, nk, n, copy_out, u8_out, s);
+  }
+  int dpmpp(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s) const {
+    return on ? dpmpp_cfg_step_launch(x, eps, hist, w, w_dev, per, c_recip, c_recipm1, cx, c0, c1, n, s)
+              : dpmpp_step_launch(x, eps, hist, c_recip, c_recipm1, cx, c0, c1, n, s);
   }
   int ddim(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s) const {
     return on ? ddim_cfg_step_launch(x, eps, w, w_dev, per, c_recip, c_recipm1, acp_prev, n, s) : ddim_step_launch(x, eps, c_recip, c_recipm1, acp_prev, n, s);
@@ -251,17 +256,25 @@ int gather_row(const float* row, int count, float dt, float* const* kbuf, const 
   return nk;
 }
 
+// Adams-Bashforth over the loop below (mi355_cfm_ab_sample): steps k >= order - 1 take x_{k+1} = x_k + sum_j w[k * order + j] v_{k-j} (the step
+// length inside the weight) from a ring of `order` stored velocities, v_k in slot k % order; the order - 1 steps before them are Runge-Kutta steps
+// whose first stage (c_1 == 0: v(t_k, x_k) itself) goes straight into slot k.
+struct AbPlan { int order; const float* w; };
+
 // n_steps >= 1 steps of `state` (n elements per half: the whole state, or each half of a guided sampler's x | x), the network evaluated at
 // batch evalB on cond / labels as given.  *step_launches: every launch of the last step (evaluations, stage launches, fill launches).
+// ab (null: a Runge-Kutta step per interval): the tableau is the start method of an Adams-Bashforth sampler.
 int cfm_rk_loop(mi355_unet* net, const Scratch& sc, const RkBufs& rk, const Guide& guide, float* state, int x_channels, const float* cond, int cond_channels,
                 const int32_t* labels, const float* t_span_host, int n_steps, int stages, const float* a_host, const float* b_host, const float* c_host,
-                float* traj, uint8_t* u8_out, int evalB, int64_t n, hipStream_t s, int64_t* step_launches) {
-  // every evaluation time is known in advance: one embedding row (block of num_classes rows with labels) per (step, stage)
-  std::vector<float> te((size_t)n_steps * stages);
-  for (int k = 0; k < n_steps; ++k)
+                float* traj, uint8_t* u8_out, int evalB, int64_t n, hipStream_t s, int64_t* step_launches, const AbPlan* ab = nullptr) {
+  // every evaluation time is known in advance: one embedding row (block of num_classes rows with labels) per (step, stage), one per multistep step
+  const int n_rk = ab && ab->order - 1 < n_steps ? ab->order - 1 : n_steps;
+  std::vector<float> te((size_t)n_rk * stages + (size_t)(n_steps - n_rk));
+  for (int k = 0; k < n_rk; ++k)
     for (int i = 0; i < stages; ++i) te[(size_t)k * stages + i] = rk_stage_time(t_span_host[k], t_span_host[k + 1], c_host[i]);
+  for (int k = n_rk; k < n_steps; ++k) te[(size_t)n_rk * stages + (size_t)(k - n_rk)] = t_span_host[k];
   EvalEmb emb;
-  if (int rc = emb.init(net, sc, te.data(), (int64_t)n_steps * stages, labels != nullptr, true, s)) return rc;
+  if (int rc = emb.init(net, sc, te.data(), (int64_t)te.size(), labels != nullptr, true, s)) return rc;
   UnetRun run = uniform_t_run();   // no euler_x: the last conv stores v (conv_edge bit 3 stays out of these evaluations)
   run.labels = labels;
   const float* kp[4]; float cf[4];
@@ -269,20 +282,34 @@ int cfm_rk_loop(mi355_unet* net, const Scratch& sc, const RkBufs& rk, const Guid
   for (int k = 0; k < n_steps; ++k) {
     const float dt = t_span_host[k + 1] - t_span_host[k];
     *step_launches = 0;
+    float* const out_traj = traj ? traj + (size_t)(k + 1) * n : nullptr;
+    uint8_t* const out_u8 = k + 1 == n_steps ? u8_out : nullptr;
+    if (k >= n_rk) {   // one evaluation into the oldest slot, one launch over the non-zero weights (a row without one was refused)
+      if ((rc = emb.select(run, (size_t)n_rk * stages + (size_t)(k - n_rk), evalB, s, step_launches))) return rc;
+      if ((rc = unet_forward(net, state, x_channels, cond, cond_channels, sc.t, rk.k[k % ab->order], evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+      *step_launches += net->last_launches + 1;
+      int nk = 0;
+      for (int j = 0; j < ab->order; ++j)
+        if (const float wj = ab->w[(size_t)k * ab->order + j]; wj != 0.f) { kp[nk] = rk.k[(k - j) % ab->order]; cf[nk] = wj; ++nk; }
+      if ((rc = guide.stage(state, state, kp, cf, nk, n, out_traj, out_u8, s))) return rc;
+      continue;
+    }
+    float* kbuf[4];   // the stage derivatives: Runge-Kutta k_1..k_s; a start step: ring slot k, then the buffers behind the ring
+    for (int i = 0; i < stages; ++i) kbuf[i] = !ab ? rk.k[i] : (i == 0 ? rk.k[k] : rk.k[ab->order + i - 1]);
     for (int i = 0; i < stages; ++i) {
       // y_i = state + sum_{j<i} (dt * a_ij) k_j over the non-zero a_ij; none: the stage reads the state itself
       const float* yin = state;
-      if (const int nk = gather_row(a_host + (size_t)i * stages, i, dt, rk.k, kp, cf)) {
+      if (const int nk = gather_row(a_host + (size_t)i * stages, i, dt, kbuf, kp, cf)) {
         if ((rc = guide.stage(rk.ystage, state, kp, cf, nk, n, nullptr, nullptr, s))) return rc;
         yin = rk.ystage; ++*step_launches;
       }
       if ((rc = emb.select(run, (size_t)k * stages + i, evalB, s, step_launches))) return rc;
-      if ((rc = unet_forward(net, yin, x_channels, cond, cond_channels, sc.t, rk.k[i], evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+      if ((rc = unet_forward(net, yin, x_channels, cond, cond_channels, sc.t, kbuf[i], evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
       *step_launches += net->last_launches;
     }
     // the step's update, in place, with the trajectory slot and (last step) the image bytes from the same launch; nk >= 1: an all-zero b was refused
-    const int nk = gather_row(b_host, stages, dt, rk.k, kp, cf);
-    if ((rc = guide.stage(state, state, kp, cf, nk, n, traj ? traj + (size_t)(k + 1) * n : nullptr, k + 1 == n_steps ? u8_out : nullptr, s))) return rc;
+    const int nk = gather_row(b_host, stages, dt, kbuf, kp, cf);
+    if ((rc = guide.stage(state, state, kp, cf, nk, n, out_traj, out_u8, s))) return rc;
     ++*step_launches;
   }
   return 0;
@@ -310,6 +337,11 @@ struct LoopSched {
   int n_walk = 0;
   const float* renoise_a = nullptr;    // an upward move L -> L+1: x <- renoise_a[L] x + renoise_b[L] z
   const float* renoise_b = nullptr;
+  // MI355_DDIM, the multistep entry points: step i is the DPM-Solver++ step x <- ms_cx[i] x + ms_c0[i] D + ms_c1[i] hist, hist <- D
+  const float* ms_cx = nullptr;
+  const float* ms_c0 = nullptr;
+  const float* ms_c1 = nullptr;
+  float* hist = nullptr;               // the previous step's data prediction (n elements, behind the entry point's workspace)
 };
 // emb: row i = the evaluation of step i (ddpm_times(Ns), or a schedule's tau_i / train_steps), selected whenever step i runs, revisits included.
 int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const DdpmLoop& a, const LoopSched& ls, int channels, const mi355_ddpm_tables* tb,
@@ -342,6 +374,8 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     run_corr.emb_row = run.emb_row;
     if ((rc = unet_forward(net, x, channels, a.cond_pred, channels, sc.t, sc.v, a.evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
     if (mode == MI355_DDIM) {
+      if (ls.ms_cx)
+        return a.guide.dpmpp(x, sc.v, ls.hist, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], ls.ms_cx[i], ls.ms_c0[i], ls.ms_c1[i], n, s);
       if (!ls.ddim_sigma)
         return a.guide.ddim(x, sc.v, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i], n, s);
       const float* z = nullptr; int ph = 0; uint64_t off = 0;   // step 0 has acp_prev = 1: no noise term, no draw
@@ -407,6 +441,34 @@ int check_schedule(const char* who, const mi355_ddpm_tables* tb, const mi355_ddp
   MI355_REQUIRE(!up || (sd->renoise_a && sd->renoise_b), -1, f + "walk has upward moves: renoise_a and renoise_b are needed");
   ls.walk = sd->walk; ls.n_walk = sd->n_walk; ls.renoise_a = sd->renoise_a; ls.renoise_b = sd->renoise_b;
   return 0;
+}
+// Every refusal of a mi355_multistep_schedule, before any launch, each naming its argument; sd: its steps as a mi355_ddpm_schedule (for sched_times).
+int check_multistep(const char* who, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_multistep_schedule* ms, bool guided,
+                    mi355_ddpm_schedule& sd, LoopSched& ls) {
+  const std::string f = std::string(who) + ": ";
+  MI355_REQUIRE(ms, -1, f + "msched is null");
+  MI355_REQUIRE(opt->mode == MI355_DDIM, -1, f + "opt->mode must be MI355_DDIM (the multistep solver is deterministic and works on the DDIM form)");
+  sd = mi355_ddpm_schedule();
+  sd.steps = ms->steps; sd.train_steps = ms->train_steps;
+  if (int rc = check_schedule(who, tb, opt, &sd, guided, ls)) return rc;
+  const int K = tb->Ns;
+  MI355_REQUIRE(K <= 0 || ms->cx, -1, f + "cx is null");
+  MI355_REQUIRE(K <= 0 || ms->c0, -1, f + "c0 is null");
+  MI355_REQUIRE(K <= 0 || ms->c1, -1, f + "c1 is null");
+  for (int k = 0; k < K; ++k) {
+    MI355_REQUIRE(std::isfinite(ms->cx[k]), -1, f + "cx must be finite");
+    MI355_REQUIRE(std::isfinite(ms->c0[k]), -1, f + "c0 must be finite");
+    MI355_REQUIRE(std::isfinite(ms->c1[k]), -1, f + "c1 must be finite");
+  }
+  MI355_REQUIRE(K <= 0 || ms->c1[K - 1] == 0.f, -1, f + "c1[K-1] must be 0: the first step run has no history to read");
+  ls.ms_cx = ms->cx; ls.ms_c0 = ms->c0; ls.ms_c1 = ms->c1;
+  return 0;
+}
+// the history buffer of the multistep entry points: one state behind the unscheduled entry point's workspace
+inline int64_t multistep_hist_offset(const mi355_unet* net, int batch, bool guided) { return (int64_t)al256((size_t)layout_bytes(net, batch, guided, 0)); }
+inline int64_t multistep_bytes(const mi355_unet* net, int batch, bool guided) {
+  const size_t hw = (size_t)net->cfg.image_size * net->cfg.image_size;
+  return multistep_hist_offset(net, batch, guided) + (int64_t)al256((size_t)batch * net->cfg.out_channels * hw * 4);
 }
 std::vector<float> sched_times(int K, const mi355_ddpm_schedule* sd) {   // evaluation k = step k: network(x, (float)tau_k / (float)train_steps)
   std::vector<float> th((size_t)(K > 0 ? K : 0));
@@ -625,6 +687,125 @@ int mi355_ddpm_cfg_sample_sched(mi355_unet* net, float* x, int channels, const f
   if (int rc = check_schedule("ddpm_cfg_sample_sched", tb, opt, sched, true, ls)) return rc;
   return ddpm_cfg_sample_run("ddpm_cfg_sample_sched", net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, sched_times(tb->Ns, sched), ls,
                              noise, n_noise_draws, batch, workspace, workspace_bytes, stream);
+}
+
+int64_t mi355_ddpm_multistep_workspace_bytes(const mi355_unet* net, int batch, int guided) {
+  if (!net || batch <= 0) { mi355_set_error("ddpm_multistep_workspace_bytes: bad argument"); return -1; }
+  return multistep_bytes(net, batch, guided != 0);
+}
+
+int mi355_ddpm_multistep_sample(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt,
+                                const mi355_multistep_schedule* msched, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(tb && opt, -1, "ddpm_multistep_sample: tables or opt is null");
+  mi355_ddpm_schedule sd; LoopSched ls;   // the schedule's refusals need no handle
+  if (int rc = check_multistep("ddpm_multistep_sample", tb, opt, msched, false, sd, ls)) return rc;
+  MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_multistep_sample: bad argument (net, x, workspace, batch)");
+  MI355_REQUIRE(workspace_bytes >= multistep_bytes(net, batch, false), -2, "ddpm_multistep_sample: workspace too small");
+  ls.hist = reinterpret_cast<float*>(static_cast<char*>(workspace) + multistep_hist_offset(net, batch, false));
+  if (int rc = ddpm_sample_run("ddpm_multistep_sample", net, x, channels, cond, tb, opt, sched_times(tb->Ns, &sd), ls, nullptr, 0, batch, workspace,
+                               workspace_bytes, stream)) return rc;
+  if (tb->Ns > 0) ++net->last_launches;   // mi355_unet_get_stats: the last evaluation and its step launch
+  return 0;
+}
+
+int mi355_ddpm_multistep_cfg_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w,
+                                    const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt,
+                                    const mi355_multistep_schedule* msched, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(tb && opt, -1, "ddpm_multistep_cfg_sample: tables or opt is null");
+  mi355_ddpm_schedule sd; LoopSched ls;
+  if (int rc = check_multistep("ddpm_multistep_cfg_sample", tb, opt, msched, true, sd, ls)) return rc;
+  MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_multistep_cfg_sample: bad argument (net, x, workspace, batch)");
+  const bool roomy = workspace_bytes >= multistep_bytes(net, batch, true);
+  // a short workspace is refused by the guided run's own size check, its last refusal, so that its other refusals keep their order
+  ls.hist = roomy ? reinterpret_cast<float*>(static_cast<char*>(workspace) + multistep_hist_offset(net, batch, true)) : nullptr;
+  if (int rc = ddpm_cfg_sample_run("ddpm_multistep_cfg_sample", net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, sched_times(tb->Ns, &sd), ls,
+                                   nullptr, 0, batch, workspace, roomy ? workspace_bytes : 0, stream)) return rc;
+  if (tb->Ns > 0) ++net->last_launches;
+  return 0;
+}
+
+// Adams-Bashforth CFM samplers: the loop of mi355_cfm_rk_sample / mi355_cfm_cfg_sample with the tableau as the start method (cfm_rk_loop, AbPlan).
+namespace {
+int check_ab(const char* who, int order, const float* w_host, int n_t, int stages, const float* a_host, const float* b_host, const float* c_host) {
+  const std::string f = std::string(who) + ": ";
+  MI355_REQUIRE(order >= 2 && order <= 4, -1, f + "order must be 2, 3 or 4");
+  MI355_REQUIRE(w_host, -1, f + "w_host is null");
+  if (int rc = check_tableau(who, stages, a_host, b_host, c_host)) return rc;
+  MI355_REQUIRE(c_host[0] == 0.f, -1, f + "c_host[0] must be 0: the start method's first stage is the history sample v(t_k, x_k)");
+  for (int k = order - 1; k + 1 < n_t; ++k) {
+    bool any = false;
+    for (int j = 0; j < order; ++j) {
+      MI355_REQUIRE(std::isfinite(w_host[(size_t)k * order + j]), -1, f + "w_host must be finite");
+      any = any || w_host[(size_t)k * order + j] != 0.f;
+    }
+    MI355_REQUIRE(any, -1, f + "w_host has an all-zero row at a multistep step");
+  }
+  return 0;
+}
+}  // namespace
+
+int64_t mi355_cfm_ab_workspace_bytes(const mi355_unet* net, int batch, int order, int start_stages, int guided) {
+  if (!net || batch <= 0 || order < 2 || order > 4 || start_stages < 1 || start_stages > 4) {
+    mi355_set_error("cfm_ab_workspace_bytes: bad argument (2 <= order <= 4, 1 <= start_stages <= 4)");
+    return -1;
+  }
+  return layout_bytes(net, batch, guided != 0, order + start_stages - 1);
+}
+
+int mi355_cfm_ab_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, const int32_t* labels, const float* t_span_host,
+                        int n_t, int order, const float* w_host, int start_stages, const float* a_host, const float* b_host, const float* c_host,
+                        float* traj, uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(t_span_host && n_t >= 1, -1, "cfm_ab_sample: t_span_host is null or empty");
+  if (int rc = check_ab("cfm_ab_sample", order, w_host, n_t, start_stages, a_host, b_host, c_host)) return rc;   // needs no handle
+  MI355_REQUIRE(net && x && batch > 0, -1, "cfm_ab_sample: bad argument (net, x, batch)");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_ab_sample: class labels given to a net built without num_classes");
+  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_ab_sample: the vector field must have the state's channel count");
+  MI355_REQUIRE(workspace_bytes >= mi355_cfm_ab_workspace_bytes(net, batch, order, start_stages, 0), -2, "cfm_ab_sample: workspace too small");
+  Layout l;
+  if (int rc = carve(net, batch, false, order + start_stages - 1, workspace, workspace_bytes, l)) return rc;
+  hipStream_t s = S(stream);
+  const int64_t n = (int64_t)batch * x_channels * net->cfg.image_size * net->cfg.image_size;
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (n_t == 1) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
+  const AbPlan ab{order, w_host};
+  int64_t step_launches = 0;
+  if (int rc = cfm_rk_loop(net, l.sc, l.rk, Guide(), x, x_channels, cond, cond_channels, labels, t_span_host, n_t - 1, start_stages, a_host, b_host, c_host,
+                           traj, u8_out, batch, n, s, &step_launches, &ab)) return rc;
+  net->last_launches = step_launches;   // mi355_unet_get_stats: every launch of the last step
+  return 0;
+}
+
+int mi355_cfm_ab_cfg_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, float none_value, const int32_t* labels,
+                            int null_label, float w, const float* w_dev, const float* t_span_host, int n_t, int order, const float* w_host,
+                            int start_stages, const float* a_host, const float* b_host, const float* c_host, float* traj, uint8_t* u8_out, int batch,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(t_span_host && n_t >= 1, -1, "cfm_ab_cfg_sample: t_span_host is null or empty");
+  if (int rc = check_ab("cfm_ab_cfg_sample", order, w_host, n_t, start_stages, a_host, b_host, c_host)) return rc;
+  MI355_REQUIRE(net && x && batch > 0, -1, "cfm_ab_cfg_sample: bad argument (net, x, batch)");
+  MI355_REQUIRE(cond || labels, -1, "cfm_ab_cfg_sample: nothing to guide (neither a condition nor class labels)");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_ab_cfg_sample: class labels given to a net built without num_classes");
+  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, "cfm_ab_cfg_sample: null_label must be a class index in [0, num_classes)");
+  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_ab_cfg_sample: the vector field must have the state's channel count");
+  MI355_REQUIRE(!cond || (cond_channels > 0 && (size_t)cond_channels == cfg_cond_channels(net)), -2,
+                "cfm_ab_cfg_sample: the condition must have in_channels - out_channels channels");
+  MI355_REQUIRE(workspace_bytes >= mi355_cfm_ab_workspace_bytes(net, batch, order, start_stages, 1), -2, "cfm_ab_cfg_sample: workspace too small");
+  Layout l;
+  if (int rc = carve(net, batch, true, order + start_stages - 1, workspace, workspace_bytes, l)) return rc;
+  const CfgTail& tl = l.cfg;
+  hipStream_t s = S(stream);
+  const int64_t hw = (int64_t)net->cfg.image_size * net->cfg.image_size;
+  const int64_t per = (int64_t)x_channels * hw, n = (int64_t)batch * per, nc = (int64_t)batch * cond_channels * hw;
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (n_t == 1) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
+  if (int rc = cfg_fill_tail(tl, x, n, cond, nc, none_value, labels, null_label, batch, s)) return rc;
+  Guide guide; guide.on = true; guide.w = w; guide.w_dev = w_dev; guide.per = per;
+  const AbPlan ab{order, w_host};
+  int64_t step_launches = 0;
+  if (int rc = cfm_rk_loop(net, l.sc, l.rk, guide, tl.x2, x_channels, cond ? tl.cond2 : nullptr, cond_channels, labels ? tl.labels2 : nullptr, t_span_host,
+                           n_t - 1, start_stages, a_host, b_host, c_host, traj, u8_out, 2 * batch, n, s, &step_launches, &ab)) return rc;
+  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  net->last_launches = step_launches;
+  return 0;
 }
 
 // Training-free in-painting / super-resolution of an unconditional flow: replacement along the straight path and / or reconstruction guidance

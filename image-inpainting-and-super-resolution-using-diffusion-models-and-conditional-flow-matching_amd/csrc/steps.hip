@@ -520,3 +520,54 @@ int paint_patch_launch(const float* img, const int* top, const int* left, int pa
   MI355_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+// DPM-Solver++ multistep step (Lu et al. 2022, Algorithm 2) in the data-prediction form, on the clipped x0_hat of every step above:
+//   D = clip(c_recip x - c_recipm1 eps, -1, 1);   x <- cx x + c0 D + c1 hist;   hist <- D
+// evaluated as ((cx x) + (c0 D)) + (c1 hist), every product and sum rounded (8 roundings with D's three).  c1 == 0 (order 1, the first step run,
+// the last one): hist is not read and the sum ends at the second term, so an uninitialised history never reaches the state.  hist == null: D is
+// not kept.  The host coefficients are DDPM.dpm_solver_coefs.
+namespace {
+__device__ inline void dpmpp4(const float (&xv)[4], const float (&ev)[4], const float (&hv)[4], float c_recip, float c_recipm1, float cx, float c0,
+                              float c1, bool two, float (&xo)[4], float (&dv)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float d = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
+    const float m = cx * xv[j] + c0 * d;
+    xo[j] = two ? m + c1 * hv[j] : m;
+    dv[j] = d;
+  }
+}
+}  // namespace
+
+int dpmpp_step_launch(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(n <= 0 || (x && eps), -1, "dpmpp_step: null argument");
+  MI355_REQUIRE(c1 == 0.f || hist || n <= 0, -1, "dpmpp_step: c1 != 0 needs hist (the previous step's data prediction)");
+  const bool two = c1 != 0.f;
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
+    float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4];
+    ld4(x, i, cnt, xv); ld4(eps, i, cnt, ev);
+    if (two) ld4(hist, i, cnt, hv);
+    dpmpp4(xv, ev, hv, c_recip, c_recipm1, cx, c0, c1, two, xv, dv);
+    st4(x, i, cnt, xv);
+    if (hist) st4(hist, i, cnt, dv);
+  });
+}
+
+// its classifier-free-guided form, built as ddim_cfg_step_launch: eps [2n], x [2n] (first half read, both halves written), hist [n]
+int dpmpp_cfg_step_launch(float* x, const float* eps, float* hist, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float cx,
+                          float c0, float c1, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "dpmpp_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
+  MI355_REQUIRE(n <= 0 || (x && eps), -1, "dpmpp_cfg_step: null argument");
+  MI355_REQUIRE(c1 == 0.f || hist || n <= 0, -1, "dpmpp_cfg_step: c1 != 0 needs hist (the previous step's data prediction)");
+  const bool two = c1 != 0.f;
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
+    float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4];
+    ld4(x, i, cnt, xv);
+    cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
+    if (two) ld4(hist, i, cnt, hv);
+    dpmpp4(xv, ev, hv, c_recip, c_recipm1, cx, c0, c1, two, xv, dv);
+    st4(x, i, cnt, xv);
+    st4(x + n, i, cnt, xv);
+    if (hist) st4(hist, i, cnt, dv);
+  });
+}

@@ -13,6 +13,8 @@ Two execution paths, both entirely on the HIP backend:
     host loop that calls it once per step and applies the fused HIP step kernels (csrc/steps.hip).
 Noise: by default drawn in-kernel (Philox4x32-10, seeded from torch.initial_seed()); parity tests
 inject the draws of the reference's `torch.randn_like` call sequence with `injected_noise([...])`.
+Build-defined extensions without a reference counterpart: get_ddim_sample_fn (DDIM(eta)) and get_dpm_solver_sample_fn (DPM-Solver++ multistep,
+orders 1 and 2: one evaluation and one step kernel per step, the previous step's data prediction kept on the device).
 ReconstructionGuidance (sampling.py:136-206) differentiates the x0 model through the U-Net: the gradient is the HIP engine's
 vector-Jacobian product (`UNetEngine.vjp`, csrc/unet_backward.hip) of a differentiable plan of the same network, so it needs an
 `eps_model` made by `make_eps_model(network, ddpm)` around a `UNetModel`.
@@ -414,6 +416,48 @@ def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihoo
         rep = dict(condition=condition, start_fraction=conditioning.start_fraction, noise=bool(conditioning.noise), pad_value=pad)
         return _run_generic(eps_model, ddpm, xT, amortized=False, cond_pred=None, cond_corr=None, replacement=rep,
                             n_corrector=conditioning.n_corrector, delta=conditioning.delta, walk=walk)
+
+    return sample
+
+
+def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Likelihood] = None, guidance_scale=None, order=2):
+    """BUILD-DEFINED EXTENSION (no reference counterpart): DPM-Solver++ multistep (Lu et al. 2022, Algorithm 2) of order 1 or 2 on the same tables,
+    in the data-prediction form with the reference's clipped x0_hat.  sample(xT, condition=None), deterministic, one evaluation per step like
+    get_ddim_sample_fn; order 1 is the deterministic DDIM step written with other coefficients, order 2 reuses the previous step's data
+    prediction.  The coefficients are ddpm.dpm_solver_coefs(order); the second order pays on steps spaced evenly in logSNR:
+    ddpm.respace(ddpm.logsnr_steps(K)).  guidance_scale (None: unguided): classifier-free guidance of eps against the none_like condition; needs
+    a condition.  Fused path (eps_model built by make_eps_model for this very schedule): the whole loop in mi355_ddpm_multistep_sample; any other
+    callable: a host loop over dpmpp_step_ (guided: cfg_combine, then the step).  Sample quality is untested."""
+    coefs = ddpm.dpm_solver_coefs(order)
+    cx, c0, c1 = (c.tolist() for c in coefs)
+
+    @torch.no_grad()
+    def sample(xT, condition=None):
+        T = _tables(ddpm)
+        engine = _fast_engine(eps_model, ddpm, xT)
+        if condition is not None:
+            condition = condition.to(xT.device).float().contiguous()
+        if guidance_scale is not None and condition is None:
+            raise ValueError("guidance_scale needs a condition to guide towards")
+        xi = xT.detach().clone().float().contiguous()
+        if engine is not None:
+            nv = _none_value(likelihood, xT) if likelihood is not None else 0.0
+            sched = {}
+            if getattr(ddpm, "timesteps", None) is not None:
+                sched = dict(timesteps=ddpm.timesteps, train_steps=int(ddpm.base_Ns))
+            return engine.ddpm_multistep(xi, T, coefs, cond=condition, none_value=nv, guidance_scale=guidance_scale, **sched)
+        none = None
+        if guidance_scale is not None:
+            none = likelihood.none_like(xT) if likelihood is not None else torch.zeros_like(condition)
+        hist = torch.empty_like(xi)
+        for i in reversed(range(ddpm.Ns)):
+            eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i)).float()
+            if none is not None:
+                eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
+                eps = _ops.cfg_combine(torch.cat((eps, eu)).contiguous(), guidance_scale)
+            _ops.dpmpp_step_(xi, eps.contiguous(), hist, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
+                             cx[i], c0[i], c1[i])
+        return process_x0(xi)
 
     return sample
 

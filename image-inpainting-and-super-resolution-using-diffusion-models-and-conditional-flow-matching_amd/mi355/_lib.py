@@ -108,6 +108,11 @@ class DDPMScheduleC(C.Structure):
                 ("n_walk", C.c_int32), ("renoise_a", _FP), ("renoise_b", _FP)]
 
 
+class MultistepScheduleC(C.Structure):
+    """mi355_multistep_schedule (include/mi355_sampler.h): the steps of a DPM-Solver++ run in training time and its per-step coefficients."""
+    _fields_ = [("steps", C.POINTER(C.c_int32)), ("train_steps", C.c_int32), ("cx", _FP), ("c0", _FP), ("c1", _FP)]
+
+
 _VP, _I, _I64, _F, _U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
@@ -177,6 +182,16 @@ SIGNATURES = {
                                      _I64, _VP]),
     "mi355_ddpm_cfg_sample_sched": (_I, [_VP, _VP, _I, _VP, _VP, _I, _F, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC),
                                          C.POINTER(DDPMScheduleC), _VP, _I64, _I, _VP, _I64, _VP]),
+    "mi355_dpmpp_step": (_I, [_VP, _VP, _VP, _F, _F, _F, _F, _F, _I64, _VP]),
+    "mi355_dpmpp_cfg_step": (_I, [_VP, _VP, _VP, _F, _VP, _I64, _F, _F, _F, _F, _F, _I64, _VP]),
+    "mi355_ddpm_multistep_workspace_bytes": (_I64, [_VP, _I, _I]),
+    "mi355_ddpm_multistep_sample": (_I, [_VP, _VP, _I, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), C.POINTER(MultistepScheduleC), _I, _VP, _I64,
+                                         _VP]),
+    "mi355_ddpm_multistep_cfg_sample": (_I, [_VP, _VP, _I, _VP, _VP, _I, _F, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC),
+                                             C.POINTER(MultistepScheduleC), _I, _VP, _I64, _VP]),
+    "mi355_cfm_ab_workspace_bytes": (_I64, [_VP, _I, _I, _I, _I]),
+    "mi355_cfm_ab_sample": (_I, [_VP, _VP, _I, _VP, _I, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
+    "mi355_cfm_ab_cfg_sample": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _I, _F, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_rk_sqnorm": (_I, [_VP, _VP, _VP, _VP, _F, _F, _I64, _VP, _VP]),
     "mi355_rk_interp": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _F, _F, _I64, _VP]),
     "mi355_op_workspace_bytes": (_I64, [_I, _I, _I]),

@@ -436,6 +436,54 @@ class UNetEngine:
               "mi355_cfm_rk_sample")
         return x, traj, u8
 
+    def cfm_ab(self, x: torch.Tensor, t_span: Sequence[float], method="ab2", cond: Optional[torch.Tensor] = None, keep_traj: bool = False,
+               want_u8: bool = False, y: Optional[torch.Tensor] = None, guidance_scale=None, null_label: Optional[int] = None,
+               none_value: float = -2.0, start=None):
+        """In-place Adams-Bashforth integration of x over t_span (host floats), one step per interval, the whole loop one library call
+        (mi355_cfm_ab_sample; with guidance_scale: mi355_cfm_ab_cfg_sample).  method: "ab2", "ab3" or "ab4" (mi355.ode.AB_SOLVERS): one
+        evaluation per step from step order - 1 on, the steps before it by the start method (start: a name of mi355.ode.TABLEAUS or an (a, b, c)
+        tableau whose c_1 is 0; None: mi355.ode.AB_START[method]).  The weights are mi355.ode.ab_weights(t_span, order).  Returns
+        (x, traj or None, u8 or None).  cond, y, guidance_scale, null_label, none_value: as in cfm_rk / cfm_cfg.  A batch beyond max_batch()
+        (guided: cfg_batch()) runs in slices."""
+        from .ode import AB_SOLVERS, AB_START, ab_weights, resolve_tableau
+
+        if method not in AB_SOLVERS:
+            raise NotImplementedError(f"method={method!r}: the Adams-Bashforth samplers are {AB_SOLVERS}")
+        order = AB_SOLVERS.index(method) + 2
+        tableau = resolve_tableau(AB_START[method] if start is None else start)
+        if tableau[2][0] != 0.0:
+            raise ValueError("the start method's first stage must sit at t_k (c_1 == 0): it is the history sample")
+        B, Cx, Cc = self._split(x, cond)
+        lab, _ = self._labels(y, B)
+        guided = guidance_scale is not None
+        w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label) if guided else (0.0, None, 0)
+        ts = [float(v) for v in t_span]
+        weights = ab_weights(ts, order).contiguous()   # CPU fp32 [n_steps, order]
+        traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
+        stages, a_arr, b_arr, c_arr = _tableau_arrays(tableau)
+        arr = (C.c_float * len(ts))(*ts)
+        wp = C.cast(weights.data_ptr(), C.POINTER(C.c_float)) if weights.numel() else (C.c_float * 1)()
+        for lo, hi, whole in _slices(B, self.cfg_batch() if guided else self.max_batch()):
+            xs = x if whole else x[lo:hi]
+            tr = traj if whole else self._traj_u8(xs, len(ts), keep_traj, False)[0]
+            us = u8 if whole else _cut(u8, lo, hi)
+            cs, ls = _cut(cond, lo, hi), _cut(lab, lo, hi)
+            self._fwd_state = None
+            ws, wsb = self._workspace_sized("mi355_cfm_ab_workspace_bytes", hi - lo, order, stages, int(guided))
+            common = (arr, len(ts), order, wp, stages, a_arr, b_arr, c_arr, self._chk(tr, "traj") if tr is not None else None,
+                      self._chk(us, "u8", torch.uint8) if us is not None else None, hi - lo, ws, wsb, self._stream())
+            if guided:
+                check(self.L.mi355_cfm_ab_cfg_sample(self.handle, self._chk(xs, "x"), Cx, self._chk(cs, "condition") if cs is not None else None, Cc,
+                                                     float(none_value), C.c_void_p(ls.data_ptr()) if ls is not None else None, int(nl), float(w),
+                                                     self._chk(_cut(wt, lo, hi), "guidance_scale") if wt is not None else None, *common),
+                      "mi355_cfm_ab_cfg_sample")
+            else:
+                check(self.L.mi355_cfm_ab_sample(self.handle, self._chk(xs, "x"), Cx, self._chk(cs, "condition") if cs is not None else None, Cc,
+                                                 C.c_void_p(ls.data_ptr()) if ls is not None else None, *common), "mi355_cfm_ab_sample")
+            if traj is not None and not whole:
+                traj[:, lo:hi] = tr
+        return x, traj, u8
+
     def cfm_recon(self, x: torch.Tensor, t_span: Sequence[float], y: Optional[torch.Tensor], mode: int, *, scales: Optional[Sequence[float]] = None,
                   replace: Optional[str] = None, final_paste: bool = False, pad_value: float = -2.0, noise: Optional[torch.Tensor] = None,
                   seed: Optional[int] = None, keep_traj: bool = False, want_u8: bool = False, return_loss: bool = False,
@@ -615,6 +663,59 @@ class UNetEngine:
         check(self.L.mi355_ddpm_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
                                        C.byref(tb), C.byref(opt), self._chk(noise, "noise") if noise is not None else None, ndraws, B,
                                        ws, wsb, self._stream()), "mi355_ddpm_sample")
+        return x
+
+    def ddpm_multistep(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], coefs, *, cond: Optional[torch.Tensor] = None, none_value=-2.0,
+                       guidance_scale=None, y: Optional[torch.Tensor] = None, null_label: Optional[int] = None, timesteps=None, train_steps=None):
+        """In-place DPM-Solver++ multistep sampling (mi355_ddpm_multistep_sample; with guidance_scale: mi355_ddpm_multistep_cfg_sample): one
+        evaluation and one step launch per step, deterministic.  tables: as in ddpm_sample; coefs: (cx, c0, c1) of DDPM.dpm_solver_coefs(order)
+        for the same chain.  cond: None (prior; an amortized net sees none_value) or the condition of an amortized net.  timesteps / train_steps
+        (both or neither): where the steps sit in training time (a RespacedDDPM's timesteps and base_Ns); None: steps 0..Ns-1 of Ns.
+        guidance_scale, y, null_label: as in ddpm_sample.  A guided batch beyond cfg_batch() runs in slices."""
+        B, Cx = x.shape[:2]
+        if cond is not None and cond.shape != x.shape:
+            raise ValueError("condition must have the shape of x")
+        if guidance_scale is None and y is not None:
+            raise NotImplementedError("ddpm_multistep takes class labels on the guided path only (guidance_scale=)")
+        if (timesteps is None) != (train_steps is None):
+            raise ValueError("timesteps and train_steps go together")
+        tb, keep = self._ddpm_tables(tables)
+        K = int(tb.Ns)
+        steps = list(range(K)) if timesteps is None else [int(t) for t in timesteps]
+        if len(steps) != K:
+            raise ValueError("timesteps must have one entry per row of the (respaced) tables")
+        try:
+            cs = [torch.as_tensor(c, dtype=torch.float32).detach().to("cpu").contiguous() for c in coefs]
+        except TypeError:
+            raise ValueError("coefs must be the (cx, c0, c1) of DDPM.dpm_solver_coefs") from None
+        if len(cs) != 3 or any(c.numel() != K for c in cs):
+            raise ValueError("coefs must be (cx, c0, c1), one entry per step each")
+        fp = C.POINTER(C.c_float)
+        ms = _lib.MultistepScheduleC()
+        steps_arr = (C.c_int32 * max(1, K))(*steps)
+        ms.steps, ms.train_steps = C.cast(steps_arr, C.POINTER(C.c_int32)), K if train_steps is None else int(train_steps)
+        ms.cx, ms.c0, ms.c1 = (C.cast(c.data_ptr(), fp) for c in cs)
+        opt = _lib.DDPMOptionsC(_lib.DDIM, 0, 0.1, 1e-5, 1.0, 1.0, 1, -2.0, float(none_value), int(cond is None), 0)
+        self._fwd_state = None
+        if guidance_scale is None:
+            ws, wsb = self._workspace_sized("mi355_ddpm_multistep_workspace_bytes", B, 0)
+            check(self.L.mi355_ddpm_multistep_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
+                                                     C.byref(tb), C.byref(opt), C.byref(ms), B, ws, wsb, self._stream()), "mi355_ddpm_multistep_sample")
+            return x
+        lab, _ = self._labels(y, B)
+        w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
+        for lo, hi, whole in _slices(B, self.cfg_batch()):
+            xs = x if whole else x[lo:hi].contiguous()
+            cn = cond if whole or cond is None else cond[lo:hi].contiguous()
+            ls, wl = _cut(lab, lo, hi), _cut(wt, lo, hi)
+            ws, wsb = self._workspace_sized("mi355_ddpm_multistep_workspace_bytes", hi - lo, 1)
+            check(self.L.mi355_ddpm_multistep_cfg_sample(self.handle, self._chk(xs, "x"), Cx, self._chk(cn, "condition") if cn is not None else None,
+                                                         C.c_void_p(ls.data_ptr()) if ls is not None else None, int(nl), float(w),
+                                                         self._chk(wl, "guidance_scale") if wl is not None else None, C.byref(tb), C.byref(opt),
+                                                         C.byref(ms), hi - lo, ws, wsb, self._stream()), "mi355_ddpm_multistep_cfg_sample")
+            if not whole:
+                x[lo:hi] = xs
+        del keep, steps_arr
         return x
 
     @staticmethod

@@ -22,6 +22,11 @@ FixedStepRK is the host-driven loop for any callable and any tuple state, one mi
 Which names the un-vendored libraries give these tables is recalled, not checked - "parity unpinned": torchdyn's "rk4" is recalled as the
 classical tableau ("rk4" here), torchdiffeq's fixed-grid "rk4" as the 3/8 rule ("rk4_38" here), "midpoint" as the explicit midpoint rule
 in both.  The tables themselves are held to their order conditions and a measured convergence order (tests/test_rk_cpu.py).
+
+Adams-Bashforth methods of order 2 to 4 (`AB_SOLVERS`, `ab_weights`, `AdamsBashforth`; no reference counterpart): one evaluation per step
+from step order - 1 on, x_{k+1} = x_k + sum_j w_kj v_{k-j} with the weights integrated over the grid as given (variable-step form), after
+order - 1 Runge-Kutta start steps (`AB_START`).  The same rule runs inside the library as mi355_cfm_ab_sample (UNetEngine.cfm_ab);
+weights, exactness and measured orders: tests/test_multistep_cpu.py.
 """
 from __future__ import annotations
 
@@ -269,6 +274,108 @@ class FixedStepRK:
                 ks.append(self._f(float(ti), self._stage(y, ks, self.a[i][:i], dt)))
             y1 = self._stage(y, ks, self.b, dt)
             y = y1 if y1 is not y else [v.clone() for v in y]
+            outs.append(y)
+        return outs
+
+    def integrate(self, y0: Sequence[torch.Tensor], t0: float, t_end: float) -> State:
+        return self.integrate_times(y0, [t0, t_end])[-1]
+
+
+# ---- Adams-Bashforth (fixed grid, variable step) ------------------------------------------------------------------------------------------
+
+AB_SOLVERS = ("ab2", "ab3", "ab4")   # order q = 2, 3, 4: one evaluation per step from step q - 1 on; a table of their own, not TABLEAUS
+# the first q - 1 steps: a Runge-Kutta method of local order >= q - 1 (the global order survives) whose first stage sits at t_k (c_1 = 0), so
+# that it is v(t_k, x_k), the history sample
+AB_START = {"ab2": "euler", "ab3": "midpoint", "ab4": "rk4"}
+
+
+def _ab_order(method) -> int:
+    if method not in AB_SOLVERS:
+        raise NotImplementedError(f"method={method!r}: the Adams-Bashforth samplers are {AB_SOLVERS}")
+    return AB_SOLVERS.index(method) + 2
+
+
+def _ab_weights64(t, order: int):
+    """ab_weights in fp64 on the fp64 grid t (numpy)."""
+    import numpy as np
+
+    if isinstance(order, bool) or order not in (2, 3, 4):
+        raise ValueError(f"order must be 2, 3 or 4, got {order!r}")
+    if t.size < 1 or not np.isfinite(t).all():
+        raise ValueError("t_span must hold finite times")
+    d = np.diff(t)
+    if d.size and not ((d > 0).all() or (d < 0).all()):
+        raise ValueError("t_span must be strictly monotone: the Lagrange nodes of a step must be distinct")
+    n = t.size - 1
+    w = np.zeros((max(n, 0), order))
+    for k in range(order - 1, n):
+        nodes = t[k - np.arange(order)] - t[k]            # shifted to t_k = 0: the integral runs over [0, dt]
+        dt = t[k + 1] - t[k]
+        for j in range(order):
+            p = np.poly1d([1.0])
+            for m in range(order):
+                if m != j:
+                    p = p * np.poly1d([1.0, -nodes[m]]) / (nodes[j] - nodes[m])
+            w[k, j] = np.polyint(p)(dt)
+    return w
+
+
+def ab_weights(t_span: Sequence[float], order: int) -> torch.Tensor:
+    """CPU fp32 [n_steps, order]: row k holds w_kj = the integral over [t_k, t_{k+1}] of the Lagrange basis polynomial of node t_{k-j} among
+    t_k, ..., t_{k-order+1} (the step length is inside the weight), so that x_{k+1} = x_k + sum_j w_kj v_{k-j} integrates polynomials of degree
+    order - 1 exactly.  Computed in fp64 from the fp32 grid values (what the library sees) and rounded once.  Rows k < order - 1 (start steps)
+    are zero.  A grid that is not strictly monotone raises ValueError."""
+    import numpy as np
+
+    t = np.asarray([float(v) for v in t_span], dtype=np.float32).astype(np.float64)
+    return torch.from_numpy(_ab_weights64(t, order).astype(np.float32))
+
+
+class AdamsBashforth:
+    """Host-driven Adams-Bashforth integration of y' = func(t, y) for any callable and any tuple state, beside FixedStepRK: steps 0..order-2
+    by the start method (FixedStepRK's step; its first stage is kept as the history sample), then one evaluation and one mi355_rk_stage
+    launch per step and component.  The library runs the same rule as mi355_cfm_ab_sample (UNetEngine.cfm_ab)."""
+
+    def __init__(self, func: Callable[[float, State], Sequence[torch.Tensor]], method="ab2", start=None, ops=None, dtype=torch.float32):
+        self.order = _ab_order(method)
+        self.rk = FixedStepRK(func, AB_START[method] if start is None else start, ops=ops, dtype=dtype)
+        if self.rk.c[0] != 0.0:
+            raise ValueError("the start method's first stage must sit at t_k (c_1 == 0): it is the history sample")
+        self.ops = self.rk.ops
+        self.dtype = dtype
+
+    @property
+    def nfe(self) -> int:
+        return self.rk.nfe
+
+    @torch.no_grad()
+    def integrate_times(self, y0: Sequence[torch.Tensor], times: Sequence[float]) -> List[State]:
+        """States at times[1:], one step per interval (the grid may be non-uniform or decreasing, not repeating)."""
+        q, rk = self.order, self.rk
+        # the weights from the grid as the state's type holds it, rounded to that type (fp32: ab_weights itself)
+        w = torch.from_numpy(_ab_weights64(torch.tensor([float(v) for v in times], dtype=self.dtype).double().numpy(), q)).to(self.dtype)
+        y = [v.detach().to(self.dtype).contiguous() for v in y0]
+        hist: List[State] = []   # v_k, v_{k-1}, ...
+        outs: List[State] = []
+        for k in range(len(times) - 1):
+            if k < q - 1:
+                t0, t1 = rk._s(times[k]), rk._s(times[k + 1])
+                dt = t1 - t0
+                ks: List[State] = []
+                for i in range(rk.stages):
+                    ti = t0 if rk.c[i] == 0.0 else (t1 if rk.c[i] == 1.0 else t0 + rk._s(rk.c[i]) * dt)
+                    ks.append(rk._f(float(ti), rk._stage(y, ks, rk.a[i][:i], dt)))
+                hist.insert(0, ks[0])
+                y1 = rk._stage(y, ks, rk.b, dt)
+                y = y1 if y1 is not y else [v.clone() for v in y]
+            else:
+                hist.insert(0, rk._f(float(rk._s(times[k])), y))
+                del hist[q:]
+                nz = [(hist[j], float(w[k, j])) for j in range(q) if float(w[k, j]) != 0.0]
+                out = [torch.empty_like(v) for v in y]
+                for i in range(len(y)):
+                    self.ops.rk_stage(out[i], y[i], [h[i] for h, _ in nz], [c for _, c in nz])
+                y = out
             outs.append(y)
         return outs
 

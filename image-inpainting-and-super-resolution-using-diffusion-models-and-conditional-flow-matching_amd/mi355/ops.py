@@ -130,6 +130,35 @@ class Ops:
                                                  int(philox is not None and z is None), seed, off, n, _stream()), "mi355_ddim_eta_cfg_step")
         return x2
 
+    def dpmpp_step_(self, x, eps, hist, c_recip, c_recipm1, cx, c0, c1):
+        """DPM-Solver++ multistep step in place: D = clip(c_recip x - c_recipm1 eps, -1, 1); x <- cx x + c0 D + c1 hist; hist <- D.  hist: the
+        previous step's D (not read when c1 == 0), or None (D is not kept; c1 must then be 0).  -> x"""
+        _same(x, eps, "x", "eps")
+        if hist is not None:
+            _same(x, hist, "x", "hist")
+        elif float(c1) != 0.0:
+            raise ValueError("c1 != 0 needs hist (the previous step's data prediction)")
+        check(_lib.lib().mi355_dpmpp_step(_req(x, "x"), _req(eps, "eps"), _req(hist, "hist") if hist is not None else None, float(c_recip),
+                                          float(c_recipm1), float(cx), float(c0), float(c1), x.numel(), _stream()), "mi355_dpmpp_step")
+        return x
+
+    def dpmpp_cfg_step_(self, x2, eps2, hist, w, c_recip, c_recipm1, cx, c0, c1):
+        """dpmpp_step_ on the guided eps: x2, eps2, w as in ddim_cfg_step_; hist [B, ...] (or None)."""
+        _same(x2, eps2, "x2", "eps2")
+        if x2.shape[0] % 2:
+            raise ValueError("x2 holds the state twice: an even leading size")
+        B = x2.shape[0] // 2
+        n = x2.numel() // 2
+        if hist is not None and hist.numel() != n:
+            raise ValueError("hist must have the B-image state's size")
+        if hist is None and float(c1) != 0.0:
+            raise ValueError("c1 != 0 needs hist (the previous step's data prediction)")
+        wf, wp, keep = self._cfg_w(w, B)
+        check(_lib.lib().mi355_dpmpp_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _req(hist, "hist") if hist is not None else None, wf, wp,
+                                              n // B if B else 1, float(c_recip), float(c_recipm1), float(cx), float(c0), float(c1), n, _stream()),
+              "mi355_dpmpp_cfg_step")
+        return x2
+
     def renoise_(self, x, z, a, b, philox=None):
         """The forward move q(x_k | x_{k-1}) in place: x <- a x + b z (a = sqrt(alphas_k), b = sqrt(betas_k)); z / philox as in ddpm_step_."""
         zp = _req(z, "z") if z is not None else None

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 
 from image_diffusion.unet import UNetModel
-from mi355.ode import RK_SOLVERS
+from mi355.ode import AB_SOLVERS, RK_SOLVERS
 from mi355.ops import default_ops
 
 
@@ -159,8 +159,9 @@ class GuidedVectorField:
 
 class NeuralODE:
     """torchdyn.core.NeuralODE front-end: solver="euler" (fixed step), "midpoint", "heun2", "rk4", "rk4_38" (fixed-step explicit
-    Runge-Kutta, the tableaus of mi355.ode.TABLEAUS: "rk4" the classical one, "rk4_38" the 3/8 rule) or "dopri5" (adaptive,
-    mi355.ode.Dopri5).
+    Runge-Kutta, the tableaus of mi355.ode.TABLEAUS: "rk4" the classical one, "rk4_38" the 3/8 rule), "ab2", "ab3", "ab4" (Adams-Bashforth,
+    mi355.ode.AB_SOLVERS: one evaluation per step after a Runge-Kutta start; mi355_cfm_ab_sample / mi355.ode.AdamsBashforth) or "dopri5"
+    (adaptive, mi355.ode.Dopri5).
 
     trajectory(x, t_span) -> Tensor[len(t_span), *x.shape], one step per interval of t_span for the fixed-step solvers.  With a
     UNetModelWrapper vector field these run the whole integration inside libmi355_sampler (mi355_cfm_euler_sample /
@@ -170,8 +171,8 @@ class NeuralODE:
     RK_SOLVERS = RK_SOLVERS   # mi355.ode: every fixed-step tableau name but "euler"
 
     def __init__(self, vector_field, solver="euler", sensitivity="adjoint", atol=1e-4, rtol=1e-4, **kwargs):
-        if solver not in ("euler", "dopri5") + self.RK_SOLVERS:
-            raise NotImplementedError(f"solver={solver!r}: only 'euler', 'dopri5' and {self.RK_SOLVERS} are built")
+        if solver not in ("euler", "dopri5") + self.RK_SOLVERS + AB_SOLVERS:
+            raise NotImplementedError(f"solver={solver!r}: only 'euler', 'dopri5', {self.RK_SOLVERS} and {AB_SOLVERS} are built")
         self.vf = vector_field
         self.solver = solver
         self.atol, self.rtol = atol, rtol
@@ -203,7 +204,16 @@ class NeuralODE:
             kw = self.vf._kw(x.device)
             if self.solver == "euler":
                 return eng.cfm_euler(x, ts, keep_traj=True, **kw)[1]
+            if self.solver in AB_SOLVERS:
+                return eng.cfm_ab(x, ts, self.solver, keep_traj=True, **kw)[1]
             return eng.cfm_rk(x, ts, self.solver, keep_traj=True, **kw)[1]
+        if self.solver in AB_SOLVERS:   # Adams-Bashforth: one library call on the device, the host class for any other callable
+            if type(self.vf) is UNetModelWrapper and x.is_cuda:
+                return self.vf.engine(x.device).cfm_ab(x, ts, self.solver, keep_traj=True)[1]
+            from mi355.ode import AdamsBashforth
+
+            states = AdamsBashforth(lambda t, y: [self._call(t, y[0])], self.solver).integrate_times([x], ts)
+            return torch.stack([x] + [s[0] for s in states])
         if self.solver in self.RK_SOLVERS:
             if type(self.vf) is UNetModelWrapper and x.is_cuda:
                 _, traj, _ = self.vf.engine(x.device).cfm_rk(x, ts, self.solver, keep_traj=True)
