@@ -292,6 +292,16 @@ int mi355_dpmpp_cfg_step(float* x, const float* eps, float* hist, float w, const
                          float cx, float c0, float c1, int64_t n, void* stream) {
   return dpmpp_cfg_step_launch(x, eps, hist, w, w_dev, elems_per_image, c_recip, c_recipm1, cx, c0, c1, n, S(stream));
 }
+int mi355_x0_shape_stats(const float* x, const float* eps, float w, const float* w_dev, int guided, float c_recip, float c_recipm1,
+                         const mi355_x0_shaping* shaping, float* shape, float* detail, int batch, int64_t elems_per_image, void* stream) {
+  return x0_shape_stats_launch(x, eps, guided, w, w_dev, c_recip, c_recipm1, shaping, shape, detail, batch, elems_per_image, S(stream));
+}
+int mi355_x0_shaped_step(int kind, float* x, const float* eps, const float* z, float* hist, int guided, float w, const float* w_dev,
+                         int64_t elems_per_image, float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed,
+                         uint64_t offset, const float* shape, int64_t n, void* stream) {
+  return x0_shaped_step_launch(kind, x, eps, z, hist, guided, w, w_dev, elems_per_image, c_recip, c_recipm1, a, b, c, sigma, use_philox, seed, offset,
+                               shape, n, S(stream));
+}
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream) {
   return rk_sqnorm_launch(a, sub, b, b2, atol, rtol, n, out, S(stream));

@@ -296,26 +296,41 @@ int euler_step_launch(float* x, const float* v, float dt, int64_t n, hipStream_t
 int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, float cb, float dt, const float* g, float g_s, const float* dW,
                           int use_philox, uint64_t seed, uint64_t offset, float* out, float w, int64_t n, hipStream_t s);
 int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
-                     float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
+                     float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape = nullptr, int64_t per = 0);
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,
                           float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
-int ddim_step_launch(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s);
+int ddim_step_launch(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s, const float* shape = nullptr,
+                     int64_t per = 0);
 // classifier-free-guided ddpm / ddim steps: eps [2n] = conditional | unconditional evaluation, x [2n] the duplicated state (both halves written)
 int ddpm_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
-                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
+                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s,
+                         const float* shape = nullptr);
 int ddim_cfg_step_launch(float* x, const float* eps, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float acp_prev, int64_t n,
-                         hipStream_t s);
+                         hipStream_t s, const float* shape = nullptr);
 // DDIM(eta) step, its guided form (operands as ddim_cfg_step_launch) and the forward re-noising move x <- a x + b z of a RePaint walk
 int ddim_eta_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int use_philox,
-                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
+                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape = nullptr, int64_t per = 0);
 int ddim_eta_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
-                             float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
+                             float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s,
+                             const float* shape = nullptr);
 int renoise_step_launch(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 // DPM-Solver++ multistep step on the clipped x0_hat: D = clip(c_recip x - c_recipm1 eps); x <- cx x + c0 D + c1 hist; hist <- D (hist: not read when
 // c1 == 0, not written when null), and its guided form (operands as ddim_cfg_step_launch, hist [n])
-int dpmpp_step_launch(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s);
+int dpmpp_step_launch(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s,
+                      const float* shape = nullptr, int64_t per = 0);
 int dpmpp_cfg_step_launch(float* x, const float* eps, float* hist, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float cx,
-                          float c0, float c1, int64_t n, hipStream_t s);
+                          float c0, float c1, int64_t n, hipStream_t s, const float* shape = nullptr);
+// Per-image shaping of a predictor step's data prediction (mi355_x0_shaping).  The eight step launchers above take `shape`: null = the static clip
+// (the unshaped kernels), else rows (f, s) per image of `per` elements: eps is scaled by f, x0_hat = clip(x0, -s, s) / s.  x0_shape_stats_launch
+// fills the rows, one workgroup per image (and detail [B, 4] = sigma_c, sigma_g, s_raw, 0 when not null); check_x0_shaping holds the refusals of a
+// mi355_x0_shaping (null: none), each prefixed by `who`; x0_shaped_step_launch picks a step by number (0 ancestral: a, b = coef1, coef2; 1 DDIM:
+// a = acp_prev; 2 DDIM(eta): a = acp_prev; 3 DPM-Solver++: a, b, c = cx, c0, c1).
+int check_x0_shaping(const char* who, const mi355_x0_shaping* sh, int guided);
+int x0_shape_stats_launch(const float* x, const float* eps, int guided, float w, const float* w_dev, float c_recip, float c_recipm1,
+                          const mi355_x0_shaping* sh, float* shape, float* detail, int batch, int64_t per, hipStream_t s);
+int x0_shaped_step_launch(int kind, float* x, const float* eps, const float* z, float* hist, int guided, float w, const float* w_dev, int64_t per,
+                          float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed, uint64_t offset,
+                          const float* shape, int64_t n, hipStream_t s);
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb,
                         int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int clip_launch(float* x, float lo, float hi, int64_t n, hipStream_t s);

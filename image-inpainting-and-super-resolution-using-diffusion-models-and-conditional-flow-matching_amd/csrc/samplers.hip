@@ -129,22 +129,25 @@ struct Guide {
   int stage(float* out, const float* y0, const float* const* kp, const float* cf, int nk, int64_t n, float* copy_out, uint8_t* u8_out, hipStream_t s) const {
     return on ? cfg_stage_launch(out, y0, kp, cf, nk, n, w, w_dev, per, 1, copy_out, u8_out, s) : rk_stage_launch(out, y0, kp, cf, nk, n, copy_out, u8_out, s);
   }
-  int dpmpp(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s) const {
-    return on ? dpmpp_cfg_step_launch(x, eps, hist, w, w_dev, per, c_recip, c_recipm1, cx, c0, c1, n, s)
-              : dpmpp_step_launch(x, eps, hist, c_recip, c_recipm1, cx, c0, c1, n, s);
+  // the DDPM predictor steps; shape (null: the static clip): the per-image rows of x0_shape_stats_launch, images of sper elements
+  int dpmpp(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s,
+            const float* shape, int64_t sper) const {
+    return on ? dpmpp_cfg_step_launch(x, eps, hist, w, w_dev, per, c_recip, c_recipm1, cx, c0, c1, n, s, shape)
+              : dpmpp_step_launch(x, eps, hist, c_recip, c_recipm1, cx, c0, c1, n, s, shape, sper);
   }
-  int ddim(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s) const {
-    return on ? ddim_cfg_step_launch(x, eps, w, w_dev, per, c_recip, c_recipm1, acp_prev, n, s) : ddim_step_launch(x, eps, c_recip, c_recipm1, acp_prev, n, s);
+  int ddim(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s, const float* shape, int64_t sper) const {
+    return on ? ddim_cfg_step_launch(x, eps, w, w_dev, per, c_recip, c_recipm1, acp_prev, n, s, shape)
+              : ddim_step_launch(x, eps, c_recip, c_recipm1, acp_prev, n, s, shape, sper);
   }
   int ddim_eta(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int philox, uint64_t seed,
-               uint64_t off, int64_t n, hipStream_t s) const {
-    return on ? ddim_eta_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, acp_prev, sigma, philox, seed, off, n, s)
-              : ddim_eta_step_launch(x, eps, z, c_recip, c_recipm1, acp_prev, sigma, philox, seed, off, n, s);
+               uint64_t off, int64_t n, hipStream_t s, const float* shape, int64_t sper) const {
+    return on ? ddim_eta_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, acp_prev, sigma, philox, seed, off, n, s, shape)
+              : ddim_eta_step_launch(x, eps, z, c_recip, c_recipm1, acp_prev, sigma, philox, seed, off, n, s, shape, sper);
   }
   int ddpm(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float sigma, int philox, uint64_t seed,
-           uint64_t off, int64_t n, hipStream_t s) const {
-    return on ? ddpm_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, coef1, coef2, sigma, philox, seed, off, n, s)
-              : ddpm_step_launch(x, eps, z, c_recip, c_recipm1, coef1, coef2, sigma, philox, seed, off, n, s);
+           uint64_t off, int64_t n, hipStream_t s, const float* shape, int64_t sper) const {
+    return on ? ddpm_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, coef1, coef2, sigma, philox, seed, off, n, s, shape)
+              : ddpm_step_launch(x, eps, z, c_recip, c_recipm1, coef1, coef2, sigma, philox, seed, off, n, s, shape, sper);
   }
 };
 // x2 = x | x, cond2 = cond | none_value, labels2 = labels | null_label: built once per call
@@ -342,12 +345,16 @@ struct LoopSched {
   const float* ms_c0 = nullptr;
   const float* ms_c1 = nullptr;
   float* hist = nullptr;               // the previous step's data prediction (n elements, behind the entry point's workspace)
+  // mi355_ddpm_shaped_sample with shaping on: every predictor step is preceded by the statistics launch that fills shape [batch][2], and reads it
+  const mi355_x0_shaping* shaping = nullptr;
+  float* shape = nullptr;              // behind the entry point's workspace
 };
 // emb: row i = the evaluation of step i (ddpm_times(Ns), or a schedule's tau_i / train_steps), selected whenever step i runs, revisits included.
 int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const DdpmLoop& a, const LoopSched& ls, int channels, const mi355_ddpm_tables* tb,
               const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch, int64_t n, hipStream_t s) {
   const int mode = opt->mode, Ns = tb->Ns;
   const int64_t n_al = (n + 3) / 4 * 4;
+  const int64_t sper = n / batch;   // elements per image (the shaping rows)
   float* x = a.state;
   UnetRun run = uniform_t_run(), run_corr = uniform_t_run();
   run.labels = a.labels_pred;
@@ -373,21 +380,24 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     if ((rc = emb.select(run, (size_t)i, a.evalB, s))) return rc;
     run_corr.emb_row = run.emb_row;
     if ((rc = unet_forward(net, x, channels, a.cond_pred, channels, sc.t, sc.v, a.evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    if (ls.shape && (rc = x0_shape_stats_launch(x, sc.v, a.guide.on, a.guide.w, a.guide.w_dev, tb->sqrt_recip_alphas_cumprod[i],
+                                                tb->sqrt_recipm1_alphas_cumprod[i], ls.shaping, ls.shape, nullptr, batch, sper, s))) return rc;
     if (mode == MI355_DDIM) {
       if (ls.ms_cx)
-        return a.guide.dpmpp(x, sc.v, ls.hist, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], ls.ms_cx[i], ls.ms_c0[i], ls.ms_c1[i], n, s);
+        return a.guide.dpmpp(x, sc.v, ls.hist, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], ls.ms_cx[i], ls.ms_c0[i], ls.ms_c1[i], n, s,
+                             ls.shape, sper);
       if (!ls.ddim_sigma)
-        return a.guide.ddim(x, sc.v, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i], n, s);
+        return a.guide.ddim(x, sc.v, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i], n, s, ls.shape, sper);
       const float* z = nullptr; int ph = 0; uint64_t off = 0;   // step 0 has acp_prev = 1: no noise term, no draw
       if (i > 0 && (rc = next_noise(z, ph, off))) return rc;
       return a.guide.ddim_eta(x, sc.v, z, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i],
-                              ls.ddim_sigma[i], ph, opt->seed, off, n, s);
+                              ls.ddim_sigma[i], ph, opt->seed, off, n, s, ls.shape, sper);
     }
     const float* z = nullptr; int ph = 0; uint64_t off = 0;
     if (i > 0 && (rc = next_noise(z, ph, off))) return rc;
     const float sigma = expf(0.5f * tb->posterior_log_variance_clipped[i]);
     if ((rc = a.guide.ddpm(x, sc.v, z, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->posterior_mean_coef1[i],
-                           tb->posterior_mean_coef2[i], sigma, ph, opt->seed, off, n, s))) return rc;
+                           tb->posterior_mean_coef2[i], sigma, ph, opt->seed, off, n, s, ls.shape, sper))) return rc;
     for (int c = 0; c < opt->n_corrector; ++c) {   // at batch B (a guided sampler's first half)
       if ((rc = unet_forward(net, x, channels, a.cond_corr, channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run_corr))) return rc;
       const float* z2 = nullptr; int ph2 = 0; uint64_t off2 = 0;
@@ -721,6 +731,57 @@ int mi355_ddpm_multistep_cfg_sample(mi355_unet* net, float* x, int channels, con
   if (int rc = ddpm_cfg_sample_run("ddpm_multistep_cfg_sample", net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, sched_times(tb->Ns, &sd), ls,
                                    nullptr, 0, batch, workspace, roomy ? workspace_bytes : 0, stream)) return rc;
   if (tb->Ns > 0) ++net->last_launches;
+  return 0;
+}
+
+// Per-image shaping of the data prediction (mi355_x0_shaping): one entry point over the six loops above.  The rows (f, s) of the images live behind
+// the workspace of the loop chosen.
+namespace {
+inline int64_t shaped_rows_offset(const mi355_unet* net, int batch, bool guided, bool multistep) {
+  return multistep ? multistep_bytes(net, batch, guided) : (int64_t)al256((size_t)layout_bytes(net, batch, guided, 0));
+}
+inline int64_t shaped_bytes(const mi355_unet* net, int batch, bool guided, bool multistep) {
+  return shaped_rows_offset(net, batch, guided, multistep) + (int64_t)al256((size_t)batch * 2 * 4);
+}
+}  // namespace
+
+int64_t mi355_ddpm_shaped_workspace_bytes(const mi355_unet* net, int batch, int guided, int multistep) {
+  if (!net || batch <= 0) { mi355_set_error("ddpm_shaped_workspace_bytes: bad argument"); return -1; }
+  return shaped_bytes(net, batch, guided != 0, multistep != 0);
+}
+
+int mi355_ddpm_shaped_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, int guided, float w,
+                             const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                             const mi355_multistep_schedule* msched, const mi355_x0_shaping* shaping, const float* noise, int64_t n_noise_draws,
+                             int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "ddpm_shaped_sample";
+  MI355_REQUIRE(tb && opt, -1, "ddpm_shaped_sample: tables or opt is null");
+  MI355_REQUIRE(!(sched && msched), -1, "ddpm_shaped_sample: both sched and msched given (a run follows one schedule)");
+  if (int rc = check_x0_shaping(who, shaping, guided)) return rc;   // these refusals need no handle
+  const bool g = guided != 0, on = shaping && (shaping->quantile > 0.f || shaping->rescale_phi > 0.f);
+  mi355_ddpm_schedule sd; LoopSched ls;
+  std::vector<float> th;
+  if (msched) {
+    MI355_REQUIRE(!noise, -1, "ddpm_shaped_sample: noise given with msched (the multistep solver is deterministic and draws none)");
+    if (int rc = check_multistep(who, tb, opt, msched, g, sd, ls)) return rc;
+    th = sched_times(tb->Ns, &sd);
+  } else if (sched) {
+    if (int rc = check_schedule(who, tb, opt, sched, g, ls)) return rc;
+    th = sched_times(tb->Ns, sched);
+  } else {
+    th = ddpm_times(tb->Ns);
+  }
+  MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_shaped_sample: bad argument (net, x, workspace, batch)");
+  const bool roomy = workspace_bytes >= shaped_bytes(net, batch, g, msched != nullptr);
+  // a short workspace is refused by the guided run's own size check, its last refusal, so that its other refusals keep their order
+  MI355_REQUIRE(roomy || g, -2, "ddpm_shaped_sample: workspace too small");
+  char* const ws = static_cast<char*>(workspace);
+  if (msched) ls.hist = roomy ? reinterpret_cast<float*>(ws + multistep_hist_offset(net, batch, g)) : nullptr;
+  if (on && roomy) { ls.shaping = shaping; ls.shape = reinterpret_cast<float*>(ws + shaped_rows_offset(net, batch, g, msched != nullptr)); }
+  if (int rc = g ? ddpm_cfg_sample_run(who, net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, th, ls, noise, n_noise_draws, batch, workspace,
+                                       roomy ? workspace_bytes : 0, stream)
+                 : ddpm_sample_run(who, net, x, channels, cond, tb, opt, th, ls, noise, n_noise_draws, batch, workspace, workspace_bytes, stream)) return rc;
+  if (tb->Ns > 0) net->last_launches += on ? 2 : 1;   // mi355_unet_get_stats: the last evaluation, the statistics launch, the step launch
   return 0;
 }
 

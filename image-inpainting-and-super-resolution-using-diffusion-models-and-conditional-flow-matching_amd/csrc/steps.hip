@@ -8,6 +8,9 @@
 //   clip / uint8 / unit range   sampling.py:13-14, cifar10/compute_fid.py:87, cifar10/utils_cifar.py:40-41
 // Noise is either injected (a pre-drawn tensor, for parity with the reference's torch.randn_like
 // stream) or generated in-kernel with Philox4x32-10 + Box-Muller keyed by (seed, element index).
+#include <cmath>
+#include <string>
+
 #include "ops.h"
 
 // torch evaluates a*x - b*e as mul, mul, sub (three roundings); keep that shape so the ill-conditioned
@@ -84,6 +87,79 @@ __device__ inline void noise4(const float* z, int use_philox, uint64_t seed, uin
   else { zz[0] = zz[1] = zz[2] = zz[3] = 0.f; }
 }
 
+// x0_hat before its clip, the ONE expression every predictor step and x0_shape_stats_kernel evaluate (product, product, difference: this file has
+// contraction off), so that the order statistic the stats kernel selects is an element of what the step clamps
+__device__ inline float x0_pre(float c_recip, float c_recipm1, float x, float e) { return c_recip * x - c_recipm1 * e; }
+// classifier-free guidance of one element: eps_u + w (eps_c - eps_u), the difference, the product and the sum each rounded
+__device__ inline float cfg_mix(float ec, float eu, float w) {
+  const float d = ec - eu;
+  const float p = w * d;
+  return eu + p;
+}
+__device__ inline void cfg_eps4(const float* eps, int64_t n, float w, const float* w_dev, int64_t per, int64_t i, int cnt, float (&ev)[4]) {
+  float ec[4], eu[4], wv[4] = {w, w, w, w};
+  ld4(eps, i, cnt, ec); ld4(eps + n, i, cnt, eu);
+  if (w_dev) {   // a group of four may straddle images when per % 4 != 0
+    int64_t img = i / per, r = i - img * per;
+    for (int l = 0; l < cnt; ++l) {
+      while (r >= per) { r -= per; ++img; }
+      wv[l] = w_dev[img];
+      ++r;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ev[j] = cfg_mix(ec[j], eu[j], wv[j]);
+}
+
+// Where a predictor step takes its eps from.  CFG false: eps [n].  CFG true, the classifier-free-guided forms: eps holds 2n values, the conditional
+// evaluation in [0, n) and the unconditional one in [n, 2n) (one network call at twice the batch), combined by cfg_eps4; x then holds the duplicated state
+// [2n]: the first half is read, the result goes to both halves.  w_dev (optional): one scale per image of `per` elements.
+template <bool CFG> struct EpsSrc {
+  const float* eps; int64_t n; float w; const float* w_dev; int64_t per;
+  __device__ inline void load(int64_t i, int cnt, float (&ev)[4]) const {
+    if constexpr (CFG) cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
+    else ld4(eps, i, cnt, ev);
+  }
+  __device__ inline void store(float* x, int64_t i, int cnt, const float (&v)[4]) const {
+    st4(x, i, cnt, v);
+    if constexpr (CFG) st4(x + n, i, cnt, v);
+  }
+};
+
+// How a predictor step ends its data prediction.  SH false: x0_hat = clip(x0_pre, -1, 1), the reference's process_x0; no row is read.  SH true
+// (mi355_x0_shaping): image b of `per` elements has the row shape[b] = (f, s) of x0_shape_stats_kernel; eps is scaled by f (guidance rescale), x0_hat =
+// clip(x0_pre, -s, s) / s (dynamic thresholding).  A row (1, 1) gives the static clip's bits: 1 * eps and a division by 1 are exact.
+template <bool SH> struct X0Rows {
+  const float* shape; int64_t per;
+  __device__ inline void load(int64_t i, int cnt, float (&f)[4], float (&s)[4]) const {
+    if constexpr (SH) {
+#pragma unroll
+      for (int l = 0; l < 4; ++l) { f[l] = 1.f; s[l] = 1.f; }
+      int64_t img = i / per, r = i - img * per;   // a group of four may straddle images when per % 4 != 0
+      for (int l = 0; l < cnt; ++l) {
+        while (r >= per) { r -= per; ++img; }
+        f[l] = shape[2 * img]; s[l] = shape[2 * img + 1];
+        ++r;
+      }
+    }
+  }
+  __device__ inline float x0(float c_recip, float c_recipm1, float x, float e, float f, float s) const {
+    if constexpr (SH) return clip_nan(x0_pre(c_recip, c_recipm1, x, f * e), -s, s) / s;
+    else return clip_nan(x0_pre(c_recip, c_recipm1, x, e), -1.f, 1.f);
+  }
+};
+// run f(EpsSrc<CFG>, X0Rows<SH>) for the form a launcher was asked for
+template <typename F> int step_form(bool cfg, const float* eps, int64_t n, float w, const float* w_dev, int64_t per, const float* shape, F&& f) {
+  if (cfg) {
+    const EpsSrc<true> e{eps, n, w, w_dev, per};
+    return shape ? f(e, X0Rows<true>{shape, per}) : f(e, X0Rows<false>{nullptr, 0});
+  }
+  const EpsSrc<false> e{eps, n, 0.f, nullptr, 0};
+  return shape ? f(e, X0Rows<true>{shape, per}) : f(e, X0Rows<false>{nullptr, 0});
+}
+#define MI355_SHAPE_ARGS(name) \
+  MI355_REQUIRE(!shape || (per > 0 && n % per == 0), -1, name ": per-image shaping rows need n to be whole images of elems_per_image elements")
+
 }  // namespace
 
 int euler_step_launch(float* x, const float* v, float dt, int64_t n, hipStream_t s) {
@@ -134,21 +210,35 @@ int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, fl
   });
 }
 
-int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
-                     float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
-  MI355_REQUIRE(offset % 4 == 0, -1, "ddpm_step: the Philox offset must be a multiple of 4");
-  const uint64_t off4 = offset / 4;
+// The predictor steps.  Each has four forms, chosen by step_form: plain or classifier-free-guided (EpsSrc), static clip or per-image shaping (X0Rows).
+namespace {
+template <class E, class R>
+int ddpm_step_form(E es, R rows, float* x, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float sigma, int use_philox,
+                   uint64_t seed, uint64_t off4, int64_t n, hipStream_t s) {
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
-    float xv[4], ev[4], zz[4];
-    ld4(x, i, cnt, xv); ld4(eps, i, cnt, ev);
+    float xv[4], ev[4], zz[4], fv[4], sv[4];
+    ld4(x, i, cnt, xv);
+    es.load(i, cnt, ev);
     noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
+    rows.load(i, cnt, fv, sv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);  // predict_start_from_noise + process_x0
+      const float x0 = rows.x0(c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);   // predict_start_from_noise + process_x0
       const float mean = coef1 * x0 + coef2 * xv[j];                                // q_posterior
       xv[j] = mean + sigma * zz[j];                                                 // exp(0.5*logvar) * noise
     }
-    st4(x, i, cnt, xv);
+    es.store(x, i, cnt, xv);
+  });
+}
+}  // namespace
+
+int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
+                     float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape, int64_t per) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "ddpm_step: the Philox offset must be a multiple of 4");
+  MI355_SHAPE_ARGS("ddpm_step");
+  const uint64_t off4 = offset / 4;
+  return step_form(false, eps, n, 0.f, nullptr, per, shape, [=](auto es, auto rows) {
+    return ddpm_step_form(es, rows, x, z, c_recip, c_recipm1, coef1, coef2, sigma, use_philox, seed, off4, n, s);
   });
 }
 
@@ -171,86 +261,55 @@ int corrector_step_launch(float* x, const float* eps, const float* z, float c_re
   });
 }
 
-int ddim_step_launch(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s) {
-  const float sa = sqrtf(acp_prev), sb = sqrtf(1.0f - acp_prev);
+namespace {
+template <class E, class R>
+int ddim_step_form(E es, R rows, float* x, float c_recip, float c_recipm1, float sa, float sb, int64_t n, hipStream_t s) {
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
-    float xv[4], ev[4];
-    ld4(x, i, cnt, xv); ld4(eps, i, cnt, ev);
+    float xv[4], ev[4], fv[4], sv[4];
+    ld4(x, i, cnt, xv);
+    es.load(i, cnt, ev);
+    rows.load(i, cnt, fv, sv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
-      const float e2 = (c_recip * xv[j] - x0) / c_recipm1;
+      const float x0 = rows.x0(c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);
+      const float e2 = (c_recip * xv[j] - x0) / c_recipm1;   // the eps that x0_hat stands for: of the clipped (shaped: the thresholded) prediction
       xv[j] = sa * x0 + sb * e2;
     }
-    st4(x, i, cnt, xv);
+    es.store(x, i, cnt, xv);
   });
-}
-
-// Classifier-free-guided forms of the two steps above: eps holds 2n values, the conditional evaluation in [0, n) and the unconditional one in
-// [n, 2n) (one network call at twice the batch); eps_g = eps_u + w * (eps_c - eps_u) with the difference, the product and the sum each rounded,
-// then the arithmetic of ddpm_step_launch / ddim_step_launch on eps_g.  x holds the duplicated state [2n]: the first half is read, the result goes
-// to both halves.  w_dev (optional): one scale per image of `per` elements.  Philox: indexed by the element of the n-element state.
-namespace {
-__device__ inline void cfg_eps4(const float* eps, int64_t n, float w, const float* w_dev, int64_t per, int64_t i, int cnt, float (&ev)[4]) {
-  float ec[4], eu[4], wv[4] = {w, w, w, w};
-  ld4(eps, i, cnt, ec); ld4(eps + n, i, cnt, eu);
-  if (w_dev) {   // a group of four may straddle images when per % 4 != 0
-    int64_t img = i / per, r = i - img * per;
-    for (int l = 0; l < cnt; ++l) {
-      while (r >= per) { r -= per; ++img; }
-      wv[l] = w_dev[img];
-      ++r;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float d = ec[j] - eu[j];
-    const float p = wv[j] * d;
-    ev[j] = eu[j] + p;
-  }
 }
 }  // namespace
 
+int ddim_step_launch(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s, const float* shape, int64_t per) {
+  MI355_SHAPE_ARGS("ddim_step");
+  const float sa = sqrtf(acp_prev), sb = sqrtf(1.0f - acp_prev);
+  return step_form(false, eps, n, 0.f, nullptr, per, shape,
+                   [=](auto es, auto rows) { return ddim_step_form(es, rows, x, c_recip, c_recipm1, sa, sb, n, s); });
+}
+
+// Classifier-free-guided forms of the two steps above (EpsSrc<true>): eps_g = eps_u + w * (eps_c - eps_u) with the difference, the product and the
+// sum each rounded, then the arithmetic of ddpm_step_launch / ddim_step_launch on eps_g.  Philox: indexed by the element of the n-element state.
 int ddpm_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
-                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s,
+                         const float* shape) {
   MI355_REQUIRE(offset % 4 == 0, -1, "ddpm_cfg_step: the Philox offset must be a multiple of 4");
   MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "ddpm_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
   MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddpm_cfg_step: null argument");
+  MI355_SHAPE_ARGS("ddpm_cfg_step");
   const uint64_t off4 = offset / 4;
-  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
-    float xv[4], ev[4], zz[4];
-    ld4(x, i, cnt, xv);
-    cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
-    noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
-      const float mean = coef1 * x0 + coef2 * xv[j];
-      xv[j] = mean + sigma * zz[j];
-    }
-    st4(x, i, cnt, xv);
-    st4(x + n, i, cnt, xv);
+  return step_form(true, eps, n, w, w_dev, per, shape, [=](auto es, auto rows) {
+    return ddpm_step_form(es, rows, x, z, c_recip, c_recipm1, coef1, coef2, sigma, use_philox, seed, off4, n, s);
   });
 }
 
 int ddim_cfg_step_launch(float* x, const float* eps, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float acp_prev, int64_t n,
-                         hipStream_t s) {
+                         hipStream_t s, const float* shape) {
   MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "ddim_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
   MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_cfg_step: null argument");
+  MI355_SHAPE_ARGS("ddim_cfg_step");
   const float sa = sqrtf(acp_prev), sb = sqrtf(1.0f - acp_prev);
-  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
-    float xv[4], ev[4];
-    ld4(x, i, cnt, xv);
-    cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
-      const float e2 = (c_recip * xv[j] - x0) / c_recipm1;
-      xv[j] = sa * x0 + sb * e2;
-    }
-    st4(x, i, cnt, xv);
-    st4(x + n, i, cnt, xv);
-  });
+  return step_form(true, eps, n, w, w_dev, per, shape,
+                   [=](auto es, auto rows) { return ddim_step_form(es, rows, x, c_recip, c_recipm1, sa, sb, n, s); });
 }
 
 // DDIM(eta) step (Song et al. 2021, eq. 12) with the reference's clipped x0_hat: ddim_step_launch's x0 and e2, then
@@ -264,58 +323,55 @@ inline DdimEta ddim_eta_coefs(float acp_prev, float sigma) {
   const float r = 1.0f - acp_prev;
   return {sqrtf(acp_prev), sqrtf(fmaxf(r - s2, 0.f))};
 }
-}  // namespace
-
-int ddim_eta_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int use_philox,
-                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
-  MI355_REQUIRE(offset % 4 == 0, -1, "ddim_eta_step: the Philox offset must be a multiple of 4");
-  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_eta_step: null argument");
-  MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, "ddim_eta_step: sigma must be finite and >= 0");
-  const uint64_t off4 = offset / 4;
-  const DdimEta c = ddim_eta_coefs(acp_prev, sigma);
-  const float sa = c.sa, sb = c.sb;
-  const int noisy = z != nullptr || use_philox;
+template <class E, class R>
+int ddim_eta_step_form(E es, R rows, float* x, const float* z, float c_recip, float c_recipm1, float sa, float sb, float sigma, int noisy, int use_philox,
+                       uint64_t seed, uint64_t off4, int64_t n, hipStream_t s) {
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
-    float xv[4], ev[4], zz[4] = {0.f, 0.f, 0.f, 0.f};
-    ld4(x, i, cnt, xv); ld4(eps, i, cnt, ev);
+    float xv[4], ev[4], zz[4] = {0.f, 0.f, 0.f, 0.f}, fv[4], sv[4];
+    ld4(x, i, cnt, xv);
+    es.load(i, cnt, ev);
     if (noisy) noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
+    rows.load(i, cnt, fv, sv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
+      const float x0 = rows.x0(c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);
       const float e2 = (c_recip * xv[j] - x0) / c_recipm1;
       const float m = sa * x0 + sb * e2;
       xv[j] = noisy ? m + sigma * zz[j] : m;
     }
-    st4(x, i, cnt, xv);
+    es.store(x, i, cnt, xv);
+  });
+}
+}  // namespace
+
+int ddim_eta_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int use_philox,
+                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape, int64_t per) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "ddim_eta_step: the Philox offset must be a multiple of 4");
+  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_eta_step: null argument");
+  MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, "ddim_eta_step: sigma must be finite and >= 0");
+  MI355_SHAPE_ARGS("ddim_eta_step");
+  const uint64_t off4 = offset / 4;
+  const DdimEta c = ddim_eta_coefs(acp_prev, sigma);
+  const int noisy = z != nullptr || use_philox;
+  return step_form(false, eps, n, 0.f, nullptr, per, shape, [=](auto es, auto rows) {
+    return ddim_eta_step_form(es, rows, x, z, c_recip, c_recipm1, c.sa, c.sb, sigma, noisy, use_philox, seed, off4, n, s);
   });
 }
 
 // its classifier-free-guided form, built as ddim_cfg_step_launch: eps [2n], x [2n] (first half read, both halves written), Philox indexed by the
 // element of the n-element state
 int ddim_eta_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
-                             float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+                             float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape) {
   MI355_REQUIRE(offset % 4 == 0, -1, "ddim_eta_cfg_step: the Philox offset must be a multiple of 4");
   MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "ddim_eta_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
   MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_eta_cfg_step: null argument");
   MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, "ddim_eta_cfg_step: sigma must be finite and >= 0");
+  MI355_SHAPE_ARGS("ddim_eta_cfg_step");
   const uint64_t off4 = offset / 4;
   const DdimEta c = ddim_eta_coefs(acp_prev, sigma);
-  const float sa = c.sa, sb = c.sb;
   const int noisy = z != nullptr || use_philox;
-  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
-    float xv[4], ev[4], zz[4] = {0.f, 0.f, 0.f, 0.f};
-    ld4(x, i, cnt, xv);
-    cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
-    if (noisy) noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
-      const float e2 = (c_recip * xv[j] - x0) / c_recipm1;
-      const float m = sa * x0 + sb * e2;
-      xv[j] = noisy ? m + sigma * zz[j] : m;
-    }
-    st4(x, i, cnt, xv);
-    st4(x + n, i, cnt, xv);
+  return step_form(true, eps, n, w, w_dev, per, shape, [=](auto es, auto rows) {
+    return ddim_eta_step_form(es, rows, x, z, c_recip, c_recipm1, c.sa, c.sb, sigma, noisy, use_philox, seed, off4, n, s);
   });
 }
 
@@ -526,48 +582,225 @@ int paint_patch_launch(const float* img, const int* top, const int* left, int pa
 // evaluated as ((cx x) + (c0 D)) + (c1 hist), every product and sum rounded (8 roundings with D's three).  c1 == 0 (order 1, the first step run,
 // the last one): hist is not read and the sum ends at the second term, so an uninitialised history never reaches the state.  hist == null: D is
 // not kept.  The host coefficients are DDPM.dpm_solver_coefs.
+// With shaping rows D is the shaped x0_hat, and that is what the history keeps.
 namespace {
-__device__ inline void dpmpp4(const float (&xv)[4], const float (&ev)[4], const float (&hv)[4], float c_recip, float c_recipm1, float cx, float c0,
-                              float c1, bool two, float (&xo)[4], float (&dv)[4]) {
+template <class E, class R>
+int dpmpp_step_form(E es, R rows, float* x, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s) {
+  const bool two = c1 != 0.f;
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
+    float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4], fv[4], sv[4];
+    ld4(x, i, cnt, xv);
+    es.load(i, cnt, ev);
+    if (two) ld4(hist, i, cnt, hv);
+    rows.load(i, cnt, fv, sv);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float d = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
-    const float m = cx * xv[j] + c0 * d;
-    xo[j] = two ? m + c1 * hv[j] : m;
-    dv[j] = d;
-  }
+    for (int j = 0; j < 4; ++j) {
+      const float d = rows.x0(c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);
+      const float m = cx * xv[j] + c0 * d;
+      xv[j] = two ? m + c1 * hv[j] : m;
+      dv[j] = d;
+    }
+    es.store(x, i, cnt, xv);
+    if (hist) st4(hist, i, cnt, dv);
+  });
 }
 }  // namespace
 
-int dpmpp_step_launch(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s) {
+int dpmpp_step_launch(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s,
+                      const float* shape, int64_t per) {
   MI355_REQUIRE(n <= 0 || (x && eps), -1, "dpmpp_step: null argument");
   MI355_REQUIRE(c1 == 0.f || hist || n <= 0, -1, "dpmpp_step: c1 != 0 needs hist (the previous step's data prediction)");
-  const bool two = c1 != 0.f;
-  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
-    float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4];
-    ld4(x, i, cnt, xv); ld4(eps, i, cnt, ev);
-    if (two) ld4(hist, i, cnt, hv);
-    dpmpp4(xv, ev, hv, c_recip, c_recipm1, cx, c0, c1, two, xv, dv);
-    st4(x, i, cnt, xv);
-    if (hist) st4(hist, i, cnt, dv);
-  });
+  MI355_SHAPE_ARGS("dpmpp_step");
+  return step_form(false, eps, n, 0.f, nullptr, per, shape,
+                   [=](auto es, auto rows) { return dpmpp_step_form(es, rows, x, hist, c_recip, c_recipm1, cx, c0, c1, n, s); });
 }
 
 // its classifier-free-guided form, built as ddim_cfg_step_launch: eps [2n], x [2n] (first half read, both halves written), hist [n]
 int dpmpp_cfg_step_launch(float* x, const float* eps, float* hist, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float cx,
-                          float c0, float c1, int64_t n, hipStream_t s) {
+                          float c0, float c1, int64_t n, hipStream_t s, const float* shape) {
   MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "dpmpp_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
   MI355_REQUIRE(n <= 0 || (x && eps), -1, "dpmpp_cfg_step: null argument");
   MI355_REQUIRE(c1 == 0.f || hist || n <= 0, -1, "dpmpp_cfg_step: c1 != 0 needs hist (the previous step's data prediction)");
-  const bool two = c1 != 0.f;
-  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
-    float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4];
-    ld4(x, i, cnt, xv);
-    cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
-    if (two) ld4(hist, i, cnt, hv);
-    dpmpp4(xv, ev, hv, c_recip, c_recipm1, cx, c0, c1, two, xv, dv);
-    st4(x, i, cnt, xv);
-    st4(x + n, i, cnt, xv);
-    if (hist) st4(hist, i, cnt, dv);
-  });
+  MI355_SHAPE_ARGS("dpmpp_cfg_step");
+  return step_form(true, eps, n, w, w_dev, per, shape,
+                   [=](auto es, auto rows) { return dpmpp_step_form(es, rows, x, hist, c_recip, c_recipm1, cx, c0, c1, n, s); });
+}
+
+// ---- per-image statistics of a predictor step's data prediction (mi355_x0_shaping) -------------------------------------------------------------------
+// One workgroup per image, no communication between workgroups, no global atomics.  For image b of `per` elements, with eps_g the plain eps or
+// cfg_mix of the two halves (w, or w_dev[b]):
+//   guidance rescale (Lin et al. 2023, section 3.4): sigma_c, sigma_g = the population standard deviations of eps_c and eps_g over the image (mean first,
+//     then the centred sum of squares, fp32, in the fixed order of block_sum2), f = phi * (sigma_c / sigma_g) + (1 - phi); f = 1 when sigma_g == 0;
+//   dynamic thresholding (Saharia et al. 2022, section 2.3): lo, hi = the k-th and min(k + 1, per - 1)-th smallest of |x0_pre(x, f * eps_g)|,
+//     s_raw = lo + frac * (hi - lo) (torch.quantile's linear interpolation), s = min(max(s_raw, 1), s_max); an image with a NaN gets s = NaN.
+// The selection is exact: a radix select over the bit patterns of |x0| (non-negative floats order as their uint32; the sign bit is cleared, so -0 is
+// +0), four passes of 8 bits from the top, each a 256-bin histogram in LDS (one per wave, to spread the ds_add traffic) of the keys that carry the
+// prefix chosen so far, then a scan of the bins for the one that holds the rank.  Every pass recomputes x0 from x and eps, which sit in L2 behind
+// the evaluation that wrote them: one code path for every image size (a 3 x 128 x 128 image is 192 KiB, more than a CU's LDS).  A bin index is
+// (key >> shift) & 255 and a rank is < per, so a NaN or an infinity indexes nothing out of range and no loop depends on the data.
+namespace {
+constexpr int XS_THREADS = 1024, XS_WAVES = XS_THREADS / 64;
+struct X0StatsArgs {
+  const float* x; const float* eps; const float* w_dev; float* shape; float* detail;
+  int64_t n, per, k;
+  float w, c_recip, c_recipm1, phi, one_minus_phi, frac, s_max;
+  int guided, do_var, do_sel;
+};
+
+__global__ void __launch_bounds__(XS_THREADS) x0_shape_stats_kernel(X0StatsArgs a) {
+  __shared__ uint32_t hist[XS_WAVES][256];
+  __shared__ float redf[2][XS_WAVES];
+  __shared__ uint32_t redu[XS_WAVES];
+  __shared__ uint32_t sel[4];
+  __shared__ uint32_t any_nan;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t b = blockIdx.x, per = a.per;
+  const float* xp = a.x + b * per;
+  const float* ec = a.eps + b * per;
+  const float* eu = ec + a.n;   // read only when guided
+  const float w = a.w_dev ? a.w_dev[b] : a.w;
+  const bool guided = a.guided != 0;
+  auto eps_g = [&](int64_t j) { return guided ? cfg_mix(ec[j], eu[j], w) : ec[j]; };
+  // sums of p and q over the workgroup, the same value in every thread: butterfly inside a wave, then the waves in order
+  auto block_sum2 = [&](float& p, float& q) {
+    for (int o = 32; o > 0; o >>= 1) { p += __shfl_xor(p, o); q += __shfl_xor(q, o); }
+    __syncthreads();
+    if (lane == 0) { redf[0][wv] = p; redf[1][wv] = q; }
+    __syncthreads();
+    p = 0.f; q = 0.f;
+    for (int i = 0; i < XS_WAVES; ++i) { p += redf[0][i]; q += redf[1][i]; }
+  };
+
+  float f = 1.f, sig_c = 0.f, sig_g = 0.f;
+  if (a.do_var) {
+    float sc = 0.f, sg = 0.f;
+    for (int64_t j = tid; j < per; j += XS_THREADS) { sc += ec[j]; sg += eps_g(j); }
+    block_sum2(sc, sg);
+    const float mc = sc / (float)per, mg = sg / (float)per;
+    float qc = 0.f, qg = 0.f;
+    for (int64_t j = tid; j < per; j += XS_THREADS) {
+      const float dc = ec[j] - mc, dg = eps_g(j) - mg;
+      qc += dc * dc; qg += dg * dg;
+    }
+    block_sum2(qc, qg);
+    sig_c = sqrtf(qc / (float)per); sig_g = sqrtf(qg / (float)per);
+    if (a.phi != 0.f && sig_g != 0.f) f = a.phi * (sig_c / sig_g) + a.one_minus_phi;
+  }
+
+  float s = 1.f, s_raw = 0.f;
+  if (a.do_sel) {
+    auto key_of = [&](int64_t j) { return __float_as_uint(x0_pre(a.c_recip, a.c_recipm1, xp[j], f * eps_g(j))) & 0x7fffffffu; };
+    uint32_t prefix = 0, rank = (uint32_t)a.k, eq = 0, saw_nan = 0;
+    if (tid == 0) any_nan = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+      const int shift = 24 - 8 * pass;
+      const uint32_t mask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
+      for (int t = tid; t < XS_WAVES * 256; t += XS_THREADS) (&hist[0][0])[t] = 0;
+      __syncthreads();
+      for (int64_t j = tid; j < per; j += XS_THREADS) {
+        const uint32_t key = key_of(j);
+        saw_nan |= key > 0x7f800000u;
+        if ((key & mask) == prefix) atomicAdd(&hist[wv][(key >> shift) & 255u], 1u);
+      }
+      __syncthreads();
+      uint32_t c = 0, incl = 0;
+      if (tid < 256) {   // bin tid: its count over the waves, then an inclusive scan over the 256 bins (waves 0..3 whole)
+        for (int i = 0; i < XS_WAVES; ++i) c += hist[i][tid];
+        incl = c;
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+        if (lane == 63) redu[wv] = incl;
+      }
+      __syncthreads();
+      if (tid < 256) {
+        for (int i = 0; i < wv; ++i) incl += redu[i];
+        const uint32_t excl = incl - c;
+        if (rank >= excl && rank < incl) { sel[0] = (uint32_t)tid; sel[1] = rank - excl; sel[2] = c; }   // exactly one bin: rank < the keys counted
+      }
+      __syncthreads();
+      prefix |= sel[0] << shift; rank = sel[1]; eq = sel[2];
+    }
+    // prefix is the k-th smallest key, one of `eq` equal keys, and the k-th is number `rank` among them.  The next one in order is the same value, or
+    // the smallest key above it; none above (k = per - 1): min(k + 1, per - 1) = k.
+    uint32_t mn = 0xffffffffu;
+    for (int64_t j = tid; j < per; j += XS_THREADS) { const uint32_t key = key_of(j); if (key > prefix && key < mn) mn = key; }
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(mn, o); mn = v < mn ? v : mn; }
+    if (saw_nan) any_nan = 1;
+    if (lane == 0) redu[wv] = mn;   // the scan's last read of redu lies before the loop's last barrier
+    __syncthreads();
+    for (int i = 0; i < XS_WAVES; ++i) mn = redu[i] < mn ? redu[i] : mn;
+    const uint32_t hi_key = (rank + 1 < eq || mn == 0xffffffffu) ? prefix : mn;
+    const float lo = __uint_as_float(prefix), hi = __uint_as_float(hi_key);
+    const float d = hi - lo;
+    const float t = a.frac * d;
+    s_raw = any_nan ? __builtin_nanf("") : lo + t;
+    s = s_raw != s_raw ? s_raw : (s_raw < 1.f ? 1.f : s_raw);
+    if (a.s_max > 0.f && s > a.s_max) s = a.s_max;
+  }
+  if (tid == 0) {
+    a.shape[2 * b] = f; a.shape[2 * b + 1] = s;
+    if (a.detail) { float* dt = a.detail + 4 * b; dt[0] = sig_c; dt[1] = sig_g; dt[2] = s_raw; dt[3] = 0.f; }
+  }
+}
+}  // namespace
+
+int check_x0_shaping(const char* who, const mi355_x0_shaping* sh, int guided) {
+  if (!sh) return 0;
+  const std::string f = std::string(who) + ": ";
+  MI355_REQUIRE(sh->quantile >= 0.f && sh->quantile <= 1.f, -1, f + "shaping->quantile must be finite and in [0, 1] (0: thresholding off)");
+  MI355_REQUIRE(sh->max_threshold == 0.f || sh->max_threshold >= 1.f, -1, f + "shaping->max_threshold must be 0 (no cap) or >= 1");
+  MI355_REQUIRE(sh->rescale_phi >= 0.f && sh->rescale_phi <= 1.f, -1, f + "shaping->rescale_phi must be in [0, 1]");
+  MI355_REQUIRE(sh->rescale_phi == 0.f || guided, -1,
+                f + "shaping->rescale_phi > 0 needs guided != 0 (the rescale compares the guided eps with the conditional one)");
+  return 0;
+}
+
+int x0_shape_stats_launch(const float* x, const float* eps, int guided, float w, const float* w_dev, float c_recip, float c_recipm1,
+                          const mi355_x0_shaping* sh, float* shape, float* detail, int batch, int64_t per, hipStream_t s) {
+  if (int rc = check_x0_shaping("x0_shape_stats", sh, guided)) return rc;
+  MI355_REQUIRE(x, -1, "x0_shape_stats: x is null");
+  MI355_REQUIRE(eps, -1, "x0_shape_stats: eps is null");
+  MI355_REQUIRE(shape, -1, "x0_shape_stats: shape is null");
+  MI355_REQUIRE(batch > 0, -1, "x0_shape_stats: batch must be > 0");
+  MI355_REQUIRE(per > 0 && per <= ((int64_t)1 << 30), -1, "x0_shape_stats: elems_per_image must be in [1, 2^30]");
+  X0StatsArgs a = {};
+  a.x = x; a.eps = eps; a.w_dev = guided ? w_dev : nullptr; a.shape = shape; a.detail = detail;
+  a.n = (int64_t)batch * per; a.per = per;
+  a.w = w; a.c_recip = c_recip; a.c_recipm1 = c_recipm1;
+  a.guided = guided != 0;
+  const float q = sh ? sh->quantile : 0.f, phi = sh ? sh->rescale_phi : 0.f;
+  a.phi = phi; a.one_minus_phi = 1.0f - phi;
+  a.s_max = sh ? sh->max_threshold : 0.f;
+  a.do_var = phi != 0.f || detail != nullptr;
+  a.do_sel = q > 0.f;
+  if (a.do_sel) {   // torch.quantile's position: q (per - 1) in double, its floor and its fraction
+    const double pos = (double)q * (double)(per - 1);
+    a.k = (int64_t)std::floor(pos);
+    if (a.k > per - 1) a.k = per - 1;
+    a.frac = (float)(pos - (double)a.k);
+  }
+  hipLaunchKernelGGL(x0_shape_stats_kernel, dim3((unsigned)batch), dim3(XS_THREADS), 0, s, a);
+  MI355_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// One shaped (or, shape == null, unshaped) predictor step chosen by number: the test layer's view of the eight forms above.
+int x0_shaped_step_launch(int kind, float* x, const float* eps, const float* z, float* hist, int guided, float w, const float* w_dev, int64_t per,
+                          float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed, uint64_t offset,
+                          const float* shape, int64_t n, hipStream_t s) {
+  MI355_REQUIRE(kind >= 0 && kind <= 3, -1, "x0_shaped_step: kind must be 0 (ancestral), 1 (DDIM), 2 (DDIM(eta)) or 3 (DPM-Solver++)");
+  MI355_REQUIRE(per > 0 && n % per == 0, -1, "x0_shaped_step: n must be whole images of elems_per_image elements");
+  switch (kind) {
+    case 0:
+      return guided ? ddpm_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, a, b, sigma, use_philox, seed, offset, n, s, shape)
+                    : ddpm_step_launch(x, eps, z, c_recip, c_recipm1, a, b, sigma, use_philox, seed, offset, n, s, shape, per);
+    case 1:
+      return guided ? ddim_cfg_step_launch(x, eps, w, w_dev, per, c_recip, c_recipm1, a, n, s, shape)
+                    : ddim_step_launch(x, eps, c_recip, c_recipm1, a, n, s, shape, per);
+    case 2:
+      return guided ? ddim_eta_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, a, sigma, use_philox, seed, offset, n, s, shape)
+                    : ddim_eta_step_launch(x, eps, z, c_recip, c_recipm1, a, sigma, use_philox, seed, offset, n, s, shape, per);
+    default:
+      return guided ? dpmpp_cfg_step_launch(x, eps, hist, w, w_dev, per, c_recip, c_recipm1, a, b, c, n, s, shape)
+                    : dpmpp_step_launch(x, eps, hist, c_recip, c_recipm1, a, b, c, n, s, shape, per);
+  }
 }

@@ -14,7 +14,9 @@ Two execution paths, both entirely on the HIP backend:
 Noise: by default drawn in-kernel (Philox4x32-10, seeded from torch.initial_seed()); parity tests
 inject the draws of the reference's `torch.randn_like` call sequence with `injected_noise([...])`.
 Build-defined extensions without a reference counterpart: get_ddim_sample_fn (DDIM(eta)) and get_dpm_solver_sample_fn (DPM-Solver++ multistep,
-orders 1 and 2: one evaluation and one step kernel per step, the previous step's data prediction kept on the device).
+orders 1 and 2: one evaluation and one step kernel per step, the previous step's data prediction kept on the device).  A chain made by
+DDPM.with_x0_shaping(...) has every sampler here end its predictor steps' data prediction per image (dynamic thresholding, guidance rescale) instead of
+with the static clip: the fast path in mi355_ddpm_shaped_sample, the generic one through x0_shape_stats and x0_shaped_step_; sample quality untested.
 ReconstructionGuidance (sampling.py:136-206) differentiates the x0 model through the U-Net: the gradient is the HIP engine's
 vector-Jacobian product (`UNetEngine.vjp`, csrc/unet_backward.hip) of a differentiable plan of the same network, so it needs an
 `eps_model` made by `make_eps_model(network, ddpm)` around a `UNetModel`.
@@ -150,10 +152,31 @@ def _tables(ddpm: DDPM):
     return ddpm.host_tables()
 
 
-def _predictor(eps, xi, i, T, noise: _Noise):
-    """step() (sampling.py:59-67): x0_hat -> clip -> posterior mean -> + exp(0.5 logvar) z (z iff i > 0)."""
+def _shaping_of(ddpm, guided: bool):
+    """ddpm.x0_shaping (DDPM.with_x0_shaping; None on a plain chain), refused where it asks an unguided sampler for the guidance rescale."""
+    shaping = getattr(ddpm, "x0_shaping", None)
+    if shaping is not None and shaping.guidance_rescale > 0.0 and not guided:
+        raise ValueError("guidance_rescale > 0 rescales the guided eps against the conditional one: it needs a guided sampler "
+                         "(ClassifierFreeGuidance, or guidance_scale=)")
+    return shaping
+
+
+def _shape_rows(xi, eps, i, T, shaping, w=None):
+    """The per-image rows (f, s) of step i's shaped data prediction, or None without shaping.  w: eps is the [2B] pair of a guided step."""
+    if shaping is None:
+        return None
+    return _ops.x0_shape_stats(xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), shaping, w=w)
+
+
+def _predictor(eps, xi, i, T, noise: _Noise, shape=None):
+    """step() (sampling.py:59-67): x0_hat -> clip -> posterior mean -> + exp(0.5 logvar) z (z iff i > 0).  shape: the rows of _shape_rows
+    (per-image shaping in place of the clip)."""
     z, ph = noise.next() if i > 0 else (None, None)
     sigma = float((0.5 * T["posterior_log_variance_clipped"][i]).exp())  # fp32, like (0.5*logvar).exp()
+    if shape is not None:
+        _ops.x0_shaped_step_("ddpm", xi, eps, shape, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
+                             float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i]), sigma=sigma, z=z, philox=ph)
+        return xi
     _ops.ddpm_step_(xi, eps, z, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
                     float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i]), sigma, ph)
     return xi
@@ -187,6 +210,7 @@ def _walk_moves(Ns, walk):
 
 def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replacement=None, n_corrector=0, delta=0.1, walk=None):
     T = _tables(ddpm)
+    shaping = _shaping_of(ddpm, False)
     xi = xT.detach().clone().float().contiguous()
     noise = _Noise(xi)
     for level, down in _walk_moves(ddpm.Ns, walk):
@@ -199,37 +223,42 @@ def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replac
             z, ph = noise.next() if replacement["noise"] else (None, None)
             _ops.replace_mask_(xi, replacement["condition"], z, replacement["pad_value"], replacement["noise"],
                                float(T["sqrt_alphas_cumprod"][i]), float(T["sqrt_one_minus_alphas_cumprod"][i]), ph)
-        eps = eps_model(_net_in(xi, cond_pred, amortized), _times(xi, i))
-        _predictor(eps.float().contiguous(), xi, i, T, noise)
+        eps = eps_model(_net_in(xi, cond_pred, amortized), _times(xi, i)).float().contiguous()
+        _predictor(eps, xi, i, T, noise, _shape_rows(xi, eps, i, T, shaping))
         for _ in range(n_corrector):
             eps = eps_model(_net_in(xi, cond_corr, amortized), _times(xi, i))
             _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise)
     return process_x0(xi)
 
 
-def _ddim_move(eps, xi, i, T, sigma, noise):
-    """One DDIM step: sigma None = the deterministic kernel; else DDIM(eta) with sigma[i] and one draw iff i > 0."""
+def _ddim_move(eps, xi, i, T, sigma, noise, shape=None):
+    """One DDIM step: sigma None = the deterministic kernel; else DDIM(eta) with sigma[i] and one draw iff i > 0.  shape: as in _predictor."""
     cr, crm1, prev = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), float(T["alphas_cumprod_prev"][i])
     if sigma is None:
-        return _ops.ddim_step_(xi, eps, cr, crm1, prev)
+        return _ops.ddim_step_(xi, eps, cr, crm1, prev) if shape is None else _ops.x0_shaped_step_("ddim", xi, eps, shape, cr, crm1, prev)
     z, ph = noise.next() if i > 0 else (None, None)
+    if shape is not None:
+        return _ops.x0_shaped_step_("ddim_eta", xi, eps, shape, cr, crm1, prev, sigma=float(sigma[i]), z=z, philox=ph)
     return _ops.ddim_eta_step_(xi, eps, z, cr, crm1, prev, float(sigma[i]), ph)
 
 
 def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corrector=0, delta=0.1, ddim=False, ddim_sigma=None):
     """The guided host loop for any eps_model callable: two calls per predictor step (condition, none_like), cfg_combine, the step kernel;
-    correctors as in _run_generic (the net sees none_like)."""
+    correctors as in _run_generic (the net sees none_like).  With shaping the rows come from the pair (the rescale needs eps_c beside eps_g)."""
     T = _tables(ddpm)
+    shaping = _shaping_of(ddpm, True)
     xi = xT.detach().clone().float().contiguous()
     noise = _Noise(xi)
     for i in reversed(range(ddpm.Ns)):
         ec = eps_model(_net_in(xi, cond, True), _times(xi, i)).float()
         eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
-        eps = _ops.cfg_combine(torch.cat((ec, eu)).contiguous(), guidance_scale)
+        eps2 = torch.cat((ec, eu)).contiguous()
+        shape = _shape_rows(xi, eps2, i, T, shaping, w=guidance_scale)
+        eps = _ops.cfg_combine(eps2, guidance_scale)
         if ddim:
-            _ddim_move(eps, xi, i, T, ddim_sigma, noise)
+            _ddim_move(eps, xi, i, T, ddim_sigma, noise, shape)
             continue
-        _predictor(eps, xi, i, T, noise)
+        _predictor(eps, xi, i, T, noise, shape)
         for _ in range(n_corrector):
             eps = eps_model(_net_in(xi, none, True), _times(xi, i))
             _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise)
@@ -252,9 +281,14 @@ def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_f
         # the scheduled entry points: a respaced chain's steps in training time (an unrespaced one's: 0..Ns-1 of Ns)
         sched = dict(timesteps=getattr(ddpm, "timesteps", None) or tuple(range(ddpm.Ns)), train_steps=int(getattr(ddpm, "base_Ns", ddpm.Ns)),
                      ddim_sigma=ddim_sigma, walk=walk)
-    engine.ddpm_sample(xi, _tables(ddpm), mode=mode, cond=cond, noise=noise, n_corrector=n_corrector, delta=float(delta),
-                       tmin=ddpm.tmin, tmax=ddpm.tmax, start_fraction=float(start_fraction), noise_condition=bool(noise_condition),
-                       pad_value=float(pad_value), none_value=float(none_value), seed=seed, guidance_scale=guidance_scale, **sched)
+    kw = dict(mode=mode, cond=cond, noise=noise, n_corrector=n_corrector, delta=float(delta), tmin=ddpm.tmin, tmax=ddpm.tmax,
+              start_fraction=float(start_fraction), noise_condition=bool(noise_condition), pad_value=float(pad_value), none_value=float(none_value),
+              seed=seed, guidance_scale=guidance_scale, **sched)
+    shaping = _shaping_of(ddpm, guidance_scale is not None)
+    if shaping is not None:   # the same loop with per-image shaping of x0_hat: mi355_ddpm_shaped_sample
+        engine.ddpm_shaped(xi, _tables(ddpm), shaping, **kw)
+    else:
+        engine.ddpm_sample(xi, _tables(ddpm), **kw)
     return xi
 
 
@@ -344,6 +378,9 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
             "a UNetModel (an arbitrary callable has no backward pass on the HIP backend)")
     if conditioning.update_rule not in ("before", "after"):
         raise ValueError(f"unknown update_rule {conditioning.update_rule!r}")
+    if getattr(ddpm, "x0_shaping", None) is not None:
+        raise NotImplementedError("ReconstructionGuidance differentiates the clipped x0_hat through the network: per-image x0 shaping "
+                                  "(DDPM.with_x0_shaping) is not built into that gradient - pass the unshaped chain")
     if hasattr(likelihood, "pad_value"):
         mode, pad = 0, float(likelihood.pad_value)      # Painting.loss (likelihoods.py:58-66)
     elif type(likelihood).__name__ == "HyperResolution":
@@ -430,6 +467,7 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
     callable: a host loop over dpmpp_step_ (guided: cfg_combine, then the step).  Sample quality is untested."""
     coefs = ddpm.dpm_solver_coefs(order)
     cx, c0, c1 = (c.tolist() for c in coefs)
+    shaping = _shaping_of(ddpm, guidance_scale is not None)
 
     @torch.no_grad()
     def sample(xT, condition=None):
@@ -445,18 +483,29 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
             sched = {}
             if getattr(ddpm, "timesteps", None) is not None:
                 sched = dict(timesteps=ddpm.timesteps, train_steps=int(ddpm.base_Ns))
+            if shaping is not None:
+                return engine.ddpm_shaped(xi, T, shaping, mode=_lib.DDIM, coefs=coefs, cond=condition, none_value=nv, guidance_scale=guidance_scale,
+                                          **sched)
             return engine.ddpm_multistep(xi, T, coefs, cond=condition, none_value=nv, guidance_scale=guidance_scale, **sched)
         none = None
         if guidance_scale is not None:
             none = likelihood.none_like(xT) if likelihood is not None else torch.zeros_like(condition)
         hist = torch.empty_like(xi)
         for i in reversed(range(ddpm.Ns)):
-            eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i)).float()
+            eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i)).float().contiguous()
+            shape = None
             if none is not None:
                 eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
-                eps = _ops.cfg_combine(torch.cat((eps, eu)).contiguous(), guidance_scale)
-            _ops.dpmpp_step_(xi, eps.contiguous(), hist, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
-                             cx[i], c0[i], c1[i])
+                eps2 = torch.cat((eps, eu)).contiguous()
+                shape = _shape_rows(xi, eps2, i, T, shaping, w=guidance_scale)
+                eps = _ops.cfg_combine(eps2, guidance_scale)
+            else:
+                shape = _shape_rows(xi, eps, i, T, shaping)
+            cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
+            if shape is not None:
+                _ops.x0_shaped_step_("dpmpp", xi, eps, shape, cr, crm1, cx[i], c0[i], c1[i], hist=hist)
+            else:
+                _ops.dpmpp_step_(xi, eps, hist, cr, crm1, cx[i], c0[i], c1[i])
         return process_x0(xi)
 
     return sample
@@ -472,6 +521,7 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
     if not (math.isfinite(eta) and eta >= 0.0):
         raise ValueError(f"eta must be finite and >= 0, got {eta!r}")
     sigma = ddpm.ddim_sigma(eta) if eta != 0.0 else None
+    shaping = _shaping_of(ddpm, guidance_scale is not None)
 
     @torch.no_grad()
     def sample(xT, condition=None):
@@ -490,8 +540,8 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
         xi = xT.detach().clone().float().contiguous()
         noise = _Noise(xi) if sigma is not None else None
         for i in reversed(range(ddpm.Ns)):
-            eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i))
-            _ddim_move(eps.float().contiguous(), xi, i, T, sigma, noise)
+            eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i)).float().contiguous()
+            _ddim_move(eps, xi, i, T, sigma, noise, _shape_rows(xi, eps, i, T, shaping))
         return process_x0(xi)
 
     return sample

@@ -6,7 +6,10 @@ elementwise kernels lives in csrc/steps.hip and is driven by `image_diffusion.sa
 """
 from __future__ import annotations
 
-from typing import Callable
+import copy
+import math
+from dataclasses import dataclass
+from typing import Callable, Optional
 
 import numpy as np
 import torch
@@ -41,9 +44,40 @@ def extract(a, t, x_shape):
     return out.reshape(b, *((1,) * (len(x_shape) - 1)))
 
 
+@dataclass(frozen=True)
+class X0Shaping:
+    """What a shaped DDPM view carries (DDPM.with_x0_shaping; mi355_x0_shaping in include/mi355_sampler.h): None / 0.0 = that part is off."""
+    dynamic_threshold: Optional[float] = None   # the quantile p in (0, 1] of |x0_hat| over an image (Saharia et al. 2022)
+    max_threshold: Optional[float] = None       # cap of the threshold, >= 1
+    guidance_rescale: float = 0.0               # phi in [0, 1] (Lin et al. 2023)
+
+
+def _x0_shaping(dynamic_threshold, max_threshold, guidance_rescale) -> Optional[X0Shaping]:
+    """The library's refusals (mi355_ddpm_shaped_sample), as ValueError; everything off: None."""
+    def num(v, name):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number, got {v!r}")
+        return float(v)
+
+    q = None if dynamic_threshold is None else num(dynamic_threshold, "dynamic_threshold")
+    if q is not None and not (math.isfinite(q) and 0.0 < q <= 1.0):
+        raise ValueError(f"dynamic_threshold must be a quantile in (0, 1] (None: off), got {dynamic_threshold!r}")
+    m = None if max_threshold is None else num(max_threshold, "max_threshold")
+    if m is not None and not m >= 1.0:
+        raise ValueError(f"max_threshold must be >= 1 (None: no cap), got {max_threshold!r}")
+    phi = num(guidance_rescale, "guidance_rescale")
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale!r}")
+    if q is None and phi == 0.0:
+        return None
+    return X0Shaping(q, m, phi)
+
+
 class DDPM(nn.Module):
     """sde_diffusion.py:107-167.  `DDPM(Ns <= 20)` has non-finite entries exactly like the reference
     (betas[-1] = 20/Ns >= 1): this is reproduced, not repaired (SURVEY.md finding 4)."""
+
+    x0_shaping: Optional[X0Shaping] = None   # set on the views of with_x0_shaping
 
     def __init__(self, Ns: int):
         super().__init__()
@@ -178,6 +212,20 @@ class DDPM(nn.Module):
         targets = np.linspace(lam[0], lam[-1], int(K))
         return tuple(sorted({int(np.argmin(np.abs(lam - t))) for t in targets}))
 
+    def with_x0_shaping(self, dynamic_threshold=None, max_threshold=None, guidance_rescale=0.0) -> "DDPM":
+        """BUILD-DEFINED EXTENSION (no reference counterpart): a view of this chain - the same buffers, the same steps - whose samplers end every
+        predictor step's data prediction per image instead of with the static clip to [-1, 1] (`x0_shaping`; the fused loops:
+        mi355_ddpm_shaped_sample).  dynamic_threshold: the quantile p in (0, 1] of |x0_hat| over the image; s = min(max(quantile, 1),
+        max_threshold), x0_hat <- clamp(x0_hat, -s, s) / s (Saharia et al. 2022, Imagen, section 2.3).  guidance_rescale: phi in [0, 1], the guided
+        eps is scaled by phi * std(eps_c) / std(eps_g) + 1 - phi per image (Lin et al. 2023, section 3.4); guided samplers only.  Commutes with
+        respace.  All off: a view without shaping.  The corrector and the final clip keep the static clip.  Sample quality is untested."""
+        view = copy.copy(self)
+        # its own registries over the same tensors: moving the view does not re-point the base's buffers
+        view.__dict__["_buffers"] = self._buffers.copy()
+        view.__dict__["_non_persistent_buffers_set"] = set(self._non_persistent_buffers_set)
+        view.__dict__["x0_shaping"] = _x0_shaping(dynamic_threshold, max_threshold, guidance_rescale)
+        return view
+
     def respace(self, timesteps) -> "RespacedDDPM":
         """This chain on the sub-sequence `timesteps` of its steps (RespacedDDPM)."""
         return RespacedDDPM(self, timesteps)
@@ -235,6 +283,7 @@ class RespacedDDPM(DDPM):
         self.base_Ns = base_Ns
         self.Ns = len(steps)
         self.tmin, self.tmax, self.ts = base.tmin, base.tmax, base.ts
+        self.x0_shaping = getattr(base, "x0_shaping", None)   # a shaped base's respacing stays shaped
         acp32 = base.alphas_cumprod.detach().to("cpu", torch.float32)[list(steps)]
         if not bool(torch.all(torch.isfinite(acp32) & (acp32 > 0))):
             raise ValueError("the base's alphas_cumprod is not finite and positive at every kept step (DDPM(Ns <= 20) is not respaced)")

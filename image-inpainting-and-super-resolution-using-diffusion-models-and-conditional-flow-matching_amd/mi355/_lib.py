@@ -113,6 +113,22 @@ class MultistepScheduleC(C.Structure):
     _fields_ = [("steps", C.POINTER(C.c_int32)), ("train_steps", C.c_int32), ("cx", _FP), ("c0", _FP), ("c1", _FP)]
 
 
+class X0ShapingC(C.Structure):
+    """mi355_x0_shaping (include/mi355_sampler.h): per-image dynamic thresholding and guidance rescale of the DDPM data prediction; 0 = off."""
+    _fields_ = [("quantile", C.c_float), ("max_threshold", C.c_float), ("rescale_phi", C.c_float)]
+
+
+def x0_shaping(shaping):
+    """None, an object with dynamic_threshold / max_threshold / guidance_rescale (DDPM.x0_shaping), or a (quantile, max_threshold, rescale_phi)
+    triple -> X0ShapingC or None.  None stands for "off" in each place."""
+    if shaping is None:
+        return None
+    if hasattr(shaping, "dynamic_threshold"):
+        shaping = (shaping.dynamic_threshold, shaping.max_threshold, shaping.guidance_rescale)
+    q, m, phi = shaping
+    return X0ShapingC(float(q or 0.0), float(m or 0.0), float(phi or 0.0))
+
+
 _VP, _I, _I64, _F, _U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
@@ -189,6 +205,11 @@ SIGNATURES = {
                                          _VP]),
     "mi355_ddpm_multistep_cfg_sample": (_I, [_VP, _VP, _I, _VP, _VP, _I, _F, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC),
                                              C.POINTER(MultistepScheduleC), _I, _VP, _I64, _VP]),
+    "mi355_ddpm_shaped_workspace_bytes": (_I64, [_VP, _I, _I, _I]),
+    "mi355_ddpm_shaped_sample": (_I, [_VP, _VP, _I, _VP, _VP, _I, _I, _F, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), C.POINTER(DDPMScheduleC),
+                                      C.POINTER(MultistepScheduleC), C.POINTER(X0ShapingC), _VP, _I64, _I, _VP, _I64, _VP]),
+    "mi355_x0_shape_stats": (_I, [_VP, _VP, _F, _VP, _I, _F, _F, C.POINTER(X0ShapingC), _VP, _VP, _I, _I64, _VP]),
+    "mi355_x0_shaped_step": (_I, [_I, _VP, _VP, _VP, _VP, _I, _F, _VP, _I64, _F, _F, _F, _F, _F, _F, _I, _U64, _U64, _VP, _I64, _VP]),
     "mi355_cfm_ab_workspace_bytes": (_I64, [_VP, _I, _I, _I, _I]),
     "mi355_cfm_ab_sample": (_I, [_VP, _VP, _I, _VP, _I, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_cfm_ab_cfg_sample": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _I, _F, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),

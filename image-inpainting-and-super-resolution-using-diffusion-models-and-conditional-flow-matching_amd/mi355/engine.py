@@ -718,6 +718,69 @@ class UNetEngine:
         del keep, steps_arr
         return x
 
+    def ddpm_shaped(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], shaping, *, mode: int, cond: Optional[torch.Tensor] = None,
+                    noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0, noise_condition=True,
+                    pad_value=-2.0, none_value=-2.0, seed=0, guidance_scale=None, y: Optional[torch.Tensor] = None, null_label: Optional[int] = None,
+                    timesteps=None, train_steps=None, ddim_sigma=None, walk=None, coefs=None):
+        """In-place DDPM sampling with per-image shaping of every predictor step's data prediction (mi355_ddpm_shaped_sample): dynamic
+        thresholding and guidance rescale.  shaping: DDPM.x0_shaping, a (quantile, max_threshold, rescale_phi) triple, or None (the unshaped
+        loop, bit for bit).  coefs None: the arguments and the loops of ddpm_sample; coefs = (cx, c0, c1): those of ddpm_multistep (mode must
+        be DDIM; no noise).  guidance_scale not None: the guided loops; a batch beyond cfg_batch() runs in slices (Philox: seed + slice)."""
+        B, Cx = x.shape[:2]
+        if cond is not None and cond.shape != x.shape:
+            raise ValueError("condition must have the shape of x")
+        if guidance_scale is None and y is not None:
+            raise NotImplementedError("ddpm_shaped takes class labels on the guided path only (guidance_scale=)")
+        sh = _lib.x0_shaping(shaping)
+        tb, keep = self._ddpm_tables(tables)
+        K = int(tb.Ns)
+        sched = ms = None
+        if coefs is not None:
+            if ddim_sigma is not None or walk is not None or noise is not None:
+                raise ValueError("the multistep solver (coefs=) is deterministic: it takes no ddim_sigma, walk or noise")
+            if (timesteps is None) != (train_steps is None):
+                raise ValueError("timesteps and train_steps go together")
+            steps = list(range(K)) if timesteps is None else [int(t) for t in timesteps]
+            cs = [torch.as_tensor(c, dtype=torch.float32).detach().to("cpu").contiguous() for c in coefs]
+            if len(steps) != K or len(cs) != 3 or any(c.numel() != K for c in cs):
+                raise ValueError("timesteps and coefs = (cx, c0, c1) must have one entry per row of the tables")
+            fp = C.POINTER(C.c_float)
+            ms = _lib.MultistepScheduleC()
+            steps_arr = (C.c_int32 * max(1, K))(*steps)
+            ms.steps, ms.train_steps = C.cast(steps_arr, C.POINTER(C.c_int32)), K if train_steps is None else int(train_steps)
+            ms.cx, ms.c0, ms.c1 = (C.cast(c.data_ptr(), fp) for c in cs)
+            keep += cs + [steps_arr]
+        else:
+            sched = self._ddpm_schedule(tables, timesteps, train_steps, ddim_sigma, walk)
+        if noise is not None and noise.shape[1:] != x.shape:
+            raise ValueError("injected noise must be [n_draws, B, C, H, W]")
+        guided = guidance_scale is not None
+        lab = wt = None
+        w, nl, mb = 0.0, 0, B
+        if guided:
+            lab, _ = self._labels(y, B)
+            w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
+            mb = self.cfg_batch()
+        self._fwd_state = None
+        for i, (lo, hi, whole) in enumerate(_slices(B, mb)):
+            xs = x if whole else x[lo:hi].contiguous()
+            cn = cond if whole or cond is None else cond[lo:hi].contiguous()
+            nz = noise if whole or noise is None else noise[:, lo:hi].contiguous()
+            ls, wl = _cut(lab, lo, hi), _cut(wt, lo, hi)
+            opt = _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value,
+                                    int(cond is None), (int(seed) + i) % 2 ** 64)
+            ws, wsb = self._workspace_sized("mi355_ddpm_shaped_workspace_bytes", hi - lo, int(guided), int(ms is not None))
+            check(self.L.mi355_ddpm_shaped_sample(self.handle, self._chk(xs, "x"), Cx, self._chk(cn, "condition") if cn is not None else None,
+                                                  C.c_void_p(ls.data_ptr()) if ls is not None else None, int(nl), int(guided), float(w),
+                                                  self._chk(wl, "guidance_scale") if wl is not None else None, C.byref(tb), C.byref(opt),
+                                                  C.byref(sched[0]) if sched is not None else None, C.byref(ms) if ms is not None else None,
+                                                  C.byref(sh) if sh is not None else None, self._chk(nz, "noise") if nz is not None else None,
+                                                  nz.shape[0] if nz is not None else 0, hi - lo, ws, wsb, self._stream()), "mi355_ddpm_shaped_sample")
+            if not whole:
+                x[lo:hi] = xs
+        del keep
+        return x
+
     @staticmethod
     def _ddpm_tables(tables):
         """name -> CPU fp32 tensor [Ns]  =>  (mi355_ddpm_tables, the tensors it points into)."""

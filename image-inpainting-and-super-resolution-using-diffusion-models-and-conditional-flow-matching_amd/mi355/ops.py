@@ -159,6 +159,50 @@ class Ops:
               "mi355_dpmpp_cfg_step")
         return x2
 
+    def x0_shape_stats(self, x, eps, c_recip, c_recipm1, shaping, w=None, detail=False):
+        """The per-image rows of a shaped predictor step (mi355_x0_shape_stats): shape [B, 2] = (f, s), f the guidance-rescale factor of eps and
+        s the dynamic threshold of x0 = c_recip x - c_recipm1 (f eps).  x [B, ...]; eps [B, ...], or with w (a float or a [B] tensor) [2B, ...] =
+        conditional | unconditional.  shaping: (quantile, max_threshold, rescale_phi), 0 or None = off, or DDPM.x0_shaping.
+        detail: also -> [B, 4] = (sigma_c, sigma_g, s_raw, 0).  -> shape, or (shape, detail)"""
+        B = x.shape[0]
+        guided = w is not None
+        if tuple(eps.shape) != ((2 * B if guided else B),) + tuple(x.shape[1:]):
+            raise ValueError(f"eps {tuple(eps.shape)} must be x's shape {tuple(x.shape)}" + (" with twice the leading size" if guided else ""))
+        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
+        sh = _lib.x0_shaping(shaping)
+        shape = torch.empty(B, 2, device=x.device, dtype=torch.float32)
+        det = torch.empty(B, 4, device=x.device, dtype=torch.float32) if detail else None
+        check(_lib.lib().mi355_x0_shape_stats(_req(x, "x"), _req(eps, "eps"), wf, wp, int(guided), float(c_recip), float(c_recipm1),
+                                              C.byref(sh) if sh is not None else None, _req(shape, "shape"), _req(det, "detail") if detail else None,
+                                              B, x.numel() // B if B else 1, _stream()), "mi355_x0_shape_stats")
+        return (shape, det) if detail else shape
+
+    _STEP_KINDS = {"ddpm": 0, "ddim": 1, "ddim_eta": 2, "dpmpp": 3}
+
+    def x0_shaped_step_(self, kind, x, eps, shape, c_recip, c_recipm1, a, b=0.0, c=0.0, sigma=0.0, z=None, philox=None, hist=None, w=None):
+        """One predictor step in place on the rows shape [B, 2] of x0_shape_stats (None: the unshaped step): kind "ddpm" (a, b = coef1, coef2;
+        sigma; z / philox as in ddpm_step_), "ddim" (a = acp_prev), "ddim_eta" (a = acp_prev; sigma; z / philox) or "dpmpp" (a, b, c = cx, c0, c1;
+        hist).  w (a float or a [B] tensor): the guided form, x and eps [2B, ...] as in ddpm_cfg_step_; z and hist stay [B, ...].  -> x"""
+        _same(x, eps, "x", "eps")
+        guided = w is not None
+        if guided and x.shape[0] % 2:
+            raise ValueError("x holds the state twice: an even leading size")
+        B = x.shape[0] // 2 if guided else x.shape[0]
+        n = x.numel() // 2 if guided else x.numel()
+        for t, name in ((z, "z"), (hist, "hist")):
+            if t is not None and t.numel() != n:
+                raise ValueError(f"{name} must have the B-image state's size")
+        if shape is not None and tuple(shape.shape) != (B, 2):
+            raise ValueError(f"shape must be [{B}, 2], got {tuple(shape.shape)}")
+        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_x0_shaped_step(self._STEP_KINDS[kind], _req(x, "x"), _req(eps, "eps"), _req(z, "z") if z is not None else None,
+                                              _req(hist, "hist") if hist is not None else None, int(guided), wf, wp, n // B if B else 1,
+                                              float(c_recip), float(c_recipm1), float(a), float(b), float(c), float(sigma),
+                                              int(philox is not None and z is None), seed, off, _req(shape, "shape") if shape is not None else None,
+                                              n, _stream()), "mi355_x0_shaped_step")
+        return x
+
     def renoise_(self, x, z, a, b, philox=None):
         """The forward move q(x_k | x_{k-1}) in place: x <- a x + b z (a = sqrt(alphas_k), b = sqrt(betas_k)); z / philox as in ddpm_step_."""
         zp = _req(z, "z") if z is not None else None

@@ -53,7 +53,8 @@ extern "C" {
  * mi355_ddpm_sample_sched, mi355_ddpm_cfg_sample_sched and the ops mi355_ddim_eta_step, mi355_ddim_eta_cfg_step, mi355_renoise_step (new symbols
  * and one new struct only); then the multistep samplers: mi355_dpmpp_step, mi355_dpmpp_cfg_step, mi355_ddpm_multistep_workspace_bytes,
  * mi355_ddpm_multistep_sample, mi355_ddpm_multistep_cfg_sample, mi355_cfm_ab_workspace_bytes, mi355_cfm_ab_sample, mi355_cfm_ab_cfg_sample (new
- * symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * symbols and one new struct only); then per-image shaping of the DDPM data prediction (dynamic thresholding, guidance rescale):
+ * mi355_ddpm_shaped_workspace_bytes, mi355_ddpm_shaped_sample, mi355_x0_shape_stats, mi355_x0_shaped_step (new symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -461,6 +462,54 @@ int mi355_ddpm_multistep_sample(mi355_unet* net, float* x, int channels, const f
 int mi355_ddpm_multistep_cfg_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w,
                                     const float* w_dev, const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt,
                                     const mi355_multistep_schedule* msched, int batch, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Per-image shaping of the data prediction of every DDPM predictor step: dynamic thresholding (Saharia et al. 2022, Imagen, section 2.3) and guidance
+ * rescale (Lin et al. 2023, section 3.4); no reference counterpart (the reference clips x0_hat to [-1, 1], sampling.py:13-15).  Per predictor step
+ * and per image b of per = C * H * W elements, with eps_g the plain eps or the guided eps_u + w (eps_c - eps_u):
+ *   rescale   : sigma_c, sigma_g = the population standard deviations of eps_c and eps_g over the image (their ratio is that of any other
+ *               normalisation; mean first, then the centred sum of squares, fp32, fixed order); f_b = rescale_phi * (sigma_c / sigma_g) +
+ *               (1 - rescale_phi), f_b = 1 when sigma_g == 0 or rescale_phi == 0; eps' = f_b * eps_g.  Guided calls only.
+ *   threshold : x0 = c_recip x - c_recipm1 eps' (product, product, difference, each rounded); pos = (double)quantile * (per - 1), k = floor(pos),
+ *               frac = (float)(pos - k); lo, hi = the k-th and min(k + 1, per - 1)-th smallest of |x0| over the image; s_raw = lo + frac * (hi - lo)
+ *               (the product and both sums rounded: torch.quantile's linear interpolation); s_b = min(max(s_raw, 1), max_threshold);
+ *               x0_hat = clamp(x0, -s_b, s_b) / s_b.  s_b = 1 is the static clip bit for bit.  An image that holds a NaN gets s_b = NaN and an
+ *               all-NaN x0_hat, as the eager expression gives.
+ * The order statistic is exact (a radix select over the bit patterns of |x0|; -0 counts as +0).  The corrector step and the loop's final clip keep
+ * the static clip.  Sample quality is untested (no trained checkpoint is at hand); the arithmetic is tested against an fp64 restatement. */
+typedef struct mi355_x0_shaping {
+  float quantile;       /* in [0, 1]; 0 = thresholding off */
+  float max_threshold;  /* 0 = no cap, else >= 1 */
+  float rescale_phi;    /* in [0, 1]; 0 = off */
+} mi355_x0_shaping;
+/* mi355_ddpm_shaped_sample: ONE entry point over the six DDPM loops, with the shaping above in every predictor step.  guided == 0: the loop of
+ * mi355_ddpm_sample (labels, null_label, w, w_dev are not read); guided != 0: that of mi355_ddpm_cfg_sample.  sched (or NULL): as in the _sched entry
+ * points; msched (or NULL): as in the multistep entry points (noise must then be NULL: the solver draws none); both NULL: the unscheduled loops.
+ * Every refusal of the loop so chosen applies unchanged, under this entry point's name.  Per predictor step one more launch (the statistics kernel,
+ * one workgroup per image) in front of the step launch, which reads the per-image rows; no copy.  The DPM-Solver++ history keeps the shaped D_i.
+ * With shaping NULL, or quantile == 0 and rescale_phi == 0, no statistics kernel runs and the result is bit-identical to the existing entry point's.
+ * workspace: mi355_ddpm_shaped_workspace_bytes(net, batch, guided, multistep) = the amount of the loop chosen (multistep != 0: with its history)
+ * rounded up to 256, then float[batch][2] rounded up to 256; needed whatever `shaping` is.  After the call mi355_unet_get_stats reports the
+ * launches of the last evaluation plus its step launch plus, with shaping on, the statistics launch.
+ * Errors beyond the loops' own, MI355_ERR_ARG before any launch, each naming its argument: both sched and msched given; quantile outside [0, 1] or
+ * not finite; max_threshold neither 0 nor >= 1; rescale_phi outside [0, 1]; rescale_phi > 0 with guided == 0.
+ *
+ * mi355_x0_shape_stats: the statistics kernel as an op.  x [B * per]; eps [B * per], or, guided != 0, [2 * B * per] = conditional | unconditional
+ * (w, w_dev as in mi355_ddim_cfg_step).  shape [B][2] = (f_b, s_b); detail (or NULL) [B][4] = (sigma_c, sigma_g, s_raw, 0), the two sigmas also with
+ * rescale_phi == 0 (an unguided call: both of eps), s_raw = 0 with quantile == 0.  shaping NULL: all off.  elems_per_image in [1, 2^30].
+ *
+ * mi355_x0_shaped_step: one predictor step on rows (f, s) (shape NULL: the unshaped step) - kind 0: mi355_ddpm_step (a, b = coef1, coef2; sigma, z,
+ * Philox), 1: mi355_ddim_step (a = acp_prev), 2: mi355_ddim_eta_step (a = acp_prev; sigma, z, Philox), 3: mi355_dpmpp_step (a, b, c = cx, c0, c1;
+ * hist); guided != 0: their _cfg_ forms (x, eps [2n]; w, w_dev).  Arguments a kind does not name are not read.  n must be whole images. */
+int64_t mi355_ddpm_shaped_workspace_bytes(const mi355_unet* net, int batch, int guided, int multistep);
+int mi355_ddpm_shaped_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, int guided, float w,
+                             const float* w_dev, const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                             const mi355_multistep_schedule* msched, const mi355_x0_shaping* shaping, const float* noise, int64_t n_noise_draws,
+                             int batch, void* workspace, int64_t workspace_bytes, void* stream);
+int mi355_x0_shape_stats(const float* x, const float* eps, float w, const float* w_dev, int guided, float c_recip, float c_recipm1,
+                         const mi355_x0_shaping* shaping, float* shape, float* detail, int batch, int64_t elems_per_image, void* stream);
+int mi355_x0_shaped_step(int kind, float* x, const float* eps, const float* z, float* hist, int guided, float w, const float* w_dev,
+                         int64_t elems_per_image, float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed,
+                         uint64_t offset, const float* shape, int64_t n, void* stream);
 
 /* Adams-Bashforth CFM samplers of order q = 2, 3, 4 (no reference counterpart): one evaluation per step from step q - 1 on,
  *   x_{k+1} = x_k + sum_{j<q} w_host[k * q + j] * v_{k-j},   v_k = model(t_k, x_k),
