@@ -28,26 +28,38 @@ __global__ void timestep_embedding_kernel(const float* t, int B, int dim, float 
 // out[b][j] = bias[j] + sum_k act(in[b][k]) * Wt[k][j].  One thread per (j, LR-row batch slab): the LR input rows
 // are staged in LDS (broadcast reads), Wt reads are coalesced across lanes, 4 independent loads in flight.
 constexpr int LB = 8;
+constexpr int LIN_KB = 32;   // terms per block of the blocked summation (a multiple of 4)
 template <int LR>
 __device__ __forceinline__ void linear_rows(const float* xin, const float* __restrict__ Wt, const float* __restrict__ bias,
                                             float* __restrict__ out, int b0, int B, int K, int J, int j, int out_act) {
+  // One fmaf chain over all of K rounds every step at the size of the running sum: at K = 2048 that is four to five times the error of the
+  // reference's blocked fp32 GEMM and misses the op test's budget (tests/test_embed_ref_cpu.py).  Blocks of LIN_KB terms are summed in a chain of their own
+  // and added to the total: K / LIN_KB + LIN_KB roundings at full size instead of K.
   float acc[LR];
 #pragma unroll
   for (int r = 0; r < LR; ++r) acc[r] = 0.f;
-  int k = 0;
-  for (; k + 4 <= K; k += 4) {
-    const float w0 = Wt[(size_t)k * J + j], w1 = Wt[(size_t)(k + 1) * J + j];
-    const float w2 = Wt[(size_t)(k + 2) * J + j], w3 = Wt[(size_t)(k + 3) * J + j];
+  for (int kb = 0; kb < K; kb += LIN_KB) {
+    const int ke = kb + LIN_KB < K ? kb + LIN_KB : K;
+    float part[LR];
 #pragma unroll
-    for (int r = 0; r < LR; ++r) {
-      const f32x4 x = *reinterpret_cast<const f32x4*>(xin + r * K + k);
-      acc[r] = fmaf(x[3], w3, fmaf(x[2], w2, fmaf(x[1], w1, fmaf(x[0], w0, acc[r]))));
+    for (int r = 0; r < LR; ++r) part[r] = 0.f;
+    int k = kb;
+    for (; k + 4 <= ke; k += 4) {
+      const float w0 = Wt[(size_t)k * J + j], w1 = Wt[(size_t)(k + 1) * J + j];
+      const float w2 = Wt[(size_t)(k + 2) * J + j], w3 = Wt[(size_t)(k + 3) * J + j];
+#pragma unroll
+      for (int r = 0; r < LR; ++r) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(xin + r * K + k);
+        part[r] = fmaf(x[3], w3, fmaf(x[2], w2, fmaf(x[1], w1, fmaf(x[0], w0, part[r]))));
+      }
     }
-  }
-  for (; k < K; ++k) {
-    const float w = Wt[(size_t)k * J + j];
+    for (; k < ke; ++k) {
+      const float w = Wt[(size_t)k * J + j];
 #pragma unroll
-    for (int r = 0; r < LR; ++r) acc[r] = fmaf(xin[r * K + k], w, acc[r]);
+      for (int r = 0; r < LR; ++r) part[r] = fmaf(xin[r * K + k], w, part[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < LR; ++r) acc[r] += part[r];
   }
   const float bj = bias ? bias[j] : 0.f;
 #pragma unroll
@@ -241,9 +253,13 @@ int timestep_embedding_launch(const float* t, int B, int dim, float max_period, 
   return 0;
 }
 
+int linear_form(int B, int K) { return B <= LB && K % 32 == 0 ? 1 : 0; }
+
+int label_emb_linear_form(int K) { return (size_t)16 * K * 4 <= 64 * 1024 ? 16 : LB; }
+
 int linear_launch(const float* in, const float* Wt, const float* bias, float* out, int B, int K, int J, int in_act, int out_act,
                   hipStream_t s) {
-  if (B <= LB && K % 32 == 0) {
+  if (linear_form(B, K) == 1) {
     hipLaunchKernelGGL(linear_small_kernel, dim3((J + 63) / 64), dim3(256), 0, s, in, Wt, bias, out, B, K, J, in_act, out_act);
     MI355_CHECK_HIP(hipGetLastError());
     return 0;
@@ -260,7 +276,7 @@ int label_emb_linear_launch(const float* h, int h_div, const float* lemb, const 
   MI355_REQUIRE(R > 0 && h_div > 0 && n_classes > 0, -1, "label_emb_linear: bad sizes");
   MI355_REQUIRE(K % 4 == 0 && (size_t)LB * K * 4 <= 64 * 1024, -4, "label_emb_linear: K must be a multiple of 4 and <= 2048");
   // 16-row slabs halve the weight re-reads of the per-step form (B rows) where they fit the LDS budget of linear_kernel
-  if ((size_t)16 * K * 4 <= 64 * 1024) {
+  if (label_emb_linear_form(K) == 16) {
     hipLaunchKernelGGL(label_emb_linear_kernel<16>, dim3((J + 127) / 128, (R + 15) / 16), dim3(128), (size_t)16 * K * 4, s, h, h_div, lemb,
                        labels, n_classes, Wt, bias, out, R, K, J, err);
   } else {

@@ -276,10 +276,12 @@ int timestep_embedding_launch(const float* t, int B, int dim, float max_period, 
 // out_act: 0 none, 1 silu(out)
 int linear_launch(const float* in, const float* Wt, const float* bias, float* out, int B, int K, int J, int in_act,
                   int out_act, hipStream_t s);
+int linear_form(int B, int K);   // the kernel linear_launch takes: 0 = linear_kernel (8-row slabs in LDS), 1 = linear_small_kernel (K split over four waves)
 // Class-conditional emb_layers (R rows): out[r][j] = bias[j] + sum_k silu(h[r / h_div][k] + lemb[lab(r)][k]) * Wt[k][j], lab(r) = labels ?
 // labels[r] : r % n_classes.  A label outside [0, n_classes) adds a zero row and stores 2 into the error word `err` (if not null).
 int label_emb_linear_launch(const float* h, int h_div, const float* lemb, const int32_t* labels, int n_classes, const float* Wt,
                             const float* bias, float* out, int R, int K, int J, uint32_t* err, hipStream_t s);
+int label_emb_linear_form(int K);   // rows per slab of the template form label_emb_linear_launch takes: 16 (K <= 1024) or 8
 // out[b] = table[labels[b]] (rows of J floats, J % 4 == 0); a label outside [0, n_classes) gives a zero row and stores 2 into `err`
 int emb_gather_launch(const float* table, const int32_t* labels, int n_classes, float* out, int B, int J, uint32_t* err, hipStream_t s);
 

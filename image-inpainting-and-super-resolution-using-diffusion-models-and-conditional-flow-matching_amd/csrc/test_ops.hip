@@ -751,4 +751,103 @@ int mi355_conv2d_fwd(const float* x, const float* x1, int cin1, const float* w_h
   return 0;
 }
 
+// ---- the embedding path and the layout kernels (later additions to ABI 108): csrc/embed.hip and unpack_channels of csrc/backward.hip, each through
+// its own *_launch function, nothing packed or unpacked in between; every op synchronises the stream ----
+namespace {
+// a pinned, mapped host word as a handle's error word is (unet_engine.hip): the kernels store into it over the bus
+struct ErrWord {
+  uint32_t* host = nullptr; uint32_t* dev = nullptr;
+  ~ErrWord() { if (host) (void)hipHostFree(host); }
+  int init() {
+    MI355_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&host), 64, hipHostMallocMapped));
+    *host = 0u;
+    MI355_CHECK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), host, 0));
+    return 0;
+  }
+};
+// the ABI's dtype code -> the internal element-type code (ops.h); MI355_BF16X2 stores bf16
+int layout_op_dtype(int dtype, const char* who, int* out) {
+  if (dtype != MI355_F32 && dtype != MI355_BF16 && dtype != MI355_BF16X2 && dtype != MI355_F16) { mi355_set_error(std::string(who) + ": bad dtype"); return -1; }
+  *out = dtype == MI355_F16 ? DT_F16 : (dtype == MI355_BF16X2 ? DT_BF16 : dtype);
+  return 0;
+}
+}  // namespace
+
+int mi355_linear(const float* in, const float* wt, const float* bias, float* out, int batch, int k, int j, int in_act, int out_act, int32_t* form,
+                 void* stream) {
+  if (form) *form = -1;
+  MI355_REQUIRE(in && wt && out && batch > 0 && k > 0 && j > 0, -1, "linear: bad argument");
+  hipStream_t s = S(stream);
+  if (int rc = linear_launch(in, wt, bias, out, batch, k, j, in_act, out_act, s)) return rc;
+  if (form) *form = linear_form(batch, k);
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mi355_label_emb_linear(const float* h, int h_div, const float* lemb, const int32_t* labels, int n_classes, const float* wt, const float* bias,
+                           float* out, int rows, int k, int j, int32_t* err_word, int32_t* form, void* stream) {
+  if (form) *form = -1;
+  if (err_word) *err_word = -1;
+  MI355_REQUIRE(h && lemb && wt && out && err_word && k > 0 && j > 0, -1, "label_emb_linear: bad argument");
+  hipStream_t s = S(stream);
+  ErrWord e;
+  if (int rc = e.init()) return rc;
+  if (int rc = label_emb_linear_launch(h, h_div, lemb, labels, n_classes, wt, bias, out, rows, k, j, e.dev, s)) return rc;
+  if (form) *form = label_emb_linear_form(k);
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  *err_word = (int32_t)*e.host;
+  return 0;
+}
+
+int mi355_emb_gather(const float* table, const int32_t* labels, int n_classes, float* out, int batch, int j, int32_t* err_word, void* stream) {
+  if (err_word) *err_word = -1;
+  MI355_REQUIRE(err_word && j > 0, -1, "emb_gather: bad argument");
+  hipStream_t s = S(stream);
+  ErrWord e;
+  if (int rc = e.init()) return rc;
+  if (int rc = emb_gather_launch(table, labels, n_classes, out, batch, j, e.dev, s)) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  *err_word = (int32_t)*e.host;
+  return 0;
+}
+
+int mi355_pack_nhwc(const float* x, int cx, const float* cond, int cc, int batch, int hw, int cpad, void* out, int dtype, void* stream) {
+  MI355_REQUIRE(x && out && batch > 0 && hw > 0 && cx > 0 && cc >= 0 && (cond != nullptr) == (cc > 0), -1, "pack_nhwc: bad argument");
+  MI355_REQUIRE(cpad >= cx + cc, -2, "pack_nhwc: cpad must hold cx + cc channels");
+  if (int rc = layout_op_dtype(dtype, "pack_nhwc", &dtype)) return rc;
+  hipStream_t s = S(stream);
+  if (int rc = pack_nhwc_launch(dtype, x, cx, cond, cc, batch, hw, cpad, out, s)) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mi355_unpack_nchw(const void* in, int batch, int hw, int channels, float* out, int dtype, void* stream) {
+  MI355_REQUIRE(in && out && batch > 0 && hw > 0 && channels > 0, -1, "unpack_nchw: bad argument");
+  if (int rc = layout_op_dtype(dtype, "unpack_nchw", &dtype)) return rc;
+  hipStream_t s = S(stream);
+  if (int rc = unpack_nchw_launch(dtype, in, batch, hw, channels, out, s)) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mi355_unpack_channels(const void* in, int batch, int hw, int stride, int c0, int count, float* out, int dtype, void* stream) {
+  MI355_REQUIRE(in && out && batch > 0 && hw > 0 && count > 0 && c0 >= 0, -1, "unpack_channels: bad argument");
+  MI355_REQUIRE(c0 + count <= stride, -2, "unpack_channels: channels c0 .. c0 + count must lie inside a row");
+  if (int rc = layout_op_dtype(dtype, "unpack_channels", &dtype)) return rc;
+  hipStream_t s = S(stream);
+  if (int rc = unpack_channels_launch(dtype, in, batch, hw, stride, c0, count, out, s)) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mi355_resample(const void* in, void* out, int batch, int h, int w, int channels, int mode, int dtype, void* stream) {
+  MI355_REQUIRE(in && out && batch > 0 && h > 0 && w > 0 && channels > 0, -1, "resample: bad argument");
+  MI355_REQUIRE(mode == CONV_UP2 || (mode == CONV_POOL2 && h >= 2 && w >= 2), -1, "resample: mode must be 2 (nearest x2) or 3 (2x2 average pool, h and w >= 2)");
+  if (int rc = layout_op_dtype(dtype, "resample", &dtype)) return rc;
+  hipStream_t s = S(stream);
+  if (int rc = resample_launch(dtype, in, out, batch, h, w, channels, mode, s)) return rc;
+  MI355_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 }  // extern "C"

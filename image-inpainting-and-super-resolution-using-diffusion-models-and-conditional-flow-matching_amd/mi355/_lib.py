@@ -237,6 +237,13 @@ SIGNATURES = {
                               _I64, _VP]),
     "mi355_conv2d_fwd": (_I, [_VP, _VP, _I, _FP, _FP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _F, _I,
                               C.POINTER(DebugConfigC), C.POINTER(C.c_int32), _VP, _I64, _VP]),
+    "mi355_linear": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _VP]),
+    "mi355_label_emb_linear": (_I, [_VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _VP]),
+    "mi355_emb_gather": (_I, [_VP, _VP, _I, _VP, _I, _I, C.POINTER(C.c_int32), _VP]),
+    "mi355_pack_nhwc": (_I, [_VP, _I, _VP, _I, _I, _I, _I, _VP, _I, _VP]),
+    "mi355_unpack_nchw": (_I, [_VP, _I, _I, _I, _VP, _I, _VP]),
+    "mi355_unpack_channels": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP]),
+    "mi355_resample": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
 }
 
 _lock = threading.Lock()

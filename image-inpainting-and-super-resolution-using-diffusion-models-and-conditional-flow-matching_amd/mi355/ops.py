@@ -857,5 +857,107 @@ class Ops:
                                           0.0, dtype, C.byref(debug) if debug is not None else None, route, None, 0, None), "mi355_conv2d_fwd")
         return dict(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3], reads_nchw=route[4], axpy=route[5], ksplit=route[6], n_mt=route[7])
 
+    # --- the embedding path and the layout kernels, one op each (see include/mi355_sampler.h); these ops synchronise the stream ---
+    ELEM = {_lib.MI355_F32: torch.float32, _lib.MI355_BF16: torch.bfloat16, _lib.MI355_BF16X2: torch.bfloat16, _lib.MI355_F16: torch.float16}
+
+    def linear(self, x, wt, bias=None, in_act=False, out_act=False, out=None):
+        """out[:B] = silu?(bias + silu?(x) @ wt) through linear_launch.  x [B, K], wt [K, J] (the transposed weight), bias [J] or None; out: a
+        tensor [>= B, J] to write into (rows beyond B are not touched), or None.  -> (out, form): form 1 = the K-split small kernel, 0 = the slab kernel."""
+        if x.dim() != 2 or wt.dim() != 2 or wt.shape[0] != x.shape[1]:
+            raise ValueError(f"x must be [B, K] and wt [K, J], got {tuple(x.shape)} and {tuple(wt.shape)}")
+        B, K = x.shape
+        J = wt.shape[1]
+        if bias is not None and tuple(bias.shape) != (J,):
+            raise ValueError(f"bias must be {(J,)}")
+        if out is None:
+            out = torch.full((B, J), float("nan"), device=x.device)
+        elif out.dim() != 2 or out.shape[0] < B or out.shape[1] != J:
+            raise ValueError(f"out must be [>= {B}, {J}]")
+        form = C.c_int32(-1)
+        check(_lib.lib().mi355_linear(_req(x, "x"), _req(wt, "wt"), _req(bias, "bias") if bias is not None else None, _req(out, "out"), B, K, J,
+                                      int(bool(in_act)), int(bool(out_act)), C.byref(form), _stream()), "mi355_linear")
+        return out, form.value
+
+    def label_emb_linear(self, h, lemb, wt, bias, rows, h_div, labels=None, out=None):
+        """out[r] = bias + silu(h[r // h_div] + lemb[lab(r)]) @ wt through label_emb_linear_launch, lab(r) = labels[r] or, labels None, r % n_classes.
+        h [>= (rows - 1) // h_div + 1, K], lemb [n_classes, K], wt [K, J], bias [J] or None, labels int32 [rows] or None.
+        -> (out [rows, J], error word, form): error word 2 = a label out of range (its row gets no label term); form = 16 or 8 rows per slab."""
+        if h.dim() != 2 or lemb.dim() != 2 or wt.dim() != 2 or lemb.shape[1] != h.shape[1] or wt.shape[0] != h.shape[1]:
+            raise ValueError("h must be [*, K], lemb [n_classes, K] and wt [K, J]")
+        K, J, n_classes = h.shape[1], wt.shape[1], lemb.shape[0]
+        if rows < 1 or h_div < 1 or h.shape[0] < (rows - 1) // h_div + 1:
+            raise ValueError(f"h has {h.shape[0]} rows, rows = {rows} with h_div = {h_div} need {(rows - 1) // max(h_div, 1) + 1}")
+        if labels is not None and tuple(labels.shape) != (rows,):
+            raise ValueError(f"labels must be {(rows,)}")
+        if bias is not None and tuple(bias.shape) != (J,):
+            raise ValueError(f"bias must be {(J,)}")
+        if out is None:
+            out = torch.full((rows, J), float("nan"), device=h.device)
+        elif out.dim() != 2 or out.shape[0] < rows or out.shape[1] != J:
+            raise ValueError(f"out must be [>= {rows}, {J}]")
+        err, form = C.c_int32(-1), C.c_int32(-1)
+        check(_lib.lib().mi355_label_emb_linear(_req(h, "h"), int(h_div), _req(lemb, "lemb"), _req(labels, "labels", torch.int32) if labels is not None else None,
+                                                n_classes, _req(wt, "wt"), _req(bias, "bias") if bias is not None else None, _req(out, "out"), int(rows), K, J,
+                                                C.byref(err), C.byref(form), _stream()), "mi355_label_emb_linear")
+        return out, err.value, form.value
+
+    def emb_gather(self, table, labels, out=None):
+        """out[b] = table[labels[b]] through emb_gather_launch; table [n_classes, J], labels int32 [B].  -> (out [B, J], error word)"""
+        if table.dim() != 2 or labels.dim() != 1:
+            raise ValueError("table must be [n_classes, J] and labels [B]")
+        B, J = labels.shape[0], table.shape[1]
+        if out is None:
+            out = torch.full((B, J), float("nan"), device=table.device)
+        elif out.dim() != 2 or out.shape[0] < B or out.shape[1] != J:
+            raise ValueError(f"out must be [>= {B}, {J}]")
+        err = C.c_int32(-1)
+        check(_lib.lib().mi355_emb_gather(_req(table, "table"), _req(labels, "labels", torch.int32), table.shape[0], _req(out, "out"), B, J, C.byref(err),
+                                          _stream()), "mi355_emb_gather")
+        return out, err.value
+
+    def pack_nhwc(self, x, cond=None, cpad=None, dtype=_lib.MI355_F32):
+        """NCHW fp32 x [B, Cx, *] | cond [B, Cc, *] -> NHWC [B, HW, cpad] in the element type of `dtype` (pack_nhwc_launch); cpad None: Cx + Cc rounded
+        up to a 16-byte fragment.  The result starts as NaN."""
+        B, Cx = x.shape[:2]
+        hw = x[0, 0].numel()
+        Cc = 0 if cond is None else cond.shape[1]
+        if cond is not None and (cond.shape[0] != B or cond[0, 0].numel() != hw):
+            raise ValueError("cond must match x in batch and spatial size")
+        V = 4 if dtype == _lib.MI355_F32 else 8
+        cpad = (Cx + Cc + V - 1) // V * V if cpad is None else int(cpad)
+        out = torch.full((B, hw, cpad), float("nan"), device=x.device, dtype=self.ELEM[dtype])
+        check(_lib.lib().mi355_pack_nhwc(_req(x, "x"), Cx, _req(cond, "cond") if cond is not None else None, Cc, B, hw, cpad,
+                                         _req(out, "out", self.ELEM[dtype]), dtype, _stream()), "mi355_pack_nhwc")
+        return out
+
+    def unpack_nchw(self, t, dtype=_lib.MI355_F32):
+        """NHWC t [B, HW, C] in the element type of `dtype` -> NCHW fp32 [B, C, HW] (unpack_nchw_launch)."""
+        B, hw, Cc = t.shape
+        out = torch.full((B, Cc, hw), float("nan"), device=t.device)
+        check(_lib.lib().mi355_unpack_nchw(_req(t, "t", self.ELEM[dtype]), B, hw, Cc, _req(out, "out"), dtype, _stream()), "mi355_unpack_nchw")
+        return out
+
+    def unpack_channels(self, t, c0, count, dtype=_lib.MI355_F32):
+        """Channels c0 .. c0 + count of NHWC t [B, HW, stride] -> NCHW fp32 [B, count, HW] (unpack_channels_launch: fp32 and bf16)."""
+        B, hw, stride = t.shape
+        if c0 < 0 or count < 1 or c0 + count > stride:
+            raise ValueError(f"channels {c0} .. {c0 + count} must lie inside a row of {stride}")
+        out = torch.full((B, count, hw), float("nan"), device=t.device)
+        check(_lib.lib().mi355_unpack_channels(_req(t, "t", self.ELEM[dtype]), B, hw, stride, int(c0), int(count), _req(out, "out"), dtype, _stream()),
+              "mi355_unpack_channels")
+        return out
+
+    def resample(self, t, mode, dtype=_lib.MI355_F32):
+        """NHWC t [B, H, W, C] in the element type of `dtype`: mode "up" nearest x2 -> [B, 2H, 2W, C]; "pool" AvgPool2d(2) -> [B, H // 2, W // 2, C]
+        (resample_launch).  The result starts as NaN."""
+        if mode not in ("up", "pool"):
+            raise ValueError("mode must be 'up' or 'pool'")
+        B, H, W, Cc = t.shape
+        Ho, Wo = (2 * H, 2 * W) if mode == "up" else (H // 2, W // 2)
+        out = torch.full((B, Ho, Wo, Cc), float("nan"), device=t.device, dtype=self.ELEM[dtype])
+        check(_lib.lib().mi355_resample(_req(t, "t", self.ELEM[dtype]), _req(out, "out", self.ELEM[dtype]), B, H, W, Cc, 2 if mode == "up" else 3, dtype,
+                                        _stream()), "mi355_resample")
+        return out
+
 
 default_ops = Ops()

@@ -54,7 +54,9 @@ extern "C" {
  * and one new struct only); then the multistep samplers: mi355_dpmpp_step, mi355_dpmpp_cfg_step, mi355_ddpm_multistep_workspace_bytes,
  * mi355_ddpm_multistep_sample, mi355_ddpm_multistep_cfg_sample, mi355_cfm_ab_workspace_bytes, mi355_cfm_ab_sample, mi355_cfm_ab_cfg_sample (new
  * symbols and one new struct only); then per-image shaping of the DDPM data prediction (dynamic thresholding, guidance rescale):
- * mi355_ddpm_shaped_workspace_bytes, mi355_ddpm_shaped_sample, mi355_x0_shape_stats, mi355_x0_shaped_step (new symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * mi355_ddpm_shaped_workspace_bytes, mi355_ddpm_shaped_sample, mi355_x0_shape_stats, mi355_x0_shaped_step (new symbols and one new struct only); then the embedding path and the layout
+ * kernels as test ops: mi355_linear, mi355_label_emb_linear, mi355_emb_gather, mi355_pack_nhwc, mi355_unpack_nchw, mi355_unpack_channels,
+ * mi355_resample (new symbols only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -893,6 +895,41 @@ int mi355_conv2d_fwd(const float* x, const float* x1, int cin1, const float* w_h
                      int w, int cout, int ksize, int stride, int resample, const float* pro_a, const float* pro_b, int pro_silu, const float* emb,
                      const float* res, int res_mode, int flags, float* axpy_x, float axpy_scale, int dtype, const mi355_debug_config* debug,
                      int32_t route[8], void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- the embedding path and the layout kernels, one op each (later additions to ABI 108; csrc/embed.hip, csrc/backward.hip) -----------------
+ * Each op calls the launch function the engine calls, on the caller's DEVICE buffers as they are (nothing is packed, copied or initialised in
+ * between), and synchronises `stream`.  Nothing is launched when an op returns an error.
+ *
+ * mi355_linear: out [B][J] = out_act?silu( bias [J] + sum_k in_act?silu(in [B][K]) wt [K][J] ), all fp32, wt the TRANSPOSED weight, bias may be
+ * NULL (unet.py:564-569 time_embed = Linear, SiLU, Linear; unet.py:297-305 emb_layers = SiLU, Linear).  *form (host, may be NULL) = the kernel the
+ * launcher chose: 1 = linear_small_kernel (B <= 8 and K % 32 == 0: K split over four waves, any K), 0 = linear_kernel (8-row slabs staged in
+ * LDS: K % 4 == 0 and K <= 2048, otherwise MI355_ERR_UNSUPPORTED); -1 if nothing was launched. */
+int mi355_linear(const float* in, const float* wt, const float* bias, float* out, int batch, int k, int j, int in_act, int out_act, int32_t* form,
+                 void* stream);
+/* Class-conditional emb_layers: out [R][J] = bias [J] + sum_k silu(h [r / h_div][k] + lemb [lab(r)][k]) wt [k][J], lab(r) = labels ? labels [r] :
+ * r % n_classes (labels: DEVICE int32 [R] or NULL); h has (R - 1) / h_div + 1 rows of K, lemb n_classes rows of K.  h_div = 1: a time per row;
+ * h_div = R: one time; labels NULL with h_div = n_classes: the samplers' (step, class) table.  A label outside [0, n_classes) adds a zero row and
+ * stores 2 into the error word: the op allocates a pinned host word as a handle's is, zeroes it, passes it and returns its value after the
+ * synchronise in *err_word (host).  *form (host, may be NULL) = rows per slab of the template form: 16 (K <= 1024) or 8; -1 if nothing was
+ * launched.  K % 4 != 0 or K > 2048: MI355_ERR_UNSUPPORTED. */
+int mi355_label_emb_linear(const float* h, int h_div, const float* lemb, const int32_t* labels, int n_classes, const float* wt, const float* bias,
+                           float* out, int rows, int k, int j, int32_t* err_word, int32_t* form, void* stream);
+/* out [B][J] = table [labels [b]][J] (label_emb(y), unet.py:572); a label outside [0, n_classes) gives a zero row and error word 2, returned as by
+ * mi355_label_emb_linear.  J % 4 != 0 or a buffer that is not 16-byte aligned: MI355_ERR_SHAPE. */
+int mi355_emb_gather(const float* table, const int32_t* labels, int n_classes, float* out, int batch, int j, int32_t* err_word, void* stream);
+/* NCHW fp32 x [B][cx][hw] | cond [B][cc][hw] (NULL with cc = 0) -> NHWC out [B][hw][cpad] in the element type of `dtype` (MI355_F32 fp32, MI355_BF16
+ * and MI355_BF16X2 bf16, MI355_F16 fp16), round to nearest even, channels cx + cc .. cpad zero.  cpad: a multiple of the 16-byte fragment (4 fp32 / 8
+ * two-byte channels), else MI355_ERR_SHAPE. */
+int mi355_pack_nhwc(const float* x, int cx, const float* cond, int cc, int batch, int hw, int cpad, void* out, int dtype, void* stream);
+/* NHWC in [B][hw][channels] in the element type of `dtype` -> NCHW fp32 out [B][channels][hw] (exact). */
+int mi355_unpack_nchw(const void* in, int batch, int hw, int channels, float* out, int dtype, void* stream);
+/* NHWC in [B][hw][stride] -> NCHW fp32 out [B][count][hw] = channels c0 .. c0 + count of every row (csrc/backward.hip unpack_channels_kernel; exact).
+ * fp32 and bf16 only: MI355_F16 is the launcher's MI355_ERR_UNSUPPORTED.  c0 + count > stride: MI355_ERR_SHAPE. */
+int mi355_unpack_channels(const void* in, int batch, int hw, int stride, int c0, int count, float* out, int dtype, void* stream);
+/* Plain resampling of an NHWC tensor in [B][h][w][channels] of the element type of `dtype` (conv_resample = False, unet.py:209, 236): mode 2 nearest x2
+ * -> out [B][2h][2w][channels]; mode 3 AvgPool2d(2) -> out [B][h / 2][w / 2][channels] (an odd last row / column is dropped), pooled in fp32 and
+ * rounded once. */
+int mi355_resample(const void* in, void* out, int batch, int h, int w, int channels, int mode, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
