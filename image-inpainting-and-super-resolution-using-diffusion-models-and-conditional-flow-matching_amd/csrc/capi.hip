@@ -195,16 +195,31 @@ int mi355_sde_euler_step(float* x, const float* a, const float* b, float ca, flo
   MI355_REQUIRE((ca == 1.f || ca == -1.f) && (cb == 1.f || cb == -1.f), -1, "sde_euler_step: ca and cb must be +1 or -1");
   return sde_euler_step_launch(x, a, b, ca, cb, dt, g, g_scalar, dW, use_philox, seed, offset, out, w, n, S(stream));
 }
+// The predictor-step exports: each fills a PredictorStep for the one launcher (ops.h).
+static PredictorStep predictor(int kind, float* x, const float* eps, float c_recip, float c_recipm1, int64_t n) {
+  PredictorStep p;
+  p.kind = kind; p.x = x; p.eps = eps; p.c_recip = c_recip; p.c_recipm1 = c_recipm1; p.n = n;
+  return p;
+}
+static void with_noise(PredictorStep& p, const float* z, int use_philox, uint64_t seed, uint64_t offset) {
+  p.z = z; p.use_philox = use_philox; p.seed = seed; p.offset = offset;
+}
+static void with_guide(PredictorStep& p, float w, const float* w_dev, int64_t per) { p.guide = {true, w, w_dev}; p.per = per; }
 int mi355_ddpm_step(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
                     float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
-  return ddpm_step_launch(x, eps, z, c_recip, c_recipm1, coef1, coef2, sigma, use_philox, seed, offset, n, S(stream));
+  PredictorStep p = predictor(STEP_ANCESTRAL, x, eps, c_recip, c_recipm1, n);
+  p.a = coef1; p.b = coef2; p.sigma = sigma;
+  with_noise(p, z, use_philox, seed, offset);
+  return predictor_step_launch(p, S(stream));
 }
 int mi355_corrector_step(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float recip_sqrt_m1, float dt,
                          float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
   return corrector_step_launch(x, eps, z, c_recip, c_recipm1, recip_sqrt_m1, dt, delta, use_philox, seed, offset, n, S(stream));
 }
 int mi355_ddim_step(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, void* stream) {
-  return ddim_step_launch(x, eps, c_recip, c_recipm1, acp_prev, n, S(stream));
+  PredictorStep p = predictor(STEP_DDIM, x, eps, c_recip, c_recipm1, n);
+  p.a = acp_prev;
+  return predictor_step_launch(p, S(stream));
 }
 int mi355_replace_mask(float* x, const float* cond, const float* z, float pad_value, int noisy, float sa, float sb, int use_philox,
                        uint64_t seed, uint64_t offset, int64_t n, void* stream) {
@@ -268,39 +283,66 @@ int mi355_cfg_stage(float* out, const float* y0, const float* const k[4], const 
 }
 int mi355_ddpm_cfg_step(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1,
                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
-  return ddpm_cfg_step_launch(x, eps, z, w, w_dev, elems_per_image, c_recip, c_recipm1, coef1, coef2, sigma, use_philox, seed, offset, n, S(stream));
+  PredictorStep p = predictor(STEP_ANCESTRAL, x, eps, c_recip, c_recipm1, n);
+  p.a = coef1; p.b = coef2; p.sigma = sigma;
+  with_noise(p, z, use_philox, seed, offset);
+  with_guide(p, w, w_dev, elems_per_image);
+  return predictor_step_launch(p, S(stream));
 }
 int mi355_ddim_cfg_step(float* x, const float* eps, float w, const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1, float acp_prev,
                         int64_t n, void* stream) {
-  return ddim_cfg_step_launch(x, eps, w, w_dev, elems_per_image, c_recip, c_recipm1, acp_prev, n, S(stream));
+  PredictorStep p = predictor(STEP_DDIM, x, eps, c_recip, c_recipm1, n);
+  p.a = acp_prev;
+  with_guide(p, w, w_dev, elems_per_image);
+  return predictor_step_launch(p, S(stream));
 }
 int mi355_ddim_eta_step(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int use_philox,
                         uint64_t seed, uint64_t offset, int64_t n, void* stream) {
-  return ddim_eta_step_launch(x, eps, z, c_recip, c_recipm1, acp_prev, sigma, use_philox, seed, offset, n, S(stream));
+  PredictorStep p = predictor(STEP_DDIM_ETA, x, eps, c_recip, c_recipm1, n);
+  p.a = acp_prev; p.sigma = sigma;
+  with_noise(p, z, use_philox, seed, offset);
+  return predictor_step_launch(p, S(stream));
 }
 int mi355_ddim_eta_cfg_step(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t elems_per_image, float c_recip,
                             float c_recipm1, float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
-  return ddim_eta_cfg_step_launch(x, eps, z, w, w_dev, elems_per_image, c_recip, c_recipm1, acp_prev, sigma, use_philox, seed, offset, n, S(stream));
+  PredictorStep p = predictor(STEP_DDIM_ETA, x, eps, c_recip, c_recipm1, n);
+  p.a = acp_prev; p.sigma = sigma;
+  with_noise(p, z, use_philox, seed, offset);
+  with_guide(p, w, w_dev, elems_per_image);
+  return predictor_step_launch(p, S(stream));
 }
 int mi355_renoise_step(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
   return renoise_step_launch(x, z, a, b, use_philox, seed, offset, n, S(stream));
 }
 int mi355_dpmpp_step(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, void* stream) {
-  return dpmpp_step_launch(x, eps, hist, c_recip, c_recipm1, cx, c0, c1, n, S(stream));
+  PredictorStep p = predictor(STEP_DPMPP, x, eps, c_recip, c_recipm1, n);
+  p.hist = hist; p.a = cx; p.b = c0; p.c = c1;
+  return predictor_step_launch(p, S(stream));
 }
 int mi355_dpmpp_cfg_step(float* x, const float* eps, float* hist, float w, const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1,
                          float cx, float c0, float c1, int64_t n, void* stream) {
-  return dpmpp_cfg_step_launch(x, eps, hist, w, w_dev, elems_per_image, c_recip, c_recipm1, cx, c0, c1, n, S(stream));
+  PredictorStep p = predictor(STEP_DPMPP, x, eps, c_recip, c_recipm1, n);
+  p.hist = hist; p.a = cx; p.b = c0; p.c = c1;
+  with_guide(p, w, w_dev, elems_per_image);
+  return predictor_step_launch(p, S(stream));
 }
 int mi355_x0_shape_stats(const float* x, const float* eps, float w, const float* w_dev, int guided, float c_recip, float c_recipm1,
                          const mi355_x0_shaping* shaping, float* shape, float* detail, int batch, int64_t elems_per_image, void* stream) {
-  return x0_shape_stats_launch(x, eps, guided, w, w_dev, c_recip, c_recipm1, shaping, shape, detail, batch, elems_per_image, S(stream));
+  return x0_shape_stats_launch(x, eps, StepGuide{guided != 0, w, w_dev}, c_recip, c_recipm1, shaping, shape, detail, batch, elems_per_image, S(stream));
 }
+// One shaped (or, shape == null, unshaped) predictor step chosen by number: 0 ancestral (a, b = coef1, coef2), 1 DDIM (a = acp_prev), 2 DDIM(eta)
+// (a = acp_prev), 3 DPM-Solver++ (a, b, c = cx, c0, c1); the numbers are the STEP_* kinds.
 int mi355_x0_shaped_step(int kind, float* x, const float* eps, const float* z, float* hist, int guided, float w, const float* w_dev,
                          int64_t elems_per_image, float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed,
                          uint64_t offset, const float* shape, int64_t n, void* stream) {
-  return x0_shaped_step_launch(kind, x, eps, z, hist, guided, w, w_dev, elems_per_image, c_recip, c_recipm1, a, b, c, sigma, use_philox, seed, offset,
-                               shape, n, S(stream));
+  const int64_t per = elems_per_image;
+  MI355_REQUIRE(kind >= 0 && kind <= 3, -1, "x0_shaped_step: kind must be 0 (ancestral), 1 (DDIM), 2 (DDIM(eta)) or 3 (DPM-Solver++)");
+  MI355_REQUIRE(per > 0 && n % per == 0, -1, "x0_shaped_step: n must be whole images of elems_per_image elements");
+  PredictorStep p = predictor(kind, x, eps, c_recip, c_recipm1, n);
+  p.hist = hist; p.a = a; p.b = b; p.c = c; p.sigma = sigma; p.shape = shape; p.per = per;
+  with_noise(p, z, use_philox, seed, offset);
+  if (guided) with_guide(p, w, w_dev, per);
+  return predictor_step_launch(p, S(stream));
 }
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream) {

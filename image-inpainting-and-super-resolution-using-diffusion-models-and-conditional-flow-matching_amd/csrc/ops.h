@@ -297,42 +297,37 @@ int resample_launch(int dtype, const void* in, void* out, int N, int Hs, int Ws,
 int euler_step_launch(float* x, const float* v, float dt, int64_t n, hipStream_t s);
 int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, float cb, float dt, const float* g, float g_s, const float* dW,
                           int use_philox, uint64_t seed, uint64_t offset, float* out, float w, int64_t n, hipStream_t s);
-int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
-                     float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape = nullptr, int64_t per = 0);
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,
                           float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
-int ddim_step_launch(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s, const float* shape = nullptr,
-                     int64_t per = 0);
-// classifier-free-guided ddpm / ddim steps: eps [2n] = conditional | unconditional evaluation, x [2n] the duplicated state (both halves written)
-int ddpm_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
-                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s,
-                         const float* shape = nullptr);
-int ddim_cfg_step_launch(float* x, const float* eps, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float acp_prev, int64_t n,
-                         hipStream_t s, const float* shape = nullptr);
-// DDIM(eta) step, its guided form (operands as ddim_cfg_step_launch) and the forward re-noising move x <- a x + b z of a RePaint walk
-int ddim_eta_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int use_philox,
-                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape = nullptr, int64_t per = 0);
-int ddim_eta_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
-                             float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s,
-                             const float* shape = nullptr);
 int renoise_step_launch(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
-// DPM-Solver++ multistep step on the clipped x0_hat: D = clip(c_recip x - c_recipm1 eps); x <- cx x + c0 D + c1 hist; hist <- D (hist: not read when
-// c1 == 0, not written when null), and its guided form (operands as ddim_cfg_step_launch, hist [n])
-int dpmpp_step_launch(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s,
-                      const float* shape = nullptr, int64_t per = 0);
-int dpmpp_cfg_step_launch(float* x, const float* eps, float* hist, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float cx,
-                          float c0, float c1, int64_t n, hipStream_t s, const float* shape = nullptr);
-// Per-image shaping of a predictor step's data prediction (mi355_x0_shaping).  The eight step launchers above take `shape`: null = the static clip
-// (the unshaped kernels), else rows (f, s) per image of `per` elements: eps is scaled by f, x0_hat = clip(x0, -s, s) / s.  x0_shape_stats_launch
-// fills the rows, one workgroup per image (and detail [B, 4] = sigma_c, sigma_g, s_raw, 0 when not null); check_x0_shaping holds the refusals of a
-// mi355_x0_shaping (null: none), each prefixed by `who`; x0_shaped_step_launch picks a step by number (0 ancestral: a, b = coef1, coef2; 1 DDIM:
-// a = acp_prev; 2 DDIM(eta): a = acp_prev; 3 DPM-Solver++: a, b, c = cx, c0, c1).
+// The predictor steps of the DDPM loops: ONE descriptor, ONE launcher.  Every kind forms the data prediction x0_hat = clip(c_recip x - c_recipm1 eps)
+// and moves x from it:
+//   STEP_ANCESTRAL  a, b = posterior_mean_coef1, coef2: x <- a x0_hat + b x + sigma z
+//   STEP_DDIM       a = acp_prev:                       x <- sqrt(a) x0_hat + sqrt(1 - a) e2, e2 the eps that x0_hat stands for
+//   STEP_DDIM_ETA   a = acp_prev, sigma finite >= 0:    the same with sqrt(max(1 - a - sigma^2, 0)) and + sigma z (no noise given: no noise term)
+//   STEP_DPMPP      a, b, c = cx, c0, c1:               x <- a x + b x0_hat + c hist; hist <- x0_hat (hist: not read when c == 0, not written when null)
+// Noise (the two kinds with a z term): z injected, or Philox at (seed, offset), offset a multiple of 4, indexed by the element of the n-element state.
+// guide.on: eps [2n] = conditional | unconditional evaluation, combined as eps_u + w (eps_c - eps_u) with w, or w_dev[image] over images of `per`
+// elements; x [2n] is the duplicated state (first half read, both halves written).  shape (null: the static clip to [-1, 1]): rows (f, s) per image of
+// `per` elements, filled by x0_shape_stats_launch: eps is scaled by f, x0_hat = clip(x0, -s, s) / s.  Refusals are prefixed ddpm_step, ddpm_cfg_step,
+// ddim_step, ... dpmpp_cfg_step after the kind and guide.on.
+enum { STEP_ANCESTRAL = 0, STEP_DDIM = 1, STEP_DDIM_ETA = 2, STEP_DPMPP = 3 };
+struct StepGuide { bool on = false; float w = 0.f; const float* w_dev = nullptr; };
+struct PredictorStep {
+  int kind = STEP_ANCESTRAL;   // a STEP_* value (mi355_x0_shaped_step, which takes it from its caller, checks the range)
+  float* x = nullptr; const float* eps = nullptr; const float* z = nullptr; float* hist = nullptr;
+  float c_recip = 0.f, c_recipm1 = 0.f;
+  float a = 0.f, b = 0.f, c = 0.f, sigma = 0.f;
+  int use_philox = 0; uint64_t seed = 0, offset = 0;
+  StepGuide guide;
+  int64_t per = 0; const float* shape = nullptr; int64_t n = 0;
+};
+int predictor_step_launch(const PredictorStep& p, hipStream_t s);
+// The statistics behind `shape`, one workgroup per image (and detail [B, 4] = sigma_c, sigma_g, s_raw, 0 when not null); check_x0_shaping holds the
+// refusals of a mi355_x0_shaping (null: none), each prefixed by `who`.
 int check_x0_shaping(const char* who, const mi355_x0_shaping* sh, int guided);
-int x0_shape_stats_launch(const float* x, const float* eps, int guided, float w, const float* w_dev, float c_recip, float c_recipm1,
-                          const mi355_x0_shaping* sh, float* shape, float* detail, int batch, int64_t per, hipStream_t s);
-int x0_shaped_step_launch(int kind, float* x, const float* eps, const float* z, float* hist, int guided, float w, const float* w_dev, int64_t per,
-                          float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed, uint64_t offset,
-                          const float* shape, int64_t n, hipStream_t s);
+int x0_shape_stats_launch(const float* x, const float* eps, const StepGuide& g, float c_recip, float c_recipm1, const mi355_x0_shaping* sh, float* shape,
+                          float* detail, int batch, int64_t per, hipStream_t s);
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb,
                         int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int clip_launch(float* x, float lo, float hi, int64_t n, hipStream_t s);

@@ -32,14 +32,19 @@ struct RkBufs { float* k[7]; float* ystage; };
 // "coupled" replacement pastes along), the seed's two outputs and the U-Net VJP, each a state; the low-res residual [B, C, h_low, w_low]
 struct ReconDims { int h_low, w_low; };
 struct ReconTail { float* x_init; float* g_eps; float* g_x; float* vjp; float* resid; };
-struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; ReconTail rec; uintptr_t end; };
+// the DDPM multistep history (the previous step's data prediction: one state at `batch`, also under guidance) and the shaping rows [batch][2]
+struct DdpmTail { float* hist; float* rows; };
+struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; ReconTail rec; DdpmTail ddpm; uintptr_t end; };
+// What a sampler call keeps in its workspace.  guided: the network runs at 2 * batch and the guidance tail follows its workspace; stages > 0: the
+// Runge-Kutta buffers follow; recon: the reconstruction tail; hist, rows: the DDPM tail closes the layout.
+struct LayoutSpec { int batch = 0; bool guided = false; int stages = 0; const ReconDims* recon = nullptr; bool hist = false; bool rows = false; };
 inline size_t cfg_cond_channels(const mi355_unet* net) { return (size_t)(net->cfg.in_channels > net->cfg.out_channels ? net->cfg.in_channels - net->cfg.out_channels : 0); }
 
-// guided: the network runs at 2 * batch and the guidance tail follows its workspace; stages > 0: the Runge-Kutta buffers follow; recon: the
-// reconstruction tail closes the layout
-Layout layout(const mi355_unet* net, int batch, bool guided, int stages, uintptr_t base, const ReconDims* recon = nullptr) {
+Layout layout(const mi355_unet* net, const LayoutSpec& sp, uintptr_t base) {
   const size_t hw = (size_t)net->cfg.image_size * net->cfg.image_size;
-  const int B = guided ? 2 * batch : batch;
+  const bool guided = sp.guided;
+  const int stages = sp.stages, B = guided ? 2 * sp.batch : sp.batch;
+  const ReconDims* const recon = sp.recon;
   const size_t state = (size_t)B * net->cfg.out_channels * hw * 4;
   Layout l = {};
   Walk w{base};
@@ -52,7 +57,7 @@ Layout layout(const mi355_unet* net, int batch, bool guided, int stages, uintptr
   l.sc.unet_bytes = unet_workspace_bytes(net, B);
   l.sc.unet_ws = reinterpret_cast<char*>(w.p);
   w.p += (size_t)l.sc.unet_bytes;   // not rounded up: mi355_unet_workspace_bytes ends here
-  if (guided || stages || recon) w.p = al256(w.p);
+  if (guided || stages || recon || sp.hist || sp.rows) w.p = al256(w.p);
   if (guided) {
     l.cfg.x2 = w.take(state);
     l.cfg.cond2 = w.take((size_t)B * cfg_cond_channels(net) * hw * 4);
@@ -67,17 +72,21 @@ Layout layout(const mi355_unet* net, int batch, bool guided, int stages, uintptr
     l.rec.vjp = w.take(state);
     l.rec.resid = w.take((size_t)B * net->cfg.out_channels * recon->h_low * recon->w_low * 4);
   }
+  if (sp.hist) l.ddpm.hist = w.take((size_t)sp.batch * net->cfg.out_channels * hw * 4);
+  if (sp.rows) l.ddpm.rows = w.take((size_t)sp.batch * 2 * 4);
   l.end = w.p;
   return l;
 }
-inline int64_t layout_bytes(const mi355_unet* net, int batch, bool guided, int stages) { return (int64_t)layout(net, batch, guided, stages, 0).end; }
+inline int64_t layout_bytes(const mi355_unet* net, const LayoutSpec& sp) { return (int64_t)layout(net, sp, 0).end; }
+inline LayoutSpec plain_spec(int batch, bool guided = false, int stages = 0) { LayoutSpec sp; sp.batch = batch; sp.guided = guided; sp.stages = stages; return sp; }
 
-// The layout of a sampler call in the caller's workspace.
-int carve(const mi355_unet* net, int batch, bool guided, int stages, void* workspace, int64_t workspace_bytes, Layout& l, const ReconDims* recon = nullptr) {
+// The layout of a sampler call in the caller's workspace.  who (optional): the entry point's name in front of the short-workspace refusal.
+int carve(const mi355_unet* net, const LayoutSpec& sp, void* workspace, int64_t workspace_bytes, Layout& l, const char* who = nullptr) {
   MI355_REQUIRE(net && workspace, -1, "null argument");
   MI355_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, -1, "workspace must be 256-byte aligned");
-  l = layout(net, batch, guided, stages, reinterpret_cast<uintptr_t>(workspace), recon);
-  MI355_REQUIRE(workspace_bytes >= (int64_t)(l.end - reinterpret_cast<uintptr_t>(workspace)), -2, "workspace too small");
+  l = layout(net, sp, reinterpret_cast<uintptr_t>(workspace));
+  MI355_REQUIRE(workspace_bytes >= (int64_t)(l.end - reinterpret_cast<uintptr_t>(workspace)), -2,
+                (who ? std::string(who) + ": " : std::string()) + "workspace too small");
   return 0;
 }
 
@@ -124,30 +133,10 @@ class EvalEmb {
 // ---- classifier-free guidance: every evaluation is ONE forward at batch 2B (images 0..B-1 conditional, B..2B-1 unconditional) -------------------
 // The one point where a guided loop differs from its plain form: the launch that consumes the network output.  off: the plain kernel; on: its
 // guided form, which combines the two halves with w (or the per-image w_dev) over `per` elements per image.
-struct Guide {
-  bool on = false; float w = 0.f; const float* w_dev = nullptr; int64_t per = 0;
+struct Guide : StepGuide {
+  int64_t per = 0;
   int stage(float* out, const float* y0, const float* const* kp, const float* cf, int nk, int64_t n, float* copy_out, uint8_t* u8_out, hipStream_t s) const {
     return on ? cfg_stage_launch(out, y0, kp, cf, nk, n, w, w_dev, per, 1, copy_out, u8_out, s) : rk_stage_launch(out, y0, kp, cf, nk, n, copy_out, u8_out, s);
-  }
-  // the DDPM predictor steps; shape (null: the static clip): the per-image rows of x0_shape_stats_launch, images of sper elements
-  int dpmpp(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s,
-            const float* shape, int64_t sper) const {
-    return on ? dpmpp_cfg_step_launch(x, eps, hist, w, w_dev, per, c_recip, c_recipm1, cx, c0, c1, n, s, shape)
-              : dpmpp_step_launch(x, eps, hist, c_recip, c_recipm1, cx, c0, c1, n, s, shape, sper);
-  }
-  int ddim(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s, const float* shape, int64_t sper) const {
-    return on ? ddim_cfg_step_launch(x, eps, w, w_dev, per, c_recip, c_recipm1, acp_prev, n, s, shape)
-              : ddim_step_launch(x, eps, c_recip, c_recipm1, acp_prev, n, s, shape, sper);
-  }
-  int ddim_eta(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int philox, uint64_t seed,
-               uint64_t off, int64_t n, hipStream_t s, const float* shape, int64_t sper) const {
-    return on ? ddim_eta_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, acp_prev, sigma, philox, seed, off, n, s, shape)
-              : ddim_eta_step_launch(x, eps, z, c_recip, c_recipm1, acp_prev, sigma, philox, seed, off, n, s, shape, sper);
-  }
-  int ddpm(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float sigma, int philox, uint64_t seed,
-           uint64_t off, int64_t n, hipStream_t s, const float* shape, int64_t sper) const {
-    return on ? ddpm_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, coef1, coef2, sigma, philox, seed, off, n, s, shape)
-              : ddpm_step_launch(x, eps, z, c_recip, c_recipm1, coef1, coef2, sigma, philox, seed, off, n, s, shape, sper);
   }
 };
 // x2 = x | x, cond2 = cond | none_value, labels2 = labels | null_label: built once per call
@@ -380,24 +369,25 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     if ((rc = emb.select(run, (size_t)i, a.evalB, s))) return rc;
     run_corr.emb_row = run.emb_row;
     if ((rc = unet_forward(net, x, channels, a.cond_pred, channels, sc.t, sc.v, a.evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
-    if (ls.shape && (rc = x0_shape_stats_launch(x, sc.v, a.guide.on, a.guide.w, a.guide.w_dev, tb->sqrt_recip_alphas_cumprod[i],
-                                                tb->sqrt_recipm1_alphas_cumprod[i], ls.shaping, ls.shape, nullptr, batch, sper, s))) return rc;
+    PredictorStep p;
+    p.x = x; p.eps = sc.v; p.c_recip = tb->sqrt_recip_alphas_cumprod[i]; p.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[i];
+    p.seed = opt->seed; p.guide = a.guide; p.per = sper; p.shape = ls.shape; p.n = n;
+    if (ls.shape && (rc = x0_shape_stats_launch(x, sc.v, a.guide, p.c_recip, p.c_recipm1, ls.shaping, ls.shape, nullptr, batch, sper, s))) return rc;
     if (mode == MI355_DDIM) {
-      if (ls.ms_cx)
-        return a.guide.dpmpp(x, sc.v, ls.hist, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], ls.ms_cx[i], ls.ms_c0[i], ls.ms_c1[i], n, s,
-                             ls.shape, sper);
-      if (!ls.ddim_sigma)
-        return a.guide.ddim(x, sc.v, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i], n, s, ls.shape, sper);
-      const float* z = nullptr; int ph = 0; uint64_t off = 0;   // step 0 has acp_prev = 1: no noise term, no draw
-      if (i > 0 && (rc = next_noise(z, ph, off))) return rc;
-      return a.guide.ddim_eta(x, sc.v, z, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->alphas_cumprod_prev[i],
-                              ls.ddim_sigma[i], ph, opt->seed, off, n, s, ls.shape, sper);
+      if (ls.ms_cx) {
+        p.kind = STEP_DPMPP; p.hist = ls.hist; p.a = ls.ms_cx[i]; p.b = ls.ms_c0[i]; p.c = ls.ms_c1[i];
+      } else if (!ls.ddim_sigma) {
+        p.kind = STEP_DDIM; p.a = tb->alphas_cumprod_prev[i];
+      } else {
+        p.kind = STEP_DDIM_ETA; p.a = tb->alphas_cumprod_prev[i]; p.sigma = ls.ddim_sigma[i];
+        if (i > 0 && (rc = next_noise(p.z, p.use_philox, p.offset))) return rc;   // step 0 has acp_prev = 1: no noise term, no draw
+      }
+      return predictor_step_launch(p, s);
     }
-    const float* z = nullptr; int ph = 0; uint64_t off = 0;
-    if (i > 0 && (rc = next_noise(z, ph, off))) return rc;
-    const float sigma = expf(0.5f * tb->posterior_log_variance_clipped[i]);
-    if ((rc = a.guide.ddpm(x, sc.v, z, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i], tb->posterior_mean_coef1[i],
-                           tb->posterior_mean_coef2[i], sigma, ph, opt->seed, off, n, s, ls.shape, sper))) return rc;
+    p.kind = STEP_ANCESTRAL; p.a = tb->posterior_mean_coef1[i]; p.b = tb->posterior_mean_coef2[i];
+    if (i > 0 && (rc = next_noise(p.z, p.use_philox, p.offset))) return rc;
+    p.sigma = expf(0.5f * tb->posterior_log_variance_clipped[i]);
+    if ((rc = predictor_step_launch(p, s))) return rc;
     for (int c = 0; c < opt->n_corrector; ++c) {   // at batch B (a guided sampler's first half)
       if ((rc = unet_forward(net, x, channels, a.cond_corr, channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run_corr))) return rc;
       const float* z2 = nullptr; int ph2 = 0; uint64_t off2 = 0;
@@ -474,76 +464,130 @@ int check_multistep(const char* who, const mi355_ddpm_tables* tb, const mi355_dd
   ls.ms_cx = ms->cx; ls.ms_c0 = ms->c0; ls.ms_c1 = ms->c1;
   return 0;
 }
-// the history buffer of the multistep entry points: one state behind the unscheduled entry point's workspace
-inline int64_t multistep_hist_offset(const mi355_unet* net, int batch, bool guided) { return (int64_t)al256((size_t)layout_bytes(net, batch, guided, 0)); }
-inline int64_t multistep_bytes(const mi355_unet* net, int batch, bool guided) {
-  const size_t hw = (size_t)net->cfg.image_size * net->cfg.image_size;
-  return multistep_hist_offset(net, batch, guided) + (int64_t)al256((size_t)batch * net->cfg.out_channels * hw * 4);
-}
 std::vector<float> sched_times(int K, const mi355_ddpm_schedule* sd) {   // evaluation k = step k: network(x, (float)tau_k / (float)train_steps)
   std::vector<float> th((size_t)(K > 0 ? K : 0));
   for (int k = 0; k < K; ++k) th[k] = (float)sd->steps[k] / (float)sd->train_steps;
   return th;
 }
 
-// The body of mi355_ddpm_sample and mi355_ddpm_sample_sched: th = the K evaluation times, ls = what the schedule adds (`who` prefixes the refusals).
-int ddpm_sample_run(const char* who, mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt,
-                    const std::vector<float>& th, const LoopSched& ls, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
-                    int64_t workspace_bytes, void* stream) {
-  const std::string f = std::string(who) + ": ";
-  MI355_REQUIRE(channels == net->cfg.out_channels, -2, f + "eps model must output the state's channel count");
-  const int mode = opt->mode;
-  const bool amortized = net->cfg.in_channels == 2 * channels;
-  MI355_REQUIRE(amortized || net->cfg.in_channels == channels, -2, f + "network in_channels must be C or 2C");
-  MI355_REQUIRE(mode != MI355_DDPM_REPLACEMENT || (!amortized && cond), -2, f + "replacement needs an unconditional net and a condition");
-  MI355_REQUIRE(mode != MI355_DDPM_AMORTIZED || (amortized && cond), -2, f + "amortized needs a 2C-input net and a condition");
-  Layout l;
-  if (int rc = carve(net, batch, false, 0, workspace, workspace_bytes, l)) return rc;
-  const Scratch& sc = l.sc;
-  hipStream_t s = S(stream);
-  const int64_t n = (int64_t)batch * channels * net->cfg.image_size * net->cfg.image_size;
-  EvalEmb emb;
-  if (int rc = emb.init(net, sc, th.data(), tb->Ns, false, true, s)) return rc;
-  if (amortized) { if (int rc = fill_launch(sc.none, opt->none_value, n, s)) return rc; }
-  DdpmLoop a = {};
-  a.who = who; a.state = x; a.evalB = batch; a.mask_cond = cond;
-  // the net's condition input on predictor steps / on corrector steps (the reference's corrector calls
-  // x0_model without the condition, sampling.py:116 -> none_like)
-  a.cond_pred = !amortized ? nullptr : ((mode == MI355_DDPM_AMORTIZED || (mode == MI355_DDIM && cond)) ? cond : sc.none);
-  a.cond_corr = amortized ? sc.none : nullptr;
-  return ddpm_loop(net, sc, emb, a, ls, channels, tb, opt, noise, n_noise_draws, batch, n, s);
+// One DDPM call: the seven entry points check their own arguments, fill this, and run ddpm_run.
+struct DdpmGuidance { const int32_t* labels; int null_label; float w; const float* w_dev; };
+struct DdpmCall {
+  const char* who;                  // the entry point's name: prefix of the refusals
+  const DdpmGuidance* guided;       // null: the plain loop
+  std::vector<float> th;            // the K evaluation times
+  LoopSched ls;                     // what the schedule adds; hist and shape are placed by ddpm_run
+  LayoutSpec spec;                  // batch, guided, the DDPM tail
+  bool bare_size_refusal = false;   // mi355_ddpm_sample(_sched): their short-workspace refusal carries no prefix
+  bool count_step = false;          // mi355_unet_get_stats: the last evaluation AND the launches of its step (the multistep and shaped entry points)
+};
+DdpmCall ddpm_call(const char* who, int batch, const DdpmGuidance* guided) {
+  DdpmCall c = {};
+  c.who = who; c.guided = guided; c.spec.batch = batch; c.spec.guided = guided != nullptr;
+  return c;
 }
 
-// The body of mi355_ddpm_cfg_sample and mi355_ddpm_cfg_sample_sched.
-int ddpm_cfg_sample_run(const char* who, mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w,
-                        const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const std::vector<float>& th, const LoopSched& ls,
-                        const float* noise, int64_t n_noise_draws, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
-  const std::string f = std::string(who) + ": ";
-  const int mode = opt->mode;
-  MI355_REQUIRE(mode == MI355_DDPM_AMORTIZED || mode == MI355_DDIM, -1,
-                f + "guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement modes are refused)");
-  MI355_REQUIRE(cond || labels, -1, f + "nothing to guide (neither a condition nor class labels)");
-  MI355_REQUIRE(!labels || net->num_classes > 0, -1, f + "class labels given to a net built without num_classes");
-  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, f + "null_label must be a class index in [0, num_classes)");
-  MI355_REQUIRE(channels == net->cfg.out_channels, -2, f + "eps model must output the state's channel count");
-  MI355_REQUIRE(net->cfg.in_channels == 2 * channels && cond, -2, f + "needs a 2C-input net and a condition");
-  MI355_REQUIRE(workspace_bytes >= mi355_ddpm_cfg_workspace_bytes(net, batch), -2, f + "workspace too small");
+int ddpm_run(DdpmCall& c, mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt,
+             const float* noise, int64_t n_noise_draws, void* workspace, int64_t workspace_bytes, void* stream) {
+  const std::string f = std::string(c.who) + ": ";
+  const DdpmGuidance* const g = c.guided;
+  const int mode = opt->mode, batch = c.spec.batch;
+  const bool amortized = net->cfg.in_channels == 2 * channels;
+  if (g) {
+    const int32_t* const labels = g->labels; const int null_label = g->null_label;
+    MI355_REQUIRE(mode == MI355_DDPM_AMORTIZED || mode == MI355_DDIM, -1,
+                  f + "guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement modes are refused)");
+    MI355_REQUIRE(cond || labels, -1, f + "nothing to guide (neither a condition nor class labels)");
+    MI355_REQUIRE(!labels || net->num_classes > 0, -1, f + "class labels given to a net built without num_classes");
+    MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, f + "null_label must be a class index in [0, num_classes)");
+    MI355_REQUIRE(channels == net->cfg.out_channels, -2, f + "eps model must output the state's channel count");
+    MI355_REQUIRE(net->cfg.in_channels == 2 * channels && cond, -2, f + "needs a 2C-input net and a condition");
+  } else {
+    MI355_REQUIRE(channels == net->cfg.out_channels, -2, f + "eps model must output the state's channel count");
+    MI355_REQUIRE(amortized || net->cfg.in_channels == channels, -2, f + "network in_channels must be C or 2C");
+    MI355_REQUIRE(mode != MI355_DDPM_REPLACEMENT || (!amortized && cond), -2, f + "replacement needs an unconditional net and a condition");
+    MI355_REQUIRE(mode != MI355_DDPM_AMORTIZED || (amortized && cond), -2, f + "amortized needs a 2C-input net and a condition");
+  }
   Layout l;
-  if (int rc = carve(net, batch, true, 0, workspace, workspace_bytes, l)) return rc;
+  if (int rc = carve(net, c.spec, workspace, workspace_bytes, l, c.bare_size_refusal ? nullptr : c.who)) return rc;
   const Scratch& sc = l.sc;
   const CfgTail& tl = l.cfg;
+  c.ls.hist = l.ddpm.hist; c.ls.shape = c.ls.shaping ? l.ddpm.rows : nullptr;
   hipStream_t s = S(stream);
   const int64_t per = (int64_t)channels * net->cfg.image_size * net->cfg.image_size, n = (int64_t)batch * per;
   EvalEmb emb;   // row i (block of num_classes rows with labels) = step i
-  if (int rc = emb.init(net, sc, th.data(), tb->Ns, labels != nullptr, true, s)) return rc;
-  if (int rc = cfg_fill_tail(tl, x, n, cond, n, opt->none_value, labels, null_label, batch, s)) return rc;
+  if (int rc = emb.init(net, sc, c.th.data(), tb->Ns, g && g->labels, true, s)) return rc;
   DdpmLoop a = {};
-  a.who = who; a.state = tl.x2; a.evalB = 2 * batch; a.mirror = tl.x2 + n;
-  a.cond_pred = tl.cond2; a.labels_pred = labels ? tl.labels2 : nullptr;
-  a.cond_corr = tl.cond2 + n; a.labels_corr = labels ? tl.labels2 + batch : nullptr;
-  a.guide.on = true; a.guide.w = w; a.guide.w_dev = w_dev; a.guide.per = per;
-  if (int rc = ddpm_loop(net, sc, emb, a, ls, channels, tb, opt, noise, n_noise_draws, batch, n, s)) return rc;
-  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  a.who = c.who;
+  if (g) {
+    if (int rc = cfg_fill_tail(tl, x, n, cond, n, opt->none_value, g->labels, g->null_label, batch, s)) return rc;
+    a.state = tl.x2; a.evalB = 2 * batch; a.mirror = tl.x2 + n;
+    a.cond_pred = tl.cond2; a.labels_pred = g->labels ? tl.labels2 : nullptr;
+    a.cond_corr = tl.cond2 + n; a.labels_corr = g->labels ? tl.labels2 + batch : nullptr;
+    a.guide.on = true; a.guide.w = g->w; a.guide.w_dev = g->w_dev; a.guide.per = per;
+  } else {
+    if (amortized) { if (int rc = fill_launch(sc.none, opt->none_value, n, s)) return rc; }
+    a.state = x; a.evalB = batch; a.mask_cond = cond;
+    // the net's condition input on predictor steps / on corrector steps (the reference's corrector calls
+    // x0_model without the condition, sampling.py:116 -> none_like)
+    a.cond_pred = !amortized ? nullptr : ((mode == MI355_DDPM_AMORTIZED || (mode == MI355_DDIM && cond)) ? cond : sc.none);
+    a.cond_corr = amortized ? sc.none : nullptr;
+  }
+  if (int rc = ddpm_loop(net, sc, emb, a, c.ls, channels, tb, opt, noise, n_noise_draws, batch, n, s)) return rc;
+  if (g) MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  // after the loop last_launches is the last evaluation's count; with count_step the launches of its step join it: the step launch, and the
+  // statistics launch in front of it where shaping is on
+  if (c.count_step && tb->Ns > 0) net->last_launches += c.ls.shape ? 2 : 1;
+  return 0;
+}
+
+// ---- the fixed-step flow samplers: Runge-Kutta and Adams-Bashforth, plain and guided -----------------------------------------------------------
+// One body behind mi355_cfm_rk_sample, mi355_cfm_cfg_sample, mi355_cfm_ab_sample and mi355_cfm_ab_cfg_sample, run after the entry point's own
+// no-handle checks, which fill a CfmCall; the other arguments are the entry point's own.
+struct CfmGuidance { float none_value; int null_label; float w; const float* w_dev; };
+struct CfmCall {
+  const char* who;                       // the entry point's name: prefix of the refusals
+  int stages; const float* a_host; const float* b_host; const float* c_host;   // the tableau; with ab, its start method
+  const CfmGuidance* guided = nullptr;   // null: the plain loop
+  const AbPlan* ab = nullptr;            // null: a Runge-Kutta step per interval
+  bool report_launches = true;           // mi355_unet_get_stats: every launch of the last step (evaluations and stage launches)
+};
+int cfm_fixed_run(const CfmCall& c, mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, const int32_t* labels,
+                  const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  const std::string f = std::string(c.who) + ": ";
+  const CfmGuidance* const g = c.guided;
+  const AbPlan* const ab = c.ab;
+  const int stages = c.stages;
+  if (g) MI355_REQUIRE(cond || labels, -1, f + "nothing to guide (neither a condition nor class labels)");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, f + "class labels given to a net built without num_classes");
+  if (g) {
+    const int null_label = g->null_label;
+    MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, f + "null_label must be a class index in [0, num_classes)");
+  }
+  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, f + "the vector field must have the state's channel count");
+  if (g)
+    MI355_REQUIRE(!cond || (cond_channels > 0 && (size_t)cond_channels == cfg_cond_channels(net)), -2,
+                  f + "the condition must have in_channels - out_channels channels");
+  Layout l;
+  if (int rc = carve(net, plain_spec(batch, g != nullptr, ab ? ab->order + stages - 1 : stages), workspace, workspace_bytes, l, c.who)) return rc;
+  const CfgTail& tl = l.cfg;
+  hipStream_t s = S(stream);
+  const int64_t hw = (int64_t)net->cfg.image_size * net->cfg.image_size;
+  const int64_t per = (int64_t)x_channels * hw, n = (int64_t)batch * per, nc = (int64_t)batch * cond_channels * hw;
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (n_t == 1) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
+  Guide guide;
+  float* state = x;
+  if (g) {   // the loop runs on x | x at twice the batch, on cond | none_value and labels | null_label
+    if (int rc = cfg_fill_tail(tl, x, n, cond, nc, g->none_value, labels, g->null_label, batch, s)) return rc;
+    guide.on = true; guide.w = g->w; guide.w_dev = g->w_dev; guide.per = per;
+    state = tl.x2; cond = cond ? tl.cond2 : nullptr; labels = labels ? tl.labels2 : nullptr;
+  }
+  int64_t step_launches = 0;
+  if (int rc = cfm_rk_loop(net, l.sc, l.rk, guide, state, x_channels, cond, cond_channels, labels, t_span_host, n_t - 1, stages, c.a_host, c.b_host, c.c_host,
+                           traj, u8_out, g ? 2 * batch : batch, n, s, &step_launches, ab)) return rc;
+  if (g) MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (c.report_launches) net->last_launches = step_launches;
   return 0;
 }
 
@@ -553,22 +597,22 @@ extern "C" {
 
 int64_t mi355_unet_workspace_bytes(const mi355_unet* net, int batch) {
   if (!net || batch <= 0) { mi355_set_error("bad argument"); return -1; }
-  return layout_bytes(net, batch, false, 0);
+  return layout_bytes(net, plain_spec(batch));
 }
 
 int64_t mi355_cfm_rk_workspace_bytes(const mi355_unet* net, int batch, int stages) {
   if (!net || batch <= 0 || stages < 1 || stages > 4) { mi355_set_error("cfm_rk_workspace_bytes: bad argument (1 <= stages <= 4)"); return -1; }
-  return layout_bytes(net, batch, false, stages);
+  return layout_bytes(net, plain_spec(batch, false, stages));
 }
 
 int64_t mi355_cfg_workspace_bytes(const mi355_unet* net, int batch, int stages) {
   if (!net || batch <= 0 || stages < 1 || stages > 4) { mi355_set_error("cfg_workspace_bytes: bad argument (1 <= stages <= 4)"); return -1; }
-  return layout_bytes(net, batch, true, stages);
+  return layout_bytes(net, plain_spec(batch, true, stages));
 }
 
 int64_t mi355_ddpm_cfg_workspace_bytes(const mi355_unet* net, int batch) {
   if (!net || batch <= 0) { mi355_set_error("ddpm_cfg_workspace_bytes: bad argument"); return -1; }
-  return layout_bytes(net, batch, true, 0);
+  return layout_bytes(net, plain_spec(batch, true));
 }
 
 int mi355_cfm_euler_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
@@ -585,7 +629,7 @@ int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, con
   MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_euler_sample: class labels given to a net built without num_classes");
   MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_euler_sample: the vector field must have the state's channel count");
   Layout l;
-  if (int rc = carve(net, batch, false, 0, workspace, workspace_bytes, l)) return rc;
+  if (int rc = carve(net, plain_spec(batch), workspace, workspace_bytes, l)) return rc;
   const Scratch& sc = l.sc;
   hipStream_t s = S(stream);
   EvalEmb emb;   // t_span_host is the caller's array: no wait
@@ -613,23 +657,15 @@ int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, con
   return 0;
 }
 
+// Runge-Kutta entry points: the handle checks run first, check_tableau behind them.
 int mi355_cfm_rk_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, const int32_t* labels,
                         const float* t_span_host, int n_t, int stages, const float* a_host, const float* b_host, const float* c_host, float* traj,
                         uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(net && x && t_span_host && n_t >= 1 && batch > 0, -1, "cfm_rk_sample: bad argument");
   if (int rc = check_tableau("cfm_rk_sample", stages, a_host, b_host, c_host)) return rc;
-  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_rk_sample: class labels given to a net built without num_classes");
-  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_rk_sample: the vector field must have the state's channel count");
-  MI355_REQUIRE(workspace_bytes >= mi355_cfm_rk_workspace_bytes(net, batch, stages), -2, "cfm_rk_sample: workspace too small");
-  Layout l;
-  if (int rc = carve(net, batch, false, stages, workspace, workspace_bytes, l)) return rc;
-  hipStream_t s = S(stream);
-  const int64_t n = (int64_t)batch * x_channels * net->cfg.image_size * net->cfg.image_size;
-  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-  if (n_t == 1) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
-  int64_t step_launches = 0;   // not reported: mi355_unet_get_stats keeps the last evaluation's count
-  return cfm_rk_loop(net, l.sc, l.rk, Guide(), x, x_channels, cond, cond_channels, labels, t_span_host, n_t - 1, stages, a_host, b_host, c_host, traj, u8_out,
-                     batch, n, s, &step_launches);
+  CfmCall c{"cfm_rk_sample", stages, a_host, b_host, c_host};
+  c.report_launches = false;   // this entry point alone: mi355_unet_get_stats keeps the last evaluation's count after it
+  return cfm_fixed_run(c, net, x, x_channels, cond, cond_channels, labels, t_span_host, n_t, traj, u8_out, batch, workspace, workspace_bytes, stream);
 }
 
 int mi355_cfm_cfg_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, float none_value, const int32_t* labels,
@@ -638,151 +674,117 @@ int mi355_cfm_cfg_sample(mi355_unet* net, float* x, int x_channels, const float*
                          void* stream) {
   MI355_REQUIRE(net && x && t_span_host && n_t >= 1 && batch > 0, -1, "cfm_cfg_sample: bad argument");
   if (int rc = check_tableau("cfm_cfg_sample", stages, a_host, b_host, c_host)) return rc;
-  MI355_REQUIRE(cond || labels, -1, "cfm_cfg_sample: nothing to guide (neither a condition nor class labels)");
-  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_cfg_sample: class labels given to a net built without num_classes");
-  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, "cfm_cfg_sample: null_label must be a class index in [0, num_classes)");
-  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_cfg_sample: the vector field must have the state's channel count");
-  MI355_REQUIRE(!cond || (cond_channels > 0 && (size_t)cond_channels == cfg_cond_channels(net)), -2,
-                "cfm_cfg_sample: the condition must have in_channels - out_channels channels");
-  MI355_REQUIRE(workspace_bytes >= mi355_cfg_workspace_bytes(net, batch, stages), -2, "cfm_cfg_sample: workspace too small");
-  Layout l;
-  if (int rc = carve(net, batch, true, stages, workspace, workspace_bytes, l)) return rc;
-  const CfgTail& tl = l.cfg;
-  hipStream_t s = S(stream);
-  const int64_t hw = (int64_t)net->cfg.image_size * net->cfg.image_size;
-  const int64_t per = (int64_t)x_channels * hw, n = (int64_t)batch * per, nc = (int64_t)batch * cond_channels * hw;
-  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-  if (n_t == 1) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
-  if (int rc = cfg_fill_tail(tl, x, n, cond, nc, none_value, labels, null_label, batch, s)) return rc;
-  Guide guide; guide.on = true; guide.w = w; guide.w_dev = w_dev; guide.per = per;
-  int64_t step_launches = 0;
-  if (int rc = cfm_rk_loop(net, l.sc, l.rk, guide, tl.x2, x_channels, cond ? tl.cond2 : nullptr, cond_channels, labels ? tl.labels2 : nullptr, t_span_host,
-                           n_t - 1, stages, a_host, b_host, c_host, traj, u8_out, 2 * batch, n, s, &step_launches)) return rc;
-  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-  net->last_launches = step_launches;   // mi355_unet_get_stats: every launch of the last step (evaluations and stage launches)
-  return 0;
+  const CfmGuidance g{none_value, null_label, w, w_dev};
+  CfmCall c{"cfm_cfg_sample", stages, a_host, b_host, c_host};
+  c.guided = &g;
+  return cfm_fixed_run(c, net, x, x_channels, cond, cond_channels, labels, t_span_host, n_t, traj, u8_out, batch, workspace, workspace_bytes, stream);
 }
 
 int mi355_ddpm_sample(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb,
                       const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
                       int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(net && x && tb && opt, -1, "ddpm_sample: null argument");
-  return ddpm_sample_run("ddpm_sample", net, x, channels, cond, tb, opt, ddpm_times(tb->Ns), LoopSched(), noise, n_noise_draws, batch, workspace,
-                         workspace_bytes, stream);
+  DdpmCall c = ddpm_call("ddpm_sample", batch, nullptr);
+  c.th = ddpm_times(tb->Ns); c.bare_size_refusal = true;
+  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }
 
 int mi355_ddpm_sample_sched(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb,
                             const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched, const float* noise, int64_t n_noise_draws, int batch,
                             void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(net && x && tb && opt, -1, "ddpm_sample_sched: null argument");
-  LoopSched ls;
-  if (int rc = check_schedule("ddpm_sample_sched", tb, opt, sched, false, ls)) return rc;
-  return ddpm_sample_run("ddpm_sample_sched", net, x, channels, cond, tb, opt, sched_times(tb->Ns, sched), ls, noise, n_noise_draws, batch, workspace,
-                         workspace_bytes, stream);
+  DdpmCall c = ddpm_call("ddpm_sample_sched", batch, nullptr);
+  if (int rc = check_schedule(c.who, tb, opt, sched, false, c.ls)) return rc;
+  c.th = sched_times(tb->Ns, sched); c.bare_size_refusal = true;
+  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }
 
 int mi355_ddpm_cfg_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w, const float* w_dev,
                           const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const float* noise, int64_t n_noise_draws, int batch,
                           void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(net && x && tb && opt && batch > 0, -1, "ddpm_cfg_sample: bad argument");
-  return ddpm_cfg_sample_run("ddpm_cfg_sample", net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, ddpm_times(tb->Ns), LoopSched(), noise,
-                             n_noise_draws, batch, workspace, workspace_bytes, stream);
+  const DdpmGuidance g{labels, null_label, w, w_dev};
+  DdpmCall c = ddpm_call("ddpm_cfg_sample", batch, &g);
+  c.th = ddpm_times(tb->Ns);
+  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }
 
 int mi355_ddpm_cfg_sample_sched(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w,
                                 const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
                                 const float* noise, int64_t n_noise_draws, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(net && x && tb && opt && batch > 0, -1, "ddpm_cfg_sample_sched: bad argument");
-  LoopSched ls;
-  if (int rc = check_schedule("ddpm_cfg_sample_sched", tb, opt, sched, true, ls)) return rc;
-  return ddpm_cfg_sample_run("ddpm_cfg_sample_sched", net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, sched_times(tb->Ns, sched), ls,
-                             noise, n_noise_draws, batch, workspace, workspace_bytes, stream);
+  const DdpmGuidance g{labels, null_label, w, w_dev};
+  DdpmCall c = ddpm_call("ddpm_cfg_sample_sched", batch, &g);
+  if (int rc = check_schedule(c.who, tb, opt, sched, true, c.ls)) return rc;
+  c.th = sched_times(tb->Ns, sched);
+  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }
 
+// The multistep entry points keep the history, one state at `batch`, behind the unscheduled entry point's workspace.
 int64_t mi355_ddpm_multistep_workspace_bytes(const mi355_unet* net, int batch, int guided) {
   if (!net || batch <= 0) { mi355_set_error("ddpm_multistep_workspace_bytes: bad argument"); return -1; }
-  return multistep_bytes(net, batch, guided != 0);
+  LayoutSpec sp = plain_spec(batch, guided != 0);
+  sp.hist = true;
+  return layout_bytes(net, sp);
 }
 
 int mi355_ddpm_multistep_sample(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt,
                                 const mi355_multistep_schedule* msched, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(tb && opt, -1, "ddpm_multistep_sample: tables or opt is null");
-  mi355_ddpm_schedule sd; LoopSched ls;   // the schedule's refusals need no handle
-  if (int rc = check_multistep("ddpm_multistep_sample", tb, opt, msched, false, sd, ls)) return rc;
+  DdpmCall c = ddpm_call("ddpm_multistep_sample", batch, nullptr);
+  mi355_ddpm_schedule sd;   // the schedule's refusals need no handle
+  if (int rc = check_multistep(c.who, tb, opt, msched, false, sd, c.ls)) return rc;
   MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_multistep_sample: bad argument (net, x, workspace, batch)");
-  MI355_REQUIRE(workspace_bytes >= multistep_bytes(net, batch, false), -2, "ddpm_multistep_sample: workspace too small");
-  ls.hist = reinterpret_cast<float*>(static_cast<char*>(workspace) + multistep_hist_offset(net, batch, false));
-  if (int rc = ddpm_sample_run("ddpm_multistep_sample", net, x, channels, cond, tb, opt, sched_times(tb->Ns, &sd), ls, nullptr, 0, batch, workspace,
-                               workspace_bytes, stream)) return rc;
-  if (tb->Ns > 0) ++net->last_launches;   // mi355_unet_get_stats: the last evaluation and its step launch
-  return 0;
+  c.th = sched_times(tb->Ns, &sd); c.spec.hist = true; c.count_step = true;
+  return ddpm_run(c, net, x, channels, cond, tb, opt, nullptr, 0, workspace, workspace_bytes, stream);
 }
 
 int mi355_ddpm_multistep_cfg_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w,
                                     const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt,
                                     const mi355_multistep_schedule* msched, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(tb && opt, -1, "ddpm_multistep_cfg_sample: tables or opt is null");
-  mi355_ddpm_schedule sd; LoopSched ls;
-  if (int rc = check_multistep("ddpm_multistep_cfg_sample", tb, opt, msched, true, sd, ls)) return rc;
+  const DdpmGuidance g{labels, null_label, w, w_dev};
+  DdpmCall c = ddpm_call("ddpm_multistep_cfg_sample", batch, &g);
+  mi355_ddpm_schedule sd;
+  if (int rc = check_multistep(c.who, tb, opt, msched, true, sd, c.ls)) return rc;
   MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_multistep_cfg_sample: bad argument (net, x, workspace, batch)");
-  const bool roomy = workspace_bytes >= multistep_bytes(net, batch, true);
-  // a short workspace is refused by the guided run's own size check, its last refusal, so that its other refusals keep their order
-  ls.hist = roomy ? reinterpret_cast<float*>(static_cast<char*>(workspace) + multistep_hist_offset(net, batch, true)) : nullptr;
-  if (int rc = ddpm_cfg_sample_run("ddpm_multistep_cfg_sample", net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, sched_times(tb->Ns, &sd), ls,
-                                   nullptr, 0, batch, workspace, roomy ? workspace_bytes : 0, stream)) return rc;
-  if (tb->Ns > 0) ++net->last_launches;
-  return 0;
+  c.th = sched_times(tb->Ns, &sd); c.spec.hist = true; c.count_step = true;
+  return ddpm_run(c, net, x, channels, cond, tb, opt, nullptr, 0, workspace, workspace_bytes, stream);
 }
 
-// Per-image shaping of the data prediction (mi355_x0_shaping): one entry point over the six loops above.  The rows (f, s) of the images live behind
-// the workspace of the loop chosen.
-namespace {
-inline int64_t shaped_rows_offset(const mi355_unet* net, int batch, bool guided, bool multistep) {
-  return multistep ? multistep_bytes(net, batch, guided) : (int64_t)al256((size_t)layout_bytes(net, batch, guided, 0));
-}
-inline int64_t shaped_bytes(const mi355_unet* net, int batch, bool guided, bool multistep) {
-  return shaped_rows_offset(net, batch, guided, multistep) + (int64_t)al256((size_t)batch * 2 * 4);
-}
-}  // namespace
-
+// Per-image shaping of the data prediction (mi355_x0_shaping): one entry point over the six loops above.  The rows (f, s) of the images close the
+// workspace of the loop chosen (kept in the layout whether or not shaping is on: the size does not depend on the shaping).
 int64_t mi355_ddpm_shaped_workspace_bytes(const mi355_unet* net, int batch, int guided, int multistep) {
   if (!net || batch <= 0) { mi355_set_error("ddpm_shaped_workspace_bytes: bad argument"); return -1; }
-  return shaped_bytes(net, batch, guided != 0, multistep != 0);
+  LayoutSpec sp = plain_spec(batch, guided != 0);
+  sp.hist = multistep != 0; sp.rows = true;
+  return layout_bytes(net, sp);
 }
 
 int mi355_ddpm_shaped_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, int guided, float w,
                              const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
                              const mi355_multistep_schedule* msched, const mi355_x0_shaping* shaping, const float* noise, int64_t n_noise_draws,
                              int batch, void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* who = "ddpm_shaped_sample";
   MI355_REQUIRE(tb && opt, -1, "ddpm_shaped_sample: tables or opt is null");
   MI355_REQUIRE(!(sched && msched), -1, "ddpm_shaped_sample: both sched and msched given (a run follows one schedule)");
-  if (int rc = check_x0_shaping(who, shaping, guided)) return rc;   // these refusals need no handle
-  const bool g = guided != 0, on = shaping && (shaping->quantile > 0.f || shaping->rescale_phi > 0.f);
-  mi355_ddpm_schedule sd; LoopSched ls;
-  std::vector<float> th;
+  const DdpmGuidance g{labels, null_label, w, w_dev};
+  DdpmCall c = ddpm_call("ddpm_shaped_sample", batch, guided ? &g : nullptr);
+  if (int rc = check_x0_shaping(c.who, shaping, guided)) return rc;   // these refusals need no handle
+  mi355_ddpm_schedule sd;
   if (msched) {
     MI355_REQUIRE(!noise, -1, "ddpm_shaped_sample: noise given with msched (the multistep solver is deterministic and draws none)");
-    if (int rc = check_multistep(who, tb, opt, msched, g, sd, ls)) return rc;
-    th = sched_times(tb->Ns, &sd);
+    if (int rc = check_multistep(c.who, tb, opt, msched, c.spec.guided, sd, c.ls)) return rc;
+    c.th = sched_times(tb->Ns, &sd);
   } else if (sched) {
-    if (int rc = check_schedule(who, tb, opt, sched, g, ls)) return rc;
-    th = sched_times(tb->Ns, sched);
+    if (int rc = check_schedule(c.who, tb, opt, sched, c.spec.guided, c.ls)) return rc;
+    c.th = sched_times(tb->Ns, sched);
   } else {
-    th = ddpm_times(tb->Ns);
+    c.th = ddpm_times(tb->Ns);
   }
   MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_shaped_sample: bad argument (net, x, workspace, batch)");
-  const bool roomy = workspace_bytes >= shaped_bytes(net, batch, g, msched != nullptr);
-  // a short workspace is refused by the guided run's own size check, its last refusal, so that its other refusals keep their order
-  MI355_REQUIRE(roomy || g, -2, "ddpm_shaped_sample: workspace too small");
-  char* const ws = static_cast<char*>(workspace);
-  if (msched) ls.hist = roomy ? reinterpret_cast<float*>(ws + multistep_hist_offset(net, batch, g)) : nullptr;
-  if (on && roomy) { ls.shaping = shaping; ls.shape = reinterpret_cast<float*>(ws + shaped_rows_offset(net, batch, g, msched != nullptr)); }
-  if (int rc = g ? ddpm_cfg_sample_run(who, net, x, channels, cond, labels, null_label, w, w_dev, tb, opt, th, ls, noise, n_noise_draws, batch, workspace,
-                                       roomy ? workspace_bytes : 0, stream)
-                 : ddpm_sample_run(who, net, x, channels, cond, tb, opt, th, ls, noise, n_noise_draws, batch, workspace, workspace_bytes, stream)) return rc;
-  if (tb->Ns > 0) net->last_launches += on ? 2 : 1;   // mi355_unet_get_stats: the last evaluation, the statistics launch, the step launch
-  return 0;
+  c.spec.hist = msched != nullptr; c.spec.rows = true; c.count_step = true;
+  if (shaping && (shaping->quantile > 0.f || shaping->rescale_phi > 0.f)) c.ls.shaping = shaping;   // off: the unshaped loop, bit for bit
+  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }
 
 // Adams-Bashforth CFM samplers: the loop of mi355_cfm_rk_sample / mi355_cfm_cfg_sample with the tableau as the start method (cfm_rk_loop, AbPlan).
@@ -810,30 +812,20 @@ int64_t mi355_cfm_ab_workspace_bytes(const mi355_unet* net, int batch, int order
     mi355_set_error("cfm_ab_workspace_bytes: bad argument (2 <= order <= 4, 1 <= start_stages <= 4)");
     return -1;
   }
-  return layout_bytes(net, batch, guided != 0, order + start_stages - 1);
+  return layout_bytes(net, plain_spec(batch, guided != 0, order + start_stages - 1));
 }
 
+// Adams-Bashforth entry points: check_ab needs no handle and runs before the handle checks.
 int mi355_cfm_ab_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, const int32_t* labels, const float* t_span_host,
                         int n_t, int order, const float* w_host, int start_stages, const float* a_host, const float* b_host, const float* c_host,
                         float* traj, uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(t_span_host && n_t >= 1, -1, "cfm_ab_sample: t_span_host is null or empty");
-  if (int rc = check_ab("cfm_ab_sample", order, w_host, n_t, start_stages, a_host, b_host, c_host)) return rc;   // needs no handle
+  if (int rc = check_ab("cfm_ab_sample", order, w_host, n_t, start_stages, a_host, b_host, c_host)) return rc;
   MI355_REQUIRE(net && x && batch > 0, -1, "cfm_ab_sample: bad argument (net, x, batch)");
-  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_ab_sample: class labels given to a net built without num_classes");
-  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_ab_sample: the vector field must have the state's channel count");
-  MI355_REQUIRE(workspace_bytes >= mi355_cfm_ab_workspace_bytes(net, batch, order, start_stages, 0), -2, "cfm_ab_sample: workspace too small");
-  Layout l;
-  if (int rc = carve(net, batch, false, order + start_stages - 1, workspace, workspace_bytes, l)) return rc;
-  hipStream_t s = S(stream);
-  const int64_t n = (int64_t)batch * x_channels * net->cfg.image_size * net->cfg.image_size;
-  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-  if (n_t == 1) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
   const AbPlan ab{order, w_host};
-  int64_t step_launches = 0;
-  if (int rc = cfm_rk_loop(net, l.sc, l.rk, Guide(), x, x_channels, cond, cond_channels, labels, t_span_host, n_t - 1, start_stages, a_host, b_host, c_host,
-                           traj, u8_out, batch, n, s, &step_launches, &ab)) return rc;
-  net->last_launches = step_launches;   // mi355_unet_get_stats: every launch of the last step
-  return 0;
+  CfmCall c{"cfm_ab_sample", start_stages, a_host, b_host, c_host};
+  c.ab = &ab;
+  return cfm_fixed_run(c, net, x, x_channels, cond, cond_channels, labels, t_span_host, n_t, traj, u8_out, batch, workspace, workspace_bytes, stream);
 }
 
 int mi355_cfm_ab_cfg_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, float none_value, const int32_t* labels,
@@ -843,30 +835,11 @@ int mi355_cfm_ab_cfg_sample(mi355_unet* net, float* x, int x_channels, const flo
   MI355_REQUIRE(t_span_host && n_t >= 1, -1, "cfm_ab_cfg_sample: t_span_host is null or empty");
   if (int rc = check_ab("cfm_ab_cfg_sample", order, w_host, n_t, start_stages, a_host, b_host, c_host)) return rc;
   MI355_REQUIRE(net && x && batch > 0, -1, "cfm_ab_cfg_sample: bad argument (net, x, batch)");
-  MI355_REQUIRE(cond || labels, -1, "cfm_ab_cfg_sample: nothing to guide (neither a condition nor class labels)");
-  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_ab_cfg_sample: class labels given to a net built without num_classes");
-  MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, "cfm_ab_cfg_sample: null_label must be a class index in [0, num_classes)");
-  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_ab_cfg_sample: the vector field must have the state's channel count");
-  MI355_REQUIRE(!cond || (cond_channels > 0 && (size_t)cond_channels == cfg_cond_channels(net)), -2,
-                "cfm_ab_cfg_sample: the condition must have in_channels - out_channels channels");
-  MI355_REQUIRE(workspace_bytes >= mi355_cfm_ab_workspace_bytes(net, batch, order, start_stages, 1), -2, "cfm_ab_cfg_sample: workspace too small");
-  Layout l;
-  if (int rc = carve(net, batch, true, order + start_stages - 1, workspace, workspace_bytes, l)) return rc;
-  const CfgTail& tl = l.cfg;
-  hipStream_t s = S(stream);
-  const int64_t hw = (int64_t)net->cfg.image_size * net->cfg.image_size;
-  const int64_t per = (int64_t)x_channels * hw, n = (int64_t)batch * per, nc = (int64_t)batch * cond_channels * hw;
-  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-  if (n_t == 1) return u8_out ? quantize_u8_launch(x, u8_out, n, s) : 0;
-  if (int rc = cfg_fill_tail(tl, x, n, cond, nc, none_value, labels, null_label, batch, s)) return rc;
-  Guide guide; guide.on = true; guide.w = w; guide.w_dev = w_dev; guide.per = per;
+  const CfmGuidance g{none_value, null_label, w, w_dev};
   const AbPlan ab{order, w_host};
-  int64_t step_launches = 0;
-  if (int rc = cfm_rk_loop(net, l.sc, l.rk, guide, tl.x2, x_channels, cond ? tl.cond2 : nullptr, cond_channels, labels ? tl.labels2 : nullptr, t_span_host,
-                           n_t - 1, start_stages, a_host, b_host, c_host, traj, u8_out, 2 * batch, n, s, &step_launches, &ab)) return rc;
-  MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-  net->last_launches = step_launches;
-  return 0;
+  CfmCall c{"cfm_ab_cfg_sample", start_stages, a_host, b_host, c_host};
+  c.guided = &g; c.ab = &ab;
+  return cfm_fixed_run(c, net, x, x_channels, cond, cond_channels, labels, t_span_host, n_t, traj, u8_out, batch, workspace, workspace_bytes, stream);
 }
 
 // Training-free in-painting / super-resolution of an unconditional flow: replacement along the straight path and / or reconstruction guidance
@@ -875,7 +848,9 @@ int mi355_cfm_ab_cfg_sample(mi355_unet* net, float* x, int x_channels, const flo
 int64_t mi355_cfm_recon_workspace_bytes(const mi355_unet* net, int batch, int h_low, int w_low) {
   if (!net || batch <= 0 || h_low < 0 || w_low < 0) { mi355_set_error("cfm_recon_workspace_bytes: bad argument"); return -1; }
   const ReconDims rd{h_low, w_low};
-  return (int64_t)layout(net, batch, false, 0, 0, &rd).end;
+  LayoutSpec sp = plain_spec(batch);
+  sp.recon = &rd;
+  return layout_bytes(net, sp);
 }
 
 int mi355_cfm_recon_sample(mi355_unet* net, float* x, int channels, const int32_t* labels, const float* t_span_host, int n_t, const float* y, int mode,
@@ -902,8 +877,10 @@ int mi355_cfm_recon_sample(mi355_unet* net, float* x, int channels, const int32_
     MI355_REQUIRE(H % h_low == 0 && W % w_low == 0, -4, "cfm_recon_sample: the low resolution must divide the state's (integer factors only)");
   }
   const ReconDims rd{mode == 2 ? h_low : 0, mode == 2 ? w_low : 0};
+  LayoutSpec sp = plain_spec(batch);
+  sp.recon = &rd;
   Layout l;
-  if (int rc = carve(net, batch, false, 0, workspace, workspace_bytes, l, &rd)) return rc;
+  if (int rc = carve(net, sp, workspace, workspace_bytes, l)) return rc;
   const Scratch& sc = l.sc;
   const ReconTail& rt = l.rec;
   hipStream_t s = S(stream);
@@ -989,8 +966,8 @@ int mi355_sf2m_euler_sample(mi355_unet* drift, mi355_unet* score, float* x, int 
     MI355_REQUIRE(out_step_host[j] >= 0 && out_step_host[j] < n_steps && out_w_host[j] >= 0.f && out_w_host[j] <= 1.f, -1,
                   "sf2m_euler_sample: an output's step must be in [0, n_steps) and its weight in [0, 1]");
   Layout ld, ls;
-  if (int rc = carve(drift, batch, false, 0, drift_workspace, drift_workspace_bytes, ld)) return rc;
-  if (int rc = carve(score, batch, false, 0, score_workspace, score_workspace_bytes, ls)) return rc;
+  if (int rc = carve(drift, plain_spec(batch), drift_workspace, drift_workspace_bytes, ld)) return rc;
+  if (int rc = carve(score, plain_spec(batch), score_workspace, score_workspace_bytes, ls)) return rc;
   const Scratch &sd = ld.sc, &ss = ls.sc;
   hipStream_t s = S(stream);
   const int64_t n = (int64_t)batch * channels * cd.image_size * cd.image_size;

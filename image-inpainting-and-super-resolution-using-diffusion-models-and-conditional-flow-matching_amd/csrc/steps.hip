@@ -148,7 +148,7 @@ template <bool SH> struct X0Rows {
     else return clip_nan(x0_pre(c_recip, c_recipm1, x, e), -1.f, 1.f);
   }
 };
-// run f(EpsSrc<CFG>, X0Rows<SH>) for the form a launcher was asked for
+// run f(EpsSrc<CFG>, X0Rows<SH>) for the form predictor_step_launch was asked for
 template <typename F> int step_form(bool cfg, const float* eps, int64_t n, float w, const float* w_dev, int64_t per, const float* shape, F&& f) {
   if (cfg) {
     const EpsSrc<true> e{eps, n, w, w_dev, per};
@@ -157,9 +157,6 @@ template <typename F> int step_form(bool cfg, const float* eps, int64_t n, float
   const EpsSrc<false> e{eps, n, 0.f, nullptr, 0};
   return shape ? f(e, X0Rows<true>{shape, per}) : f(e, X0Rows<false>{nullptr, 0});
 }
-#define MI355_SHAPE_ARGS(name) \
-  MI355_REQUIRE(!shape || (per > 0 && n % per == 0), -1, name ": per-image shaping rows need n to be whole images of elems_per_image elements")
-
 }  // namespace
 
 int euler_step_launch(float* x, const float* v, float dt, int64_t n, hipStream_t s) {
@@ -210,7 +207,8 @@ int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, fl
   });
 }
 
-// The predictor steps.  Each has four forms, chosen by step_form: plain or classifier-free-guided (EpsSrc), static clip or per-image shaping (X0Rows).
+// The predictor steps: one kernel template per kind, all launched by predictor_step_launch (below the last of them).  Each has four forms, chosen by
+// step_form: plain or classifier-free-guided (EpsSrc), static clip or per-image shaping (X0Rows).
 namespace {
 template <class E, class R>
 int ddpm_step_form(E es, R rows, float* x, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float sigma, int use_philox,
@@ -231,16 +229,6 @@ int ddpm_step_form(E es, R rows, float* x, const float* z, float c_recip, float 
   });
 }
 }  // namespace
-
-int ddpm_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float coef1, float coef2,
-                     float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape, int64_t per) {
-  MI355_REQUIRE(offset % 4 == 0, -1, "ddpm_step: the Philox offset must be a multiple of 4");
-  MI355_SHAPE_ARGS("ddpm_step");
-  const uint64_t off4 = offset / 4;
-  return step_form(false, eps, n, 0.f, nullptr, per, shape, [=](auto es, auto rows) {
-    return ddpm_step_form(es, rows, x, z, c_recip, c_recipm1, coef1, coef2, sigma, use_philox, seed, off4, n, s);
-  });
-}
 
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,
                           float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
@@ -280,42 +268,10 @@ int ddim_step_form(E es, R rows, float* x, float c_recip, float c_recipm1, float
 }
 }  // namespace
 
-int ddim_step_launch(float* x, const float* eps, float c_recip, float c_recipm1, float acp_prev, int64_t n, hipStream_t s, const float* shape, int64_t per) {
-  MI355_SHAPE_ARGS("ddim_step");
-  const float sa = sqrtf(acp_prev), sb = sqrtf(1.0f - acp_prev);
-  return step_form(false, eps, n, 0.f, nullptr, per, shape,
-                   [=](auto es, auto rows) { return ddim_step_form(es, rows, x, c_recip, c_recipm1, sa, sb, n, s); });
-}
-
-// Classifier-free-guided forms of the two steps above (EpsSrc<true>): eps_g = eps_u + w * (eps_c - eps_u) with the difference, the product and the
-// sum each rounded, then the arithmetic of ddpm_step_launch / ddim_step_launch on eps_g.  Philox: indexed by the element of the n-element state.
-int ddpm_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
-                         float coef1, float coef2, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s,
-                         const float* shape) {
-  MI355_REQUIRE(offset % 4 == 0, -1, "ddpm_cfg_step: the Philox offset must be a multiple of 4");
-  MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "ddpm_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
-  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddpm_cfg_step: null argument");
-  MI355_SHAPE_ARGS("ddpm_cfg_step");
-  const uint64_t off4 = offset / 4;
-  return step_form(true, eps, n, w, w_dev, per, shape, [=](auto es, auto rows) {
-    return ddpm_step_form(es, rows, x, z, c_recip, c_recipm1, coef1, coef2, sigma, use_philox, seed, off4, n, s);
-  });
-}
-
-int ddim_cfg_step_launch(float* x, const float* eps, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float acp_prev, int64_t n,
-                         hipStream_t s, const float* shape) {
-  MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "ddim_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
-  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_cfg_step: null argument");
-  MI355_SHAPE_ARGS("ddim_cfg_step");
-  const float sa = sqrtf(acp_prev), sb = sqrtf(1.0f - acp_prev);
-  return step_form(true, eps, n, w, w_dev, per, shape,
-                   [=](auto es, auto rows) { return ddim_step_form(es, rows, x, c_recip, c_recipm1, sa, sb, n, s); });
-}
-
-// DDIM(eta) step (Song et al. 2021, eq. 12) with the reference's clipped x0_hat: ddim_step_launch's x0 and e2, then
+// DDIM(eta) step (Song et al. 2021, eq. 12) with the reference's clipped x0_hat: the DDIM step's x0 and e2, then
 //   x <- sqrt(acp_prev) x0 + sqrt(max(1 - acp_prev - sigma^2, 0)) e2 + sigma z,
-// the two square roots taken here on the host (1 - acp_prev - sigma^2 left to right, sigma^2 rounded).  Noise as ddpm_step_launch; with neither z
-// nor Philox the noise term is not added at all, so sigma = 0 without noise gives ddim_step_launch's bits.
+// the two square roots taken here on the host (1 - acp_prev - sigma^2 left to right, sigma^2 rounded).  Noise as the ancestral step; with neither z
+// nor Philox the noise term is not added at all, so sigma = 0 without noise gives the DDIM step's bits.
 namespace {
 struct DdimEta { float sa, sb; };
 inline DdimEta ddim_eta_coefs(float acp_prev, float sigma) {
@@ -344,39 +300,8 @@ int ddim_eta_step_form(E es, R rows, float* x, const float* z, float c_recip, fl
 }
 }  // namespace
 
-int ddim_eta_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float acp_prev, float sigma, int use_philox,
-                         uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape, int64_t per) {
-  MI355_REQUIRE(offset % 4 == 0, -1, "ddim_eta_step: the Philox offset must be a multiple of 4");
-  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_eta_step: null argument");
-  MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, "ddim_eta_step: sigma must be finite and >= 0");
-  MI355_SHAPE_ARGS("ddim_eta_step");
-  const uint64_t off4 = offset / 4;
-  const DdimEta c = ddim_eta_coefs(acp_prev, sigma);
-  const int noisy = z != nullptr || use_philox;
-  return step_form(false, eps, n, 0.f, nullptr, per, shape, [=](auto es, auto rows) {
-    return ddim_eta_step_form(es, rows, x, z, c_recip, c_recipm1, c.sa, c.sb, sigma, noisy, use_philox, seed, off4, n, s);
-  });
-}
-
-// its classifier-free-guided form, built as ddim_cfg_step_launch: eps [2n], x [2n] (first half read, both halves written), Philox indexed by the
-// element of the n-element state
-int ddim_eta_cfg_step_launch(float* x, const float* eps, const float* z, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1,
-                             float acp_prev, float sigma, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, const float* shape) {
-  MI355_REQUIRE(offset % 4 == 0, -1, "ddim_eta_cfg_step: the Philox offset must be a multiple of 4");
-  MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "ddim_eta_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
-  MI355_REQUIRE(n <= 0 || (x && eps), -1, "ddim_eta_cfg_step: null argument");
-  MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, "ddim_eta_cfg_step: sigma must be finite and >= 0");
-  MI355_SHAPE_ARGS("ddim_eta_cfg_step");
-  const uint64_t off4 = offset / 4;
-  const DdimEta c = ddim_eta_coefs(acp_prev, sigma);
-  const int noisy = z != nullptr || use_philox;
-  return step_form(true, eps, n, w, w_dev, per, shape, [=](auto es, auto rows) {
-    return ddim_eta_step_form(es, rows, x, z, c_recip, c_recipm1, c.sa, c.sb, sigma, noisy, use_philox, seed, off4, n, s);
-  });
-}
-
 // Forward move q(x_k | x_{k-1}) of a (respaced) chain: x <- a x + b z with a = sqrt(alphas_k), b = sqrt(betas_k), two rounded products and one
-// sum.  Noise as ddpm_step_launch (neither z nor Philox: z = 0, x <- a x + b * 0).
+// sum.  Noise as the ancestral step (neither z nor Philox: z = 0, x <- a x + b * 0).
 int renoise_step_launch(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
   MI355_REQUIRE(offset % 4 == 0, -1, "renoise_step: the Philox offset must be a multiple of 4");
   MI355_REQUIRE(n <= 0 || x, -1, "renoise_step: null argument");
@@ -606,24 +531,42 @@ int dpmpp_step_form(E es, R rows, float* x, float* hist, float c_recip, float c_
 }
 }  // namespace
 
-int dpmpp_step_launch(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s,
-                      const float* shape, int64_t per) {
-  MI355_REQUIRE(n <= 0 || (x && eps), -1, "dpmpp_step: null argument");
-  MI355_REQUIRE(c1 == 0.f || hist || n <= 0, -1, "dpmpp_step: c1 != 0 needs hist (the previous step's data prediction)");
-  MI355_SHAPE_ARGS("dpmpp_step");
-  return step_form(false, eps, n, 0.f, nullptr, per, shape,
-                   [=](auto es, auto rows) { return dpmpp_step_form(es, rows, x, hist, c_recip, c_recipm1, cx, c0, c1, n, s); });
-}
-
-// its classifier-free-guided form, built as ddim_cfg_step_launch: eps [2n], x [2n] (first half read, both halves written), hist [n]
-int dpmpp_cfg_step_launch(float* x, const float* eps, float* hist, float w, const float* w_dev, int64_t per, float c_recip, float c_recipm1, float cx,
-                          float c0, float c1, int64_t n, hipStream_t s, const float* shape) {
-  MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, "dpmpp_cfg_step: per-image scales need n to be whole images of elems_per_image elements");
-  MI355_REQUIRE(n <= 0 || (x && eps), -1, "dpmpp_cfg_step: null argument");
-  MI355_REQUIRE(c1 == 0.f || hist || n <= 0, -1, "dpmpp_cfg_step: c1 != 0 needs hist (the previous step's data prediction)");
-  MI355_SHAPE_ARGS("dpmpp_cfg_step");
-  return step_form(true, eps, n, w, w_dev, per, shape,
-                   [=](auto es, auto rows) { return dpmpp_step_form(es, rows, x, hist, c_recip, c_recipm1, cx, c0, c1, n, s); });
+// The one launcher of the four predictor steps (PredictorStep, ops.h): every refusal once, prefixed by the name of the form asked for, then the host
+// side of the kind's coefficients, then the kernel template of the kind in the form step_form picks.
+int predictor_step_launch(const PredictorStep& p, hipStream_t s) {
+  static const char* const names[4][2] = {
+      {"ddpm_step", "ddpm_cfg_step"}, {"ddim_step", "ddim_cfg_step"}, {"ddim_eta_step", "ddim_eta_cfg_step"}, {"dpmpp_step", "dpmpp_cfg_step"}};
+  const bool cfg = p.guide.on;
+  const auto f = [&] { return std::string(names[p.kind][cfg]) + ": "; };   // built inside a refusal only: MI355_REQUIRE evaluates its message on failure
+  float* const x = p.x; const float* const eps = p.eps; const float* const z = p.z; float* const hist = p.hist;
+  const float* const w_dev = cfg ? p.guide.w_dev : nullptr; const float* const shape = p.shape;
+  const float c_recip = p.c_recip, c_recipm1 = p.c_recipm1, sigma = p.sigma, c1 = p.c;
+  const int use_philox = p.use_philox;
+  const uint64_t seed = p.seed, offset = p.offset;
+  const int64_t per = p.per, n = p.n;
+  const bool draws = p.kind == STEP_ANCESTRAL || p.kind == STEP_DDIM_ETA;   // the kinds with a noise term: the others never read the noise triple
+  if (draws) MI355_REQUIRE(offset % 4 == 0, -1, f() + "the Philox offset must be a multiple of 4");
+  MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, f() + "per-image scales need n to be whole images of elems_per_image elements");
+  MI355_REQUIRE(n <= 0 || (x && eps), -1, f() + "null argument");
+  if (p.kind == STEP_DDIM_ETA) MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, f() + "sigma must be finite and >= 0");
+  if (p.kind == STEP_DPMPP) MI355_REQUIRE(c1 == 0.f || hist || n <= 0, -1, f() + "c1 != 0 needs hist (the previous step's data prediction)");
+  MI355_REQUIRE(!shape || (per > 0 && n % per == 0), -1, f() + "per-image shaping rows need n to be whole images of elems_per_image elements");
+  const uint64_t off4 = offset / 4;
+  return step_form(cfg, eps, n, p.guide.w, w_dev, per, shape, [=](auto es, auto rows) {
+    switch (p.kind) {
+      case STEP_ANCESTRAL:
+        return ddpm_step_form(es, rows, x, z, c_recip, c_recipm1, p.a, p.b, sigma, use_philox, seed, off4, n, s);
+      case STEP_DDIM:
+        return ddim_step_form(es, rows, x, c_recip, c_recipm1, sqrtf(p.a), sqrtf(1.0f - p.a), n, s);
+      case STEP_DDIM_ETA: {
+        const DdimEta c = ddim_eta_coefs(p.a, sigma);
+        const int noisy = z != nullptr || use_philox;
+        return ddim_eta_step_form(es, rows, x, z, c_recip, c_recipm1, c.sa, c.sb, sigma, noisy, use_philox, seed, off4, n, s);
+      }
+      default:
+        return dpmpp_step_form(es, rows, x, hist, c_recip, c_recipm1, p.a, p.b, c1, n, s);
+    }
+  });
 }
 
 // ---- per-image statistics of a predictor step's data prediction (mi355_x0_shaping) -------------------------------------------------------------------
@@ -754,8 +697,9 @@ int check_x0_shaping(const char* who, const mi355_x0_shaping* sh, int guided) {
   return 0;
 }
 
-int x0_shape_stats_launch(const float* x, const float* eps, int guided, float w, const float* w_dev, float c_recip, float c_recipm1,
-                          const mi355_x0_shaping* sh, float* shape, float* detail, int batch, int64_t per, hipStream_t s) {
+int x0_shape_stats_launch(const float* x, const float* eps, const StepGuide& g, float c_recip, float c_recipm1, const mi355_x0_shaping* sh, float* shape,
+                          float* detail, int batch, int64_t per, hipStream_t s) {
+  const int guided = g.on;
   if (int rc = check_x0_shaping("x0_shape_stats", sh, guided)) return rc;
   MI355_REQUIRE(x, -1, "x0_shape_stats: x is null");
   MI355_REQUIRE(eps, -1, "x0_shape_stats: eps is null");
@@ -763,10 +707,10 @@ int x0_shape_stats_launch(const float* x, const float* eps, int guided, float w,
   MI355_REQUIRE(batch > 0, -1, "x0_shape_stats: batch must be > 0");
   MI355_REQUIRE(per > 0 && per <= ((int64_t)1 << 30), -1, "x0_shape_stats: elems_per_image must be in [1, 2^30]");
   X0StatsArgs a = {};
-  a.x = x; a.eps = eps; a.w_dev = guided ? w_dev : nullptr; a.shape = shape; a.detail = detail;
+  a.x = x; a.eps = eps; a.w_dev = guided ? g.w_dev : nullptr; a.shape = shape; a.detail = detail;
   a.n = (int64_t)batch * per; a.per = per;
-  a.w = w; a.c_recip = c_recip; a.c_recipm1 = c_recipm1;
-  a.guided = guided != 0;
+  a.w = g.w; a.c_recip = c_recip; a.c_recipm1 = c_recipm1;
+  a.guided = guided;
   const float q = sh ? sh->quantile : 0.f, phi = sh ? sh->rescale_phi : 0.f;
   a.phi = phi; a.one_minus_phi = 1.0f - phi;
   a.s_max = sh ? sh->max_threshold : 0.f;
@@ -783,24 +727,3 @@ int x0_shape_stats_launch(const float* x, const float* eps, int guided, float w,
   return 0;
 }
 
-// One shaped (or, shape == null, unshaped) predictor step chosen by number: the test layer's view of the eight forms above.
-int x0_shaped_step_launch(int kind, float* x, const float* eps, const float* z, float* hist, int guided, float w, const float* w_dev, int64_t per,
-                          float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed, uint64_t offset,
-                          const float* shape, int64_t n, hipStream_t s) {
-  MI355_REQUIRE(kind >= 0 && kind <= 3, -1, "x0_shaped_step: kind must be 0 (ancestral), 1 (DDIM), 2 (DDIM(eta)) or 3 (DPM-Solver++)");
-  MI355_REQUIRE(per > 0 && n % per == 0, -1, "x0_shaped_step: n must be whole images of elems_per_image elements");
-  switch (kind) {
-    case 0:
-      return guided ? ddpm_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, a, b, sigma, use_philox, seed, offset, n, s, shape)
-                    : ddpm_step_launch(x, eps, z, c_recip, c_recipm1, a, b, sigma, use_philox, seed, offset, n, s, shape, per);
-    case 1:
-      return guided ? ddim_cfg_step_launch(x, eps, w, w_dev, per, c_recip, c_recipm1, a, n, s, shape)
-                    : ddim_step_launch(x, eps, c_recip, c_recipm1, a, n, s, shape, per);
-    case 2:
-      return guided ? ddim_eta_cfg_step_launch(x, eps, z, w, w_dev, per, c_recip, c_recipm1, a, sigma, use_philox, seed, offset, n, s, shape)
-                    : ddim_eta_step_launch(x, eps, z, c_recip, c_recipm1, a, sigma, use_philox, seed, offset, n, s, shape, per);
-    default:
-      return guided ? dpmpp_cfg_step_launch(x, eps, hist, w, w_dev, per, c_recip, c_recipm1, a, b, c, n, s, shape)
-                    : dpmpp_step_launch(x, eps, hist, c_recip, c_recipm1, a, b, c, n, s, shape, per);
-  }
-}

@@ -622,47 +622,33 @@ class UNetEngine:
         guidance_scale (a float or a [B] tensor; None: mi355_ddpm_sample, untouched): classifier-free guidance of the predictor's eps
         (mi355_ddpm_cfg_sample; Amortized mode, or DDIM with a condition, on a 2C-input net), eps_u from the none_value-filled condition and, with
         y (class labels [B]), null_label (default: the last class).  A batch beyond cfg_batch() runs in slices (Philox: seed + slice index)."""
-        B, Cx = x.shape[:2]
+        B = x.shape[0]
         if cond is not None and cond.shape != x.shape:
             raise ValueError("condition must have the shape of x")
         if guidance_scale is None and y is not None:
             raise NotImplementedError("ddpm_sample takes class labels on the guided path only (guidance_scale=)")
         sched = self._ddpm_schedule(tables, timesteps, train_steps, ddim_sigma, walk)
+        if noise is not None and noise.shape[1:] != x.shape:
+            raise ValueError("injected noise must be [n_draws, B, C, H, W]")
         if guidance_scale is not None:
             if mode not in (_lib.DDPM_AMORTIZED, _lib.DDIM):
                 raise NotImplementedError("guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement are refused)")
             lab, _ = self._labels(y, B)
             w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
-            if noise is not None and noise.shape[1:] != x.shape:
-                raise ValueError("injected noise must be [n_draws, B, C, H, W]")
-            for i, (lo, hi, whole) in enumerate(_slices(B, self.cfg_batch())):
-                xs = x if whole else x[lo:hi].contiguous()
-                self._ddpm_cfg_call(xs, tables, mode, cond if whole or cond is None else cond[lo:hi].contiguous(),
-                                    _cut(lab, lo, hi), nl, w, _cut(wt, lo, hi),
-                                    noise if whole or noise is None else noise[:, lo:hi].contiguous(),
-                                    dict(n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, none_value=none_value, seed=(seed + i) % 2 ** 64),
+            for xs, cn, nz, ls, wl, sd in self._guided_slices(x, cond, noise, lab, wt, seed, self.cfg_batch()):
+                self._ddpm_cfg_call(xs, tables, mode, cn, ls, nl, w, wl, nz,
+                                    dict(n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, none_value=none_value, seed=sd),
                                     **({} if sched is None else {"sched": sched}))
-                if not whole:
-                    x[lo:hi] = xs
             return x
         tb, keep = self._ddpm_tables(tables)
+        self._fwd_state = None
         opt = _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value,
                                 int(cond is None), seed)
-        ndraws = 0
-        if noise is not None:
-            if noise.shape[1:] != x.shape:
-                raise ValueError("injected noise must be [n_draws, B, C, H, W]")
-            ndraws = noise.shape[0]
-        self._fwd_state = None
+        name = "mi355_ddpm_sample" if sched is None else "mi355_ddpm_sample_sched"
         ws, wsb = self.workspace(B)
-        if sched is not None:
-            check(self.L.mi355_ddpm_sample_sched(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                                 C.byref(tb), C.byref(opt), C.byref(sched[0]), self._chk(noise, "noise") if noise is not None else None,
-                                                 ndraws, B, ws, wsb, self._stream()), "mi355_ddpm_sample_sched")
-            return x
-        check(self.L.mi355_ddpm_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                       C.byref(tb), C.byref(opt), self._chk(noise, "noise") if noise is not None else None, ndraws, B,
-                                       ws, wsb, self._stream()), "mi355_ddpm_sample")
+        check(getattr(self.L, name)(self.handle, *self._ddpm_args(x, cond), C.byref(tb), C.byref(opt), *(() if sched is None else (C.byref(sched[0]),)),
+                                    *self._noise_args(noise), B, ws, wsb, self._stream()), name)
+        del keep
         return x
 
     def ddpm_multistep(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], coefs, *, cond: Optional[torch.Tensor] = None, none_value=-2.0,
@@ -672,7 +658,7 @@ class UNetEngine:
         for the same chain.  cond: None (prior; an amortized net sees none_value) or the condition of an amortized net.  timesteps / train_steps
         (both or neither): where the steps sit in training time (a RespacedDDPM's timesteps and base_Ns); None: steps 0..Ns-1 of Ns.
         guidance_scale, y, null_label: as in ddpm_sample.  A guided batch beyond cfg_batch() runs in slices."""
-        B, Cx = x.shape[:2]
+        B = x.shape[0]
         if cond is not None and cond.shape != x.shape:
             raise ValueError("condition must have the shape of x")
         if guidance_scale is None and y is not None:
@@ -690,32 +676,21 @@ class UNetEngine:
             raise ValueError("coefs must be the (cx, c0, c1) of DDPM.dpm_solver_coefs") from None
         if len(cs) != 3 or any(c.numel() != K for c in cs):
             raise ValueError("coefs must be (cx, c0, c1), one entry per step each")
-        fp = C.POINTER(C.c_float)
-        ms = _lib.MultistepScheduleC()
-        steps_arr = (C.c_int32 * max(1, K))(*steps)
-        ms.steps, ms.train_steps = C.cast(steps_arr, C.POINTER(C.c_int32)), K if train_steps is None else int(train_steps)
-        ms.cx, ms.c0, ms.c1 = (C.cast(c.data_ptr(), fp) for c in cs)
+        ms, keep_ms = self._multistep_schedule(tb, cs, steps, train_steps)
         opt = _lib.DDPMOptionsC(_lib.DDIM, 0, 0.1, 1e-5, 1.0, 1.0, 1, -2.0, float(none_value), int(cond is None), 0)
         self._fwd_state = None
         if guidance_scale is None:
             ws, wsb = self._workspace_sized("mi355_ddpm_multistep_workspace_bytes", B, 0)
-            check(self.L.mi355_ddpm_multistep_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                                     C.byref(tb), C.byref(opt), C.byref(ms), B, ws, wsb, self._stream()), "mi355_ddpm_multistep_sample")
+            check(self.L.mi355_ddpm_multistep_sample(self.handle, *self._ddpm_args(x, cond), C.byref(tb), C.byref(opt), C.byref(ms), B, ws, wsb,
+                                                     self._stream()), "mi355_ddpm_multistep_sample")
             return x
         lab, _ = self._labels(y, B)
         w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
-        for lo, hi, whole in _slices(B, self.cfg_batch()):
-            xs = x if whole else x[lo:hi].contiguous()
-            cn = cond if whole or cond is None else cond[lo:hi].contiguous()
-            ls, wl = _cut(lab, lo, hi), _cut(wt, lo, hi)
-            ws, wsb = self._workspace_sized("mi355_ddpm_multistep_workspace_bytes", hi - lo, 1)
-            check(self.L.mi355_ddpm_multistep_cfg_sample(self.handle, self._chk(xs, "x"), Cx, self._chk(cn, "condition") if cn is not None else None,
-                                                         C.c_void_p(ls.data_ptr()) if ls is not None else None, int(nl), float(w),
-                                                         self._chk(wl, "guidance_scale") if wl is not None else None, C.byref(tb), C.byref(opt),
-                                                         C.byref(ms), hi - lo, ws, wsb, self._stream()), "mi355_ddpm_multistep_cfg_sample")
-            if not whole:
-                x[lo:hi] = xs
-        del keep, steps_arr
+        for xs, cn, _, ls, wl, _ in self._guided_slices(x, cond, None, lab, wt, 0, self.cfg_batch()):
+            ws, wsb = self._workspace_sized("mi355_ddpm_multistep_workspace_bytes", xs.shape[0], 1)
+            check(self.L.mi355_ddpm_multistep_cfg_sample(self.handle, *self._ddpm_args(xs, cn, ls, nl, w, wl), C.byref(tb), C.byref(opt), C.byref(ms),
+                                                         xs.shape[0], ws, wsb, self._stream()), "mi355_ddpm_multistep_cfg_sample")
+        del keep, keep_ms
         return x
 
     def ddpm_shaped(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], shaping, *, mode: int, cond: Optional[torch.Tensor] = None,
@@ -726,7 +701,7 @@ class UNetEngine:
         thresholding and guidance rescale.  shaping: DDPM.x0_shaping, a (quantile, max_threshold, rescale_phi) triple, or None (the unshaped
         loop, bit for bit).  coefs None: the arguments and the loops of ddpm_sample; coefs = (cx, c0, c1): those of ddpm_multistep (mode must
         be DDIM; no noise).  guidance_scale not None: the guided loops; a batch beyond cfg_batch() runs in slices (Philox: seed + slice)."""
-        B, Cx = x.shape[:2]
+        B = x.shape[0]
         if cond is not None and cond.shape != x.shape:
             raise ValueError("condition must have the shape of x")
         if guidance_scale is None and y is not None:
@@ -744,12 +719,8 @@ class UNetEngine:
             cs = [torch.as_tensor(c, dtype=torch.float32).detach().to("cpu").contiguous() for c in coefs]
             if len(steps) != K or len(cs) != 3 or any(c.numel() != K for c in cs):
                 raise ValueError("timesteps and coefs = (cx, c0, c1) must have one entry per row of the tables")
-            fp = C.POINTER(C.c_float)
-            ms = _lib.MultistepScheduleC()
-            steps_arr = (C.c_int32 * max(1, K))(*steps)
-            ms.steps, ms.train_steps = C.cast(steps_arr, C.POINTER(C.c_int32)), K if train_steps is None else int(train_steps)
-            ms.cx, ms.c0, ms.c1 = (C.cast(c.data_ptr(), fp) for c in cs)
-            keep += cs + [steps_arr]
+            ms, keep_ms = self._multistep_schedule(tb, cs, steps, train_steps)
+            keep += keep_ms
         else:
             sched = self._ddpm_schedule(tables, timesteps, train_steps, ddim_sigma, walk)
         if noise is not None and noise.shape[1:] != x.shape:
@@ -762,24 +733,62 @@ class UNetEngine:
             w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
             mb = self.cfg_batch()
         self._fwd_state = None
-        for i, (lo, hi, whole) in enumerate(_slices(B, mb)):
-            xs = x if whole else x[lo:hi].contiguous()
-            cn = cond if whole or cond is None else cond[lo:hi].contiguous()
-            nz = noise if whole or noise is None else noise[:, lo:hi].contiguous()
-            ls, wl = _cut(lab, lo, hi), _cut(wt, lo, hi)
+        for xs, cn, nz, ls, wl, sd in self._guided_slices(x, cond, noise, lab, wt, int(seed), mb):
             opt = _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value,
-                                    int(cond is None), (int(seed) + i) % 2 ** 64)
-            ws, wsb = self._workspace_sized("mi355_ddpm_shaped_workspace_bytes", hi - lo, int(guided), int(ms is not None))
-            check(self.L.mi355_ddpm_shaped_sample(self.handle, self._chk(xs, "x"), Cx, self._chk(cn, "condition") if cn is not None else None,
-                                                  C.c_void_p(ls.data_ptr()) if ls is not None else None, int(nl), int(guided), float(w),
-                                                  self._chk(wl, "guidance_scale") if wl is not None else None, C.byref(tb), C.byref(opt),
+                                    int(cond is None), sd)
+            ws, wsb = self._workspace_sized("mi355_ddpm_shaped_workspace_bytes", xs.shape[0], int(guided), int(ms is not None))
+            a = self._ddpm_args(xs, cn, ls, nl, w, wl)
+            check(self.L.mi355_ddpm_shaped_sample(self.handle, *a[:5], int(guided), *a[5:], C.byref(tb), C.byref(opt),
                                                   C.byref(sched[0]) if sched is not None else None, C.byref(ms) if ms is not None else None,
-                                                  C.byref(sh) if sh is not None else None, self._chk(nz, "noise") if nz is not None else None,
-                                                  nz.shape[0] if nz is not None else 0, hi - lo, ws, wsb, self._stream()), "mi355_ddpm_shaped_sample")
-            if not whole:
-                x[lo:hi] = xs
+                                                  C.byref(sh) if sh is not None else None, *self._noise_args(nz), xs.shape[0], ws, wsb, self._stream()),
+                  "mi355_ddpm_shaped_sample")
         del keep
         return x
+
+    def _ddpm_cfg_call(self, x, tables, mode, cond, lab, null_label, w, wt, noise, o, sched=None):
+        """One mi355_ddpm_cfg_sample (sched: mi355_ddpm_cfg_sample_sched) call (a batch within cfg_batch())."""
+        B = x.shape[0]
+        tb, keep = self._ddpm_tables(tables)
+        opt = _lib.DDPMOptionsC(mode, o["n_corrector"], o["delta"], o["tmin"], o["tmax"], 1.0, 1, -2.0, o["none_value"], int(cond is None), o["seed"])
+        self._fwd_state = None
+        ws, wsb = self._workspace_sized("mi355_ddpm_cfg_workspace_bytes", B)
+        name = "mi355_ddpm_cfg_sample" if sched is None else "mi355_ddpm_cfg_sample_sched"
+        check(getattr(self.L, name)(self.handle, *self._ddpm_args(x, cond, lab, null_label, w, wt), C.byref(tb), C.byref(opt),
+                                    *(() if sched is None else (C.byref(sched[0]),)), *self._noise_args(noise), B, ws, wsb, self._stream()), name)
+        del keep
+
+    @staticmethod
+    def _guided_slices(x, cond, noise, lab, wt, seed, mb):
+        """The slices of one (guided) DDPM call run at most mb images at a time: yields the cut x, condition, injected noise, labels, per-image
+        scales and the slice's Philox seed (seed + slice index); a slice that is not the caller's batch itself is written back after its call."""
+        B = x.shape[0]
+        for i, (lo, hi, whole) in enumerate(_slices(B, mb)):
+            xs = x if whole else x[lo:hi].contiguous()
+            yield (xs, cond if whole or cond is None else cond[lo:hi].contiguous(), noise if whole or noise is None else noise[:, lo:hi].contiguous(),
+                   _cut(lab, lo, hi), _cut(wt, lo, hi), (seed + i) % 2 ** 64)
+            if not whole:
+                x[lo:hi] = xs
+
+    def _ddpm_args(self, x, cond, lab=None, null_label=None, w=None, wt=None):
+        """The pointer arguments every DDPM call starts with: x, Cx, cond; a guided call (w given) adds labels, null_label, w, w_dev."""
+        a = (self._chk(x, "x"), x.shape[1], self._chk(cond, "condition") if cond is not None else None)
+        if w is None:
+            return a
+        return a + (C.c_void_p(lab.data_ptr()) if lab is not None else None, int(null_label), float(w),
+                    self._chk(wt, "guidance_scale") if wt is not None else None)
+
+    def _noise_args(self, noise):
+        return (self._chk(noise, "noise") if noise is not None else None, noise.shape[0] if noise is not None else 0)
+
+    @staticmethod
+    def _multistep_schedule(tb, coefs, timesteps, train_steps):
+        """coefs: the (cx, c0, c1) CPU fp32 tensors, timesteps: the K training indices  =>  (mi355_multistep_schedule, what it points into)."""
+        K = int(tb.Ns)
+        ms = _lib.MultistepScheduleC()
+        steps_arr = (C.c_int32 * max(1, K))(*timesteps)
+        ms.steps, ms.train_steps = C.cast(steps_arr, C.POINTER(C.c_int32)), K if train_steps is None else int(train_steps)
+        ms.cx, ms.c0, ms.c1 = (C.cast(c.data_ptr(), C.POINTER(C.c_float)) for c in coefs)
+        return ms, list(coefs) + [steps_arr]
 
     @staticmethod
     def _ddpm_tables(tables):
@@ -830,25 +839,3 @@ class UNetEngine:
                 keep += [ra, rb]
                 sd.renoise_a, sd.renoise_b = C.cast(ra.data_ptr(), fp), C.cast(rb.data_ptr(), fp)
         return sd, keep
-
-    def _ddpm_cfg_call(self, x, tables, mode, cond, lab, null_label, w, wt, noise, o, sched=None):
-        """One mi355_ddpm_cfg_sample (sched: mi355_ddpm_cfg_sample_sched) call (a batch within cfg_batch())."""
-        B, Cx = x.shape[:2]
-        tb, keep = self._ddpm_tables(tables)
-        opt = _lib.DDPMOptionsC(mode, o["n_corrector"], o["delta"], o["tmin"], o["tmax"], 1.0, 1, -2.0, o["none_value"], int(cond is None), o["seed"])
-        self._fwd_state = None
-        ws, wsb = self._workspace_sized("mi355_ddpm_cfg_workspace_bytes", B)
-        if sched is not None:
-            check(self.L.mi355_ddpm_cfg_sample_sched(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                                     C.c_void_p(lab.data_ptr()) if lab is not None else None, int(null_label), float(w),
-                                                     self._chk(wt, "guidance_scale") if wt is not None else None, C.byref(tb), C.byref(opt),
-                                                     C.byref(sched[0]), self._chk(noise, "noise") if noise is not None else None,
-                                                     noise.shape[0] if noise is not None else 0, B, ws, wsb, self._stream()),
-                  "mi355_ddpm_cfg_sample_sched")
-            return
-        check(self.L.mi355_ddpm_cfg_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                           C.c_void_p(lab.data_ptr()) if lab is not None else None, int(null_label), float(w),
-                                           self._chk(wt, "guidance_scale") if wt is not None else None, C.byref(tb), C.byref(opt),
-                                           self._chk(noise, "noise") if noise is not None else None, noise.shape[0] if noise is not None else 0, B,
-                                           ws, wsb, self._stream()), "mi355_ddpm_cfg_sample")
-        del keep

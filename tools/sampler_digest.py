@@ -1,5 +1,5 @@
 """Digest of every sampler loop of libmi355_sampler.so on a tiny net with seeded inputs: one line per output tensor with its SHA-256, the
-launch count mi355_unet_get_stats reports after the call, and the values of the four workspace size functions.
+launch count mi355_unet_get_stats reports after the call, and the values of the workspace size functions.
 
 The forward is bitwise reproducible (reductions run in a fixed order), so two builds of the library whose host code issues the same launches
 with the same arguments print the same lines.  Run it once per library, each run in its own process:
@@ -78,6 +78,16 @@ def sizes(prec, tag, eng):
         for st in (1, 2, 3, 4):
             emit(f"{prec} bytes {tag} cfm_rk_workspace batch={b} stages={st} {L.mi355_cfm_rk_workspace_bytes(eng.handle, b, st)}")
             emit(f"{prec} bytes {tag} cfg_workspace batch={b} stages={st} {L.mi355_cfg_workspace_bytes(eng.handle, b, st)}")
+        for g in (0, 1):
+            emit(f"{prec} bytes {tag} ddpm_multistep_workspace batch={b} guided={g} {L.mi355_ddpm_multistep_workspace_bytes(eng.handle, b, g)}")
+            for ms in (0, 1):
+                emit(f"{prec} bytes {tag} ddpm_shaped_workspace batch={b} guided={g} multistep={ms} {L.mi355_ddpm_shaped_workspace_bytes(eng.handle, b, g, ms)}")
+            for order in (2, 3, 4):
+                for st in (1, 2, 4):
+                    emit(f"{prec} bytes {tag} cfm_ab_workspace batch={b} order={order} start_stages={st} guided={g} "
+                         f"{L.mi355_cfm_ab_workspace_bytes(eng.handle, b, order, st, g)}")
+        for hl in (0, 4):
+            emit(f"{prec} bytes {tag} cfm_recon_workspace batch={b} low={hl} {L.mi355_cfm_recon_workspace_bytes(eng.handle, b, hl, hl)}")
 
 
 def span(n):
@@ -166,6 +176,61 @@ def run(prec):
     case(prec, "ddpm_cfg_labels_cond_per_eval", l6,
          {"x": l6.ddpm_sample(xT.clone(), big_l.host_tables(), mode=_lib.DDPM_AMORTIZED, cond=cond, guidance_scale=2.0, y=y4, null_label=3,
                               tmin=big_l.tmin, tmax=big_l.tmax, seed=1234)})
+
+    # ---- the DDPM loops on a sub-sequence of the steps: respacing, DDIM(eta), a RePaint walk, DPM-Solver++, per-image shaping ----
+    from image_diffusion.conditioning import repaint_walk
+    r = ddpm.respace(8)
+    R = r.host_tables()
+    sched = dict(timesteps=r.timesteps, train_steps=r.base_Ns)
+    rkw = dict(tmin=r.tmin, tmax=r.tmax, seed=1234)
+    coefs = r.dpm_solver_coefs(2)
+    walk = repaint_walk(r.Ns, 2, 2)
+    assert any(b > a for a, b in zip(walk, walk[1:]))
+    shaping = (0.9, 0.0, 0.7)   # quantile, no cap, rescale_phi (guided calls only: the rescale compares the guided eps with the conditional one)
+    case(prec, "ddpm_respaced_prior", u3, {"x": u3.ddpm_sample(xT.clone(), R, mode=_lib.DDPM_PRIOR, noise=draws, **sched, **rkw)})
+    case(prec, "ddpm_respaced_amortized_corr1", u6, {"x": u6.ddpm_sample(xT.clone(), R, mode=_lib.DDPM_AMORTIZED, cond=cond, n_corrector=1, **sched, **rkw)})
+    for nname, noise in (("injected", draws), ("philox", None)):
+        case(prec, f"ddpm_ddim_eta_{nname}", u6,
+             {"x": u6.ddpm_sample(xT.clone(), R, mode=_lib.DDIM, cond=cond, noise=noise, ddim_sigma=r.ddim_sigma(0.5), **sched, **rkw)})
+        case(prec, f"ddpm_cfg_ddim_eta_{nname}", u6,
+             {"x": u6.ddpm_sample(xT.clone(), R, mode=_lib.DDIM, cond=cond, noise=noise, ddim_sigma=r.ddim_sigma(0.5), guidance_scale=wv, **sched, **rkw)})
+    case(prec, "ddpm_repaint_walk", u3,
+         {"x": u3.ddpm_sample(xT.clone(), R, mode=_lib.DDPM_REPLACEMENT, cond=cond, noise=draws, start_fraction=0.8, walk=walk, **sched, **rkw)})
+    case(prec, "dpmpp_plain", u3, {"x": u3.ddpm_multistep(xT.clone(), R, coefs, **sched)})
+    case(prec, "dpmpp_unscheduled", u3, {"x": u3.ddpm_multistep(xT.clone(), T, ddpm.dpm_solver_coefs(2))})
+    case(prec, "dpmpp_guided_labels_cond", l6, {"x": l6.ddpm_multistep(xT.clone(), R, coefs, cond=cond, guidance_scale=2.0, y=y4, null_label=3, **sched)})
+    for gname, eng, gkw, sh in (("plain", u3, {}, (0.9, 0.0, 0.0)), ("guided", u6, dict(cond=cond, guidance_scale=wv), shaping)):
+        mode = _lib.DDIM if gkw else _lib.DDPM_PRIOR
+        case(prec, f"shaped_{gname}_scheduled", eng,
+             {"x": eng.ddpm_shaped(xT.clone(), R, sh, mode=mode, noise=draws, ddim_sigma=r.ddim_sigma(0.5) if gkw else None, **gkw, **sched, **rkw)})
+        case(prec, f"shaped_{gname}_multistep", eng, {"x": eng.ddpm_shaped(xT.clone(), R, sh, mode=_lib.DDIM, coefs=coefs, **gkw, **sched)})
+        case(prec, f"shaped_{gname}_none", eng, {"x": eng.ddpm_shaped(xT.clone(), R, None, mode=mode, noise=draws, **gkw, **sched, **rkw)})
+    case(prec, "shaped_guided_amortized_corr1", u6,
+         {"x": u6.ddpm_shaped(xT.clone(), T, shaping, mode=_lib.DDPM_AMORTIZED, cond=cond, n_corrector=1, guidance_scale=2.0, **kw, seed=1234)})
+    case(prec, "ddpm_cfg_sliced_at_cfg_batch", u6,   # max_batch 4: cfg_batch() = 2, slices of 2 + 1 images
+         {"x": sliced(u6, 4, lambda: u6.ddpm_sample(xT.clone(), R, mode=_lib.DDIM, cond=cond, guidance_scale=wv, ddim_sigma=r.ddim_sigma(0.5), **sched, **rkw))})
+    case(prec, "shaped_guided_sliced", u6,
+         {"x": sliced(u6, 4, lambda: u6.ddpm_shaped(xT.clone(), R, shaping, mode=_lib.DDIM, coefs=coefs, cond=cond, guidance_scale=wv, **sched))})
+
+    # ---- Adams-Bashforth: a span that stays inside the start method (2 steps at order 3), and one that leaves it ----
+    for n_steps in (2, 5):
+        case(prec, f"ab3_plain_{n_steps}", u3, dict(zip(xtu, u3.cfm_ab(x0.clone(), span(n_steps), "ab3", keep_traj=True, want_u8=True))))
+        case(prec, f"ab3_guided_{n_steps}", l6,
+             dict(zip(xtu, l6.cfm_ab(x0.clone(), span(n_steps), "ab3", cond=cond, keep_traj=True, want_u8=True, y=y4, guidance_scale=wv, null_label=3))))
+    case(prec, "ab2_one_time", u3, dict(zip(xtu, u3.cfm_ab(x0.clone(), [0.5], "ab2", keep_traj=True, want_u8=True))))
+
+    # ---- training-free reconstruction: painting with replacement; low resolution with guidance and its loss ----
+    xtul = ("x", "traj", "u8", "loss")
+    case(prec, "recon_mode0_coupled", u3, dict(zip(xtul, u3.cfm_recon(x0.clone(), span(3), cond, 0, replace="coupled", final_paste=True, keep_traj=True, want_u8=True))))
+    case(prec, "recon_mode0_fresh_philox", u3, dict(zip(xtul, u3.cfm_recon(x0.clone(), span(3), cond, 0, replace="fresh", seed=99, want_u8=True))))
+    if prec == "fp32":   # (the differentiable plan is digested in fp32 only, as in run_forward)
+        d3 = UNetModel(image_size=S, in_channels=3, model_channels=32, out_channels=3, num_res_blocks=1, attention_resolutions=(2,), channel_mult=(1, 2),
+                       num_heads=2, precision=prec)
+        d3.load_state_dict(synth_state_dict(param_shapes(d3), 7005))
+        d3 = d3.to(DEV).engine(DEV, differentiable=True)
+        ylow = (randn(7103, B, 3, 4, 4) * 0.5).to(DEV)
+        case(prec, "recon_mode2_loss", d3, dict(zip(xtul, d3.cfm_recon(x0.clone(), span(3), ylow, 2, scales=[0.5, 0.0, 0.25], keep_traj=True, want_u8=True,
+                                                                        return_loss=True))))
 
     # ---- SF2M Euler-Maruyama: two nets, two output times inside step 1 ----
     grid = span(3)
