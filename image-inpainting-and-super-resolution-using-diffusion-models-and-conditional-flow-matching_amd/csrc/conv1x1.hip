@@ -5,7 +5,8 @@
 // channel chunks once (GroupNorm prologue applied once, not once per output-channel tile), keeps it in LDS, and
 // then walks the output-channel tiles of its N range streaming only weights (register-prefetched, double-buffered
 // in LDS, one barrier per 3-chunk group).  Epilogue straight from the accumulators (rows = channels, cols = pixels).
-#include "ops.h"
+#include "conv_kargs.h"
+#include "conv_epilogue.h"
 
 namespace {
 
@@ -221,24 +222,15 @@ __global__ void __launch_bounds__(NT1, 2) conv1x1_kernel(K1Args p) {
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni) {
             f32x4 o = f32x4{acc[mi][ni][0] + ad[ni][0], acc[mi][ni][1] + ad[ni][1], acc[mi][ni][2] + ad[ni][2], acc[mi][ni][3] + ad[ni][3]};
-            if (p.res) { const f32x4 t = __builtin_bit_cast(f32x4, rr[mi][ni]); o = f32x4{o[0] + t[0], o[1] + t[1], o[2] + t[2], o[3] + t[3]}; }
+            if (p.res) o = epi_quad_res<true>(o, rr[mi][ni]);
             if (do_gn) gp.add(ni, o[0], o[1], o[2], o[3], gn_mask, ovalid[mi] ? 1.f : 0.f);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rso, obase + ni * 16 * ESZ, 0, 0);
+            epi_quad_store(o, rso, obase + ni * 16 * ESZ);
           }
         } else {
 #pragma unroll
           for (int k = 0; k < NP2; ++k) {
             float ra[4] = {0.f, 0.f, 0.f, 0.f}, rb[4] = {0.f, 0.f, 0.f, 0.f};
-            if (p.res) {
-              const auto s0 = __builtin_amdgcn_permlane16_swap(rr[mi][k][0], rr[mi][k][2], false, false);
-              const auto s1 = __builtin_amdgcn_permlane16_swap(rr[mi][k][1], rr[mi][k][3], false, false);
-              const uint32_t xa[2] = {s0[0], s1[0]}, xb[2] = {s0[1], s1[1]};
-#pragma unroll
-              for (int j = 0; j < 2; ++j) {
-                unpack2(xa[j], ra[2 * j], ra[2 * j + 1], T());
-                unpack2(xb[j], rb[2 * j], rb[2 * j + 1], T());
-              }
-            }
+            if (p.res) epi_pair_unswap(rr[mi][k], ra, rb, T());
             float va[4], vb[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -250,10 +242,7 @@ __global__ void __launch_bounds__(NT1, 2) conv1x1_kernel(K1Args p) {
               gp.add(2 * k, va[0], va[1], va[2], va[3], gn_mask, vm);
               gp.add(2 * k + 1, vb[0], vb[1], vb[2], vb[3], gn_mask, vm);
             }
-            const u32x2 pa2 = pack4(va, T()), pb2 = pack4(vb, T());
-            const auto w0 = __builtin_amdgcn_permlane16_swap(pa2[0], pb2[0], false, false);
-            const auto w1 = __builtin_amdgcn_permlane16_swap(pa2[1], pb2[1], false, false);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{w0[0], w1[0], w0[1], w1[1]}, rso, obase + k * PSTEP * ESZ, 0, 0);
+            epi_pair_store(va, vb, rso, obase + k * PSTEP * ESZ, T());
           }
         }
       }

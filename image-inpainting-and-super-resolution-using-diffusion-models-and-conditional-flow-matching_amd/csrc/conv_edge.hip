@@ -13,7 +13,8 @@
 //     the patch (16-byte slots XOR-swizzled by the pixel's column: conflict-free for every tap, row shifts are plain offsets), B fragments
 //     from the first rows of the packed weight tiles, copied once into LDS;
 //   * lanes 0-15 of every wave hold the real output channels of 16 consecutive pixels: 64-byte NCHW fp32 segments, bias added in flight.
-#include "ops.h"
+#include "conv_kargs.h"
+#include "conv_epilogue.h"
 
 namespace {
 
@@ -317,10 +318,7 @@ __global__ void __launch_bounds__(256, 4) conv3x3_in_kernel(InArgs p) {
           gs[2 * k + 1] += (vb[0] + vb[1]) + (vb[2] + vb[3]);
           gq[2 * k + 1] = __builtin_fmaf(vb[0], vb[0], __builtin_fmaf(vb[1], vb[1], __builtin_fmaf(vb[2], vb[2], __builtin_fmaf(vb[3], vb[3], gq[2 * k + 1]))));
         }
-        const u32x2 pa2 = pack4(va, T()), pb2 = pack4(vb, T());
-        const auto w0 = __builtin_amdgcn_permlane16_swap(pa2[0], pb2[0], false, false);
-        const auto w1 = __builtin_amdgcn_permlane16_swap(pa2[1], pb2[1], false, false);
-        *reinterpret_cast<u32x4*>(op + k * 64) = u32x4{w0[0], w1[0], w0[1], w1[1]};
+        *reinterpret_cast<u32x4*>(op + k * 64) = epi_pair_pack(va, vb, T());   // (a plain pointer store: this kernel has no buffer descriptor)
       }
     }
   }

@@ -19,6 +19,7 @@
 //     tiles are double-buffered in LDS, so there is one barrier per kernel row (48 MFMAs per wave).
 // 4 waves per workgroup, v_mfma_f32_16x16x32_bf16 (or v_mfma_f32_16x16x4_f32 in the fp32 build).
 #include "conv_kargs.h"
+#include "conv_epilogue.h"
 
 namespace {
 
@@ -413,27 +414,15 @@ __global__ void __launch_bounds__(64 * WM * WN, WM * WN / 2) conv_igemm_kernel(C
         for (int ni = 0; ni < NI; ++ni) {
           const f32x4 ad = add4[MULTI ? mi : 0][ni];
           f32x4 o = f32x4{acc[mi][ni][0] + ad[0], acc[mi][ni][1] + ad[1], acc[mi][ni][2] + ad[2], acc[mi][ni][3] + ad[3]};
-          if (p.res_mode != RES_NONE) {
-            const f32x4 t = __builtin_bit_cast(f32x4, rr[mi][ni]);
-            o = f32x4{o[0] + t[0], o[1] + t[1], o[2] + t[2], o[3] + t[3]};
-          }
+          if (p.res_mode != RES_NONE) o = epi_quad_res<true>(o, rr[mi][ni]);
           if (do_gn) gp.add(ni, o[0], o[1], o[2], o[3], gn_mask, pvalid[mi] ? 1.f : 0.f);
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rso, ovo[mi] + ni * 16 * ESZ, 0, 0);
+          epi_quad_store(o, rso, ovo[mi] + ni * 16 * ESZ);
         }
       } else {
 #pragma unroll
         for (int k = 0; k < NP2; ++k) {
           float ra[4] = {0.f, 0.f, 0.f, 0.f}, rb[4] = {0.f, 0.f, 0.f, 0.f};
-          if (p.res_mode != RES_NONE) {   // un-swap the 8-channel residual piece back to the accumulator layout
-            const auto s0 = __builtin_amdgcn_permlane16_swap(rr[mi][k][0], rr[mi][k][2], false, false);
-            const auto s1 = __builtin_amdgcn_permlane16_swap(rr[mi][k][1], rr[mi][k][3], false, false);
-            const uint32_t xa[2] = {s0[0], s1[0]}, xb[2] = {s0[1], s1[1]};
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              unpack2(xa[j], ra[2 * j], ra[2 * j + 1], T());
-              unpack2(xb[j], rb[2 * j], rb[2 * j + 1], T());
-            }
-          }
+          if (p.res_mode != RES_NONE) epi_pair_unswap(rr[mi][k], ra, rb, T());
           const f32x4 ada = add4[MULTI ? mi : 0][2 * k], adb = add4[MULTI ? mi : 0][2 * k + 1];
           float va[4], vb[4];
 #pragma unroll
@@ -446,10 +435,7 @@ __global__ void __launch_bounds__(64 * WM * WN, WM * WN / 2) conv_igemm_kernel(C
             gp.add(2 * k, va[0], va[1], va[2], va[3], gn_mask, vm);
             gp.add(2 * k + 1, vb[0], vb[1], vb[2], vb[3], gn_mask, vm);
           }
-          const u32x2 pa2 = pack4(va, T()), pb2 = pack4(vb, T());
-          const auto w0 = __builtin_amdgcn_permlane16_swap(pa2[0], pb2[0], false, false);
-          const auto w1 = __builtin_amdgcn_permlane16_swap(pa2[1], pb2[1], false, false);
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{w0[0], w1[0], w0[1], w1[1]}, rso, ovo[mi] + k * PSTEP * ESZ, 0, 0);
+          epi_pair_store(va, vb, rso, ovo[mi] + k * PSTEP * ESZ, T());
         }
       }
     }

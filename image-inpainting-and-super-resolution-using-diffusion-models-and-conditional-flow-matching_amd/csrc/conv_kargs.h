@@ -104,3 +104,9 @@ struct ConvPre {
 };
 
 int ws_num_cus();   // CUs of the current device (256 where there is none): the persistent kernels' grid and the "every CU gets a tile" rules
+// grid of a persistent kernel that walks n_mt pixel tiles x n_nt channel tiles (the host half of TileWalk, conv_epilogue.h): one workgroup per CU,
+// fewer where the walk has fewer items
+inline int persistent_grid(int n_mt, int n_nt) {
+  const int ntp = ((n_mt + 7) / 8) * 8 * n_nt, ncu = ws_num_cus();
+  return ntp < ncu ? ntp : ncu;
+}

@@ -1,5 +1,6 @@
 // The ping-pong persistent 3x3 conv as a unit of its own: the kernel and its launchers (conv_pp.inc.h) and the family's route / launch (ops.h).
 #include "conv_kargs.h"
+#include "conv_epilogue.h"
 
 #ifndef PP_IMPL   // experiments: make variant VARFLAGS='-DPP_IMPL="\"../../tools/experiments/<file>\""' VARTAG=_x builds a library around another version of the kernel
 #define PP_IMPL "conv_pp.inc.h"

@@ -218,17 +218,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
   const int tpi = p.tiles_x * p.tiles_y;
   const int T9 = p.nchunks * TAPS;            // taps per tile (a multiple of 2 TAPS: the launcher requires an even chunk count)
   const int npt = p.N * tpi;                  // UP: pixel tiles per phase (tiles_x / tiles_y tile the LOW-RES image)
-  // Tile walk (as conv3x3_ws_kernel): 8 consecutive workgroups (one per XCD) take 8 consecutive pixel tiles, the workgroup 8 further on
-  // (same XCD, same L2) the next channel tile of the same pixels.
-  const int ntp = ((n_mt + 7) / 8) * 8 * n_nt;
-  auto decode = [&](int t, int& mt, int& nt) {
-    const int per = 8 * n_nt, blk = t / per, r = t - blk * per;
-    nt = r >> 3; mt = blk * 8 + (r & 7);
-  };
-  auto next_valid = [&](int t) {
-    for (t += gridDim.x; t < ntp; t += gridDim.x) { int mt, nt; decode(t, mt, nt); if (mt < n_mt) break; }
-    return t;
-  };
+  const TileWalk walk(n_mt, n_nt, gridDim.x, blockIdx.x);   // conv_epilogue.h
+  const int ntp = walk.ntp;
   auto origin = [&](int mt, int& n0, int& y0, int& x0, int& ph) {
     ph = UP ? mt / npt : 0;
     if constexpr (UP != 0) mt -= ph * npt;
@@ -236,8 +227,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
     const int tyi = rem / p.tiles_x, txi = rem - tyi * p.tiles_x;
     n0 = ng; y0 = tyi * TH; x0 = txi * VW;
   };
-  int t_first = (int)blockIdx.x - (int)gridDim.x;
-  t_first = next_valid(t_first);
+  const int t_first = walk.first();
   if (t_first >= ntp) return;                 // the whole workgroup leaves together
 
   const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.src0), 0, p.bytes0, 0x00020000);
@@ -255,7 +245,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
   // moves half g.  Narrow: one 128-row tile, 8 pieces, wave w moves piece w.  Piece j lands at ring slot + 1024 j: row r at 64 r.
   // UP: [nt128][phase][chunk][tap 0..3][128 rows][64 B] (conv_pack_weights_up2): the stream of a (phase, channel) tile is linear as well
   auto ws_base = [&](int t) {
-    int mt, nt; decode(t, mt, nt);
+    int mt, nt; walk.decode(t, mt, nt);
     const int t128 = CFG == 0 ? 2 * nt + grp : nt;
     return (uint32_t)((UP ? 4 * t128 + mt / npt : t128) * T9) * 8192u;
   };
@@ -289,7 +279,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
     asm volatile("" : "+s"(t));
     int mt, nt, n0, y0, x0, ph;
-    decode(t, mt, nt);
+    walk.decode(t, mt, nt);
     origin(mt, n0, y0, x0, ph);
     const int cy0 = y0 - 1 + (ph >> 1), cx0 = x0 - 1 + (ph & 1);   // (UP: low-res coordinates, shifted by the phase)
     const int Hb = UP ? p.Hs : p.Hc, Wb = UP ? p.Ws : p.Wc;
@@ -394,23 +384,12 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
   f32x4 cin[NI];                           // bias + timestep embedding of this lane's channels: the accumulators start from it
   auto cinit_load = [&](int t) {
     int mt, nt, n0, y0, x0, ph;
-    decode(t, mt, nt);
+    walk.decode(t, mt, nt);
     origin(mt, n0, y0, x0, ph);
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-      const int co = nt * BN + wn * 64 + ni * 16 + 4 * lq;   // Cout % BN == 0: always in range
-      f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (p.bias) v = *reinterpret_cast<const f32x4*>(p.bias + co);
-      if (p.emb) { const f32x4 e = *reinterpret_cast<const f32x4*>(p.emb + (size_t)n0 * p.emb_stride + co); v = f32x4{v[0] + e[0], v[1] + e[1], v[2] + e[2], v[3] + e[3]}; }
-      cin[ni] = v;
-    }
+    for (int ni = 0; ni < NI; ++ni) cin[ni] = epi_cinit_quad(p, nt * BN + wn * 64 + ni * 16 + 4 * lq, n0);
   };
-  auto acc_init = [&]() {
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = cin[ni];
-  };
+  auto acc_init = [&]() { epi_acc_init(acc, cin); };
 
   constexpr int abl = PP_ABLATE;   // timing experiments, compile-time (make variant PPABL=<mask>; results become wrong): 4 no MFMA, 8 no weight DMA, 16 no patch DMA, 128 no fragment reads, 256 no prologue math
   STAMP_DECL
@@ -442,10 +421,10 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
   int extra = 0;
 
   for (int t = t_first; t < ntp;) {
-    const int t_next = next_valid(t);
+    const int t_next = walk.next_valid(t);
     const int t_nextc = t_next < ntp ? t_next : t;   // the streams' next tile (clamped at the end of the walk)
     int mt, nt, n0, y0, x0, ph;
-    decode(t, mt, nt);
+    walk.decode(t, mt, nt);
     origin(mt, n0, y0, x0, ph);
     if (grp == 1) pp_barrier();            // one tick behind group 0
     STAMP(7)
@@ -551,8 +530,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
       }
     }
 
-    // ---------------- epilogue (as conv3x3_ws_kernel: MFMA rows are channels, columns are pixels; lane (lr, lq) holds 4 consecutive
-    // channels of pixel lr per 16 x 16 tile; bf16 pairs of channel tiles merge into 16-byte stores by two v_permlane16_swap) ----------------
+    // ---------------- epilogue (layout and the pair primitives: conv_epilogue.h; the row loop is the same text in conv_ws.inc.h and stays
+    // written out: see the header why; conv_pp1.inc.h has the same loop with its own un-swap / pack / store, NOT on the primitives) ----------------
     cinit_load(t_nextc);                     // the next tile's start values travel while this tile is stored
     const int co_w = nt * BN + wn * 64 + 4 * lq;
     const int co_s = PAIR ? nt * BN + wn * 64 + (lq & 1) * 16 + (lq >> 1) * 8 : co_w;
@@ -602,16 +581,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
 #pragma unroll
           for (int k = 0; k < NP2; ++k) {
             float ra[4] = {0.f, 0.f, 0.f, 0.f}, rb[4] = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (HAS_RES) {   // un-swap the 8-channel residual piece back to the accumulator layout
-              const auto s0 = __builtin_amdgcn_permlane16_swap(rr[j][k][0], rr[j][k][2], false, false);
-              const auto s1 = __builtin_amdgcn_permlane16_swap(rr[j][k][1], rr[j][k][3], false, false);
-              const uint32_t xa[2] = {s0[0], s1[0]}, xb[2] = {s0[1], s1[1]};
-#pragma unroll
-              for (int q = 0; q < 2; ++q) {
-                unpack2(xa[q], ra[2 * q], ra[2 * q + 1], T());
-                unpack2(xb[q], rb[2 * q], rb[2 * q + 1], T());
-              }
-            }
+            if constexpr (HAS_RES) epi_pair_unswap(rr[j][k], ra, rb, T());   // back to the accumulator layout
             float va[4], vb[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -622,10 +592,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
               gp.add(2 * k, va[0], va[1], va[2], va[3], GNM == 2, vm[j]);
               gp.add(2 * k + 1, vb[0], vb[1], vb[2], vb[3], GNM == 2, vm[j]);
             }
-            const u32x2 pa2 = pack4(va, T()), pb2 = pack4(vb, T());
-            const auto w0 = __builtin_amdgcn_permlane16_swap(pa2[0], pb2[0], false, false);
-            const auto w1 = __builtin_amdgcn_permlane16_swap(pa2[1], pb2[1], false, false);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{w0[0], w1[0], w0[1], w1[1]}, rso, ovo[j] + k * PSTEP * ESZ, 0, 0);
+            epi_pair_store(va, vb, rso, ovo[j] + k * PSTEP * ESZ, T());
           }
         }
       }
@@ -700,7 +667,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
             f32x4 o;
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = actv(ga[ni][j] * acc[mi][ni][j] + gb[ni][j]);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rso, ovo + ni * 16 * ESZ, 0, 0);
+            epi_quad_store(o, rso, ovo + ni * 16 * ESZ);
           }
         } else {
 #pragma unroll
@@ -711,10 +678,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pp_kernel(ConvKArgs p, int n_m
               va[q] = actv(ga[2 * k][q] * acc[mi][2 * k][q] + gb[2 * k][q]);
               vb[q] = actv(ga[2 * k + 1][q] * acc[mi][2 * k + 1][q] + gb[2 * k + 1][q]);
             }
-            const u32x2 pa2 = pack4(va, T()), pb2 = pack4(vb, T());
-            const auto w0 = __builtin_amdgcn_permlane16_swap(pa2[0], pb2[0], false, false);
-            const auto w1 = __builtin_amdgcn_permlane16_swap(pa2[1], pb2[1], false, false);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{w0[0], w1[0], w0[1], w1[1]}, rso, ovo + k * PSTEP * ESZ, 0, 0);
+            epi_pair_store(va, vb, rso, ovo + k * PSTEP * ESZ, T());
           }
         }
       }
@@ -752,8 +716,7 @@ int launch_pp_k(ConvKArgs a, hipStream_t s) {
   a.tiles_x = (Wt + Dg::VW - 1) / Dg::VW; a.tiles_y = (Ht + Dg::TH - 1) / Dg::TH;
   const int n_mt = (UP ? 4 : 1) * a.N * a.tiles_x * a.tiles_y, n_nt = a.Cout / Dg::BN;
   if (int rc = mi355_allow_big_lds(conv3x3_pp_kernel<T, CFG, PRO, ACT, UP>, "conv3x3 (ping-pong)")) return rc;
-  const int ntp = ((n_mt + 7) / 8) * 8 * n_nt, ncu = ws_num_cus();
-  const int grid = ntp < ncu ? ntp : ncu;   // one persistent workgroup per CU
+  const int grid = persistent_grid(n_mt, n_nt);
   hipLaunchKernelGGL((conv3x3_pp_kernel<T, CFG, PRO, ACT, UP>), dim3(grid), dim3(512), Dg::lds_bytes(PRO, ACT) + PP_TRACE_BYTES, s, a, n_mt, n_nt);
   return 0;
 }

@@ -1,6 +1,7 @@
 // The ping-pong 1x1 conv as a unit of its own: the kernel (conv_pp1.inc.h, on the wait / barrier helpers of conv_pp.inc.h, whose kernel is not instantiated
 // here) and the family's route / launch (ops.h).
 #include "conv_kargs.h"
+#include "conv_epilogue.h"
 
 namespace {
 #include "conv_pp.inc.h"

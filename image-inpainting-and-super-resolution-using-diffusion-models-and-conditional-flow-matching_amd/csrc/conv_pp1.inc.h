@@ -48,7 +48,9 @@ __global__ void __launch_bounds__(512, 2) conv1x1_pp_kernel(ConvKArgs p, int n_m
   const int TT = p.nchunks;                   // steps per tile (a multiple of 4: the launcher)
   const int HW = p.Ho * p.Wo;                 // a multiple of 256 (the launcher): a tile never straddles two images
   // Tile walk: 8 consecutive workgroups (one per XCD) take 8 consecutive pixel tiles, the workgroup 8 further on (same XCD, same L2) the
-  // next 256-channel tile of the same pixels.
+  // next 256-channel tile of the same pixels.  (This kernel keeps its own copy of TileWalk, of the start values and of the pair epilogue of
+  // conv_epilogue.h: on the shared forms it spilled more SGPRs or VGPRs and its launches ran 1-2 % slower, profiles/conv_epilogue_parity.md.  A change
+  // to any of the three in the header has to be made here as well.)
   const int ntp = ((n_mt + 7) / 8) * 8 * n_nt;
   auto decode = [&](int t, int& mt, int& nt) {
     const int per = 8 * n_nt, blk = t / per, r = t - blk * per;
@@ -290,8 +292,7 @@ __global__ void __launch_bounds__(512, 2) conv1x1_pp_kernel(ConvKArgs p, int n_m
 template <typename T, int WIDE>
 static int pp1_launch_k(const ConvKArgs& a, int n_mt, int n_nt, hipStream_t stream) {
   if (int rc = mi355_allow_big_lds(conv1x1_pp_kernel<T, WIDE>, "conv1x1 (ping-pong)")) return rc;
-  const int ntp = ((n_mt + 7) / 8) * 8 * n_nt, ncu = ws_num_cus();
-  const int grid = ntp < ncu ? ntp : ncu;   // one persistent workgroup per CU
+  const int grid = persistent_grid(n_mt, n_nt);
   hipLaunchKernelGGL((conv1x1_pp_kernel<T, WIDE>), dim3(grid), dim3(512), pp1::Cfg<WIDE>::LDS_BYTES, stream, a, n_mt, n_nt);
   return 0;
 }

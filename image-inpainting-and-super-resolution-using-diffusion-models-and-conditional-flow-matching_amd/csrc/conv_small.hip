@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "conv_kargs.h"
+#include "conv_epilogue.h"
 
 namespace {
 #include "conv_small.inc.h"

@@ -297,7 +297,7 @@ __global__ void __launch_bounds__(NI == 4 ? 256 : 512, NI == 4 ? 1 : 2) conv3x3_
       }
   }
 
-  // ---- epilogue (as conv_igemm_kernel's): lane (lr, lq) holds channels 4 lq .. 4 lq + 3 of pixel lr per 16x16 tile ----
+  // ---- epilogue (the pair / quad primitives of conv_epilogue.h): lane (lr, lq) holds channels 4 lq .. 4 lq + 3 of pixel lr per 16x16 tile ----
   constexpr bool PAIR = E::DTYPE == 1;
   constexpr int NP2 = PAIR ? NI / 2 : NI, PSTEP = PAIR ? 32 : 16;
   const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (p.ablate & 1) ? 0u : p.obytes, 0x00020000);
@@ -347,22 +347,13 @@ __global__ void __launch_bounds__(NI == 4 ? 256 : 512, NI == 4 ? 1 : 2) conv3x3_
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni) {
         o[ni] = f32x4{acc[mi][ni][0] + ad[ni][0], acc[mi][ni][1] + ad[ni][1], acc[mi][ni][2] + ad[ni][2], acc[mi][ni][3] + ad[ni][3]};
-        if (p.res_mode != RES_NONE) { const f32x4 t = __builtin_bit_cast(f32x4, rr[ni]); o[ni] = f32x4{o[ni][0] + t[0], o[ni][1] + t[1], o[ni][2] + t[2], o[ni][3] + t[3]}; }
+        if (p.res_mode != RES_NONE) o[ni] = epi_quad_res<true>(o[ni], rr[ni]);
       }
     } else {
 #pragma unroll
       for (int k = 0; k < NP2; ++k) {
         float ra[4] = {0.f, 0.f, 0.f, 0.f}, rb[4] = {0.f, 0.f, 0.f, 0.f};
-        if (p.res_mode != RES_NONE) {   // un-swap the 8-channel residual piece back to the accumulator layout
-          const auto s0 = __builtin_amdgcn_permlane16_swap(rr[k][0], rr[k][2], false, false);
-          const auto s1 = __builtin_amdgcn_permlane16_swap(rr[k][1], rr[k][3], false, false);
-          const uint32_t xa[2] = {s0[0], s1[0]}, xb[2] = {s0[1], s1[1]};
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            unpack2(xa[j], ra[2 * j], ra[2 * j + 1], T());
-            unpack2(xb[j], rb[2 * j], rb[2 * j + 1], T());
-          }
-        }
+        if (p.res_mode != RES_NONE) epi_pair_unswap(rr[k], ra, rb, T());
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           o[2 * k][j] = acc[mi][2 * k][j] + ad[2 * k][j] + ra[j];
@@ -374,15 +365,10 @@ __global__ void __launch_bounds__(NI == 4 ? 256 : 512, NI == 4 ? 1 : 2) conv3x3_
   auto store_vals = [&](const f32x4 (&o)[NI], const __amdgpu_buffer_rsrc_t& rs, uint32_t ovo) {
     if constexpr (!PAIR) {
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[ni]), rs, ovo + ni * 16 * ESZ, 0, 0);
+      for (int ni = 0; ni < NI; ++ni) epi_quad_store(o[ni], rs, ovo + ni * 16 * ESZ);
     } else {
 #pragma unroll
-      for (int k = 0; k < NP2; ++k) {
-        const u32x2 pa2 = pack4(o[2 * k], T()), pb2 = pack4(o[2 * k + 1], T());
-        const auto w0 = __builtin_amdgcn_permlane16_swap(pa2[0], pb2[0], false, false);
-        const auto w1 = __builtin_amdgcn_permlane16_swap(pa2[1], pb2[1], false, false);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{w0[0], w1[0], w0[1], w1[1]}, rs, ovo + k * PSTEP * ESZ, 0, 0);
-      }
+      for (int k = 0; k < NP2; ++k) epi_pair_store(o[2 * k], o[2 * k + 1], rs, ovo + k * PSTEP * ESZ, T());
     }
   };
   auto for_mine = [&](auto f) {           // the pixel tiles this wave finishes

@@ -1,5 +1,6 @@
 // The warp-specialised persistent 3x3 conv as a unit of its own: the kernel and its launcher (conv_ws.inc.h) and the family's route / launch (ops.h).
 #include "conv_kargs.h"
+#include "conv_epilogue.h"
 
 namespace {
 #include "conv_ws.inc.h"

@@ -128,25 +128,15 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
   const int nsk = SKIP ? (p.SC0 + p.SC1) / CHUNK : 0;   // skip chunks per tile
   const int nsp = (nsk + 1) >> 1, nrp = ngr >> 1;       // skip item pairs / kernel row pairs per tile
   const int wtiles = p.nchunks * 9 + nsk;               // weight tiles per 128-channel pack tile
-  // Tile walk: items t = 0 .. ntp-1; 8 consecutive workgroups (one per XCD) take 8 consecutive pixel tiles, and the
-  // workgroup 8 further on (same XCD, same L2) takes the next channel tile of the same pixels.
-  const int ntp = ((n_mt + 7) / 8) * 8 * n_nt;
-  auto decode = [&](int t, int& mt, int& nt) {
-    const int per = 8 * n_nt, blk = t / per, r = t - blk * per;
-    nt = r >> 3; mt = blk * 8 + (r & 7);
-  };
-  auto next_valid = [&](int t) {     // next item of this workgroup's walk that is a real tile (or >= ntp)
-    for (t += gridDim.x; t < ntp; t += gridDim.x) { int mt, nt; decode(t, mt, nt); if (mt < n_mt) break; }
-    return t;
-  };
+  const TileWalk walk(n_mt, n_nt, gridDim.x, blockIdx.x);   // conv_epilogue.h
+  const int ntp = walk.ntp;
   auto origin = [&](int mt, int& n0, int& y0, int& x0) {
     const int ng = mt / tpi, rem = mt - ng * tpi;
     const int tyi = rem / p.tiles_x, txi = rem - tyi * p.tiles_x;
     n0 = ng; y0 = tyi * TH; x0 = txi * VW;
   };
-  int t_first = (int)blockIdx.x - (int)gridDim.x;
-  t_first = next_valid(t_first);
-  if (t_first >= ntp) return;        // whole workgroup leaves together: no barrier is ever reached
+  const int t_first = walk.first();
+  if (t_first >= ntp) return;       // whole workgroup leaves together: no barrier is ever reached
   if (threadIdx.x < 16) c_prod[threadIdx.x] = 0u;
   if constexpr ((WS_ABLATE & 2048) != 0) {   // consumers-alone experiment: random bf16 operands in [0.5, 1) of either sign (zeros would raise the clock)
     for (int i = threadIdx.x; i < (NPLANES * PLANE + NWBUF * 3 * WTILE) / 16; i += 512) {
@@ -336,13 +326,13 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
     for (int i = 0; i < WIT; ++i) woff[i] = (i * 256 + tid) * 16;
     // patch stream: the chunk whose pieces are being issued (one chunk ahead of the row stream)
     int pt_t = t_first, pt_c = 0, pt_plane = 0;
-    { int mt, nt; decode(pt_t, mt, nt); setup(mt); }
+    { int mt, nt; walk.decode(pt_t, mt, nt); setup(mt); }
     auto pt_advance = [&]() {
       pt_plane = pt_plane == NPLANES - 1 ? 0 : pt_plane + 1;
       if (++pt_c == p.nchunks) {
         pt_c = 0;
-        pt_t = next_valid(pt_t);
-        if (pt_t < ntp) { int mt, nt; decode(pt_t, mt, nt); setup(mt); }
+        pt_t = walk.next_valid(pt_t);
+        if (pt_t < ntp) { int mt, nt; walk.decode(pt_t, mt, nt); setup(mt); }
       }
     };
     // this wave's pieces of slot ky for the patch stream's chunk -> number issued (wave-uniform)
@@ -362,7 +352,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
       return 2;
     };
     int wl_t = t_first, wl_row = 0, wl_nt, wl_buf = 0;
-    { int mt; decode(wl_t, mt, wl_nt); }
+    { int mt; walk.decode(wl_t, mt, wl_nt); }
     auto dma_w = [&]() {               // next row of the weight stream -> wbuf[wl_buf] (6 pieces per wave)
       const uint32_t so = ((uint32_t)wl_nt * p.nchunks * 9 + (uint32_t)wl_row * 3) * WTILE;
       if constexpr (!(WS_ABLATE & 8)) {
@@ -374,8 +364,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
       wl_buf = wl_buf == NWBUF - 1 ? 0 : wl_buf + 1;
       if (++wl_row == ngr) {
         wl_row = 0;
-        wl_t = next_valid(wl_t);
-        if (wl_t < ntp) { int mt; decode(wl_t, mt, wl_nt); }
+        wl_t = walk.next_valid(wl_t);
+        if (wl_t < ntp) { int mt; walk.decode(wl_t, mt, wl_nt); }
       }
     };
     // all but this interval's own DMA pieces (6 weight pieces + k patch pieces) have landed; lgkmcnt(0): this wave's cbuf write
@@ -396,7 +386,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
     int cst_par = 0;
     auto cinit_load = [&](int t) {
       int mt, nt, n0, y0, x0;
-      decode(t, mt, nt);
+      walk.decode(t, mt, nt);
       origin(mt, n0, y0, x0);
       const int co = min(nt * BN + (tid & 31) * 4, p.Cout - 4);
       const float* dummy = reinterpret_cast<const float*>(p.w);
@@ -421,7 +411,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
     dma_w();                           // row 0
     STAMP(0)
     for (int t = t_first; t < ntp;) {
-      const int t_next = next_valid(t);
+      const int t_next = walk.next_valid(t);
       for (int c = 0; c < p.nchunks; ++c) {
         const bool last_c = c + 1 == p.nchunks && t_next < ntp;
         auto tail = [&](int k) {
@@ -492,12 +482,12 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
       }
     };
     int ld_t = t_first, ld_c = 0;
-    { int mt, nt; decode(ld_t, mt, nt); setup(mt); }
+    { int mt, nt; walk.decode(ld_t, mt, nt); setup(mt); }
     auto ld_advance = [&]() {
       if (++ld_c == p.nchunks) {
         ld_c = 0;
-        ld_t = next_valid(ld_t);
-        if (ld_t < ntp) { int mt, nt; decode(ld_t, mt, nt); setup(mt); }
+        ld_t = walk.next_valid(ld_t);
+        if (ld_t < ntp) { int mt, nt; walk.decode(ld_t, mt, nt); setup(mt); }
       }
     };
     u32x4 raw[PIT] = {};                                  // fragment u of the chunk that is committed next
@@ -552,7 +542,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
         spix[i] = (y < p.Ho && x < p.Wo) ? (n0 * p.Ho + y) * p.Wo + x : -1;
       }
     };
-    { int mt; decode(wl_t, mt, wl_nt); if constexpr (SKIP) skip_setup(mt); }
+    { int mt; walk.decode(wl_t, mt, wl_nt); if constexpr (SKIP) skip_setup(mt); }
     auto dma_w = [&]() {               // next row of the stream -> wbuf[wl_buf]
       if constexpr (!SKIP) {
       const uint32_t so = ((uint32_t)wl_nt * p.nchunks * 9 + (uint32_t)wl_row * 3) * WTILE;
@@ -565,8 +555,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
       wl_buf = wl_buf == NWBUF - 1 ? 0 : wl_buf + 1;
       if (++wl_row == ngr) {
         wl_row = 0;
-        wl_t = next_valid(wl_t);
-        if (wl_t < ntp) { int mt; decode(wl_t, mt, wl_nt); }
+        wl_t = walk.next_valid(wl_t);
+        if (wl_t < ntp) { int mt; walk.decode(wl_t, mt, wl_nt); }
       }
       } else {
       // six 1-KB pieces per wave either way: a kernel row's three weight tiles, or a skip item's weight tile (two) and dense plane (four)
@@ -602,8 +592,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
         wl_k = 0;
         if (++wl_row == ngr) {
           wl_row = 0; wl_s = 0;
-          wl_t = next_valid(wl_t);
-          if (wl_t < ntp) { int mt; decode(wl_t, mt, wl_nt); skip_setup(mt); }
+          wl_t = walk.next_valid(wl_t);
+          if (wl_t < ntp) { int mt; walk.decode(wl_t, mt, wl_nt); skip_setup(mt); }
         }
       }
       }
@@ -631,7 +621,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
     int cst_par = 0;
     auto cinit_load = [&](int t) {     // loads only (no wait, no branch: see issue_frag), consumed by cinit_commit two intervals later
       int mt, nt, n0, y0, x0;
-      decode(t, mt, nt);
+      walk.decode(t, mt, nt);
       origin(mt, n0, y0, x0);
       const int co = min(nt * BN + (tid & 31) * 4, p.Cout - 4);   // Cout % 128 == 0 for this kernel; the clamp only guards the address
       const float* dummy = reinterpret_cast<const float*>(p.w);           // any readable 16 bytes: an absent operand is zeroed at commit
@@ -668,7 +658,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
     STAMP(0)
     int plane = 0;                     // plane of the chunk the consumers multiply during this body
     for (int t = t_first; t < ntp;) {
-      const int t_next = next_valid(t);
+      const int t_next = walk.next_valid(t);
       // One chunk (t, c) of the consumer stream = three intervals, each ending in the barrier that publishes one kernel row:
       //   ky = 0: the last two fragments of chunk c itself (its plane was still being read one chunk ago until now)
       //   ky = 1, 2: fragments 0-3 of the chunk AFTER c into the other plane (free since the barrier that ended ky = 0)
@@ -899,9 +889,9 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
     read_a(IC<0>(), IC<0>(), IC<0>());
     read_b(IC<0>(), IC<0>());
     for (int t = t_first; t < ntp;) {
-      const int t_next = next_valid(t);
+      const int t_next = walk.next_valid(t);
       int mt, nt, n0, y0, x0;
-      decode(t, mt, nt);
+      walk.decode(t, mt, nt);
       origin(mt, n0, y0, x0);
       const int co_w = nt * BN + wn * 64 + 4 * lq;
       for (int r = 0; r < ngr; r += 2) {
@@ -934,8 +924,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
           for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = f32x4{accb[mi][4 * ni], accb[mi][4 * ni + 1], accb[mi][4 * ni + 2], accb[mi][4 * ni + 3]};
       }
       STAMP(6)
-      // ---- epilogue: MFMA rows are channels and columns are pixels, so lane (lr, lq) holds 4 consecutive channels of
-      // pixel lr per 16x16 tile; bf16 pairs of channel tiles are merged into 16-byte stores by two v_permlane16_swap ----
+      // ---- epilogue (layout and the pair primitives: conv_epilogue.h; the row loop is the same text in conv_pp.inc.h and stays
+      // written out: see the header why; conv_pp1.inc.h has the same loop with its own un-swap / pack / store, NOT on the primitives) ----
       const int co_s = PAIR ? nt * BN + wn * 64 + (lq & 1) * 16 + (lq >> 1) * 8 : co_w;
       GnPartial<NI> gp;
       const bool do_gn = p.gn_stats != nullptr;
@@ -985,16 +975,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
 #pragma unroll
             for (int k = 0; k < NP2; ++k) {
               float ra[4] = {0.f, 0.f, 0.f, 0.f}, rb[4] = {0.f, 0.f, 0.f, 0.f};
-              if constexpr (HAS_RES) {   // un-swap the 8-channel residual piece back to the accumulator layout
-                const auto s0 = __builtin_amdgcn_permlane16_swap(rr[j][k][0], rr[j][k][2], false, false);
-                const auto s1 = __builtin_amdgcn_permlane16_swap(rr[j][k][1], rr[j][k][3], false, false);
-                const uint32_t xa[2] = {s0[0], s1[0]}, xb[2] = {s0[1], s1[1]};
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                  unpack2(xa[q], ra[2 * q], ra[2 * q + 1], T());
-                  unpack2(xb[q], rb[2 * q], rb[2 * q + 1], T());
-                }
-              }
+              if constexpr (HAS_RES) epi_pair_unswap(rr[j][k], ra, rb, T());   // back to the accumulator layout
               float va[4], vb[4];
 #pragma unroll
               for (int q = 0; q < 4; ++q) {
@@ -1005,10 +986,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
                 gp.add(2 * k, va[0], va[1], va[2], va[3], GNM == 2, vm[j]);
                 gp.add(2 * k + 1, vb[0], vb[1], vb[2], vb[3], GNM == 2, vm[j]);
               }
-              const u32x2 pa2 = pack4(va, T()), pb2 = pack4(vb, T());
-              const auto w0 = __builtin_amdgcn_permlane16_swap(pa2[0], pb2[0], false, false);
-              const auto w1 = __builtin_amdgcn_permlane16_swap(pa2[1], pb2[1], false, false);
-              __builtin_amdgcn_raw_buffer_store_b128(u32x4{w0[0], w1[0], w0[1], w1[1]}, rso, ovo[j] + k * PSTEP * ESZ, 0, 0);
+              epi_pair_store(va, vb, rso, ovo[j] + k * PSTEP * ESZ, T());
             }
           }
         }
@@ -1038,27 +1016,23 @@ __global__ void __launch_bounds__(512, 2) conv3x3_ws_kernel(ConvKArgs p, int n_m
   }
 }
 
+template <typename T, int PRO, bool SKIP>
+int launch_ws_k(const ConvKArgs& a, int n_mt, int n_nt, int grid_cap, hipStream_t s) {
+  if (int rc = mi355_allow_big_lds(conv3x3_ws_kernel<T, PRO, SKIP>, "conv3x3 (persistent)")) return rc;
+  int grid = persistent_grid(n_mt, n_nt);
+  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;   // (tests: several tiles per workgroup at small shapes)
+  hipLaunchKernelGGL((conv3x3_ws_kernel<T, PRO, SKIP>), dim3(grid), dim3(512), ws::LDS_BYTES, s, a, n_mt, n_nt);
+  return 0;
+}
+
 // a shape ws_route (conv_ws.hip) accepts
 template <typename T>
 int launch_ws(ConvKArgs a, int grid_cap, hipStream_t s) {
   a.lvw = 4; a.lth = 4; a.PW = ws::PW; a.PH = ws::PH; a.NP = ws::NPX;
   a.tiles_x = (a.Wo + ws::VW - 1) / ws::VW; a.tiles_y = (a.Ho + ws::TH - 1) / ws::TH;
   const int n_mt = a.N * a.tiles_x * a.tiles_y, n_nt = (a.Cout + 127) / 128;
-  const int ncu = ws_num_cus();
-  using KernT = void (*)(ConvKArgs, int, int);
-  KernT kern = !a.pro_a ? (KernT)conv3x3_ws_kernel<T, 0> : (a.pro_silu ? (KernT)conv3x3_ws_kernel<T, 2> : (KernT)conv3x3_ws_kernel<T, 1>);
-  int rc;
-  if (a.sk0) {   // the carried skip conv (ws_route: a prologue form)
-    kern = a.pro_silu ? (KernT)conv3x3_ws_kernel<T, 2, true> : (KernT)conv3x3_ws_kernel<T, 1, true>;
-    rc = a.pro_silu ? mi355_allow_big_lds(conv3x3_ws_kernel<T, 2, true>, "conv3x3 (persistent)") : mi355_allow_big_lds(conv3x3_ws_kernel<T, 1, true>, "conv3x3 (persistent)");
-  } else
-  if (!a.pro_a) rc = mi355_allow_big_lds(conv3x3_ws_kernel<T, 0>, "conv3x3 (persistent)");
-  else if (a.pro_silu) rc = mi355_allow_big_lds(conv3x3_ws_kernel<T, 2>, "conv3x3 (persistent)");
-  else rc = mi355_allow_big_lds(conv3x3_ws_kernel<T, 1>, "conv3x3 (persistent)");
-  if (rc) return rc;
-  const int ntp = ((n_mt + 7) / 8) * 8 * n_nt;
-  int grid = ntp < ncu ? ntp : ncu;   // one persistent workgroup per CU
-  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;   // (tests: several tiles per workgroup at small shapes)
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), ws::LDS_BYTES, s, a, n_mt, n_nt);
-  return 0;
+  if (a.sk0)   // the carried skip conv (ws_route: a prologue form)
+    return a.pro_silu ? launch_ws_k<T, 2, true>(a, n_mt, n_nt, grid_cap, s) : launch_ws_k<T, 1, true>(a, n_mt, n_nt, grid_cap, s);
+  if (!a.pro_a) return launch_ws_k<T, 0, false>(a, n_mt, n_nt, grid_cap, s);
+  return a.pro_silu ? launch_ws_k<T, 2, false>(a, n_mt, n_nt, grid_cap, s) : launch_ws_k<T, 1, false>(a, n_mt, n_nt, grid_cap, s);
 }
