@@ -26,6 +26,8 @@ struct PlanTensor {
   // tensor; the producing conv fills stats[N][slots][C/4][2] at stats_off_per_image * N floats into the statistics arena
   int stats_cap = 0; size_t stats_off_per_image = 0;
 };
+// PlanTensor::stats_cap of a tensor of HW pixels: >= the slots of every kernel variant (at most one slot per 32 pixels)
+inline int gn_stats_cap(int HW) { return 4 * ((HW + 63) / 64) + 8; }
 
 enum OpKind { OP_GN = 0, OP_CONV = 1, OP_ATTN = 2, OP_RESAMPLE = 3, OP_POOLAFF = 4, OP_ATTN_FUSED = 5 };
 
@@ -50,6 +52,8 @@ struct PlanOp {
   // (conv_pack_weights_up2), for the ping-pong kernel's phase form; both images are kept, the route decides per launch
   int has_wu = 0; size_t wu_off = 0;
 };
+// PlanOp::cin_pad of a conv over sources of C0 (+ C1) channels: NHWC conv outputs come in whole 32-channel tiles
+inline int conv_dgrad_cin_pad(int C0, int C1) { return (C0 + C1 + 31) / 32 * 32; }
 
 struct mi355_unet {
   mi355_unet_config cfg;

@@ -181,7 +181,7 @@ struct Walker {
         for (int s : {s0, s1}) {
           if (s < 0 || net->tensors[s].stats_cap) continue;
           PlanTensor& t = net->tensors[s];
-          t.stats_cap = 4 * ((t.H * t.W + 63) / 64) + 8;   // >= slots of every kernel variant: at most one slot per 32 pixels
+          t.stats_cap = gn_stats_cap(t.H * t.W);
           t.stats_off_per_image = net->stats_floats_per_image;
           net->stats_floats_per_image += (size_t)t.stats_cap * (t.C / 4) * 2;
         }
@@ -213,7 +213,7 @@ struct Walker {
     op.dst = out_mode == OUT_NHWC ? tensor(Cout, Ho, Wo) : -1;
     if (cfg.differentiable) {
       if (use_pro) op.gn_site = last_site;
-      op.cin_pad = (int)align_up(T(s0).C + (s1 >= 0 ? T(s1).C : 0), 32);   // NHWC conv outputs come in whole 32-channel tiles
+      op.cin_pad = conv_dgrad_cin_pad(T(s0).C, s1 >= 0 ? T(s1).C : 0);
       const float* pw = P(prefix + ".weight", conv1d ? std::vector<int64_t>{Cout, Cin_logical, 1} : std::vector<int64_t>{Cout, Cin_logical, ks, ks});
       op.wT_off = alloc(conv_packed_weight_bytes_dgrad(dtype, Cout, Cin_logical, ks, op.cin_pad));
       if (!dry && pw) conv_pack_weights_dgrad(dtype, pw, Cout, Cin_logical, ks, op.cin_pad, blob.data() + op.wT_off);

@@ -34,6 +34,51 @@ def _same(a, b, na, nb):
         raise ValueError(f"{na} {tuple(a.shape)} and {nb} {tuple(b.shape)} must have the same shape")
 
 
+def _opt(t, name, dtype=torch.float32):
+    """_req of an operand that may be None."""
+    return _req(t, name, dtype) if t is not None else None
+
+
+# --- marshalling shared by the single-op wrappers (the conv ops, their route queries and the ops that take a workspace) ---
+def _host(t, shape=None):
+    """A weight or bias the C side reads from host memory -> (its fp32 CPU copy, to be kept alive over the call; a float pointer to it)."""
+    if t is None:
+        return None, None
+    h = t.detach().to("cpu", torch.float32).reshape(shape or t.shape).contiguous()
+    return h, C.cast(h.data_ptr(), C.POINTER(C.c_float))
+
+
+def _conv_out_size(H, W, k, stride=1, resample=0):
+    """Output size of a padded k x k conv over an H x W input that is first resampled: 2 nearest x2, 3 a 2x2 average pool."""
+    Hc, Wc = (2 * H, 2 * W) if resample == 2 else ((H // 2, W // 2) if resample == 3 else (H, W))
+    return (Hc + 2 * (k // 2) - k) // stride + 1, (Wc + 2 * (k // 2) - k) // stride + 1
+
+
+def _check_emb_res(emb, res, res_mode, B, Co, Ho, Wo):
+    if emb is not None and tuple(emb.shape) != (B, Co):
+        raise ValueError("emb must be [B, Co]")
+    want = (B, Co, Ho, Wo) if res_mode == 1 else (B, Co, Ho // 2, Wo // 2)
+    if res is not None and tuple(res.shape) != want:
+        raise ValueError(f"res must be {want}")
+
+
+def _workspace(L, B, channels, hw, device, fill=None):
+    """-> (the tensor, to be kept alive over the call; its pointer; its size): mi355_op_workspace_bytes of device memory, every byte `fill` if given."""
+    wsb = L.mi355_op_workspace_bytes(B, channels, hw)
+    ws = torch.empty(wsb, device=device, dtype=torch.uint8) if fill is None else torch.full((wsb,), int(fill), device=device, dtype=torch.uint8)
+    return ws, C.c_void_p(ws.data_ptr()), wsb
+
+
+def _debug_ptr(debug, or_default):
+    """The mi355_debug_config argument; debug None: the default struct (or_default) or NULL - the ops differ in which they hand over."""
+    return C.byref(debug) if debug is not None else (C.byref(_lib.debug_config()) if or_default else None)
+
+
+def _route_dict(route):
+    """The words a conv op reports of its launch (the first four, or all eight) -> dict."""
+    return dict(zip(("kernel", "form", "tile_m", "tile_n", "reads_nchw", "axpy", "ksplit", "n_mt"), route))
+
+
 class Ops:
     """Default op table used by the samplers (tests may inject a recording double with the same methods)."""
 
@@ -72,16 +117,15 @@ class Ops:
         if out is not None:
             _same(x, out, "x", "out")
         seed, off = philox if philox else (0, 0)
-        check(_lib.lib().mi355_sde_euler_step(_req(x, "x"), _req(a, "a"), _req(b, "b") if b is not None else None, float(ca), float(cb), float(dt),
-                                              gp, gs, _req(dW, "dW") if dW is not None else None, int(philox is not None and dW is None),
-                                              int(seed), int(off), _req(out, "out") if out is not None else None, float(w), x.numel(), _stream()),
+        check(_lib.lib().mi355_sde_euler_step(_req(x, "x"), _req(a, "a"), _opt(b, "b"), float(ca), float(cb), float(dt), gp, gs, _opt(dW, "dW"),
+                                              int(philox is not None and dW is None), int(seed), int(off), _opt(out, "out"), float(w), x.numel(), _stream()),
               "mi355_sde_euler_step")
         return x
 
     def ddpm_step_(self, x, eps, z, c_recip, c_recipm1, coef1, coef2, sigma, philox=None):
         """z: injected noise tensor, or None; philox: (seed, offset) for device noise; both None = no noise (i == 0)."""
         _same(x, eps, "x", "eps")
-        zp = _req(z, "z") if z is not None else None
+        zp = _opt(z, "z")
         if z is not None:
             _same(x, z, "x", "z")
         seed, off = philox if philox else (0, 0)
@@ -91,7 +135,7 @@ class Ops:
 
     def corrector_step_(self, x, eps, z, c_recip, c_recipm1, rsm1, dt, delta, philox=None):
         _same(x, eps, "x", "eps")
-        zp = _req(z, "z") if z is not None else None
+        zp = _opt(z, "z")
         seed, off = philox if philox else (0, 0)
         check(_lib.lib().mi355_corrector_step(_req(x, "x"), _req(eps, "eps"), zp, c_recip, c_recipm1, rsm1, dt, delta,
                                               int(philox is not None and z is None), seed, off, x.numel(), _stream()))
@@ -106,7 +150,7 @@ class Ops:
         """DDIM(eta) step in place: ddim_step_'s x0 and e2, x <- sqrt(acp_prev) x0 + sqrt(max(1 - acp_prev - sigma^2, 0)) e2 + sigma z.
         z / philox as in ddpm_step_; both None = no noise term (sigma = 0 then gives ddim_step_'s bits)."""
         _same(x, eps, "x", "eps")
-        zp = _req(z, "z") if z is not None else None
+        zp = _opt(z, "z")
         if z is not None:
             _same(x, z, "x", "z")
         seed, off = philox if philox else (0, 0)
@@ -125,9 +169,8 @@ class Ops:
             raise ValueError("z must have the B-image state's size")
         wf, wp, keep = self._cfg_w(w, B)
         seed, off = philox if philox else (0, 0)
-        check(_lib.lib().mi355_ddim_eta_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _req(z, "z") if z is not None else None, wf, wp,
-                                                 n // B if B else 1, c_recip, c_recipm1, acp_prev, float(sigma),
-                                                 int(philox is not None and z is None), seed, off, n, _stream()), "mi355_ddim_eta_cfg_step")
+        check(_lib.lib().mi355_ddim_eta_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _opt(z, "z"), wf, wp, n // B if B else 1, c_recip, c_recipm1, acp_prev,
+                                                 float(sigma), int(philox is not None and z is None), seed, off, n, _stream()), "mi355_ddim_eta_cfg_step")
         return x2
 
     def dpmpp_step_(self, x, eps, hist, c_recip, c_recipm1, cx, c0, c1):
@@ -138,8 +181,8 @@ class Ops:
             _same(x, hist, "x", "hist")
         elif float(c1) != 0.0:
             raise ValueError("c1 != 0 needs hist (the previous step's data prediction)")
-        check(_lib.lib().mi355_dpmpp_step(_req(x, "x"), _req(eps, "eps"), _req(hist, "hist") if hist is not None else None, float(c_recip),
-                                          float(c_recipm1), float(cx), float(c0), float(c1), x.numel(), _stream()), "mi355_dpmpp_step")
+        check(_lib.lib().mi355_dpmpp_step(_req(x, "x"), _req(eps, "eps"), _opt(hist, "hist"), float(c_recip), float(c_recipm1), float(cx), float(c0), float(c1),
+                                          x.numel(), _stream()), "mi355_dpmpp_step")
         return x
 
     def dpmpp_cfg_step_(self, x2, eps2, hist, w, c_recip, c_recipm1, cx, c0, c1):
@@ -154,9 +197,8 @@ class Ops:
         if hist is None and float(c1) != 0.0:
             raise ValueError("c1 != 0 needs hist (the previous step's data prediction)")
         wf, wp, keep = self._cfg_w(w, B)
-        check(_lib.lib().mi355_dpmpp_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _req(hist, "hist") if hist is not None else None, wf, wp,
-                                              n // B if B else 1, float(c_recip), float(c_recipm1), float(cx), float(c0), float(c1), n, _stream()),
-              "mi355_dpmpp_cfg_step")
+        check(_lib.lib().mi355_dpmpp_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _opt(hist, "hist"), wf, wp, n // B if B else 1, float(c_recip),
+                                              float(c_recipm1), float(cx), float(c0), float(c1), n, _stream()), "mi355_dpmpp_cfg_step")
         return x2
 
     def x0_shape_stats(self, x, eps, c_recip, c_recipm1, shaping, w=None, detail=False):
@@ -196,16 +238,14 @@ class Ops:
             raise ValueError(f"shape must be [{B}, 2], got {tuple(shape.shape)}")
         wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
         seed, off = philox if philox else (0, 0)
-        check(_lib.lib().mi355_x0_shaped_step(self._STEP_KINDS[kind], _req(x, "x"), _req(eps, "eps"), _req(z, "z") if z is not None else None,
-                                              _req(hist, "hist") if hist is not None else None, int(guided), wf, wp, n // B if B else 1,
-                                              float(c_recip), float(c_recipm1), float(a), float(b), float(c), float(sigma),
-                                              int(philox is not None and z is None), seed, off, _req(shape, "shape") if shape is not None else None,
-                                              n, _stream()), "mi355_x0_shaped_step")
+        check(_lib.lib().mi355_x0_shaped_step(self._STEP_KINDS[kind], _req(x, "x"), _req(eps, "eps"), _opt(z, "z"), _opt(hist, "hist"), int(guided), wf, wp,
+                                              n // B if B else 1, float(c_recip), float(c_recipm1), float(a), float(b), float(c), float(sigma),
+                                              int(philox is not None and z is None), seed, off, _opt(shape, "shape"), n, _stream()), "mi355_x0_shaped_step")
         return x
 
     def renoise_(self, x, z, a, b, philox=None):
         """The forward move q(x_k | x_{k-1}) in place: x <- a x + b z (a = sqrt(alphas_k), b = sqrt(betas_k)); z / philox as in ddpm_step_."""
-        zp = _req(z, "z") if z is not None else None
+        zp = _opt(z, "z")
         if z is not None:
             _same(x, z, "x", "z")
         seed, off = philox if philox else (0, 0)
@@ -215,7 +255,7 @@ class Ops:
 
     def replace_mask_(self, x, cond, z, pad_value, noisy, sa, sb, philox=None):
         _same(x, cond, "x", "condition")
-        zp = _req(z, "z") if z is not None else None
+        zp = _opt(z, "z")
         seed, off = philox if philox else (0, 0)
         check(_lib.lib().mi355_replace_mask(_req(x, "x"), _req(cond, "condition"), zp, float(pad_value), int(noisy), sa, sb,
                                             int(philox is not None and z is None), seed, off, x.numel(), _stream()))
@@ -326,8 +366,7 @@ class Ops:
         if y is not None:
             _same(x, y, "x", "y")
         out = torch.empty_like(x) if out is None else out
-        check(_lib.lib().mi355_lincomb_per_sample(_req(out, "out"), _req(x, "x"), _req(y, "y") if y is not None else None, _req(a, "a"),
-                                                  _req(b, "b") if b is not None else None, B, x[0].numel(), _stream()))
+        check(_lib.lib().mi355_lincomb_per_sample(_req(out, "out"), _req(x, "x"), _opt(y, "y"), _req(a, "a"), _opt(b, "b"), B, x[0].numel(), _stream()))
         return out
 
     def resize_bilinear(self, x, size):
@@ -372,8 +411,7 @@ class Ops:
         assert len(ks) == len(coeffs) <= 7
         arr = (C.c_float * 7)(*([float(c) for c in coeffs] + [0.0] * (7 - len(coeffs))))
         kp = [_req(k, "k") for k in ks] + [None] * (7 - len(ks))
-        check(_lib.lib().mi355_rk_combine(_req(out, "out"), _req(y0, "y0") if y0 is not None else None, *kp, arr, len(ks), out.numel(),
-                                          _stream()))
+        check(_lib.lib().mi355_rk_combine(_req(out, "out"), _opt(y0, "y0"), *kp, arr, len(ks), out.numel(), _stream()))
         return out
 
     def rk_stage(self, out, y0, ks, coeffs, copy_out=None, u8_out=None):
@@ -391,9 +429,8 @@ class Ops:
             _same(out, u8_out, "out", "u8_out")
         arr = (C.c_float * 4)(*([float(c) for c in coeffs] + [0.0] * (4 - len(coeffs))))
         kp = (C.c_void_p * 4)(*([_req(k, "k") for k in ks] + [None] * (4 - len(ks))))
-        check(_lib.lib().mi355_rk_stage(_req(out, "out"), _req(y0, "y0"), kp, arr, len(ks), out.numel(),
-                                        _req(copy_out, "copy_out") if copy_out is not None else None,
-                                        _req(u8_out, "u8_out", torch.uint8) if u8_out is not None else None, _stream()), "mi355_rk_stage")
+        check(_lib.lib().mi355_rk_stage(_req(out, "out"), _req(y0, "y0"), kp, arr, len(ks), out.numel(), _opt(copy_out, "copy_out"),
+                                        _opt(u8_out, "u8_out", torch.uint8), _stream()), "mi355_rk_stage")
         return out
 
     # --- classifier-free guidance (csrc/ode.hip cfg_stage_kernel, csrc/steps.hip) ---
@@ -430,9 +467,8 @@ class Ops:
         wf, wp, keep = self._cfg_w(w, B)
         arr = (C.c_float * 4)(*([float(c) for c in coeffs] + [0.0] * (4 - len(coeffs))))
         kp = (C.c_void_p * 4)(*([_req(k, "k") for k in ks] + [None] * (4 - len(ks))))
-        check(_lib.lib().mi355_cfg_stage(_req(out, "out"), _req(y0, "y0") if y0 is not None else None, kp, arr, len(ks), n, wf, wp,
-                                         n // B if B else 1, int(bool(dup)), _req(copy_out, "copy_out") if copy_out is not None else None,
-                                         _req(u8_out, "u8_out", torch.uint8) if u8_out is not None else None, _stream()), "mi355_cfg_stage")
+        check(_lib.lib().mi355_cfg_stage(_req(out, "out"), _opt(y0, "y0"), kp, arr, len(ks), n, wf, wp, n // B if B else 1, int(bool(dup)),
+                                         _opt(copy_out, "copy_out"), _opt(u8_out, "u8_out", torch.uint8), _stream()), "mi355_cfg_stage")
         return out
 
     def cfg_combine(self, v2, w, out=None):
@@ -453,9 +489,8 @@ class Ops:
             raise ValueError("z must have the B-image state's size")
         wf, wp, keep = self._cfg_w(w, B)
         seed, off = philox if philox else (0, 0)
-        check(_lib.lib().mi355_ddpm_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _req(z, "z") if z is not None else None, wf, wp, n // B if B else 1,
-                                             c_recip, c_recipm1, coef1, coef2, sigma, int(philox is not None and z is None), seed, off, n, _stream()),
-              "mi355_ddpm_cfg_step")
+        check(_lib.lib().mi355_ddpm_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _opt(z, "z"), wf, wp, n // B if B else 1, c_recip, c_recipm1, coef1, coef2,
+                                             sigma, int(philox is not None and z is None), seed, off, n, _stream()), "mi355_ddpm_cfg_step")
         return x2
 
     def ddim_cfg_step_(self, x2, eps2, w, c_recip, c_recipm1, acp_prev):
@@ -472,8 +507,7 @@ class Ops:
 
     def rk_sqnorm(self, acc, a, sub=None, b=None, b2=None, atol=1.0, rtol=0.0):
         """acc (device fp64 scalar tensor) += sum(((a - sub) / (atol + rtol * max(|b|, |b2|)))**2)."""
-        check(_lib.lib().mi355_rk_sqnorm(_req(a, "a"), _req(sub, "sub") if sub is not None else None, _req(b, "b") if b is not None else None,
-                                         _req(b2, "b2") if b2 is not None else None, float(atol), float(rtol), a.numel(),
+        check(_lib.lib().mi355_rk_sqnorm(_req(a, "a"), _opt(sub, "sub"), _opt(b, "b"), _opt(b2, "b2"), float(atol), float(rtol), a.numel(),
                                          _req(acc, "acc", torch.float64), _stream()))
         return acc
 
@@ -495,34 +529,21 @@ class Ops:
         assert Ci == Cin + Cin1
         if x1 is not None and (x1.shape[0] != B or x1.shape[2:] != x.shape[2:]):
             raise ValueError("x1 must match x in batch and spatial size")
-        Hc = H * 2 if resample == 2 else (H // 2 if resample == 3 else H)
-        Wc = W * 2 if resample == 2 else (W // 2 if resample == 3 else W)
-        Ho = (Hc + 2 * (k // 2) - k) // stride + 1
-        Wo = (Wc + 2 * (k // 2) - k) // stride + 1
-        if emb is not None and emb.shape != (B, Co):
-            raise ValueError("emb must be [B, Co]")
-        if res is not None:
-            want = (B, Co, Ho, Wo) if res_mode == 1 else (B, Co, Ho // 2, Wo // 2)
-            if tuple(res.shape) != want:
-                raise ValueError(f"res must be {want}")
+        Ho, Wo = _conv_out_size(H, W, k, stride, resample)
+        _check_emb_res(emb, res, res_mode, B, Co, Ho, Wo)
         y = torch.empty(B, Co, Ho, Wo, device=x.device, dtype=torch.float32)
         L = _lib.lib()
-        wsb = L.mi355_op_workspace_bytes(B, max(Ci, Co), max(H * W, Ho * Wo))
-        ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
-        w = weight.detach().to("cpu", torch.float32).contiguous()
-        b = bias.detach().to("cpu", torch.float32).contiguous() if bias is not None else None
-        fp = C.POINTER(C.c_float)
-        args = (_req(x, "x"), _req(x1, "x1") if x1 is not None else None, Cin1, C.cast(w.data_ptr(), fp),
-                C.cast(b.data_ptr(), fp) if b is not None else None, _req(y, "y"), B, Cin, H, W, Co, k, stride, resample,
-                _req(gn[0], "gamma") if gn else None, _req(gn[1], "beta") if gn else None, int(gn_silu),
-                _req(emb, "emb") if emb is not None else None, _req(res, "res") if res is not None else None, int(res_mode),
-                dtype, C.byref(debug if debug is not None else _lib.debug_config()), C.c_void_p(ws.data_ptr()), wsb, _stream())
+        ws, wsp, wsb = _workspace(L, B, max(Ci, Co), max(H * W, Ho * Wo), x.device)
+        (w, wp), (b, bp) = _host(weight), _host(bias)
+        gamma, beta = gn if gn else (None, None)
+        args = (_req(x, "x"), _opt(x1, "x1"), Cin1, wp, bp, _req(y, "y"), B, Cin, H, W, Co, k, stride, resample, _opt(gamma, "gamma"),
+                _opt(beta, "beta"), int(gn_silu), _opt(emb, "emb"), _opt(res, "res"), int(res_mode), dtype, _debug_ptr(debug, True), wsp, wsb, _stream())
         if info is None:
             check(L.mi355_conv2d(*args), "mi355_conv2d")
         else:
             ex = _lib.ConvExtrasC()
             check(L.mi355_conv2d_ex(*args, C.byref(ex)), "mi355_conv2d_ex")
-            info.update(kernel=ex.route[0], form=ex.route[1], tile_m=ex.route[2], tile_n=ex.route[3])
+            info.update(_route_dict(ex.route))
         return y
 
     def conv2d_ex(self, x, weight, bias, dtype=_lib.MI355_F32, skip=None, sites=(), film=None, debug=None, gn=None, gn_silu=False, emb=None,
@@ -539,17 +560,13 @@ class Ops:
         assert Ci == Cin and k == 3 and len(sites) <= 2
         y = torch.empty(B, Co, H, W, device=x.device, dtype=torch.float32)
         L = _lib.lib()
-        wsb = L.mi355_op_workspace_bytes(B, max(Ci, Co), H * W)
-        ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
-        w = weight.detach().to("cpu", torch.float32).contiguous()
-        b = bias.detach().to("cpu", torch.float32).contiguous() if bias is not None else None
-        fp = C.POINTER(C.c_float)
+        ws, wsp, wsb = _workspace(L, B, max(Ci, Co), H * W, x.device)
+        (w, wp), (b, bp) = _host(weight), _host(bias)
         ex = _lib.ConvExtrasC()
         keep = []
         if skip is not None:
             xs0, xs1, w1, b1 = skip
-            w1c = w1.detach().to("cpu", torch.float32).reshape(Co, -1).contiguous()
-            b1c = b1.detach().to("cpu", torch.float32).contiguous() if b1 is not None else None
+            w1c, b1c = _host(w1, (Co, -1))[0], _host(b1)[0]
             keep += [w1c, b1c]
             ex.skip_x0 = _req(xs0, "skip_x0"); ex.skip_c0 = xs0.shape[1]
             if xs1 is not None:
@@ -570,13 +587,10 @@ class Ops:
             keep += [one, zero]
             ex.route[3] = 0x53544154   # MI355_CONV_EXTRAS_STATS: the stat_* fields are present
             ex.stat_gamma = _req(one, "stat_gamma"); ex.stat_beta = _req(zero, "stat_beta"); ex.stat_a = _req(sa, "stat_a"); ex.stat_b = _req(sb, "stat_b")
-        if emb is not None and emb.shape != (B, Co):
-            raise ValueError("emb must be [B, Co]")
-        check(L.mi355_conv2d_ex(_req(x, "x"), None, 0, C.cast(w.data_ptr(), fp), C.cast(b.data_ptr(), fp) if b is not None else None, _req(y, "y"),
-                                B, Cin, H, W, Co, 3, 1, 0, _req(gn[0], "gamma") if gn else None, _req(gn[1], "beta") if gn else None, int(gn_silu),
-                                _req(emb, "emb") if emb is not None else None, None, 1, dtype,
-                                C.byref(debug if debug is not None else _lib.debug_config()), C.c_void_p(ws.data_ptr()), wsb, _stream(), C.byref(ex)),
-              "mi355_conv2d_ex")
+        _check_emb_res(emb, None, 1, B, Co, H, W)
+        gamma, beta = gn if gn else (None, None)
+        check(L.mi355_conv2d_ex(_req(x, "x"), None, 0, wp, bp, _req(y, "y"), B, Cin, H, W, Co, 3, 1, 0, _opt(gamma, "gamma"), _opt(beta, "beta"), int(gn_silu),
+                                _opt(emb, "emb"), None, 1, dtype, _debug_ptr(debug, True), wsp, wsb, _stream(), C.byref(ex)), "mi355_conv2d_ex")
         if stats is not None:
             stats.update(slots=ex.stat_slots, a=sa if ex.stat_slots > 0 else None, b=sb if ex.stat_slots > 0 else None,
                          kernel=ex.route[0], tile_m=ex.route[2], tile_n=ex.route[3])
@@ -587,10 +601,8 @@ class Ops:
         ch = width // (3 * heads)
         out = torch.empty(B, heads * ch, T, device=qkv.device, dtype=torch.float32)
         L = _lib.lib()
-        wsb = L.mi355_op_workspace_bytes(B, width, T)
-        ws = torch.empty(wsb, device=qkv.device, dtype=torch.uint8)
-        check(L.mi355_qkv_attention(_req(qkv, "qkv"), _req(out, "out"), B, heads, ch, T, int(new_order), dtype,
-                                    C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_qkv_attention")
+        ws, wsp, wsb = _workspace(L, B, width, T, qkv.device)
+        check(L.mi355_qkv_attention(_req(qkv, "qkv"), _req(out, "out"), B, heads, ch, T, int(new_order), dtype, wsp, wsb, _stream()), "mi355_qkv_attention")
         return out
 
     def qkv_attention_vjp(self, qkv, grad_out, heads, new_order=False, dtype=_lib.MI355_F32, ws_fill=None):
@@ -603,11 +615,9 @@ class Ops:
             raise ValueError(f"grad_out must be {(B, heads * ch, T)}, got {tuple(grad_out.shape)}")
         gq = torch.empty_like(qkv)
         L = _lib.lib()
-        wsb = L.mi355_op_workspace_bytes(B, width, T)
-        ws = torch.empty(wsb, device=qkv.device, dtype=torch.uint8) if ws_fill is None else \
-            torch.full((wsb,), int(ws_fill), device=qkv.device, dtype=torch.uint8)
-        check(L.mi355_qkv_attention_vjp(_req(qkv, "qkv"), _req(grad_out, "grad_out"), _req(gq, "grad_qkv"), B, heads, ch, T, int(new_order),
-                                        dtype, C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_qkv_attention_vjp")
+        ws, wsp, wsb = _workspace(L, B, width, T, qkv.device, ws_fill)
+        check(L.mi355_qkv_attention_vjp(_req(qkv, "qkv"), _req(grad_out, "grad_out"), _req(gq, "grad_qkv"), B, heads, ch, T, int(new_order), dtype, wsp, wsb,
+                                        _stream()), "mi355_qkv_attention_vjp")
         return gq
 
     def attn_block_fused(self, x, a, b, weight, bias, heads, new_order=False, dtype=_lib.MI355_F32, debug=None):
@@ -617,19 +627,15 @@ class Ops:
         B, Cc, T = x.shape
         if tuple(a.shape) != (B, Cc) or tuple(b.shape) != (B, Cc):
             raise ValueError(f"a and b must be {(B, Cc)}")
-        w = weight.detach().to("cpu", torch.float32).reshape(weight.shape[0], -1).contiguous()
-        bh = bias.detach().to("cpu", torch.float32).contiguous()
+        (w, wp), (bh, bp) = _host(weight, (weight.shape[0], -1)), _host(bias)
         if tuple(w.shape) != (3 * Cc, Cc) or tuple(bh.shape) != (3 * Cc,):
             raise ValueError(f"weight must be {(3 * Cc, Cc)} and bias {(3 * Cc,)}")
         out = torch.empty(B, Cc, T, device=x.device, dtype=torch.float32)
         L = _lib.lib()
-        wsb = L.mi355_op_workspace_bytes(B, 3 * Cc, T)
-        ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
-        fp = C.POINTER(C.c_float)
+        ws, wsp, wsb = _workspace(L, B, 3 * Cc, T, x.device)
         form = (C.c_int32 * 3)(-1, -1, -1)
-        check(L.mi355_attn_block_fused(_req(x, "x"), _req(a, "a"), _req(b, "b"), C.cast(w.data_ptr(), fp), C.cast(bh.data_ptr(), fp), _req(out, "out"),
-                                       B, Cc, T, heads, int(new_order), dtype, C.byref(debug if debug is not None else _lib.debug_config()),
-                                       form, C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_attn_block_fused")
+        check(L.mi355_attn_block_fused(_req(x, "x"), _req(a, "a"), _req(b, "b"), wp, bp, _req(out, "out"), B, Cc, T, heads, int(new_order), dtype,
+                                       _debug_ptr(debug, True), form, wsp, wsb, _stream()), "mi355_attn_block_fused")
         return out, (("image", form[1]) if form[0] == 1 else ("persistent", form[1], form[2]))
 
     # --- GroupNorm32 test ops: the kernels the network launches, one op each (NCHW fp32 tensors; see include/mi355_sampler.h) ---
@@ -653,9 +659,8 @@ class Ops:
         rstd = torch.full((B, 32), float("nan"), device=dev) if stats else None
         y = torch.full((B, Cc) + tuple(x.shape[2:]), float("nan"), device=dev) if apply else None
         form = C.c_int32(-1)
-        check(_lib.lib().mi355_gn_affine(_req(x, "x"), _req(x1, "x1") if x1 is not None else None, _req(gamma, "gamma"), _req(beta, "beta"),
-                                         _req(film, "film") if film is not None else None, float(eps), _req(a, "a"), _req(b, "b"),
-                                         _req(mean, "mean") if stats else None, _req(rstd, "rstd") if stats else None,
+        check(_lib.lib().mi355_gn_affine(_req(x, "x"), _opt(x1, "x1"), _req(gamma, "gamma"), _req(beta, "beta"), _opt(film, "film"), float(eps), _req(a, "a"),
+                                         _req(b, "b"), _req(mean, "mean") if stats else None, _req(rstd, "rstd") if stats else None,
                                          _req(y, "y") if apply else None, int(apply == "silu"), C.byref(form), B, C0, C1, hw, dtype, _stream()),
               "mi355_gn_affine")
         return dict(a=a, b=b, mean=mean, rstd=rstd, y=y, form=form.value)
@@ -672,9 +677,7 @@ class Ops:
         if x1 is not None:
             Co1, Ci1, k1, _ = weight1.shape
             assert Ci1 == x1.shape[1] and k1 == k and x1.shape[0] == B and x1.shape[2:] == x.shape[2:]
-        Hc, Wc = (H * 2, W * 2) if resample == 2 else (H, W)
-        Ho = (Hc + 2 * (k // 2) - k) // stride + 1
-        Wo = (Wc + 2 * (k // 2) - k) // stride + 1
+        Ho, Wo = _conv_out_size(H, W, k, stride, 2 if resample == 2 else 0)
         Cc = Co + Co1
         if tuple(gamma.shape) != (Cc,) or tuple(beta.shape) != (Cc,) or (film is not None and tuple(film.shape) != (B, 2 * Cc)):
             raise ValueError("gamma / beta must be [Co + Co1], film [B, 2 (Co + Co1)]")
@@ -683,16 +686,12 @@ class Ops:
         y1 = torch.full((B, Co1, Ho, Wo), float("nan"), device=dev) if x1 is not None else None
         a = torch.full((B, Cc), float("nan"), device=dev)
         b = torch.full((B, Cc), float("nan"), device=dev)
-        fp = C.POINTER(C.c_float)
-        host = lambda t: t.detach().to("cpu", torch.float32).contiguous() if t is not None else None
-        w0, b0, w1, b1 = host(weight), host(bias), host(weight1), host(bias1)
-        hp = lambda t: C.cast(t.data_ptr(), fp) if t is not None else None
+        (w0, w0p), (b0, b0p), (w1, w1p), (b1, b1p) = _host(weight), _host(bias), _host(weight1), _host(bias1)
         info = (C.c_int32 * 6)()
-        check(_lib.lib().mi355_conv2d_gn(_req(x, "x"), hp(w0), hp(b0), _req(y, "y"), Cin, Co,
-                                         _req(x1, "x1") if x1 is not None else None, hp(w1), hp(b1), _req(y1, "y1") if x1 is not None else None,
-                                         x1.shape[1] if x1 is not None else 0, Co1, B, H, W, k, stride, resample, _req(gamma, "gamma"),
-                                         _req(beta, "beta"), _req(film, "film") if film is not None else None, float(eps), _req(a, "a"), _req(b, "b"),
-                                         dtype, C.byref(debug if debug is not None else _lib.debug_config()), info, _stream()), "mi355_conv2d_gn")
+        check(_lib.lib().mi355_conv2d_gn(_req(x, "x"), w0p, b0p, _req(y, "y"), Cin, Co, _opt(x1, "x1"), w1p, b1p, _opt(y1, "y1"),
+                                         x1.shape[1] if x1 is not None else 0, Co1, B, H, W, k, stride, resample, _req(gamma, "gamma"), _req(beta, "beta"),
+                                         _opt(film, "film"), float(eps), _req(a, "a"), _req(b, "b"), dtype, _debug_ptr(debug, True), info, _stream()),
+              "mi355_conv2d_gn")
         return dict(y=y, y1=y1, a=a, b=b, kernel=info[0], slots=info[1], form=info[2], kernel1=info[3], slots1=info[4], form1=info[5])
 
     def affine_pool(self, x, a=None, b=None, silu=False, dtype=_lib.MI355_F32):
@@ -701,8 +700,8 @@ class Ops:
         if (a is None) != (b is None) or (a is not None and (tuple(a.shape) != (B, Cc) or tuple(b.shape) != (B, Cc))):
             raise ValueError("a and b must both be [B, C] or both None")
         out = torch.full((B, Cc, H // 2, W // 2), float("nan"), device=x.device)
-        check(_lib.lib().mi355_affine_pool(_req(x, "x"), _req(a, "a") if a is not None else None, _req(b, "b") if b is not None else None,
-                                           int(bool(silu)), _req(out, "out"), B, Cc, H, W, dtype, _stream()), "mi355_affine_pool")
+        check(_lib.lib().mi355_affine_pool(_req(x, "x"), _opt(a, "a"), _opt(b, "b"), int(bool(silu)), _req(out, "out"), B, Cc, H, W, dtype, _stream()),
+              "mi355_affine_pool")
         return out
 
     def gn_silu_vjp(self, x, du, gamma, beta, x1=None, film=None, eps=1e-5, silu=True, du_stride=None, g0=None, g1=None,
@@ -725,10 +724,9 @@ class Ops:
             _same(g1, x1, "g1", "x1")
         g0 = g0 if acc0 else torch.full_like(x, float("nan"))
         g1 = None if x1 is None else (g1 if acc1 else torch.full_like(x1, float("nan")))
-        check(_lib.lib().mi355_gn_silu_vjp(_req(x, "x"), _req(x1, "x1") if x1 is not None else None, _req(gamma, "gamma"), _req(beta, "beta"),
-                                           _req(film, "film") if film is not None else None, float(eps), int(bool(silu)), _req(du, "du"),
-                                           int(du_stride or Cc), _req(g0, "g0"), _req(g1, "g1") if g1 is not None else None, int(acc0), int(acc1),
-                                           B, C0, C1, hw, dtype, _stream()), "mi355_gn_silu_vjp")
+        check(_lib.lib().mi355_gn_silu_vjp(_req(x, "x"), _opt(x1, "x1"), _req(gamma, "gamma"), _req(beta, "beta"), _opt(film, "film"), float(eps),
+                                           int(bool(silu)), _req(du, "du"), int(du_stride or Cc), _req(g0, "g0"), _opt(g1, "g1"), int(acc0), int(acc1), B, C0,
+                                           C1, hw, dtype, _stream()), "mi355_gn_silu_vjp")
         return g0, g1
 
     def grad_gather(self, src, shape, mode, coff=0, scale=1.0, dst=None, dtype=_lib.MI355_F32):
@@ -774,16 +772,14 @@ class Ops:
             g0 = g0 if acc0 else torch.full((B, c0, h, w), float("nan"), device=dev)
             g1 = None if not c1 else (g1 if acc1 else torch.full((B, c1, h, w), float("nan"), device=dev))
         L = _lib.lib()
-        wsb = L.mi355_op_workspace_bytes(B, max(cin_pad, gch), max(h * w, Ho * Wo))
-        ws = torch.empty(wsb, device=dev, dtype=torch.uint8) if ws_fill is None else torch.full((wsb,), int(ws_fill), device=dev, dtype=torch.uint8)
-        wh = weight.detach().to("cpu", torch.float32).contiguous()
+        ws, wsp, wsb = _workspace(L, B, max(cin_pad, gch), max(h * w, Ho * Wo), dev, ws_fill)
+        wh, whp = _host(weight)
         route = (C.c_int32 * 4)(-1, -1, -1, -1)
-        check(L.mi355_conv2d_vjp(C.cast(wh.data_ptr(), C.POINTER(C.c_float)), _req(grad_out, "grad_out"), None if raw else _req(g0, "g0"),
-                                 _req(g1, "g1") if g1 is not None else None, _req(out, "du_raw") if raw else None, int(acc0), int(acc1), B, Co, Ci,
-                                 int(c0), int(c1), h, w, k, int(mode), gch, dtype, C.byref(debug) if debug is not None else None, route,
-                                 C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_conv2d_vjp")
+        check(L.mi355_conv2d_vjp(whp, _req(grad_out, "grad_out"), None if raw else _req(g0, "g0"), _opt(g1, "g1"), _req(out, "du_raw") if raw else None,
+                                 int(acc0), int(acc1), B, Co, Ci, int(c0), int(c1), h, w, k, int(mode), gch, dtype, _debug_ptr(debug, False), route, wsp, wsb,
+                                 _stream()), "mi355_conv2d_vjp")
         if info is not None:
-            info.update(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3])
+            info.update(_route_dict(route))
         return out if raw else (g0, g1)
 
     def conv2d_vjp_route(self, B, Co, Ci, c0, c1, h, w, k, mode=0, dtype=_lib.MI355_F32, debug=None):
@@ -791,9 +787,9 @@ class Ops:
         -> dict(kernel, form, tile_m, tile_n)"""
         ch = 16 if dtype == _lib.MI355_F32 else 32
         route = (C.c_int32 * 4)(-1, -1, -1, -1)
-        check(_lib.lib().mi355_conv2d_vjp(None, None, None, None, None, 0, 0, B, Co, Ci, int(c0), int(c1), h, w, k, int(mode), (Co + ch - 1) // ch * ch,
-                                          dtype, C.byref(debug) if debug is not None else None, route, None, 0, None), "mi355_conv2d_vjp")
-        return dict(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3])
+        check(_lib.lib().mi355_conv2d_vjp(None, None, None, None, None, 0, 0, B, Co, Ci, int(c0), int(c1), h, w, k, int(mode), (Co + ch - 1) // ch * ch, dtype,
+                                          _debug_ptr(debug, False), route, None, 0, None), "mi355_conv2d_vjp")
+        return _route_dict(route)
 
     def conv2d_fwd(self, x, weight, bias=None, stride=1, resample=0, pro=None, pro_silu=False, dtype=_lib.MI355_F32, x1=None, emb=None, res=None,
                    res_mode=1, nchw_src=False, axpy_x=None, axpy_scale=0.0, debug=None, ws_fill=None, info=None):
@@ -810,38 +806,26 @@ class Ops:
             raise ValueError(f"weight has {Ci} input channels, the sources {Cin} + {Cin1}")
         if x1 is not None and (x1.shape[0] != B or x1.shape[2:] != x.shape[2:]):
             raise ValueError("x1 must match x in batch and spatial size")
-        Hc, Wc = (2 * H, 2 * W) if resample == 2 else (H, W)
-        Ho = (Hc + 2 * (k // 2) - k) // stride + 1
-        Wo = (Wc + 2 * (k // 2) - k) // stride + 1
+        Ho, Wo = _conv_out_size(H, W, k, stride, 2 if resample == 2 else 0)
         if pro is not None and (tuple(pro[0].shape) != (B, Ci) or tuple(pro[1].shape) != (B, Ci)):
             raise ValueError(f"pro = (a, b) must both be {(B, Ci)}")
-        if emb is not None and tuple(emb.shape) != (B, Co):
-            raise ValueError("emb must be [B, Co]")
-        if res is not None:
-            want = (B, Co, Ho, Wo) if res_mode == 1 else (B, Co, Ho // 2, Wo // 2)
-            if tuple(res.shape) != want:
-                raise ValueError(f"res must be {want}")
+        _check_emb_res(emb, res, res_mode, B, Co, Ho, Wo)
         if axpy_x is not None and tuple(axpy_x.shape) != (B, Co, Ho, Wo):
             raise ValueError(f"axpy_x must be {(B, Co, Ho, Wo)}")
         dev = x.device
         y = torch.full((B, Co, Ho, Wo), float("nan"), device=dev)
         xu = axpy_x.clone() if axpy_x is not None else None
         L = _lib.lib()
-        wsb = L.mi355_op_workspace_bytes(B, max(Ci, Co), max(H * W, Ho * Wo))
-        ws = torch.empty(wsb, device=dev, dtype=torch.uint8) if ws_fill is None else torch.full((wsb,), int(ws_fill), device=dev, dtype=torch.uint8)
-        wh = weight.detach().to("cpu", torch.float32).contiguous()
-        bh = bias.detach().to("cpu", torch.float32).contiguous() if bias is not None else None
-        fp = C.POINTER(C.c_float)
+        ws, wsp, wsb = _workspace(L, B, max(Ci, Co), max(H * W, Ho * Wo), dev, ws_fill)
+        (wh, whp), (bh, bhp) = _host(weight), _host(bias)
+        pro_a, pro_b = pro if pro else (None, None)
         route = (C.c_int32 * 8)(*([-1] * 8))
-        check(L.mi355_conv2d_fwd(_req(x, "x"), _req(x1, "x1") if x1 is not None else None, Cin1, C.cast(wh.data_ptr(), fp),
-                                 C.cast(bh.data_ptr(), fp) if bh is not None else None, _req(y, "y"), B, Cin, H, W, Co, k, int(stride), int(resample),
-                                 _req(pro[0], "pro_a") if pro else None, _req(pro[1], "pro_b") if pro else None, int(bool(pro_silu)),
-                                 _req(emb, "emb") if emb is not None else None, _req(res, "res") if res is not None else None, int(res_mode),
-                                 int(bool(nchw_src)), _req(xu, "axpy_x") if xu is not None else None, float(axpy_scale), dtype,
-                                 C.byref(debug) if debug is not None else None, route, C.c_void_p(ws.data_ptr()), wsb, _stream()), "mi355_conv2d_fwd")
+        check(L.mi355_conv2d_fwd(_req(x, "x"), _opt(x1, "x1"), Cin1, whp, bhp, _req(y, "y"), B, Cin, H, W, Co, k, int(stride), int(resample),
+                                 _opt(pro_a, "pro_a"), _opt(pro_b, "pro_b"), int(bool(pro_silu)), _opt(emb, "emb"), _opt(res, "res"), int(res_mode),
+                                 int(bool(nchw_src)), _opt(xu, "axpy_x"), float(axpy_scale), dtype, _debug_ptr(debug, False), route, wsp, wsb, _stream()),
+              "mi355_conv2d_fwd")
         if info is not None:
-            info.update(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3], reads_nchw=route[4], axpy=route[5], ksplit=route[6], n_mt=route[7],
-                        y=y, axpy_x=xu)
+            info.update(_route_dict(route), y=y, axpy_x=xu)
         return xu if route[5] == 1 else y
 
     def conv2d_fwd_route(self, B, Cin, Co, h, w, k, stride=1, resample=0, Cin1=0, bias=True, pro=False, pro_silu=False, emb=False, res_mode=0,
@@ -849,13 +833,12 @@ class Ops:
         """What conv_route decides for the forward conv conv2d_fwd would launch for these sizes and optional parts (res_mode 0: no residual): host
         code, nothing is launched (no GPU needed).  -> dict(kernel, form, tile_m, tile_n, reads_nchw, axpy, ksplit, n_mt)"""
         some = C.c_void_p(256)   # stands for "present": the route query reads no pointer
-        fp = C.POINTER(C.c_float)
         route = (C.c_int32 * 8)(*([-1] * 8))
-        check(_lib.lib().mi355_conv2d_fwd(None, None, int(Cin1), None, C.cast(some, fp) if bias else None, None, B, Cin, h, w, Co, k, int(stride),
-                                          int(resample), some if pro else None, some if pro else None, int(bool(pro_silu)), some if emb else None,
-                                          some if res_mode else None, int(res_mode) if res_mode else 1, int(bool(nchw_src)), some if axpy else None,
-                                          0.0, dtype, C.byref(debug) if debug is not None else None, route, None, 0, None), "mi355_conv2d_fwd")
-        return dict(kernel=route[0], form=route[1], tile_m=route[2], tile_n=route[3], reads_nchw=route[4], axpy=route[5], ksplit=route[6], n_mt=route[7])
+        check(_lib.lib().mi355_conv2d_fwd(None, None, int(Cin1), None, C.cast(some, C.POINTER(C.c_float)) if bias else None, None, B, Cin, h, w, Co, k,
+                                          int(stride), int(resample), some if pro else None, some if pro else None, int(bool(pro_silu)), some if emb else None,
+                                          some if res_mode else None, int(res_mode) if res_mode else 1, int(bool(nchw_src)), some if axpy else None, 0.0, dtype,
+                                          _debug_ptr(debug, False), route, None, 0, None), "mi355_conv2d_fwd")
+        return _route_dict(route)
 
     # --- the embedding path and the layout kernels, one op each (see include/mi355_sampler.h); these ops synchronise the stream ---
     ELEM = {_lib.MI355_F32: torch.float32, _lib.MI355_BF16: torch.bfloat16, _lib.MI355_BF16X2: torch.bfloat16, _lib.MI355_F16: torch.float16}
@@ -874,8 +857,8 @@ class Ops:
         elif out.dim() != 2 or out.shape[0] < B or out.shape[1] != J:
             raise ValueError(f"out must be [>= {B}, {J}]")
         form = C.c_int32(-1)
-        check(_lib.lib().mi355_linear(_req(x, "x"), _req(wt, "wt"), _req(bias, "bias") if bias is not None else None, _req(out, "out"), B, K, J,
-                                      int(bool(in_act)), int(bool(out_act)), C.byref(form), _stream()), "mi355_linear")
+        check(_lib.lib().mi355_linear(_req(x, "x"), _req(wt, "wt"), _opt(bias, "bias"), _req(out, "out"), B, K, J, int(bool(in_act)), int(bool(out_act)),
+                                      C.byref(form), _stream()), "mi355_linear")
         return out, form.value
 
     def label_emb_linear(self, h, lemb, wt, bias, rows, h_div, labels=None, out=None):
@@ -896,9 +879,9 @@ class Ops:
         elif out.dim() != 2 or out.shape[0] < rows or out.shape[1] != J:
             raise ValueError(f"out must be [>= {rows}, {J}]")
         err, form = C.c_int32(-1), C.c_int32(-1)
-        check(_lib.lib().mi355_label_emb_linear(_req(h, "h"), int(h_div), _req(lemb, "lemb"), _req(labels, "labels", torch.int32) if labels is not None else None,
-                                                n_classes, _req(wt, "wt"), _req(bias, "bias") if bias is not None else None, _req(out, "out"), int(rows), K, J,
-                                                C.byref(err), C.byref(form), _stream()), "mi355_label_emb_linear")
+        check(_lib.lib().mi355_label_emb_linear(_req(h, "h"), int(h_div), _req(lemb, "lemb"), _opt(labels, "labels", torch.int32), n_classes, _req(wt, "wt"),
+                                                _opt(bias, "bias"), _req(out, "out"), int(rows), K, J, C.byref(err), C.byref(form), _stream()),
+              "mi355_label_emb_linear")
         return out, err.value, form.value
 
     def emb_gather(self, table, labels, out=None):
@@ -926,8 +909,8 @@ class Ops:
         V = 4 if dtype == _lib.MI355_F32 else 8
         cpad = (Cx + Cc + V - 1) // V * V if cpad is None else int(cpad)
         out = torch.full((B, hw, cpad), float("nan"), device=x.device, dtype=self.ELEM[dtype])
-        check(_lib.lib().mi355_pack_nhwc(_req(x, "x"), Cx, _req(cond, "cond") if cond is not None else None, Cc, B, hw, cpad,
-                                         _req(out, "out", self.ELEM[dtype]), dtype, _stream()), "mi355_pack_nhwc")
+        check(_lib.lib().mi355_pack_nhwc(_req(x, "x"), Cx, _opt(cond, "cond"), Cc, B, hw, cpad, _req(out, "out", self.ELEM[dtype]), dtype, _stream()),
+              "mi355_pack_nhwc")
         return out
 
     def unpack_nchw(self, t, dtype=_lib.MI355_F32):
