@@ -16,7 +16,9 @@
 // the current one and written to the other buffer after the tile's MFMAs, so there is ONE barrier per key tile and the
 // load latency hides behind the compute.  Head sizes up to 512 channels (torchcfm's default single head at 384 / 512
 // channels, mnist/train_mnist_hy.py:312-318) use 32-key tiles (and, in fp32, a single buffer) to stay inside 160 KB.
+// The fragment loops, the softmax, the transposed read, the store and the staging rule are attn_core.h's.
 #include "ops.h"
+#include "attn_core.h"
 
 namespace {
 
@@ -26,8 +28,6 @@ struct AttnKArgs {
   int qoff_h, koff, voff;  // channel offsets: q of head h at h*qoff_h, k at koff + h*qoff_h, v at voff + h*qoff_h
   float scale2;
 };
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // Register budget: with a 512-register budget (one workgroup per CU) the compiler puts the MFMA accumulators into AccVGPRs, and the
 // softmax / rescale between the two GEMMs then costs a v_accvgpr_read or _write per accumulator register and key tile (192 of them
@@ -40,14 +40,12 @@ template <typename T, int CH, int QB, int KT, int NBUF>
 __global__ void __launch_bounds__(256, (attn_min_blocks<T, CH, QB>())) attention_kernel(AttnKArgs p) {
   using E = Elem<T>;
   constexpr int V = E::VEC, CHUNK = E::CHUNK, SZ = sizeof(T);
-  constexpr bool BF = E::DTYPE == 1;
   constexpr int KST = CH / CHUNK;           // k-steps over channels for S^T
   constexpr int CI = CH / 16;               // 16-channel row tiles of O^T
   constexpr int MT = KT / 16;               // 16-key row tiles of S^T per key tile
   constexpr int ROW = CH * SZ + 32;         // K / V tile row stride (bytes)
   constexpr int TILE = KT * ROW;            // bytes of one K (or V) tile
-  constexpr int FPR = CH / V;               // 16-B fragments per row
-  constexpr int NF = (KT * FPR + 255) / 256;   // fragments per thread per tile (K and V each)
+  constexpr int NF = attn_stage_frags<T, CH, KT>();   // 16-B fragments per thread per tile (K and V each)
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [NBUF][K tile | V tile]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -86,7 +84,10 @@ __global__ void __launch_bounds__(256, (attn_min_blocks<T, CH, QB>())) attention
     for (int ci = 0; ci < CI; ++ci) o[qb][ci] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  // ---- staging: thread owns fragments e = tid + 256 u of a tile (row e / FPR, 16-B slot e % FPR), K and V alike ----
+  // ---- staging: thread owns fragments e = tid + 256 u of a tile (row e / FPR, 16-B slot e % FPR), K and V alike; loads and LDS writes
+  //      apart.  The load half is attn_stage_rows_load's rule in this kernel's own text: on the shared form attention_kernel<float, 512, 1,
+  //      32, 1>, which sits at the 512-register limit, spills 16 registers instead of 12 (profiles/attn_core_parity.md) ----
+  constexpr int FPR = CH / V;               // 16-B fragments per row
   u32x4 kreg[NF], vreg[NF];
   auto load_tile = [&](int kt) {
 #pragma unroll
@@ -101,26 +102,9 @@ __global__ void __launch_bounds__(256, (attn_min_blocks<T, CH, QB>())) attention
       }
     }
   };
-  auto store_tile = [&](int buf) {
-    char* kb = smem + buf * (2 * TILE);
-#pragma unroll
-    for (int u = 0; u < NF; ++u) {
-      const int e = tid + 256 * u, s = e / FPR, f = e - s * FPR;
-      if (e < KT * FPR) {
-        *reinterpret_cast<u32x4*>(kb + s * ROW + f * 16) = kreg[u];
-        *reinterpret_cast<u32x4*>(kb + TILE + s * ROW + f * 16) = vreg[u];
-      }
-    }
-  };
+  auto store_tile = [&](int buf) { attn_stage_rows_store<T, CH, KT>(smem + buf * (2 * TILE), smem + buf * (2 * TILE) + TILE, kreg, vreg, tid); };
 
   const int ntiles = (p.T + KT - 1) / KT;
-  // the column maximum over the four lanes that share a query: two VALU row swaps instead of two LDS round trips
-  auto colmax = [&](float v) {
-    const auto s16 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(uint32_t, v), __builtin_bit_cast(uint32_t, v), false, false);
-    v = fmaxf(__builtin_bit_cast(float, (uint32_t)s16[0]), __builtin_bit_cast(float, (uint32_t)s16[1]));
-    const auto s32 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, v), __builtin_bit_cast(uint32_t, v), false, false);
-    return fmaxf(__builtin_bit_cast(float, (uint32_t)s32[0]), __builtin_bit_cast(float, (uint32_t)s32[1]));
-  };
   load_tile(0);
   store_tile(0);
   for (int kt = 0; kt < ntiles; ++kt) {
@@ -136,18 +120,8 @@ __global__ void __launch_bounds__(256, (attn_min_blocks<T, CH, QB>())) attention
     for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
       for (int mi = 0; mi < MT; ++mi) sacc[qb][mi] = f32x4{-m_run[qb], -m_run[qb], -m_run[qb], -m_run[qb]};   // the column's reference offset
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-      for (int ks = 0; ks < KST; ++ks) {
-        const u32x4 kf = *reinterpret_cast<const u32x4*>(klds + (mi * 16 + lr) * ROW + (ks * 4 + lq) * 16);
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) mma16(sacc[qb][mi], kf, qf[qb][ks], T());
-      }
-    // ---- online softmax over keys (column = query = lane&15; rows spread over regs and lane>>4), in the log2 domain: the accumulators
-    //      hold s - m_ref, so p = exp2(sacc) (max, exp2, add per element).  The reference offset of a column moves only when a tile's
-    //      maximum exceeds it by more than 8 (p <= 2^8): then the tile is shifted and O / l rescaled on a wave-uniform slow path; the
-    //      first tile always takes it (its offset becomes the tile maximum, whatever its sign) ----
+    attn_scores<T, ROW, MT, KST, QB>(sacc, klds, qf, lr, lq);
+    // ---- online softmax over keys (column = query = lane&15; rows spread over regs and lane>>4), offset-in-accumulator form ----
     if ((kt + 1) * KT > p.T) {              // only a ragged last tile has keys to mask (wave-uniform)
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb)
@@ -157,77 +131,9 @@ __global__ void __launch_bounds__(256, (attn_min_blocks<T, CH, QB>())) attention
           for (int r = 0; r < 4; ++r)
             if (kt * KT + mi * 16 + lq * 4 + r >= p.T) sacc[qb][mi][r] = -INFINITY;
     }
-    const bool first = kt == 0;
 #pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sacc[qb][mi][r]);
-      mx = colmax(mx);
-      const float delta = first ? mx : (mx > 8.0f ? mx : 0.0f);
-      if (first || __builtin_amdgcn_ballot_w64(delta != 0.0f) != 0) {
-        const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);
-        m_run[qb] += delta;
-        l_run[qb] *= alpha;
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) sacc[qb][mi][r] -= delta;
-#pragma unroll
-        for (int ci = 0; ci < CI; ++ci)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[qb][ci][r] *= alpha;
-      }
-      float psum = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = __builtin_amdgcn_exp2f(sacc[qb][mi][r]);
-          sacc[qb][mi][r] = pv;
-          psum += pv;
-        }
-      l_run[qb] += psum;
-    }
-
-    // ---- O^T += V^T P^T ----
-    if constexpr (BF) {
-#pragma unroll
-      for (int s2 = 0; s2 < MT / 2; ++s2) {  // 32 keys per MFMA: keys 32 s2 + 4 lq + {0..3} and + 16
-        u32x4 pfrag[QB];
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) {
-          const u32x2 p0 = pack4(sacc[qb][2 * s2], T()), p1 = pack4(sacc[qb][2 * s2 + 1], T());
-          pfrag[qb] = u32x4{p0[0], p0[1], p1[0], p1[1]};
-        }
-        // transposed read: lane 4q + p of a 16-lane group addresses row q, columns 4p .. 4p+3 of a 4-key x 16-channel block and
-        // receives column (lane & 15) of its 4 rows = V^T[channel 16 ci + lr][4 consecutive keys]  (EXEC is all ones here)
-        const char* vrow = vlds + (32 * s2 + 4 * lq + (lr >> 2)) * ROW + 8 * (lr & 3);
-#pragma unroll
-        for (int ci = 0; ci < CI; ++ci) {
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vrow + ci * 32));
-          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vrow + 16 * ROW + ci * 32));
-          const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-          const u32x4 vf = u32x4{l2[0], l2[1], h2[0], h2[1]};
-#pragma unroll
-          for (int qb = 0; qb < QB; ++qb) mma16(o[qb][ci], vf, pfrag[qb], T());
-        }
-      }
-    } else {
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi) {  // 16 keys per fragment pair: MFMA r of mma16 multiplies key 16 mi + 4 lq + r
-#pragma unroll
-        for (int ci = 0; ci < CI; ++ci) {
-          const char* vp = vlds + (16 * mi + 4 * lq) * ROW + (16 * ci + lr) * 4;
-          const u32x4 vf = u32x4{*reinterpret_cast<const uint32_t*>(vp), *reinterpret_cast<const uint32_t*>(vp + ROW),
-                                 *reinterpret_cast<const uint32_t*>(vp + 2 * ROW), *reinterpret_cast<const uint32_t*>(vp + 3 * ROW)};
-#pragma unroll
-          for (int qb = 0; qb < QB; ++qb) mma16(o[qb][ci], vf, __builtin_bit_cast(u32x4, sacc[qb][mi]), T());
-        }
-      }
-    }
+    for (int qb = 0; qb < QB; ++qb) attn_softmax_offset<MT, CI>(sacc[qb], o[qb], m_run[qb], l_run[qb], kt == 0);
+    attn_pv<T, ROW, MT, CI, QB>(o, sacc, vlds, lr, lq);   // O^T += V^T P^T
     if (kt + 1 < ntiles) {
       if (NBUF == 2) store_tile((kt + 1) & 1);   // the other buffer: last read during tile kt - 1, before this tile's barrier
       else { __syncthreads(); load_tile(kt + 1); store_tile(0); }
@@ -236,23 +142,8 @@ __global__ void __launch_bounds__(256, (attn_min_blocks<T, CH, QB>())) attention
   // ---- normalise and store: lane holds channels ci*16 + 4*lq + r of query q0 + 16 qb + lr ----
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
-    float l = l_run[qb];
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-    const float inv = 1.0f / l;
     const int q = q0 + 16 * qb + lr;
-    if (q < p.T) {
-      T* op = reinterpret_cast<T*>(p.out) + ((size_t)n * p.T + q) * p.C + h * CH;
-#pragma unroll
-      for (int ci = 0; ci < CI; ++ci) {
-        T* dst = op + ci * 16 + 4 * lq;
-        if constexpr (!BF) {
-          *reinterpret_cast<f32x4*>(dst) = f32x4{o[qb][ci][0] * inv, o[qb][ci][1] * inv, o[qb][ci][2] * inv, o[qb][ci][3] * inv};
-        } else {
-          *reinterpret_cast<u32x2*>(dst) = pack4(f32x4{o[qb][ci][0] * inv, o[qb][ci][1] * inv, o[qb][ci][2] * inv, o[qb][ci][3] * inv}, T());
-        }
-      }
-    }
+    attn_store_normalised<T, CI>(reinterpret_cast<T*>(p.out) + ((size_t)n * p.T + q) * p.C + h * CH, q < p.T, o[qb], l_run[qb], lq);
   }
 }
 
@@ -292,9 +183,8 @@ int launch_attn(const AttnKArgs& a, int ch, hipStream_t s) {
 int attention_launch(const AttnDesc& d, hipStream_t stream) {
   AttnKArgs a;
   a.qkv = d.qkv; a.out = d.out; a.N = d.N; a.T = d.T; a.heads = d.heads; a.C = d.heads * d.ch;
-  if (d.new_order) { a.qoff_h = d.ch; a.koff = a.C; a.voff = 2 * a.C; }
-  else { a.qoff_h = 3 * d.ch; a.koff = d.ch; a.voff = 2 * d.ch; }
-  a.scale2 = 1.0f / sqrtf((float)d.ch);
+  const AttnChannelOffsets co = attn_channel_offsets(d.new_order, d.ch, a.C);
+  a.qoff_h = co.qoff_h; a.koff = co.koff; a.voff = co.voff; a.scale2 = co.scale2;
   int rc = dispatch_dtype(d.dtype, [&](auto t) { return launch_attn<decltype(t)>(a, d.ch, stream); });
   if (rc) return rc;
   MI355_CHECK_HIP(hipGetLastError());

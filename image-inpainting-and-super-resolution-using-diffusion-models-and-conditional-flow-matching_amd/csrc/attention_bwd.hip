@@ -9,7 +9,10 @@
 //                     dK^T += Q^T dS - the accumulator tiles are the next MFMA's B operand as they stand (their rows, the
 //                     queries, are the summed index), Q^T / dA^T come through the transposed LDS read.
 // qkv / dqkv: NHWC [N][T][3C] in the reference's channel order; a, da: [N][T][C]; L, D: fp32 [N * heads][T].
+// The fragment loops, the transposed operand read, the accumulator pack, the gradient stores and the tile staging are attn_core.h's; its
+// primitives take QB column blocks per wave, these kernels have one: the [1] of their fragment and accumulator arrays.
 #include "ops.h"
+#include "attn_core.h"
 
 namespace {
 
@@ -20,37 +23,6 @@ struct AttnBwdArgs {
   int qoff_h, koff, voff;
   float scale2;
 };
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-// A^T-operand fragment of a row-major LDS tile ([row][channel], row stride ROW bytes): channels 16 ci + (lane & 15) as MFMA rows,
-// 8 (bf16) / 4 (fp32) tile rows as the k index, in the k order of the B fragments built from two accumulator tiles
-// (bf16: rows r0 + 4 lq + {0..3} and r0 + 16 + 4 lq + {0..3}; fp32: rows r0 + 4 lq + {0..3})
-template <typename T, int ROW>
-__device__ __forceinline__ u32x4 tr_frag(const char* tile, int r0, int ci, int lr, int lq) {
-  if constexpr (Elem<T>::DTYPE == 1) {
-    const char* vrow = tile + (r0 + 4 * lq + (lr >> 2)) * ROW + 8 * (lr & 3) + ci * 32;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vrow));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vrow + 16 * ROW));
-    const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-    return u32x4{l2[0], l2[1], h2[0], h2[1]};
-  } else {
-    const char* vp = tile + (r0 + 4 * lq) * ROW + (16 * ci + lr) * 4;
-    return u32x4{*reinterpret_cast<const uint32_t*>(vp), *reinterpret_cast<const uint32_t*>(vp + ROW),
-                 *reinterpret_cast<const uint32_t*>(vp + 2 * ROW), *reinterpret_cast<const uint32_t*>(vp + 3 * ROW)};
-  }
-}
-// B fragment (k = the accumulator tiles' row index) from one (fp32) or two (bf16) 16x16 accumulator tiles
-template <typename T>
-__device__ __forceinline__ u32x4 acc_frag(const f32x4& t0, const f32x4& t1) {
-  if constexpr (Elem<T>::DTYPE == 1) {
-    bf16x8 pb;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { pb[r] = (bf16)t0[r]; pb[4 + r] = (bf16)t1[r]; }
-    return __builtin_bit_cast(u32x4, pb);
-  } else {
-    return __builtin_bit_cast(u32x4, t0);
-  }
-}
 
 // Register budget as in attention.hip (attn_min_blocks): two workgroups per CU = a 256-register budget = MFMAs in their VGPR form, no
 // v_accvgpr copies around the softmax; the head sizes whose live set needs more keep the full budget.
@@ -62,9 +34,8 @@ template <typename T, int CH>
 __global__ void __launch_bounds__(256, (bwd_q_min_blocks<T, CH>())) attention_bwd_q_kernel(AttnBwdArgs p) {
   using E = Elem<T>;
   constexpr int V = E::VEC, CHUNK = E::CHUNK, SZ = sizeof(T);
-  constexpr bool BF = E::DTYPE == 1;
   constexpr int KST = CH / CHUNK, CI = CH / 16, KT = 64, MT = 4;
-  constexpr int ROW = CH * SZ + 32, TILE = KT * ROW, FPR = CH / V, NF = (KT * FPR + 255) / 256;
+  constexpr int ROW = CH * SZ + 32, TILE = KT * ROW, NF = attn_stage_frags<T, CH, KT>();
   extern __shared__ __attribute__((aligned(16))) char smem[];   // K tile | V tile
   char* klds = smem; char* vlds = smem + TILE;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -78,17 +49,17 @@ __global__ void __launch_bounds__(256, (bwd_q_min_blocks<T, CH>())) attention_bw
   const T* arow = reinterpret_cast<const T*>(p.a) + ((size_t)n * p.T + (qok ? q : 0)) * p.C + h * CH;
   const T* drow = reinterpret_cast<const T*>(p.da) + ((size_t)n * p.T + (qok ? q : 0)) * p.C + h * CH;
 
-  u32x4 qf[KST], df[KST];
+  u32x4 qf[1][KST], df[1][KST];
   float dsum = 0.f;
 #pragma unroll
   for (int ks = 0; ks < KST; ++ks) {
-    qf[ks] = u32x4{0u, 0u, 0u, 0u}; df[ks] = u32x4{0u, 0u, 0u, 0u};
+    qf[0][ks] = u32x4{0u, 0u, 0u, 0u}; df[0][ks] = u32x4{0u, 0u, 0u, 0u};
     if (qok) {
-      qf[ks] = *reinterpret_cast<const u32x4*>(base + (size_t)q * rs + qc + ks * CHUNK + lq * V);
-      df[ks] = *reinterpret_cast<const u32x4*>(drow + ks * CHUNK + lq * V);
+      qf[0][ks] = *reinterpret_cast<const u32x4*>(base + (size_t)q * rs + qc + ks * CHUNK + lq * V);
+      df[0][ks] = *reinterpret_cast<const u32x4*>(drow + ks * CHUNK + lq * V);
       float fa[V], fd[V];
       frag_to_float(*reinterpret_cast<const u32x4*>(arow + ks * CHUNK + lq * V), fa, T());
-      frag_to_float(df[ks], fd, T());
+      frag_to_float(df[0][ks], fd, T());
 #pragma unroll
       for (int j = 0; j < V; ++j) dsum += fa[j] * fd[j];
     }
@@ -98,47 +69,34 @@ __global__ void __launch_bounds__(256, (bwd_q_min_blocks<T, CH>())) attention_bw
 
   auto stage = [&](int kt) {
     u32x4 kreg[NF], vreg[NF];
-#pragma unroll
-    for (int u = 0; u < NF; ++u) {
-      const int e = tid + 256 * u, s = e / FPR, f = e - s * FPR, key = kt * KT + s;
-      kreg[u] = u32x4{0u, 0u, 0u, 0u}; vreg[u] = u32x4{0u, 0u, 0u, 0u};
-      if (e < KT * FPR && key < p.T) {
-        kreg[u] = *reinterpret_cast<const u32x4*>(base + (size_t)key * rs + kc + f * V);
-        vreg[u] = *reinterpret_cast<const u32x4*>(base + (size_t)key * rs + vc + f * V);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < NF; ++u) {
-      const int e = tid + 256 * u, s = e / FPR, f = e - s * FPR;
-      if (e < KT * FPR) { *reinterpret_cast<u32x4*>(klds + s * ROW + f * 16) = kreg[u]; *reinterpret_cast<u32x4*>(vlds + s * ROW + f * 16) = vreg[u]; }
-    }
+    attn_stage_rows_load<T, CH, KT>(kreg, vreg, base + kc, rs, base + vc, rs, kt * KT, p.T, tid);
+    attn_stage_rows_store<T, CH, KT>(klds, vlds, kreg, vreg, tid);
   };
-  auto scores = [&](int kt, f32x4 (&sacc)[MT]) {   // S^T tile (raw q.k), -inf on keys past the end
+  auto scores = [&](int kt, f32x4 (&sacc)[1][MT]) {   // S^T tile (raw q.k), -inf on keys past the end
 #pragma unroll
-    for (int mi = 0; mi < MT; ++mi) {
-      sacc[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int mi = 0; mi < MT; ++mi) sacc[0][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+    attn_scores<T, ROW, MT, KST, 1>(sacc, klds, qf, lr, lq);
 #pragma unroll
-      for (int ks = 0; ks < KST; ++ks)
-        mma16(sacc[mi], *reinterpret_cast<const u32x4*>(klds + (mi * 16 + lr) * ROW + (ks * 4 + lq) * 16), qf[ks], T());
+    for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) if (kt * KT + mi * 16 + lq * 4 + r >= p.T) sacc[mi][r] = -INFINITY;
-    }
+      for (int r = 0; r < 4; ++r) if (kt * KT + mi * 16 + lq * 4 + r >= p.T) sacc[0][mi][r] = -INFINITY;
   };
   const int ntiles = (p.T + KT - 1) / KT;
   const float c2 = p.scale2 * 1.4426950408889634f;
-  // ---- pass 1: softmax statistics ----
+  // ---- pass 1: softmax statistics.  Its own form, not attn_softmax_offset: there is no O to rescale and q is unscaled here (pass 2 and the
+  //      second kernel need the raw S for exp2(S c2 - L)), so the statistics are the classic running (max, sum) with m_run = -inf ----
   float m_run = -INFINITY, l_run = 0.f;
   for (int kt = 0; kt < ntiles; ++kt) {
     __syncthreads();
     stage(kt);
     __syncthreads();
-    f32x4 sacc[MT];
+    f32x4 sacc[1][MT];
     scores(kt, sacc);
     float mx = -INFINITY;
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sacc[mi][r]);
+      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sacc[0][mi][r]);
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));
     const float m_new = fmaxf(m_run, mx * c2);
@@ -146,7 +104,7 @@ __global__ void __launch_bounds__(256, (bwd_q_min_blocks<T, CH>())) attention_bw
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) psum += __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[mi][r], c2, -m_new));
+      for (int r = 0; r < 4; ++r) psum += __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[0][mi][r], c2, -m_new));
     l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_new) + psum;
     m_run = m_new;
   }
@@ -155,43 +113,28 @@ __global__ void __launch_bounds__(256, (bwd_q_min_blocks<T, CH>())) attention_bw
   const float Lq = m_run + log2f(l_run);
   if (qok && lq == 0) { p.L[(size_t)blockIdx.y * p.T + q] = Lq; p.D[(size_t)blockIdx.y * p.T + q] = dsum; }
   // ---- pass 2: dQ^T += K^T dS^T ----
-  f32x4 dq[CI];
+  f32x4 dq[1][CI];
 #pragma unroll
-  for (int ci = 0; ci < CI; ++ci) dq[ci] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int ci = 0; ci < CI; ++ci) dq[0][ci] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int kt = 0; kt < ntiles; ++kt) {
     __syncthreads();
     stage(kt);
     __syncthreads();
-    f32x4 sacc[MT], dp[MT];
+    f32x4 sacc[1][MT], dp[1][MT];
     scores(kt, sacc);
 #pragma unroll
-    for (int mi = 0; mi < MT; ++mi) {
-      dp[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int mi = 0; mi < MT; ++mi) dp[0][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+    attn_scores<T, ROW, MT, KST, 1>(dp, vlds, df, lr, lq);   // dP^T = V dA^T
 #pragma unroll
-      for (int ks = 0; ks < KST; ++ks)
-        mma16(dp[mi], *reinterpret_cast<const u32x4*>(vlds + (mi * 16 + lr) * ROW + (ks * 4 + lq) * 16), df[ks], T());   // dP^T = V dA^T
+    for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[mi][r], c2, -Lq));   // 0 on masked keys
-        sacc[mi][r] = pr * (dp[mi][r] - dsum) * p.scale2;                                  // dS^T (the S scale folded in)
+        const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[0][mi][r], c2, -Lq));   // 0 on masked keys
+        sacc[0][mi][r] = pr * (dp[0][mi][r] - dsum) * p.scale2;                              // dS^T (the S scale folded in)
       }
-    }
-#pragma unroll
-    for (int s2 = 0; s2 < (BF ? MT / 2 : MT); ++s2) {
-      const u32x4 sf = BF ? acc_frag<T>(sacc[2 * s2], sacc[2 * s2 + 1]) : acc_frag<T>(sacc[s2], sacc[s2]);
-#pragma unroll
-      for (int ci = 0; ci < CI; ++ci) mma16(dq[ci], tr_frag<T, ROW>(klds, (BF ? 32 : 16) * s2, ci, lr, lq), sf, T());
-    }
+    attn_pv<T, ROW, MT, CI, 1>(dq, sacc, klds, lr, lq);
   }
-  if (qok) {
-    T* op = reinterpret_cast<T*>(p.dqkv) + ((size_t)n * p.T + q) * rs + qc;
-#pragma unroll
-    for (int ci = 0; ci < CI; ++ci) {
-      float o4[4] = {dq[ci][0], dq[ci][1], dq[ci][2], dq[ci][3]};
-      if constexpr (!BF) *reinterpret_cast<f32x4*>(op + ci * 16 + 4 * lq) = f32x4{o4[0], o4[1], o4[2], o4[3]};
-      else { bf16x4 t; for (int r = 0; r < 4; ++r) t[r] = (bf16)o4[r]; *reinterpret_cast<bf16x4*>(op + ci * 16 + 4 * lq) = t; }
-    }
-  }
+  if (qok) attn_store_quads<T, CI>(reinterpret_cast<T*>(p.dqkv) + ((size_t)n * p.T + q) * rs + qc, dq[0], 1.0f, lq);
 }
 
 // ---- dK, dV -------------------------------------------------------------------------------------------------------------------------
@@ -199,7 +142,6 @@ template <typename T, int CH>
 __global__ void __launch_bounds__(256, (bwd_kv_min_blocks<T, CH>())) attention_bwd_kv_kernel(AttnBwdArgs p) {
   using E = Elem<T>;
   constexpr int V = E::VEC, CHUNK = E::CHUNK, SZ = sizeof(T);
-  constexpr bool BF = E::DTYPE == 1;
   constexpr int KST = CH / CHUNK, CI = CH / 16, QT = 64, MT = 4;
   constexpr int ROW = CH * SZ + 32, TILE = QT * ROW, FPR = CH / V, NF = (QT * FPR + 255) / 256;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // Q tile | dA tile | L[64] | D[64]
@@ -214,23 +156,25 @@ __global__ void __launch_bounds__(256, (bwd_kv_min_blocks<T, CH>())) attention_b
   const T* base = reinterpret_cast<const T*>(p.qkv) + (size_t)n * p.T * rs;
   const T* dab = reinterpret_cast<const T*>(p.da) + (size_t)n * p.T * p.C + h * CH;
   const int qc = h * p.qoff_h, kc = p.koff + h * p.qoff_h, vc = p.voff + h * p.qoff_h;
-  u32x4 kf[KST], vf[KST];
+  u32x4 kf[1][KST], vf[1][KST];
 #pragma unroll
   for (int ks = 0; ks < KST; ++ks) {
-    kf[ks] = u32x4{0u, 0u, 0u, 0u}; vf[ks] = u32x4{0u, 0u, 0u, 0u};
+    kf[0][ks] = u32x4{0u, 0u, 0u, 0u}; vf[0][ks] = u32x4{0u, 0u, 0u, 0u};
     if (kok) {
-      kf[ks] = *reinterpret_cast<const u32x4*>(base + (size_t)key * rs + kc + ks * CHUNK + lq * V);
-      vf[ks] = *reinterpret_cast<const u32x4*>(base + (size_t)key * rs + vc + ks * CHUNK + lq * V);
+      kf[0][ks] = *reinterpret_cast<const u32x4*>(base + (size_t)key * rs + kc + ks * CHUNK + lq * V);
+      vf[0][ks] = *reinterpret_cast<const u32x4*>(base + (size_t)key * rs + vc + ks * CHUNK + lq * V);
     }
   }
-  f32x4 dk[CI], dv[CI];
+  f32x4 dk[1][CI], dv[1][CI];
 #pragma unroll
-  for (int ci = 0; ci < CI; ++ci) { dk[ci] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[ci] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (int ci = 0; ci < CI; ++ci) { dk[0][ci] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[0][ci] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   const float c2 = p.scale2 * 1.4426950408889634f;
   const int ntiles = (p.T + QT - 1) / QT;
   for (int qt = 0; qt < ntiles; ++qt) {
     __syncthreads();
-    {   // stage the query tile: Q and dA rows (zero past the end), L (+inf past the end: P = 0) and D
+    {   // stage the query tile: Q and dA rows (zero past the end), L (+inf past the end: P = 0) and D.  attn_stage_rows' rule in this kernel's
+        // own text: attention_bwd_kv_kernel<float, 256> sits at the 512-register limit and spills 23 registers on the shared form, 18 at
+        // the parent, 6 like this (profiles/attn_core_parity.md)
       u32x4 qreg[NF], dreg[NF];
 #pragma unroll
       for (int u = 0; u < NF; ++u) {
@@ -254,49 +198,27 @@ __global__ void __launch_bounds__(256, (bwd_kv_min_blocks<T, CH>())) attention_b
     }
     __syncthreads();
     // S = Q K^T and dP = dA V^T: rows = queries (registers / lane >> 4), columns = this wave's keys (lane & 15)
-    f32x4 pt[MT], ds[MT];
+    f32x4 pt[1][MT], ds[1][MT];
 #pragma unroll
-    for (int mi = 0; mi < MT; ++mi) {
-      f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int mi = 0; mi < MT; ++mi) { pt[0][mi] = f32x4{0.f, 0.f, 0.f, 0.f}; ds[0][mi] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    attn_scores<T, ROW, MT, KST, 1>(pt, qlds, kf, lr, lq);
+    attn_scores<T, ROW, MT, KST, 1>(ds, dlds, vf, lr, lq);
 #pragma unroll
-      for (int ks = 0; ks < KST; ++ks) {
-        mma16(s, *reinterpret_cast<const u32x4*>(qlds + (mi * 16 + lr) * ROW + (ks * 4 + lq) * 16), kf[ks], T());
-        mma16(dp, *reinterpret_cast<const u32x4*>(dlds + (mi * 16 + lr) * ROW + (ks * 4 + lq) * 16), vf[ks], T());
-      }
+    for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = mi * 16 + lq * 4 + r;
-        const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c2, -Ll[row]));
-        pt[mi][r] = pr;
-        ds[mi][r] = pr * (dp[r] - Dl[row]) * p.scale2;
+        const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(pt[0][mi][r], c2, -Ll[row]));
+        pt[0][mi][r] = pr;
+        ds[0][mi][r] = pr * (ds[0][mi][r] - Dl[row]) * p.scale2;
       }
-    }
-#pragma unroll
-    for (int s2 = 0; s2 < (BF ? MT / 2 : MT); ++s2) {
-      const u32x4 pf = BF ? acc_frag<T>(pt[2 * s2], pt[2 * s2 + 1]) : acc_frag<T>(pt[s2], pt[s2]);
-      const u32x4 sf = BF ? acc_frag<T>(ds[2 * s2], ds[2 * s2 + 1]) : acc_frag<T>(ds[s2], ds[s2]);
-#pragma unroll
-      for (int ci = 0; ci < CI; ++ci) {
-        mma16(dv[ci], tr_frag<T, ROW>(dlds, (BF ? 32 : 16) * s2, ci, lr, lq), pf, T());   // dV^T += dA^T P
-        mma16(dk[ci], tr_frag<T, ROW>(qlds, (BF ? 32 : 16) * s2, ci, lr, lq), sf, T());   // dK^T += Q^T dS
-      }
-    }
+    attn_pv<T, ROW, MT, CI, 1>(dv, pt, dlds, lr, lq);   // dV^T += dA^T P
+    attn_pv<T, ROW, MT, CI, 1>(dk, ds, qlds, lr, lq);   // dK^T += Q^T dS
   }
   if (kok) {
-    T* okp = reinterpret_cast<T*>(p.dqkv) + ((size_t)n * p.T + key) * rs + kc;
-    T* ovp = reinterpret_cast<T*>(p.dqkv) + ((size_t)n * p.T + key) * rs + vc;
-#pragma unroll
-    for (int ci = 0; ci < CI; ++ci) {
-      if constexpr (!BF) {
-        *reinterpret_cast<f32x4*>(okp + ci * 16 + 4 * lq) = dk[ci];
-        *reinterpret_cast<f32x4*>(ovp + ci * 16 + 4 * lq) = dv[ci];
-      } else {
-        bf16x4 tk, tv;
-        for (int r = 0; r < 4; ++r) { tk[r] = (bf16)dk[ci][r]; tv[r] = (bf16)dv[ci][r]; }
-        *reinterpret_cast<bf16x4*>(okp + ci * 16 + 4 * lq) = tk;
-        *reinterpret_cast<bf16x4*>(ovp + ci * 16 + 4 * lq) = tv;
-      }
-    }
+    T* orow = reinterpret_cast<T*>(p.dqkv) + ((size_t)n * p.T + key) * rs;
+    attn_store_quads<T, CI>(orow + kc, dk[0], 1.0f, lq);
+    attn_store_quads<T, CI>(orow + vc, dv[0], 1.0f, lq);
   }
 }
 
@@ -338,9 +260,8 @@ int attention_bwd_launch(const AttnBwdDesc& d, hipStream_t stream) {
   AttnBwdArgs a;
   a.qkv = d.qkv; a.a = d.a; a.da = d.da; a.dqkv = d.dqkv; a.L = d.L; a.D = d.D;
   a.N = d.N; a.T = d.T; a.heads = d.heads; a.C = d.heads * d.ch;
-  if (d.new_order) { a.qoff_h = d.ch; a.koff = a.C; a.voff = 2 * a.C; }
-  else { a.qoff_h = 3 * d.ch; a.koff = d.ch; a.voff = 2 * d.ch; }
-  a.scale2 = 1.0f / sqrtf((float)d.ch);
+  const AttnChannelOffsets co = attn_channel_offsets(d.new_order, d.ch, a.C);
+  a.qoff_h = co.qoff_h; a.koff = co.koff; a.voff = co.voff; a.scale2 = co.scale2;
   int rc = d.dtype == 0 ? launch_bwd_ch<float>(a, d.ch, stream) : launch_bwd_ch<bf16>(a, d.ch, stream);
   if (rc) return rc;
   MI355_CHECK_HIP(hipGetLastError());

@@ -17,7 +17,9 @@
 // Shapes: head size 64, T = 128 or 256 tokens, C <= 512 (the 16x16 / 8x16 attention levels of every mc = 128 configuration);
 // anything else runs the unfused ops.  The four heads of an image are dispatched 8 workgroups apart (same XCD under the
 // round-robin placement, speed only), so x is fetched into one L2 once.
+// The attention phase's fragment loops, the persistent kernel's softmax and the normalised store are attn_core.h's.
 #include "ops.h"
+#include "attn_core.h"
 
 namespace {
 
@@ -30,14 +32,90 @@ struct AttnFuseArgs {
   float scale2;
 };
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 template <int I> struct IC3 { static constexpr int value = I; };
+
+// ---- pieces the two kernels below share (head size 64, 512 threads) ----
+// row j of head h's 192 q | k | v rows in the [3C] output channels of the qkv conv: legacy = [h*192, h*192 + 192), new = q | k | v blocks of C
+__device__ __forceinline__ int head_row(int new_order, int C, int h, int j) { return new_order ? (j >> 6) * C + h * 64 + (j & 63) : h * 192 + j; }
+
+// Chunks c0 .. c0 + nc of head h's weight rows -> wlds [nc][192 rows][64 B], out of the packed image w (nchunks chunks per row): per chunk,
+// fragment e = tid + 512 u < 768 is (row e >> 2, 16-B slot e & 3); 64-byte rows are copied verbatim (the packed image's XOR swizzle depends
+// on (row >> 1) & 3 only, and every head's row base is a multiple of 8); the per-thread source / destination offsets are chunk-invariant.
+__device__ __forceinline__ void stage_head_weights(char* wlds, const void* w, int nchunks, int c0, int nc, int new_order, int C, int h, int tid) {
+  constexpr int WBUF = 192 * 64;
+  uint32_t wso[2]; int wdo[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int e = tid + 512 * u, j = min(e >> 2, 191), r = head_row(new_order, C, h, j);
+    wso[u] = ((uint32_t)(r >> 7) * nchunks) * 8192u + (uint32_t)(r & 127) * 64u + (e & 3) * 16;
+    wdo[u] = j * 64 + (e & 3) * 16;
+  }
+  const bool second = tid + 512 < 768;
+  const char* wsrc = reinterpret_cast<const char*>(w) + (size_t)c0 * 8192;
+  for (int cl = 0; cl < nc; cl += 4) {   // four chunks in flight per thread (8 x 16 B)
+    u32x4 t[4][2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int cc = min(cl + k, nc - 1);
+      t[k][0] = *reinterpret_cast<const u32x4*>(wsrc + wso[0] + (size_t)cc * 8192);
+      t[k][1] = *reinterpret_cast<const u32x4*>(wsrc + wso[1] + (size_t)cc * 8192);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (cl + k < nc) {
+        *reinterpret_cast<u32x4*>(wlds + (cl + k) * WBUF + wdo[0]) = t[k][0];
+        if (second) *reinterpret_cast<u32x4*>(wlds + (cl + k) * WBUF + wdo[1]) = t[k][1];
+      }
+    }
+  }
+}
+
+// GroupNorm affine a x + b on the QB x fragments of one 64-byte channel chunk (the attention norm has no SiLU, unet.py:379,397):
+// ab = a[C] | b[C], c = the lane's first channel
+template <typename T, int QB>
+__device__ __forceinline__ void gn_affine_frag(u32x4 (&xf)[QB], const u32x4 (&x)[QB], const float* ab, int C, int c) {
+  constexpr int V = Elem<T>::VEC;
+  float av[V], bv[V];
+#pragma unroll
+  for (int j = 0; j < V; j += 4) {
+    const f32x4 a4 = *reinterpret_cast<const f32x4*>(ab + c + j);
+    const f32x4 b4 = *reinterpret_cast<const f32x4*>(ab + C + c + j);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { av[j + k] = a4[k]; bv[j + k] = b4[k]; }
+  }
+#pragma unroll
+  for (int qb = 0; qb < QB; ++qb) {
+    float f[V];
+    frag_to_float(x[qb], f, T());
+#pragma unroll
+    for (int j = 0; j < V; ++j) f[j] = av[j] * f[j] + bv[j];
+    xf[qb] = float_to_frag(f, T());
+  }
+}
+
+// One token's k and v rows -> row `row` of the row-major K and V tiles, from the lane's quads of the four 16-channel row tiles (channels
+// 16 ct + 4 lq + r): Q = u32x2 (two-byte elements, packed: kv_quad) or f32x4.  V is written in the natural [key][channel] order; K in the q
+// fragments' channel order - two-byte: the 16-byte slot (ks, lq) holds tile 2 ks (first 8 bytes) and tile 2 ks + 1 (last 8).
+template <typename T> __device__ __forceinline__ auto kv_quad(const f32x4& v) { if constexpr (sizeof(T) == 2) return pack4(v, T()); else return v; }
+template <int ROW, typename Q>
+__device__ __forceinline__ void write_kv_rows(char* klds, char* vlds, int row, int lq, const Q (&k)[4], const Q (&v)[4]) {
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+    if constexpr (sizeof(Q) == 8) {
+      *reinterpret_cast<u32x2*>(klds + row * ROW + (ct >> 1) * 64 + lq * 16 + (ct & 1) * 8) = k[ct];
+      *reinterpret_cast<u32x2*>(vlds + row * ROW + (16 * ct + 4 * lq) * 2) = v[ct];
+    } else {
+      *reinterpret_cast<f32x4*>(klds + row * ROW + ct * 64 + lq * 16) = k[ct];
+      *reinterpret_cast<f32x4*>(vlds + row * ROW + (16 * ct + 4 * lq) * 4) = v[ct];
+    }
+  }
+}
 
 template <typename T, int QB>
 __global__ void __launch_bounds__(512) attn_fused_kernel(AttnFuseArgs p) {
   using E = Elem<T>;
   constexpr int V = E::VEC, CHUNK = E::CHUNK, SZ = sizeof(T), CH = 64;
-  constexpr bool BF = E::DTYPE == 1;
+  constexpr int FT = attn_frag_tiles<T>();
   constexpr int KST = CH / CHUNK, CI = CH / 16, NCT = 12;   // k-steps of S^T, channel tiles of O^T, 16-row tiles of the head's q|k|v rows
   constexpr int ROW = CH * SZ + 32;                          // K / V row stride in LDS (bytes)
   constexpr int TT = 128 * QB;                               // tokens
@@ -58,9 +136,6 @@ __global__ void __launch_bounds__(512) attn_fused_kernel(AttnFuseArgs p) {
   const T* xb = reinterpret_cast<const T*>(p.x) + (size_t)n * TT * C;
   const int tok0 = wave * (16 * QB);
 
-  // rows of this head in the [3C] output channels of the qkv conv: legacy = [h*192, h*192 + 192), new = q | k | v blocks of C
-  auto grow = [&](int j) { return p.new_order ? (j >> 6) * C + h * CH + (j & 63) : h * (3 * CH) + j; };
-
   // x fragments (B operand): lane holds x[tok0 + 16 qb + lr][c*CHUNK + lq*V .. +V); a ring two chunks deep
   u32x4 xr[3][QB];
   auto load_x = [&](int c, u32x4 (&dst)[QB]) {
@@ -70,36 +145,6 @@ __global__ void __launch_bounds__(512) attn_fused_kernel(AttnFuseArgs p) {
   load_x(0, xr[0]);
   if (p.nchunks > 1) load_x(1, xr[1]);
 
-  // ---- the head's weights are staged stage_chunks chunks at a time: per chunk, fragment e = tid + 512 u < 768 is (row e >> 2, 16-B
-  //      slot e & 3); 64-byte rows are copied verbatim (the packed image's XOR swizzle depends on (row >> 1) & 3 only, and every
-  //      head's row base is a multiple of 8); the per-thread source / destination offsets are chunk-invariant ----
-  uint32_t wso[2]; int wdo[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int e = tid + 512 * u, j = min(e >> 2, 191), r = grow(j);
-    wso[u] = ((uint32_t)(r >> 7) * p.nchunks) * 8192u + (uint32_t)(r & 127) * 64u + (e & 3) * 16;
-    wdo[u] = j * 64 + (e & 3) * 16;
-  }
-  const bool second = tid + 512 < 768;
-  auto stage_weights = [&](int c0, int nc) {
-    const char* wsrc = reinterpret_cast<const char*>(p.w) + (size_t)c0 * 8192;
-    for (int cl = 0; cl < nc; cl += 4) {   // four chunks in flight per thread (8 x 16 B)
-      u32x4 t[4][2];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int cc = min(cl + k, nc - 1);
-        t[k][0] = *reinterpret_cast<const u32x4*>(wsrc + wso[0] + (size_t)cc * 8192);
-        t[k][1] = *reinterpret_cast<const u32x4*>(wsrc + wso[1] + (size_t)cc * 8192);
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (cl + k < nc) {
-          *reinterpret_cast<u32x4*>(wlds + (cl + k) * WBUF + wdo[0]) = t[k][0];
-          if (second) *reinterpret_cast<u32x4*>(wlds + (cl + k) * WBUF + wdo[1]) = t[k][1];
-        }
-      }
-    }
-  };
   for (int c = tid; c < C; c += 512) { ablds[c] = p.ga[(size_t)n * C + c]; ablds[C + c] = p.gb[(size_t)n * C + c]; }
 
   f32x4 acc[NCT][QB];
@@ -113,26 +158,8 @@ __global__ void __launch_bounds__(512) attn_fused_kernel(AttnFuseArgs p) {
   auto chunk = [&](int c, auto slotc) {
     constexpr int slot = decltype(slotc)::value;
     if (c + 2 < p.nchunks) load_x(c + 2, xr[(slot + 2) % 3]);
-    // GroupNorm affine on the x fragments (the attention norm has no SiLU, unet.py:379,397)
     u32x4 xf[QB];
-    {
-      float av[V], bv[V];
-#pragma unroll
-      for (int j = 0; j < V; j += 4) {
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(ablds + c * CHUNK + lq * V + j);
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(ablds + C + c * CHUNK + lq * V + j);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { av[j + k] = a4[k]; bv[j + k] = b4[k]; }
-      }
-#pragma unroll
-      for (int qb = 0; qb < QB; ++qb) {
-        float f[V];
-        frag_to_float(xr[slot][qb], f, T());
-#pragma unroll
-        for (int j = 0; j < V; ++j) f[j] = av[j] * f[j] + bv[j];
-        xf[qb] = float_to_frag(f, T());
-      }
-    }
+    gn_affine_frag<T, QB>(xf, xr[slot], ablds, C, c * CHUNK + lq * V);
     const char* wb = wlds + (c - c0) * WBUF + lr * 64 + 16 * (lq ^ ((lr >> 1) & 3));
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
@@ -145,7 +172,7 @@ __global__ void __launch_bounds__(512) attn_fused_kernel(AttnFuseArgs p) {
   for (c0 = 0; c0 < p.nchunks; c0 += p.stage_chunks) {
     const int nc = min(p.stage_chunks, p.nchunks - c0);
     if (c0 > 0) __syncthreads();           // every wave is done with the previous stage's weights
-    stage_weights(c0, nc);
+    stage_head_weights(wlds, p.w, p.nchunks, c0, nc, p.new_order, C, h, tid);   // stage_chunks chunks of the head's weights at a time
     __syncthreads();                       // this stage's weights (and, first time, the (a, b) table) are staged
     for (int c = c0; c < c0 + nc; c += 3) {
       chunk(c, IC3<0>());
@@ -156,7 +183,7 @@ __global__ void __launch_bounds__(512) attn_fused_kernel(AttnFuseArgs p) {
   // bias of the qkv conv: lane's rows of tile ct are channels ct*16 + 4 lq .. + 3
 #pragma unroll
   for (int ct = 0; ct < NCT; ++ct) {
-    const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.bias + grow(ct * 16 + 4 * lq));
+    const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.bias + head_row(p.new_order, C, h, ct * 16 + 4 * lq));
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
@@ -168,30 +195,15 @@ __global__ void __launch_bounds__(512) attn_fused_kernel(AttnFuseArgs p) {
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
-    for (int ks = 0; ks < KST; ++ks) {
-      if constexpr (BF) {   // 32-channel k-step = tiles 2 ks and 2 ks + 1: elements 0-3 = channels 32 ks + 4 lq + r, 4-7 = + 16
-        const u32x2 t0 = pack4(acc[2 * ks][qb], T()), t1 = pack4(acc[2 * ks + 1][qb], T());
-        qf[qb][ks] = u32x4{t0[0], t0[1], t1[0], t1[1]};
-      } else {
-        qf[qb][ks] = __builtin_bit_cast(u32x4, acc[ks][qb]);
-      }
-    }
+    for (int ks = 0; ks < KST; ++ks)   // two-byte: 32-channel k-step = tiles 2 ks and 2 ks + 1: elements 0-3 = channels 32 ks + 4 lq + r, 4-7 = + 16
+      qf[qb][ks] = attn_acc_frag<T>(acc[FT * ks][qb], acc[FT * ks + FT - 1][qb]);
   __syncthreads();                         // every wave has finished reading the weight buffers K / V are about to overwrite
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
-    const int tok = tok0 + 16 * qb + lr;
+    decltype(kv_quad<T>(acc[0][0])) k4[4], v4[4];
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      const f32x4 kv = acc[4 + ct][qb], vv = acc[8 + ct][qb];
-      if constexpr (BF) {
-        // K: the 16-byte slot (ks, lq) holds tile 2 ks (first 8 bytes) and tile 2 ks + 1 (last 8) = the q fragments' channel order
-        *reinterpret_cast<u32x2*>(klds + tok * ROW + (ct >> 1) * 64 + lq * 16 + (ct & 1) * 8) = pack4(kv, T());
-        *reinterpret_cast<u32x2*>(vlds + tok * ROW + (16 * ct + 4 * lq) * 2) = pack4(vv, T());   // V: natural [key][channel]
-      } else {
-        *reinterpret_cast<f32x4*>(klds + tok * ROW + ct * 64 + lq * 16) = kv;
-        *reinterpret_cast<f32x4*>(vlds + tok * ROW + (16 * ct + 4 * lq) * 4) = vv;
-      }
-    }
+    for (int ct = 0; ct < 4; ++ct) { k4[ct] = kv_quad<T>(acc[4 + ct][qb]); v4[ct] = kv_quad<T>(acc[8 + ct][qb]); }
+    write_kv_rows<ROW>(klds, vlds, tok0 + 16 * qb + lr, lq, k4, v4);
   }
   __syncthreads();
 
@@ -213,16 +225,12 @@ __global__ void __launch_bounds__(512) attn_fused_kernel(AttnFuseArgs p) {
     for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) sacc[qb][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+    attn_scores<T, ROW, 4, KST, QB>(sacc, kb, qf, lr, lq);
+    // log2-domain online softmax, p = exp2(s * c2 - m2), c2 = ch^-1/2 * log2(e).  This kernel's own form, not attn_softmax_offset: q is
+    // unscaled here and the offset is applied per element by an fma (m_run starts at -inf), which rounds differently from the
+    // offset-in-accumulator form - converting it changes the output bits and is a change of its own.
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ks = 0; ks < KST; ++ks) {
-        const u32x4 kf = *reinterpret_cast<const u32x4*>(kb + (mi * 16 + lr) * ROW + (ks * 4 + lq) * 16);
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) mma16(sacc[qb][mi], kf, qf[qb][ks], T());
-      }
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {   // log2-domain online softmax: p = exp2(s * c2 - m2), c2 = ch^-1/2 * log2(e)
+    for (int qb = 0; qb < QB; ++qb) {
       float mx = -INFINITY;
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi)
@@ -251,56 +259,11 @@ __global__ void __launch_bounds__(512) attn_fused_kernel(AttnFuseArgs p) {
       l_run[qb] += psum;
       m_run[qb] = m_new;
     }
-    if constexpr (BF) {
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        u32x4 pfrag[QB];
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) {
-          const u32x2 p0 = pack4(sacc[qb][2 * s2], T()), p1 = pack4(sacc[qb][2 * s2 + 1], T());
-          pfrag[qb] = u32x4{p0[0], p0[1], p1[0], p1[1]};
-        }
-        const char* vrow = vb + (32 * s2 + 4 * lq + (lr >> 2)) * ROW + 8 * (lr & 3);
-#pragma unroll
-        for (int ci = 0; ci < CI; ++ci) {
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vrow + ci * 32));
-          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vrow + 16 * ROW + ci * 32));
-          const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-          const u32x4 vf = u32x4{l2[0], l2[1], h2[0], h2[1]};
-#pragma unroll
-          for (int qb = 0; qb < QB; ++qb) mma16(o[qb][ci], vf, pfrag[qb], T());
-        }
-      }
-    } else {
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ci = 0; ci < CI; ++ci) {
-          const char* vp = vb + (16 * mi + 4 * lq) * ROW + (16 * ci + lr) * 4;
-          const u32x4 vf = u32x4{*reinterpret_cast<const uint32_t*>(vp), *reinterpret_cast<const uint32_t*>(vp + ROW),
-                                 *reinterpret_cast<const uint32_t*>(vp + 2 * ROW), *reinterpret_cast<const uint32_t*>(vp + 3 * ROW)};
-#pragma unroll
-          for (int qb = 0; qb < QB; ++qb) mma16(o[qb][ci], vf, __builtin_bit_cast(u32x4, sacc[qb][mi]), T());
-        }
-    }
+    attn_pv<T, ROW, 4, CI, QB>(o, sacc, vb, lr, lq);
   }
 #pragma unroll
-  for (int qb = 0; qb < QB; ++qb) {
-    float l = l_run[qb];
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-    const float inv = 1.0f / l;
-    T* op = reinterpret_cast<T*>(p.out) + ((size_t)n * TT + tok0 + 16 * qb + lr) * C + h * CH;
-#pragma unroll
-    for (int ci = 0; ci < CI; ++ci) {
-      T* dst = op + ci * 16 + 4 * lq;
-      if constexpr (!BF) {
-        *reinterpret_cast<f32x4*>(dst) = f32x4{o[qb][ci][0] * inv, o[qb][ci][1] * inv, o[qb][ci][2] * inv, o[qb][ci][3] * inv};
-      } else {
-        *reinterpret_cast<u32x2*>(dst) = pack4(f32x4{o[qb][ci][0] * inv, o[qb][ci][1] * inv, o[qb][ci][2] * inv, o[qb][ci][3] * inv}, T());
-      }
-    }
-  }
+  for (int qb = 0; qb < QB; ++qb)
+    attn_store_normalised<T, CI>(reinterpret_cast<T*>(p.out) + ((size_t)n * TT + tok0 + 16 * qb + lr) * C + h * CH, true, o[qb], l_run[qb], lq);
 }
 
 // ---- persistent form (bf16, T = 256, C = 32 NCH <= 256): one workgroup per CU keeps ITS head's q|k|v weight rows in LDS for every image
@@ -334,7 +297,6 @@ __global__ void __launch_bounds__(512) attn_fused_pers_kernel(AttnFuseArgs p, in
   if (ilane >= lanes || ilane >= p.N) return;          // whole workgroup, before any barrier
   const int tok0 = wave * (16 * QB);
   if constexpr ((ATTN_ABLATE & 512) != 0) { if (wave >= 4) __builtin_amdgcn_s_setprio(1); }   // experiment: the younger wave of each SIMD first
-  auto grow = [&](int j) { return p.new_order ? (j >> 6) * C + h * CH + (j & 63) : h * (3 * CH) + j; };
 
   u32x4 xr[NCH][QB];
   // quarter j of an image's x fragments (chunks j NCH/4 ...): the next image's quarters are issued one per key tile of the attention
@@ -349,34 +311,10 @@ __global__ void __launch_bounds__(512) attn_fused_pers_kernel(AttnFuseArgs p, in
       for (int qb = 0; qb < QB; ++qb) xr[c][qb] = *reinterpret_cast<const u32x4*>(xb + (size_t)(tok0 + 16 * qb + lr) * C + c * CHUNK + lq * V);
   };
   load_x(ilane, lr0, lq0, IC3<0>()); load_x(ilane, lr0, lq0, IC3<1>()); load_x(ilane, lr0, lq0, IC3<2>()); load_x(ilane, lr0, lq0, IC3<3>());
-  {   // the head's weight rows, once (copied verbatim: see attn_fused_kernel)
-    uint32_t wso[2]; int wdo[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int e = tid + 512 * u, j = min(e >> 2, 191), r = grow(j);
-      wso[u] = ((uint32_t)(r >> 7) * NCH) * 8192u + (uint32_t)(r & 127) * 64u + (e & 3) * 16;
-      wdo[u] = j * 64 + (e & 3) * 16;
-    }
-    const bool second = tid + 512 < 768;
-    const char* wsrc = reinterpret_cast<const char*>(p.w);
-#pragma unroll
-    for (int cl = 0; cl < NCH; cl += 4) {
-      u32x4 t[4][2];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        t[k][0] = *reinterpret_cast<const u32x4*>(wsrc + wso[0] + (size_t)(cl + k) * 8192);
-        t[k][1] = *reinterpret_cast<const u32x4*>(wsrc + wso[1] + (size_t)(cl + k) * 8192);
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        *reinterpret_cast<u32x4*>(wlds + (cl + k) * WBUF + wdo[0]) = t[k][0];
-        if (second) *reinterpret_cast<u32x4*>(wlds + (cl + k) * WBUF + wdo[1]) = t[k][1];
-      }
-    }
-  }
+  stage_head_weights(wlds, p.w, NCH, 0, NCH, p.new_order, C, h, tid);   // the head's weight rows, once
   if (tid < 2 * C) ablds[tid] = tid < C ? p.ga[(size_t)ilane * C + tid] : p.gb[(size_t)ilane * C + tid - C];
   float* biaslds = ablds + 4 * C;                      // the head's 192 bias values, row order
-  if (tid < 192) biaslds[tid] = p.bias[grow(tid)];
+  if (tid < 192) biaslds[tid] = p.bias[head_row(p.new_order, C, h, tid)];
   __syncthreads();
 
   const float c2 = p.scale2 * 1.4426950408889634f;
@@ -405,21 +343,10 @@ __global__ void __launch_bounds__(512) attn_fused_pers_kernel(AttnFuseArgs p, in
     u32x4 xf[NCH][QB];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      float av[V], bv[V];
+      gn_affine_frag<T, QB>(xf[c], xr[c], ab, C, c * CHUNK + lq * V);
+      if constexpr ((ATTN_ABLATE & 64) != 0) {
 #pragma unroll
-      for (int j = 0; j < V; j += 4) {
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(ab + c * CHUNK + lq * V + j);
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(ab + C + c * CHUNK + lq * V + j);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { av[j + k] = a4[k]; bv[j + k] = b4[k]; }
-      }
-#pragma unroll
-      for (int qb = 0; qb < QB; ++qb) {
-        float f[V];
-        frag_to_float(xr[c][qb], f, T());
-#pragma unroll
-        for (int j = 0; j < V; ++j) f[j] = av[j] * f[j] + bv[j];
-        xf[c][qb] = (ATTN_ABLATE & 64) ? xr[c][qb] : float_to_frag(f, T());
+        for (int qb = 0; qb < QB; ++qb) xf[c][qb] = xr[c][qb];
       }
     }
     stamp(1);
@@ -492,15 +419,7 @@ __global__ void __launch_bounds__(512) attn_fused_pers_kernel(AttnFuseArgs p, in
     if (more && tid < 2 * C) ablds[((it + 1) & 1) * 2 * C + tid] = abn;   // read two barriers later at the earliest
     auto write_kv = [&](int key0) {
 #pragma unroll
-      for (int qb = 0; qb < QB; ++qb) {
-        const int key = key0 + 16 * qb + lr;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-          // K: the 16-byte slot (ks, lq) holds tile 2 ks (first 8 bytes) and tile 2 ks + 1 (last 8) = the q fragments' channel order
-          *reinterpret_cast<u32x2*>(klds + key * ROW + (ct >> 1) * 64 + lq * 16 + (ct & 1) * 8) = kpk[qb][ct];
-          *reinterpret_cast<u32x2*>(vlds + key * ROW + (16 * ct + 4 * lq) * 2) = vpk[qb][ct];   // V: natural [key][channel]
-        }
-      }
+      for (int qb = 0; qb < QB; ++qb) write_kv_rows<ROW>(klds, vlds, key0 + 16 * qb + lr, lq, kpk[qb], vpk[qb]);
     };
     // ---------------- phase 3: attention over the key buffer, two rounds of 128 keys ----------------
     f32x4 o[QB][CI];
@@ -511,17 +430,8 @@ __global__ void __launch_bounds__(512) attn_fused_pers_kernel(AttnFuseArgs p, in
 #pragma unroll
       for (int ci = 0; ci < CI; ++ci) o[qb][ci] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    // The reference offset m_run of a query column enters as the START value of its S^T accumulators, so p = exp2(sacc) with no
-    // multiply-add per element; it moves only when a tile's maximum exceeds it by more than 8 (p <= 2^8), and then the tile is shifted
-    // and O / l rescaled on a wave-uniform slow path.  The very first tile always takes that path (its offset is the tile maximum).
-    // The column maximum is reduced over the four lanes that share a query with two VALU row swaps (v_permlane16_swap /
-    // v_permlane32_swap) instead of two LDS round trips.
-    auto colmax = [&](float v) {
-      const auto s16 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(uint32_t, v), __builtin_bit_cast(uint32_t, v), false, false);
-      v = fmaxf(__builtin_bit_cast(float, (uint32_t)s16[0]), __builtin_bit_cast(float, (uint32_t)s16[1]));
-      const auto s32 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, v), __builtin_bit_cast(uint32_t, v), false, false);
-      return fmaxf(__builtin_bit_cast(float, (uint32_t)s32[0]), __builtin_bit_cast(float, (uint32_t)s32[1]));
-    };
+    // Offset-in-accumulator online softmax (attn_core.h): the reference offset m_run of a query column enters as the START value of its S^T
+    // accumulators, so p = exp2(sacc) with no multiply-add per element; the very first tile takes the slow path (its offset is the tile maximum).
     auto attend = [&](auto roundc) {
       constexpr int RND = decltype(roundc)::value;
 #pragma unroll
@@ -535,62 +445,10 @@ __global__ void __launch_bounds__(512) attn_fused_pers_kernel(AttnFuseArgs p, in
         for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
           for (int mi = 0; mi < 4; ++mi) sacc[qb][mi] = f32x4{-m_run[qb], -m_run[qb], -m_run[qb], -m_run[qb]};
+        attn_scores<T, ROW, 4, KST, QB>(sacc, kb, qf, lr, lq);
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-          for (int ks = 0; ks < KST; ++ks) {
-            const u32x4 kf = (ATTN_ABLATE & 16) ? u32x4{(uint32_t)lane << 8, 0x3c003c00u, (uint32_t)(mi + kt), 0x3c003c00u} : *reinterpret_cast<const u32x4*>(kb + (mi * 16 + lr) * ROW + (ks * 4 + lq) * 16);
-#pragma unroll
-            for (int qb = 0; qb < QB; ++qb) mma16(sacc[qb][mi], kf, qf[qb][ks], T());
-          }
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) {
-          float mx = fmaxf(fmaxf(sacc[qb][0][0], sacc[qb][0][1]), fmaxf(sacc[qb][0][2], sacc[qb][0][3]));
-#pragma unroll
-          for (int mi = 1; mi < 4; ++mi)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sacc[qb][mi][r]);
-          mx = colmax(mx);
-          const float delta = first ? mx : (mx > 8.0f ? mx : 0.0f);
-          if (first || __builtin_amdgcn_ballot_w64(delta != 0.0f) != 0) {   // wave-uniform: some column's offset moves
-            const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);
-            m_run[qb] += delta;
-            l_run[qb] *= alpha;
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) sacc[qb][mi][r] -= delta;
-#pragma unroll
-            for (int ci = 0; ci < CI; ++ci)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) o[qb][ci][r] *= alpha;
-          }
-          float psum = 0.f;
-#pragma unroll
-          for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { const float pv = (ATTN_ABLATE & 8) ? sacc[qb][mi][r] : __builtin_amdgcn_exp2f(sacc[qb][mi][r]); sacc[qb][mi][r] = pv; psum += pv; }
-          l_run[qb] += psum;
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          u32x4 pfrag[QB];
-#pragma unroll
-          for (int qb = 0; qb < QB; ++qb) {
-            const u32x2 p0 = pack4(sacc[qb][2 * s2], T()), p1 = pack4(sacc[qb][2 * s2 + 1], T());
-            pfrag[qb] = u32x4{p0[0], p0[1], p1[0], p1[1]};
-          }
-          const char* vrow = vb + (32 * s2 + 4 * lq + (lr >> 2)) * ROW + 8 * (lr & 3);
-#pragma unroll
-          for (int ci = 0; ci < CI; ++ci) {
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vrow + ci * 32));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vrow + 16 * ROW + ci * 32));
-            const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-            const u32x4 vf = (ATTN_ABLATE & 16) ? u32x4{(uint32_t)lane << 8, 0x3c003c00u, (uint32_t)(ci + kt), 0x3c003c00u} : u32x4{l2[0], l2[1], h2[0], h2[1]};
-#pragma unroll
-            for (int qb = 0; qb < QB; ++qb) mma16(o[qb][ci], vf, pfrag[qb], T());
-          }
-        }
+        for (int qb = 0; qb < QB; ++qb) attn_softmax_offset<4, CI>(sacc[qb], o[qb], m_run[qb], l_run[qb], first);
+        attn_pv<T, ROW, 4, CI, QB>(o, sacc, vb, lr, lq);
       }
     };
     stamp(5);
@@ -609,17 +467,8 @@ __global__ void __launch_bounds__(512) attn_fused_pers_kernel(AttnFuseArgs p, in
     if constexpr (!(ATTN_ABLATE & 1)) attend(IC3<1>());
     stamp(11);
 #pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-      float l = l_run[qb];
-      l += __shfl_xor(l, 16);
-      l += __shfl_xor(l, 32);
-      const float inv = 1.0f / l;
-      T* op = reinterpret_cast<T*>(p.out) + ((size_t)n * TT + tok0 + 16 * qb + lr) * C + h * CH;
-#pragma unroll
-      for (int ci = 0; ci < CI; ++ci) {
-        *reinterpret_cast<u32x2*>(op + ci * 16 + 4 * lq) = pack4(f32x4{o[qb][ci][0] * inv, o[qb][ci][1] * inv, o[qb][ci][2] * inv, o[qb][ci][3] * inv}, T());
-      }
-    }
+    for (int qb = 0; qb < QB; ++qb)
+      attn_store_normalised<T, CI>(reinterpret_cast<T*>(p.out) + ((size_t)n * TT + tok0 + 16 * qb + lr) * C + h * CH, true, o[qb], l_run[qb], lq);
     stamp(12);
   }
   if constexpr (STAMP) {
@@ -658,8 +507,6 @@ int launch_fused(const AttnFuseArgs& a, hipStream_t s) {
 
 bool attn_fused_eligible(int dtype, int T, int C, int heads, int ch, const mi355_debug_config* knobs) {
   const int enabled = (knobs ? knobs : &mi355_default_debug())->attn_fused;
-  const int CHUNK = dtype == 0 ? 16 : 32;
-  (void)CHUNK;
   return (enabled & 1) && ch == 64 && heads * ch == C && (T == 128 || T == 256) && C % 128 == 0 && C <= 512;   // 3C % 128 == 0: 128-row weight tiles
 }
 

@@ -191,6 +191,13 @@ struct AttnDesc {
   int new_order = 0;
 };
 int attention_launch(const AttnDesc& d, hipStream_t stream);
+// Where head h's channels sit in a [3C] qkv row, either order: q at h * qoff_h, k at koff + h * qoff_h, v at voff + h * qoff_h; and the
+// score scale ch^-1/2 (the reference scales q and k by ch^-1/4 each).  Forward and backward launchers alike.
+struct AttnChannelOffsets { int qoff_h, koff, voff; float scale2; };
+inline AttnChannelOffsets attn_channel_offsets(int new_order, int ch, int C) {
+  const float scale2 = 1.0f / sqrtf((float)ch);
+  return new_order ? AttnChannelOffsets{ch, C, 2 * C, scale2} : AttnChannelOffsets{3 * ch, ch, 2 * ch, scale2};
+}
 // GroupNorm-apply -> qkv 1x1 -> attention of one AttentionBlock in one kernel (attn_fused.hip): x NHWC [N][T][C], (a, b) [N][C],
 // w / bias = the qkv conv's packed weights (conv_pack_weights, ks 1, Cout 3C) / bias [3C]; out NHWC [N][T][C]
 struct AttnFusedDesc {

@@ -13,7 +13,9 @@ and compare the files.  --save keeps the tensors themselves, for a max-abs compa
 --cases forward adds (or, alone, selects) the digest of single forwards, on the smallest nets and batches at which each decision of the
 executor (csrc/unet_engine.hip: unet_resolve) goes either way: per case the SHA-256 of the output, the launch count, every field of every
 profile() record except ms, and for every conv output tensor whether read_tensor refuses it and why (0 readable, 1 never written, 2
-normalised in place).  --inventory needs no GPU: the parameter inventory (names, shapes, order) and the weight-image bytes of the same nets.
+normalised in place).  --cases attention: one line per call of the three attention ops (qkv_attention, attn_block_fused,
+qkv_attention_vjp) on the shapes at which each of the five attention kernels takes another path.  --inventory needs no GPU: the parameter
+inventory (names, shapes, order) and the weight-image bytes of the same nets.
 """
 import argparse
 import hashlib
@@ -360,13 +362,81 @@ def run_forward(prec):
         fwd_case(prec, "fwd_differentiable_b3", fwd_engine("differentiable", prec, differentiable=True), 3, vjp=True)
 
 
+# ---- the attention ops, one call each ---------------------------------------------------------------------------------------------------
+ATTN_SHAPES = [(2, 4, 64, 16), (2, 1, 64, 49), (1, 1, 192, 70), (1, 2, 128, 100), (2, 4, 64, 256), (2, 1, 96, 256), (1, 3, 32, 300), (1, 1, 256, 256),
+               (2, 1, 384, 256), (2, 1, 512, 64)]   # (B, heads, ch, T): every launch_attn case, both QB, ragged last tiles, 32-key tiles, single-buffer fp32
+
+
+def run_attention():
+    """One line per call of ops.qkv_attention, ops.attn_block_fused and ops.qkv_attention_vjp, on the shapes the tests name as the smallest at
+    which each kernel path can go wrong; fixed-seed inputs, both channel orders, every precision the op accepts."""
+    from mi355.ops import default_ops as ops
+
+    names = {_lib.MI355_F32: "fp32", _lib.MI355_BF16: "bf16", _lib.MI355_F16: "fp16"}
+    orders = ((False, "legacy"), (True, "new"))
+
+    def line(tag, t):
+        torch.cuda.synchronize()
+        t = t.detach().cpu().contiguous()
+        KEPT[f"attention/{tag}"] = t
+        emit(f"attention {tag} {tuple(t.shape)} sha256={hashlib.sha256(t.numpy().tobytes()).hexdigest()}")
+
+    # the generic kernel
+    for i, (b, heads, ch, t) in enumerate(ATTN_SHAPES):
+        qkv = (randn(7700 + i, b, 3 * heads * ch, t) * 0.5).to(DEV)
+        for new, oname in orders:
+            for dt, dname in names.items():
+                line(f"qkv {dname} {oname} B{b} H{heads} ch{ch} T{t}", ops.qkv_attention(qkv, heads, new, dt))
+    # its softmax slow path: a late huge key, and every logit near -288 (tests/test_gpu_ops.py: test_attention_softmax_spike)
+    ch, t = 64, 256
+    late = randn(11, 1, 3 * ch, t) * 0.5
+    late[0, ch:2 * ch, 200] = late[0, 0:ch, 7] * 40.0
+    low = randn(12, 1, 3 * ch, t) * 0.5
+    low[0, 0:ch] = 6.0 + 0.1 * low[0, 0:ch]
+    low[0, ch:2 * ch] = -6.0 + 0.1 * low[0, ch:2 * ch]
+    for sname, q in (("late_key", late), ("all_low", low)):
+        for dt, dname in names.items():
+            line(f"qkv_spike {sname} {dname}", ops.qkv_attention(q.to(DEV), 1, False, dt))
+
+    # the fused block: per-image kernel (knob 3), then the persistent kernel through the knob's lane override
+    def block(seed, n, c, t):
+        return ((randn(seed, n, c, t)).to(DEV), (1.0 + 0.2 * randn(seed + 1, n, c)).to(DEV), (0.2 * randn(seed + 2, n, c)).to(DEV),
+                randn(seed + 3, 3 * c, c) / c ** 0.5, 0.1 * randn(seed + 4, 3 * c))
+
+    for t in (128, 256):
+        for c in (128, 256, 384, 512):
+            for n in (1, 9):
+                x, a, b, w, bias = block(7800 + t + c + 7 * n, n, c, t)
+                for new, oname in orders:
+                    for dt, dname in names.items():
+                        out, form = ops.attn_block_fused(x, a, b, w, bias, c // 64, new, dt, debug=_lib.debug_config(attn_fused=3))
+                        line(f"fused_image {dname} {oname} T{t} C{c} N{n} form={form}", out)
+    for c in (128, 256):
+        for n, lanes in ((24, 5), (3, 8), (17, 8)):
+            x, a, b, w, bias = block(7900 + c + 7 * n, n, c, 256)
+            for new, oname in orders:
+                for dt in (_lib.MI355_BF16, _lib.MI355_F16):
+                    out, form = ops.attn_block_fused(x, a, b, w, bias, c // 64, new, dt, debug=_lib.debug_config(attn_fused=1 | (lanes << 8)))
+                    line(f"fused_persistent {names[dt]} {oname} C{c} N{n} lanes{lanes} form={form}", out)
+
+    # the backward
+    for ch in (32, 64, 96, 128, 192, 256):
+        for t in (70, 256):
+            heads = 2 if ch <= 64 else 1
+            qkv = (randn(8000 + ch + t, 2, 3 * heads * ch, t) * 0.5).to(DEV)
+            g = randn(8001 + ch + t, 2, heads * ch, t).to(DEV)
+            for new, oname in orders:
+                for dt in (_lib.MI355_F32, _lib.MI355_BF16):
+                    line(f"qkv_vjp {names[dt]} {oname} H{heads} ch{ch} T{t}", ops.qkv_attention_vjp(qkv, g, heads, new, dt))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--out", help="also write the lines to this file")
     ap.add_argument("--save", help="keep every output tensor in this torch file")
     ap.add_argument("--mark", action="store_true", help="one torch.flip launch behind every case: the cut marks of a kernel trace")
     ap.add_argument("--precisions", default="fp32,bf16")
-    ap.add_argument("--cases", default="sampler", help="comma list of: sampler (the loops), forward (single forwards)")
+    ap.add_argument("--cases", default="sampler", help="comma list of: sampler (the loops), forward (single forwards), attention (the attention ops; once, not per precision)")
     ap.add_argument("--inventory", action="store_true", help="no GPU: parameter inventories and weight-image bytes of the forward nets only")
     a = ap.parse_args()
     MARK[0] = a.mark
@@ -378,6 +448,8 @@ def main():
             run(prec)
         if "forward" in a.cases.split(","):
             run_forward(prec)
+    if not a.inventory and "attention" in a.cases.split(","):
+        run_attention()
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(LINES) + "\n")
