@@ -47,8 +47,10 @@ def draw_x0_shard(batch, seed, call_idx, device, shape=(3, 32, 32)):
 
 
 def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integration_method="euler", device="cuda:0", tol=1e-5, seed=0,
-                   guidance_scale=None, null_label=None):
-    """guidance_scale (None: unguided, the reference's call): classifier-free guidance on a class-conditional net; each image's label is drawn
+                   guidance_scale=None, null_label=None, cache_interval=None, cache_branch=None):
+    """cache_interval / cache_branch (None: every step evaluates the whole net): feature reuse across the Euler steps (DeepCache; one full
+    evaluation in cache_interval, the cache_branch outermost block pairs recomputed at every step: UNetEngine.cfm_euler); Euler only, unguided.
+    guidance_scale (None: unguided, the reference's call): classifier-free guidance on a class-conditional net; each image's label is drawn
     uniformly from the classes other than null_label (default: the last class) by the batch's seeded generator.
     integration_method: "euler", "dopri5", a fixed-step Runge-Kutta name ("midpoint", "heun2", "rk4", "rk4_38": mi355.ode.TABLEAUS) or an
     Adams-Bashforth name ("ab2", "ab3", "ab4": mi355.ode.AB_SOLVERS).
@@ -59,6 +61,11 @@ def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integrat
 
     if integration_method not in ("euler", "dopri5") + rk + ab:
         raise NotImplementedError(f"--integration_method must be euler, dopri5 or one of {rk + ab}")
+    cache = {}
+    if cache_interval is not None or cache_branch is not None:
+        if integration_method != "euler":
+            raise NotImplementedError("--cache_interval / --cache_branch are built for --integration_method euler only")
+        cache = dict(cache_interval=1 if cache_interval is None else int(cache_interval), cache_branch=cache_branch)
     device = torch.device(device)
     calls = [0]
     guide = {}
@@ -86,7 +93,7 @@ def make_gen_1_img(new_net, batch_size_fid=1024, integration_steps=100, integrat
             calls[0] += 1
             if integration_method == "euler":
                 t_span = torch.linspace(0, 1, integration_steps + 1).tolist()
-                _, _, img = new_net.engine(device).cfm_euler(x, t_span, want_u8=True, **kw)  # (traj*127.5+128).clip(0,255).to(uint8)
+                _, _, img = new_net.engine(device).cfm_euler(x, t_span, want_u8=True, **kw, **cache)  # (traj*127.5+128).clip(0,255).to(uint8)
             elif integration_method in rk:
                 t_span = torch.linspace(0, 1, integration_steps + 1).tolist()
                 _, _, img = new_net.engine(device).cfm_rk(x, t_span, integration_method, want_u8=True, **kw)
@@ -120,6 +127,8 @@ def main(argv=None):
     ap.add_argument("--guidance_scale", type=float, default=None, help="classifier-free guidance scale w (needs --num_classes); unset: unguided")
     ap.add_argument("--null_label", type=int, default=None, help="the class index trained as the null token (default: the last class)")
     ap.add_argument("--num_classes", type=int, default=None, help="build the class-conditional net (K + 1 classes with a null token); the checkpoint must be that net's")
+    ap.add_argument("--cache_interval", type=int, default=None, help="feature reuse (DeepCache), euler only: one full U-Net evaluation in N steps; unset: every step is full")
+    ap.add_argument("--cache_branch", type=int, default=None, help="feature reuse: the outermost block pairs recomputed at every step (default 1; UNetEngine.cache_branches() lists them)")
     a = ap.parse_args(argv)
     rank, world, local = mdist.init_from_env()
     device = f"cuda:{local}"
@@ -127,7 +136,8 @@ def main(argv=None):
     path = f"{a.input_dir}/{a.model}/{a.model}_cifar10_weights_step_{a.step}.pt"
     print("path: ", path)
     load_checkpoint(net, path)
-    gen = make_gen_1_img(net, a.batch_size_fid, a.integration_steps, a.integration_method, device, a.tol, a.seed, a.guidance_scale, a.null_label)
+    gen = make_gen_1_img(net, a.batch_size_fid, a.integration_steps, a.integration_method, device, a.tol, a.seed, a.guidance_scale, a.null_label,
+                         a.cache_interval, a.cache_branch)
     try:
         from cleanfid import fid
     except ImportError as e:

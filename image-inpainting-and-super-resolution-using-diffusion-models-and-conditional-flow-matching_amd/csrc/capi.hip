@@ -77,21 +77,53 @@ int mi355_unet_forward_t(mi355_unet* net, const float* x, int x_channels, const 
   return unet_forward(net, x, x_channels, cond, cond_channels, tdev, out, batch, workspace, workspace_bytes, S(stream), uniform_t_run());
 }
 
-int mi355_unet_forward_labels(mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, const float* t, float t_host,
-                              const int32_t* labels, float* out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
-  MI355_REQUIRE(net && workspace && batch > 0, -1, "unet_forward_labels: bad argument");
-  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "unet_forward_labels: class labels given to a net built without num_classes");
+// mi355_unet_forward_labels and mi355_unet_forward_cached: one body; branch 0 = the whole forward
+static int forward_labels_run(const std::string& who, mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, const float* t,
+                              float t_host, const int32_t* labels, float* out, int batch, void* workspace, int64_t workspace_bytes, void* stream, int branch) {
+  MI355_REQUIRE(net && workspace && batch > 0, -1, who + ": bad argument");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, who + ": class labels given to a net built without num_classes");
+  if (branch) {   // refused here, before the time is staged: nothing is launched
+    if (unet_cache_range(net, branch, nullptr, nullptr, nullptr)) { mi355_set_error(who + ": branch: " + mi355_last_error()); return -1; }
+    MI355_REQUIRE(!net->cfg.differentiable, -4, who + ": branch: a differentiable plan cannot run a shallow evaluation (the backward pass would see activations of two forwards)");
+  }
   UnetRun run;
   run.labels = labels;
+  run.reuse_branch = branch;
   if (!t) {   // one host time for the batch: staged as in mi355_unet_forward_t
     const WsLayout l = unet_ws_layout(net, batch);
-    MI355_REQUIRE((int64_t)l.total <= workspace_bytes, -2, "unet_forward_labels: workspace too small");
+    MI355_REQUIRE((int64_t)l.total <= workspace_bytes, -2, who + ": workspace too small");
     float* tdev = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + l.emb2);
     if (int rc = fill_launch(tdev, t_host, 1, S(stream))) return rc;
     t = tdev;
     run.t_uniform = 1;
   }
   return unet_forward(net, x, x_channels, cond, cond_channels, t, out, batch, workspace, workspace_bytes, S(stream), run);
+}
+
+int mi355_unet_forward_labels(mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, const float* t, float t_host,
+                              const int32_t* labels, float* out, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  return forward_labels_run("unet_forward_labels", net, x, x_channels, cond, cond_channels, t, t_host, labels, out, batch, workspace, workspace_bytes, stream, 0);
+}
+
+int mi355_unet_cache_info(const mi355_unet_config* cfg, int branch, int32_t out[8]) {
+  MI355_REQUIRE(cfg && out, -1, "unet_cache_info: null argument");
+  mi355_unet tmp;
+  if (int64_t rc = unet_plan_dry(*cfg, &tmp); rc < 0) return (int)rc;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = unet_cache_branches(&tmp);
+  if (branch == 0) return 0;
+  int lo, hi, tid;
+  if (unet_cache_range(&tmp, branch, &lo, &hi, &tid)) { mi355_set_error(std::string("unet_cache_info: branch: ") + mi355_last_error()); return -1; }
+  const PlanTensor& t = tmp.tensors[tid];
+  out[1] = lo; out[2] = hi; out[3] = tid; out[4] = t.C; out[5] = t.H; out[6] = t.W;
+  out[7] = (int32_t)(unet_cache_retained_share(&tmp, branch) * 1e6 + 0.5);
+  return 0;
+}
+
+int mi355_unet_forward_cached(mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, const float* t, float t_host,
+                              const int32_t* labels, float* out, int batch, void* workspace, int64_t workspace_bytes, void* stream, int branch) {
+  return forward_labels_run("unet_forward_cached", net, x, x_channels, cond, cond_channels, t, t_host, labels, out, batch, workspace, workspace_bytes, stream,
+                            branch);
 }
 
 int mi355_unet_vjp(mi355_unet* net, const float* grad_out, float* grad_x, int x_channels, int batch, void* workspace, int64_t workspace_bytes,
@@ -244,6 +276,11 @@ int mi355_ema_update(float* target, const float* source, float decay, float one_
 int mi355_mse_per_sample(const float* a, const float* b, float* out, int batch, int64_t elems_per_sample, void* stream) {
   MI355_REQUIRE(a && b && out, -1, "mse_per_sample: null argument");
   return mse_per_sample_launch(a, b, out, batch, elems_per_sample, S(stream));
+}
+int mi355_feature_drift(const void* cur, void* prev, int dtype, int batch, int64_t elems_per_image, float* out, void* stream) {
+  MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_BF16 || dtype == MI355_BF16X2 || dtype == MI355_F16, -1,
+                "feature_drift: dtype must be MI355_F32, MI355_BF16, MI355_BF16X2 or MI355_F16");
+  return feature_drift_launch(dtype == MI355_F16 ? DT_F16 : (dtype == MI355_F32 ? DT_F32 : DT_BF16), cur, prev, batch, elems_per_image, out, S(stream));
 }
 int mi355_image_metrics(const float* x, const float* ref, float* out, int batch, int channels, int h, int w, float data_range,
                         const float* taps_host, int win, float cov_norm, float k1, float k2, void* stream) {

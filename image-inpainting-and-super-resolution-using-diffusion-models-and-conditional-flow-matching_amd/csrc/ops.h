@@ -339,6 +339,8 @@ int replace_mask_launch(float* x, const float* cond, const float* z, float pad, 
                         int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int clip_launch(float* x, float lo, float hi, int64_t n, hipStream_t s);
 int mse_per_sample_launch(const float* a, const float* b, float* out, int batch, int64_t per, hipStream_t s);
+// out[b] = ||cur_b - prev_b||^2 / ||prev_b||^2, then prev <- cur; cur, prev [batch][per] of the internal dtype's element type (steps.hip)
+int feature_drift_launch(int dtype, const void* cur, void* prev, int batch, int64_t per, float* out, hipStream_t s);
 int lincomb_per_sample_launch(float* out, const float* x, const float* y, const float* a, const float* b, int batch, int64_t per,
                               hipStream_t s);
 // per-sample { mse, data_range, psnr, ssim } of x against ref, one workgroup per sample (metrics.hip); taps_host NULL = uniform window

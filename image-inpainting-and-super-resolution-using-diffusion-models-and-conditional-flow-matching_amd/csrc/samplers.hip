@@ -34,10 +34,11 @@ struct ReconDims { int h_low, w_low; };
 struct ReconTail { float* x_init; float* g_eps; float* g_x; float* vjp; float* resid; };
 // the DDPM multistep history (the previous step's data prediction: one state at `batch`, also under guidance) and the shaping rows [batch][2]
 struct DdpmTail { float* hist; float* rows; };
-struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; ReconTail rec; DdpmTail ddpm; uintptr_t end; };
+// feature cache with drift_out: the cached feature as the previous full evaluation left it (plan element type), behind everything else
+struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; ReconTail rec; DdpmTail ddpm; void* feat_prev; uintptr_t end; };
 // What a sampler call keeps in its workspace.  guided: the network runs at 2 * batch and the guidance tail follows its workspace; stages > 0: the
 // Runge-Kutta buffers follow; recon: the reconstruction tail; hist, rows: the DDPM tail closes the layout.
-struct LayoutSpec { int batch = 0; bool guided = false; int stages = 0; const ReconDims* recon = nullptr; bool hist = false; bool rows = false; };
+struct LayoutSpec { int batch = 0; bool guided = false; int stages = 0; const ReconDims* recon = nullptr; bool hist = false; bool rows = false; size_t feat_bytes = 0; };
 inline size_t cfg_cond_channels(const mi355_unet* net) { return (size_t)(net->cfg.in_channels > net->cfg.out_channels ? net->cfg.in_channels - net->cfg.out_channels : 0); }
 
 Layout layout(const mi355_unet* net, const LayoutSpec& sp, uintptr_t base) {
@@ -57,7 +58,7 @@ Layout layout(const mi355_unet* net, const LayoutSpec& sp, uintptr_t base) {
   l.sc.unet_bytes = unet_workspace_bytes(net, B);
   l.sc.unet_ws = reinterpret_cast<char*>(w.p);
   w.p += (size_t)l.sc.unet_bytes;   // not rounded up: mi355_unet_workspace_bytes ends here
-  if (guided || stages || recon || sp.hist || sp.rows) w.p = al256(w.p);
+  if (guided || stages || recon || sp.hist || sp.rows || sp.feat_bytes) w.p = al256(w.p);
   if (guided) {
     l.cfg.x2 = w.take(state);
     l.cfg.cond2 = w.take((size_t)B * cfg_cond_channels(net) * hw * 4);
@@ -74,6 +75,7 @@ Layout layout(const mi355_unet* net, const LayoutSpec& sp, uintptr_t base) {
   }
   if (sp.hist) l.ddpm.hist = w.take((size_t)sp.batch * net->cfg.out_channels * hw * 4);
   if (sp.rows) l.ddpm.rows = w.take((size_t)sp.batch * 2 * 4);
+  if (sp.feat_bytes) l.feat_prev = w.take<void>(sp.feat_bytes);
   l.end = w.p;
   return l;
 }
@@ -155,19 +157,73 @@ int cfg_fill_tail(const CfgTail& t, const float* x, int64_t n, const float* cond
   return 0;
 }
 
+// ---- feature reuse across evaluations (DeepCache; mi355_feature_cache) -----------------------------------------------------------------
+// Every refusal of a cache schedule, before any launch, each naming its argument.  n_evals: the evaluations the loop is about to make.
+int check_cache(const char* who, const mi355_unet* net, const mi355_feature_cache* cache, int64_t n_evals) {
+  const std::string f = std::string(who) + ": ";
+  MI355_REQUIRE(cache, -1, f + "cache is null");
+  MI355_REQUIRE(cache->full, -1, f + "cache->full is null");
+  if (unet_cache_range(net, cache->branch, nullptr, nullptr, nullptr)) {
+    mi355_set_error(f + "cache->branch: " + mi355_last_error());
+    return -1;
+  }
+  MI355_REQUIRE(!net->cfg.differentiable, -4, f + "cache: a differentiable plan cannot run shallow evaluations");
+  MI355_REQUIRE((int64_t)cache->n_evals == n_evals, -1,
+                f + "cache->n_evals must be the number of evaluations the loop makes (" + std::to_string(n_evals) + ", got " + std::to_string(cache->n_evals) + ")");
+  MI355_REQUIRE(n_evals == 0 || cache->full[0] != 0, -1, f + "cache->full[0] must be non-zero (the first evaluation has nothing to reuse)");
+  return 0;
+}
+// bytes of the cached feature of branch k at `batch` images (the F_prev buffer of drift_out)
+size_t cache_feature_bytes(const mi355_unet* net, int k, int batch) {
+  int tid = 0;
+  if (unet_cache_range(net, k, nullptr, nullptr, &tid)) return 0;
+  const PlanTensor& t = net->tensors[tid];
+  return (size_t)t.C * t.H * t.W * (size_t)batch * (net->cfg.dtype == 0 ? 4 : 2);
+}
+// A loop's view of its cache schedule (a null CacheRun*: every evaluation is whole).  With drift_out, every full evaluation is followed by ONE
+// launch: the first copies the cached feature into prev, the later ones are feature_drift_launch (row e of drift_out, prev <- the feature).
+struct CacheRun {
+  const mi355_feature_cache* cache = nullptr;
+  const mi355_unet* net = nullptr;
+  int tensor = -1; void* feat = nullptr; void* prev = nullptr; int64_t per = 0; int batch = 0; bool seeded = false;
+  int init(const mi355_unet* n, const mi355_feature_cache* c, const Scratch& sc, void* feat_prev, int B, hipStream_t s) {
+    cache = c; net = n; batch = B;
+    if (!c->drift_out) return 0;
+    if (int rc = unet_cache_range(n, c->branch, nullptr, nullptr, &tensor)) return rc;
+    const PlanTensor& t = n->tensors[tensor];
+    per = (int64_t)t.C * t.H * t.W;
+    feat = WsView(n, sc.unet_ws, B).tensor(tensor); prev = feat_prev;
+    return fill_launch(c->drift_out, -1.f, (int64_t)c->n_evals * B, s);   // rows of shallow evaluations and of the first full one
+  }
+  int branch_of(int64_t e) const { return cache->full[e] ? 0 : cache->branch; }
+  int after(int64_t e, hipStream_t s) {   // evaluation e has been issued
+    if (!cache->drift_out || !cache->full[e]) return 0;
+    MI355_REQUIRE(net->tensor_state[tensor].load(std::memory_order_relaxed) == 0, -4, "feature cache: drift_out needs the cached feature as stored, and this forward did not materialise it");
+    if (!seeded) {
+      seeded = true;
+      MI355_CHECK_HIP(hipMemcpyAsync(prev, feat, (size_t)per * batch * (net->cfg.dtype == 0 ? 4 : 2), hipMemcpyDeviceToDevice, s));
+      return 0;
+    }
+    return feature_drift_launch(net->cfg.dtype, feat, prev, batch, per, cache->drift_out + e * batch, s);
+  }
+};
+
 // ---- flow-matching Euler ----------------------------------------------------------------------------------
 // The loop proper: every launch of every step on stream s (the caller's stream, or the handle's capture stream while a graph is recorded).
 // labels: class-conditional steps (with a table: step k's block of the (step, class) table, one gather launch per step).
 int cfm_euler_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, float* x, int x_channels, const float* cond, int cond_channels, float* cdrift,
-                   const float* t_span_host, int n_t, float* traj, int batch, int64_t n, int64_t nc, hipStream_t s, const int32_t* labels = nullptr) {
+                   const float* t_span_host, int n_t, float* traj, int batch, int64_t n, int64_t nc, hipStream_t s, const int32_t* labels = nullptr,
+                   CacheRun* cache = nullptr) {
   UnetRun run = uniform_t_run();
   run.labels = labels;
   for (int k = 0; k + 1 < n_t; ++k) {
     const float dt = t_span_host[k + 1] - t_span_host[k];
     int rc;
     if ((rc = emb.select(run, (size_t)k, batch, s))) return rc;
+    run.reuse_branch = cache ? cache->branch_of(k) : 0;   // step k is evaluation k
     run.euler_x = x; run.euler_dt = dt;   // x += dt * v: in the last conv's epilogue, or as a launch of unet_forward's own behind it
     if ((rc = unet_forward(net, x, x_channels, cond, cond_channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    if (cache && (rc = cache->after(k, s))) return rc;
     if (cdrift && (rc = euler_step_launch(cdrift, cdrift, dt, nc, s))) return rc;
     if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * n, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
   }
@@ -337,6 +393,8 @@ struct LoopSched {
   // mi355_ddpm_shaped_sample with shaping on: every predictor step is preceded by the statistics launch that fills shape [batch][2], and reads it
   const mi355_x0_shaping* shaping = nullptr;
   float* shape = nullptr;              // behind the entry point's workspace
+  // mi355_ddpm_sample_sched_cached: evaluation e of the loop (predictors and correctors, in loop order) is shallow where cache->full[e] == 0
+  CacheRun* cache = nullptr;
 };
 // emb: row i = the evaluation of step i (ddpm_times(Ns), or a schedule's tau_i / train_steps), selected whenever step i runs, revisits included.
 int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const DdpmLoop& a, const LoopSched& ls, int channels, const mi355_ddpm_tables* tb,
@@ -349,7 +407,7 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
   run.labels = a.labels_pred;
   run_corr.labels = a.labels_corr;
   int rc;
-  int64_t draw = 0;
+  int64_t draw = 0, eval = 0;
   auto next_noise = [&](const float*& zptr, int& philox, uint64_t& off) -> int {
     if (noise) {
       MI355_REQUIRE(draw < n_noise_draws, -2, std::string(a.who) + ": injected noise exhausted");
@@ -368,7 +426,10 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     }
     if ((rc = emb.select(run, (size_t)i, a.evalB, s))) return rc;
     run_corr.emb_row = run.emb_row;
+    run.reuse_branch = ls.cache ? ls.cache->branch_of(eval) : 0;
     if ((rc = unet_forward(net, x, channels, a.cond_pred, channels, sc.t, sc.v, a.evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    if (ls.cache && (rc = ls.cache->after(eval, s))) return rc;
+    ++eval;
     PredictorStep p;
     p.x = x; p.eps = sc.v; p.c_recip = tb->sqrt_recip_alphas_cumprod[i]; p.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[i];
     p.seed = opt->seed; p.guide = a.guide; p.per = sper; p.shape = ls.shape; p.n = n;
@@ -389,7 +450,10 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     p.sigma = expf(0.5f * tb->posterior_log_variance_clipped[i]);
     if ((rc = predictor_step_launch(p, s))) return rc;
     for (int c = 0; c < opt->n_corrector; ++c) {   // at batch B (a guided sampler's first half)
+      run_corr.reuse_branch = ls.cache ? ls.cache->branch_of(eval) : 0;
       if ((rc = unet_forward(net, x, channels, a.cond_corr, channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run_corr))) return rc;
+      if (ls.cache && (rc = ls.cache->after(eval, s))) return rc;
+      ++eval;
       const float* z2 = nullptr; int ph2 = 0; uint64_t off2 = 0;
       if ((rc = next_noise(z2, ph2, off2))) return rc;
       const float dt = (opt->tmax - opt->tmin) / (float)Ns;
@@ -470,6 +534,16 @@ std::vector<float> sched_times(int K, const mi355_ddpm_schedule* sd) {   // eval
   return th;
 }
 
+// The evaluations ddpm_loop makes: one per downward move, and n_corrector more behind each ancestral predictor (the DDIM steps have no corrector).
+int64_t ddpm_eval_count(const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const LoopSched& ls) {
+  int64_t down = tb->Ns > 0 ? tb->Ns : 0;
+  if (ls.walk) {
+    down = 0;
+    for (int j = 0; j + 1 < ls.n_walk; ++j) down += ls.walk[j + 1] < ls.walk[j];
+  }
+  return down * (1 + (opt->mode == MI355_DDIM ? 0 : (int64_t)(opt->n_corrector > 0 ? opt->n_corrector : 0)));
+}
+
 // One DDPM call: the seven entry points check their own arguments, fill this, and run ddpm_run.
 struct DdpmGuidance { const int32_t* labels; int null_label; float w; const float* w_dev; };
 struct DdpmCall {
@@ -480,6 +554,7 @@ struct DdpmCall {
   LayoutSpec spec;                  // batch, guided, the DDPM tail
   bool bare_size_refusal = false;   // mi355_ddpm_sample(_sched): their short-workspace refusal carries no prefix
   bool count_step = false;          // mi355_unet_get_stats: the last evaluation AND the launches of its step (the multistep and shaped entry points)
+  const mi355_feature_cache* cache = nullptr;   // mi355_ddpm_sample_sched_cached (checked by check_cache)
 };
 DdpmCall ddpm_call(const char* who, int batch, const DdpmGuidance* guided) {
   DdpmCall c = {};
@@ -532,6 +607,11 @@ int ddpm_run(DdpmCall& c, mi355_unet* net, float* x, int channels, const float* 
     // x0_model without the condition, sampling.py:116 -> none_like)
     a.cond_pred = !amortized ? nullptr : ((mode == MI355_DDPM_AMORTIZED || (mode == MI355_DDIM && cond)) ? cond : sc.none);
     a.cond_corr = amortized ? sc.none : nullptr;
+  }
+  CacheRun cr;
+  if (c.cache) {
+    if (int rc = cr.init(net, c.cache, sc, l.feat_prev, batch, s)) return rc;
+    c.ls.cache = &cr;
   }
   if (int rc = ddpm_loop(net, sc, emb, a, c.ls, channels, tb, opt, noise, n_noise_draws, batch, n, s)) return rc;
   if (g) MI355_CHECK_HIP(hipMemcpyAsync(x, tl.x2, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
@@ -615,6 +695,14 @@ int64_t mi355_ddpm_cfg_workspace_bytes(const mi355_unet* net, int batch) {
   return layout_bytes(net, plain_spec(batch, true));
 }
 
+int64_t mi355_feature_cache_workspace_bytes(const mi355_unet* net, int batch, int branch, int drift) {
+  if (!net || batch <= 0) { mi355_set_error("feature_cache_workspace_bytes: bad argument"); return -1; }
+  if (unet_cache_range(net, branch, nullptr, nullptr, nullptr)) { mi355_set_error(std::string("feature_cache_workspace_bytes: branch: ") + mi355_last_error()); return -1; }
+  LayoutSpec sp = plain_spec(batch);
+  if (drift) sp.feat_bytes = cache_feature_bytes(net, branch, batch);
+  return (int64_t)al256((size_t)layout_bytes(net, sp));
+}
+
 int mi355_cfm_euler_sample(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
                            const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch, void* workspace,
                            int64_t workspace_bytes, void* stream) {
@@ -622,16 +710,41 @@ int mi355_cfm_euler_sample(mi355_unet* net, float* x, int x_channels, const floa
                                        workspace, workspace_bytes, stream);
 }
 
+// mi355_cfm_euler_sample_labels and mi355_cfm_euler_sample_cached: one body, cache null for the first
+static int cfm_euler_run(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift, const int32_t* labels,
+                         const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes, void* stream,
+                         const mi355_feature_cache* cache);
+
 int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
                                   const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
                                   void* workspace, int64_t workspace_bytes, void* stream) {
+  return cfm_euler_run(net, x, x_channels, cond, cond_channels, cond_drift, labels, t_span_host, n_t, traj, u8_out, batch, workspace, workspace_bytes, stream,
+                       nullptr);
+}
+
+int mi355_cfm_euler_sample_cached(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
+                                  const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
+                                  void* workspace, int64_t workspace_bytes, void* stream, const mi355_feature_cache* cache) {
+  MI355_REQUIRE(net && x && t_span_host && n_t >= 1, -1, "cfm_euler_sample_cached: bad argument");
+  if (int rc = check_cache("cfm_euler_sample_cached", net, cache, (int64_t)n_t - 1)) return rc;
+  return cfm_euler_run(net, x, x_channels, cond, cond_channels, cond_drift, labels, t_span_host, n_t, traj, u8_out, batch, workspace, workspace_bytes, stream,
+                       cache);
+}
+
+static int cfm_euler_run(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift, const int32_t* labels,
+                         const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch, void* workspace, int64_t workspace_bytes, void* stream,
+                         const mi355_feature_cache* cache) {
   MI355_REQUIRE(net && x && t_span_host && n_t >= 1, -1, "cfm_euler_sample: bad argument");
   MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_euler_sample: class labels given to a net built without num_classes");
   MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_euler_sample: the vector field must have the state's channel count");
   Layout l;
-  if (int rc = carve(net, plain_spec(batch), workspace, workspace_bytes, l)) return rc;
+  LayoutSpec spec = plain_spec(batch);
+  if (cache && cache->drift_out) spec.feat_bytes = cache_feature_bytes(net, cache->branch, batch);
+  if (int rc = carve(net, spec, workspace, workspace_bytes, l)) return rc;
   const Scratch& sc = l.sc;
   hipStream_t s = S(stream);
+  CacheRun cr;
+  if (cache) { if (int rc = cr.init(net, cache, sc, l.feat_prev, batch, s)) return rc; }
   EvalEmb emb;   // t_span_host is the caller's array: no wait
   if (int rc = emb.init(net, sc, t_span_host, n_t - 1, labels != nullptr, false, s)) return rc;
   const int64_t n = (int64_t)batch * x_channels * net->cfg.image_size * net->cfg.image_size;
@@ -648,10 +761,10 @@ int mi355_cfm_euler_sample_labels(mi355_unet* net, float* x, int x_channels, con
     cond = cdrift;
   }
   int rc;
-  if (net->knobs.sampler_graph && emb.table() && !traj && !cdrift && !labels && n_t > 1)
+  if (net->knobs.sampler_graph && emb.table() && !traj && !cdrift && !labels && !cache && n_t > 1)
     rc = cfm_euler_graph(net, sc, emb, x, x_channels, cond, cond_channels, t_span_host, n_t, batch, n, workspace, s);
   else
-    rc = cfm_euler_loop(net, sc, emb, x, x_channels, cond, cond_channels, cdrift, t_span_host, n_t, traj, batch, n, nc, s, labels);
+    rc = cfm_euler_loop(net, sc, emb, x, x_channels, cond, cond_channels, cdrift, t_span_host, n_t, traj, batch, n, nc, s, labels, cache ? &cr : nullptr);
   if (rc) return rc;
   if (u8_out) return quantize_u8_launch(x, u8_out, n, s);
   return 0;
@@ -695,6 +808,19 @@ int mi355_ddpm_sample_sched(mi355_unet* net, float* x, int channels, const float
   MI355_REQUIRE(net && x && tb && opt, -1, "ddpm_sample_sched: null argument");
   DdpmCall c = ddpm_call("ddpm_sample_sched", batch, nullptr);
   if (int rc = check_schedule(c.who, tb, opt, sched, false, c.ls)) return rc;
+  c.th = sched_times(tb->Ns, sched); c.bare_size_refusal = true;
+  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
+}
+
+int mi355_ddpm_sample_sched_cached(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb,
+                                   const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched, const float* noise, int64_t n_noise_draws, int batch,
+                                   void* workspace, int64_t workspace_bytes, void* stream, const mi355_feature_cache* cache) {
+  MI355_REQUIRE(net && x && tb && opt, -1, "ddpm_sample_sched_cached: null argument");
+  DdpmCall c = ddpm_call("ddpm_sample_sched_cached", batch, nullptr);
+  if (int rc = check_schedule(c.who, tb, opt, sched, false, c.ls)) return rc;
+  if (int rc = check_cache(c.who, net, cache, ddpm_eval_count(tb, opt, c.ls))) return rc;
+  c.cache = cache;
+  if (cache->drift_out) c.spec.feat_bytes = cache_feature_bytes(net, cache->branch, batch);
   c.th = sched_times(tb->Ns, sched); c.bare_size_refusal = true;
   return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }

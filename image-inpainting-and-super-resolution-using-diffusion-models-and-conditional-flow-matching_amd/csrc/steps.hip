@@ -363,6 +363,68 @@ int mse_per_sample_launch(const float* a, const float* b, float* out, int batch,
   return 0;
 }
 
+// Per-image drift of a cached feature between two full evaluations (feature reuse across sampler steps, mi355_feature_cache::drift_out):
+//   out[b] = ||cur_b - prev_b||^2 / ||prev_b||^2,  then prev_b <- cur_b,
+// cur and prev [batch][per] in the plan's element type, read once each; the copy rides in the same pass.  Bandwidth-bound: one 512-thread
+// workgroup per image, 16-byte loads and stores, four fragments of each tensor in flight per thread; sums in fp32, one accumulator per
+// fragment element (a thread's chain is per / (512 * VEC) terms long), then the wave shuffle and eight LDS partials.  Every (image, fragment)
+// is read and written by one thread, in a fixed order: no atomics, bitwise reproducible.  prev == 0 everywhere: IEEE (inf, or NaN for 0 / 0).
+template <typename T>
+__global__ void __launch_bounds__(512) feature_drift_kernel(const T* __restrict__ cur, T* __restrict__ prev, float* out, int64_t per) {
+  constexpr int V = Elem<T>::VEC;
+  __shared__ float sh[2][8];
+  const u32x4* pc = reinterpret_cast<const u32x4*>(cur + (int64_t)blockIdx.x * per);
+  u32x4* pp = reinterpret_cast<u32x4*>(prev + (int64_t)blockIdx.x * per);
+  const int64_t nv = per / V;
+  float num[V], den[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) num[j] = den[j] = 0.f;
+  for (int64_t i0 = threadIdx.x; i0 < nv; i0 += 4 * 512) {
+    u32x4 c[4], p[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = i0 + u * 512;
+      if (i < nv) { c[u] = pc[i]; p[u] = pp[i]; }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = i0 + u * 512;
+      if (i >= nv) continue;
+      float fc[V], fp[V];
+      frag_to_float(c[u], fc, T()); frag_to_float(p[u], fp, T());
+#pragma unroll
+      for (int j = 0; j < V; ++j) { const float d = fc[j] - fp[j]; num[j] += d * d; den[j] += fp[j] * fp[j]; }
+      pp[i] = c[u];
+    }
+  }
+  float n = 0.f, d = 0.f;
+#pragma unroll
+  for (int j = 0; j < V; ++j) { n += num[j]; d += den[j]; }
+  for (int o = 32; o > 0; o >>= 1) { n += __shfl_xor(n, o); d += __shfl_xor(d, o); }
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = n; sh[1][threadIdx.x >> 6] = d; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    n = d = 0.f;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) { n += sh[0][w]; d += sh[1][w]; }
+    out[blockIdx.x] = n / d;
+  }
+}
+int feature_drift_launch(int dtype, const void* cur, void* prev, int batch, int64_t per, float* out, hipStream_t s) {
+  MI355_REQUIRE(cur && prev && out, -1, "feature_drift: null argument");
+  MI355_REQUIRE(cur != prev, -1, "feature_drift: cur and prev must be different buffers");
+  MI355_REQUIRE(batch > 0, -1, "feature_drift: batch must be positive");
+  const int vec = dtype == DT_F32 ? 4 : 8;
+  MI355_REQUIRE(per > 0 && per % vec == 0, -2, "feature_drift: elems_per_image must be a positive multiple of 16 bytes of elements");
+  MI355_REQUIRE(((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(prev)) & 15) == 0, -2, "feature_drift: cur and prev must be 16-byte aligned");
+  return dispatch_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(feature_drift_kernel<T>, dim3((unsigned)batch), dim3(512), 0, s, reinterpret_cast<const T*>(cur), reinterpret_cast<T*>(prev), out, per);
+    MI355_CHECK_HIP(hipGetLastError());
+    return 0;
+  });
+}
+
 // EMA of a parameter tensor: target = target * decay + source * (1 - decay)  (cifar10/utils_cifar.py:47-53), two separately
 // rounded products like the reference's eager expression (this file is compiled with fp contraction off).
 int ema_update_launch(float* target, const float* source, float decay, float one_minus_decay, int64_t n, hipStream_t s) {

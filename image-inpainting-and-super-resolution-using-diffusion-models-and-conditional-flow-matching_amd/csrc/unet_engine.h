@@ -81,6 +81,11 @@ struct mi355_unet {
   int in_tensor = -1, out_channels = 0;
   // stats per image
   double conv_flops = 0, attn_flops = 0, act_bytes = 0, weight_bytes = 0;
+  // Feature reuse across sampler steps (DeepCache).  The blocks of UNetModel as the plan lays them out: first plan op of input_blocks[i] and of
+  // output_blocks[i] (n of each), the tensor id of h entering output_blocks[i] (before its concat), and conv_flops + attn_flops planned before
+  // each of those ops.  Set by the plan walk, never changed afterwards (unet_cache_range reads them).
+  std::vector<int> in_block_op, out_block_op, out_block_h;
+  std::vector<double> in_block_flops, out_block_flops;
   int wsplit = 0;         // MI355_BF16X2: conv / qkv weights packed as hi | lo bf16 halves along K (ConvDesc::wsplit)
   int64_t launches = 0;   // device launches of one forward as planned (an upper bound: a GroupNorm pass a conv epilogue absorbed is not launched)
   mutable int64_t last_launches = 0;   // what the most recent forward really launched (0 before the first)
@@ -113,6 +118,11 @@ struct UnetRun {
   // emb_row set, emb_row is this step's block of a (step, class) table [num_classes][emb_total] and the images' rows are gathered from it
   // (one launch); without, the rows are computed from t and the labels (unet_embedding_rows_labels, the usual four launches)
   const int32_t* labels = nullptr;
+  // Feature reuse (DeepCache): 0 = the whole forward.  k in 1..n-1 (n = the net's input / output blocks) = a SHALLOW evaluation of branch k:
+  // input_blocks[0..k-1] on this call's x, then output_blocks[n-k..n-1] and out on the feature h that the most recent WHOLE forward on this
+  // workspace at this batch left in front of output_blocks[n-k].  The forward is resolved exactly as with 0; the plan ops of unet_cache_range
+  // are then not issued.  The caller's contract (not checkable here): that previous forward was a whole one.
+  int reuse_branch = 0;
   // optional per-op profiling (mi355_unet_profile)
   std::vector<mi355_op_profile>* prof = nullptr;
   std::vector<hipEvent_t>* prof_events = nullptr;
@@ -173,9 +183,17 @@ struct ResolvedForward {
   bool pack = true;                 // false: the first conv reads the caller's NCHW tensors itself (no pack_nhwc launch)
   std::vector<ForwardStep> steps;   // one per plan op, in plan order
   bool euler_in_conv = false;       // the last conv's epilogue applies UnetRun's Euler update
+  // UnetRun::reuse_branch: steps [skip_lo, skip_hi) are resolved (what they settle for later steps stands) but not issued; empty for a whole forward
+  size_t skip_lo = 0, skip_hi = 0;
+  bool issued(size_t i) const { return i < skip_lo || i >= skip_hi; }
 };
 int unet_resolve(const WsView& v, const float* x, int Cx, const float* cond, int Cc, float* out, const UnetRun& run, ResolvedForward* f);
 inline bool unet_step_launches(const ForwardStep& s) { return !std::holds_alternative<GnAbsorbed>(s) && !std::holds_alternative<ConvCarried>(s); }
+// Branch k of the feature cache: the plan ops [*lo, *hi) a shallow evaluation does not issue (input_blocks[k] .. the producer of the cached
+// feature) and the cached feature's tensor id.  n - 1 branches (unet_cache_branches).  k outside 1..n-1: MI355_ERR_ARG with a message.
+int unet_cache_branches(const mi355_unet* net);
+int unet_cache_range(const mi355_unet* net, int k, int* lo, int* hi, int* tensor);
+double unet_cache_retained_share(const mi355_unet* net, int k);   // of conv_flops + attn_flops, for a valid k
 int64_t unet_launch_count(const ResolvedForward& f);   // launches the issue pass makes (the sampler's Euler step not counted)
 // the plan alone, no host parameters and no weight image: the bytes that image would take, or < 0
 int64_t unet_plan_dry(const mi355_unet_config& cfg, mi355_unet* net);

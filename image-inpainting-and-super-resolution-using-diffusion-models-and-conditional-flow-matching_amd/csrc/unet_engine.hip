@@ -362,9 +362,18 @@ struct Walker {
     net->in_tensor = tensor(net->in_pad, S, S);
     int h = net->in_tensor;
     std::vector<int> hs;
+    bool in_open = true;   // the next block of the list opens an input_blocks[i] (each ends with its push)
     for (const Block& b : unet_blocks(cfg)) {
       int skip = -1;
       if (b.pop) { skip = hs.back(); hs.pop_back(); }
+      // the model's block boundaries (feature reuse, unet_cache_range): input_blocks[i] runs from here to its push, output_blocks[i] opens with its pop
+      const bool opens_in = in_open && b.prefix.rfind("input_blocks.", 0) == 0;
+      if (opens_in || b.pop) {
+        (b.pop ? net->out_block_op : net->in_block_op).push_back((int)net->ops.size());
+        (b.pop ? net->out_block_flops : net->in_block_flops).push_back(net->conv_flops + net->attn_flops);
+        if (b.pop) net->out_block_h.push_back(h);
+        in_open = false;
+      }
       switch (b.kind) {
         case BLK_CONV_IN: h = add_conv(b.prefix, h, -1, b.cin, b.cout, 3, CONV_UNIT, false, 0, 0, -1, -1, RES_NONE, OUT_NHWC); break;
         case BLK_RES: h = res_block(b.prefix, h, skip, b.cin, b.cout, b.dir > 0, b.dir < 0); break;
@@ -379,7 +388,7 @@ struct Walker {
           break;
       }
       if (!err.empty()) return -1;
-      if (b.push) hs.push_back(h);
+      if (b.push) { hs.push_back(h); in_open = true; }
     }
     // batched emb_layers: Wt [4mc][emb_total], bias [emb_total]
     const int K = 4 * mc;
@@ -471,6 +480,32 @@ static int check_plan(const mi355_unet* net) {
   return 0;
 }
 
+int unet_cache_branches(const mi355_unet* net) { return (int)net->in_block_op.size() - 1; }
+int unet_cache_range(const mi355_unet* net, int k, int* lo, int* hi, int* tensor) {
+  const int n = (int)net->in_block_op.size();
+  MI355_REQUIRE(k >= 1 && k <= n - 1, -1, "feature cache: branch must be in 1.." + std::to_string(n - 1) + " for this net (got " + std::to_string(k) + ")");
+  if (lo) *lo = net->in_block_op[k];
+  if (hi) *hi = net->out_block_op[n - k];
+  if (tensor) *tensor = net->out_block_h[n - k];
+  return 0;
+}
+double unet_cache_retained_share(const mi355_unet* net, int k) {
+  const int n = (int)net->in_block_op.size();
+  const double total = net->conv_flops + net->attn_flops;
+  return total > 0 ? 1.0 - (net->out_block_flops[n - k] - net->in_block_flops[k]) / total : 1.0;
+}
+// What unet_cache_range takes for granted: as many input as output blocks, and the op in front of each output block produces the h entering it.
+static int check_cache_blocks(const mi355_unet* net) {
+  const size_t n = net->in_block_op.size();
+  MI355_REQUIRE(n >= 1 && net->out_block_op.size() == n && net->out_block_h.size() == n, -4, "unet plan: input and output blocks do not pair up");
+  for (size_t i = 0; i < n; ++i) {
+    const int o = net->out_block_op[i];
+    MI355_REQUIRE(o >= 1 && net->ops[o - 1].dst == net->out_block_h[i] && (i == 0 || net->in_block_op[i] > net->in_block_op[i - 1]), -4,
+                  "unet plan: the op in front of an output block does not produce its input");
+  }
+  return 0;
+}
+
 static int run_walker(const mi355_unet_config& cfg, const float* const* host, mi355_unet* net, Walker& w) {
   // MI355_BF16X2 = bf16 storage and MFMAs with every conv / qkv weight held as hi + lo bf16 halves: from here on the plan is a bf16 plan with wsplit set
   // and MI355_F16 -> DT_F16: net->cfg.dtype holds the INTERNAL element-type code (ops.h) from here on
@@ -484,7 +519,8 @@ static int run_walker(const mi355_unet_config& cfg, const float* const* host, mi
   net->knobs = cfg.debug ? *cfg.debug : mi355_default_debug();
   net->cfg.debug = nullptr;
   if (w.walk() != 0 || !w.err.empty()) { mi355_set_error("unet plan: " + w.err); return -4; }
-  return check_plan(net);
+  if (int rc = check_plan(net)) return rc;
+  return check_cache_blocks(net);
 }
 
 int64_t unet_plan_dry(const mi355_unet_config& cfg, mi355_unet* net) {
@@ -930,13 +966,24 @@ int unet_resolve(const WsView& v, const float* x, int Cx, const float* cond, int
   f->emb = labelled ? (run.emb_row ? EMB_GATHER : EMB_LABELS) : (run.emb_row ? EMB_ROW : EMB_TIME);
   f->Be = run.t_uniform ? 1 : B; f->estride = run.t_uniform && !labelled ? 0 : net->emb_total;
   f->embp = f->emb == EMB_ROW ? run.emb_row : v.f32(v.l.embp);
+  int lo = 0, hi = 0;
+  if (run.reuse_branch) {   // refusals first: nothing is resolved, nothing launched
+    if (int rc = unet_cache_range(net, run.reuse_branch, &lo, &hi, nullptr)) return rc;
+    MI355_REQUIRE(!net->cfg.differentiable, -4, "feature cache: a differentiable plan cannot run a shallow evaluation (the backward pass would see activations of two forwards)");
+  }
   Resolver r{net, v, run, B, x, Cx, cond, Cc, out, f->embp, f->estride, {}, {}};
-  return r.resolve(f);
+  if (int rc = r.resolve(f)) return rc;
+  f->skip_lo = (size_t)lo; f->skip_hi = (size_t)hi;
+  // The cached feature is read raw across the cut (the popping ResBlock's skip conv always reads it: cin != cout over a concat), so the whole
+  // forward that produced it stored it as the reference defines it; a plan in which it did not cannot be cut here.
+  if (hi && (is<ConvStep>(f->steps[hi - 1]) || is<ConvCarried>(f->steps[hi - 1])))
+    MI355_REQUIRE(tensor_state_of(f->steps[hi - 1]) == 0, -4, "feature cache: the producer of the cached feature does not store it as the reference defines it");
+  return 0;
 }
 
 int64_t unet_launch_count(const ResolvedForward& f) {
   int64_t n = (f.emb == EMB_ROW ? 0 : f.emb == EMB_GATHER ? 1 : 4) + (f.pack ? 1 : 0);
-  for (const ForwardStep& s : f.steps) n += unet_step_launches(s);
+  for (size_t i = 0; i < f.steps.size(); ++i) n += f.issued(i) && unet_step_launches(f.steps[i]);
   return n;
 }
 
@@ -957,6 +1004,7 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
   if (!f.pack && (size_t)net->in_tensor < net->tensor_state_n) net->tensor_state[net->in_tensor].store((char)1, std::memory_order_relaxed);
   for (size_t i = 0; i < f.steps.size(); ++i) {
     const PlanOp& op = net->ops[i];
+    if (!f.issued(i)) continue;   // a shallow evaluation: the tensor keeps what the whole forward left, and its record
     if (op.kind == OP_CONV && op.dst >= 0 && (size_t)op.dst < net->tensor_state_n) net->tensor_state[op.dst].store(tensor_state_of(f.steps[i]), std::memory_order_relaxed);
   }
 
@@ -978,6 +1026,7 @@ int unet_forward(const mi355_unet* net, const float* x, int Cx, const float* con
   if (f.pack && (rc = pack_nhwc_launch(net->cfg.dtype, x, Cx, cond, cond ? Cc : 0, B, S * S, net->in_pad, v.tensor(net->in_tensor), stream))) return rc;
   if (run.prof) { mi355_op_profile r{}; r.kind = MI355_OP_PRELUDE; mark(r); }
   for (size_t i = 0; i < f.steps.size(); ++i) {
+    if (!f.issued(i)) continue;
     if ((rc = std::visit([&](const auto& d) { return issue(d, stream); }, f.steps[i]))) return rc;
     if (run.prof) mark(profile_record(net, net->ops[i], f.steps[i], B));
   }

@@ -265,8 +265,38 @@ def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corre
     return process_x0(xi)
 
 
+class FeatureCache:
+    """Feature reuse across the network evaluations of a sampler (DeepCache: Ma, Fang, Wang, CVPR 2024; training-free; BUILD-DEFINED
+    EXTENSION, no reference counterpart): the deep features of the U-Net are recomputed on a schedule and reused in between, only the
+    `branch` outermost block pairs run at every evaluation.  interval=N: one full evaluation in N (full at evaluation e iff e % N == 0);
+    schedule: the explicit list, one truth value per evaluation in loop order (correctors included; the first must be true); branch: 1..n-1,
+    see UNetEngine.cache_branches() for what each branch keeps and costs.  Taken by the sample functions that end in UNetEngine.ddpm_sample
+    (prior, amortized, replacement / RePaint, DDIM, on respaced chains too): as feature_cache= of get_prior_sample_fn and
+    get_conditional_sample_fn, or carried by the chain, ddpm.with_feature_cache(FeatureCache(...)), which get_ddim_sample_fn reads as well;
+    the guided, reconstruction-guided, multistep and shaped loops refuse it.  Sample quality under feature reuse is untested (no trained checkpoint is at hand); the arithmetic
+    is tested against an fp64 / fp32 restatement."""
+
+    def __init__(self, interval=None, schedule=None, branch=1):
+        if (interval is None) == (schedule is None):
+            raise ValueError("FeatureCache needs exactly one of interval= and schedule=")
+        self.interval, self.schedule, self.branch = interval, (None if schedule is None else tuple(bool(f) for f in schedule)), int(branch)
+
+    def kwargs(self):
+        return dict(cache_interval=self.interval, cache_schedule=self.schedule, cache_branch=self.branch)
+
+
+def _cache_of(ddpm, feature_cache=None):
+    """The cache a sample function runs under: its own argument, else the chain's (DDPM.with_feature_cache)."""
+    return feature_cache if feature_cache is not None else getattr(ddpm, "feature_cache", None)
+
+
+def _refuse_feature_cache(feature_cache, loop: str):
+    if feature_cache is not None:
+        raise NotImplementedError(f"feature_cache is not built for {loop} (it runs with the prior, amortized, replacement / RePaint and DDIM samplers)")
+
+
 def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_fraction=1.0, noise_condition=True,
-              pad_value=-2.0, none_value=-2.0, guidance_scale=None, ddim_sigma=None, walk=None):
+              pad_value=-2.0, none_value=-2.0, guidance_scale=None, ddim_sigma=None, walk=None, feature_cache=None):
     global _draw_counter
     xi = xT.detach().clone().float().contiguous()
     noise = None
@@ -285,6 +315,13 @@ def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_f
               start_fraction=float(start_fraction), noise_condition=bool(noise_condition), pad_value=float(pad_value), none_value=float(none_value),
               seed=seed, guidance_scale=guidance_scale, **sched)
     shaping = _shaping_of(ddpm, guidance_scale is not None)
+    feature_cache = _cache_of(ddpm, feature_cache)
+    if feature_cache is not None:
+        if guidance_scale is not None:
+            _refuse_feature_cache(feature_cache, "the guided (classifier-free guidance) loops")
+        if shaping is not None:
+            _refuse_feature_cache(feature_cache, "the shaped loops (DDPM.with_x0_shaping)")
+        kw.update(feature_cache.kwargs())
     if shaping is not None:   # the same loop with per-image shaping of x0_hat: mi355_ddpm_shaped_sample
         engine.ddpm_shaped(xi, _tables(ddpm), shaping, **kw)
     else:
@@ -294,15 +331,24 @@ def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_f
 
 # Prior sampling ------------------------------------------------------------------------------------
 
-def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood):
-    """sampling.py:50-75.  Under Amortized conditioning the net is fed `likelihood.none_like` (sampling.py:36-37)."""
+def _need_fused(engine, feature_cache):
+    if feature_cache is not None and engine is None:
+        raise NotImplementedError("feature_cache runs inside the fused loop: pass an eps_model built by make_eps_model(network, ddpm) for this "
+                                  "schedule and device tensors (an arbitrary callable is evaluated whole)")
+
+
+def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood, feature_cache=None):
+    """sampling.py:50-75.  Under Amortized conditioning the net is fed `likelihood.none_like` (sampling.py:36-37).
+    feature_cache (None: untouched): a FeatureCache."""
     amortized = isinstance(conditioning, Amortized)
+    feature_cache = _cache_of(ddpm, feature_cache)
 
     @torch.no_grad()
     def sample(xT):
         engine = _fast_engine(eps_model, ddpm, xT)
+        _need_fused(engine, feature_cache)
         if engine is not None:
-            return _run_fast(engine, ddpm, xT, _lib.DDPM_PRIOR, None, none_value=_none_value(likelihood, xT))
+            return _run_fast(engine, ddpm, xT, _lib.DDPM_PRIOR, None, none_value=_none_value(likelihood, xT), feature_cache=feature_cache)
         none = likelihood.none_like(xT) if amortized else None
         return _run_generic(eps_model, ddpm, xT, amortized=amortized, cond_pred=none, cond_corr=none)
 
@@ -311,22 +357,27 @@ def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Condition
 
 # Conditional sampling ---------------------------------------------------------------------------------
 
-def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood):
+def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood, feature_cache=None):
+    """feature_cache (None: the chain's, ddpm.feature_cache; neither: untouched): a FeatureCache; Amortized, Replacement and RePaint take it, the
+    other conditionings refuse it by name."""
+    feature_cache = _cache_of(ddpm, feature_cache)
     if isinstance(conditioning, ClassifierFreeGuidance):   # (an Amortized: before it)
+        _refuse_feature_cache(feature_cache, "ClassifierFreeGuidance (the guided loops)")
         return _cfg_sample_fn(eps_model, ddpm, conditioning, likelihood)
     if isinstance(conditioning, Amortized):
-        return _amortized_sample_fn(eps_model, ddpm, conditioning, likelihood)
+        return _amortized_sample_fn(eps_model, ddpm, conditioning, likelihood, feature_cache)
     if isinstance(conditioning, RePaint):   # (a Replacement: before it)
         return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, walk=repaint_walk(ddpm.Ns, conditioning.jump_length,
-                                                                                                   conditioning.n_resample))
+                                                                                                   conditioning.n_resample), feature_cache=feature_cache)
     if isinstance(conditioning, Replacement):
-        return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood)
+        return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, feature_cache=feature_cache)
     if isinstance(conditioning, ReconstructionGuidance):
+        _refuse_feature_cache(feature_cache, "ReconstructionGuidance (the backward pass needs a whole forward)")
         return _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning, likelihood)
     raise NotImplementedError(f"no sampler for conditioning type {type(conditioning).__name__}")
 
 
-def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood):
+def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood, feature_cache=None):
     """sampling.py:80-133.  The corrector calls the x0 model WITHOUT the condition (sampling.py:116), so the
     network sees none_like there - reproduced."""
 
@@ -334,9 +385,10 @@ def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood):
     def sample(xT, condition):
         condition = condition.to(xT.device).float().contiguous()
         engine = _fast_engine(eps_model, ddpm, xT)
+        _need_fused(engine, feature_cache)
         if engine is not None:
             return _run_fast(engine, ddpm, xT, _lib.DDPM_AMORTIZED, condition, n_corrector=conditioning.n_corrector,
-                             delta=conditioning.delta, none_value=_none_value(likelihood, xT))
+                             delta=conditioning.delta, none_value=_none_value(likelihood, xT), feature_cache=feature_cache)
         return _run_generic(eps_model, ddpm, xT, amortized=True, cond_pred=condition, cond_corr=likelihood.none_like(xT),
                             n_corrector=conditioning.n_corrector, delta=conditioning.delta)
 
@@ -434,7 +486,7 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
     return sample
 
 
-def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihood, walk=None):
+def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihood, walk=None, feature_cache=None):
     """sampling.py:209-260: overwrite the known pixels with the (noised) condition before each predictor step.
     walk (RePaint; None: the plain descent): the levels to visit, conditioning.repaint_walk; a move up re-noises the state by
     q(x_k | x_{k-1}) (mi355_renoise_step), a move down is the replacement step of its level.  A walk without upward moves is the plain descent."""
@@ -446,10 +498,11 @@ def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihoo
         condition = condition.to(xT.device).float().contiguous()
         pad = float(likelihood.pad_value)
         engine = _fast_engine(eps_model, ddpm, xT)
+        _need_fused(engine, feature_cache)
         if engine is not None:
             return _run_fast(engine, ddpm, xT, _lib.DDPM_REPLACEMENT, condition, n_corrector=conditioning.n_corrector,
                              delta=conditioning.delta, start_fraction=conditioning.start_fraction,
-                             noise_condition=conditioning.noise, pad_value=pad, walk=walk)
+                             noise_condition=conditioning.noise, pad_value=pad, walk=walk, feature_cache=feature_cache)
         rep = dict(condition=condition, start_fraction=conditioning.start_fraction, noise=bool(conditioning.noise), pad_value=pad)
         return _run_generic(eps_model, ddpm, xT, amortized=False, cond_pred=None, cond_corr=None, replacement=rep,
                             n_corrector=conditioning.n_corrector, delta=conditioning.delta, walk=walk)
@@ -465,6 +518,7 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
     ddpm.respace(ddpm.logsnr_steps(K)).  guidance_scale (None: unguided): classifier-free guidance of eps against the none_like condition; needs
     a condition.  Fused path (eps_model built by make_eps_model for this very schedule): the whole loop in mi355_ddpm_multistep_sample; any other
     callable: a host loop over dpmpp_step_ (guided: cfg_combine, then the step).  Sample quality is untested."""
+    _refuse_feature_cache(_cache_of(ddpm), "the DPM-Solver++ multistep loops")
     coefs = ddpm.dpm_solver_coefs(order)
     cx, c0, c1 = (c.tolist() for c in coefs)
     shaping = _shaping_of(ddpm, guidance_scale is not None)
@@ -517,6 +571,9 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
     guidance_scale (None: unguided): classifier-free guidance of eps against the none_like condition; needs a condition.
     eta (0: the deterministic sampler, untouched): stochastic DDIM with sigma = ddpm.ddim_sigma(eta), one noise draw per step with i > 0;
     eta = 1 has the ancestral step's mean and variance.  On a RespacedDDPM this is DDIM on a sub-sequence of the training steps."""
+    feature_cache = _cache_of(ddpm)   # DDPM.with_feature_cache: feature reuse across the steps (the fused path only; not under guidance)
+    if guidance_scale is not None:
+        _refuse_feature_cache(feature_cache, "the guided (classifier-free guidance) loops")
     eta = float(eta)
     if not (math.isfinite(eta) and eta >= 0.0):
         raise ValueError(f"eta must be finite and >= 0, got {eta!r}")
@@ -531,9 +588,11 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
             condition = condition.to(xT.device).float().contiguous()
         if guidance_scale is not None and condition is None:
             raise ValueError("guidance_scale needs a condition to guide towards")
+        _need_fused(engine, feature_cache)
         if engine is not None:
             nv = _none_value(likelihood, xT) if likelihood is not None else 0.0
-            return _run_fast(engine, ddpm, xT, _lib.DDIM, condition, none_value=nv, guidance_scale=guidance_scale, ddim_sigma=sigma)
+            return _run_fast(engine, ddpm, xT, _lib.DDIM, condition, none_value=nv, guidance_scale=guidance_scale, ddim_sigma=sigma,
+                             feature_cache=feature_cache)
         if guidance_scale is not None:
             none = likelihood.none_like(xT) if likelihood is not None else torch.zeros_like(condition)
             return _run_generic_cfg(eps_model, ddpm, xT, cond=condition, none=none, guidance_scale=guidance_scale, ddim=True, ddim_sigma=sigma)

@@ -78,6 +78,7 @@ class DDPM(nn.Module):
     (betas[-1] = 20/Ns >= 1): this is reproduced, not repaired (SURVEY.md finding 4)."""
 
     x0_shaping: Optional[X0Shaping] = None   # set on the views of with_x0_shaping
+    feature_cache = None                     # set on the views of with_feature_cache (a sampling.FeatureCache)
 
     def __init__(self, Ns: int):
         super().__init__()
@@ -219,11 +220,24 @@ class DDPM(nn.Module):
         max_threshold), x0_hat <- clamp(x0_hat, -s, s) / s (Saharia et al. 2022, Imagen, section 2.3).  guidance_rescale: phi in [0, 1], the guided
         eps is scaled by phi * std(eps_c) / std(eps_g) + 1 - phi per image (Lin et al. 2023, section 3.4); guided samplers only.  Commutes with
         respace.  All off: a view without shaping.  The corrector and the final clip keep the static clip.  Sample quality is untested."""
+        view = self._view()
+        view.__dict__["x0_shaping"] = _x0_shaping(dynamic_threshold, max_threshold, guidance_rescale)
+        return view
+
+    def with_feature_cache(self, feature_cache) -> "DDPM":
+        """BUILD-DEFINED EXTENSION (no reference counterpart): a view of this chain - the same buffers, the same steps - whose fused samplers
+        reuse the U-Net's deep features across evaluations (DeepCache; feature_cache: a sampling.FeatureCache, or None for a view without
+        one).  The sample functions that end in UNetEngine.ddpm_sample (prior, amortized, replacement / RePaint, DDIM) honour it, the others
+        refuse such a chain by name.  Commutes with respace.  Sample quality is untested."""
+        view = self._view()
+        view.__dict__["feature_cache"] = feature_cache
+        return view
+
+    def _view(self) -> "DDPM":
         view = copy.copy(self)
         # its own registries over the same tensors: moving the view does not re-point the base's buffers
         view.__dict__["_buffers"] = self._buffers.copy()
         view.__dict__["_non_persistent_buffers_set"] = set(self._non_persistent_buffers_set)
-        view.__dict__["x0_shaping"] = _x0_shaping(dynamic_threshold, max_threshold, guidance_rescale)
         return view
 
     def respace(self, timesteps) -> "RespacedDDPM":
@@ -284,6 +298,7 @@ class RespacedDDPM(DDPM):
         self.Ns = len(steps)
         self.tmin, self.tmax, self.ts = base.tmin, base.tmax, base.ts
         self.x0_shaping = getattr(base, "x0_shaping", None)   # a shaped base's respacing stays shaped
+        self.feature_cache = getattr(base, "feature_cache", None)
         acp32 = base.alphas_cumprod.detach().to("cpu", torch.float32)[list(steps)]
         if not bool(torch.all(torch.isfinite(acp32) & (acp32 > 0))):
             raise ValueError("the base's alphas_cumprod is not finite and positive at every kept step (DDPM(Ns <= 20) is not respaced)")

@@ -118,6 +118,21 @@ class X0ShapingC(C.Structure):
     _fields_ = [("quantile", C.c_float), ("max_threshold", C.c_float), ("rescale_phi", C.c_float)]
 
 
+class FeatureCacheC(C.Structure):
+    """mi355_feature_cache (include/mi355_sampler.h): the branch and the full / shallow schedule of a sampler loop under feature reuse."""
+    _fields_ = [("branch", C.c_int32), ("n_evals", C.c_int32), ("full", C.POINTER(C.c_uint8)), ("drift_out", _FP)]
+
+
+def feature_cache(branch, full, drift_ptr=None):
+    """branch k and a sequence of truth values, one per evaluation -> FeatureCacheC (the byte array is kept alive by the struct).
+    drift_ptr: the address of a device float[len(full)][B] for drift_out, or None."""
+    full = [1 if f else 0 for f in full]
+    arr = (C.c_uint8 * max(1, len(full)))(*full)
+    fc = FeatureCacheC(int(branch), len(full), C.cast(arr, C.POINTER(C.c_uint8)), C.cast(C.c_void_p(drift_ptr), _FP) if drift_ptr else None)
+    fc._keepalive = arr
+    return fc
+
+
 def x0_shaping(shaping):
     """None, an object with dynamic_threshold / max_threshold / guidance_rescale (DDPM.x0_shaping), or a (quantile, max_threshold, rescale_phi)
     triple -> X0ShapingC or None.  None stands for "off" in each place."""
@@ -146,6 +161,13 @@ SIGNATURES = {
     "mi355_unet_forward": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_unet_forward_t": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _I, _VP, _I64, _VP]),
     "mi355_unet_forward_labels": (_I, [_VP, _VP, _I, _VP, _I, _VP, _F, _VP, _VP, _I, _VP, _I64, _VP]),
+    "mi355_unet_cache_info": (_I, [C.POINTER(UNetConfigC), _I, C.POINTER(C.c_int32)]),
+    "mi355_unet_forward_cached": (_I, [_VP, _VP, _I, _VP, _I, _VP, _F, _VP, _VP, _I, _VP, _I64, _VP, _I]),
+    "mi355_cfm_euler_sample_cached": (_I, [_VP, _VP, _I, _VP, _I, _I, _VP, _FP, _I, _VP, _VP, _I, _VP, _I64, _VP, C.POINTER(FeatureCacheC)]),
+    "mi355_ddpm_sample_sched_cached": (_I, [_VP, _VP, _I, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), C.POINTER(DDPMScheduleC), _VP, _I64, _I,
+                                            _VP, _I64, _VP, C.POINTER(FeatureCacheC)]),
+    "mi355_feature_cache_workspace_bytes": (_I64, [_VP, _I, _I, _I]),
+    "mi355_feature_drift": (_I, [_VP, _VP, _I, _I, _I64, _VP, _VP]),
     "mi355_unet_vjp": (_I, [_VP, _VP, _VP, _I, _I, _VP, _I64, _VP]),
     "mi355_unet_plan_op": (_I, [_VP, _I, C.POINTER(C.c_int32)]),
     "mi355_unet_read_tensor": (_I, [_VP, _I, _I, _VP, _I, _VP, _I64, _VP]),

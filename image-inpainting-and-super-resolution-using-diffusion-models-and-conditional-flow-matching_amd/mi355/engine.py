@@ -47,6 +47,43 @@ def _tableau_arrays(tableau):
     return stages, (C.c_float * (stages * stages))(*[v for row in a for v in row]), (C.c_float * stages)(*b), (C.c_float * stages)(*c)
 
 
+def feature_cache_args(n_evals, interval=None, branch=None, schedule=None, guidance_scale=None):
+    """The feature-cache arguments of a sampler that makes n_evals network evaluations (an int, or a callable that counts them: asked only
+    when a cache is given) -> None (no cache: today's code path) or
+    (branch k, [full_0, ..., full_{n_evals-1}]).  interval=N is DeepCache's uniform 1:N schedule full[e] = (e % N == 0); schedule is the
+    explicit list, one truth value per evaluation in loop order; branch defaults to 1."""
+    if interval is None and schedule is None:
+        if branch is not None:
+            raise ValueError("cache_branch needs a schedule: give cache_interval or cache_schedule")
+        return None
+    if interval is not None and schedule is not None:
+        raise ValueError("cache_interval and cache_schedule both given: a run follows one schedule")
+    if guidance_scale is not None:
+        raise NotImplementedError("feature caching is not built for the guided (classifier-free guidance) loops yet; nor for the Runge-Kutta / "
+                                  "Adams-Bashforth, multistep, shaped, reconstruction and SF2M loops")
+    n_evals = n_evals() if callable(n_evals) else n_evals
+    k = 1 if branch is None else int(branch)
+    if k < 1:
+        raise ValueError(f"cache_branch must be >= 1, got {branch}")
+    if interval is not None:
+        if int(interval) != interval or int(interval) < 1:
+            raise ValueError(f"cache_interval must be an integer >= 1, got {interval}")
+        full = [e % int(interval) == 0 for e in range(n_evals)]
+    else:
+        full = [bool(f) for f in schedule]
+        if len(full) != n_evals:
+            raise ValueError(f"cache_schedule must have one entry per network evaluation ({n_evals}), got {len(full)}")
+        if full and not full[0]:
+            raise ValueError("cache_schedule[0] must be true: the first evaluation has nothing to reuse")
+    return k, full
+
+
+def ddpm_eval_count(K: int, mode: int, n_corrector: int, walk=None) -> int:
+    """The network evaluations of one DDPM run, in loop order: one per downward move and, in the ancestral modes, n_corrector behind each."""
+    down = K if walk is None else sum(1 for a, b in zip(walk, list(walk)[1:]) if b < a)
+    return down * (1 + (0 if mode == _lib.DDIM else max(0, int(n_corrector))))
+
+
 class UNetEngine:
     def __init__(self, cfg_kwargs: dict, state_dict: Dict[str, torch.Tensor], device, precision: str = "bf16", differentiable: bool = False,
                  debug=None):
@@ -78,7 +115,8 @@ class UNetEngine:
         self.handle = handle
         self._ws: Optional[torch.Tensor] = None
         self._ws_bytes: Dict[tuple, int] = {}   # sizes of the samplers' workspaces with tail buffers, per (size function, its arguments)
-        self._fwd_state = None   # (batch, workspace pointer) of the last forward(): what vjp() differentiates
+        self._fwd = None          # (batch, workspace pointer) of the last forward(): what vjp() differentiates
+        self._full_state = None   # (batch, workspace pointer) while that workspace holds a full evaluation at that batch: what forward_cached() reuses
         self.in_channels = self.cfg.in_channels
         self.out_channels = self.cfg.out_channels
         self.image_size = self.cfg.image_size
@@ -91,6 +129,17 @@ class UNetEngine:
                 self.handle = None
         except Exception:
             pass
+
+    # every method that runs the net resets _fwd_state to None; the feature cache's mark goes with it (only forward() / forward_cached() set it again)
+    @property
+    def _fwd_state(self):
+        return self._fwd
+
+    @_fwd_state.setter
+    def _fwd_state(self, v):
+        self._fwd = v
+        if v is None:
+            self._full_state = None
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -229,7 +278,49 @@ class UNetEngine:
             check(self.L.mi355_unet_forward_t(self.handle, xp, Cx, cp, Cc, float(t), op, B, ws, wsb, self._stream()), "mi355_unet_forward_t")
         else:
             check(self.L.mi355_unet_forward(self.handle, xp, Cx, cp, Cc, tp, op, B, ws, wsb, self._stream()), "mi355_unet_forward")
-        self._fwd_state = (B, self._ws.data_ptr())
+        self._fwd_state = self._full_state = (B, self._ws.data_ptr())
+        return out
+
+    def cache_branches(self):
+        """The feature-cache branches of this net (mi355_unet_cache_info), one dict per branch k = 1..n-1: branch, skip_ops (the plan-op range
+        [lo, hi) a shallow evaluation does not issue), tensor (the cached feature's id), shape (C, H, W) and retained_flops (the share of the
+        conv + attention FLOPs a shallow evaluation still does).  A schedule with one full evaluation in N costs about
+        (1 + (N - 1) * retained_flops) / N of the uncached FLOPs."""
+        buf = (C.c_int32 * 8)()
+        check(self.L.mi355_unet_cache_info(C.byref(self.cfg), 0, buf), "mi355_unet_cache_info")
+        out = []
+        for k in range(1, int(buf[0]) + 1):
+            check(self.L.mi355_unet_cache_info(C.byref(self.cfg), k, buf), "mi355_unet_cache_info")
+            out.append({"branch": k, "skip_ops": (int(buf[1]), int(buf[2])), "tensor": int(buf[3]), "shape": (int(buf[4]), int(buf[5]), int(buf[6])),
+                        "retained_flops": buf[7] / 1e6})
+        return out
+
+    def forward_cached(self, x: torch.Tensor, t, cond: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                       y: Optional[torch.Tensor] = None, *, branch: int):
+        """forward() under the feature cache (mi355_unet_forward_cached).  branch=0: a full evaluation (as forward()); branch=k: a shallow one,
+        which recomputes the k outermost block pairs on this x and t and reuses the feature the last full evaluation left in this engine's
+        workspace.  Raises MI355BackendError unless that workspace still holds a full evaluation at this batch (forward() or
+        forward_cached(branch=0), with nothing but shallow evaluations since)."""
+        B, Cx, Cc = self._split(x, cond)
+        lab, lab_p = self._labels(y, B)
+        host_t = isinstance(t, (int, float))
+        if not host_t and t.shape != (B,):
+            raise ValueError(f"timesteps must have shape ({B},)")
+        if out is None:
+            out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
+        ws, wsb = self.workspace(B)
+        state = (B, self._ws.data_ptr())
+        if branch and self._full_state != state:
+            raise MI355BackendError("forward_cached: this engine's workspace does not hold a full evaluation at this batch (run forward() or "
+                                    "forward_cached(branch=0) first; any other call that runs the net, or another batch, discards it)")
+        xp, cp = self._chk(x, "x"), self._chk(cond, "condition") if cond is not None else None
+        tp, op = None if host_t else self._chk(t, "timesteps"), self._chk(out, "out")
+        self._fwd_state = None
+        check(self.L.mi355_unet_forward_cached(self.handle, xp, Cx, cp, Cc, tp, float(t) if host_t else 0.0, lab_p, op, B, ws, wsb, self._stream(),
+                                               int(branch)), "mi355_unet_forward_cached")
+        self._full_state = state
+        if not branch:
+            self._fwd_state = state
         return out
 
     def vjp(self, grad_out: torch.Tensor, x_channels: Optional[int] = None, out: Optional[torch.Tensor] = None):
@@ -353,14 +444,22 @@ class UNetEngine:
 
     def cfm_euler(self, x: torch.Tensor, t_span: Sequence[float], cond: Optional[torch.Tensor] = None, keep_traj: bool = False,
                   want_u8: bool = False, cond_drift: bool = False, y: Optional[torch.Tensor] = None, guidance_scale=None,
-                  null_label: Optional[int] = None, none_value: float = -2.0):
+                  null_label: Optional[int] = None, none_value: float = -2.0, cache_interval=None, cache_branch=None, cache_schedule=None,
+                  cache_drift: bool = False):
         """In-place Euler integration of x over t_span (host floats).  Returns (x, traj or None, u8 or None).
+        cache_interval / cache_branch / cache_schedule (all None: the paths below, untouched): feature reuse across steps (DeepCache;
+        mi355_cfm_euler_sample_cached).  Step k is evaluation k; see mi355.engine.feature_cache_args and cache_branches().  Not with guidance_scale.
+        cache_drift=True (needs a schedule; cache_interval=1 measures every step): also returns, as a fourth value, the [n_steps, B] tensor of
+        ||F_e - F_prev||^2 / ||F_prev||^2 per image between consecutive full evaluations (-1 in the rows of shallow evaluations and of the first).
         cond_drift: the condition is integrated with derivative `cond` (the concatenated-state sampler of
         mnist/utils_mnist2.py:118-138); the caller's tensor is not modified.
         A batch beyond max_batch() is integrated in slices (every image's trajectory is independent of its batch mates; the kernels chosen for a
         slice may sum in another order than those of the whole batch would).
         y: class labels [B] of a class-conditional engine: every step evaluates model(t_k, x_k, y) (mi355_cfm_euler_sample_labels).
         guidance_scale (a float or a [B] tensor; None: the paths above, untouched): classifier-free guidance, see cfm_cfg."""
+        cache = feature_cache_args(max(0, len(t_span) - 1), cache_interval, cache_branch, cache_schedule, guidance_scale)
+        if cache_drift and cache is None:
+            raise ValueError("cache_drift measures the cached feature: give cache_interval or cache_schedule (cache_interval=1: every step)")
         if guidance_scale is not None:
             if cond_drift:
                 raise NotImplementedError("cond_drift (the drifting condition of the concatenated-state sampler) is not built with guidance")
@@ -370,17 +469,30 @@ class UNetEngine:
         mb = self.max_batch()
         traj, u8 = self._traj_u8(x, len(t_span), keep_traj, want_u8)
         if B > mb:
+            drifts = []
             for lo, hi, _ in _slices(B, mb):
-                _, tr, u = self.cfm_euler(x[lo:hi], t_span, _cut(cond, lo, hi), keep_traj, want_u8, cond_drift, _cut(lab, lo, hi))
+                r = self.cfm_euler(x[lo:hi], t_span, _cut(cond, lo, hi), keep_traj, want_u8, cond_drift, _cut(lab, lo, hi),
+                                   cache_interval=cache_interval, cache_branch=cache_branch, cache_schedule=cache_schedule, cache_drift=cache_drift)
                 if traj is not None:
-                    traj[:, lo:hi] = tr
+                    traj[:, lo:hi] = r[1]
                 if u8 is not None:
-                    u8[lo:hi] = u
-            return x, traj, u8
+                    u8[lo:hi] = r[2]
+                drifts.append(r[3] if cache_drift else None)
+            return (x, traj, u8, torch.cat(drifts, dim=1)) if cache_drift else (x, traj, u8)
         ts = [float(v) for v in t_span]
         arr = (C.c_float * len(ts))(*ts)
         self._fwd_state = None
         ws, wsb = self.workspace(B)
+        if cache is not None:
+            drift = torch.empty(len(cache[1]), B, device=self.device, dtype=torch.float32) if cache_drift else None
+            if cache_drift:
+                ws, wsb = self._workspace_sized("mi355_feature_cache_workspace_bytes", B, cache[0], 1)
+            fc = _lib.feature_cache(*cache, drift_ptr=drift.data_ptr() if drift is not None and drift.numel() else None)
+            check(self.L.mi355_cfm_euler_sample_cached(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
+                                                       Cc, int(bool(cond_drift)), lab_p, arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
+                                                       self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream(),
+                                                       C.byref(fc)), "mi355_cfm_euler_sample_cached")
+            return (x, traj, u8, drift) if cache_drift else (x, traj, u8)
         if lab is not None:
             check(self.L.mi355_cfm_euler_sample_labels(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
                                                        Cc, int(bool(cond_drift)), lab_p, arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
@@ -612,9 +724,13 @@ class UNetEngine:
 
     def ddpm_sample(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], *, mode: int, cond: Optional[torch.Tensor] = None,
                     noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0,
-                    noise_condition=True, pad_value=-2.0, none_value=-2.0, seed=0, guidance_scale=None, y: Optional[torch.Tensor] = None,
-                    null_label: Optional[int] = None, timesteps=None, train_steps=None, ddim_sigma=None, walk=None):
+                    noise_condition=True, pad_value=-2.0, none_value=-2.0, seed=0, guidance_scale=None, cache_interval=None, cache_branch=None,
+                    cache_schedule=None, y: Optional[torch.Tensor] = None, null_label: Optional[int] = None, timesteps=None, train_steps=None,
+                    ddim_sigma=None, walk=None):
         """In-place reverse-denoising loop.  tables: name -> CPU fp32 tensor [Ns] (DDPM buffers).
+        cache_interval / cache_branch / cache_schedule (all None: the paths below, untouched): feature reuse across evaluations (DeepCache;
+        mi355_ddpm_sample_sched_cached; an unscheduled call runs as the identity schedule, which is bit-identical).  Evaluations are numbered in loop
+        order, correctors included (ddpm_eval_count); see mi355.engine.feature_cache_args and cache_branches().  Not with guidance_scale.
         timesteps / train_steps (both or neither; None: exactly the unscheduled calls): `tables` are the K respaced tables of a RespacedDDPM, step k
         sits at training index timesteps[k] of train_steps (mi355_ddpm_sample_sched / mi355_ddpm_cfg_sample_sched).  With them, ddim_sigma ([K] floats,
         DDIM mode: the DDIM(eta) step) and walk (levels K, ..., 0 moving by +-1, e.g. conditioning.repaint_walk; upward moves re-noise with
@@ -628,6 +744,11 @@ class UNetEngine:
         if guidance_scale is None and y is not None:
             raise NotImplementedError("ddpm_sample takes class labels on the guided path only (guidance_scale=)")
         sched = self._ddpm_schedule(tables, timesteps, train_steps, ddim_sigma, walk)
+        cache = feature_cache_args(lambda: ddpm_eval_count(int(tables["alphas_cumprod_prev"].numel()), mode, n_corrector, walk), cache_interval,
+                                   cache_branch, cache_schedule, guidance_scale)
+        if cache is not None and sched is None:   # the cached loop is the scheduled one: steps 0..K-1 of K is the unscheduled loop bit for bit
+            K = int(tables["alphas_cumprod_prev"].numel())
+            sched = self._ddpm_schedule(tables, list(range(K)), K, None, None)
         if noise is not None and noise.shape[1:] != x.shape:
             raise ValueError("injected noise must be [n_draws, B, C, H, W]")
         if guidance_scale is not None:
@@ -644,10 +765,11 @@ class UNetEngine:
         self._fwd_state = None
         opt = _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value,
                                 int(cond is None), seed)
-        name = "mi355_ddpm_sample" if sched is None else "mi355_ddpm_sample_sched"
+        name = "mi355_ddpm_sample" if sched is None else "mi355_ddpm_sample_sched" if cache is None else "mi355_ddpm_sample_sched_cached"
+        fc = _lib.feature_cache(*cache) if cache is not None else None
         ws, wsb = self.workspace(B)
         check(getattr(self.L, name)(self.handle, *self._ddpm_args(x, cond), C.byref(tb), C.byref(opt), *(() if sched is None else (C.byref(sched[0]),)),
-                                    *self._noise_args(noise), B, ws, wsb, self._stream()), name)
+                                    *self._noise_args(noise), B, ws, wsb, self._stream(), *(() if fc is None else (C.byref(fc),))), name)
         del keep
         return x
 

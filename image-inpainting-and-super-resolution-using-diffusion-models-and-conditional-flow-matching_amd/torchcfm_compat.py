@@ -166,13 +166,23 @@ class NeuralODE:
     trajectory(x, t_span) -> Tensor[len(t_span), *x.shape], one step per interval of t_span for the fixed-step solvers.  With a
     UNetModelWrapper vector field these run the whole integration inside libmi355_sampler (mi355_cfm_euler_sample /
     mi355_cfm_rk_sample); any other callable f(t, x[, args]) is driven step by step from the host with the HIP update kernels
-    (mi355.ode.FixedStepRK for the Runge-Kutta methods).  dopri5 is one continuous adaptive solve with dense output at the requested times."""
+    (mi355.ode.FixedStepRK for the Runge-Kutta methods).  dopri5 is one continuous adaptive solve with dense output at the requested times.
+
+    cache_interval / cache_branch (BUILD-DEFINED EXTENSION; None: untouched): feature reuse across the Euler steps of a UNetModelWrapper
+    (DeepCache: one full U-Net evaluation in cache_interval steps, the cache_branch outermost block pairs recomputed at every step;
+    UNetEngine.cfm_euler).  solver="euler" on the device only; any other solver or vector field refuses it."""
 
     RK_SOLVERS = RK_SOLVERS   # mi355.ode: every fixed-step tableau name but "euler"
 
-    def __init__(self, vector_field, solver="euler", sensitivity="adjoint", atol=1e-4, rtol=1e-4, **kwargs):
+    def __init__(self, vector_field, solver="euler", sensitivity="adjoint", atol=1e-4, rtol=1e-4, cache_interval=None, cache_branch=None, **kwargs):
         if solver not in ("euler", "dopri5") + self.RK_SOLVERS + AB_SOLVERS:
             raise NotImplementedError(f"solver={solver!r}: only 'euler', 'dopri5', {self.RK_SOLVERS} and {AB_SOLVERS} are built")
+        self.cache = {}
+        if cache_interval is not None or cache_branch is not None:
+            if solver != "euler" or type(vector_field) is not UNetModelWrapper:
+                raise NotImplementedError("cache_interval / cache_branch (feature reuse) are built for solver='euler' on a UNetModelWrapper "
+                                          "(not for the guided, Runge-Kutta, Adams-Bashforth or adaptive solvers, nor for other callables)")
+            self.cache = dict(cache_interval=1 if cache_interval is None else cache_interval, cache_branch=cache_branch)
         self.vf = vector_field
         self.solver = solver
         self.atol, self.rtol = atol, rtol
@@ -223,8 +233,11 @@ class NeuralODE:
             states = FixedStepRK(lambda t, y: [self._call(t, y[0])], self.solver).integrate_times([x], ts)
             return torch.stack([x] + [s[0] for s in states])
         if type(self.vf) is UNetModelWrapper and x.is_cuda:
-            _, traj, _ = self.vf.engine(x.device).cfm_euler(x, ts, keep_traj=True)
+            _, traj, _ = self.vf.engine(x.device).cfm_euler(x, ts, keep_traj=True, **self.cache)
             return traj
+        if self.cache:
+            from mi355._lib import MI355BackendError
+            raise MI355BackendError("feature reuse (cache_interval) runs inside the device loop: x must be a device tensor")
         out = [x.clone()]
         for k in range(len(ts) - 1):
             t = ts[k] if isinstance(self.vf, UNetModelWrapper) else torch.tensor(ts[k], device=x.device, dtype=torch.float32)

@@ -56,7 +56,9 @@ extern "C" {
  * symbols and one new struct only); then per-image shaping of the DDPM data prediction (dynamic thresholding, guidance rescale):
  * mi355_ddpm_shaped_workspace_bytes, mi355_ddpm_shaped_sample, mi355_x0_shape_stats, mi355_x0_shaped_step (new symbols and one new struct only); then the embedding path and the layout
  * kernels as test ops: mi355_linear, mi355_label_emb_linear, mi355_emb_gather, mi355_pack_nhwc, mi355_unpack_nchw, mi355_unpack_channels,
- * mi355_resample (new symbols only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * mi355_resample (new symbols only); then feature reuse across sampler steps (DeepCache): mi355_unet_cache_info, mi355_unet_forward_cached,
+ * mi355_cfm_euler_sample_cached, mi355_ddpm_sample_sched_cached, mi355_feature_cache_workspace_bytes, mi355_feature_drift (new symbols and one new
+ * struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -433,6 +435,69 @@ int mi355_ddpm_sample_sched(mi355_unet* net, float* x, int channels, const float
 int mi355_ddpm_cfg_sample_sched(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, float w,
                                 const float* w_dev, const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
                                 const float* noise, int64_t n_noise_draws, int batch, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- feature reuse across sampler steps (DeepCache: Ma, Fang, Wang, CVPR 2024; training-free; no reference counterpart) ------------------------
+ * Let input_blocks[0..n-1] and output_blocks[0..n-1] be the blocks of UNetModel.  BRANCH k, 1 <= k <= n-1, is the number of outermost block pairs
+ * that are always recomputed.  The CACHED FEATURE of branch k is the tensor h as it stands just before torch.cat([h, hs.pop()]) of
+ * output_blocks[n-k].  A FULL evaluation is mi355_unet_forward.  A SHALLOW evaluation of branch k computes the embedding for its own t (and
+ * labels), runs input_blocks[0..k-1] on its own x, takes the cached feature as left by the most recent full evaluation on the same workspace at the
+ * same batch, and runs output_blocks[n-k..n-1] and out.  In the engine it is the same resolved forward with one contiguous range of plan ops not
+ * issued (every activation has its own place in the workspace, so what the full evaluation left there stands); mi355_unet_get_stats, the
+ * mi355_unet_read_tensor record and the launch counts describe only what was issued.  All four precisions.  No workspace beyond the uncached entry
+ * points' (drift_out apart).  A CACHE SCHEDULE is a host array full[E] of bytes, one per network evaluation the loop makes, in loop order: evaluation e is full iff
+ * full[e] != 0; full[0] must be non-zero.  (DeepCache's uniform 1:N schedule is full[e] = (e % N == 0).)
+ * Sample quality under feature reuse is untested (no trained checkpoint is at hand); the arithmetic is tested against an fp64 / fp32 restatement. */
+typedef struct mi355_feature_cache {
+  int32_t branch;        /* k, in 1..n-1 (mi355_unet_cache_info gives n-1) */
+  int32_t n_evals;       /* E: must equal the number of evaluations the loop makes */
+  const uint8_t* full;   /* host uint8[E] */
+  float* drift_out;      /* NULL, or device float[E][B]: per-image drift of the cached feature, see below */
+} mi355_feature_cache;
+/* drift_out (calibration: how fast does the cached feature of THIS checkpoint move, per image - the figure to choose branch and schedule by):
+ * every full evaluation e after the first writes drift_out[e][b] = ||F_e - F_prev||^2 / ||F_prev||^2 for image b, F the cached feature in the
+ * plan's element type and F_prev its value at the previous full evaluation; the rows of shallow evaluations and of the first full one hold -1.
+ * One launch per full evaluation (mi355_feature_drift: F_e and F_prev are read once, F_prev is overwritten with F_e in the same pass; the first
+ * full evaluation's launch is the copy that seeds F_prev) and one fill of drift_out before the loop.  F_prev lives behind the sampler's workspace:
+ * size the workspace with mi355_feature_cache_workspace_bytes(net, batch, branch, 1) = the uncached entry point's amount rounded up to 256 bytes
+ * plus the cached feature's bytes at `batch` (drift = 0: the rounded amount alone).  With drift_out NULL nothing is launched or kept. */
+int64_t mi355_feature_cache_workspace_bytes(const mi355_unet* net, int batch, int branch, int drift);
+/* The drift kernel alone (a test op): out[b] = ||cur_b - prev_b||^2 / ||prev_b||^2 (fp32 sums), then prev_b <- cur_b.  cur, prev: device
+ * [batch][elems_per_image] in dtype's element type (MI355_F32: float; MI355_BF16 / MI355_BF16X2: bf16; MI355_F16: fp16), different buffers, 16-byte
+ * aligned, elems_per_image a multiple of 16 bytes of elements (else MI355_ERR_SHAPE).  out: device float[batch].  One 512-thread workgroup per image. */
+int mi355_feature_drift(const void* cur, void* prev, int dtype, int batch, int64_t elems_per_image, float* out, void* stream);
+
+/* Host only (no GPU; the plan alone, as mi355_unet_param_count).  out[0] = the number of branches n-1; for branch >= 1 also out[1], out[2] = the
+ * plan-op range [lo, hi) a shallow evaluation does not issue (mi355_unet_plan_op indices), out[3] = the cached feature's tensor id, out[4..6] = its
+ * (C, H, W), out[7] = the share of conv_flops + attn_flops a shallow evaluation retains, in parts per million.  branch = 0 fills out[0] only (the
+ * rest 0).  branch outside 0..n-1: MI355_ERR_ARG. */
+int mi355_unet_cache_info(const mi355_unet_config* cfg, int branch, int32_t out[8]);
+
+/* mi355_unet_forward_labels with a branch: 0 = a full evaluation, identical to mi355_unet_forward_labels; k = a shallow evaluation of branch k.
+ * THE CALLER'S CONTRACT for k != 0: the previous forward on this workspace at this batch was a full one (of this handle, by any entry point that
+ * runs the whole net), or a shallow one that itself met this contract, and nothing else has written the workspace since.  The library cannot check it: a workspace that does not hold a full evaluation's
+ * activations gives a result that is wrong without any error.  Refusals, before any launch: branch outside 0..n-1 (MI355_ERR_ARG, names `branch`);
+ * a shallow evaluation on a handle created with differentiable = 1 (MI355_ERR_UNSUPPORTED: the backward pass would see mixed activations). */
+int mi355_unet_forward_cached(mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, const float* t, float t_host,
+                              const int32_t* labels, float* out, int batch, void* workspace, int64_t workspace_bytes, void* stream, int branch);
+
+/* mi355_cfm_euler_sample_labels under a cache schedule: the same loop (the precomputed embedding table, the (step, class) gather, the Euler update in
+ * the last conv's epilogue, traj, u8_out, cond, cond_drift, labels), step k being evaluation k, so cache->n_evals must equal n_t - 1.  sampler_graph
+ * is not used (as with labels).  With full[e] = 1 for every e the result is BIT-IDENTICAL to mi355_cfm_euler_sample_labels'.
+ * Errors beyond that entry point's, all MI355_ERR_ARG before any launch, each naming its argument: cache NULL; cache->full NULL; cache->full[0] == 0;
+ * cache->n_evals != n_t - 1; cache->branch outside 1..n-1.  Not built (a later change): the guided, Runge-Kutta / Adams-Bashforth, multistep,
+ * shaped, reconstruction and SF2M loops. */
+int mi355_cfm_euler_sample_cached(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
+                                  const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
+                                  void* workspace, int64_t workspace_bytes, void* stream, const mi355_feature_cache* cache);
+
+/* mi355_ddpm_sample_sched under a cache schedule: the same loop, all three modes and MI355_DDIM, walks with upward moves included.  Evaluations are
+ * numbered in loop order, correctors included: a downward move is one predictor evaluation followed (ancestral modes) by its n_corrector corrector
+ * evaluations; an upward move makes none.  cache->n_evals must equal D * (1 + n_corrector) for D downward moves (D = K without a walk; MI355_DDIM has
+ * no correctors: D).  With full[e] = 1 for every e the result is BIT-IDENTICAL to mi355_ddpm_sample_sched's.  Errors beyond that entry point's:
+ * those of mi355_cfm_euler_sample_cached, named the same way. */
+int mi355_ddpm_sample_sched_cached(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tables,
+                                   const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched, const float* noise, int64_t n_noise_draws, int batch,
+                                   void* workspace, int64_t workspace_bytes, void* stream, const mi355_feature_cache* cache);
 
 /* DPM-Solver++ multistep sampling of a DDPM net, orders 1 and 2 (Lu et al. 2022, Algorithm 2, data-prediction form; no reference counterpart).
  * The loop of mi355_ddpm_sample_sched in MI355_DDIM mode with step i replaced by ONE mi355_dpmpp_step launch (guided entry: mi355_dpmpp_cfg_step):
