@@ -358,6 +358,16 @@ int paint_patch_launch(const float* img, const int* top, const int* left, int pa
 int groupnorm_nchw_launch(const float* x, const float* gamma, const float* beta, float* y, int N, int C, int HW, int groups,
                           float eps, int silu, hipStream_t s);
 
+// tiled sampling (tile.hip): the geometry of a mi355_tile_plan over a net of frame S (tile_geom holds every refusal that needs no handle, each
+// prefixed by `who`), the copy of a canvas [B, C, Hc, Wc] into its windows [B * nW, C, S, S] (labels: [B] -> [B * nW]), and the weighted average of
+// window predictions back onto the canvas (vbar, and x <- x + dt * vbar where euler_x is given)
+struct TileGeom { int S, Hc, Wc, sy, sx, ny, nx, nW, weight; };
+int tile_geom(int image_size, const mi355_tile_plan* plan, TileGeom* g, const char* who);
+inline int tile_origin(int i, int s, int L, int S) { return i * s < L - S ? i * s : L - S; }
+int tile_gather_launch(const float* canvas, float* windows, int B, int C, const TileGeom& g, hipStream_t s);
+int tile_labels_launch(const int32_t* labels, int32_t* out, int B, int nW, hipStream_t s);
+int tile_blend_launch(const float* windows, float* vbar, float* euler_x, float dt, int B, int C, const TileGeom& g, hipStream_t s);
+
 // adaptive RK45 helpers (ode.hip)
 int rk_combine_launch(float* out, const float* y0, const float* const* k, const float* c, int nk, int64_t n, hipStream_t s);
 // one stage of a fixed-step explicit RK sampler: out = y0 + sum_j c[j] * k[j] (1 <= nk <= 4; out may be y0), the result also to copy_out and,

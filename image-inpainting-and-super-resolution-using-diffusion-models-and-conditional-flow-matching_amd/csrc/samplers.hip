@@ -1,6 +1,7 @@
 // The sampler loops of libmi355_sampler.so (see include/mi355_sampler.h): workspace layouts, the embedding rows of the evaluations, and the
 // Euler (+ graph form), Runge-Kutta, DDPM, their classifier-free-guided forms, the replacement / reconstruction-guided flow sampler, and SF2M entry
 // points.  Host code only.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -35,10 +36,15 @@ struct ReconTail { float* x_init; float* g_eps; float* g_x; float* vjp; float* r
 // the DDPM multistep history (the previous step's data prediction: one state at `batch`, also under guidance) and the shaping rows [batch][2]
 struct DdpmTail { float* hist; float* rows; };
 // feature cache with drift_out: the cached feature as the previous full evaluation left it (plan element type), behind everything else
-struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; ReconTail rec; DdpmTail ddpm; void* feat_prev; uintptr_t end; };
+// tiled sampling (TiledEval): B canvases cut by g.  Behind everything else: the windows the net reads (x | condition: [B * nW, in_channels, S, S]),
+// the windows it writes [B * nW, out_channels, S, S], the blended canvas [B, out_channels, Hc, Wc], the repeated labels [B * nW]
+struct TileSpec { int B; TileGeom g; };
+struct TiledTail { float* in; float* out; float* vbar; int32_t* labels; };
+struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; ReconTail rec; DdpmTail ddpm; void* feat_prev; TiledTail tile; uintptr_t end; };
 // What a sampler call keeps in its workspace.  guided: the network runs at 2 * batch and the guidance tail follows its workspace; stages > 0: the
 // Runge-Kutta buffers follow; recon: the reconstruction tail; hist, rows: the DDPM tail closes the layout.
-struct LayoutSpec { int batch = 0; bool guided = false; int stages = 0; const ReconDims* recon = nullptr; bool hist = false; bool rows = false; size_t feat_bytes = 0; };
+struct LayoutSpec { int batch = 0; bool guided = false; int stages = 0; const ReconDims* recon = nullptr; bool hist = false; bool rows = false; size_t feat_bytes = 0;
+                    const TileSpec* tile = nullptr; };
 inline size_t cfg_cond_channels(const mi355_unet* net) { return (size_t)(net->cfg.in_channels > net->cfg.out_channels ? net->cfg.in_channels - net->cfg.out_channels : 0); }
 
 Layout layout(const mi355_unet* net, const LayoutSpec& sp, uintptr_t base) {
@@ -58,7 +64,7 @@ Layout layout(const mi355_unet* net, const LayoutSpec& sp, uintptr_t base) {
   l.sc.unet_bytes = unet_workspace_bytes(net, B);
   l.sc.unet_ws = reinterpret_cast<char*>(w.p);
   w.p += (size_t)l.sc.unet_bytes;   // not rounded up: mi355_unet_workspace_bytes ends here
-  if (guided || stages || recon || sp.hist || sp.rows || sp.feat_bytes) w.p = al256(w.p);
+  if (guided || stages || recon || sp.hist || sp.rows || sp.feat_bytes || sp.tile) w.p = al256(w.p);
   if (guided) {
     l.cfg.x2 = w.take(state);
     l.cfg.cond2 = w.take((size_t)B * cfg_cond_channels(net) * hw * 4);
@@ -76,6 +82,13 @@ Layout layout(const mi355_unet* net, const LayoutSpec& sp, uintptr_t base) {
   if (sp.hist) l.ddpm.hist = w.take((size_t)sp.batch * net->cfg.out_channels * hw * 4);
   if (sp.rows) l.ddpm.rows = w.take((size_t)sp.batch * 2 * 4);
   if (sp.feat_bytes) l.feat_prev = w.take<void>(sp.feat_bytes);
+  if (sp.tile) {   // with a tile spec, sp.batch is the chunk the net runs at
+    const size_t rows = (size_t)sp.tile->B * sp.tile->g.nW;
+    l.tile.in = w.take(rows * net->cfg.in_channels * hw * 4);
+    l.tile.out = w.take(rows * net->cfg.out_channels * hw * 4);
+    l.tile.vbar = w.take((size_t)sp.tile->B * net->cfg.out_channels * sp.tile->g.Hc * sp.tile->g.Wc * 4);
+    l.tile.labels = w.take<int32_t>(net->num_classes > 0 ? rows * 4 : 0);
+  }
   l.end = w.p;
   return l;
 }
@@ -208,18 +221,83 @@ struct CacheRun {
   }
 };
 
+// ---- tiled evaluation (canvases larger than the net's frame; tile.hip) ----------------------------------------------------------------------
+// Largest batch one forward takes: every activation tensor is addressed through 32-bit buffer offsets (the convs refuse beyond 4 GiB with "run
+// the batch in slices"), and a concat source pair or an in-flight double of the same tensor halves that.  The samplers' fp32 scratch holds up to
+// 32 channels per image.
+int64_t net_max_batch(const mi355_unet* net) {
+  const size_t esz = net->cfg.dtype == 0 ? 4 : 2;
+  size_t per = (size_t)32 * net->cfg.image_size * net->cfg.image_size * 4;
+  for (const PlanTensor& t : net->tensors) per = std::max(per, (size_t)t.C * t.H * t.W * (t.f32 ? 4 : esz));
+  return std::max<int64_t>(1, (int64_t)(0xFFFF0000ull / (2 * per)));
+}
+// Every refusal of a tile plan, before any launch, each naming its field.  who: the entry point's name.
+int check_tile_plan(const char* who, const mi355_unet* net, const mi355_tile_plan* plan, int batch, TileSpec& ts) {
+  const std::string f = std::string(who) + ": ";
+  MI355_REQUIRE(net && batch > 0, -1, f + "bad argument (net, batch)");
+  if (int rc = tile_geom(net->cfg.image_size, plan, &ts.g, who)) return rc;
+  MI355_REQUIRE(plan->chunk <= net_max_batch(net), -1,
+                f + "chunk is above the handle's largest batch (" + std::to_string(net_max_batch(net)) + ")");
+  MI355_REQUIRE((int64_t)batch * ts.g.nW < (1ll << 31), -4, f + "batch * windows per canvas does not fit an int");
+  ts.B = batch;
+  return 0;
+}
+// What the loops call in place of unet_forward (a null TiledEval*: the existing path).  One evaluation = gather the state's windows, the forward on
+// the windows in chunks of at most `chunk` rows (labels and condition windows sliced per chunk, no euler_x), blend: n_chunks forwards + 2 launches.
+// The result is vbar (a canvas); with euler_x the blend also takes x <- x + dt * vbar.
+struct TiledEval {
+  TileGeom g; int B = 0, chunk = 0;
+  TiledTail buf;
+  const int32_t* labels = nullptr;   // null, or buf.labels once repeat_labels has run
+  int64_t rows() const { return (int64_t)B * g.nW; }
+  int64_t hw() const { return (int64_t)g.S * g.S; }
+  float* cond_windows(int Cx) const { return buf.in + rows() * Cx * hw(); }
+  // once per call: the condition canvas -> its windows (behind the state's windows), the labels [B] -> [B * nW]
+  int gather_cond(const float* cond, int Cx, int Cc, hipStream_t s) const { return tile_gather_launch(cond, cond_windows(Cx), B, Cc, g, s); }
+  int repeat_labels(const int32_t* lab, hipStream_t s) { labels = buf.labels; return tile_labels_launch(lab, buf.labels, B, g.nW, s); }
+  // condw: null, the windows of gather_cond, or (uniform) one buffer of `chunk` rows that every chunk reads, such as the none_value fill
+  int eval(const mi355_unet* net, const Scratch& sc, const UnetRun& run, const float* x, int Cx, const float* condw, int Cc, bool uniform, float* euler_x,
+           float dt, hipStream_t s) const {
+    if (int rc = tile_gather_launch(x, buf.in, B, Cx, g, s)) return rc;
+    UnetRun r = run;
+    r.euler_x = nullptr; r.euler_dt = 0.f;
+    const int Cout = net->cfg.out_channels;
+    int64_t launches = 2;
+    for (int64_t off = 0; off < rows(); off += chunk) {
+      const int m = (int)std::min<int64_t>(chunk, rows() - off);
+      r.labels = labels ? labels + off : nullptr;
+      const float* c = !condw ? nullptr : (uniform ? condw : condw + off * Cc * hw());
+      if (int rc = unet_forward(net, buf.in + off * Cx * hw(), Cx, c, Cc, sc.t, buf.out + off * Cout * hw(), m, sc.unet_ws, sc.unet_bytes, s, r)) return rc;
+      launches += net->last_launches;
+    }
+    if (int rc = tile_blend_launch(buf.out, buf.vbar, euler_x, dt, B, Cout, g, s)) return rc;
+    net->last_launches = launches;   // mi355_unet_get_stats: every launch of the last tiled evaluation
+    return 0;
+  }
+};
+TiledEval tiled_eval(const TileSpec& ts, int chunk, const Layout& l) {
+  TiledEval t;
+  t.g = ts.g; t.B = ts.B; t.chunk = chunk; t.buf = l.tile;
+  return t;
+}
+
 // ---- flow-matching Euler ----------------------------------------------------------------------------------
 // The loop proper: every launch of every step on stream s (the caller's stream, or the handle's capture stream while a graph is recorded).
 // labels: class-conditional steps (with a table: step k's block of the (step, class) table, one gather launch per step).
 int cfm_euler_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, float* x, int x_channels, const float* cond, int cond_channels, float* cdrift,
                    const float* t_span_host, int n_t, float* traj, int batch, int64_t n, int64_t nc, hipStream_t s, const int32_t* labels = nullptr,
-                   CacheRun* cache = nullptr) {
+                   CacheRun* cache = nullptr, const TiledEval* tiled = nullptr) {
   UnetRun run = uniform_t_run();
   run.labels = labels;
   for (int k = 0; k + 1 < n_t; ++k) {
     const float dt = t_span_host[k + 1] - t_span_host[k];
     int rc;
     if ((rc = emb.select(run, (size_t)k, batch, s))) return rc;
+    if (tiled) {   // x is a canvas, cond its windows, batch the chunk: the blend launch carries x += dt * vbar
+      if ((rc = tiled->eval(net, sc, run, x, x_channels, cond, cond_channels, false, x, dt, s))) return rc;
+      if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * n, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      continue;
+    }
     run.reuse_branch = cache ? cache->branch_of(k) : 0;   // step k is evaluation k
     run.euler_x = x; run.euler_dt = dt;   // x += dt * v: in the last conv's epilogue, or as a launch of unet_forward's own behind it
     if ((rc = unet_forward(net, x, x_channels, cond, cond_channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
@@ -375,6 +453,7 @@ struct DdpmLoop {
   const float* cond_pred; const int32_t* labels_pred;   // what the net sees on predictor steps (at evalB)
   const float* cond_corr; const int32_t* labels_corr;   // ... and on corrector steps (at batch): no condition (sampling.py:116 -> none_like, the null label)
   const float* mask_cond;   // replacement mode: the condition pasted over the state
+  const TiledEval* tiled;   // not null: the state is a canvas, evalB the chunk, cond_pred / cond_corr window buffers (sc.none: read by every chunk)
   float* mirror;            // guided: the state's second half, refreshed after a step's correctors
   Guide guide;
 };
@@ -403,6 +482,7 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
   const int64_t n_al = (n + 3) / 4 * 4;
   const int64_t sper = n / batch;   // elements per image (the shaping rows)
   float* x = a.state;
+  float* const eps = a.tiled ? a.tiled->buf.vbar : sc.v;   // the network's prediction for the state
   UnetRun run = uniform_t_run(), run_corr = uniform_t_run();
   run.labels = a.labels_pred;
   run_corr.labels = a.labels_corr;
@@ -427,11 +507,13 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     if ((rc = emb.select(run, (size_t)i, a.evalB, s))) return rc;
     run_corr.emb_row = run.emb_row;
     run.reuse_branch = ls.cache ? ls.cache->branch_of(eval) : 0;
-    if ((rc = unet_forward(net, x, channels, a.cond_pred, channels, sc.t, sc.v, a.evalB, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    if (a.tiled) rc = a.tiled->eval(net, sc, run, x, channels, a.cond_pred, channels, a.cond_pred == sc.none, nullptr, 0.f, s);
+    else rc = unet_forward(net, x, channels, a.cond_pred, channels, sc.t, sc.v, a.evalB, sc.unet_ws, sc.unet_bytes, s, run);
+    if (rc) return rc;
     if (ls.cache && (rc = ls.cache->after(eval, s))) return rc;
     ++eval;
     PredictorStep p;
-    p.x = x; p.eps = sc.v; p.c_recip = tb->sqrt_recip_alphas_cumprod[i]; p.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[i];
+    p.x = x; p.eps = eps; p.c_recip = tb->sqrt_recip_alphas_cumprod[i]; p.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[i];
     p.seed = opt->seed; p.guide = a.guide; p.per = sper; p.shape = ls.shape; p.n = n;
     if (ls.shape && (rc = x0_shape_stats_launch(x, sc.v, a.guide, p.c_recip, p.c_recipm1, ls.shaping, ls.shape, nullptr, batch, sper, s))) return rc;
     if (mode == MI355_DDIM) {
@@ -451,13 +533,15 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     if ((rc = predictor_step_launch(p, s))) return rc;
     for (int c = 0; c < opt->n_corrector; ++c) {   // at batch B (a guided sampler's first half)
       run_corr.reuse_branch = ls.cache ? ls.cache->branch_of(eval) : 0;
-      if ((rc = unet_forward(net, x, channels, a.cond_corr, channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run_corr))) return rc;
+      if (a.tiled) rc = a.tiled->eval(net, sc, run_corr, x, channels, a.cond_corr, channels, true, nullptr, 0.f, s);
+      else rc = unet_forward(net, x, channels, a.cond_corr, channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run_corr);
+      if (rc) return rc;
       if (ls.cache && (rc = ls.cache->after(eval, s))) return rc;
       ++eval;
       const float* z2 = nullptr; int ph2 = 0; uint64_t off2 = 0;
       if ((rc = next_noise(z2, ph2, off2))) return rc;
       const float dt = (opt->tmax - opt->tmin) / (float)Ns;
-      if ((rc = corrector_step_launch(x, sc.v, z2, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i],
+      if ((rc = corrector_step_launch(x, eps, z2, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i],
                                       tb->recip_sqrt_m1_alphas_cumprod[i], dt, opt->delta, ph2, opt->seed, off2, n, s))) return rc;
     }
     if (a.mirror && opt->n_corrector > 0) MI355_CHECK_HIP(hipMemcpyAsync(a.mirror, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
@@ -555,6 +639,7 @@ struct DdpmCall {
   bool bare_size_refusal = false;   // mi355_ddpm_sample(_sched): their short-workspace refusal carries no prefix
   bool count_step = false;          // mi355_unet_get_stats: the last evaluation AND the launches of its step (the multistep and shaped entry points)
   const mi355_feature_cache* cache = nullptr;   // mi355_ddpm_sample_sched_cached (checked by check_cache)
+  const TileSpec* tile = nullptr;   // mi355_ddpm_sample_tiled (checked by check_tile_plan): x, cond and noise are canvases, spec.batch is the chunk
 };
 DdpmCall ddpm_call(const char* who, int batch, const DdpmGuidance* guided) {
   DdpmCall c = {};
@@ -566,7 +651,7 @@ int ddpm_run(DdpmCall& c, mi355_unet* net, float* x, int channels, const float* 
              const float* noise, int64_t n_noise_draws, void* workspace, int64_t workspace_bytes, void* stream) {
   const std::string f = std::string(c.who) + ": ";
   const DdpmGuidance* const g = c.guided;
-  const int mode = opt->mode, batch = c.spec.batch;
+  const int mode = opt->mode, batch = c.tile ? c.tile->B : c.spec.batch;
   const bool amortized = net->cfg.in_channels == 2 * channels;
   if (g) {
     const int32_t* const labels = g->labels; const int null_label = g->null_label;
@@ -589,17 +674,29 @@ int ddpm_run(DdpmCall& c, mi355_unet* net, float* x, int channels, const float* 
   const CfgTail& tl = l.cfg;
   c.ls.hist = l.ddpm.hist; c.ls.shape = c.ls.shaping ? l.ddpm.rows : nullptr;
   hipStream_t s = S(stream);
-  const int64_t per = (int64_t)channels * net->cfg.image_size * net->cfg.image_size, n = (int64_t)batch * per;
+  const int64_t hw = c.tile ? (int64_t)c.tile->g.Hc * c.tile->g.Wc : (int64_t)net->cfg.image_size * net->cfg.image_size;
+  const int64_t per = (int64_t)channels * hw, n = (int64_t)batch * per;
   EvalEmb emb;   // row i (block of num_classes rows with labels) = step i
   if (int rc = emb.init(net, sc, c.th.data(), tb->Ns, g && g->labels, true, s)) return rc;
   DdpmLoop a = {};
   a.who = c.who;
+  TiledEval te;
   if (g) {
     if (int rc = cfg_fill_tail(tl, x, n, cond, n, opt->none_value, g->labels, g->null_label, batch, s)) return rc;
     a.state = tl.x2; a.evalB = 2 * batch; a.mirror = tl.x2 + n;
     a.cond_pred = tl.cond2; a.labels_pred = g->labels ? tl.labels2 : nullptr;
     a.cond_corr = tl.cond2 + n; a.labels_corr = g->labels ? tl.labels2 + batch : nullptr;
     a.guide.on = true; a.guide.w = g->w; a.guide.w_dev = g->w_dev; a.guide.per = per;
+  } else if (c.tile) {
+    // the loop below on canvases: the condition the net sees becomes its windows (gathered once), the none_value condition one chunk-sized fill
+    te = tiled_eval(*c.tile, c.spec.batch, l);
+    const int64_t whw = (int64_t)net->cfg.image_size * net->cfg.image_size;
+    if (amortized) { if (int rc = fill_launch(sc.none, opt->none_value, (int64_t)c.spec.batch * channels * whw, s)) return rc; }
+    const bool sees_cond = amortized && (mode == MI355_DDPM_AMORTIZED || (mode == MI355_DDIM && cond));
+    if (sees_cond) { if (int rc = te.gather_cond(cond, channels, channels, s)) return rc; }
+    a.state = x; a.evalB = c.spec.batch; a.mask_cond = cond; a.tiled = &te;
+    a.cond_pred = !amortized ? nullptr : (sees_cond ? te.cond_windows(channels) : sc.none);
+    a.cond_corr = amortized ? sc.none : nullptr;
   } else {
     if (amortized) { if (int rc = fill_launch(sc.none, opt->none_value, n, s)) return rc; }
     a.state = x; a.evalB = batch; a.mask_cond = cond;
@@ -1133,6 +1230,121 @@ int mi355_sf2m_euler_sample(mi355_unet* drift, mi355_unet* score, float* x, int 
     rc = sde_euler_step_launch(x, sd.v, ss.v, ca, 1.f, dt, nullptr, sigma, dw, !dW, seed, off, fused, fused_w, n, s);
   }
   return rc;
+}
+
+// ---- tiled sampling: the entry points (TiledEval; include/mi355_sampler.h) -------------------------------------------------------------------
+int mi355_tile_count(int image_size, const mi355_tile_plan* plan, int32_t out[3]) {
+  MI355_REQUIRE(out, -1, "tile_count: out is null");
+  TileGeom g;
+  if (int rc = tile_geom(image_size, plan, &g, "tile_count")) return rc;
+  out[0] = g.ny; out[1] = g.nx; out[2] = g.nW;
+  return 0;
+}
+
+int mi355_tile_origins(int image_size, const mi355_tile_plan* plan, int32_t* oy, int32_t* ox) {
+  MI355_REQUIRE(oy && ox, -1, "tile_origins: oy or ox is null");
+  TileGeom g;
+  if (int rc = tile_geom(image_size, plan, &g, "tile_origins")) return rc;
+  for (int i = 0; i < g.ny; ++i) oy[i] = tile_origin(i, g.sy, g.Hc, g.S);
+  for (int i = 0; i < g.nx; ++i) ox[i] = tile_origin(i, g.sx, g.Wc, g.S);
+  return 0;
+}
+
+int64_t mi355_tiled_workspace_bytes(const mi355_unet* net, int batch, const mi355_tile_plan* plan) {
+  TileSpec ts;
+  if (int rc = check_tile_plan("tiled_workspace_bytes", net, plan, batch, ts)) return rc;
+  LayoutSpec sp = plain_spec(plan->chunk);
+  sp.tile = &ts;
+  return layout_bytes(net, sp);
+}
+
+int mi355_tile_gather(const float* canvas, float* windows, int batch, int channels, int image_size, const mi355_tile_plan* plan, void* stream) {
+  TileGeom g;
+  if (int rc = tile_geom(image_size, plan, &g, "tile_gather")) return rc;
+  return tile_gather_launch(canvas, windows, batch, channels, g, S(stream));
+}
+
+int mi355_tile_labels(const int32_t* labels, int32_t* out, int batch, int n_windows, void* stream) {
+  return tile_labels_launch(labels, out, batch, n_windows, S(stream));
+}
+
+int mi355_tile_blend(const float* windows, float* vbar, float* euler_x, float dt, int batch, int channels, int image_size, const mi355_tile_plan* plan,
+                     void* stream) {
+  TileGeom g;
+  if (int rc = tile_geom(image_size, plan, &g, "tile_blend")) return rc;
+  return tile_blend_launch(windows, vbar, euler_x, dt, batch, channels, g, S(stream));
+}
+
+int mi355_unet_forward_tiled(mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, float t_host, const int32_t* labels,
+                             float* out, int batch, const mi355_tile_plan* plan, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* const who = "unet_forward_tiled";
+  TileSpec ts;
+  if (int rc = check_tile_plan(who, net, plan, batch, ts)) return rc;
+  MI355_REQUIRE(x && out, -1, "unet_forward_tiled: x or out is null");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "unet_forward_tiled: class labels given to a net built without num_classes");
+  MI355_REQUIRE(x_channels > 0 && x_channels + (cond ? cond_channels : 0) == net->cfg.in_channels, -2,
+                "unet_forward_tiled: x_channels and cond_channels do not add up to in_channels");
+  LayoutSpec spec = plain_spec(plan->chunk);
+  spec.tile = &ts;
+  Layout l;
+  if (int rc = carve(net, spec, workspace, workspace_bytes, l, who)) return rc;
+  hipStream_t s = S(stream);
+  TiledEval te = tiled_eval(ts, plan->chunk, l);
+  if (cond) { if (int rc = te.gather_cond(cond, x_channels, cond_channels, s)) return rc; }
+  if (labels) { if (int rc = te.repeat_labels(labels, s)) return rc; }
+  if (int rc = fill_launch(l.sc.t, t_host, plan->chunk, s)) return rc;
+  if (int rc = te.eval(net, l.sc, uniform_t_run(), x, x_channels, cond ? te.cond_windows(x_channels) : nullptr, cond_channels, false, nullptr, 0.f, s)) return rc;
+  const int64_t n = (int64_t)batch * net->cfg.out_channels * ts.g.Hc * ts.g.Wc;
+  MI355_CHECK_HIP(hipMemcpyAsync(out, l.tile.vbar, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+int mi355_cfm_euler_sample_tiled(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
+                                 const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
+                                 void* workspace, int64_t workspace_bytes, void* stream, const mi355_tile_plan* plan) {
+  MI355_REQUIRE(net && x && t_span_host && n_t >= 1, -1, "cfm_euler_sample_tiled: bad argument");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "cfm_euler_sample_tiled: class labels given to a net built without num_classes");
+  MI355_REQUIRE(x_channels == net->cfg.out_channels, -2, "cfm_euler_sample_tiled: the vector field must have the state's channel count");
+  const char* const who = "cfm_euler_sample_tiled";
+  TileSpec ts;
+  if (int rc = check_tile_plan(who, net, plan, batch, ts)) return rc;
+  MI355_REQUIRE(!cond_drift, -4, "cfm_euler_sample_tiled: cond_drift (the drifting condition of the concatenated-state sampler) is not built under tiling");
+  MI355_REQUIRE(x_channels + (cond ? cond_channels : 0) == net->cfg.in_channels, -2,
+                "cfm_euler_sample_tiled: x_channels and cond_channels do not add up to in_channels");
+  LayoutSpec spec = plain_spec(plan->chunk);
+  spec.tile = &ts;
+  Layout l;
+  if (int rc = carve(net, spec, workspace, workspace_bytes, l, who)) return rc;
+  const Scratch& sc = l.sc;
+  hipStream_t s = S(stream);
+  TiledEval te = tiled_eval(ts, plan->chunk, l);
+  EvalEmb emb;   // t_span_host is the caller's array: no wait
+  if (int rc = emb.init(net, sc, t_span_host, n_t - 1, labels != nullptr, false, s)) return rc;
+  const int64_t n = (int64_t)batch * x_channels * ts.g.Hc * ts.g.Wc;
+  if (traj) MI355_CHECK_HIP(hipMemcpyAsync(traj, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  if (cond) { if (int rc = te.gather_cond(cond, x_channels, cond_channels, s)) return rc; }
+  if (labels) { if (int rc = te.repeat_labels(labels, s)) return rc; }
+  if (int rc = cfm_euler_loop(net, sc, emb, x, x_channels, cond ? te.cond_windows(x_channels) : nullptr, cond_channels, nullptr, t_span_host, n_t, traj,
+                              plan->chunk, n, 0, s, te.labels, nullptr, &te)) return rc;
+  if (u8_out) return quantize_u8_launch(x, u8_out, n, s);
+  return 0;
+}
+
+int mi355_ddpm_sample_tiled(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt,
+                            const mi355_ddpm_schedule* sched, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
+                            int64_t workspace_bytes, void* stream, const mi355_tile_plan* plan) {
+  MI355_REQUIRE(net && x && tb && opt, -1, "ddpm_sample_tiled: null argument");
+  TileSpec ts;
+  if (int rc = check_tile_plan("ddpm_sample_tiled", net, plan, batch, ts)) return rc;
+  DdpmCall c = ddpm_call("ddpm_sample_tiled", plan->chunk, nullptr);   // the net runs at the chunk
+  if (sched) {
+    if (int rc = check_schedule(c.who, tb, opt, sched, false, c.ls)) return rc;
+    c.th = sched_times(tb->Ns, sched);
+  } else {
+    c.th = ddpm_times(tb->Ns);
+  }
+  c.tile = &ts; c.spec.tile = &ts;
+  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

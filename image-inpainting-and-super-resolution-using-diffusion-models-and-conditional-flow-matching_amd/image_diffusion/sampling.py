@@ -285,6 +285,41 @@ class FeatureCache:
         return dict(cache_interval=self.interval, cache_schedule=self.schedule, cache_branch=self.branch)
 
 
+class Tiling:
+    """Tiled sampling of canvases larger than the network's frame (MultiDiffusion: Bar-Tal et al., ICML 2023; training-free; BUILD-DEFINED
+    EXTENSION, no reference counterpart): at every network evaluation the canvas [B, C, Hc, Wc] (Hc, Wc >= image_size) is cut into overlapping
+    image_size windows, the net runs on all windows as a batch, and the predictions are fused per pixel by a weighted average; the sampler's own
+    step is then taken on the canvas.  stride: an int or (sy, sx) in 1..image_size (None: image_size // 2); weight: "uniform" (the plain
+    average) or "tent" (fades the seams); chunk: windows per forward (None: all of a call's, up to the engine's max_batch()).  Taken as tiling=
+    by get_prior_sample_fn and get_conditional_sample_fn (Amortized, Replacement, RePaint), or carried by the chain,
+    ddpm.with_tiling(Tiling(...)), which get_ddim_sample_fn reads as well (the fused path only); and by torchcfm_compat.NeuralODE.  The guided,
+    reconstruction-guided, multistep, shaped and cached loops refuse it.  Sample quality under tiling is
+    untested (no trained checkpoint is at hand); the arithmetic is tested against an fp64 / fp32 restatement."""
+
+    def __init__(self, stride=None, weight="uniform", chunk=None):
+        if weight not in _lib.TILE_WEIGHTS:
+            raise ValueError(f"Tiling weight must be one of {sorted(_lib.TILE_WEIGHTS)}, got {weight!r}")
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError(f"Tiling chunk must be >= 1, got {chunk}")
+        self.stride, self.weight, self.chunk = stride, weight, (None if chunk is None else int(chunk))
+
+
+def _tiling_of(ddpm, tiling=None):
+    """The tiling a sample function runs under: its own argument, else the chain's (DDPM.with_tiling)."""
+    return tiling if tiling is not None else getattr(ddpm, "tiling", None)
+
+
+def _refuse_tiling(tiling, loop: str):
+    if tiling is not None:
+        raise NotImplementedError(f"tiling is not built for {loop} (it runs with the prior, amortized, replacement / RePaint and DDIM samplers)")
+
+
+def _need_fused_tiling(engine, tiling):
+    if tiling is not None and engine is None:
+        raise NotImplementedError("tiling runs inside the fused loop: pass an eps_model built by make_eps_model(network, ddpm) for this "
+                                  "schedule and device tensors (an arbitrary callable sees whole frames only)")
+
+
 def _cache_of(ddpm, feature_cache=None):
     """The cache a sample function runs under: its own argument, else the chain's (DDPM.with_feature_cache)."""
     return feature_cache if feature_cache is not None else getattr(ddpm, "feature_cache", None)
@@ -296,7 +331,7 @@ def _refuse_feature_cache(feature_cache, loop: str):
 
 
 def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_fraction=1.0, noise_condition=True,
-              pad_value=-2.0, none_value=-2.0, guidance_scale=None, ddim_sigma=None, walk=None, feature_cache=None):
+              pad_value=-2.0, none_value=-2.0, guidance_scale=None, ddim_sigma=None, walk=None, feature_cache=None, tiling=None):
     global _draw_counter
     xi = xT.detach().clone().float().contiguous()
     noise = None
@@ -322,6 +357,15 @@ def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_f
         if shaping is not None:
             _refuse_feature_cache(feature_cache, "the shaped loops (DDPM.with_x0_shaping)")
         kw.update(feature_cache.kwargs())
+    tiling = _tiling_of(ddpm, tiling)
+    if tiling is not None:
+        if guidance_scale is not None:
+            _refuse_tiling(tiling, "the guided (classifier-free guidance) loops")
+        if shaping is not None:
+            _refuse_tiling(tiling, "the shaped loops (DDPM.with_x0_shaping)")
+        if feature_cache is not None:
+            raise NotImplementedError("tiling together with feature_cache is not built")
+        kw["tiling"] = tiling
     if shaping is not None:   # the same loop with per-image shaping of x0_hat: mi355_ddpm_shaped_sample
         engine.ddpm_shaped(xi, _tables(ddpm), shaping, **kw)
     else:
@@ -337,18 +381,21 @@ def _need_fused(engine, feature_cache):
                                   "schedule and device tensors (an arbitrary callable is evaluated whole)")
 
 
-def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood, feature_cache=None):
+def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood, feature_cache=None, tiling=None):
     """sampling.py:50-75.  Under Amortized conditioning the net is fed `likelihood.none_like` (sampling.py:36-37).
-    feature_cache (None: untouched): a FeatureCache."""
+    feature_cache (None: untouched): a FeatureCache.  tiling (None: the chain's, ddpm.tiling; neither: untouched): a Tiling; xT is then a canvas."""
     amortized = isinstance(conditioning, Amortized)
     feature_cache = _cache_of(ddpm, feature_cache)
+    tiling = _tiling_of(ddpm, tiling)
 
     @torch.no_grad()
     def sample(xT):
         engine = _fast_engine(eps_model, ddpm, xT)
         _need_fused(engine, feature_cache)
+        _need_fused_tiling(engine, tiling)
         if engine is not None:
-            return _run_fast(engine, ddpm, xT, _lib.DDPM_PRIOR, None, none_value=_none_value(likelihood, xT), feature_cache=feature_cache)
+            return _run_fast(engine, ddpm, xT, _lib.DDPM_PRIOR, None, none_value=_none_value(likelihood, xT), feature_cache=feature_cache,
+                             tiling=tiling)
         none = likelihood.none_like(xT) if amortized else None
         return _run_generic(eps_model, ddpm, xT, amortized=amortized, cond_pred=none, cond_corr=none)
 
@@ -357,27 +404,32 @@ def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Condition
 
 # Conditional sampling ---------------------------------------------------------------------------------
 
-def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood, feature_cache=None):
+def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood, feature_cache=None, tiling=None):
     """feature_cache (None: the chain's, ddpm.feature_cache; neither: untouched): a FeatureCache; Amortized, Replacement and RePaint take it, the
-    other conditionings refuse it by name."""
+    other conditionings refuse it by name.  tiling (None: the chain's, ddpm.tiling; neither: untouched): a Tiling, xT and the condition are then
+    canvases; taken and refused by the same conditionings."""
     feature_cache = _cache_of(ddpm, feature_cache)
+    tiling = _tiling_of(ddpm, tiling)
     if isinstance(conditioning, ClassifierFreeGuidance):   # (an Amortized: before it)
         _refuse_feature_cache(feature_cache, "ClassifierFreeGuidance (the guided loops)")
+        _refuse_tiling(tiling, "ClassifierFreeGuidance (the guided loops)")
         return _cfg_sample_fn(eps_model, ddpm, conditioning, likelihood)
     if isinstance(conditioning, Amortized):
-        return _amortized_sample_fn(eps_model, ddpm, conditioning, likelihood, feature_cache)
+        return _amortized_sample_fn(eps_model, ddpm, conditioning, likelihood, feature_cache, tiling)
     if isinstance(conditioning, RePaint):   # (a Replacement: before it)
         return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, walk=repaint_walk(ddpm.Ns, conditioning.jump_length,
-                                                                                                   conditioning.n_resample), feature_cache=feature_cache)
+                                                                                                   conditioning.n_resample), feature_cache=feature_cache,
+                                      tiling=tiling)
     if isinstance(conditioning, Replacement):
-        return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, feature_cache=feature_cache)
+        return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, feature_cache=feature_cache, tiling=tiling)
     if isinstance(conditioning, ReconstructionGuidance):
         _refuse_feature_cache(feature_cache, "ReconstructionGuidance (the backward pass needs a whole forward)")
+        _refuse_tiling(tiling, "ReconstructionGuidance (the backward pass needs a whole forward)")
         return _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning, likelihood)
     raise NotImplementedError(f"no sampler for conditioning type {type(conditioning).__name__}")
 
 
-def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood, feature_cache=None):
+def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood, feature_cache=None, tiling=None):
     """sampling.py:80-133.  The corrector calls the x0 model WITHOUT the condition (sampling.py:116), so the
     network sees none_like there - reproduced."""
 
@@ -386,9 +438,10 @@ def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood, f
         condition = condition.to(xT.device).float().contiguous()
         engine = _fast_engine(eps_model, ddpm, xT)
         _need_fused(engine, feature_cache)
+        _need_fused_tiling(engine, tiling)
         if engine is not None:
             return _run_fast(engine, ddpm, xT, _lib.DDPM_AMORTIZED, condition, n_corrector=conditioning.n_corrector,
-                             delta=conditioning.delta, none_value=_none_value(likelihood, xT), feature_cache=feature_cache)
+                             delta=conditioning.delta, none_value=_none_value(likelihood, xT), feature_cache=feature_cache, tiling=tiling)
         return _run_generic(eps_model, ddpm, xT, amortized=True, cond_pred=condition, cond_corr=likelihood.none_like(xT),
                             n_corrector=conditioning.n_corrector, delta=conditioning.delta)
 
@@ -486,7 +539,7 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
     return sample
 
 
-def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihood, walk=None, feature_cache=None):
+def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihood, walk=None, feature_cache=None, tiling=None):
     """sampling.py:209-260: overwrite the known pixels with the (noised) condition before each predictor step.
     walk (RePaint; None: the plain descent): the levels to visit, conditioning.repaint_walk; a move up re-noises the state by
     q(x_k | x_{k-1}) (mi355_renoise_step), a move down is the replacement step of its level.  A walk without upward moves is the plain descent."""
@@ -499,10 +552,11 @@ def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihoo
         pad = float(likelihood.pad_value)
         engine = _fast_engine(eps_model, ddpm, xT)
         _need_fused(engine, feature_cache)
+        _need_fused_tiling(engine, tiling)
         if engine is not None:
             return _run_fast(engine, ddpm, xT, _lib.DDPM_REPLACEMENT, condition, n_corrector=conditioning.n_corrector,
                              delta=conditioning.delta, start_fraction=conditioning.start_fraction,
-                             noise_condition=conditioning.noise, pad_value=pad, walk=walk, feature_cache=feature_cache)
+                             noise_condition=conditioning.noise, pad_value=pad, walk=walk, feature_cache=feature_cache, tiling=tiling)
         rep = dict(condition=condition, start_fraction=conditioning.start_fraction, noise=bool(conditioning.noise), pad_value=pad)
         return _run_generic(eps_model, ddpm, xT, amortized=False, cond_pred=None, cond_corr=None, replacement=rep,
                             n_corrector=conditioning.n_corrector, delta=conditioning.delta, walk=walk)
@@ -519,6 +573,7 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
     a condition.  Fused path (eps_model built by make_eps_model for this very schedule): the whole loop in mi355_ddpm_multistep_sample; any other
     callable: a host loop over dpmpp_step_ (guided: cfg_combine, then the step).  Sample quality is untested."""
     _refuse_feature_cache(_cache_of(ddpm), "the DPM-Solver++ multistep loops")
+    _refuse_tiling(_tiling_of(ddpm), "the DPM-Solver++ multistep loops")
     coefs = ddpm.dpm_solver_coefs(order)
     cx, c0, c1 = (c.tolist() for c in coefs)
     shaping = _shaping_of(ddpm, guidance_scale is not None)
@@ -570,7 +625,11 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
     DDIM(eta=0) on the same tables with the reference's clipped x0_hat.  sample(xT, condition=None).
     guidance_scale (None: unguided): classifier-free guidance of eps against the none_like condition; needs a condition.
     eta (0: the deterministic sampler, untouched): stochastic DDIM with sigma = ddpm.ddim_sigma(eta), one noise draw per step with i > 0;
-    eta = 1 has the ancestral step's mean and variance.  On a RespacedDDPM this is DDIM on a sub-sequence of the training steps."""
+    eta = 1 has the ancestral step's mean and variance.  On a RespacedDDPM this is DDIM on a sub-sequence of the training steps.
+    On a chain that carries a Tiling (ddpm.with_tiling(Tiling(...))) xT (and the condition) are canvases.  Not with guidance_scale."""
+    tiling = _tiling_of(ddpm)
+    if guidance_scale is not None:
+        _refuse_tiling(tiling, "the guided (classifier-free guidance) loops")
     feature_cache = _cache_of(ddpm)   # DDPM.with_feature_cache: feature reuse across the steps (the fused path only; not under guidance)
     if guidance_scale is not None:
         _refuse_feature_cache(feature_cache, "the guided (classifier-free guidance) loops")
@@ -589,10 +648,11 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
         if guidance_scale is not None and condition is None:
             raise ValueError("guidance_scale needs a condition to guide towards")
         _need_fused(engine, feature_cache)
+        _need_fused_tiling(engine, tiling)
         if engine is not None:
             nv = _none_value(likelihood, xT) if likelihood is not None else 0.0
             return _run_fast(engine, ddpm, xT, _lib.DDIM, condition, none_value=nv, guidance_scale=guidance_scale, ddim_sigma=sigma,
-                             feature_cache=feature_cache)
+                             feature_cache=feature_cache, tiling=tiling)
         if guidance_scale is not None:
             none = likelihood.none_like(xT) if likelihood is not None else torch.zeros_like(condition)
             return _run_generic_cfg(eps_model, ddpm, xT, cond=condition, none=none, guidance_scale=guidance_scale, ddim=True, ddim_sigma=sigma)

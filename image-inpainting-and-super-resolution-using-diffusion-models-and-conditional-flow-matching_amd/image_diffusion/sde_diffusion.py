@@ -79,6 +79,7 @@ class DDPM(nn.Module):
 
     x0_shaping: Optional[X0Shaping] = None   # set on the views of with_x0_shaping
     feature_cache = None                     # set on the views of with_feature_cache (a sampling.FeatureCache)
+    tiling = None                            # set on the views of with_tiling (a sampling.Tiling)
 
     def __init__(self, Ns: int):
         super().__init__()
@@ -233,6 +234,15 @@ class DDPM(nn.Module):
         view.__dict__["feature_cache"] = feature_cache
         return view
 
+    def with_tiling(self, tiling) -> "DDPM":
+        """BUILD-DEFINED EXTENSION (no reference counterpart): a view of this chain - the same buffers, the same steps - whose fused samplers
+        take canvases larger than the network's frame (MultiDiffusion; tiling: a sampling.Tiling, or None for a view without one).  The sample
+        functions that end in UNetEngine.ddpm_sample (prior, amortized, replacement / RePaint, DDIM) honour it, the others refuse such a chain
+        by name.  Commutes with respace.  Sample quality is untested."""
+        view = self._view()
+        view.__dict__["tiling"] = tiling
+        return view
+
     def _view(self) -> "DDPM":
         view = copy.copy(self)
         # its own registries over the same tensors: moving the view does not re-point the base's buffers
@@ -299,6 +309,7 @@ class RespacedDDPM(DDPM):
         self.tmin, self.tmax, self.ts = base.tmin, base.tmax, base.ts
         self.x0_shaping = getattr(base, "x0_shaping", None)   # a shaped base's respacing stays shaped
         self.feature_cache = getattr(base, "feature_cache", None)
+        self.tiling = getattr(base, "tiling", None)
         acp32 = base.alphas_cumprod.detach().to("cpu", torch.float32)[list(steps)]
         if not bool(torch.all(torch.isfinite(acp32) & (acp32 > 0))):
             raise ValueError("the base's alphas_cumprod is not finite and positive at every kept step (DDPM(Ns <= 20) is not respaced)")

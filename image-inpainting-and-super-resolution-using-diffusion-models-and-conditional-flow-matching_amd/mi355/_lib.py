@@ -133,6 +133,15 @@ def feature_cache(branch, full, drift_ptr=None):
     return fc
 
 
+class TilePlanC(C.Structure):
+    """mi355_tile_plan (include/mi355_sampler.h): the canvas, the window strides, the blend weight and the windows per forward of a tiled call."""
+    _fields_ = [("canvas_h", C.c_int32), ("canvas_w", C.c_int32), ("stride_y", C.c_int32), ("stride_x", C.c_int32), ("weight", C.c_int32),
+                ("chunk", C.c_int32)]
+
+
+TILE_WEIGHTS = {"uniform": 0, "tent": 1}   # MI355_TILE_UNIFORM, MI355_TILE_TENT
+
+
 def x0_shaping(shaping):
     """None, an object with dynamic_threshold / max_threshold / guidance_rescale (DDPM.x0_shaping), or a (quantile, max_threshold, rescale_phi)
     triple -> X0ShapingC or None.  None stands for "off" in each place."""
@@ -168,6 +177,16 @@ SIGNATURES = {
                                             _VP, _I64, _VP, C.POINTER(FeatureCacheC)]),
     "mi355_feature_cache_workspace_bytes": (_I64, [_VP, _I, _I, _I]),
     "mi355_feature_drift": (_I, [_VP, _VP, _I, _I, _I64, _VP, _VP]),
+    "mi355_tile_count": (_I, [_I, C.POINTER(TilePlanC), C.POINTER(C.c_int32)]),
+    "mi355_tile_origins": (_I, [_I, C.POINTER(TilePlanC), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mi355_tiled_workspace_bytes": (_I64, [_VP, _I, C.POINTER(TilePlanC)]),
+    "mi355_tile_gather": (_I, [_VP, _VP, _I, _I, _I, C.POINTER(TilePlanC), _VP]),
+    "mi355_tile_labels": (_I, [_VP, _VP, _I, _I, _VP]),
+    "mi355_tile_blend": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, C.POINTER(TilePlanC), _VP]),
+    "mi355_unet_forward_tiled": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _VP, _I, C.POINTER(TilePlanC), _VP, _I64, _VP]),
+    "mi355_cfm_euler_sample_tiled": (_I, [_VP, _VP, _I, _VP, _I, _I, _VP, _FP, _I, _VP, _VP, _I, _VP, _I64, _VP, C.POINTER(TilePlanC)]),
+    "mi355_ddpm_sample_tiled": (_I, [_VP, _VP, _I, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), C.POINTER(DDPMScheduleC), _VP, _I64, _I, _VP,
+                                     _I64, _VP, C.POINTER(TilePlanC)]),
     "mi355_unet_vjp": (_I, [_VP, _VP, _VP, _I, _I, _VP, _I64, _VP]),
     "mi355_unet_plan_op": (_I, [_VP, _I, C.POINTER(C.c_int32)]),
     "mi355_unet_read_tensor": (_I, [_VP, _I, _I, _VP, _I, _VP, _I64, _VP]),

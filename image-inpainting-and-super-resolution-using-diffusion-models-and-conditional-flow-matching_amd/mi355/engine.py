@@ -84,6 +84,26 @@ def ddpm_eval_count(K: int, mode: int, n_corrector: int, walk=None) -> int:
     return down * (1 + (0 if mode == _lib.DDIM else max(0, int(n_corrector))))
 
 
+def tile_plan(image_size: int, canvas_hw, stride=None, weight="uniform", chunk=None):
+    """The window geometry of a tiled call (host only; UNetEngine.tile_plan): asks mi355_tile_count / mi355_tile_origins, so the binding and the
+    kernels share one function.  chunk=None leaves the plan's chunk at 1 for the caller to settle."""
+    Hc, Wc = (int(v) for v in canvas_hw)
+    if stride is None:
+        stride = max(1, int(image_size) // 2)
+    sy, sx = (int(stride), int(stride)) if isinstance(stride, int) else (int(v) for v in stride)
+    if weight not in _lib.TILE_WEIGHTS:
+        raise ValueError(f"tiling weight must be one of {sorted(_lib.TILE_WEIGHTS)}, got {weight!r}")
+    plan = _lib.TilePlanC(Hc, Wc, sy, sx, _lib.TILE_WEIGHTS[weight], 1 if chunk is None else int(chunk))
+    L = _lib.lib()
+    cnt = (C.c_int32 * 3)()
+    check(L.mi355_tile_count(int(image_size), C.byref(plan), cnt), "mi355_tile_count")
+    oy, ox = (C.c_int32 * cnt[0])(), (C.c_int32 * cnt[1])()
+    check(L.mi355_tile_origins(int(image_size), C.byref(plan), oy, ox), "mi355_tile_origins")
+    oy, ox = list(oy), list(ox)
+    return {"plan": plan, "ny": int(cnt[0]), "nx": int(cnt[1]), "n_windows": int(cnt[2]), "oy": oy, "ox": ox,
+            "origins": [(a, b) for a in oy for b in ox]}
+
+
 class UNetEngine:
     def __init__(self, cfg_kwargs: dict, state_dict: Dict[str, torch.Tensor], device, precision: str = "bf16", differentiable: bool = False,
                  debug=None):
@@ -191,6 +211,59 @@ class UNetEngine:
         if Cx + Cc != self.in_channels:
             raise ValueError(f"x ({Cx}) + condition ({Cc}) channels != in_channels ({self.in_channels})")
         return B, Cx, Cc
+
+    # ---- tiled sampling: canvases larger than the net's frame (MultiDiffusion; mi355_tile_plan in include/mi355_sampler.h) ----
+    def tile_plan(self, canvas_hw, stride=None, weight="uniform", chunk=None):
+        """The geometry of a tiled call on canvases of canvas_hw = (Hc, Wc), from the library's own host function (mi355_tile_count /
+        mi355_tile_origins) -> dict(plan, ny, nx, n_windows, oy, ox, origins).  stride: an int or (sy, sx), default image_size // 2; weight:
+        "uniform" or "tent"; chunk: windows per forward (None: as many as a call has, up to max_batch(), decided per call).  origins: the
+        (oy, ox) of the windows in batch order (row-major)."""
+        return tile_plan(self.image_size, canvas_hw, stride, weight, chunk)
+
+    def _tiled(self, tiling, x, cond, channels: bool = True):
+        """The checks of a tiled call -> (B, Cx, Cc, mi355_tile_plan with its chunk settled).  tiling: an object or dict with stride, weight, chunk."""
+        get = tiling.get if isinstance(tiling, dict) else lambda k, d=None: getattr(tiling, k, d)
+        if x.dim() != 4:
+            raise ValueError("x must be [B, C, Hc, Wc]")
+        B, Cx, Hc, Wc = x.shape
+        Cc = 0
+        if cond is not None:
+            if cond.shape[0] != B or cond.shape[2:] != x.shape[2:]:
+                raise ValueError("condition must match x in batch and spatial size")
+            Cc = cond.shape[1]
+        if channels and Cx + Cc != self.in_channels:   # (the DDPM loop decides itself what the net sees: the library checks its channels)
+            raise ValueError(f"x ({Cx}) + condition ({Cc}) channels != in_channels ({self.in_channels})")
+        chunk = get("chunk")
+        tp = self.tile_plan((Hc, Wc), get("stride"), get("weight", "uniform") or "uniform", chunk)
+        plan = tp["plan"]
+        if chunk is None:
+            plan.chunk = min(B * tp["n_windows"], self.max_batch())
+        elif plan.chunk > self.max_batch():
+            raise ValueError(f"tiling chunk ({plan.chunk}) is above max_batch() ({self.max_batch()})")
+        return B, Cx, Cc, plan
+
+    def forward_tiled(self, x: torch.Tensor, t: float, cond: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None, *, tiling,
+                      out: Optional[torch.Tensor] = None):
+        """One tiled evaluation at the host time t (mi355_unet_forward_tiled): x [B, C, Hc, Wc] is cut into overlapping image_size windows, the net
+        runs on them in chunks, and the window predictions are blended per pixel -> [B, out_channels, Hc, Wc].  cond: a condition canvas; y: one
+        class label per canvas."""
+        B, Cx, Cc, plan = self._tiled(tiling, x, cond)
+        lab, lab_p = self._labels(y, B)
+        if out is None:
+            out = torch.empty(B, self.out_channels, x.shape[2], x.shape[3], device=self.device, dtype=torch.float32)
+        self._fwd_state = None
+        ws, wsb = self._workspace_tiled(B, plan)
+        check(self.L.mi355_unet_forward_tiled(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc,
+                                              float(t), lab_p, self._chk(out, "out"), B, C.byref(plan), ws, wsb, self._stream()),
+              "mi355_unet_forward_tiled")
+        return out
+
+    def _workspace_tiled(self, B: int, plan):
+        need = check(self.L.mi355_tiled_workspace_bytes(self.handle, B, C.byref(plan)), "mi355_tiled_workspace_bytes")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return C.c_void_p(self._ws.data_ptr()), self._ws.numel()
 
     # ---- classifier-free guidance: v = v_u + w (v_c - v_u), both halves from one evaluation at batch 2B ----
     def _guidance_args(self, guidance_scale, B: int, y, cond, null_label):
@@ -445,8 +518,11 @@ class UNetEngine:
     def cfm_euler(self, x: torch.Tensor, t_span: Sequence[float], cond: Optional[torch.Tensor] = None, keep_traj: bool = False,
                   want_u8: bool = False, cond_drift: bool = False, y: Optional[torch.Tensor] = None, guidance_scale=None,
                   null_label: Optional[int] = None, none_value: float = -2.0, cache_interval=None, cache_branch=None, cache_schedule=None,
-                  cache_drift: bool = False):
+                  cache_drift: bool = False, tiling=None):
         """In-place Euler integration of x over t_span (host floats).  Returns (x, traj or None, u8 or None).
+        tiling (None: every path below, untouched; an object or dict with stride, weight, chunk, e.g. image_diffusion.sampling.Tiling): x (and
+        cond) are canvases [B, C, Hc, Wc] with Hc, Wc >= image_size; every step evaluates the net on overlapping windows and blends them
+        (mi355_cfm_euler_sample_tiled).  B * windows beyond chunk is handled inside the call.  Not with guidance_scale, cache_* or cond_drift.
         cache_interval / cache_branch / cache_schedule (all None: the paths below, untouched): feature reuse across steps (DeepCache;
         mi355_cfm_euler_sample_cached).  Step k is evaluation k; see mi355.engine.feature_cache_args and cache_branches().  Not with guidance_scale.
         cache_drift=True (needs a schedule; cache_interval=1 measures every step): also returns, as a fourth value, the [n_steps, B] tensor of
@@ -457,6 +533,10 @@ class UNetEngine:
         slice may sum in another order than those of the whole batch would).
         y: class labels [B] of a class-conditional engine: every step evaluates model(t_k, x_k, y) (mi355_cfm_euler_sample_labels).
         guidance_scale (a float or a [B] tensor; None: the paths above, untouched): classifier-free guidance, see cfm_cfg."""
+        if tiling is not None:
+            return self._cfm_euler_tiled(x, t_span, cond, keep_traj, want_u8, y, tiling,
+                                         dict(guidance_scale=guidance_scale, cache_interval=cache_interval, cache_branch=cache_branch,
+                                              cache_schedule=cache_schedule, cache_drift=cache_drift or None, cond_drift=cond_drift or None))
         cache = feature_cache_args(max(0, len(t_span) - 1), cache_interval, cache_branch, cache_schedule, guidance_scale)
         if cache_drift and cache is None:
             raise ValueError("cache_drift measures the cached feature: give cache_interval or cache_schedule (cache_interval=1: every step)")
@@ -503,6 +583,28 @@ class UNetEngine:
                                             Cc, int(bool(cond_drift)), arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
                                             self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
               "mi355_cfm_euler_sample")
+        return x, traj, u8
+
+    @staticmethod
+    def _tiling_refusals(others: dict):
+        """tiling together with an option that has no tiled entry point: NotImplementedError naming the pair."""
+        for k, v in others.items():
+            if v is not None:
+                raise NotImplementedError(f"tiling together with {k} is not built (tiled sampling has the plain Euler and DDPM loops only)")
+
+    def _cfm_euler_tiled(self, x, t_span, cond, keep_traj, want_u8, y, tiling, others):
+        self._tiling_refusals(others)
+        B, Cx, Cc, plan = self._tiled(tiling, x, cond)
+        lab, lab_p = self._labels(y, B)
+        ts = [float(v) for v in t_span]
+        arr = (C.c_float * len(ts))(*ts)
+        traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
+        self._fwd_state = None
+        ws, wsb = self._workspace_tiled(B, plan)
+        check(self.L.mi355_cfm_euler_sample_tiled(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc, 0,
+                                                  lab_p, arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
+                                                  self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream(),
+                                                  C.byref(plan)), "mi355_cfm_euler_sample_tiled")
         return x, traj, u8
 
     def _workspace_rk(self, batch: int, stages: int):
@@ -725,9 +827,12 @@ class UNetEngine:
     def ddpm_sample(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], *, mode: int, cond: Optional[torch.Tensor] = None,
                     noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0,
                     noise_condition=True, pad_value=-2.0, none_value=-2.0, seed=0, guidance_scale=None, cache_interval=None, cache_branch=None,
-                    cache_schedule=None, y: Optional[torch.Tensor] = None, null_label: Optional[int] = None, timesteps=None, train_steps=None,
-                    ddim_sigma=None, walk=None):
+                    cache_schedule=None, tiling=None, y: Optional[torch.Tensor] = None, null_label: Optional[int] = None, timesteps=None,
+                    train_steps=None, ddim_sigma=None, walk=None):
         """In-place reverse-denoising loop.  tables: name -> CPU fp32 tensor [Ns] (DDPM buffers).
+        tiling (None: every path below, untouched; an object or dict with stride, weight, chunk): x, cond and the injected noise are canvases
+        [.., C, Hc, Wc] with Hc, Wc >= image_size; every evaluation runs the net on overlapping windows and blends the eps predictions, the step
+        arithmetic is the loop's own on the canvas (mi355_ddpm_sample_tiled).  Not with guidance_scale or cache_*.
         cache_interval / cache_branch / cache_schedule (all None: the paths below, untouched): feature reuse across evaluations (DeepCache;
         mi355_ddpm_sample_sched_cached; an unscheduled call runs as the identity schedule, which is bit-identical).  Evaluations are numbered in loop
         order, correctors included (ddpm_eval_count); see mi355.engine.feature_cache_args and cache_branches().  Not with guidance_scale.
@@ -743,6 +848,9 @@ class UNetEngine:
             raise ValueError("condition must have the shape of x")
         if guidance_scale is None and y is not None:
             raise NotImplementedError("ddpm_sample takes class labels on the guided path only (guidance_scale=)")
+        if tiling is not None:
+            self._tiling_refusals(dict(guidance_scale=guidance_scale, cache_interval=cache_interval, cache_branch=cache_branch,
+                                       cache_schedule=cache_schedule))
         sched = self._ddpm_schedule(tables, timesteps, train_steps, ddim_sigma, walk)
         cache = feature_cache_args(lambda: ddpm_eval_count(int(tables["alphas_cumprod_prev"].numel()), mode, n_corrector, walk), cache_interval,
                                    cache_branch, cache_schedule, guidance_scale)
@@ -765,6 +873,14 @@ class UNetEngine:
         self._fwd_state = None
         opt = _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value,
                                 int(cond is None), seed)
+        if tiling is not None:
+            plan = self._tiled(tiling, x, None, channels=False)[3]
+            ws, wsb = self._workspace_tiled(B, plan)
+            check(self.L.mi355_ddpm_sample_tiled(self.handle, *self._ddpm_args(x, cond), C.byref(tb), C.byref(opt),
+                                                 C.byref(sched[0]) if sched is not None else None, *self._noise_args(noise), B, ws, wsb, self._stream(),
+                                                 C.byref(plan)), "mi355_ddpm_sample_tiled")
+            del keep
+            return x
         name = "mi355_ddpm_sample" if sched is None else "mi355_ddpm_sample_sched" if cache is None else "mi355_ddpm_sample_sched_cached"
         fc = _lib.feature_cache(*cache) if cache is not None else None
         ws, wsb = self.workspace(B)

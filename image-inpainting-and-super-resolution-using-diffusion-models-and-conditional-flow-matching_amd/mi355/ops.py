@@ -261,6 +261,35 @@ class Ops:
                                             int(philox is not None and z is None), seed, off, x.numel(), _stream()))
         return x
 
+    # --- tiled sampling (csrc/tile.hip): plan = mi355.engine.tile_plan(image_size, (Hc, Wc), stride, weight) ---
+    def tile_gather(self, canvas, image_size, plan):
+        """canvas [B, C, Hc, Wc] -> its windows [B * n_windows, C, S, S] in batch order (canvas-major, windows row-major): an exact copy."""
+        B, Cc = canvas.shape[:2]
+        out = torch.empty(B * plan["n_windows"], Cc, image_size, image_size, device=canvas.device, dtype=torch.float32)
+        check(_lib.lib().mi355_tile_gather(_req(canvas, "canvas"), _req(out, "windows"), B, Cc, int(image_size), C.byref(plan["plan"]), _stream()))
+        return out
+
+    def tile_labels(self, y, n_windows):
+        """labels [B] int32 -> [B * n_windows]: every window of a canvas carries the canvas's label."""
+        out = torch.empty(y.shape[0] * int(n_windows), device=y.device, dtype=torch.int32)
+        check(_lib.lib().mi355_tile_labels(_req(y, "y", torch.int32), _req(out, "out", torch.int32), y.shape[0], int(n_windows), _stream()))
+        return out
+
+    def tile_blend_(self, windows, plan, out=None, x=None, dt=0.0):
+        """windows [B * n_windows, C, S, S] -> the per-pixel weighted average on the canvas [B, C, Hc, Wc] (windows in ascending index: num += w v,
+        den += w, num / den; mi355_tile_blend), written to out (made if None).  x (None: no update): x <- x + dt * average, in place."""
+        S = windows.shape[2]
+        if windows.shape[0] % plan["n_windows"]:
+            raise ValueError("windows must hold n_windows rows per canvas")
+        B, Cc = windows.shape[0] // plan["n_windows"], windows.shape[1]
+        shape = (B, Cc, plan["plan"].canvas_h, plan["plan"].canvas_w)
+        if out is None:
+            out = torch.empty(shape, device=windows.device, dtype=torch.float32)
+        if tuple(out.shape) != shape or (x is not None and tuple(x.shape) != shape):
+            raise ValueError(f"out and x must be {shape}")
+        check(_lib.lib().mi355_tile_blend(_req(windows, "windows"), _req(out, "out"), _opt(x, "x"), float(dt), B, Cc, S, C.byref(plan["plan"]), _stream()))
+        return out
+
     def guidance_seed(self, x, eps, cond, c_recip, c_recipm1, mode, pad_value):
         """-> (g_eps, g_x): cotangent for the U-Net VJP and the direct-path gradient of the per-sample constraint
         (mode 0 = Painting.loss with the pad sentinel masked, 1 = HyperResolution.loss; sampling.py:148-160)."""

@@ -170,11 +170,16 @@ class NeuralODE:
 
     cache_interval / cache_branch (BUILD-DEFINED EXTENSION; None: untouched): feature reuse across the Euler steps of a UNetModelWrapper
     (DeepCache: one full U-Net evaluation in cache_interval steps, the cache_branch outermost block pairs recomputed at every step;
-    UNetEngine.cfm_euler).  solver="euler" on the device only; any other solver or vector field refuses it."""
+    UNetEngine.cfm_euler).  solver="euler" on the device only; any other solver or vector field refuses it.
+
+    tiling (BUILD-DEFINED EXTENSION; None: untouched; an image_diffusion.sampling.Tiling): x is a canvas [B, C, Hc, Wc] larger than the model's
+    frame, every Euler step evaluates the model on overlapping windows and blends them (MultiDiffusion; UNetEngine.cfm_euler(tiling=)).
+    solver="euler" on a UNetModelWrapper on the device only; not with cache_interval / cache_branch."""
 
     RK_SOLVERS = RK_SOLVERS   # mi355.ode: every fixed-step tableau name but "euler"
 
-    def __init__(self, vector_field, solver="euler", sensitivity="adjoint", atol=1e-4, rtol=1e-4, cache_interval=None, cache_branch=None, **kwargs):
+    def __init__(self, vector_field, solver="euler", sensitivity="adjoint", atol=1e-4, rtol=1e-4, cache_interval=None, cache_branch=None, tiling=None,
+                 **kwargs):
         if solver not in ("euler", "dopri5") + self.RK_SOLVERS + AB_SOLVERS:
             raise NotImplementedError(f"solver={solver!r}: only 'euler', 'dopri5', {self.RK_SOLVERS} and {AB_SOLVERS} are built")
         self.cache = {}
@@ -183,6 +188,13 @@ class NeuralODE:
                 raise NotImplementedError("cache_interval / cache_branch (feature reuse) are built for solver='euler' on a UNetModelWrapper "
                                           "(not for the guided, Runge-Kutta, Adams-Bashforth or adaptive solvers, nor for other callables)")
             self.cache = dict(cache_interval=1 if cache_interval is None else cache_interval, cache_branch=cache_branch)
+        if tiling is not None:
+            if solver != "euler" or type(vector_field) is not UNetModelWrapper:
+                raise NotImplementedError("tiling is built for solver='euler' on a UNetModelWrapper (not for the guided, Runge-Kutta, "
+                                          "Adams-Bashforth or adaptive solvers, nor for other callables)")
+            if self.cache:
+                raise NotImplementedError("tiling together with cache_interval / cache_branch is not built")
+            self.cache = dict(tiling=tiling)   # (the keyword the Euler call below takes in its place)
         self.vf = vector_field
         self.solver = solver
         self.atol, self.rtol = atol, rtol
@@ -237,7 +249,7 @@ class NeuralODE:
             return traj
         if self.cache:
             from mi355._lib import MI355BackendError
-            raise MI355BackendError("feature reuse (cache_interval) runs inside the device loop: x must be a device tensor")
+            raise MI355BackendError("feature reuse (cache_interval) and tiling run inside the device loop: x must be a device tensor")
         out = [x.clone()]
         for k in range(len(ts) - 1):
             t = ts[k] if isinstance(self.vf, UNetModelWrapper) else torch.tensor(ts[k], device=x.device, dtype=torch.float32)

@@ -58,7 +58,9 @@ extern "C" {
  * kernels as test ops: mi355_linear, mi355_label_emb_linear, mi355_emb_gather, mi355_pack_nhwc, mi355_unpack_nchw, mi355_unpack_channels,
  * mi355_resample (new symbols only); then feature reuse across sampler steps (DeepCache): mi355_unet_cache_info, mi355_unet_forward_cached,
  * mi355_cfm_euler_sample_cached, mi355_ddpm_sample_sched_cached, mi355_feature_cache_workspace_bytes, mi355_feature_drift (new symbols and one new
- * struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * struct only); then tiled sampling of canvases larger than the net's frame: mi355_tile_count, mi355_tile_origins, mi355_tiled_workspace_bytes,
+ * mi355_tile_gather, mi355_tile_labels, mi355_tile_blend, mi355_unet_forward_tiled, mi355_cfm_euler_sample_tiled, mi355_ddpm_sample_tiled (new
+ * symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -498,6 +500,60 @@ int mi355_cfm_euler_sample_cached(mi355_unet* net, float* x, int x_channels, con
 int mi355_ddpm_sample_sched_cached(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tables,
                                    const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched, const float* noise, int64_t n_noise_draws, int batch,
                                    void* workspace, int64_t workspace_bytes, void* stream, const mi355_feature_cache* cache);
+
+/* ---- tiled sampling: canvases larger than the net's frame (MultiDiffusion, Bar-Tal et al. 2023; csrc/tile.hip) ------------------------------
+ * A canvas [B, C, Hc, Wc] with Hc, Wc >= S = image_size is sampled with a net trained on S x S frames.  Every network evaluation of a loop becomes:
+ * cut the canvas into overlapping S x S windows (one gather launch), evaluate the net on the windows as a batch, in chunks of at most `chunk`
+ * rows (the existing forward, a uniform step time, labels and condition windows sliced per chunk), and fuse the window predictions per pixel by a
+ * weighted average (one blend launch): n_chunks forwards + 2 launches.  Everything else of a step is the loop's own arithmetic on the canvas.
+ * GEOMETRY.  Along an axis of length L with stride s, 1 <= s <= S, there are n = ceil((L - S) / s) + 1 windows at origins o_i = min(i * s, L - S):
+ * the last window is clamped to the edge, so every pixel is covered and no window leaves the canvas.  Windows are ordered row-major over (iy, ix),
+ * nW = ny * nx per canvas; window w of canvas b is batch row b * nW + w.  WEIGHTS are separable, p(dy) * p(dx) over the offsets inside the window:
+ * MI355_TILE_UNIFORM p = 1 (MultiDiffusion's plain average), MI355_TILE_TENT p(i) = min(i + 1, S - i) (fades the seams; positive everywhere).
+ * BLEND ORDER (the contract; bit-exact against the eager fp32 expression): for each canvas element, over the windows that cover it in ascending
+ * window index, num += weight * v (product, then sum, each rounded), den += weight; vbar = num / den; with euler_x: x <- x + dt * vbar.
+ * Not built under tiling: guidance, the feature cache, the multistep / Runge-Kutta / Adams-Bashforth loops, x0 shaping, mi355_cfm_recon_sample,
+ * SF2M, cond_drift, per-window labels.  Sample quality under tiling is untested (no trained checkpoint is at hand); the arithmetic is tested
+ * against an fp64 / fp32 restatement. */
+#define MI355_TILE_UNIFORM 0
+#define MI355_TILE_TENT 1
+typedef struct mi355_tile_plan {
+  int32_t canvas_h, canvas_w;   /* Hc, Wc: each >= image_size */
+  int32_t stride_y, stride_x;   /* each in 1..image_size */
+  int32_t weight;               /* MI355_TILE_UNIFORM or MI355_TILE_TENT */
+  int32_t chunk;                /* windows per forward: 1..the handle's largest batch (the entry points that take a handle check the upper end) */
+} mi355_tile_plan;
+/* Host only.  out = { ny, nx, nW }; oy[ny], ox[nx] = the window origins.  Refusals (also those of every entry point below, before any launch, each
+ * naming its field): a canvas side below image_size (MI355_ERR_SHAPE); a stride outside 1..image_size, an unknown weight, chunk < 1 (MI355_ERR_ARG). */
+int mi355_tile_count(int image_size, const mi355_tile_plan* plan, int32_t out[3]);
+int mi355_tile_origins(int image_size, const mi355_tile_plan* plan, int32_t* oy, int32_t* ox);
+/* Host only: the workspace of the three tiled entry points for `batch` canvases = the sampler workspace at batch `chunk`, then the window buffers
+ * (network input [batch * nW, in_channels, S, S], network output [batch * nW, out_channels, S, S]), the blended canvas [batch, out_channels, Hc, Wc]
+ * and, for a class-conditional net, the repeated labels.  chunk above the handle's largest batch (32-bit buffer offsets): MI355_ERR_ARG. */
+int64_t mi355_tiled_workspace_bytes(const mi355_unet* net, int batch, const mi355_tile_plan* plan);
+/* The kernels alone (test ops).  canvas [batch, channels, Hc, Wc] -> windows [batch * nW, channels, S, S], an exact copy; labels [batch] ->
+ * out [batch * n_windows]; windows -> vbar [batch, channels, Hc, Wc] in the blend order above, and euler_x (NULL: none) <- euler_x + dt * vbar. */
+int mi355_tile_gather(const float* canvas, float* windows, int batch, int channels, int image_size, const mi355_tile_plan* plan, void* stream);
+int mi355_tile_labels(const int32_t* labels, int32_t* out, int batch, int n_windows, void* stream);
+int mi355_tile_blend(const float* windows, float* vbar, float* euler_x, float dt, int batch, int channels, int image_size, const mi355_tile_plan* plan,
+                     void* stream);
+/* One tiled evaluation at the host time t_host: out [batch, out_channels, Hc, Wc] = the blended prediction for the canvases x (and cond, a canvas
+ * of cond_channels channels, or NULL); labels: NULL or int32 [batch], one per canvas. */
+int mi355_unet_forward_tiled(mi355_unet* net, const float* x, int x_channels, const float* cond, int cond_channels, float t_host, const int32_t* labels,
+                             float* out, int batch, const mi355_tile_plan* plan, void* workspace, int64_t workspace_bytes, void* stream);
+/* mi355_cfm_euler_sample_labels on canvases: per step one tiled evaluation whose blend launch carries x <- x + dt * vbar.  traj and u8_out work as
+ * before (they are elementwise on the canvas).  The condition canvas is gathered once before the loop.  cond_drift != 0: MI355_ERR_UNSUPPORTED. */
+int mi355_cfm_euler_sample_tiled(mi355_unet* net, float* x, int x_channels, const float* cond, int cond_channels, int cond_drift,
+                                 const int32_t* labels, const float* t_span_host, int n_t, float* traj, uint8_t* u8_out, int batch,
+                                 void* workspace, int64_t workspace_bytes, void* stream, const mi355_tile_plan* plan);
+/* mi355_ddpm_sample_sched on canvases (sched NULL: the plain descent of mi355_ddpm_sample): all three modes and MI355_DDIM, correctors and walks
+ * included.  The blended eps is the network's prediction for the canvas; everything behind it is the existing step arithmetic on the Hc x Wc state
+ * (paste, predictor, x0 clip, corrector, renoise, final clip).  Noise draws are canvas-sized: injected noise is [draws, batch, C, Hc, Wc], the Philox
+ * offset of draw d is d * n_al with n_al the canvas state's element count rounded up to 4.  The amortized condition canvas is gathered once; the
+ * correctors' none_value condition is a constant and is filled directly. */
+int mi355_ddpm_sample_tiled(mi355_unet* net, float* x, int channels, const float* cond, const mi355_ddpm_tables* tables,
+                            const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched, const float* noise, int64_t n_noise_draws, int batch,
+                            void* workspace, int64_t workspace_bytes, void* stream, const mi355_tile_plan* plan);
 
 /* DPM-Solver++ multistep sampling of a DDPM net, orders 1 and 2 (Lu et al. 2022, Algorithm 2, data-prediction form; no reference counterpart).
  * The loop of mi355_ddpm_sample_sched in MI355_DDIM mode with step i replaced by ONE mi355_dpmpp_step launch (guided entry: mi355_dpmpp_cfg_step):

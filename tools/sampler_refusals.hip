@@ -1,6 +1,6 @@
 // Host-only record of what the sampler entry points of libmi355_sampler.so answer before they touch a device: every mi355_*_workspace_bytes
-// value, and for every sampler entry point (and the predictor-step exports) the return code and mi355_last_error() text of a list of calls with
-// ONE fault each.  Nets are planned with unet_plan_dry and driven with made-up pointers, as tools/resolve_steps.hip does; nothing is launched and no
+// value, and for every sampler entry point (the tiled ones and the predictor-step exports included) the return code and mi355_last_error() text of
+// a list of calls with ONE fault each.  Nets are planned with unet_plan_dry and driven with made-up pointers, as tools/resolve_steps.hip does; nothing is launched and no
 // device is needed.  Every call the program makes must be refused before its first HIP call, in words that name the faulted argument: a case that
 // returns 0 or -3 (a HIP error), or that is refused for another reason, fails the program.  No call is made that the host checks would accept, and
 // the program must not be run where a device is present (it refuses to start there): an accepted call would launch on made-up addresses.
@@ -252,6 +252,50 @@ int report(const char* entry, const char* what, const char* expect, int rc) {
   return 1;
 }
 
+// Tiled sampling: the workspace rule (the sampler workspace at batch `chunk`, then the window buffers the net reads and writes, the blended
+// canvas and the repeated labels) and the refusals of the three entry points, one fault each.
+int tiled_cases(mi355_unet* net, bool cc, int B) {
+  const mi355_unet_config& c = net->cfg;
+  const int S = c.image_size;
+  const mi355_tile_plan good{2 * S, 3 * S - 5, S / 2, S / 3, MI355_TILE_TENT, 4};
+  int32_t cnt[3] = {0, 0, 0};
+  int bad = mi355_tile_count(S, &good, cnt) != 0;
+  const int64_t need = mi355_tiled_workspace_bytes(net, B, &good), plain = mi355_unet_workspace_bytes(net, good.chunk);
+  const int64_t rows = (int64_t)B * cnt[2], hw = (int64_t)S * S;
+  const int64_t parts = rows * (c.in_channels + c.out_channels) * hw * 4 + (int64_t)B * c.out_channels * good.canvas_h * good.canvas_w * 4;
+  printf("  bytes tiled_workspace %lld (windows %d x %d; plain at chunk %lld + window and canvas buffers %lld)\n", (long long)need, cnt[0], cnt[1],
+         (long long)plain, (long long)parts);
+  if (need < plain + parts) { printf("  ^ FAILED: the tiled workspace is smaller than its parts\n"); ++bad; }
+  struct Case { const char* what; const char* expect; mi355_tile_plan plan; int64_t ws_bytes; int cond_drift; };
+  const int64_t big = int64_t(1) << 50;
+  const Case cases[] = {
+      {"canvas_h below image_size", "canvas_h", {S - 1, 2 * S, 8, 8, 0, 4}, big, 0},
+      {"canvas_w below image_size", "canvas_w", {2 * S, S - 1, 8, 8, 0, 4}, big, 0},
+      {"stride_y 0", "stride_y", {2 * S, 2 * S, 0, 8, 0, 4}, big, 0},
+      {"stride_x above image_size", "stride_x", {2 * S, 2 * S, 8, S + 1, 0, 4}, big, 0},
+      {"unknown weight", "weight", {2 * S, 2 * S, 8, 8, 7, 4}, big, 0},
+      {"chunk 0", "chunk", {2 * S, 2 * S, 8, 8, 0, 0}, big, 0},
+      {"chunk above the largest batch", "chunk is above", {2 * S, 2 * S, 8, 8, 0, 1 << 30}, big, 0},
+      {"workspace one byte short", "workspace too small", good, need - 1, 0},
+  };
+  Args a(net, net, cc, B);
+  for (const Case& k : cases) {
+    bad += report("unet_forward_tiled", k.what, k.expect,
+                  mi355_unet_forward_tiled(net, a.x, 3, a.cond, a.cond_channels, 0.5f, a.labels, fake<float>(9), B, &k.plan, a.ws, k.ws_bytes, nullptr));
+    bad += report("cfm_euler_sample_tiled", k.what, k.expect,
+                  mi355_cfm_euler_sample_tiled(net, a.x, 3, a.cond, a.cond_channels, 0, a.labels, a.ts, a.n_t, nullptr, nullptr, B, a.ws, k.ws_bytes, nullptr,
+                                               &k.plan));
+    bad += report("ddpm_sample_tiled", k.what, k.expect,
+                  mi355_ddpm_sample_tiled(net, a.x, 3, a.cond, a.tbp, a.optp, nullptr, nullptr, 0, B, a.ws, k.ws_bytes, nullptr, &k.plan));
+    if (k.ws_bytes == big) bad += report("tiled_workspace_bytes", k.what, k.expect, (int)mi355_tiled_workspace_bytes(net, B, &k.plan));
+  }
+  bad += report("cfm_euler_sample_tiled", "cond_drift", "cond_drift",
+                mi355_cfm_euler_sample_tiled(net, a.x, 3, a.cond, a.cond_channels, 1, a.labels, a.ts, a.n_t, nullptr, nullptr, B, a.ws, big, nullptr, &good));
+  bad += report("cfm_euler_sample_tiled", "null plan", "plan is null",
+                mi355_cfm_euler_sample_tiled(net, a.x, 3, a.cond, a.cond_channels, 0, a.labels, a.ts, a.n_t, nullptr, nullptr, B, a.ws, big, nullptr, nullptr));
+  return bad;
+}
+
 int run_plan(const char* name, const mi355_unet_config& cfg, int B) {
   mi355_unet net, score;
   if (unet_plan_dry(cfg, &net) < 0 || unet_plan_dry(cfg, &score) < 0) { fprintf(stderr, "%s: plan failed: %s\n", name, mi355_last_error()); return 1; }
@@ -290,6 +334,7 @@ int run_plan(const char* name, const mi355_unet_config& cfg, int B) {
       bad += report(e.name, f.name, f.expect, e.call(a));
     }
   }
+  bad += tiled_cases(&net, cc, B);
   return bad;
 }
 
