@@ -381,6 +381,38 @@ int mi355_x0_shaped_step(int kind, float* x, const float* eps, const float* z, f
   if (guided) with_guide(p, w, w_dev, per);
   return predictor_step_launch(p, S(stream));
 }
+// The steps above on a network output wider than the state (a learned-variance net's [B, 2C, H, W]): eps of image b at eps + b * eps_stride.  kind 0..3
+// as mi355_x0_shaped_step; 4: the Langevin corrector (a, b, c = recip_sqrt_m1, dt, delta; never guided).
+int mi355_strided_step(int kind, float* x, const float* eps, int64_t eps_stride, const float* z, float* hist, int guided, float w, const float* w_dev,
+                       int64_t elems_per_image, float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed,
+                       uint64_t offset, int64_t n, void* stream) {
+  const int64_t per = elems_per_image;
+  MI355_REQUIRE(kind >= 0 && kind <= 4, -1, "strided_step: kind must be 0 (ancestral), 1 (DDIM), 2 (DDIM(eta)), 3 (DPM-Solver++) or 4 (corrector)");
+  MI355_REQUIRE(per > 0 && n % per == 0, -1, "strided_step: n must be whole images of elems_per_image elements");
+  MI355_REQUIRE(eps_stride >= per, -1, "strided_step: eps_stride must be >= elems_per_image");
+  if (kind == 4) {
+    MI355_REQUIRE(!guided, -1, "strided_step: the corrector has no guided form");
+    MI355_REQUIRE(n <= 0 || (x && eps), -1, "strided_step: null argument");
+    return corrector_step_launch(x, eps, z, c_recip, c_recipm1, a, b, c, use_philox, seed, offset, n, S(stream), per, eps_stride);
+  }
+  PredictorStep p = predictor(kind, x, eps, c_recip, c_recipm1, n);
+  p.hist = hist; p.a = a; p.b = b; p.c = c; p.sigma = sigma; p.per = per; p.eps_stride = eps_stride;
+  with_noise(p, z, use_philox, seed, offset);
+  if (guided) with_guide(p, w, w_dev, per);
+  return predictor_step_launch(p, S(stream));
+}
+// The ancestral step of a learned-variance net: out [batch (guided: 2 batch), 2C, H, W] is the network output, eps in channels [0, C), v in [C, 2C).
+int mi355_ddpm_lv_step(float* x, const float* out, const float* z, float w, const float* w_dev, int guided, int64_t elems_per_image, float c_recip,
+                       float c_recipm1, float coef1, float coef2, float min_log, float max_log, int use_philox, uint64_t seed, uint64_t offset, int batch,
+                       void* stream) {
+  MI355_REQUIRE(elems_per_image > 0, -1, "ddpm_lv_step: elems_per_image must be > 0");
+  MI355_REQUIRE(batch >= 0, -1, "ddpm_lv_step: batch must be >= 0");
+  PredictorStep p = predictor(STEP_ANCESTRAL_LV, x, out, c_recip, c_recipm1, (int64_t)batch * elems_per_image);
+  p.a = coef1; p.b = coef2; p.min_log = min_log; p.max_log = max_log; p.per = elems_per_image; p.eps_stride = 2 * elems_per_image;
+  with_noise(p, z, use_philox, seed, offset);
+  if (guided) with_guide(p, w, w_dev, elems_per_image);
+  return predictor_step_launch(p, S(stream));
+}
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream) {
   return rk_sqnorm_launch(a, sub, b, b2, atol, rtol, n, out, S(stream));

@@ -304,8 +304,9 @@ int resample_launch(int dtype, const void* in, void* out, int N, int Hs, int Ws,
 int euler_step_launch(float* x, const float* v, float dt, int64_t n, hipStream_t s);
 int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, float cb, float dt, const float* g, float g_s, const float* dW,
                           int use_philox, uint64_t seed, uint64_t offset, float* out, float w, int64_t n, hipStream_t s);
+// per, eps_stride (0, 0: contiguous): eps of image b of `per` elements is read at eps + b * eps_stride (PredictorStep::eps_stride)
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,
-                          float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
+                          float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, int64_t per = 0, int64_t eps_stride = 0);
 int renoise_step_launch(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 // The predictor steps of the DDPM loops: ONE descriptor, ONE launcher.  Every kind forms the data prediction x0_hat = clip(c_recip x - c_recipm1 eps)
 // and moves x from it:
@@ -313,12 +314,16 @@ int renoise_step_launch(float* x, const float* z, float a, float b, int use_phil
 //   STEP_DDIM       a = acp_prev:                       x <- sqrt(a) x0_hat + sqrt(1 - a) e2, e2 the eps that x0_hat stands for
 //   STEP_DDIM_ETA   a = acp_prev, sigma finite >= 0:    the same with sqrt(max(1 - a - sigma^2, 0)) and + sigma z (no noise given: no noise term)
 //   STEP_DPMPP      a, b, c = cx, c0, c1:               x <- a x + b x0_hat + c hist; hist <- x0_hat (hist: not read when c == 0, not written when null)
-// Noise (the two kinds with a z term): z injected, or Philox at (seed, offset), offset a multiple of 4, indexed by the element of the n-element state.
+//   STEP_ANCESTRAL_LV  a, b as STEP_ANCESTRAL; min_log, max_log: x <- a x0_hat + b x + exp(0.5 logvar) z, logvar = frac max_log + (1 - frac) min_log,
+//                   frac = (v + 1) / 2, v read at eps + per under eps_stride (>= 2 per): the learned variance range of improved DDPM; no shaping rows
+// eps_stride (0 = per, the contiguous read): element r of image b is read at eps[b * eps_stride + r] - the eps channels of a [B, 2C, H, W] network
+// output with per = C H W and eps_stride = 2 per; in the guided forms the unconditional half starts at B * eps_stride.  Not with shaping rows.
+// Noise (the kinds with a z term): z injected, or Philox at (seed, offset), offset a multiple of 4, indexed by the element of the n-element state.
 // guide.on: eps [2n] = conditional | unconditional evaluation, combined as eps_u + w (eps_c - eps_u) with w, or w_dev[image] over images of `per`
 // elements; x [2n] is the duplicated state (first half read, both halves written).  shape (null: the static clip to [-1, 1]): rows (f, s) per image of
 // `per` elements, filled by x0_shape_stats_launch: eps is scaled by f, x0_hat = clip(x0, -s, s) / s.  Refusals are prefixed ddpm_step, ddpm_cfg_step,
 // ddim_step, ... dpmpp_cfg_step after the kind and guide.on.
-enum { STEP_ANCESTRAL = 0, STEP_DDIM = 1, STEP_DDIM_ETA = 2, STEP_DPMPP = 3 };
+enum { STEP_ANCESTRAL = 0, STEP_DDIM = 1, STEP_DDIM_ETA = 2, STEP_DPMPP = 3, STEP_ANCESTRAL_LV = 4 };
 struct StepGuide { bool on = false; float w = 0.f; const float* w_dev = nullptr; };
 struct PredictorStep {
   int kind = STEP_ANCESTRAL;   // a STEP_* value (mi355_x0_shaped_step, which takes it from its caller, checks the range)
@@ -328,6 +333,8 @@ struct PredictorStep {
   int use_philox = 0; uint64_t seed = 0, offset = 0;
   StepGuide guide;
   int64_t per = 0; const float* shape = nullptr; int64_t n = 0;
+  int64_t eps_stride = 0;
+  float min_log = 0.f, max_log = 0.f;
 };
 int predictor_step_launch(const PredictorStep& p, hipStream_t s);
 // The statistics behind `shape`, one workgroup per image (and detail [B, 4] = sigma_c, sigma_g, s_raw, 0 when not null); check_x0_shaping holds the

@@ -43,9 +43,13 @@ struct TiledTail { float* in; float* out; float* vbar; int32_t* labels; };
 struct Layout { Scratch sc; CfgTail cfg; RkBufs rk; ReconTail rec; DdpmTail ddpm; void* feat_prev; TiledTail tile; uintptr_t end; };
 // What a sampler call keeps in its workspace.  guided: the network runs at 2 * batch and the guidance tail follows its workspace; stages > 0: the
 // Runge-Kutta buffers follow; recon: the reconstruction tail; hist, rows: the DDPM tail closes the layout.
+// lv (mi355_ddpm_lv_sample): a guided net with in_channels == out_channels is a learned-variance net (state and condition of out_channels / 2 channels each).
 struct LayoutSpec { int batch = 0; bool guided = false; int stages = 0; const ReconDims* recon = nullptr; bool hist = false; bool rows = false; size_t feat_bytes = 0;
-                    const TileSpec* tile = nullptr; };
-inline size_t cfg_cond_channels(const mi355_unet* net) { return (size_t)(net->cfg.in_channels > net->cfg.out_channels ? net->cfg.in_channels - net->cfg.out_channels : 0); }
+                    const TileSpec* tile = nullptr; bool lv = false; };
+inline size_t cfg_cond_channels(const mi355_unet* net, bool lv = false) {
+  if (lv && net->cfg.in_channels == net->cfg.out_channels) return (size_t)(net->cfg.in_channels / 2);
+  return (size_t)(net->cfg.in_channels > net->cfg.out_channels ? net->cfg.in_channels - net->cfg.out_channels : 0);
+}
 
 Layout layout(const mi355_unet* net, const LayoutSpec& sp, uintptr_t base) {
   const size_t hw = (size_t)net->cfg.image_size * net->cfg.image_size;
@@ -67,7 +71,7 @@ Layout layout(const mi355_unet* net, const LayoutSpec& sp, uintptr_t base) {
   if (guided || stages || recon || sp.hist || sp.rows || sp.feat_bytes || sp.tile) w.p = al256(w.p);
   if (guided) {
     l.cfg.x2 = w.take(state);
-    l.cfg.cond2 = w.take((size_t)B * cfg_cond_channels(net) * hw * 4);
+    l.cfg.cond2 = w.take((size_t)B * cfg_cond_channels(net, sp.lv) * hw * 4);
     l.cfg.labels2 = w.take<int32_t>(net->num_classes > 0 ? (size_t)B * 4 : 0);
   }
   for (int i = 0; i < stages; ++i) l.rk.k[i] = w.take(state);
@@ -472,6 +476,9 @@ struct LoopSched {
   // mi355_ddpm_shaped_sample with shaping on: every predictor step is preceded by the statistics launch that fills shape [batch][2], and reads it
   const mi355_x0_shaping* shaping = nullptr;
   float* shape = nullptr;              // behind the entry point's workspace
+  // mi355_ddpm_lv_sample with a learned variance range: the net writes [evalB, 2 * channels, H, W]; every consumer reads its eps channels under the image
+  // stride 2 * per, and the ancestral predictor of step i > 0 is STEP_ANCESTRAL_LV with max_log[i] (min_log: the tables' clipped posterior log-variance)
+  const float* lv_max_log = nullptr;
   // mi355_ddpm_sample_sched_cached: evaluation e of the loop (predictors and correctors, in loop order) is shallow where cache->full[e] == 0
   CacheRun* cache = nullptr;
 };
@@ -515,6 +522,7 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     PredictorStep p;
     p.x = x; p.eps = eps; p.c_recip = tb->sqrt_recip_alphas_cumprod[i]; p.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[i];
     p.seed = opt->seed; p.guide = a.guide; p.per = sper; p.shape = ls.shape; p.n = n;
+    p.eps_stride = ls.lv_max_log ? 2 * sper : 0;
     if (ls.shape && (rc = x0_shape_stats_launch(x, sc.v, a.guide, p.c_recip, p.c_recipm1, ls.shaping, ls.shape, nullptr, batch, sper, s))) return rc;
     if (mode == MI355_DDIM) {
       if (ls.ms_cx) {
@@ -529,7 +537,11 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     }
     p.kind = STEP_ANCESTRAL; p.a = tb->posterior_mean_coef1[i]; p.b = tb->posterior_mean_coef2[i];
     if (i > 0 && (rc = next_noise(p.z, p.use_philox, p.offset))) return rc;
-    p.sigma = expf(0.5f * tb->posterior_log_variance_clipped[i]);
+    if (ls.lv_max_log && i > 0) {   // step 0 draws no noise: the plain step, which never reads v
+      p.kind = STEP_ANCESTRAL_LV; p.min_log = tb->posterior_log_variance_clipped[i]; p.max_log = ls.lv_max_log[i];
+    } else {
+      p.sigma = expf(0.5f * tb->posterior_log_variance_clipped[i]);
+    }
     if ((rc = predictor_step_launch(p, s))) return rc;
     for (int c = 0; c < opt->n_corrector; ++c) {   // at batch B (a guided sampler's first half)
       run_corr.reuse_branch = ls.cache ? ls.cache->branch_of(eval) : 0;
@@ -542,7 +554,7 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
       if ((rc = next_noise(z2, ph2, off2))) return rc;
       const float dt = (opt->tmax - opt->tmin) / (float)Ns;
       if ((rc = corrector_step_launch(x, eps, z2, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i],
-                                      tb->recip_sqrt_m1_alphas_cumprod[i], dt, opt->delta, ph2, opt->seed, off2, n, s))) return rc;
+                                      tb->recip_sqrt_m1_alphas_cumprod[i], dt, opt->delta, ph2, opt->seed, off2, n, s, sper, p.eps_stride))) return rc;
     }
     if (a.mirror && opt->n_corrector > 0) MI355_CHECK_HIP(hipMemcpyAsync(a.mirror, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     return 0;
@@ -653,6 +665,10 @@ int ddpm_run(DdpmCall& c, mi355_unet* net, float* x, int channels, const float* 
   const DdpmGuidance* const g = c.guided;
   const int mode = opt->mode, batch = c.tile ? c.tile->B : c.spec.batch;
   const bool amortized = net->cfg.in_channels == 2 * channels;
+  const bool learned = c.ls.lv_max_log != nullptr;
+  const char* const width = learned ? "var->learned needs a net whose out_channels == 2 * channels (eps and the variance channels)"
+                                    : "eps model must output the state's channel count";
+  const int eps_channels = learned ? 2 * channels : channels;
   if (g) {
     const int32_t* const labels = g->labels; const int null_label = g->null_label;
     MI355_REQUIRE(mode == MI355_DDPM_AMORTIZED || mode == MI355_DDIM, -1,
@@ -660,10 +676,10 @@ int ddpm_run(DdpmCall& c, mi355_unet* net, float* x, int channels, const float* 
     MI355_REQUIRE(cond || labels, -1, f + "nothing to guide (neither a condition nor class labels)");
     MI355_REQUIRE(!labels || net->num_classes > 0, -1, f + "class labels given to a net built without num_classes");
     MI355_REQUIRE(!labels || (null_label >= 0 && null_label < net->num_classes), -1, f + "null_label must be a class index in [0, num_classes)");
-    MI355_REQUIRE(channels == net->cfg.out_channels, -2, f + "eps model must output the state's channel count");
+    MI355_REQUIRE(eps_channels == net->cfg.out_channels, -2, f + width);
     MI355_REQUIRE(net->cfg.in_channels == 2 * channels && cond, -2, f + "needs a 2C-input net and a condition");
   } else {
-    MI355_REQUIRE(channels == net->cfg.out_channels, -2, f + "eps model must output the state's channel count");
+    MI355_REQUIRE(eps_channels == net->cfg.out_channels, -2, f + width);
     MI355_REQUIRE(amortized || net->cfg.in_channels == channels, -2, f + "network in_channels must be C or 2C");
     MI355_REQUIRE(mode != MI355_DDPM_REPLACEMENT || (!amortized && cond), -2, f + "replacement needs an unconditional net and a condition");
     MI355_REQUIRE(mode != MI355_DDPM_AMORTIZED || (amortized && cond), -2, f + "amortized needs a 2C-input net and a condition");
@@ -1007,6 +1023,48 @@ int mi355_ddpm_shaped_sample(mi355_unet* net, float* x, int channels, const floa
   MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_shaped_sample: bad argument (net, x, workspace, batch)");
   c.spec.hist = msched != nullptr; c.spec.rows = true; c.count_step = true;
   if (shaping && (shaping->quantile > 0.f || shaping->rescale_phi > 0.f)) c.ls.shaping = shaping;   // off: the unshaped loop, bit for bit
+  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
+}
+
+// Learned-variance nets (improved DDPM's learned range) and caller-given evaluation times: one entry point over the six loops above.  var null, or
+// neither learned nor times: the loop chosen runs as its own entry point does, bit for bit.
+int64_t mi355_ddpm_lv_workspace_bytes(const mi355_unet* net, int batch, int guided, int multistep) {
+  if (!net || batch <= 0) { mi355_set_error("ddpm_lv_workspace_bytes: bad argument"); return -1; }
+  LayoutSpec sp = plain_spec(batch, guided != 0);
+  sp.hist = multistep != 0; sp.lv = true;
+  return layout_bytes(net, sp);
+}
+
+int mi355_ddpm_lv_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, int guided, float w,
+                         const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                         const mi355_multistep_schedule* msched, const mi355_ddpm_variance* var, const float* noise, int64_t n_noise_draws, int batch,
+                         void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(tb && opt, -1, "ddpm_lv_sample: tables or opt is null");
+  MI355_REQUIRE(!(sched && msched), -1, "ddpm_lv_sample: both sched and msched given (a run follows one schedule)");
+  const DdpmGuidance g{labels, null_label, w, w_dev};
+  DdpmCall c = ddpm_call("ddpm_lv_sample", batch, guided ? &g : nullptr);
+  const int K = tb->Ns;
+  if (var) {   // these refusals need no handle
+    MI355_REQUIRE(var->learned == 0 || var->learned == 1, -1, "ddpm_lv_sample: var->learned must be 0 (the tables' fixed variance) or 1 (the learned range)");
+    MI355_REQUIRE(!var->learned || var->max_log || K <= 0, -1, "ddpm_lv_sample: var->learned needs var->max_log (log(betas[k]) of the chain)");
+    for (int k = 0; var->learned && k < K; ++k) MI355_REQUIRE(std::isfinite(var->max_log[k]), -1, "ddpm_lv_sample: var->max_log must be finite");
+    for (int k = 0; var->times && k < K; ++k) MI355_REQUIRE(std::isfinite(var->times[k]), -1, "ddpm_lv_sample: var->times must be finite");
+  }
+  mi355_ddpm_schedule sd;
+  if (msched) {
+    MI355_REQUIRE(!noise, -1, "ddpm_lv_sample: noise given with msched (the multistep solver is deterministic and draws none)");
+    if (int rc = check_multistep(c.who, tb, opt, msched, c.spec.guided, sd, c.ls)) return rc;
+    c.th = sched_times(K, &sd);
+  } else if (sched) {
+    if (int rc = check_schedule(c.who, tb, opt, sched, c.spec.guided, c.ls)) return rc;
+    c.th = sched_times(K, sched);
+  } else {
+    c.th = ddpm_times(K);
+  }
+  MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_lv_sample: bad argument (net, x, workspace, batch)");
+  if (var && var->times) c.th.assign(var->times, var->times + (K > 0 ? K : 0));
+  if (var && var->learned && K > 0) c.ls.lv_max_log = var->max_log;
+  c.spec.hist = msched != nullptr; c.spec.lv = true; c.count_step = true;
   return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }
 

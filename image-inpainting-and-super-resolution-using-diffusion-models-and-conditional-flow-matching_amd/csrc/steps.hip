@@ -96,9 +96,27 @@ __device__ inline float cfg_mix(float ec, float eu, float w) {
   const float p = w * d;
   return eu + p;
 }
-__device__ inline void cfg_eps4(const float* eps, int64_t n, float w, const float* w_dev, int64_t per, int64_t i, int cnt, float (&ev)[4]) {
+// Four elements of a per-image strided tensor: element r of image b sits at p[b * stride + r] (the eps channels of a [B, 2C, H, W] network output:
+// per = C H W, stride = 2 per).  i indexes the dense [B][per] state; a group of four may straddle images when per % 4 != 0.
+__device__ inline void ld4_strided(const float* p, int64_t per, int64_t stride, int64_t i, int cnt, float (&v)[4]) {
+  int64_t img = i / per, r = i - img * per;
+  if (cnt == 4 && r + 4 <= per) { ld4(p + img * stride + r, 0, 4, v); return; }
+#pragma unroll
+  for (int l = 0; l < 4; ++l) v[l] = 0.f;
+  for (int l = 0; l < cnt; ++l) {
+    while (r >= per) { r -= per; ++img; }
+    v[l] = p[img * stride + r];
+    ++r;
+  }
+}
+// eps of image b at eps + b * stride; stride == per: the contiguous read.  The same rule reads v (the variance channels) at eps + per.
+__device__ inline void ld4_eps(const float* eps, int64_t per, int64_t stride, int64_t i, int cnt, float (&v)[4]) {
+  if (stride == per) ld4(eps, i, cnt, v);
+  else ld4_strided(eps, per, stride, i, cnt, v);
+}
+__device__ inline void cfg_eps4(const float* eps, int64_t nu, float w, const float* w_dev, int64_t per, int64_t stride, int64_t i, int cnt, float (&ev)[4]) {
   float ec[4], eu[4], wv[4] = {w, w, w, w};
-  ld4(eps, i, cnt, ec); ld4(eps + n, i, cnt, eu);
+  ld4_eps(eps, per, stride, i, cnt, ec); ld4_eps(eps + nu, per, stride, i, cnt, eu);
   if (w_dev) {   // a group of four may straddle images when per % 4 != 0
     int64_t img = i / per, r = i - img * per;
     for (int l = 0; l < cnt; ++l) {
@@ -114,12 +132,15 @@ __device__ inline void cfg_eps4(const float* eps, int64_t n, float w, const floa
 // Where a predictor step takes its eps from.  CFG false: eps [n].  CFG true, the classifier-free-guided forms: eps holds 2n values, the conditional
 // evaluation in [0, n) and the unconditional one in [n, 2n) (one network call at twice the batch), combined by cfg_eps4; x then holds the duplicated state
 // [2n]: the first half is read, the result goes to both halves.  w_dev (optional): one scale per image of `per` elements.
+// stride (== per: contiguous): the image stride of eps, so that the unconditional half starts nu = (n / per) * stride floats behind the conditional one.
 template <bool CFG> struct EpsSrc {
-  const float* eps; int64_t n; float w; const float* w_dev; int64_t per;
+  const float* eps; int64_t n; float w; const float* w_dev; int64_t per, stride, nu;
   __device__ inline void load(int64_t i, int cnt, float (&ev)[4]) const {
-    if constexpr (CFG) cfg_eps4(eps, n, w, w_dev, per, i, cnt, ev);
-    else ld4(eps, i, cnt, ev);
+    if constexpr (CFG) cfg_eps4(eps, nu, w, w_dev, per, stride, i, cnt, ev);
+    else ld4_eps(eps, per, stride, i, cnt, ev);
   }
+  // the learned-variance channels of the (conditional) evaluation: [C, 2C) of each image, at eps + per under the same stride
+  __device__ inline void load_v(int64_t i, int cnt, float (&vv)[4]) const { ld4_strided(eps + per, per, stride, i, cnt, vv); }
   __device__ inline void store(float* x, int64_t i, int cnt, const float (&v)[4]) const {
     st4(x, i, cnt, v);
     if constexpr (CFG) st4(x + n, i, cnt, v);
@@ -149,12 +170,13 @@ template <bool SH> struct X0Rows {
   }
 };
 // run f(EpsSrc<CFG>, X0Rows<SH>) for the form predictor_step_launch was asked for
-template <typename F> int step_form(bool cfg, const float* eps, int64_t n, float w, const float* w_dev, int64_t per, const float* shape, F&& f) {
+template <typename F> int step_form(bool cfg, const float* eps, int64_t n, float w, const float* w_dev, int64_t per, int64_t stride, const float* shape, F&& f) {
+  const int64_t nu = stride == per ? n : n / per * stride;
   if (cfg) {
-    const EpsSrc<true> e{eps, n, w, w_dev, per};
+    const EpsSrc<true> e{eps, n, w, w_dev, per, stride, nu};
     return shape ? f(e, X0Rows<true>{shape, per}) : f(e, X0Rows<false>{nullptr, 0});
   }
-  const EpsSrc<false> e{eps, n, 0.f, nullptr, 0};
+  const EpsSrc<false> e{eps, n, 0.f, nullptr, per, stride, nu};
   return shape ? f(e, X0Rows<true>{shape, per}) : f(e, X0Rows<false>{nullptr, 0});
 }
 }  // namespace
@@ -230,14 +252,42 @@ int ddpm_step_form(E es, R rows, float* x, const float* z, float c_recip, float 
 }
 }  // namespace
 
+// The ancestral step of a learned-variance net (Nichol & Dhariwal 2021, eq. 15): the network's second half v interpolates the log-variance between
+// max_log = log(beta) and min_log = the clipped posterior log-variance; v is not clamped.  Every operation rounded (no contraction: this file).
+namespace {
+template <class E>
+int ddpm_lv_step_form(E es, float* x, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float min_log, float max_log,
+                      int use_philox, uint64_t seed, uint64_t off4, int64_t n, hipStream_t s) {
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
+    float xv[4], ev[4], vv[4], zz[4];
+    ld4(x, i, cnt, xv);
+    es.load(i, cnt, ev);
+    es.load_v(i, cnt, vv);
+    noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float frac = (vv[j] + 1.f) * 0.5f;
+      const float logvar = frac * max_log + (1.f - frac) * min_log;
+      const float x0 = clip_nan(x0_pre(c_recip, c_recipm1, xv[j], ev[j]), -1.f, 1.f);
+      const float mean = coef1 * x0 + coef2 * xv[j];
+      xv[j] = mean + expf(0.5f * logvar) * zz[j];
+    }
+    es.store(x, i, cnt, xv);
+  });
+}
+}  // namespace
+
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,
-                          float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s) {
+                          float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, int64_t per, int64_t eps_stride) {
   MI355_REQUIRE(offset % 4 == 0, -1, "corrector_step: the Philox offset must be a multiple of 4");
+  const int64_t stride = eps_stride ? eps_stride : per;
+  MI355_REQUIRE(stride == per || (per > 0 && n % per == 0 && stride > per), -1,
+                "corrector_step: an eps stride needs n to be whole images of elems_per_image elements and eps_stride >= elems_per_image");
   const uint64_t off4 = offset / 4;
   const float kd = 0.5f * dt * delta, kn = sqrtf(dt * delta);
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
     float xv[4], ev[4], zz[4];
-    ld4(x, i, cnt, xv); ld4(eps, i, cnt, ev);
+    ld4(x, i, cnt, xv); ld4_eps(eps, per, stride, i, cnt, ev);
     noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -596,8 +646,8 @@ int dpmpp_step_form(E es, R rows, float* x, float* hist, float c_recip, float c_
 // The one launcher of the four predictor steps (PredictorStep, ops.h): every refusal once, prefixed by the name of the form asked for, then the host
 // side of the kind's coefficients, then the kernel template of the kind in the form step_form picks.
 int predictor_step_launch(const PredictorStep& p, hipStream_t s) {
-  static const char* const names[4][2] = {
-      {"ddpm_step", "ddpm_cfg_step"}, {"ddim_step", "ddim_cfg_step"}, {"ddim_eta_step", "ddim_eta_cfg_step"}, {"dpmpp_step", "dpmpp_cfg_step"}};
+  static const char* const names[5][2] = {{"ddpm_step", "ddpm_cfg_step"}, {"ddim_step", "ddim_cfg_step"}, {"ddim_eta_step", "ddim_eta_cfg_step"},
+                                          {"dpmpp_step", "dpmpp_cfg_step"}, {"ddpm_lv_step", "ddpm_lv_cfg_step"}};
   const bool cfg = p.guide.on;
   const auto f = [&] { return std::string(names[p.kind][cfg]) + ": "; };   // built inside a refusal only: MI355_REQUIRE evaluates its message on failure
   float* const x = p.x; const float* const eps = p.eps; const float* const z = p.z; float* const hist = p.hist;
@@ -606,15 +656,31 @@ int predictor_step_launch(const PredictorStep& p, hipStream_t s) {
   const int use_philox = p.use_philox;
   const uint64_t seed = p.seed, offset = p.offset;
   const int64_t per = p.per, n = p.n;
-  const bool draws = p.kind == STEP_ANCESTRAL || p.kind == STEP_DDIM_ETA;   // the kinds with a noise term: the others never read the noise triple
+  const int64_t stride = p.eps_stride ? p.eps_stride : per;   // == per: the contiguous read
+  const bool draws = p.kind == STEP_ANCESTRAL || p.kind == STEP_DDIM_ETA || p.kind == STEP_ANCESTRAL_LV;   // the kinds with a noise term: the others never read the noise triple
   if (draws) MI355_REQUIRE(offset % 4 == 0, -1, f() + "the Philox offset must be a multiple of 4");
   MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, f() + "per-image scales need n to be whole images of elems_per_image elements");
   MI355_REQUIRE(n <= 0 || (x && eps), -1, f() + "null argument");
   if (p.kind == STEP_DDIM_ETA) MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, f() + "sigma must be finite and >= 0");
   if (p.kind == STEP_DPMPP) MI355_REQUIRE(c1 == 0.f || hist || n <= 0, -1, f() + "c1 != 0 needs hist (the previous step's data prediction)");
   MI355_REQUIRE(!shape || (per > 0 && n % per == 0), -1, f() + "per-image shaping rows need n to be whole images of elems_per_image elements");
+  MI355_REQUIRE(stride == per || (per > 0 && n % per == 0 && stride > per), -1,
+                f() + "an eps stride needs n to be whole images of elems_per_image elements and eps_stride >= elems_per_image");
+  MI355_REQUIRE(stride == per || !shape, -1, f() + "per-image shaping rows are not built for a strided eps");
+  if (p.kind == STEP_ANCESTRAL_LV) {
+    MI355_REQUIRE(!shape, -1, f() + "per-image shaping rows are not built for the learned-variance step");
+    MI355_REQUIRE(per > 0 && n % per == 0 && stride >= 2 * per, -1,
+                  f() + "the variance channels sit behind the eps channels of each image: eps_stride >= 2 * elems_per_image, n whole images");
+    MI355_REQUIRE(std::isfinite(p.min_log) && std::isfinite(p.max_log), -1, f() + "min_log and max_log must be finite");
+  }
   const uint64_t off4 = offset / 4;
-  return step_form(cfg, eps, n, p.guide.w, w_dev, per, shape, [=](auto es, auto rows) {
+  if (p.kind == STEP_ANCESTRAL_LV) {
+    const float min_log = p.min_log, max_log = p.max_log;
+    return step_form(cfg, eps, n, p.guide.w, w_dev, per, stride, nullptr, [=](auto es, auto) {
+      return ddpm_lv_step_form(es, x, z, c_recip, c_recipm1, p.a, p.b, min_log, max_log, use_philox, seed, off4, n, s);
+    });
+  }
+  return step_form(cfg, eps, n, p.guide.w, w_dev, per, stride, shape, [=](auto es, auto rows) {
     switch (p.kind) {
       case STEP_ANCESTRAL:
         return ddpm_step_form(es, rows, x, z, c_recip, c_recipm1, p.a, p.b, sigma, use_philox, seed, off4, n, s);

@@ -17,6 +17,9 @@ Build-defined extensions without a reference counterpart: get_ddim_sample_fn (DD
 orders 1 and 2: one evaluation and one step kernel per step, the previous step's data prediction kept on the device).  A chain made by
 DDPM.with_x0_shaping(...) has every sampler here end its predictor steps' data prediction per image (dynamic thresholding, guidance rescale) instead of
 with the static clip: the fast path in mi355_ddpm_shaped_sample, the generic one through x0_shape_stats and x0_shaped_step_; sample quality untested.
+A chain made by DDPM.with_learned_variance() samples a net with 2C outputs (eps | v, improved-DDPM's learned variance range): the fast path in
+mi355_ddpm_lv_sample, the generic one through ddpm_lv_step_ and strided_step_ on the net's output as it is; DDPM.from_betas chains (linear, cosine;
+a time_scale between step and network time) run there as well; sample quality untested.
 ReconstructionGuidance (sampling.py:136-206) differentiates the x0 model through the U-Net: the gradient is the HIP engine's
 vector-Jacobian product (`UNetEngine.vjp`, csrc/unet_backward.hip) of a differentiable plan of the same network, so it needs an
 `eps_model` made by `make_eps_model(network, ddpm)` around a `UNetModel`.
@@ -67,8 +70,11 @@ def use_ops(ops):
 
 
 def _sched_key(ddpm: DDPM):
-    """What identifies a sampling schedule: the training step count and the kept steps (None: all of them)."""
-    return (int(getattr(ddpm, "base_Ns", ddpm.Ns)), getattr(ddpm, "timesteps", None))
+    """What identifies a sampling schedule: the training step count, the kept steps (None: all of them) and, where it is not 1, the factor
+    between a step's position and the time the net sees (DDPM.from_betas)."""
+    key = (int(getattr(ddpm, "base_Ns", ddpm.Ns)), getattr(ddpm, "timesteps", None))
+    ts = float(getattr(ddpm, "time_scale", 1.0))
+    return key if ts == 1.0 else key + (ts,)
 
 
 def make_eps_model(network, ddpm: DDPM):
@@ -77,7 +83,7 @@ def make_eps_model(network, ddpm: DDPM):
     eps_model(xi, i) = network(xi, tau_i / base_Ns), for an int i and for the long [B] tensor the samplers pass."""
     steps = getattr(ddpm, "timesteps", None)
 
-    if steps is None:
+    if steps is None and float(getattr(ddpm, "time_scale", 1.0)) == 1.0:
         def eps_model(xi, i):
             return network(xi, 1.0 * i / ddpm.Ns)
     else:
@@ -168,11 +174,51 @@ def _shape_rows(xi, eps, i, T, shaping, w=None):
     return _ops.x0_shape_stats(xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), shaping, w=w)
 
 
-def _predictor(eps, xi, i, T, noise: _Noise, shape=None):
+def _learned_of(ddpm, *, tiling=None, feature_cache=None):
+    """ddpm.max_log() of a learned-variance chain (DDPM.with_learned_variance), None on a plain one; refused, by name, with what is not built
+    for such a chain."""
+    if not getattr(ddpm, "learned_variance", False):
+        return None
+    if getattr(ddpm, "x0_shaping", None) is not None:
+        raise NotImplementedError("per-image x0_shaping (DDPM.with_x0_shaping) is not built for a learned-variance chain (DDPM.with_learned_variance)")
+    if tiling is not None:
+        raise NotImplementedError("tiling is not built for a learned-variance chain (DDPM.with_learned_variance)")
+    if feature_cache is not None:
+        raise NotImplementedError("feature_cache is not built for a learned-variance chain (DDPM.with_learned_variance)")
+    return ddpm.max_log()
+
+
+def _check_width(out_channels, xi, max_log, host_loop=False):
+    """The channels the net writes against the chain: the state's C, or 2C (eps | v) on a learned-variance chain.  host_loop: a plain chain is
+    left to the step ops, which refuse an eps that has not the state's shape."""
+    if host_loop and max_log is None:
+        return
+    if out_channels != xi.shape[1] * (2 if max_log is not None else 1):
+        raise ValueError(f"the net writes {out_channels} channels for a state of {xi.shape[1]}: " +
+                         ("a learned-variance chain (DDPM.with_learned_variance) needs a net with twice the state's channels (eps | v)"
+                          if max_log is not None else "a net with twice the state's channels (learn_sigma) needs ddpm.with_learned_variance()"))
+
+
+def _check_engine_width(engine, xi, max_log):
+    """_check_width of a fused call: the engine's net against the chain, where learned variance is in play (a learned chain, or a 2C-output
+    net on a plain one); any other width is the library's own refusal."""
+    out_channels = getattr(engine, "out_channels", None)
+    if out_channels is not None and (max_log is not None or out_channels == 2 * xi.shape[1]):
+        _check_width(out_channels, xi, max_log)
+
+
+def _predictor(eps, xi, i, T, noise: _Noise, shape=None, max_log=None, w=None):
     """step() (sampling.py:59-67): x0_hat -> clip -> posterior mean -> + exp(0.5 logvar) z (z iff i > 0).  shape: the rows of _shape_rows
-    (per-image shaping in place of the clip)."""
+    (per-image shaping in place of the clip).  max_log (a learned-variance chain): eps is the net's 2C output, passed whole; with w, the
+    [2B] pair of a guided step and xi the duplicated state."""
     z, ph = noise.next() if i > 0 else (None, None)
     sigma = float((0.5 * T["posterior_log_variance_clipped"][i]).exp())  # fp32, like (0.5*logvar).exp()
+    if max_log is not None:
+        cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
+        c1, c2 = float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i])
+        if i > 0:
+            return _ops.ddpm_lv_step_(xi, eps, z, cr, crm1, c1, c2, float(T["posterior_log_variance_clipped"][i]), float(max_log[i]), ph, w=w)
+        return _ops.strided_step_("ddpm", xi, eps, cr, crm1, c1, c2, sigma=sigma, w=w)   # step 0 draws no noise and never reads v
     if shape is not None:
         _ops.x0_shaped_step_("ddpm", xi, eps, shape, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
                              float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i]), sigma=sigma, z=z, philox=ph)
@@ -182,10 +228,13 @@ def _predictor(eps, xi, i, T, noise: _Noise, shape=None):
     return xi
 
 
-def _corrector(eps, xi, i, T, ddpm, delta, noise: _Noise):
-    """corrector_step (sampling.py:113-121)."""
+def _corrector(eps, xi, i, T, ddpm, delta, noise: _Noise, max_log=None):
+    """corrector_step (sampling.py:113-121).  max_log (a learned-variance chain): eps is the net's 2C output, passed whole."""
     z, ph = noise.next()
     dt = (ddpm.tmax - ddpm.tmin) / ddpm.Ns
+    if max_log is not None:
+        return _ops.strided_step_("corrector", xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
+                                  float(T["recip_sqrt_m1_alphas_cumprod"][i]), dt, float(delta), z=z, philox=ph)
     _ops.corrector_step_(xi, eps, z, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
                          float(T["recip_sqrt_m1_alphas_cumprod"][i]), dt, float(delta), ph)
     return xi
@@ -211,6 +260,7 @@ def _walk_moves(Ns, walk):
 def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replacement=None, n_corrector=0, delta=0.1, walk=None):
     T = _tables(ddpm)
     shaping = _shaping_of(ddpm, False)
+    max_log = _learned_of(ddpm)
     xi = xT.detach().clone().float().contiguous()
     noise = _Noise(xi)
     for level, down in _walk_moves(ddpm.Ns, walk):
@@ -224,16 +274,23 @@ def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replac
             _ops.replace_mask_(xi, replacement["condition"], z, replacement["pad_value"], replacement["noise"],
                                float(T["sqrt_alphas_cumprod"][i]), float(T["sqrt_one_minus_alphas_cumprod"][i]), ph)
         eps = eps_model(_net_in(xi, cond_pred, amortized), _times(xi, i)).float().contiguous()
-        _predictor(eps, xi, i, T, noise, _shape_rows(xi, eps, i, T, shaping))
+        _check_width(eps.shape[1], xi, max_log, host_loop=True)
+        _predictor(eps, xi, i, T, noise, _shape_rows(xi, eps, i, T, shaping), max_log)
         for _ in range(n_corrector):
             eps = eps_model(_net_in(xi, cond_corr, amortized), _times(xi, i))
-            _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise)
+            _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise, max_log)
     return process_x0(xi)
 
 
-def _ddim_move(eps, xi, i, T, sigma, noise, shape=None):
-    """One DDIM step: sigma None = the deterministic kernel; else DDIM(eta) with sigma[i] and one draw iff i > 0.  shape: as in _predictor."""
+def _ddim_move(eps, xi, i, T, sigma, noise, shape=None, wide=False, w=None):
+    """One DDIM step: sigma None = the deterministic kernel; else DDIM(eta) with sigma[i] and one draw iff i > 0.  shape: as in _predictor.
+    wide (a learned-variance chain): eps is the net's 2C output, passed whole; with w, the [2B] pair of a guided step, xi the duplicated state."""
     cr, crm1, prev = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), float(T["alphas_cumprod_prev"][i])
+    if wide:
+        if sigma is None:
+            return _ops.strided_step_("ddim", xi, eps, cr, crm1, prev, w=w)
+        z, ph = noise.next() if i > 0 else (None, None)
+        return _ops.strided_step_("ddim_eta", xi, eps, cr, crm1, prev, sigma=float(sigma[i]), z=z, philox=ph, w=w)
     if sigma is None:
         return _ops.ddim_step_(xi, eps, cr, crm1, prev) if shape is None else _ops.x0_shaped_step_("ddim", xi, eps, shape, cr, crm1, prev)
     z, ph = noise.next() if i > 0 else (None, None)
@@ -247,12 +304,26 @@ def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corre
     correctors as in _run_generic (the net sees none_like).  With shaping the rows come from the pair (the rescale needs eps_c beside eps_g)."""
     T = _tables(ddpm)
     shaping = _shaping_of(ddpm, True)
+    max_log = _learned_of(ddpm)
     xi = xT.detach().clone().float().contiguous()
     noise = _Noise(xi)
+    B = xi.shape[0]
     for i in reversed(range(ddpm.Ns)):
         ec = eps_model(_net_in(xi, cond, True), _times(xi, i)).float()
         eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
         eps2 = torch.cat((ec, eu)).contiguous()
+        _check_width(eps2.shape[1], xi, max_log, host_loop=True)
+        if max_log is not None:   # the guided step kernels on the 2C pair itself (v from the conditional half), the state duplicated for them
+            x2 = torch.cat((xi, xi))
+            if ddim:
+                _ddim_move(eps2, x2, i, T, ddim_sigma, noise, wide=True, w=guidance_scale)
+            else:
+                _predictor(eps2, x2, i, T, noise, max_log=max_log, w=guidance_scale)
+            xi.copy_(x2[:B])
+            for _ in range(0 if ddim else n_corrector):
+                eps = eps_model(_net_in(xi, none, True), _times(xi, i))
+                _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise, max_log)
+            continue
         shape = _shape_rows(xi, eps2, i, T, shaping, w=guidance_scale)
         eps = _ops.cfg_combine(eps2, guidance_scale)
         if ddim:
@@ -351,13 +422,16 @@ def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_f
               seed=seed, guidance_scale=guidance_scale, **sched)
     shaping = _shaping_of(ddpm, guidance_scale is not None)
     feature_cache = _cache_of(ddpm, feature_cache)
+    tiling = _tiling_of(ddpm, tiling)
+    max_log = _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)
+    times = _custom_times(ddpm)
+    _check_engine_width(engine, xi, max_log)
     if feature_cache is not None:
         if guidance_scale is not None:
             _refuse_feature_cache(feature_cache, "the guided (classifier-free guidance) loops")
         if shaping is not None:
             _refuse_feature_cache(feature_cache, "the shaped loops (DDPM.with_x0_shaping)")
         kw.update(feature_cache.kwargs())
-    tiling = _tiling_of(ddpm, tiling)
     if tiling is not None:
         if guidance_scale is not None:
             _refuse_tiling(tiling, "the guided (classifier-free guidance) loops")
@@ -366,11 +440,23 @@ def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_f
         if feature_cache is not None:
             raise NotImplementedError("tiling together with feature_cache is not built")
         kw["tiling"] = tiling
-    if shaping is not None:   # the same loop with per-image shaping of x0_hat: mi355_ddpm_shaped_sample
+    if max_log is not None or times is not None:   # a learned variance range and / or the chain's own times: mi355_ddpm_lv_sample
+        for what, v in (("x0_shaping", shaping), ("tiling", tiling), ("feature_cache", feature_cache)):
+            if v is not None:
+                raise NotImplementedError(f"{what} is not built for a chain with a time_scale (DDPM.from_betas(..., time_scale=))")
+        engine.ddpm_learned(xi, _tables(ddpm), max_log, times=times, **kw)
+    elif shaping is not None:   # the same loop with per-image shaping of x0_hat: mi355_ddpm_shaped_sample
         engine.ddpm_shaped(xi, _tables(ddpm), shaping, **kw)
     else:
         engine.ddpm_sample(xi, _tables(ddpm), **kw)
     return xi
+
+
+def _custom_times(ddpm):
+    """The K times the net sees on a chain whose time_scale is not 1 (DDPM.from_betas), None where the fused loops' own rule holds."""
+    if float(getattr(ddpm, "time_scale", 1.0)) == 1.0:
+        return None
+    return torch.tensor([ddpm.time(k) for k in range(ddpm.Ns)], dtype=torch.float32)
 
 
 # Prior sampling ------------------------------------------------------------------------------------
@@ -387,6 +473,7 @@ def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Condition
     amortized = isinstance(conditioning, Amortized)
     feature_cache = _cache_of(ddpm, feature_cache)
     tiling = _tiling_of(ddpm, tiling)
+    _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)   # a learned-variance chain: its refusals, before the first sample
 
     @torch.no_grad()
     def sample(xT):
@@ -410,6 +497,7 @@ def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Con
     canvases; taken and refused by the same conditionings."""
     feature_cache = _cache_of(ddpm, feature_cache)
     tiling = _tiling_of(ddpm, tiling)
+    _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)   # a learned-variance chain: its refusals, before the first sample
     if isinstance(conditioning, ClassifierFreeGuidance):   # (an Amortized: before it)
         _refuse_feature_cache(feature_cache, "ClassifierFreeGuidance (the guided loops)")
         _refuse_tiling(tiling, "ClassifierFreeGuidance (the guided loops)")
@@ -483,6 +571,9 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
             "a UNetModel (an arbitrary callable has no backward pass on the HIP backend)")
     if conditioning.update_rule not in ("before", "after"):
         raise ValueError(f"unknown update_rule {conditioning.update_rule!r}")
+    if getattr(ddpm, "learned_variance", False):
+        raise NotImplementedError("ReconstructionGuidance is not built for a learned-variance chain (DDPM.with_learned_variance): the seed and "
+                                  "the backward pass take a net that writes the state's channels")
     if getattr(ddpm, "x0_shaping", None) is not None:
         raise NotImplementedError("ReconstructionGuidance differentiates the clipped x0_hat through the network: per-image x0 shaping "
                                   "(DDPM.with_x0_shaping) is not built into that gradient - pass the unshaped chain")
@@ -577,6 +668,8 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
     coefs = ddpm.dpm_solver_coefs(order)
     cx, c0, c1 = (c.tolist() for c in coefs)
     shaping = _shaping_of(ddpm, guidance_scale is not None)
+    max_log = _learned_of(ddpm)   # a learned-variance chain: the solver reads the eps channels of the 2C output
+    times = _custom_times(ddpm)
 
     @torch.no_grad()
     def sample(xT, condition=None):
@@ -592,6 +685,12 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
             sched = {}
             if getattr(ddpm, "timesteps", None) is not None:
                 sched = dict(timesteps=ddpm.timesteps, train_steps=int(ddpm.base_Ns))
+            if max_log is not None or times is not None:
+                if shaping is not None:
+                    raise NotImplementedError("x0_shaping is not built for a chain with a time_scale (DDPM.from_betas(..., time_scale=))")
+                _check_engine_width(engine, xi, max_log)
+                return engine.ddpm_learned(xi, T, max_log, times=times, mode=_lib.DDIM, coefs=coefs, cond=condition, none_value=nv,
+                                           guidance_scale=guidance_scale, **sched)
             if shaping is not None:
                 return engine.ddpm_shaped(xi, T, shaping, mode=_lib.DDIM, coefs=coefs, cond=condition, none_value=nv, guidance_scale=guidance_scale,
                                           **sched)
@@ -603,6 +702,17 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
         for i in reversed(range(ddpm.Ns)):
             eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i)).float().contiguous()
             shape = None
+            _check_width(eps.shape[1], xi, max_log, host_loop=True)
+            cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
+            if max_log is not None:   # the 2C output, passed whole (guided: the pair, on the duplicated state)
+                if none is None:
+                    _ops.strided_step_("dpmpp", xi, eps, cr, crm1, cx[i], c0[i], c1[i], hist=hist)
+                    continue
+                eps2 = torch.cat((eps, eps_model(_net_in(xi, none, True), _times(xi, i)).float())).contiguous()
+                x2 = torch.cat((xi, xi))
+                _ops.strided_step_("dpmpp", x2, eps2, cr, crm1, cx[i], c0[i], c1[i], hist=hist, w=guidance_scale)
+                xi.copy_(x2[:xi.shape[0]])
+                continue
             if none is not None:
                 eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
                 eps2 = torch.cat((eps, eu)).contiguous()
@@ -610,7 +720,6 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
                 eps = _ops.cfg_combine(eps2, guidance_scale)
             else:
                 shape = _shape_rows(xi, eps, i, T, shaping)
-            cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
             if shape is not None:
                 _ops.x0_shaped_step_("dpmpp", xi, eps, shape, cr, crm1, cx[i], c0[i], c1[i], hist=hist)
             else:
@@ -638,6 +747,7 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
         raise ValueError(f"eta must be finite and >= 0, got {eta!r}")
     sigma = ddpm.ddim_sigma(eta) if eta != 0.0 else None
     shaping = _shaping_of(ddpm, guidance_scale is not None)
+    max_log = _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)
 
     @torch.no_grad()
     def sample(xT, condition=None):
@@ -660,7 +770,8 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
         noise = _Noise(xi) if sigma is not None else None
         for i in reversed(range(ddpm.Ns)):
             eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i)).float().contiguous()
-            _ddim_move(eps, xi, i, T, sigma, noise, _shape_rows(xi, eps, i, T, shaping))
+            _check_width(eps.shape[1], xi, max_log, host_loop=True)
+            _ddim_move(eps, xi, i, T, sigma, noise, _shape_rows(xi, eps, i, T, shaping), wide=max_log is not None)
         return process_x0(xi)
 
     return sample

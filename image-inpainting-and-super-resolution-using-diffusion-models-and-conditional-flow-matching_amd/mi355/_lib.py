@@ -118,6 +118,11 @@ class X0ShapingC(C.Structure):
     _fields_ = [("quantile", C.c_float), ("max_threshold", C.c_float), ("rescale_phi", C.c_float)]
 
 
+class DDPMVarianceC(C.Structure):
+    """mi355_ddpm_variance (include/mi355_sampler.h): the learned variance range of a 2C-output net and / or the times the net sees."""
+    _fields_ = [("learned", C.c_int32), ("max_log", _FP), ("times", _FP)]
+
+
 class FeatureCacheC(C.Structure):
     """mi355_feature_cache (include/mi355_sampler.h): the branch and the full / shallow schedule of a sampler loop under feature reuse."""
     _fields_ = [("branch", C.c_int32), ("n_evals", C.c_int32), ("full", C.POINTER(C.c_uint8)), ("drift_out", _FP)]
@@ -251,6 +256,11 @@ SIGNATURES = {
                                       C.POINTER(MultistepScheduleC), C.POINTER(X0ShapingC), _VP, _I64, _I, _VP, _I64, _VP]),
     "mi355_x0_shape_stats": (_I, [_VP, _VP, _F, _VP, _I, _F, _F, C.POINTER(X0ShapingC), _VP, _VP, _I, _I64, _VP]),
     "mi355_x0_shaped_step": (_I, [_I, _VP, _VP, _VP, _VP, _I, _F, _VP, _I64, _F, _F, _F, _F, _F, _F, _I, _U64, _U64, _VP, _I64, _VP]),
+    "mi355_ddpm_lv_workspace_bytes": (_I64, [_VP, _I, _I, _I]),
+    "mi355_ddpm_lv_sample": (_I, [_VP, _VP, _I, _VP, _VP, _I, _I, _F, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), C.POINTER(DDPMScheduleC),
+                                  C.POINTER(MultistepScheduleC), C.POINTER(DDPMVarianceC), _VP, _I64, _I, _VP, _I64, _VP]),
+    "mi355_ddpm_lv_step": (_I, [_VP, _VP, _VP, _F, _VP, _I, _I64, _F, _F, _F, _F, _F, _F, _I, _U64, _U64, _I, _VP]),
+    "mi355_strided_step": (_I, [_I, _VP, _VP, _I64, _VP, _VP, _I, _F, _VP, _I64, _F, _F, _F, _F, _F, _F, _I, _U64, _U64, _I64, _VP]),
     "mi355_cfm_ab_workspace_bytes": (_I64, [_VP, _I, _I, _I, _I]),
     "mi355_cfm_ab_sample": (_I, [_VP, _VP, _I, _VP, _I, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_cfm_ab_cfg_sample": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _I, _F, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),

@@ -939,13 +939,51 @@ class UNetEngine:
         thresholding and guidance rescale.  shaping: DDPM.x0_shaping, a (quantile, max_threshold, rescale_phi) triple, or None (the unshaped
         loop, bit for bit).  coefs None: the arguments and the loops of ddpm_sample; coefs = (cx, c0, c1): those of ddpm_multistep (mode must
         be DDIM; no noise).  guidance_scale not None: the guided loops; a batch beyond cfg_batch() runs in slices (Philox: seed + slice)."""
+        sh = _lib.x0_shaping(shaping)
+        return self._ddpm_one_entry("ddpm_shaped", "mi355_ddpm_shaped_sample", "mi355_ddpm_shaped_workspace_bytes", sh, [], x, tables, mode=mode,
+                                    cond=cond, noise=noise, n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, start_fraction=start_fraction,
+                                    noise_condition=noise_condition, pad_value=pad_value, none_value=none_value, seed=seed,
+                                    guidance_scale=guidance_scale, y=y, null_label=null_label, timesteps=timesteps, train_steps=train_steps,
+                                    ddim_sigma=ddim_sigma, walk=walk, coefs=coefs)
+
+    def ddpm_learned(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], max_log=None, *, mode: int, times=None, cond: Optional[torch.Tensor] = None,
+                     noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0, noise_condition=True,
+                     pad_value=-2.0, none_value=-2.0, seed=0, guidance_scale=None, y: Optional[torch.Tensor] = None, null_label: Optional[int] = None,
+                     timesteps=None, train_steps=None, ddim_sigma=None, walk=None, coefs=None):
+        """In-place DDPM sampling of a learned-variance net (mi355_ddpm_lv_sample): the engine's net writes twice x's channels, eps then v, and
+        the ancestral step's variance is the learned range between tables["posterior_log_variance_clipped"] and max_log ([K] floats: log(betas) of
+        the chain, DDPM.max_log()).  max_log None: the fixed-variance loops on a net of x's channel count, bit for bit.  times ([K] floats, or
+        None: the loops' own rule): the time the net sees at step k (DDPM.time of a from_betas chain).  Everything else: the arguments and the
+        loops of ddpm_shaped (coefs: the multistep solver)."""
+        K = int(tables["alphas_cumprod_prev"].numel())
+        keep = []
+        var = _lib.DDPMVarianceC(0, None, None)
+        for name, v in (("max_log", max_log), ("times", times)):
+            if v is None:
+                continue
+            t = torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").contiguous()
+            if t.numel() != K:
+                raise ValueError(f"{name} must have one entry per row of the tables")
+            keep.append(t)
+            setattr(var, name, C.cast(t.data_ptr(), C.POINTER(C.c_float)))
+        var.learned = int(max_log is not None)
+        return self._ddpm_one_entry("ddpm_learned", "mi355_ddpm_lv_sample", "mi355_ddpm_lv_workspace_bytes", var if keep else None, keep, x, tables,
+                                    mode=mode, cond=cond, noise=noise, n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax,
+                                    start_fraction=start_fraction, noise_condition=noise_condition, pad_value=pad_value, none_value=none_value, seed=seed,
+                                    guidance_scale=guidance_scale, y=y, null_label=null_label, timesteps=timesteps, train_steps=train_steps,
+                                    ddim_sigma=ddim_sigma, walk=walk, coefs=coefs)
+
+    def _ddpm_one_entry(self, who, entry, ws_fn, extra, keep_extra, x, tables, *, mode, cond, noise, n_corrector, delta, tmin, tmax, start_fraction,
+                        noise_condition, pad_value, none_value, seed, guidance_scale, y, null_label, timesteps, train_steps, ddim_sigma, walk, coefs):
+        """The entry points that sit over the six DDPM loops (mi355_ddpm_shaped_sample, mi355_ddpm_lv_sample): one argument list, with the entry
+        point's own struct `extra` (or None) between the schedules and the noise."""
         B = x.shape[0]
         if cond is not None and cond.shape != x.shape:
             raise ValueError("condition must have the shape of x")
         if guidance_scale is None and y is not None:
-            raise NotImplementedError("ddpm_shaped takes class labels on the guided path only (guidance_scale=)")
-        sh = _lib.x0_shaping(shaping)
+            raise NotImplementedError(f"{who} takes class labels on the guided path only (guidance_scale=)")
         tb, keep = self._ddpm_tables(tables)
+        keep += keep_extra
         K = int(tb.Ns)
         sched = ms = None
         if coefs is not None:
@@ -974,12 +1012,12 @@ class UNetEngine:
         for xs, cn, nz, ls, wl, sd in self._guided_slices(x, cond, noise, lab, wt, int(seed), mb):
             opt = _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value,
                                     int(cond is None), sd)
-            ws, wsb = self._workspace_sized("mi355_ddpm_shaped_workspace_bytes", xs.shape[0], int(guided), int(ms is not None))
+            ws, wsb = self._workspace_sized(ws_fn, xs.shape[0], int(guided), int(ms is not None))
             a = self._ddpm_args(xs, cn, ls, nl, w, wl)
-            check(self.L.mi355_ddpm_shaped_sample(self.handle, *a[:5], int(guided), *a[5:], C.byref(tb), C.byref(opt),
-                                                  C.byref(sched[0]) if sched is not None else None, C.byref(ms) if ms is not None else None,
-                                                  C.byref(sh) if sh is not None else None, *self._noise_args(nz), xs.shape[0], ws, wsb, self._stream()),
-                  "mi355_ddpm_shaped_sample")
+            check(getattr(self.L, entry)(self.handle, *a[:5], int(guided), *a[5:], C.byref(tb), C.byref(opt),
+                                         C.byref(sched[0]) if sched is not None else None, C.byref(ms) if ms is not None else None,
+                                         C.byref(extra) if extra is not None else None, *self._noise_args(nz), xs.shape[0], ws, wsb, self._stream()),
+                  entry)
         del keep
         return x
 

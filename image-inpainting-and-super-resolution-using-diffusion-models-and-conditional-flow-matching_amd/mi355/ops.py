@@ -243,6 +243,54 @@ class Ops:
                                               int(philox is not None and z is None), seed, off, _opt(shape, "shape"), n, _stream()), "mi355_x0_shaped_step")
         return x
 
+    _STRIDED_KINDS = dict(_STEP_KINDS, corrector=4)
+
+    @staticmethod
+    def _wide_out(x, out, guided):
+        """Checks of a step on a network output wider than the state: x [B, C, ...] (guided: [2B, C, ...]), out [.., Cw >= C, ...], the same
+        leading and trailing sizes -> (B, elements per image of the state, image stride of out)."""
+        if guided and x.shape[0] % 2:
+            raise ValueError("x holds the state twice: an even leading size")
+        if out.dim() != x.dim() or x.dim() < 2 or out.shape[0] != x.shape[0] or out.shape[2:] != x.shape[2:] or out.shape[1] < x.shape[1]:
+            raise ValueError(f"the network output {tuple(out.shape)} must be x's shape {tuple(x.shape)} with at least as many channels")
+        B = x.shape[0] // 2 if guided else x.shape[0]
+        per = x[0].numel() if x.shape[0] else 1
+        return B, per, (out[0].numel() if out.shape[0] else per)
+
+    def strided_step_(self, kind, x, out, c_recip, c_recipm1, a, b=0.0, c=0.0, sigma=0.0, z=None, philox=None, hist=None, w=None):
+        """x0_shaped_step_'s unshaped steps, and the corrector (kind "corrector": a, b, c = rsm1, dt, delta; never guided), reading eps from the
+        first C channels of a wider network output out [B, Cw, ...] in place (mi355_strided_step): nothing is sliced or copied.  -> x"""
+        guided = w is not None
+        B, per, stride = self._wide_out(x, out, guided)
+        n = B * per
+        for t, name in ((z, "z"), (hist, "hist")):
+            if t is not None and t.numel() != n:
+                raise ValueError(f"{name} must have the B-image state's size")
+        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_strided_step(self._STRIDED_KINDS[kind], _req(x, "x"), _req(out, "out"), stride, _opt(z, "z"), _opt(hist, "hist"), int(guided),
+                                            wf, wp, per, float(c_recip), float(c_recipm1), float(a), float(b), float(c), float(sigma),
+                                            int(philox is not None and z is None), seed, off, n, _stream()), "mi355_strided_step")
+        return x
+
+    def ddpm_lv_step_(self, x, out, z, c_recip, c_recipm1, coef1, coef2, min_log, max_log, philox=None, w=None):
+        """The ancestral step of a learned-variance net in place (mi355_ddpm_lv_step): out [B, 2C, ...] is the network output, eps in channels
+        [0, C), v in [C, 2C); sigma = exp(0.5 (frac max_log + (1 - frac) min_log)), frac = (v + 1) / 2.  z / philox as in ddpm_step_.  w (a float
+        or a [B] tensor): the guided form, x [2B, C, ...] the duplicated state and out [2B, 2C, ...] = conditional | unconditional (v from the
+        conditional half); z stays [B, ...].  -> x"""
+        guided = w is not None
+        B, per, stride = self._wide_out(x, out, guided)
+        if stride != 2 * per:
+            raise ValueError(f"a learned-variance net writes twice the state's channels, got {tuple(out.shape)} for the state {tuple(x.shape)}")
+        if z is not None and z.numel() != B * per:
+            raise ValueError("z must have the B-image state's size")
+        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_ddpm_lv_step(_req(x, "x"), _req(out, "out"), _opt(z, "z"), wf, wp, int(guided), per, float(c_recip), float(c_recipm1),
+                                            float(coef1), float(coef2), float(min_log), float(max_log), int(philox is not None and z is None), seed, off,
+                                            B, _stream()), "mi355_ddpm_lv_step")
+        return x
+
     def renoise_(self, x, z, a, b, philox=None):
         """The forward move q(x_k | x_{k-1}) in place: x <- a x + b z (a = sqrt(alphas_k), b = sqrt(betas_k)); z / philox as in ddpm_step_."""
         zp = _opt(z, "z")

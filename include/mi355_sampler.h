@@ -60,7 +60,8 @@ extern "C" {
  * mi355_cfm_euler_sample_cached, mi355_ddpm_sample_sched_cached, mi355_feature_cache_workspace_bytes, mi355_feature_drift (new symbols and one new
  * struct only); then tiled sampling of canvases larger than the net's frame: mi355_tile_count, mi355_tile_origins, mi355_tiled_workspace_bytes,
  * mi355_tile_gather, mi355_tile_labels, mi355_tile_blend, mi355_unet_forward_tiled, mi355_cfm_euler_sample_tiled, mi355_ddpm_sample_tiled (new
- * symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * symbols and one new struct only); then learned-variance DDPM nets and caller-given evaluation times: mi355_ddpm_lv_workspace_bytes,
+ * mi355_ddpm_lv_sample, mi355_ddpm_lv_step, mi355_strided_step (new symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -633,6 +634,46 @@ int mi355_x0_shape_stats(const float* x, const float* eps, float w, const float*
 int mi355_x0_shaped_step(int kind, float* x, const float* eps, const float* z, float* hist, int guided, float w, const float* w_dev,
                          int64_t elems_per_image, float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed,
                          uint64_t offset, const float* shape, int64_t n, void* stream);
+
+/* Learned-variance DDPM nets (Nichol & Dhariwal 2021, improved DDPM, eq. 15; guided-diffusion's learn_sigma = True with the LEARNED_RANGE model type):
+ * the net writes [B, 2C, H, W], eps in channels [0, C) and v in [C, 2C).  The ancestral step of step i > 0 then is, per element, every operation
+ * rounded to fp32 and none contracted,
+ *   frac = (v + 1) * 0.5;  logvar = frac * max_log[i] + (1 - frac) * min_log[i];
+ *   x0 = clip(c_recip x - c_recipm1 eps, -1, 1);  x <- (coef1 x0 + coef2 x) + exp(0.5 logvar) * z,
+ * min_log = tables->posterior_log_variance_clipped, max_log = log(betas) of the chain the tables describe (the respaced chain's own betas).  v is not
+ * clamped.  Step 0 draws no noise and runs as the plain ancestral step, which never reads v.  Under guidance eps is the guided eps and v comes from
+ * the conditional half.  DDIM, DDIM(eta), DPM-Solver++ and the Langevin corrector read the eps channels only; the replacement paste, RePaint walks,
+ * the final clip, the draw numbering and the Philox offsets are those of the loops as they are.  No reference counterpart (the reference's nets have
+ * a fixed variance); sample quality is untested (no trained checkpoint is at hand); the arithmetic is tested against an fp64 restatement.
+ *
+ * mi355_ddpm_lv_sample: ONE entry point over the six DDPM loops (guided, sched, msched as in mi355_ddpm_shaped_sample).  var NULL, or learned == 0 and
+ * times NULL: the loop chosen, bit-identical to its own entry point.  times (or NULL): the time the net sees at step k, in place of k / Ns or
+ * steps[k] / train_steps (a chain whose net was trained on t in [0, 1000): times[k] = the integer step).  workspace: mi355_ddpm_lv_workspace_bytes(net,
+ * batch, guided, multistep), the amount of the loop chosen.  After the call mi355_unet_get_stats reports the launches of the last evaluation plus its
+ * step launch.  Errors beyond the loops' own, before any launch, each naming its argument: learned not 0 or 1; learned without max_log; a
+ * non-finite max_log or times entry; learned on a net whose out_channels != 2 * channels.
+ *
+ * mi355_ddpm_lv_step: the step as an op.  out [batch, 2C, H, W] (guided != 0: [2 * batch, ...] = conditional | unconditional, x [2 * batch * per] the
+ * duplicated state), elems_per_image = C * H * W; z [batch * per], or Philox at (seed, offset), as mi355_ddpm_step.
+ * mi355_strided_step: the predictor steps (kind 0..3 as mi355_x0_shaped_step, unshaped) and the Langevin corrector (kind 4: a, b, c = recip_sqrt_m1,
+ * dt, delta; guided must be 0) reading eps of image b at eps + b * eps_stride, eps_stride >= elems_per_image; under guidance the unconditional half
+ * starts at (n / elems_per_image) * eps_stride.  eps_stride == elems_per_image gives the bits of the contiguous ops. */
+typedef struct mi355_ddpm_variance {
+  int32_t learned;            /* 0: fixed (tables), 1: learned range, net out_channels == 2 * channels */
+  const float* max_log;       /* host float[K]: log(betas[k]) of the (respaced) chain; read iff learned */
+  const float* times;         /* host float[K] or NULL: the time the net sees at step k; NULL = the entry points' own rule */
+} mi355_ddpm_variance;
+int64_t mi355_ddpm_lv_workspace_bytes(const mi355_unet* net, int batch, int guided, int multistep);
+int mi355_ddpm_lv_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, int guided, float w,
+                         const float* w_dev, const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                         const mi355_multistep_schedule* msched, const mi355_ddpm_variance* var, const float* noise, int64_t n_noise_draws, int batch,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int mi355_ddpm_lv_step(float* x, const float* out, const float* z, float w, const float* w_dev, int guided, int64_t elems_per_image, float c_recip,
+                       float c_recipm1, float coef1, float coef2, float min_log, float max_log, int use_philox, uint64_t seed, uint64_t offset, int batch,
+                       void* stream);
+int mi355_strided_step(int kind, float* x, const float* eps, int64_t eps_stride, const float* z, float* hist, int guided, float w, const float* w_dev,
+                       int64_t elems_per_image, float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed,
+                       uint64_t offset, int64_t n, void* stream);
 
 /* Adams-Bashforth CFM samplers of order q = 2, 3, 4 (no reference counterpart): one evaluation per step from step q - 1 on,
  *   x_{k+1} = x_k + sum_{j<q} w_host[k * q + j] * v_{k-j},   v_k = model(t_k, x_k),
