@@ -413,6 +413,23 @@ int mi355_ddpm_lv_step(float* x, const float* out, const float* z, float w, cons
   if (guided) with_guide(p, w, w_dev, elems_per_image);
   return predictor_step_launch(p, S(stream));
 }
+// The variational bound's launches as ops (vlb.hip, steps.hip): the noising q(x_k | x_0), one step's terms, the prior term and the total.
+int mi355_q_sample(float* out, const float* x0, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
+  return q_sample_launch(out, x0, z, a, b, use_philox, seed, offset, n, S(stream));
+}
+int mi355_vlb_terms(const float* x0, const float* x_k, const float* out, int64_t out_stride, const float* z, int use_philox, uint64_t seed, uint64_t offset,
+                    float c_recip, float c_recipm1, float coef1, float coef2, float true_log, float model_log, float min_log, float max_log, int k_is_zero,
+                    int learned, int cdf, int clip_denoised, float* dst, int64_t dst_stride, int batch, int64_t elems_per_image, void* stream) {
+  VlbStep st;
+  st.c_recip = c_recip; st.c_recipm1 = c_recipm1; st.coef1 = coef1; st.coef2 = coef2;
+  st.true_log = true_log; st.model_log = model_log; st.min_log = min_log; st.max_log = max_log;
+  st.k_is_zero = k_is_zero; st.learned = learned; st.cdf = cdf; st.clip = clip_denoised;
+  return vlb_terms_launch(x0, x_k, out, out_stride, z, use_philox, seed, offset, st, dst, dst_stride, batch, elems_per_image, S(stream));
+}
+int mi355_vlb_prior(const float* x0, float sqrt_acp_last, float sqrt_one_minus_acp_last, const float* terms, int64_t terms_stride, int n_steps,
+                    float* summary, int batch, int64_t elems_per_image, void* stream) {
+  return vlb_prior_launch(x0, sqrt_acp_last, sqrt_one_minus_acp_last, terms, terms_stride, n_steps, summary, batch, elems_per_image, S(stream));
+}
 int mi355_rk_sqnorm(const float* a, const float* sub, const float* b, const float* b2, float atol, float rtol, int64_t n, double* out,
                     void* stream) {
   return rk_sqnorm_launch(a, sub, b, b2, atol, rtol, n, out, S(stream));

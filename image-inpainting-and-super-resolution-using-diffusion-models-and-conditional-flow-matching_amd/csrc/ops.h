@@ -345,6 +345,26 @@ int x0_shape_stats_launch(const float* x, const float* eps, const StepGuide& g, 
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb,
                         int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int clip_launch(float* x, float lo, float hi, int64_t n, hipStream_t s);
+// q(x_k | x_0) out of place (steps.hip): out = a x0 + b z, products and sum each rounded; noise as the ancestral step
+int q_sample_launch(float* out, const float* x0, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n,
+                    hipStream_t s);
+// The variational bound of a DDPM net (vlb.hip; the formulas: include/mi355_sampler.h, mi355_ddpm_vlb).  One step's three per-image numbers
+// dst[b * dst_stride + 0..2] = { vb, xstart_mse, mse } from x0, x_k [batch][per], the network output out (eps of image b at out + b * out_stride, v
+// behind it at + per, read iff learned) and the step's draw (z [batch][per], or Philox at (seed, offset) regenerated); fp64 per element, sums in a
+// fixed order, each number rounded to fp32 once.  k_is_zero: the discretised decoder (cdf 0: erfc, 1: the tanh approximation) in place of the KL.
+struct VlbStep {
+  float c_recip = 0.f, c_recipm1 = 0.f, coef1 = 0.f, coef2 = 0.f;   // the chain tables at step k
+  float true_log = 0.f;                                             // log-variance of q(x_{k-1} | x_k, x_0)
+  float model_log = 0.f;                                            // the model's, fixed (read iff !learned)
+  float min_log = 0.f, max_log = 0.f;                               // the learned range (read iff learned)
+  int k_is_zero = 0, learned = 0, cdf = 0, clip = 0;
+};
+int vlb_terms_launch(const float* x0, const float* xk, const float* out, int64_t out_stride, const float* z, int use_philox, uint64_t seed,
+                     uint64_t offset, const VlbStep& st, float* dst, int64_t dst_stride, int batch, int64_t per, hipStream_t s);
+// summary[b * 2] = prior_bpd of image b; with terms (vb of step k of image b at terms[b * terms_stride + 3 k], k < K) also summary[b * 2 + 1] =
+// the fp64 sum of the K vb values and the rounded prior, rounded once
+int vlb_prior_launch(const float* x0, float sa_last, float sb_last, const float* terms, int64_t terms_stride, int K, float* summary, int batch,
+                     int64_t per, hipStream_t s);
 int mse_per_sample_launch(const float* a, const float* b, float* out, int batch, int64_t per, hipStream_t s);
 // out[b] = ||cur_b - prev_b||^2 / ||prev_b||^2, then prev <- cur; cur, prev [batch][per] of the internal dtype's element type (steps.hip)
 int feature_drift_launch(int dtype, const void* cur, void* prev, int batch, int64_t per, float* out, hipStream_t s);

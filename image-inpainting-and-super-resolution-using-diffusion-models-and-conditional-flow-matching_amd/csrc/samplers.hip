@@ -1068,6 +1068,93 @@ int mi355_ddpm_lv_sample(mi355_unet* net, float* x, int channels, const float* c
   return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }
 
+// The variational bound of a DDPM net on data x0 (the formulas: include/mi355_sampler.h): steps K-1 .. 0, each the noising launch into the workspace's
+// resident state, the evaluation, the terms launch (vlb.hip); then the prior term and the totals.  x0 is read by every step and never written.
+int64_t mi355_ddpm_vlb_workspace_bytes(const mi355_unet* net, int batch) {
+  if (!net || batch <= 0) { mi355_set_error("ddpm_vlb_workspace_bytes: bad argument"); return -1; }
+  return layout_bytes(net, plain_spec(batch));
+}
+
+int mi355_ddpm_vlb(mi355_unet* net, const float* x0, int channels, const float* cond, const int32_t* labels, const mi355_ddpm_tables* tb,
+                   const mi355_vlb_options* opt, const float* noise, int64_t n_noise_draws, float* out_terms, float* summary, int batch, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(tb, -1, "ddpm_vlb: tables is null");
+  MI355_REQUIRE(opt, -1, "ddpm_vlb: opt is null");
+  const int K = tb->Ns;
+  MI355_REQUIRE(K >= 2, -1, "ddpm_vlb: tables->Ns must be >= 2 (the bound has a decoder step and at least one KL step)");
+  MI355_REQUIRE(opt->learned == 0 || opt->learned == 1, -1, "ddpm_vlb: opt->learned must be 0 (the fixed model_log) or 1 (the learned range)");
+  MI355_REQUIRE(opt->cdf == 0 || opt->cdf == 1, -1, "ddpm_vlb: opt->cdf must be 0 (exact, erfc) or 1 (the tanh approximation)");
+  MI355_REQUIRE(opt->clip_denoised == 0 || opt->clip_denoised == 1, -1, "ddpm_vlb: opt->clip_denoised must be 0 or 1");
+  const bool learned = opt->learned != 0;
+  // every table the mode reads: present and finite (DDPM(Ns <= 20) has non-finite chain tables and is refused here)
+  const struct { const float* p; const char* name; bool read; } tabs[] = {
+      {opt->true_log, "opt->true_log", true}, {opt->model_log, "opt->model_log", !learned}, {opt->min_log, "opt->min_log", learned},
+      {opt->max_log, "opt->max_log", learned}, {tb->sqrt_recip_alphas_cumprod, "tables->sqrt_recip_alphas_cumprod", true},
+      {tb->sqrt_recipm1_alphas_cumprod, "tables->sqrt_recipm1_alphas_cumprod", true}, {tb->posterior_mean_coef1, "tables->posterior_mean_coef1", true},
+      {tb->posterior_mean_coef2, "tables->posterior_mean_coef2", true}, {tb->sqrt_alphas_cumprod, "tables->sqrt_alphas_cumprod", true},
+      {tb->sqrt_one_minus_alphas_cumprod, "tables->sqrt_one_minus_alphas_cumprod", true}};
+  for (const auto& t : tabs) {
+    if (!t.read) continue;
+    MI355_REQUIRE(t.p, -1, std::string("ddpm_vlb: ") + t.name + " is null");
+    for (int k = 0; k < K; ++k) MI355_REQUIRE(std::isfinite(t.p[k]), -1, std::string("ddpm_vlb: ") + t.name + " must be finite");
+  }
+  MI355_REQUIRE(tb->sqrt_one_minus_alphas_cumprod[K - 1] > 0.f, -1, "ddpm_vlb: tables->sqrt_one_minus_alphas_cumprod[K-1] must be > 0 (the prior term takes its log)");
+  for (int k = 0; opt->times && k < K; ++k) MI355_REQUIRE(std::isfinite(opt->times[k]), -1, "ddpm_vlb: opt->times must be finite");
+  MI355_REQUIRE(net, -1, "ddpm_vlb: net is null");
+  MI355_REQUIRE(x0, -1, "ddpm_vlb: x0 is null");
+  MI355_REQUIRE(out_terms, -1, "ddpm_vlb: out_terms is null");
+  MI355_REQUIRE(summary, -1, "ddpm_vlb: summary is null");
+  MI355_REQUIRE(workspace, -1, "ddpm_vlb: workspace is null");
+  MI355_REQUIRE(batch > 0 && channels > 0, -1, "ddpm_vlb: batch and channels must be > 0");
+  MI355_REQUIRE(!learned || net->cfg.out_channels == 2 * channels, -2,
+                "ddpm_vlb: opt->learned needs a net whose out_channels == 2 * channels (eps and the variance channels)");
+  MI355_REQUIRE(learned || net->cfg.out_channels == channels, -2,
+                "ddpm_vlb: a fixed variance (opt->learned == 0) needs a net whose out_channels == channels");
+  const bool amortized = net->cfg.in_channels == 2 * channels;
+  MI355_REQUIRE(amortized || net->cfg.in_channels == channels, -2, "ddpm_vlb: network in_channels must be channels or 2 * channels");
+  MI355_REQUIRE(!cond || amortized, -2, "ddpm_vlb: cond given to a net that takes no condition (in_channels == channels)");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, "ddpm_vlb: labels given to a net built without num_classes");
+  MI355_REQUIRE(!noise || n_noise_draws >= K, -2, "ddpm_vlb: injected noise exhausted (noise holds fewer than tables->Ns draws)");
+  Layout l;
+  if (int rc = carve(net, plain_spec(batch), workspace, workspace_bytes, l, "ddpm_vlb")) return rc;
+  const Scratch& sc = l.sc;
+  hipStream_t s = S(stream);
+  const int64_t hw = (int64_t)net->cfg.image_size * net->cfg.image_size;
+  const int64_t per = (int64_t)channels * hw, n = (int64_t)batch * per, n_al = (n + 3) / 4 * 4;
+  const std::vector<float> th = opt->times ? std::vector<float>(opt->times, opt->times + K) : ddpm_times(K);
+  EvalEmb emb;   // row k (block of num_classes rows with labels) = step k
+  if (int rc = emb.init(net, sc, th.data(), K, labels != nullptr, true, s)) return rc;
+  if (amortized && !cond) { if (int rc = fill_launch(sc.none, opt->none_value, n, s)) return rc; }
+  const float* const condp = amortized ? (cond ? cond : sc.none) : nullptr;
+  float* const xk = sc.xstate;   // [batch, out_channels, H, W] floats: room for the state's channels
+  UnetRun run = uniform_t_run();
+  run.labels = labels;
+  VlbStep st;
+  st.learned = opt->learned; st.cdf = opt->cdf; st.clip = opt->clip_denoised;
+  for (int k = K - 1; k >= 0; --k) {
+    const int64_t draw = K - 1 - k;
+    const float* const z = noise ? noise + (size_t)draw * n : nullptr;
+    const int philox = noise ? 0 : 1;
+    const uint64_t off = noise ? 0 : (uint64_t)draw * (uint64_t)n_al;
+    int rc;
+    if ((rc = q_sample_launch(xk, x0, z, tb->sqrt_alphas_cumprod[k], tb->sqrt_one_minus_alphas_cumprod[k], philox, opt->seed, off, n, s))) return rc;
+    if ((rc = emb.select(run, (size_t)k, batch, s))) return rc;
+    if ((rc = unet_forward(net, xk, channels, condp, channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
+    st.c_recip = tb->sqrt_recip_alphas_cumprod[k]; st.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[k];
+    st.coef1 = tb->posterior_mean_coef1[k]; st.coef2 = tb->posterior_mean_coef2[k];
+    st.true_log = opt->true_log[k];
+    if (learned) { st.min_log = opt->min_log[k]; st.max_log = opt->max_log[k]; }
+    else st.model_log = opt->model_log[k];
+    st.k_is_zero = k == 0;
+    if ((rc = vlb_terms_launch(x0, xk, sc.v, (int64_t)net->cfg.out_channels * hw, z, philox, opt->seed, off, st, out_terms + 3 * (size_t)k, 3 * (int64_t)K,
+                               batch, per, s))) return rc;
+  }
+  if (int rc = vlb_prior_launch(x0, tb->sqrt_alphas_cumprod[K - 1], tb->sqrt_one_minus_alphas_cumprod[K - 1], out_terms, 3 * (int64_t)K, K, summary, batch,
+                                per, s)) return rc;
+  net->last_launches += 2;   // the last evaluation with its noising and terms launches
+  return 0;
+}
+
 // Adams-Bashforth CFM samplers: the loop of mi355_cfm_rk_sample / mi355_cfm_cfg_sample with the tableau as the start method (cfm_rk_loop, AbPlan).
 namespace {
 int check_ab(const char* who, int order, const float* w_host, int n_t, int stages, const float* a_host, const float* b_host, const float* c_host) {

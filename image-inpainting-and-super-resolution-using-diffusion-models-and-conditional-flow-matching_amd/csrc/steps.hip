@@ -17,35 +17,9 @@
 // x0 = c_recip*x - c_recipm1*eps (c ~ 1e3 at high noise levels) tracks the reference bit-for-bit where possible.
 #pragma clang fp contract(off)
 
+#include "philox.h"
+
 namespace {
-
-struct Philox {
-  static constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-  __device__ static inline void round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)M0 * c[0], p1 = (uint64_t)M1 * c[2];
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c[0] = hi1 ^ c[1] ^ k0; c[1] = lo1; c[2] = hi0 ^ c[3] ^ k1; c[3] = lo0;
-  }
-  __device__ static inline void gen(uint64_t seed, uint64_t ctr, uint32_t (&out)[4]) {
-    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) { round(c, k0, k1); k0 += W0; k1 += W1; }
-    out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-  }
-};
-
-// 4 standard normals for counter `ctr` (elements 4*ctr .. 4*ctr+3 of the stream)
-__device__ inline void randn4(uint64_t seed, uint64_t ctr, float (&z)[4]) {
-  uint32_t r[4];
-  Philox::gen(seed, ctr, r);
-  const float k = 2.3283064365386963e-10f;  // 2^-32
-  const float u0 = ((float)r[0] + 0.5f) * k, u1 = ((float)r[1] + 0.5f) * k;
-  const float u2 = ((float)r[2] + 0.5f) * k, u3 = ((float)r[3] + 0.5f) * k;
-  const float ra = sqrtf(-2.0f * logf(fminf(fmaxf(u0, 1e-12f), 1.0f))), rb = sqrtf(-2.0f * logf(fminf(fmaxf(u2, 1e-12f), 1.0f)));
-  const float ta = 6.283185307179586f * u1, tb = 6.283185307179586f * u3;
-  z[0] = ra * cosf(ta); z[1] = ra * sinf(ta); z[2] = rb * cosf(tb); z[3] = rb * sinf(tb);
-}
 
 // Every kernel below handles 4 consecutive elements per thread (16-B accesses) with a scalar tail.
 template <typename F>
@@ -363,6 +337,24 @@ int renoise_step_launch(float* x, const float* z, float a, float b, int use_phil
 #pragma unroll
     for (int j = 0; j < 4; ++j) xv[j] = a * xv[j] + b * zz[j];
     st4(x, i, cnt, xv);
+  });
+}
+
+// The forward marginal q(x_k | x_0) out of place: out = a x0 + b z with a = sqrt_alphas_cumprod[k], b = sqrt_one_minus_alphas_cumprod[k], two rounded
+// products and one sum (the bits of lincomb_per_sample_launch on the same operands); x0 is left as it is.  Noise as the ancestral step.
+int q_sample_launch(float* out, const float* x0, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n,
+                    hipStream_t s) {
+  MI355_REQUIRE(offset % 4 == 0, -1, "q_sample: the Philox offset must be a multiple of 4");
+  MI355_REQUIRE(n <= 0 || (out && x0), -1, "q_sample: null argument");
+  MI355_REQUIRE(out != x0 || n <= 0, -1, "q_sample: out must not be x0 (renoise_step is the in-place move)");
+  const uint64_t off4 = offset / 4;
+  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
+    float xv[4], zz[4], o[4];
+    ld4(x0, i, cnt, xv);
+    noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = a * xv[j] + b * zz[j];
+    st4(out, i, cnt, o);
   });
 }
 

@@ -30,11 +30,13 @@ def to_img(x):
 
 
 def evaluate(cond_sample_fn, likelihood, batches, experiment_dir, num_batches=None, lpips_fn=None, fid=None, save_images=True,
-             noise_fn=torch.randn_like, metrics=("mse", "lpips")):
+             noise_fn=torch.randn_like, metrics=("mse", "lpips"), vlb_fn=None):
     """batches: iterable of image tensors [B,C,H,W] in [-1,1] already on the sampling device (or (images, labels) pairs).
-    metrics: which per-sample numbers to collect, any of "mse", "lpips", "psnr", "ssim" (reported in that order).
+    metrics: which per-sample numbers to collect, any of "mse", "lpips", "psnr", "ssim", "bpd" (reported in that order).
+    vlb_fn (image_diffusion.bound.get_vlb_fn; None: "bpd" stays empty): with "bpd" in metrics, the ground-truth batch's total_bpd - the
+    variational bound of the model on the data, which scores the model and not the sample - joins the per-sample numbers.
     Returns the `results` dict that is also written to `<experiment_dir>/results.json`."""
-    known = ("mse", "lpips", "psnr", "ssim")
+    known = ("mse", "lpips", "psnr", "ssim", "bpd")
     unknown = [m for m in metrics if m not in known]
     if unknown:
         raise ValueError(f"unknown metrics {unknown}: choose from {known}")
@@ -75,6 +77,8 @@ def evaluate(cond_sample_fn, likelihood, batches, experiment_dir, num_batches=No
             collected["mse"].append(default_ops.mse_per_sample(x0.float().contiguous(), batch))
         if lpips_fn is not None and "lpips" in collected:
             collected["lpips"].append(lpips_fn(x0, batch).reshape(-1).float())
+        if vlb_fn is not None and "bpd" in collected:
+            collected["bpd"].append(vlb_fn(batch).total_bpd.reshape(-1).float())
     results = {}
     for name, vals in collected.items():
         if vals:

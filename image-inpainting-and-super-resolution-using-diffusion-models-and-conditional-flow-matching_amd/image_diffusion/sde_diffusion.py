@@ -252,6 +252,33 @@ class DDPM(nn.Module):
         b = self._betas64 if self._betas64 is not None else self.betas.detach().to("cpu", torch.float64)
         return torch.log(b).to(torch.float32)
 
+    def vlb_log_variances(self, kind: str):
+        """BUILD-DEFINED EXTENSION (no reference counterpart): the log-variance tables of the variational bound (image_diffusion.bound,
+        mi355_ddpm_vlb) as CPU fp32 [Ns] tensors, evaluated in fp64 from this chain's own betas (before their rounding where the chain has them, as
+        max_log()) and rounded once.  With pv = betas (1 - acp_prev) / (1 - acp):
+            small[k] = log(pv[k]),    small[0] = log(pv[1])     the posterior's log-variance; entry 0 by the bound's convention (pv[0] = 0), not
+                                                                the samplers' log(1e-20) clip
+            large[k] = log(betas[k]), large[0] = log(pv[1])
+        kind "fixed_small": {"true_log": small, "model_log": small}; "fixed_large": {"true_log": small, "model_log": large}; "learned":
+        {"true_log": small, "min_log": small, "max_log": max_log()} (the range a learned-variance net interpolates in; min_log[0] is what makes
+        step 0 of such a net meaningful).  A respaced chain yields its own bound, from its own betas.  Ns < 2 raises ValueError."""
+        if kind not in ("learned", "fixed_small", "fixed_large"):
+            raise ValueError(f'kind must be "learned", "fixed_small" or "fixed_large", got {kind!r}')
+        if self.Ns < 2:
+            raise ValueError(f"the variational bound needs a chain of at least 2 steps, got Ns = {self.Ns}")
+        b = self._betas64 if self._betas64 is not None else self.betas.detach().to("cpu", torch.float64)
+        b = b.detach().to("cpu", torch.float64)
+        acp = torch.cumprod(1.0 - b, dim=0)
+        prev = torch.cat((torch.ones(1, dtype=torch.float64), acp[:-1]))
+        small = torch.log(b * (1.0 - prev) / (1.0 - acp))
+        small[0] = small[1]
+        large = torch.log(b)
+        large[0] = small[1]
+        small32, large32 = small.to(torch.float32), large.to(torch.float32)
+        if kind == "learned":
+            return {"true_log": small32, "min_log": small32.clone(), "max_log": self.max_log()}
+        return {"true_log": small32, "model_log": small32.clone() if kind == "fixed_small" else large32}
+
     def ddim_sigma(self, eta: float) -> torch.Tensor:
         """CPU fp32 [Ns]: eta * sqrt((1 - acp_prev) / (1 - acp)) * sqrt(1 - acp / acp_prev) of DDIM (Song et al. 2021, eq. 16), evaluated in fp64
         from the fp32 buffers and rounded once.  eta = 0: the deterministic DDIM; eta = 1: sigma^2 is the posterior variance."""

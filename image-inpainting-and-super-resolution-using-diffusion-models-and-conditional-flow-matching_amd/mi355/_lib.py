@@ -123,6 +123,12 @@ class DDPMVarianceC(C.Structure):
     _fields_ = [("learned", C.c_int32), ("max_log", _FP), ("times", _FP)]
 
 
+class VLBOptionsC(C.Structure):
+    """mi355_vlb_options (include/mi355_sampler.h): the variance mode, the CDF, the log-variance tables and the times of a variational-bound call."""
+    _fields_ = [("learned", C.c_int32), ("cdf", C.c_int32), ("clip_denoised", C.c_int32), ("true_log", _FP), ("model_log", _FP), ("min_log", _FP),
+                ("max_log", _FP), ("times", _FP), ("none_value", C.c_float), ("seed", C.c_uint64)]
+
+
 class FeatureCacheC(C.Structure):
     """mi355_feature_cache (include/mi355_sampler.h): the branch and the full / shallow schedule of a sampler loop under feature reuse."""
     _fields_ = [("branch", C.c_int32), ("n_evals", C.c_int32), ("full", C.POINTER(C.c_uint8)), ("drift_out", _FP)]
@@ -261,6 +267,11 @@ SIGNATURES = {
                                   C.POINTER(MultistepScheduleC), C.POINTER(DDPMVarianceC), _VP, _I64, _I, _VP, _I64, _VP]),
     "mi355_ddpm_lv_step": (_I, [_VP, _VP, _VP, _F, _VP, _I, _I64, _F, _F, _F, _F, _F, _F, _I, _U64, _U64, _I, _VP]),
     "mi355_strided_step": (_I, [_I, _VP, _VP, _I64, _VP, _VP, _I, _F, _VP, _I64, _F, _F, _F, _F, _F, _F, _I, _U64, _U64, _I64, _VP]),
+    "mi355_ddpm_vlb_workspace_bytes": (_I64, [_VP, _I]),
+    "mi355_ddpm_vlb": (_I, [_VP, _VP, _I, _VP, _VP, C.POINTER(DDPMTablesC), C.POINTER(VLBOptionsC), _VP, _I64, _VP, _VP, _I, _VP, _I64, _VP]),
+    "mi355_q_sample": (_I, [_VP, _VP, _VP, _F, _F, _I, _U64, _U64, _I64, _VP]),
+    "mi355_vlb_terms": (_I, [_VP, _VP, _VP, _I64, _VP, _I, _U64, _U64, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _VP, _I64, _I, _I64, _VP]),
+    "mi355_vlb_prior": (_I, [_VP, _F, _F, _VP, _I64, _I, _VP, _I, _I64, _VP]),
     "mi355_cfm_ab_workspace_bytes": (_I64, [_VP, _I, _I, _I, _I]),
     "mi355_cfm_ab_sample": (_I, [_VP, _VP, _I, _VP, _I, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_cfm_ab_cfg_sample": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _I, _F, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),

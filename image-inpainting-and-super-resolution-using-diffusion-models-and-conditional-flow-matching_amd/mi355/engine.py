@@ -1021,6 +1021,57 @@ class UNetEngine:
         del keep
         return x
 
+    def ddpm_vlb(self, x0: torch.Tensor, tables: Dict[str, torch.Tensor], logs: Dict[str, torch.Tensor], *, learned: bool, times=None,
+                 cond: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, seed=None, cdf="exact",
+                 clip_denoised=True, none_value=-2.0):
+        """The variational bound of the engine's net on data x0 [B, C, H, W] in [-1, 1] (mi355_ddpm_vlb): all K steps of the chain `tables`
+        describes in ONE library call per batch.  logs: the [K] log-variance tables of DDPM.vlb_log_variances - "true_log", and "model_log"
+        (fixed variance) or "min_log" and "max_log" (learned: the net writes twice x0's channels).  times ([K] floats, or None: k / K): the time
+        the net sees at step k.  cond: the condition of a 2C-input net (None: such a net sees none_value).  noise: [K, B, C, H, W] injected draws
+        (draw j belongs to step K-1-j), or None: device Philox at `seed`.  cdf: "exact" or "tanh".
+        -> (terms [B, K, 3] = vb, xstart_mse, mse per step; summary [B, 2] = prior_bpd, total_bpd).  A batch beyond max_batch() runs in slices
+        (Philox: seed + slice)."""
+        if x0.dim() != 4:
+            raise ValueError("x0 must be [B, C, H, W]")
+        if cond is not None and cond.shape != x0.shape:
+            raise ValueError("condition must have the shape of x0")
+        if cdf not in ("exact", "tanh"):
+            raise ValueError(f'cdf must be "exact" or "tanh", got {cdf!r}')
+        B = x0.shape[0]
+        tb, keep = self._ddpm_tables(tables)
+        K = int(tb.Ns)
+        opt = _lib.VLBOptionsC(int(bool(learned)), int(cdf == "tanh"), int(bool(clip_denoised)), None, None, None, None, None, float(none_value), 0)
+        need = ("true_log", "min_log", "max_log") if learned else ("true_log", "model_log")
+        for name, v in [(n, logs.get(n)) for n in need] + [("times", times)]:
+            if v is None:
+                if name == "times":
+                    continue
+                raise ValueError(f"logs[{name!r}] is needed ({'learned' if learned else 'fixed'} variance): DDPM.vlb_log_variances builds it")
+            t = torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").contiguous()
+            if t.numel() != K:
+                raise ValueError(f"{name} must have one entry per row of the tables")
+            keep.append(t)
+            setattr(opt, name, C.cast(t.data_ptr(), C.POINTER(C.c_float)))
+        if noise is not None and (noise.dim() != 5 or tuple(noise.shape[1:]) != tuple(x0.shape)):
+            raise ValueError(f"noise must be [draws, *x0.shape], got {tuple(noise.shape)}")
+        lab, _ = self._labels(y, B)
+        terms = torch.empty(B, K, 3, device=self.device, dtype=torch.float32)
+        summary = torch.empty(B, 2, device=self.device, dtype=torch.float32)
+        self._fwd_state = None
+        seed = 0 if seed is None else int(seed)
+        for i, (lo, hi, whole) in enumerate(_slices(B, self.max_batch())):
+            xs, cn, nz, ls = x0[lo:hi], _cut(cond, lo, hi), noise if whole or noise is None else noise[:, lo:hi].contiguous(), _cut(lab, lo, hi)
+            tm, sm = (terms, summary) if whole else (torch.empty(hi - lo, K, 3, device=self.device), torch.empty(hi - lo, 2, device=self.device))
+            opt.seed = (seed + i) % 2 ** 64
+            ws, wsb = self._workspace_sized("mi355_ddpm_vlb_workspace_bytes", hi - lo)
+            check(self.L.mi355_ddpm_vlb(self.handle, self._chk(xs, "x0"), xs.shape[1], self._chk(cn, "condition") if cn is not None else None,
+                                        C.c_void_p(ls.data_ptr()) if ls is not None else None, C.byref(tb), C.byref(opt), *self._noise_args(nz), self._chk(tm, "terms"),
+                                        self._chk(sm, "summary"), hi - lo, ws, wsb, self._stream()), "mi355_ddpm_vlb")
+            if not whole:
+                terms[lo:hi], summary[lo:hi] = tm, sm
+        del keep
+        return terms, summary
+
     def _ddpm_cfg_call(self, x, tables, mode, cond, lab, null_label, w, wt, noise, o, sched=None):
         """One mi355_ddpm_cfg_sample (sched: mi355_ddpm_cfg_sample_sched) call (a batch within cfg_batch())."""
         B = x.shape[0]

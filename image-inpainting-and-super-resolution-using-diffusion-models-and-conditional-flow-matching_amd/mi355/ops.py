@@ -291,6 +291,59 @@ class Ops:
                                             B, _stream()), "mi355_ddpm_lv_step")
         return x
 
+    def q_sample(self, x0, a, b, z=None, philox=None, out=None):
+        """The forward marginal q(x_k | x_0) out of place (mi355_q_sample): a x0 + b z with a = sqrt_alphas_cumprod[k], b =
+        sqrt_one_minus_alphas_cumprod[k], two rounded products and a sum; z / philox as in ddpm_step_.  x0 is left as it is.  -> out"""
+        if z is not None:
+            _same(x0, z, "x0", "z")
+        out = torch.empty_like(x0) if out is None else out
+        _same(x0, out, "x0", "out")
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_q_sample(_req(out, "out"), _req(x0, "x0"), _opt(z, "z"), float(a), float(b), int(philox is not None and z is None), seed,
+                                        off, x0.numel(), _stream()), "mi355_q_sample")
+        return out
+
+    def vlb_terms(self, x0, x_k, out, *, c_recip, c_recipm1, coef1, coef2, true_log, model_log=0.0, min_log=0.0, max_log=0.0, k_is_zero, learned,
+                  cdf="exact", clip_denoised=True, z=None, philox=None, dst=None):
+        """One step of the variational bound (mi355_vlb_terms): x0, x_k [B, C, ...], out [B, C or more, ...] the network output (eps in channels
+        [0, C); learned: v in [C, 2C), read in place), the step's draw z (or philox = (seed, offset): regenerated) -> float32 [B, 3] = vb (bits/dim:
+        the KL of step k > 0, the discretised decoder's NLL with k_is_zero), xstart_mse, mse.  cdf: "exact" (erfc) or "tanh" (guided-diffusion's
+        approximation).  dst: a [B, 3] view to write into (its row stride may be wider: a [B, K, 3] tensor's [:, k])."""
+        _same(x0, x_k, "x0", "x_k")
+        B, per, stride = self._wide_out(x0, out, False)
+        if learned and stride < 2 * per:
+            raise ValueError(f"a learned-variance net writes twice the state's channels, got {tuple(out.shape)} for the state {tuple(x0.shape)}")
+        if z is not None:
+            _same(x0, z, "x0", "z")
+        if cdf not in ("exact", "tanh"):
+            raise ValueError(f'cdf must be "exact" or "tanh", got {cdf!r}')
+        if dst is None:
+            dst = torch.empty(B, 3, device=x0.device, dtype=torch.float32)
+        if not dst.is_cuda or dst.dtype != torch.float32 or dst.shape != (B, 3) or (B and dst.stride(1) != 1):
+            raise ValueError("dst must be a float32 device view of shape [B, 3] with unit inner stride")
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_vlb_terms(_req(x0, "x0"), _req(x_k, "x_k"), _req(out, "out"), stride, _opt(z, "z"), int(philox is not None and z is None),
+                                         seed, off, float(c_recip), float(c_recipm1), float(coef1), float(coef2), float(true_log), float(model_log),
+                                         float(min_log), float(max_log), int(bool(k_is_zero)), int(bool(learned)), int(cdf == "tanh"),
+                                         int(bool(clip_denoised)), C.c_void_p(dst.data_ptr()), dst.stride(0) if B > 1 else 3, B, per, _stream()),
+              "mi355_vlb_terms")
+        return dst
+
+    def vlb_prior(self, x0, sqrt_acp_last, sqrt_one_minus_acp_last, terms=None):
+        """The prior term of the variational bound (mi355_vlb_prior) -> float32 [B, 2]: column 0 = KL(q(x_K | x0) || N(0, 1)) in bits/dim; with
+        terms ([B, K, 3], what vlb_terms wrote for every step) column 1 = the fp64 sum of terms[:, :, 0] and column 0, rounded once."""
+        B = x0.shape[0]
+        per = x0[0].numel() if B else 1
+        K = 0
+        if terms is not None:
+            if terms.dim() != 3 or terms.shape[0] != B or terms.shape[2] != 3:
+                raise ValueError(f"terms must be [B, K, 3], got {tuple(terms.shape)}")
+            K = terms.shape[1]
+        summary = torch.zeros(B, 2, device=x0.device, dtype=torch.float32)
+        check(_lib.lib().mi355_vlb_prior(_req(x0, "x0"), float(sqrt_acp_last), float(sqrt_one_minus_acp_last), _opt(terms, "terms"), 3 * K, K,
+                                         _req(summary, "summary"), B, per, _stream()), "mi355_vlb_prior")
+        return summary
+
     def renoise_(self, x, z, a, b, philox=None):
         """The forward move q(x_k | x_{k-1}) in place: x <- a x + b z (a = sqrt(alphas_k), b = sqrt(betas_k)); z / philox as in ddpm_step_."""
         zp = _opt(z, "z")

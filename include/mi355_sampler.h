@@ -61,7 +61,8 @@ extern "C" {
  * struct only); then tiled sampling of canvases larger than the net's frame: mi355_tile_count, mi355_tile_origins, mi355_tiled_workspace_bytes,
  * mi355_tile_gather, mi355_tile_labels, mi355_tile_blend, mi355_unet_forward_tiled, mi355_cfm_euler_sample_tiled, mi355_ddpm_sample_tiled (new
  * symbols and one new struct only); then learned-variance DDPM nets and caller-given evaluation times: mi355_ddpm_lv_workspace_bytes,
- * mi355_ddpm_lv_sample, mi355_ddpm_lv_step, mi355_strided_step (new symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * mi355_ddpm_lv_sample, mi355_ddpm_lv_step, mi355_strided_step (new symbols and one new struct only); then the variational bound of a DDPM net:
+ * mi355_ddpm_vlb_workspace_bytes, mi355_ddpm_vlb, mi355_q_sample, mi355_vlb_terms, mi355_vlb_prior (new symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -674,6 +675,72 @@ int mi355_ddpm_lv_step(float* x, const float* out, const float* z, float w, cons
 int mi355_strided_step(int kind, float* x, const float* eps, int64_t eps_stride, const float* z, float* hist, int guided, float w, const float* w_dev,
                        int64_t elems_per_image, float c_recip, float c_recipm1, float a, float b, float c, float sigma, int use_philox, uint64_t seed,
                        uint64_t offset, int64_t n, void* stream);
+
+/* The variational bound (NLL in bits/dim) of a DDPM net on data x0 [B, C, H, W] in [-1, 1] (Ho et al. 2020; Nichol & Dhariwal 2021; the quantities of
+ * guided-diffusion's calc_bpd_loop).  Forward only.  No reference counterpart (the reference trains with the simple loss and never evaluates the bound).
+ * For each step k = K-1 .. 0 of the chain the tables describe (K = tables->Ns >= 2):
+ *   noising   z_k = draw number K-1-k (noise[K-1-k], or Philox at offset (K-1-k) * n_al, n_al = B C H W rounded up to a multiple of 4, as the samplers
+ *             number their draws);  x_k = fl(fl(sa[k] x0) + fl(sb[k] z_k)) in fp32, sa = sqrt_alphas_cumprod, sb = sqrt_one_minus_alphas_cumprod;
+ *   network   out = net(x_k [| cond], times[k] or k / K, labels);  eps = out[:, :C], v = out[:, C:2C] (learned);
+ *   terms     in fp64 on the fp32 values widened, each output rounded to fp32 once, sums in a fixed order (no atomics: two runs give the same bits):
+ *     x0_hat = c_recip[k] x_k - c_recipm1[k] eps, clipped to [-1, 1] iff clip_denoised;  mean_p = coef1[k] x0_hat + coef2[k] x_k;
+ *     mean_q = coef1[k] x0 + coef2[k] x_k;  lq = true_log[k];  lp = model_log[k], or learned: frac max_log[k] + (1 - frac) min_log[k], frac = (v + 1) / 2
+ *     (v not clamped);
+ *     k > 0:  kl = 0.5 (-1 + lp - lq + exp(lq - lp) + (mean_q - mean_p)^2 exp(-lp));  vb[b, k] = mean(kl) / ln 2;
+ *     k == 0: the discretised Gaussian decoder on 8-bit bins: c = x0 - mean_p, s = exp(-0.5 lp), a+ = s (c + 1/255), a- = s (c - 1/255),
+ *             log p = log(max(P, 1e-12)) with P = Phi(a+) where x0 < -0.999, 1 - Phi(a-) where x0 > 0.999, Phi(a+) - Phi(a-) otherwise (the comparisons
+ *             on the widened fp32 x0);  vb[b, 0] = mean(-log p) / ln 2;
+ *     xstart_mse[b, k] = mean((x0_hat - x0)^2);  mse[b, k] = mean((eps - z_k)^2).
+ *   Phi: cdf 0 (exact) Phi(a) = 0.5 erfc(-a / sqrt 2), every probability taken where the values are at most 0.5: 1 - Phi(a-) as Phi(-a-), and for c > 0
+ *   the inner bin as Phi(-a-) - Phi(-a+), so that a far tail keeps its relative accuracy; cdf 1: guided-diffusion's approximation
+ *   0.5 (1 + tanh(sqrt(2 / pi) (a + 0.044715 a^3))) in the three expressions verbatim (for comparison with published numbers, which used it).
+ *   prior_bpd[b] = mean(0.5 (-1 - L + exp(L) + (sa[K-1] x0)^2)) / ln 2, L = 2 log(sb[K-1]);  total_bpd[b] = the fp64 sum of the rounded vb[b, :] and
+ *   the rounded prior_bpd[b], rounded once.
+ * The three log-variance tables are the caller's (DDPM.vlb_log_variances builds them in fp64 from the chain's betas): true_log and min_log = the
+ * posterior log-variance with entry 0 = entry 1 (the bound's convention, not the samplers' log(1e-20) clip), max_log = log(betas), model_log = true_log
+ * ("fixed_small") or log(betas) with entry 0 = true_log[1] ("fixed_large").
+ *
+ * mi355_ddpm_vlb: ONE call evaluates all K steps of one batch: per step the noising launch, the evaluation and the terms launch; the prior launch
+ * closes the call.  The embedding rows of the K times are built once per call, as the DDPM loops do.  x0 is never written.  out_terms [B][K][3] =
+ * { vb, xstart_mse, mse };  summary [B][2] = { prior_bpd, total_bpd }.  cond: the condition of a 2C-input net, or NULL (such a net then sees
+ * none_value, the Amortized prior).  workspace: mi355_ddpm_vlb_workspace_bytes(net, batch), 256-byte aligned.  After the call mi355_unet_get_stats
+ * reports the launches of the last evaluation plus its noising and terms launches.  Errors, all before any launch, each naming its argument (-1
+ * unless noted): tables or opt NULL; K < 2; learned, cdf or clip_denoised not 0 or 1; a table the mode reads NULL, or with a non-finite entry (the
+ * chain tables sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1 / 2, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod
+ * included: DDPM(Ns <= 20) is refused); a non-finite times entry; net, x0, out_terms, summary or workspace NULL; learned on a net whose out_channels
+ * != 2 * channels, or not learned on one whose out_channels != channels (-2); in_channels neither channels nor 2 * channels (-2); cond on a net
+ * that takes none (-2); labels on a net without classes; fewer than K injected draws (-2, "injected noise exhausted"); a short workspace (-2).
+ *
+ * mi355_q_sample: the noising as an op, out [n] = a x0 + b z (out != x0), z [n] or Philox at (seed, offset).
+ * mi355_vlb_terms: one step's terms as an op: x0, x_k [batch][elems_per_image]; eps of image b at out + b * out_stride, v behind it at
+ * + elems_per_image (read iff learned; out_stride >= 2 * elems_per_image then); z [batch][elems_per_image], or NULL with use_philox: the draw at
+ * (seed, offset) regenerated; dst[b * dst_stride + 0..2] = { vb, xstart_mse, mse }.  model_log is read iff !learned, min_log and max_log iff learned;
+ * a non-finite scalar that is read, a flag that is not 0 or 1 and an offset that is no multiple of 4 are refused.
+ * mi355_vlb_prior: summary[2 b] = prior_bpd; with terms (vb of step k of image b at terms[b * terms_stride + 3 k], k < n_steps) also summary[2 b + 1]
+ * = total_bpd.  It therefore runs after the last step's terms launch.
+ * bits/dim of a real checkpoint is unmeasured (no trained checkpoint is at hand); the arithmetic is tested against an fp64 restatement. */
+typedef struct mi355_vlb_options {
+  int32_t learned;          /* 0 fixed (model_log), 1 learned range (min_log, max_log; net out_channels == 2 * channels) */
+  int32_t cdf;              /* 0 exact (erfc), 1 guided-diffusion's tanh approximation */
+  int32_t clip_denoised;    /* clip x0_hat to [-1, 1] */
+  const float* true_log;    /* host float[K] */
+  const float* model_log;   /* host float[K], read iff !learned */
+  const float* min_log;     /* host float[K], read iff learned */
+  const float* max_log;     /* host float[K], read iff learned */
+  const float* times;       /* host float[K] or NULL, as mi355_ddpm_variance::times */
+  float none_value;         /* cond == NULL on a 2C-input net: feed this as the condition (the Amortized prior) */
+  uint64_t seed;            /* device Philox when noise == NULL */
+} mi355_vlb_options;
+int64_t mi355_ddpm_vlb_workspace_bytes(const mi355_unet* net, int batch);
+int mi355_ddpm_vlb(mi355_unet* net, const float* x0, int channels, const float* cond, const int32_t* labels, const mi355_ddpm_tables* tables,
+                   const mi355_vlb_options* opt, const float* noise, int64_t n_noise_draws, float* out_terms /* [B][K][3] */,
+                   float* summary /* [B][2] */, int batch, void* workspace, int64_t workspace_bytes, void* stream);
+int mi355_q_sample(float* out, const float* x0, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream);
+int mi355_vlb_terms(const float* x0, const float* x_k, const float* out, int64_t out_stride, const float* z, int use_philox, uint64_t seed, uint64_t offset,
+                    float c_recip, float c_recipm1, float coef1, float coef2, float true_log, float model_log, float min_log, float max_log, int k_is_zero,
+                    int learned, int cdf, int clip_denoised, float* dst, int64_t dst_stride, int batch, int64_t elems_per_image, void* stream);
+int mi355_vlb_prior(const float* x0, float sqrt_acp_last, float sqrt_one_minus_acp_last, const float* terms, int64_t terms_stride, int n_steps,
+                    float* summary, int batch, int64_t elems_per_image, void* stream);
 
 /* Adams-Bashforth CFM samplers of order q = 2, 3, 4 (no reference counterpart): one evaluation per step from step q - 1 on,
  *   x_{k+1} = x_k + sum_{j<q} w_host[k * q + j] * v_{k-j},   v_k = model(t_k, x_k),

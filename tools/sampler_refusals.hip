@@ -252,6 +252,63 @@ int report(const char* entry, const char* what, const char* expect, int rc) {
   return 1;
 }
 
+// The variational bound: its workspace is the plain sampler's, and every refusal of mi355_ddpm_vlb comes before the first launch, one fault each.
+int vlb_cases(mi355_unet* net, bool cc, int B) {
+  const int64_t need = mi355_ddpm_vlb_workspace_bytes(net, B);
+  printf("  bytes ddpm_vlb_workspace %lld\n", (long long)need);
+  int bad = need != mi355_unet_workspace_bytes(net, B);
+  if (bad) printf("  ^ FAILED: the bound's workspace is not the plain sampler's\n");
+  struct Case {
+    const char* what; const char* expect;
+    int learned = 0, cdf = 0, clip = 1, Ns = K, channels = 3; int64_t ws_bytes = int64_t(1) << 50, n_draws = 0;
+    bool no_true = false, no_model = false, no_min = false, bad_true = false, bad_chain = false, bad_times = false, cond = false, labels = false, noise = false,
+         no_x0 = false, no_terms = false, no_summary = false, no_ws = false, no_tb = false, no_opt = false, no_net = false;
+  };
+  const auto mk = [](const char* what, const char* expect) { Case c; c.what = what; c.expect = expect; return c; };
+  Case cases[24];
+  int n = 0;
+  { Case c = mk("tables null", "tables is null"); c.no_tb = true; cases[n++] = c; }
+  { Case c = mk("opt null", "opt is null"); c.no_opt = true; cases[n++] = c; }
+  { Case c = mk("one step", "Ns must be >= 2"); c.Ns = 1; cases[n++] = c; }
+  { Case c = mk("learned 2", "opt->learned"); c.learned = 2; cases[n++] = c; }
+  { Case c = mk("cdf 2", "opt->cdf"); c.cdf = 2; cases[n++] = c; }
+  { Case c = mk("clip_denoised -1", "opt->clip_denoised"); c.clip = -1; cases[n++] = c; }
+  { Case c = mk("true_log null", "opt->true_log is null"); c.no_true = true; cases[n++] = c; }
+  { Case c = mk("model_log null, fixed", "opt->model_log is null"); c.no_model = true; cases[n++] = c; }
+  { Case c = mk("min_log null, learned", "opt->min_log is null"); c.learned = 1; c.no_min = true; cases[n++] = c; }
+  { Case c = mk("true_log not finite", "opt->true_log must be finite"); c.bad_true = true; cases[n++] = c; }
+  { Case c = mk("a chain table not finite", "tables->posterior_mean_coef1 must be finite"); c.bad_chain = true; cases[n++] = c; }
+  { Case c = mk("times not finite", "opt->times must be finite"); c.bad_times = true; cases[n++] = c; }
+  { Case c = mk("net null", "net is null"); c.no_net = true; cases[n++] = c; }
+  { Case c = mk("x0 null", "x0 is null"); c.no_x0 = true; cases[n++] = c; }
+  { Case c = mk("out_terms null", "out_terms is null"); c.no_terms = true; cases[n++] = c; }
+  { Case c = mk("summary null", "summary is null"); c.no_summary = true; cases[n++] = c; }
+  { Case c = mk("workspace null", "workspace is null"); c.no_ws = true; cases[n++] = c; }
+  { Case c = mk("learned on a C-output net", "out_channels == 2 * channels"); c.learned = 1; cases[n++] = c; }
+  { Case c = mk("fixed with the wrong channel count", "out_channels == channels"); c.channels = 1; cases[n++] = c; }
+  if (!cc) { Case c = mk("cond on a net that takes none", "takes no condition"); c.cond = true; cases[n++] = c; }
+  if (!cc) { Case c = mk("labels on a net without classes", "without num_classes"); c.labels = true; cases[n++] = c; }
+  { Case c = mk("too few injected draws", "injected noise exhausted"); c.noise = true; c.n_draws = K - 1; cases[n++] = c; }
+  { Case c = mk("workspace one byte short", "workspace too small"); c.ws_bytes = need - 1; cases[n++] = c; }
+  for (int i = 0; i < n; ++i) {
+    const Case& c = cases[i];
+    float fine[K] = {-3.f, -2.5f, -2.f, -1.f}, nanful[K] = {-3.f, NAN, -2.f, -1.f}, ones[K] = {1.f, 1.f, 1.f, 1.f}, half[K] = {0.5f, 0.5f, 0.5f, 0.5f},
+          inff[K] = {1.f, 1.f, INFINITY, 1.f};
+    const mi355_ddpm_tables tb{c.Ns, ones, ones, c.bad_chain ? inff : ones, ones, fine, half, half, ones, ones};
+    mi355_vlb_options o{};
+    o.learned = c.learned; o.cdf = c.cdf; o.clip_denoised = c.clip;
+    o.true_log = c.no_true ? nullptr : (c.bad_true ? nanful : fine);
+    o.model_log = c.no_model ? nullptr : fine; o.min_log = c.no_min ? nullptr : fine; o.max_log = fine;
+    o.times = c.bad_times ? nanful : nullptr; o.none_value = -2.f; o.seed = 1;
+    const int rc = mi355_ddpm_vlb(c.no_net ? nullptr : net, c.no_x0 ? nullptr : fake<float>(3), c.channels, (c.cond || cc) ? fake<float>(5) : nullptr,
+                                  (c.labels || cc) ? fake<int32_t>(8) : nullptr, c.no_tb ? nullptr : &tb, c.no_opt ? nullptr : &o,
+                                  c.noise ? fake<float>(9) : nullptr, c.n_draws, c.no_terms ? nullptr : fake<float>(10), c.no_summary ? nullptr : fake<float>(11),
+                                  B, c.no_ws ? nullptr : fake<void>(2), c.ws_bytes, nullptr);
+    bad += report("mi355_ddpm_vlb", c.what, c.expect, rc);
+  }
+  return bad;
+}
+
 // Tiled sampling: the workspace rule (the sampler workspace at batch `chunk`, then the window buffers the net reads and writes, the blended
 // canvas and the repeated labels) and the refusals of the three entry points, one fault each.
 int tiled_cases(mi355_unet* net, bool cc, int B) {
@@ -335,6 +392,7 @@ int run_plan(const char* name, const mi355_unet_config& cfg, int B) {
     }
   }
   bad += tiled_cases(&net, cc, B);
+  bad += vlb_cases(&net, cc, B);
   return bad;
 }
 
