@@ -426,6 +426,49 @@ int mi355_vlb_terms(const float* x0, const float* x_k, const float* out, int64_t
   st.k_is_zero = k_is_zero; st.learned = learned; st.cdf = cdf; st.clip = clip_denoised;
   return vlb_terms_launch(x0, x_k, out, out_stride, z, use_philox, seed, offset, st, dst, dst_stride, batch, elems_per_image, S(stream));
 }
+// The steps, the statistics and the bound's terms of a net whose output is x0 or v (mi355_ddpm_prediction): the ops above with the prediction kind and
+// sa, sb = sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod of the step (read by kind 2 alone).
+// mi355_pred_step - kind 0..3: the predictor steps of mi355_x0_shaped_step; 4: the Langevin corrector (a, b, c = recip_sqrt_m1, dt, delta; never guided,
+// never shaped); 5: the learned-variance ancestral step (a, b = coef1, coef2; out_stride >= 2 * elems_per_image).  out_stride 0: contiguous.
+int mi355_pred_step(int kind, int pred_kind, float* x, const float* out, int64_t out_stride, const float* z, float* hist, int guided, float w,
+                    const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1, float sa, float sb, float a, float b, float c, float sigma,
+                    float min_log, float max_log, int use_philox, uint64_t seed, uint64_t offset, const float* shape, int64_t n, void* stream) {
+  const int64_t per = elems_per_image;
+  MI355_REQUIRE(kind >= 0 && kind <= 5, -1,
+                "pred_step: kind must be 0 (ancestral), 1 (DDIM), 2 (DDIM(eta)), 3 (DPM-Solver++), 4 (corrector) or 5 (learned-variance ancestral)");
+  MI355_REQUIRE(pred_kind >= PRED_EPS && pred_kind <= PRED_V, -1, "pred_step: pred_kind must be 0 (eps), 1 (x0) or 2 (v)");
+  MI355_REQUIRE(per > 0 && n % per == 0, -1, "pred_step: n must be whole images of elems_per_image elements");
+  MI355_REQUIRE(out_stride == 0 || out_stride >= per, -1, "pred_step: out_stride must be 0 (contiguous) or >= elems_per_image");
+  if (kind == 4) {
+    MI355_REQUIRE(!guided, -1, "pred_step: the corrector has no guided form");
+    MI355_REQUIRE(!shape, -1, "pred_step: the corrector keeps the static clip (shape must be NULL)");
+    MI355_REQUIRE(n <= 0 || (x && out), -1, "pred_step: null argument");
+    return corrector_step_launch(x, out, z, c_recip, c_recipm1, a, b, c, use_philox, seed, offset, n, S(stream), per, out_stride, pred_kind, sa, sb);
+  }
+  PredictorStep p = predictor(kind == 5 ? STEP_ANCESTRAL_LV : kind, x, out, c_recip, c_recipm1, n);
+  p.hist = hist; p.a = a; p.b = b; p.c = c; p.sigma = sigma; p.shape = shape; p.per = per; p.eps_stride = out_stride;
+  p.min_log = min_log; p.max_log = max_log; p.pred = pred_kind; p.sa = sa; p.sb = sb;
+  with_noise(p, z, use_philox, seed, offset);
+  if (guided) with_guide(p, w, w_dev, per);
+  return predictor_step_launch(p, S(stream));
+}
+int mi355_pred_shape_stats(int pred_kind, const float* x, const float* out, float w, const float* w_dev, int guided, float c_recip, float c_recipm1,
+                           float sa, float sb, const mi355_x0_shaping* shaping, float* shape, float* detail, int batch, int64_t elems_per_image,
+                           void* stream) {
+  return x0_shape_stats_launch(x, out, StepGuide{guided != 0, w, w_dev}, c_recip, c_recipm1, shaping, shape, detail, batch, elems_per_image, S(stream),
+                               pred_kind, sa, sb);
+}
+int mi355_vlb_terms_pred(const float* x0, const float* x_k, const float* out, int64_t out_stride, const float* z, int use_philox, uint64_t seed,
+                         uint64_t offset, float c_recip, float c_recipm1, float coef1, float coef2, float true_log, float model_log, float min_log,
+                         float max_log, int k_is_zero, int learned, int cdf, int clip_denoised, int pred_kind, float sa, float sb, float* dst,
+                         int64_t dst_stride, int batch, int64_t elems_per_image, void* stream) {
+  VlbStep st;
+  st.c_recip = c_recip; st.c_recipm1 = c_recipm1; st.coef1 = coef1; st.coef2 = coef2;
+  st.true_log = true_log; st.model_log = model_log; st.min_log = min_log; st.max_log = max_log;
+  st.k_is_zero = k_is_zero; st.learned = learned; st.cdf = cdf; st.clip = clip_denoised;
+  st.pred = pred_kind; st.sa = sa; st.sb = sb;
+  return vlb_terms_launch(x0, x_k, out, out_stride, z, use_philox, seed, offset, st, dst, dst_stride, batch, elems_per_image, S(stream));
+}
 int mi355_vlb_prior(const float* x0, float sqrt_acp_last, float sqrt_one_minus_acp_last, const float* terms, int64_t terms_stride, int n_steps,
                     float* summary, int batch, int64_t elems_per_image, void* stream) {
   return vlb_prior_launch(x0, sqrt_acp_last, sqrt_one_minus_acp_last, terms, terms_stride, n_steps, summary, batch, elems_per_image, S(stream));

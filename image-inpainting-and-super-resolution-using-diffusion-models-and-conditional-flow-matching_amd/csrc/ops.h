@@ -304,9 +304,14 @@ int resample_launch(int dtype, const void* in, void* out, int N, int Hs, int Ws,
 int euler_step_launch(float* x, const float* v, float dt, int64_t n, hipStream_t s);
 int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, float cb, float dt, const float* g, float g_s, const float* dW,
                           int use_philox, uint64_t seed, uint64_t offset, float* out, float w, int64_t n, hipStream_t s);
-// per, eps_stride (0, 0: contiguous): eps of image b of `per` elements is read at eps + b * eps_stride (PredictorStep::eps_stride)
+// What a DDPM net's output stands for (mi355_ddpm_prediction::kind): the noise eps, the data x0 itself, or v = sa eps - sb x0 (Salimans & Ho 2022).
+// Every consumer forms the unclipped data prediction x0_pre of the kind - eps: c_recip x - c_recipm1 out; x0: out (x is not read for it); v: sa x - sb out,
+// sa = sqrt_alphas_cumprod, sb = sqrt_one_minus_alphas_cumprod of the step - and goes on from it as it always did.
+enum { PRED_EPS = 0, PRED_X0 = 1, PRED_V = 2 };
+// per, eps_stride (0, 0: contiguous): eps of image b of `per` elements is read at eps + b * eps_stride (PredictorStep::eps_stride); pred, sa, sb: PRED_*
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,
-                          float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, int64_t per = 0, int64_t eps_stride = 0);
+                          float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, int64_t per = 0, int64_t eps_stride = 0,
+                          int pred = PRED_EPS, float sa = 0.f, float sb = 0.f);
 int renoise_step_launch(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 // The predictor steps of the DDPM loops: ONE descriptor, ONE launcher.  Every kind forms the data prediction x0_hat = clip(c_recip x - c_recipm1 eps)
 // and moves x from it:
@@ -335,13 +340,14 @@ struct PredictorStep {
   int64_t per = 0; const float* shape = nullptr; int64_t n = 0;
   int64_t eps_stride = 0;
   float min_log = 0.f, max_log = 0.f;
+  int pred = PRED_EPS; float sa = 0.f, sb = 0.f;   // what `eps` holds (PRED_*); sa, sb are read by PRED_V alone
 };
 int predictor_step_launch(const PredictorStep& p, hipStream_t s);
 // The statistics behind `shape`, one workgroup per image (and detail [B, 4] = sigma_c, sigma_g, s_raw, 0 when not null); check_x0_shaping holds the
 // refusals of a mi355_x0_shaping (null: none), each prefixed by `who`.
 int check_x0_shaping(const char* who, const mi355_x0_shaping* sh, int guided);
 int x0_shape_stats_launch(const float* x, const float* eps, const StepGuide& g, float c_recip, float c_recipm1, const mi355_x0_shaping* sh, float* shape,
-                          float* detail, int batch, int64_t per, hipStream_t s);
+                          float* detail, int batch, int64_t per, hipStream_t s, int pred = PRED_EPS, float sa = 0.f, float sb = 0.f);
 int replace_mask_launch(float* x, const float* cond, const float* z, float pad, int noisy, float sa, float sb,
                         int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s);
 int clip_launch(float* x, float lo, float hi, int64_t n, hipStream_t s);
@@ -358,6 +364,8 @@ struct VlbStep {
   float model_log = 0.f;                                            // the model's, fixed (read iff !learned)
   float min_log = 0.f, max_log = 0.f;                               // the learned range (read iff learned)
   int k_is_zero = 0, learned = 0, cdf = 0, clip = 0;
+  int pred = PRED_EPS; float sa = 0.f, sb = 0.f;                     // what `out` holds (PRED_*): x0_hat from x0_pre of the kind, mse against the kind's training
+                                                                    // target (z; x0; sa z - sb x0); sa, sb = sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod at k
 };
 int vlb_terms_launch(const float* x0, const float* xk, const float* out, int64_t out_stride, const float* z, int use_philox, uint64_t seed,
                      uint64_t offset, const VlbStep& st, float* dst, int64_t dst_stride, int batch, int64_t per, hipStream_t s);

@@ -481,6 +481,8 @@ struct LoopSched {
   const float* lv_max_log = nullptr;
   // mi355_ddpm_sample_sched_cached: evaluation e of the loop (predictors and correctors, in loop order) is shallow where cache->full[e] == 0
   CacheRun* cache = nullptr;
+  // mi355_ddpm_pred_sample: what the net's output stands for (PRED_*, ops.h); every step, the correctors and the statistics launch form x0_pre of the kind
+  int pred = PRED_EPS;
 };
 // emb: row i = the evaluation of step i (ddpm_times(Ns), or a schedule's tau_i / train_steps), selected whenever step i runs, revisits included.
 int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const DdpmLoop& a, const LoopSched& ls, int channels, const mi355_ddpm_tables* tb,
@@ -523,7 +525,10 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     p.x = x; p.eps = eps; p.c_recip = tb->sqrt_recip_alphas_cumprod[i]; p.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[i];
     p.seed = opt->seed; p.guide = a.guide; p.per = sper; p.shape = ls.shape; p.n = n;
     p.eps_stride = ls.lv_max_log ? 2 * sper : 0;
-    if (ls.shape && (rc = x0_shape_stats_launch(x, sc.v, a.guide, p.c_recip, p.c_recipm1, ls.shaping, ls.shape, nullptr, batch, sper, s))) return rc;
+    if (ls.pred == PRED_V) { p.sa = tb->sqrt_alphas_cumprod[i]; p.sb = tb->sqrt_one_minus_alphas_cumprod[i]; }
+    p.pred = ls.pred;
+    if (ls.shape && (rc = x0_shape_stats_launch(x, sc.v, a.guide, p.c_recip, p.c_recipm1, ls.shaping, ls.shape, nullptr, batch, sper, s, p.pred, p.sa, p.sb)))
+      return rc;
     if (mode == MI355_DDIM) {
       if (ls.ms_cx) {
         p.kind = STEP_DPMPP; p.hist = ls.hist; p.a = ls.ms_cx[i]; p.b = ls.ms_c0[i]; p.c = ls.ms_c1[i];
@@ -554,7 +559,8 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
       if ((rc = next_noise(z2, ph2, off2))) return rc;
       const float dt = (opt->tmax - opt->tmin) / (float)Ns;
       if ((rc = corrector_step_launch(x, eps, z2, tb->sqrt_recip_alphas_cumprod[i], tb->sqrt_recipm1_alphas_cumprod[i],
-                                      tb->recip_sqrt_m1_alphas_cumprod[i], dt, opt->delta, ph2, opt->seed, off2, n, s, sper, p.eps_stride))) return rc;
+                                      tb->recip_sqrt_m1_alphas_cumprod[i], dt, opt->delta, ph2, opt->seed, off2, n, s, sper, p.eps_stride, p.pred, p.sa, p.sb)))
+        return rc;
     }
     if (a.mirror && opt->n_corrector > 0) MI355_CHECK_HIP(hipMemcpyAsync(a.mirror, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     return 0;
@@ -1000,30 +1006,68 @@ int64_t mi355_ddpm_shaped_workspace_bytes(const mi355_unet* net, int batch, int 
   return layout_bytes(net, sp);
 }
 
+// The entry points that sit over the six loops - mi355_ddpm_shaped_sample (rows), mi355_ddpm_lv_sample (lv), mi355_ddpm_pred_sample (both) - are ONE body:
+// the refusals that need no handle in the order each entry point always had (its own struct's, then the schedule's), under its name, then ddpm_run.
+struct OverLoops {
+  const char* who; bool rows, lv;
+  const mi355_ddpm_variance* var; const mi355_x0_shaping* shaping; const mi355_ddpm_prediction* pred;
+};
+static int ddpm_over_loops(const OverLoops& o, mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, int guided,
+                           float w, const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                           const mi355_multistep_schedule* msched, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
+                           int64_t workspace_bytes, void* stream) {
+  const std::string f = std::string(o.who) + ": ";
+  const mi355_ddpm_variance* const var = o.var;
+  const mi355_x0_shaping* const shaping = o.shaping;
+  MI355_REQUIRE(tb && opt, -1, f + "tables or opt is null");
+  MI355_REQUIRE(!(sched && msched), -1, f + "both sched and msched given (a run follows one schedule)");
+  const DdpmGuidance g{labels, null_label, w, w_dev};
+  DdpmCall c = ddpm_call(o.who, batch, guided ? &g : nullptr);
+  const int K = tb->Ns;
+  if (o.pred) {   // these refusals need no handle
+    MI355_REQUIRE(o.pred->kind >= PRED_EPS && o.pred->kind <= PRED_V, -1, f + "pred->kind must be 0 (eps), 1 (x0) or 2 (v)");
+    if (o.pred->kind == PRED_V)
+      MI355_REQUIRE((tb->sqrt_alphas_cumprod && tb->sqrt_one_minus_alphas_cumprod) || K <= 0, -1,
+                    f + "pred->kind 2 (v) needs tables->sqrt_alphas_cumprod and tables->sqrt_one_minus_alphas_cumprod");
+    c.ls.pred = o.pred->kind;
+  }
+  if (var) {
+    MI355_REQUIRE(var->learned == 0 || var->learned == 1, -1, f + "var->learned must be 0 (the tables' fixed variance) or 1 (the learned range)");
+    MI355_REQUIRE(!var->learned || var->max_log || K <= 0, -1, f + "var->learned needs var->max_log (log(betas[k]) of the chain)");
+    for (int k = 0; var->learned && k < K; ++k) MI355_REQUIRE(std::isfinite(var->max_log[k]), -1, f + "var->max_log must be finite");
+    for (int k = 0; var->times && k < K; ++k) MI355_REQUIRE(std::isfinite(var->times[k]), -1, f + "var->times must be finite");
+  }
+  if (int rc = check_x0_shaping(o.who, shaping, guided)) return rc;
+  const bool shaped = shaping && (shaping->quantile > 0.f || shaping->rescale_phi > 0.f);
+  MI355_REQUIRE(!(shaped && var && var->learned), -1, f + "var->learned together with shaping: per-image shaping rows are not built for the learned-variance step");
+  const LoopSched keep = c.ls;   // check_schedule starts its LoopSched afresh
+  mi355_ddpm_schedule sd;
+  if (msched) {
+    MI355_REQUIRE(!noise, -1, f + "noise given with msched (the multistep solver is deterministic and draws none)");
+    if (int rc = check_multistep(c.who, tb, opt, msched, c.spec.guided, sd, c.ls)) return rc;
+    c.th = sched_times(K, &sd);
+  } else if (sched) {
+    if (int rc = check_schedule(c.who, tb, opt, sched, c.spec.guided, c.ls)) return rc;
+    c.th = sched_times(K, sched);
+  } else {
+    c.th = ddpm_times(K);
+  }
+  c.ls.pred = keep.pred;
+  MI355_REQUIRE(net && x && workspace && batch > 0, -1, f + "bad argument (net, x, workspace, batch)");
+  if (var && var->times) c.th.assign(var->times, var->times + (K > 0 ? K : 0));
+  if (var && var->learned && K > 0) c.ls.lv_max_log = var->max_log;
+  c.spec.hist = msched != nullptr; c.spec.rows = o.rows; c.spec.lv = o.lv; c.count_step = true;
+  if (shaped) c.ls.shaping = shaping;   // off: the unshaped loop, bit for bit
+  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
+}
+
 int mi355_ddpm_shaped_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, int guided, float w,
                              const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
                              const mi355_multistep_schedule* msched, const mi355_x0_shaping* shaping, const float* noise, int64_t n_noise_draws,
                              int batch, void* workspace, int64_t workspace_bytes, void* stream) {
-  MI355_REQUIRE(tb && opt, -1, "ddpm_shaped_sample: tables or opt is null");
-  MI355_REQUIRE(!(sched && msched), -1, "ddpm_shaped_sample: both sched and msched given (a run follows one schedule)");
-  const DdpmGuidance g{labels, null_label, w, w_dev};
-  DdpmCall c = ddpm_call("ddpm_shaped_sample", batch, guided ? &g : nullptr);
-  if (int rc = check_x0_shaping(c.who, shaping, guided)) return rc;   // these refusals need no handle
-  mi355_ddpm_schedule sd;
-  if (msched) {
-    MI355_REQUIRE(!noise, -1, "ddpm_shaped_sample: noise given with msched (the multistep solver is deterministic and draws none)");
-    if (int rc = check_multistep(c.who, tb, opt, msched, c.spec.guided, sd, c.ls)) return rc;
-    c.th = sched_times(tb->Ns, &sd);
-  } else if (sched) {
-    if (int rc = check_schedule(c.who, tb, opt, sched, c.spec.guided, c.ls)) return rc;
-    c.th = sched_times(tb->Ns, sched);
-  } else {
-    c.th = ddpm_times(tb->Ns);
-  }
-  MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_shaped_sample: bad argument (net, x, workspace, batch)");
-  c.spec.hist = msched != nullptr; c.spec.rows = true; c.count_step = true;
-  if (shaping && (shaping->quantile > 0.f || shaping->rescale_phi > 0.f)) c.ls.shaping = shaping;   // off: the unshaped loop, bit for bit
-  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
+  const OverLoops o{"ddpm_shaped_sample", true, false, nullptr, shaping, nullptr};
+  return ddpm_over_loops(o, net, x, channels, cond, labels, null_label, guided, w, w_dev, tb, opt, sched, msched, noise, n_noise_draws, batch, workspace,
+                         workspace_bytes, stream);
 }
 
 // Learned-variance nets (improved DDPM's learned range) and caller-given evaluation times: one entry point over the six loops above.  var null, or
@@ -1039,33 +1083,28 @@ int mi355_ddpm_lv_sample(mi355_unet* net, float* x, int channels, const float* c
                          const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
                          const mi355_multistep_schedule* msched, const mi355_ddpm_variance* var, const float* noise, int64_t n_noise_draws, int batch,
                          void* workspace, int64_t workspace_bytes, void* stream) {
-  MI355_REQUIRE(tb && opt, -1, "ddpm_lv_sample: tables or opt is null");
-  MI355_REQUIRE(!(sched && msched), -1, "ddpm_lv_sample: both sched and msched given (a run follows one schedule)");
-  const DdpmGuidance g{labels, null_label, w, w_dev};
-  DdpmCall c = ddpm_call("ddpm_lv_sample", batch, guided ? &g : nullptr);
-  const int K = tb->Ns;
-  if (var) {   // these refusals need no handle
-    MI355_REQUIRE(var->learned == 0 || var->learned == 1, -1, "ddpm_lv_sample: var->learned must be 0 (the tables' fixed variance) or 1 (the learned range)");
-    MI355_REQUIRE(!var->learned || var->max_log || K <= 0, -1, "ddpm_lv_sample: var->learned needs var->max_log (log(betas[k]) of the chain)");
-    for (int k = 0; var->learned && k < K; ++k) MI355_REQUIRE(std::isfinite(var->max_log[k]), -1, "ddpm_lv_sample: var->max_log must be finite");
-    for (int k = 0; var->times && k < K; ++k) MI355_REQUIRE(std::isfinite(var->times[k]), -1, "ddpm_lv_sample: var->times must be finite");
-  }
-  mi355_ddpm_schedule sd;
-  if (msched) {
-    MI355_REQUIRE(!noise, -1, "ddpm_lv_sample: noise given with msched (the multistep solver is deterministic and draws none)");
-    if (int rc = check_multistep(c.who, tb, opt, msched, c.spec.guided, sd, c.ls)) return rc;
-    c.th = sched_times(K, &sd);
-  } else if (sched) {
-    if (int rc = check_schedule(c.who, tb, opt, sched, c.spec.guided, c.ls)) return rc;
-    c.th = sched_times(K, sched);
-  } else {
-    c.th = ddpm_times(K);
-  }
-  MI355_REQUIRE(net && x && workspace && batch > 0, -1, "ddpm_lv_sample: bad argument (net, x, workspace, batch)");
-  if (var && var->times) c.th.assign(var->times, var->times + (K > 0 ? K : 0));
-  if (var && var->learned && K > 0) c.ls.lv_max_log = var->max_log;
-  c.spec.hist = msched != nullptr; c.spec.lv = true; c.count_step = true;
-  return ddpm_run(c, net, x, channels, cond, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
+  const OverLoops o{"ddpm_lv_sample", false, true, var, nullptr, nullptr};
+  return ddpm_over_loops(o, net, x, channels, cond, labels, null_label, guided, w, w_dev, tb, opt, sched, msched, noise, n_noise_draws, batch, workspace,
+                         workspace_bytes, stream);
+}
+
+// x0- and v-prediction nets (mi355_ddpm_prediction): the entry point above with the shaping rows and the prediction kind beside the variance.  pred null
+// or kind 0: the loop the other arguments choose, bit for bit.
+int64_t mi355_ddpm_pred_workspace_bytes(const mi355_unet* net, int batch, int guided, int multistep) {
+  if (!net || batch <= 0) { mi355_set_error("ddpm_pred_workspace_bytes: bad argument"); return -1; }
+  LayoutSpec sp = plain_spec(batch, guided != 0);
+  sp.hist = multistep != 0; sp.rows = true; sp.lv = true;
+  return layout_bytes(net, sp);
+}
+
+int mi355_ddpm_pred_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, int guided, float w,
+                           const float* w_dev, const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                           const mi355_multistep_schedule* msched, const mi355_ddpm_variance* var, const mi355_x0_shaping* shaping,
+                           const mi355_ddpm_prediction* pred, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
+                           int64_t workspace_bytes, void* stream) {
+  const OverLoops o{"ddpm_pred_sample", true, true, var, shaping, pred};
+  return ddpm_over_loops(o, net, x, channels, cond, labels, null_label, guided, w, w_dev, tb, opt, sched, msched, noise, n_noise_draws, batch, workspace,
+                         workspace_bytes, stream);
 }
 
 // The variational bound of a DDPM net on data x0 (the formulas: include/mi355_sampler.h): steps K-1 .. 0, each the noising launch into the workspace's
@@ -1075,9 +1114,10 @@ int64_t mi355_ddpm_vlb_workspace_bytes(const mi355_unet* net, int batch) {
   return layout_bytes(net, plain_spec(batch));
 }
 
-int mi355_ddpm_vlb(mi355_unet* net, const float* x0, int channels, const float* cond, const int32_t* labels, const mi355_ddpm_tables* tb,
-                   const mi355_vlb_options* opt, const float* noise, int64_t n_noise_draws, float* out_terms, float* summary, int batch, void* workspace,
-                   int64_t workspace_bytes, void* stream) {
+// the body of mi355_ddpm_vlb and mi355_ddpm_vlb_pred; pred: a checked PRED_* kind
+static int ddpm_vlb_run(int pred, mi355_unet* net, const float* x0, int channels, const float* cond, const int32_t* labels, const mi355_ddpm_tables* tb,
+                        const mi355_vlb_options* opt, const float* noise, int64_t n_noise_draws, float* out_terms, float* summary, int batch,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
   MI355_REQUIRE(tb, -1, "ddpm_vlb: tables is null");
   MI355_REQUIRE(opt, -1, "ddpm_vlb: opt is null");
   const int K = tb->Ns;
@@ -1130,7 +1170,7 @@ int mi355_ddpm_vlb(mi355_unet* net, const float* x0, int channels, const float* 
   UnetRun run = uniform_t_run();
   run.labels = labels;
   VlbStep st;
-  st.learned = opt->learned; st.cdf = opt->cdf; st.clip = opt->clip_denoised;
+  st.learned = opt->learned; st.cdf = opt->cdf; st.clip = opt->clip_denoised; st.pred = pred;
   for (int k = K - 1; k >= 0; --k) {
     const int64_t draw = K - 1 - k;
     const float* const z = noise ? noise + (size_t)draw * n : nullptr;
@@ -1141,6 +1181,7 @@ int mi355_ddpm_vlb(mi355_unet* net, const float* x0, int channels, const float* 
     if ((rc = emb.select(run, (size_t)k, batch, s))) return rc;
     if ((rc = unet_forward(net, xk, channels, condp, channels, sc.t, sc.v, batch, sc.unet_ws, sc.unet_bytes, s, run))) return rc;
     st.c_recip = tb->sqrt_recip_alphas_cumprod[k]; st.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[k];
+    st.sa = tb->sqrt_alphas_cumprod[k]; st.sb = tb->sqrt_one_minus_alphas_cumprod[k];
     st.coef1 = tb->posterior_mean_coef1[k]; st.coef2 = tb->posterior_mean_coef2[k];
     st.true_log = opt->true_log[k];
     if (learned) { st.min_log = opt->min_log[k]; st.max_log = opt->max_log[k]; }
@@ -1153,6 +1194,20 @@ int mi355_ddpm_vlb(mi355_unet* net, const float* x0, int channels, const float* 
                                 per, s)) return rc;
   net->last_launches += 2;   // the last evaluation with its noising and terms launches
   return 0;
+}
+
+int mi355_ddpm_vlb(mi355_unet* net, const float* x0, int channels, const float* cond, const int32_t* labels, const mi355_ddpm_tables* tb,
+                   const mi355_vlb_options* opt, const float* noise, int64_t n_noise_draws, float* out_terms, float* summary, int batch, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
+  return ddpm_vlb_run(PRED_EPS, net, x0, channels, cond, labels, tb, opt, noise, n_noise_draws, out_terms, summary, batch, workspace, workspace_bytes, stream);
+}
+
+int mi355_ddpm_vlb_pred(mi355_unet* net, const float* x0, int channels, const float* cond, const int32_t* labels, const mi355_ddpm_tables* tb,
+                        const mi355_vlb_options* opt, const mi355_ddpm_prediction* pred, const float* noise, int64_t n_noise_draws, float* out_terms,
+                        float* summary, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  MI355_REQUIRE(!pred || (pred->kind >= PRED_EPS && pred->kind <= PRED_V), -1, "ddpm_vlb_pred: pred->kind must be 0 (eps), 1 (x0) or 2 (v)");
+  return ddpm_vlb_run(pred ? pred->kind : PRED_EPS, net, x0, channels, cond, labels, tb, opt, noise, n_noise_draws, out_terms, summary, batch, workspace,
+                      workspace_bytes, stream);
 }
 
 // Adams-Bashforth CFM samplers: the loop of mi355_cfm_rk_sample / mi355_cfm_cfg_sample with the tableau as the start method (cfm_rk_loop, AbPlan).

@@ -64,6 +64,20 @@ __device__ inline void noise4(const float* z, int use_philox, uint64_t seed, uin
 // x0_hat before its clip, the ONE expression every predictor step and x0_shape_stats_kernel evaluate (product, product, difference: this file has
 // contraction off), so that the order statistic the stats kernel selects is an element of what the step clamps
 __device__ inline float x0_pre(float c_recip, float c_recipm1, float x, float e) { return c_recip * x - c_recipm1 * e; }
+// What the network output `o` stands for (PRED_*, ops.h), resolved at compile time: x0_pre of the kind.  eps: the expression above on the step's own
+// c_recip, c_recipm1 (nothing carried).  x0: the output itself, no arithmetic, x is not read for it.  v (Salimans & Ho 2022): sa x - sb o with sa =
+// sqrt_alphas_cumprod, sb = sqrt_one_minus_alphas_cumprod of the step, the same three roundings.
+template <int K> struct Pred;
+template <> struct Pred<PRED_EPS> {
+  __device__ inline float pre(float c_recip, float c_recipm1, float x, float o) const { return x0_pre(c_recip, c_recipm1, x, o); }
+};
+template <> struct Pred<PRED_X0> {
+  __device__ inline float pre(float, float, float, float o) const { return o; }
+};
+template <> struct Pred<PRED_V> {
+  float sa, sb;
+  __device__ inline float pre(float, float, float x, float o) const { return x0_pre(sa, sb, x, o); }
+};
 // classifier-free guidance of one element: eps_u + w (eps_c - eps_u), the difference, the product and the sum each rounded
 __device__ inline float cfg_mix(float ec, float eu, float w) {
   const float d = ec - eu;
@@ -138,20 +152,29 @@ template <bool SH> struct X0Rows {
       }
     }
   }
-  __device__ inline float x0(float c_recip, float c_recipm1, float x, float e, float f, float s) const {
-    if constexpr (SH) return clip_nan(x0_pre(c_recip, c_recipm1, x, f * e), -s, s) / s;
-    else return clip_nan(x0_pre(c_recip, c_recipm1, x, e), -1.f, 1.f);
+  template <class P> __device__ inline float x0(const P& pr, float c_recip, float c_recipm1, float x, float e, float f, float s) const {
+    if constexpr (SH) return clip_nan(pr.pre(c_recip, c_recipm1, x, f * e), -s, s) / s;
+    else return clip_nan(pr.pre(c_recip, c_recipm1, x, e), -1.f, 1.f);
   }
 };
-// run f(EpsSrc<CFG>, X0Rows<SH>) for the form predictor_step_launch was asked for
-template <typename F> int step_form(bool cfg, const float* eps, int64_t n, float w, const float* w_dev, int64_t per, int64_t stride, const float* shape, F&& f) {
+// run f(Pred<K>) for a prediction kind (checked by the caller)
+template <typename F> int pred_form(int pred, float sa, float sb, F&& f) {
+  if (pred == PRED_X0) return f(Pred<PRED_X0>{});
+  if (pred == PRED_V) return f(Pred<PRED_V>{sa, sb});
+  return f(Pred<PRED_EPS>{});
+}
+// run f(EpsSrc<CFG>, X0Rows<SH>, Pred<K>) for the form predictor_step_launch was asked for
+template <typename F> int step_form(bool cfg, const float* eps, int64_t n, float w, const float* w_dev, int64_t per, int64_t stride, const float* shape, int pred,
+                                    float sa, float sb, F&& f) {
   const int64_t nu = stride == per ? n : n / per * stride;
-  if (cfg) {
-    const EpsSrc<true> e{eps, n, w, w_dev, per, stride, nu};
-    return shape ? f(e, X0Rows<true>{shape, per}) : f(e, X0Rows<false>{nullptr, 0});
-  }
-  const EpsSrc<false> e{eps, n, 0.f, nullptr, per, stride, nu};
-  return shape ? f(e, X0Rows<true>{shape, per}) : f(e, X0Rows<false>{nullptr, 0});
+  return pred_form(pred, sa, sb, [&](auto pr) {
+    if (cfg) {
+      const EpsSrc<true> e{eps, n, w, w_dev, per, stride, nu};
+      return shape ? f(e, X0Rows<true>{shape, per}, pr) : f(e, X0Rows<false>{nullptr, 0}, pr);
+    }
+    const EpsSrc<false> e{eps, n, 0.f, nullptr, per, stride, nu};
+    return shape ? f(e, X0Rows<true>{shape, per}, pr) : f(e, X0Rows<false>{nullptr, 0}, pr);
+  });
 }
 }  // namespace
 
@@ -206,8 +229,8 @@ int sde_euler_step_launch(float* x, const float* a, const float* b, float ca, fl
 // The predictor steps: one kernel template per kind, all launched by predictor_step_launch (below the last of them).  Each has four forms, chosen by
 // step_form: plain or classifier-free-guided (EpsSrc), static clip or per-image shaping (X0Rows).
 namespace {
-template <class E, class R>
-int ddpm_step_form(E es, R rows, float* x, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float sigma, int use_philox,
+template <class E, class R, class P>
+int ddpm_step_form(E es, R rows, P pr, float* x, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float sigma, int use_philox,
                    uint64_t seed, uint64_t off4, int64_t n, hipStream_t s) {
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
     float xv[4], ev[4], zz[4], fv[4], sv[4];
@@ -217,7 +240,7 @@ int ddpm_step_form(E es, R rows, float* x, const float* z, float c_recip, float 
     rows.load(i, cnt, fv, sv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float x0 = rows.x0(c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);   // predict_start_from_noise + process_x0
+      const float x0 = rows.x0(pr, c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);   // predict_start_from_noise + process_x0
       const float mean = coef1 * x0 + coef2 * xv[j];                                // q_posterior
       xv[j] = mean + sigma * zz[j];                                                 // exp(0.5*logvar) * noise
     }
@@ -229,8 +252,8 @@ int ddpm_step_form(E es, R rows, float* x, const float* z, float c_recip, float 
 // The ancestral step of a learned-variance net (Nichol & Dhariwal 2021, eq. 15): the network's second half v interpolates the log-variance between
 // max_log = log(beta) and min_log = the clipped posterior log-variance; v is not clamped.  Every operation rounded (no contraction: this file).
 namespace {
-template <class E>
-int ddpm_lv_step_form(E es, float* x, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float min_log, float max_log,
+template <class E, class P>
+int ddpm_lv_step_form(E es, P pr, float* x, const float* z, float c_recip, float c_recipm1, float coef1, float coef2, float min_log, float max_log,
                       int use_philox, uint64_t seed, uint64_t off4, int64_t n, hipStream_t s) {
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
     float xv[4], ev[4], vv[4], zz[4];
@@ -242,7 +265,7 @@ int ddpm_lv_step_form(E es, float* x, const float* z, float c_recip, float c_rec
     for (int j = 0; j < 4; ++j) {
       const float frac = (vv[j] + 1.f) * 0.5f;
       const float logvar = frac * max_log + (1.f - frac) * min_log;
-      const float x0 = clip_nan(x0_pre(c_recip, c_recipm1, xv[j], ev[j]), -1.f, 1.f);
+      const float x0 = clip_nan(pr.pre(c_recip, c_recipm1, xv[j], ev[j]), -1.f, 1.f);
       const float mean = coef1 * x0 + coef2 * xv[j];
       xv[j] = mean + expf(0.5f * logvar) * zz[j];
     }
@@ -252,30 +275,34 @@ int ddpm_lv_step_form(E es, float* x, const float* z, float c_recip, float c_rec
 }  // namespace
 
 int corrector_step_launch(float* x, const float* eps, const float* z, float c_recip, float c_recipm1, float rsm1, float dt,
-                          float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, int64_t per, int64_t eps_stride) {
+                          float delta, int use_philox, uint64_t seed, uint64_t offset, int64_t n, hipStream_t s, int64_t per, int64_t eps_stride, int pred,
+                          float sa, float sb) {
   MI355_REQUIRE(offset % 4 == 0, -1, "corrector_step: the Philox offset must be a multiple of 4");
+  MI355_REQUIRE(pred >= PRED_EPS && pred <= PRED_V, -1, "corrector_step: the prediction kind must be 0 (eps), 1 (x0) or 2 (v)");
   const int64_t stride = eps_stride ? eps_stride : per;
   MI355_REQUIRE(stride == per || (per > 0 && n % per == 0 && stride > per), -1,
                 "corrector_step: an eps stride needs n to be whole images of elems_per_image elements and eps_stride >= elems_per_image");
   const uint64_t off4 = offset / 4;
   const float kd = 0.5f * dt * delta, kn = sqrtf(dt * delta);
-  return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
-    float xv[4], ev[4], zz[4];
-    ld4(x, i, cnt, xv); ld4_eps(eps, per, stride, i, cnt, ev);
-    noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
+  return pred_form(pred, sa, sb, [=](auto pr) {
+    return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
+      float xv[4], ev[4], zz[4];
+      ld4(x, i, cnt, xv); ld4_eps(eps, per, stride, i, cnt, ev);
+      noise4(z, use_philox, seed, off4, i, i4, cnt, zz);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x0 = clip_nan(c_recip * xv[j] - c_recipm1 * ev[j], -1.f, 1.f);
-      const float score = -rsm1 * x0;  // score_from_x0
-      xv[j] = xv[j] + (kd * score + kn * zz[j]);
-    }
-    st4(x, i, cnt, xv);
+      for (int j = 0; j < 4; ++j) {
+        const float x0 = clip_nan(pr.pre(c_recip, c_recipm1, xv[j], ev[j]), -1.f, 1.f);
+        const float score = -rsm1 * x0;  // score_from_x0
+        xv[j] = xv[j] + (kd * score + kn * zz[j]);
+      }
+      st4(x, i, cnt, xv);
+    });
   });
 }
 
 namespace {
-template <class E, class R>
-int ddim_step_form(E es, R rows, float* x, float c_recip, float c_recipm1, float sa, float sb, int64_t n, hipStream_t s) {
+template <class E, class R, class P>
+int ddim_step_form(E es, R rows, P pr, float* x, float c_recip, float c_recipm1, float sa, float sb, int64_t n, hipStream_t s) {
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
     float xv[4], ev[4], fv[4], sv[4];
     ld4(x, i, cnt, xv);
@@ -283,7 +310,7 @@ int ddim_step_form(E es, R rows, float* x, float c_recip, float c_recipm1, float
     rows.load(i, cnt, fv, sv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float x0 = rows.x0(c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);
+      const float x0 = rows.x0(pr, c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);
       const float e2 = (c_recip * xv[j] - x0) / c_recipm1;   // the eps that x0_hat stands for: of the clipped (shaped: the thresholded) prediction
       xv[j] = sa * x0 + sb * e2;
     }
@@ -303,8 +330,8 @@ inline DdimEta ddim_eta_coefs(float acp_prev, float sigma) {
   const float r = 1.0f - acp_prev;
   return {sqrtf(acp_prev), sqrtf(fmaxf(r - s2, 0.f))};
 }
-template <class E, class R>
-int ddim_eta_step_form(E es, R rows, float* x, const float* z, float c_recip, float c_recipm1, float sa, float sb, float sigma, int noisy, int use_philox,
+template <class E, class R, class P>
+int ddim_eta_step_form(E es, R rows, P pr, float* x, const float* z, float c_recip, float c_recipm1, float sa, float sb, float sigma, int noisy, int use_philox,
                        uint64_t seed, uint64_t off4, int64_t n, hipStream_t s) {
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t i4, int cnt) {
     float xv[4], ev[4], zz[4] = {0.f, 0.f, 0.f, 0.f}, fv[4], sv[4];
@@ -314,7 +341,7 @@ int ddim_eta_step_form(E es, R rows, float* x, const float* z, float c_recip, fl
     rows.load(i, cnt, fv, sv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float x0 = rows.x0(c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);
+      const float x0 = rows.x0(pr, c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);
       const float e2 = (c_recip * xv[j] - x0) / c_recipm1;
       const float m = sa * x0 + sb * e2;
       xv[j] = noisy ? m + sigma * zz[j] : m;
@@ -613,8 +640,8 @@ int paint_patch_launch(const float* img, const int* top, const int* left, int pa
 // not kept.  The host coefficients are DDPM.dpm_solver_coefs.
 // With shaping rows D is the shaped x0_hat, and that is what the history keeps.
 namespace {
-template <class E, class R>
-int dpmpp_step_form(E es, R rows, float* x, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s) {
+template <class E, class R, class P>
+int dpmpp_step_form(E es, R rows, P pr, float* x, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, hipStream_t s) {
   const bool two = c1 != 0.f;
   return launch_ew4(n, s, [=] __device__(int64_t i, int64_t, int cnt) {
     float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4], fv[4], sv[4];
@@ -624,7 +651,7 @@ int dpmpp_step_form(E es, R rows, float* x, float* hist, float c_recip, float c_
     rows.load(i, cnt, fv, sv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float d = rows.x0(c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);
+      const float d = rows.x0(pr, c_recip, c_recipm1, xv[j], ev[j], fv[j], sv[j]);
       const float m = cx * xv[j] + c0 * d;
       xv[j] = two ? m + c1 * hv[j] : m;
       dv[j] = d;
@@ -653,6 +680,7 @@ int predictor_step_launch(const PredictorStep& p, hipStream_t s) {
   if (draws) MI355_REQUIRE(offset % 4 == 0, -1, f() + "the Philox offset must be a multiple of 4");
   MI355_REQUIRE(!w_dev || (per > 0 && n % per == 0), -1, f() + "per-image scales need n to be whole images of elems_per_image elements");
   MI355_REQUIRE(n <= 0 || (x && eps), -1, f() + "null argument");
+  MI355_REQUIRE(p.pred >= PRED_EPS && p.pred <= PRED_V, -1, f() + "the prediction kind must be 0 (eps), 1 (x0) or 2 (v)");
   if (p.kind == STEP_DDIM_ETA) MI355_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, -1, f() + "sigma must be finite and >= 0");
   if (p.kind == STEP_DPMPP) MI355_REQUIRE(c1 == 0.f || hist || n <= 0, -1, f() + "c1 != 0 needs hist (the previous step's data prediction)");
   MI355_REQUIRE(!shape || (per > 0 && n % per == 0), -1, f() + "per-image shaping rows need n to be whole images of elems_per_image elements");
@@ -668,23 +696,23 @@ int predictor_step_launch(const PredictorStep& p, hipStream_t s) {
   const uint64_t off4 = offset / 4;
   if (p.kind == STEP_ANCESTRAL_LV) {
     const float min_log = p.min_log, max_log = p.max_log;
-    return step_form(cfg, eps, n, p.guide.w, w_dev, per, stride, nullptr, [=](auto es, auto) {
-      return ddpm_lv_step_form(es, x, z, c_recip, c_recipm1, p.a, p.b, min_log, max_log, use_philox, seed, off4, n, s);
+    return step_form(cfg, eps, n, p.guide.w, w_dev, per, stride, nullptr, p.pred, p.sa, p.sb, [=](auto es, auto, auto pr) {
+      return ddpm_lv_step_form(es, pr, x, z, c_recip, c_recipm1, p.a, p.b, min_log, max_log, use_philox, seed, off4, n, s);
     });
   }
-  return step_form(cfg, eps, n, p.guide.w, w_dev, per, stride, shape, [=](auto es, auto rows) {
+  return step_form(cfg, eps, n, p.guide.w, w_dev, per, stride, shape, p.pred, p.sa, p.sb, [=](auto es, auto rows, auto pr) {
     switch (p.kind) {
       case STEP_ANCESTRAL:
-        return ddpm_step_form(es, rows, x, z, c_recip, c_recipm1, p.a, p.b, sigma, use_philox, seed, off4, n, s);
+        return ddpm_step_form(es, rows, pr, x, z, c_recip, c_recipm1, p.a, p.b, sigma, use_philox, seed, off4, n, s);
       case STEP_DDIM:
-        return ddim_step_form(es, rows, x, c_recip, c_recipm1, sqrtf(p.a), sqrtf(1.0f - p.a), n, s);
+        return ddim_step_form(es, rows, pr, x, c_recip, c_recipm1, sqrtf(p.a), sqrtf(1.0f - p.a), n, s);
       case STEP_DDIM_ETA: {
         const DdimEta c = ddim_eta_coefs(p.a, sigma);
         const int noisy = z != nullptr || use_philox;
-        return ddim_eta_step_form(es, rows, x, z, c_recip, c_recipm1, c.sa, c.sb, sigma, noisy, use_philox, seed, off4, n, s);
+        return ddim_eta_step_form(es, rows, pr, x, z, c_recip, c_recipm1, c.sa, c.sb, sigma, noisy, use_philox, seed, off4, n, s);
       }
       default:
-        return dpmpp_step_form(es, rows, x, hist, c_recip, c_recipm1, p.a, p.b, c1, n, s);
+        return dpmpp_step_form(es, rows, pr, x, hist, c_recip, c_recipm1, p.a, p.b, c1, n, s);
     }
   });
 }
@@ -708,6 +736,7 @@ struct X0StatsArgs {
   int64_t n, per, k;
   float w, c_recip, c_recipm1, phi, one_minus_phi, frac, s_max;
   int guided, do_var, do_sel;
+  int pred;   // PRED_*: x0_pre of the kind; c_recip, c_recipm1 then hold sa, sb for v and are not read for x0 (nor is x)
 };
 
 __global__ void __launch_bounds__(XS_THREADS) x0_shape_stats_kernel(X0StatsArgs a) {
@@ -752,7 +781,11 @@ __global__ void __launch_bounds__(XS_THREADS) x0_shape_stats_kernel(X0StatsArgs 
 
   float s = 1.f, s_raw = 0.f;
   if (a.do_sel) {
-    auto key_of = [&](int64_t j) { return __float_as_uint(x0_pre(a.c_recip, a.c_recipm1, xp[j], f * eps_g(j))) & 0x7fffffffu; };
+    const bool reads_x = a.pred != PRED_X0;   // uniform over the launch
+    auto key_of = [&](int64_t j) {
+      const float fe = f * eps_g(j);
+      return __float_as_uint(reads_x ? x0_pre(a.c_recip, a.c_recipm1, xp[j], fe) : fe) & 0x7fffffffu;
+    };
     uint32_t prefix = 0, rank = (uint32_t)a.k, eq = 0, saw_nan = 0;
     if (tid == 0) any_nan = 0;
     for (int pass = 0; pass < 4; ++pass) {
@@ -818,10 +851,11 @@ int check_x0_shaping(const char* who, const mi355_x0_shaping* sh, int guided) {
 }
 
 int x0_shape_stats_launch(const float* x, const float* eps, const StepGuide& g, float c_recip, float c_recipm1, const mi355_x0_shaping* sh, float* shape,
-                          float* detail, int batch, int64_t per, hipStream_t s) {
+                          float* detail, int batch, int64_t per, hipStream_t s, int pred, float sa, float sb) {
   const int guided = g.on;
   if (int rc = check_x0_shaping("x0_shape_stats", sh, guided)) return rc;
-  MI355_REQUIRE(x, -1, "x0_shape_stats: x is null");
+  MI355_REQUIRE(pred >= PRED_EPS && pred <= PRED_V, -1, "x0_shape_stats: the prediction kind must be 0 (eps), 1 (x0) or 2 (v)");
+  MI355_REQUIRE(x || pred == PRED_X0, -1, "x0_shape_stats: x is null");
   MI355_REQUIRE(eps, -1, "x0_shape_stats: eps is null");
   MI355_REQUIRE(shape, -1, "x0_shape_stats: shape is null");
   MI355_REQUIRE(batch > 0, -1, "x0_shape_stats: batch must be > 0");
@@ -829,8 +863,8 @@ int x0_shape_stats_launch(const float* x, const float* eps, const StepGuide& g, 
   X0StatsArgs a = {};
   a.x = x; a.eps = eps; a.w_dev = guided ? g.w_dev : nullptr; a.shape = shape; a.detail = detail;
   a.n = (int64_t)batch * per; a.per = per;
-  a.w = g.w; a.c_recip = c_recip; a.c_recipm1 = c_recipm1;
-  a.guided = guided;
+  a.w = g.w; a.c_recip = pred == PRED_V ? sa : c_recip; a.c_recipm1 = pred == PRED_V ? sb : c_recipm1;
+  a.guided = guided; a.pred = pred;
   const float q = sh ? sh->quantile : 0.f, phi = sh ? sh->rescale_phi : 0.f;
   a.phi = phi; a.one_minus_phi = 1.0f - phi;
   a.s_max = sh ? sh->max_threshold : 0.f;

@@ -21,7 +21,7 @@ namespace {
 
 constexpr double LN2 = 0.6931471805599453;
 
-struct VlbScalars { double c_recip, c_recipm1, coef1, coef2, lq, lp_fixed, min_log, max_log; };
+struct VlbScalars { double c_recip, c_recipm1, coef1, coef2, lq, lp_fixed, min_log, max_log, sa, sb; int pred; };
 
 // four consecutive floats: one 16-byte load where the address allows it
 __device__ inline void ld4v(const float* p, float (&v)[4]) {
@@ -97,11 +97,12 @@ __device__ inline double decoder_nll(double x0, double mean_p, double lp) {
   return -log(p < 1e-12 ? 1e-12 : p);   // a NaN stays one
 }
 
-// one element into the three running sums acc = { vb term, (x0_hat - x0)^2, (eps - z)^2 }
+// one element into the three running sums acc = { vb term, (x0_hat - x0)^2, (out - target)^2 }, target what a net of the kind is trained on: z for
+// eps, x0 for x0, sa z - sb x0 for v; x0_hat from x0_pre of the kind (c.pred is uniform over the launch)
 template <bool K0, int CDF>
 __device__ inline void vlb_elem(const VlbScalars& c, bool learned, bool clip, float x0f, float xkf, float ef, float vf, float zf, double (&acc)[3]) {
   const double x0 = (double)x0f, xk = (double)xkf, eps = (double)ef, z = (double)zf;
-  double xh = c.c_recip * xk - c.c_recipm1 * eps;
+  double xh = c.pred == PRED_X0 ? eps : (c.pred == PRED_V ? c.sa * xk - c.sb * eps : c.c_recip * xk - c.c_recipm1 * eps);
   if (clip) xh = xh < -1.0 ? -1.0 : (xh > 1.0 ? 1.0 : xh);
   const double mean_p = c.coef1 * xh + c.coef2 * xk;
   double lp = c.lp_fixed;
@@ -116,7 +117,8 @@ __device__ inline void vlb_elem(const VlbScalars& c, bool learned, bool clip, fl
     const double d = mean_q - mean_p;
     acc[0] += 0.5 * (-1.0 + lp - c.lq + exp(c.lq - lp) + d * d * exp(-lp));
   }
-  const double dx = xh - x0, de = eps - z;
+  const double target = c.pred == PRED_X0 ? x0 : (c.pred == PRED_V ? c.sa * z - c.sb * x0 : z);
+  const double dx = xh - x0, de = eps - target;
   acc[1] += dx * dx;
   acc[2] += de * de;
 }
@@ -207,6 +209,8 @@ int vlb_terms_launch(const float* x0, const float* xk, const float* out, int64_t
   MI355_REQUIRE(st.learned == 0 || st.learned == 1, -1, "vlb_terms: learned must be 0 (model_log) or 1 (the range min_log, max_log)");
   MI355_REQUIRE(st.cdf == 0 || st.cdf == 1, -1, "vlb_terms: cdf must be 0 (exact, erfc) or 1 (the tanh approximation)");
   MI355_REQUIRE(st.clip == 0 || st.clip == 1, -1, "vlb_terms: clip_denoised must be 0 or 1");
+  MI355_REQUIRE(st.pred >= PRED_EPS && st.pred <= PRED_V, -1, "vlb_terms: the prediction kind must be 0 (eps), 1 (x0) or 2 (v)");
+  if (st.pred == PRED_V) MI355_REQUIRE(std::isfinite(st.sa) && std::isfinite(st.sb), -1, "vlb_terms: sa and sb must be finite");
   MI355_REQUIRE(per > 0, -1, "vlb_terms: elems_per_image must be > 0");
   MI355_REQUIRE(batch >= 0, -1, "vlb_terms: batch must be >= 0");
   MI355_REQUIRE(out_stride >= (st.learned ? 2 : 1) * per, -1,
@@ -222,7 +226,7 @@ int vlb_terms_launch(const float* x0, const float* xk, const float* out, int64_t
   MI355_REQUIRE(x0 && xk && out && dst, -1, "vlb_terms: null argument");
   MI355_REQUIRE(z || use_philox, -1, "vlb_terms: the step's draw is needed (z, or Philox at (seed, offset))");
   const VlbScalars c{(double)st.c_recip, (double)st.c_recipm1, (double)st.coef1, (double)st.coef2,
-                     (double)st.true_log, (double)st.model_log, (double)st.min_log, (double)st.max_log};
+                     (double)st.true_log, (double)st.model_log, (double)st.min_log, (double)st.max_log, (double)st.sa, (double)st.sb, st.pred};
   const uint64_t off4 = offset / 4;
   const dim3 grid((unsigned)batch), block(256);
   if (!st.k_is_zero)

@@ -27,7 +27,7 @@ class VLBResult(NamedTuple):
     prior_bpd: torch.Tensor    # [B]     KL(q(x_K | x0) || N(0, 1))
     vb: torch.Tensor           # [B, K]  step k's term: the KL for k > 0, the decoder's NLL at k = 0
     xstart_mse: torch.Tensor   # [B, K]  mean((x0_hat - x0)^2)
-    mse: torch.Tensor          # [B, K]  mean((eps - z_k)^2)
+    mse: torch.Tensor          # [B, K]  mean((out - target)^2), target z_k ("eps" chains), x0 ("x0"), sa z_k - sb x0 ("v")
 
 
 def _refuse(pair: str, why: str):
@@ -39,7 +39,8 @@ def get_vlb_fn(eps_model: Callable, ddpm: DDPM, conditioning: Optional[Condition
     """-> vlb(x0, condition=None, y=None, noise=None, seed=None) -> VLBResult, every field float32 on x0's device.
 
     variance: "learned" (the net writes eps | v; the range between the posterior variance and beta), "fixed_small" (the posterior variance) or
-    "fixed_large" (beta); None: "learned" on a with_learned_variance chain, "fixed_small" otherwise.  cdf: "exact" (erfc) or "tanh"
+    "fixed_large" (beta); None: "learned" on a with_learned_variance chain, "fixed_large" on a with_fixed_variance("large") one, "fixed_small"
+    otherwise.  The prediction kind is the chain's (DDPM.with_prediction): x0_hat and the mse target follow it (mi355_ddpm_vlb_pred).  cdf: "exact" (erfc) or "tanh"
     (guided-diffusion's approximation, for comparison with published numbers).  Under Amortized conditioning the net sees x_k | condition;
     condition None: x_k | likelihood.none_like.  y: class labels of a class-conditional net.  noise: [K, B, C, H, W] injected draws (draw j
     belongs to step K-1-j), else device Philox at seed (None: torch's initial seed).  A chain view carrying x0 shaping, tiling or a feature cache,
@@ -55,7 +56,8 @@ def get_vlb_fn(eps_model: Callable, ddpm: DDPM, conditioning: Optional[Condition
     if isinstance(conditioning, ClassifierFreeGuidance) or getattr(conditioning, "guidance_scale", None) is not None:
         _refuse("guidance_scale (ClassifierFreeGuidance)", "a guided model's sum is not a bound; evaluate the conditional model (Amortized)")
     if variance is None:
-        variance = "learned" if getattr(ddpm, "learned_variance", False) else "fixed_small"
+        variance = ("learned" if getattr(ddpm, "learned_variance", False) else
+                    "fixed_large" if getattr(ddpm, "fixed_variance", "small") == "large" else "fixed_small")
     if variance not in VARIANCES:
         raise ValueError(f"variance must be one of {VARIANCES} or None, got {variance!r}")
     logs = ddpm.vlb_log_variances(variance)   # Ns < 2: ValueError
@@ -64,6 +66,7 @@ def get_vlb_fn(eps_model: Callable, ddpm: DDPM, conditioning: Optional[Condition
     if amortized and likelihood is None:
         raise ValueError("Amortized conditioning needs the likelihood (its none_like is what the net sees without a condition)")
     times = torch.tensor([ddpm.time(k) for k in range(ddpm.Ns)], dtype=torch.float32)
+    prediction = getattr(ddpm, "prediction", "eps")
 
     @torch.no_grad()
     def vlb(x0, condition=None, y=None, noise=None, seed=None):
@@ -83,7 +86,8 @@ def get_vlb_fn(eps_model: Callable, ddpm: DDPM, conditioning: Optional[Condition
         nz = None if noise is None else noise.to(x.device, torch.float32).contiguous()
         terms, summary = engine.ddpm_vlb(x, ddpm.host_tables(), logs, learned=learned, times=times,
                                          cond=None if condition is None else condition.float().contiguous(), y=y, noise=nz, seed=seed, cdf=cdf,
-                                         clip_denoised=clip_denoised, none_value=sampling._none_value(likelihood, x) if amortized else 0.0)
+                                         clip_denoised=clip_denoised, none_value=sampling._none_value(likelihood, x) if amortized else 0.0,
+                                         **({} if prediction == "eps" else {"prediction": prediction}))
         return VLBResult(summary[:, 1], summary[:, 0], terms[:, :, 0], terms[:, :, 1], terms[:, :, 2])
 
     return vlb

@@ -20,6 +20,9 @@ with the static clip: the fast path in mi355_ddpm_shaped_sample, the generic one
 A chain made by DDPM.with_learned_variance() samples a net with 2C outputs (eps | v, improved-DDPM's learned variance range): the fast path in
 mi355_ddpm_lv_sample, the generic one through ddpm_lv_step_ and strided_step_ on the net's output as it is; DDPM.from_betas chains (linear, cosine;
 a time_scale between step and network time) run there as well; sample quality untested.
+A chain made by DDPM.with_prediction("x0" | "v") samples a net whose output is the data prediction or v: the fast path in mi355_ddpm_pred_sample,
+the generic one through pred_step_ (and pred_shape_stats) on the net's raw output, one step op per step; make_eps_model keeps its name, the model
+returns whatever the net writes; sample quality untested.
 ReconstructionGuidance (sampling.py:136-206) differentiates the x0 model through the U-Net: the gradient is the HIP engine's
 vector-Jacobian product (`UNetEngine.vjp`, csrc/unet_backward.hip) of a differentiable plan of the same network, so it needs an
 `eps_model` made by `make_eps_model(network, ddpm)` around a `UNetModel`.
@@ -167,10 +170,35 @@ def _shaping_of(ddpm, guided: bool):
     return shaping
 
 
-def _shape_rows(xi, eps, i, T, shaping, w=None):
-    """The per-image rows (f, s) of step i's shaped data prediction, or None without shaping.  w: eps is the [2B] pair of a guided step."""
+def _pred_of(ddpm, *, tiling=None, feature_cache=None) -> str:
+    """ddpm.prediction (DDPM.with_prediction; "eps" on a plain chain); refused, by name, with what is not built for an x0- or v-prediction
+    chain, and with a fixed large variance on a learned-variance chain (which of the two variances is meant?)."""
+    pred = getattr(ddpm, "prediction", "eps")
+    if getattr(ddpm, "fixed_variance", "small") == "large" and getattr(ddpm, "learned_variance", False):
+        raise NotImplementedError('a fixed variance (DDPM.with_fixed_variance("large")) is not built for a learned-variance chain '
+                                  "(DDPM.with_learned_variance): the chain has one variance")
+    if pred == "eps":
+        return pred
+    if tiling is not None:
+        raise NotImplementedError("tiling is not built for an x0- or v-prediction chain (DDPM.with_prediction)")
+    if feature_cache is not None:
+        raise NotImplementedError("feature_cache is not built for an x0- or v-prediction chain (DDPM.with_prediction)")
+    return pred
+
+
+def _pred_kw(T, i):
+    """sa, sb of step i for pred_step_ / pred_shape_stats (read by the "v" kind)."""
+    return dict(sa=float(T["sqrt_alphas_cumprod"][i]), sb=float(T["sqrt_one_minus_alphas_cumprod"][i]))
+
+
+def _shape_rows(xi, eps, i, T, shaping, w=None, pred="eps"):
+    """The per-image rows (f, s) of step i's shaped data prediction, or None without shaping.  w: eps is the [2B] pair of a guided step.
+    pred (not "eps"): eps is the raw output of an x0- or v-prediction net."""
     if shaping is None:
         return None
+    if pred != "eps":
+        return _ops.pred_shape_stats(pred, xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), shaping, w=w,
+                                     **_pred_kw(T, i))
     return _ops.x0_shape_stats(xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), shaping, w=w)
 
 
@@ -207,12 +235,20 @@ def _check_engine_width(engine, xi, max_log):
         _check_width(out_channels, xi, max_log)
 
 
-def _predictor(eps, xi, i, T, noise: _Noise, shape=None, max_log=None, w=None):
+def _predictor(eps, xi, i, T, noise: _Noise, shape=None, max_log=None, w=None, pred="eps"):
     """step() (sampling.py:59-67): x0_hat -> clip -> posterior mean -> + exp(0.5 logvar) z (z iff i > 0).  shape: the rows of _shape_rows
     (per-image shaping in place of the clip).  max_log (a learned-variance chain): eps is the net's 2C output, passed whole; with w, the
-    [2B] pair of a guided step and xi the duplicated state."""
+    [2B] pair of a guided step and xi the duplicated state.  pred (not "eps"): eps is the raw output of an x0- or v-prediction net, passed
+    whole to the one step op that takes the kind."""
     z, ph = noise.next() if i > 0 else (None, None)
     sigma = float((0.5 * T["posterior_log_variance_clipped"][i]).exp())  # fp32, like (0.5*logvar).exp()
+    if pred != "eps":
+        cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
+        c1, c2 = float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i])
+        if max_log is not None and i > 0:
+            return _ops.pred_step_("ddpm_lv", pred, xi, eps, cr, crm1, c1, c2, min_log=float(T["posterior_log_variance_clipped"][i]),
+                                   max_log=float(max_log[i]), z=z, philox=ph, w=w, **_pred_kw(T, i))
+        return _ops.pred_step_("ddpm", pred, xi, eps, cr, crm1, c1, c2, sigma=sigma, z=z, philox=ph, w=w, shape=shape, **_pred_kw(T, i))
     if max_log is not None:
         cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
         c1, c2 = float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i])
@@ -228,10 +264,14 @@ def _predictor(eps, xi, i, T, noise: _Noise, shape=None, max_log=None, w=None):
     return xi
 
 
-def _corrector(eps, xi, i, T, ddpm, delta, noise: _Noise, max_log=None):
-    """corrector_step (sampling.py:113-121).  max_log (a learned-variance chain): eps is the net's 2C output, passed whole."""
+def _corrector(eps, xi, i, T, ddpm, delta, noise: _Noise, max_log=None, pred="eps"):
+    """corrector_step (sampling.py:113-121).  max_log (a learned-variance chain): eps is the net's 2C output, passed whole.  pred: as in
+    _predictor."""
     z, ph = noise.next()
     dt = (ddpm.tmax - ddpm.tmin) / ddpm.Ns
+    if pred != "eps":
+        return _ops.pred_step_("corrector", pred, xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
+                               float(T["recip_sqrt_m1_alphas_cumprod"][i]), dt, float(delta), z=z, philox=ph, **_pred_kw(T, i))
     if max_log is not None:
         return _ops.strided_step_("corrector", xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
                                   float(T["recip_sqrt_m1_alphas_cumprod"][i]), dt, float(delta), z=z, philox=ph)
@@ -261,6 +301,7 @@ def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replac
     T = _tables(ddpm)
     shaping = _shaping_of(ddpm, False)
     max_log = _learned_of(ddpm)
+    pred = _pred_of(ddpm)
     xi = xT.detach().clone().float().contiguous()
     noise = _Noise(xi)
     for level, down in _walk_moves(ddpm.Ns, walk):
@@ -275,17 +316,22 @@ def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replac
                                float(T["sqrt_alphas_cumprod"][i]), float(T["sqrt_one_minus_alphas_cumprod"][i]), ph)
         eps = eps_model(_net_in(xi, cond_pred, amortized), _times(xi, i)).float().contiguous()
         _check_width(eps.shape[1], xi, max_log, host_loop=True)
-        _predictor(eps, xi, i, T, noise, _shape_rows(xi, eps, i, T, shaping), max_log)
+        _predictor(eps, xi, i, T, noise, _shape_rows(xi, eps, i, T, shaping, pred=pred), max_log, pred=pred)
         for _ in range(n_corrector):
             eps = eps_model(_net_in(xi, cond_corr, amortized), _times(xi, i))
-            _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise, max_log)
+            _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise, max_log, pred=pred)
     return process_x0(xi)
 
 
-def _ddim_move(eps, xi, i, T, sigma, noise, shape=None, wide=False, w=None):
+def _ddim_move(eps, xi, i, T, sigma, noise, shape=None, wide=False, w=None, pred="eps"):
     """One DDIM step: sigma None = the deterministic kernel; else DDIM(eta) with sigma[i] and one draw iff i > 0.  shape: as in _predictor.
     wide (a learned-variance chain): eps is the net's 2C output, passed whole; with w, the [2B] pair of a guided step, xi the duplicated state."""
     cr, crm1, prev = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), float(T["alphas_cumprod_prev"][i])
+    if pred != "eps":   # the raw output of an x0- or v-prediction net, passed whole (wide or not) to the one step op that takes the kind
+        if sigma is None:
+            return _ops.pred_step_("ddim", pred, xi, eps, cr, crm1, prev, w=w, shape=shape, **_pred_kw(T, i))
+        z, ph = noise.next() if i > 0 else (None, None)
+        return _ops.pred_step_("ddim_eta", pred, xi, eps, cr, crm1, prev, sigma=float(sigma[i]), z=z, philox=ph, w=w, shape=shape, **_pred_kw(T, i))
     if wide:
         if sigma is None:
             return _ops.strided_step_("ddim", xi, eps, cr, crm1, prev, w=w)
@@ -305,6 +351,7 @@ def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corre
     T = _tables(ddpm)
     shaping = _shaping_of(ddpm, True)
     max_log = _learned_of(ddpm)
+    pred = _pred_of(ddpm)
     xi = xT.detach().clone().float().contiguous()
     noise = _Noise(xi)
     B = xi.shape[0]
@@ -313,16 +360,19 @@ def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corre
         eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
         eps2 = torch.cat((ec, eu)).contiguous()
         _check_width(eps2.shape[1], xi, max_log, host_loop=True)
-        if max_log is not None:   # the guided step kernels on the 2C pair itself (v from the conditional half), the state duplicated for them
+        if max_log is not None or pred != "eps":
+            # the guided step kernels on the pair itself (a 2C pair: v from the conditional half; an x0- or v-prediction pair: mixed raw), the
+            # state duplicated for them
             x2 = torch.cat((xi, xi))
+            shape = _shape_rows(xi, eps2, i, T, shaping, w=guidance_scale, pred=pred) if pred != "eps" else None
             if ddim:
-                _ddim_move(eps2, x2, i, T, ddim_sigma, noise, wide=True, w=guidance_scale)
+                _ddim_move(eps2, x2, i, T, ddim_sigma, noise, shape, wide=True, w=guidance_scale, pred=pred)
             else:
-                _predictor(eps2, x2, i, T, noise, max_log=max_log, w=guidance_scale)
+                _predictor(eps2, x2, i, T, noise, shape, max_log=max_log, w=guidance_scale, pred=pred)
             xi.copy_(x2[:B])
             for _ in range(0 if ddim else n_corrector):
                 eps = eps_model(_net_in(xi, none, True), _times(xi, i))
-                _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise, max_log)
+                _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise, max_log, pred=pred)
             continue
         shape = _shape_rows(xi, eps2, i, T, shaping, w=guidance_scale)
         eps = _ops.cfg_combine(eps2, guidance_scale)
@@ -424,8 +474,12 @@ def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_f
     feature_cache = _cache_of(ddpm, feature_cache)
     tiling = _tiling_of(ddpm, tiling)
     max_log = _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)
+    pred = _pred_of(ddpm, tiling=tiling, feature_cache=feature_cache)
     times = _custom_times(ddpm)
     _check_engine_width(engine, xi, max_log)
+    if pred != "eps":   # an x0- or v-prediction net: mi355_ddpm_pred_sample, which takes the shaping, the variance range and the times beside the kind
+        engine.ddpm_pred(xi, _tables(ddpm), pred, shaping=shaping, max_log=max_log, times=times, **kw)
+        return xi
     if feature_cache is not None:
         if guidance_scale is not None:
             _refuse_feature_cache(feature_cache, "the guided (classifier-free guidance) loops")
@@ -474,6 +528,7 @@ def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Condition
     feature_cache = _cache_of(ddpm, feature_cache)
     tiling = _tiling_of(ddpm, tiling)
     _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)   # a learned-variance chain: its refusals, before the first sample
+    _pred_of(ddpm, tiling=tiling, feature_cache=feature_cache)      # an x0- or v-prediction chain: likewise
 
     @torch.no_grad()
     def sample(xT):
@@ -498,6 +553,7 @@ def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Con
     feature_cache = _cache_of(ddpm, feature_cache)
     tiling = _tiling_of(ddpm, tiling)
     _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)   # a learned-variance chain: its refusals, before the first sample
+    _pred_of(ddpm, tiling=tiling, feature_cache=feature_cache)      # an x0- or v-prediction chain: likewise
     if isinstance(conditioning, ClassifierFreeGuidance):   # (an Amortized: before it)
         _refuse_feature_cache(feature_cache, "ClassifierFreeGuidance (the guided loops)")
         _refuse_tiling(tiling, "ClassifierFreeGuidance (the guided loops)")
@@ -571,6 +627,9 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
             "a UNetModel (an arbitrary callable has no backward pass on the HIP backend)")
     if conditioning.update_rule not in ("before", "after"):
         raise ValueError(f"unknown update_rule {conditioning.update_rule!r}")
+    if getattr(ddpm, "prediction", "eps") != "eps":
+        raise NotImplementedError("ReconstructionGuidance is not built for an x0- or v-prediction chain (DDPM.with_prediction): the seed "
+                                  "differentiates x0_hat = c_recip x - c_recipm1 eps of an eps net")
     if getattr(ddpm, "learned_variance", False):
         raise NotImplementedError("ReconstructionGuidance is not built for a learned-variance chain (DDPM.with_learned_variance): the seed and "
                                   "the backward pass take a net that writes the state's channels")
@@ -669,6 +728,7 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
     cx, c0, c1 = (c.tolist() for c in coefs)
     shaping = _shaping_of(ddpm, guidance_scale is not None)
     max_log = _learned_of(ddpm)   # a learned-variance chain: the solver reads the eps channels of the 2C output
+    pred = _pred_of(ddpm)
     times = _custom_times(ddpm)
 
     @torch.no_grad()
@@ -685,6 +745,10 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
             sched = {}
             if getattr(ddpm, "timesteps", None) is not None:
                 sched = dict(timesteps=ddpm.timesteps, train_steps=int(ddpm.base_Ns))
+            if pred != "eps":
+                _check_engine_width(engine, xi, max_log)
+                return engine.ddpm_pred(xi, T, pred, shaping=shaping, max_log=max_log, times=times, mode=_lib.DDIM, coefs=coefs, cond=condition,
+                                        none_value=nv, guidance_scale=guidance_scale, **sched)
             if max_log is not None or times is not None:
                 if shaping is not None:
                     raise NotImplementedError("x0_shaping is not built for a chain with a time_scale (DDPM.from_betas(..., time_scale=))")
@@ -704,6 +768,17 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
             shape = None
             _check_width(eps.shape[1], xi, max_log, host_loop=True)
             cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
+            if pred != "eps":   # the raw output of an x0- or v-prediction net, passed whole (guided: the pair, on the duplicated state)
+                if none is None:
+                    _ops.pred_step_("dpmpp", pred, xi, eps, cr, crm1, cx[i], c0[i], c1[i], hist=hist,
+                                    shape=_shape_rows(xi, eps, i, T, shaping, pred=pred), **_pred_kw(T, i))
+                    continue
+                eps2 = torch.cat((eps, eps_model(_net_in(xi, none, True), _times(xi, i)).float())).contiguous()
+                x2 = torch.cat((xi, xi))
+                _ops.pred_step_("dpmpp", pred, x2, eps2, cr, crm1, cx[i], c0[i], c1[i], hist=hist, w=guidance_scale,
+                                shape=_shape_rows(xi, eps2, i, T, shaping, w=guidance_scale, pred=pred), **_pred_kw(T, i))
+                xi.copy_(x2[:xi.shape[0]])
+                continue
             if max_log is not None:   # the 2C output, passed whole (guided: the pair, on the duplicated state)
                 if none is None:
                     _ops.strided_step_("dpmpp", xi, eps, cr, crm1, cx[i], c0[i], c1[i], hist=hist)
@@ -748,6 +823,7 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
     sigma = ddpm.ddim_sigma(eta) if eta != 0.0 else None
     shaping = _shaping_of(ddpm, guidance_scale is not None)
     max_log = _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)
+    pred = _pred_of(ddpm, tiling=tiling, feature_cache=feature_cache)
 
     @torch.no_grad()
     def sample(xT, condition=None):
@@ -771,7 +847,7 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
         for i in reversed(range(ddpm.Ns)):
             eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i)).float().contiguous()
             _check_width(eps.shape[1], xi, max_log, host_loop=True)
-            _ddim_move(eps, xi, i, T, sigma, noise, _shape_rows(xi, eps, i, T, shaping), wide=max_log is not None)
+            _ddim_move(eps, xi, i, T, sigma, noise, _shape_rows(xi, eps, i, T, shaping, pred=pred), wide=max_log is not None, pred=pred)
         return process_x0(xi)
 
     return sample

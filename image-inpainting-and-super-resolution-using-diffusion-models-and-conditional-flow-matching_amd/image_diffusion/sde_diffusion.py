@@ -119,6 +119,9 @@ class DDPM(nn.Module):
     learned_variance = False                 # set on the views of with_learned_variance
     time_scale = 1.0                         # from_betas: the net sees tau * time_scale / base_Ns
     _betas64 = None                          # from_betas / RespacedDDPM: the chain's betas before their rounding to fp32 (max_log)
+    prediction = "eps"                       # set on the views of with_prediction: what the net's output stands for ("eps", "x0", "v")
+    fixed_variance = "small"                 # set on the views of with_fixed_variance: "small" (the posterior variance) or "large" (beta)
+    _host_large = None
 
     def __init__(self, Ns: int):
         super().__init__()
@@ -188,13 +191,21 @@ class DDPM(nn.Module):
                          self._coef(self.sqrt_one_minus_alphas_cumprod, i, x_start)), noise
 
     def host_tables(self):
-        """CPU fp32 copies of the buffers (per-step scalars are passed to the kernels by value)."""
+        """CPU fp32 copies of the buffers (per-step scalars are passed to the kernels by value).  On a with_fixed_variance("large") view
+        posterior_log_variance_clipped[k], k >= 1, is max_log()[k] = log(betas[k]); entry 0 is the buffer's (step 0 draws no noise)."""
         if self._host is None:
             self._host = {n: getattr(self, n).detach().to("cpu", torch.float32).contiguous() for n in TABLE_NAMES}
-        return self._host
+        if self.fixed_variance != "large":
+            return self._host
+        if self._host_large is None:
+            large = self._host["posterior_log_variance_clipped"].clone()
+            large[1:] = self.max_log()[1:]
+            self.__dict__["_host_large"] = dict(self._host, posterior_log_variance_clipped=large)
+        return self._host_large
 
     def _apply(self, fn, *a, **k):
         self._host = None
+        self.__dict__["_host_large"] = None
         return super()._apply(fn, *a, **k)
 
     # ---- BUILD-DEFINED EXTENSION (no reference counterpart): sampling on a sub-sequence of the steps ----
@@ -244,6 +255,34 @@ class DDPM(nn.Module):
         Commutes with respace (the respaced chain's own betas) and with_x0_shaping.  Sample quality is untested."""
         view = self._view()
         view.__dict__["learned_variance"] = bool(learned)
+        return view
+
+    def with_prediction(self, prediction: str = "eps") -> "DDPM":
+        """BUILD-DEFINED EXTENSION (no reference counterpart): a view of this chain - the same buffers, the same steps - for a net whose output is
+        not the noise: "x0" (improved-DDPM / guided-diffusion's predict_xstart=True: the output is the data prediction itself) or "v" (Salimans &
+        Ho 2022: v = sqrt_alphas_cumprod eps - sqrt_one_minus_alphas_cumprod x0, so x0 = sqrt_alphas_cumprod x - sqrt_one_minus_alphas_cumprod v);
+        "eps": a view like the chain itself.  Every sampler forms the unclipped data prediction of the kind from the net's raw output and goes on
+        as it always did (the fused loops: mi355_ddpm_pred_sample); the bound takes x0_hat and the mse target from the kind.  Commutes with respace,
+        with_learned_variance (the net writes [prediction | variance channels]), with_x0_shaping and with_fixed_variance.  Not built for such a
+        chain: ReconstructionGuidance, tiling, the feature cache.  Sample quality is untested."""
+        if prediction not in ("eps", "x0", "v"):
+            raise ValueError(f'prediction must be "eps", "x0" or "v", got {prediction!r}')
+        view = self._view()
+        view.__dict__["prediction"] = prediction
+        return view
+
+    def with_fixed_variance(self, variance: str = "small") -> "DDPM":
+        """BUILD-DEFINED EXTENSION (no reference counterpart): a view of this chain whose ancestral steps draw with the fixed "large" variance
+        beta_k (guided-diffusion's sigma_small=False, its default for nets without learn_sigma) instead of the posterior variance ("small": a view
+        like the chain itself): host_tables()["posterior_log_variance_clipped"][k] is log(betas[k]) of the chain's own betas for k >= 1, in fp64
+        and rounded once (max_log()); entry 0 stays, step 0 draws no noise.  Host only: the kernels read the table they are given.  get_vlb_fn
+        picks "fixed_large" on such a chain.  Commutes with respace (the respaced chain's own betas) and the other views; a learned-variance chain
+        ignores nothing silently: the samplers refuse the pair."""
+        if variance not in ("small", "large"):
+            raise ValueError(f'variance must be "small" or "large", got {variance!r}')
+        view = self._view()
+        view.__dict__["fixed_variance"] = variance
+        view.__dict__["_host_large"] = None
         return view
 
     def max_log(self) -> torch.Tensor:
@@ -428,6 +467,8 @@ class RespacedDDPM(DDPM):
         self.tiling = getattr(base, "tiling", None)
         self.learned_variance = bool(getattr(base, "learned_variance", False))   # max_log() is then log of the betas recomputed below
         self.time_scale = float(getattr(base, "time_scale", 1.0))
+        self.prediction = getattr(base, "prediction", "eps")
+        self.fixed_variance = getattr(base, "fixed_variance", "small")   # "large": log of the betas recomputed below
         acp32 = base.alphas_cumprod.detach().to("cpu", torch.float32)[list(steps)]
         if not bool(torch.all(torch.isfinite(acp32) & (acp32 > 0))):
             raise ValueError("the base's alphas_cumprod is not finite and positive at every kept step (DDPM(Ns <= 20) is not respaced)")

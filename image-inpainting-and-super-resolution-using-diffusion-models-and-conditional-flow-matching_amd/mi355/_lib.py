@@ -123,6 +123,23 @@ class DDPMVarianceC(C.Structure):
     _fields_ = [("learned", C.c_int32), ("max_log", _FP), ("times", _FP)]
 
 
+class DDPMPredictionC(C.Structure):
+    """mi355_ddpm_prediction (include/mi355_sampler.h): what the net's output stands for - 0 eps, 1 x0, 2 v."""
+    _fields_ = [("kind", C.c_int32)]
+
+
+PREDICTIONS = {"eps": 0, "x0": 1, "v": 2}   # DDPM.prediction -> mi355_ddpm_prediction::kind
+
+
+def prediction_kind(prediction) -> int:
+    """None or a name of PREDICTIONS -> the kind number; anything else: ValueError."""
+    if prediction is None:
+        return 0
+    if prediction not in PREDICTIONS:
+        raise ValueError(f'prediction must be one of "eps", "x0", "v", got {prediction!r}')
+    return PREDICTIONS[prediction]
+
+
 class VLBOptionsC(C.Structure):
     """mi355_vlb_options (include/mi355_sampler.h): the variance mode, the CDF, the log-variance tables and the times of a variational-bound call."""
     _fields_ = [("learned", C.c_int32), ("cdf", C.c_int32), ("clip_denoised", C.c_int32), ("true_log", _FP), ("model_log", _FP), ("min_log", _FP),
@@ -272,6 +289,16 @@ SIGNATURES = {
     "mi355_q_sample": (_I, [_VP, _VP, _VP, _F, _F, _I, _U64, _U64, _I64, _VP]),
     "mi355_vlb_terms": (_I, [_VP, _VP, _VP, _I64, _VP, _I, _U64, _U64, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _VP, _I64, _I, _I64, _VP]),
     "mi355_vlb_prior": (_I, [_VP, _F, _F, _VP, _I64, _I, _VP, _I, _I64, _VP]),
+    "mi355_ddpm_pred_workspace_bytes": (_I64, [_VP, _I, _I, _I]),
+    "mi355_ddpm_pred_sample": (_I, [_VP, _VP, _I, _VP, _VP, _I, _I, _F, _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC), C.POINTER(DDPMScheduleC),
+                                    C.POINTER(MultistepScheduleC), C.POINTER(DDPMVarianceC), C.POINTER(X0ShapingC), C.POINTER(DDPMPredictionC), _VP, _I64,
+                                    _I, _VP, _I64, _VP]),
+    "mi355_ddpm_vlb_pred": (_I, [_VP, _VP, _I, _VP, _VP, C.POINTER(DDPMTablesC), C.POINTER(VLBOptionsC), C.POINTER(DDPMPredictionC), _VP, _I64, _VP, _VP,
+                                 _I, _VP, _I64, _VP]),
+    "mi355_pred_step": (_I, [_I, _I, _VP, _VP, _I64, _VP, _VP, _I, _F, _VP, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _U64, _U64, _VP, _I64, _VP]),
+    "mi355_pred_shape_stats": (_I, [_I, _VP, _VP, _F, _VP, _I, _F, _F, _F, _F, C.POINTER(X0ShapingC), _VP, _VP, _I, _I64, _VP]),
+    "mi355_vlb_terms_pred": (_I, [_VP, _VP, _VP, _I64, _VP, _I, _U64, _U64, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _F, _F, _VP, _I64, _I, _I64,
+                                  _VP]),
     "mi355_cfm_ab_workspace_bytes": (_I64, [_VP, _I, _I, _I, _I]),
     "mi355_cfm_ab_sample": (_I, [_VP, _VP, _I, _VP, _I, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_cfm_ab_cfg_sample": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _I, _F, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),

@@ -827,9 +827,11 @@ class UNetEngine:
     def ddpm_sample(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], *, mode: int, cond: Optional[torch.Tensor] = None,
                     noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0,
                     noise_condition=True, pad_value=-2.0, none_value=-2.0, seed=0, guidance_scale=None, cache_interval=None, cache_branch=None,
-                    cache_schedule=None, tiling=None, y: Optional[torch.Tensor] = None, null_label: Optional[int] = None, timesteps=None,
-                    train_steps=None, ddim_sigma=None, walk=None):
+                    cache_schedule=None, tiling=None, prediction=None, y: Optional[torch.Tensor] = None, null_label: Optional[int] = None,
+                    timesteps=None, train_steps=None, ddim_sigma=None, walk=None):
         """In-place reverse-denoising loop.  tables: name -> CPU fp32 tensor [Ns] (DDPM buffers).
+        prediction (None or "eps": every path below, untouched; "x0", "v"): what the net's output stands for; such a call runs through ddpm_pred
+        (mi355_ddpm_pred_sample).  Not with tiling or cache_*.
         tiling (None: every path below, untouched; an object or dict with stride, weight, chunk): x, cond and the injected noise are canvases
         [.., C, Hc, Wc] with Hc, Wc >= image_size; every evaluation runs the net on overlapping windows and blends the eps predictions, the step
         arithmetic is the loop's own on the canvas (mi355_ddpm_sample_tiled).  Not with guidance_scale or cache_*.
@@ -844,6 +846,14 @@ class UNetEngine:
         (mi355_ddpm_cfg_sample; Amortized mode, or DDIM with a condition, on a 2C-input net), eps_u from the none_value-filled condition and, with
         y (class labels [B]), null_label (default: the last class).  A batch beyond cfg_batch() runs in slices (Philox: seed + slice index)."""
         B = x.shape[0]
+        if _lib.prediction_kind(prediction) != 0:
+            for what, v in (("tiling", tiling), ("cache_interval", cache_interval), ("cache_branch", cache_branch), ("cache_schedule", cache_schedule)):
+                if v is not None:
+                    raise NotImplementedError(f"{what} is not built for an x0- or v-prediction net (prediction={prediction!r})")
+            return self.ddpm_pred(x, tables, prediction, mode=mode, cond=cond, noise=noise, n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax,
+                                  start_fraction=start_fraction, noise_condition=noise_condition, pad_value=pad_value, none_value=none_value, seed=seed,
+                                  guidance_scale=guidance_scale, y=y, null_label=null_label, timesteps=timesteps, train_steps=train_steps,
+                                  ddim_sigma=ddim_sigma, walk=walk)
         if cond is not None and cond.shape != x.shape:
             raise ValueError("condition must have the shape of x")
         if guidance_scale is None and y is not None:
@@ -973,10 +983,37 @@ class UNetEngine:
                                     guidance_scale=guidance_scale, y=y, null_label=null_label, timesteps=timesteps, train_steps=train_steps,
                                     ddim_sigma=ddim_sigma, walk=walk, coefs=coefs)
 
+    def ddpm_pred(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], prediction, *, mode: int, shaping=None, max_log=None, times=None,
+                  cond: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0,
+                  start_fraction=1.0, noise_condition=True, pad_value=-2.0, none_value=-2.0, seed=0, guidance_scale=None,
+                  y: Optional[torch.Tensor] = None, null_label: Optional[int] = None, timesteps=None, train_steps=None, ddim_sigma=None, walk=None,
+                  coefs=None):
+        """In-place DDPM sampling of a net whose output is "eps", "x0" or "v" (mi355_ddpm_pred_sample): every step forms the data prediction of
+        the kind from the net's raw output and goes on as ddpm_sample / ddpm_multistep (coefs), ddpm_shaped (shaping) and ddpm_learned (max_log,
+        times) do; "eps" gives their bits.  shaping together with max_log is refused by the library."""
+        K = int(tables["alphas_cumprod_prev"].numel())
+        keep = []
+        var = _lib.DDPMVarianceC(0, None, None)
+        for name, v in (("max_log", max_log), ("times", times)):
+            if v is None:
+                continue
+            t = torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").contiguous()
+            if t.numel() != K:
+                raise ValueError(f"{name} must have one entry per row of the tables")
+            keep.append(t)
+            setattr(var, name, C.cast(t.data_ptr(), C.POINTER(C.c_float)))
+        var.learned = int(max_log is not None)
+        extra = (var if keep else None, _lib.x0_shaping(shaping), _lib.DDPMPredictionC(_lib.prediction_kind(prediction)))
+        return self._ddpm_one_entry("ddpm_pred", "mi355_ddpm_pred_sample", "mi355_ddpm_pred_workspace_bytes", extra, keep, x, tables, mode=mode,
+                                    cond=cond, noise=noise, n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, start_fraction=start_fraction,
+                                    noise_condition=noise_condition, pad_value=pad_value, none_value=none_value, seed=seed,
+                                    guidance_scale=guidance_scale, y=y, null_label=null_label, timesteps=timesteps, train_steps=train_steps,
+                                    ddim_sigma=ddim_sigma, walk=walk, coefs=coefs)
+
     def _ddpm_one_entry(self, who, entry, ws_fn, extra, keep_extra, x, tables, *, mode, cond, noise, n_corrector, delta, tmin, tmax, start_fraction,
                         noise_condition, pad_value, none_value, seed, guidance_scale, y, null_label, timesteps, train_steps, ddim_sigma, walk, coefs):
-        """The entry points that sit over the six DDPM loops (mi355_ddpm_shaped_sample, mi355_ddpm_lv_sample): one argument list, with the entry
-        point's own struct `extra` (or None) between the schedules and the noise."""
+        """The entry points that sit over the six DDPM loops (mi355_ddpm_shaped_sample, mi355_ddpm_lv_sample, mi355_ddpm_pred_sample): one argument
+        list, with the entry point's own struct `extra` (or None; a tuple: several, in order) between the schedules and the noise."""
         B = x.shape[0]
         if cond is not None and cond.shape != x.shape:
             raise ValueError("condition must have the shape of x")
@@ -1016,21 +1053,24 @@ class UNetEngine:
             a = self._ddpm_args(xs, cn, ls, nl, w, wl)
             check(getattr(self.L, entry)(self.handle, *a[:5], int(guided), *a[5:], C.byref(tb), C.byref(opt),
                                          C.byref(sched[0]) if sched is not None else None, C.byref(ms) if ms is not None else None,
-                                         C.byref(extra) if extra is not None else None, *self._noise_args(nz), xs.shape[0], ws, wsb, self._stream()),
+                                         *(C.byref(e) if e is not None else None for e in (extra if isinstance(extra, tuple) else (extra,))),
+                                         *self._noise_args(nz), xs.shape[0], ws, wsb, self._stream()),
                   entry)
         del keep
         return x
 
     def ddpm_vlb(self, x0: torch.Tensor, tables: Dict[str, torch.Tensor], logs: Dict[str, torch.Tensor], *, learned: bool, times=None,
                  cond: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, seed=None, cdf="exact",
-                 clip_denoised=True, none_value=-2.0):
+                 clip_denoised=True, none_value=-2.0, prediction=None):
         """The variational bound of the engine's net on data x0 [B, C, H, W] in [-1, 1] (mi355_ddpm_vlb): all K steps of the chain `tables`
         describes in ONE library call per batch.  logs: the [K] log-variance tables of DDPM.vlb_log_variances - "true_log", and "model_log"
         (fixed variance) or "min_log" and "max_log" (learned: the net writes twice x0's channels).  times ([K] floats, or None: k / K): the time
         the net sees at step k.  cond: the condition of a 2C-input net (None: such a net sees none_value).  noise: [K, B, C, H, W] injected draws
         (draw j belongs to step K-1-j), or None: device Philox at `seed`.  cdf: "exact" or "tanh".
         -> (terms [B, K, 3] = vb, xstart_mse, mse per step; summary [B, 2] = prior_bpd, total_bpd).  A batch beyond max_batch() runs in slices
-        (Philox: seed + slice)."""
+        (Philox: seed + slice).  prediction (None or "eps": mi355_ddpm_vlb; "x0", "v": mi355_ddpm_vlb_pred): what the net's output stands for -
+        x0_hat comes from it, and the third term is the squared error against the kind's training target."""
+        pred = _lib.DDPMPredictionC(_lib.prediction_kind(prediction))
         if x0.dim() != 4:
             raise ValueError("x0 must be [B, C, H, W]")
         if cond is not None and cond.shape != x0.shape:
@@ -1064,9 +1104,11 @@ class UNetEngine:
             tm, sm = (terms, summary) if whole else (torch.empty(hi - lo, K, 3, device=self.device), torch.empty(hi - lo, 2, device=self.device))
             opt.seed = (seed + i) % 2 ** 64
             ws, wsb = self._workspace_sized("mi355_ddpm_vlb_workspace_bytes", hi - lo)
-            check(self.L.mi355_ddpm_vlb(self.handle, self._chk(xs, "x0"), xs.shape[1], self._chk(cn, "condition") if cn is not None else None,
-                                        C.c_void_p(ls.data_ptr()) if ls is not None else None, C.byref(tb), C.byref(opt), *self._noise_args(nz), self._chk(tm, "terms"),
-                                        self._chk(sm, "summary"), hi - lo, ws, wsb, self._stream()), "mi355_ddpm_vlb")
+            name = "mi355_ddpm_vlb" if pred.kind == 0 else "mi355_ddpm_vlb_pred"
+            check(getattr(self.L, name)(self.handle, self._chk(xs, "x0"), xs.shape[1], self._chk(cn, "condition") if cn is not None else None,
+                                        C.c_void_p(ls.data_ptr()) if ls is not None else None, C.byref(tb), C.byref(opt),
+                                        *(() if pred.kind == 0 else (C.byref(pred),)), *self._noise_args(nz), self._chk(tm, "terms"),
+                                        self._chk(sm, "summary"), hi - lo, ws, wsb, self._stream()), name)
             if not whole:
                 terms[lo:hi], summary[lo:hi] = tm, sm
         del keep

@@ -291,6 +291,51 @@ class Ops:
                                             B, _stream()), "mi355_ddpm_lv_step")
         return x
 
+    _PRED_STEP_KINDS = dict(_STRIDED_KINDS, ddpm_lv=5)
+
+    def pred_step_(self, kind, prediction, x, out, c_recip, c_recipm1, a, b=0.0, c=0.0, sigma=0.0, *, sa=0.0, sb=0.0, min_log=0.0, max_log=0.0, z=None,
+                   philox=None, hist=None, w=None, shape=None):
+        """One step in place on the raw output `out` of a net of the given prediction ("eps", "x0" or "v"; mi355_pred_step): the data prediction
+        is x0_pre of the kind - c_recip x - c_recipm1 out; out itself; sa x - sb out (sa, sb = sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod of
+        the step) - and the step goes on from it as x0_shaped_step_ (kind "ddpm", "ddim", "ddim_eta", "dpmpp"; shape: its rows or None),
+        strided_step_ (out [B, Cw >= C, ...] read in place; kind "corrector": a, b, c = rsm1, dt, delta) and ddpm_lv_step_ (kind "ddpm_lv": a, b =
+        coef1, coef2; min_log, max_log; out [B, 2C, ...]) do.  w: the guided form, x and out [2B, ...].  -> x"""
+        guided = w is not None
+        B, per, stride = self._wide_out(x, out, guided)
+        n = B * per
+        if kind == "ddpm_lv" and stride != 2 * per:
+            raise ValueError(f"a learned-variance net writes twice the state's channels, got {tuple(out.shape)} for the state {tuple(x.shape)}")
+        for t, name in ((z, "z"), (hist, "hist")):
+            if t is not None and t.numel() != n:
+                raise ValueError(f"{name} must have the B-image state's size")
+        if shape is not None and tuple(shape.shape) != (B, 2):
+            raise ValueError(f"shape must be [{B}, 2], got {tuple(shape.shape)}")
+        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_pred_step(self._PRED_STEP_KINDS[kind], _lib.prediction_kind(prediction), _req(x, "x"), _req(out, "out"),
+                                         0 if stride == per else stride, _opt(z, "z"), _opt(hist, "hist"), int(guided), wf, wp, per, float(c_recip),
+                                         float(c_recipm1), float(sa), float(sb), float(a), float(b), float(c), float(sigma), float(min_log),
+                                         float(max_log), int(philox is not None and z is None), seed, off, _opt(shape, "shape"), n, _stream()),
+              "mi355_pred_step")
+        return x
+
+    def pred_shape_stats(self, prediction, x, out, c_recip, c_recipm1, shaping, *, sa=0.0, sb=0.0, w=None, detail=False):
+        """x0_shape_stats on the raw output of a net of the given prediction (mi355_pred_shape_stats): s is the threshold of |x0_pre| of the kind
+        (see pred_step_), f the rescale factor of the raw output.  With "x0", x is not read (it only gives the shape).  -> shape, or (shape, detail)"""
+        B = x.shape[0]
+        guided = w is not None
+        if tuple(out.shape) != ((2 * B if guided else B),) + tuple(x.shape[1:]):
+            raise ValueError(f"out {tuple(out.shape)} must be x's shape {tuple(x.shape)}" + (" with twice the leading size" if guided else ""))
+        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
+        sh = _lib.x0_shaping(shaping)
+        shape = torch.empty(B, 2, device=x.device, dtype=torch.float32)
+        det = torch.empty(B, 4, device=x.device, dtype=torch.float32) if detail else None
+        check(_lib.lib().mi355_pred_shape_stats(_lib.prediction_kind(prediction), _req(x, "x"), _req(out, "out"), wf, wp, int(guided), float(c_recip),
+                                                float(c_recipm1), float(sa), float(sb), C.byref(sh) if sh is not None else None, _req(shape, "shape"),
+                                                _req(det, "detail") if detail else None, B, x.numel() // B if B else 1, _stream()),
+              "mi355_pred_shape_stats")
+        return (shape, det) if detail else shape
+
     def q_sample(self, x0, a, b, z=None, philox=None, out=None):
         """The forward marginal q(x_k | x_0) out of place (mi355_q_sample): a x0 + b z with a = sqrt_alphas_cumprod[k], b =
         sqrt_one_minus_alphas_cumprod[k], two rounded products and a sum; z / philox as in ddpm_step_.  x0 is left as it is.  -> out"""
@@ -304,11 +349,13 @@ class Ops:
         return out
 
     def vlb_terms(self, x0, x_k, out, *, c_recip, c_recipm1, coef1, coef2, true_log, model_log=0.0, min_log=0.0, max_log=0.0, k_is_zero, learned,
-                  cdf="exact", clip_denoised=True, z=None, philox=None, dst=None):
+                  cdf="exact", clip_denoised=True, z=None, philox=None, dst=None, prediction=None, sa=0.0, sb=0.0):
         """One step of the variational bound (mi355_vlb_terms): x0, x_k [B, C, ...], out [B, C or more, ...] the network output (eps in channels
         [0, C); learned: v in [C, 2C), read in place), the step's draw z (or philox = (seed, offset): regenerated) -> float32 [B, 3] = vb (bits/dim:
         the KL of step k > 0, the discretised decoder's NLL with k_is_zero), xstart_mse, mse.  cdf: "exact" (erfc) or "tanh" (guided-diffusion's
-        approximation).  dst: a [B, 3] view to write into (its row stride may be wider: a [B, K, 3] tensor's [:, k])."""
+        approximation).  dst: a [B, 3] view to write into (its row stride may be wider: a [B, K, 3] tensor's [:, k]).  prediction (None: "eps",
+        mi355_vlb_terms itself; "x0", "v": mi355_vlb_terms_pred with sa, sb = sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod of the step):
+        x0_hat comes from x0_pre of the kind and mse is taken against the kind's training target (z; x0; sa z - sb x0)."""
         _same(x0, x_k, "x0", "x_k")
         B, per, stride = self._wide_out(x0, out, False)
         if learned and stride < 2 * per:
@@ -322,6 +369,14 @@ class Ops:
         if not dst.is_cuda or dst.dtype != torch.float32 or dst.shape != (B, 3) or (B and dst.stride(1) != 1):
             raise ValueError("dst must be a float32 device view of shape [B, 3] with unit inner stride")
         seed, off = philox if philox else (0, 0)
+        if prediction is not None:
+            check(_lib.lib().mi355_vlb_terms_pred(_req(x0, "x0"), _req(x_k, "x_k"), _req(out, "out"), stride, _opt(z, "z"),
+                                                  int(philox is not None and z is None), seed, off, float(c_recip), float(c_recipm1), float(coef1),
+                                                  float(coef2), float(true_log), float(model_log), float(min_log), float(max_log), int(bool(k_is_zero)),
+                                                  int(bool(learned)), int(cdf == "tanh"), int(bool(clip_denoised)), _lib.prediction_kind(prediction),
+                                                  float(sa), float(sb), C.c_void_p(dst.data_ptr()), dst.stride(0) if B > 1 else 3, B, per, _stream()),
+                  "mi355_vlb_terms_pred")
+            return dst
         check(_lib.lib().mi355_vlb_terms(_req(x0, "x0"), _req(x_k, "x_k"), _req(out, "out"), stride, _opt(z, "z"), int(philox is not None and z is None),
                                          seed, off, float(c_recip), float(c_recipm1), float(coef1), float(coef2), float(true_log), float(model_log),
                                          float(min_log), float(max_log), int(bool(k_is_zero)), int(bool(learned)), int(cdf == "tanh"),

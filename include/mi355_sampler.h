@@ -62,7 +62,9 @@ extern "C" {
  * mi355_tile_gather, mi355_tile_labels, mi355_tile_blend, mi355_unet_forward_tiled, mi355_cfm_euler_sample_tiled, mi355_ddpm_sample_tiled (new
  * symbols and one new struct only); then learned-variance DDPM nets and caller-given evaluation times: mi355_ddpm_lv_workspace_bytes,
  * mi355_ddpm_lv_sample, mi355_ddpm_lv_step, mi355_strided_step (new symbols and one new struct only); then the variational bound of a DDPM net:
- * mi355_ddpm_vlb_workspace_bytes, mi355_ddpm_vlb, mi355_q_sample, mi355_vlb_terms, mi355_vlb_prior (new symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
+ * mi355_ddpm_vlb_workspace_bytes, mi355_ddpm_vlb, mi355_q_sample, mi355_vlb_terms, mi355_vlb_prior (new symbols and one new struct only); then x0-
+ * and v-prediction DDPM nets: mi355_ddpm_pred_workspace_bytes, mi355_ddpm_pred_sample, mi355_ddpm_vlb_pred, mi355_pred_step, mi355_pred_shape_stats,
+ * mi355_vlb_terms_pred (new symbols and one new struct only).  107: the GroupNorm test ops mi355_gn_affine, mi355_conv2d_gn,
  * mi355_affine_pool, mi355_gn_silu_vjp and mi355_grad_gather (each launches one of the network's own GroupNorm kernels); later additions to 107: mi355_rk_stage, mi355_cfm_rk_workspace_bytes and
  * mi355_cfm_rk_sample (the fixed-step explicit Runge-Kutta CFM samplers: midpoint, Heun, RK4); then classifier-free guidance: mi355_cfg_workspace_bytes,
  * mi355_cfm_cfg_sample, mi355_ddpm_cfg_workspace_bytes, mi355_ddpm_cfg_sample and the ops mi355_cfg_stage, mi355_ddpm_cfg_step, mi355_ddim_cfg_step (new
@@ -741,6 +743,62 @@ int mi355_vlb_terms(const float* x0, const float* x_k, const float* out, int64_t
                     int learned, int cdf, int clip_denoised, float* dst, int64_t dst_stride, int batch, int64_t elems_per_image, void* stream);
 int mi355_vlb_prior(const float* x0, float sqrt_acp_last, float sqrt_one_minus_acp_last, const float* terms, int64_t terms_stride, int n_steps,
                     float* summary, int batch, int64_t elems_per_image, void* stream);
+
+/* x0- and v-prediction DDPM nets (improved-DDPM / guided-diffusion's predict_xstart = True; v-prediction: Salimans & Ho 2022).  No reference
+ * counterpart (the reference's nets predict eps).  A chain has a prediction kind: 0 eps (every entry point above), 1 x0, 2 v.  Let out be the network
+ * output for the state x at step i - under classifier-free guidance the guided mix out_u + w (out_c - out_u) of the raw outputs, under guidance rescale
+ * then scaled by f_b, the two standard deviations taken over the raw outputs.  The unclipped data prediction is, every operation rounded to fp32 and
+ * none contracted,
+ *   kind 0 (eps): x0_pre = c_recip x - c_recipm1 out            (product, product, difference: as everywhere above)
+ *   kind 1 (x0) : x0_pre = out                                  (no arithmetic; x is not read for it)
+ *   kind 2 (v)  : x0_pre = sa x - sb out,  sa = tables->sqrt_alphas_cumprod[i], sb = tables->sqrt_one_minus_alphas_cumprod[i]
+ *                                                               (product, product, difference; a respaced chain's own values)
+ * and everything behind x0_pre is unchanged: the static clip or the per-image (f, s) shaping (the quantile is that of |x0_pre| of the kind), the
+ * posterior mean, DDIM's e2 = (c_recip x - x0_hat) / c_recipm1, the DPM-Solver++ data prediction and its history, the corrector's score_from_x0, the
+ * learned-variance step (the net writes [pred | variance channels]), the replacement paste, RePaint walks, the draw numbering, the Philox offsets and
+ * the final clip.  The kind is resolved at compile time inside the step kernels: no launch and no pass over memory is added.
+ * In the bound (fp64 per element on the widened fp32 values): x0_hat from x0_pre of the kind; mse[b, k] = mean((out - target)^2) with target = z_k
+ * (eps), x0 (x0), sa[k] z_k - sb[k] x0 (v) - the training target of guided-diffusion's training_losses; xstart_mse and vb follow from x0_hat.
+ * Sample quality and bits/dim are untested (no trained checkpoint is at hand); the arithmetic is tested against an fp64 restatement.
+ * Out of scope: guided-diffusion's PREVIOUS_X mean type and LEARNED (direct log-variance) variance type; tiled and cached loops; reconstruction
+ * guidance; the CFM samplers; training.
+ *
+ * mi355_ddpm_pred_sample: ONE entry point over the six DDPM loops: the arguments of mi355_ddpm_lv_sample, then shaping (as in
+ * mi355_ddpm_shaped_sample) and pred.  pred NULL or kind 0: the loop the other arguments choose, bit-identical to mi355_ddpm_lv_sample (shaping off)
+ * resp. mi355_ddpm_shaped_sample (var NULL).  workspace: mi355_ddpm_pred_workspace_bytes(net, batch, guided, multistep).  After the call
+ * mi355_unet_get_stats reports what those entry points report.  Errors beyond theirs, MI355_ERR_ARG before any launch, each naming its argument:
+ * pred->kind outside 0..2; kind 2 without the two tables; var->learned together with shaping switched on.
+ * mi355_ddpm_vlb_pred: mi355_ddpm_vlb with pred (NULL or kind 0: the same bits).  A kind outside 0..2 is refused before any launch; every other
+ * refusal is mi355_ddpm_vlb's own, under its name.
+ * mi355_pred_step: one step as an op, a superset of mi355_x0_shaped_step, mi355_strided_step and mi355_ddpm_lv_step.  kind 0..3: as
+ * mi355_x0_shaped_step; 4: the Langevin corrector (a, b, c = recip_sqrt_m1, dt, delta; guided must be 0, shape NULL); 5: the learned-variance
+ * ancestral step (a, b = coef1, coef2; min_log, max_log; out_stride >= 2 * elems_per_image).  out: the network output, image b at out + b *
+ * out_stride (0: contiguous, = elems_per_image); shaping rows need the contiguous read.  pred_kind 0: the bits of those ops.  sa, sb are read by
+ * pred_kind 2 alone.
+ * mi355_pred_shape_stats: mi355_x0_shape_stats for a prediction kind; with pred_kind 1, x is not read and may be NULL.
+ * mi355_vlb_terms_pred: mi355_vlb_terms for a prediction kind. */
+typedef struct mi355_ddpm_prediction {
+  int32_t kind;   /* 0 eps, 1 x0, 2 v */
+} mi355_ddpm_prediction;
+int64_t mi355_ddpm_pred_workspace_bytes(const mi355_unet* net, int batch, int guided, int multistep);
+int mi355_ddpm_pred_sample(mi355_unet* net, float* x, int channels, const float* cond, const int32_t* labels, int null_label, int guided, float w,
+                           const float* w_dev, const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                           const mi355_multistep_schedule* msched, const mi355_ddpm_variance* var, const mi355_x0_shaping* shaping,
+                           const mi355_ddpm_prediction* pred, const float* noise, int64_t n_noise_draws, int batch, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+int mi355_ddpm_vlb_pred(mi355_unet* net, const float* x0, int channels, const float* cond, const int32_t* labels, const mi355_ddpm_tables* tables,
+                        const mi355_vlb_options* opt, const mi355_ddpm_prediction* pred, const float* noise, int64_t n_noise_draws,
+                        float* out_terms /* [B][K][3] */, float* summary /* [B][2] */, int batch, void* workspace, int64_t workspace_bytes, void* stream);
+int mi355_pred_step(int kind, int pred_kind, float* x, const float* out, int64_t out_stride, const float* z, float* hist, int guided, float w,
+                    const float* w_dev, int64_t elems_per_image, float c_recip, float c_recipm1, float sa, float sb, float a, float b, float c, float sigma,
+                    float min_log, float max_log, int use_philox, uint64_t seed, uint64_t offset, const float* shape, int64_t n, void* stream);
+int mi355_pred_shape_stats(int pred_kind, const float* x, const float* out, float w, const float* w_dev, int guided, float c_recip, float c_recipm1,
+                           float sa, float sb, const mi355_x0_shaping* shaping, float* shape, float* detail, int batch, int64_t elems_per_image,
+                           void* stream);
+int mi355_vlb_terms_pred(const float* x0, const float* x_k, const float* out, int64_t out_stride, const float* z, int use_philox, uint64_t seed,
+                         uint64_t offset, float c_recip, float c_recipm1, float coef1, float coef2, float true_log, float model_log, float min_log,
+                         float max_log, int k_is_zero, int learned, int cdf, int clip_denoised, int pred_kind, float sa, float sb, float* dst,
+                         int64_t dst_stride, int batch, int64_t elems_per_image, void* stream);
 
 /* Adams-Bashforth CFM samplers of order q = 2, 3, 4 (no reference counterpart): one evaluation per step from step q - 1 on,
  *   x_{k+1} = x_k + sum_{j<q} w_host[k * q + j] * v_{k-j},   v_k = model(t_k, x_k),

@@ -232,6 +232,39 @@ const StepCase step_cases[] = {
     {"x0_shape_stats | quantile 2", "quantile", [] { const mi355_x0_shaping sh{2.f, 0.f, 0.f}; return mi355_x0_shape_stats(X, E, 0.f, nullptr, 0, 1.f, 1.f, &sh, SHP, nullptr, 2, 32, nullptr); }},
     {"x0_shape_stats | null shape", "shape is null", [] { const mi355_x0_shaping sh{0.9f, 0.f, 0.f}; return mi355_x0_shape_stats(X, E, 0.f, nullptr, 0, 1.f, 1.f, &sh, nullptr, nullptr, 2, 32, nullptr); }},
     {"x0_shape_stats | batch 0", "batch must be", [] { const mi355_x0_shaping sh{0.9f, 0.f, 0.f}; return mi355_x0_shape_stats(X, E, 0.f, nullptr, 0, 1.f, 1.f, &sh, SHP, nullptr, 0, 32, nullptr); }},
+    // x0- and v-prediction nets: the ops that take the kind, and the two entry points' refusals that need no handle
+    {"pred_step | kind 6", "kind must be", [] { return mi355_pred_step(6, 1, X, E, 0, nullptr, H, 0, 0.f, nullptr, 32, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 0.f, -3.f, -1.f, 1, 7, 0, nullptr, 64, nullptr); }},
+    {"pred_step | pred_kind 3", "pred_kind must be", [] { return mi355_pred_step(1, 3, X, E, 0, nullptr, H, 0, 0.f, nullptr, 32, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 0.f, -3.f, -1.f, 1, 7, 0, nullptr, 64, nullptr); }},
+    {"pred_step | pred_kind -1, corrector", "pred_kind must be", [] { return mi355_pred_step(4, -1, X, E, 0, nullptr, H, 0, 0.f, nullptr, 32, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 0.f, -3.f, -1.f, 1, 7, 0, nullptr, 64, nullptr); }},
+    {"pred_step | part images", "whole images", [] { return mi355_pred_step(0, 2, X, E, 0, nullptr, H, 0, 0.f, nullptr, 48, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 0.f, -3.f, -1.f, 1, 7, 0, nullptr, 64, nullptr); }},
+    {"pred_step | out_stride under elems_per_image", "out_stride", [] { return mi355_pred_step(1, 2, X, E, 8, nullptr, H, 0, 0.f, nullptr, 32, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 0.f, -3.f, -1.f, 1, 7, 0, nullptr, 64, nullptr); }},
+    {"pred_step | guided corrector", "no guided form", [] { return mi355_pred_step(4, 2, X, E, 0, nullptr, H, 1, 2.f, nullptr, 32, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 0.f, -3.f, -1.f, 1, 7, 0, nullptr, 64, nullptr); }},
+    {"pred_step | shaped corrector", "static clip", [] { return mi355_pred_step(4, 1, X, E, 0, nullptr, H, 0, 0.f, nullptr, 32, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 0.f, -3.f, -1.f, 1, 7, 0, SHP, 64, nullptr); }},
+    {"pred_step | v, ancestral, offset 2", "Philox offset", [] { return mi355_pred_step(0, 2, X, E, 0, nullptr, H, 0, 0.f, nullptr, 32, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 1.f, -3.f, -1.f, 1, 7, 2, nullptr, 64, nullptr); }},
+    {"pred_step | x0, learned variance on a narrow output", "variance channels sit behind", [] { return mi355_pred_step(5, 1, X, E, 32, nullptr, H, 0, 0.f, nullptr, 32, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 0.f, -3.f, -1.f, 1, 7, 0, nullptr, 64, nullptr); }},
+    {"pred_step | v, shaped on a strided output", "strided eps", [] { return mi355_pred_step(1, 2, X, E, 64, nullptr, H, 0, 0.f, nullptr, 32, 1.f, 1.f, .8f, .6f, .5f, 0.f, 0.f, 0.f, -3.f, -1.f, 0, 0, 0, SHP, 64, nullptr); }},
+    {"pred_step | x0, guided DPM-Solver++, null out", "null argument", [] { return mi355_pred_step(3, 1, X, nullptr, 0, nullptr, H, 1, 2.f, nullptr, 32, 1.f, 1.f, .8f, .6f, 1.f, 1.f, 0.f, 0.f, -3.f, -1.f, 0, 0, 0, nullptr, 64, nullptr); }},
+    {"pred_shape_stats | pred_kind 3", "prediction kind must be", [] { const mi355_x0_shaping sh{0.9f, 0.f, 0.f}; return mi355_pred_shape_stats(3, X, E, 0.f, nullptr, 0, 1.f, 1.f, .8f, .6f, &sh, SHP, nullptr, 2, 32, nullptr); }},
+    {"pred_shape_stats | v, null x", "x is null", [] { const mi355_x0_shaping sh{0.9f, 0.f, 0.f}; return mi355_pred_shape_stats(2, nullptr, E, 0.f, nullptr, 0, 1.f, 1.f, .8f, .6f, &sh, SHP, nullptr, 2, 32, nullptr); }},
+    {"pred_shape_stats | x0, null x, null shape", "shape is null", [] { const mi355_x0_shaping sh{0.9f, 0.f, 0.f}; return mi355_pred_shape_stats(1, nullptr, E, 0.f, nullptr, 0, 1.f, 1.f, .8f, .6f, &sh, nullptr, nullptr, 2, 32, nullptr); }},
+    {"vlb_terms_pred | pred_kind 3", "prediction kind must be", [] { return mi355_vlb_terms_pred(X, X, E, 32, nullptr, 1, 7, 0, 1.f, 1.f, .5f, .5f, -3.f, -3.f, -3.f, -1.f, 0, 0, 0, 1, 3, .8f, .6f, SHP, 3, 2, 32, nullptr); }},
+    {"vlb_terms_pred | v, sb not finite", "sa and sb must be finite", [] { return mi355_vlb_terms_pred(X, X, E, 32, nullptr, 1, 7, 0, 1.f, 1.f, .5f, .5f, -3.f, -3.f, -3.f, -1.f, 0, 0, 0, 1, 2, .8f, __builtin_nanf(""), SHP, 3, 2, 32, nullptr); }},
+    {"vlb_terms_pred | x0, no draw", "the step's draw is needed", [] { return mi355_vlb_terms_pred(X, X, E, 32, nullptr, 0, 7, 0, 1.f, 1.f, .5f, .5f, -3.f, -3.f, -3.f, -1.f, 0, 0, 0, 1, 1, .8f, .6f, SHP, 3, 2, 32, nullptr); }},
+    {"ddpm_pred_sample | pred->kind 3", "pred->kind must be", [] { float t[K] = {1.f, 1.f, 1.f, 1.f}; const mi355_ddpm_tables tb{K, t, t, t, t, t, t, t, t, t}; const mi355_ddpm_options o{};
+       const mi355_ddpm_prediction p{3}; return mi355_ddpm_pred_sample(nullptr, X, 3, nullptr, nullptr, 0, 0, 0.f, nullptr, &tb, &o, nullptr, nullptr, nullptr, nullptr, &p, nullptr, 0, 2, H, 1 << 20, nullptr); }},
+    {"ddpm_pred_sample | v without its tables", "needs tables->sqrt_alphas_cumprod", [] { float t[K] = {1.f, 1.f, 1.f, 1.f}; const mi355_ddpm_tables tb{K, t, t, t, t, t, nullptr, t, t, t};
+       const mi355_ddpm_options o{}; const mi355_ddpm_prediction p{2};
+       return mi355_ddpm_pred_sample(nullptr, X, 3, nullptr, nullptr, 0, 0, 0.f, nullptr, &tb, &o, nullptr, nullptr, nullptr, nullptr, &p, nullptr, 0, 2, H, 1 << 20, nullptr); }},
+    {"ddpm_pred_sample | x0, learned variance with shaping", "var->learned together with shaping", [] { float t[K] = {1.f, 1.f, 1.f, 1.f}; const mi355_ddpm_tables tb{K, t, t, t, t, t, t, t, t, t};
+       const mi355_ddpm_options o{}; const mi355_ddpm_prediction p{1}; const mi355_ddpm_variance v{1, t, nullptr}; const mi355_x0_shaping sh{0.9f, 0.f, 0.f};
+       return mi355_ddpm_pred_sample(nullptr, X, 3, nullptr, nullptr, 0, 0, 0.f, nullptr, &tb, &o, nullptr, nullptr, &v, &sh, &p, nullptr, 0, 2, H, 1 << 20, nullptr); }},
+    {"ddpm_pred_sample | v, no handle", "bad argument (net, x, workspace, batch)", [] { float t[K] = {1.f, 1.f, 1.f, 1.f}; const mi355_ddpm_tables tb{K, t, t, t, t, t, t, t, t, t};
+       const mi355_ddpm_options o{}; const mi355_ddpm_prediction p{2};
+       return mi355_ddpm_pred_sample(nullptr, X, 3, nullptr, nullptr, 0, 0, 0.f, nullptr, &tb, &o, nullptr, nullptr, nullptr, nullptr, &p, nullptr, 0, 2, H, 1 << 20, nullptr); }},
+    {"ddpm_vlb_pred | pred->kind -1", "pred->kind must be", [] { float t[K] = {1.f, 1.f, 1.f, 1.f}; const mi355_ddpm_tables tb{K, t, t, t, t, t, t, t, t, t}; const mi355_ddpm_prediction p{-1};
+       return mi355_ddpm_vlb_pred(nullptr, X, 3, nullptr, nullptr, &tb, nullptr, &p, nullptr, 0, E, H, 2, SHP, 1 << 20, nullptr); }},
+    {"ddpm_vlb_pred | v, opt null", "opt is null", [] { float t[K] = {1.f, 1.f, 1.f, 1.f}; const mi355_ddpm_tables tb{K, t, t, t, t, t, t, t, t, t}; const mi355_ddpm_prediction p{2};
+       return mi355_ddpm_vlb_pred(nullptr, X, 3, nullptr, nullptr, &tb, nullptr, &p, nullptr, 0, E, H, 2, SHP, 1 << 20, nullptr); }},
 };
 
 // the text of the refusal just made says one of the |-separated alternatives
