@@ -36,8 +36,22 @@ def _slices(B: int, mb: int):
         yield lo, hi, (lo, hi) == (0, B)
 
 
-def _cut(t, lo: int, hi: int):
-    return None if t is None else t[lo:hi]
+def _lab_ptr(lab):
+    """The pointer of the int32 labels _labels() made (or a slice of them), or None."""
+    return C.c_void_p(lab.data_ptr()) if lab is not None else None
+
+
+def _host_floats(v, K=None, name=None, per="row of the tables"):
+    """Host floats for the library -> (what to pass as const float*, what must stay alive over the call).  K None: a sequence of numbers, as a
+    ctypes array (len() gives its length).  K given: a [K] table (tensor, array or list) as a pointer into its CPU fp32 copy; another length is
+    the ValueError "`name` must have one entry per `per`"."""
+    if K is None:
+        arr = (C.c_float * len(v))(*[float(f) for f in v])
+        return arr, arr
+    t = torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").contiguous()
+    if t.numel() != K:
+        raise ValueError(f"{name} must have one entry per {per}")
+    return C.cast(t.data_ptr(), C.POINTER(C.c_float)), t
 
 
 def _tableau_arrays(tableau):
@@ -184,6 +198,25 @@ class UNetEngine:
             raise TypeError(f"{name} must be contiguous {dtype}")
         return C.c_void_p(t.data_ptr())
 
+    def _ptr(self, t, name: str, dtype=torch.float32):
+        """_chk of an operand that may be None."""
+        return self._chk(t, name, dtype) if t is not None else None
+
+    @staticmethod
+    def _sliced(B: int, mb: int, rows=(), cols=(), outs=(), seed=None):
+        """A batch of B run at most mb images at a time: yields per slice (its size, rows, cols, outs, its seed), every operand a tensor or None.
+        A slice that is the caller's batch itself gets the caller's own tensors.  rows [B, ...] are cut [lo:hi]: views the call reads and writes
+        in place.  cols [n, B, ...] are inputs, cut [:, lo:hi] and made contiguous.  outs [n, B, ...] are outputs: the slice gets a buffer of its
+        own, copied into [:, lo:hi] once the caller is done with the slice.  seed: None, or the Philox seed of the batch: the slice draws from
+        (seed + slice index) % 2**64."""
+        for i, (lo, hi, whole) in enumerate(_slices(B, mb)):
+            bufs = [t if whole or t is None else t.new_empty((t.shape[0], hi - lo) + tuple(t.shape[2:])) for t in outs]
+            yield (hi - lo, [t if whole or t is None else t[lo:hi] for t in rows],
+                   [t if whole or t is None else t[:, lo:hi].contiguous() for t in cols], bufs, None if seed is None else (seed + i) % 2 ** 64)
+            for t, buf in zip(outs, bufs):
+                if t is not None and not whole:
+                    t[:, lo:hi] = buf
+
     def _labels(self, y, B: int):
         """Class labels -> contiguous int32 [B] on the engine's device (ctypes pointer, tensor kept alive by the caller), or (None, None)."""
         if y is None:
@@ -253,7 +286,7 @@ class UNetEngine:
             out = torch.empty(B, self.out_channels, x.shape[2], x.shape[3], device=self.device, dtype=torch.float32)
         self._fwd_state = None
         ws, wsb = self._workspace_tiled(B, plan)
-        check(self.L.mi355_unet_forward_tiled(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc,
+        check(self.L.mi355_unet_forward_tiled(self.handle, self._chk(x, "x"), Cx, self._ptr(cond, "condition"), Cc,
                                               float(t), lab_p, self._chk(out, "out"), B, C.byref(plan), ws, wsb, self._stream()),
               "mi355_unet_forward_tiled")
         return out
@@ -315,13 +348,13 @@ class UNetEngine:
         if out is None:
             out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
         host_t = isinstance(t, (int, float))
-        for lo, hi, whole in _slices(B, mb):
-            x2 = torch.cat((x[lo:hi], x[lo:hi]))
-            c2 = torch.cat((cond[lo:hi], torch.full_like(cond[lo:hi], float(none_value)))) if cond is not None else None
-            y2 = torch.cat((lab[lo:hi], torch.full_like(lab[lo:hi], nl))) if lab is not None else None
-            t2 = t if host_t else torch.cat((t[lo:hi], t[lo:hi]))
+        for _, (xs, cs, ls, ws_, ts, os_), _, _, _ in self._sliced(B, mb, rows=(x, cond, lab, wt, None if host_t else t, out)):
+            x2 = torch.cat((xs, xs))
+            c2 = torch.cat((cs, torch.full_like(cs, float(none_value)))) if cond is not None else None
+            y2 = torch.cat((ls, torch.full_like(ls, nl))) if lab is not None else None
+            t2 = t if host_t else torch.cat((ts, ts))
             v2 = self.forward(x2, t2, cond=c2, y=y2)
-            default_ops.cfg_combine(v2, w if wt is None else wt[lo:hi], out=out if whole else out[lo:hi])
+            default_ops.cfg_combine(v2, w if wt is None else ws_, out=os_)
         self._fwd_state = None
         return out
 
@@ -342,7 +375,7 @@ class UNetEngine:
         if out is None:
             out = torch.empty(B, self.out_channels, self.image_size, self.image_size, device=self.device, dtype=torch.float32)
         ws, wsb = self.workspace(B)
-        xp, cp = self._chk(x, "x"), self._chk(cond, "condition") if cond is not None else None
+        xp, cp = self._chk(x, "x"), self._ptr(cond, "condition")
         tp, op = None if host_t else self._chk(t, "timesteps"), self._chk(out, "out")
         if lab is not None:
             check(self.L.mi355_unet_forward_labels(self.handle, xp, Cx, cp, Cc, tp, float(t) if host_t else 0.0, lab_p, op, B, ws, wsb, self._stream()),
@@ -386,7 +419,7 @@ class UNetEngine:
         if branch and self._full_state != state:
             raise MI355BackendError("forward_cached: this engine's workspace does not hold a full evaluation at this batch (run forward() or "
                                     "forward_cached(branch=0) first; any other call that runs the net, or another batch, discards it)")
-        xp, cp = self._chk(x, "x"), self._chk(cond, "condition") if cond is not None else None
+        xp, cp = self._chk(x, "x"), self._ptr(cond, "condition")
         tp, op = None if host_t else self._chk(t, "timesteps"), self._chk(out, "out")
         self._fwd_state = None
         check(self.L.mi355_unet_forward_cached(self.handle, xp, Cx, cp, Cc, tp, float(t) if host_t else 0.0, lab_p, op, B, ws, wsb, self._stream(),
@@ -447,7 +480,7 @@ class UNetEngine:
         ws, wsb = self.workspace(B)
         cap = 4096
         recs = (_lib.OpProfileC * cap)()
-        n = check(self.L.mi355_unet_profile(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
+        n = check(self.L.mi355_unet_profile(self.handle, self._chk(x, "x"), Cx, self._ptr(cond, "condition"),
                                             Cc, self._chk(t, "timesteps"), self._chk(out, "out"), B, ws, wsb, self._stream(), recs, cap),
                   "mi355_unet_profile")
         names = {0: "prelude", 1: "gn_stats", 2: "conv", 3: "attention", 4: "resample"}
@@ -492,28 +525,32 @@ class UNetEngine:
         w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
         ts = [float(v) for v in t_span]
         traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
-        for lo, hi, whole in _slices(B, self.cfg_batch()):
-            xs = x if whole else x[lo:hi]
-            tr = traj if whole else self._traj_u8(xs, len(ts), keep_traj, False)[0]
-            us = u8 if whole else _cut(u8, lo, hi)
-            self._cfm_cfg_call(xs, ts, (a, b, c), _cut(cond, lo, hi), _cut(lab, lo, hi), nl, w, _cut(wt, lo, hi), float(none_value), tr, us)
-            if traj is not None and not whole:
-                traj[:, lo:hi] = tr
+        for _, (xs, cs, ls, wl, us), _, (tr,), _ in self._sliced(B, self.cfg_batch(), rows=(x, cond, lab, wt, u8), outs=(traj,)):
+            self._cfm_cfg_call(xs, ts, (a, b, c), cs, ls, nl, w, wl, float(none_value), tr, us)
         return x, traj, u8
 
     def _cfm_cfg_call(self, x, ts, tableau, cond, lab, null_label, w, wt, none_value, traj, u8):
         """One mi355_cfm_cfg_sample call (a batch within cfg_batch())."""
-        stages, a_arr, b_arr, c_arr = _tableau_arrays(tableau)
+        tab = _tableau_arrays(tableau)
         B, Cx, Cc = self._split(x, cond)
-        arr = (C.c_float * len(ts))(*ts)
         self._fwd_state = None
-        ws, wsb = self._workspace_sized("mi355_cfg_workspace_bytes", B, stages)
-        check(self.L.mi355_cfm_cfg_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc,
-                                          none_value, C.c_void_p(lab.data_ptr()) if lab is not None else None, int(null_label), float(w),
-                                          self._chk(wt, "guidance_scale") if wt is not None else None, arr, len(ts), stages, a_arr, b_arr, c_arr,
-                                          self._chk(traj, "traj") if traj is not None else None,
-                                          self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
-              "mi355_cfm_cfg_sample")
+        ws, wsb = self._workspace_sized("mi355_cfg_workspace_bytes", B, tab[0])
+        check(self.L.mi355_cfm_cfg_sample(*self._flow_args(x, Cx, cond, Cc, lab, (none_value, null_label, w, wt)),
+                                          *self._fixed_step_args(_host_floats(ts)[0], tab, traj, u8, B, ws, wsb)), "mi355_cfm_cfg_sample")
+
+    def _flow_args(self, x, Cx, cond, Cc, lab, guide=None):
+        """What the flow samplers' calls start with: handle, x, Cx, cond, Cc, labels; a guided call (guide = (none_value, null_label, w, per-image
+        scales or None)) has none_value before the labels and the rest behind them."""
+        head = (self.handle, self._chk(x, "x"), Cx, self._ptr(cond, "condition"), Cc)
+        if guide is None:
+            return head + (_lab_ptr(lab),)
+        none_value, null_label, w, wt = guide
+        return head + (none_value, _lab_ptr(lab), int(null_label), float(w), self._ptr(wt, "guidance_scale"))
+
+    def _fixed_step_args(self, arr, tab, traj, u8, B, ws, wsb, ab=()):
+        """What the fixed-step samplers' calls end with: the times, [ab: the Adams-Bashforth order and weights,] the tableau (tab: _tableau_arrays),
+        the optional outputs, the batch, the workspace and the stream."""
+        return (arr, len(arr), *ab, *tab, self._ptr(traj, "traj"), self._ptr(u8, "u8", torch.uint8), B, ws, wsb, self._stream())
 
     def cfm_euler(self, x: torch.Tensor, t_span: Sequence[float], cond: Optional[torch.Tensor] = None, keep_traj: bool = False,
                   want_u8: bool = False, cond_drift: bool = False, y: Optional[torch.Tensor] = None, guidance_scale=None,
@@ -545,45 +582,26 @@ class UNetEngine:
                 raise NotImplementedError("cond_drift (the drifting condition of the concatenated-state sampler) is not built with guidance")
             return self.cfm_cfg(x, t_span, "euler", cond, y, guidance_scale, null_label, none_value, keep_traj, want_u8)
         B, Cx, Cc = self._split(x, cond)
-        lab, lab_p = self._labels(y, B)
-        mb = self.max_batch()
-        traj, u8 = self._traj_u8(x, len(t_span), keep_traj, want_u8)
-        if B > mb:
-            drifts = []
-            for lo, hi, _ in _slices(B, mb):
-                r = self.cfm_euler(x[lo:hi], t_span, _cut(cond, lo, hi), keep_traj, want_u8, cond_drift, _cut(lab, lo, hi),
-                                   cache_interval=cache_interval, cache_branch=cache_branch, cache_schedule=cache_schedule, cache_drift=cache_drift)
-                if traj is not None:
-                    traj[:, lo:hi] = r[1]
-                if u8 is not None:
-                    u8[lo:hi] = r[2]
-                drifts.append(r[3] if cache_drift else None)
-            return (x, traj, u8, torch.cat(drifts, dim=1)) if cache_drift else (x, traj, u8)
-        ts = [float(v) for v in t_span]
-        arr = (C.c_float * len(ts))(*ts)
-        self._fwd_state = None
-        ws, wsb = self.workspace(B)
-        if cache is not None:
-            drift = torch.empty(len(cache[1]), B, device=self.device, dtype=torch.float32) if cache_drift else None
+        lab, _ = self._labels(y, B)
+        arr, _ = _host_floats(t_span)
+        traj, u8 = self._traj_u8(x, len(arr), keep_traj, want_u8)
+        drift = torch.empty(len(cache[1]), B, device=self.device, dtype=torch.float32) if cache_drift else None
+        name = "mi355_cfm_euler_sample" + ("_cached" if cache is not None else "_labels" if lab is not None else "")
+        for n, (xs, cs, ls, us), _, (tr, dr), _ in self._sliced(B, self.max_batch(), rows=(x, cond, lab, u8), outs=(traj, drift)):
+            self._fwd_state = None
+            ws, wsb = self.workspace(n)
             if cache_drift:
-                ws, wsb = self._workspace_sized("mi355_feature_cache_workspace_bytes", B, cache[0], 1)
-            fc = _lib.feature_cache(*cache, drift_ptr=drift.data_ptr() if drift is not None and drift.numel() else None)
-            check(self.L.mi355_cfm_euler_sample_cached(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                                       Cc, int(bool(cond_drift)), lab_p, arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
-                                                       self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream(),
-                                                       C.byref(fc)), "mi355_cfm_euler_sample_cached")
-            return (x, traj, u8, drift) if cache_drift else (x, traj, u8)
-        if lab is not None:
-            check(self.L.mi355_cfm_euler_sample_labels(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                                       Cc, int(bool(cond_drift)), lab_p, arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
-                                                       self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
-                  "mi355_cfm_euler_sample_labels")
-            return x, traj, u8
-        check(self.L.mi355_cfm_euler_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None,
-                                            Cc, int(bool(cond_drift)), arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
-                                            self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
-              "mi355_cfm_euler_sample")
-        return x, traj, u8
+                ws, wsb = self._workspace_sized("mi355_feature_cache_workspace_bytes", n, cache[0], 1)
+            fc = () if cache is None else (_lib.feature_cache(*cache, drift_ptr=dr.data_ptr() if dr is not None and dr.numel() else None),)
+            self._euler_call(name, xs, Cx, cs, Cc, cond_drift, ls, arr, tr, us, n, ws, wsb, *fc)
+        return (x, traj, u8, drift) if cache_drift else (x, traj, u8)
+
+    def _euler_call(self, name, x, Cx, cond, Cc, cond_drift, lab, arr, traj, u8, B, ws, wsb, *last):
+        """One call of the Euler entry point `name`; all but the plain one take labels, and _cached / _tiled end in their struct (last)."""
+        labels = () if name == "mi355_cfm_euler_sample" else (_lab_ptr(lab),)
+        check(getattr(self.L, name)(self.handle, self._chk(x, "x"), Cx, self._ptr(cond, "condition"), Cc, int(bool(cond_drift)), *labels, arr, len(arr),
+                                    self._ptr(traj, "traj"), self._ptr(u8, "u8", torch.uint8), B, ws, wsb, self._stream(),
+                                    *(C.byref(s) for s in last)), name)
 
     @staticmethod
     def _tiling_refusals(others: dict):
@@ -595,16 +613,12 @@ class UNetEngine:
     def _cfm_euler_tiled(self, x, t_span, cond, keep_traj, want_u8, y, tiling, others):
         self._tiling_refusals(others)
         B, Cx, Cc, plan = self._tiled(tiling, x, cond)
-        lab, lab_p = self._labels(y, B)
-        ts = [float(v) for v in t_span]
-        arr = (C.c_float * len(ts))(*ts)
-        traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
+        lab, _ = self._labels(y, B)
+        arr, _ = _host_floats(t_span)
+        traj, u8 = self._traj_u8(x, len(arr), keep_traj, want_u8)
         self._fwd_state = None
         ws, wsb = self._workspace_tiled(B, plan)
-        check(self.L.mi355_cfm_euler_sample_tiled(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc, 0,
-                                                  lab_p, arr, len(ts), self._chk(traj, "traj") if traj is not None else None,
-                                                  self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream(),
-                                                  C.byref(plan)), "mi355_cfm_euler_sample_tiled")
+        self._euler_call("mi355_cfm_euler_sample_tiled", x, Cx, cond, Cc, False, lab, arr, traj, u8, B, ws, wsb, plan)
         return x, traj, u8
 
     def _workspace_rk(self, batch: int, stages: int):
@@ -628,26 +642,15 @@ class UNetEngine:
 
         tableau = resolve_tableau(method)
         B, Cx, Cc = self._split(x, cond)
-        lab, lab_p = self._labels(y, B)
-        mb = self.max_batch()
-        ts = [float(v) for v in t_span]
-        traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
-        if B > mb:
-            for lo, hi, _ in _slices(B, mb):
-                _, tr, u = self.cfm_rk(x[lo:hi], ts, tableau, _cut(cond, lo, hi), keep_traj, want_u8, _cut(lab, lo, hi))
-                if traj is not None:
-                    traj[:, lo:hi] = tr
-                if u8 is not None:
-                    u8[lo:hi] = u
-            return x, traj, u8
-        arr = (C.c_float * len(ts))(*ts)
-        stages, a_arr, b_arr, c_arr = _tableau_arrays(tableau)
-        self._fwd_state = None
-        ws, wsb = self._workspace_rk(B, stages)
-        check(self.L.mi355_cfm_rk_sample(self.handle, self._chk(x, "x"), Cx, self._chk(cond, "condition") if cond is not None else None, Cc, lab_p,
-                                         arr, len(ts), stages, a_arr, b_arr, c_arr, self._chk(traj, "traj") if traj is not None else None,
-                                         self._chk(u8, "u8", torch.uint8) if u8 is not None else None, B, ws, wsb, self._stream()),
-              "mi355_cfm_rk_sample")
+        lab, _ = self._labels(y, B)
+        arr, _ = _host_floats(t_span)
+        traj, u8 = self._traj_u8(x, len(arr), keep_traj, want_u8)
+        tab = _tableau_arrays(tableau)
+        for n, (xs, cs, ls, us), _, (tr,), _ in self._sliced(B, self.max_batch(), rows=(x, cond, lab, u8), outs=(traj,)):
+            self._fwd_state = None
+            ws, wsb = self._workspace_rk(n, tab[0])
+            check(self.L.mi355_cfm_rk_sample(*self._flow_args(xs, Cx, cs, Cc, ls), *self._fixed_step_args(arr, tab, tr, us, n, ws, wsb)),
+                  "mi355_cfm_rk_sample")
         return x, traj, u8
 
     def cfm_ab(self, x: torch.Tensor, t_span: Sequence[float], method="ab2", cond: Optional[torch.Tensor] = None, keep_traj: bool = False,
@@ -674,28 +677,16 @@ class UNetEngine:
         ts = [float(v) for v in t_span]
         weights = ab_weights(ts, order).contiguous()   # CPU fp32 [n_steps, order]
         traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
-        stages, a_arr, b_arr, c_arr = _tableau_arrays(tableau)
-        arr = (C.c_float * len(ts))(*ts)
+        tab = _tableau_arrays(tableau)
+        arr, _ = _host_floats(ts)
         wp = C.cast(weights.data_ptr(), C.POINTER(C.c_float)) if weights.numel() else (C.c_float * 1)()
-        for lo, hi, whole in _slices(B, self.cfg_batch() if guided else self.max_batch()):
-            xs = x if whole else x[lo:hi]
-            tr = traj if whole else self._traj_u8(xs, len(ts), keep_traj, False)[0]
-            us = u8 if whole else _cut(u8, lo, hi)
-            cs, ls = _cut(cond, lo, hi), _cut(lab, lo, hi)
+        name = "mi355_cfm_ab_cfg_sample" if guided else "mi355_cfm_ab_sample"
+        mb = self.cfg_batch() if guided else self.max_batch()
+        for n, (xs, cs, ls, wl, us), _, (tr,), _ in self._sliced(B, mb, rows=(x, cond, lab, wt, u8), outs=(traj,)):
             self._fwd_state = None
-            ws, wsb = self._workspace_sized("mi355_cfm_ab_workspace_bytes", hi - lo, order, stages, int(guided))
-            common = (arr, len(ts), order, wp, stages, a_arr, b_arr, c_arr, self._chk(tr, "traj") if tr is not None else None,
-                      self._chk(us, "u8", torch.uint8) if us is not None else None, hi - lo, ws, wsb, self._stream())
-            if guided:
-                check(self.L.mi355_cfm_ab_cfg_sample(self.handle, self._chk(xs, "x"), Cx, self._chk(cs, "condition") if cs is not None else None, Cc,
-                                                     float(none_value), C.c_void_p(ls.data_ptr()) if ls is not None else None, int(nl), float(w),
-                                                     self._chk(_cut(wt, lo, hi), "guidance_scale") if wt is not None else None, *common),
-                      "mi355_cfm_ab_cfg_sample")
-            else:
-                check(self.L.mi355_cfm_ab_sample(self.handle, self._chk(xs, "x"), Cx, self._chk(cs, "condition") if cs is not None else None, Cc,
-                                                 C.c_void_p(ls.data_ptr()) if ls is not None else None, *common), "mi355_cfm_ab_sample")
-            if traj is not None and not whole:
-                traj[:, lo:hi] = tr
+            ws, wsb = self._workspace_sized("mi355_cfm_ab_workspace_bytes", n, order, tab[0], int(guided))
+            check(getattr(self.L, name)(*self._flow_args(xs, Cx, cs, Cc, ls, (float(none_value), nl, w, wl) if guided else None),
+                                        *self._fixed_step_args(arr, tab, tr, us, n, ws, wsb, ab=(order, wp))), name)
         return x, traj, u8
 
     def cfm_recon(self, x: torch.Tensor, t_span: Sequence[float], y: Optional[torch.Tensor], mode: int, *, scales: Optional[Sequence[float]] = None,
@@ -746,33 +737,21 @@ class UNetEngine:
         lab, _ = self._labels(y_labels, B)
         traj, u8 = self._traj_u8(x, len(ts), keep_traj, want_u8)
         loss = torch.empty(max(n_steps, 0), B, device=self.device, dtype=torch.float32) if return_loss else None
-        for i, (lo, hi, whole) in enumerate(_slices(B, self.max_batch())):
-            xs = x if whole else x[lo:hi]
-            tr = traj if whole else self._traj_u8(xs, len(ts), keep_traj, False)[0]
-            ls = loss if whole or loss is None else torch.empty(n_steps, hi - lo, device=self.device, dtype=torch.float32)
-            self._cfm_recon_call(xs, ts, y if whole or y is None else y[lo:hi].contiguous(), int(mode), sc, rep, bool(final_paste), float(pad_value),
-                                 noise if whole or noise is None else noise[:, lo:hi].contiguous(), (int(seed or 0) + i) % 2 ** 64,
-                                 _cut(lab, lo, hi), tr, u8 if whole else _cut(u8, lo, hi), ls, hl, wl)
-            if not whole:
-                if traj is not None:
-                    traj[:, lo:hi] = tr
-                if loss is not None:
-                    loss[:, lo:hi] = ls
+        for _, (xs, ys, ls, us), (nz,), (tr, lo), sd in self._sliced(B, self.max_batch(), rows=(x, y, lab, u8), cols=(noise,), outs=(traj, loss),
+                                                                     seed=int(seed or 0)):
+            self._cfm_recon_call(xs, ts, ys, int(mode), sc, rep, bool(final_paste), float(pad_value), nz, sd, ls, tr, us, lo, hl, wl)
         return x, traj, u8, loss
 
     def _cfm_recon_call(self, x, ts, y, mode, scales, rep, final_paste, pad_value, noise, seed, lab, traj, u8, loss, hl, wl):
         """One mi355_cfm_recon_sample call (a batch within max_batch())."""
         B, Cx = x.shape[:2]
-        arr = (C.c_float * len(ts))(*ts)
+        arr, _ = _host_floats(ts)
         sarr = (C.c_float * max(1, len(ts) - 1))(*scales) if scales is not None else None
         self._fwd_state = None
         ws, wsb = self._workspace_sized("mi355_cfm_recon_workspace_bytes", B, hl, wl)
-        check(self.L.mi355_cfm_recon_sample(self.handle, self._chk(x, "x"), Cx, C.c_void_p(lab.data_ptr()) if lab is not None else None, arr, len(ts),
-                                            self._chk(y, "y") if y is not None else None, mode, pad_value, hl, wl, sarr, rep, int(final_paste),
-                                            self._chk(noise, "noise") if noise is not None else None, seed,
-                                            self._chk(traj, "traj") if traj is not None else None,
-                                            self._chk(u8, "u8", torch.uint8) if u8 is not None else None,
-                                            self._chk(loss, "loss") if loss is not None else None, B, ws, wsb, self._stream()),
+        check(self.L.mi355_cfm_recon_sample(self.handle, self._chk(x, "x"), Cx, _lab_ptr(lab), arr, len(ts), self._ptr(y, "y"), mode, pad_value, hl, wl,
+                                            sarr, rep, int(final_paste), self._ptr(noise, "noise"), seed, self._ptr(traj, "traj"),
+                                            self._ptr(u8, "u8", torch.uint8), self._ptr(loss, "loss"), B, ws, wsb, self._stream()),
               "mi355_cfm_recon_sample")
 
     def sf2m_euler(self, score_engine: "UNetEngine", x: torch.Tensor, t_grid: Sequence[float], sigma: float, reverse: bool = False,
@@ -798,30 +777,20 @@ class UNetEngine:
         if dW is None and seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         lab_eng = self if self.num_classes else score_engine   # the net without num_classes is refused by the library (both must be conditional)
-        lab, lab_p = lab_eng._labels(y, B)
+        lab, _ = lab_eng._labels(y, B)
         mb = min(self.max_batch(), score_engine.max_batch())
         traj = self._traj_u8(x, len(outs), bool(outs), False)[0]
-        if B > mb:
-            for i, (lo, hi, _) in enumerate(_slices(B, mb)):
-                xs = x[lo:hi].contiguous()
-                _, tr = self.sf2m_euler(score_engine, xs, ts, sigma, reverse, _cut(lab, lo, hi),
-                                        dW[:, lo:hi].contiguous() if dW is not None else None,
-                                        None if dW is not None else (seed + i) % 2 ** 64, outs)
-                x[lo:hi] = xs
-                if traj is not None:
-                    traj[:, lo:hi] = tr
-            return x, traj
-        grid = (C.c_float * len(ts))(*ts)
+        grid, _ = _host_floats(ts)
         osteps = (C.c_int32 * max(1, len(outs)))(*[k for k, _ in outs])
         ows = (C.c_float * max(1, len(outs)))(*[w for _, w in outs])
-        self._fwd_state = None
-        score_engine._fwd_state = None
-        ws_d, wsb_d = self.workspace(B)
-        ws_s, wsb_s = score_engine.workspace(B)
-        check(self.L.mi355_sf2m_euler_sample(self.handle, score_engine.handle, self._chk(x, "x"), Cx, lab_p, grid, n, float(sigma), int(bool(reverse)),
-                                             self._chk(dW, "dW") if dW is not None else None, int(seed or 0) % 2 ** 64, osteps, ows, len(outs),
-                                             self._chk(traj, "traj") if traj is not None else None, B, ws_d, wsb_d, ws_s, wsb_s, self._stream()),
-              "mi355_sf2m_euler_sample")
+        for nb, (xs, ls), (dw,), (tr,), sd in self._sliced(B, mb, rows=(x, lab), cols=(dW,), outs=(traj,), seed=seed if dW is None else None):
+            self._fwd_state = None
+            score_engine._fwd_state = None
+            ws_d, wsb_d = self.workspace(nb)
+            ws_s, wsb_s = score_engine.workspace(nb)
+            check(self.L.mi355_sf2m_euler_sample(self.handle, score_engine.handle, self._chk(xs, "x"), Cx, _lab_ptr(ls), grid, n, float(sigma),
+                                                 int(bool(reverse)), self._ptr(dw, "dW"), int(sd or 0) % 2 ** 64, osteps, ows, len(outs),
+                                                 self._ptr(tr, "traj"), nb, ws_d, wsb_d, ws_s, wsb_s, self._stream()), "mi355_sf2m_euler_sample")
         return x, traj
 
     def ddpm_sample(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], *, mode: int, cond: Optional[torch.Tensor] = None,
@@ -874,28 +843,23 @@ class UNetEngine:
                 raise NotImplementedError("guidance is built for the amortized sampler and for DDIM with a condition (prior and replacement are refused)")
             lab, _ = self._labels(y, B)
             w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
-            for xs, cn, nz, ls, wl, sd in self._guided_slices(x, cond, noise, lab, wt, seed, self.cfg_batch()):
+            for _, (xs, cn, ls, wl), (nz,), _, sd in self._sliced(B, self.cfg_batch(), rows=(x, cond, lab, wt), cols=(noise,), seed=seed):
                 self._ddpm_cfg_call(xs, tables, mode, cn, ls, nl, w, wl, nz,
                                     dict(n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, none_value=none_value, seed=sd),
                                     **({} if sched is None else {"sched": sched}))
             return x
         tb, keep = self._ddpm_tables(tables)
         self._fwd_state = None
-        opt = _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value,
-                                int(cond is None), seed)
+        opt = self._ddpm_options(mode, cond, seed, none_value, n_corrector, delta, tmin, tmax, start_fraction, noise_condition, pad_value)
         if tiling is not None:
             plan = self._tiled(tiling, x, None, channels=False)[3]
             ws, wsb = self._workspace_tiled(B, plan)
-            check(self.L.mi355_ddpm_sample_tiled(self.handle, *self._ddpm_args(x, cond), C.byref(tb), C.byref(opt),
-                                                 C.byref(sched[0]) if sched is not None else None, *self._noise_args(noise), B, ws, wsb, self._stream(),
-                                                 C.byref(plan)), "mi355_ddpm_sample_tiled")
-            del keep
-            return x
-        name = "mi355_ddpm_sample" if sched is None else "mi355_ddpm_sample_sched" if cache is None else "mi355_ddpm_sample_sched_cached"
-        fc = _lib.feature_cache(*cache) if cache is not None else None
-        ws, wsb = self.workspace(B)
-        check(getattr(self.L, name)(self.handle, *self._ddpm_args(x, cond), C.byref(tb), C.byref(opt), *(() if sched is None else (C.byref(sched[0]),)),
-                                    *self._noise_args(noise), B, ws, wsb, self._stream(), *(() if fc is None else (C.byref(fc),))), name)
+            name, mid, last = "mi355_ddpm_sample_tiled", (None if sched is None else sched[0],), (plan,)
+        else:
+            name = "mi355_ddpm_sample" if sched is None else "mi355_ddpm_sample_sched" if cache is None else "mi355_ddpm_sample_sched_cached"
+            ws, wsb = self.workspace(B)
+            mid, last = () if sched is None else (sched[0],), () if cache is None else (_lib.feature_cache(*cache),)
+        self._ddpm_call(name, x, cond, tb, opt, B, ws, wsb, mid=mid, noise=self._noise_args(noise), last=last)
         del keep
         return x
 
@@ -925,19 +889,13 @@ class UNetEngine:
         if len(cs) != 3 or any(c.numel() != K for c in cs):
             raise ValueError("coefs must be (cx, c0, c1), one entry per step each")
         ms, keep_ms = self._multistep_schedule(tb, cs, steps, train_steps)
-        opt = _lib.DDPMOptionsC(_lib.DDIM, 0, 0.1, 1e-5, 1.0, 1.0, 1, -2.0, float(none_value), int(cond is None), 0)
-        self._fwd_state = None
-        if guidance_scale is None:
-            ws, wsb = self._workspace_sized("mi355_ddpm_multistep_workspace_bytes", B, 0)
-            check(self.L.mi355_ddpm_multistep_sample(self.handle, *self._ddpm_args(x, cond), C.byref(tb), C.byref(opt), C.byref(ms), B, ws, wsb,
-                                                     self._stream()), "mi355_ddpm_multistep_sample")
-            return x
-        lab, _ = self._labels(y, B)
-        w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
-        for xs, cn, _, ls, wl, _ in self._guided_slices(x, cond, None, lab, wt, 0, self.cfg_batch()):
-            ws, wsb = self._workspace_sized("mi355_ddpm_multistep_workspace_bytes", xs.shape[0], 1)
-            check(self.L.mi355_ddpm_multistep_cfg_sample(self.handle, *self._ddpm_args(xs, cn, ls, nl, w, wl), C.byref(tb), C.byref(opt), C.byref(ms),
-                                                         xs.shape[0], ws, wsb, self._stream()), "mi355_ddpm_multistep_cfg_sample")
+        opt = self._ddpm_options(_lib.DDIM, cond, 0, float(none_value))
+        name, guide, mb = "mi355_ddpm_multistep_sample", None, B   # (the unguided call does not slice)
+        if guidance_scale is not None:
+            lab, _ = self._labels(y, B)
+            w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
+            name, guide, mb = "mi355_ddpm_multistep_cfg_sample", (lab, nl, w, wt), self.cfg_batch()
+        self._ddpm_loop(name, "mi355_ddpm_multistep_workspace_bytes", (int(guide is not None),), mb, x, cond, None, tb, opt, guide=guide, mid=(ms,))
         del keep, keep_ms
         return x
 
@@ -949,12 +907,8 @@ class UNetEngine:
         thresholding and guidance rescale.  shaping: DDPM.x0_shaping, a (quantile, max_threshold, rescale_phi) triple, or None (the unshaped
         loop, bit for bit).  coefs None: the arguments and the loops of ddpm_sample; coefs = (cx, c0, c1): those of ddpm_multistep (mode must
         be DDIM; no noise).  guidance_scale not None: the guided loops; a batch beyond cfg_batch() runs in slices (Philox: seed + slice)."""
-        sh = _lib.x0_shaping(shaping)
-        return self._ddpm_one_entry("ddpm_shaped", "mi355_ddpm_shaped_sample", "mi355_ddpm_shaped_workspace_bytes", sh, [], x, tables, mode=mode,
-                                    cond=cond, noise=noise, n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, start_fraction=start_fraction,
-                                    noise_condition=noise_condition, pad_value=pad_value, none_value=none_value, seed=seed,
-                                    guidance_scale=guidance_scale, y=y, null_label=null_label, timesteps=timesteps, train_steps=train_steps,
-                                    ddim_sigma=ddim_sigma, walk=walk, coefs=coefs)
+        loop = {k: v for k, v in locals().items() if k not in ("self", "shaping")}   # x, tables and the keywords the three entry points share
+        return self._ddpm_one_entry("ddpm_shaped", "mi355_ddpm_shaped_sample", "mi355_ddpm_shaped_workspace_bytes", (_lib.x0_shaping(shaping),), [], **loop)
 
     def ddpm_learned(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], max_log=None, *, mode: int, times=None, cond: Optional[torch.Tensor] = None,
                      noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0, noise_condition=True,
@@ -965,23 +919,9 @@ class UNetEngine:
         the chain, DDPM.max_log()).  max_log None: the fixed-variance loops on a net of x's channel count, bit for bit.  times ([K] floats, or
         None: the loops' own rule): the time the net sees at step k (DDPM.time of a from_betas chain).  Everything else: the arguments and the
         loops of ddpm_shaped (coefs: the multistep solver)."""
-        K = int(tables["alphas_cumprod_prev"].numel())
-        keep = []
-        var = _lib.DDPMVarianceC(0, None, None)
-        for name, v in (("max_log", max_log), ("times", times)):
-            if v is None:
-                continue
-            t = torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").contiguous()
-            if t.numel() != K:
-                raise ValueError(f"{name} must have one entry per row of the tables")
-            keep.append(t)
-            setattr(var, name, C.cast(t.data_ptr(), C.POINTER(C.c_float)))
-        var.learned = int(max_log is not None)
-        return self._ddpm_one_entry("ddpm_learned", "mi355_ddpm_lv_sample", "mi355_ddpm_lv_workspace_bytes", var if keep else None, keep, x, tables,
-                                    mode=mode, cond=cond, noise=noise, n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax,
-                                    start_fraction=start_fraction, noise_condition=noise_condition, pad_value=pad_value, none_value=none_value, seed=seed,
-                                    guidance_scale=guidance_scale, y=y, null_label=null_label, timesteps=timesteps, train_steps=train_steps,
-                                    ddim_sigma=ddim_sigma, walk=walk, coefs=coefs)
+        loop = {k: v for k, v in locals().items() if k not in ("self", "max_log", "times")}
+        var, keep = self._ddpm_variance(tables, max_log, times)
+        return self._ddpm_one_entry("ddpm_learned", "mi355_ddpm_lv_sample", "mi355_ddpm_lv_workspace_bytes", (var,), keep, **loop)
 
     def ddpm_pred(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], prediction, *, mode: int, shaping=None, max_log=None, times=None,
                   cond: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0,
@@ -991,29 +931,28 @@ class UNetEngine:
         """In-place DDPM sampling of a net whose output is "eps", "x0" or "v" (mi355_ddpm_pred_sample): every step forms the data prediction of
         the kind from the net's raw output and goes on as ddpm_sample / ddpm_multistep (coefs), ddpm_shaped (shaping) and ddpm_learned (max_log,
         times) do; "eps" gives their bits.  shaping together with max_log is refused by the library."""
-        K = int(tables["alphas_cumprod_prev"].numel())
-        keep = []
-        var = _lib.DDPMVarianceC(0, None, None)
-        for name, v in (("max_log", max_log), ("times", times)):
-            if v is None:
-                continue
-            t = torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").contiguous()
-            if t.numel() != K:
-                raise ValueError(f"{name} must have one entry per row of the tables")
-            keep.append(t)
-            setattr(var, name, C.cast(t.data_ptr(), C.POINTER(C.c_float)))
-        var.learned = int(max_log is not None)
-        extra = (var if keep else None, _lib.x0_shaping(shaping), _lib.DDPMPredictionC(_lib.prediction_kind(prediction)))
-        return self._ddpm_one_entry("ddpm_pred", "mi355_ddpm_pred_sample", "mi355_ddpm_pred_workspace_bytes", extra, keep, x, tables, mode=mode,
-                                    cond=cond, noise=noise, n_corrector=n_corrector, delta=delta, tmin=tmin, tmax=tmax, start_fraction=start_fraction,
-                                    noise_condition=noise_condition, pad_value=pad_value, none_value=none_value, seed=seed,
-                                    guidance_scale=guidance_scale, y=y, null_label=null_label, timesteps=timesteps, train_steps=train_steps,
-                                    ddim_sigma=ddim_sigma, walk=walk, coefs=coefs)
+        loop = {k: v for k, v in locals().items() if k not in ("self", "prediction", "shaping", "max_log", "times")}
+        var, keep = self._ddpm_variance(tables, max_log, times)
+        extra = (var, _lib.x0_shaping(shaping), _lib.DDPMPredictionC(_lib.prediction_kind(prediction)))
+        return self._ddpm_one_entry("ddpm_pred", "mi355_ddpm_pred_sample", "mi355_ddpm_pred_workspace_bytes", extra, keep, **loop)
 
-    def _ddpm_one_entry(self, who, entry, ws_fn, extra, keep_extra, x, tables, *, mode, cond, noise, n_corrector, delta, tmin, tmax, start_fraction,
+    @staticmethod
+    def _ddpm_variance(tables, max_log, times):
+        """-> (mi355_ddpm_variance, or None when neither max_log nor times is given; the host tensors it points into)."""
+        K = int(tables["alphas_cumprod_prev"].numel())
+        var, keep = _lib.DDPMVarianceC(int(max_log is not None), None, None), []
+        for name, v in (("max_log", max_log), ("times", times)):
+            if v is not None:
+                ptr, t = _host_floats(v, K, name)
+                keep.append(t)
+                setattr(var, name, ptr)
+        return (var if keep else None), keep
+
+    def _ddpm_one_entry(self, who, entry, ws_fn, extra, keep_extra, *, x, tables, mode, cond, noise, n_corrector, delta, tmin, tmax, start_fraction,
                         noise_condition, pad_value, none_value, seed, guidance_scale, y, null_label, timesteps, train_steps, ddim_sigma, walk, coefs):
         """The entry points that sit over the six DDPM loops (mi355_ddpm_shaped_sample, mi355_ddpm_lv_sample, mi355_ddpm_pred_sample): one argument
-        list, with the entry point's own struct `extra` (or None; a tuple: several, in order) between the schedules and the noise."""
+        list, with the entry point's own structs `extra` (a tuple, in order; None: a null pointer) between the schedules and the noise.  The
+        keywords are the public methods' own."""
         B = x.shape[0]
         if cond is not None and cond.shape != x.shape:
             raise ValueError("condition must have the shape of x")
@@ -1039,23 +978,14 @@ class UNetEngine:
         if noise is not None and noise.shape[1:] != x.shape:
             raise ValueError("injected noise must be [n_draws, B, C, H, W]")
         guided = guidance_scale is not None
-        lab = wt = None
-        w, nl, mb = 0.0, 0, B
+        guide, mb = (None, 0, 0.0, None), B
         if guided:
             lab, _ = self._labels(y, B)
             w, wt, nl = self._guidance_args(guidance_scale, B, lab, cond, null_label)
-            mb = self.cfg_batch()
-        self._fwd_state = None
-        for xs, cn, nz, ls, wl, sd in self._guided_slices(x, cond, noise, lab, wt, int(seed), mb):
-            opt = _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value,
-                                    int(cond is None), sd)
-            ws, wsb = self._workspace_sized(ws_fn, xs.shape[0], int(guided), int(ms is not None))
-            a = self._ddpm_args(xs, cn, ls, nl, w, wl)
-            check(getattr(self.L, entry)(self.handle, *a[:5], int(guided), *a[5:], C.byref(tb), C.byref(opt),
-                                         C.byref(sched[0]) if sched is not None else None, C.byref(ms) if ms is not None else None,
-                                         *(C.byref(e) if e is not None else None for e in (extra if isinstance(extra, tuple) else (extra,))),
-                                         *self._noise_args(nz), xs.shape[0], ws, wsb, self._stream()),
-                  entry)
+            guide, mb = (lab, nl, w, wt), self.cfg_batch()
+        opt = self._ddpm_options(mode, cond, 0, none_value, n_corrector, delta, tmin, tmax, start_fraction, noise_condition, pad_value)
+        self._ddpm_loop(entry, ws_fn, (int(guided), int(ms is not None)), mb, x, cond, noise, tb, opt, seed=int(seed), guide=guide, flag=guided,
+                        mid=(None if sched is None else sched[0], ms) + extra, draws=True)
         del keep
         return x
 
@@ -1087,11 +1017,9 @@ class UNetEngine:
                 if name == "times":
                     continue
                 raise ValueError(f"logs[{name!r}] is needed ({'learned' if learned else 'fixed'} variance): DDPM.vlb_log_variances builds it")
-            t = torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").contiguous()
-            if t.numel() != K:
-                raise ValueError(f"{name} must have one entry per row of the tables")
+            ptr, t = _host_floats(v, K, name)
             keep.append(t)
-            setattr(opt, name, C.cast(t.data_ptr(), C.POINTER(C.c_float)))
+            setattr(opt, name, ptr)
         if noise is not None and (noise.dim() != 5 or tuple(noise.shape[1:]) != tuple(x0.shape)):
             raise ValueError(f"noise must be [draws, *x0.shape], got {tuple(noise.shape)}")
         lab, _ = self._labels(y, B)
@@ -1099,18 +1027,13 @@ class UNetEngine:
         summary = torch.empty(B, 2, device=self.device, dtype=torch.float32)
         self._fwd_state = None
         seed = 0 if seed is None else int(seed)
-        for i, (lo, hi, whole) in enumerate(_slices(B, self.max_batch())):
-            xs, cn, nz, ls = x0[lo:hi], _cut(cond, lo, hi), noise if whole or noise is None else noise[:, lo:hi].contiguous(), _cut(lab, lo, hi)
-            tm, sm = (terms, summary) if whole else (torch.empty(hi - lo, K, 3, device=self.device), torch.empty(hi - lo, 2, device=self.device))
-            opt.seed = (seed + i) % 2 ** 64
-            ws, wsb = self._workspace_sized("mi355_ddpm_vlb_workspace_bytes", hi - lo)
-            name = "mi355_ddpm_vlb" if pred.kind == 0 else "mi355_ddpm_vlb_pred"
-            check(getattr(self.L, name)(self.handle, self._chk(xs, "x0"), xs.shape[1], self._chk(cn, "condition") if cn is not None else None,
-                                        C.c_void_p(ls.data_ptr()) if ls is not None else None, C.byref(tb), C.byref(opt),
+        name = "mi355_ddpm_vlb" if pred.kind == 0 else "mi355_ddpm_vlb_pred"
+        for n, (xs, cn, ls, tm, sm), (nz,), _, sd in self._sliced(B, self.max_batch(), rows=(x0, cond, lab, terms, summary), cols=(noise,), seed=seed):
+            opt.seed = sd
+            ws, wsb = self._workspace_sized("mi355_ddpm_vlb_workspace_bytes", n)
+            check(getattr(self.L, name)(self.handle, self._chk(xs, "x0"), xs.shape[1], self._ptr(cn, "condition"), _lab_ptr(ls), C.byref(tb), C.byref(opt),
                                         *(() if pred.kind == 0 else (C.byref(pred),)), *self._noise_args(nz), self._chk(tm, "terms"),
-                                        self._chk(sm, "summary"), hi - lo, ws, wsb, self._stream()), name)
-            if not whole:
-                terms[lo:hi], summary[lo:hi] = tm, sm
+                                        self._chk(sm, "summary"), n, ws, wsb, self._stream()), name)
         del keep
         return terms, summary
 
@@ -1118,36 +1041,48 @@ class UNetEngine:
         """One mi355_ddpm_cfg_sample (sched: mi355_ddpm_cfg_sample_sched) call (a batch within cfg_batch())."""
         B = x.shape[0]
         tb, keep = self._ddpm_tables(tables)
-        opt = _lib.DDPMOptionsC(mode, o["n_corrector"], o["delta"], o["tmin"], o["tmax"], 1.0, 1, -2.0, o["none_value"], int(cond is None), o["seed"])
+        opt = self._ddpm_options(mode, cond, o["seed"], o["none_value"], o["n_corrector"], o["delta"], o["tmin"], o["tmax"])
         self._fwd_state = None
         ws, wsb = self._workspace_sized("mi355_ddpm_cfg_workspace_bytes", B)
         name = "mi355_ddpm_cfg_sample" if sched is None else "mi355_ddpm_cfg_sample_sched"
-        check(getattr(self.L, name)(self.handle, *self._ddpm_args(x, cond, lab, null_label, w, wt), C.byref(tb), C.byref(opt),
-                                    *(() if sched is None else (C.byref(sched[0]),)), *self._noise_args(noise), B, ws, wsb, self._stream()), name)
+        self._ddpm_call(name, x, cond, tb, opt, B, ws, wsb, guide=(lab, null_label, w, wt), mid=() if sched is None else (sched[0],),
+                        noise=self._noise_args(noise))
         del keep
 
     @staticmethod
-    def _guided_slices(x, cond, noise, lab, wt, seed, mb):
-        """The slices of one (guided) DDPM call run at most mb images at a time: yields the cut x, condition, injected noise, labels, per-image
-        scales and the slice's Philox seed (seed + slice index); a slice that is not the caller's batch itself is written back after its call."""
-        B = x.shape[0]
-        for i, (lo, hi, whole) in enumerate(_slices(B, mb)):
-            xs = x if whole else x[lo:hi].contiguous()
-            yield (xs, cond if whole or cond is None else cond[lo:hi].contiguous(), noise if whole or noise is None else noise[:, lo:hi].contiguous(),
-                   _cut(lab, lo, hi), _cut(wt, lo, hi), (seed + i) % 2 ** 64)
-            if not whole:
-                x[lo:hi] = xs
+    def _ddpm_options(mode, cond, seed, none_value=-2.0, n_corrector=0, delta=0.1, tmin=1e-5, tmax=1.0, start_fraction=1.0, noise_condition=True,
+                      pad_value=-2.0):
+        """mi355_ddpm_options.  The defaults are what the guided ddpm_sample path and the multistep solver pass for the fields they do not take."""
+        return _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value, int(cond is None), seed)
 
-    def _ddpm_args(self, x, cond, lab=None, null_label=None, w=None, wt=None):
-        """The pointer arguments every DDPM call starts with: x, Cx, cond; a guided call (w given) adds labels, null_label, w, w_dev."""
-        a = (self._chk(x, "x"), x.shape[1], self._chk(cond, "condition") if cond is not None else None)
-        if w is None:
-            return a
-        return a + (C.c_void_p(lab.data_ptr()) if lab is not None else None, int(null_label), float(w),
-                    self._chk(wt, "guidance_scale") if wt is not None else None)
+    def _ddpm_loop(self, name, ws_fn, ws_tail, mb, x, cond, noise, tb, opt, seed=None, guide=None, flag=None, mid=(), draws=False):
+        """The calls of the DDPM entry point `name` on a batch run at most mb images at a time, each on a workspace of ws_fn(batch, *ws_tail).  seed:
+        the Philox seed of the batch, the slices draw from seed + slice index (None: opt's own).  draws: the entry point takes injected noise.
+        guide, flag, mid: see _ddpm_call."""
+        lab, nl, w, wt = guide or (None, 0, 0.0, None)
+        self._fwd_state = None
+        for n, (xs, cn, ls, wl), (nz,), _, sd in self._sliced(x.shape[0], mb, rows=(x, cond, lab, wt), cols=(noise,), seed=seed):
+            if sd is not None:
+                opt.seed = sd
+            ws, wsb = self._workspace_sized(ws_fn, n, *ws_tail)
+            self._ddpm_call(name, xs, cn, tb, opt, n, ws, wsb, guide=guide and (ls, nl, w, wl), flag=flag, mid=mid,
+                            noise=self._noise_args(nz) if draws else ())
+
+    def _ddpm_call(self, name, x, cond, tb, opt, B, ws, wsb, guide=None, flag=None, mid=(), noise=(), last=()):
+        """One call of the DDPM entry point `name`, in the argument order they share: handle, x, C, cond, [labels, null_label, (guided flag,) w,
+        per-image scales,] tables, options, mid, [noise, n_draws,] batch, workspace, stream, last.  guide: (labels, null_label, w, scales) where the
+        entry point takes guidance, flag: its guided flag where it has one.  mid: the schedules and the entry point's own structs, each a struct
+        or None (a null pointer); noise: _noise_args where the entry point draws; last: the feature cache or the tile plan."""
+        g = ()
+        if guide is not None:
+            lab, nl, w, wt = guide
+            g = (_lab_ptr(lab), int(nl), *(() if flag is None else (int(flag),)), float(w), self._ptr(wt, "guidance_scale"))
+        check(getattr(self.L, name)(self.handle, self._chk(x, "x"), x.shape[1], self._ptr(cond, "condition"), *g, C.byref(tb), C.byref(opt),
+                                    *(None if s is None else C.byref(s) for s in mid), *noise, B, ws, wsb, self._stream(),
+                                    *(C.byref(s) for s in last)), name)
 
     def _noise_args(self, noise):
-        return (self._chk(noise, "noise") if noise is not None else None, noise.shape[0] if noise is not None else 0)
+        return (self._ptr(noise, "noise"), noise.shape[0] if noise is not None else 0)
 
     @staticmethod
     def _multistep_schedule(tb, coefs, timesteps, train_steps):
@@ -1193,11 +1128,8 @@ class UNetEngine:
         keep = [(C.c_int32 * max(1, K))(*[int(t) for t in timesteps])]
         sd.steps, sd.train_steps = C.cast(keep[0], ip), int(train_steps)
         if ddim_sigma is not None:
-            sg = torch.as_tensor(ddim_sigma, dtype=torch.float32).detach().to("cpu").contiguous()
-            if sg.numel() != K:
-                raise ValueError("ddim_sigma must have one entry per step")
+            sd.ddim_sigma, sg = _host_floats(ddim_sigma, K, "ddim_sigma", per="step")
             keep.append(sg)
-            sd.ddim_sigma = C.cast(sg.data_ptr(), fp)
         if walk is not None:
             wl = (C.c_int32 * max(1, len(walk)))(*[int(v) for v in walk])
             keep.append(wl)

@@ -5,6 +5,7 @@ hand-written kernel is launched, enqueues on torch's current HIP stream and neve
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import torch
@@ -77,6 +78,9 @@ def _debug_ptr(debug, or_default):
 def _route_dict(route):
     """The words a conv op reports of its launch (the first four, or all eight) -> dict."""
     return dict(zip(("kernel", "form", "tile_m", "tile_n", "reads_nchw", "axpy", "ksplit", "n_mt"), route))
+
+
+_StepOperands = collections.namedtuple("_StepOperands", "guided B per n stride wf wp keep use_philox seed off")
 
 
 class Ops:
@@ -161,16 +165,9 @@ class Ops:
     def ddim_eta_cfg_step_(self, x2, eps2, z, w, c_recip, c_recipm1, acp_prev, sigma, philox=None):
         """ddim_eta_step_ on the guided eps, operands as ddpm_cfg_step_."""
         _same(x2, eps2, "x2", "eps2")
-        if x2.shape[0] % 2:
-            raise ValueError("x2 holds the state twice: an even leading size")
-        B = x2.shape[0] // 2
-        n = x2.numel() // 2
-        if z is not None and z.numel() != n:
-            raise ValueError("z must have the B-image state's size")
-        wf, wp, keep = self._cfg_w(w, B)
-        seed, off = philox if philox else (0, 0)
-        check(_lib.lib().mi355_ddim_eta_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _opt(z, "z"), wf, wp, n // B if B else 1, c_recip, c_recipm1, acp_prev,
-                                                 float(sigma), int(philox is not None and z is None), seed, off, n, _stream()), "mi355_ddim_eta_cfg_step")
+        o = self._step_operands(x2, w, philox, z=z, name="x2")
+        check(_lib.lib().mi355_ddim_eta_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _opt(z, "z"), o.wf, o.wp, o.per, c_recip, c_recipm1, acp_prev,
+                                                 float(sigma), o.use_philox, o.seed, o.off, o.n, _stream()), "mi355_ddim_eta_cfg_step")
         return x2
 
     def dpmpp_step_(self, x, eps, hist, c_recip, c_recipm1, cx, c0, c1):
@@ -188,17 +185,11 @@ class Ops:
     def dpmpp_cfg_step_(self, x2, eps2, hist, w, c_recip, c_recipm1, cx, c0, c1):
         """dpmpp_step_ on the guided eps: x2, eps2, w as in ddim_cfg_step_; hist [B, ...] (or None)."""
         _same(x2, eps2, "x2", "eps2")
-        if x2.shape[0] % 2:
-            raise ValueError("x2 holds the state twice: an even leading size")
-        B = x2.shape[0] // 2
-        n = x2.numel() // 2
-        if hist is not None and hist.numel() != n:
-            raise ValueError("hist must have the B-image state's size")
+        o = self._step_operands(x2, w, hist=hist, name="x2")
         if hist is None and float(c1) != 0.0:
             raise ValueError("c1 != 0 needs hist (the previous step's data prediction)")
-        wf, wp, keep = self._cfg_w(w, B)
-        check(_lib.lib().mi355_dpmpp_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _opt(hist, "hist"), wf, wp, n // B if B else 1, float(c_recip),
-                                              float(c_recipm1), float(cx), float(c0), float(c1), n, _stream()), "mi355_dpmpp_cfg_step")
+        check(_lib.lib().mi355_dpmpp_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _opt(hist, "hist"), o.wf, o.wp, o.per, float(c_recip),
+                                              float(c_recipm1), float(cx), float(c0), float(c1), o.n, _stream()), "mi355_dpmpp_cfg_step")
         return x2
 
     def x0_shape_stats(self, x, eps, c_recip, c_recipm1, shaping, w=None, detail=False):
@@ -210,13 +201,13 @@ class Ops:
         guided = w is not None
         if tuple(eps.shape) != ((2 * B if guided else B),) + tuple(x.shape[1:]):
             raise ValueError(f"eps {tuple(eps.shape)} must be x's shape {tuple(x.shape)}" + (" with twice the leading size" if guided else ""))
-        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
+        o = self._step_operands(x, w, doubled=False)
         sh = _lib.x0_shaping(shaping)
         shape = torch.empty(B, 2, device=x.device, dtype=torch.float32)
         det = torch.empty(B, 4, device=x.device, dtype=torch.float32) if detail else None
-        check(_lib.lib().mi355_x0_shape_stats(_req(x, "x"), _req(eps, "eps"), wf, wp, int(guided), float(c_recip), float(c_recipm1),
+        check(_lib.lib().mi355_x0_shape_stats(_req(x, "x"), _req(eps, "eps"), o.wf, o.wp, int(guided), float(c_recip), float(c_recipm1),
                                               C.byref(sh) if sh is not None else None, _req(shape, "shape"), _req(det, "detail") if detail else None,
-                                              B, x.numel() // B if B else 1, _stream()), "mi355_x0_shape_stats")
+                                              B, o.per, _stream()), "mi355_x0_shape_stats")
         return (shape, det) if detail else shape
 
     _STEP_KINDS = {"ddpm": 0, "ddim": 1, "ddim_eta": 2, "dpmpp": 3}
@@ -226,21 +217,10 @@ class Ops:
         sigma; z / philox as in ddpm_step_), "ddim" (a = acp_prev), "ddim_eta" (a = acp_prev; sigma; z / philox) or "dpmpp" (a, b, c = cx, c0, c1;
         hist).  w (a float or a [B] tensor): the guided form, x and eps [2B, ...] as in ddpm_cfg_step_; z and hist stay [B, ...].  -> x"""
         _same(x, eps, "x", "eps")
-        guided = w is not None
-        if guided and x.shape[0] % 2:
-            raise ValueError("x holds the state twice: an even leading size")
-        B = x.shape[0] // 2 if guided else x.shape[0]
-        n = x.numel() // 2 if guided else x.numel()
-        for t, name in ((z, "z"), (hist, "hist")):
-            if t is not None and t.numel() != n:
-                raise ValueError(f"{name} must have the B-image state's size")
-        if shape is not None and tuple(shape.shape) != (B, 2):
-            raise ValueError(f"shape must be [{B}, 2], got {tuple(shape.shape)}")
-        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
-        seed, off = philox if philox else (0, 0)
-        check(_lib.lib().mi355_x0_shaped_step(self._STEP_KINDS[kind], _req(x, "x"), _req(eps, "eps"), _opt(z, "z"), _opt(hist, "hist"), int(guided), wf, wp,
-                                              n // B if B else 1, float(c_recip), float(c_recipm1), float(a), float(b), float(c), float(sigma),
-                                              int(philox is not None and z is None), seed, off, _opt(shape, "shape"), n, _stream()), "mi355_x0_shaped_step")
+        o = self._step_operands(x, w, philox, z=z, hist=hist, shape=shape)
+        check(_lib.lib().mi355_x0_shaped_step(self._STEP_KINDS[kind], _req(x, "x"), _req(eps, "eps"), _opt(z, "z"), _opt(hist, "hist"), int(o.guided), o.wf,
+                                              o.wp, o.per, float(c_recip), float(c_recipm1), float(a), float(b), float(c), float(sigma), o.use_philox,
+                                              o.seed, o.off, _opt(shape, "shape"), o.n, _stream()), "mi355_x0_shaped_step")
         return x
 
     _STRIDED_KINDS = dict(_STEP_KINDS, corrector=4)
@@ -260,17 +240,10 @@ class Ops:
     def strided_step_(self, kind, x, out, c_recip, c_recipm1, a, b=0.0, c=0.0, sigma=0.0, z=None, philox=None, hist=None, w=None):
         """x0_shaped_step_'s unshaped steps, and the corrector (kind "corrector": a, b, c = rsm1, dt, delta; never guided), reading eps from the
         first C channels of a wider network output out [B, Cw, ...] in place (mi355_strided_step): nothing is sliced or copied.  -> x"""
-        guided = w is not None
-        B, per, stride = self._wide_out(x, out, guided)
-        n = B * per
-        for t, name in ((z, "z"), (hist, "hist")):
-            if t is not None and t.numel() != n:
-                raise ValueError(f"{name} must have the B-image state's size")
-        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
-        seed, off = philox if philox else (0, 0)
-        check(_lib.lib().mi355_strided_step(self._STRIDED_KINDS[kind], _req(x, "x"), _req(out, "out"), stride, _opt(z, "z"), _opt(hist, "hist"), int(guided),
-                                            wf, wp, per, float(c_recip), float(c_recipm1), float(a), float(b), float(c), float(sigma),
-                                            int(philox is not None and z is None), seed, off, n, _stream()), "mi355_strided_step")
+        o = self._step_operands(x, w, philox, z=z, hist=hist, out=out)
+        check(_lib.lib().mi355_strided_step(self._STRIDED_KINDS[kind], _req(x, "x"), _req(out, "out"), o.stride, _opt(z, "z"), _opt(hist, "hist"),
+                                            int(o.guided), o.wf, o.wp, o.per, float(c_recip), float(c_recipm1), float(a), float(b), float(c), float(sigma),
+                                            o.use_philox, o.seed, o.off, o.n, _stream()), "mi355_strided_step")
         return x
 
     def ddpm_lv_step_(self, x, out, z, c_recip, c_recipm1, coef1, coef2, min_log, max_log, philox=None, w=None):
@@ -278,17 +251,10 @@ class Ops:
         [0, C), v in [C, 2C); sigma = exp(0.5 (frac max_log + (1 - frac) min_log)), frac = (v + 1) / 2.  z / philox as in ddpm_step_.  w (a float
         or a [B] tensor): the guided form, x [2B, C, ...] the duplicated state and out [2B, 2C, ...] = conditional | unconditional (v from the
         conditional half); z stays [B, ...].  -> x"""
-        guided = w is not None
-        B, per, stride = self._wide_out(x, out, guided)
-        if stride != 2 * per:
-            raise ValueError(f"a learned-variance net writes twice the state's channels, got {tuple(out.shape)} for the state {tuple(x.shape)}")
-        if z is not None and z.numel() != B * per:
-            raise ValueError("z must have the B-image state's size")
-        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
-        seed, off = philox if philox else (0, 0)
-        check(_lib.lib().mi355_ddpm_lv_step(_req(x, "x"), _req(out, "out"), _opt(z, "z"), wf, wp, int(guided), per, float(c_recip), float(c_recipm1),
-                                            float(coef1), float(coef2), float(min_log), float(max_log), int(philox is not None and z is None), seed, off,
-                                            B, _stream()), "mi355_ddpm_lv_step")
+        o = self._step_operands(x, w, philox, z=z, out=out, twice=True)
+        check(_lib.lib().mi355_ddpm_lv_step(_req(x, "x"), _req(out, "out"), _opt(z, "z"), o.wf, o.wp, int(o.guided), o.per, float(c_recip), float(c_recipm1),
+                                            float(coef1), float(coef2), float(min_log), float(max_log), o.use_philox, o.seed, o.off, o.B, _stream()),
+              "mi355_ddpm_lv_step")
         return x
 
     _PRED_STEP_KINDS = dict(_STRIDED_KINDS, ddpm_lv=5)
@@ -300,23 +266,11 @@ class Ops:
         the step) - and the step goes on from it as x0_shaped_step_ (kind "ddpm", "ddim", "ddim_eta", "dpmpp"; shape: its rows or None),
         strided_step_ (out [B, Cw >= C, ...] read in place; kind "corrector": a, b, c = rsm1, dt, delta) and ddpm_lv_step_ (kind "ddpm_lv": a, b =
         coef1, coef2; min_log, max_log; out [B, 2C, ...]) do.  w: the guided form, x and out [2B, ...].  -> x"""
-        guided = w is not None
-        B, per, stride = self._wide_out(x, out, guided)
-        n = B * per
-        if kind == "ddpm_lv" and stride != 2 * per:
-            raise ValueError(f"a learned-variance net writes twice the state's channels, got {tuple(out.shape)} for the state {tuple(x.shape)}")
-        for t, name in ((z, "z"), (hist, "hist")):
-            if t is not None and t.numel() != n:
-                raise ValueError(f"{name} must have the B-image state's size")
-        if shape is not None and tuple(shape.shape) != (B, 2):
-            raise ValueError(f"shape must be [{B}, 2], got {tuple(shape.shape)}")
-        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
-        seed, off = philox if philox else (0, 0)
+        o = self._step_operands(x, w, philox, z=z, hist=hist, shape=shape, out=out, twice=kind == "ddpm_lv")
         check(_lib.lib().mi355_pred_step(self._PRED_STEP_KINDS[kind], _lib.prediction_kind(prediction), _req(x, "x"), _req(out, "out"),
-                                         0 if stride == per else stride, _opt(z, "z"), _opt(hist, "hist"), int(guided), wf, wp, per, float(c_recip),
-                                         float(c_recipm1), float(sa), float(sb), float(a), float(b), float(c), float(sigma), float(min_log),
-                                         float(max_log), int(philox is not None and z is None), seed, off, _opt(shape, "shape"), n, _stream()),
-              "mi355_pred_step")
+                                         0 if o.stride == o.per else o.stride, _opt(z, "z"), _opt(hist, "hist"), int(o.guided), o.wf, o.wp, o.per,
+                                         float(c_recip), float(c_recipm1), float(sa), float(sb), float(a), float(b), float(c), float(sigma), float(min_log),
+                                         float(max_log), o.use_philox, o.seed, o.off, _opt(shape, "shape"), o.n, _stream()), "mi355_pred_step")
         return x
 
     def pred_shape_stats(self, prediction, x, out, c_recip, c_recipm1, shaping, *, sa=0.0, sb=0.0, w=None, detail=False):
@@ -326,14 +280,13 @@ class Ops:
         guided = w is not None
         if tuple(out.shape) != ((2 * B if guided else B),) + tuple(x.shape[1:]):
             raise ValueError(f"out {tuple(out.shape)} must be x's shape {tuple(x.shape)}" + (" with twice the leading size" if guided else ""))
-        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
+        o = self._step_operands(x, w, doubled=False)
         sh = _lib.x0_shaping(shaping)
         shape = torch.empty(B, 2, device=x.device, dtype=torch.float32)
         det = torch.empty(B, 4, device=x.device, dtype=torch.float32) if detail else None
-        check(_lib.lib().mi355_pred_shape_stats(_lib.prediction_kind(prediction), _req(x, "x"), _req(out, "out"), wf, wp, int(guided), float(c_recip),
+        check(_lib.lib().mi355_pred_shape_stats(_lib.prediction_kind(prediction), _req(x, "x"), _req(out, "out"), o.wf, o.wp, int(guided), float(c_recip),
                                                 float(c_recipm1), float(sa), float(sb), C.byref(sh) if sh is not None else None, _req(shape, "shape"),
-                                                _req(det, "detail") if detail else None, B, x.numel() // B if B else 1, _stream()),
-              "mi355_pred_shape_stats")
+                                                _req(det, "detail") if detail else None, B, o.per, _stream()), "mi355_pred_shape_stats")
         return (shape, det) if detail else shape
 
     def q_sample(self, x0, a, b, z=None, philox=None, out=None):
@@ -629,6 +582,31 @@ class Ops:
             return 0.0, _req(w, "w"), w
         return float(w), None, None
 
+    def _step_operands(self, x, w, philox=None, *, z=None, hist=None, shape=None, out=None, twice=False, doubled=True, name="x"):
+        """What the predictor-step and shape-statistics wrappers hand over besides their tensors and coefficients, with the size checks that go with
+        it -> _StepOperands.  w: the guidance scale (a float or a [B] tensor; None: not guided).  doubled: a guided x is [2B, ...] (the step ops;
+        the statistics ops keep x [B, ...]).  out: a network output wider than the state (_wide_out; twice: it must hold twice x's channels).  z,
+        hist: [B, ...] operands of the B-image state's size; shape: the [B, 2] rows of the statistics; philox: (seed, offset) or None."""
+        guided = w is not None
+        if out is not None:
+            B, per, stride = self._wide_out(x, out, guided)
+            if twice and stride != 2 * per:
+                raise ValueError(f"a learned-variance net writes twice the state's channels, got {tuple(out.shape)} for the state {tuple(x.shape)}")
+        else:
+            if guided and doubled and x.shape[0] % 2:
+                raise ValueError(f"{name} holds the state twice: an even leading size")
+            B = x.shape[0] // 2 if guided and doubled else x.shape[0]
+            per = stride = x.numel() // x.shape[0] if x.shape[0] else 1
+        n = B * per
+        for t, nm in ((z, "z"), (hist, "hist")):
+            if t is not None and t.numel() != n:
+                raise ValueError(f"{nm} must have the B-image state's size")
+        if shape is not None and tuple(shape.shape) != (B, 2):
+            raise ValueError(f"shape must be [{B}, 2], got {tuple(shape.shape)}")
+        wf, wp, keep = self._cfg_w(w, B) if guided else (0.0, None, None)
+        seed, off = philox if philox else (0, 0)
+        return _StepOperands(guided, B, per, n, stride, wf, wp, keep, int(philox is not None and z is None), seed, off)
+
     def cfg_stage(self, out, y0, ks, coeffs, w, dup=False, copy_out=None, u8_out=None):
         """rk_stage over classifier-free-guided derivatives: every ks[j] is [2B, ...] (the conditional evaluation in the first half, the
         unconditional one in the second), g_j = u + w (c - u) with each operation rounded, out = y0 + sum_j coeffs[j] * g_j.  w: a float
@@ -666,27 +644,16 @@ class Ops:
         """ddpm_step_ on the guided eps: x2 [2B, ...] the duplicated state (first half read, both halves written), eps2 [2B, ...] =
         conditional | unconditional; z [B, ...] injected noise or None; philox (seed, offset) indexes the B-image state."""
         _same(x2, eps2, "x2", "eps2")
-        B = x2.shape[0] // 2
-        if x2.shape[0] % 2:
-            raise ValueError("x2 holds the state twice: an even leading size")
-        n = x2.numel() // 2
-        if z is not None and z.numel() != n:
-            raise ValueError("z must have the B-image state's size")
-        wf, wp, keep = self._cfg_w(w, B)
-        seed, off = philox if philox else (0, 0)
-        check(_lib.lib().mi355_ddpm_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _opt(z, "z"), wf, wp, n // B if B else 1, c_recip, c_recipm1, coef1, coef2,
-                                             sigma, int(philox is not None and z is None), seed, off, n, _stream()), "mi355_ddpm_cfg_step")
+        o = self._step_operands(x2, w, philox, z=z, name="x2")
+        check(_lib.lib().mi355_ddpm_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), _opt(z, "z"), o.wf, o.wp, o.per, c_recip, c_recipm1, coef1, coef2,
+                                             sigma, o.use_philox, o.seed, o.off, o.n, _stream()), "mi355_ddpm_cfg_step")
         return x2
 
     def ddim_cfg_step_(self, x2, eps2, w, c_recip, c_recipm1, acp_prev):
         """ddim_step_ on the guided eps, operands as ddpm_cfg_step_."""
         _same(x2, eps2, "x2", "eps2")
-        if x2.shape[0] % 2:
-            raise ValueError("x2 holds the state twice: an even leading size")
-        B = x2.shape[0] // 2
-        n = x2.numel() // 2
-        wf, wp, keep = self._cfg_w(w, B)
-        check(_lib.lib().mi355_ddim_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), wf, wp, n // B if B else 1, c_recip, c_recipm1, acp_prev, n, _stream()),
+        o = self._step_operands(x2, w, name="x2")
+        check(_lib.lib().mi355_ddim_cfg_step(_req(x2, "x2"), _req(eps2, "eps2"), o.wf, o.wp, o.per, c_recip, c_recipm1, acp_prev, o.n, _stream()),
               "mi355_ddim_cfg_step")
         return x2
 

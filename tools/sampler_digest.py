@@ -18,6 +18,7 @@ qkv_attention_vjp) on the shapes at which each of the five attention kernels tak
 inventory (names, shapes, order) and the weight-image bytes of the same nets.
 """
 import argparse
+import ctypes as C
 import hashlib
 import os
 import sys
@@ -33,17 +34,18 @@ import torch  # noqa: E402
 from image_diffusion.sde_diffusion import DDPM  # noqa: E402
 from image_diffusion.unet import UNetModel, param_shapes  # noqa: E402
 from mi355 import _lib  # noqa: E402
-from mi355.engine import _PREC, MI355BackendError, param_inventory  # noqa: E402
+from mi355.engine import _PREC, MI355BackendError, param_inventory, tile_plan  # noqa: E402
 from mi355.synth import randn, synth_state_dict  # noqa: E402
 
 DEV = "cuda:0"
 B, S, NS = 3, 16, 24   # batch, image size, DDPM steps (DDPM(Ns <= 20) has non-finite tables, as the reference does)
+CANVAS, TILING = (24, 24), dict(stride=8, weight="uniform", chunk=5)   # tiled calls: 2 x 2 windows per canvas, B * 4 = 12 windows in chunks of 5
 LINES, KEPT, MARK = [], {}, [False]
 
 
-def net(prec, in_ch=3, num_classes=None, seed=0, **debug):
-    """The 16x16 / 32-channel two-level net of smoke(), with 3 output channels."""
-    kw = dict(image_size=S, in_channels=in_ch, model_channels=32, out_channels=3, num_res_blocks=1, attention_resolutions=(2,),
+def net(prec, in_ch=3, num_classes=None, seed=0, out_ch=3, **debug):
+    """The 16x16 / 32-channel two-level net of smoke(), with 3 output channels (out_ch=6: a learned-variance net of 3-channel states)."""
+    kw = dict(image_size=S, in_channels=in_ch, model_channels=32, out_channels=out_ch, num_res_blocks=1, attention_resolutions=(2,),
               channel_mult=(1, 2), num_heads=2, num_classes=num_classes, precision=prec)
     m = UNetModel(**kw)
     m.load_state_dict(synth_state_dict(param_shapes(UNetModel(**kw)), 7000 + seed))
@@ -74,7 +76,13 @@ def case(prec, name, eng, outs):
 
 def sizes(prec, tag, eng):
     L = eng.L
+    plan = tile_plan(S, CANVAS, TILING["stride"], TILING["weight"], TILING["chunk"])["plan"]
     for b in (1, B, 2 * B):
+        emit(f"{prec} bytes {tag} ddpm_vlb_workspace batch={b} {L.mi355_ddpm_vlb_workspace_bytes(eng.handle, b)}")
+        emit(f"{prec} bytes {tag} tiled_workspace batch={b} canvas={CANVAS} {L.mi355_tiled_workspace_bytes(eng.handle, b, C.byref(plan))}")
+        for drift in (0, 1):
+            emit(f"{prec} bytes {tag} feature_cache_workspace batch={b} branch=1 drift={drift} "
+                 f"{L.mi355_feature_cache_workspace_bytes(eng.handle, b, 1, drift)}")
         emit(f"{prec} bytes {tag} unet_workspace batch={b} {L.mi355_unet_workspace_bytes(eng.handle, b)}")
         emit(f"{prec} bytes {tag} ddpm_cfg_workspace batch={b} {L.mi355_ddpm_cfg_workspace_bytes(eng.handle, b)}")
         for st in (1, 2, 3, 4):
@@ -84,6 +92,8 @@ def sizes(prec, tag, eng):
             emit(f"{prec} bytes {tag} ddpm_multistep_workspace batch={b} guided={g} {L.mi355_ddpm_multistep_workspace_bytes(eng.handle, b, g)}")
             for ms in (0, 1):
                 emit(f"{prec} bytes {tag} ddpm_shaped_workspace batch={b} guided={g} multistep={ms} {L.mi355_ddpm_shaped_workspace_bytes(eng.handle, b, g, ms)}")
+                emit(f"{prec} bytes {tag} ddpm_lv_workspace batch={b} guided={g} multistep={ms} {L.mi355_ddpm_lv_workspace_bytes(eng.handle, b, g, ms)}")
+                emit(f"{prec} bytes {tag} ddpm_pred_workspace batch={b} guided={g} multistep={ms} {L.mi355_ddpm_pred_workspace_bytes(eng.handle, b, g, ms)}")
             for order in (2, 3, 4):
                 for st in (1, 2, 4):
                     emit(f"{prec} bytes {tag} cfm_ab_workspace batch={b} order={order} start_stages={st} guided={g} "
@@ -107,7 +117,8 @@ def sliced(eng, mb, fn):
 def run(prec):
     u3, u6, l3, l6 = net(prec), net(prec, 6, seed=1), net(prec, 3, 10, seed=2), net(prec, 6, 4, seed=3)
     score = net(prec, seed=4)
-    for tag, e in (("u3", u3), ("u6", u6), ("l3", l3), ("l6", l6)):
+    w3, w6 = net(prec, seed=5, out_ch=6), net(prec, 6, seed=6, out_ch=6)   # learned-variance nets: eps | v
+    for tag, e in (("u3", u3), ("u6", u6), ("l3", l3), ("l6", l6), ("w3", w3), ("w6", w6)):
         sizes(prec, tag, e)
     x0 = randn(7101, B, 3, S, S).to(DEV)
     cond = (randn(7102, B, 3, S, S) * 0.5).clamp(-1, 1).to(DEV)
@@ -244,6 +255,67 @@ def run(prec):
                  dict(zip(("x", "traj"), u3.sf2m_euler(score, x0.clone(), grid, 0.3, reverse=rev, outputs=outs, **nk))))
     case(prec, "sf2m_per_eval", u3, {"x": u3.sf2m_euler(score, x0.clone(), span(1030), 0.3, seed=77)[0]})
     case(prec, "sf2m_sliced", u3, dict(zip(("x", "traj"), sliced(u3, 2, lambda: u3.sf2m_euler(score, x0.clone(), grid, 0.3, outputs=outs, seed=77)))))
+
+    # ---- the slicing loops of the Adams-Bashforth and the reconstruction samplers ----
+    case(prec, "ab3_plain_sliced", u3, dict(zip(xtu, sliced(u3, 2, lambda: u3.cfm_ab(x0.clone(), span(5), "ab3", keep_traj=True, want_u8=True)))))
+    case(prec, "ab3_guided_sliced", l6, dict(zip(xtu, sliced(l6, 4, lambda: l6.cfm_ab(
+        x0.clone(), span(5), "ab3", cond=cond, keep_traj=True, want_u8=True, y=y4, guidance_scale=wv, null_label=3)))))
+    case(prec, "recon_mode0_fresh_philox_sliced", u3, dict(zip(xtul, sliced(u3, 2, lambda: u3.cfm_recon(
+        x0.clone(), span(3), cond, 0, replace="fresh", seed=99, final_paste=True, keep_traj=True, want_u8=True)))))
+
+    # ---- feature reuse across steps (DeepCache): Euler with an interval and with an explicit schedule and its drift; the DDPM loops ----
+    xtud = ("x", "traj", "u8", "drift")
+    full = [1, 0, 1, 1, 0, 0]
+    case(prec, "euler_cached_interval", u3, dict(zip(xtu, u3.cfm_euler(x0.clone(), span(6), keep_traj=True, want_u8=True, cache_interval=3))))
+    case(prec, "euler_cached_schedule_drift", l3,
+         dict(zip(xtud, l3.cfm_euler(x0.clone(), span(6), keep_traj=True, want_u8=True, y=y, cache_schedule=full, cache_drift=True))))
+    case(prec, "euler_cached_schedule_drift_sliced", l3, dict(zip(xtud, sliced(l3, 2, lambda: l3.cfm_euler(
+        x0.clone(), span(6), keep_traj=True, want_u8=True, y=y, cache_schedule=full, cache_drift=True)))))
+    case(prec, "ddpm_cached_unscheduled", u3, {"x": u3.ddpm_sample(xT.clone(), T, mode=_lib.DDPM_PRIOR, cache_interval=2, **kw, seed=1234)})
+    case(prec, "ddpm_cached_respaced_corr1", u6,
+         {"x": u6.ddpm_sample(xT.clone(), R, mode=_lib.DDPM_AMORTIZED, cond=cond, n_corrector=1, cache_interval=3, noise=draws, **sched, **rkw)})
+
+    # ---- tiled calls: 24x24 canvases, windows of the net's 16x16 at stride 8, more than one chunk ----
+    xc = randn(7401, B, 3, *CANVAS).to(DEV)
+    cc = (randn(7402, B, 3, *CANVAS) * 0.5).clamp(-1, 1).to(DEV)
+    xTc = randn(7403, B, 3, *CANVAS).to(DEV)
+    case(prec, "forward_tiled", u3, {"out": u3.forward_tiled(xc, 0.3, tiling=TILING)})
+    case(prec, "euler_tiled", u3, dict(zip(xtu, u3.cfm_euler(xc.clone(), span(3), keep_traj=True, want_u8=True, tiling=TILING))))
+    case(prec, "euler_tiled_labels_cond", l6,
+         dict(zip(xtu, l6.cfm_euler(xc.clone(), span(3), cond=cc, keep_traj=True, want_u8=True, y=y4, tiling=dict(TILING, weight="tent")))))
+    case(prec, "ddpm_tiled_amortized_corr1", u6,
+         {"x": u6.ddpm_sample(xTc.clone(), T, mode=_lib.DDPM_AMORTIZED, cond=cc, n_corrector=1, tiling=TILING, **kw, seed=1234)})
+    case(prec, "ddpm_tiled_ddim_respaced", u3, {"x": u3.ddpm_sample(xTc.clone(), R, mode=_lib.DDIM, tiling=TILING, **sched, **rkw)})
+
+    # ---- learned-variance nets (6 output channels: eps | v) ----
+    ml = r.max_log()
+    times = [r.time(k) for k in range(r.Ns)]
+    case(prec, "learned_ancestral", w3, {"x": w3.ddpm_learned(xT.clone(), R, ml, mode=_lib.DDPM_PRIOR, noise=draws, **sched, **rkw)})
+    case(prec, "learned_guided_sliced", w6, {"x": sliced(w6, 4, lambda: w6.ddpm_learned(
+        xT.clone(), R, ml, mode=_lib.DDPM_AMORTIZED, cond=cond, n_corrector=1, guidance_scale=wv, **sched, **rkw))})
+    case(prec, "learned_multistep", w3, {"x": w3.ddpm_learned(xT.clone(), R, ml, mode=_lib.DDIM, coefs=coefs, **sched)})
+    case(prec, "learned_none_times", u3, {"x": u3.ddpm_learned(xT.clone(), R, None, mode=_lib.DDPM_PRIOR, times=times, **sched, **rkw)})
+
+    # ---- x0- and v-prediction nets ----
+    for kind in ("x0", "v"):
+        case(prec, f"pred_{kind}_plain", u3, {"x": u3.ddpm_pred(xT.clone(), R, kind, mode=_lib.DDPM_PRIOR, noise=draws, **sched, **rkw)})
+        case(prec, f"pred_{kind}_guided", u6,
+             {"x": u6.ddpm_pred(xT.clone(), R, kind, mode=_lib.DDPM_AMORTIZED, cond=cond, n_corrector=1, guidance_scale=wv, **sched, **rkw)})
+    case(prec, "pred_v_guided_shaped", u6,
+         {"x": u6.ddpm_pred(xT.clone(), R, "v", mode=_lib.DDIM, shaping=shaping, cond=cond, guidance_scale=2.0, ddim_sigma=r.ddim_sigma(0.5), **sched, **rkw)})
+    case(prec, "pred_x0_multistep", u3, {"x": u3.ddpm_pred(xT.clone(), R, "x0", mode=_lib.DDIM, coefs=coefs, **sched)})
+    case(prec, "ddpm_sample_prediction_v", u3, {"x": u3.ddpm_sample(xT.clone(), R, mode=_lib.DDPM_PRIOR, prediction="v", **sched, **rkw)})
+
+    # ---- the variational bound: every step of the respaced chain in one call ----
+    ts_ = ("terms", "summary")
+    xd = x0.clamp(-1, 1)
+    vn = draws[:r.Ns].contiguous()
+    fixed, learned = r.vlb_log_variances("fixed_small"), r.vlb_log_variances("learned")
+    for nname, nk in (("injected", dict(noise=vn)), ("philox", dict(seed=55))):
+        case(prec, f"vlb_fixed_{nname}", u3, dict(zip(ts_, u3.ddpm_vlb(xd, R, fixed, learned=False, **nk))))
+        case(prec, f"vlb_learned_{nname}", w6, dict(zip(ts_, w6.ddpm_vlb(xd, R, learned, learned=True, cond=cond, times=times, **nk))))
+    case(prec, "vlb_pred_x0", u3, dict(zip(ts_, u3.ddpm_vlb(xd, R, fixed, learned=False, prediction="x0", seed=55))))
+    case(prec, "vlb_fixed_sliced", l3, dict(zip(ts_, sliced(l3, 2, lambda: l3.ddpm_vlb(xd, R, fixed, learned=False, y=y, cdf="tanh", seed=55)))))
 
 
 # ---- single forwards --------------------------------------------------------------------------------------------------------------------
