@@ -351,6 +351,19 @@ int mi355_ddim_eta_cfg_step(float* x, const float* eps, const float* z, float w,
 int mi355_renoise_step(float* x, const float* z, float a, float b, int use_philox, uint64_t seed, uint64_t offset, int64_t n, void* stream) {
   return renoise_step_launch(x, z, a, b, use_philox, seed, offset, n, S(stream));
 }
+int mi355_nullspace_step(const mi355_nullspace_op* op, int form, int pred_kind, float* x, const float* out, int64_t out_stride, const float* y,
+                         const float* z, int batch, int channels, int h, int w, float c_recip, float c_recipm1, float sa, float sb, float a, float b,
+                         float lam, float sigma, int use_philox, uint64_t seed, uint64_t offset, void* stream) {
+  NullspaceStep p;
+  p.op = op; p.form = form; p.pred = pred_kind; p.x = x; p.out = out; p.out_stride = out_stride; p.y = y; p.z = z;
+  p.batch = batch; p.channels = channels; p.h = h; p.w = w;
+  p.c_recip = c_recip; p.c_recipm1 = c_recipm1; p.sa = sa; p.sb = sb; p.a = a; p.b = b; p.lam = lam; p.sigma = sigma;
+  p.use_philox = use_philox; p.seed = seed; p.offset = offset;
+  return nullspace_step_launch(p, S(stream));
+}
+int mi355_block_mean(const float* in, float* out, int64_t planes, int h, int w, int h_low, int w_low, void* stream) {
+  return block_mean_launch(in, out, planes, h, w, h_low, w_low, S(stream));
+}
 int mi355_dpmpp_step(float* x, const float* eps, float* hist, float c_recip, float c_recipm1, float cx, float c0, float c1, int64_t n, void* stream) {
   PredictorStep p = predictor(STEP_DPMPP, x, eps, c_recip, c_recipm1, n);
   p.hist = hist; p.a = cx; p.b = c0; p.c = c1;

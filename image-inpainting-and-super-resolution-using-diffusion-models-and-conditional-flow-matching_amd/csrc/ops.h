@@ -343,6 +343,23 @@ struct PredictorStep {
   int pred = PRED_EPS; float sa = 0.f, sb = 0.f;   // what `eps` holds (PRED_*); sa, sb are read by PRED_V alone
 };
 int predictor_step_launch(const PredictorStep& p, hipStream_t s);
+// The null-space (DDNM) predictor step (nullspace.hip; the arithmetic: its file comment and include/mi355_sampler.h): the data prediction of the state
+// [batch, channels, h, w] is rectified against the measurement y of `op` with the step's lam, then the state moves from it by form 0 (ancestral: a, b =
+// posterior_mean_coef1, coef2) or form 1 (DDIM(eta): a = acp_prev).  out: the network output, image b at out + b * out_stride (0: contiguous); pred, sa,
+// sb: PRED_*.  Noise as the predictor steps'.  One launch; check_nullspace_op holds the refusals of an operator against an h x w state, prefixed by `who`.
+struct NullspaceStep {
+  const mi355_nullspace_op* op = nullptr;
+  int form = 0;
+  float* x = nullptr; const float* out = nullptr; int64_t out_stride = 0; const float* y = nullptr; const float* z = nullptr;
+  int batch = 0, channels = 0, h = 0, w = 0;
+  float c_recip = 0.f, c_recipm1 = 0.f, a = 0.f, b = 0.f, lam = 0.f, sigma = 0.f;
+  int use_philox = 0; uint64_t seed = 0, offset = 0;
+  int pred = PRED_EPS; float sa = 0.f, sb = 0.f;
+};
+int check_nullspace_op(const char* who, const mi355_nullspace_op* op, int h, int w);
+int nullspace_step_launch(const NullspaceStep& p, hipStream_t s);
+// out [planes, h_low, w_low] = the block means of in [planes, h, w]: A of operator kind 1, in the step's summation order (the same bits)
+int block_mean_launch(const float* in, float* out, int64_t planes, int h, int w, int h_low, int w_low, hipStream_t s);
 // The statistics behind `shape`, one workgroup per image (and detail [B, 4] = sigma_c, sigma_g, s_raw, 0 when not null); check_x0_shaping holds the
 // refusals of a mi355_x0_shaping (null: none), each prefixed by `who`.
 int check_x0_shaping(const char* who, const mi355_x0_shaping* sh, int guided);

@@ -483,6 +483,14 @@ struct LoopSched {
   CacheRun* cache = nullptr;
   // mi355_ddpm_pred_sample: what the net's output stands for (PRED_*, ops.h); every step, the correctors and the statistics launch form x0_pre of the kind
   int pred = PRED_EPS;
+  // mi355_ddpm_nullspace_sample: the predictor of step i is the null-space step (nullspace.hip) of the operator ns_op on the measurement ns_y with
+  // ns_lam[i]; form 0 (the ancestral modes) with ns_sigma[i], form 1 (MI355_DDIM) with ddim_sigma[i].  wide_out: the net writes [evalB, 2 * channels,
+  // H, W] and the step reads its eps channels under the image stride 2 * per (form 1 alone: no variance is read)
+  const mi355_nullspace_op* ns_op = nullptr;
+  const float* ns_y = nullptr;
+  const float* ns_lam = nullptr;
+  const float* ns_sigma = nullptr;
+  bool wide_out = false;
 };
 // emb: row i = the evaluation of step i (ddpm_times(Ns), or a schedule's tau_i / train_steps), selected whenever step i runs, revisits included.
 int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const DdpmLoop& a, const LoopSched& ls, int channels, const mi355_ddpm_tables* tb,
@@ -521,6 +529,19 @@ int ddpm_loop(mi355_unet* net, const Scratch& sc, const EvalEmb& emb, const Ddpm
     if (rc) return rc;
     if (ls.cache && (rc = ls.cache->after(eval, s))) return rc;
     ++eval;
+    if (ls.ns_op) {
+      NullspaceStep q;
+      q.op = ls.ns_op; q.form = mode == MI355_DDIM ? 1 : 0; q.x = x; q.out = eps; q.out_stride = ls.wide_out ? 2 * sper : 0; q.y = ls.ns_y;
+      q.batch = batch; q.channels = channels; q.h = q.w = net->cfg.image_size;
+      q.c_recip = tb->sqrt_recip_alphas_cumprod[i]; q.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[i]; q.lam = ls.ns_lam[i]; q.seed = opt->seed;
+      q.pred = ls.pred;
+      if (ls.pred == PRED_V) { q.sa = tb->sqrt_alphas_cumprod[i]; q.sb = tb->sqrt_one_minus_alphas_cumprod[i]; }
+      bool draws = i > 0;   // step 0 draws none in either form
+      if (q.form == 1) { q.a = tb->alphas_cumprod_prev[i]; q.sigma = ls.ddim_sigma ? ls.ddim_sigma[i] : 0.f; draws = draws && ls.ddim_sigma; }
+      else { q.a = tb->posterior_mean_coef1[i]; q.b = tb->posterior_mean_coef2[i]; q.sigma = ls.ns_sigma[i]; }
+      if (draws && (rc = next_noise(q.z, q.use_philox, q.offset))) return rc;
+      return nullspace_step_launch(q, s);
+    }
     PredictorStep p;
     p.x = x; p.eps = eps; p.c_recip = tb->sqrt_recip_alphas_cumprod[i]; p.c_recipm1 = tb->sqrt_recipm1_alphas_cumprod[i];
     p.seed = opt->seed; p.guide = a.guide; p.per = sper; p.shape = ls.shape; p.n = n;
@@ -658,6 +679,7 @@ struct DdpmCall {
   bool count_step = false;          // mi355_unet_get_stats: the last evaluation AND the launches of its step (the multistep and shaped entry points)
   const mi355_feature_cache* cache = nullptr;   // mi355_ddpm_sample_sched_cached (checked by check_cache)
   const TileSpec* tile = nullptr;   // mi355_ddpm_sample_tiled (checked by check_tile_plan): x, cond and noise are canvases, spec.batch is the chunk
+  const int32_t* labels = nullptr;  // mi355_ddpm_nullspace_sample: class labels of the plain (unguided, untiled) loop
 };
 DdpmCall ddpm_call(const char* who, int batch, const DdpmGuidance* guided) {
   DdpmCall c = {};
@@ -674,7 +696,7 @@ int ddpm_run(DdpmCall& c, mi355_unet* net, float* x, int channels, const float* 
   const bool learned = c.ls.lv_max_log != nullptr;
   const char* const width = learned ? "var->learned needs a net whose out_channels == 2 * channels (eps and the variance channels)"
                                     : "eps model must output the state's channel count";
-  const int eps_channels = learned ? 2 * channels : channels;
+  const int eps_channels = learned || c.ls.wide_out ? 2 * channels : channels;
   if (g) {
     const int32_t* const labels = g->labels; const int null_label = g->null_label;
     MI355_REQUIRE(mode == MI355_DDPM_AMORTIZED || mode == MI355_DDIM, -1,
@@ -699,7 +721,7 @@ int ddpm_run(DdpmCall& c, mi355_unet* net, float* x, int channels, const float* 
   const int64_t hw = c.tile ? (int64_t)c.tile->g.Hc * c.tile->g.Wc : (int64_t)net->cfg.image_size * net->cfg.image_size;
   const int64_t per = (int64_t)channels * hw, n = (int64_t)batch * per;
   EvalEmb emb;   // row i (block of num_classes rows with labels) = step i
-  if (int rc = emb.init(net, sc, c.th.data(), tb->Ns, g && g->labels, true, s)) return rc;
+  if (int rc = emb.init(net, sc, c.th.data(), tb->Ns, (g && g->labels) || c.labels, true, s)) return rc;
   DdpmLoop a = {};
   a.who = c.who;
   TiledEval te;
@@ -721,7 +743,7 @@ int ddpm_run(DdpmCall& c, mi355_unet* net, float* x, int channels, const float* 
     a.cond_corr = amortized ? sc.none : nullptr;
   } else {
     if (amortized) { if (int rc = fill_launch(sc.none, opt->none_value, n, s)) return rc; }
-    a.state = x; a.evalB = batch; a.mask_cond = cond;
+    a.state = x; a.evalB = batch; a.mask_cond = cond; a.labels_pred = c.labels;
     // the net's condition input on predictor steps / on corrector steps (the reference's corrector calls
     // x0_model without the condition, sampling.py:116 -> none_like)
     a.cond_pred = !amortized ? nullptr : ((mode == MI355_DDPM_AMORTIZED || (mode == MI355_DDIM && cond)) ? cond : sc.none);
@@ -1105,6 +1127,63 @@ int mi355_ddpm_pred_sample(mi355_unet* net, float* x, int channels, const float*
   const OverLoops o{"ddpm_pred_sample", true, true, var, shaping, pred};
   return ddpm_over_loops(o, net, x, channels, cond, labels, null_label, guided, w, w_dev, tb, opt, sched, msched, noise, n_noise_draws, batch, workspace,
                          workspace_bytes, stream);
+}
+
+// Null-space (DDNM) restoration: the scheduled loop with the null-space predictor (LoopSched::ns_op).  Every refusal before any launch.
+int64_t mi355_ddpm_nullspace_workspace_bytes(const mi355_unet* net, int batch) {
+  if (!net || batch <= 0) { mi355_set_error("ddpm_nullspace_workspace_bytes: bad argument"); return -1; }
+  return layout_bytes(net, plain_spec(batch));
+}
+
+int mi355_ddpm_nullspace_sample(mi355_unet* net, float* x, int channels, const float* y, const mi355_nullspace_op* op, const int32_t* labels,
+                                const mi355_ddpm_tables* tb, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                                const mi355_nullspace_schedule* ns, const mi355_ddpm_prediction* pred, const float* noise, int64_t n_noise_draws,
+                                int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* const who = "ddpm_nullspace_sample";
+  const std::string f = std::string(who) + ": ";
+  MI355_REQUIRE(tb && opt, -1, f + "tables or opt is null");
+  MI355_REQUIRE(y, -1, f + "y is null");
+  MI355_REQUIRE(op, -1, f + "op is null");
+  MI355_REQUIRE(ns, -1, f + "ns is null");
+  MI355_REQUIRE(opt->mode == MI355_DDPM_PRIOR || opt->mode == MI355_DDIM, -1,
+                f + "opt->mode must be MI355_DDPM_PRIOR (form 0, the ancestral step) or MI355_DDIM (form 1)");
+  MI355_REQUIRE(opt->n_corrector == 0, -1, f + "opt->n_corrector must be 0 (no corrector is built behind the null-space step)");
+  const int K = tb->Ns;
+  const bool form1 = opt->mode == MI355_DDIM;
+  MI355_REQUIRE(form1 || ns->sigma || K <= 0, -1, f + "ns->sigma is null (form 0 takes the noise std of every step from it)");
+  MI355_REQUIRE(!form1 || !ns->sigma, -1, f + "ns->sigma given in form 1 (MI355_DDIM takes its sigma from sched->ddim_sigma)");
+  MI355_REQUIRE(ns->lam || K <= 0, -1, f + "ns->lam is null");
+  for (int k = 0; k < K; ++k) {
+    MI355_REQUIRE(ns->lam[k] >= 0.f && ns->lam[k] <= 3.0e38f, -1, f + "ns->lam must be finite and >= 0");
+    MI355_REQUIRE(ns->lam[k] <= 1.f, -1, f + "ns->lam must be <= 1");
+    if (ns->sigma) MI355_REQUIRE(ns->sigma[k] >= 0.f && ns->sigma[k] <= 3.0e38f, -1, f + "ns->sigma must be finite and >= 0");
+  }
+  DdpmCall c = ddpm_call(who, batch, nullptr);
+  if (pred) {
+    MI355_REQUIRE(pred->kind >= PRED_EPS && pred->kind <= PRED_V, -1, f + "pred->kind must be 0 (eps), 1 (x0) or 2 (v)");
+    if (pred->kind == PRED_V)
+      MI355_REQUIRE((tb->sqrt_alphas_cumprod && tb->sqrt_one_minus_alphas_cumprod) || K <= 0, -1,
+                    f + "pred->kind 2 (v) needs tables->sqrt_alphas_cumprod and tables->sqrt_one_minus_alphas_cumprod");
+  }
+  if (sched) {
+    if (int rc = check_schedule(who, tb, opt, sched, false, c.ls)) return rc;   // starts c.ls afresh
+    c.th = sched_times(K, sched);
+  } else {
+    c.th = ddpm_times(K);
+  }
+  MI355_REQUIRE(net && x && workspace && batch > 0, -1, f + "bad argument (net, x, workspace, batch)");
+  MI355_REQUIRE(net->cfg.in_channels == channels, -2,
+                f + "net: an unconditional net is needed (in_channels == channels; a 2C-input amortized net sees a condition this sampler does not give)");
+  MI355_REQUIRE(net->cfg.out_channels == channels || net->cfg.out_channels == 2 * channels, -2, f + "net: out_channels must be channels or 2 * channels");
+  const bool wide = net->cfg.out_channels == 2 * channels;
+  MI355_REQUIRE(!wide || form1, -2,
+                f + "net: a 2C-output (learned-variance) net is read in form 1 (MI355_DDIM) alone: its variance and DDNM+'s are not reconciled");
+  MI355_REQUIRE(!labels || net->num_classes > 0, -1, f + "labels: class labels given to a net built without num_classes");
+  if (int rc = check_nullspace_op(who, op, net->cfg.image_size, net->cfg.image_size)) return rc;
+  if (pred) c.ls.pred = pred->kind;
+  c.ls.ns_op = op; c.ls.ns_y = y; c.ls.ns_lam = ns->lam; c.ls.ns_sigma = ns->sigma; c.ls.wide_out = wide;
+  c.labels = labels; c.count_step = true;
+  return ddpm_run(c, net, x, channels, nullptr, tb, opt, noise, n_noise_draws, workspace, workspace_bytes, stream);
 }
 
 // The variational bound of a DDPM net on data x0 (the formulas: include/mi355_sampler.h): steps K-1 .. 0, each the noising launch into the workspace's

@@ -17,90 +17,15 @@
 // x0 = c_recip*x - c_recipm1*eps (c ~ 1e3 at high noise levels) tracks the reference bit-for-bit where possible.
 #pragma clang fp contract(off)
 
-#include "philox.h"
+#include "step_common.h"   // launch_ew4, ld4 / st4, noise4, x0_pre, Pred<K>, ld4_eps, pred_form, ddim_eta_coefs: shared with nullspace.hip
 
 namespace {
 
-// Every kernel below handles 4 consecutive elements per thread (16-B accesses) with a scalar tail.
-template <typename F>
-__global__ void __launch_bounds__(256) ew4_kernel(int64_t n, F f) {
-  const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x);
-  const int64_t i = i4 * 4;
-  if (i >= n) return;
-  f(i, i4, (int)((n - i) < 4 ? (n - i) : 4));
-}
-
-template <typename F>
-int launch_ew4(int64_t n, hipStream_t s, F f) {
-  if (n <= 0) return 0;
-  const int64_t nthreads = (n + 3) / 4;
-  hipLaunchKernelGGL(ew4_kernel<F>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, n, f);
-  MI355_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-__device__ inline void ld4(const float* p, int64_t i, int cnt, float (&v)[4]) {
-  if (cnt == 4 && ((reinterpret_cast<uintptr_t>(p + i) & 15) == 0)) {
-    f32x4 t = *reinterpret_cast<const f32x4*>(p + i);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    for (int j = 0; j < 4; ++j) v[j] = j < cnt ? p[i + j] : 0.f;
-  }
-}
-__device__ inline void st4(float* p, int64_t i, int cnt, const float (&v)[4]) {
-  if (cnt == 4 && ((reinterpret_cast<uintptr_t>(p + i) & 15) == 0)) {
-    *reinterpret_cast<f32x4*>(p + i) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-    for (int j = 0; j < cnt; ++j) p[i + j] = v[j];
-  }
-}
-__device__ inline void noise4(const float* z, int use_philox, uint64_t seed, uint64_t offset4, int64_t i, int64_t i4, int cnt,
-                              float (&zz)[4]) {
-  if (z) ld4(z, i, cnt, zz);
-  else if (use_philox) randn4(seed, offset4 + (uint64_t)i4, zz);
-  else { zz[0] = zz[1] = zz[2] = zz[3] = 0.f; }
-}
-
-// x0_hat before its clip, the ONE expression every predictor step and x0_shape_stats_kernel evaluate (product, product, difference: this file has
-// contraction off), so that the order statistic the stats kernel selects is an element of what the step clamps
-__device__ inline float x0_pre(float c_recip, float c_recipm1, float x, float e) { return c_recip * x - c_recipm1 * e; }
-// What the network output `o` stands for (PRED_*, ops.h), resolved at compile time: x0_pre of the kind.  eps: the expression above on the step's own
-// c_recip, c_recipm1 (nothing carried).  x0: the output itself, no arithmetic, x is not read for it.  v (Salimans & Ho 2022): sa x - sb o with sa =
-// sqrt_alphas_cumprod, sb = sqrt_one_minus_alphas_cumprod of the step, the same three roundings.
-template <int K> struct Pred;
-template <> struct Pred<PRED_EPS> {
-  __device__ inline float pre(float c_recip, float c_recipm1, float x, float o) const { return x0_pre(c_recip, c_recipm1, x, o); }
-};
-template <> struct Pred<PRED_X0> {
-  __device__ inline float pre(float, float, float, float o) const { return o; }
-};
-template <> struct Pred<PRED_V> {
-  float sa, sb;
-  __device__ inline float pre(float, float, float x, float o) const { return x0_pre(sa, sb, x, o); }
-};
 // classifier-free guidance of one element: eps_u + w (eps_c - eps_u), the difference, the product and the sum each rounded
 __device__ inline float cfg_mix(float ec, float eu, float w) {
   const float d = ec - eu;
   const float p = w * d;
   return eu + p;
-}
-// Four elements of a per-image strided tensor: element r of image b sits at p[b * stride + r] (the eps channels of a [B, 2C, H, W] network output:
-// per = C H W, stride = 2 per).  i indexes the dense [B][per] state; a group of four may straddle images when per % 4 != 0.
-__device__ inline void ld4_strided(const float* p, int64_t per, int64_t stride, int64_t i, int cnt, float (&v)[4]) {
-  int64_t img = i / per, r = i - img * per;
-  if (cnt == 4 && r + 4 <= per) { ld4(p + img * stride + r, 0, 4, v); return; }
-#pragma unroll
-  for (int l = 0; l < 4; ++l) v[l] = 0.f;
-  for (int l = 0; l < cnt; ++l) {
-    while (r >= per) { r -= per; ++img; }
-    v[l] = p[img * stride + r];
-    ++r;
-  }
-}
-// eps of image b at eps + b * stride; stride == per: the contiguous read.  The same rule reads v (the variance channels) at eps + per.
-__device__ inline void ld4_eps(const float* eps, int64_t per, int64_t stride, int64_t i, int cnt, float (&v)[4]) {
-  if (stride == per) ld4(eps, i, cnt, v);
-  else ld4_strided(eps, per, stride, i, cnt, v);
 }
 __device__ inline void cfg_eps4(const float* eps, int64_t nu, float w, const float* w_dev, int64_t per, int64_t stride, int64_t i, int cnt, float (&ev)[4]) {
   float ec[4], eu[4], wv[4] = {w, w, w, w};
@@ -157,12 +82,6 @@ template <bool SH> struct X0Rows {
     else return clip_nan(pr.pre(c_recip, c_recipm1, x, e), -1.f, 1.f);
   }
 };
-// run f(Pred<K>) for a prediction kind (checked by the caller)
-template <typename F> int pred_form(int pred, float sa, float sb, F&& f) {
-  if (pred == PRED_X0) return f(Pred<PRED_X0>{});
-  if (pred == PRED_V) return f(Pred<PRED_V>{sa, sb});
-  return f(Pred<PRED_EPS>{});
-}
 // run f(EpsSrc<CFG>, X0Rows<SH>, Pred<K>) for the form predictor_step_launch was asked for
 template <typename F> int step_form(bool cfg, const float* eps, int64_t n, float w, const float* w_dev, int64_t per, int64_t stride, const float* shape, int pred,
                                     float sa, float sb, F&& f) {
@@ -324,12 +243,6 @@ int ddim_step_form(E es, R rows, P pr, float* x, float c_recip, float c_recipm1,
 // the two square roots taken here on the host (1 - acp_prev - sigma^2 left to right, sigma^2 rounded).  Noise as the ancestral step; with neither z
 // nor Philox the noise term is not added at all, so sigma = 0 without noise gives the DDIM step's bits.
 namespace {
-struct DdimEta { float sa, sb; };
-inline DdimEta ddim_eta_coefs(float acp_prev, float sigma) {
-  const float s2 = sigma * sigma;
-  const float r = 1.0f - acp_prev;
-  return {sqrtf(acp_prev), sqrtf(fmaxf(r - s2, 0.f))};
-}
 template <class E, class R, class P>
 int ddim_eta_step_form(E es, R rows, P pr, float* x, const float* z, float c_recip, float c_recipm1, float sa, float sb, float sigma, int noisy, int use_philox,
                        uint64_t seed, uint64_t off4, int64_t n, hipStream_t s) {

@@ -72,6 +72,29 @@ class RePaint(Replacement):
             raise ValueError(f"n_resample must be an int >= 1, got {self.n_resample!r}")
 
 
+class NullSpace(Conditioning):
+    """Null-space restoration with an unconditional DDPM net (DDNM: Wang, Yu, Zhang, ICLR 2023): every step rectifies its data prediction,
+    x0_hat <- x0_hat - lam A^+(A x0_hat - y), for the likelihood's linear operator A (in-/out-painting masks, AveragePooling, LowResolution with an
+    integer factor): one evaluation per step, no backward, no step size.  sigma_y: the noise std of the measurement in the data's units (> 0:
+    DDNM+, DDPM.nullspace_coefs; the ancestral form only).  eta: None = the ancestral form; a number >= 0 = the DDIM(eta) form with
+    ddpm.ddim_sigma(eta).  jump_length, n_resample: DDNM's time travel, the walk repaint_walk(ddpm.Ns, jump_length, n_resample); (1, 1) is the
+    plain descent.  No reference counterpart; sample quality is untested."""
+    KEY, PARAMS = "null_space", ("sigma_y", "eta", "jump_length", "n_resample")
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if isinstance(self.sigma_y, bool) or not (float(self.sigma_y) >= 0.0 and float(self.sigma_y) < float("inf")):
+            raise ValueError(f"sigma_y must be finite and >= 0, got {self.sigma_y!r}")
+        if self.eta is not None and (isinstance(self.eta, bool) or not (float(self.eta) >= 0.0 and float(self.eta) < float("inf"))):
+            raise ValueError(f"eta must be None (the ancestral form) or a finite number >= 0, got {self.eta!r}")
+        if self.eta is not None and float(self.sigma_y) > 0.0:
+            raise ValueError("sigma_y > 0 (DDNM+) belongs to the ancestral form: eta must be None")
+        if int(self.jump_length) != self.jump_length or self.jump_length < 1:
+            raise ValueError(f"jump_length must be an int >= 1, got {self.jump_length!r}")
+        if int(self.n_resample) != self.n_resample or self.n_resample < 1:
+            raise ValueError(f"n_resample must be an int >= 1, got {self.n_resample!r}")
+
+
 def repaint_walk(K: int, jump_length: int, n_resample: int):
     """The levels a RePaint sampler visits on a K-step chain: a restatement of the jump schedule of Lugmayr et al. 2022 (their
     get_schedule_jump with jump_n_sample = n_resample).  Level L in [0, K] is the state before step L - 1 is applied; K is noise, 0 the result.
@@ -147,7 +170,7 @@ def flow_split_index(n_steps: int, start_fraction: float) -> int:
 
 
 _REGISTRY: Dict[str, Type[Conditioning]] = {c.KEY: c for c in (Amortized, ClassifierFreeGuidance, ReconstructionGuidance, Replacement, RePaint,
-                                                               FlowReplacement, FlowReconstructionGuidance)}
+                                                               NullSpace, FlowReplacement, FlowReconstructionGuidance)}
 
 
 def get_conditioning(type_: str) -> Type[Conditioning]:

@@ -165,8 +165,50 @@ class LowResolution(Likelihood):
         return (d * d).mean(dim=(1, 2, 3))
 
 
+class AveragePooling(Likelihood):
+    """The block-mean measurement y = A(x): average pooling with window = stride = factor (an int, or (fy, fx)), the super-resolution operator of
+    DDNM (Wang, Yu, Zhang 2023), and the consistency term mean((A(x) - y)^2).  No reference counterpart.  The image size must be a multiple of
+    the factor.  Device tensors: mi355_block_mean (the summation order of the null-space step); CPU tensors: F.avg_pool2d."""
+
+    def __init__(self, factor):
+        fy, fx = (factor, factor) if not isinstance(factor, (tuple, list)) else tuple(factor)
+        for f in (fy, fx):
+            if isinstance(f, bool) or int(f) != f or f < 1:
+                raise ValueError(f"factor must be an int >= 1 (or a pair of them), got {factor!r}")
+        self.factor = (int(fy), int(fx))
+
+    @classmethod
+    def from_configdict(cls, config):
+        return cls(config["factor"])
+
+    def _low(self, x):
+        fy, fx = self.factor
+        if x.shape[-2] % fy or x.shape[-1] % fx:
+            raise ValueError(f"the image size {tuple(x.shape[-2:])} must be a multiple of the factor {self.factor}")
+        return x.shape[-2] // fy, x.shape[-1] // fx
+
+    def _sample(self, images):
+        size = self._low(images)
+        if images.is_cuda:
+            from mi355.ops import default_ops
+
+            return default_ops.block_mean(images.detach().float().contiguous(), size)
+        return F.avg_pool2d(images, kernel_size=self.factor, stride=self.factor)
+
+    def sample(self, x):
+        return self._sample(x)   # per-image pooling is independent: the whole batch in one call (one launch on the device)
+
+    def none_like(self, x):
+        hl, wl = self._low(x)
+        return torch.zeros(x.shape[0], x.shape[1], hl, wl, dtype=x.dtype, device=x.device)
+
+    def loss(self, x, condition):
+        d = self._sample(x) - condition
+        return (d * d).mean(dim=(1, 2, 3))
+
+
 _BY_NAME: Dict[str, Type[Likelihood]] = {"inpainting": InPainting, "outpainting": OutPainting, "hyperresolution": HyperResolution,
-                                         "lowresolution": LowResolution}
+                                         "lowresolution": LowResolution, "averagepooling": AveragePooling}
 
 
 def get_likelihood(type_: str) -> Type[Likelihood]:

@@ -38,7 +38,7 @@ import torch
 from mi355 import _lib
 from mi355.ops import default_ops
 
-from .conditioning import Amortized, ClassifierFreeGuidance, Conditioning, ReconstructionGuidance, RePaint, Replacement, repaint_walk
+from .conditioning import Amortized, ClassifierFreeGuidance, Conditioning, NullSpace, ReconstructionGuidance, RePaint, Replacement, repaint_walk
 from .likelihoods import Likelihood
 from .sde_diffusion import DDPM
 
@@ -566,6 +566,10 @@ def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Con
                                       tiling=tiling)
     if isinstance(conditioning, Replacement):
         return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, feature_cache=feature_cache, tiling=tiling)
+    if isinstance(conditioning, NullSpace):
+        _refuse_feature_cache(feature_cache, "NullSpace (the null-space loop)")
+        _refuse_tiling(tiling, "NullSpace (the null-space loop)")
+        return _nullspace_sample_fn(eps_model, ddpm, conditioning, likelihood)
     if isinstance(conditioning, ReconstructionGuidance):
         _refuse_feature_cache(feature_cache, "ReconstructionGuidance (the backward pass needs a whole forward)")
         _refuse_tiling(tiling, "ReconstructionGuidance (the backward pass needs a whole forward)")
@@ -684,6 +688,111 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
             for _ in range(conditioning.n_corrector):
                 epc = eng.forward(xi, t)
                 _corrector(epc, xi, i, T, ddpm, conditioning.delta, noise)
+        return process_x0(xi)
+
+    return sample
+
+
+def _nullspace_operator(likelihood, xT):
+    """The mi355_nullspace_op of a likelihood for a state of xT's shape: InPainting / OutPainting -> the mask (kind 0), AveragePooling -> the block
+    mean (kind 1), LowResolution -> the bilinear taps of an integer factor (kind 2).  Anything else is refused by name."""
+    name = type(likelihood).__name__
+    H, W = int(xT.shape[-2]), int(xT.shape[-1])
+    if hasattr(likelihood, "pad_value"):
+        return default_ops.nullspace_op("mask", pad_value=float(likelihood.pad_value))
+    if name == "HyperResolution":
+        raise NotImplementedError("NullSpace is not built for HyperResolution: its condition is the re-enlarged image, an operator without a disjoint "
+                                  "pseudo-inverse - measure with LowResolution (the low-resolution image itself) or AveragePooling")
+    if name == "AveragePooling":
+        fy, fx = likelihood.factor
+        if H % fy or W % fx:
+            raise NotImplementedError(f"NullSpace: the AveragePooling factor {likelihood.factor} does not divide the image size {(H, W)}")
+        return default_ops.nullspace_op("block_mean", (xT.shape[0], xT.shape[1], H // fy, W // fx))
+    if name == "LowResolution":
+        hl, wl = int(likelihood.target_height), int(likelihood.target_width)
+        if hl < 1 or wl < 1 or H % hl or W % wl:
+            raise NotImplementedError(f"NullSpace: the LowResolution factor {(H / max(hl, 1), W / max(wl, 1))} (image {(H, W)} over target {(hl, wl)}) is "
+                                      "not an integer: the rows of the bilinear reduction are disjoint for integer factors only")
+        return default_ops.nullspace_op("bilinear", (xT.shape[0], xT.shape[1], hl, wl))
+    raise NotImplementedError(f"NullSpace has no linear operator for likelihood {name}")
+
+
+def _nullspace_sample_fn(eps_model, ddpm, conditioning: NullSpace, likelihood):
+    """BUILD-DEFINED EXTENSION (no reference counterpart): DDNM (Wang, Yu, Zhang 2023) with an unconditional eps_model.  sample(xT, condition,
+    y=None): condition is likelihood.sample's measurement, y optional class labels [B] of a class-conditional net (the fused path).  Per step one
+    evaluation and ONE launch, the null-space step (mi355_nullspace_step): the data prediction is rectified against the measurement with
+    ddpm.nullspace_coefs(sigma_y)'s lam, then the state moves by the ancestral step (eta None; its sigma from the same call) or the DDIM(eta) step
+    (ddpm.ddim_sigma(eta); eta 0: deterministic, no draw).  jump_length / n_resample: the walk of DDNM's time travel.  Fused path (eps_model built by
+    make_eps_model for this very schedule): the whole loop in mi355_ddpm_nullspace_sample; any other callable: a host loop over nullspace_step_.
+    x0- and v-prediction chains and respaced chains are taken; a learned-variance chain in the DDIM form only.  Sample quality is untested."""
+    form = 0 if conditioning.eta is None else 1
+    sigma_y = float(conditioning.sigma_y)
+    if form == 1 and sigma_y > 0.0:
+        raise ValueError("sigma_y > 0 (DDNM+) belongs to the ancestral form (eta=None): the DDIM form has no closed-form noise split here")
+    if getattr(ddpm, "x0_shaping", None) is not None:
+        raise NotImplementedError("x0 shaping (DDPM.with_x0_shaping) is not built for NullSpace: the rectification works on the statically clipped x0_hat")
+    if getattr(ddpm, "learned_variance", False) and form == 0:
+        raise NotImplementedError("a learned-variance chain (DDPM.with_learned_variance) is taken by NullSpace in the DDIM form only (eta=): its "
+                                  "learned variance and DDNM+'s are not reconciled")
+    if _custom_times(ddpm) is not None:
+        raise NotImplementedError("NullSpace is not built for a chain with a time_scale (DDPM.from_betas(..., time_scale=))")
+    for what in ("n_corrector", "guidance_scale", "order"):   # correctors, classifier-free guidance, multistep solvers: not parameters of NullSpace
+        if getattr(conditioning, what, None):
+            raise NotImplementedError(f"{what} is not built for NullSpace")
+    pred = _pred_of(ddpm)
+    wide = bool(getattr(ddpm, "learned_variance", False))
+    lam, sig = ddpm.nullspace_coefs(sigma_y)
+    dsig = ddpm.ddim_sigma(float(conditioning.eta)) if form == 1 and float(conditioning.eta) != 0.0 else None
+    walk = repaint_walk(ddpm.Ns, conditioning.jump_length, conditioning.n_resample)
+    if all(b < a for a, b in zip(walk, walk[1:])):
+        walk = None
+
+    @torch.no_grad()
+    def sample(xT, condition, y=None):
+        global _draw_counter
+        T = _tables(ddpm)
+        op = _nullspace_operator(likelihood, xT)
+        condition = condition.to(xT.device).float().contiguous()
+        xi = xT.detach().clone().float().contiguous()
+        engine = _fast_engine(eps_model, ddpm, xT)
+        if engine is not None:
+            out_channels = getattr(engine, "out_channels", None)
+            if out_channels is not None:
+                _check_width(out_channels, xi, True if wide else None)
+            noise, seed = None, int(torch.initial_seed()) & ((1 << 63) - 1)
+            if _injected is not None:
+                noise = torch.stack([z.to(xi.device, torch.float32) for z in _injected]).contiguous()
+            else:
+                seed = (seed + 0x9E3779B97F4A7C15 * (_draw_counter + 1)) & ((1 << 63) - 1)
+                _draw_counter += 1
+            sched = {}
+            if getattr(ddpm, "timesteps", None) is not None or dsig is not None or walk is not None:
+                sched = dict(timesteps=getattr(ddpm, "timesteps", None) or tuple(range(ddpm.Ns)), train_steps=int(getattr(ddpm, "base_Ns", ddpm.Ns)),
+                             ddim_sigma=dsig, walk=walk)
+            engine.ddpm_nullspace(xi, T, condition, op, lam, sig if form == 0 else None, mode=_lib.DDIM if form else _lib.DDPM_PRIOR, prediction=pred,
+                                  labels=y, noise=noise, seed=seed, **sched)
+            return xi
+        if y is not None:
+            raise NotImplementedError("class labels run inside the fused loop: pass an eps_model built by make_eps_model(network, ddpm) for this "
+                                      "schedule and device tensors (an arbitrary callable takes (x, i) alone)")
+        noise = _Noise(xi)
+        for level, down in _walk_moves(ddpm.Ns, walk):
+            if not down:   # q(x_level+1 | x_level): one draw
+                z, ph = noise.next()
+                _ops.renoise_(xi, z, float(T["alphas"][level].sqrt()), float(T["betas"][level].sqrt()), ph)
+                continue
+            i = level - 1
+            out = eps_model(xi, _times(xi, i)).float().contiguous()
+            _check_width(out.shape[1], xi, True if wide else None)
+            cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
+            if form == 0:
+                z, ph = noise.next() if i > 0 else (None, None)
+                _ops.nullspace_step_(op, 0, pred, xi, out, condition, cr, crm1, float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i]),
+                                     lam=float(lam[i]), sigma=float(sig[i]), z=z, philox=ph, **_pred_kw(T, i))
+            else:
+                z, ph = noise.next() if (dsig is not None and i > 0) else (None, None)
+                _ops.nullspace_step_(op, 1, pred, xi, out, condition, cr, crm1, float(T["alphas_cumprod_prev"][i]), lam=float(lam[i]),
+                                     sigma=float(dsig[i]) if dsig is not None else 0.0, z=z, philox=ph, **_pred_kw(T, i))
         return process_x0(xi)
 
     return sample

@@ -325,6 +325,31 @@ class DDPM(nn.Module):
         prev = self.alphas_cumprod_prev.detach().to("cpu", torch.float64)
         return (float(eta) * torch.sqrt((1.0 - prev) / (1.0 - acp)) * torch.sqrt(1.0 - acp / prev)).to(torch.float32)
 
+    def nullspace_coefs(self, sigma_y: float = 0.0):
+        """BUILD-DEFINED EXTENSION (no reference counterpart): CPU fp32 (lam, sigma), each [Ns]: the per-step rectification weight and noise std of
+        the null-space samplers (DDNM / DDNM+: Wang, Yu, Zhang 2023, eq. 17-19 in the simplified form; mi355_ddpm_nullspace_sample) for a
+        measurement with noise std sigma_y, in the units of the data ([-1, 1] scale).  With a_i = posterior_mean_coef1[i] and s_i = exp(0.5 *
+        posterior_log_variance_clipped[i]) for i > 0, s_0 = 0 (step 0 draws no noise), of host_tables():
+            lam_i   = 1 if sigma_y == 0 or s_i >= a_i sigma_y, else s_i / (a_i sigma_y)
+            sigma_i = sqrt(max(s_i^2 - (a_i lam_i sigma_y)^2, 0))
+        so that the noise the rectified prediction carries into the step, a_i lam_i sigma_y, and the noise drawn add up to the posterior's
+        variance.  sigma_y = 0 is plain DDNM: lam = 1 and sigma the posterior's.  Evaluated in fp64 from the fp32 tables and rounded once."""
+        sy = float(sigma_y)
+        if isinstance(sigma_y, bool) or not (math.isfinite(sy) and sy >= 0.0):
+            raise ValueError(f"sigma_y must be finite and >= 0, got {sigma_y!r}")
+        host = self.host_tables()
+        a = host["posterior_mean_coef1"].to(torch.float64).numpy()
+        s = np.exp(0.5 * host["posterior_log_variance_clipped"].to(torch.float64).numpy())
+        s[0] = 0.0
+        lam = np.ones_like(s)
+        if sy > 0.0:
+            small = s < a * sy
+            with np.errstate(all="ignore"):
+                lam[small] = s[small] / (a[small] * sy)
+        sigma = np.sqrt(np.maximum(s * s - (a * lam * sy) ** 2, 0.0))
+        sigma[lam < 1.0] = 0.0   # there a lam sigma_y = s: the difference is zero, not its rounding residue
+        return torch.from_numpy(lam.astype(np.float32)), torch.from_numpy(sigma.astype(np.float32))
+
     def dpm_solver_coefs(self, order: int = 2):
         """CPU fp32 (cx, c0, c1), each [Ns]: the per-step coefficients of DPM-Solver++ multistep (Lu et al. 2022, Algorithm 2) in the data-prediction
         form, x <- cx_i x + c0_i D_i + c1_i D_{i+1} with D the clipped x0_hat (mi355_dpmpp_step).  Step i takes the state from alphas_cumprod[i] to

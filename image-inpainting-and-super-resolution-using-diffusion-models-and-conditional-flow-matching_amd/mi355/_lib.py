@@ -128,6 +128,19 @@ class DDPMPredictionC(C.Structure):
     _fields_ = [("kind", C.c_int32)]
 
 
+class NullspaceOpC(C.Structure):
+    """mi355_nullspace_op (include/mi355_sampler.h): the measurement operator of the null-space samplers - 0 mask, 1 block mean, 2 bilinear taps."""
+    _fields_ = [("kind", C.c_int32), ("pad_value", C.c_float), ("h_low", C.c_int32), ("w_low", C.c_int32)]
+
+
+class NullspaceScheduleC(C.Structure):
+    """mi355_nullspace_schedule (include/mi355_sampler.h): lam and (form 0) the noise std of every step, host float[K]."""
+    _fields_ = [("lam", _FP), ("sigma", _FP)]
+
+
+NULLSPACE_KINDS = {"mask": 0, "block_mean": 1, "bilinear": 2}   # mi355_nullspace_op::kind
+
+
 PREDICTIONS = {"eps": 0, "x0": 1, "v": 2}   # DDPM.prediction -> mi355_ddpm_prediction::kind
 
 
@@ -299,6 +312,13 @@ SIGNATURES = {
     "mi355_pred_shape_stats": (_I, [_I, _VP, _VP, _F, _VP, _I, _F, _F, _F, _F, C.POINTER(X0ShapingC), _VP, _VP, _I, _I64, _VP]),
     "mi355_vlb_terms_pred": (_I, [_VP, _VP, _VP, _I64, _VP, _I, _U64, _U64, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _F, _F, _VP, _I64, _I, _I64,
                                   _VP]),
+    "mi355_nullspace_step": (_I, [C.POINTER(NullspaceOpC), _I, _I, _VP, _VP, _I64, _VP, _VP, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _U64, _U64,
+                                  _VP]),
+    "mi355_block_mean": (_I, [_VP, _VP, _I64, _I, _I, _I, _I, _VP]),
+    "mi355_ddpm_nullspace_workspace_bytes": (_I64, [_VP, _I]),
+    "mi355_ddpm_nullspace_sample": (_I, [_VP, _VP, _I, _VP, C.POINTER(NullspaceOpC), _VP, C.POINTER(DDPMTablesC), C.POINTER(DDPMOptionsC),
+                                         C.POINTER(DDPMScheduleC), C.POINTER(NullspaceScheduleC), C.POINTER(DDPMPredictionC), _VP, _I64, _I, _VP, _I64,
+                                         _VP]),
     "mi355_cfm_ab_workspace_bytes": (_I64, [_VP, _I, _I, _I, _I]),
     "mi355_cfm_ab_sample": (_I, [_VP, _VP, _I, _VP, _I, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),
     "mi355_cfm_ab_cfg_sample": (_I, [_VP, _VP, _I, _VP, _I, _F, _VP, _I, _F, _VP, _FP, _I, _I, _FP, _I, _FP, _FP, _FP, _VP, _VP, _I, _VP, _I64, _VP]),

@@ -936,6 +936,41 @@ class UNetEngine:
         extra = (var, _lib.x0_shaping(shaping), _lib.DDPMPredictionC(_lib.prediction_kind(prediction)))
         return self._ddpm_one_entry("ddpm_pred", "mi355_ddpm_pred_sample", "mi355_ddpm_pred_workspace_bytes", extra, keep, **loop)
 
+    def ddpm_nullspace(self, x: torch.Tensor, tables: Dict[str, torch.Tensor], y: torch.Tensor, op, lam, sigma=None, *, mode: int, prediction=None,
+                       labels: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, seed=0, timesteps=None, train_steps=None,
+                       ddim_sigma=None, walk=None):
+        """In-place null-space (DDNM) restoration with the engine's unconditional net (mi355_ddpm_nullspace_sample): every step rectifies its data
+        prediction against the measurement y of the operator op (mi355.ops.Ops.nullspace_op) with lam[k], then moves the state from it.  mode
+        DDPM_PRIOR: the ancestral form with the noise std sigma[k] (DDPM.nullspace_coefs); DDIM: the DDIM(eta) form with ddim_sigma (None:
+        deterministic), sigma must be None.  labels: class labels [B] of a class-conditional net.  prediction, noise, seed, timesteps / train_steps,
+        ddim_sigma, walk: as in ddpm_pred (walk: DDNM's time travel, conditioning.repaint_walk).  A net that writes 2C channels is read in the DDIM
+        form alone.  -> x"""
+        B = x.shape[0]
+        if not isinstance(op, _lib.NullspaceOpC):
+            raise TypeError("op must be a NullspaceOpC (mi355.ops.Ops.nullspace_op)")
+        if y is None:
+            raise ValueError("y (the measurement) is needed")
+        if y.shape[0] != B:
+            raise ValueError("the measurement y must have x's batch size")
+        if noise is not None and noise.shape[1:] != x.shape:
+            raise ValueError("injected noise must be [n_draws, B, C, H, W]")
+        tb, keep = self._ddpm_tables(tables)
+        K = int(tb.Ns)
+        ns = _lib.NullspaceScheduleC()
+        ns.lam, t = _host_floats(lam, K, "lam", per="step")
+        keep.append(t)
+        if sigma is not None:
+            ns.sigma, t = _host_floats(sigma, K, "sigma", per="step")
+            keep.append(t)
+        sched = self._ddpm_schedule(tables, timesteps, train_steps, ddim_sigma, walk)
+        lab, _ = self._labels(labels, B)
+        opt = self._ddpm_options(mode, y, 0)
+        self._ddpm_loop("mi355_ddpm_nullspace_sample", "mi355_ddpm_nullspace_workspace_bytes", (), B, x, y, noise, tb, opt, seed=int(seed),
+                        guide=(lab, 0, 0.0, None), head=lambda ls: (C.byref(op), _lab_ptr(ls)),
+                        mid=(None if sched is None else sched[0], ns, _lib.DDPMPredictionC(_lib.prediction_kind(prediction))), draws=True)
+        del keep
+        return x
+
     @staticmethod
     def _ddpm_variance(tables, max_log, times):
         """-> (mi355_ddpm_variance, or None when neither max_log nor times is given; the host tensors it points into)."""
@@ -1055,10 +1090,10 @@ class UNetEngine:
         """mi355_ddpm_options.  The defaults are what the guided ddpm_sample path and the multistep solver pass for the fields they do not take."""
         return _lib.DDPMOptionsC(mode, n_corrector, delta, tmin, tmax, start_fraction, int(noise_condition), pad_value, none_value, int(cond is None), seed)
 
-    def _ddpm_loop(self, name, ws_fn, ws_tail, mb, x, cond, noise, tb, opt, seed=None, guide=None, flag=None, mid=(), draws=False):
+    def _ddpm_loop(self, name, ws_fn, ws_tail, mb, x, cond, noise, tb, opt, seed=None, guide=None, flag=None, mid=(), draws=False, head=None):
         """The calls of the DDPM entry point `name` on a batch run at most mb images at a time, each on a workspace of ws_fn(batch, *ws_tail).  seed:
         the Philox seed of the batch, the slices draw from seed + slice index (None: opt's own).  draws: the entry point takes injected noise.
-        guide, flag, mid: see _ddpm_call."""
+        guide, flag, mid, head: see _ddpm_call."""
         lab, nl, w, wt = guide or (None, 0, 0.0, None)
         self._fwd_state = None
         for n, (xs, cn, ls, wl), (nz,), _, sd in self._sliced(x.shape[0], mb, rows=(x, cond, lab, wt), cols=(noise,), seed=seed):
@@ -1066,15 +1101,19 @@ class UNetEngine:
                 opt.seed = sd
             ws, wsb = self._workspace_sized(ws_fn, n, *ws_tail)
             self._ddpm_call(name, xs, cn, tb, opt, n, ws, wsb, guide=guide and (ls, nl, w, wl), flag=flag, mid=mid,
-                            noise=self._noise_args(nz) if draws else ())
+                            noise=self._noise_args(nz) if draws else (), head=head)
 
-    def _ddpm_call(self, name, x, cond, tb, opt, B, ws, wsb, guide=None, flag=None, mid=(), noise=(), last=()):
+    def _ddpm_call(self, name, x, cond, tb, opt, B, ws, wsb, guide=None, flag=None, mid=(), noise=(), last=(), head=None):
         """One call of the DDPM entry point `name`, in the argument order they share: handle, x, C, cond, [labels, null_label, (guided flag,) w,
         per-image scales,] tables, options, mid, [noise, n_draws,] batch, workspace, stream, last.  guide: (labels, null_label, w, scales) where the
         entry point takes guidance, flag: its guided flag where it has one.  mid: the schedules and the entry point's own structs, each a struct
-        or None (a null pointer); noise: _noise_args where the entry point draws; last: the feature cache or the tile plan."""
+        or None (a null pointer); noise: _noise_args where the entry point draws; last: the feature cache or the tile plan.  head (with guide =
+        (labels, ...)): what the entry point takes between the condition and the tables in place of the guidance arguments, a function of the
+        (sliced) labels -> tuple (mi355_ddpm_nullspace_sample: the operator and the labels; its measurement rides in the condition's place)."""
         g = ()
-        if guide is not None:
+        if head is not None:
+            g = head(guide[0] if guide is not None else None)
+        elif guide is not None:
             lab, nl, w, wt = guide
             g = (_lab_ptr(lab), int(nl), *(() if flag is None else (int(flag),)), float(w), self._ptr(wt, "guidance_scale"))
         check(getattr(self.L, name)(self.handle, self._chk(x, "x"), x.shape[1], self._ptr(cond, "condition"), *g, C.byref(tb), C.byref(opt),

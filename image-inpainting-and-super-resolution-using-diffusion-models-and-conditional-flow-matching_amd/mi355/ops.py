@@ -289,6 +289,52 @@ class Ops:
                                                 _req(det, "detail") if detail else None, B, o.per, _stream()), "mi355_pred_shape_stats")
         return (shape, det) if detail else shape
 
+    @staticmethod
+    def nullspace_op(kind, y_shape=None, pad_value=0.0):
+        """The mi355_nullspace_op of a kind ("mask", "block_mean", "bilinear", or its number) for a measurement of shape y_shape [B, C, h_low, w_low]
+        (kinds 1, 2) resp. the sentinel pad_value of unknown pixels (kind 0)."""
+        k = _lib.NULLSPACE_KINDS.get(kind, kind)
+        if k not in (0, 1, 2):
+            raise ValueError(f'the null-space operator must be one of {sorted(_lib.NULLSPACE_KINDS)} (or 0..2), got {kind!r}')
+        if k == 0:
+            return _lib.NullspaceOpC(0, float(pad_value), 0, 0)
+        if y_shape is None or len(y_shape) != 4:
+            raise ValueError("kinds 1 and 2 need the measurement's shape [B, C, h_low, w_low]")
+        return _lib.NullspaceOpC(k, 0.0, int(y_shape[2]), int(y_shape[3]))
+
+    def nullspace_step_(self, op, form, prediction, x, out, y, c_recip, c_recipm1, a, b=0.0, lam=1.0, sigma=0.0, *, sa=0.0, sb=0.0, z=None, philox=None):
+        """The null-space (DDNM) predictor step in place, one launch (mi355_nullspace_step): the data prediction x0 of `out` (a net of the given
+        prediction; out [B, Cw >= C, H, W] is read in place) is rectified against the measurement y of the operator op (nullspace_op, or a
+        NullspaceOpC), x0h = x0 - lam * (A(x0) - y) on the taps of each row, and x [B, C, H, W] moves from x0h: form 0 the ancestral step (a, b = coef1,
+        coef2; sigma), form 1 the DDIM(eta) step (a = acp_prev; sigma).  z / philox as in ddpm_step_ (form 1 with neither: no noise term).  -> x"""
+        if x.dim() != 4:
+            raise ValueError(f"x must be [B, C, H, W], got {tuple(x.shape)}")
+        B, per, stride = self._wide_out(x, out, False)
+        if z is not None:
+            _same(x, z, "x", "z")
+        if form not in (0, 1):
+            raise ValueError("form must be 0 (ancestral) or 1 (DDIM(eta))")
+        want = tuple(x.shape) if op.kind == 0 else (x.shape[0], x.shape[1], op.h_low, op.w_low)
+        if tuple(y.shape) != want:
+            raise ValueError(f"the measurement y {tuple(y.shape)} must be {want} for this operator")
+        seed, off = philox if philox else (0, 0)
+        check(_lib.lib().mi355_nullspace_step(C.byref(op), int(form), _lib.prediction_kind(prediction), _req(x, "x"), _req(out, "out"),
+                                              0 if stride == per else stride, _req(y, "y"), _opt(z, "z"), x.shape[0], x.shape[1], x.shape[2], x.shape[3],
+                                              float(c_recip), float(c_recipm1), float(sa), float(sb), float(a), float(b), float(lam), float(sigma),
+                                              int(philox is not None and z is None), int(seed), int(off), _stream()), "mi355_nullspace_step")
+        return x
+
+    def block_mean(self, x, size):
+        """Average pooling of [..., H, W] planes to size = (h_low, w_low) with window = stride = (H / h_low, W / w_low) (mi355_block_mean): the
+        operator A of null-space kind 1, in the step's summation order.  -> [..., h_low, w_low]"""
+        if x.dim() < 2:
+            raise ValueError("x must have at least two dimensions")
+        hl, wl = int(size[0]), int(size[1])
+        out = torch.empty(tuple(x.shape[:-2]) + (hl, wl), device=x.device, dtype=torch.float32)
+        planes = x.numel() // max(1, x.shape[-2] * x.shape[-1])
+        check(_lib.lib().mi355_block_mean(_req(x, "x"), _req(out, "out"), planes, x.shape[-2], x.shape[-1], hl, wl, _stream()), "mi355_block_mean")
+        return out
+
     def q_sample(self, x0, a, b, z=None, philox=None, out=None):
         """The forward marginal q(x_k | x_0) out of place (mi355_q_sample): a x0 + b z with a = sqrt_alphas_cumprod[k], b =
         sqrt_one_minus_alphas_cumprod[k], two rounded products and a sum; z / philox as in ddpm_step_.  x0 is left as it is.  -> out"""

@@ -800,6 +800,76 @@ int mi355_vlb_terms_pred(const float* x0, const float* x_k, const float* out, in
                          float max_log, int k_is_zero, int learned, int cdf, int clip_denoised, int pred_kind, float sa, float sb, float* dst,
                          int64_t dst_stride, int batch, int64_t elems_per_image, void* stream);
 
+/* Null-space (DDNM) in-painting and super-resolution with an unconditional DDPM net: Wang, Yu, Zhang, "Zero-Shot Image Restoration Using Denoising
+ * Diffusion Null-Space Model", ICLR 2023.  No reference counterpart.  One evaluation per step, no backward, no step size: for a linear measurement
+ * y = A x the step rectifies its DATA PREDICTION, x0_hat <- x0_hat - A^+(A x0_hat - y), which keeps the net's null-space content and sets the
+ * range-space content to the measurement, and then moves the state from it.  Per element, every operation rounded to fp32 and none contracted:
+ *   x0   = clip(x0_pre(kind of prediction), -1, 1)               as every step above (mi355_ddpm_prediction; NaN-propagating clip)
+ *   r[q] = A(x0)[q] - y[q]
+ *   x0h  = x0 - lam * r[q(p)]   if p is a tap of row q, else x0  (product, then difference)
+ *   form 0 (ancestral):  x <- (coef1 * x0h + coef2 * x) + sigma * z
+ *   form 1 (DDIM(eta)):  mi355_ddim_eta_step's expression with x0h in place of x0_hat: e2 = (c_recip x - x0h) / c_recipm1,
+ *                        x <- sqrt(acp_prev) x0h + sqrt(max(1 - acp_prev - sigma^2, 0)) e2 (+ sigma z where noise is given)
+ * Form 1 takes DDIM's direction from the eps that the RECTIFIED prediction stands for: this library's convention for every DDIM step (e2 of the
+ * clipped, shaped prediction).  The authors' code keeps the net's raw eps there; the two differ wherever the rectification or the clip acts.
+ * Operators (mi355_nullspace_op): row operators with disjoint supports and equal weights inside a row, so A A^T is diagonal and A^+ r is r[q] on
+ * every tap of q.
+ *   kind 0, mask: y [B, C, H, W]; a pixel is known iff y != pad_value (likelihoods.Painting's sentinel); the row is the pixel itself.
+ *   kind 1, block mean: average pooling with window = stride = (sy, sx) = (H / h_low, W / w_low), the paper's super-resolution operator; y [B, C, h_low,
+ *     w_low].  A(x0)[q] = S / (float)(sy sx) with S summed in a FIXED order: each of the block's sy rows left to right, then the sy row sums top to
+ *     bottom.  mi355_block_mean sums in the same order: the two agree bit for bit, and from run to run.
+ *   kind 2, bilinear taps: the operator D of mi355_lowres_seed (F.interpolate, bilinear, align_corners = False) for an integer factor, with
+ *     mi355_resize_bilinear's taps, weights and operation order l0y (l0x v00 + l1x v01) + l1y (l0x v10 + l1x v11): along an axis an even factor s has
+ *     the taps s o + s / 2 - 1 and s o + s / 2 with weight 1/2 each, an odd one the single tap s o + (s - 1) / 2 with weight 1 (a tap of weight 0 is
+ *     not read; it enters the expression as 0.f, the resize kernel's bits on finite data).  Pixels that are no tap of any row are pure null space.
+ * Factors 1..32 per axis.  A NaN in x or in the network output makes every tap of its own row NaN (kinds 1, 2) resp. its own element (kind 0) and
+ * nothing else; a pixel outside the taps keeps its own value, NaN or not.  lam == 0 gives the bits of mi355_pred_step of the same form on finite
+ * inputs.  Operator refusals, before any launch, each naming its argument: kind outside 0..2 or h_low / w_low < 1 -> MI355_ERR_ARG; a non-integer
+ * factor or one above 32 -> MI355_ERR_UNSUPPORTED.
+ *
+ * mi355_nullspace_step: one step as an op, ONE launch.  x [batch, channels, h, w] in place; out: the network output, image b at out + b * out_stride
+ * (0: contiguous; 2 * channels * h * w reads the eps channels of a 2C-output net in place); y as the operator says; pred_kind 0..2 with sa, sb for v;
+ * form 0: a, b = posterior_mean_coef1, coef2; form 1: a = acp_prev (b unused); lam in [0, 1] and sigma finite >= 0 are host scalars; the noise triple
+ * (z | use_philox, seed, offset) is mi355_ddpm_step's (form 1 with neither: no noise term).  x, out, y (and z) are read once, x is written once, nothing
+ * else touches global memory, no atomics.  Kind 0 is the flat four-elements-per-thread launch of the other steps.  Kinds 1 and 2: a workgroup owns
+ * whole bands (the sy rows of a row of blocks) of the [batch * channels * h, w] row matrix - several consecutive bands, across planes, where they
+ * are small; column chunks of whole blocks where a band exceeds 1024 quads - holds x0 in LDS and reduces there; any w and any pointer offset (16-byte
+ * accesses where the address allows, as the other steps).
+ * mi355_block_mean: out [planes, h_low, w_low] = A of kind 1 applied to in [planes, h, w].
+ *
+ * mi355_ddpm_nullspace_sample: mi355_ddpm_sample_sched's loop with the predictor replaced by the step above.  opt->mode MI355_DDPM_PRIOR: form 0 with
+ * ns->sigma; MI355_DDIM: form 1 with sched->ddim_sigma (NULL: deterministic).  sched NULL: the net's own chain.  Respaced steps and walks with upward
+ * moves (each one mi355_renoise_step: DDNM's "time travel") as there.  Draws: a form-0 step with i > 0 one, a form-1 step with ddim_sigma and i > 0
+ * one, every upward move one; numbering, Philox offsets and the final clip are the scheduled loop's.  ns->lam, ns->sigma: host float[K] (DDNM+:
+ * DDPM.nullspace_coefs of the Python package).  The net is unconditional (in_channels == channels), labels optional for a class-conditional one; a
+ * net with out_channels == 2 * channels is read under the image stride in form 1 and refused in form 0 (its learned variance and DDNM+'s variance are
+ * not reconciled).  With lam all zero (and sigma the posterior's, form 0) the result is bit-identical to mi355_ddpm_pred_sample with the same mode,
+ * schedule, seed and noise.  After the call mi355_unet_get_stats reports the last step's launches: the evaluation's plus one.  workspace:
+ * mi355_ddpm_nullspace_workspace_bytes(net, batch).  Refusals, before any launch, each naming its argument: NULL y, op or ns; ns->sigma missing in
+ * form 0 or given in form 1; a lam or sigma negative or not finite; lam > 1; n_corrector != 0; any other mode; a 2C-input (amortized) net; the
+ * operator refusals above (MI355_ERR_ARG, resp. MI355_ERR_UNSUPPORTED); a short workspace (MI355_ERR_SHAPE).
+ * Sample quality is untested (no trained checkpoint is at hand); the arithmetic is tested against an fp64 restatement.  Out of scope: the CFM
+ * samplers, blur and colourisation operators, the SVD form of DDNM+, guided (classifier-free or reconstruction) variants, x0 shaping, tiling, the
+ * feature cache, correctors, multistep solvers. */
+typedef struct mi355_nullspace_op {
+  int32_t kind;          /* 0 mask, 1 block mean, 2 bilinear taps */
+  float   pad_value;     /* kind 0: sentinel of unknown pixels in y (likelihoods.Painting) */
+  int32_t h_low, w_low;  /* kinds 1, 2: y is [B, C, h_low, w_low]; H % h_low == 0, W % w_low == 0 */
+} mi355_nullspace_op;
+typedef struct mi355_nullspace_schedule {
+  const float* lam;     /* host float[K] */
+  const float* sigma;   /* host float[K]: noise std of step i (form 0); NULL in form 1 (sched->ddim_sigma is used) */
+} mi355_nullspace_schedule;
+int mi355_nullspace_step(const mi355_nullspace_op* op, int form, int pred_kind, float* x, const float* out, int64_t out_stride, const float* y,
+                         const float* z, int batch, int channels, int h, int w, float c_recip, float c_recipm1, float sa, float sb, float a, float b,
+                         float lam, float sigma, int use_philox, uint64_t seed, uint64_t offset, void* stream);
+int mi355_block_mean(const float* in, float* out, int64_t planes, int h, int w, int h_low, int w_low, void* stream);
+int64_t mi355_ddpm_nullspace_workspace_bytes(const mi355_unet* net, int batch);
+int mi355_ddpm_nullspace_sample(mi355_unet* net, float* x, int channels, const float* y, const mi355_nullspace_op* op, const int32_t* labels,
+                                const mi355_ddpm_tables* tables, const mi355_ddpm_options* opt, const mi355_ddpm_schedule* sched,
+                                const mi355_nullspace_schedule* ns, const mi355_ddpm_prediction* pred, const float* noise,
+                                int64_t n_noise_draws, int batch, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Adams-Bashforth CFM samplers of order q = 2, 3, 4 (no reference counterpart): one evaluation per step from step q - 1 on,
  *   x_{k+1} = x_k + sum_{j<q} w_host[k * q + j] * v_{k-j},   v_k = model(t_k, x_k),
  * w_host [n_t - 1][q] holding the integrals over [t_k, t_{k+1}] of the Lagrange basis polynomials of the nodes t_k, ..., t_{k-q+1} (the step length is
