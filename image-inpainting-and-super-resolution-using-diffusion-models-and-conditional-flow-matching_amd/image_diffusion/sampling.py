@@ -5,33 +5,37 @@ Same factories and call contracts as the reference:
     get_conditional_sample_fn(eps_model, ddpm, conditioning, likelihood)  -> sample(xT, condition)
 `eps_model(xi, i)` takes a long [B] step-index tensor (experiments/main.py:140).  Dispatch is on
 `type(conditioning)` (the reference uses the un-vendored `plum` package for that).
+Build-defined extensions without a reference counterpart: get_ddim_sample_fn (DDIM(eta)), get_dpm_solver_sample_fn (DPM-Solver++ multistep, orders
+1 and 2), the ClassifierFreeGuidance, RePaint and NullSpace conditionings, FeatureCache and Tiling; sample quality of all of them is untested.
 
-Two execution paths, both entirely on the HIP backend:
-  * fast path - `eps_model` was made by `make_eps_model(network, ddpm)` with a `UNetModel`: the whole
-    loop runs inside libmi355_sampler (`mi355_ddpm_sample`), one C call per sample() call;
-  * generic path - any callable `eps_model` (e.g. the reference's own lambda around a UNetModel): a
-    host loop that calls it once per step and applies the fused HIP step kernels (csrc/steps.hip).
+Every factory reads the chain's form once (_chain_form: what the net's output stands for, the learned variance range, per-image x0 shaping, the
+chain's own times, tiling, feature cache; DDPM.with_prediction, with_learned_variance, with_x0_shaping, from_betas, with_tiling,
+with_feature_cache) and refuses there, by name, what is not built for it.  Two execution paths, both entirely on the HIP backend:
+  * fused - `eps_model` was made by `make_eps_model(network, ddpm)` with a `UNetModel` for this very schedule: the whole loop runs inside
+    libmi355_sampler, one C call per sample() call.  _fused_operands prepares the state, the injected draws or the call's Philox seed and the
+    schedule; _fused_call picks the engine method from the chain's form (ddpm_pred, ddpm_learned, ddpm_shaped, else ddpm_sample or
+    ddpm_multistep); the null-space sampler calls ddpm_nullspace on the same operands.
+  * host loop - any callable `eps_model` (e.g. the reference's own lambda around a UNetModel): ONE loop, _run_host, walks the chain (a RePaint
+    walk re-noises on its upward moves), pastes the replacement's known pixels, evaluates the eps_model, takes the predictor step of the sampler's
+    kind and the Langevin correctors, and clips.  ONE dispatch, _step, maps (step kind, chain form) to the fused HIP step kernel
+    (csrc/steps.hip) and makes the step's noise draw: kinds "ddpm", "ddim", "ddim_eta", "dpmpp", "corrector" and "nullspace"; a plain chain
+    takes the kind's own op, a shaped one x0_shaped_step_ on the rows of _shape_rows, a learned-variance one strided_step_ / ddpm_lv_step_ on
+    the net's 2C output as it is, an x0- or v-prediction one pred_step_ on the raw output.  Under guidance the loop evaluates the condition,
+    then `none`, and takes one of two forms: combine then plain step (cfg_combine, then the unguided step on the state: eps chains without a
+    learned variance), or the pair on the duplicated state (the guided step kernel on cat(xi, xi) with the raw [2B] pair: learned variance, x0
+    and v prediction).
 Noise: by default drawn in-kernel (Philox4x32-10, seeded from torch.initial_seed()); parity tests
 inject the draws of the reference's `torch.randn_like` call sequence with `injected_noise([...])`.
-Build-defined extensions without a reference counterpart: get_ddim_sample_fn (DDIM(eta)) and get_dpm_solver_sample_fn (DPM-Solver++ multistep,
-orders 1 and 2: one evaluation and one step kernel per step, the previous step's data prediction kept on the device).  A chain made by
-DDPM.with_x0_shaping(...) has every sampler here end its predictor steps' data prediction per image (dynamic thresholding, guidance rescale) instead of
-with the static clip: the fast path in mi355_ddpm_shaped_sample, the generic one through x0_shape_stats and x0_shaped_step_; sample quality untested.
-A chain made by DDPM.with_learned_variance() samples a net with 2C outputs (eps | v, improved-DDPM's learned variance range): the fast path in
-mi355_ddpm_lv_sample, the generic one through ddpm_lv_step_ and strided_step_ on the net's output as it is; DDPM.from_betas chains (linear, cosine;
-a time_scale between step and network time) run there as well; sample quality untested.
-A chain made by DDPM.with_prediction("x0" | "v") samples a net whose output is the data prediction or v: the fast path in mi355_ddpm_pred_sample,
-the generic one through pred_step_ (and pred_shape_stats) on the net's raw output, one step op per step; make_eps_model keeps its name, the model
-returns whatever the net writes; sample quality untested.
 ReconstructionGuidance (sampling.py:136-206) differentiates the x0 model through the U-Net: the gradient is the HIP engine's
 vector-Jacobian product (`UNetEngine.vjp`, csrc/unet_backward.hip) of a differentiable plan of the same network, so it needs an
-`eps_model` made by `make_eps_model(network, ddpm)` around a `UNetModel`.
+`eps_model` made by `make_eps_model(network, ddpm)` around a `UNetModel`; its loop (two engines, the VJP between evaluation and step) is its
+own and takes its predictor and corrector from _step.
 """
 from __future__ import annotations
 
 import contextlib
 import math
-from typing import Callable, List, Optional
+from typing import Callable, List, NamedTuple, Optional
 
 import torch
 
@@ -83,7 +87,8 @@ def _sched_key(ddpm: DDPM):
 def make_eps_model(network, ddpm: DDPM):
     """eps_model(xi, i) = network(xi, 1.0*i/Ns) (loss_functions.py:18-19, experiments/main.py:140),
     tagged so the samplers can run the whole loop inside the C library.  On a RespacedDDPM step i sits at training index tau_i:
-    eps_model(xi, i) = network(xi, tau_i / base_Ns), for an int i and for the long [B] tensor the samplers pass."""
+    eps_model(xi, i) = network(xi, tau_i / base_Ns), for an int i and for the long [B] tensor the samplers pass.  The name stays on an x0- or
+    v-prediction chain: the model returns whatever the net writes."""
     steps = getattr(ddpm, "timesteps", None)
 
     if steps is None and float(getattr(ddpm, "time_scale", 1.0)) == 1.0:
@@ -161,59 +166,93 @@ def _tables(ddpm: DDPM):
     return ddpm.host_tables()
 
 
-def _shaping_of(ddpm, guided: bool):
-    """ddpm.x0_shaping (DDPM.with_x0_shaping; None on a plain chain), refused where it asks an unguided sampler for the guidance rescale."""
-    shaping = getattr(ddpm, "x0_shaping", None)
-    if shaping is not None and shaping.guidance_rescale > 0.0 and not guided:
+# The chain's form ---------------------------------------------------------------------------------------
+
+class _Form(NamedTuple):
+    """What a factory reads off its chain, once."""
+    pred: str                   # what the net's output stands for: "eps", "x0" or "v" (DDPM.with_prediction)
+    max_log: Optional[torch.Tensor]   # ddpm.max_log() of a learned-variance chain (DDPM.with_learned_variance), else None
+    shaping: object             # ddpm.x0_shaping (DDPM.with_x0_shaping), None on a plain chain
+    times: Optional[torch.Tensor]     # the K times the net sees where the chain's time_scale is not 1 (DDPM.from_betas), else None
+    tiling: object              # the factory's argument, else the chain's (DDPM.with_tiling)
+    feature_cache: object       # the factory's argument, else the chain's (DDPM.with_feature_cache)
+
+    @property
+    def wide(self) -> bool:
+        """The net writes 2C channels (eps | v), passed whole to the step ops."""
+        return self.max_log is not None
+
+
+def _need_guided(form: _Form, guided: bool):
+    if form.shaping is not None and form.shaping.guidance_rescale > 0.0 and not guided:
         raise ValueError("guidance_rescale > 0 rescales the guided eps against the conditional one: it needs a guided sampler "
                          "(ClassifierFreeGuidance, or guidance_scale=)")
-    return shaping
 
 
-def _pred_of(ddpm, *, tiling=None, feature_cache=None) -> str:
-    """ddpm.prediction (DDPM.with_prediction; "eps" on a plain chain); refused, by name, with what is not built for an x0- or v-prediction
-    chain, and with a fixed large variance on a learned-variance chain (which of the two variances is meant?)."""
+def _chain_form(ddpm, *, guided=None, tiling=None, feature_cache=None) -> _Form:
+    """The chain's form with the refusals, by name, of what is not built for it.  guided (None: not known before sample()): the guidance
+    rescale needs a guided sampler, _need_guided."""
     pred = getattr(ddpm, "prediction", "eps")
-    if getattr(ddpm, "fixed_variance", "small") == "large" and getattr(ddpm, "learned_variance", False):
-        raise NotImplementedError('a fixed variance (DDPM.with_fixed_variance("large")) is not built for a learned-variance chain '
-                                  "(DDPM.with_learned_variance): the chain has one variance")
-    if pred == "eps":
-        return pred
-    if tiling is not None:
-        raise NotImplementedError("tiling is not built for an x0- or v-prediction chain (DDPM.with_prediction)")
-    if feature_cache is not None:
-        raise NotImplementedError("feature_cache is not built for an x0- or v-prediction chain (DDPM.with_prediction)")
-    return pred
+    learned = bool(getattr(ddpm, "learned_variance", False))
+    form = _Form(pred, ddpm.max_log() if learned else None, getattr(ddpm, "x0_shaping", None), _custom_times(ddpm),
+                 tiling if tiling is not None else getattr(ddpm, "tiling", None),
+                 feature_cache if feature_cache is not None else getattr(ddpm, "feature_cache", None))
+    if guided is not None:
+        _need_guided(form, guided)
+    def whole_frames_only(chain):
+        for what, v in (("tiling", form.tiling), ("feature_cache", form.feature_cache)):
+            if v is not None:
+                raise NotImplementedError(f"{what} is not built for {chain}")
 
-
-def _pred_kw(T, i):
-    """sa, sb of step i for pred_step_ / pred_shape_stats (read by the "v" kind)."""
-    return dict(sa=float(T["sqrt_alphas_cumprod"][i]), sb=float(T["sqrt_one_minus_alphas_cumprod"][i]))
-
-
-def _shape_rows(xi, eps, i, T, shaping, w=None, pred="eps"):
-    """The per-image rows (f, s) of step i's shaped data prediction, or None without shaping.  w: eps is the [2B] pair of a guided step.
-    pred (not "eps"): eps is the raw output of an x0- or v-prediction net."""
-    if shaping is None:
-        return None
+    if learned:
+        if form.shaping is not None:
+            raise NotImplementedError("per-image x0_shaping (DDPM.with_x0_shaping) is not built for a learned-variance chain (DDPM.with_learned_variance)")
+        whole_frames_only("a learned-variance chain (DDPM.with_learned_variance)")
+        if getattr(ddpm, "fixed_variance", "small") == "large":   # which of the two variances is meant?
+            raise NotImplementedError('a fixed variance (DDPM.with_fixed_variance("large")) is not built for a learned-variance chain '
+                                      "(DDPM.with_learned_variance): the chain has one variance")
     if pred != "eps":
-        return _ops.pred_shape_stats(pred, xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), shaping, w=w,
-                                     **_pred_kw(T, i))
-    return _ops.x0_shape_stats(xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), shaping, w=w)
+        whole_frames_only("an x0- or v-prediction chain (DDPM.with_prediction)")
+    return form
 
 
-def _learned_of(ddpm, *, tiling=None, feature_cache=None):
-    """ddpm.max_log() of a learned-variance chain (DDPM.with_learned_variance), None on a plain one; refused, by name, with what is not built
-    for such a chain."""
-    if not getattr(ddpm, "learned_variance", False):
+def _refuse(loop: str, **what):
+    """tiling= / feature_cache= (checked in the order given) where the loop takes neither."""
+    for name, v in what.items():
+        if v is not None:
+            raise NotImplementedError(f"{name} is not built for {loop} (it runs with the prior, amortized, replacement / RePaint and DDIM samplers)")
+
+
+class _Coefs(NamedTuple):
+    """The floats of step i, each from the fp32 host tables."""
+    i: int
+    c_recip: float
+    c_recipm1: float
+    coef1: float
+    coef2: float
+    sigma: float      # exp(0.5 * posterior log-variance), in fp32 like the reference's (0.5 * logvar).exp()
+    acp_prev: float
+    sa: float         # sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod: the paste, and the "v" kind's data prediction
+    sb: float
+    min_log: float    # the clipped posterior log-variance: the lower end of a learned variance range
+    rsm1: float
+
+
+def _coefs(T, i) -> _Coefs:
+    return _Coefs(i, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), float(T["posterior_mean_coef1"][i]),
+                  float(T["posterior_mean_coef2"][i]), float((0.5 * T["posterior_log_variance_clipped"][i]).exp()),
+                  float(T["alphas_cumprod_prev"][i]), float(T["sqrt_alphas_cumprod"][i]), float(T["sqrt_one_minus_alphas_cumprod"][i]),
+                  float(T["posterior_log_variance_clipped"][i]), float(T["recip_sqrt_m1_alphas_cumprod"][i]))
+
+
+def _shape_rows(xi, out, c: _Coefs, form: _Form, w=None):
+    """The per-image rows (f, s) of the step's shaped data prediction, or None without shaping.  w: out is the [2B] pair of a guided step (the
+    rescale needs eps_c beside eps_g)."""
+    if form.shaping is None:
         return None
-    if getattr(ddpm, "x0_shaping", None) is not None:
-        raise NotImplementedError("per-image x0_shaping (DDPM.with_x0_shaping) is not built for a learned-variance chain (DDPM.with_learned_variance)")
-    if tiling is not None:
-        raise NotImplementedError("tiling is not built for a learned-variance chain (DDPM.with_learned_variance)")
-    if feature_cache is not None:
-        raise NotImplementedError("feature_cache is not built for a learned-variance chain (DDPM.with_learned_variance)")
-    return ddpm.max_log()
+    if form.pred != "eps":
+        return _ops.pred_shape_stats(form.pred, xi, out, c.c_recip, c.c_recipm1, form.shaping, w=w, sa=c.sa, sb=c.sb)
+    return _ops.x0_shape_stats(xi, out, c.c_recip, c.c_recipm1, form.shaping, w=w)
 
 
 def _check_width(out_channels, xi, max_log, host_loop=False):
@@ -235,49 +274,57 @@ def _check_engine_width(engine, xi, max_log):
         _check_width(out_channels, xi, max_log)
 
 
-def _predictor(eps, xi, i, T, noise: _Noise, shape=None, max_log=None, w=None, pred="eps"):
-    """step() (sampling.py:59-67): x0_hat -> clip -> posterior mean -> + exp(0.5 logvar) z (z iff i > 0).  shape: the rows of _shape_rows
-    (per-image shaping in place of the clip).  max_log (a learned-variance chain): eps is the net's 2C output, passed whole; with w, the
-    [2B] pair of a guided step and xi the duplicated state.  pred (not "eps"): eps is the raw output of an x0- or v-prediction net, passed
-    whole to the one step op that takes the kind."""
-    z, ph = noise.next() if i > 0 else (None, None)
-    sigma = float((0.5 * T["posterior_log_variance_clipped"][i]).exp())  # fp32, like (0.5*logvar).exp()
-    if pred != "eps":
-        cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
-        c1, c2 = float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i])
-        if max_log is not None and i > 0:
-            return _ops.pred_step_("ddpm_lv", pred, xi, eps, cr, crm1, c1, c2, min_log=float(T["posterior_log_variance_clipped"][i]),
-                                   max_log=float(max_log[i]), z=z, philox=ph, w=w, **_pred_kw(T, i))
-        return _ops.pred_step_("ddpm", pred, xi, eps, cr, crm1, c1, c2, sigma=sigma, z=z, philox=ph, w=w, shape=shape, **_pred_kw(T, i))
-    if max_log is not None:
-        cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
-        c1, c2 = float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i])
-        if i > 0:
-            return _ops.ddpm_lv_step_(xi, eps, z, cr, crm1, c1, c2, float(T["posterior_log_variance_clipped"][i]), float(max_log[i]), ph, w=w)
-        return _ops.strided_step_("ddpm", xi, eps, cr, crm1, c1, c2, sigma=sigma, w=w)   # step 0 draws no noise and never reads v
+def _step(kind, xi, out, c: _Coefs, form: _Form, noise: _Noise, args=(), *, w=None, hist=None, shape=None):
+    """One step of `kind` in place on xi from the net's output `out`, with the kind's noise draw (before anything else):
+        "ddpm"       step() (sampling.py:59-67): x0_hat -> clip -> posterior mean -> + sigma z; one draw iff i > 0
+        "ddim"       the deterministic DDIM step
+        "ddim_eta"   args = (sigma_i,): DDIM(eta); one draw iff i > 0
+        "dpmpp"      args = (cx_i, c0_i, c1_i): DPM-Solver++ multistep on hist, the previous step's data prediction
+        "corrector"  args = (dt, delta): corrector_step (sampling.py:113-121); one draw
+        "nullspace"  args = (op, form, y, lam_i, sigma_i or None): the null-space step, ancestral (form 0) or DDIM(eta) (form 1; None: no draw)
+    The chain's form picks the op: a plain chain the kind's own; shape (the rows of _shape_rows, per-image shaping in place of the clip)
+    x0_shaped_step_; a learned-variance chain strided_step_ on the 2C output passed whole, ddpm_lv_step_ where the learned variance is drawn
+    with (the ancestral step, i > 0; step 0 draws no noise and never reads v); an x0- or v-prediction chain pred_step_ on the raw output.
+    w: out is the [2B] pair of a guided step and xi the duplicated state."""
+    cr, crm1 = c.c_recip, c.c_recipm1
+    if kind == "nullspace":
+        op, ns_form, y, lam, sigma = args
+        z, ph = noise.next() if (sigma is not None and c.i > 0) else (None, None)
+        a, b = (c.coef1, c.coef2) if ns_form == 0 else (c.acp_prev, 0.0)
+        return _ops.nullspace_step_(op, ns_form, form.pred, xi, out, y, cr, crm1, a, b, lam=lam, sigma=0.0 if sigma is None else sigma, z=z,
+                                    philox=ph, sa=c.sa, sb=c.sb)
+    z, ph = noise.next() if (kind == "corrector" or (kind in ("ddpm", "ddim_eta") and c.i > 0)) else (None, None)
+    b = cc = sigma = 0.0   # the ops' three numbers a, b, c of the kind, and its sigma
+    if kind == "ddpm":
+        a, b, sigma = c.coef1, c.coef2, c.sigma
+    elif kind == "ddim":
+        a = c.acp_prev
+    elif kind == "ddim_eta":
+        a, (sigma,) = c.acp_prev, args
+    elif kind == "dpmpp":
+        a, b, cc = args
+    else:
+        a, (b, cc) = c.rsm1, args
+    lv = form.wide and kind == "ddpm" and c.i > 0
+    lo, hi = (c.min_log, float(form.max_log[c.i])) if lv else (0.0, 0.0)   # the learned range, in place of sigma
+    if form.pred != "eps":
+        return _ops.pred_step_("ddpm_lv" if lv else kind, form.pred, xi, out, cr, crm1, a, b, cc, 0.0 if lv else sigma, sa=c.sa, sb=c.sb, min_log=lo,
+                               max_log=hi, z=z, philox=ph, hist=hist, w=w, shape=shape)
+    if lv:
+        return _ops.ddpm_lv_step_(xi, out, z, cr, crm1, a, b, lo, hi, ph, w=w)
+    if form.wide:
+        return _ops.strided_step_(kind, xi, out, cr, crm1, a, b, cc, sigma, z=z, philox=ph, hist=hist, w=w)
     if shape is not None:
-        _ops.x0_shaped_step_("ddpm", xi, eps, shape, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
-                             float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i]), sigma=sigma, z=z, philox=ph)
-        return xi
-    _ops.ddpm_step_(xi, eps, z, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
-                    float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i]), sigma, ph)
-    return xi
-
-
-def _corrector(eps, xi, i, T, ddpm, delta, noise: _Noise, max_log=None, pred="eps"):
-    """corrector_step (sampling.py:113-121).  max_log (a learned-variance chain): eps is the net's 2C output, passed whole.  pred: as in
-    _predictor."""
-    z, ph = noise.next()
-    dt = (ddpm.tmax - ddpm.tmin) / ddpm.Ns
-    if pred != "eps":
-        return _ops.pred_step_("corrector", pred, xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
-                               float(T["recip_sqrt_m1_alphas_cumprod"][i]), dt, float(delta), z=z, philox=ph, **_pred_kw(T, i))
-    if max_log is not None:
-        return _ops.strided_step_("corrector", xi, eps, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
-                                  float(T["recip_sqrt_m1_alphas_cumprod"][i]), dt, float(delta), z=z, philox=ph)
-    _ops.corrector_step_(xi, eps, z, float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]),
-                         float(T["recip_sqrt_m1_alphas_cumprod"][i]), dt, float(delta), ph)
-    return xi
+        return _ops.x0_shaped_step_(kind, xi, out, shape, cr, crm1, a, b, cc, sigma, z=z, philox=ph, hist=hist)
+    if kind == "ddpm":
+        return _ops.ddpm_step_(xi, out, z, cr, crm1, a, b, sigma, ph)
+    if kind == "ddim":
+        return _ops.ddim_step_(xi, out, cr, crm1, a)
+    if kind == "ddim_eta":
+        return _ops.ddim_eta_step_(xi, out, z, cr, crm1, a, sigma, ph)
+    if kind == "dpmpp":
+        return _ops.dpmpp_step_(xi, out, hist, cr, crm1, a, b, cc)
+    return _ops.corrector_step_(xi, out, z, cr, crm1, a, b, cc, ph)
 
 
 def _times(xi, i):
@@ -297,93 +344,57 @@ def _walk_moves(Ns, walk):
     return [(a, b < a) for a, b in zip(walk, walk[1:])]
 
 
-def _run_generic(eps_model, ddpm, xT, *, amortized, cond_pred, cond_corr, replacement=None, n_corrector=0, delta=0.1, walk=None):
+def _run_host(eps_model, ddpm, xT, form: _Form, kind="ddpm", step_args=lambda i: (), *, cond=None, concat=False, none=None, w=None, cond_corr=None,
+              replacement=None, n_corrector=0, delta=0.1, walk=None):
+    """The host loop for any eps_model callable.  Per move of the walk (None: the plain descent): an upward move re-noises the state by
+    q(x_level+1 | x_level) (one draw); a downward move pastes the replacement's known pixels (one draw iff they are noised), evaluates the net
+    on cond (concatenated iff concat), takes the predictor step of `kind` (_step; step_args(i): the kind's own numbers) and n_corrector
+    correctors, each on an evaluation on cond_corr.  w (a float or a [B] tensor; None: unguided): classifier-free guidance, a second evaluation
+    on `none` behind the conditional one, the width check on the pair, the shaping rows from the pair, and one of two forms - the pair on the
+    duplicated state where the step kernel must see it raw (a 2C pair: v from the conditional half; an x0- or v-prediction pair: mixed raw),
+    else cfg_combine and the unguided step."""
+    _need_guided(form, w is not None)
     T = _tables(ddpm)
-    shaping = _shaping_of(ddpm, False)
-    max_log = _learned_of(ddpm)
-    pred = _pred_of(ddpm)
     xi = xT.detach().clone().float().contiguous()
     noise = _Noise(xi)
+    hist = torch.empty_like(xi) if kind == "dpmpp" else None
+    dt = (ddpm.tmax - ddpm.tmin) / ddpm.Ns
     for level, down in _walk_moves(ddpm.Ns, walk):
         if not down:   # q(x_level+1 | x_level): one draw
             z, ph = noise.next()
             _ops.renoise_(xi, z, float(T["alphas"][level].sqrt()), float(T["betas"][level].sqrt()), ph)
             continue
         i = level - 1
+        c = _coefs(T, i)
         if replacement is not None and i < int(ddpm.Ns * replacement["start_fraction"]):
             z, ph = noise.next() if replacement["noise"] else (None, None)
-            _ops.replace_mask_(xi, replacement["condition"], z, replacement["pad_value"], replacement["noise"],
-                               float(T["sqrt_alphas_cumprod"][i]), float(T["sqrt_one_minus_alphas_cumprod"][i]), ph)
-        eps = eps_model(_net_in(xi, cond_pred, amortized), _times(xi, i)).float().contiguous()
-        _check_width(eps.shape[1], xi, max_log, host_loop=True)
-        _predictor(eps, xi, i, T, noise, _shape_rows(xi, eps, i, T, shaping, pred=pred), max_log, pred=pred)
+            _ops.replace_mask_(xi, replacement["condition"], z, replacement["pad_value"], replacement["noise"], c.sa, c.sb, ph)
+        out = eps_model(_net_in(xi, cond, concat), _times(xi, i)).float()
+        if w is not None:
+            out = torch.cat((out, eps_model(_net_in(xi, none, True), _times(xi, i)).float()))
+        out = out.contiguous()
+        _check_width(out.shape[1], xi, form.max_log, host_loop=kind != "nullspace")
+        shape = _shape_rows(xi, out, c, form, w=w)
+        if w is None:
+            _step(kind, xi, out, c, form, noise, step_args(i), hist=hist, shape=shape)
+        elif form.wide or form.pred != "eps":
+            x2 = torch.cat((xi, xi))
+            _step(kind, x2, out, c, form, noise, step_args(i), w=w, hist=hist, shape=shape)
+            xi.copy_(x2[:xi.shape[0]])
+        else:
+            _step(kind, xi, _ops.cfg_combine(out, w), c, form, noise, step_args(i), hist=hist, shape=shape)
         for _ in range(n_corrector):
-            eps = eps_model(_net_in(xi, cond_corr, amortized), _times(xi, i))
-            _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise, max_log, pred=pred)
+            out = eps_model(_net_in(xi, cond_corr, concat), _times(xi, i))
+            _step("corrector", xi, out.float().contiguous(), c, form, noise, (dt, float(delta)))
     return process_x0(xi)
-
-
-def _ddim_move(eps, xi, i, T, sigma, noise, shape=None, wide=False, w=None, pred="eps"):
-    """One DDIM step: sigma None = the deterministic kernel; else DDIM(eta) with sigma[i] and one draw iff i > 0.  shape: as in _predictor.
-    wide (a learned-variance chain): eps is the net's 2C output, passed whole; with w, the [2B] pair of a guided step, xi the duplicated state."""
-    cr, crm1, prev = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i]), float(T["alphas_cumprod_prev"][i])
-    if pred != "eps":   # the raw output of an x0- or v-prediction net, passed whole (wide or not) to the one step op that takes the kind
-        if sigma is None:
-            return _ops.pred_step_("ddim", pred, xi, eps, cr, crm1, prev, w=w, shape=shape, **_pred_kw(T, i))
-        z, ph = noise.next() if i > 0 else (None, None)
-        return _ops.pred_step_("ddim_eta", pred, xi, eps, cr, crm1, prev, sigma=float(sigma[i]), z=z, philox=ph, w=w, shape=shape, **_pred_kw(T, i))
-    if wide:
-        if sigma is None:
-            return _ops.strided_step_("ddim", xi, eps, cr, crm1, prev, w=w)
-        z, ph = noise.next() if i > 0 else (None, None)
-        return _ops.strided_step_("ddim_eta", xi, eps, cr, crm1, prev, sigma=float(sigma[i]), z=z, philox=ph, w=w)
-    if sigma is None:
-        return _ops.ddim_step_(xi, eps, cr, crm1, prev) if shape is None else _ops.x0_shaped_step_("ddim", xi, eps, shape, cr, crm1, prev)
-    z, ph = noise.next() if i > 0 else (None, None)
-    if shape is not None:
-        return _ops.x0_shaped_step_("ddim_eta", xi, eps, shape, cr, crm1, prev, sigma=float(sigma[i]), z=z, philox=ph)
-    return _ops.ddim_eta_step_(xi, eps, z, cr, crm1, prev, float(sigma[i]), ph)
 
 
 def _run_generic_cfg(eps_model, ddpm, xT, *, cond, none, guidance_scale, n_corrector=0, delta=0.1, ddim=False, ddim_sigma=None):
-    """The guided host loop for any eps_model callable: two calls per predictor step (condition, none_like), cfg_combine, the step kernel;
-    correctors as in _run_generic (the net sees none_like).  With shaping the rows come from the pair (the rescale needs eps_c beside eps_g)."""
-    T = _tables(ddpm)
-    shaping = _shaping_of(ddpm, True)
-    max_log = _learned_of(ddpm)
-    pred = _pred_of(ddpm)
-    xi = xT.detach().clone().float().contiguous()
-    noise = _Noise(xi)
-    B = xi.shape[0]
-    for i in reversed(range(ddpm.Ns)):
-        ec = eps_model(_net_in(xi, cond, True), _times(xi, i)).float()
-        eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
-        eps2 = torch.cat((ec, eu)).contiguous()
-        _check_width(eps2.shape[1], xi, max_log, host_loop=True)
-        if max_log is not None or pred != "eps":
-            # the guided step kernels on the pair itself (a 2C pair: v from the conditional half; an x0- or v-prediction pair: mixed raw), the
-            # state duplicated for them
-            x2 = torch.cat((xi, xi))
-            shape = _shape_rows(xi, eps2, i, T, shaping, w=guidance_scale, pred=pred) if pred != "eps" else None
-            if ddim:
-                _ddim_move(eps2, x2, i, T, ddim_sigma, noise, shape, wide=True, w=guidance_scale, pred=pred)
-            else:
-                _predictor(eps2, x2, i, T, noise, shape, max_log=max_log, w=guidance_scale, pred=pred)
-            xi.copy_(x2[:B])
-            for _ in range(0 if ddim else n_corrector):
-                eps = eps_model(_net_in(xi, none, True), _times(xi, i))
-                _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise, max_log, pred=pred)
-            continue
-        shape = _shape_rows(xi, eps2, i, T, shaping, w=guidance_scale)
-        eps = _ops.cfg_combine(eps2, guidance_scale)
-        if ddim:
-            _ddim_move(eps, xi, i, T, ddim_sigma, noise, shape)
-            continue
-        _predictor(eps, xi, i, T, noise, shape)
-        for _ in range(n_corrector):
-            eps = eps_model(_net_in(xi, none, True), _times(xi, i))
-            _corrector(eps.float().contiguous(), xi, i, T, ddpm, delta, noise)
-    return process_x0(xi)
+    """The guided host loop under its earlier name and signature: _run_host with (none, w); ddim: the DDIM(eta) kinds, no correctors."""
+    kind, step_args = ("ddpm", lambda i: ()) if not ddim else ("ddim", lambda i: ()) if ddim_sigma is None else ("ddim_eta", lambda i: (float(ddim_sigma[i]),))
+    form = _chain_form(ddpm.with_tiling(None).with_feature_cache(None), guided=True)   # (tiling and cache are the factories' to refuse)
+    return _run_host(eps_model, ddpm, xT, form, kind, step_args, cond=cond, concat=True, none=none, w=guidance_scale,
+                     cond_corr=none, n_corrector=0 if ddim else n_corrector, delta=delta)
 
 
 class FeatureCache:
@@ -425,85 +436,78 @@ class Tiling:
         self.stride, self.weight, self.chunk = stride, weight, (None if chunk is None else int(chunk))
 
 
-def _tiling_of(ddpm, tiling=None):
-    """The tiling a sample function runs under: its own argument, else the chain's (DDPM.with_tiling)."""
-    return tiling if tiling is not None else getattr(ddpm, "tiling", None)
+# The fused path: one preparation, one choice of the engine method ----------------------------------------------------
+
+def _fused_operands(ddpm, xT, *, ddim_sigma=None, walk=None, draws=True):
+    """-> (xi, noise, seed, sched) of a fused call: the state; the injected draws stacked, or None and the call's Philox seed, keyed with
+    _draw_counter; the keywords of the scheduled entry points - a respaced chain's steps in training time (an unrespaced one's: 0..Ns-1 of Ns),
+    the DDIM sigma and the walk - where the call has any of them.  draws=False (a deterministic multistep call): no noise, no seed, no key
+    taken, and a schedule of the steps alone."""
+    global _draw_counter
+    xi = xT.detach().clone().float().contiguous()
+    noise, seed = None, None
+    if draws:
+        seed = int(torch.initial_seed()) & ((1 << 63) - 1)
+        if _injected is not None:
+            noise = torch.stack([z.to(xi.device, torch.float32) for z in _injected]).contiguous()
+        else:
+            seed = (seed + 0x9E3779B97F4A7C15 * (_draw_counter + 1)) & ((1 << 63) - 1)
+            _draw_counter += 1
+    sched = {}
+    if getattr(ddpm, "timesteps", None) is not None or ddim_sigma is not None or walk is not None:
+        sched = dict(timesteps=getattr(ddpm, "timesteps", None) or tuple(range(ddpm.Ns)), train_steps=int(getattr(ddpm, "base_Ns", ddpm.Ns)))
+        if draws:
+            sched.update(ddim_sigma=ddim_sigma, walk=walk)
+    return xi, noise, seed, sched
 
 
-def _refuse_tiling(tiling, loop: str):
-    if tiling is not None:
-        raise NotImplementedError(f"tiling is not built for {loop} (it runs with the prior, amortized, replacement / RePaint and DDIM samplers)")
-
-
-def _need_fused_tiling(engine, tiling):
-    if tiling is not None and engine is None:
-        raise NotImplementedError("tiling runs inside the fused loop: pass an eps_model built by make_eps_model(network, ddpm) for this "
-                                  "schedule and device tensors (an arbitrary callable sees whole frames only)")
-
-
-def _cache_of(ddpm, feature_cache=None):
-    """The cache a sample function runs under: its own argument, else the chain's (DDPM.with_feature_cache)."""
-    return feature_cache if feature_cache is not None else getattr(ddpm, "feature_cache", None)
-
-
-def _refuse_feature_cache(feature_cache, loop: str):
-    if feature_cache is not None:
-        raise NotImplementedError(f"feature_cache is not built for {loop} (it runs with the prior, amortized, replacement / RePaint and DDIM samplers)")
+def _fused_call(engine, ddpm, xi, form: _Form, kw, coefs=None):
+    """The engine method of the chain's form, on the keywords kw every one of them takes: ddpm_pred (an x0- or v-prediction net; it takes the
+    shaping, the variance range and the times beside the kind), ddpm_learned (a learned variance range and / or the chain's own times),
+    ddpm_shaped (per-image shaping of x0_hat), else ddpm_sample - or, with coefs (DPM-Solver++), ddpm_multistep, the first three in their
+    multistep form.  -> xi"""
+    T = _tables(ddpm)
+    guided = kw.get("guidance_scale") is not None
+    multistep = {} if coefs is None else dict(mode=_lib.DDIM, coefs=coefs)
+    if coefs is None or form.pred != "eps" or form.max_log is not None or form.times is not None:
+        _check_engine_width(engine, xi, form.max_log)   # (ddpm_multistep and its shaped form leave a plain chain's width to the library)
+    if form.pred != "eps":
+        engine.ddpm_pred(xi, T, form.pred, shaping=form.shaping, max_log=form.max_log, times=form.times, **multistep, **kw)
+        return xi
+    for name, v in (("feature_cache", form.feature_cache), ("tiling", form.tiling)):
+        if guided:
+            _refuse("the guided (classifier-free guidance) loops", **{name: v})
+        if form.shaping is not None:
+            _refuse("the shaped loops (DDPM.with_x0_shaping)", **{name: v})
+    if form.feature_cache is not None and form.tiling is not None:
+        raise NotImplementedError("tiling together with feature_cache is not built")
+    if form.feature_cache is not None:
+        kw = dict(kw, **form.feature_cache.kwargs())
+    if form.tiling is not None:
+        kw = dict(kw, tiling=form.tiling)
+    if form.max_log is not None or form.times is not None:
+        for what, v in (("x0_shaping", form.shaping), ("tiling", form.tiling), ("feature_cache", form.feature_cache)):
+            if v is not None:
+                raise NotImplementedError(f"{what} is not built for a chain with a time_scale (DDPM.from_betas(..., time_scale=))")
+        engine.ddpm_learned(xi, T, form.max_log, times=form.times, **multistep, **kw)
+    elif form.shaping is not None:
+        engine.ddpm_shaped(xi, T, form.shaping, **multistep, **kw)
+    elif coefs is not None:
+        engine.ddpm_multistep(xi, T, coefs, **kw)
+    else:
+        engine.ddpm_sample(xi, T, **kw)
+    return xi
 
 
 def _run_fast(engine, ddpm, xT, mode, cond, *, n_corrector=0, delta=0.1, start_fraction=1.0, noise_condition=True,
               pad_value=-2.0, none_value=-2.0, guidance_scale=None, ddim_sigma=None, walk=None, feature_cache=None, tiling=None):
-    global _draw_counter
-    xi = xT.detach().clone().float().contiguous()
-    noise = None
-    seed = int(torch.initial_seed()) & ((1 << 63) - 1)
-    if _injected is not None:
-        noise = torch.stack([z.to(xi.device, torch.float32) for z in _injected]).contiguous()
-    else:
-        seed = (seed + 0x9E3779B97F4A7C15 * (_draw_counter + 1)) & ((1 << 63) - 1)
-        _draw_counter += 1
-    sched = {}
-    if getattr(ddpm, "timesteps", None) is not None or ddim_sigma is not None or walk is not None:
-        # the scheduled entry points: a respaced chain's steps in training time (an unrespaced one's: 0..Ns-1 of Ns)
-        sched = dict(timesteps=getattr(ddpm, "timesteps", None) or tuple(range(ddpm.Ns)), train_steps=int(getattr(ddpm, "base_Ns", ddpm.Ns)),
-                     ddim_sigma=ddim_sigma, walk=walk)
+    """One fused call of the noise-drawing loops; the chain's form is read here, with the caller's feature_cache= and tiling=."""
+    xi, noise, seed, sched = _fused_operands(ddpm, xT, ddim_sigma=ddim_sigma, walk=walk)
     kw = dict(mode=mode, cond=cond, noise=noise, n_corrector=n_corrector, delta=float(delta), tmin=ddpm.tmin, tmax=ddpm.tmax,
               start_fraction=float(start_fraction), noise_condition=bool(noise_condition), pad_value=float(pad_value), none_value=float(none_value),
               seed=seed, guidance_scale=guidance_scale, **sched)
-    shaping = _shaping_of(ddpm, guidance_scale is not None)
-    feature_cache = _cache_of(ddpm, feature_cache)
-    tiling = _tiling_of(ddpm, tiling)
-    max_log = _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)
-    pred = _pred_of(ddpm, tiling=tiling, feature_cache=feature_cache)
-    times = _custom_times(ddpm)
-    _check_engine_width(engine, xi, max_log)
-    if pred != "eps":   # an x0- or v-prediction net: mi355_ddpm_pred_sample, which takes the shaping, the variance range and the times beside the kind
-        engine.ddpm_pred(xi, _tables(ddpm), pred, shaping=shaping, max_log=max_log, times=times, **kw)
-        return xi
-    if feature_cache is not None:
-        if guidance_scale is not None:
-            _refuse_feature_cache(feature_cache, "the guided (classifier-free guidance) loops")
-        if shaping is not None:
-            _refuse_feature_cache(feature_cache, "the shaped loops (DDPM.with_x0_shaping)")
-        kw.update(feature_cache.kwargs())
-    if tiling is not None:
-        if guidance_scale is not None:
-            _refuse_tiling(tiling, "the guided (classifier-free guidance) loops")
-        if shaping is not None:
-            _refuse_tiling(tiling, "the shaped loops (DDPM.with_x0_shaping)")
-        if feature_cache is not None:
-            raise NotImplementedError("tiling together with feature_cache is not built")
-        kw["tiling"] = tiling
-    if max_log is not None or times is not None:   # a learned variance range and / or the chain's own times: mi355_ddpm_lv_sample
-        for what, v in (("x0_shaping", shaping), ("tiling", tiling), ("feature_cache", feature_cache)):
-            if v is not None:
-                raise NotImplementedError(f"{what} is not built for a chain with a time_scale (DDPM.from_betas(..., time_scale=))")
-        engine.ddpm_learned(xi, _tables(ddpm), max_log, times=times, **kw)
-    elif shaping is not None:   # the same loop with per-image shaping of x0_hat: mi355_ddpm_shaped_sample
-        engine.ddpm_shaped(xi, _tables(ddpm), shaping, **kw)
-    else:
-        engine.ddpm_sample(xi, _tables(ddpm), **kw)
-    return xi
+    form = _chain_form(ddpm, guided=guidance_scale is not None, tiling=tiling, feature_cache=feature_cache)
+    return _fused_call(engine, ddpm, xi, form, kw)
 
 
 def _custom_times(ddpm):
@@ -513,33 +517,32 @@ def _custom_times(ddpm):
     return torch.tensor([ddpm.time(k) for k in range(ddpm.Ns)], dtype=torch.float32)
 
 
-# Prior sampling ------------------------------------------------------------------------------------
-
-def _need_fused(engine, feature_cache):
-    if feature_cache is not None and engine is None:
+def _need_fused(engine, form: _Form):
+    """A feature cache and tiling run inside the fused loop only."""
+    if form.feature_cache is not None and engine is None:
         raise NotImplementedError("feature_cache runs inside the fused loop: pass an eps_model built by make_eps_model(network, ddpm) for this "
                                   "schedule and device tensors (an arbitrary callable is evaluated whole)")
+    if form.tiling is not None and engine is None:
+        raise NotImplementedError("tiling runs inside the fused loop: pass an eps_model built by make_eps_model(network, ddpm) for this "
+                                  "schedule and device tensors (an arbitrary callable sees whole frames only)")
 
+
+# Prior sampling ------------------------------------------------------------------------------------
 
 def get_prior_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Conditioning, likelihood: Likelihood, feature_cache=None, tiling=None):
     """sampling.py:50-75.  Under Amortized conditioning the net is fed `likelihood.none_like` (sampling.py:36-37).
     feature_cache (None: untouched): a FeatureCache.  tiling (None: the chain's, ddpm.tiling; neither: untouched): a Tiling; xT is then a canvas."""
     amortized = isinstance(conditioning, Amortized)
-    feature_cache = _cache_of(ddpm, feature_cache)
-    tiling = _tiling_of(ddpm, tiling)
-    _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)   # a learned-variance chain: its refusals, before the first sample
-    _pred_of(ddpm, tiling=tiling, feature_cache=feature_cache)      # an x0- or v-prediction chain: likewise
+    form = _chain_form(ddpm, tiling=tiling, feature_cache=feature_cache)   # with its refusals, before the first sample
 
     @torch.no_grad()
     def sample(xT):
         engine = _fast_engine(eps_model, ddpm, xT)
-        _need_fused(engine, feature_cache)
-        _need_fused_tiling(engine, tiling)
+        _need_fused(engine, form)
         if engine is not None:
-            return _run_fast(engine, ddpm, xT, _lib.DDPM_PRIOR, None, none_value=_none_value(likelihood, xT), feature_cache=feature_cache,
-                             tiling=tiling)
+            return _run_fast(engine, ddpm, xT, _lib.DDPM_PRIOR, None, none_value=_none_value(likelihood, xT), feature_cache=form.feature_cache, tiling=form.tiling)
         none = likelihood.none_like(xT) if amortized else None
-        return _run_generic(eps_model, ddpm, xT, amortized=amortized, cond_pred=none, cond_corr=none)
+        return _run_host(eps_model, ddpm, xT, form, cond=none, concat=amortized, cond_corr=none)
 
     return sample
 
@@ -550,34 +553,27 @@ def get_conditional_sample_fn(eps_model: Callable, ddpm: DDPM, conditioning: Con
     """feature_cache (None: the chain's, ddpm.feature_cache; neither: untouched): a FeatureCache; Amortized, Replacement and RePaint take it, the
     other conditionings refuse it by name.  tiling (None: the chain's, ddpm.tiling; neither: untouched): a Tiling, xT and the condition are then
     canvases; taken and refused by the same conditionings."""
-    feature_cache = _cache_of(ddpm, feature_cache)
-    tiling = _tiling_of(ddpm, tiling)
-    _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)   # a learned-variance chain: its refusals, before the first sample
-    _pred_of(ddpm, tiling=tiling, feature_cache=feature_cache)      # an x0- or v-prediction chain: likewise
+    form = _chain_form(ddpm, tiling=tiling, feature_cache=feature_cache)   # with its refusals, before the first sample
     if isinstance(conditioning, ClassifierFreeGuidance):   # (an Amortized: before it)
-        _refuse_feature_cache(feature_cache, "ClassifierFreeGuidance (the guided loops)")
-        _refuse_tiling(tiling, "ClassifierFreeGuidance (the guided loops)")
-        return _cfg_sample_fn(eps_model, ddpm, conditioning, likelihood)
+        _refuse("ClassifierFreeGuidance (the guided loops)", feature_cache=form.feature_cache, tiling=form.tiling)
+        return _cfg_sample_fn(eps_model, ddpm, conditioning, likelihood, form)
     if isinstance(conditioning, Amortized):
-        return _amortized_sample_fn(eps_model, ddpm, conditioning, likelihood, feature_cache, tiling)
+        return _amortized_sample_fn(eps_model, ddpm, conditioning, likelihood, form)
     if isinstance(conditioning, RePaint):   # (a Replacement: before it)
-        return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, walk=repaint_walk(ddpm.Ns, conditioning.jump_length,
-                                                                                                   conditioning.n_resample), feature_cache=feature_cache,
-                                      tiling=tiling)
+        return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, form,
+                                      walk=repaint_walk(ddpm.Ns, conditioning.jump_length, conditioning.n_resample))
     if isinstance(conditioning, Replacement):
-        return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, feature_cache=feature_cache, tiling=tiling)
+        return _replacement_sample_fn(eps_model, ddpm, conditioning, likelihood, form)
     if isinstance(conditioning, NullSpace):
-        _refuse_feature_cache(feature_cache, "NullSpace (the null-space loop)")
-        _refuse_tiling(tiling, "NullSpace (the null-space loop)")
-        return _nullspace_sample_fn(eps_model, ddpm, conditioning, likelihood)
+        _refuse("NullSpace (the null-space loop)", feature_cache=form.feature_cache, tiling=form.tiling)
+        return _nullspace_sample_fn(eps_model, ddpm, conditioning, likelihood, form)
     if isinstance(conditioning, ReconstructionGuidance):
-        _refuse_feature_cache(feature_cache, "ReconstructionGuidance (the backward pass needs a whole forward)")
-        _refuse_tiling(tiling, "ReconstructionGuidance (the backward pass needs a whole forward)")
-        return _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning, likelihood)
+        _refuse("ReconstructionGuidance (the backward pass needs a whole forward)", feature_cache=form.feature_cache, tiling=form.tiling)
+        return _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning, likelihood, form)
     raise NotImplementedError(f"no sampler for conditioning type {type(conditioning).__name__}")
 
 
-def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood, feature_cache=None, tiling=None):
+def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood, form: _Form):
     """sampling.py:80-133.  The corrector calls the x0 model WITHOUT the condition (sampling.py:116), so the
     network sees none_like there - reproduced."""
 
@@ -585,21 +581,20 @@ def _amortized_sample_fn(eps_model, ddpm, conditioning: Amortized, likelihood, f
     def sample(xT, condition):
         condition = condition.to(xT.device).float().contiguous()
         engine = _fast_engine(eps_model, ddpm, xT)
-        _need_fused(engine, feature_cache)
-        _need_fused_tiling(engine, tiling)
+        _need_fused(engine, form)
         if engine is not None:
             return _run_fast(engine, ddpm, xT, _lib.DDPM_AMORTIZED, condition, n_corrector=conditioning.n_corrector,
-                             delta=conditioning.delta, none_value=_none_value(likelihood, xT), feature_cache=feature_cache, tiling=tiling)
-        return _run_generic(eps_model, ddpm, xT, amortized=True, cond_pred=condition, cond_corr=likelihood.none_like(xT),
-                            n_corrector=conditioning.n_corrector, delta=conditioning.delta)
+                             delta=conditioning.delta, none_value=_none_value(likelihood, xT), feature_cache=form.feature_cache, tiling=form.tiling)
+        return _run_host(eps_model, ddpm, xT, form, cond=condition, concat=True, cond_corr=likelihood.none_like(xT),
+                         n_corrector=conditioning.n_corrector, delta=conditioning.delta)
 
     return sample
 
 
-def _cfg_sample_fn(eps_model, ddpm, conditioning: ClassifierFreeGuidance, likelihood):
+def _cfg_sample_fn(eps_model, ddpm, conditioning: ClassifierFreeGuidance, likelihood, form: _Form):
     """Amortized sampling with the predictor's eps guided: eps_u + guidance_scale * (eps_c - eps_u), eps_u from likelihood.none_like.
     Fast path: the whole loop in mi355_ddpm_cfg_sample (one forward at twice the batch per predictor step); generic path: two eps_model
-    calls per predictor step and the cfg_combine kernel.  The corrector is the amortized sampler's."""
+    calls per predictor step (_run_host).  The corrector is the amortized sampler's."""
 
     @torch.no_grad()
     def sample(xT, condition):
@@ -608,14 +603,15 @@ def _cfg_sample_fn(eps_model, ddpm, conditioning: ClassifierFreeGuidance, likeli
         engine = _fast_engine(eps_model, ddpm, xT)
         if engine is not None:
             return _run_fast(engine, ddpm, xT, _lib.DDPM_AMORTIZED, condition, n_corrector=conditioning.n_corrector,
-                             delta=conditioning.delta, none_value=_none_value(likelihood, xT), guidance_scale=w)
-        return _run_generic_cfg(eps_model, ddpm, xT, cond=condition, none=likelihood.none_like(xT), guidance_scale=w,
-                                n_corrector=conditioning.n_corrector, delta=conditioning.delta)
+                             delta=conditioning.delta, none_value=_none_value(likelihood, xT), guidance_scale=w, feature_cache=form.feature_cache, tiling=form.tiling)
+        none = likelihood.none_like(xT)
+        return _run_host(eps_model, ddpm, xT, form, cond=condition, concat=True, none=none, w=w, cond_corr=none,
+                         n_corrector=conditioning.n_corrector, delta=conditioning.delta)
 
     return sample
 
 
-def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: ReconstructionGuidance, likelihood):
+def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: ReconstructionGuidance, likelihood, form: _Form):
     """sampling.py:136-206.  Per step i < int(Ns * start_fraction):
         x_grad = vmap(grad(lambda xi: likelihood.loss(x0_model(xi, i), y)))(xi)      (x0_model = clip(predict_start_from_noise(eps_model)))
         x_update = -gamma * alpha_i * (1 - alpha_i) * x_grad;  "before": xi += x_update (the predictor then runs on the moved xi),
@@ -631,13 +627,13 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
             "a UNetModel (an arbitrary callable has no backward pass on the HIP backend)")
     if conditioning.update_rule not in ("before", "after"):
         raise ValueError(f"unknown update_rule {conditioning.update_rule!r}")
-    if getattr(ddpm, "prediction", "eps") != "eps":
+    if form.pred != "eps":
         raise NotImplementedError("ReconstructionGuidance is not built for an x0- or v-prediction chain (DDPM.with_prediction): the seed "
                                   "differentiates x0_hat = c_recip x - c_recipm1 eps of an eps net")
-    if getattr(ddpm, "learned_variance", False):
+    if form.wide:
         raise NotImplementedError("ReconstructionGuidance is not built for a learned-variance chain (DDPM.with_learned_variance): the seed and "
                                   "the backward pass take a net that writes the state's channels")
-    if getattr(ddpm, "x0_shaping", None) is not None:
+    if form.shaping is not None:
         raise NotImplementedError("ReconstructionGuidance differentiates the clipped x0_hat through the network: per-image x0 shaping "
                                   "(DDPM.with_x0_shaping) is not built into that gradient - pass the unshaped chain")
     if hasattr(likelihood, "pad_value"):
@@ -662,17 +658,17 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
         deng, eng = net.engine(xi.device, differentiable=True), net.engine(xi.device)
         noise = _Noise(xi)
         n_guided = int(ddpm.Ns * conditioning.start_fraction)
+        dt = (ddpm.tmax - ddpm.tmin) / ddpm.Ns
         for i in reversed(range(ddpm.Ns)):
             t = torch.full((B,), ddpm.time(i), device=xi.device, dtype=torch.float32)
+            c = _coefs(T, i)
             update, eps = None, None
             if i < n_guided:
                 eps = deng.forward(xi, t)
                 if mode == 2:
-                    g_eps, g_x, _ = _ops.lowres_seed(xi, eps, condition, float(T["sqrt_recip_alphas_cumprod"][i]),
-                                                     float(T["sqrt_recipm1_alphas_cumprod"][i]))
+                    g_eps, g_x, _ = _ops.lowres_seed(xi, eps, condition, c.c_recip, c.c_recipm1)
                 else:
-                    g_eps, g_x = _ops.guidance_seed(xi, eps, condition, float(T["sqrt_recip_alphas_cumprod"][i]),
-                                                    float(T["sqrt_recipm1_alphas_cumprod"][i]), mode, pad)
+                    g_eps, g_x = _ops.guidance_seed(xi, eps, condition, c.c_recip, c.c_recipm1, mode, pad)
                 vjp = deng.vjp(g_eps)
                 a_i = float(alphas[i])
                 scale = float(conditioning.gamma) * a_i * (1.0 - a_i)
@@ -682,12 +678,12 @@ def _reconstruction_guidance_sample_fn(eps_model, ddpm, conditioning: Reconstruc
                     eps = None                       # xi moved: the predictor needs the network at the new point
             if eps is None:
                 eps = eng.forward(xi, t)
-            _predictor(eps, xi, i, T, noise)
+            _step("ddpm", xi, eps, c, form, noise)
             if update is not None and conditioning.update_rule == "after":
                 _ops.euler_step_(xi, update, 1.0)    # pred_img += x_update
             for _ in range(conditioning.n_corrector):
                 epc = eng.forward(xi, t)
-                _corrector(epc, xi, i, T, ddpm, conditioning.delta, noise)
+                _step("corrector", xi, epc, c, form, noise, (dt, float(conditioning.delta)))
         return process_x0(xi)
 
     return sample
@@ -717,88 +713,59 @@ def _nullspace_operator(likelihood, xT):
     raise NotImplementedError(f"NullSpace has no linear operator for likelihood {name}")
 
 
-def _nullspace_sample_fn(eps_model, ddpm, conditioning: NullSpace, likelihood):
+def _nullspace_sample_fn(eps_model, ddpm, conditioning: NullSpace, likelihood, form: _Form):
     """BUILD-DEFINED EXTENSION (no reference counterpart): DDNM (Wang, Yu, Zhang 2023) with an unconditional eps_model.  sample(xT, condition,
     y=None): condition is likelihood.sample's measurement, y optional class labels [B] of a class-conditional net (the fused path).  Per step one
     evaluation and ONE launch, the null-space step (mi355_nullspace_step): the data prediction is rectified against the measurement with
     ddpm.nullspace_coefs(sigma_y)'s lam, then the state moves by the ancestral step (eta None; its sigma from the same call) or the DDIM(eta) step
     (ddpm.ddim_sigma(eta); eta 0: deterministic, no draw).  jump_length / n_resample: the walk of DDNM's time travel.  Fused path (eps_model built by
-    make_eps_model for this very schedule): the whole loop in mi355_ddpm_nullspace_sample; any other callable: a host loop over nullspace_step_.
-    x0- and v-prediction chains and respaced chains are taken; a learned-variance chain in the DDIM form only.  Sample quality is untested."""
-    form = 0 if conditioning.eta is None else 1
+    make_eps_model for this very schedule): the whole loop in mi355_ddpm_nullspace_sample; any other callable: the host loop with the step kind
+    "nullspace".  x0- and v-prediction chains and respaced chains are taken; a learned-variance chain in the DDIM form only.  Sample quality is
+    untested."""
+    ns_form = 0 if conditioning.eta is None else 1
     sigma_y = float(conditioning.sigma_y)
-    if form == 1 and sigma_y > 0.0:
+    if ns_form == 1 and sigma_y > 0.0:
         raise ValueError("sigma_y > 0 (DDNM+) belongs to the ancestral form (eta=None): the DDIM form has no closed-form noise split here")
-    if getattr(ddpm, "x0_shaping", None) is not None:
+    if form.shaping is not None:
         raise NotImplementedError("x0 shaping (DDPM.with_x0_shaping) is not built for NullSpace: the rectification works on the statically clipped x0_hat")
-    if getattr(ddpm, "learned_variance", False) and form == 0:
+    if form.wide and ns_form == 0:
         raise NotImplementedError("a learned-variance chain (DDPM.with_learned_variance) is taken by NullSpace in the DDIM form only (eta=): its "
                                   "learned variance and DDNM+'s are not reconciled")
-    if _custom_times(ddpm) is not None:
+    if form.times is not None:
         raise NotImplementedError("NullSpace is not built for a chain with a time_scale (DDPM.from_betas(..., time_scale=))")
     for what in ("n_corrector", "guidance_scale", "order"):   # correctors, classifier-free guidance, multistep solvers: not parameters of NullSpace
         if getattr(conditioning, what, None):
             raise NotImplementedError(f"{what} is not built for NullSpace")
-    pred = _pred_of(ddpm)
-    wide = bool(getattr(ddpm, "learned_variance", False))
     lam, sig = ddpm.nullspace_coefs(sigma_y)
-    dsig = ddpm.ddim_sigma(float(conditioning.eta)) if form == 1 and float(conditioning.eta) != 0.0 else None
+    dsig = ddpm.ddim_sigma(float(conditioning.eta)) if ns_form == 1 and float(conditioning.eta) != 0.0 else None
+    step_sigma = sig if ns_form == 0 else dsig   # the draw's std per step; None: the deterministic DDIM form
     walk = repaint_walk(ddpm.Ns, conditioning.jump_length, conditioning.n_resample)
     if all(b < a for a, b in zip(walk, walk[1:])):
         walk = None
 
     @torch.no_grad()
     def sample(xT, condition, y=None):
-        global _draw_counter
-        T = _tables(ddpm)
         op = _nullspace_operator(likelihood, xT)
         condition = condition.to(xT.device).float().contiguous()
-        xi = xT.detach().clone().float().contiguous()
         engine = _fast_engine(eps_model, ddpm, xT)
         if engine is not None:
             out_channels = getattr(engine, "out_channels", None)
             if out_channels is not None:
-                _check_width(out_channels, xi, True if wide else None)
-            noise, seed = None, int(torch.initial_seed()) & ((1 << 63) - 1)
-            if _injected is not None:
-                noise = torch.stack([z.to(xi.device, torch.float32) for z in _injected]).contiguous()
-            else:
-                seed = (seed + 0x9E3779B97F4A7C15 * (_draw_counter + 1)) & ((1 << 63) - 1)
-                _draw_counter += 1
-            sched = {}
-            if getattr(ddpm, "timesteps", None) is not None or dsig is not None or walk is not None:
-                sched = dict(timesteps=getattr(ddpm, "timesteps", None) or tuple(range(ddpm.Ns)), train_steps=int(getattr(ddpm, "base_Ns", ddpm.Ns)),
-                             ddim_sigma=dsig, walk=walk)
-            engine.ddpm_nullspace(xi, T, condition, op, lam, sig if form == 0 else None, mode=_lib.DDIM if form else _lib.DDPM_PRIOR, prediction=pred,
-                                  labels=y, noise=noise, seed=seed, **sched)
+                _check_width(out_channels, xT, form.max_log)
+            xi, noise, seed, sched = _fused_operands(ddpm, xT, ddim_sigma=dsig, walk=walk)
+            engine.ddpm_nullspace(xi, _tables(ddpm), condition, op, lam, sig if ns_form == 0 else None, mode=_lib.DDIM if ns_form else _lib.DDPM_PRIOR,
+                                  prediction=form.pred, labels=y, noise=noise, seed=seed, **sched)
             return xi
         if y is not None:
             raise NotImplementedError("class labels run inside the fused loop: pass an eps_model built by make_eps_model(network, ddpm) for this "
                                       "schedule and device tensors (an arbitrary callable takes (x, i) alone)")
-        noise = _Noise(xi)
-        for level, down in _walk_moves(ddpm.Ns, walk):
-            if not down:   # q(x_level+1 | x_level): one draw
-                z, ph = noise.next()
-                _ops.renoise_(xi, z, float(T["alphas"][level].sqrt()), float(T["betas"][level].sqrt()), ph)
-                continue
-            i = level - 1
-            out = eps_model(xi, _times(xi, i)).float().contiguous()
-            _check_width(out.shape[1], xi, True if wide else None)
-            cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
-            if form == 0:
-                z, ph = noise.next() if i > 0 else (None, None)
-                _ops.nullspace_step_(op, 0, pred, xi, out, condition, cr, crm1, float(T["posterior_mean_coef1"][i]), float(T["posterior_mean_coef2"][i]),
-                                     lam=float(lam[i]), sigma=float(sig[i]), z=z, philox=ph, **_pred_kw(T, i))
-            else:
-                z, ph = noise.next() if (dsig is not None and i > 0) else (None, None)
-                _ops.nullspace_step_(op, 1, pred, xi, out, condition, cr, crm1, float(T["alphas_cumprod_prev"][i]), lam=float(lam[i]),
-                                     sigma=float(dsig[i]) if dsig is not None else 0.0, z=z, philox=ph, **_pred_kw(T, i))
-        return process_x0(xi)
+        return _run_host(eps_model, ddpm, xT, form, "nullspace",
+                         lambda i: (op, ns_form, condition, float(lam[i]), None if step_sigma is None else float(step_sigma[i])), walk=walk)
 
     return sample
 
 
-def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihood, walk=None, feature_cache=None, tiling=None):
+def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihood, form: _Form, walk=None):
     """sampling.py:209-260: overwrite the known pixels with the (noised) condition before each predictor step.
     walk (RePaint; None: the plain descent): the levels to visit, conditioning.repaint_walk; a move up re-noises the state by
     q(x_k | x_{k-1}) (mi355_renoise_step), a move down is the replacement step of its level.  A walk without upward moves is the plain descent."""
@@ -810,17 +777,31 @@ def _replacement_sample_fn(eps_model, ddpm, conditioning: Replacement, likelihoo
         condition = condition.to(xT.device).float().contiguous()
         pad = float(likelihood.pad_value)
         engine = _fast_engine(eps_model, ddpm, xT)
-        _need_fused(engine, feature_cache)
-        _need_fused_tiling(engine, tiling)
+        _need_fused(engine, form)
         if engine is not None:
             return _run_fast(engine, ddpm, xT, _lib.DDPM_REPLACEMENT, condition, n_corrector=conditioning.n_corrector,
                              delta=conditioning.delta, start_fraction=conditioning.start_fraction,
-                             noise_condition=conditioning.noise, pad_value=pad, walk=walk, feature_cache=feature_cache, tiling=tiling)
+                             noise_condition=conditioning.noise, pad_value=pad, walk=walk, feature_cache=form.feature_cache, tiling=form.tiling)
         rep = dict(condition=condition, start_fraction=conditioning.start_fraction, noise=bool(conditioning.noise), pad_value=pad)
-        return _run_generic(eps_model, ddpm, xT, amortized=False, cond_pred=None, cond_corr=None, replacement=rep,
-                            n_corrector=conditioning.n_corrector, delta=conditioning.delta, walk=walk)
+        return _run_host(eps_model, ddpm, xT, form, replacement=rep, n_corrector=conditioning.n_corrector, delta=conditioning.delta, walk=walk)
 
     return sample
+
+
+def _guided_condition(xT, condition, guidance_scale):
+    """The condition of a sample(xT, condition=None) call on the state's device; guidance needs one."""
+    if condition is not None:
+        condition = condition.to(xT.device).float().contiguous()
+    if guidance_scale is not None and condition is None:
+        raise ValueError("guidance_scale needs a condition to guide towards")
+    return condition
+
+
+def _guided_none(xT, condition, guidance_scale, likelihood):
+    """What a guided host loop evaluates beside the condition: likelihood.none_like, zeros without a likelihood (unguided: None)."""
+    if guidance_scale is None:
+        return None
+    return likelihood.none_like(xT) if likelihood is not None else torch.zeros_like(condition)
 
 
 def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Likelihood] = None, guidance_scale=None, order=2):
@@ -830,85 +811,22 @@ def get_dpm_solver_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Option
     prediction.  The coefficients are ddpm.dpm_solver_coefs(order); the second order pays on steps spaced evenly in logSNR:
     ddpm.respace(ddpm.logsnr_steps(K)).  guidance_scale (None: unguided): classifier-free guidance of eps against the none_like condition; needs
     a condition.  Fused path (eps_model built by make_eps_model for this very schedule): the whole loop in mi355_ddpm_multistep_sample; any other
-    callable: a host loop over dpmpp_step_ (guided: cfg_combine, then the step).  Sample quality is untested."""
-    _refuse_feature_cache(_cache_of(ddpm), "the DPM-Solver++ multistep loops")
-    _refuse_tiling(_tiling_of(ddpm), "the DPM-Solver++ multistep loops")
+    callable: the host loop with the step kind "dpmpp".  Sample quality is untested."""
+    _refuse("the DPM-Solver++ multistep loops", feature_cache=getattr(ddpm, "feature_cache", None), tiling=getattr(ddpm, "tiling", None))
     coefs = ddpm.dpm_solver_coefs(order)
     cx, c0, c1 = (c.tolist() for c in coefs)
-    shaping = _shaping_of(ddpm, guidance_scale is not None)
-    max_log = _learned_of(ddpm)   # a learned-variance chain: the solver reads the eps channels of the 2C output
-    pred = _pred_of(ddpm)
-    times = _custom_times(ddpm)
+    form = _chain_form(ddpm, guided=guidance_scale is not None)   # (a learned-variance chain: the solver reads the eps channels of the 2C output)
 
     @torch.no_grad()
     def sample(xT, condition=None):
-        T = _tables(ddpm)
         engine = _fast_engine(eps_model, ddpm, xT)
-        if condition is not None:
-            condition = condition.to(xT.device).float().contiguous()
-        if guidance_scale is not None and condition is None:
-            raise ValueError("guidance_scale needs a condition to guide towards")
-        xi = xT.detach().clone().float().contiguous()
+        condition = _guided_condition(xT, condition, guidance_scale)
         if engine is not None:
+            xi, _, _, sched = _fused_operands(ddpm, xT, draws=False)
             nv = _none_value(likelihood, xT) if likelihood is not None else 0.0
-            sched = {}
-            if getattr(ddpm, "timesteps", None) is not None:
-                sched = dict(timesteps=ddpm.timesteps, train_steps=int(ddpm.base_Ns))
-            if pred != "eps":
-                _check_engine_width(engine, xi, max_log)
-                return engine.ddpm_pred(xi, T, pred, shaping=shaping, max_log=max_log, times=times, mode=_lib.DDIM, coefs=coefs, cond=condition,
-                                        none_value=nv, guidance_scale=guidance_scale, **sched)
-            if max_log is not None or times is not None:
-                if shaping is not None:
-                    raise NotImplementedError("x0_shaping is not built for a chain with a time_scale (DDPM.from_betas(..., time_scale=))")
-                _check_engine_width(engine, xi, max_log)
-                return engine.ddpm_learned(xi, T, max_log, times=times, mode=_lib.DDIM, coefs=coefs, cond=condition, none_value=nv,
-                                           guidance_scale=guidance_scale, **sched)
-            if shaping is not None:
-                return engine.ddpm_shaped(xi, T, shaping, mode=_lib.DDIM, coefs=coefs, cond=condition, none_value=nv, guidance_scale=guidance_scale,
-                                          **sched)
-            return engine.ddpm_multistep(xi, T, coefs, cond=condition, none_value=nv, guidance_scale=guidance_scale, **sched)
-        none = None
-        if guidance_scale is not None:
-            none = likelihood.none_like(xT) if likelihood is not None else torch.zeros_like(condition)
-        hist = torch.empty_like(xi)
-        for i in reversed(range(ddpm.Ns)):
-            eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i)).float().contiguous()
-            shape = None
-            _check_width(eps.shape[1], xi, max_log, host_loop=True)
-            cr, crm1 = float(T["sqrt_recip_alphas_cumprod"][i]), float(T["sqrt_recipm1_alphas_cumprod"][i])
-            if pred != "eps":   # the raw output of an x0- or v-prediction net, passed whole (guided: the pair, on the duplicated state)
-                if none is None:
-                    _ops.pred_step_("dpmpp", pred, xi, eps, cr, crm1, cx[i], c0[i], c1[i], hist=hist,
-                                    shape=_shape_rows(xi, eps, i, T, shaping, pred=pred), **_pred_kw(T, i))
-                    continue
-                eps2 = torch.cat((eps, eps_model(_net_in(xi, none, True), _times(xi, i)).float())).contiguous()
-                x2 = torch.cat((xi, xi))
-                _ops.pred_step_("dpmpp", pred, x2, eps2, cr, crm1, cx[i], c0[i], c1[i], hist=hist, w=guidance_scale,
-                                shape=_shape_rows(xi, eps2, i, T, shaping, w=guidance_scale, pred=pred), **_pred_kw(T, i))
-                xi.copy_(x2[:xi.shape[0]])
-                continue
-            if max_log is not None:   # the 2C output, passed whole (guided: the pair, on the duplicated state)
-                if none is None:
-                    _ops.strided_step_("dpmpp", xi, eps, cr, crm1, cx[i], c0[i], c1[i], hist=hist)
-                    continue
-                eps2 = torch.cat((eps, eps_model(_net_in(xi, none, True), _times(xi, i)).float())).contiguous()
-                x2 = torch.cat((xi, xi))
-                _ops.strided_step_("dpmpp", x2, eps2, cr, crm1, cx[i], c0[i], c1[i], hist=hist, w=guidance_scale)
-                xi.copy_(x2[:xi.shape[0]])
-                continue
-            if none is not None:
-                eu = eps_model(_net_in(xi, none, True), _times(xi, i)).float()
-                eps2 = torch.cat((eps, eu)).contiguous()
-                shape = _shape_rows(xi, eps2, i, T, shaping, w=guidance_scale)
-                eps = _ops.cfg_combine(eps2, guidance_scale)
-            else:
-                shape = _shape_rows(xi, eps, i, T, shaping)
-            if shape is not None:
-                _ops.x0_shaped_step_("dpmpp", xi, eps, shape, cr, crm1, cx[i], c0[i], c1[i], hist=hist)
-            else:
-                _ops.dpmpp_step_(xi, eps, hist, cr, crm1, cx[i], c0[i], c1[i])
-        return process_x0(xi)
+            return _fused_call(engine, ddpm, xi, form, dict(cond=condition, none_value=nv, guidance_scale=guidance_scale, **sched), coefs)
+        return _run_host(eps_model, ddpm, xT, form, "dpmpp", lambda i: (cx[i], c0[i], c1[i]), cond=condition, concat=condition is not None,
+                         none=_guided_none(xT, condition, guidance_scale, likelihood), w=guidance_scale)
 
     return sample
 
@@ -919,44 +837,26 @@ def get_ddim_sample_fn(eps_model: Callable, ddpm: DDPM, likelihood: Optional[Lik
     guidance_scale (None: unguided): classifier-free guidance of eps against the none_like condition; needs a condition.
     eta (0: the deterministic sampler, untouched): stochastic DDIM with sigma = ddpm.ddim_sigma(eta), one noise draw per step with i > 0;
     eta = 1 has the ancestral step's mean and variance.  On a RespacedDDPM this is DDIM on a sub-sequence of the training steps.
-    On a chain that carries a Tiling (ddpm.with_tiling(Tiling(...))) xT (and the condition) are canvases.  Not with guidance_scale."""
-    tiling = _tiling_of(ddpm)
+    On a chain that carries a Tiling (ddpm.with_tiling(Tiling(...))) xT (and the condition) are canvases, on one that carries a FeatureCache
+    the features are reused across the steps (both the fused path only).  Not with guidance_scale."""
     if guidance_scale is not None:
-        _refuse_tiling(tiling, "the guided (classifier-free guidance) loops")
-    feature_cache = _cache_of(ddpm)   # DDPM.with_feature_cache: feature reuse across the steps (the fused path only; not under guidance)
-    if guidance_scale is not None:
-        _refuse_feature_cache(feature_cache, "the guided (classifier-free guidance) loops")
+        _refuse("the guided (classifier-free guidance) loops", tiling=getattr(ddpm, "tiling", None), feature_cache=getattr(ddpm, "feature_cache", None))
     eta = float(eta)
     if not (math.isfinite(eta) and eta >= 0.0):
         raise ValueError(f"eta must be finite and >= 0, got {eta!r}")
     sigma = ddpm.ddim_sigma(eta) if eta != 0.0 else None
-    shaping = _shaping_of(ddpm, guidance_scale is not None)
-    max_log = _learned_of(ddpm, tiling=tiling, feature_cache=feature_cache)
-    pred = _pred_of(ddpm, tiling=tiling, feature_cache=feature_cache)
+    form = _chain_form(ddpm, guided=guidance_scale is not None)
 
     @torch.no_grad()
     def sample(xT, condition=None):
-        T = _tables(ddpm)
         engine = _fast_engine(eps_model, ddpm, xT)
-        if condition is not None:
-            condition = condition.to(xT.device).float().contiguous()
-        if guidance_scale is not None and condition is None:
-            raise ValueError("guidance_scale needs a condition to guide towards")
-        _need_fused(engine, feature_cache)
-        _need_fused_tiling(engine, tiling)
+        condition = _guided_condition(xT, condition, guidance_scale)
+        _need_fused(engine, form)
         if engine is not None:
             nv = _none_value(likelihood, xT) if likelihood is not None else 0.0
-            return _run_fast(engine, ddpm, xT, _lib.DDIM, condition, none_value=nv, guidance_scale=guidance_scale, ddim_sigma=sigma,
-                             feature_cache=feature_cache, tiling=tiling)
-        if guidance_scale is not None:
-            none = likelihood.none_like(xT) if likelihood is not None else torch.zeros_like(condition)
-            return _run_generic_cfg(eps_model, ddpm, xT, cond=condition, none=none, guidance_scale=guidance_scale, ddim=True, ddim_sigma=sigma)
-        xi = xT.detach().clone().float().contiguous()
-        noise = _Noise(xi) if sigma is not None else None
-        for i in reversed(range(ddpm.Ns)):
-            eps = eps_model(_net_in(xi, condition, condition is not None), _times(xi, i)).float().contiguous()
-            _check_width(eps.shape[1], xi, max_log, host_loop=True)
-            _ddim_move(eps, xi, i, T, sigma, noise, _shape_rows(xi, eps, i, T, shaping, pred=pred), wide=max_log is not None, pred=pred)
-        return process_x0(xi)
+            return _run_fast(engine, ddpm, xT, _lib.DDIM, condition, none_value=nv, guidance_scale=guidance_scale, ddim_sigma=sigma, feature_cache=form.feature_cache, tiling=form.tiling)
+        kind, step_args = ("ddim", lambda i: ()) if sigma is None else ("ddim_eta", lambda i: (float(sigma[i]),))
+        return _run_host(eps_model, ddpm, xT, form, kind, step_args, cond=condition, concat=condition is not None,
+                         none=_guided_none(xT, condition, guidance_scale, likelihood), w=guidance_scale)
 
     return sample

@@ -13,9 +13,11 @@ and compare the files.  --save keeps the tensors themselves, for a max-abs compa
 --cases forward adds (or, alone, selects) the digest of single forwards, on the smallest nets and batches at which each decision of the
 executor (csrc/unet_engine.hip: unet_resolve) goes either way: per case the SHA-256 of the output, the launch count, every field of every
 profile() record except ms, and for every conv output tensor whether read_tensor refuses it and why (0 readable, 1 never written, 2
-normalised in place).  --cases attention: one line per call of the three attention ops (qkv_attention, attn_block_fused,
-qkv_attention_vjp) on the shapes at which each of the five attention kernels takes another path.  --inventory needs no GPU: the parameter
-inventory (names, shapes, order) and the weight-image bytes of the same nets.
+normalised in place).  --cases hostloop: the Python samplers of image_diffusion/sampling.py on an untagged eps_model (the host loops over
+the step ops), one line per (sampler, chain form, noise source), and ReconstructionGuidance in its three modes and both update rules.
+--cases attention: one line per call of the three attention ops (qkv_attention, attn_block_fused, qkv_attention_vjp) on the shapes at which
+each of the five attention kernels takes another path.  --inventory needs no GPU: the parameter inventory (names, shapes, order) and the
+weight-image bytes of the same nets.
 """
 import argparse
 import ctypes as C
@@ -318,6 +320,105 @@ def run(prec):
     case(prec, "vlb_fixed_sliced", l3, dict(zip(ts_, sliced(l3, 2, lambda: l3.ddpm_vlb(xd, R, fixed, learned=False, y=y, cdf="tanh", seed=55)))))
 
 
+# ---- the Python samplers' host loops (image_diffusion/sampling.py) on an untagged eps_model ----------------------------------------------
+def run_hostloop(prec):
+    """One line per (sampler, chain form, noise source): the result of sample() with an untagged `lambda xi, i: fast(xi, i)` around an
+    engine-backed model - the host loop over the step ops - on a 4-step respacing; a refused pair (NotImplementedError, ValueError) prints the exception's type and message; any other
+    exception ends the run.
+    ReconstructionGuidance (three likelihoods, both update rules) takes the tagged model, as it must.  Every case starts from a fresh
+    _draw_counter / _noise_offset and the same torch.manual_seed."""
+    from image_diffusion import sampling
+    from image_diffusion.conditioning import Amortized, ClassifierFreeGuidance, NullSpace, ReconstructionGuidance, RePaint, Replacement
+    from image_diffusion.likelihoods import AveragePooling, HyperResolution, InPainting, LowResolution
+    from image_diffusion.sde_diffusion import linear_betas
+
+    def model(in_ch, out_ch, seed):
+        kw = dict(image_size=S, in_channels=in_ch, model_channels=32, out_channels=out_ch, num_res_blocks=1, attention_resolutions=(2,),
+                  channel_mult=(1, 2), num_heads=2, precision=prec)
+        m = UNetModel(**kw)
+        m.load_state_dict(synth_state_dict(param_shapes(UNetModel(**kw)), 7000 + seed))
+        return m.to(DEV)
+
+    nets = {(3, 3): model(3, 3, 0), (6, 3): model(6, 3, 1), (3, 6): model(3, 6, 5), (6, 6): model(6, 6, 6)}
+    base = DDPM(NS).respace(4)
+    scaled = DDPM.from_betas(linear_betas(NS), time_scale=float(NS)).respace(4)
+    chains = {
+        "plain": base, "shaped_q": base.with_x0_shaping(dynamic_threshold=0.9),
+        "shaped_q_rescale": base.with_x0_shaping(dynamic_threshold=0.9, guidance_rescale=0.7), "learned": base.with_learned_variance(),
+        "x0": base.with_prediction("x0"), "v": base.with_prediction("v"), "v_learned": base.with_prediction("v").with_learned_variance(),
+        "v_shaped": base.with_prediction("v").with_x0_shaping(dynamic_threshold=0.9), "time_scale": scaled,
+    }
+    xT = randn(7201, B, 3, S, S).to(DEV)
+    cond = (randn(7102, B, 3, S, S) * 0.5).clamp(-1, 1).to(DEV)
+    cond[:, :, 4:10, 5:11] = -2.0
+    ylow = (randn(7103, B, 3, 4, 4) * 0.5).to(DEV)
+    draws = [randn(7210 + j, B, 3, S, S).to(DEV) for j in range(40)]
+    wv = torch.tensor([0.5, 2.0, 3.5], device=DEV)
+    lik, pool = InPainting(patch_size=6, pad_value=-2.0), AveragePooling(4)
+    cnd = lambda c, k, **kw: (lambda e, d: sampling.get_conditional_sample_fn(e, d, c, k, **kw))   # noqa: E731
+    with_cond, alone = (lambda s: s(xT, cond)), (lambda s: s(xT))
+    # name -> (net input channels, factory(eps_model, chain), call(sample))
+    samplers = {
+        "prior_unconditional": (3, lambda e, d: sampling.get_prior_sample_fn(e, d, Replacement(0.1, 1.0, True, 0), lik), alone),
+        "prior_amortized": (6, lambda e, d: sampling.get_prior_sample_fn(e, d, Amortized(0.1, 0, 0.1), lik), alone),
+        "amortized": (6, cnd(Amortized(0.1, 0, 0.1), lik), with_cond),
+        "amortized_corrector": (6, cnd(Amortized(0.1, 1, 0.25), lik), with_cond),
+        "replacement_noisy": (3, cnd(Replacement(0.1, 0.6, True, 0), lik), with_cond),
+        "replacement_clean_corrector": (3, cnd(Replacement(0.2, 0.6, False, 1), lik), with_cond),
+        "repaint_walk": (3, cnd(RePaint(0.1, 0.6, True, 0, 1, 2), lik), with_cond),
+        "cfg_float_corrector": (6, cnd(ClassifierFreeGuidance(0.1, 1, 0.1, 2.0), lik), with_cond),
+        "ddim_eta0": (3, lambda e, d: sampling.get_ddim_sample_fn(e, d, lik), alone),
+        "ddim_eta05": (3, lambda e, d: sampling.get_ddim_sample_fn(e, d, None, eta=0.5), alone),
+        "ddim_eta0_guided": (6, lambda e, d: sampling.get_ddim_sample_fn(e, d, lik, guidance_scale=2.0), with_cond),
+        "ddim_eta05_guided_tensor_w": (6, lambda e, d: sampling.get_ddim_sample_fn(e, d, None, guidance_scale=wv, eta=0.5), with_cond),
+        "dpm1": (3, lambda e, d: sampling.get_dpm_solver_sample_fn(e, d, None, order=1), alone),
+        "dpm2_condition": (6, lambda e, d: sampling.get_dpm_solver_sample_fn(e, d, lik, order=2), with_cond),
+        "dpm1_guided_likelihood": (6, lambda e, d: sampling.get_dpm_solver_sample_fn(e, d, lik, guidance_scale=2.0, order=1), with_cond),
+        "dpm2_guided": (6, lambda e, d: sampling.get_dpm_solver_sample_fn(e, d, None, guidance_scale=wv, order=2), with_cond),
+        "nullspace_ancestral": (3, cnd(NullSpace(0.0, None, 1, 1), lik), with_cond),
+        "nullspace_ancestral_plus_walk": (3, cnd(NullSpace(0.3, None, 1, 2), lik), with_cond),
+        "nullspace_ddim_eta0": (3, cnd(NullSpace(0.0, 0.0, 1, 1), lik), with_cond),
+        "nullspace_ddim_eta05_walk_pool": (3, cnd(NullSpace(0.0, 0.5, 1, 2), pool), lambda s: s(xT, pool.sample(cond))),
+    }
+    recon = {}
+    for rule in ("before", "after"):
+        recon[f"recon_painting_{rule}"] = (cnd(ReconstructionGuidance(0.5, 0.6, rule, 1, 0.1), lik), with_cond)
+        recon[f"recon_hyper_{rule}"] = (cnd(ReconstructionGuidance(0.5, 0.6, rule, 0, 0.1), HyperResolution(4, 4)), with_cond)
+        recon[f"recon_lowres_{rule}"] = (cnd(ReconstructionGuidance(0.5, 0.6, rule, 0, 0.1), LowResolution(4, 4)), lambda s: s(xT, ylow))
+
+    def one(name, cname, nname, factory, call, eps_model, chain):
+        sampling._draw_counter, sampling._noise_offset = 0, 0
+        torch.manual_seed(1234)
+        try:
+            sample = factory(eps_model, chain)
+            if nname == "injected":
+                with sampling.injected_noise(draws):
+                    x = call(sample)
+            else:
+                x = call(sample)
+        except (NotImplementedError, ValueError) as e:   # the refusals raised on purpose; anything else (the backend, the device) ends the run
+            emit(f"{prec} hostloop {name} {cname} {nname} refused {type(e).__name__} {str(e)!r}")
+            return
+        torch.cuda.synchronize()
+        if MARK[0]:
+            torch.arange(4, device=DEV).flip(0)
+        t = x.detach().cpu().contiguous()
+        KEPT[f"{prec}/hostloop/{name}/{cname}/{nname}"] = t
+        emit(f"{prec} hostloop {name} {cname} {nname} {tuple(t.shape)} sha256={hashlib.sha256(t.numpy().tobytes()).hexdigest()} "
+             f"draws={sampling._draw_counter} offset={sampling._noise_offset}")
+
+    for cname, chain in chains.items():
+        out_ch = 6 if chain.learned_variance else 3
+        for name, (in_ch, factory, call) in samplers.items():
+            fast = sampling.make_eps_model(nets[(in_ch, out_ch)], chain)
+            generic = lambda xi, i, fast=fast: fast(xi, i)   # noqa: E731  (untagged: the host loop over the step ops)
+            for nname in ("injected", "philox"):
+                one(name, cname, nname, factory, call, generic, chain)
+    for name, (factory, call) in recon.items():   # (every other chain form is refused at the factory: the CPU transcripts hold those rows)
+        for nname in ("injected", "philox"):
+            one(name, "plain", nname, factory, call, sampling.make_eps_model(nets[(3, 3)], base), base)
+
+
 # ---- single forwards --------------------------------------------------------------------------------------------------------------------
 CIFAR = dict(image_size=32, in_channels=3, model_channels=128, out_channels=3, num_res_blocks=2, attention_resolutions=(2,),
              channel_mult=(1, 2, 2, 2), num_heads=4, num_head_channels=64)
@@ -508,7 +609,8 @@ def main():
     ap.add_argument("--save", help="keep every output tensor in this torch file")
     ap.add_argument("--mark", action="store_true", help="one torch.flip launch behind every case: the cut marks of a kernel trace")
     ap.add_argument("--precisions", default="fp32,bf16")
-    ap.add_argument("--cases", default="sampler", help="comma list of: sampler (the loops), forward (single forwards), attention (the attention ops; once, not per precision)")
+    ap.add_argument("--cases", default="sampler", help="comma list of: sampler (the loops), forward (single forwards), hostloop (the Python samplers on an untagged eps_model), "
+                    "attention (the attention ops; once, not per precision)")
     ap.add_argument("--inventory", action="store_true", help="no GPU: parameter inventories and weight-image bytes of the forward nets only")
     a = ap.parse_args()
     MARK[0] = a.mark
@@ -520,6 +622,8 @@ def main():
             run(prec)
         if "forward" in a.cases.split(","):
             run_forward(prec)
+        if "hostloop" in a.cases.split(","):
+            run_hostloop(prec)
     if not a.inventory and "attention" in a.cases.split(","):
         run_attention()
     if a.out:
